@@ -12,7 +12,12 @@ stack (weak scaling, no data-path collective).
 itself (one child process per GPU, RCCL rendezvous on 127.0.0.1); under
 `torch.distributed.run` it is one of the ranks.  The launching parent never touches the GPU.
 
-Prints ONE JSON line on rank 0.  Besides the contract's fields it carries
+A plain run sets up, warms up, times `--steps` stacks and prints the headline line (with
+`--dump-outputs DIR`: also the last timed stack's results, see `dump_outputs`).  Everything
+else -- the correctness guard, per-kernel HIP-event timing and rooflines, the CPU oracle and
+the sub-records below -- runs only with `--full`.
+
+Prints ONE JSON line on rank 0.  With `--full`, besides the contract's fields it carries
   parity            device vs CPU oracle on the first days of the benchmarked stack itself,
   exact_torus_mode  the same stack with exact reference-torus results ('auto' mode),
   real_wind         BASELINE config 3a/3b: Carnarvon wind, R=2048, 30 days, device chain rate,
@@ -175,14 +180,22 @@ def parse(argv=None):
     ap.add_argument('--kshape', type=int, default=2049)
     ap.add_argument('--ndays', type=int, default=30)
     ap.add_argument('--mode', default='fast', choices=['fast', 'exact', 'fold', 'auto'])
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also the correctness guard, per-kernel timing and rooflines, the CPU oracle '
+                         'baseline and parity, and the sub-records (off: headline figure only)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write the results of the last timed stack to DIR/*.npy (float64)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU oracle')
     ap.add_argument('--cpu-days', type=int, default=6)   # ~10 s of one host core
     ap.add_argument('--no-extras', action='store_true',
-                    help='skip the exact_torus_mode / real_wind / bayes sub-records')
+                    help='with --full: skip the exact_torus_mode / real_wind / bayes sub-records')
     ap.add_argument('--rehearse', action='store_true',
                     help='launcher/rendezvous rehearsal without device work (CPU test of the N>1 '
                          'control flow with BENCH_BACKEND=gloo); prints value null')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
 
 
 # --------------------------------------------------------------------------- launcher
@@ -302,6 +315,38 @@ def max_abs_vs(solver, fields):
     return float(max(np.abs(solver.dense(0, d) - f).max() for d, f in enumerate(fields)))
 
 
+DUMP_CELLS = 98304       # per half of the sample: 30 days x 2 x 98304 float64 = 47 MB
+
+
+def dump_cells(N):
+    """-> (rows, cols) int32: the fixed cells `dump_outputs` samples on an N x N domain"""
+    rng = np.random.default_rng(20240613)
+    near = np.clip(np.rint(rng.normal(N // 2, N / 16.0, (2, DUMP_CELLS))), 0, N - 1)
+    rows = np.concatenate([rng.integers(0, N, DUMP_CELLS), near[0]]).astype(np.int32)
+    cols = np.concatenate([rng.integers(0, N, DUMP_CELLS), near[1]]).astype(np.int32)
+    return rows, cols
+
+
+def dump_outputs(out_dir, solver, nd, negval=1e-8):
+    """What a caller of the timed chain receives for its last stack, as float64 .npy files:
+      day_stats    [nd, 5]  per day: nnz, sum, delta, padmax, flag (`chain_stats`)
+      day_samples  [nd, n]  the thresholded, renormalised day solutions (`chain_solution`) at a fixed
+                            sample of cells: half uniform over the domain, half normal around its centre
+                            (where the mass is), drawn from a fixed seed -- the same cells on every run.
+    A dense day is 134 MB at the headline size, so the fields are sampled on the device (`gather_multi`)."""
+    from parasitoids_amd import _lib
+    os.makedirs(out_dir, exist_ok=True)
+    stats = solver.chain_stats(0, nd)
+    rows, cols = dump_cells(solver.dom_len)
+    vals = solver.gather_multi([_lib.REC_CHAIN] * nd, list(range(nd)), rows, cols, scale=1.0, negval=negval)
+    delta = np.array([st.delta for st in stats])
+    # chain_solution's entries: (v + delta) where v >= negval (gather_multi gives v there, 0 elsewhere)
+    sol = np.where(vals != 0.0, vals + delta[:, None], 0.0)
+    np.save(os.path.join(out_dir, 'day_stats.npy'),
+            np.array([[st.nnz, st.sum, st.delta, st.padmax, st.flag] for st in stats], dtype=np.float64))
+    np.save(os.path.join(out_dir, 'day_samples.npy'), sol.astype(np.float64))
+
+
 # --------------------------------------------------------------------------- main
 def main():
     args = parse()
@@ -387,8 +432,8 @@ def main():
         dist.barrier() if world > 1 else None
         dt, per = gather_times(1.0 + 0.0 * rank)
         idents = rank_identities()
-        mg = None
-        if world > 1:
+        mg = par = None
+        if world > 1 and args.full:
             import bench_extras
             mg = bench_extras.multi_gpu_record(rank, world, rehearse=True,       # configs 4 / 5 control flow, stand-in work
                                                fail_stage=os.environ.get('BENCH_FAIL_STAGE'))
@@ -399,7 +444,7 @@ def main():
                               'steps': args.steps, 'warmup': args.warmup, 'rehearsal': True,
                               'ranks_seen': len(per), 'backend': backend,
                               'world_size': dist.get_world_size() if world > 1 else 1, 'ranks': idents,
-                              'multi_gpu': mg, 'parity': {'per_rank_max_abs': par} if world > 1 else None}))
+                              'multi_gpu': mg, 'parity': {'per_rank_max_abs': par} if par else None}))
         if world > 1:
             dist.barrier()
             dist.destroy_process_group()
@@ -424,45 +469,49 @@ def main():
     for _ in range(args.warmup):
         step()
     fence()
-    # correctness guard outside the timed region: mass conserved, moments add up
-    stats = solver.chain_stats(0, nd)
-    raw = solver.dense(0, nd - 1)                 # unthresholded last-day field
-    idx = np.arange(N, dtype=np.float64)
-    s = raw.sum()
-    rowm = raw.sum(1)
-    mr = (rowm * idx).sum() / s
-    vr = (rowm * (idx - mr) ** 2).sum() / s
-    exp_mr = R + sum(synthetic.moments(k)[1] - K // 2 for k in kernels)
-    exp_vr = sum(synthetic.moments(k)[3] for k in kernels)
-    check = os.environ.get('BENCH_SKIP_CHECK') is None    # kernel-timing experiments with stubbed phases only
-    flagged = any(st.flag for st in stats)
-    if check:
-        assert s < 1.0 + 1e-9 and abs(stats[-1].sum + stats[-1].delta * stats[-1].nnz - 1.0) < 1e-12
-        # Mass can leave the domain without raising the flag (many pad cells below 1e-8 each);
-        # when it all stayed inside, mean and variance must add up exactly
-        if not flagged and abs(s - 1.0) < 1e-9:
-            assert abs(mr - exp_mr) < 1e-6 and abs(vr / exp_vr - 1) < 1e-7, (mr, exp_mr, vr, exp_vr)
-        elif (R, K, nd) == (2048, 2049, 30):
-            raise AssertionError('headline stack lost mass: sum %r flagged %r' % (s, flagged))
-    del raw
+    if args.full:
+        # correctness guard outside the timed region: mass conserved, moments add up
+        stats = solver.chain_stats(0, nd)
+        raw = solver.dense(0, nd - 1)                 # unthresholded last-day field
+        idx = np.arange(N, dtype=np.float64)
+        s = raw.sum()
+        rowm = raw.sum(1)
+        mr = (rowm * idx).sum() / s
+        vr = (rowm * (idx - mr) ** 2).sum() / s
+        exp_mr = R + sum(synthetic.moments(k)[1] - K // 2 for k in kernels)
+        exp_vr = sum(synthetic.moments(k)[3] for k in kernels)
+        check = os.environ.get('BENCH_SKIP_CHECK') is None    # kernel-timing experiments with stubbed phases only
+        flagged = any(st.flag for st in stats)
+        if check:
+            assert s < 1.0 + 1e-9 and abs(stats[-1].sum + stats[-1].delta * stats[-1].nnz - 1.0) < 1e-12
+            # Mass can leave the domain without raising the flag (many pad cells below 1e-8 each);
+            # when it all stayed inside, mean and variance must add up exactly
+            if not flagged and abs(s - 1.0) < 1e-9:
+                assert abs(mr - exp_mr) < 1e-6 and abs(vr / exp_vr - 1) < 1e-7, (mr, exp_mr, vr, exp_vr)
+            elif (R, K, nd) == (2048, 2049, 30):
+                raise AssertionError('headline stack lost mass: sum %r flagged %r' % (s, flagged))
+        del raw
 
-    # HIP events bracket every PROF_EVERY-th launch of each kernel class inside the timed
-    # region (bracketing all ~250 launches per stack costs ~9 % of the throughput)
-    solver.prof_enable(os.environ.get('BENCH_NO_PROF') is None, every=PROF_EVERY)
-    fence()
+        # HIP events bracket every PROF_EVERY-th launch of each kernel class inside the timed
+        # region (bracketing all ~250 launches per stack costs ~9 % of the throughput)
+        solver.prof_enable(os.environ.get('BENCH_NO_PROF') is None, every=PROF_EVERY)
+        fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     fence()
     dt_own = time.perf_counter() - t0
-    prof = solver.prof_read()
-    prof_days = solver.prof_days()
-    prof_launches = solver.prof_launches()
-    solver.prof_enable(False)
+    if args.full:
+        prof = solver.prof_read()
+        prof_days = solver.prof_days()
+        prof_launches = solver.prof_launches()
+        solver.prof_enable(False)
     dt, per_rank = gather_times(dt_own)
     idents = rank_identities()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, solver, nd)
     rank_parity = None
-    if world > 1 and not args.no_cpu_baseline:
+    if args.full and world > 1 and not args.no_cpu_baseline:
         # every rank checks ITS stack against the oracle (2 day steps, ~5 s of one host core each)
         _, of = cpu_baseline(state, kernels, K, 2)
         rank_parity = gather_parity(max_abs_vs(solver, of))
@@ -472,6 +521,25 @@ def main():
         nranks = dist.get_world_size() if world > 1 else 1
         grid_days = nranks * args.steps * nd
         value = grid_days / dt
+        out = {
+            'metric': 'grid-days/sec on 4096^2 fp64 domain',
+            'value': round(value, 3),
+            'unit': 'grid-days/s',
+            'n_gpus': nranks, 'steps': args.steps, 'warmup': args.warmup,
+            'ms_per_step': round(dt / args.steps * 1e3, 3),
+            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+            'dtype': 'f64', 'data': 'synthetic',
+            'config': {'workload': 'C3 synthetic stack: N=%d (nominal %d^2), %d Gaussian day kernels '
+                                   'K=%d, reference torus P=%d, FFT size %d (%s mode), prob model, '
+                                   'one replica stack per GPU' % (N, 2 * R, nd, K, P, solver.fft_len,
+                                                                  args.mode),
+                       'dom_len': N, 'ndays': nd, 'kshape': K, 'P': P, 'fft_len': solver.fft_len,
+                       'kernels_direct': bool(solver.kernels_direct), 'full_column_pipeline': bool(solver.full_column)},
+            'per_rank_grid_days_per_s': [round(args.steps * nd / t, 2) for t in per_rank],
+            'world_size': nranks, 'backend': backend if world > 1 else None, 'ranks': idents,
+            'distinct_devices': len(set((i.get('uuid'), i.get('pci_bus_id'), i.get('local_device')) for i in idents)),
+        }
+    if rank == 0 and args.full:
         kern = {}
         model_p2 = dict(MODEL_P2)
         days_of = dict(DAYS_PER_LAUNCH)
@@ -514,23 +582,7 @@ def main():
                   * (1 if k in days_of else PROF_EVERY))
         ach = kern[dom].get('hbm_GBps')
         traffic, traffic_src = pmc_traffic(dom) if (R, K, nd) == (2048, 2049, 30) else (None, None)
-        out = {
-            'metric': 'grid-days/sec on 4096^2 fp64 domain',
-            'value': round(value, 3),
-            'unit': 'grid-days/s',
-            'n_gpus': nranks, 'steps': args.steps, 'warmup': args.warmup,
-            'ms_per_step': round(dt / args.steps * 1e3, 3),
-            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-            'dtype': 'f64', 'data': 'synthetic',
-            'config': {'workload': 'C3 synthetic stack: N=%d (nominal %d^2), %d Gaussian day kernels '
-                                   'K=%d, reference torus P=%d, FFT size %d (%s mode), prob model, '
-                                   'one replica stack per GPU' % (N, 2 * R, nd, K, P, solver.fft_len,
-                                                                  args.mode),
-                       'dom_len': N, 'ndays': nd, 'kshape': K, 'P': P, 'fft_len': solver.fft_len,
-                       'kernels_direct': bool(solver.kernels_direct), 'full_column_pipeline': bool(solver.full_column)},
-            'per_rank_grid_days_per_s': [round(args.steps * nd / t, 2) for t in per_rank],
-            'world_size': nranks, 'backend': backend if world > 1 else None, 'ranks': idents,
-            'distinct_devices': len(set((i.get('uuid'), i.get('pci_bus_id'), i.get('local_device')) for i in idents)),
+        out.update({
             # SURVEY 8d's normative whole-chain figure: the unfused model's 96 P^2 per grid-day
             # times the measured rate.  A model rate, not a bandwidth measurement.
             'alg_bytes_per_grid_day': 96.0 * P * P,
@@ -563,7 +615,7 @@ def main():
                                                  'same_library': pmc_traffic.provenance.get('lib_sha256') == lib_sha256()}
                                                 if (traffic_src and pmc_traffic.provenance) else None)},
             'kernels': kern,
-        }
+        })
         # Whole-chain roofline: the compulsory bytes of the stack as launched / the
         # measured step time, next to the PMC bytes of one stack.  SURVEY 8d's 96 P^2 model above
         # (`alg_*`, `survey_model_*`) is superseded for this code: fusion keeps the state column in LDS
@@ -644,7 +696,7 @@ def main():
                 except Exception as e:          # a sub-record must not cost the headline line
                     out[key] = {'error': '%s: %s' % (type(e).__name__, e)}
     mg = None
-    if world > 1 and not args.no_extras and (R, K, nd) == (2048, 2049, 30):
+    if args.full and world > 1 and not args.no_extras and (R, K, nd) == (2048, 2049, 30):
         # configs 4 and 5 over the ranks of this job (every rank takes part in the gathers)
         solver.close()
         import bench_extras

@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 pass() {  # name counters...
   local name=$1; shift
   BENCH_NO_PROF=1 rocprofv3 --kernel-trace --pmc "$@" -d "$out/$name" -o pmc --output-format csv -- \
-    python3 "$root/bench.py" --steps 3 --warmup 2 --no-extras --no-cpu-baseline > "$out/$name.log" 2>&1 || tail -3 "$out/$name.log"
+    python3 "$root/bench.py" --full --steps 3 --warmup 2 --no-extras --no-cpu-baseline > "$out/$name.log" 2>&1 || tail -3 "$out/$name.log"
   python3 "$root/scripts/pmc_summary.py" "$out/$name" | grep -E "k_colfull_dual|k_row_inv_rs2|k_row_fwd_rs" > "$out/$name.txt" || true
   cat "$out/$name.txt"
 }

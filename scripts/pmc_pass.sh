@@ -9,5 +9,5 @@ out=$root/gpurun_out/pmc_$tag
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
 BENCH_NO_PROF=1 rocprofv3 --kernel-trace --pmc "$@" -d "$out" -o pmc --output-format csv -- \
-  python3 "$root/bench.py" --steps 1 --warmup 1 --no-cpu-baseline > "$out/bench.log" 2>&1
+  python3 "$root/bench.py" --full --steps 1 --warmup 1 --no-cpu-baseline > "$out/bench.log" 2>&1
 python3 "$root/scripts/pmc_summary.py" "$out" | tee "$out/summary.txt"

@@ -15,7 +15,7 @@ for L in SIZES:
     K = 2 * (L - N) + 1
     for tp in ('0', '1'):
         env = dict(os.environ, PS_TPIPE=tp)
-        p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--no-extras', '--no-cpu-baseline',
+        p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--no-extras', '--no-cpu-baseline',
                             '--rad-res', str(R), '--kshape', str(K), '--steps', '3', '--warmup', '1'],
                            env=env, capture_output=True, text=True)
         if p.returncode != 0:

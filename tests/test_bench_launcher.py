@@ -18,7 +18,7 @@ def _run(script, *argv, env=None):
 
 
 def test_bench_gpus2_launches_two_ranks():
-    p = _run('bench.py', '--gpus', '2', '--rehearse')
+    p = _run('bench.py', '--gpus', '2', '--rehearse', '--full')
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1                      # rank 0 only
@@ -35,6 +35,22 @@ def test_bench_gpus2_launches_two_ranks():
     assert abs(by['value'] - sum(by['per_rank_samples_per_hour'])) < 1.0
     assert by['per_rank_samples_per_hour'][1] - by['per_rank_samples_per_hour'][0] == 1.0   # each rank ran its own seed
     assert d['parity']['per_rank_max_abs'] == [1e-19, 2e-19]
+
+
+def test_plain_bench_gpus2_runs_only_the_headline():
+    """Without --full the N-rank run is the headline alone: no configs 4 / 5, no oracle parity."""
+    p = _run('bench.py', '--gpus', '2', '--rehearse')
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d['n_gpus'] == 2 and d['ranks_seen'] == 2 and [r['rank'] for r in d['ranks']] == [0, 1]
+    assert d['multi_gpu'] is None and d['parity'] is None
+
+
+def test_bench_rejects_no_timed_steps():
+    p = _run('bench.py', '--gpus', '1', '--steps', '0', '--rehearse')
+    assert p.returncode != 0 and '--steps must be >= 1' in p.stderr
 
 
 def test_bench_refuses_a_world_that_is_not_gpus():
@@ -57,7 +73,7 @@ def test_a_failing_rank_does_not_hang_the_multi_gpu_record():
     """every rank takes part in every collective of multi_gpu_record; a stage that fails on
     one rank arrives on rank 0 as an error record instead of leaving the others in a barrier."""
     for stage, other in (('ensemble', 'bayes'), ('bayes', 'ensemble')):
-        p = _run('bench.py', '--gpus', '2', '--rehearse', env={'BENCH_FAIL_STAGE': stage})
+        p = _run('bench.py', '--gpus', '2', '--rehearse', '--full', env={'BENCH_FAIL_STAGE': stage})
         assert p.returncode == 0, p.stderr[-2000:]
         d = json.loads([l for l in p.stdout.splitlines() if l.startswith('{')][0])
         mg = d['multi_gpu']
