@@ -322,6 +322,38 @@ int ps_chain_set_kernels_device(ps_solver* s, int nk, const int64_t* off, const 
 int ps_solver_set_state_device(ps_solver* s, const void* row_dev, const void* col_dev, const void* val_dev,
                                int64_t nnz, int kshape);
 
+/* ---- posterior predictive spread: per-cell weighted moments of many model evaluations ----
+ * (no reference counterpart: CompareToData.assess_fit / Plot_Result show one run at a point estimate).
+ * A summary lives on one device and holds nslot day slots of N x N cells; per cell the weighted mean and
+ * M2 (fp64) and one uint32 count per threshold (0..4): the weight of the members whose value reached it.
+ * Host side: the total weight W (< 2^32: the counts are exact) and the member count.  One thread owns a
+ * cell: no atomics, the result is bitwise the same for the same members in the same order. */
+typedef struct ps_summary ps_summary;
+/* thr[nthr] thresholds (v >= thr counts) */
+int ps_summary_create(int device, int N, int nslot, int nthr, const double* thr, ps_summary** out);
+/* Accumulate one member with integer weight w >= 1 from the records of solver s (same device, same N):
+ * slot i reads record (kind[i], idx[i]) and adds, per cell, exactly what the matching
+ * ps_record_fetch_* returns there (0 where it returns no entry):
+ *   t = rec * stat_scale[i];  v = (t != 0 && !(t < negval)) ? (t + delta) * post_scale[i] : 0
+ * delta = the day's device statistics' delta when use_delta[i] (chain records), else 0.  Weighted Welford
+ * (West 1979): W' = W + w, d = v - mean, mean += d w / W', M2 += w d (v - mean).  One launch on the
+ * solver's stream, no host synchronisation; an event orders it after the summary's previous operation
+ * on whatever stream that ran.  nslot must equal the summary's. */
+int ps_summary_add(ps_summary* a, ps_solver* s, int nslot, const int32_t* kind, const int32_t* idx,
+                   const double* stat_scale, const double* post_scale, const int32_t* use_delta,
+                   double negval, uint32_t weight);
+/* dst += src (Chan et al. pairwise update), same device, N, slots and thresholds; src stays as it is */
+int ps_summary_merge(ps_summary* dst, ps_summary* src);
+int ps_summary_info(ps_summary* a, double* total_weight, int64_t* members);
+/* one slot to the host (synchronises): what 0 mean, 1 variance M2 / W, 2 + k P(v >= thr[k]) = count_k / W.
+ * PS_ERR_STATE at W = 0. */
+int ps_summary_fetch(ps_summary* a, int slot, int what, double* out /* N*N */);
+int ps_summary_reset(ps_summary* a);
+/* measurement: HIP-event timing of the ps_summary_add launches.  enable 1 on, 0 off, < 0 unchanged;
+ * total_ms / launches (either may be NULL) receive the timed launches so far (synchronises). */
+int ps_summary_prof(ps_summary* a, int enable, double* total_ms, int64_t* launches);
+void ps_summary_destroy(ps_summary* a);
+
 #ifdef __cplusplus
 }
 #endif

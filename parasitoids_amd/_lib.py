@@ -117,6 +117,15 @@ SIGNATURES = {
     'ps_model_export_device': (C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP, _VP, C.c_int64]),
     'ps_chain_set_kernels_device': (C.c_int, [_VP, C.c_int, _I64P, _I32P, _VP, _VP, _VP]),
     'ps_solver_set_state_device': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, C.c_int]),
+    'ps_summary_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _F64P, C.POINTER(_VP)]),
+    'ps_summary_add': (C.c_int, [_VP, _VP, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P, C.c_double,
+                                 C.c_uint32]),
+    'ps_summary_merge': (C.c_int, [_VP, _VP]),
+    'ps_summary_info': (C.c_int, [_VP, _F64P, _I64P]),
+    'ps_summary_fetch': (C.c_int, [_VP, C.c_int, C.c_int, _F64P]),
+    'ps_summary_reset': (C.c_int, [_VP]),
+    'ps_summary_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P]),
+    'ps_summary_destroy': (None, [_VP]),
 }
 
 _lib = None

@@ -114,3 +114,12 @@ int ps_solver_set_state_device_coo(ps_solver* s, const int* row, const int* col,
                                    int64_t nnz, int off);
 int ps_solver_dom_len_internal(ps_solver* s);
 int ps_solver_device_internal(ps_solver* s);
+
+// the view of one solver record that ps_summary.hip accumulates (ps_solver_record_internal)
+struct PsRecordView {
+  const double* rec;            // N x N, row-major, device
+  const ps_day_stats* stats;    // the day's device statistics (chain records), or nullptr
+  hipStream_t stream;           // the stream the record is written on
+  int N, device;
+};
+int ps_solver_record_internal(ps_solver* s, int kind, int idx, int want_stats, PsRecordView* out);

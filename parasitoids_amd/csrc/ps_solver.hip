@@ -2969,4 +2969,33 @@ extern "C" int ps_solver_owner_fft(ps_solver* s, int owner) {
 int ps_solver_dom_len_internal(ps_solver* s) { return s->N; }
 int ps_solver_device_internal(ps_solver* s) { return s->device; }
 
+// ps_summary.hip: one record of s with the device statistics of its day.  The chain leaves the
+// statistics to ps_chain_stats (finalize_days); with want_stats the day's are finalised here, on the
+// stream the record was written on (an auto-mode day may belong to a helper: its statistics are the
+// helper's, the record and the stream the front's).  Enqueues only: no host synchronisation.
+int ps_solver_record_internal(ps_solver* s, int kind, int idx, int want_stats, PsRecordView* out) {
+  if (!s || !out) return ps_fail(PS_ERR_BAD_ARG, "record view: bad arguments");
+  PS_HIP(hipSetDevice(s->device));
+  double* rec;
+  PS_TRY(get_record(s, kind, idx, &rec));
+  out->rec = rec;
+  out->stats = nullptr;
+  out->stream = s->stream;
+  out->N = s->N;
+  out->device = s->device;
+  if (!want_stats) return PS_OK;
+  if (kind != PS_REC_CHAIN || idx >= s->nstat)
+    return ps_fail(PS_ERR_STATE, "record (%d,%d) has no day statistics", kind, idx);
+  ps_solver* c = s;
+  if (s->auto_exact && s->auto_first >= 0 && idx < (int)s->owner.size()) {
+    const int o = s->owner[idx];
+    c = o == 1 ? s->wide : (o == 2 ? s->child : (o == 3 ? s->narrow : s));
+    if (!c) return ps_fail(PS_ERR_STATE, "auto mode: day %d has no owner", idx);
+    if (idx >= c->nstat) return ps_fail(PS_ERR_STATE, "auto mode: day %d has no statistics", idx);
+  }
+  PS_TRY(finalize_days(c, idx, 1, c->last_renorm));
+  out->stats = reinterpret_cast<const ps_day_stats*>(c->dstats.p + idx);
+  return PS_OK;
+}
+
 

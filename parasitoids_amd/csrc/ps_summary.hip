@@ -1,0 +1,330 @@
+// Posterior predictive spread (include/parasitoid_hip.h, ps_summary_*): per-cell weighted mean, M2
+// and threshold counts of many model evaluations, accumulated on the device from the solver's
+// records.  Layout per slot (pitch = N*N rounded up to 64 cells, so every slot starts 16-byte
+// aligned): mean[slot][pitch], m2[slot][pitch] (fp64), cnt[slot][k][pitch] (uint32).  An add reads
+// 8 B of record and reads + writes 16 B of mean, 16 B of M2 and 8 B per threshold of every cell of
+// every slot -- less where a pair of cells is unchanged (value == mean: nothing is stored).
+#include <vector>
+
+#include "ps_common.h"
+
+#define PS_SUM_MAX_THR 4
+#define PS_SUM_CHUNK 32   // slots per launch: 32 descriptors = 1.3 kB of kernel arguments
+
+namespace {
+
+struct SumSlot {
+  const double* rec;
+  const ps_day_stats* stats;   // nullptr: no delta
+  double stat_scale, post_scale;
+  int slot;
+};
+struct SumSlots {
+  SumSlot s[PS_SUM_CHUNK];
+};
+struct SumThr {
+  double t[PS_SUM_MAX_THR];
+};
+
+// what ps_record_fetch_* holds at the cell (k_compact_rows, chain_kernels.h), 0 where it holds nothing
+__device__ inline double sum_value(double r, double stat_scale, double post_scale, double delta, double negval) {
+  const double t = r * stat_scale;
+  const bool keep = (t != 0.0) && !(t < negval);
+  return keep ? (t + delta) * post_scale : 0.0;
+}
+
+__device__ inline bool sum_update(double v, double w, double Wn, double& m, double& m2) {
+  const double d = v - m;
+  if (d == 0.0) return false;          // mean and M2 stay bit for bit as they are
+  m += d * w / Wn;
+  m2 += w * d * (v - m);
+  return true;
+}
+
+// blockIdx.y = slot of the chunk; a thread owns a pair of cells (the tail cell of an odd N*N alone)
+__global__ void k_summary_add(SumSlots desc, double* __restrict__ mean, double* __restrict__ m2,
+                              uint32_t* __restrict__ cnt, int64_t ncell, int64_t pitch, int nthr, SumThr thr,
+                              double negval, double w, double Wn, uint32_t wi) {
+  const SumSlot sd = desc.s[blockIdx.y];
+  const double delta = sd.stats ? sd.stats->delta : 0.0;
+  const double* __restrict__ rec = sd.rec;
+  double* ms = mean + (int64_t)sd.slot * pitch;
+  double* qs = m2 + (int64_t)sd.slot * pitch;
+  uint32_t* cs = cnt + (int64_t)sd.slot * nthr * pitch;
+  const int64_t npair = ncell >> 1;
+  for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j <= npair; j += (int64_t)gridDim.x * blockDim.x) {
+    if (j < npair) {
+      const double2 r = *reinterpret_cast<const double2*>(rec + 2 * j);
+      double2 m = *reinterpret_cast<const double2*>(ms + 2 * j);
+      double2 q = *reinterpret_cast<const double2*>(qs + 2 * j);
+      const double v0 = sum_value(r.x, sd.stat_scale, sd.post_scale, delta, negval);
+      const double v1 = sum_value(r.y, sd.stat_scale, sd.post_scale, delta, negval);
+      const bool c0 = sum_update(v0, w, Wn, m.x, q.x);
+      const bool c1 = sum_update(v1, w, Wn, m.y, q.y);
+      if (c0 || c1) {
+        *reinterpret_cast<double2*>(ms + 2 * j) = m;
+        *reinterpret_cast<double2*>(qs + 2 * j) = q;
+      }
+      for (int k = 0; k < nthr; ++k) {
+        const bool e0 = v0 >= thr.t[k], e1 = v1 >= thr.t[k];
+        if (e0 || e1) {
+          uint2* p = reinterpret_cast<uint2*>(cs + (int64_t)k * pitch + 2 * j);
+          uint2 c = *p;
+          c.x += e0 ? wi : 0u;
+          c.y += e1 ? wi : 0u;
+          *p = c;
+        }
+      }
+    } else if (ncell & 1) {
+      const int64_t i = ncell - 1;
+      const double v = sum_value(rec[i], sd.stat_scale, sd.post_scale, delta, negval);
+      double m = ms[i], q = qs[i];
+      if (sum_update(v, w, Wn, m, q)) {
+        ms[i] = m;
+        qs[i] = q;
+      }
+      for (int k = 0; k < nthr; ++k)
+        if (v >= thr.t[k]) cs[(int64_t)k * pitch + i] += wi;
+    }
+  }
+}
+
+// Chan, Golub & LeVeque: (Wa, mean_a, M2a) + (Wb, mean_b, M2b) over every slot's cells
+__global__ void k_summary_merge(double* __restrict__ ma, double* __restrict__ qa, uint32_t* __restrict__ ca,
+                                const double* __restrict__ mb, const double* __restrict__ qb,
+                                const uint32_t* __restrict__ cb, int64_t nval, int64_t ncnt, double Wa,
+                                double Wb) {
+  const double W = Wa + Wb;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nval; i += stride) {
+    const double d = mb[i] - ma[i];
+    ma[i] = ma[i] + d * (Wb / W);
+    qa[i] = qa[i] + qb[i] + d * d * (Wa * Wb / W);
+  }
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < ncnt; i += stride) ca[i] += cb[i];
+}
+
+}  // namespace
+
+struct ps_summary {
+  int device = 0, N = 0, nslot = 0, nthr = 0;
+  double thr[PS_SUM_MAX_THR] = {0, 0, 0, 0};
+  int64_t ncell = 0, pitch = 0;
+  double* mean = nullptr;
+  double* m2 = nullptr;
+  uint32_t* cnt = nullptr;
+  uint64_t W = 0;
+  int64_t members = 0;
+  hipStream_t stream = nullptr;   // reset / merge / fetch
+  hipEvent_t ev = nullptr;        // the summary's last operation, on whatever stream it ran
+  bool ev_live = false;
+  bool prof_on = false;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof;
+};
+
+static size_t val_bytes(const ps_summary* a) { return (size_t)a->nslot * a->pitch * sizeof(double); }
+static size_t cnt_bytes(const ps_summary* a) { return (size_t)a->nslot * a->nthr * a->pitch * sizeof(uint32_t); }
+
+// order `stream` behind the summary's previous operation
+static int after_last(ps_summary* a, hipStream_t stream) {
+  if (a->ev_live) PS_HIP(hipStreamWaitEvent(stream, a->ev, 0));
+  return PS_OK;
+}
+static int mark_last(ps_summary* a, hipStream_t stream) {
+  PS_HIP(hipEventRecord(a->ev, stream));
+  a->ev_live = true;
+  return PS_OK;
+}
+
+extern "C" void ps_summary_destroy(ps_summary* a) {
+  if (!a) return;
+  (void)hipSetDevice(a->device);
+  if (a->ev_live) (void)hipEventSynchronize(a->ev);
+  if (a->stream) (void)hipStreamSynchronize(a->stream);
+  for (auto& p : a->prof) {
+    (void)hipEventDestroy(p.first);
+    (void)hipEventDestroy(p.second);
+  }
+  if (a->mean) (void)hipFree(a->mean);
+  if (a->m2) (void)hipFree(a->m2);
+  if (a->cnt) (void)hipFree(a->cnt);
+  if (a->ev) (void)hipEventDestroy(a->ev);
+  if (a->stream) (void)hipStreamDestroy(a->stream);
+  delete a;
+}
+
+extern "C" int ps_summary_reset(ps_summary* a) {
+  if (!a) return ps_fail(PS_ERR_BAD_ARG, "summary_reset: null summary");
+  PS_HIP(hipSetDevice(a->device));
+  PS_TRY(after_last(a, a->stream));
+  PS_HIP(hipMemsetAsync(a->mean, 0, val_bytes(a), a->stream));
+  PS_HIP(hipMemsetAsync(a->m2, 0, val_bytes(a), a->stream));
+  if (a->nthr) PS_HIP(hipMemsetAsync(a->cnt, 0, cnt_bytes(a), a->stream));
+  PS_TRY(mark_last(a, a->stream));
+  a->W = 0;
+  a->members = 0;
+  return PS_OK;
+}
+
+extern "C" int ps_summary_create(int device, int N, int nslot, int nthr, const double* thr, ps_summary** out) {
+  if (!out || N < 1 || nslot < 1 || nthr < 0 || nthr > PS_SUM_MAX_THR || (nthr > 0 && !thr))
+    return ps_fail(PS_ERR_BAD_ARG, "summary_create: N %d, %d slots, %d thresholds (at most %d)", N, nslot, nthr,
+                   PS_SUM_MAX_THR);
+  *out = nullptr;
+  PS_TRY(ps_use_device(device));
+  ps_summary* a = new ps_summary();
+  a->device = device;
+  a->N = N;
+  a->nslot = nslot;
+  a->nthr = nthr;
+  for (int k = 0; k < nthr; ++k) a->thr[k] = thr[k];
+  a->ncell = (int64_t)N * N;
+  a->pitch = (a->ncell + 63) / 64 * 64;
+  auto fail = [&](int rc) {
+    ps_summary_destroy(a);
+    return rc;
+  };
+  hipError_t e = hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&a->ev, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipMalloc((void**)&a->mean, val_bytes(a));
+  if (e == hipSuccess) e = hipMalloc((void**)&a->m2, val_bytes(a));
+  if (e == hipSuccess && nthr) e = hipMalloc((void**)&a->cnt, cnt_bytes(a));
+  if (e != hipSuccess)
+    return fail(ps_fail(e == hipErrorOutOfMemory ? PS_ERR_OOM : PS_ERR_HIP, "summary_create: %s", hipGetErrorString(e)));
+  int rc = ps_summary_reset(a);
+  if (rc != PS_OK) return fail(rc);
+  *out = a;
+  return PS_OK;
+}
+
+extern "C" int ps_summary_add(ps_summary* a, ps_solver* s, int nslot, const int32_t* kind, const int32_t* idx,
+                              const double* stat_scale, const double* post_scale, const int32_t* use_delta,
+                              double negval, uint32_t weight) {
+  if (!a || !s || !kind || !idx || !stat_scale || !post_scale || !use_delta)
+    return ps_fail(PS_ERR_BAD_ARG, "summary_add: bad arguments");
+  if (nslot != a->nslot) return ps_fail(PS_ERR_BAD_ARG, "summary_add: %d slots given, the summary has %d", nslot, a->nslot);
+  if (weight < 1) return ps_fail(PS_ERR_BAD_ARG, "summary_add: weight must be >= 1");
+  if (a->W + weight > 0xffffffffull)
+    return ps_fail(PS_ERR_BAD_ARG, "summary_add: total weight %llu would overflow the uint32 counts",
+                   (unsigned long long)(a->W + weight));
+  PS_HIP(hipSetDevice(a->device));
+  // every descriptor first: an add with a bad slot enqueues nothing
+  std::vector<SumSlot> d((size_t)nslot);
+  hipStream_t stream = nullptr;
+  for (int i = 0; i < nslot; ++i) {
+    PsRecordView v;
+    PS_TRY(ps_solver_record_internal(s, kind[i], idx[i], use_delta[i] != 0, &v));
+    if (v.device != a->device)
+      return ps_fail(PS_ERR_BAD_ARG, "summary_add: solver on device %d, summary on device %d", v.device, a->device);
+    if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "summary_add: solver domain %d, summary domain %d", v.N, a->N);
+    d[i] = SumSlot{v.rec, v.stats, stat_scale[i], post_scale[i], i};
+    stream = v.stream;
+  }
+  PS_TRY(after_last(a, stream));
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (a->prof_on) {
+    PS_HIP(hipEventCreate(&e0));
+    PS_HIP(hipEventCreate(&e1));
+    a->prof.push_back({e0, e1});
+    PS_HIP(hipEventRecord(e0, stream));
+  }
+  SumThr thr;
+  for (int k = 0; k < PS_SUM_MAX_THR; ++k) thr.t[k] = a->thr[k];
+  const double Wn = (double)(a->W + weight);
+  const int64_t npair = a->ncell / 2 + 1;
+  const int threads = 256;
+  const int bx = (int)std::min<int64_t>((npair + threads - 1) / threads, 4096);
+  for (int c0 = 0; c0 < nslot; c0 += PS_SUM_CHUNK) {
+    const int n = std::min(PS_SUM_CHUNK, nslot - c0);
+    SumSlots desc;
+    for (int i = 0; i < n; ++i) desc.s[i] = d[(size_t)(c0 + i)];
+    hipLaunchKernelGGL(k_summary_add, dim3(bx, n), dim3(threads), 0, stream, desc, a->mean, a->m2, a->cnt, a->ncell,
+                       a->pitch, a->nthr, thr, negval, (double)weight, Wn, weight);
+    PS_HIP(hipGetLastError());
+  }
+  if (e1) PS_HIP(hipEventRecord(e1, stream));
+  PS_TRY(mark_last(a, stream));
+  a->W += weight;
+  a->members += 1;
+  return PS_OK;
+}
+
+extern "C" int ps_summary_merge(ps_summary* dst, ps_summary* src) {
+  if (!dst || !src || dst == src) return ps_fail(PS_ERR_BAD_ARG, "summary_merge: bad arguments");
+  if (dst->device != src->device || dst->N != src->N || dst->nslot != src->nslot || dst->nthr != src->nthr)
+    return ps_fail(PS_ERR_BAD_ARG, "summary_merge: summaries differ in device, domain, slots or thresholds");
+  for (int k = 0; k < dst->nthr; ++k)
+    if (dst->thr[k] != src->thr[k]) return ps_fail(PS_ERR_BAD_ARG, "summary_merge: threshold %d differs", k);
+  if (dst->W + src->W > 0xffffffffull) return ps_fail(PS_ERR_BAD_ARG, "summary_merge: total weight would overflow");
+  if (src->W == 0) return PS_OK;
+  PS_HIP(hipSetDevice(dst->device));
+  PS_TRY(after_last(dst, dst->stream));
+  PS_TRY(after_last(src, dst->stream));
+  if (dst->W == 0) {   // a copy: the merged summary is src bit for bit
+    PS_HIP(hipMemcpyAsync(dst->mean, src->mean, val_bytes(dst), hipMemcpyDeviceToDevice, dst->stream));
+    PS_HIP(hipMemcpyAsync(dst->m2, src->m2, val_bytes(dst), hipMemcpyDeviceToDevice, dst->stream));
+    if (dst->nthr) PS_HIP(hipMemcpyAsync(dst->cnt, src->cnt, cnt_bytes(dst), hipMemcpyDeviceToDevice, dst->stream));
+  } else {
+    const int64_t nval = (int64_t)dst->nslot * dst->pitch;
+    hipLaunchKernelGGL(k_summary_merge, dim3(2048), dim3(256), 0, dst->stream, dst->mean, dst->m2, dst->cnt, src->mean,
+                       src->m2, src->cnt, nval, nval * dst->nthr, (double)dst->W, (double)src->W);
+    PS_HIP(hipGetLastError());
+  }
+  PS_TRY(mark_last(dst, dst->stream));
+  PS_TRY(mark_last(src, dst->stream));   // src is read until then
+  dst->W += src->W;
+  dst->members += src->members;
+  return PS_OK;
+}
+
+extern "C" int ps_summary_info(ps_summary* a, double* total_weight, int64_t* members) {
+  if (!a) return ps_fail(PS_ERR_BAD_ARG, "summary_info: null summary");
+  if (total_weight) *total_weight = (double)a->W;
+  if (members) *members = a->members;
+  return PS_OK;
+}
+
+extern "C" int ps_summary_fetch(ps_summary* a, int slot, int what, double* out) {
+  if (!a || !out) return ps_fail(PS_ERR_BAD_ARG, "summary_fetch: bad arguments");
+  if (slot < 0 || slot >= a->nslot) return ps_fail(PS_ERR_BAD_ARG, "summary_fetch: slot %d of %d", slot, a->nslot);
+  if (what < 0 || what >= 2 + a->nthr)
+    return ps_fail(PS_ERR_BAD_ARG, "summary_fetch: quantity %d (0 mean, 1 variance, 2..%d exceedance)", what, 1 + a->nthr);
+  if (a->W == 0) return ps_fail(PS_ERR_STATE, "summary_fetch: nothing accumulated (W = 0)");
+  PS_HIP(hipSetDevice(a->device));
+  PS_TRY(after_last(a, a->stream));
+  const double W = (double)a->W;
+  const size_t n = (size_t)a->ncell;
+  if (what == 0) {
+    PS_HIP(hipMemcpyAsync(out, a->mean + (int64_t)slot * a->pitch, n * sizeof(double), hipMemcpyDeviceToHost, a->stream));
+    PS_HIP(hipStreamSynchronize(a->stream));
+  } else if (what == 1) {
+    PS_HIP(hipMemcpyAsync(out, a->m2 + (int64_t)slot * a->pitch, n * sizeof(double), hipMemcpyDeviceToHost, a->stream));
+    PS_HIP(hipStreamSynchronize(a->stream));
+    for (size_t i = 0; i < n; ++i) out[i] /= W;
+  } else {
+    std::vector<uint32_t> c(n);
+    const uint32_t* src = a->cnt + ((int64_t)slot * a->nthr + (what - 2)) * a->pitch;
+    PS_HIP(hipMemcpyAsync(c.data(), src, n * sizeof(uint32_t), hipMemcpyDeviceToHost, a->stream));
+    PS_HIP(hipStreamSynchronize(a->stream));
+    for (size_t i = 0; i < n; ++i) out[i] = (double)c[i] / W;
+  }
+  return PS_OK;
+}
+
+extern "C" int ps_summary_prof(ps_summary* a, int enable, double* total_ms, int64_t* launches) {
+  if (!a) return ps_fail(PS_ERR_BAD_ARG, "summary_prof: null summary");
+  PS_HIP(hipSetDevice(a->device));
+  if (enable >= 0) a->prof_on = enable != 0;
+  if (total_ms || launches) {
+    double ms = 0.0;
+    for (auto& p : a->prof) {
+      PS_HIP(hipEventSynchronize(p.second));
+      float t = 0.f;
+      PS_HIP(hipEventElapsedTime(&t, p.first, p.second));
+      ms += t;
+    }
+    if (total_ms) *total_ms = ms;
+    if (launches) *launches = (int64_t)a->prof.size();
+  }
+  return PS_OK;
+}

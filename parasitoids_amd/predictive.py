@@ -1,0 +1,404 @@
+"""Posterior predictive spread from MCMC chains (no reference counterpart: CompareToData.assess_fit
+and Plot_Result show one run at a point estimate).
+
+`SpreadSummary` accumulates, on the device, the per-cell weighted mean, variance and threshold
+exceedance of the daily populations of many model evaluations (ps_summary_*, csrc/ps_summary.hip):
+the value added for a cell is exactly what `PopModel.population(day)` holds there, 0 where it holds
+nothing.  `posterior_predictive` feeds it from `mcmc.Sampler.save` chains -- one evaluation per run of
+identical model parameters, weighted by the run's length -- and, given the site's observations,
+draws replicated observations from the reference's Poisson model (Bayes_Run.py:344-433).
+"""
+import ctypes as C
+import json
+import os
+import threading
+import time
+
+import numpy as np
+
+from . import _lib as L
+from . import mcmc
+
+NEGVAL = 1e-8          # r_small_vals threshold of the daily solutions (CalcSol.py:126-132)
+
+
+class SpreadSummary():
+    '''Weighted per-cell moments of `pop_model`'s days over the members added.  days: model days
+    (0 = release day) to keep, default all; thresholds: up to 4 population densities whose
+    exceedance probability is kept.'''
+
+    def __init__(self, pop_model, days=None, thresholds=()):
+        self._lib = L.load()
+        self._h = L._VP()
+        self.pm = pop_model
+        self.days = list(range(len(pop_model.days)) if days is None else days)
+        if not self.days or min(self.days) < 0:
+            raise ValueError('days must be a non-empty list of model days >= 0')
+        self.thresholds = [float(t) for t in thresholds]
+        self.N = 2 * int(pop_model.rad_res) + 1
+        self.device = L.default_device() if pop_model.device is None else int(pop_model.device)
+        thr = L.f64(self.thresholds if self.thresholds else [0.0])
+        L.check(self._lib.ps_summary_create(self.device, self.N, len(self.days), len(self.thresholds),
+                                            L.p_f64(thr), C.byref(self._h)))
+        n = len(self.days)
+        self._kind = L.i32([L.REC_STATE if d == 0 else L.REC_CHAIN for d in self.days])
+        self._idx = L.i32([0 if d == 0 else d - 1 for d in self.days])
+        self._delta = L.i32([0 if d == 0 else 1 for d in self.days])
+        self._slot = {d: i for i, d in enumerate(self.days)}
+        self._n = n
+
+    def add(self, weight=1):
+        '''Accumulate the last evaluation of the model with integer weight >= 1 (enqueued on the
+        solver's stream; no host synchronisation).'''
+        pm = self.pm
+        nd = getattr(pm, '_nd', 0)
+        if pm.solver is None or max(self.days) >= nd:
+            raise ValueError('the last evaluation has %d days; the summary needs day %d' % (nd, max(self.days)))
+        r = float(pm.r_number)
+        stat = L.f64([1.0 if d == 0 else r for d in self.days])
+        post = L.f64([r if d == 0 else 1.0 for d in self.days])
+        w = int(weight)
+        if w < 1:
+            raise ValueError('weight must be a positive integer')
+        L.check(self._lib.ps_summary_add(self._h, pm.solver._h, self._n, L.p_i32(self._kind), L.p_i32(self._idx),
+                                         L.p_f64(stat), L.p_f64(post), L.p_i32(self._delta), NEGVAL, w))
+
+    def merge(self, other):
+        '''self += other (same device, domain, days and thresholds)'''
+        if list(other.days) != self.days:
+            raise ValueError('summaries over different days')
+        L.check(self._lib.ps_summary_merge(self._h, other._h))
+
+    def reset(self):
+        L.check(self._lib.ps_summary_reset(self._h))
+
+    def _info(self):
+        w, m = C.c_double(), C.c_int64()
+        L.check(self._lib.ps_summary_info(self._h, C.byref(w), C.byref(m)))
+        return w.value, m.value
+
+    @property
+    def total_weight(self):
+        return self._info()[0]
+
+    @property
+    def members(self):
+        return self._info()[1]
+
+    def _fetch(self, day, what):
+        if day not in self._slot:
+            raise ValueError('day %r is not in the summary %s' % (day, self.days))
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        L.check(self._lib.ps_summary_fetch(self._h, self._slot[day], int(what), L.p_f64(out)))
+        return out
+
+    def fetch_slot(self, slot, what):
+        '''raw access by slot index (0 mean, 1 variance, 2 + k exceedance)'''
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        L.check(self._lib.ps_summary_fetch(self._h, int(slot), int(what), L.p_f64(out)))
+        return out
+
+    def mean(self, day):
+        return self._fetch(day, 0)
+
+    def variance(self, day):
+        return self._fetch(day, 1)
+
+    def sd(self, day):
+        return np.sqrt(self.variance(day))
+
+    def exceedance(self, day, k):
+        '''P(population >= thresholds[k]) per cell'''
+        if not 0 <= k < len(self.thresholds):
+            raise ValueError('threshold %r of %d' % (k, len(self.thresholds)))
+        return self._fetch(day, 2 + k)
+
+    def profile(self, enable=None):
+        '''HIP-event time of the accumulate launches: (total ms, launches); enable switches it'''
+        ms, n = C.c_double(), C.c_int64()
+        L.check(self._lib.ps_summary_prof(self._h, -1 if enable is None else int(bool(enable)), C.byref(ms),
+                                          C.byref(n)))
+        return ms.value, n.value
+
+    def close(self):
+        if self._h:
+            self._lib.ps_summary_destroy(self._h)
+            self._h = L._VP()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ------------------------------------------------------------------ traces
+def model_names():
+    return [m[0] for m in mcmc.MODEL_BLOCK]
+
+
+def nuisance_names():
+    return [m[0] for m in mcmc.NUISANCE]
+
+
+def load_chain(chain):
+    '''(trace, names, source) of one `Sampler.save` file or (trace, names) pair'''
+    if isinstance(chain, (str, os.PathLike)):
+        fname = str(chain)
+        f = np.load(fname if fname.endswith('.npz') else fname + '.npz', allow_pickle=False)
+        return np.asarray(f['trace'], dtype=np.float64), [str(n) for n in f['names']], fname
+    trace, names = chain
+    return np.asarray(trace, dtype=np.float64), [str(n) for n in names], None
+
+
+def _columns(names, want):
+    '''column index of every name of `want`; the ValueError of Sampler.resume when one is missing'''
+    pos = {n: i for i, n in enumerate(names)}
+    if any(n not in pos for n in want):
+        raise ValueError('the chain file was written for a different model')
+    return [pos[n] for n in want]
+
+
+def runs(trace, model_cols, burn=0, thin=1):
+    '''burn / thin one chain, then split it into runs of identical model-block rows ->
+    (rows [n, ncol], [(first_row, length), ...])'''
+    if burn < 0 or thin < 1:
+        raise ValueError('burn must be >= 0 and thin >= 1')
+    rows = trace[burn::thin]
+    out = []
+    i = 0
+    theta = rows[:, model_cols]
+    while i < len(rows):
+        j = i + 1
+        while j < len(rows) and np.array_equal(theta[j], theta[i]):
+            j += 1
+        out.append((i, j - i))
+        i = j
+    return rows, out
+
+
+# ------------------------------------------------------------------ observation model
+def observation_rates(expected, locinfo, nuis, sent_obs_probs):
+    '''Poisson rates of the reference's observation model (Bayes_Run.py:344-433), as mcmc.loglik_parts
+    uses them: release grids xi * emergence * effort * em_obs_prob, sentinel fields
+    xi * emergence * sent_obs_prob[field], grid counts grid_obs_prob * samples * density.
+    -> (list of release arrays, list of sentinel arrays, grid array)'''
+    rel, sen, grid = expected
+    xi, em_p, grid_p = (float(v) for v in nuis)
+    c = mcmc.observation_cache(locinfo)
+    r_rel = [xi * np.asarray(e, dtype=np.float64) * (c['effort'][ii] * em_p)[:, None] for ii, e in enumerate(rel)]
+    sp = np.asarray(sent_obs_probs, dtype=np.float64)[:, None]
+    r_sen = [xi * np.asarray(e, dtype=np.float64) * sp for e in sen]
+    r_grid = grid_p * c['samples'] * np.asarray(grid, dtype=np.float64)
+    return r_rel, r_sen, r_grid
+
+
+def _flat(arrs):
+    arrs = [np.asarray(a, dtype=np.float64).ravel() for a in arrs]
+    return np.concatenate(arrs) if arrs else np.zeros(0)
+
+
+def observation_predictive(rates, locinfo, seed=0):
+    '''rates: one observation_rates result per trace row.  Replicated counts drawn with
+    default_rng(seed) -> per group (release, sentinel, grid): mean rate, 5/50/95 % quantiles of
+    the replicated counts per observation, P(total replicated >= total observed).'''
+    c = mcmc.observation_cache(locinfo)
+    observed = {'release': _flat(c['rel']), 'sentinel': _flat(c['sen']), 'grid': _flat([c['grid']])}
+    rng = np.random.default_rng(seed)
+    out = {}
+    for g, gi in (('release', 0), ('sentinel', 1), ('grid', 2)):
+        lam = np.array([_flat(r[gi] if gi < 2 else [r[2]]) for r in rates]).reshape(len(rates), -1)
+        rep = rng.poisson(lam) if lam.size else np.zeros(lam.shape)
+        obs = observed[g]
+        out[g] = {'mean_rate': lam.mean(0) if len(rates) else np.zeros(obs.size),
+                  'q05': np.quantile(rep, 0.05, axis=0) if len(rates) else np.zeros(obs.size),
+                  'q50': np.quantile(rep, 0.50, axis=0) if len(rates) else np.zeros(obs.size),
+                  'q95': np.quantile(rep, 0.95, axis=0) if len(rates) else np.zeros(obs.size),
+                  'observed': obs,
+                  'p_total': float(np.mean(rep.sum(1) >= obs.sum())) if len(rates) else float('nan')}
+    return out
+
+
+# ------------------------------------------------------------------ driver
+class PredictiveResult():
+    '''What posterior_predictive returns: `summary` (a SpreadSummary, None without a device),
+    `rows` (trace rows after burn / thin), `evaluations`, `failed`, `seconds`, `runs`
+    ([(chain, first_row, weight)] of every evaluated run), `observations` (observation_predictive
+    or None) and `provenance`.'''
+
+    def __init__(self, summary, rows, evaluations, failed, seconds, runs, observations, provenance, days):
+        self.summary = summary
+        self.rows = rows
+        self.evaluations = evaluations
+        self.failed = failed
+        self.seconds = seconds
+        self.runs = runs
+        self.observations = observations
+        self.provenance = provenance
+        self.days = days
+
+    def save(self, outfile, params=None):
+        '''outfile.npz in the layout of Run.save_result (Run.py:490-516 of the reference), which
+        Plot_Result.main reads: per day `{day}_data/_ind/_indptr` of the posterior mean thresholded at
+        1e-8, `days`; besides `{day}_sd_*` and `{day}_pexc{k}_*` CSR triplets.  outfile.json: the
+        params, the thresholds, the chain provenance.  -> (npz path, json path)'''
+        from scipy import sparse
+        s = self.summary
+        if s is None:
+            raise ValueError('no spread summary to save (evaluate= runs without a device)')
+        out = {}
+        labels = []
+        for d in s.days:
+            label = s.pm.days[d] if d < len(s.pm.days) else d
+            labels.append(label)
+            maps = [('', s.mean(d)), ('_sd', s.sd(d))]
+            maps += [('_pexc%d' % k, s.exceedance(d, k)) for k in range(len(s.thresholds))]
+            for suffix, m in maps:
+                csr = sparse.csr_matrix(np.where(m >= NEGVAL, m, 0.0))
+                out['%s%s_data' % (label, suffix)] = csr.data
+                out['%s%s_ind' % (label, suffix)] = csr.indices
+                out['%s%s_indptr' % (label, suffix)] = csr.indptr
+        out['days'] = np.array(labels)
+        d = os.path.dirname(str(outfile))
+        if d and not os.path.exists(d):
+            os.makedirs(d)
+        np.savez(str(outfile), **out)
+        if params is None:
+            pdict = {}
+        elif isinstance(params, dict):
+            pdict = dict(params)
+        else:
+            pdict = dict(params.__dict__)
+            pdict.pop('maps_key', None)
+        meta = dict(pdict)
+        meta['predictive'] = {'thresholds': s.thresholds, 'total_weight': s.total_weight, 'members': s.members,
+                              'rows': self.rows, 'evaluations': self.evaluations, 'failed': self.failed,
+                              'chains': self.provenance}
+        with open(str(outfile) + '.json', 'w') as fobj:
+            json.dump(meta, fobj, default=str)
+        return str(outfile) + '.npz', str(outfile) + '.json'
+
+
+def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, locinfo):
+    '''one chain: evaluate every run, add it to the summary -> (expected per run or None, failed)'''
+    expected = []
+    failed = 0
+    for first, length in run_list:
+        theta = rows[first, model_cols]
+        if evaluate is not None:
+            exp = evaluate(theta)
+            if exp is None:
+                failed += 1
+            expected.append(exp)
+            continue
+        try:
+            pm.evaluate(*mcmc.model_args(theta), want_stats=False)
+        except (AssertionError, ValueError):
+            failed += 1
+            expected.append(None)
+            continue
+        except L.HipError as e:
+            if e.code not in mcmc._PARAMETER_ERRORS:
+                raise
+            failed += 1
+            expected.append(None)
+            continue
+        summary.add(length)
+        expected.append(mcmc.expected_observations(pm, locinfo) if want_obs else True)
+    return expected, failed
+
+
+def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, thresholds=(), locinfo=None,
+                         cell_area=None, seed=0, evaluate=None):
+    '''Posterior predictive spread of one or more chains (`Sampler.save` files or (trace, names)
+    pairs).  Burn and thin apply per chain; consecutive rows with identical model parameters are one
+    evaluation weighted by the run's length.  pop_model: one PopModel or a list -- with several, one
+    host thread per model runs its chains, each chain into its own summary, and the summaries are
+    merged in chain order (the result does not depend on the interleaving).  locinfo: observations
+    for the observation-level predictive (every row: the rates of its run's evaluation with its own
+    nuisance parameters).  evaluate(theta) -> expected observations or None: no device, no summary.'''
+    t0 = time.perf_counter()
+    if isinstance(chains, (str, os.PathLike)) or (isinstance(chains, tuple) and len(chains) == 2
+                                                   and not isinstance(chains[0], (str, os.PathLike, tuple))):
+        chains = [chains]
+    loaded = [load_chain(c) for c in chains]
+    want_obs = locinfo is not None
+    model_want = model_names()
+    obs_want = nuisance_names()
+    if want_obs:
+        obs_want = obs_want + ['sent_obs_probs_{}'.format(k) for k in locinfo.sent_ids]
+    prepared = []
+    for trace, names, src in loaded:
+        mcols = _columns(names, model_want)
+        ocols = _columns(names, obs_want) if want_obs else None
+        rows, rl = runs(trace, mcols, burn, thin)
+        prepared.append((rows, rl, mcols, ocols, src))
+    pms = list(pop_model) if isinstance(pop_model, (list, tuple)) else [pop_model]
+    if evaluate is None and (not pms or pms[0] is None):
+        raise ValueError('a PopModel is needed without evaluate=')
+    nch = len(prepared)
+    summaries = [None] * nch
+    results = [None] * nch
+    errs = []
+
+    def work(p):
+        try:
+            pm = pms[p]
+            for ci in range(p, nch, len(pms)):
+                rows, rl, mcols, _o, _s = prepared[ci]
+                summ = SpreadSummary(pm, days, thresholds) if evaluate is None else None
+                summaries[ci] = summ
+                results[ci] = _evaluate_runs(pm, summ, rows, rl, mcols, evaluate, want_obs, locinfo)
+        except BaseException as e:       # re-raised in the caller's thread
+            errs.append((p, e))
+
+    if evaluate is None and len(pms) > 1 and nch > 1:
+        threads = [threading.Thread(target=work, args=(p,), name='predictive-%d' % p)
+                   for p in range(min(len(pms), nch))]
+        for t in threads:
+            t.start()
+        for t in threads:
+            t.join()
+    else:
+        pms = pms[:1]
+        work(0)
+    if errs:
+        for s in summaries:
+            if s is not None:
+                s.close()
+        raise errs[0][1]
+    summary = None
+    if evaluate is None:
+        summary = summaries[0]
+        for s in summaries[1:]:
+            summary.merge(s)
+            s.close()
+    evaluations = sum(len(p[1]) for p in prepared)
+    failed = sum(r[1] for r in results)
+    run_rec = [(ci, first, length) for ci, p in enumerate(prepared)
+               for (first, length), e in zip(p[1], results[ci][0]) if e is not None]
+    observations = None
+    if want_obs:
+        rates = []
+        for ci, (rows, rl, mcols, ocols, _s) in enumerate(prepared):
+            for (first, length), exp in zip(rl, results[ci][0]):
+                if exp is None:
+                    continue
+                for r in range(first, first + length):
+                    v = rows[r, ocols]
+                    rates.append(observation_rates(exp, locinfo, v[:3], v[3:]))
+        observations = observation_predictive(rates, locinfo, seed)
+    prov = [{'source': p[4], 'rows': int(len(p[0])), 'runs': len(p[1]), 'burn': int(burn), 'thin': int(thin)}
+            for p in prepared]
+    res = PredictiveResult(summary, int(sum(len(p[0]) for p in prepared)), evaluations, failed,
+                           time.perf_counter() - t0, run_rec, observations, prov,
+                           None if summary is None else summary.days)
+    if cell_area is not None:
+        res.cell_area = float(cell_area)
+    return res

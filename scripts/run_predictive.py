@@ -1,0 +1,108 @@
+#!/usr/bin/env python3
+"""Posterior predictive spread of saved MCMC chains (parasitoids_amd/predictive.py): per day and
+cell the posterior mean population, its spread and exceedance probabilities, accumulated on the
+GPU, plus the observation-level predictive of the reference's Poisson model.  Kalbar wind and
+LocInfo as scripts/run_mcmc.py loads them; --synthetic uses the synthetic Kalbar-like observations.
+Without --chain a short chain is sampled first (--samples) and saved next to --out.
+
+    python scripts/run_predictive.py --chain c.npz [...] [--burn 0] [--thin 1] [--rad-res 400]
+        [--mode auto] [--thresholds 1,10] [--out PREFIX] [--synthetic] [--chains-parallel]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+import warnings
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--chain', nargs='+', default=None)
+    ap.add_argument('--burn', type=int, default=0)
+    ap.add_argument('--thin', type=int, default=1)
+    ap.add_argument('--rad-res', type=int, default=400)
+    ap.add_argument('--mode', default='auto', choices=['exact', 'fold', 'fast', 'auto'])
+    ap.add_argument('--thresholds', default='1,10')
+    ap.add_argument('--out', default='predictive_out/pp')
+    ap.add_argument('--synthetic', action='store_true')
+    ap.add_argument('--chains-parallel', action='store_true',
+                    help='one PopModel and host thread per chain (mcmc.run_parallel style)')
+    ap.add_argument('--samples', type=int, default=60, help='without --chain: length of the chain sampled first')
+    ap.add_argument('--seed', type=int, default=1000)
+    args = ap.parse_args()
+    warnings.simplefilter('ignore', RuntimeWarning)
+    from parasitoids_amd import ParasitoidModel as PM
+    from parasitoids_amd import mcmc
+    from parasitoids_amd.pop_model import PopModel
+    from parasitoids_amd.predictive import posterior_predictive
+    wd, days = PM.get_wind_data(os.path.join(ROOT, 'parasitoids_amd', 'data', 'kalbar'), 30, '00:00')
+
+    def make_pm():
+        return PopModel(wd, days, domain_info=(10000.0, args.rad_res), r_number=130000, mode=args.mode)
+    pm = make_pm()
+    if args.synthetic:
+        li = mcmc.synthetic_locinfo(pm, args.rad_res, seed=9)
+    else:
+        from parasitoids_amd.Data_Import import LocInfo
+        li = LocInfo('kalbar', (-27.947131, 152.584171), (10000.0, args.rad_res))   # Run.py:129
+    cell_area = (10000.0 / args.rad_res) ** 2
+    out_dir = os.path.dirname(args.out)
+    if out_dir:
+        os.makedirs(out_dir, exist_ok=True)
+    chains = args.chain
+    bayes_rate = None
+    if not chains:
+        smp = mcmc.Sampler(pm, li, cell_area, seed=args.seed)
+        r = smp.run(args.samples)
+        bayes_rate = r['evaluations_this_run'] * 3600.0 / r['seconds']
+        chains = [args.out + '_chain.npz']
+        smp.save(chains[0])
+    pms = [pm] + ([make_pm() for _ in chains[1:]] if args.chains_parallel else [])
+    thr = [float(t) for t in args.thresholds.split(',') if t.strip()]
+    t0 = time.perf_counter()
+    res = posterior_predictive(pms if len(pms) > 1 else pm, chains, burn=args.burn, thin=args.thin,
+                               thresholds=thr, locinfo=li, cell_area=cell_area, seed=args.seed)
+    dt = time.perf_counter() - t0
+    # accumulate-kernel time: the same members once more with HIP events around every add
+    from parasitoids_amd.predictive import SpreadSummary, load_chain, runs
+    with SpreadSummary(pm, None, thr) as S:
+        S.profile(True)
+        n = 0
+        for c in chains[:1]:
+            trace, names, _ = load_chain(c)
+            cols = [names.index(m[0]) for m in mcmc.MODEL_BLOCK]
+            rows, rl = runs(trace, cols, args.burn, args.thin)
+            for first, length in rl[:8]:
+                try:
+                    pm.evaluate(*mcmc.model_args(rows[first, cols]), want_stats=False)
+                except Exception:
+                    continue
+                S.add(length)
+                n += 1
+        ms, launches = S.profile()
+    npz, js = res.save(args.out, {'chains': chains, 'burn': args.burn, 'thin': args.thin, 'rad_res': args.rad_res,
+                                  'mode': args.mode, 'synthetic': bool(args.synthetic)})
+    ncell = (2 * args.rad_res + 1) ** 2
+    nday = len(res.summary.days)
+    per = ms / max(launches, 1)
+    out = {'metric': 'posterior predictive members/hour (Kalbar wind, %s observations)'
+                     % ('synthetic' if args.synthetic else 'Kalbar field'),
+           'value': round(3600.0 * res.evaluations / dt, 1), 'unit': 'members/hour',
+           'rows': res.rows, 'evaluations': res.evaluations, 'failed': res.failed, 'seconds': round(dt, 3),
+           'accumulate_ms_per_member': round(per, 4), 'accumulate_launches_timed': launches,
+           'accumulate_GBps': round((8 + 32 + 8 * len(thr)) * ncell * nday / (per * 1e-3) / 1e9, 1) if per > 0 else None,
+           'days': nday, 'thresholds': thr, 'chains': len(chains), 'chains_parallel': len(pms) > 1,
+           'bayes_evaluations_per_hour': None if bayes_rate is None else round(bayes_rate, 1),
+           'outputs': [npz, js]}
+    print(json.dumps(out))
+    res.summary.close()
+    for p in pms:
+        p.close()
+
+
+if __name__ == '__main__':
+    main()
