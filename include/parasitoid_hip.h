@@ -354,6 +354,49 @@ int ps_summary_reset(ps_summary* a);
 int ps_summary_prof(ps_summary* a, int enable, double* total_ms, int64_t* launches);
 void ps_summary_destroy(ps_summary* a);
 
+/* ---- linearised spread: delta-method maps around a point estimate ----
+ * The spread map of the normal approximation that Bayes_MAP.py:525 fits (pymc.NormApprox: MAP + the
+ * inverse Hessian of the joint log density); the reference reports only the parameter covariance.
+ * A handle lives on one device and holds nslot day slots of N x N cells (pitch = N*N rounded up to 64),
+ * all fp64: center[slot], J[param][slot] (per-cell sensitivities dU/dtheta_i), and after finalisation
+ * var[slot] and exc[k][slot].  Limits: nparam <= 16, nthr <= 4.  The whole block,
+ * (nparam + 2 + nthr) * nslot * pitch * 8 bytes, is checked against the free device memory first:
+ * PS_ERR_OOM before anything is allocated.  One thread owns a pair of cells: no atomics, the same calls
+ * in the same order give the same bits.  Every operation records an event that the next one waits on,
+ * on whatever stream it runs (the solver's for set_center / add, the handle's own otherwise). */
+typedef struct ps_linspread ps_linspread;
+/* thr[nthr] thresholds (exceedance P(U >= thr)) */
+int ps_linspread_create(int device, int N, int nslot, int nparam, int nthr, const double* thr, ps_linspread** out);
+/* center[slot i] = the value record (kind[i], idx[i]) of solver s holds at each cell, by the rule of
+ * ps_summary_add (what ps_record_fetch_* returns there, 0 where it returns no entry):
+ *   t = rec * stat_scale[i];  v = (t != 0 && !(t < negval)) ? (t + delta) * post_scale[i] : 0
+ * One launch on the solver's stream, no host synchronisation. */
+int ps_linspread_set_center(ps_linspread* h, ps_solver* s, int nslot, const int32_t* kind, const int32_t* idx,
+                            const double* stat_scale, const double* post_scale, const int32_t* use_delta,
+                            double negval);
+/* J[param][slot i] += coef * v (v as above) for every slot in one launch on the solver's stream; cell
+ * pairs whose values are both 0 are not stored.  A central difference over a stencil pair:
+ * add(i, +1/(2h), at theta + h e_i), add(i, -1/(2h), at theta - h e_i).  coef finite and non-zero. */
+int ps_linspread_add(ps_linspread* h, ps_solver* s, int param, double coef, int nslot, const int32_t* kind,
+                     const int32_t* idx, const double* stat_scale, const double* post_scale,
+                     const int32_t* use_delta, double negval);
+/* Sigma = F F' (F: nparam x rank, row-major, rank <= 16; nparam must equal the handle's).  Per cell
+ *   var = sum_k (sum_i F_ik J_i)^2   (never negative, unlike J' Sigma J with round-off)
+ *   exc_k = 0.5 erfc((thr_k - center) / (sqrt(var) sqrt 2)),  exactly (center >= thr_k) where var == 0.
+ * PS_ERR_STATE without a centre.  Any later set_center / add invalidates the result. */
+int ps_linspread_finalize(ps_linspread* h, int nparam, int rank, const double* F);
+/* one slot to the host (synchronises): what 0 centre, 1 variance, 2 + k exceedance k, 16 + i J_i.
+ * PS_ERR_STATE for the centre before set_center and for 1.. before finalize. */
+int ps_linspread_fetch(ps_linspread* h, int slot, int what, double* out /* N*N */);
+/* state: centre set, finalized, adds per parameter (adds[nparam]); any pointer may be NULL */
+int ps_linspread_info(ps_linspread* h, int* centered, int* finalized, int64_t* adds);
+int ps_linspread_reset(ps_linspread* h);
+/* measurement: HIP-event timing of the add and finalize launches (not set_center).  enable 1 on, 0 off,
+ * < 0 unchanged; the totals so far go to the non-NULL outputs (synchronises). */
+int ps_linspread_prof(ps_linspread* h, int enable, double* add_ms, int64_t* add_launches, double* fin_ms,
+                      int64_t* fin_launches);
+void ps_linspread_destroy(ps_linspread* h);
+
 #ifdef __cplusplus
 }
 #endif

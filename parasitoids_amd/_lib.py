@@ -126,6 +126,16 @@ SIGNATURES = {
     'ps_summary_reset': (C.c_int, [_VP]),
     'ps_summary_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P]),
     'ps_summary_destroy': (None, [_VP]),
+    'ps_linspread_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F64P, C.POINTER(_VP)]),
+    'ps_linspread_set_center': (C.c_int, [_VP, _VP, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P, C.c_double]),
+    'ps_linspread_add': (C.c_int, [_VP, _VP, C.c_int, C.c_double, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P,
+                                   C.c_double]),
+    'ps_linspread_finalize': (C.c_int, [_VP, C.c_int, C.c_int, _F64P]),
+    'ps_linspread_fetch': (C.c_int, [_VP, C.c_int, C.c_int, _F64P]),
+    'ps_linspread_info': (C.c_int, [_VP, _I32P, _I32P, _I64P]),
+    'ps_linspread_reset': (C.c_int, [_VP]),
+    'ps_linspread_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P, _F64P, _I64P]),
+    'ps_linspread_destroy': (None, [_VP]),
 }
 
 _lib = None

@@ -123,3 +123,11 @@ struct PsRecordView {
   int N, device;
 };
 int ps_solver_record_internal(ps_solver* s, int kind, int idx, int want_stats, PsRecordView* out);
+
+// the value one solver record holds at a cell, as ps_record_fetch_* returns it (k_compact_rows,
+// chain_kernels.h), 0 where it returns no entry; shared by ps_summary.hip and ps_linspread.hip
+__device__ inline double ps_record_value(double r, double stat_scale, double post_scale, double delta, double negval) {
+  const double t = r * stat_scale;
+  const bool keep = (t != 0.0) && !(t < negval);
+  return keep ? (t + delta) * post_scale : 0.0;
+}

@@ -26,13 +26,6 @@ struct SumThr {
   double t[PS_SUM_MAX_THR];
 };
 
-// what ps_record_fetch_* holds at the cell (k_compact_rows, chain_kernels.h), 0 where it holds nothing
-__device__ inline double sum_value(double r, double stat_scale, double post_scale, double delta, double negval) {
-  const double t = r * stat_scale;
-  const bool keep = (t != 0.0) && !(t < negval);
-  return keep ? (t + delta) * post_scale : 0.0;
-}
-
 __device__ inline bool sum_update(double v, double w, double Wn, double& m, double& m2) {
   const double d = v - m;
   if (d == 0.0) return false;          // mean and M2 stay bit for bit as they are
@@ -57,8 +50,8 @@ __global__ void k_summary_add(SumSlots desc, double* __restrict__ mean, double* 
       const double2 r = *reinterpret_cast<const double2*>(rec + 2 * j);
       double2 m = *reinterpret_cast<const double2*>(ms + 2 * j);
       double2 q = *reinterpret_cast<const double2*>(qs + 2 * j);
-      const double v0 = sum_value(r.x, sd.stat_scale, sd.post_scale, delta, negval);
-      const double v1 = sum_value(r.y, sd.stat_scale, sd.post_scale, delta, negval);
+      const double v0 = ps_record_value(r.x, sd.stat_scale, sd.post_scale, delta, negval);
+      const double v1 = ps_record_value(r.y, sd.stat_scale, sd.post_scale, delta, negval);
       const bool c0 = sum_update(v0, w, Wn, m.x, q.x);
       const bool c1 = sum_update(v1, w, Wn, m.y, q.y);
       if (c0 || c1) {
@@ -77,7 +70,7 @@ __global__ void k_summary_add(SumSlots desc, double* __restrict__ mean, double* 
       }
     } else if (ncell & 1) {
       const int64_t i = ncell - 1;
-      const double v = sum_value(rec[i], sd.stat_scale, sd.post_scale, delta, negval);
+      const double v = ps_record_value(rec[i], sd.stat_scale, sd.post_scale, delta, negval);
       double m = ms[i], q = qs[i];
       if (sum_update(v, w, Wn, m, q)) {
         ms[i] = m;

@@ -225,6 +225,40 @@ def observation_predictive(rates, locinfo, seed=0):
     return out
 
 
+# ------------------------------------------------------------------ result files
+def save_maps(outfile, maps):
+    '''outfile.npz in the layout of Run.save_result (Run.py:490-516 of the reference), which
+    Plot_Result.main reads.  maps: [(day label, [(suffix, N x N array), ...]), ...] -> per day and
+    suffix the CSR triplet `{label}{suffix}_data/_ind/_indptr` of the array thresholded at 1e-8,
+    and `days` = the labels.  The directory is created if needed.'''
+    from scipy import sparse
+    out = {}
+    labels = []
+    for label, day_maps in maps:
+        labels.append(label)
+        for suffix, m in day_maps:
+            csr = sparse.csr_matrix(np.where(m >= NEGVAL, m, 0.0))
+            out['%s%s_data' % (label, suffix)] = csr.data
+            out['%s%s_ind' % (label, suffix)] = csr.indices
+            out['%s%s_indptr' % (label, suffix)] = csr.indptr
+    out['days'] = np.array(labels)
+    d = os.path.dirname(str(outfile))
+    if d and not os.path.exists(d):
+        os.makedirs(d)
+    np.savez(str(outfile), **out)
+
+
+def params_dict(params):
+    '''the run parameters of a result file: None, a dict or a Run.Params-like object'''
+    if params is None:
+        return {}
+    if isinstance(params, dict):
+        return dict(params)
+    pdict = dict(params.__dict__)
+    pdict.pop('maps_key', None)
+    return pdict
+
+
 # ------------------------------------------------------------------ driver
 class PredictiveResult():
     '''What posterior_predictive returns: `summary` (a SpreadSummary, None without a device),
@@ -248,34 +282,17 @@ class PredictiveResult():
         Plot_Result.main reads: per day `{day}_data/_ind/_indptr` of the posterior mean thresholded at
         1e-8, `days`; besides `{day}_sd_*` and `{day}_pexc{k}_*` CSR triplets.  outfile.json: the
         params, the thresholds, the chain provenance.  -> (npz path, json path)'''
-        from scipy import sparse
         s = self.summary
         if s is None:
             raise ValueError('no spread summary to save (evaluate= runs without a device)')
-        out = {}
-        labels = []
+        maps = []
         for d in s.days:
             label = s.pm.days[d] if d < len(s.pm.days) else d
-            labels.append(label)
-            maps = [('', s.mean(d)), ('_sd', s.sd(d))]
-            maps += [('_pexc%d' % k, s.exceedance(d, k)) for k in range(len(s.thresholds))]
-            for suffix, m in maps:
-                csr = sparse.csr_matrix(np.where(m >= NEGVAL, m, 0.0))
-                out['%s%s_data' % (label, suffix)] = csr.data
-                out['%s%s_ind' % (label, suffix)] = csr.indices
-                out['%s%s_indptr' % (label, suffix)] = csr.indptr
-        out['days'] = np.array(labels)
-        d = os.path.dirname(str(outfile))
-        if d and not os.path.exists(d):
-            os.makedirs(d)
-        np.savez(str(outfile), **out)
-        if params is None:
-            pdict = {}
-        elif isinstance(params, dict):
-            pdict = dict(params)
-        else:
-            pdict = dict(params.__dict__)
-            pdict.pop('maps_key', None)
+            day_maps = [('', s.mean(d)), ('_sd', s.sd(d))]
+            day_maps += [('_pexc%d' % k, s.exceedance(d, k)) for k in range(len(s.thresholds))]
+            maps.append((label, day_maps))
+        save_maps(outfile, maps)
+        pdict = params_dict(params)
         meta = dict(pdict)
         meta['predictive'] = {'thresholds': s.thresholds, 'total_weight': s.total_weight, 'members': s.members,
                               'rows': self.rows, 'evaluations': self.evaluations, 'failed': self.failed,
