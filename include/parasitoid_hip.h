@@ -397,6 +397,45 @@ int ps_linspread_prof(ps_linspread* h, int enable, double* add_ms, int64_t* add_
                       int64_t* fin_launches);
 void ps_linspread_destroy(ps_linspread* h);
 
+/* ---- posterior predictive histograms: per-cell weighted distributions on fixed bin edges ----
+ * (no reference counterpart).  A histogram lives on one device and holds nslot day slots of N x N cells
+ * and a strictly increasing edge table e_0 < ... < e_B (2 <= nedge = B + 1 <= 1024, every edge finite
+ * and > 0), uploaded once.  Bin b = searchsorted(edges, v, side='right'): bin 0 holds v < e_0 (zeros
+ * included), bin b in 1..B holds e_{b-1} <= v < e_b, bin B + 1 holds v >= e_B.  Per slot uint32 count
+ * planes [b = 1 .. B+1][pitch] (bin-major; bin 0 is W - the rest, never stored) and one word per cell with
+ * its lowest and highest touched bin, so that quantiles and exceedances read only those planes.  The
+ * full size, nslot * pitch * (nedge + 1) * 4 B, is checked against the free device memory first:
+ * PS_ERR_OOM before anything is allocated.  Host side: W (< 2^32) and the member count.  Counts are
+ * integers and one thread owns a pair of cells: no atomics, and neither the order of adds nor that of
+ * merges changes a bit.  Every operation records an event the next one waits on, whichever stream it
+ * runs on (the solver's for add, the handle's own otherwise). */
+typedef struct ps_hist ps_hist;
+int ps_hist_create(int device, int N, int nslot, int nedge, const double* edges, ps_hist** out);
+/* count_b(v) += weight for every slot and cell, v by the rule of ps_summary_add (same arguments, same
+ * value bit for bit).  One launch on the solver's stream, no host synchronisation. */
+int ps_hist_add(ps_hist* h, ps_solver* s, int nslot, const int32_t* kind, const int32_t* idx,
+                const double* stat_scale, const double* post_scale, const int32_t* use_delta, double negval,
+                uint32_t weight);
+/* dst += src (counts add), same device, N, slots and edges; src stays as it is */
+int ps_hist_merge(ps_hist* dst, ps_hist* src);
+int ps_hist_info(ps_hist* h, double* total_weight, int64_t* members, int* nedge);
+/* One slot's quantile at p in (0, 1] (synchronises; any output may be NULL).  C_b = the weight through
+ * bin b, b* = the smallest b with (double)C_b >= p * (double)W.  lower / upper: the bracket
+ * [e_{b*-1}, e_{b*}) that holds the exact weighted lower quantile, [0, e_0) at b* = 0, [e_B, inf) at
+ * b* = B + 1.  value: e_{b*-1} * (e_{b*} / e_{b*-1})^f with f = (p W - C_{b*-1}) / count_{b*} for
+ * 1 <= b* <= B, 0 at b* = 0, e_B at b* = B + 1.  PS_ERR_STATE at W = 0. */
+int ps_hist_quantile(ps_hist* h, int slot, double p, double* value, double* lower, double* upper);
+/* P(v >= e_k) = (W - C_k) / W per cell, exact (synchronises).  PS_ERR_STATE at W = 0. */
+int ps_hist_exceed(ps_hist* h, int slot, int k, double* out /* N*N */);
+/* count of bin b (0 .. B + 1) per cell; bin 0 derived as W - the rest (synchronises) */
+int ps_hist_fetch_counts(ps_hist* h, int slot, int b, uint32_t* out /* N*N */);
+int ps_hist_reset(ps_hist* h);
+/* measurement: HIP-event timing of the add and quantile launches.  enable 1 on, 0 off, < 0 unchanged;
+ * the totals so far go to the non-NULL outputs (synchronises). */
+int ps_hist_prof(ps_hist* h, int enable, double* add_ms, int64_t* add_launches, double* q_ms,
+                 int64_t* q_launches);
+void ps_hist_destroy(ps_hist* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -136,6 +136,16 @@ SIGNATURES = {
     'ps_linspread_reset': (C.c_int, [_VP]),
     'ps_linspread_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P, _F64P, _I64P]),
     'ps_linspread_destroy': (None, [_VP]),
+    'ps_hist_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _F64P, C.POINTER(_VP)]),
+    'ps_hist_add': (C.c_int, [_VP, _VP, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P, C.c_double, C.c_uint32]),
+    'ps_hist_merge': (C.c_int, [_VP, _VP]),
+    'ps_hist_info': (C.c_int, [_VP, _F64P, _I64P, _I32P]),
+    'ps_hist_quantile': (C.c_int, [_VP, C.c_int, C.c_double, _F64P, _F64P, _F64P]),
+    'ps_hist_exceed': (C.c_int, [_VP, C.c_int, C.c_int, _F64P]),
+    'ps_hist_fetch_counts': (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(C.c_uint32)]),
+    'ps_hist_reset': (C.c_int, [_VP]),
+    'ps_hist_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P, _F64P, _I64P]),
+    'ps_hist_destroy': (None, [_VP]),
 }
 
 _lib = None

@@ -7,6 +7,9 @@ the value added for a cell is exactly what `PopModel.population(day)` holds ther
 nothing.  `posterior_predictive` feeds it from `mcmc.Sampler.save` chains -- one evaluation per run of
 identical model parameters, weighted by the run's length -- and, given the site's observations,
 draws replicated observations from the reference's Poisson model (Bayes_Run.py:344-433).
+`SpreadHistogram` keeps, on the device, the per-cell weighted distribution of the same values on fixed
+bin edges (ps_hist_*, csrc/ps_hist.hip): quantile maps with their exact brackets, and exceedance at any
+bin edge chosen after the run.
 """
 import ctypes as C
 import json
@@ -20,6 +23,28 @@ from . import _lib as L
 from . import mcmc
 
 NEGVAL = 1e-8          # r_small_vals threshold of the daily solutions (CalcSol.py:126-132)
+DEFAULT_BINS = (1e-8, 1e6, 16)   # NEGVAL .. above any r_number, 16 bins per decade: 225 edges
+MAX_EDGES = 1024
+
+
+def _day_slots(days):
+    '''record (kind, idx, use_delta) of every model day: day 0 the state, day d chain record d - 1'''
+    kind = L.i32([L.REC_STATE if d == 0 else L.REC_CHAIN for d in days])
+    idx = L.i32([0 if d == 0 else d - 1 for d in days])
+    delta = L.i32([0 if d == 0 else 1 for d in days])
+    return kind, idx, delta
+
+
+def _day_scales(pm, days):
+    '''(stat_scale, post_scale) per day: what PopModel.population applies to each record'''
+    r = float(pm.r_number)
+    return L.f64([1.0 if d == 0 else r for d in days]), L.f64([r if d == 0 else 1.0 for d in days])
+
+
+def _check_evaluated(pm, days, what):
+    nd = getattr(pm, '_nd', 0)
+    if pm.solver is None or max(days) >= nd:
+        raise ValueError('the last evaluation has %d days; the %s needs day %d' % (nd, what, max(days)))
 
 
 class SpreadSummary():
@@ -41,9 +66,7 @@ class SpreadSummary():
         L.check(self._lib.ps_summary_create(self.device, self.N, len(self.days), len(self.thresholds),
                                             L.p_f64(thr), C.byref(self._h)))
         n = len(self.days)
-        self._kind = L.i32([L.REC_STATE if d == 0 else L.REC_CHAIN for d in self.days])
-        self._idx = L.i32([0 if d == 0 else d - 1 for d in self.days])
-        self._delta = L.i32([0 if d == 0 else 1 for d in self.days])
+        self._kind, self._idx, self._delta = _day_slots(self.days)
         self._slot = {d: i for i, d in enumerate(self.days)}
         self._n = n
 
@@ -51,12 +74,8 @@ class SpreadSummary():
         '''Accumulate the last evaluation of the model with integer weight >= 1 (enqueued on the
         solver's stream; no host synchronisation).'''
         pm = self.pm
-        nd = getattr(pm, '_nd', 0)
-        if pm.solver is None or max(self.days) >= nd:
-            raise ValueError('the last evaluation has %d days; the summary needs day %d' % (nd, max(self.days)))
-        r = float(pm.r_number)
-        stat = L.f64([1.0 if d == 0 else r for d in self.days])
-        post = L.f64([r if d == 0 else 1.0 for d in self.days])
+        _check_evaluated(pm, self.days, 'summary')
+        stat, post = _day_scales(pm, self.days)
         w = int(weight)
         if w < 1:
             raise ValueError('weight must be a positive integer')
@@ -123,6 +142,179 @@ class SpreadSummary():
     def close(self):
         if self._h:
             self._lib.ps_summary_destroy(self._h)
+            self._h = L._VP()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def bin_edges(bins=DEFAULT_BINS, edges=None):
+    '''The histogram's edge table e_0 < ... < e_B (float64, 2..1024 edges, every edge finite and > 0).
+    edges: an explicit table; else bins = (lo, hi, per_decade):
+    B = int(round(per_decade * log10(hi / lo))), edges = lo * 10 ** (arange(B + 1) / per_decade).'''
+    if edges is None:
+        try:
+            lo, hi, per = bins
+        except (TypeError, ValueError):
+            raise ValueError('bins must be (lo, hi, per_decade), got %r' % (bins,))
+        if not (np.isfinite(lo) and lo > 0):
+            raise ValueError('bins: lo = %r must be finite and > 0' % (lo,))
+        if not (np.isfinite(hi) and hi > lo):
+            raise ValueError('bins: hi = %r must be finite and > lo = %r' % (hi, lo))
+        if not (np.isfinite(per) and per >= 1):
+            raise ValueError('bins: per_decade = %r must be >= 1' % (per,))
+        B = int(round(per * np.log10(hi / lo)))
+        if B + 1 > MAX_EDGES:
+            raise ValueError('bins %r give %d edges, at most %d' % (tuple(bins), B + 1, MAX_EDGES))
+        edges = lo * 10.0 ** (np.arange(B + 1) / per)
+    e = np.array(edges, dtype=np.float64).ravel()
+    if not 2 <= e.size <= MAX_EDGES:
+        raise ValueError('%d edges; a histogram needs 2..%d' % (e.size, MAX_EDGES))
+    if not np.all(np.isfinite(e)) or not np.all(e > 0):
+        raise ValueError('every edge must be finite and > 0')
+    if not np.all(np.diff(e) > 0):
+        raise ValueError('edges must be strictly increasing')
+    return e
+
+
+def check_levels(quantiles):
+    '''quantile levels as a list of floats, each in (0, 1]; ValueError otherwise'''
+    levels = [float(p) for p in quantiles]
+    bad = [p for p in levels if not 0.0 < p <= 1.0]
+    if bad:
+        raise ValueError('quantile levels must lie in (0, 1]: %r' % (bad,))
+    return levels
+
+
+def quantile_tag(p):
+    '''the key suffix of level p: 0.05 -> q5, 0.5 -> q50, 0.025 -> q2p5'''
+    return 'q' + ('%g' % (100 * p)).replace('.', 'p')
+
+
+class SpreadHistogram():
+    '''Weighted per-cell histograms of `pop_model`'s days over the members added, on fixed bin edges
+    (`bin_edges(bins, edges)`).  days: model days to keep, default all.  The value of a cell is the one
+    SpreadSummary adds; bin b = searchsorted(edges, v, side='right'), b = 0 .. B + 1.'''
+
+    def __init__(self, pop_model, days=None, bins=DEFAULT_BINS, edges=None):
+        self._lib = L.load()
+        self._h = L._VP()
+        self.pm = pop_model
+        self.days = list(range(len(pop_model.days)) if days is None else days)
+        if not self.days or min(self.days) < 0:
+            raise ValueError('days must be a non-empty list of model days >= 0')
+        self._edges = bin_edges(bins, edges)
+        self.bins = None if edges is not None else tuple(float(b) for b in bins)
+        self.N = 2 * int(pop_model.rad_res) + 1
+        self.device = L.default_device() if pop_model.device is None else int(pop_model.device)
+        pitch = (self.N * self.N + 63) // 64 * 64
+        self.nbytes = len(self.days) * pitch * (self._edges.size + 1) * 4   # count planes + range words
+        L.check(self._lib.ps_hist_create(self.device, self.N, len(self.days), self._edges.size,
+                                         L.p_f64(self._edges), C.byref(self._h)))
+        self._kind, self._idx, self._delta = _day_slots(self.days)
+        self._slot = {d: i for i, d in enumerate(self.days)}
+
+    @property
+    def edges(self):
+        return self._edges.copy()
+
+    def add(self, weight=1):
+        '''Accumulate the last evaluation of the model with integer weight >= 1 (enqueued on the
+        solver's stream; no host synchronisation).'''
+        pm = self.pm
+        _check_evaluated(pm, self.days, 'histogram')
+        stat, post = _day_scales(pm, self.days)
+        w = int(weight)
+        if w < 1:
+            raise ValueError('weight must be a positive integer')
+        L.check(self._lib.ps_hist_add(self._h, pm.solver._h, len(self.days), L.p_i32(self._kind),
+                                      L.p_i32(self._idx), L.p_f64(stat), L.p_f64(post), L.p_i32(self._delta),
+                                      NEGVAL, w))
+
+    def merge(self, other):
+        '''self += other (same device, domain, days and edges)'''
+        if list(other.days) != self.days:
+            raise ValueError('histograms over different days')
+        L.check(self._lib.ps_hist_merge(self._h, other._h))
+
+    def reset(self):
+        L.check(self._lib.ps_hist_reset(self._h))
+
+    def _info(self):
+        w, m, n = C.c_double(), C.c_int64(), C.c_int32()
+        L.check(self._lib.ps_hist_info(self._h, C.byref(w), C.byref(m), C.byref(n)))
+        return w.value, m.value
+
+    @property
+    def total_weight(self):
+        return self._info()[0]
+
+    @property
+    def members(self):
+        return self._info()[1]
+
+    def _slot_of(self, day):
+        if day not in self._slot:
+            raise ValueError('day %r is not in the histogram %s' % (day, self.days))
+        return self._slot[day]
+
+    def counts(self, day):
+        '''[B + 2, N, N] uint32: the weight of every bin per cell, bin 0 = W - the others'''
+        s = self._slot_of(day)
+        out = np.empty((self._edges.size + 1, self.N, self.N), dtype=np.uint32)
+        for b in range(out.shape[0]):
+            L.check(self._lib.ps_hist_fetch_counts(self._h, s, b, out[b].ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def _quantile(self, day, p, value, lower, upper):
+        s = self._slot_of(day)
+        if not 0.0 < float(p) <= 1.0:
+            raise ValueError('quantile level %r is not in (0, 1]' % (p,))
+        ptr = [None if a is None else L.p_f64(a) for a in (value, lower, upper)]
+        L.check(self._lib.ps_hist_quantile(self._h, s, float(p), *ptr))
+
+    def quantile(self, day, p):
+        '''N x N point map of the weighted lower quantile at level p (log-interpolated inside its bin)'''
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        self._quantile(day, p, out, None, None)
+        return out
+
+    def quantile_bounds(self, day, p):
+        '''(lower, upper): the bin [lower, upper) that holds the exact weighted quantile at level p'''
+        lo = np.empty((self.N, self.N), dtype=np.float64)
+        hi = np.empty((self.N, self.N), dtype=np.float64)
+        self._quantile(day, p, None, lo, hi)
+        return lo, hi
+
+    def exceedance(self, day, t):
+        '''P(population >= t) per cell, exact; t must be one of the edges (ValueError otherwise)'''
+        k = np.flatnonzero(self._edges == float(t))
+        if k.size != 1:
+            raise ValueError('threshold %r is not a bin edge; exceedance is exact only at the edges' % (t,))
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        L.check(self._lib.ps_hist_exceed(self._h, self._slot_of(day), int(k[0]), L.p_f64(out)))
+        return out
+
+    def profile(self, enable=None):
+        '''HIP-event time of the add and quantile launches: (add ms, adds, quantile ms, quantile
+        launches); enable switches it'''
+        am, an, qm, qn = C.c_double(), C.c_int64(), C.c_double(), C.c_int64()
+        L.check(self._lib.ps_hist_prof(self._h, -1 if enable is None else int(bool(enable)), C.byref(am),
+                                       C.byref(an), C.byref(qm), C.byref(qn)))
+        return am.value, an.value, qm.value, qn.value
+
+    def close(self):
+        if self._h:
+            self._lib.ps_hist_destroy(self._h)
             self._h = L._VP()
 
     def __enter__(self):
@@ -264,10 +456,14 @@ class PredictiveResult():
     '''What posterior_predictive returns: `summary` (a SpreadSummary, None without a device),
     `rows` (trace rows after burn / thin), `evaluations`, `failed`, `seconds`, `runs`
     ([(chain, first_row, weight)] of every evaluated run), `observations` (observation_predictive
-    or None) and `provenance`.'''
+    or None) and `provenance`; with quantile levels `histogram` (a SpreadHistogram, None without a
+    device) and `quantiles` (the levels), else both None.'''
 
-    def __init__(self, summary, rows, evaluations, failed, seconds, runs, observations, provenance, days):
+    def __init__(self, summary, rows, evaluations, failed, seconds, runs, observations, provenance, days,
+                 histogram=None, quantiles=None):
         self.summary = summary
+        self.histogram = histogram
+        self.quantiles = quantiles
         self.rows = rows
         self.evaluations = evaluations
         self.failed = failed
@@ -280,16 +476,21 @@ class PredictiveResult():
     def save(self, outfile, params=None):
         '''outfile.npz in the layout of Run.save_result (Run.py:490-516 of the reference), which
         Plot_Result.main reads: per day `{day}_data/_ind/_indptr` of the posterior mean thresholded at
-        1e-8, `days`; besides `{day}_sd_*` and `{day}_pexc{k}_*` CSR triplets.  outfile.json: the
-        params, the thresholds, the chain provenance.  -> (npz path, json path)'''
+        1e-8, `days`; besides `{day}_sd_*` and `{day}_pexc{k}_*` CSR triplets, and with a histogram
+        `{day}_q{tag}_*` of the quantile point maps (quantile_tag: q5, q50, q95, q2p5).  outfile.json: the
+        params, the thresholds, the chain provenance, with a histogram the quantile levels and the edge
+        definition.  -> (npz path, json path)'''
         s = self.summary
         if s is None:
             raise ValueError('no spread summary to save (evaluate= runs without a device)')
+        h = self.histogram
+        levels = list(self.quantiles or ()) if h is not None else []
         maps = []
         for d in s.days:
             label = s.pm.days[d] if d < len(s.pm.days) else d
             day_maps = [('', s.mean(d)), ('_sd', s.sd(d))]
             day_maps += [('_pexc%d' % k, s.exceedance(d, k)) for k in range(len(s.thresholds))]
+            day_maps += [('_' + quantile_tag(p), h.quantile(d, p)) for p in levels]
             maps.append((label, day_maps))
         save_maps(outfile, maps)
         pdict = params_dict(params)
@@ -297,13 +498,18 @@ class PredictiveResult():
         meta['predictive'] = {'thresholds': s.thresholds, 'total_weight': s.total_weight, 'members': s.members,
                               'rows': self.rows, 'evaluations': self.evaluations, 'failed': self.failed,
                               'chains': self.provenance}
+        if h is not None:
+            meta['predictive']['quantiles'] = {'levels': levels, 'bins': None if h.bins is None else list(h.bins),
+                                               'edges': None if h.bins is not None else [float(e) for e in h.edges],
+                                               'nedge': int(h.edges.size)}
         with open(str(outfile) + '.json', 'w') as fobj:
             json.dump(meta, fobj, default=str)
         return str(outfile) + '.npz', str(outfile) + '.json'
 
 
-def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, locinfo):
-    '''one chain: evaluate every run, add it to the summary -> (expected per run or None, failed)'''
+def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, locinfo, histogram=None):
+    '''one chain: evaluate every run, add it to the summary (and the histogram) -> (expected per run or
+    None, failed)'''
     expected = []
     failed = 0
     for first, length in run_list:
@@ -327,20 +533,27 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
             expected.append(None)
             continue
         summary.add(length)
+        if histogram is not None:
+            histogram.add(length)
         expected.append(mcmc.expected_observations(pm, locinfo) if want_obs else True)
     return expected, failed
 
 
 def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, thresholds=(), locinfo=None,
-                         cell_area=None, seed=0, evaluate=None):
+                         cell_area=None, seed=0, evaluate=None, quantiles=None, bins=DEFAULT_BINS, edges=None):
     '''Posterior predictive spread of one or more chains (`Sampler.save` files or (trace, names)
     pairs).  Burn and thin apply per chain; consecutive rows with identical model parameters are one
     evaluation weighted by the run's length.  pop_model: one PopModel or a list -- with several, one
     host thread per model runs its chains, each chain into its own summary, and the summaries are
     merged in chain order (the result does not depend on the interleaving).  locinfo: observations
     for the observation-level predictive (every row: the rates of its run's evaluation with its own
-    nuisance parameters).  evaluate(theta) -> expected observations or None: no device, no summary.'''
+    nuisance parameters).  evaluate(theta) -> expected observations or None: no device, no summary.
+    quantiles: levels in (0, 1]; each chain then also fills a SpreadHistogram (bins / edges as
+    bin_edges) with the same weights, merged in chain order into `histogram`.'''
     t0 = time.perf_counter()
+    levels = (check_levels(quantiles) if quantiles is not None else []) or None
+    if levels:
+        bin_edges(bins, edges)        # a bad edge definition fails before any evaluation
     if isinstance(chains, (str, os.PathLike)) or (isinstance(chains, tuple) and len(chains) == 2
                                                    and not isinstance(chains[0], (str, os.PathLike, tuple))):
         chains = [chains]
@@ -361,6 +574,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         raise ValueError('a PopModel is needed without evaluate=')
     nch = len(prepared)
     summaries = [None] * nch
+    histograms = [None] * nch
     results = [None] * nch
     errs = []
 
@@ -371,7 +585,9 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                 rows, rl, mcols, _o, _s = prepared[ci]
                 summ = SpreadSummary(pm, days, thresholds) if evaluate is None else None
                 summaries[ci] = summ
-                results[ci] = _evaluate_runs(pm, summ, rows, rl, mcols, evaluate, want_obs, locinfo)
+                hist = SpreadHistogram(pm, days, bins, edges) if evaluate is None and levels else None
+                histograms[ci] = hist
+                results[ci] = _evaluate_runs(pm, summ, rows, rl, mcols, evaluate, want_obs, locinfo, hist)
         except BaseException as e:       # re-raised in the caller's thread
             errs.append((p, e))
 
@@ -386,16 +602,22 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         pms = pms[:1]
         work(0)
     if errs:
-        for s in summaries:
+        for s in summaries + histograms:
             if s is not None:
                 s.close()
         raise errs[0][1]
     summary = None
+    histogram = None
     if evaluate is None:
         summary = summaries[0]
         for s in summaries[1:]:
             summary.merge(s)
             s.close()
+        if levels:
+            histogram = histograms[0]
+            for h in histograms[1:]:
+                histogram.merge(h)
+                h.close()
     evaluations = sum(len(p[1]) for p in prepared)
     failed = sum(r[1] for r in results)
     run_rec = [(ci, first, length) for ci, p in enumerate(prepared)
@@ -415,7 +637,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
             for p in prepared]
     res = PredictiveResult(summary, int(sum(len(p[0]) for p in prepared)), evaluations, failed,
                            time.perf_counter() - t0, run_rec, observations, prov,
-                           None if summary is None else summary.days)
+                           None if summary is None else summary.days, histogram, levels)
     if cell_area is not None:
         res.cell_area = float(cell_area)
     return res
