@@ -436,6 +436,48 @@ int ps_hist_prof(ps_hist* h, int enable, double* add_ms, int64_t* add_launches, 
                  int64_t* q_launches);
 void ps_hist_destroy(ps_hist* h);
 
+/* ---- posterior arrival maps: when the members reach each cell, and the area they reach ----
+ * (no reference counterpart).  A handle lives on one device and holds nslot day slots (1..32) of N x N
+ * cells and 1..4 strictly increasing thresholds t_0 < ... < t_{K-1}, each finite and > 0.  For one member,
+ * v_s(c) is the value ps_summary_add adds for slot s (same arguments, same value bit for bit), and the
+ * arrival slot is a_k(c) = min{s : v_s(c) >= t_k}, nslot ("never") if no slot qualifies.  Per threshold
+ * and slot uint32 count planes cnt[k][s][pitch] (pitch as ps_summary): the weight of the members with
+ * a_k(c) = s; "never" is W - the rest, not stored.  Per member, in add order, its reached cells
+ * n_k(s) = #{c : a_k(c) <= s} and its weight; a merge appends src's members after dst's.  The whole count
+ * block, nthr * nslot * pitch * 4 B plus scratch, is checked against the free device memory first:
+ * PS_ERR_OOM before anything is allocated.  Host side: W (< 2^32) and the member count.  Counts are
+ * integers and every cell has one writer: neither the order of adds, nor that of merges, nor the launch
+ * configuration changes a bit.  Every operation records an event the next one waits on, whichever stream
+ * it runs on (the solver's for add, the handle's own otherwise). */
+typedef struct ps_arrival ps_arrival;
+int ps_arrival_create(int device, int N, int nslot, int nthr, const double* thr, ps_arrival** out);
+/* One member with weight >= 1 (arguments as ps_hist_add): one launch walks the slots of every cell pair in
+ * order, a second small one sums the member's n_k(s), both on the solver's stream, no host synchronisation
+ * (except once when the member rows double their capacity). */
+int ps_arrival_add(ps_arrival* a, ps_solver* s, int nslot, const int32_t* kind, const int32_t* idx,
+                   const double* stat_scale, const double* post_scale, const int32_t* use_delta, double negval,
+                   uint32_t weight);
+/* dst += src (counts add, src's member rows appended), same device, N, slots and thresholds; src unchanged */
+int ps_arrival_merge(ps_arrival* dst, ps_arrival* src);
+int ps_arrival_info(ps_arrival* a, double* total_weight, int64_t* members);
+/* P(arrived by slot) = C_k[slot] / W per cell, C_k[s] = sum over s' <= s of the counts (synchronises).
+ * PS_ERR_STATE at W = 0. */
+int ps_arrival_prob(ps_arrival* a, int k, int slot, double* out /* N*N */);
+/* the smallest slot s with (double)C_k[s] >= p * (double)W per cell, -1 where even the last slot falls
+ * short; p in (0, 1] (synchronises).  PS_ERR_STATE at W = 0. */
+int ps_arrival_quantile(ps_arrival* a, int k, double p, int32_t* out /* N*N */);
+/* count plane of threshold k and slot 0 .. nslot; slot == nslot: never, W - the rest (synchronises) */
+int ps_arrival_fetch_counts(ps_arrival* a, int k, int slot, uint32_t* out /* N*N */);
+/* members first .. first + count - 1: cells[count][nthr][nslot] = n_k(s), weights[count] (either may be NULL;
+ * synchronises) */
+int ps_arrival_fetch_reached(ps_arrival* a, int64_t first, int64_t count, uint32_t* cells, uint32_t* weights);
+int ps_arrival_reset(ps_arrival* a);
+/* measurement: HIP-event timing of the add launches (both kernels) and of the map launches (prob, quantile,
+ * never counts).  enable 1 on, 0 off, < 0 unchanged; the totals so far go to the non-NULL outputs
+ * (synchronises). */
+int ps_arrival_prof(ps_arrival* a, int enable, double* add_ms, int64_t* adds, double* map_ms, int64_t* maps);
+void ps_arrival_destroy(ps_arrival* a);
+
 #ifdef __cplusplus
 }
 #endif

@@ -146,6 +146,18 @@ SIGNATURES = {
     'ps_hist_reset': (C.c_int, [_VP]),
     'ps_hist_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P, _F64P, _I64P]),
     'ps_hist_destroy': (None, [_VP]),
+    'ps_arrival_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _F64P, C.POINTER(_VP)]),
+    'ps_arrival_add': (C.c_int, [_VP, _VP, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P, C.c_double, C.c_uint32]),
+    'ps_arrival_merge': (C.c_int, [_VP, _VP]),
+    'ps_arrival_info': (C.c_int, [_VP, _F64P, _I64P]),
+    'ps_arrival_prob': (C.c_int, [_VP, C.c_int, C.c_int, _F64P]),
+    'ps_arrival_quantile': (C.c_int, [_VP, C.c_int, C.c_double, _I32P]),
+    'ps_arrival_fetch_counts': (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(C.c_uint32)]),
+    'ps_arrival_fetch_reached': (C.c_int, [_VP, C.c_int64, C.c_int64, C.POINTER(C.c_uint32),
+                                           C.POINTER(C.c_uint32)]),
+    'ps_arrival_reset': (C.c_int, [_VP]),
+    'ps_arrival_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P, _F64P, _I64P]),
+    'ps_arrival_destroy': (None, [_VP]),
 }
 
 _lib = None

@@ -9,7 +9,10 @@ identical model parameters, weighted by the run's length -- and, given the site'
 draws replicated observations from the reference's Poisson model (Bayes_Run.py:344-433).
 `SpreadHistogram` keeps, on the device, the per-cell weighted distribution of the same values on fixed
 bin edges (ps_hist_*, csrc/ps_hist.hip): quantile maps with their exact brackets, and exceedance at any
-bin edge chosen after the run.
+bin edge chosen after the run.  `ArrivalMaps` keeps, on the device, per threshold and cell the weighted
+distribution of the first listed day on which a member's value reaches the threshold, and per member the
+number of cells reached by each day (ps_arrival_*, csrc/ps_arrival.hip): arrival probabilities and
+arrival-day quantile maps, and the posterior of the reached area.
 """
 import ctypes as C
 import json
@@ -25,6 +28,8 @@ from . import mcmc
 NEGVAL = 1e-8          # r_small_vals threshold of the daily solutions (CalcSol.py:126-132)
 DEFAULT_BINS = (1e-8, 1e6, 16)   # NEGVAL .. above any r_number, 16 bins per decade: 225 edges
 MAX_EDGES = 1024
+MAX_ARRIVAL_SLOTS = 32     # ps_arrival: the day slots of one launch's descriptors
+MAX_ARRIVAL_THRESHOLDS = 4
 
 
 def _day_slots(days):
@@ -330,6 +335,193 @@ class SpreadHistogram():
             pass
 
 
+def check_arrival_thresholds(thresholds):
+    '''arrival thresholds as a list of floats: 1..4 of them, each finite and > 0, strictly increasing;
+    ValueError otherwise'''
+    try:
+        thr = [float(t) for t in thresholds]
+    except (TypeError, ValueError):
+        raise ValueError('arrival thresholds must be numbers, got %r' % (thresholds,))
+    if not 1 <= len(thr) <= MAX_ARRIVAL_THRESHOLDS:
+        raise ValueError('%d arrival thresholds; 1..%d are kept' % (len(thr), MAX_ARRIVAL_THRESHOLDS))
+    if not all(np.isfinite(t) and t > 0 for t in thr):
+        raise ValueError('every arrival threshold must be finite and > 0: %r' % (thr,))
+    if any(b <= a for a, b in zip(thr, thr[1:])):
+        raise ValueError('arrival thresholds must be strictly increasing: %r' % (thr,))
+    return thr
+
+
+def check_arrival_days(days):
+    '''arrival day slots as a list of ints: 1..32 model days >= 0, strictly increasing; ValueError otherwise'''
+    d = [int(x) for x in days]
+    if not 1 <= len(d) <= MAX_ARRIVAL_SLOTS:
+        raise ValueError('%d arrival days; 1..%d fit one launch' % (len(d), MAX_ARRIVAL_SLOTS))
+    if d[0] < 0 or any(b <= a for a, b in zip(d, d[1:])):
+        raise ValueError('arrival days must be model days >= 0, strictly increasing: %r' % (d,))
+    return d
+
+
+def weighted_lower_quantile(values, weights, p):
+    '''min{a : sum of w_m over a_m <= a >= p W}, compared as (double)(integer weight) >= p * (double)W'''
+    v = np.asarray(values)
+    w = np.asarray(weights, dtype=np.int64)
+    order = np.argsort(v, kind='stable')
+    cw = np.cumsum(w[order])
+    j = int(np.argmax(cw.astype(np.float64) >= float(p) * float(w.sum())))
+    return v[order][j]
+
+
+class ArrivalMaps():
+    '''When `pop_model`'s members reach each cell: for thresholds t_0 < ... < t_{K-1} (1..4, finite, > 0)
+    and the model days `days` (strictly increasing, at most 32, default all), per threshold and cell the
+    weighted distribution of the arrival day a_k = the first listed day whose value (the one SpreadSummary
+    adds) is >= t_k, "never" if none; and per member the cells reached by each day.  Counts are integers:
+    the order of adds and merges changes no bit.'''
+
+    def __init__(self, pop_model, thresholds, days=None):
+        self._h = L._VP()
+        self.thresholds = check_arrival_thresholds(thresholds)
+        self.days = check_arrival_days(range(len(pop_model.days)) if days is None else days)
+        self._lib = L.load()
+        self.pm = pop_model
+        self.N = 2 * int(pop_model.rad_res) + 1
+        self.cell_area = (float(pop_model.rad_dist) / int(pop_model.rad_res)) ** 2
+        self.device = L.default_device() if pop_model.device is None else int(pop_model.device)
+        pitch = (self.N * self.N + 63) // 64 * 64
+        self.nbytes = len(self.thresholds) * len(self.days) * pitch * 4     # the count planes
+        thr = L.f64(self.thresholds)
+        L.check(self._lib.ps_arrival_create(self.device, self.N, len(self.days), len(self.thresholds), L.p_f64(thr),
+                                            C.byref(self._h)))
+        self._kind, self._idx, self._delta = _day_slots(self.days)
+        self._slot = {d: i for i, d in enumerate(self.days)}
+
+    def add(self, weight=1):
+        '''Accumulate the last evaluation of the model with integer weight >= 1 (enqueued on the
+        solver's stream; no host synchronisation).'''
+        pm = self.pm
+        _check_evaluated(pm, self.days, 'arrival maps')
+        stat, post = _day_scales(pm, self.days)
+        w = int(weight)
+        if w < 1:
+            raise ValueError('weight must be a positive integer')
+        L.check(self._lib.ps_arrival_add(self._h, pm.solver._h, len(self.days), L.p_i32(self._kind),
+                                         L.p_i32(self._idx), L.p_f64(stat), L.p_f64(post), L.p_i32(self._delta),
+                                         NEGVAL, w))
+
+    def merge(self, other):
+        '''self += other (same device, domain, days and thresholds); other's members follow self's'''
+        if list(other.days) != self.days:
+            raise ValueError('arrival maps over different days')
+        L.check(self._lib.ps_arrival_merge(self._h, other._h))
+
+    def reset(self):
+        L.check(self._lib.ps_arrival_reset(self._h))
+
+    def _info(self):
+        w, m = C.c_double(), C.c_int64()
+        L.check(self._lib.ps_arrival_info(self._h, C.byref(w), C.byref(m)))
+        return w.value, m.value
+
+    @property
+    def total_weight(self):
+        return self._info()[0]
+
+    @property
+    def members(self):
+        return self._info()[1]
+
+    def _k(self, k):
+        if not 0 <= int(k) < len(self.thresholds):
+            raise ValueError('threshold %r of %d' % (k, len(self.thresholds)))
+        return int(k)
+
+    def _slot_of(self, day):
+        if day not in self._slot:
+            raise ValueError('day %r is not in the arrival maps %s' % (day, self.days))
+        return self._slot[day]
+
+    def counts(self, k, day):
+        '''[N, N] uint32: the weight of the members whose arrival day at t_k is `day`; day=None: never'''
+        s = len(self.days) if day is None else self._slot_of(day)
+        out = np.empty((self.N, self.N), dtype=np.uint32)
+        L.check(self._lib.ps_arrival_fetch_counts(self._h, self._k(k), s, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def prob_by(self, k, day):
+        '''[N, N] float64: P(arrived at t_k by `day`) = C_k / W, C_k the weight of the arrivals up to `day`'''
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        L.check(self._lib.ps_arrival_prob(self._h, self._k(k), self._slot_of(day), L.p_f64(out)))
+        return out
+
+    def quantile(self, k, p):
+        '''[N, N] int32 map of model days: the first day whose C_k reaches p W ((double)C >= p * (double)W),
+        -1 where even the last day falls short (not within the window)'''
+        if not 0.0 < float(p) <= 1.0:
+            raise ValueError('quantile level %r is not in (0, 1]' % (p,))
+        slot = np.empty((self.N, self.N), dtype=np.int32)
+        L.check(self._lib.ps_arrival_quantile(self._h, self._k(k), float(p), L.p_i32(slot)))
+        day = np.append(np.asarray(self.days, dtype=np.int32), np.int32(-1))
+        return day[slot]          # slot -1 picks the appended -1
+
+    def _reached(self):
+        m = self.members
+        cells = np.empty((m, len(self.thresholds), len(self.days)), dtype=np.uint32)
+        w = np.empty(m, dtype=np.uint32)
+        u32 = C.POINTER(C.c_uint32)
+        L.check(self._lib.ps_arrival_fetch_reached(self._h, 0, m, cells.ctypes.data_as(u32), w.ctypes.data_as(u32)))
+        return cells, w
+
+    def reached(self, k):
+        '''(cells [members, days] int64, weights [members] int64): per member in add order the number of cells
+        that reached t_k by each day'''
+        k = self._k(k)
+        cells, w = self._reached()
+        return cells[:, k, :].astype(np.int64), w.astype(np.int64)
+
+    def reached_area(self, k, levels=(0.05, 0.5, 0.95)):
+        '''Per day the posterior of the area that reached t_k: [{'day', 'mean', 'quantiles', 'radius_mean',
+        'radius_quantiles'}, ...].  Areas in m^2 (cells x (rad_dist / rad_res)^2): the weighted mean and the
+        weighted lower quantiles min{a : sum of w_m over a_m <= a >= p W} at `levels`; radii sqrt(A / pi) in m.'''
+        levels = check_levels(levels)
+        cells, w = self.reached(k)
+        W = int(w.sum())
+        if W == 0:
+            raise ValueError('nothing accumulated')
+        out = []
+        for s, d in enumerate(self.days):
+            n = cells[:, s]
+            mean = float(int((n * w).sum())) / float(W) * self.cell_area
+            q = [float(weighted_lower_quantile(n, w, p)) * self.cell_area for p in levels]
+            out.append({'day': d, 'mean': mean, 'quantiles': q, 'radius_mean': float(np.sqrt(mean / np.pi)),
+                        'radius_quantiles': [float(np.sqrt(a / np.pi)) for a in q]})
+        return out
+
+    def profile(self, enable=None):
+        '''HIP-event time of the add and map launches: (add ms, adds, map ms, map launches); enable
+        switches it'''
+        am, an, qm, qn = C.c_double(), C.c_int64(), C.c_double(), C.c_int64()
+        L.check(self._lib.ps_arrival_prof(self._h, -1 if enable is None else int(bool(enable)), C.byref(am),
+                                          C.byref(an), C.byref(qm), C.byref(qn)))
+        return am.value, an.value, qm.value, qn.value
+
+    def close(self):
+        if self._h:
+            self._lib.ps_arrival_destroy(self._h)
+            self._h = L._VP()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ------------------------------------------------------------------ traces
 def model_names():
     return [m[0] for m in mcmc.MODEL_BLOCK]
@@ -418,13 +610,13 @@ def observation_predictive(rates, locinfo, seed=0):
 
 
 # ------------------------------------------------------------------ result files
-def save_maps(outfile, maps):
+def save_maps(outfile, maps, extra=None):
     '''outfile.npz in the layout of Run.save_result (Run.py:490-516 of the reference), which
     Plot_Result.main reads.  maps: [(day label, [(suffix, N x N array), ...]), ...] -> per day and
     suffix the CSR triplet `{label}{suffix}_data/_ind/_indptr` of the array thresholded at 1e-8,
-    and `days` = the labels.  The directory is created if needed.'''
+    and `days` = the labels; extra: {key: array} written as given.  The directory is created if needed.'''
     from scipy import sparse
-    out = {}
+    out = dict(extra or {})
     labels = []
     for label, day_maps in maps:
         labels.append(label)
@@ -457,13 +649,16 @@ class PredictiveResult():
     `rows` (trace rows after burn / thin), `evaluations`, `failed`, `seconds`, `runs`
     ([(chain, first_row, weight)] of every evaluated run), `observations` (observation_predictive
     or None) and `provenance`; with quantile levels `histogram` (a SpreadHistogram, None without a
-    device) and `quantiles` (the levels), else both None.'''
+    device) and `quantiles` (the levels), else both None; with arrival thresholds `arrival` (ArrivalMaps,
+    None without a device) and `arrival_levels`, else both None.'''
 
     def __init__(self, summary, rows, evaluations, failed, seconds, runs, observations, provenance, days,
-                 histogram=None, quantiles=None):
+                 histogram=None, quantiles=None, arrival=None, arrival_levels=None):
         self.summary = summary
         self.histogram = histogram
         self.quantiles = quantiles
+        self.arrival = arrival
+        self.arrival_levels = arrival_levels
         self.rows = rows
         self.evaluations = evaluations
         self.failed = failed
@@ -477,22 +672,37 @@ class PredictiveResult():
         '''outfile.npz in the layout of Run.save_result (Run.py:490-516 of the reference), which
         Plot_Result.main reads: per day `{day}_data/_ind/_indptr` of the posterior mean thresholded at
         1e-8, `days`; besides `{day}_sd_*` and `{day}_pexc{k}_*` CSR triplets, and with a histogram
-        `{day}_q{tag}_*` of the quantile point maps (quantile_tag: q5, q50, q95, q2p5).  outfile.json: the
-        params, the thresholds, the chain provenance, with a histogram the quantile levels and the edge
-        definition.  -> (npz path, json path)'''
+        `{day}_q{tag}_*` of the quantile point maps (quantile_tag: q5, q50, q95, q2p5).  With arrival maps
+        `{day}_parr{k}_*` (P(arrived at t_k by that day)), dense int16 `arrival{k}_{tag}` model-day maps
+        (-1: not within the window; dense because the CSR writer drops day 0), `arrival{k}_cells` [members,
+        days] and `arrival_weights`.  outfile.json: the params, the thresholds, the chain provenance, with a
+        histogram the quantile levels and the edge definition, with arrival maps their thresholds, levels,
+        days, cell area and per threshold and day the reached area.  -> (npz path, json path)'''
         s = self.summary
         if s is None:
             raise ValueError('no spread summary to save (evaluate= runs without a device)')
         h = self.histogram
         levels = list(self.quantiles or ()) if h is not None else []
+        A = self.arrival
+        a_levels = list(self.arrival_levels or ()) if A is not None else []
         maps = []
         for d in s.days:
             label = s.pm.days[d] if d < len(s.pm.days) else d
             day_maps = [('', s.mean(d)), ('_sd', s.sd(d))]
             day_maps += [('_pexc%d' % k, s.exceedance(d, k)) for k in range(len(s.thresholds))]
             day_maps += [('_' + quantile_tag(p), h.quantile(d, p)) for p in levels]
+            if A is not None:
+                day_maps += [('_parr%d' % k, A.prob_by(k, d)) for k in range(len(A.thresholds))]
             maps.append((label, day_maps))
-        save_maps(outfile, maps)
+        extra = {}
+        if A is not None:
+            for k in range(len(A.thresholds)):
+                for p in a_levels:
+                    extra['arrival%d_%s' % (k, quantile_tag(p))] = A.quantile(k, p).astype(np.int16)
+                cells, w = A.reached(k)
+                extra['arrival%d_cells' % k] = cells
+            extra['arrival_weights'] = w
+        save_maps(outfile, maps, extra)
         pdict = params_dict(params)
         meta = dict(pdict)
         meta['predictive'] = {'thresholds': s.thresholds, 'total_weight': s.total_weight, 'members': s.members,
@@ -502,14 +712,20 @@ class PredictiveResult():
             meta['predictive']['quantiles'] = {'levels': levels, 'bins': None if h.bins is None else list(h.bins),
                                                'edges': None if h.bins is not None else [float(e) for e in h.edges],
                                                'nedge': int(h.edges.size)}
+        if A is not None:
+            meta['predictive']['arrival'] = {'thresholds': list(A.thresholds), 'levels': a_levels,
+                                             'days': list(A.days), 'cell_area': A.cell_area,
+                                             'reached_area': [A.reached_area(k, a_levels)
+                                                              for k in range(len(A.thresholds))]}
         with open(str(outfile) + '.json', 'w') as fobj:
             json.dump(meta, fobj, default=str)
         return str(outfile) + '.npz', str(outfile) + '.json'
 
 
-def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, locinfo, histogram=None):
-    '''one chain: evaluate every run, add it to the summary (and the histogram) -> (expected per run or
-    None, failed)'''
+def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, locinfo, histogram=None,
+                   arrival=None):
+    '''one chain: evaluate every run, add it to the summary (and the histogram, the arrival maps) ->
+    (expected per run or None, failed)'''
     expected = []
     failed = 0
     for first, length in run_list:
@@ -535,12 +751,15 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
         summary.add(length)
         if histogram is not None:
             histogram.add(length)
+        if arrival is not None:
+            arrival.add(length)
         expected.append(mcmc.expected_observations(pm, locinfo) if want_obs else True)
     return expected, failed
 
 
 def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, thresholds=(), locinfo=None,
-                         cell_area=None, seed=0, evaluate=None, quantiles=None, bins=DEFAULT_BINS, edges=None):
+                         cell_area=None, seed=0, evaluate=None, quantiles=None, bins=DEFAULT_BINS, edges=None,
+                         arrival=None, arrival_levels=(0.05, 0.5, 0.95)):
     '''Posterior predictive spread of one or more chains (`Sampler.save` files or (trace, names)
     pairs).  Burn and thin apply per chain; consecutive rows with identical model parameters are one
     evaluation weighted by the run's length.  pop_model: one PopModel or a list -- with several, one
@@ -549,11 +768,20 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     for the observation-level predictive (every row: the rates of its run's evaluation with its own
     nuisance parameters).  evaluate(theta) -> expected observations or None: no device, no summary.
     quantiles: levels in (0, 1]; each chain then also fills a SpreadHistogram (bins / edges as
-    bin_edges) with the same weights, merged in chain order into `histogram`.'''
+    bin_edges) with the same weights, merged in chain order into `histogram`.  arrival: thresholds (1..4,
+    finite, > 0, strictly increasing); each chain then also fills ArrivalMaps over the summary's days
+    (strictly increasing, at most 32) with the same weights, merged in chain order into `arrival`;
+    arrival_levels: the levels of its saved arrival-day quantile maps.'''
     t0 = time.perf_counter()
     levels = (check_levels(quantiles) if quantiles is not None else []) or None
     if levels:
         bin_edges(bins, edges)        # a bad edge definition fails before any evaluation
+    a_thr = a_levels = None
+    if arrival is not None:           # bad arrival arguments fail before any evaluation too
+        a_thr = check_arrival_thresholds(arrival)
+        a_levels = check_levels(arrival_levels)
+        if days is not None:
+            check_arrival_days(days)
     if isinstance(chains, (str, os.PathLike)) or (isinstance(chains, tuple) and len(chains) == 2
                                                    and not isinstance(chains[0], (str, os.PathLike, tuple))):
         chains = [chains]
@@ -572,9 +800,12 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     pms = list(pop_model) if isinstance(pop_model, (list, tuple)) else [pop_model]
     if evaluate is None and (not pms or pms[0] is None):
         raise ValueError('a PopModel is needed without evaluate=')
+    if a_thr and evaluate is None and days is None:
+        check_arrival_days(range(len(pms[0].days)))
     nch = len(prepared)
     summaries = [None] * nch
     histograms = [None] * nch
+    arrivals = [None] * nch
     results = [None] * nch
     errs = []
 
@@ -587,7 +818,9 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                 summaries[ci] = summ
                 hist = SpreadHistogram(pm, days, bins, edges) if evaluate is None and levels else None
                 histograms[ci] = hist
-                results[ci] = _evaluate_runs(pm, summ, rows, rl, mcols, evaluate, want_obs, locinfo, hist)
+                arr = ArrivalMaps(pm, a_thr, summ.days) if evaluate is None and a_thr else None
+                arrivals[ci] = arr
+                results[ci] = _evaluate_runs(pm, summ, rows, rl, mcols, evaluate, want_obs, locinfo, hist, arr)
         except BaseException as e:       # re-raised in the caller's thread
             errs.append((p, e))
 
@@ -602,12 +835,13 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         pms = pms[:1]
         work(0)
     if errs:
-        for s in summaries + histograms:
+        for s in summaries + histograms + arrivals:
             if s is not None:
                 s.close()
         raise errs[0][1]
     summary = None
     histogram = None
+    arrival_maps = None
     if evaluate is None:
         summary = summaries[0]
         for s in summaries[1:]:
@@ -618,6 +852,11 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
             for h in histograms[1:]:
                 histogram.merge(h)
                 h.close()
+        if a_thr:
+            arrival_maps = arrivals[0]
+            for a in arrivals[1:]:
+                arrival_maps.merge(a)
+                a.close()
     evaluations = sum(len(p[1]) for p in prepared)
     failed = sum(r[1] for r in results)
     run_rec = [(ci, first, length) for ci, p in enumerate(prepared)
@@ -637,7 +876,8 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
             for p in prepared]
     res = PredictiveResult(summary, int(sum(len(p[0]) for p in prepared)), evaluations, failed,
                            time.perf_counter() - t0, run_rec, observations, prov,
-                           None if summary is None else summary.days, histogram, levels)
+                           None if summary is None else summary.days, histogram, levels, arrival_maps,
+                           a_levels if a_thr else None)
     if cell_area is not None:
         res.cell_area = float(cell_area)
     return res

@@ -2,13 +2,14 @@
 """Posterior predictive spread of saved MCMC chains (parasitoids_amd/predictive.py): per day and
 cell the posterior mean population, its spread and exceedance probabilities, accumulated on the
 GPU, plus the observation-level predictive of the reference's Poisson model; with --quantiles also
-per-cell quantile maps from device histograms on fixed bin edges (--bins).  Kalbar wind and
+per-cell quantile maps from device histograms on fixed bin edges (--bins); with --arrival also arrival
+probability and arrival-day quantile maps and the reached area per day (--arrival-levels).  Kalbar wind and
 LocInfo as scripts/run_mcmc.py loads them; --synthetic uses the synthetic Kalbar-like observations.
 Without --chain a short chain is sampled first (--samples) and saved next to --out.
 
     python scripts/run_predictive.py --chain c.npz [...] [--burn 0] [--thin 1] [--rad-res 400]
         [--mode auto] [--thresholds 1,10] [--out PREFIX] [--synthetic] [--chains-parallel]
-        [--quantiles 0.05,0.5,0.95] [--bins 1e-8,1e6,16]
+        [--quantiles 0.05,0.5,0.95] [--bins 1e-8,1e6,16] [--arrival 1,10] [--arrival-levels 0.05,0.5,0.95]
 """
 import argparse
 import json
@@ -37,15 +38,22 @@ def main():
     ap.add_argument('--seed', type=int, default=1000)
     ap.add_argument('--quantiles', default='', help='quantile levels in (0, 1], e.g. 0.05,0.5,0.95 (default: off)')
     ap.add_argument('--bins', default='1e-8,1e6,16', help='histogram edges LO,HI,PER_DECADE (with --quantiles)')
+    ap.add_argument('--arrival', default='', help='arrival thresholds, e.g. 1,10 (default: off)')
+    ap.add_argument('--arrival-levels', default='0.05,0.5,0.95',
+                    help='arrival-day quantile levels in (0, 1] (with --arrival)')
     args = ap.parse_args()
     warnings.simplefilter('ignore', RuntimeWarning)
     from parasitoids_amd import ParasitoidModel as PM
     from parasitoids_amd import mcmc
     from parasitoids_amd.pop_model import PopModel
-    from parasitoids_amd.predictive import bin_edges, check_levels, posterior_predictive
+    from parasitoids_amd.predictive import bin_edges, check_arrival_thresholds, check_levels, posterior_predictive
     levels = check_levels([float(q) for q in args.quantiles.split(',') if q.strip()])
     bins = tuple(float(b) for b in args.bins.split(','))
     bin_edges(bins)                      # a bad --bins fails before any work
+    arrival = [float(t) for t in args.arrival.split(',') if t.strip()]
+    a_levels = check_levels([float(q) for q in args.arrival_levels.split(',') if q.strip()])
+    if arrival:
+        check_arrival_thresholds(arrival)   # as do bad --arrival thresholds
     wd, days = PM.get_wind_data(os.path.join(ROOT, 'parasitoids_amd', 'data', 'kalbar'), 30, '00:00')
 
     def make_pm():
@@ -73,15 +81,18 @@ def main():
     t0 = time.perf_counter()
     res = posterior_predictive(pms if len(pms) > 1 else pm, chains, burn=args.burn, thin=args.thin,
                                thresholds=thr, locinfo=li, cell_area=cell_area, seed=args.seed,
-                               quantiles=levels or None, bins=bins)
+                               quantiles=levels or None, bins=bins, arrival=arrival or None, arrival_levels=a_levels)
     dt = time.perf_counter() - t0
     # accumulate-kernel time: the same members once more with HIP events around every add
-    from parasitoids_amd.predictive import SpreadHistogram, SpreadSummary, load_chain, runs
+    from parasitoids_amd.predictive import ArrivalMaps, SpreadHistogram, SpreadSummary, load_chain, runs
     H = SpreadHistogram(pm, None, bins) if levels else None
+    A = ArrivalMaps(pm, arrival) if arrival else None
     with SpreadSummary(pm, None, thr) as S:
         S.profile(True)
         if H is not None:
             H.profile(True)
+        if A is not None:
+            A.profile(True)
         n = 0
         for c in chains[:1]:
             trace, names, _ = load_chain(c)
@@ -95,12 +106,18 @@ def main():
                 S.add(length)
                 if H is not None:
                     H.add(length)
+                if A is not None:
+                    A.add(length)
                 n += 1
         ms, launches = S.profile()
     if H is not None:
         h_ms, h_launches = H.profile()[:2]
         H.close()
         res.histogram.profile(True)     # every quantile launch of the saved maps
+    if A is not None:
+        a_ms, a_launches = A.profile()[:2]
+        A.close()
+        res.arrival.profile(True)       # every map launch of the save
     npz, js = res.save(args.out, {'chains': chains, 'burn': args.burn, 'thin': args.thin, 'rad_res': args.rad_res,
                                   'mode': args.mode, 'synthetic': bool(args.synthetic)})
     ncell = (2 * args.rad_res + 1) ** 2
@@ -119,10 +136,16 @@ def main():
         out['histogram_add_ms_per_member'] = round(h_ms / max(h_launches, 1), 4)
         out['quantile_ms_total'] = round(res.histogram.profile()[2], 3)
         out['histogram_bytes'] = res.histogram.nbytes
+    if arrival:
+        out['arrival_add_ms_per_member'] = round(a_ms / max(a_launches, 1), 4)
+        out['arrival_maps_ms_total'] = round(res.arrival.profile()[2], 3)
+        out['arrival_bytes'] = res.arrival.nbytes
     print(json.dumps(out))
     res.summary.close()
     if res.histogram is not None:
         res.histogram.close()
+    if res.arrival is not None:
+        res.arrival.close()
     for p in pms:
         p.close()
 
