@@ -88,6 +88,8 @@ int ps_solver_retarget(ps_solver* s, int max_shape);
 int ps_solver_destroy(ps_solver* s);
 /* P = reference torus, Pfft = transform size in use, H = Pfft/2+1 */
 int ps_solver_info(ps_solver* s, int* dom_len, int* P, int* Pfft, int* H);
+/* Everything enqueued on the handle's stream is done and the last ps_chain_run is final (its last
+ * window of days verified, see ps_chain_run) when this returns. */
 int ps_solver_sync(ps_solver* s);
 /* Tuning / A-B knobs.  The reference has one switch (globalvars.py:5: `cuda`); this library's
  * knobs (csrc/ps_config.h) exist for measurements and for the A/B legs of
@@ -105,6 +107,11 @@ int ps_solver_kernels_direct(ps_solver* s);
  * pass per column transform: register-resident FFT sizes in PS_MODE_FAST), 0 for the tiled
  * two-sub-pass column kernels */
 int ps_solver_pipeline(ps_solver* s);
+/* measurement aid, read-only (makes no run final): *pending = 1 while the last ps_chain_run's final window
+ * is still unchecked (see ps_chain_run); counts[4] = runs that returned with a check pending, pending checks
+ * that found a flag and redid the days behind it, runs whose kernel staging was queued ahead of that check,
+ * host uploads that went through the handle's pinned staging.  Either pointer may be null. */
+int ps_solver_deferred_info(ps_solver* s, int* pending, int64_t* counts);
 /* PS_MODE_AUTO: *first_fold_day = first chain day of the last ps_chain_run that ran on the folded
  * reference torus (-1: every day was clean and ran on the fast torus); *fold_fft = FFT size of the
  * fold path (0 if it was never needed).  Other modes: -1 / 0. */
@@ -117,7 +124,10 @@ int ps_solver_auto_info(ps_solver* s, int* first_fold_day, int* fold_fft);
 int ps_solver_auto_route(ps_solver* s, int first, int count, int32_t* owner);
 
 /* CudaSolve.__init__ (cuda_lib.py:34-54) / CalcSol.fft2 (CalcSol.py:11-24):
- * state_hat = FFT2(zero-padded N x N sparse field). */
+ * state_hat = FFT2(zero-padded N x N sparse field).  The arrays are the caller's again when the
+ * call returns: they are copied into pinned staging owned by the handle (grown on demand) and the
+ * call enqueues without waiting for the stream.  Only if that pinned block cannot be allocated does
+ * the call copy from the caller's arrays and wait for the stream instead. */
 int ps_solver_set_state_coo(ps_solver* s, const int32_t* row, const int32_t* col,
                             const double* val, int64_t nnz);
 
@@ -153,7 +163,15 @@ int ps_chain_set_kernels(ps_solver* s, int nk, const int64_t* off, const int32_t
  * fftconv2 -> ifft2 -> statistics/flag -> (flagged) truncate + re-FFT, all enqueued on
  * the handle's stream.  The flag decisions are taken on the device; the call itself waits for
  * the device only where it verifies a window of days that it ran without the conditional
- * launches (it returns with the last window verified).  Day d's field is chain record d; the
+ * launches.  A PS_MODE_FAST run on the full-column pipeline may return with its LAST window enqueued
+ * but not yet verified: the library verifies it -- and redoes the days behind a flag, exactly as
+ * the call itself would have -- at the start of the next call on the handle that reads or changes
+ * anything of the run (statistics, records, profiling counters, kernels, options, another run,
+ * ps_solver_sync, ...), so every result a caller can see is final.  ps_solver_set_state_* alone does
+ * not: a sampler chain's set_state + ps_chain_run on the same kernels keeps the device busy across
+ * the boundary.  Synchronising the device by other means (hipDeviceSynchronize) therefore does not
+ * make a run final; ps_solver_sync does.  PS_NO_DEFER_CHECK=1: the call returns with the last window
+ * verified.  Day d's field is chain record d; the
  * statistics of every day run since the kernels were uploaded stay readable (ps_chain_stats).
  * A run may be continued (first > 0 right after a run that ended at first) in PS_MODE_EXACT / FAST /
  * FOLD.  PS_MODE_AUTO runs need a fresh state (ps_solver_set_state_*) before EVERY call: once a run

@@ -14,9 +14,11 @@ static __global__ void k_scatter_coo(const int* __restrict__ row, const int* __r
     atomicAdd(&dst[(int64_t)(row[i] + roff) * ld + col[i] + coff], val[i]);
 }
 
-// zero rows [r0, r1] of each of gridDim.y consecutive K x K blocks (the band of staging rows
-// some kernel of the chunk writes: the row pass reads nothing else)
-static __global__ void k_zero_band(double* dst, int K, int r0, int r1) {
+// zero the live rows [range[2d], range[2d+1]] of the d-th of gridDim.y consecutive K x K blocks (the
+// staging rows that day's kernel writes: the row pass of the day reads nothing else)
+static __global__ void k_zero_band(double* dst, int K, const int* __restrict__ range) {
+  const int r0 = max(range[2 * blockIdx.y], 0), r1 = min(range[2 * blockIdx.y + 1], K - 1);
+  if (r1 < r0) return;
   double* base = dst + (int64_t)blockIdx.y * K * K + (int64_t)r0 * K;
   const int64_t n = (int64_t)(r1 - r0 + 1) * K;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)

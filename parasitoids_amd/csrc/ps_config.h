@@ -64,6 +64,7 @@
   X("PS_SPEC_DEPTH", spec_depth, 2, INT, R)                                                         \
   X("PS_NO_FLAG_HISTORY", no_flag_history, 0, FLAG, R)                                              \
   X("PS_NO_WINDOW_HINT", no_window_hint, 0, FLAG, R)                                                \
+  X("PS_NO_DEFER_CHECK", no_defer_check, 0, FLAG, R)                                                \
   X("PS_FIRST_WINDOW", first_window, -1, INT, R)                                                    \
   X("PS_KT_SPLIT", kt_split, -1, INT, R)                                                            \
   X("PS_NO_LAZY_KT", no_lazy_kt, 0, FLAG, R)                                                        \

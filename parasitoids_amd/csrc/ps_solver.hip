@@ -203,7 +203,26 @@ struct ps_solver {
   unsigned long long* hhist = nullptr;
   int hhist_n = 0, hist_first = -1, hist_count = 0;
   hipEvent_t hist_ev = nullptr;
-  int rs_r2 = 0, rs_r3 = 0;   // register-resident row kernels (fft_rs.h) for Pf = 16 * rs_r2 * rs_r3, or 0
+  // Deferred check of a run's last speculation window (settle): ps_chain_run has returned with the window
+  // enqueued and its pad maxima on their way to hflags; whoever next observes or disturbs the run settles it
+  // first.  set_state does not: it touches nothing a recovery reads.  PS_NO_DEFER_CHECK=1: A/B knob.
+  struct Pending {
+    bool on = false;
+    int first = 0, count = 0;   // the run
+    int d0 = 0, w = 0, ev = 0;  // its last window and the event behind the copy of its pad maxima
+    double negval = 0, stat_scale = 0;
+    double thr = 1e-8;          // a pad maximum above this is a flag (the run's flag_thr)
+  } pend;
+  // what ps_solver_deferred_info reports: runs that returned with a check pending, pending checks that found a
+  // flag, runs whose kernel staging was queued ahead of settle, uploads that went through the pinned staging
+  long long n_deferred = 0, n_late_flags = 0, n_staged_early = 0, n_staged_uploads = 0;
+  bool kt_early = false;       // Bhat already holds this run's kernel transforms (enqueued ahead of settle)
+  // set_state / per-call uploads: the caller's triplets go through pinned staging, two slots, each guarded by
+  // the event behind its copies, so the call returns without waiting for the stream
+  struct Stage { char* p = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool busy = false; } stage[2];
+  int stage_next = 0;
+  int hsrange[2] = {1, 0};     // host copy of srange while srange_valid
+  int rs_r2 = 0, rs_r3 = 0;  // register-resident row kernels (fft_rs.h) for Pf = 16 * rs_r2 * rs_r3, or 0
   int L1 = 0, L2 = 0;
   DevBuf<cplx> tp_lo, tp_hi;
   int tp_shift = 0;
@@ -340,6 +359,14 @@ struct ProfScope {
     s->prof_pending.push_back(r);
   }
 };
+
+static int settle(ps_solver* s);   // the deferred check of the last chain run (ps_solver::Pending)
+// Prologue of every entry point that observes or disturbs the last chain run -- records, statistics, flags,
+// the state's spectrum, the kernels, the profiling counters: the run is final once this returns.
+static int enter(ps_solver* s) {
+  PS_HIP(hipSetDevice(s->device));
+  return settle(s);
+}
 
 // ------------------------------------------------------------------ helpers
 static int row_threads(int L, bool big = false) { return L <= 1024 ? 256 : ((L <= 2560 || big) ? 512 : 1024); }
@@ -1150,6 +1177,9 @@ static int solver_create(ps_solver** out, int device, int dom_len, int max_shape
 extern "C" int ps_solver_destroy(ps_solver* s) {
   if (!s) return PS_OK;
   (void)hipSetDevice(s->device);
+  // a check still pending is dropped, not settled: nobody is left to read the run, and everything it
+  // enqueued is done after the synchronisation below
+  s->pend.on = false;
   if (s->stream) (void)hipStreamSynchronize(s->stream);
   if (s->child) {
     ps_solver_destroy(s->child);
@@ -1191,6 +1221,10 @@ extern "C" int ps_solver_destroy(ps_solver* s) {
   for (auto e : s->prof_pool) (void)hipEventDestroy(e);
   for (auto e : s->spec_ev) if (e) (void)hipEventDestroy(e);
   if (s->hflags) (void)hipHostFree(s->hflags);
+  for (auto& st : s->stage) {
+    if (st.ev) (void)hipEventDestroy(st.ev);
+    if (st.p) (void)hipHostFree(st.p);
+  }
   if (s->hhist) (void)hipHostFree(s->hhist);
   if (s->hist_ev) (void)hipEventDestroy(s->hist_ev);
   s->dkoff.release(); s->dkshape.release();
@@ -1208,7 +1242,7 @@ extern "C" int ps_solver_retarget(ps_solver* s, int max_shape) {
     if (s->N + m > s->Pf)
       return ps_fail(PS_ERR_BAD_SHAPE, "retarget: max_shape %d needs an FFT size >= %d, the solver has %d", max_shape,
                      s->N + m, s->Pf);
-    PS_HIP(hipSetDevice(s->device));
+    PS_TRY(enter(s));
     PS_HIP(hipStreamSynchronize(s->stream));
     if (s->child && ps_solver_retarget(s->child, max_shape) != PS_OK) {
       ps_solver_destroy(s->child);
@@ -1238,7 +1272,7 @@ extern "C" int ps_solver_retarget(ps_solver* s, int max_shape) {
   if (s->N + 3 * m > s->Pf)
     return ps_fail(PS_ERR_BAD_SHAPE, "retarget: max_shape %d needs an FFT size >= %d, the solver has %d", max_shape,
                    s->N + 3 * m, s->Pf);
-  PS_HIP(hipSetDevice(s->device));
+  PS_TRY(enter(s));
   PS_HIP(hipStreamSynchronize(s->stream));
   s->M = m;
   s->Pref = s->N + m;
@@ -1259,7 +1293,7 @@ extern "C" int ps_solver_info(ps_solver* s, int* dom_len, int* P, int* Pfft, int
 
 extern "C" int ps_solver_sync(ps_solver* s) {
   if (!s) return ps_fail(PS_ERR_BAD_ARG, "null solver");
-  PS_HIP(hipSetDevice(s->device));
+  PS_TRY(enter(s));
   PS_HIP(hipStreamSynchronize(s->stream));
   return PS_OK;
 }
@@ -1293,22 +1327,66 @@ static int upload_coo(ps_solver* s, const int32_t* row, const int32_t* col, cons
   PS_TRY(s->orow.ensure(std::max<int64_t>(nnz, 1)));
   PS_TRY(s->ocol.ensure(std::max<int64_t>(nnz, 1)));
   PS_TRY(s->oval.ensure(std::max<int64_t>(nnz, 1)));
-  if (nnz > 0) {
+  if (nnz <= 0) return PS_OK;
+  // Host buffers are caller-owned and free when the call returns.  They are copied into pinned staging owned
+  // by the solver (two slots, grown on demand) and uploaded from there, so the host does not wait for whatever
+  // the stream still holds (the previous stack of a sampler chain); a slot is reused only after the event
+  // behind its copies -- two uploads back -- has fired.  Only when the pinned block cannot be had does the
+  // call copy from the caller's arrays and wait for the stream, as it used to.
+  const size_t bytes = (size_t)nnz * 16;
+  ps_solver::Stage& st = s->stage[s->stage_next];
+  s->stage_next ^= 1;
+  if (st.busy) PS_HIP(hipEventSynchronize(st.ev));
+  st.busy = false;
+  if (st.cap < bytes) {
+    if (st.p) (void)hipHostFree(st.p);
+    st.p = nullptr;
+    st.cap = 0;
+    const size_t cap = std::max<size_t>(bytes + bytes / 2, 4096);
+    if (hipHostMalloc((void**)&st.p, cap, hipHostMallocDefault) == hipSuccess) st.cap = cap;
+    else { st.p = nullptr; (void)hipGetLastError(); }
+  }
+  if (!st.p) {
     PS_HIP(hipMemcpyAsync(s->orow.p, row, nnz * 4, hipMemcpyHostToDevice, s->stream));
     PS_HIP(hipMemcpyAsync(s->ocol.p, col, nnz * 4, hipMemcpyHostToDevice, s->stream));
     PS_HIP(hipMemcpyAsync(s->oval.p, val, nnz * 8, hipMemcpyHostToDevice, s->stream));
-    PS_HIP(hipStreamSynchronize(s->stream));  // host buffers are caller-owned: copy completes before return
+    PS_HIP(hipStreamSynchronize(s->stream));  // copy completes before return
+    return PS_OK;
   }
+  if (!st.ev) PS_HIP(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
+  // values first: every piece starts on an 8-byte boundary
+  char* hv = st.p;
+  char* hr = hv + (size_t)nnz * 8;
+  char* hc = hr + (size_t)nnz * 4;
+  std::memcpy(hv, val, (size_t)nnz * 8);
+  std::memcpy(hr, row, (size_t)nnz * 4);
+  std::memcpy(hc, col, (size_t)nnz * 4);
+  PS_HIP(hipMemcpyAsync(s->orow.p, hr, nnz * 4, hipMemcpyHostToDevice, s->stream));
+  PS_HIP(hipMemcpyAsync(s->ocol.p, hc, nnz * 4, hipMemcpyHostToDevice, s->stream));
+  PS_HIP(hipMemcpyAsync(s->oval.p, hv, nnz * 8, hipMemcpyHostToDevice, s->stream));
+  PS_HIP(hipEventRecord(st.ev, s->stream));
+  st.busy = true;
+  ++s->n_staged_uploads;
   return PS_OK;
 }
 
-int ps_solver_set_state_device_coo(ps_solver* s, const int* row, const int* col, const double* val,
-                                   int64_t nnz, int off) {
+// `known_rows`: the caller (set_state_coo) knows which rows the new state occupies and says so afterwards.
+// Then, if the rows of the state before are known too, only those are cleared: everything else of the record
+// is zero since the last full clear (134 MB at 4097^2, 20 us).  Enqueues only; touches the state record, the
+// flags below and nothing a pending recovery reads (settle).
+static int set_state_scatter(ps_solver* s, const int* row, const int* col, const double* val, int64_t nnz, int off,
+                             bool known_rows) {
+  const bool fresh = s->recs[PS_REC_STATE].empty() || !s->recs[PS_REC_STATE][0];
   PS_TRY(ensure_record(s, PS_REC_STATE, 0));
   PS_TRY(ensure_temps(s, 1));
-  s->srange_valid = false;   // set_state_coo knows the rows and says so afterwards
   double* rec = s->recs[PS_REC_STATE][0];
-  PS_HIP(hipMemsetAsync(rec, 0, (size_t)s->N * s->N * sizeof(double), s->stream));
+  if (known_rows && s->srange_valid && !fresh && s->mode != PS_MODE_FOLD) {
+    const int lo = std::max(s->hsrange[0], 0), hi = std::min(s->hsrange[1], s->N - 1);
+    if (lo <= hi) PS_HIP(hipMemsetAsync(rec + (size_t)lo * s->N, 0, (size_t)(hi - lo + 1) * s->N * sizeof(double), s->stream));
+  } else {
+    PS_HIP(hipMemsetAsync(rec, 0, (size_t)s->N * s->N * sizeof(double), s->stream));
+  }
+  s->srange_valid = false;
   PS_TRY(scatter_from_device(s, row, col, val, nnz, rec, s->N, off));
   if (s->mode == PS_MODE_FOLD) {   // the state lives in space, on the reference torus
     PS_TRY(s->torus.ensure((size_t)s->Pref * s->Pref));
@@ -1321,6 +1399,11 @@ int ps_solver_set_state_device_coo(ps_solver* s, const int* row, const int* col,
   s->spec_valid = false;   // transformed by the first consumer (ensure_spectrum)
   s->have_state = true;
   return PS_OK;
+}
+
+int ps_solver_set_state_device_coo(ps_solver* s, const int* row, const int* col, const double* val,
+                                   int64_t nnz, int off) {
+  return set_state_scatter(s, row, col, val, nnz, off, false);
 }
 
 // Ahat <- transform of the spatial state record, in the layout of the current pipeline
@@ -1348,10 +1431,10 @@ static void set_pipeline(ps_solver* s, bool tpipe) {
 extern "C" int ps_solver_set_state_coo(ps_solver* s, const int32_t* row, const int32_t* col,
                                        const double* val, int64_t nnz) {
   if (!s || nnz < 0 || (nnz > 0 && (!row || !col || !val))) return ps_fail(PS_ERR_BAD_ARG, "set_state_coo: bad arguments");
-  PS_HIP(hipSetDevice(s->device));
+  PS_HIP(hipSetDevice(s->device));   // not enter(): a new state leaves the last run's pending check alone (settle)
   PS_TRY(check_coo(row, col, nnz, s->N, "state"));
   PS_TRY(upload_coo(s, row, col, val, nnz));
-  PS_TRY(ps_solver_set_state_device_coo(s, s->orow.p, s->ocol.p, s->oval.p, nnz, 0));
+  PS_TRY(set_state_scatter(s, s->orow.p, s->ocol.p, s->oval.p, nnz, 0, true));
   // rows that hold anything: a release state is a handful of rows of the N, and the forward row
   // pass (145 us at 4097^2 for all of them) only has to transform those
   int range[2] = {1, 0};
@@ -1363,6 +1446,8 @@ extern "C" int ps_solver_set_state_coo(ps_solver* s, const int32_t* row, const i
   PS_TRY(s->srange.ensure(2));
   hipLaunchKernelGGL(k_set_int2, dim3(1), dim3(64), 0, s->stream, s->srange.p, range[0], range[1]);
   PS_HIP(hipGetLastError());
+  s->hsrange[0] = range[0];
+  s->hsrange[1] = range[1];
   s->srange_valid = true;
   return PS_OK;
 }
@@ -1397,23 +1482,20 @@ static int transform_kernels(ps_solver* s, int first, int count, int slot0, int 
   PS_TRY(s->Bhat.ensure(spec * total));
   PS_TRY(ensure_temps(s, total));
   double* kd = s->kdense.p + (size_t)slot0 * K * K;
-  // zero only the band of staging rows some kernel of the chunk writes (the row pass reads
-  // nothing else, see krange) with one small kernel, then one batched scatter launch
-  int blo = K, bhi = -1;
+  // zero only the staging rows each kernel of the chunk writes (its day's row pass reads nothing
+  // else, see krange) with one small kernel, then one batched scatter launch.  Each day clears its OWN
+  // live rows, not the union over the chunk: the headline stack's kernels drift by +-64 cells, and the
+  // union is twice a day's band.
+  int maxrows = 0;
   int64_t maxn = 0;
   for (int d = first; d < first + count; ++d) {
-    if (s->hkrange[2 * d] <= s->hkrange[2 * d + 1]) {
-      blo = std::min(blo, s->hkrange[2 * d]);
-      bhi = std::max(bhi, s->hkrange[2 * d + 1]);
-    }
+    maxrows = std::max(maxrows, std::min(s->hkrange[2 * d + 1], K - 1) - std::max(s->hkrange[2 * d], 0) + 1);
     maxn = std::max<int64_t>(maxn, s->koff[d + 1] - s->koff[d]);
   }
-  if (bhi >= blo) {
-    blo = std::max(blo, 0);
-    bhi = std::min(bhi, K - 1);
-    const int64_t n = (int64_t)(bhi - blo + 1) * K;
+  if (maxrows > 0) {
+    const int64_t n = (int64_t)maxrows * K;
     const int blocks = (int)std::min<int64_t>((n + 255) / 256, 2048);
-    hipLaunchKernelGGL(k_zero_band, dim3(blocks, count), dim3(256), 0, s->stream, kd, K, blo, bhi);
+    hipLaunchKernelGGL(k_zero_band, dim3(blocks, count), dim3(256), 0, s->stream, kd, K, s->krange.p + 2 * first);
     PS_HIP(hipGetLastError());
   }
   if (maxn > 0) {
@@ -1459,6 +1541,7 @@ static int kernels_ready(ps_solver* s, int d) {
 // PopModel.evaluate(want_stats=False) return from ps_chain_run without synchronising.  (The
 // main stream is ordered behind the second one at the end of every ps_chain_run.)
 static int drain_kernel_readers(ps_solver* s) {
+  PS_TRY(enter(s));   // a recovery still to come reads the kernels' spectra and live-row ranges
   if (s->stream2) PS_HIP(hipStreamSynchronize(s->stream2));
   PS_HIP(hipStreamSynchronize(s->stream));
   return PS_OK;
@@ -1522,7 +1605,7 @@ static int set_kernels_common(ps_solver* s, int nk, const int64_t* off, const in
 extern "C" int ps_chain_set_kernels(ps_solver* s, int nk, const int64_t* off, const int32_t* kshape,
                                     const int32_t* row, const int32_t* col, const double* val) {
   if (!s || nk < 0 || !off || (nk > 0 && !kshape)) return ps_fail(PS_ERR_BAD_ARG, "set_kernels: bad arguments");
-  PS_HIP(hipSetDevice(s->device));
+  PS_TRY(enter(s));
   const int64_t tot = off[nk];
   for (int d = 0; d < nk; ++d) {
     if (off[d + 1] < off[d]) return ps_fail(PS_ERR_BAD_ARG, "offsets not monotone");
@@ -1806,6 +1889,102 @@ static int auto_handover(ps_solver* s, int first, int f, int end, double negval,
   return PS_OK;
 }
 
+// the pipeline ps_chain_run picks for days [first, first + count) while the state's spectrum is still to be built
+static bool want_full_column(const ps_solver* s, int first, int count) {
+  bool compact = direct_possible(s);
+  for (int d = first; d < first + count && compact; ++d) compact = day_is_compact(s, d);
+  // Compact kernels on a split column size have the direct-sum tiled route (4-day groups, no kernel
+  // spectra in HBM); it still wins where the full-column pass cannot chain days (state column + exchange
+  // buffer beyond LDS, L > 6400).  Everywhere else the full-column pipeline is ahead since the
+  // persistent row kernel and the pipelined kernel fetch: 10.5 against 11.7 ms per 30-day stack at 5184,
+  // 8.2 against 9.4 at 4608 (single-pass column sizes too: +6 % on the flag-heavy R = 400 Bayes chain).
+  bool want = !(s->split && compact) || colfull_chains(s);
+  if (s->cfg.tpipe >= 0) want = s->cfg.tpipe != 0;   // A/B knob
+  return want;
+}
+
+// one day step of a fast-mode chain on its own, with or without the flag-conditional re-transform
+static int run_day(ps_solver* s, int d, bool with_refft, double negval, double stat_scale) {
+  PS_TRY(kernels_ready(s, d));
+  const cplx* B = s->Bhat.p + (size_t)(d - s->bhat_first) * s->Pf * s->ld;
+  double* rec = s->recs[PS_REC_CHAIN][d];
+  PS_TRY(conv_inv(s, B, s->Ahat.p, 1, rec, d, negval, stat_scale, s->krange.p + 2 * d));
+  if (with_refft) {
+    // full-column pipeline: only the row half now, the column half inside the next day's pass
+    // (PS_NO_DEFER_REFFT=1: A/B knob)
+    const bool defer = !s->cfg.no_defer_refft && !s->cfg.tpipe_split;
+    if (s->tpipe && defer && rs_colfull_alt_ok(s->rs_r2, s->rs_r3)) PS_TRY(refft_rows_if_flag(s, rec, d));
+    else PS_TRY(refft_if_flag(s, rec, s->Ahat.p, d));
+  }
+  return PS_OK;
+}
+
+// A speculation window turned out to hold a flag at day f, with days up to (not including) `end` enqueued
+// behind it: f's truncated field is re-transformed for real, the pad maxima behind it are cleared (the days
+// are redone, stream order keeps what was enqueued harmless) and this solver stops speculating.
+static int recover_from_flag(ps_solver* s, int f, int end) {
+  s->refft_pending = nullptr;   // belongs to a day behind f
+  PS_TRY(fwd2d(s, s->recs[PS_REC_CHAIN][f], 0, s->N, map_plain(s->N, s->Pf), map_plain(s->N, s->Pf),
+               s->Ahat.p, 1, nullptr));
+  if (end - f - 1 > 0)
+    PS_HIP(hipMemsetAsync(s->padmax.p + f + 1, 0, (size_t)(end - f - 1) * sizeof(unsigned long long), s->stream));
+  s->speculate = false;
+  return PS_OK;
+}
+
+// what a fast-mode run leaves for the next one: the window hint, or the flags it raised
+static int finish_run(ps_solver* s, int first, int count, bool flagged) {
+  if (s->speculate && !flagged) s->noflag_hint = count;
+  if (!s->auto_exact && !s->speculate && count >= 2 && !s->cfg.no_flag_history) {
+    if (s->hhist_n < count) {
+      if (s->hist_ev) PS_HIP(hipEventSynchronize(s->hist_ev));   // an earlier run's copy may still be on its way
+      if (s->hhist) (void)hipHostFree(s->hhist);
+      s->hhist = nullptr;
+      s->hhist_n = 0;
+      PS_HIP(hipHostMalloc((void**)&s->hhist, (size_t)(count + 32) * sizeof(unsigned long long), hipHostMallocDefault));
+      s->hhist_n = count + 32;
+    }
+    if (!s->hist_ev) PS_HIP(hipEventCreateWithFlags(&s->hist_ev, hipEventDisableTiming));
+    PS_HIP(hipMemcpyAsync(s->hhist, s->padmax.p + first, (size_t)count * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream));
+    PS_HIP(hipEventRecord(s->hist_ev, s->stream));
+    s->hist_first = first;
+    s->hist_count = count;
+  }
+  return PS_OK;
+}
+
+// first day of the window [d0, d0 + w) whose pad maximum, as copied to hflags, exceeds thr; -1: none
+static int first_flagged_day(const ps_solver* s, int d0, int w, double thr) {
+  for (int i = 0; i < w; ++i) {
+    double m;
+    __builtin_memcpy(&m, &s->hflags[d0 + i], sizeof(double));
+    if (m > thr) return d0 + i;
+  }
+  return -1;
+}
+
+// The pending check of a run's last window (ps_solver::Pending): wait for its pad maxima and finish the run
+// the way the window loop of chain_run_body would have.  No flag: the days stand, the run leaves its window
+// hint.  Flag at day f: the same recovery, the days behind f one at a time with their predicated
+// re-transform, on the kernel spectra Bhat still holds (nothing between the deferred return and here may
+// replace them; a set_state in between has only written the state record, and finds spec_valid false).
+// Called by every entry point that observes or disturbs the run; a no-op when nothing is pending.
+static int settle(ps_solver* s) {
+  if (!s->pend.on) return PS_OK;
+  const ps_solver::Pending p = s->pend;
+  s->pend.on = false;
+  PS_HIP(hipEventSynchronize(s->spec_ev[p.ev]));
+  const int f = first_flagged_day(s, p.d0, p.w, p.thr);
+  if (f >= 0) {
+    const int end = p.first + p.count;
+    ++s->n_late_flags;
+    PS_TRY(recover_from_flag(s, f, end));
+    for (int d = f + 1; d < end; ++d) PS_TRY(run_day(s, d, true, p.negval, p.stat_scale));
+  }
+  PS_TRY(finish_run(s, p.first, p.count, f >= 0));
+  return resolve_refft(s);   // the last day's re-transform, if deferred: entry points find the spectrum in Ahat
+}
+
 static int chain_run_body(ps_solver* s, int first, int count, double negval, double stat_scale, int renorm);
 
 extern "C" int ps_chain_run(ps_solver* s, int first, int count, double negval, double stat_scale,
@@ -1818,6 +1997,7 @@ extern "C" int ps_chain_run(ps_solver* s, int first, int count, double negval, d
     s->kt_from = -1;
   }
   if (s) s->kt_lazy_from = -1;   // kernels this run never reached stay untransformed
+  if (s) s->kt_early = false;
   // the last day's re-transform, if it was deferred: every other entry point finds the spectrum in Ahat
   if (s && s->refft_pending) {
     if (rc == PS_OK) return resolve_refft(s);
@@ -1836,6 +2016,31 @@ static int chain_run_body(ps_solver* s, int first, int count, double negval, dou
   if (!s->kernels_on_device || first < 0 || count < 0 || first + count > s->nk)
     return ps_fail(PS_ERR_STATE, "chain_run: days [%d,%d) not uploaded (nk=%d)", first, first + count, s->nk);
   PS_HIP(hipSetDevice(s->device));
+  // The previous run's last window may still be unchecked (settle).  When this run covers the same single
+  // chunk of the same uploaded kernels in the same pipeline -- a sampler chain or an ensemble member calling
+  // set_state + run_chain again -- its kernel staging goes into the queue FIRST: it depends on no state, and
+  // it rewrites kdense / Bhat with the values they hold, so a recovery that settle may still enqueue finds
+  // the spectra it needs.  The GPU then has ~0.5 ms of work (headline stack) while the host waits for the
+  // flags and enqueues the rest.  Only where the run would stage the whole chunk on the main stream anyway,
+  // whatever the check finds: a flag ends speculation (one transform_kernels for the chunk); no flag leaves
+  // the window hint, and a hinted run of up to PS_MAX_GROUP_DAYS + 3 days is one window with no second-stream
+  // split (PS_FIRST_WINDOW unset); a run that cannot be hinted splits only from kt_split + 8 days on.  The
+  // low-priority kernel transforms of long un-hinted runs (section 4.1d) are never replaced by this.
+  // Anything else: settle first, then the usual order.
+  const int ks = s->cfg.kt_split;
+  const bool can_hint = count >= 4 && !s->cfg.no_window_hint && colfull_chains(s);
+  const bool whole_unhinted = ks == 0 || count < (ks > 0 ? ks : 14) + 8;
+  const bool whole_hinted = ks >= 0 ? (ks == 0 || count < ks + 4)
+                                    : (s->cfg.first_window <= 0 && count < PS_MAX_GROUP_DAYS + 4);
+  const bool stays_whole = can_hint ? whole_hinted : whole_unhinted;
+  if (s->pend.on && !s->cfg.no_defer_check && s->pend.first == first && s->pend.count == count &&
+      count <= s->chunk_days && s->tpipe && (s->spec_valid || want_full_column(s, first, count)) &&
+      stays_whole) {
+    PS_TRY(transform_kernels(s, first, count));
+    s->kt_early = true;
+    ++s->n_staged_early;
+  }
+  PS_TRY(settle(s));
   // sized for every uploaded day at once: a run continued in a second call must not lose the statistics
   // of the first (growing the buffers does not keep their contents)
   PS_TRY(ensure_stats(s, std::max(4, s->nk)));
@@ -2028,18 +2233,7 @@ static int chain_run_body(ps_solver* s, int first, int count, double negval, dou
   // with direct-sum kernels: 2650 against 2420 grid-days/s on the synthetic N = 4097 stack);
   // everything else -- broad prob_mass kernels, flagged days -- in the full-column pipeline
   // (Carnarvon R = 2048: 1040 -> 1440 grid-days/s).
-  if (s->tpipe_ok && !s->spec_valid) {
-    bool compact = direct_possible(s);
-    for (int d = first; d < first + count && compact; ++d) compact = day_is_compact(s, d);
-    // Compact kernels on a split column size have the direct-sum tiled route (4-day groups, no kernel
-    // spectra in HBM); it still wins where the full-column pass cannot chain days (state column + exchange
-    // buffer beyond LDS, L > 6400).  Everywhere else the full-column pipeline is ahead since the
-    // persistent row kernel and the pipelined kernel fetch: 10.5 against 11.7 ms per 30-day stack at 5184,
-    // 8.2 against 9.4 at 4608 (single-pass column sizes too: +6 % on the flag-heavy R = 400 Bayes chain).
-    bool want = !(s->split && compact) || colfull_chains(s);
-    if (s->cfg.tpipe >= 0) want = s->cfg.tpipe != 0;   // A/B knob
-    set_pipeline(s, want);
-  }
+  if (s->tpipe_ok && !s->spec_valid) set_pipeline(s, want_full_column(s, first, count));
   PS_TRY(ensure_spectrum(s));
   if (s->speculate && s->tpipe && colfull_chains(s) && hint >= count && count >= 4 && !s->cfg.no_window_hint) {
     // windows of up to PS_MAX_GROUP_DAYS days, the whole run if it fits.  Measured on the 30-day stack
@@ -2060,6 +2254,11 @@ static int chain_run_body(ps_solver* s, int first, int count, double negval, dou
   bool guided = false;
   if (!hist.empty() && s->tpipe && colfull_chains(s))
     for (int i = 0; i + 1 < count && !guided; ++i) guided = !hist[i] && !hist[i + 1];
+  // The check of the run's last window may be left to settle(): fast mode on a stream of its own (no
+  // auto-mode front or helper), one chunk, full-column pipeline, blind speculation (a guided run mixes in
+  // days that carry their own re-transform).  PS_NO_DEFER_CHECK=1: A/B knob.
+  const bool defer_ok = !s->cfg.no_defer_check && s->mode == PS_MODE_FAST && !s->auto_exact && !s->borrowed &&
+                        s->tpipe && s->speculate && !guided && count <= s->chunk_days;
   for (int c0 = first; c0 < first + count; c0 += s->chunk_days) {
     const int cn = std::min(s->chunk_days, first + count - c0);
     // Full-column pipeline, long chunk: only the kernels of the first three windows (2 + 4 + 8 days)
@@ -2069,7 +2268,9 @@ static int chain_run_body(ps_solver* s, int first, int count, double negval, dou
     const int split_days = s->cfg.kt_split >= 0 ? s->cfg.kt_split : (hinted ? s->spec_window : 14);   // = the first window(s); A/B knob: 0 = off
     const bool lazy_tail = s->auto_exact && hint_abs >= c0 && hint_abs + 2 < c0 + cn &&
                            !s->cfg.no_lazy_kt;   // see the branch below (A/B knob)
-    if (!lazy_tail && s->tpipe && s->speculate && split_days > 0 && cn >= split_days + (hinted ? 4 : 8)) {
+    if (s->kt_early) {
+      s->kt_early = false;   // the whole chunk was staged on the main stream ahead of settle (see above)
+    } else if (!lazy_tail && s->tpipe && s->speculate && split_days > 0 && cn >= split_days + (hinted ? 4 : 8)) {
       if (!s->stream2) {
         int lo = 0, hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);   // lo = numerically greatest = lowest priority
@@ -2106,20 +2307,7 @@ static int chain_run_body(ps_solver* s, int first, int count, double negval, dou
     } else {
       PS_TRY(transform_kernels(s, c0, cn));
     }
-    auto day = [&](int d, bool with_refft) -> int {
-      PS_TRY(kernels_ready(s, d));
-      const cplx* B = s->Bhat.p + (size_t)(d - s->bhat_first) * s->Pf * s->ld;
-      double* rec = s->recs[PS_REC_CHAIN][d];
-      PS_TRY(conv_inv(s, B, s->Ahat.p, 1, rec, d, negval, stat_scale, s->krange.p + 2 * d));
-      if (with_refft) {
-        // full-column pipeline: only the row half now, the column half inside the next day's pass
-        // (PS_NO_DEFER_REFFT=1: A/B knob)
-        const bool defer = !s->cfg.no_defer_refft && !s->cfg.tpipe_split;
-        if (s->tpipe && defer && rs_colfull_alt_ok(s->rs_r2, s->rs_r3)) PS_TRY(refft_rows_if_flag(s, rec, d));
-        else PS_TRY(refft_if_flag(s, rec, s->Ahat.p, d));
-      }
-      return PS_OK;
-    };
+    auto day = [&](int d, bool with_refft) -> int { return run_day(s, d, with_refft, negval, stat_scale); };
     // Speculation on the boundary flag (CalcSol.py:200-201): windows of days are enqueued
     // WITHOUT the three flag-conditional re-FFT launches (~6 us each even when they do
     // nothing) and their pad maxima are copied to pinned host memory behind them.  The host
@@ -2199,14 +2387,22 @@ static int chain_run_body(ps_solver* s, int first, int count, double negval, dou
       }
       if (q.empty()) break;
       const Win x = q.front();
+      if (defer_ok && q.size() == 1 && d >= c0 + cn) {
+        // Only the run's last window is unchecked and nothing is left to enqueue: the host does not wait
+        // for it.  settle() checks it -- and recovers, should it hold a flag -- when the next call that
+        // observes or disturbs this run comes in; a set_state + run_chain on the same kernels queues its
+        // first kernels before that, so the GPU goes from this run into the next without a gap.
+        s->pend.on = true;
+        s->pend.first = first; s->pend.count = count;
+        s->pend.d0 = x.d0; s->pend.w = x.w; s->pend.ev = x.ev;
+        s->pend.negval = negval; s->pend.stat_scale = stat_scale;
+        s->pend.thr = flag_thr;
+        ++s->n_deferred;
+        return PS_OK;
+      }
       q.pop_front();
       PS_HIP(hipEventSynchronize(s->spec_ev[x.ev]));
-      int f = -1;
-      for (int i = 0; i < x.w && f < 0; ++i) {
-        double m;
-        __builtin_memcpy(&m, &s->hflags[x.d0 + i], sizeof(double));
-        if (m > flag_thr) f = x.d0 + i;
-      }
+      const int f = first_flagged_day(s, x.d0, x.w, flag_thr);
       if (f < 0) continue;
       q.clear();   // whatever was enqueued after day f is void; stream order keeps it harmless
       flagged_at = f;
@@ -2215,38 +2411,17 @@ static int chain_run_body(ps_solver* s, int first, int count, double negval, dou
         __builtin_memcpy(&mf, &s->hflags[f], sizeof(double));
         return auto_handover(s, first, f, first + count, negval, stat_scale, renorm, mf);
       }
-      s->refft_pending = nullptr;   // belongs to a day behind f
       guided = false;
-      PS_TRY(fwd2d(s, s->recs[PS_REC_CHAIN][f], 0, s->N, map_plain(s->N, s->Pf), map_plain(s->N, s->Pf),
-                   s->Ahat.p, 1, nullptr));
-      if (d - f - 1 > 0)
-        PS_HIP(hipMemsetAsync(s->padmax.p + f + 1, 0, (size_t)(d - f - 1) * sizeof(unsigned long long), s->stream));
-      s->speculate = false;
+      PS_TRY(recover_from_flag(s, f, d));
       d = f + 1;
     }
   }
-  if (s->speculate && flagged_at < 0) s->noflag_hint = count;
-  if (!s->auto_exact && !s->speculate && count >= 2 && !s->cfg.no_flag_history) {
-    if (s->hhist_n < count) {
-      if (s->hist_ev) PS_HIP(hipEventSynchronize(s->hist_ev));   // an earlier run's copy may still be on its way
-      if (s->hhist) (void)hipHostFree(s->hhist);
-      s->hhist = nullptr;
-      s->hhist_n = 0;
-      PS_HIP(hipHostMalloc((void**)&s->hhist, (size_t)(count + 32) * sizeof(unsigned long long), hipHostMallocDefault));
-      s->hhist_n = count + 32;
-    }
-    if (!s->hist_ev) PS_HIP(hipEventCreateWithFlags(&s->hist_ev, hipEventDisableTiming));
-    PS_HIP(hipMemcpyAsync(s->hhist, s->padmax.p + first, (size_t)count * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream));
-    PS_HIP(hipEventRecord(s->hist_ev, s->stream));
-    s->hist_first = first;
-    s->hist_count = count;
-  }
-  return PS_OK;
+  return finish_run(s, first, count, flagged_at >= 0);
 }
 
 extern "C" int ps_chain_stats(ps_solver* s, int first, int count, ps_day_stats* out) {
   if (!s || !out || first < 0 || count < 0 || first + count > s->nstat) return ps_fail(PS_ERR_BAD_ARG, "chain_stats: bad range");
-  PS_HIP(hipSetDevice(s->device));
+  PS_TRY(enter(s));
   if (s->auto_exact && s->auto_first >= 0 && first + count > s->auto_first) {
     // runs of days by owner: this solver (clean prefix), the wide helper, the fold child
     int d = first;
@@ -2286,7 +2461,7 @@ extern "C" int ps_solver_fftconv2_coo(ps_solver* s, const int32_t* row, const in
   if (!s->have_state) return ps_fail(PS_ERR_STATE, "fftconv2 before set_state");
   if (kshape < 1 || kshape % 2 == 0) return ps_fail(PS_ERR_BAD_SHAPE, "kernel shape %d must be odd (CalcSol.py:58)", kshape);
   if (kshape > s->Pf) return ps_fail(PS_ERR_BAD_SHAPE, "kernel shape %d larger than the pad %d", kshape, s->Pf);
-  PS_HIP(hipSetDevice(s->device));
+  PS_TRY(enter(s));
   PS_TRY(check_coo(row, col, nnz, kshape, "kernel"));
   PS_TRY(ensure_spectrum(s));
   PS_TRY(upload_coo(s, row, col, val, nnz));
@@ -2309,7 +2484,7 @@ extern "C" int ps_solver_get_cursol(ps_solver* s, double negval, double stat_sca
   if (!s) return ps_fail(PS_ERR_BAD_ARG, "null solver");
   if (s->mode == PS_MODE_FOLD) return ps_fail(PS_ERR_UNSUPPORTED, "get_cursol: PS_MODE_FOLD offers the chain API only");
   if (!s->have_state) return ps_fail(PS_ERR_STATE, "get_cursol before set_state");
-  PS_HIP(hipSetDevice(s->device));
+  PS_TRY(enter(s));
   PS_TRY(ensure_record(s, PS_REC_CHAIN, 0));
   PS_TRY(ensure_temps(s, 1));
   PS_TRY(ensure_spectrum(s));
@@ -2330,7 +2505,7 @@ extern "C" int ps_solver_back_solve(ps_solver* s, int nfilt, const int64_t* off,
   if (!s->have_state) return ps_fail(PS_ERR_STATE, "back_solve before set_state");
   if (s->N % 2 == 0) return ps_fail(PS_ERR_BAD_SHAPE, "back_solve needs an odd domain (filters are N x N)");
   if (2 * (s->N / 2) + 1 > s->Pf) return ps_fail(PS_ERR_BAD_SHAPE, "filter larger than the pad");
-  PS_HIP(hipSetDevice(s->device));
+  PS_TRY(enter(s));
   const size_t spec = (size_t)s->Pf * s->ld;
   const int K = s->N, M = K / 2;
   PS_TRY(s->Chat.ensure(spec));
@@ -2433,7 +2608,7 @@ extern "C" int ps_chain_run_release(ps_solver* s, int first, int count, double n
   const int ndays = s->nk - nfilt;          // day kernels [0, ndays), filters [ndays, nk)
   if (!s->kernels_on_device || ndays < 0 || first + count > ndays)
     return ps_fail(PS_ERR_STATE, "run_release: days [%d,%d) + %d filters not uploaded (nk=%d)", first, first + count, nfilt, s->nk);
-  PS_HIP(hipSetDevice(s->device));
+  PS_TRY(enter(s));
   if (certified) *certified = 1;
   const size_t spec = (size_t)s->Pf * s->ld;
   const int per = nuse + 1;                  // fields per unit of work: the cohort's + nuse back-solves
@@ -2542,7 +2717,7 @@ extern "C" int ps_chain_block_prefix(ps_solver* s, int first, int count, const v
   if (!s->have_state) return ps_fail(PS_ERR_STATE, "block_prefix before set_state");
   if (!s->kernels_on_device || first + count > s->nk)
     return ps_fail(PS_ERR_STATE, "block_prefix: days [%d,%d) not uploaded (nk=%d)", first, first + count, s->nk);
-  PS_HIP(hipSetDevice(s->device));
+  PS_TRY(enter(s));
   PS_TRY(resolve_refft(s));
   if (!s->spec_valid) set_pipeline(s, true);
   if (!s->tpipe) return ps_fail(PS_ERR_UNSUPPORTED, "block_prefix: the state's spectrum is held for the tiled pipeline; set the state again");
@@ -2574,7 +2749,7 @@ extern "C" int ps_chain_block_finish(ps_solver* s, int first, int count, int npr
   if (!s || nprev < 0 || (nprev > 0 && !prev_totals)) return ps_fail(PS_ERR_BAD_ARG, "block_finish: bad arguments");
   if (s->blk_first != first || s->blk_count != count || count < 1)
     return ps_fail(PS_ERR_STATE, "block_finish: days [%d,%d) were not prepared by block_prefix", first, first + count);
-  PS_HIP(hipSetDevice(s->device));
+  PS_TRY(enter(s));
   const size_t spec = (size_t)s->Pf * s->ld;
   const int64_t n = (int64_t)s->H * s->Pf;
   PS_TRY(ensure_stats(s, std::max(4, s->nk)));
@@ -2641,7 +2816,7 @@ static int get_record(ps_solver* s, int kind, int idx, double** out) {
 extern "C" int ps_record_stats(ps_solver* s, int kind, int idx, double negval, double stat_scale,
                                int renorm, ps_day_stats* out) {
   if (!s || !out) return ps_fail(PS_ERR_BAD_ARG, "record_stats: bad arguments");
-  PS_HIP(hipSetDevice(s->device));
+  PS_TRY(enter(s));
   double* rec;
   PS_TRY(get_record(s, kind, idx, &rec));
   PS_TRY(ensure_stats(s, 4));
@@ -2664,7 +2839,7 @@ static int fetch_sparse(ps_solver* s, int kind, int idx, double negval, double s
                         double post_scale, int32_t* row, int32_t* indptr, int32_t* col, double* val,
                         int64_t cap, int64_t* nnz_out) {
   if (!s) return ps_fail(PS_ERR_BAD_ARG, "null solver");
-  PS_HIP(hipSetDevice(s->device));
+  PS_TRY(enter(s));
   double* rec;
   PS_TRY(get_record(s, kind, idx, &rec));
   PS_TRY(ensure_stats(s, 4));
@@ -2720,7 +2895,7 @@ extern "C" int ps_record_fetch_csr(ps_solver* s, int kind, int idx, double negva
 
 extern "C" int ps_record_fetch_dense(ps_solver* s, int kind, int idx, double* out) {
   if (!s || !out) return ps_fail(PS_ERR_BAD_ARG, "fetch_dense: bad arguments");
-  PS_HIP(hipSetDevice(s->device));
+  PS_TRY(enter(s));
   double* rec;
   PS_TRY(get_record(s, kind, idx, &rec));
   PS_HIP(hipMemcpyAsync(out, rec, (size_t)s->N * s->N * sizeof(double), hipMemcpyDeviceToHost, s->stream));
@@ -2732,7 +2907,7 @@ extern "C" int ps_record_gather(ps_solver* s, int kind, int idx, int64_t n, cons
                                 const int32_t* cols, double scale, double negval, double* out) {
   if (!s || n < 0 || (n > 0 && (!rows || !cols || !out))) return ps_fail(PS_ERR_BAD_ARG, "record_gather: bad arguments");
   if (n == 0) return PS_OK;
-  PS_HIP(hipSetDevice(s->device));
+  PS_TRY(enter(s));
   double* rec;
   PS_TRY(get_record(s, kind, idx, &rec));
   PS_TRY(check_coo(rows, cols, n, s->N, "gather point"));
@@ -2756,7 +2931,7 @@ extern "C" int ps_record_gather_multi(ps_solver* s, int nrec, const int32_t* kin
   if (!s || nrec < 0 || n < 0 || (nrec > 0 && (!kind || !idx)) || (n > 0 && nrec > 0 && (!rows || !cols || !out)))
     return ps_fail(PS_ERR_BAD_ARG, "record_gather_multi: bad arguments");
   if (n == 0 || nrec == 0) return PS_OK;
-  PS_HIP(hipSetDevice(s->device));
+  PS_TRY(enter(s));
   std::vector<const double*> ptrs(nrec);
   for (int r = 0; r < nrec; ++r) {
     double* rec;
@@ -2783,7 +2958,7 @@ extern "C" int ps_record_gather_multi(ps_solver* s, int nrec, const int32_t* kin
 
 extern "C" int ps_weighted_sum(ps_solver* s, int n, const int32_t* kind, const int32_t* idx, const double* w) {
   if (!s || n < 1 || !kind || !idx || !w) return ps_fail(PS_ERR_BAD_ARG, "weighted_sum: bad arguments");
-  PS_HIP(hipSetDevice(s->device));
+  PS_TRY(enter(s));
   std::vector<const double*> ptrs(n);
   for (int d = 0; d < n; ++d) {
     double* r;
@@ -2808,7 +2983,7 @@ extern "C" int ps_solver_get_spectrum(ps_solver* s, double* out) {
   if (!s || !out) return ps_fail(PS_ERR_BAD_ARG, "get_spectrum: bad arguments");
   if (s->mode == PS_MODE_FOLD) return ps_fail(PS_ERR_UNSUPPORTED, "get_spectrum: PS_MODE_FOLD offers the chain API only");
   if (!s->have_state) return ps_fail(PS_ERR_STATE, "get_spectrum before set_state");
-  PS_HIP(hipSetDevice(s->device));
+  PS_TRY(enter(s));
   if (s->tpipe) {   // the P x P spectrum interface is row-major: tiled pipeline
     if (s->spec_valid) return ps_fail(PS_ERR_UNSUPPORTED, "get_spectrum: the state is held column-major (full-column pipeline)");
     set_pipeline(s, false);
@@ -2829,7 +3004,7 @@ extern "C" int ps_solver_get_spectrum(ps_solver* s, double* out) {
 extern "C" int ps_solver_set_spectrum(ps_solver* s, const double* in) {
   if (!s || !in) return ps_fail(PS_ERR_BAD_ARG, "set_spectrum: bad arguments");
   if (s->mode == PS_MODE_FOLD) return ps_fail(PS_ERR_UNSUPPORTED, "set_spectrum: PS_MODE_FOLD offers the chain API only");
-  PS_HIP(hipSetDevice(s->device));
+  PS_TRY(enter(s));
   set_pipeline(s, false);   // row-major half spectrum
   const size_t full = (size_t)s->Pf * s->Pf;
   DevBuf<cplx> tmp;
@@ -2850,6 +3025,7 @@ extern "C" int ps_solver_set_spectrum(ps_solver* s, const double* in) {
 // ------------------------------------------------------------------- options
 extern "C" int ps_solver_set_option(ps_solver* s, const char* key, double value) {
   if (!s || !key) return ps_fail(PS_ERR_BAD_ARG, "set_option: bad arguments");
+  PS_TRY(enter(s));   // the last run ends under the options it began with
   const int rc = ps_config_set(&s->cfg, key, value, true);
   if (rc == -1) return ps_fail(PS_ERR_BAD_ARG, "set_option: unknown option %s", key);
   if (rc == -2) return ps_fail(PS_ERR_STATE, "set_option: %s takes effect when a solver is created", key);
@@ -2887,7 +3063,7 @@ static int prof_drain(ps_solver* s) {
 
 extern "C" int ps_prof_enable(ps_solver* s, int on) {
   if (!s) return ps_fail(PS_ERR_BAD_ARG, "null solver");
-  PS_HIP(hipSetDevice(s->device));
+  PS_TRY(enter(s));
   PS_TRY(prof_drain(s));
   for (int i = 0; i < PS_PROF_NCLS; ++i) { s->prof_ms[i] = 0; s->prof_cnt[i] = 0; s->prof_seen[i] = 0; s->prof_days[i] = 0; }
   s->prof_on = on != 0;
@@ -2899,7 +3075,7 @@ extern "C" int ps_prof_enable(ps_solver* s, int on) {
 
 extern "C" int ps_prof_read(ps_solver* s, int ncls, double* total_ms, int64_t* count) {
   if (!s || !total_ms || !count) return ps_fail(PS_ERR_BAD_ARG, "prof_read: bad arguments");
-  PS_HIP(hipSetDevice(s->device));
+  PS_TRY(enter(s));
   PS_TRY(prof_drain(s));
   for (int i = 0; i < ncls; ++i) {
     total_ms[i] = i < PS_PROF_NCLS ? s->prof_ms[i] : 0.0;
@@ -2910,7 +3086,7 @@ extern "C" int ps_prof_read(ps_solver* s, int ncls, double* total_ms, int64_t* c
 
 extern "C" int ps_prof_read_days(ps_solver* s, int ncls, int64_t* days) {
   if (!s || !days) return ps_fail(PS_ERR_BAD_ARG, "prof_read_days: bad arguments");
-  PS_HIP(hipSetDevice(s->device));
+  PS_TRY(enter(s));
   PS_TRY(prof_drain(s));
   for (int i = 0; i < ncls; ++i) days[i] = i < PS_PROF_NCLS ? s->prof_days[i] : 0;
   return PS_OK;
@@ -2918,7 +3094,7 @@ extern "C" int ps_prof_read_days(ps_solver* s, int ncls, int64_t* days) {
 
 extern "C" int ps_prof_read_launches(ps_solver* s, int ncls, int64_t* launches) {
   if (!s || !launches) return ps_fail(PS_ERR_BAD_ARG, "prof_read_launches: bad arguments");
-  PS_HIP(hipSetDevice(s->device));
+  PS_TRY(enter(s));
   PS_TRY(prof_drain(s));
   // the multi-day classes are all timed; of the others every prof_every-th launch is, prof_seen counts all
   for (int i = 0; i < ncls; ++i)
@@ -2943,6 +3119,19 @@ extern "C" int ps_prof_read_owner(ps_solver* s, int owner, int ncls, double* tot
 extern "C" int ps_solver_kernels_direct(ps_solver* s) { return s && s->kt_direct ? 1 : 0; }
 
 extern "C" int ps_solver_pipeline(ps_solver* s) { return s && s->tpipe ? 1 : 0; }
+
+// read-only: settles nothing
+extern "C" int ps_solver_deferred_info(ps_solver* s, int* pending, int64_t* counts) {
+  if (!s) return ps_fail(PS_ERR_BAD_ARG, "null solver");
+  if (pending) *pending = s->pend.on ? 1 : 0;
+  if (counts) {
+    counts[0] = s->n_deferred;
+    counts[1] = s->n_late_flags;
+    counts[2] = s->n_staged_early;
+    counts[3] = s->n_staged_uploads;
+  }
+  return PS_OK;
+}
 
 extern "C" int ps_solver_auto_route(ps_solver* s, int first, int count, int32_t* owner) {
   if (!s || !owner || first < 0 || count < 0) return ps_fail(PS_ERR_BAD_ARG, "auto_route: bad arguments");
@@ -2972,10 +3161,11 @@ int ps_solver_device_internal(ps_solver* s) { return s->device; }
 // ps_summary.hip: one record of s with the device statistics of its day.  The chain leaves the
 // statistics to ps_chain_stats (finalize_days); with want_stats the day's are finalised here, on the
 // stream the record was written on (an auto-mode day may belong to a helper: its statistics are the
-// helper's, the record and the stream the front's).  Enqueues only: no host synchronisation.
+// helper's, the record and the stream the front's).  Enqueues only: no host synchronisation, except for a
+// last run whose final window is still unchecked (settle).
 int ps_solver_record_internal(ps_solver* s, int kind, int idx, int want_stats, PsRecordView* out) {
   if (!s || !out) return ps_fail(PS_ERR_BAD_ARG, "record view: bad arguments");
-  PS_HIP(hipSetDevice(s->device));
+  PS_TRY(enter(s));
   double* rec;
   PS_TRY(get_record(s, kind, idx, &rec));
   out->rec = rec;

@@ -409,6 +409,16 @@ class HipSolve():
         '''True when the solver runs the full-column pipeline -- measurement aid.'''
         return bool(self._lib.ps_solver_pipeline(self._h))
 
+    def deferred_info(self):
+        '''Measurement aid (settles nothing): whether the last run_chain's final window is still unchecked,
+        and how often this solver deferred a check, found a flag in one, queued its kernel staging ahead of one,
+        and uploaded host triplets through its pinned staging.'''
+        pending = C.c_int32(0)
+        cnt = np.zeros(4, dtype=np.int64)
+        L.check(self._lib.ps_solver_deferred_info(self._h, C.byref(pending), L.p_i64(cnt)))
+        return {'pending': bool(pending.value), 'deferred': int(cnt[0]), 'late_flags': int(cnt[1]),
+                'staged_early': int(cnt[2]), 'staged_uploads': int(cnt[3])}
+
     def auto_info(self):
         '''PS_MODE_AUTO: (first chain day of the last run_chain that ran on the folded reference
         torus, or -1 when every day was clean and ran on the fast torus; FFT size of the fold
