@@ -496,6 +496,47 @@ int ps_arrival_reset(ps_arrival* a);
 int ps_arrival_prof(ps_arrival* a, int enable, double* add_ms, int64_t* adds, double* map_ms, int64_t* maps);
 void ps_arrival_destroy(ps_arrival* a);
 
+/* ---- projections over time: emergence and cumulative exposure of one member, as maps ----
+ * (the map-level form of Bayes_funcs.popdensity_to_emergence, which projects at the observation cells only).
+ * A handle lives on one device and holds a weight matrix W[nout][nin] (row-major, 1 <= nin <= 32 input
+ * records, 1 <= nout <= 32 outputs, every weight finite and >= 0, no row all zeros: PS_ERR_BAD_ARG
+ * otherwise), uploaded once at create, and nout fp64 output fields Y[e][pitch] (pitch as ps_summary).  For
+ * one member, v_d(c) is the value ps_summary_add adds for input record d (same arguments, same value bit for
+ * bit), and an apply overwrites every cell of every output with
+ *   Y_e(c) = sum over d of W[e][d] * v_d(c)
+ * summed from +0.0 in ascending d with the product and the sum rounded separately (acc = acc + w * v in
+ * IEEE double, never fused); a zero weight changes no bit, so the numpy loop that skips zero weights gives
+ * the same bits.  One thread owns a pair of cells and a tile of 8 outputs; a record is read once per tile
+ * that has a non-zero weight for it.  No atomics: the same call gives the same bits.  The full size,
+ * nout * pitch * 8 B plus the weight tables, is checked against the free device memory first: PS_ERR_OOM
+ * before anything is allocated.  Every operation records an event the next one waits on, whichever stream
+ * it runs on (the solver's for apply, the handle's own for fetch and gather, the accumulator's for
+ * ps_summary_add_project and ps_hist_add_project). */
+typedef struct ps_project ps_project;
+int ps_project_create(int device, int N, int nin, int nout, const double* W /* nout x nin */, ps_project** out);
+/* Project the records of solver s (same device, same N; arguments as ps_summary_add, nin must equal the
+ * handle's): one launch on the solver's stream, no host synchronisation, nothing copied or allocated. */
+int ps_project_apply(ps_project* p, ps_solver* s, int nin, const int32_t* kind, const int32_t* idx,
+                     const double* stat_scale, const double* post_scale, const int32_t* use_delta, double negval);
+/* one output field to the host (synchronises).  PS_ERR_STATE before the first apply. */
+int ps_project_fetch(ps_project* p, int e, double* out /* N*N */);
+/* the outputs at n listed cells: out[e * n + k] = Y_e(rows[k], cols[k]) (synchronises).  PS_ERR_BAD_ARG for
+ * a cell outside the domain, PS_ERR_STATE before the first apply. */
+int ps_project_gather(ps_project* p, int64_t n, const int32_t* rows, const int32_t* cols, double* out /* nout x n */);
+/* any pointer may be NULL */
+int ps_project_info(ps_project* p, int* N, int* nin, int* nout, int64_t* applies);
+/* measurement: HIP-event timing of the apply launches.  enable 1 on, 0 off, < 0 unchanged; total_ms /
+ * launches (either may be NULL) receive the timed launches so far (synchronises). */
+int ps_project_prof(ps_project* p, int enable, double* total_ms, int64_t* launches);
+void ps_project_destroy(ps_project* p);
+/* One member with weight >= 1 whose values are the projection's current outputs: slot e of the accumulator
+ * takes Y_e, through the accumulator's own add kernel and update rule (ps_summary_add / ps_hist_add), on the
+ * accumulator's stream behind the projection's last operation; the projection's next apply waits for it.
+ * The accumulator's slot count must equal the projection's nout, device and N must agree (PS_ERR_BAD_ARG,
+ * nothing enqueued); PS_ERR_STATE before the projection's first apply.  Weight and members advance as in add. */
+int ps_summary_add_project(ps_summary* a, ps_project* p, uint32_t weight);
+int ps_hist_add_project(ps_hist* h, ps_project* p, uint32_t weight);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,6 +159,15 @@ SIGNATURES = {
     'ps_arrival_reset': (C.c_int, [_VP]),
     'ps_arrival_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P, _F64P, _I64P]),
     'ps_arrival_destroy': (None, [_VP]),
+    'ps_project_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _F64P, C.POINTER(_VP)]),
+    'ps_project_apply': (C.c_int, [_VP, _VP, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P, C.c_double]),
+    'ps_project_fetch': (C.c_int, [_VP, C.c_int, _F64P]),
+    'ps_project_gather': (C.c_int, [_VP, C.c_int64, _I32P, _I32P, _F64P]),
+    'ps_project_info': (C.c_int, [_VP, _I32P, _I32P, _I32P, _I64P]),
+    'ps_project_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P]),
+    'ps_project_destroy': (None, [_VP]),
+    'ps_summary_add_project': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_hist_add_project': (C.c_int, [_VP, _VP, C.c_uint32]),
 }
 
 _lib = None

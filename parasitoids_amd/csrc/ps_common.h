@@ -124,6 +124,18 @@ struct PsRecordView {
 };
 int ps_solver_record_internal(ps_solver* s, int kind, int idx, int want_stats, PsRecordView* out);
 
+// the output fields of a projection that ps_summary.hip and ps_hist.hip accumulate (ps_project.hip);
+// PS_ERR_STATE before the first apply.  A reader orders its stream behind the projection's last operation
+// (wait), and the projection's next apply behind the read (mark).
+struct PsProjectView {
+  const double* Y;              // [nout][pitch], device
+  int64_t pitch;
+  int N, nout, device;
+};
+int ps_project_view_internal(ps_project* p, PsProjectView* out);
+int ps_project_wait_internal(ps_project* p, hipStream_t stream);
+int ps_project_mark_internal(ps_project* p, hipStream_t stream);
+
 // the value one solver record holds at a cell, as ps_record_fetch_* returns it (k_compact_rows,
 // chain_kernels.h), 0 where it returns no entry; shared by ps_summary.hip and ps_linspread.hip
 __device__ inline double ps_record_value(double r, double stat_scale, double post_scale, double delta, double negval) {

@@ -290,6 +290,31 @@ extern "C" int ps_hist_create(int device, int N, int nslot, int nedge, const dou
   return PS_OK;
 }
 
+// one member from the slot descriptors d (one per slot of the histogram), enqueued on `stream`
+static int hist_launch(ps_hist* a, const std::vector<HistSlot>& d, hipStream_t stream, double negval,
+                       uint32_t weight) {
+  const int nslot = a->nslot;
+  PS_TRY(hist_after_last(a, stream));
+  hipEvent_t e1 = nullptr;
+  PS_TRY(hist_prof_begin(a, a->prof_add, stream, &e1));
+  const int64_t npair = a->ncell / 2 + 1;   // the pairs and the tail cell's thread
+  const int threads = 256;
+  const int bx = (int)((npair + threads - 1) / threads);
+  for (int c0 = 0; c0 < nslot; c0 += PS_HIST_CHUNK) {
+    const int n = std::min(PS_HIST_CHUNK, nslot - c0);
+    HistSlots desc;
+    for (int i = 0; i < n; ++i) desc.s[i] = d[(size_t)(c0 + i)];
+    hipLaunchKernelGGL(k_hist_add, dim3(bx, n), dim3(threads), 0, stream, desc, a->d_edges, a->nedge, a->cnt, a->rng,
+                       a->ncell, a->pitch, negval, weight);
+    PS_HIP(hipGetLastError());
+  }
+  if (e1) PS_HIP(hipEventRecord(e1, stream));
+  PS_TRY(hist_mark_last(a, stream));
+  a->W += weight;
+  a->members += 1;
+  return PS_OK;
+}
+
 extern "C" int ps_hist_add(ps_hist* a, ps_solver* s, int nslot, const int32_t* kind, const int32_t* idx,
                            const double* stat_scale, const double* post_scale, const int32_t* use_delta, double negval,
                            uint32_t weight) {
@@ -313,25 +338,32 @@ extern "C" int ps_hist_add(ps_hist* a, ps_solver* s, int nslot, const int32_t* k
     d[i] = HistSlot{v.rec, v.stats, stat_scale[i], post_scale[i], i};
     stream = v.stream;
   }
-  PS_TRY(hist_after_last(a, stream));
-  hipEvent_t e1 = nullptr;
-  PS_TRY(hist_prof_begin(a, a->prof_add, stream, &e1));
-  const int64_t npair = a->ncell / 2 + 1;   // the pairs and the tail cell's thread
-  const int threads = 256;
-  const int bx = (int)((npair + threads - 1) / threads);
-  for (int c0 = 0; c0 < nslot; c0 += PS_HIST_CHUNK) {
-    const int n = std::min(PS_HIST_CHUNK, nslot - c0);
-    HistSlots desc;
-    for (int i = 0; i < n; ++i) desc.s[i] = d[(size_t)(c0 + i)];
-    hipLaunchKernelGGL(k_hist_add, dim3(bx, n), dim3(threads), 0, stream, desc, a->d_edges, a->nedge, a->cnt, a->rng,
-                       a->ncell, a->pitch, negval, weight);
-    PS_HIP(hipGetLastError());
-  }
-  if (e1) PS_HIP(hipEventRecord(e1, stream));
-  PS_TRY(hist_mark_last(a, stream));
-  a->W += weight;
-  a->members += 1;
-  return PS_OK;
+  return hist_launch(a, d, stream, negval, weight);
+}
+
+extern "C" int ps_hist_add_project(ps_hist* a, ps_project* p, uint32_t weight) {
+  if (!a || !p) return ps_fail(PS_ERR_BAD_ARG, "hist_add_project: bad arguments");
+  if (weight < 1) return ps_fail(PS_ERR_BAD_ARG, "hist_add_project: weight must be >= 1");
+  if (a->W + weight > 0xffffffffull)
+    return ps_fail(PS_ERR_BAD_ARG, "hist_add_project: total weight %llu would overflow the uint32 counts",
+                   (unsigned long long)(a->W + weight));
+  PsProjectView v;
+  PS_TRY(ps_project_view_internal(p, &v));
+  if (v.nout != a->nslot)
+    return ps_fail(PS_ERR_BAD_ARG, "hist_add_project: the projection has %d outputs, the histogram %d slots", v.nout,
+                   a->nslot);
+  if (v.device != a->device)
+    return ps_fail(PS_ERR_BAD_ARG, "hist_add_project: projection on device %d, histogram on device %d", v.device,
+                   a->device);
+  if (v.N != a->N)
+    return ps_fail(PS_ERR_BAD_ARG, "hist_add_project: projection domain %d, histogram domain %d", v.N, a->N);
+  PS_HIP(hipSetDevice(a->device));
+  // slot e takes Y_e: no statistics, both scales 1 and negval 0, so the value rule returns Y itself
+  std::vector<HistSlot> d((size_t)a->nslot);
+  for (int e = 0; e < a->nslot; ++e) d[(size_t)e] = HistSlot{v.Y + (int64_t)e * v.pitch, nullptr, 1.0, 1.0, e};
+  PS_TRY(ps_project_wait_internal(p, a->stream));
+  PS_TRY(hist_launch(a, d, a->stream, 0.0, weight));
+  return ps_project_mark_internal(p, a->stream);   // the next apply overwrites Y only after this read
 }
 
 extern "C" int ps_hist_merge(ps_hist* dst, ps_hist* src) {

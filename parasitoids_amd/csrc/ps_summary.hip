@@ -190,29 +190,10 @@ extern "C" int ps_summary_create(int device, int N, int nslot, int nthr, const d
   return PS_OK;
 }
 
-extern "C" int ps_summary_add(ps_summary* a, ps_solver* s, int nslot, const int32_t* kind, const int32_t* idx,
-                              const double* stat_scale, const double* post_scale, const int32_t* use_delta,
-                              double negval, uint32_t weight) {
-  if (!a || !s || !kind || !idx || !stat_scale || !post_scale || !use_delta)
-    return ps_fail(PS_ERR_BAD_ARG, "summary_add: bad arguments");
-  if (nslot != a->nslot) return ps_fail(PS_ERR_BAD_ARG, "summary_add: %d slots given, the summary has %d", nslot, a->nslot);
-  if (weight < 1) return ps_fail(PS_ERR_BAD_ARG, "summary_add: weight must be >= 1");
-  if (a->W + weight > 0xffffffffull)
-    return ps_fail(PS_ERR_BAD_ARG, "summary_add: total weight %llu would overflow the uint32 counts",
-                   (unsigned long long)(a->W + weight));
-  PS_HIP(hipSetDevice(a->device));
-  // every descriptor first: an add with a bad slot enqueues nothing
-  std::vector<SumSlot> d((size_t)nslot);
-  hipStream_t stream = nullptr;
-  for (int i = 0; i < nslot; ++i) {
-    PsRecordView v;
-    PS_TRY(ps_solver_record_internal(s, kind[i], idx[i], use_delta[i] != 0, &v));
-    if (v.device != a->device)
-      return ps_fail(PS_ERR_BAD_ARG, "summary_add: solver on device %d, summary on device %d", v.device, a->device);
-    if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "summary_add: solver domain %d, summary domain %d", v.N, a->N);
-    d[i] = SumSlot{v.rec, v.stats, stat_scale[i], post_scale[i], i};
-    stream = v.stream;
-  }
+// one member from the slot descriptors d (one per slot of the summary), enqueued on `stream`
+static int sum_launch(ps_summary* a, const std::vector<SumSlot>& d, hipStream_t stream, double negval,
+                      uint32_t weight) {
+  const int nslot = a->nslot;
   PS_TRY(after_last(a, stream));
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (a->prof_on) {
@@ -240,6 +221,57 @@ extern "C" int ps_summary_add(ps_summary* a, ps_solver* s, int nslot, const int3
   a->W += weight;
   a->members += 1;
   return PS_OK;
+}
+
+extern "C" int ps_summary_add(ps_summary* a, ps_solver* s, int nslot, const int32_t* kind, const int32_t* idx,
+                              const double* stat_scale, const double* post_scale, const int32_t* use_delta,
+                              double negval, uint32_t weight) {
+  if (!a || !s || !kind || !idx || !stat_scale || !post_scale || !use_delta)
+    return ps_fail(PS_ERR_BAD_ARG, "summary_add: bad arguments");
+  if (nslot != a->nslot) return ps_fail(PS_ERR_BAD_ARG, "summary_add: %d slots given, the summary has %d", nslot, a->nslot);
+  if (weight < 1) return ps_fail(PS_ERR_BAD_ARG, "summary_add: weight must be >= 1");
+  if (a->W + weight > 0xffffffffull)
+    return ps_fail(PS_ERR_BAD_ARG, "summary_add: total weight %llu would overflow the uint32 counts",
+                   (unsigned long long)(a->W + weight));
+  PS_HIP(hipSetDevice(a->device));
+  // every descriptor first: an add with a bad slot enqueues nothing
+  std::vector<SumSlot> d((size_t)nslot);
+  hipStream_t stream = nullptr;
+  for (int i = 0; i < nslot; ++i) {
+    PsRecordView v;
+    PS_TRY(ps_solver_record_internal(s, kind[i], idx[i], use_delta[i] != 0, &v));
+    if (v.device != a->device)
+      return ps_fail(PS_ERR_BAD_ARG, "summary_add: solver on device %d, summary on device %d", v.device, a->device);
+    if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "summary_add: solver domain %d, summary domain %d", v.N, a->N);
+    d[i] = SumSlot{v.rec, v.stats, stat_scale[i], post_scale[i], i};
+    stream = v.stream;
+  }
+  return sum_launch(a, d, stream, negval, weight);
+}
+
+extern "C" int ps_summary_add_project(ps_summary* a, ps_project* p, uint32_t weight) {
+  if (!a || !p) return ps_fail(PS_ERR_BAD_ARG, "summary_add_project: bad arguments");
+  if (weight < 1) return ps_fail(PS_ERR_BAD_ARG, "summary_add_project: weight must be >= 1");
+  if (a->W + weight > 0xffffffffull)
+    return ps_fail(PS_ERR_BAD_ARG, "summary_add_project: total weight %llu would overflow the uint32 counts",
+                   (unsigned long long)(a->W + weight));
+  PsProjectView v;
+  PS_TRY(ps_project_view_internal(p, &v));
+  if (v.nout != a->nslot)
+    return ps_fail(PS_ERR_BAD_ARG, "summary_add_project: the projection has %d outputs, the summary %d slots", v.nout,
+                   a->nslot);
+  if (v.device != a->device)
+    return ps_fail(PS_ERR_BAD_ARG, "summary_add_project: projection on device %d, summary on device %d", v.device,
+                   a->device);
+  if (v.N != a->N)
+    return ps_fail(PS_ERR_BAD_ARG, "summary_add_project: projection domain %d, summary domain %d", v.N, a->N);
+  PS_HIP(hipSetDevice(a->device));
+  // slot e takes Y_e: no statistics, both scales 1 and negval 0, so the value rule returns Y itself
+  std::vector<SumSlot> d((size_t)a->nslot);
+  for (int e = 0; e < a->nslot; ++e) d[(size_t)e] = SumSlot{v.Y + (int64_t)e * v.pitch, nullptr, 1.0, 1.0, e};
+  PS_TRY(ps_project_wait_internal(p, a->stream));
+  PS_TRY(sum_launch(a, d, a->stream, 0.0, weight));
+  return ps_project_mark_internal(p, a->stream);   // the next apply overwrites Y only after this read
 }
 
 extern "C" int ps_summary_merge(ps_summary* dst, ps_summary* src) {

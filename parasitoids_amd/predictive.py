@@ -12,7 +12,12 @@ bin edges (ps_hist_*, csrc/ps_hist.hip): quantile maps with their exact brackets
 bin edge chosen after the run.  `ArrivalMaps` keeps, on the device, per threshold and cell the weighted
 distribution of the first listed day on which a member's value reaches the threshold, and per member the
 number of cells reached by each day (ps_arrival_*, csrc/ps_arrival.hip): arrival probabilities and
-arrival-day quantile maps, and the posterior of the reached area.
+arrival-day quantile maps, and the posterior of the reached area.  `Projection` applies, on the device, a
+weight matrix along the time axis of one member's daily fields (ps_project_*, csrc/ps_project.hip): the
+emergence the field data measure (`emergence_weights`, the matrix of Bayes_funcs.popdensity_to_emergence) and
+the cumulative exposure (`exposure_weights`) as maps, which `SpreadSummary.for_projection` and
+`SpreadHistogram.for_projection` accumulate per member -- the spread of a sum over days cannot be rebuilt
+from the per-day moments.
 """
 import ctypes as C
 import json
@@ -22,6 +27,7 @@ import time
 
 import numpy as np
 
+from . import Bayes_funcs as BF
 from . import _lib as L
 from . import mcmc
 
@@ -30,6 +36,8 @@ DEFAULT_BINS = (1e-8, 1e6, 16)   # NEGVAL .. above any r_number, 16 bins per dec
 MAX_EDGES = 1024
 MAX_ARRIVAL_SLOTS = 32     # ps_arrival: the day slots of one launch's descriptors
 MAX_ARRIVAL_THRESHOLDS = 4
+MAX_PROJECT_IN = 32        # ps_project: the input records of one launch's descriptors
+MAX_PROJECT_OUT = 32
 
 
 def _day_slots(days):
@@ -58,30 +66,52 @@ class SpreadSummary():
     exceedance probability is kept.'''
 
     def __init__(self, pop_model, days=None, thresholds=()):
-        self._lib = L.load()
         self._h = L._VP()
-        self.pm = pop_model
-        self.days = list(range(len(pop_model.days)) if days is None else days)
-        if not self.days or min(self.days) < 0:
+        days = list(range(len(pop_model.days)) if days is None else days)
+        if not days or min(days) < 0:
             raise ValueError('days must be a non-empty list of model days >= 0')
+        self._setup(pop_model, days, thresholds, None)
+
+    @classmethod
+    def for_projection(cls, projection, thresholds=()):
+        '''A summary of `projection`'s outputs, one slot per output: `add(weight)` accumulates the outputs of
+        the projection's last `apply()`, and the accessors take the output index where the day-based summary
+        takes a day.'''
+        self = cls.__new__(cls)
+        self._h = L._VP()
+        self._setup(projection.pm, list(range(projection.nout)), thresholds, projection)
+        return self
+
+    def _setup(self, pop_model, days, thresholds, projection):
+        self._lib = L.load()
+        self.pm = pop_model
+        self.days = days
         self.thresholds = [float(t) for t in thresholds]
         self.N = 2 * int(pop_model.rad_res) + 1
         self.device = L.default_device() if pop_model.device is None else int(pop_model.device)
+        self._proj = projection
+        # slot of every day; of a projection the outputs that carry weight (the others are zero throughout)
+        keys = days if projection is None else projection.live
+        self._slot = {d: i for i, d in enumerate(keys)}
+        self._n = len(self._slot)
         thr = L.f64(self.thresholds if self.thresholds else [0.0])
-        L.check(self._lib.ps_summary_create(self.device, self.N, len(self.days), len(self.thresholds),
+        L.check(self._lib.ps_summary_create(self.device, self.N, self._n, len(self.thresholds),
                                             L.p_f64(thr), C.byref(self._h)))
-        n = len(self.days)
-        self._kind, self._idx, self._delta = _day_slots(self.days)
-        self._slot = {d: i for i, d in enumerate(self.days)}
-        self._n = n
+        if projection is None:
+            self._kind, self._idx, self._delta = _day_slots(self.days)
 
     def add(self, weight=1):
         '''Accumulate the last evaluation of the model with integer weight >= 1 (enqueued on the
-        solver's stream; no host synchronisation).'''
+        solver's stream; no host synchronisation).  On a projection: its last apply, on the summary's stream.'''
+        w = int(weight)
+        if self._proj is not None:
+            if w < 1:
+                raise ValueError('weight must be a positive integer')
+            L.check(self._lib.ps_summary_add_project(self._h, self._proj._h, w))
+            return
         pm = self.pm
         _check_evaluated(pm, self.days, 'summary')
         stat, post = _day_scales(pm, self.days)
-        w = int(weight)
         if w < 1:
             raise ValueError('weight must be a positive integer')
         L.check(self._lib.ps_summary_add(self._h, pm.solver._h, self._n, L.p_i32(self._kind), L.p_i32(self._idx),
@@ -89,7 +119,7 @@ class SpreadSummary():
 
     def merge(self, other):
         '''self += other (same device, domain, days and thresholds)'''
-        if list(other.days) != self.days:
+        if list(other.days) != self.days or other._slot != self._slot:
             raise ValueError('summaries over different days')
         L.check(self._lib.ps_summary_merge(self._h, other._h))
 
@@ -111,6 +141,8 @@ class SpreadSummary():
 
     def _fetch(self, day, what):
         if day not in self._slot:
+            if self._proj is not None and day in self.days:      # an output without weight
+                return np.zeros((self.N, self.N), dtype=np.float64)
             raise ValueError('day %r is not in the summary %s' % (day, self.days))
         out = np.empty((self.N, self.N), dtype=np.float64)
         L.check(self._lib.ps_summary_fetch(self._h, self._slot[day], int(what), L.p_f64(out)))
@@ -211,22 +243,40 @@ class SpreadHistogram():
     SpreadSummary adds; bin b = searchsorted(edges, v, side='right'), b = 0 .. B + 1.'''
 
     def __init__(self, pop_model, days=None, bins=DEFAULT_BINS, edges=None):
-        self._lib = L.load()
         self._h = L._VP()
-        self.pm = pop_model
-        self.days = list(range(len(pop_model.days)) if days is None else days)
-        if not self.days or min(self.days) < 0:
+        days = list(range(len(pop_model.days)) if days is None else days)
+        if not days or min(days) < 0:
             raise ValueError('days must be a non-empty list of model days >= 0')
+        self._setup(pop_model, days, bins, edges, None)
+
+    @classmethod
+    def for_projection(cls, projection, bins=DEFAULT_BINS, edges=None):
+        '''Histograms of `projection`'s outputs, one slot per output: `add(weight)` accumulates the outputs
+        of the projection's last `apply()`, and the accessors take the output index where the day-based
+        histogram takes a day.'''
+        self = cls.__new__(cls)
+        self._h = L._VP()
+        self._setup(projection.pm, list(range(projection.nout)), bins, edges, projection)
+        return self
+
+    def _setup(self, pop_model, days, bins, edges, projection):
+        self._lib = L.load()
+        self.pm = pop_model
+        self.days = days
         self._edges = bin_edges(bins, edges)
         self.bins = None if edges is not None else tuple(float(b) for b in bins)
         self.N = 2 * int(pop_model.rad_res) + 1
         self.device = L.default_device() if pop_model.device is None else int(pop_model.device)
+        self._proj = projection
+        # slot of every day; of a projection the outputs that carry weight (the others are zero throughout)
+        keys = days if projection is None else projection.live
+        self._slot = {d: i for i, d in enumerate(keys)}
         pitch = (self.N * self.N + 63) // 64 * 64
-        self.nbytes = len(self.days) * pitch * (self._edges.size + 1) * 4   # count planes + range words
-        L.check(self._lib.ps_hist_create(self.device, self.N, len(self.days), self._edges.size,
+        self.nbytes = len(self._slot) * pitch * (self._edges.size + 1) * 4   # count planes + range words
+        L.check(self._lib.ps_hist_create(self.device, self.N, len(self._slot), self._edges.size,
                                          L.p_f64(self._edges), C.byref(self._h)))
-        self._kind, self._idx, self._delta = _day_slots(self.days)
-        self._slot = {d: i for i, d in enumerate(self.days)}
+        if projection is None:
+            self._kind, self._idx, self._delta = _day_slots(self.days)
 
     @property
     def edges(self):
@@ -235,10 +285,15 @@ class SpreadHistogram():
     def add(self, weight=1):
         '''Accumulate the last evaluation of the model with integer weight >= 1 (enqueued on the
         solver's stream; no host synchronisation).'''
+        w = int(weight)
+        if self._proj is not None:       # the projection's last apply, on the histogram's stream
+            if w < 1:
+                raise ValueError('weight must be a positive integer')
+            L.check(self._lib.ps_hist_add_project(self._h, self._proj._h, w))
+            return
         pm = self.pm
         _check_evaluated(pm, self.days, 'histogram')
         stat, post = _day_scales(pm, self.days)
-        w = int(weight)
         if w < 1:
             raise ValueError('weight must be a positive integer')
         L.check(self._lib.ps_hist_add(self._h, pm.solver._h, len(self.days), L.p_i32(self._kind),
@@ -247,7 +302,7 @@ class SpreadHistogram():
 
     def merge(self, other):
         '''self += other (same device, domain, days and edges)'''
-        if list(other.days) != self.days:
+        if list(other.days) != self.days or other._slot != self._slot:
             raise ValueError('histograms over different days')
         L.check(self._lib.ps_hist_merge(self._h, other._h))
 
@@ -268,7 +323,10 @@ class SpreadHistogram():
         return self._info()[1]
 
     def _slot_of(self, day):
+        '''the device slot of a day; None for a projection's output without weight (zero throughout)'''
         if day not in self._slot:
+            if self._proj is not None and day in self.days:
+                return None
             raise ValueError('day %r is not in the histogram %s' % (day, self.days))
         return self._slot[day]
 
@@ -276,6 +334,10 @@ class SpreadHistogram():
         '''[B + 2, N, N] uint32: the weight of every bin per cell, bin 0 = W - the others'''
         s = self._slot_of(day)
         out = np.empty((self._edges.size + 1, self.N, self.N), dtype=np.uint32)
+        if s is None:
+            out[:] = 0
+            out[0] = np.uint32(self.total_weight)
+            return out
         for b in range(out.shape[0]):
             L.check(self._lib.ps_hist_fetch_counts(self._h, s, b, out[b].ctypes.data_as(C.POINTER(C.c_uint32))))
         return out
@@ -284,6 +346,11 @@ class SpreadHistogram():
         s = self._slot_of(day)
         if not 0.0 < float(p) <= 1.0:
             raise ValueError('quantile level %r is not in (0, 1]' % (p,))
+        if s is None:                    # every member's value is 0: bin 0 = [0, e_0)
+            for a, v in ((value, 0.0), (lower, 0.0), (upper, self._edges[0])):
+                if a is not None:
+                    a[:] = v
+            return
         ptr = [None if a is None else L.p_f64(a) for a in (value, lower, upper)]
         L.check(self._lib.ps_hist_quantile(self._h, s, float(p), *ptr))
 
@@ -306,7 +373,11 @@ class SpreadHistogram():
         if k.size != 1:
             raise ValueError('threshold %r is not a bin edge; exceedance is exact only at the edges' % (t,))
         out = np.empty((self.N, self.N), dtype=np.float64)
-        L.check(self._lib.ps_hist_exceed(self._h, self._slot_of(day), int(k[0]), L.p_f64(out)))
+        s = self._slot_of(day)
+        if s is None:
+            out[:] = 0.0
+            return out
+        L.check(self._lib.ps_hist_exceed(self._h, s, int(k[0]), L.p_f64(out)))
         return out
 
     def profile(self, enable=None):
@@ -522,6 +593,234 @@ class ArrivalMaps():
             pass
 
 
+def check_weights(weights, nin=None, zero_rows=False):
+    '''A projection's weight matrix as a float64 [nout, nin] array, by the rules of ps_project_create: 1..32
+    outputs, 1..32 inputs (nin if given), every weight finite and >= 0, and no row of all zeros unless
+    zero_rows (Projection keeps such rows off the device); ValueError otherwise'''
+    try:
+        W = np.array(weights, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('projection weights must be a matrix of numbers')
+    if W.ndim != 2:
+        raise ValueError('projection weights must be a matrix [outputs, inputs], got shape %r' % (W.shape,))
+    if not 1 <= W.shape[0] <= MAX_PROJECT_OUT:
+        raise ValueError('%d projection outputs; 1..%d are kept' % (W.shape[0], MAX_PROJECT_OUT))
+    if not 1 <= W.shape[1] <= MAX_PROJECT_IN:
+        raise ValueError('%d projection inputs; 1..%d fit one launch' % (W.shape[1], MAX_PROJECT_IN))
+    if nin is not None and W.shape[1] != nin:
+        raise ValueError('projection weights have %d columns for %d input days' % (W.shape[1], nin))
+    if not np.all(np.isfinite(W)) or not np.all(W >= 0):
+        raise ValueError('every projection weight must be finite and >= 0')
+    dead = np.flatnonzero(~(W != 0).any(axis=1))
+    if dead.size and not zero_rows:
+        raise ValueError('projection outputs %s have no non-zero weight' % (dead.tolist(),))
+    return np.ascontiguousarray(W)
+
+
+def check_in_days(in_days):
+    '''a projection's input days as a list of ints: 1..32 model days >= 0, strictly increasing'''
+    d = [int(x) for x in in_days]
+    if not 1 <= len(d) <= MAX_PROJECT_IN:
+        raise ValueError('%d projection input days; 1..%d fit one launch' % (len(d), MAX_PROJECT_IN))
+    if d[0] < 0 or any(b <= a for a, b in zip(d, d[1:])):
+        raise ValueError('projection input days must be model days >= 0, strictly increasing: %r' % (d,))
+    return d
+
+
+def emergence_weights(collection_day, in_days, obs_days=None):
+    '''[nout, len(in_days)] weights of the emergence projection of Bayes_funcs.popdensity_to_emergence, built
+    from Bayes_funcs._projection_matrix: leaves collected on `collection_day` (days post release) carry the
+    oviposition of the days [max(collection_day - 25, 0), collection_day), which emerges 19..25 days later.
+    obs_days=None: one output per day 0 .. 24 after the collection (the `emerg` matrix before binning);
+    else one output per observation day (days post release, strictly increasing, not before the collection;
+    nothing emerges after day collection_day + 24), each taking the emergence since the previous one as the
+    reference bins it.  An
+    output may be all zeros (no listed oviposition day emerges then).  ValueError if an oviposition day that
+    carries weight is missing from in_days.'''
+    cday = int(collection_day)
+    if cday < 1:
+        raise ValueError('collection day %r: no oviposition day before it' % (collection_day,))
+    horizon = BF.max_incubation_time
+    if obs_days is None:
+        obs = np.arange(cday, cday + horizon)
+    else:
+        obs = np.array([int(d) for d in obs_days], dtype=int)
+        if obs.size < 1 or obs[0] < cday or np.any(np.diff(obs) <= 0):
+            raise ValueError('observation days must be strictly increasing from day %d on: %r' % (cday, obs.tolist()))
+    in_days = [int(d) for d in in_days]
+    start = max(cday - horizon, 0)
+    M = BF._projection_matrix(start, cday, obs)            # [oviposition day - start, output]
+    W = np.zeros((len(obs), len(in_days)))
+    pos = {d: n for n, d in enumerate(in_days)}
+    for n, day in enumerate(range(start, cday)):
+        if day in pos:
+            W[:, pos[day]] = M[n]
+        elif np.any(M[n] != 0):
+            raise ValueError('oviposition day %d carries emergence weight and is not among the input days %r'
+                             % (day, in_days))
+    return W
+
+
+def exposure_weights(in_days, upto):
+    '''[len(upto), len(in_days)] weights of the cumulative exposure (wasp-days) up to each day of `upto`:
+    1 where in_days[d] <= upto[e], else 0'''
+    d = np.array([int(x) for x in in_days], dtype=int)
+    u = np.array([int(x) for x in upto], dtype=int)
+    return (d[None, :] <= u[:, None]).astype(np.float64)
+
+
+class Projection():
+    '''Y_e(c) = sum_d weights[e][d] v_d(c) of `pop_model`'s last evaluation, on the device: v_d the value
+    SpreadSummary adds for model day in_days[d] (strictly increasing, at most 32), weights [nout, nin] finite
+    and >= 0 (check_weights), at most 32 outputs.  The sum runs in ascending d from +0.0 with the product and
+    the sum rounded separately, so a numpy loop reproduces every bit.  An output whose weights are all zero
+    is zero throughout: it is kept off the device (`live` lists the others) and reads as zeros.'''
+
+    def __init__(self, pop_model, weights, in_days):
+        self._h = L._VP()
+        self.in_days = check_in_days(in_days)
+        self.weights = check_weights(weights, len(self.in_days), zero_rows=True)
+        self.nout = self.weights.shape[0]
+        self.live = [int(e) for e in np.flatnonzero((self.weights != 0).any(axis=1))]
+        if not self.live:
+            raise ValueError('the projection has no non-zero weight')
+        self._slot = {e: i for i, e in enumerate(self.live)}
+        self._lib = L.load()
+        self.pm = pop_model
+        self.N = 2 * int(pop_model.rad_res) + 1
+        self.device = L.default_device() if pop_model.device is None else int(pop_model.device)
+        pitch = (self.N * self.N + 63) // 64 * 64
+        self.nbytes = len(self.live) * pitch * 8            # the output fields
+        W = np.ascontiguousarray(self.weights[self.live])
+        L.check(self._lib.ps_project_create(self.device, self.N, len(self.in_days), len(self.live), L.p_f64(W),
+                                            C.byref(self._h)))
+        self._kind, self._idx, self._delta = _day_slots(self.in_days)
+
+    def apply(self):
+        '''Project the last evaluation of the model (enqueued on the solver's stream; no host
+        synchronisation); the outputs of the previous apply are overwritten.'''
+        pm = self.pm
+        _check_evaluated(pm, self.in_days, 'projection')
+        stat, post = _day_scales(pm, self.in_days)
+        L.check(self._lib.ps_project_apply(self._h, pm.solver._h, len(self.in_days), L.p_i32(self._kind),
+                                           L.p_i32(self._idx), L.p_f64(stat), L.p_f64(post), L.p_i32(self._delta),
+                                           NEGVAL))
+
+    @property
+    def applies(self):
+        n = C.c_int64()
+        L.check(self._lib.ps_project_info(self._h, None, None, None, C.byref(n)))
+        return n.value
+
+    def _e(self, e):
+        if not 0 <= int(e) < self.nout:
+            raise ValueError('output %r of %d' % (e, self.nout))
+        return int(e)
+
+    def field(self, e):
+        '''[N, N] float64: output e of the last apply'''
+        e = self._e(e)
+        if e not in self._slot:
+            return np.zeros((self.N, self.N), dtype=np.float64)
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        L.check(self._lib.ps_project_fetch(self._h, self._slot[e], L.p_f64(out)))
+        return out
+
+    def gather(self, rows, cols):
+        '''[nout, n] float64: every output of the last apply at the cells (rows[k], cols[k])'''
+        rows, cols = L.i32(np.asarray(rows).ravel()), L.i32(np.asarray(cols).ravel())
+        if rows.size != cols.size:
+            raise ValueError('%d rows and %d columns' % (rows.size, cols.size))
+        got = np.zeros((len(self.live), rows.size), dtype=np.float64)
+        L.check(self._lib.ps_project_gather(self._h, rows.size, L.p_i32(rows), L.p_i32(cols), L.p_f64(got)))
+        out = np.zeros((self.nout, rows.size), dtype=np.float64)
+        out[self.live] = got
+        return out
+
+    def profile(self, enable=None):
+        '''HIP-event time of the apply launches: (total ms, launches); enable switches it'''
+        ms, n = C.c_double(), C.c_int64()
+        L.check(self._lib.ps_project_prof(self._h, -1 if enable is None else int(bool(enable)), C.byref(ms),
+                                          C.byref(n)))
+        return ms.value, n.value
+
+    def close(self):
+        if self._h:
+            self._lib.ps_project_destroy(self._h)
+            self._h = L._VP()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def emergence_plan(emergence, ndays=None):
+    '''posterior_predictive's emergence= argument, dict(collection_day=C, obs_days=None), as (weights,
+    in_days, labels): the oviposition days [max(C - 25, 0), C), the labels in days post release (C + j, or the
+    observation days).  ValueError for a bad argument, or if the model's ndays days do not reach day C - 1.'''
+    if not isinstance(emergence, dict) or 'collection_day' not in emergence \
+            or set(emergence) - {'collection_day', 'obs_days'}:
+        raise ValueError('emergence must be dict(collection_day=C, obs_days=None), got %r' % (emergence,))
+    cday = int(emergence['collection_day'])
+    obs = emergence.get('obs_days')
+    in_days = list(range(max(cday - BF.max_incubation_time, 0), cday))
+    W = check_weights(emergence_weights(cday, in_days, obs), len(in_days), zero_rows=True)
+    if not np.any(W != 0):
+        raise ValueError('no listed emergence day carries weight')
+    if ndays is not None and cday > ndays:
+        raise ValueError('the model has %d days; emergence after a collection on day %d needs day %d'
+                         % (ndays, cday, cday - 1))
+    labels = [cday + j for j in range(W.shape[0])] if obs is None else [int(d) for d in obs]
+    return W, in_days, labels
+
+
+def exposure_plan(exposure, ndays=None):
+    '''posterior_predictive's exposure= argument, model days [D1, D2, ...] (strictly increasing, 0..31), as
+    (weights, in_days, labels) over the days 0 .. max D.  ValueError for a bad argument, or if the model's
+    ndays days do not reach the last one.'''
+    try:
+        upto = [int(d) for d in exposure]
+    except (TypeError, ValueError):
+        raise ValueError('exposure must be a list of model days, got %r' % (exposure,))
+    if not upto or upto[0] < 0 or any(b <= a for a, b in zip(upto, upto[1:])):
+        raise ValueError('exposure days must be model days >= 0, strictly increasing: %r' % (upto,))
+    in_days = check_in_days(range(upto[-1] + 1))
+    if ndays is not None and upto[-1] >= ndays:
+        raise ValueError('the model has %d days; exposure up to day %d needs it' % (ndays, upto[-1]))
+    return check_weights(exposure_weights(in_days, upto), len(in_days)), in_days, upto
+
+
+class ProjectedMaps():
+    '''The posterior of one projection, as posterior_predictive returns it: `weights` [nout, nin], `in_days`,
+    `labels` (one per output), `summary` (SpreadSummary.for_projection) and `histogram`
+    (SpreadHistogram.for_projection, None without quantile levels); both take the output index.'''
+
+    def __init__(self, weights, in_days, labels, summary, histogram=None):
+        self.weights = weights
+        self.in_days = in_days
+        self.labels = labels
+        self.summary = summary
+        self.histogram = histogram
+
+    def merge(self, other):
+        self.summary.merge(other.summary)
+        if self.histogram is not None:
+            self.histogram.merge(other.histogram)
+
+    def close(self):
+        self.summary.close()
+        if self.histogram is not None:
+            self.histogram.close()
+
+
 # ------------------------------------------------------------------ traces
 def model_names():
     return [m[0] for m in mcmc.MODEL_BLOCK]
@@ -650,11 +949,14 @@ class PredictiveResult():
     ([(chain, first_row, weight)] of every evaluated run), `observations` (observation_predictive
     or None) and `provenance`; with quantile levels `histogram` (a SpreadHistogram, None without a
     device) and `quantiles` (the levels), else both None; with arrival thresholds `arrival` (ArrivalMaps,
-    None without a device) and `arrival_levels`, else both None.'''
+    None without a device) and `arrival_levels`, else both None; `emergence` / `exposure`: ProjectedMaps of the
+    emergence and cumulative-exposure projections, None where not asked for.'''
 
     def __init__(self, summary, rows, evaluations, failed, seconds, runs, observations, provenance, days,
-                 histogram=None, quantiles=None, arrival=None, arrival_levels=None):
+                 histogram=None, quantiles=None, arrival=None, arrival_levels=None, emergence=None, exposure=None):
         self.summary = summary
+        self.emergence = emergence
+        self.exposure = exposure
         self.histogram = histogram
         self.quantiles = quantiles
         self.arrival = arrival
@@ -677,7 +979,11 @@ class PredictiveResult():
         (-1: not within the window; dense because the CSR writer drops day 0), `arrival{k}_cells` [members,
         days] and `arrival_weights`.  outfile.json: the params, the thresholds, the chain provenance, with a
         histogram the quantile levels and the edge definition, with arrival maps their thresholds, levels,
-        days, cell area and per threshold and day the reached area.  -> (npz path, json path)'''
+        days, cell area and per threshold and day the reached area.  The projections go into files of their own,
+        outfile_emergence.npz / outfile_exposure.npz in the same layout (`days` of the main file are model days):
+        per output `{label}_*` of the mean, `{label}_sd_*`, `{label}_pexc{k}_*`, `{label}_q{tag}_*`, the label
+        the emergence day in days post release, or the exposure's model day; their weights, input days and
+        labels under `predictive.emergence` / `predictive.exposure` of the json.  -> (npz path, json path)'''
         s = self.summary
         if s is None:
             raise ValueError('no spread summary to save (evaluate= runs without a device)')
@@ -717,15 +1023,30 @@ class PredictiveResult():
                                              'days': list(A.days), 'cell_area': A.cell_area,
                                              'reached_area': [A.reached_area(k, a_levels)
                                                               for k in range(len(A.thresholds))]}
+        for name, pr in (('emergence', self.emergence), ('exposure', self.exposure)):
+            if pr is None:
+                continue
+            ps, ph = pr.summary, pr.histogram
+            p_levels = list(self.quantiles or ()) if ph is not None else []
+            pmaps = []
+            for e, label in enumerate(pr.labels):
+                out_maps = [('', ps.mean(e)), ('_sd', ps.sd(e))]
+                out_maps += [('_pexc%d' % k, ps.exceedance(e, k)) for k in range(len(ps.thresholds))]
+                out_maps += [('_' + quantile_tag(p), ph.quantile(e, p)) for p in p_levels]
+                pmaps.append((label, out_maps))
+            save_maps('%s_%s' % (outfile, name), pmaps)
+            meta['predictive'][name] = {'weights': np.asarray(pr.weights).tolist(), 'in_days': list(pr.in_days),
+                                        'labels': list(pr.labels), 'thresholds': list(ps.thresholds),
+                                        'levels': p_levels}
         with open(str(outfile) + '.json', 'w') as fobj:
             json.dump(meta, fobj, default=str)
         return str(outfile) + '.npz', str(outfile) + '.json'
 
 
 def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, locinfo, histogram=None,
-                   arrival=None):
-    '''one chain: evaluate every run, add it to the summary (and the histogram, the arrival maps) ->
-    (expected per run or None, failed)'''
+                   arrival=None, projected=()):
+    '''one chain: evaluate every run, add it to the summary (and the histogram, the arrival maps; projected:
+    (Projection, ProjectedMaps) pairs, applied and then added) -> (expected per run or None, failed)'''
     expected = []
     failed = 0
     for first, length in run_list:
@@ -753,13 +1074,18 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
             histogram.add(length)
         if arrival is not None:
             arrival.add(length)
+        for proj, maps in projected:
+            proj.apply()
+            maps.summary.add(length)
+            if maps.histogram is not None:
+                maps.histogram.add(length)
         expected.append(mcmc.expected_observations(pm, locinfo) if want_obs else True)
     return expected, failed
 
 
 def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, thresholds=(), locinfo=None,
                          cell_area=None, seed=0, evaluate=None, quantiles=None, bins=DEFAULT_BINS, edges=None,
-                         arrival=None, arrival_levels=(0.05, 0.5, 0.95)):
+                         arrival=None, arrival_levels=(0.05, 0.5, 0.95), emergence=None, exposure=None):
     '''Posterior predictive spread of one or more chains (`Sampler.save` files or (trace, names)
     pairs).  Burn and thin apply per chain; consecutive rows with identical model parameters are one
     evaluation weighted by the run's length.  pop_model: one PopModel or a list -- with several, one
@@ -771,7 +1097,11 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     bin_edges) with the same weights, merged in chain order into `histogram`.  arrival: thresholds (1..4,
     finite, > 0, strictly increasing); each chain then also fills ArrivalMaps over the summary's days
     (strictly increasing, at most 32) with the same weights, merged in chain order into `arrival`;
-    arrival_levels: the levels of its saved arrival-day quantile maps.'''
+    arrival_levels: the levels of its saved arrival-day quantile maps.  emergence: dict(collection_day=C,
+    obs_days=None) (emergence_plan); exposure: model days [D1, D2, ...] (exposure_plan); each chain then also
+    applies that Projection after every evaluation and adds its outputs, with the same weights, to a
+    SpreadSummary.for_projection (same thresholds) and, with quantiles, a SpreadHistogram.for_projection
+    (same edges), merged in chain order into `emergence` / `exposure` (ProjectedMaps).'''
     t0 = time.perf_counter()
     levels = (check_levels(quantiles) if quantiles is not None else []) or None
     if levels:
@@ -782,6 +1112,9 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         a_levels = check_levels(arrival_levels)
         if days is not None:
             check_arrival_days(days)
+    wanted = [(name, arg, plan) for name, arg, plan in (('emergence', emergence, emergence_plan),
+                                                        ('exposure', exposure, exposure_plan)) if arg is not None]
+    plans = [(name,) + plan(arg) for name, arg, plan in wanted]      # and bad projection arguments
     if isinstance(chains, (str, os.PathLike)) or (isinstance(chains, tuple) and len(chains) == 2
                                                    and not isinstance(chains[0], (str, os.PathLike, tuple))):
         chains = [chains]
@@ -802,10 +1135,13 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         raise ValueError('a PopModel is needed without evaluate=')
     if a_thr and evaluate is None and days is None:
         check_arrival_days(range(len(pms[0].days)))
+    if evaluate is None:              # as do projections past the model's days
+        plans = [(name,) + plan(arg, len(pms[0].days)) for name, arg, plan in wanted]
     nch = len(prepared)
     summaries = [None] * nch
     histograms = [None] * nch
     arrivals = [None] * nch
+    projected = [[] for _ in range(nch)]       # per chain (Projection, ProjectedMaps) of every plan
     results = [None] * nch
     errs = []
 
@@ -820,7 +1156,16 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                 histograms[ci] = hist
                 arr = ArrivalMaps(pm, a_thr, summ.days) if evaluate is None and a_thr else None
                 arrivals[ci] = arr
-                results[ci] = _evaluate_runs(pm, summ, rows, rl, mcols, evaluate, want_obs, locinfo, hist, arr)
+                if evaluate is None:
+                    for _name, W, in_days, labels in plans:
+                        proj = Projection(pm, W, in_days)
+                        projected[ci].append((proj, None))
+                        maps = ProjectedMaps(W, in_days, labels, SpreadSummary.for_projection(proj, thresholds))
+                        projected[ci][-1] = (proj, maps)
+                        if levels:
+                            maps.histogram = SpreadHistogram.for_projection(proj, bins, edges)
+                results[ci] = _evaluate_runs(pm, summ, rows, rl, mcols, evaluate, want_obs, locinfo, hist, arr,
+                                             projected[ci])
         except BaseException as e:       # re-raised in the caller's thread
             errs.append((p, e))
 
@@ -835,7 +1180,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         pms = pms[:1]
         work(0)
     if errs:
-        for s in summaries + histograms + arrivals:
+        for s in summaries + histograms + arrivals + [x for pl in projected for pair in pl for x in pair]:
             if s is not None:
                 s.close()
         raise errs[0][1]
@@ -857,6 +1202,15 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
             for a in arrivals[1:]:
                 arrival_maps.merge(a)
                 a.close()
+    merged = {}
+    for k, plan in enumerate(plans if evaluate is None else []):
+        merged[plan[0]] = projected[0][k][1]
+        for pl in projected[1:]:
+            merged[plan[0]].merge(pl[k][1])
+            pl[k][1].close()
+    for pl in projected:                 # the accumulators hold what they need: the output fields go
+        for proj, _maps in pl:
+            proj.close()
     evaluations = sum(len(p[1]) for p in prepared)
     failed = sum(r[1] for r in results)
     run_rec = [(ci, first, length) for ci, p in enumerate(prepared)
@@ -877,7 +1231,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     res = PredictiveResult(summary, int(sum(len(p[0]) for p in prepared)), evaluations, failed,
                            time.perf_counter() - t0, run_rec, observations, prov,
                            None if summary is None else summary.days, histogram, levels, arrival_maps,
-                           a_levels if a_thr else None)
+                           a_levels if a_thr else None, merged.get('emergence'), merged.get('exposure'))
     if cell_area is not None:
         res.cell_area = float(cell_area)
     return res

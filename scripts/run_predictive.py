@@ -3,13 +3,17 @@
 cell the posterior mean population, its spread and exceedance probabilities, accumulated on the
 GPU, plus the observation-level predictive of the reference's Poisson model; with --quantiles also
 per-cell quantile maps from device histograms on fixed bin edges (--bins); with --arrival also arrival
-probability and arrival-day quantile maps and the reached area per day (--arrival-levels).  Kalbar wind and
+probability and arrival-day quantile maps and the reached area per day (--arrival-levels); with --emergence /
+--exposure also the posterior maps of the projected emergence after a collection on day C (daily, or binned
+into the observation days d1,d2,...) and of the cumulative exposure up to the listed model days, saved as
+PREFIX_emergence.npz / PREFIX_exposure.npz.  Kalbar wind and
 LocInfo as scripts/run_mcmc.py loads them; --synthetic uses the synthetic Kalbar-like observations.
 Without --chain a short chain is sampled first (--samples) and saved next to --out.
 
     python scripts/run_predictive.py --chain c.npz [...] [--burn 0] [--thin 1] [--rad-res 400]
         [--mode auto] [--thresholds 1,10] [--out PREFIX] [--synthetic] [--chains-parallel]
         [--quantiles 0.05,0.5,0.95] [--bins 1e-8,1e6,16] [--arrival 1,10] [--arrival-levels 0.05,0.5,0.95]
+        [--emergence C[:d1,d2,...]] [--exposure d1,d2,...]
 """
 import argparse
 import json
@@ -41,12 +45,16 @@ def main():
     ap.add_argument('--arrival', default='', help='arrival thresholds, e.g. 1,10 (default: off)')
     ap.add_argument('--arrival-levels', default='0.05,0.5,0.95',
                     help='arrival-day quantile levels in (0, 1] (with --arrival)')
+    ap.add_argument('--emergence', default='', help='collection day C, or C:d1,d2,... with the observation days '
+                                                    '(days post release; default: off)')
+    ap.add_argument('--exposure', default='', help='model days d1,d2,... of the cumulative exposure (default: off)')
     args = ap.parse_args()
     warnings.simplefilter('ignore', RuntimeWarning)
     from parasitoids_amd import ParasitoidModel as PM
     from parasitoids_amd import mcmc
     from parasitoids_amd.pop_model import PopModel
-    from parasitoids_amd.predictive import bin_edges, check_arrival_thresholds, check_levels, posterior_predictive
+    from parasitoids_amd.predictive import (bin_edges, check_arrival_thresholds, check_levels, emergence_plan,
+                                            exposure_plan, posterior_predictive)
     levels = check_levels([float(q) for q in args.quantiles.split(',') if q.strip()])
     bins = tuple(float(b) for b in args.bins.split(','))
     bin_edges(bins)                      # a bad --bins fails before any work
@@ -54,10 +62,18 @@ def main():
     a_levels = check_levels([float(q) for q in args.arrival_levels.split(',') if q.strip()])
     if arrival:
         check_arrival_thresholds(arrival)   # as do bad --arrival thresholds
+    emergence = exposure = None
+    if args.emergence:
+        cday, _, obs = args.emergence.partition(':')
+        emergence = dict(collection_day=int(cday), obs_days=[int(d) for d in obs.split(',') if d.strip()] or None)
+    if args.exposure:
+        exposure = [int(d) for d in args.exposure.split(',') if d.strip()]
     wd, days = PM.get_wind_data(os.path.join(ROOT, 'parasitoids_amd', 'data', 'kalbar'), 30, '00:00')
 
     def make_pm():
         return PopModel(wd, days, domain_info=(10000.0, args.rad_res), r_number=130000, mode=args.mode)
+    plans = ([emergence_plan(emergence, len(days))] if emergence else []) \
+        + ([exposure_plan(exposure, len(days))] if exposure else [])     # bad projections fail before any work too
     pm = make_pm()
     if args.synthetic:
         li = mcmc.synthetic_locinfo(pm, args.rad_res, seed=9)
@@ -81,10 +97,12 @@ def main():
     t0 = time.perf_counter()
     res = posterior_predictive(pms if len(pms) > 1 else pm, chains, burn=args.burn, thin=args.thin,
                                thresholds=thr, locinfo=li, cell_area=cell_area, seed=args.seed,
-                               quantiles=levels or None, bins=bins, arrival=arrival or None, arrival_levels=a_levels)
+                               quantiles=levels or None, bins=bins, arrival=arrival or None, arrival_levels=a_levels,
+                               emergence=emergence, exposure=exposure)
     dt = time.perf_counter() - t0
     # accumulate-kernel time: the same members once more with HIP events around every add
-    from parasitoids_amd.predictive import ArrivalMaps, SpreadHistogram, SpreadSummary, load_chain, runs
+    from parasitoids_amd.predictive import ArrivalMaps, Projection, SpreadHistogram, SpreadSummary, load_chain, runs
+    projections = [Projection(pm, W, in_days) for W, in_days, _labels in plans]
     H = SpreadHistogram(pm, None, bins) if levels else None
     A = ArrivalMaps(pm, arrival) if arrival else None
     with SpreadSummary(pm, None, thr) as S:
@@ -93,6 +111,8 @@ def main():
             H.profile(True)
         if A is not None:
             A.profile(True)
+        for P in projections:
+            P.profile(True)
         n = 0
         for c in chains[:1]:
             trace, names, _ = load_chain(c)
@@ -108,6 +128,8 @@ def main():
                     H.add(length)
                 if A is not None:
                     A.add(length)
+                for P in projections:
+                    P.apply()
                 n += 1
         ms, launches = S.profile()
     if H is not None:
@@ -118,6 +140,11 @@ def main():
         a_ms, a_launches = A.profile()[:2]
         A.close()
         res.arrival.profile(True)       # every map launch of the save
+    p_ms = sum(P.profile()[0] for P in projections)
+    p_launches = sum(P.profile()[1] for P in projections)
+    p_bytes = sum(P.nbytes for P in projections)
+    for P in projections:
+        P.close()
     npz, js = res.save(args.out, {'chains': chains, 'burn': args.burn, 'thin': args.thin, 'rad_res': args.rad_res,
                                   'mode': args.mode, 'synthetic': bool(args.synthetic)})
     ncell = (2 * args.rad_res + 1) ** 2
@@ -140,12 +167,21 @@ def main():
         out['arrival_add_ms_per_member'] = round(a_ms / max(a_launches, 1), 4)
         out['arrival_maps_ms_total'] = round(res.arrival.profile()[2], 3)
         out['arrival_bytes'] = res.arrival.nbytes
+    if projections:
+        out['project_ms_per_member'] = round(p_ms / max(n, 1), 4)       # every projection's apply of one member
+        out['project_launches_timed'] = p_launches
+        out['project_bytes'] = p_bytes                                   # the output fields
+        out['outputs'] += ['%s_%s.npz' % (args.out, name) for name, on in (('emergence', emergence),
+                                                                             ('exposure', exposure)) if on]
     print(json.dumps(out))
     res.summary.close()
     if res.histogram is not None:
         res.histogram.close()
     if res.arrival is not None:
         res.arrival.close()
+    for pr in (res.emergence, res.exposure):
+        if pr is not None:
+            pr.close()
     for p in pms:
         p.close()
 
