@@ -536,6 +536,64 @@ void ps_project_destroy(ps_project* p);
  * nothing enqueued); PS_ERR_STATE before the projection's first apply.  Weight and members advance as in add. */
 int ps_summary_add_project(ps_summary* a, ps_project* p, uint32_t weight);
 int ps_hist_add_project(ps_hist* h, ps_project* p, uint32_t weight);
+/* The same for arrival maps: slot e of the handle takes Y_e, so the slots are the projection's outputs in
+ * ascending order (nslot must equal nout) and a member's arrival slot is the first output that reaches the
+ * threshold.  Both kernels of an arrival add run on the handle's stream. */
+int ps_arrival_add_project(ps_arrival* a, ps_project* p, uint32_t weight);
+
+/* ---- release plans: several release sites and staggered release days of one member, as maps ----
+ * (no reference counterpart: the reference releases once, at the domain centre).  One wind station and a
+ * homogeneous landscape make the field of a release at another cell the centre release translated, and the
+ * population chain is linear in the released number.  A release `lag` days later is not a time shift (every
+ * day has its own kernel): it is the run of a solver of its own over the later days.  A handle lives on one
+ * device and holds the sites group by group -- a group is the set of sites that share one release day, so
+ * one solver -- and nout fp64 output fields Y[e][pitch] (pitch as ps_summary):
+ *   Y_e(r, c) = sum over the groups g and the sites k of g of amount_k * v_{g,e}(r - drow_k, c - dcol_k)
+ * v_{g,e} the value ps_summary_add adds for the record that group g's apply names for output e (same
+ * arguments, same value bit for bit), 0 where the source row or the source column lies outside [0, N): mass
+ * that leaves the east edge does not come back at the west edge of the next row.  Limits: 1 <= nout <= 32,
+ * 1 <= ngroup <= 8, every group_nsite >= 1, at most 32 sites in all, |drow|, |dcol| <= N - 1, every amount
+ * finite and > 0; anything else is PS_ERR_BAD_ARG with the offender named.  drow, dcol and amount list the
+ * sites of group 0, then those of group 1, and so on.  Arithmetic: per cell and output, acc starts from +0.0
+ * in group 0 and from the stored Y in later groups, and takes the group's sites in the order given as
+ * acc = acc + amount * v in IEEE double, product and sum rounded separately, never fused; a term from outside
+ * the domain adds +0.0 to acc >= +0.0 and changes no bit.  Every cell has one writer, no atomics: the same
+ * calls give the same bits.  nout * pitch * 8 B is checked against the free device memory first: PS_ERR_OOM
+ * before anything is allocated.  Every operation records an event the next one waits on, whichever stream
+ * it runs on (the group's solver's for apply, the handle's own for fetch and gather, the accumulator's for
+ * the add entry points below), so the solvers of different groups may run on different streams. */
+#define PS_REC_NONE (-1)   /* ps_sites_apply only: the group is not released yet on that output day */
+typedef struct ps_sites ps_sites;
+int ps_sites_create(int device, int N, int nout, int ngroup, const int32_t* group_nsite, const int32_t* drow,
+                    const int32_t* dcol, const double* amount, ps_sites** out);
+/* Apply group `group` from the records of solver s (same device, same N; nout must equal the handle's): slot e
+ * names the record of model day D_e - lag_group of that solver (arguments as ps_summary_add), or has kind
+ * PS_REC_NONE and contributes nothing; at least one slot must name a record.  One launch on the solver's
+ * stream, no host synchronisation, nothing copied or allocated; every descriptor is resolved before anything
+ * is enqueued.  The groups of a pass go in the order 0, 1, ..., ngroup - 1: group 0 overwrites Y, zeros
+ * included, later groups accumulate; any other group is PS_ERR_STATE (group 0 alone may come early: it
+ * abandons the pass under way and opens a new one).  A pass is complete once its last group is applied; fetch, gather and the add entry points are PS_ERR_STATE before the first complete pass
+ * and while a pass is under way. */
+int ps_sites_apply(ps_sites* p, ps_solver* s, int group, int nout, const int32_t* kind, const int32_t* idx,
+                   const double* stat_scale, const double* post_scale, const int32_t* use_delta, double negval);
+/* one output field to the host (synchronises) */
+int ps_sites_fetch(ps_sites* p, int e, double* out /* N*N */);
+/* the outputs at n listed cells: out[e * n + k] = Y_e(rows[k], cols[k]) (synchronises).  PS_ERR_BAD_ARG for a
+ * cell outside the domain. */
+int ps_sites_gather(ps_sites* p, int64_t n, const int32_t* rows, const int32_t* cols, double* out /* nout x n */);
+/* any pointer may be NULL; passes: the complete passes so far */
+int ps_sites_info(ps_sites* p, int* N, int* nout, int* ngroup, int* nsite, int64_t* passes);
+/* measurement: HIP-event timing of the apply launches (one per group and pass).  enable 1 on, 0 off, < 0
+ * unchanged; total_ms / launches (either may be NULL) receive the timed launches so far (synchronises). */
+int ps_sites_prof(ps_sites* p, int enable, double* total_ms, int64_t* launches);
+void ps_sites_destroy(ps_sites* p);
+/* One member with weight >= 1 whose values are the plan's current outputs, as the add_project entry points
+ * take a projection's: slot e of the accumulator takes Y_e, on the accumulator's stream behind the plan's
+ * last apply; the plan's next apply waits for it.  Slot count, device and N must agree (PS_ERR_BAD_ARG,
+ * nothing enqueued). */
+int ps_summary_add_sites(ps_summary* a, ps_sites* p, uint32_t weight);
+int ps_hist_add_sites(ps_hist* h, ps_sites* p, uint32_t weight);
+int ps_arrival_add_sites(ps_arrival* a, ps_sites* p, uint32_t weight);
 
 #ifdef __cplusplus
 }

@@ -31,6 +31,7 @@ MODE_FOLD = 2
 MODE_AUTO = 3
 
 REC_CHAIN, REC_BACK, REC_STATE, REC_WSUM = 0, 1, 2, 3
+REC_NONE = -1       # ps_sites_apply only: the group is not released yet on that output day
 
 
 class DayStats(C.Structure):
@@ -168,6 +169,17 @@ SIGNATURES = {
     'ps_project_destroy': (None, [_VP]),
     'ps_summary_add_project': (C.c_int, [_VP, _VP, C.c_uint32]),
     'ps_hist_add_project': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_arrival_add_project': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_sites_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _I32P, _I32P, _I32P, _F64P, C.POINTER(_VP)]),
+    'ps_sites_apply': (C.c_int, [_VP, _VP, C.c_int, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P, C.c_double]),
+    'ps_sites_fetch': (C.c_int, [_VP, C.c_int, _F64P]),
+    'ps_sites_gather': (C.c_int, [_VP, C.c_int64, _I32P, _I32P, _F64P]),
+    'ps_sites_info': (C.c_int, [_VP, _I32P, _I32P, _I32P, _I32P, _I64P]),
+    'ps_sites_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P]),
+    'ps_sites_destroy': (None, [_VP]),
+    'ps_summary_add_sites': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_hist_add_sites': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_arrival_add_sites': (C.c_int, [_VP, _VP, C.c_uint32]),
 }
 
 _lib = None

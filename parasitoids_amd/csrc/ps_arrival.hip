@@ -327,6 +327,29 @@ extern "C" int ps_arrival_create(int device, int N, int nslot, int nthr, const d
   return PS_OK;
 }
 
+// one member from the slot descriptors (one per slot of the handle, the rest null), enqueued on `stream`
+static int arr_launch(ps_arrival* a, const ArrSlots& desc, hipStream_t stream, double negval, uint32_t weight) {
+  ArrThr thr;
+  for (int k = 0; k < PS_ARR_MAX_THR; ++k) thr.t[k] = k < a->nthr ? a->thr[(size_t)k] : 0.0;
+  PS_TRY(arr_reserve_rows(a, a->members + 1));
+  PS_TRY(arr_after_last(a, stream));
+  hipEvent_t e1 = nullptr;
+  PS_TRY(arr_prof_begin(a, a->prof_add, stream, &e1));
+  hipLaunchKernelGGL(k_arrival_add, dim3(a->nblk), dim3(PS_ARR_THREADS), 0, stream, desc, thr, a->nslot, a->nthr,
+                     a->cnt, a->part, a->ncell, a->pitch, negval, weight);
+  PS_HIP(hipGetLastError());
+  const int nks = (int)arr_row_len(a);
+  hipLaunchKernelGGL(k_arrival_rows, dim3(nks), dim3(PS_ARR_THREADS), 0, stream, a->part, a->nblk,
+                     a->rows + a->members * nks);
+  PS_HIP(hipGetLastError());
+  if (e1) PS_HIP(hipEventRecord(e1, stream));
+  PS_TRY(arr_mark_last(a, stream));
+  a->W += weight;
+  a->members += 1;
+  a->weights.push_back(weight);
+  return PS_OK;
+}
+
 extern "C" int ps_arrival_add(ps_arrival* a, ps_solver* s, int nslot, const int32_t* kind, const int32_t* idx,
                               const double* stat_scale, const double* post_scale, const int32_t* use_delta,
                               double negval, uint32_t weight) {
@@ -352,25 +375,40 @@ extern "C" int ps_arrival_add(ps_arrival* a, ps_solver* s, int nslot, const int3
     stream = v.stream;
   }
   for (int i = nslot; i < PS_ARR_MAX_SLOT; ++i) desc.s[i] = ArrSlot{nullptr, nullptr, 0.0, 0.0};
-  ArrThr thr;
-  for (int k = 0; k < PS_ARR_MAX_THR; ++k) thr.t[k] = k < a->nthr ? a->thr[(size_t)k] : 0.0;
-  PS_TRY(arr_reserve_rows(a, a->members + 1));
-  PS_TRY(arr_after_last(a, stream));
-  hipEvent_t e1 = nullptr;
-  PS_TRY(arr_prof_begin(a, a->prof_add, stream, &e1));
-  hipLaunchKernelGGL(k_arrival_add, dim3(a->nblk), dim3(PS_ARR_THREADS), 0, stream, desc, thr, a->nslot, a->nthr,
-                     a->cnt, a->part, a->ncell, a->pitch, negval, weight);
-  PS_HIP(hipGetLastError());
-  const int nks = (int)arr_row_len(a);
-  hipLaunchKernelGGL(k_arrival_rows, dim3(nks), dim3(PS_ARR_THREADS), 0, stream, a->part, a->nblk,
-                     a->rows + a->members * nks);
-  PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, stream));
-  PS_TRY(arr_mark_last(a, stream));
-  a->W += weight;
-  a->members += 1;
-  a->weights.push_back(weight);
-  return PS_OK;
+  return arr_launch(a, desc, stream, negval, weight);
+}
+
+// one member whose slots are the current fields of a projection or a release plan, in ascending output order
+// (who: the entry point)
+static int arr_add_fields(ps_arrival* a, void* h, const PsFieldsOps& src, const char* who, uint32_t weight) {
+  if (!a || !h) return ps_fail(PS_ERR_BAD_ARG, "%s: bad arguments", who);
+  if (weight < 1) return ps_fail(PS_ERR_BAD_ARG, "%s: weight must be >= 1", who);
+  if (a->W + weight > 0xffffffffull)
+    return ps_fail(PS_ERR_BAD_ARG, "%s: total weight %llu would overflow the uint32 counts", who,
+                   (unsigned long long)(a->W + weight));
+  PsProjectView v;
+  PS_TRY(src.view(h, &v));
+  if (v.nout != a->nslot)
+    return ps_fail(PS_ERR_BAD_ARG, "%s: the %s has %d outputs, the handle %d slots", who, src.what, v.nout, a->nslot);
+  if (v.device != a->device)
+    return ps_fail(PS_ERR_BAD_ARG, "%s: %s on device %d, handle on device %d", who, src.what, v.device, a->device);
+  if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "%s: %s domain %d, handle domain %d", who, src.what, v.N, a->N);
+  PS_HIP(hipSetDevice(a->device));
+  // slot e takes Y_e: no statistics, both scales 1 and negval 0, so the value rule returns Y itself
+  ArrSlots desc;
+  for (int e = 0; e < PS_ARR_MAX_SLOT; ++e)
+    desc.s[e] = e < a->nslot ? ArrSlot{v.Y + (int64_t)e * v.pitch, nullptr, 1.0, 1.0} : ArrSlot{nullptr, nullptr, 0.0, 0.0};
+  PS_TRY(src.wait(h, a->stream));
+  PS_TRY(arr_launch(a, desc, a->stream, 0.0, weight));
+  return src.mark(h, a->stream);   // the next apply overwrites Y only after this read
+}
+
+extern "C" int ps_arrival_add_project(ps_arrival* a, ps_project* p, uint32_t weight) {
+  return arr_add_fields(a, p, ps_project_fields(), "arrival_add_project", weight);
+}
+
+extern "C" int ps_arrival_add_sites(ps_arrival* a, ps_sites* p, uint32_t weight) {
+  return arr_add_fields(a, p, ps_sites_fields(), "arrival_add_sites", weight);
 }
 
 extern "C" int ps_arrival_merge(ps_arrival* dst, ps_arrival* src) {

@@ -132,9 +132,17 @@ struct PsProjectView {
   int64_t pitch;
   int N, nout, device;
 };
-int ps_project_view_internal(ps_project* p, PsProjectView* out);
-int ps_project_wait_internal(ps_project* p, hipStream_t stream);
-int ps_project_mark_internal(ps_project* p, hipStream_t stream);
+// The same triple for every handle that owns such fields, so that an accumulator has one code path for all
+// of them: the projections (ps_project.hip) and the release plans (ps_sites.hip, PS_ERR_STATE also while a
+// pass over the plan's groups is under way).  what: the handle's name in the accumulators' messages.
+struct PsFieldsOps {
+  const char* what;
+  int (*view)(void* handle, PsProjectView* out);
+  int (*wait)(void* handle, hipStream_t stream);
+  int (*mark)(void* handle, hipStream_t stream);
+};
+PsFieldsOps ps_project_fields();
+PsFieldsOps ps_sites_fields();
 
 // the value one solver record holds at a cell, as ps_record_fetch_* returns it (k_compact_rows,
 // chain_kernels.h), 0 where it returns no entry; shared by ps_summary.hip and ps_linspread.hip

@@ -341,29 +341,35 @@ extern "C" int ps_hist_add(ps_hist* a, ps_solver* s, int nslot, const int32_t* k
   return hist_launch(a, d, stream, negval, weight);
 }
 
-extern "C" int ps_hist_add_project(ps_hist* a, ps_project* p, uint32_t weight) {
-  if (!a || !p) return ps_fail(PS_ERR_BAD_ARG, "hist_add_project: bad arguments");
-  if (weight < 1) return ps_fail(PS_ERR_BAD_ARG, "hist_add_project: weight must be >= 1");
+// one member whose values are the current fields of a projection or a release plan (who: the entry point)
+static int hist_add_fields(ps_hist* a, void* h, const PsFieldsOps& src, const char* who, uint32_t weight) {
+  if (!a || !h) return ps_fail(PS_ERR_BAD_ARG, "%s: bad arguments", who);
+  if (weight < 1) return ps_fail(PS_ERR_BAD_ARG, "%s: weight must be >= 1", who);
   if (a->W + weight > 0xffffffffull)
-    return ps_fail(PS_ERR_BAD_ARG, "hist_add_project: total weight %llu would overflow the uint32 counts",
+    return ps_fail(PS_ERR_BAD_ARG, "%s: total weight %llu would overflow the uint32 counts", who,
                    (unsigned long long)(a->W + weight));
   PsProjectView v;
-  PS_TRY(ps_project_view_internal(p, &v));
+  PS_TRY(src.view(h, &v));
   if (v.nout != a->nslot)
-    return ps_fail(PS_ERR_BAD_ARG, "hist_add_project: the projection has %d outputs, the histogram %d slots", v.nout,
-                   a->nslot);
+    return ps_fail(PS_ERR_BAD_ARG, "%s: the %s has %d outputs, the histogram %d slots", who, src.what, v.nout, a->nslot);
   if (v.device != a->device)
-    return ps_fail(PS_ERR_BAD_ARG, "hist_add_project: projection on device %d, histogram on device %d", v.device,
-                   a->device);
-  if (v.N != a->N)
-    return ps_fail(PS_ERR_BAD_ARG, "hist_add_project: projection domain %d, histogram domain %d", v.N, a->N);
+    return ps_fail(PS_ERR_BAD_ARG, "%s: %s on device %d, histogram on device %d", who, src.what, v.device, a->device);
+  if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "%s: %s domain %d, histogram domain %d", who, src.what, v.N, a->N);
   PS_HIP(hipSetDevice(a->device));
   // slot e takes Y_e: no statistics, both scales 1 and negval 0, so the value rule returns Y itself
   std::vector<HistSlot> d((size_t)a->nslot);
   for (int e = 0; e < a->nslot; ++e) d[(size_t)e] = HistSlot{v.Y + (int64_t)e * v.pitch, nullptr, 1.0, 1.0, e};
-  PS_TRY(ps_project_wait_internal(p, a->stream));
+  PS_TRY(src.wait(h, a->stream));
   PS_TRY(hist_launch(a, d, a->stream, 0.0, weight));
-  return ps_project_mark_internal(p, a->stream);   // the next apply overwrites Y only after this read
+  return src.mark(h, a->stream);   // the next apply overwrites Y only after this read
+}
+
+extern "C" int ps_hist_add_project(ps_hist* a, ps_project* p, uint32_t weight) {
+  return hist_add_fields(a, p, ps_project_fields(), "hist_add_project", weight);
+}
+
+extern "C" int ps_hist_add_sites(ps_hist* a, ps_sites* p, uint32_t weight) {
+  return hist_add_fields(a, p, ps_sites_fields(), "hist_add_sites", weight);
 }
 
 extern "C" int ps_hist_merge(ps_hist* dst, ps_hist* src) {

@@ -341,7 +341,8 @@ extern "C" int ps_project_prof(ps_project* p, int enable, double* total_ms, int6
   return PS_OK;
 }
 
-int ps_project_view_internal(ps_project* p, PsProjectView* out) {
+static int proj_view(void* h, PsProjectView* out) {
+  ps_project* p = static_cast<ps_project*>(h);
   if (!p || !out) return ps_fail(PS_ERR_BAD_ARG, "project view: null handle");
   if (p->applies == 0) return ps_fail(PS_ERR_STATE, "nothing projected yet: apply the projection first");
   out->Y = p->Y;
@@ -351,5 +352,6 @@ int ps_project_view_internal(ps_project* p, PsProjectView* out) {
   out->device = p->device;
   return PS_OK;
 }
-int ps_project_wait_internal(ps_project* p, hipStream_t stream) { return proj_after_last(p, stream); }
-int ps_project_mark_internal(ps_project* p, hipStream_t stream) { return proj_mark_last(p, stream); }
+static int proj_wait(void* h, hipStream_t stream) { return proj_after_last(static_cast<ps_project*>(h), stream); }
+static int proj_mark(void* h, hipStream_t stream) { return proj_mark_last(static_cast<ps_project*>(h), stream); }
+PsFieldsOps ps_project_fields() { return PsFieldsOps{"projection", proj_view, proj_wait, proj_mark}; }

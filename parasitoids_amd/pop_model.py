@@ -22,6 +22,7 @@ class PopModel():
         from . import hip_lib
         self._hip = hip_lib
         self.model = PM.WindModel(wind_data, device=device)
+        self.wind_data = wind_data      # kept for models of a later release day (predictive.lagged_models)
         self.days = list(self.model.days if days is None else days)
         self.rad_dist, self.rad_res = float(domain_info[0]), int(domain_info[1])
         # prob_model: the probability chain of get_solutions (renormalised pmf per day,

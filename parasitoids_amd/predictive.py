@@ -17,7 +17,10 @@ weight matrix along the time axis of one member's daily fields (ps_project_*, cs
 emergence the field data measure (`emergence_weights`, the matrix of Bayes_funcs.popdensity_to_emergence) and
 the cumulative exposure (`exposure_weights`) as maps, which `SpreadSummary.for_projection` and
 `SpreadHistogram.for_projection` accumulate per member -- the spread of a sum over days cannot be rebuilt
-from the per-day moments.
+from the per-day moments.  `ReleaseSites` superposes, on the device, the translated fields of several release
+sites and of releases on later days (ps_sites_*, csrc/ps_sites.hip) into the field of a whole release plan,
+which the same accumulators and `ArrivalMaps.for_projection` take per member -- neither can the spread, the
+quantiles, the arrival day or the reached area of a sum over sites be rebuilt from the per-site maps.
 """
 import ctypes as C
 import json
@@ -38,6 +41,9 @@ MAX_ARRIVAL_SLOTS = 32     # ps_arrival: the day slots of one launch's descripto
 MAX_ARRIVAL_THRESHOLDS = 4
 MAX_PROJECT_IN = 32        # ps_project: the input records of one launch's descriptors
 MAX_PROJECT_OUT = 32
+MAX_SITES = 32             # ps_sites: the sites of one plan, its release days (groups) and its outputs
+MAX_SITE_GROUPS = 8
+MAX_SITE_OUT = 32
 
 
 def _day_slots(days):
@@ -74,7 +80,7 @@ class SpreadSummary():
 
     @classmethod
     def for_projection(cls, projection, thresholds=()):
-        '''A summary of `projection`'s outputs, one slot per output: `add(weight)` accumulates the outputs of
+        '''A summary of the outputs of `projection` (a Projection or a ReleaseSites), one slot per output: `add(weight)` accumulates the outputs of
         the projection's last `apply()`, and the accessors take the output index where the day-based summary
         takes a day.'''
         self = cls.__new__(cls)
@@ -107,7 +113,7 @@ class SpreadSummary():
         if self._proj is not None:
             if w < 1:
                 raise ValueError('weight must be a positive integer')
-            L.check(self._lib.ps_summary_add_project(self._h, self._proj._h, w))
+            L.check(getattr(self._lib, 'ps_summary_add_' + self._proj.fields_kind)(self._h, self._proj._h, w))
             return
         pm = self.pm
         _check_evaluated(pm, self.days, 'summary')
@@ -251,7 +257,7 @@ class SpreadHistogram():
 
     @classmethod
     def for_projection(cls, projection, bins=DEFAULT_BINS, edges=None):
-        '''Histograms of `projection`'s outputs, one slot per output: `add(weight)` accumulates the outputs
+        '''Histograms of the outputs of `projection` (a Projection or a ReleaseSites), one slot per output: `add(weight)` accumulates the outputs
         of the projection's last `apply()`, and the accessors take the output index where the day-based
         histogram takes a day.'''
         self = cls.__new__(cls)
@@ -289,7 +295,7 @@ class SpreadHistogram():
         if self._proj is not None:       # the projection's last apply, on the histogram's stream
             if w < 1:
                 raise ValueError('weight must be a positive integer')
-            L.check(self._lib.ps_hist_add_project(self._h, self._proj._h, w))
+            L.check(getattr(self._lib, 'ps_hist_add_' + self._proj.fields_kind)(self._h, self._proj._h, w))
             return
         pm = self.pm
         _check_evaluated(pm, self.days, 'histogram')
@@ -453,6 +459,24 @@ class ArrivalMaps():
         self._h = L._VP()
         self.thresholds = check_arrival_thresholds(thresholds)
         self.days = check_arrival_days(range(len(pop_model.days)) if days is None else days)
+        self._setup(pop_model, None)
+
+    @classmethod
+    def for_projection(cls, projection, thresholds):
+        '''Arrival maps of the outputs of `projection` (a ReleaseSites or a Projection), the slots its outputs
+        that carry weight in ascending order: `add(weight)` accumulates the outputs of its last `apply()`.
+        `days` holds the output labels -- the plan's output days, or the projection's output indices -- and
+        `reached_area` is the coverage curve of the plan.'''
+        self = cls.__new__(cls)
+        self._h = L._VP()
+        self.thresholds = check_arrival_thresholds(thresholds)
+        labels = list(getattr(projection, 'days', range(projection.nout)))
+        self.days = check_arrival_days([labels[e] for e in projection.live])
+        self._setup(projection.pm, projection)
+        return self
+
+    def _setup(self, pop_model, projection):
+        self._proj = projection
         self._lib = L.load()
         self.pm = pop_model
         self.N = 2 * int(pop_model.rad_res) + 1
@@ -463,12 +487,20 @@ class ArrivalMaps():
         thr = L.f64(self.thresholds)
         L.check(self._lib.ps_arrival_create(self.device, self.N, len(self.days), len(self.thresholds), L.p_f64(thr),
                                             C.byref(self._h)))
-        self._kind, self._idx, self._delta = _day_slots(self.days)
+        if projection is None:
+            self._kind, self._idx, self._delta = _day_slots(self.days)
         self._slot = {d: i for i, d in enumerate(self.days)}
 
     def add(self, weight=1):
         '''Accumulate the last evaluation of the model with integer weight >= 1 (enqueued on the
-        solver's stream; no host synchronisation).'''
+        solver's stream; no host synchronisation).  On a projection or a plan: its last apply, on the
+        handle's stream.'''
+        if self._proj is not None:
+            w = int(weight)
+            if w < 1:
+                raise ValueError('weight must be a positive integer')
+            L.check(getattr(self._lib, 'ps_arrival_add_' + self._proj.fields_kind)(self._h, self._proj._h, w))
+            return
         pm = self.pm
         _check_evaluated(pm, self.days, 'arrival maps')
         stat, post = _day_scales(pm, self.days)
@@ -675,6 +707,7 @@ class Projection():
     and >= 0 (check_weights), at most 32 outputs.  The sum runs in ascending d from +0.0 with the product and
     the sum rounded separately, so a numpy loop reproduces every bit.  An output whose weights are all zero
     is zero throughout: it is kept off the device (`live` lists the others) and reads as zeros.'''
+    fields_kind = 'project'      # the accumulators' entry points for these fields: ps_*_add_project
 
     def __init__(self, pop_model, weights, in_days):
         self._h = L._VP()
@@ -801,24 +834,323 @@ def exposure_plan(exposure, ndays=None):
 class ProjectedMaps():
     '''The posterior of one projection, as posterior_predictive returns it: `weights` [nout, nin], `in_days`,
     `labels` (one per output), `summary` (SpreadSummary.for_projection) and `histogram`
-    (SpreadHistogram.for_projection, None without quantile levels); both take the output index.'''
+    (SpreadHistogram.for_projection, None without quantile levels); both take the output index.  Of a release
+    plan (`posterior_predictive(sites=...)`): `weights` and `in_days` are None, `labels` are the output days,
+    `plan` is ReleaseSites.describe() and `arrival` the ArrivalMaps.for_projection (None without arrival
+    thresholds), whose accessors take the output day.'''
 
-    def __init__(self, weights, in_days, labels, summary, histogram=None):
+    def __init__(self, weights, in_days, labels, summary, histogram=None, arrival=None, plan=None):
         self.weights = weights
         self.in_days = in_days
         self.labels = labels
         self.summary = summary
         self.histogram = histogram
+        self.arrival = arrival
+        self.plan = plan
 
     def merge(self, other):
         self.summary.merge(other.summary)
         if self.histogram is not None:
             self.histogram.merge(other.histogram)
+        if self.arrival is not None:
+            self.arrival.merge(other.arrival)
 
     def close(self):
         self.summary.close()
         if self.histogram is not None:
             self.histogram.close()
+        if self.arrival is not None:
+            self.arrival.close()
+
+
+# ------------------------------------------------------------------ release plans
+def check_sites(sites, rad_dist, rad_res):
+    '''A release plan as a list of dicts, one per site in the order given: east / north (m from the domain
+    centre), amount (multiples of the model's r_number, finite and > 0), lag (whole days >= 0 after the first
+    release, the smallest 0), and the cell offset by the package's convention (Data_Import.LocInfo):
+    dcol = round(east / res), drow = -round(north / res), res = rad_dist / rad_res.  1..32 sites on at most
+    8 different release days, every offset inside the domain (|drow|, |dcol| <= 2 rad_res); ValueError
+    otherwise.  rad_res=None skips the cells (no model at hand).'''
+    try:
+        rows = [tuple(s) for s in sites]
+    except TypeError:
+        raise ValueError('sites must be a list of (east_m, north_m, amount[, lag_days]), got %r' % (sites,))
+    if not 1 <= len(rows) <= MAX_SITES:
+        raise ValueError('%d release sites; 1..%d fit one plan' % (len(rows), MAX_SITES))
+    out = []
+    for k, site in enumerate(rows):
+        if len(site) not in (3, 4):
+            raise ValueError('site %d: (east_m, north_m, amount[, lag_days]) expected, got %r' % (k, site))
+        try:
+            east, north, amount = (float(v) for v in site[:3])
+            lag = site[3] if len(site) == 4 else 0
+            if int(lag) != lag:
+                raise ValueError
+            lag = int(lag)
+        except (TypeError, ValueError):
+            raise ValueError('site %d: numbers and a whole number of lag days expected, got %r' % (k, site))
+        if not (np.isfinite(east) and np.isfinite(north)):
+            raise ValueError('site %d: position %r is not finite' % (k, site[:2]))
+        if not (np.isfinite(amount) and amount > 0):
+            raise ValueError('site %d: amount %r is not finite and > 0' % (k, site[2]))
+        if lag < 0:
+            raise ValueError('site %d: lag %d is negative' % (k, lag))
+        rec = {'east': east, 'north': north, 'amount': amount, 'lag': lag}
+        if rad_res is not None:
+            res = float(rad_dist) / int(rad_res)
+            rec['dcol'] = int(np.around(east / res))
+            rec['drow'] = -int(np.around(north / res))
+            if max(abs(rec['drow']), abs(rec['dcol'])) > 2 * int(rad_res):
+                raise ValueError('site %d: offset (%d, %d) cells lies beyond the %d x %d domain'
+                                 % (k, rec['drow'], rec['dcol'], 2 * int(rad_res) + 1, 2 * int(rad_res) + 1))
+        out.append(rec)
+    lags = sorted({r['lag'] for r in out})
+    if lags[0] != 0:
+        raise ValueError('the first release defines day 0: the smallest lag must be 0, got %d' % lags[0])
+    if len(lags) > MAX_SITE_GROUPS:
+        raise ValueError('%d different release days; at most %d fit one plan' % (len(lags), MAX_SITE_GROUPS))
+    return out
+
+
+def site_groups(sites):
+    '''[(lag, [site index, ...]), ...] of a checked plan: ascending lag, the sites of a lag in the order given'''
+    return [(lag, [k for k, s in enumerate(sites) if s['lag'] == lag]) for lag in sorted({s['lag'] for s in sites})]
+
+
+def check_site_days(days, ndays=None):
+    '''a plan's output days as a list of ints: 1..32 model days >= 0 counted from the first release, strictly
+    increasing, within the model's ndays days if given; ValueError otherwise'''
+    try:
+        d = [int(x) for x in days]
+    except (TypeError, ValueError):
+        raise ValueError('release-plan days must be model days, got %r' % (days,))
+    if not 1 <= len(d) <= MAX_SITE_OUT:
+        raise ValueError('%d release-plan output days; 1..%d fit one plan' % (len(d), MAX_SITE_OUT))
+    if d[0] < 0 or any(b <= a for a, b in zip(d, d[1:])):
+        raise ValueError('release-plan days must be model days >= 0, strictly increasing: %r' % (d,))
+    if ndays is not None and d[-1] >= ndays:
+        raise ValueError('the model has %d days; the release plan asks for day %d' % (ndays, d[-1]))
+    return d
+
+
+def site_slots(lags, days):
+    '''per lag the model day of that release's own model behind every output day: D - lag, None (PS_REC_NONE)
+    while D < lag -- the group is not released yet.  ValueError for a lag after the last output day.'''
+    for lag in lags:
+        if lag > days[-1]:
+            raise ValueError('a release %d days after the first lies beyond the last output day %d' % (lag, days[-1]))
+    return [[D - lag if D >= lag else None for D in days] for lag in lags]
+
+
+def check_lagged(pop_model, lags, lagged):
+    '''the models of the later release days, {lag: PopModel} for every non-zero lag: each runs over
+    pop_model.days[lag:] with the same domain, r_number, prob_model and device; ValueError otherwise'''
+    lagged = dict(lagged or {})
+    for lag in lags:
+        if lag == 0:
+            continue
+        if lag >= len(pop_model.days):
+            raise ValueError('a release %d days after the first lies beyond the model\'s %d days'
+                             % (lag, len(pop_model.days)))
+        if lag not in lagged:
+            raise ValueError('no model for the release %d days after the first (lagged[%d])' % (lag, lag))
+        m = lagged[lag]
+        if list(m.days) != list(pop_model.days[lag:]):
+            raise ValueError('lagged[%d] runs over the days %r, not over the base model\'s days[%d:] = %r'
+                             % (lag, list(m.days), lag, list(pop_model.days[lag:])))
+        for name in ('rad_dist', 'rad_res', 'r_number', 'prob_model', 'device'):
+            if getattr(m, name) != getattr(pop_model, name):
+                raise ValueError('lagged[%d].%s = %r, the base model has %r'
+                                 % (lag, name, getattr(m, name), getattr(pop_model, name)))
+    return {lag: lagged[lag] for lag in lags if lag != 0}
+
+
+def lagged_models(pop_model, lags, wind_data=None):
+    '''{lag: PopModel} for every non-zero lag: a model over pop_model.days[lag:] -- the release that starts
+    `lag` days later sees the later days' wind -- with the base model's settings.  wind_data: the dict the
+    base model was built from (default: the one it kept).'''
+    from .pop_model import PopModel
+    wd = pop_model.wind_data if wind_data is None else wind_data
+    out = {}
+    for lag in sorted({int(x) for x in lags} - {0}):
+        if not 0 < lag < len(pop_model.days):
+            raise ValueError('a release %d days after the first lies beyond the model\'s %d days'
+                             % (lag, len(pop_model.days)))
+        out[lag] = PopModel(wd, pop_model.days[lag:], domain_info=(pop_model.rad_dist, pop_model.rad_res),
+                            r_number=pop_model.r_number, r_start=pop_model.r_start, mode=pop_model.mode,
+                            device=pop_model.device, max_solvers=pop_model._max_solvers,
+                            prob_model=pop_model.prob_model)
+    return out
+
+
+def sites_plan(arg, pop_model=None):
+    '''posterior_predictive's sites= argument, dict(sites=[(east_m, north_m, amount[, lag_days]), ...],
+    days=None), as (sites, days, lags): the checked sites (check_sites), the output days (check_site_days, None:
+    all the model's days) and the release days.  With a model at hand the cells, and the days and lags against
+    the model's days, are checked too.  ValueError for a bad plan.'''
+    if not isinstance(arg, dict) or 'sites' not in arg or set(arg) - {'sites', 'days'}:
+        raise ValueError('sites must be dict(sites=[(east_m, north_m, amount[, lag_days]), ...], days=None), got %r'
+                         % (arg,))
+    have = pop_model is not None
+    sites = check_sites(arg['sites'], pop_model.rad_dist if have else None, pop_model.rad_res if have else None)
+    lags = [lag for lag, _k in site_groups(sites)]
+    ndays = len(pop_model.days) if have else None
+    if have and lags[-1] >= ndays:
+        raise ValueError('a release %d days after the first lies beyond the model\'s %d days' % (lags[-1], ndays))
+    days = arg.get('days')
+    if days is None and have:
+        days = range(ndays)
+    if days is not None:
+        days = check_site_days(days, ndays)
+        site_slots(lags, days)
+    return sites, days, lags
+
+
+class ReleaseSites():
+    '''The field of a whole release plan, member by member, on the device: Y_e = sum over the sites of
+    amount * (the field of that site's release on output day days[e], translated to the site).  sites:
+    [(east_m, north_m, amount[, lag_days=0]), ...] (check_sites); days: output model days counted from the first
+    release (check_site_days, default all); lagged: {lag: PopModel} for every non-zero lag (check_lagged,
+    lagged_models).  One wind station and a homogeneous landscape make the translation exact; what left the
+    single-release domain is lost, so near its own far edge a far-off-centre site gives a lower bound; values
+    are thresholded (1e-8) per site before the sum.  Groups run in ascending lag and sites in the order
+    given, acc = acc + amount * v with the product and the sum rounded separately: a numpy loop reproduces
+    every bit.  Every output carries weight (`live`), so SpreadSummary.for_projection,
+    SpreadHistogram.for_projection and ArrivalMaps.for_projection accept a plan.'''
+    fields_kind = 'sites'        # the accumulators' entry points for these fields: ps_*_add_sites
+
+    def __init__(self, pop_model, sites, days=None, lagged=None):
+        self._h = L._VP()
+        self.sites = check_sites(sites, pop_model.rad_dist, pop_model.rad_res)
+        self.days = check_site_days(range(len(pop_model.days)) if days is None else days, len(pop_model.days))
+        self.groups = site_groups(self.sites)
+        self.lags = [lag for lag, _k in self.groups]
+        self.slots = site_slots(self.lags, self.days)
+        self.lagged = check_lagged(pop_model, self.lags, lagged)
+        self.nout = len(self.days)
+        self.live = list(range(self.nout))
+        self._lib = L.load()
+        self.pm = pop_model
+        self.N = 2 * int(pop_model.rad_res) + 1
+        self.device = L.default_device() if pop_model.device is None else int(pop_model.device)
+        pitch = (self.N * self.N + 63) // 64 * 64
+        self.nbytes = self.nout * pitch * 8                 # the output fields
+        order = [k for _lag, ks in self.groups for k in ks]
+        nsite = L.i32([len(ks) for _lag, ks in self.groups])
+        drow = L.i32([self.sites[k]['drow'] for k in order])
+        dcol = L.i32([self.sites[k]['dcol'] for k in order])
+        amount = L.f64([self.sites[k]['amount'] for k in order])
+        L.check(self._lib.ps_sites_create(self.device, self.N, self.nout, len(self.groups), L.p_i32(nsite),
+                                          L.p_i32(drow), L.p_i32(dcol), L.p_f64(amount), C.byref(self._h)))
+
+    @classmethod
+    def with_lagged_models(cls, pop_model, sites, days=None, wind_data=None):
+        '''the plan with the models of its later release days built here (lagged_models); `close()` closes
+        them too'''
+        lags = [lag for lag, _k in site_groups(check_sites(sites, pop_model.rad_dist, pop_model.rad_res))]
+        check_site_days(range(len(pop_model.days)) if days is None else days, len(pop_model.days))
+        made = lagged_models(pop_model, lags, wind_data)
+        try:
+            self = cls(pop_model, sites, days, made)
+        except Exception:
+            for m in made.values():
+                m.close()
+            raise
+        self._owned = list(made.values())
+        return self
+
+    def models(self):
+        '''[(lag, model), ...] in group order'''
+        return [(lag, self.pm if lag == 0 else self.lagged[lag]) for lag in self.lags]
+
+    def evaluate_lagged(self, *model_args):
+        '''evaluate the model of every later release day over the days the outputs need, enqueued only'''
+        for lag, m in self.models():
+            if lag:
+                m.evaluate(*model_args, ndays=self.days[-1] - lag + 1, want_stats=False)
+
+    def evaluate(self, *model_args):
+        '''evaluate the base model over all its days and every later release's model over the days the
+        outputs need, enqueued only (want_stats=False), then apply()'''
+        self.pm.evaluate(*model_args, want_stats=False)
+        self.evaluate_lagged(*model_args)
+        self.apply()
+
+    def apply(self):
+        '''Superpose the last evaluations of the plan's models, group by group in ascending lag (each
+        enqueued on its solver's stream; no host synchronisation); the outputs of the previous apply are
+        overwritten.'''
+        for call in self._calls():                             # every model checked before the first launch
+            L.check(self._lib.ps_sites_apply(self._h, *call))
+
+    def _calls(self):
+        '''the arguments of ps_sites_apply behind the handle, group by group, from each model's last evaluation'''
+        calls = []
+        for g, (lag, m) in enumerate(self.models()):
+            md = self.slots[g]
+            _check_evaluated(m, [d for d in md if d is not None], 'release plan (lag %d)' % lag)
+            days = [0 if d is None else d for d in md]
+            kind, idx, delta = _day_slots(days)
+            kind[np.array([d is None for d in md], dtype=bool)] = L.REC_NONE
+            stat, post = _day_scales(m, days)
+            calls.append((m.solver._h, g, self.nout, L.p_i32(kind), L.p_i32(idx), L.p_f64(stat), L.p_f64(post),
+                          L.p_i32(delta), NEGVAL))                 # the pointers keep their arrays alive
+        return calls
+
+    @property
+    def applies(self):
+        '''complete passes over the plan's groups'''
+        n = C.c_int64()
+        L.check(self._lib.ps_sites_info(self._h, None, None, None, None, C.byref(n)))
+        return n.value
+
+    def field(self, e):
+        '''[N, N] float64: output e (model day days[e]) of the last apply'''
+        if not 0 <= int(e) < self.nout:
+            raise ValueError('output %r of %d' % (e, self.nout))
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        L.check(self._lib.ps_sites_fetch(self._h, int(e), L.p_f64(out)))
+        return out
+
+    def gather(self, rows, cols):
+        '''[nout, n] float64: every output of the last apply at the cells (rows[k], cols[k])'''
+        rows, cols = L.i32(np.asarray(rows).ravel()), L.i32(np.asarray(cols).ravel())
+        if rows.size != cols.size:
+            raise ValueError('%d rows and %d columns' % (rows.size, cols.size))
+        out = np.zeros((self.nout, rows.size), dtype=np.float64)
+        L.check(self._lib.ps_sites_gather(self._h, rows.size, L.p_i32(rows), L.p_i32(cols), L.p_f64(out)))
+        return out
+
+    def profile(self, enable=None):
+        '''HIP-event time of the apply launches, one per group: (total ms, launches); enable switches it'''
+        ms, n = C.c_double(), C.c_int64()
+        L.check(self._lib.ps_sites_prof(self._h, -1 if enable is None else int(bool(enable)), C.byref(ms),
+                                        C.byref(n)))
+        return ms.value, n.value
+
+    def describe(self):
+        '''the plan for a result file: sites in metres and cells, release days, output days'''
+        return {'sites': [dict(s) for s in self.sites], 'lags': list(self.lags), 'days': list(self.days)}
+
+    def close(self):
+        if self._h:
+            self._lib.ps_sites_destroy(self._h)
+            self._h = L._VP()
+        for m in getattr(self, '_owned', []):
+            m.close()
+        self._owned = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 # ------------------------------------------------------------------ traces
@@ -950,13 +1282,16 @@ class PredictiveResult():
     or None) and `provenance`; with quantile levels `histogram` (a SpreadHistogram, None without a
     device) and `quantiles` (the levels), else both None; with arrival thresholds `arrival` (ArrivalMaps,
     None without a device) and `arrival_levels`, else both None; `emergence` / `exposure`: ProjectedMaps of the
-    emergence and cumulative-exposure projections, None where not asked for.'''
+    emergence and cumulative-exposure projections, None where not asked for; `sites`: ProjectedMaps of the
+    release plan (with `plan` and, with arrival thresholds, `arrival`), None where not asked for.'''
 
     def __init__(self, summary, rows, evaluations, failed, seconds, runs, observations, provenance, days,
-                 histogram=None, quantiles=None, arrival=None, arrival_levels=None, emergence=None, exposure=None):
+                 histogram=None, quantiles=None, arrival=None, arrival_levels=None, emergence=None, exposure=None,
+                 sites=None):
         self.summary = summary
         self.emergence = emergence
         self.exposure = exposure
+        self.sites = sites
         self.histogram = histogram
         self.quantiles = quantiles
         self.arrival = arrival
@@ -983,7 +1318,12 @@ class PredictiveResult():
         outfile_emergence.npz / outfile_exposure.npz in the same layout (`days` of the main file are model days):
         per output `{label}_*` of the mean, `{label}_sd_*`, `{label}_pexc{k}_*`, `{label}_q{tag}_*`, the label
         the emergence day in days post release, or the exposure's model day; their weights, input days and
-        labels under `predictive.emergence` / `predictive.exposure` of the json.  -> (npz path, json path)'''
+        labels under `predictive.emergence` / `predictive.exposure` of the json.  A release plan goes into
+        outfile_sites.npz in that layout too, the label the output day; with arrival maps also `{label}_parr{k}_*`,
+        the dense `arrival{k}_{tag}`, `arrival{k}_cells` and `arrival_weights` of the plan, as in the main file;
+        under `predictive.sites` of the json the plan (sites in metres and cells, lags, days), the thresholds,
+        the levels and with arrival maps their thresholds, levels, cell area and the reached area per threshold.
+        -> (npz path, json path)'''
         s = self.summary
         if s is None:
             raise ValueError('no spread summary to save (evaluate= runs without a device)')
@@ -1023,30 +1363,50 @@ class PredictiveResult():
                                              'days': list(A.days), 'cell_area': A.cell_area,
                                              'reached_area': [A.reached_area(k, a_levels)
                                                               for k in range(len(A.thresholds))]}
-        for name, pr in (('emergence', self.emergence), ('exposure', self.exposure)):
+        for name, pr in (('emergence', self.emergence), ('exposure', self.exposure), ('sites', self.sites)):
             if pr is None:
                 continue
-            ps, ph = pr.summary, pr.histogram
+            ps, ph, pa = pr.summary, pr.histogram, pr.arrival
             p_levels = list(self.quantiles or ()) if ph is not None else []
+            pa_levels = list(self.arrival_levels or ()) if pa is not None else []
             pmaps = []
             for e, label in enumerate(pr.labels):
                 out_maps = [('', ps.mean(e)), ('_sd', ps.sd(e))]
                 out_maps += [('_pexc%d' % k, ps.exceedance(e, k)) for k in range(len(ps.thresholds))]
                 out_maps += [('_' + quantile_tag(p), ph.quantile(e, p)) for p in p_levels]
+                if pa is not None:
+                    out_maps += [('_parr%d' % k, pa.prob_by(k, label)) for k in range(len(pa.thresholds))]
                 pmaps.append((label, out_maps))
-            save_maps('%s_%s' % (outfile, name), pmaps)
-            meta['predictive'][name] = {'weights': np.asarray(pr.weights).tolist(), 'in_days': list(pr.in_days),
-                                        'labels': list(pr.labels), 'thresholds': list(ps.thresholds),
-                                        'levels': p_levels}
+            pextra = {}
+            if pa is not None:
+                for k in range(len(pa.thresholds)):
+                    for p in pa_levels:
+                        pextra['arrival%d_%s' % (k, quantile_tag(p))] = pa.quantile(k, p).astype(np.int16)
+                    cells, w = pa.reached(k)
+                    pextra['arrival%d_cells' % k] = cells
+                pextra['arrival_weights'] = w
+            save_maps('%s_%s' % (outfile, name), pmaps, pextra)
+            if pr.plan is None:
+                meta['predictive'][name] = {'weights': np.asarray(pr.weights).tolist(), 'in_days': list(pr.in_days)}
+            else:
+                meta['predictive'][name] = dict(pr.plan)
+            meta['predictive'][name].update({'labels': list(pr.labels), 'thresholds': list(ps.thresholds),
+                                             'levels': p_levels})
+            if pa is not None:
+                meta['predictive'][name]['arrival'] = {
+                    'thresholds': list(pa.thresholds), 'levels': pa_levels, 'cell_area': pa.cell_area,
+                    'reached_area': [pa.reached_area(k, pa_levels) for k in range(len(pa.thresholds))]}
         with open(str(outfile) + '.json', 'w') as fobj:
             json.dump(meta, fobj, default=str)
         return str(outfile) + '.npz', str(outfile) + '.json'
 
 
 def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, locinfo, histogram=None,
-                   arrival=None, projected=()):
+                   arrival=None, projected=(), plan=None):
     '''one chain: evaluate every run, add it to the summary (and the histogram, the arrival maps; projected:
-    (Projection, ProjectedMaps) pairs, applied and then added) -> (expected per run or None, failed)'''
+    (Projection, ProjectedMaps) pairs, applied and then added; plan: a (ReleaseSites, ProjectedMaps) pair, the
+    models of its later release days evaluated with the base model -- a member for which any of them fails is
+    a failed member and is added nowhere -- applied and added last) -> (expected per run or None, failed)'''
     expected = []
     failed = 0
     for first, length in run_list:
@@ -1059,6 +1419,8 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
             continue
         try:
             pm.evaluate(*mcmc.model_args(theta), want_stats=False)
+            if plan is not None:
+                plan[0].evaluate_lagged(*mcmc.model_args(theta))
         except (AssertionError, ValueError):
             failed += 1
             expected.append(None)
@@ -1079,13 +1441,18 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
             maps.summary.add(length)
             if maps.histogram is not None:
                 maps.histogram.add(length)
+        if plan is not None:
+            plan[0].apply()
+            for acc in (plan[1].summary, plan[1].histogram, plan[1].arrival):
+                if acc is not None:
+                    acc.add(length)
         expected.append(mcmc.expected_observations(pm, locinfo) if want_obs else True)
     return expected, failed
 
 
 def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, thresholds=(), locinfo=None,
                          cell_area=None, seed=0, evaluate=None, quantiles=None, bins=DEFAULT_BINS, edges=None,
-                         arrival=None, arrival_levels=(0.05, 0.5, 0.95), emergence=None, exposure=None):
+                         arrival=None, arrival_levels=(0.05, 0.5, 0.95), emergence=None, exposure=None, sites=None):
     '''Posterior predictive spread of one or more chains (`Sampler.save` files or (trace, names)
     pairs).  Burn and thin apply per chain; consecutive rows with identical model parameters are one
     evaluation weighted by the run's length.  pop_model: one PopModel or a list -- with several, one
@@ -1101,7 +1468,13 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     obs_days=None) (emergence_plan); exposure: model days [D1, D2, ...] (exposure_plan); each chain then also
     applies that Projection after every evaluation and adds its outputs, with the same weights, to a
     SpreadSummary.for_projection (same thresholds) and, with quantiles, a SpreadHistogram.for_projection
-    (same edges), merged in chain order into `emergence` / `exposure` (ProjectedMaps).'''
+    (same edges), merged in chain order into `emergence` / `exposure` (ProjectedMaps).  sites:
+    dict(sites=[(east_m, north_m, amount[, lag_days]), ...], days=None) (sites_plan); each chain then also
+    builds one ReleaseSites (the models of the later release days, lagged_models, once per model), evaluates those models
+    with every member, applies the plan and adds its outputs, with the same weights, to a
+    SpreadSummary.for_projection (same thresholds), with quantiles a SpreadHistogram.for_projection (same
+    edges) and with arrival an ArrivalMaps.for_projection (same thresholds), merged in chain order into `sites`
+    (ProjectedMaps with `plan` and `arrival`).'''
     t0 = time.perf_counter()
     levels = (check_levels(quantiles) if quantiles is not None else []) or None
     if levels:
@@ -1115,6 +1488,12 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     wanted = [(name, arg, plan) for name, arg, plan in (('emergence', emergence, emergence_plan),
                                                         ('exposure', exposure, exposure_plan)) if arg is not None]
     plans = [(name,) + plan(arg) for name, arg, plan in wanted]      # and bad projection arguments
+    site_plan = None
+    if sites is not None:             # and a bad release plan: its cells, days and lags against the model if there is one
+        pm0 = (pop_model[0] if pop_model else None) if isinstance(pop_model, (list, tuple)) else pop_model
+        site_plan = sites_plan(sites, pm0)
+        if pm0 is None:
+            site_plan = None
     if isinstance(chains, (str, os.PathLike)) or (isinstance(chains, tuple) and len(chains) == 2
                                                    and not isinstance(chains[0], (str, os.PathLike, tuple))):
         chains = [chains]
@@ -1142,6 +1521,8 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     histograms = [None] * nch
     arrivals = [None] * nch
     projected = [[] for _ in range(nch)]       # per chain (Projection, ProjectedMaps) of every plan
+    site_maps = [None] * nch                   # per chain (ReleaseSites, ProjectedMaps)
+    late = {}                                  # per model the models of the plan's later release days
     results = [None] * nch
     errs = []
 
@@ -1164,8 +1545,20 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                         projected[ci][-1] = (proj, maps)
                         if levels:
                             maps.histogram = SpreadHistogram.for_projection(proj, bins, edges)
+                    if site_plan is not None:
+                        if p not in late:
+                            late[p] = lagged_models(pm, site_plan[2])
+                        rs = ReleaseSites(pm, sites['sites'], site_plan[1], late[p])
+                        site_maps[ci] = (rs, None)
+                        maps = ProjectedMaps(None, None, list(rs.days), SpreadSummary.for_projection(rs, thresholds),
+                                             plan=rs.describe())
+                        site_maps[ci] = (rs, maps)
+                        if levels:
+                            maps.histogram = SpreadHistogram.for_projection(rs, bins, edges)
+                        if a_thr:
+                            maps.arrival = ArrivalMaps.for_projection(rs, a_thr)
                 results[ci] = _evaluate_runs(pm, summ, rows, rl, mcols, evaluate, want_obs, locinfo, hist, arr,
-                                             projected[ci])
+                                             projected[ci], site_maps[ci])
         except BaseException as e:       # re-raised in the caller's thread
             errs.append((p, e))
 
@@ -1180,7 +1573,9 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         pms = pms[:1]
         work(0)
     if errs:
-        for s in summaries + histograms + arrivals + [x for pl in projected for pair in pl for x in pair]:
+        for s in summaries + histograms + arrivals + [x for pl in projected for pair in pl for x in pair] \
+                + [x for pair in site_maps if pair is not None for x in pair] \
+                + [m for made in late.values() for m in made.values()]:
             if s is not None:
                 s.close()
         raise errs[0][1]
@@ -1211,6 +1606,17 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     for pl in projected:                 # the accumulators hold what they need: the output fields go
         for proj, _maps in pl:
             proj.close()
+    merged_sites = None
+    if evaluate is None and site_plan is not None:
+        merged_sites = site_maps[0][1]
+        for _rs, maps in site_maps[1:]:
+            merged_sites.merge(maps)
+            maps.close()
+        for rs, _maps in site_maps:      # and the plans with the models of their later release days
+            rs.close()
+        for made in late.values():
+            for m in made.values():
+                m.close()
     evaluations = sum(len(p[1]) for p in prepared)
     failed = sum(r[1] for r in results)
     run_rec = [(ci, first, length) for ci, p in enumerate(prepared)
@@ -1231,7 +1637,8 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     res = PredictiveResult(summary, int(sum(len(p[0]) for p in prepared)), evaluations, failed,
                            time.perf_counter() - t0, run_rec, observations, prov,
                            None if summary is None else summary.days, histogram, levels, arrival_maps,
-                           a_levels if a_thr else None, merged.get('emergence'), merged.get('exposure'))
+                           a_levels if a_thr else None, merged.get('emergence'), merged.get('exposure'),
+                           merged_sites)
     if cell_area is not None:
         res.cell_area = float(cell_area)
     return res

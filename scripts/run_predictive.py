@@ -6,7 +6,9 @@ per-cell quantile maps from device histograms on fixed bin edges (--bins); with 
 probability and arrival-day quantile maps and the reached area per day (--arrival-levels); with --emergence /
 --exposure also the posterior maps of the projected emergence after a collection on day C (daily, or binned
 into the observation days d1,d2,...) and of the cumulative exposure up to the listed model days, saved as
-PREFIX_emergence.npz / PREFIX_exposure.npz.  Kalbar wind and
+PREFIX_emergence.npz / PREFIX_exposure.npz; with --sites also the posterior maps of a release plan -- several
+release sites, some released days later -- saved as PREFIX_sites.npz (with --arrival including its arrival maps
+and, in the json, its reached-area curve).  Kalbar wind and
 LocInfo as scripts/run_mcmc.py loads them; --synthetic uses the synthetic Kalbar-like observations.
 Without --chain a short chain is sampled first (--samples) and saved next to --out.
 
@@ -14,6 +16,7 @@ Without --chain a short chain is sampled first (--samples) and saved next to --o
         [--mode auto] [--thresholds 1,10] [--out PREFIX] [--synthetic] [--chains-parallel]
         [--quantiles 0.05,0.5,0.95] [--bins 1e-8,1e6,16] [--arrival 1,10] [--arrival-levels 0.05,0.5,0.95]
         [--emergence C[:d1,d2,...]] [--exposure d1,d2,...]
+        [--sites 'E,N,AMOUNT[,LAG];...'] [--sites-days d1,d2,...]
 """
 import argparse
 import json
@@ -48,13 +51,18 @@ def main():
     ap.add_argument('--emergence', default='', help='collection day C, or C:d1,d2,... with the observation days '
                                                     '(days post release; default: off)')
     ap.add_argument('--exposure', default='', help='model days d1,d2,... of the cumulative exposure (default: off)')
+    ap.add_argument('--sites', default='', help="release plan 'E,N,AMOUNT[,LAG];...': metres east and north of the "
+                                                "domain centre, multiples of the release number, days after the "
+                                                'first release (default: off)')
+    ap.add_argument('--sites-days', default='', help='output model days d1,d2,... of the release plan '
+                                                     '(default: all, at most 32)')
     args = ap.parse_args()
     warnings.simplefilter('ignore', RuntimeWarning)
     from parasitoids_amd import ParasitoidModel as PM
     from parasitoids_amd import mcmc
     from parasitoids_amd.pop_model import PopModel
     from parasitoids_amd.predictive import (bin_edges, check_arrival_thresholds, check_levels, emergence_plan,
-                                            exposure_plan, posterior_predictive)
+                                            exposure_plan, posterior_predictive, sites_plan)
     levels = check_levels([float(q) for q in args.quantiles.split(',') if q.strip()])
     bins = tuple(float(b) for b in args.bins.split(','))
     bin_edges(bins)                      # a bad --bins fails before any work
@@ -68,6 +76,12 @@ def main():
         emergence = dict(collection_day=int(cday), obs_days=[int(d) for d in obs.split(',') if d.strip()] or None)
     if args.exposure:
         exposure = [int(d) for d in args.exposure.split(',') if d.strip()]
+    sites = None
+    if args.sites:
+        sites = dict(sites=[tuple(float(v) if n < 3 else int(v) for n, v in enumerate(site.split(',')))
+                            for site in args.sites.split(';') if site.strip()],
+                     days=[int(d) for d in args.sites_days.split(',') if d.strip()] or None)
+        sites_plan(sites)                # a bad --sites fails before any work; against the model below
     wd, days = PM.get_wind_data(os.path.join(ROOT, 'parasitoids_amd', 'data', 'kalbar'), 30, '00:00')
 
     def make_pm():
@@ -75,6 +89,10 @@ def main():
     plans = ([emergence_plan(emergence, len(days))] if emergence else []) \
         + ([exposure_plan(exposure, len(days))] if exposure else [])     # bad projections fail before any work too
     pm = make_pm()
+    if sites:
+        if sites['days'] is None:
+            sites['days'] = list(range(min(len(days), 32)))
+        sites_plan(sites, pm)
     if args.synthetic:
         li = mcmc.synthetic_locinfo(pm, args.rad_res, seed=9)
     else:
@@ -98,10 +116,12 @@ def main():
     res = posterior_predictive(pms if len(pms) > 1 else pm, chains, burn=args.burn, thin=args.thin,
                                thresholds=thr, locinfo=li, cell_area=cell_area, seed=args.seed,
                                quantiles=levels or None, bins=bins, arrival=arrival or None, arrival_levels=a_levels,
-                               emergence=emergence, exposure=exposure)
+                               emergence=emergence, exposure=exposure, sites=sites)
     dt = time.perf_counter() - t0
     # accumulate-kernel time: the same members once more with HIP events around every add
-    from parasitoids_amd.predictive import ArrivalMaps, Projection, SpreadHistogram, SpreadSummary, load_chain, runs
+    from parasitoids_amd.predictive import (ArrivalMaps, Projection, ReleaseSites, SpreadHistogram, SpreadSummary,
+                                            load_chain, runs)
+    RS = ReleaseSites.with_lagged_models(pm, sites['sites'], sites['days']) if sites else None
     projections = [Projection(pm, W, in_days) for W, in_days, _labels in plans]
     H = SpreadHistogram(pm, None, bins) if levels else None
     A = ArrivalMaps(pm, arrival) if arrival else None
@@ -113,6 +133,8 @@ def main():
             A.profile(True)
         for P in projections:
             P.profile(True)
+        if RS is not None:
+            RS.profile(True)
         n = 0
         for c in chains[:1]:
             trace, names, _ = load_chain(c)
@@ -121,6 +143,8 @@ def main():
             for first, length in rl[:8]:
                 try:
                     pm.evaluate(*mcmc.model_args(rows[first, cols]), want_stats=False)
+                    if RS is not None:
+                        RS.evaluate_lagged(*mcmc.model_args(rows[first, cols]))
                 except Exception:
                     continue
                 S.add(length)
@@ -130,6 +154,8 @@ def main():
                     A.add(length)
                 for P in projections:
                     P.apply()
+                if RS is not None:
+                    RS.apply()
                 n += 1
         ms, launches = S.profile()
     if H is not None:
@@ -145,6 +171,10 @@ def main():
     p_bytes = sum(P.nbytes for P in projections)
     for P in projections:
         P.close()
+    if RS is not None:
+        s_ms, s_launches = RS.profile()
+        s_bytes, s_groups, s_nsite = RS.nbytes, len(RS.groups), len(RS.sites)
+        RS.close()
     npz, js = res.save(args.out, {'chains': chains, 'burn': args.burn, 'thin': args.thin, 'rad_res': args.rad_res,
                                   'mode': args.mode, 'synthetic': bool(args.synthetic)})
     ncell = (2 * args.rad_res + 1) ** 2
@@ -173,13 +203,19 @@ def main():
         out['project_bytes'] = p_bytes                                   # the output fields
         out['outputs'] += ['%s_%s.npz' % (args.out, name) for name, on in (('emergence', emergence),
                                                                              ('exposure', exposure)) if on]
+    if sites:
+        out['sites_ms_per_member'] = round(s_ms / max(n, 1), 4)        # every group's apply of one member
+        out['sites_launches_timed'] = s_launches
+        out['sites_bytes'] = s_bytes                                    # the output fields
+        out['sites'] = {'sites': s_nsite, 'groups': s_groups, 'days': len(sites['days'])}
+        out['outputs'] += ['%s_sites.npz' % args.out]
     print(json.dumps(out))
     res.summary.close()
     if res.histogram is not None:
         res.histogram.close()
     if res.arrival is not None:
         res.arrival.close()
-    for pr in (res.emergence, res.exposure):
+    for pr in (res.emergence, res.exposure, res.sites):
         if pr is not None:
             pr.close()
     for p in pms:
