@@ -595,6 +595,64 @@ int ps_summary_add_sites(ps_summary* a, ps_sites* p, uint32_t weight);
 int ps_hist_add_sites(ps_hist* h, ps_sites* p, uint32_t weight);
 int ps_arrival_add_sites(ps_arrival* a, ps_sites* p, uint32_t weight);
 
+/* ---- posterior sensitivity maps: which scalar of the members drives the spread of each cell ----
+ * (no reference counterpart; the global form of the J maps of ps_linspread, from the members of a chain
+ * instead of a stencil around a point estimate).  A generic accumulator of the weighted co-moments between
+ * fields and nparam scalars that the caller supplies per member -- the handle does not know what they are.
+ * It lives on one device and holds nslot slots of N x N cells (pitch as ps_summary), all fp64: mean[slot],
+ * M2[slot], C[param][slot] with C_i = sum over the members of w (v - mean_before) (theta_i - thetabar_i,after),
+ * and after finalisation expl[slot] (fp64) and dom[slot] (uint8).  Limits: 1 <= nparam <= 16, nslot >= 1.
+ * The whole block, ((nparam + 3) * 8 + 1) * nslot * pitch bytes, is checked against the free device memory
+ * first: PS_ERR_OOM before anything is allocated.  Host side: the total weight W (< 2^32) and the member
+ * count.  One thread owns a pair of cells: no atomics, the same calls in the same order give the same bits.
+ * Every operation records an event that the next one waits on, on whatever stream it runs (the solver's for
+ * add, the handle's own otherwise). */
+typedef struct ps_sens ps_sens;
+int ps_sens_create(int device, int N, int nslot, int nparam, ps_sens** out);
+/* Accumulate one member with integer weight w >= 1 from the records of solver s: the slot descriptors and
+ * the value v of a cell are those of ps_summary_add (same arguments, same value bit for bit).  e[nparam]:
+ * the member's deviation of every scalar from that scalar's weighted mean AFTER this member, computed by
+ * the caller; every e finite, nparam the handle's.  Per cell, with W' = W + w and d = v - mean:
+ *   d == 0: nothing changes, nothing is stored; else
+ *   mean += d w / W',  M2 += w d (v - mean)        (the statements of ps_summary_add: the same bits)
+ *   C_i = C_i + (w d) e_i                          (w d, the product and the sum each rounded on its own)
+ * so a host loop with one rounded operation per statement reproduces mean and every C_i bit for bit.  A pair
+ * of cells with d == 0 in both reads the record and the two moments and touches no C_i.  One launch per 32
+ * slots on the solver's stream, no host synchronisation; every descriptor is resolved before anything is
+ * enqueued. */
+int ps_sens_add(ps_sens* h, ps_solver* s, int nslot, const int32_t* kind, const int32_t* idx,
+                const double* stat_scale, const double* post_scale, const int32_t* use_delta, double negval,
+                int nparam, const double* e, uint32_t weight);
+/* The same member whose values are the current outputs of a projection or a release plan, as
+ * ps_summary_add_project / ps_summary_add_sites take them: slot k takes Y_k, on the handle's stream behind the
+ * source's last operation; its next apply waits for the read.  PS_ERR_STATE where the source has no finished
+ * fields. */
+int ps_sens_add_project(ps_sens* h, ps_project* p, int nparam, const double* e, uint32_t weight);
+int ps_sens_add_sites(ps_sens* h, ps_sites* p, int nparam, const double* e, uint32_t weight);
+/* dst += src (Chan et al. pairwise update), same device, N, slots and nparam; src stays as it is.
+ * dtheta[i] = the weighted mean of scalar i over src's members minus that over dst's, from the caller:
+ *   mean, M2 as ps_summary_merge;  C_i = Ca_i + Cb_i + (mean_b - mean_a) dtheta_i (Wa Wb / W).
+ * Into an empty dst (W = 0) it is a device copy, bit for bit. */
+int ps_sens_merge(ps_sens* dst, ps_sens* src, int nparam, const double* dtheta);
+/* F: nparam x rank, row-major, rank <= 16, with F F' the (pseudo-)inverse of the scalars' covariance;
+ * isd[nparam]: their inverse standard deviations (0 for a scalar to be left out).  Per cell, with
+ * c_i = C_i / W and var = M2 / W, every product, sum and quotient rounded on its own, the sums from +0.0 in
+ * ascending index:
+ *   expl = (sum_k (sum_i F_ik c_i)^2) / var     the share of var a linear dependence on the scalars explains
+ *                                               (a sum of squares: never negative; exactly 0 where M2 == 0)
+ *   dom  = the lowest i that maximises (c_i isd_i)^2, compared by a strict > in index order
+ *                                               (255 where M2 == 0 or every square is 0)
+ * PS_ERR_STATE at W = 0.  Any later add, merge or reset invalidates the result. */
+int ps_sens_finalize(ps_sens* h, int nparam, int rank, const double* F, const double* isd);
+/* one slot to the host (synchronises): what 0 mean, 1 variance M2 / W, 2 expl, 3 dom as doubles (-1 for 255),
+ * 16 + i covariance C_i / W.  PS_ERR_STATE at W = 0, and for 2 and 3 unless finalized since the last change. */
+int ps_sens_fetch(ps_sens* h, int slot, int what, double* out /* N*N */);
+int ps_sens_info(ps_sens* h, double* total_weight, int64_t* members);
+int ps_sens_reset(ps_sens* h);
+/* measurement: HIP-event timing of the add launches, as ps_summary_prof */
+int ps_sens_prof(ps_sens* h, int enable, double* total_ms, int64_t* launches);
+void ps_sens_destroy(ps_sens* h);
+
 #ifdef __cplusplus
 }
 #endif

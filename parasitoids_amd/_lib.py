@@ -180,6 +180,18 @@ SIGNATURES = {
     'ps_summary_add_sites': (C.c_int, [_VP, _VP, C.c_uint32]),
     'ps_hist_add_sites': (C.c_int, [_VP, _VP, C.c_uint32]),
     'ps_arrival_add_sites': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_sens_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_VP)]),
+    'ps_sens_add': (C.c_int, [_VP, _VP, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P, C.c_double, C.c_int, _F64P,
+                              C.c_uint32]),
+    'ps_sens_add_project': (C.c_int, [_VP, _VP, C.c_int, _F64P, C.c_uint32]),
+    'ps_sens_add_sites': (C.c_int, [_VP, _VP, C.c_int, _F64P, C.c_uint32]),
+    'ps_sens_merge': (C.c_int, [_VP, _VP, C.c_int, _F64P]),
+    'ps_sens_finalize': (C.c_int, [_VP, C.c_int, C.c_int, _F64P, _F64P]),
+    'ps_sens_fetch': (C.c_int, [_VP, C.c_int, C.c_int, _F64P]),
+    'ps_sens_info': (C.c_int, [_VP, _F64P, _I64P]),
+    'ps_sens_reset': (C.c_int, [_VP]),
+    'ps_sens_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P]),
+    'ps_sens_destroy': (None, [_VP]),
 }
 
 _lib = None

@@ -151,3 +151,13 @@ __device__ inline double ps_record_value(double r, double stat_scale, double pos
   const bool keep = (t != 0.0) && !(t < negval);
   return keep ? (t + delta) * post_scale : 0.0;
 }
+
+// one weighted Welford step of a cell (West 1979), shared by ps_summary.hip and ps_sens.hip so that both round
+// alike: false, and nothing changed, where the value equals the mean
+__device__ inline bool sum_update(double v, double w, double Wn, double& m, double& m2) {
+  const double d = v - m;
+  if (d == 0.0) return false;          // mean and M2 stay bit for bit as they are
+  m += d * w / Wn;
+  m2 += w * d * (v - m);
+  return true;
+}

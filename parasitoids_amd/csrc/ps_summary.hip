@@ -26,14 +26,6 @@ struct SumThr {
   double t[PS_SUM_MAX_THR];
 };
 
-__device__ inline bool sum_update(double v, double w, double Wn, double& m, double& m2) {
-  const double d = v - m;
-  if (d == 0.0) return false;          // mean and M2 stay bit for bit as they are
-  m += d * w / Wn;
-  m2 += w * d * (v - m);
-  return true;
-}
-
 // blockIdx.y = slot of the chunk; a thread owns a pair of cells (the tail cell of an odd N*N alone)
 __global__ void k_summary_add(SumSlots desc, double* __restrict__ mean, double* __restrict__ m2,
                               uint32_t* __restrict__ cnt, int64_t ncell, int64_t pitch, int nthr, SumThr thr,

@@ -21,6 +21,11 @@ from the per-day moments.  `ReleaseSites` superposes, on the device, the transla
 sites and of releases on later days (ps_sites_*, csrc/ps_sites.hip) into the field of a whole release plan,
 which the same accumulators and `ArrivalMaps.for_projection` take per member -- neither can the spread, the
 quantiles, the arrival day or the reached area of a sum over sites be rebuilt from the per-site maps.
+`SensitivityMaps` keeps, on the device, per cell the weighted co-moments between the same values and the model
+parameters of the member behind them (ps_sens_*, csrc/ps_sens.hip; `ParamMoments` is the parameters' side on the
+host): which parameter the spread at a cell comes from, as correlation maps, the share of the variance a linear
+dependence on the parameters explains, and the dominant parameter -- a chain stores no fields, so this
+covariance cannot be formed after the run.
 """
 import ctypes as C
 import json
@@ -837,9 +842,12 @@ class ProjectedMaps():
     (SpreadHistogram.for_projection, None without quantile levels); both take the output index.  Of a release
     plan (`posterior_predictive(sites=...)`): `weights` and `in_days` are None, `labels` are the output days,
     `plan` is ReleaseSites.describe() and `arrival` the ArrivalMaps.for_projection (None without arrival
-    thresholds), whose accessors take the output day.'''
+    thresholds), whose accessors take the output day.  `sensitivity`: the SensitivityMaps.for_projection (None
+    unless asked for), which takes the output index.'''
 
-    def __init__(self, weights, in_days, labels, summary, histogram=None, arrival=None, plan=None):
+    def __init__(self, weights, in_days, labels, summary, histogram=None, arrival=None, plan=None,
+                 sensitivity=None):
+        self.sensitivity = sensitivity
         self.weights = weights
         self.in_days = in_days
         self.labels = labels
@@ -854,6 +862,8 @@ class ProjectedMaps():
             self.histogram.merge(other.histogram)
         if self.arrival is not None:
             self.arrival.merge(other.arrival)
+        if self.sensitivity is not None:
+            self.sensitivity.merge(other.sensitivity)
 
     def close(self):
         self.summary.close()
@@ -861,6 +871,8 @@ class ProjectedMaps():
             self.histogram.close()
         if self.arrival is not None:
             self.arrival.close()
+        if self.sensitivity is not None:
+            self.sensitivity.close()
 
 
 # ------------------------------------------------------------------ release plans
@@ -1153,6 +1165,360 @@ class ReleaseSites():
             pass
 
 
+# ------------------------------------------------------------------ sensitivity
+MAX_SENS_PARAMS = 16       # ps_sens: the scalars of one handle
+
+
+def check_sens_params(params):
+    '''posterior_predictive's sensitivity= argument as a list of names from mcmc.MODEL_BLOCK: None or True
+    is all of them, in their order; else 1..16 different names; ValueError otherwise'''
+    known = [m[0] for m in mcmc.MODEL_BLOCK]
+    if params is None or params is True:
+        return known
+    if isinstance(params, str):
+        params = [params]
+    try:
+        names = [str(n) for n in params]
+    except TypeError:
+        raise ValueError('sensitivity parameters must be a list of names, got %r' % (params,))
+    bad = [n for n in names if n not in known]
+    if bad:
+        raise ValueError('unknown sensitivity parameters %r; the model parameters are %r' % (bad, known))
+    if not 1 <= len(names) <= MAX_SENS_PARAMS:
+        raise ValueError('%d sensitivity parameters; 1..%d fit one handle' % (len(names), MAX_SENS_PARAMS))
+    if len(set(names)) != len(names):
+        raise ValueError('sensitivity parameters listed twice: %r' % (names,))
+    return names
+
+
+class ParamMoments():
+    '''Weighted running mean, co-moment matrix and total weight of the scalars `names` (1..16) of the members,
+    on the host: the scalar side of ps_sens, whose adds take the vector `update` returns.  The first member sets
+    the mean to its scalars exactly, so a scalar that never changes has deviation, variance and co-moments
+    exactly 0.'''
+
+    def __init__(self, names):
+        self.names = [str(n) for n in names]
+        if not 1 <= len(self.names) <= MAX_SENS_PARAMS:
+            raise ValueError('%d scalars; 1..%d fit one handle' % (len(self.names), MAX_SENS_PARAMS))
+        self.reset()
+
+    def reset(self):
+        n = len(self.names)
+        self.W = 0
+        self.members = 0
+        self.m = np.zeros(n)
+        self.C = np.zeros((n, n))
+
+    def _state(self):
+        return self.W, self.members, self.m.copy(), self.C.copy()
+
+    def _restore(self, state):
+        self.W, self.members, self.m, self.C = state
+
+    def update(self, theta, w=1):
+        '''One member with integer weight w >= 1 -> e = theta - (the weighted mean after this member), the
+        vector its device add needs: Wn = W + w, d = theta - m, m' = m + d w / Wn, e = theta - m',
+        C += outer(w d, e).'''
+        t = np.array(theta, dtype=np.float64).ravel()
+        if t.size != len(self.names):
+            raise ValueError('%d scalars given, the moments hold %d' % (t.size, len(self.names)))
+        if not np.all(np.isfinite(t)):
+            raise ValueError('every scalar must be finite: %r' % (t.tolist(),))
+        if int(w) != w or int(w) < 1:
+            raise ValueError('weight must be a positive integer')
+        w = int(w)
+        if self.W + w >= 2 ** 32:
+            raise ValueError('total weight %d would reach 2^32' % (self.W + w))
+        if self.W == 0:
+            m1 = t.copy()
+        else:
+            d = t - self.m
+            m1 = self.m + d * float(w) / float(self.W + w)
+        e = t - m1
+        if self.W:
+            self.C = self.C + np.outer(float(w) * d, e)
+        self.m = m1
+        self.W += w
+        self.members += 1
+        return e
+
+    def merge(self, other):
+        '''self += other (Chan et al.) -> dtheta = other's means minus self's before the merge, the vector the
+        device merge needs'''
+        if other.names != self.names:
+            raise ValueError('moments of different scalars: %r and %r' % (self.names, other.names))
+        if self.W + other.W >= 2 ** 32:
+            raise ValueError('total weight %d would reach 2^32' % (self.W + other.W))
+        if other.W == 0:
+            return np.zeros(len(self.names))
+        d = other.m - self.m
+        if self.W == 0:
+            self.m, self.C = other.m.copy(), other.C.copy()
+        else:
+            Wa, Wb = float(self.W), float(other.W)
+            self.C = self.C + other.C + np.outer(d, d) * (Wa * Wb / (Wa + Wb))
+            self.m = self.m + d * (Wb / (Wa + Wb))
+        self.W += other.W
+        self.members += other.members
+        return d
+
+    def mean(self):
+        return self.m.copy()
+
+    def cov(self):
+        '''the weighted covariance matrix C / W (symmetrised)'''
+        if self.W == 0:
+            raise ValueError('nothing accumulated')
+        return 0.5 * (self.C + self.C.T) / float(self.W)
+
+    def constant(self):
+        '''mask of the scalars whose variance is 0'''
+        return np.diag(self.C) == 0.0
+
+    def inv_sd(self):
+        '''1 / sd per scalar, 0 for a constant one'''
+        var = np.diag(self.cov())
+        out = np.zeros(len(self.names))
+        live = ~self.constant()
+        out[live] = 1.0 / np.sqrt(var[live])
+        return out
+
+    def corr(self):
+        '''the correlation matrix of the scalars; rows and columns of constant ones are 0'''
+        isd = self.inv_sd()
+        return self.cov() * isd[:, None] * isd[None, :]
+
+    def factor(self):
+        '''(F, rank, eigenvalues): F [n, rank] with F F' the pseudo-inverse of the covariance of the
+        non-constant scalars (rows of constant ones are 0); the eigenvalues of that covariance in descending
+        order, of which those below 1e-12 times the largest -- eigenvalues[rank:] -- are dropped, never
+        regularised.'''
+        n = len(self.names)
+        live = np.flatnonzero(~self.constant())
+        if live.size == 0:
+            return np.zeros((n, 0)), 0, np.zeros(0)
+        lam, V = np.linalg.eigh(self.cov()[np.ix_(live, live)])
+        lam, V = lam[::-1], V[:, ::-1]
+        rank = int(np.count_nonzero(lam >= 1e-12 * lam[0])) if lam[0] > 0 else 0
+        F = np.zeros((n, rank))
+        F[live] = V[:, :rank] / np.sqrt(lam[:rank])
+        return F, rank, lam
+
+
+def finalize_factor(moments):
+    '''(F, rank, eigenvalues, isd) of ParamMoments for ps_sens_finalize, F and isd contiguous float64.
+    ValueError when nothing varies or members < rank + 2: a regression through that few members fits exactly
+    and would report explained == 1 everywhere.'''
+    if moments.W == 0:
+        raise ValueError('nothing accumulated')
+    F, rank, lam = moments.factor()
+    if rank < 1:
+        raise ValueError('no sensitivity parameter varies over the %d members' % moments.members)
+    if moments.members < rank + 2:
+        raise ValueError('%d members for %d independent parameters: a linear fit through fewer than rank + 2 '
+                         'members is exact and explains everything' % (moments.members, rank))
+    return L.f64(F), rank, lam, L.f64(moments.inv_sd())
+
+
+class SensitivityMaps():
+    '''Which parameter drives the posterior spread where: per cell of `pop_model`'s days the weighted
+    covariance between the value SpreadSummary adds and each of `params` (names from mcmc.MODEL_BLOCK, default
+    all 15) over the members added, on the device (ps_sens_*, csrc/ps_sens.hip), next to the mean and the
+    variance (the same bits as a SpreadSummary fed alongside).  `add(theta, weight)` takes the member's full
+    model block and picks the columns.  After `finalize()`: `explained(day)`, the share of the cell's
+    posterior variance that a linear dependence on the parameters explains -- a linear, global,
+    posterior-weighted measure, not a Sobol index, and 1 by construction when members <= rank + 1, which
+    `finalize` therefore refuses -- and `dominant(day)`, the parameter with the largest |correlation|.'''
+
+    def __init__(self, pop_model, params=None, days=None):
+        self._h = L._VP()
+        days = list(range(len(pop_model.days)) if days is None else days)
+        if not days or min(days) < 0:
+            raise ValueError('days must be a non-empty list of model days >= 0')
+        self._setup(pop_model, params, days, None)
+
+    @classmethod
+    def for_projection(cls, projection, params=None):
+        '''Sensitivity maps of the outputs of `projection` (a Projection or a ReleaseSites), one slot per
+        output: `add(theta, weight)` accumulates the outputs of its last `apply()`, and the accessors take the
+        output index where the day-based maps take a day.'''
+        self = cls.__new__(cls)
+        self._h = L._VP()
+        self._setup(projection.pm, params, list(range(projection.nout)), projection)
+        return self
+
+    def _setup(self, pop_model, params, days, projection):
+        self.params = check_sens_params(params)
+        known = [m[0] for m in mcmc.MODEL_BLOCK]
+        self._cols = [known.index(n) for n in self.params]
+        self._nblock = len(known)
+        self.moments = ParamMoments(self.params)
+        self._lib = L.load()
+        self.pm = pop_model
+        self.days = days
+        self.N = 2 * int(pop_model.rad_res) + 1
+        self.device = L.default_device() if pop_model.device is None else int(pop_model.device)
+        self._proj = projection
+        keys = days if projection is None else projection.live
+        self._slot = {d: i for i, d in enumerate(keys)}
+        self._n = len(self._slot)
+        pitch = (self.N * self.N + 63) // 64 * 64
+        self.nbytes = self._n * pitch * ((len(self.params) + 3) * 8 + 1)
+        self.rank = None
+        self.eigenvalues = None
+        L.check(self._lib.ps_sens_create(self.device, self.N, self._n, len(self.params), C.byref(self._h)))
+        if projection is None:
+            self._kind, self._idx, self._delta = _day_slots(self.days)
+
+    def add(self, theta, weight=1):
+        '''Accumulate the last evaluation of the model (on a projection or a plan: its last apply), whose
+        model block is `theta`, with integer weight >= 1; enqueued, no host synchronisation.'''
+        t = np.array(theta, dtype=np.float64).ravel()
+        if t.size != self._nblock:
+            raise ValueError('theta has %d entries, the model block %d' % (t.size, self._nblock))
+        if self._proj is None:
+            _check_evaluated(self.pm, self.days, 'sensitivity maps')
+        state = self.moments._state()
+        e = L.f64(self.moments.update(t[self._cols], weight))
+        w = int(weight)
+        try:
+            if self._proj is not None:
+                L.check(getattr(self._lib, 'ps_sens_add_' + self._proj.fields_kind)(
+                    self._h, self._proj._h, e.size, L.p_f64(e), w))
+            else:
+                stat, post = _day_scales(self.pm, self.days)
+                L.check(self._lib.ps_sens_add(self._h, self.pm.solver._h, self._n, L.p_i32(self._kind),
+                                              L.p_i32(self._idx), L.p_f64(stat), L.p_f64(post), L.p_i32(self._delta),
+                                              NEGVAL, e.size, L.p_f64(e), w))
+        except Exception:
+            self.moments._restore(state)       # a refused add is added nowhere
+            raise
+        self.rank = None
+
+    def merge(self, other):
+        '''self += other (same device, domain, days and parameters)'''
+        if list(other.days) != self.days or other._slot != self._slot or other.params != self.params:
+            raise ValueError('sensitivity maps over different days or parameters')
+        state = self.moments._state()
+        dtheta = L.f64(self.moments.merge(other.moments))
+        try:
+            L.check(self._lib.ps_sens_merge(self._h, other._h, dtheta.size, L.p_f64(dtheta)))
+        except Exception:
+            self.moments._restore(state)
+            raise
+        self.rank = None
+
+    def reset(self):
+        L.check(self._lib.ps_sens_reset(self._h))
+        self.moments.reset()
+        self.rank = None
+
+    def _info(self):
+        w, m = C.c_double(), C.c_int64()
+        L.check(self._lib.ps_sens_info(self._h, C.byref(w), C.byref(m)))
+        return w.value, m.value
+
+    @property
+    def total_weight(self):
+        return self._info()[0]
+
+    @property
+    def members(self):
+        return self._info()[1]
+
+    def finalize(self):
+        '''Compute `explained` and `dominant` from the members so far -> (rank, dropped eigenvalues).
+        ValueError when nothing varies or members < rank + 2: a regression through that few members fits
+        exactly and would report explained == 1 everywhere; the correlation maps stay available.'''
+        F, rank, lam, isd = finalize_factor(self.moments)
+        L.check(self._lib.ps_sens_finalize(self._h, len(self.params), rank, L.p_f64(F), L.p_f64(isd)))
+        self.rank, self.eigenvalues = rank, lam
+        self.F, self.isd = F, isd
+        return rank, lam[rank:]
+
+    def _fetch(self, day, what):
+        if day not in self._slot:
+            if self._proj is not None and day in self.days:      # an output without weight
+                return np.full((self.N, self.N), -1.0 if what == 3 else 0.0)
+            raise ValueError('day %r is not in the sensitivity maps %s' % (day, self.days))
+        return self.fetch_slot(self._slot[day], what)
+
+    def fetch_slot(self, slot, what):
+        '''raw access by slot index (0 mean, 1 variance, 2 explained, 3 dominant, 16 + i covariance)'''
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        L.check(self._lib.ps_sens_fetch(self._h, int(slot), int(what), L.p_f64(out)))
+        return out
+
+    def _i(self, name):
+        if name not in self.params:
+            raise ValueError('parameter %r is not among %r' % (name, self.params))
+        return self.params.index(name)
+
+    def mean(self, day):
+        return self._fetch(day, 0)
+
+    def variance(self, day):
+        return self._fetch(day, 1)
+
+    def covariance(self, day, name):
+        '''posterior covariance of the cell's value with parameter `name`'''
+        return self._fetch(day, 16 + self._i(name))
+
+    def correlation(self, day, name):
+        '''covariance / sqrt(variance of the cell x variance of the parameter), 0 where either is 0'''
+        i = self._i(name)
+        cov, var = self._fetch(day, 16 + i), self.variance(day)
+        vt = self.moments.cov()[i, i] if not self.moments.constant()[i] else 0.0
+        den = np.sqrt(var * vt)
+        out = np.zeros_like(cov)
+        np.divide(cov, den, out=out, where=den > 0)
+        return out
+
+    def explained(self, day):
+        '''share of the cell's posterior variance explained by a linear dependence on the parameters'''
+        return self._fetch(day, 2)
+
+    def dominant(self, day):
+        '''int8 index into `params` of the parameter with the largest |correlation|, -1 where nothing varies'''
+        return self._fetch(day, 3).astype(np.int8)
+
+    def describe(self):
+        '''the parameter block of a result file'''
+        mo = self.moments
+        out = {'params': list(self.params), 'members': int(mo.members), 'total_weight': int(mo.W)}
+        if mo.W:
+            _F, rank, lam = mo.factor()
+            out.update({'mean': mo.mean().tolist(), 'sd': np.sqrt(np.diag(mo.cov())).tolist(),
+                        'correlation': mo.corr().tolist(), 'rank': rank,
+                        'dropped_eigenvalues': lam[rank:].tolist()})
+        return out
+
+    def profile(self, enable=None):
+        '''HIP-event time of the accumulate launches: (total ms, launches); enable switches it'''
+        ms, n = C.c_double(), C.c_int64()
+        L.check(self._lib.ps_sens_prof(self._h, -1 if enable is None else int(bool(enable)), C.byref(ms),
+                                       C.byref(n)))
+        return ms.value, n.value
+
+    def close(self):
+        if self._h:
+            self._lib.ps_sens_destroy(self._h)
+            self._h = L._VP()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ------------------------------------------------------------------ traces
 def model_names():
     return [m[0] for m in mcmc.MODEL_BLOCK]
@@ -1241,18 +1607,19 @@ def observation_predictive(rates, locinfo, seed=0):
 
 
 # ------------------------------------------------------------------ result files
-def save_maps(outfile, maps, extra=None):
+def save_maps(outfile, maps, extra=None, signed=False):
     '''outfile.npz in the layout of Run.save_result (Run.py:490-516 of the reference), which
     Plot_Result.main reads.  maps: [(day label, [(suffix, N x N array), ...]), ...] -> per day and
     suffix the CSR triplet `{label}{suffix}_data/_ind/_indptr` of the array thresholded at 1e-8,
-    and `days` = the labels; extra: {key: array} written as given.  The directory is created if needed.'''
+    and `days` = the labels; extra: {key: array} written as given.  signed: keep the entries with
+    |value| >= 1e-8, for maps that take either sign.  The directory is created if needed.'''
     from scipy import sparse
     out = dict(extra or {})
     labels = []
     for label, day_maps in maps:
         labels.append(label)
         for suffix, m in day_maps:
-            csr = sparse.csr_matrix(np.where(m >= NEGVAL, m, 0.0))
+            csr = sparse.csr_matrix(np.where((np.abs(m) if signed else m) >= NEGVAL, m, 0.0))
             out['%s%s_data' % (label, suffix)] = csr.data
             out['%s%s_ind' % (label, suffix)] = csr.indices
             out['%s%s_indptr' % (label, suffix)] = csr.indptr
@@ -1274,6 +1641,29 @@ def params_dict(params):
     return pdict
 
 
+def save_sensitivity(outfile, sens, keys, labels):
+    '''outfile.npz of one SensitivityMaps through save_maps (keys: its days or output indices, labels: theirs in
+    the file), finalized here if it can be -> its block for the json (SensitivityMaps.describe, `finalized` and,
+    where finalize refused, `reason`)'''
+    block = sens.describe()
+    try:
+        if sens.rank is None:
+            sens.finalize()
+        block['finalized'] = True
+    except ValueError as e:
+        block['finalized'] = False
+        block['reason'] = str(e)
+    maps, extra = [], {}
+    for k, label in zip(keys, labels):
+        day_maps = [('_corr_%s' % n, sens.correlation(k, n)) for n in sens.params]
+        if block['finalized']:
+            day_maps.append(('_r2', sens.explained(k)))
+            extra['%s_dom' % label] = sens.dominant(k)
+        maps.append((label, day_maps))
+    save_maps(outfile, maps, extra, signed=True)
+    return block
+
+
 # ------------------------------------------------------------------ driver
 class PredictiveResult():
     '''What posterior_predictive returns: `summary` (a SpreadSummary, None without a device),
@@ -1283,12 +1673,15 @@ class PredictiveResult():
     device) and `quantiles` (the levels), else both None; with arrival thresholds `arrival` (ArrivalMaps,
     None without a device) and `arrival_levels`, else both None; `emergence` / `exposure`: ProjectedMaps of the
     emergence and cumulative-exposure projections, None where not asked for; `sites`: ProjectedMaps of the
-    release plan (with `plan` and, with arrival thresholds, `arrival`), None where not asked for.'''
+    release plan (with `plan` and, with arrival thresholds, `arrival`), None where not asked for;
+    `sensitivity`: SensitivityMaps over the summary's days, None where not asked for (the projections and the
+    plan then carry one of their own).'''
 
     def __init__(self, summary, rows, evaluations, failed, seconds, runs, observations, provenance, days,
                  histogram=None, quantiles=None, arrival=None, arrival_levels=None, emergence=None, exposure=None,
-                 sites=None):
+                 sites=None, sensitivity=None):
         self.summary = summary
+        self.sensitivity = sensitivity
         self.emergence = emergence
         self.exposure = exposure
         self.sites = sites
@@ -1323,6 +1716,13 @@ class PredictiveResult():
         the dense `arrival{k}_{tag}`, `arrival{k}_cells` and `arrival_weights` of the plan, as in the main file;
         under `predictive.sites` of the json the plan (sites in metres and cells, lags, days), the thresholds,
         the levels and with arrival maps their thresholds, levels, cell area and the reached area per threshold.
+        Sensitivity maps go into outfile_sens.npz (those of a projection or a plan into outfile_NAME_sens.npz):
+        per day `{day}_corr_{name}_*` signed CSR triplets (|value| >= 1e-8) of the correlation with every
+        parameter and, once finalized, `{day}_r2_*` of the explained share and dense int8 `{day}_dom` (index
+        into the parameters, -1: nothing varies; dense because the CSR writer drops index 0); under
+        `predictive.sensitivity` (`predictive.NAME.sensitivity`) of the json the parameter names, their
+        posterior means, sds and correlation matrix, rank and dropped eigenvalues, members and weight, and
+        where finalize refused -- too few members -- the reason, the correlations alone being saved.
         -> (npz path, json path)'''
         s = self.summary
         if s is None:
@@ -1363,6 +1763,9 @@ class PredictiveResult():
                                              'days': list(A.days), 'cell_area': A.cell_area,
                                              'reached_area': [A.reached_area(k, a_levels)
                                                               for k in range(len(A.thresholds))]}
+        if self.sensitivity is not None:
+            labels = [s.pm.days[d] if d < len(s.pm.days) else d for d in s.days]
+            meta['predictive']['sensitivity'] = save_sensitivity('%s_sens' % outfile, self.sensitivity, s.days, labels)
         for name, pr in (('emergence', self.emergence), ('exposure', self.exposure), ('sites', self.sites)):
             if pr is None:
                 continue
@@ -1396,17 +1799,22 @@ class PredictiveResult():
                 meta['predictive'][name]['arrival'] = {
                     'thresholds': list(pa.thresholds), 'levels': pa_levels, 'cell_area': pa.cell_area,
                     'reached_area': [pa.reached_area(k, pa_levels) for k in range(len(pa.thresholds))]}
+            if pr.sensitivity is not None:
+                meta['predictive'][name]['sensitivity'] = save_sensitivity(
+                    '%s_%s_sens' % (outfile, name), pr.sensitivity, list(range(len(pr.labels))), pr.labels)
         with open(str(outfile) + '.json', 'w') as fobj:
             json.dump(meta, fobj, default=str)
         return str(outfile) + '.npz', str(outfile) + '.json'
 
 
 def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, locinfo, histogram=None,
-                   arrival=None, projected=(), plan=None):
+                   arrival=None, projected=(), plan=None, sens=None):
     '''one chain: evaluate every run, add it to the summary (and the histogram, the arrival maps; projected:
     (Projection, ProjectedMaps) pairs, applied and then added; plan: a (ReleaseSites, ProjectedMaps) pair, the
     models of its later release days evaluated with the base model -- a member for which any of them fails is
-    a failed member and is added nowhere -- applied and added last) -> (expected per run or None, failed)'''
+    a failed member and is added nowhere -- applied and added last; sens: the chain's SensitivityMaps, and
+    every ProjectedMaps' own, fed the run's theta after the summary beside it) -> (expected per run or None,
+    failed)'''
     expected = []
     failed = 0
     for first, length in run_list:
@@ -1432,6 +1840,8 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
             expected.append(None)
             continue
         summary.add(length)
+        if sens is not None:
+            sens.add(theta, length)
         if histogram is not None:
             histogram.add(length)
         if arrival is not None:
@@ -1439,11 +1849,16 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
         for proj, maps in projected:
             proj.apply()
             maps.summary.add(length)
+            if maps.sensitivity is not None:
+                maps.sensitivity.add(theta, length)
             if maps.histogram is not None:
                 maps.histogram.add(length)
         if plan is not None:
             plan[0].apply()
-            for acc in (plan[1].summary, plan[1].histogram, plan[1].arrival):
+            plan[1].summary.add(length)
+            if plan[1].sensitivity is not None:
+                plan[1].sensitivity.add(theta, length)
+            for acc in (plan[1].histogram, plan[1].arrival):
                 if acc is not None:
                     acc.add(length)
         expected.append(mcmc.expected_observations(pm, locinfo) if want_obs else True)
@@ -1452,7 +1867,8 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
 
 def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, thresholds=(), locinfo=None,
                          cell_area=None, seed=0, evaluate=None, quantiles=None, bins=DEFAULT_BINS, edges=None,
-                         arrival=None, arrival_levels=(0.05, 0.5, 0.95), emergence=None, exposure=None, sites=None):
+                         arrival=None, arrival_levels=(0.05, 0.5, 0.95), emergence=None, exposure=None, sites=None,
+                         sensitivity=None):
     '''Posterior predictive spread of one or more chains (`Sampler.save` files or (trace, names)
     pairs).  Burn and thin apply per chain; consecutive rows with identical model parameters are one
     evaluation weighted by the run's length.  pop_model: one PopModel or a list -- with several, one
@@ -1474,8 +1890,12 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     with every member, applies the plan and adds its outputs, with the same weights, to a
     SpreadSummary.for_projection (same thresholds), with quantiles a SpreadHistogram.for_projection (same
     edges) and with arrival an ArrivalMaps.for_projection (same thresholds), merged in chain order into `sites`
-    (ProjectedMaps with `plan` and `arrival`).'''
+    (ProjectedMaps with `plan` and `arrival`).  sensitivity: True (all 15 model parameters) or names from
+    mcmc.MODEL_BLOCK (check_sens_params); each chain then also fills a SensitivityMaps over the summary's days
+    with every run's theta and length, after the summary, merged in chain order into `sensitivity`, and every
+    projection and plan asked for gets a SensitivityMaps.for_projection of its own, fed after its summary.'''
     t0 = time.perf_counter()
+    s_names = check_sens_params(sensitivity) if sensitivity is not None and sensitivity is not False else None
     levels = (check_levels(quantiles) if quantiles is not None else []) or None
     if levels:
         bin_edges(bins, edges)        # a bad edge definition fails before any evaluation
@@ -1520,6 +1940,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     summaries = [None] * nch
     histograms = [None] * nch
     arrivals = [None] * nch
+    senses = [None] * nch
     projected = [[] for _ in range(nch)]       # per chain (Projection, ProjectedMaps) of every plan
     site_maps = [None] * nch                   # per chain (ReleaseSites, ProjectedMaps)
     late = {}                                  # per model the models of the plan's later release days
@@ -1537,6 +1958,8 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                 histograms[ci] = hist
                 arr = ArrivalMaps(pm, a_thr, summ.days) if evaluate is None and a_thr else None
                 arrivals[ci] = arr
+                sens = SensitivityMaps(pm, s_names, summ.days) if evaluate is None and s_names else None
+                senses[ci] = sens
                 if evaluate is None:
                     for _name, W, in_days, labels in plans:
                         proj = Projection(pm, W, in_days)
@@ -1545,6 +1968,8 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                         projected[ci][-1] = (proj, maps)
                         if levels:
                             maps.histogram = SpreadHistogram.for_projection(proj, bins, edges)
+                        if s_names:
+                            maps.sensitivity = SensitivityMaps.for_projection(proj, s_names)
                     if site_plan is not None:
                         if p not in late:
                             late[p] = lagged_models(pm, site_plan[2])
@@ -1557,8 +1982,10 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                             maps.histogram = SpreadHistogram.for_projection(rs, bins, edges)
                         if a_thr:
                             maps.arrival = ArrivalMaps.for_projection(rs, a_thr)
+                        if s_names:
+                            maps.sensitivity = SensitivityMaps.for_projection(rs, s_names)
                 results[ci] = _evaluate_runs(pm, summ, rows, rl, mcols, evaluate, want_obs, locinfo, hist, arr,
-                                             projected[ci], site_maps[ci])
+                                             projected[ci], site_maps[ci], sens)
         except BaseException as e:       # re-raised in the caller's thread
             errs.append((p, e))
 
@@ -1573,7 +2000,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         pms = pms[:1]
         work(0)
     if errs:
-        for s in summaries + histograms + arrivals + [x for pl in projected for pair in pl for x in pair] \
+        for s in summaries + histograms + arrivals + senses + [x for pl in projected for pair in pl for x in pair] \
                 + [x for pair in site_maps if pair is not None for x in pair] \
                 + [m for made in late.values() for m in made.values()]:
             if s is not None:
@@ -1582,6 +2009,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     summary = None
     histogram = None
     arrival_maps = None
+    sens_maps = None
     if evaluate is None:
         summary = summaries[0]
         for s in summaries[1:]:
@@ -1596,6 +2024,11 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
             arrival_maps = arrivals[0]
             for a in arrivals[1:]:
                 arrival_maps.merge(a)
+                a.close()
+        if s_names:
+            sens_maps = senses[0]
+            for a in senses[1:]:
+                sens_maps.merge(a)
                 a.close()
     merged = {}
     for k, plan in enumerate(plans if evaluate is None else []):
@@ -1638,7 +2071,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                            time.perf_counter() - t0, run_rec, observations, prov,
                            None if summary is None else summary.days, histogram, levels, arrival_maps,
                            a_levels if a_thr else None, merged.get('emergence'), merged.get('exposure'),
-                           merged_sites)
+                           merged_sites, sens_maps)
     if cell_area is not None:
         res.cell_area = float(cell_area)
     return res

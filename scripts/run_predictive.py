@@ -8,7 +8,10 @@ probability and arrival-day quantile maps and the reached area per day (--arriva
 into the observation days d1,d2,...) and of the cumulative exposure up to the listed model days, saved as
 PREFIX_emergence.npz / PREFIX_exposure.npz; with --sites also the posterior maps of a release plan -- several
 release sites, some released days later -- saved as PREFIX_sites.npz (with --arrival including its arrival maps
-and, in the json, its reached-area curve).  Kalbar wind and
+and, in the json, its reached-area curve); with --sensitivity also the posterior sensitivity maps -- per day and
+cell the correlation of the population with every listed model parameter (default: all 15), the share of the
+posterior variance a linear dependence on them explains and the dominant parameter -- saved as PREFIX_sens.npz
+(and PREFIX_NAME_sens.npz for every projection and plan asked for).  Kalbar wind and
 LocInfo as scripts/run_mcmc.py loads them; --synthetic uses the synthetic Kalbar-like observations.
 Without --chain a short chain is sampled first (--samples) and saved next to --out.
 
@@ -16,7 +19,7 @@ Without --chain a short chain is sampled first (--samples) and saved next to --o
         [--mode auto] [--thresholds 1,10] [--out PREFIX] [--synthetic] [--chains-parallel]
         [--quantiles 0.05,0.5,0.95] [--bins 1e-8,1e6,16] [--arrival 1,10] [--arrival-levels 0.05,0.5,0.95]
         [--emergence C[:d1,d2,...]] [--exposure d1,d2,...]
-        [--sites 'E,N,AMOUNT[,LAG];...'] [--sites-days d1,d2,...]
+        [--sites 'E,N,AMOUNT[,LAG];...'] [--sites-days d1,d2,...] [--sensitivity [name,name,...]]
 """
 import argparse
 import json
@@ -56,13 +59,19 @@ def main():
                                                 'first release (default: off)')
     ap.add_argument('--sites-days', default='', help='output model days d1,d2,... of the release plan '
                                                      '(default: all, at most 32)')
+    ap.add_argument('--sensitivity', nargs='?', const='', default=None,
+                    help='posterior sensitivity maps to the listed model parameters, e.g. sig_x,sig_y,mu_r '
+                         '(no list: all 15; default: off)')
     args = ap.parse_args()
     warnings.simplefilter('ignore', RuntimeWarning)
     from parasitoids_amd import ParasitoidModel as PM
     from parasitoids_amd import mcmc
     from parasitoids_amd.pop_model import PopModel
-    from parasitoids_amd.predictive import (bin_edges, check_arrival_thresholds, check_levels, emergence_plan,
-                                            exposure_plan, posterior_predictive, sites_plan)
+    from parasitoids_amd.predictive import (bin_edges, check_arrival_thresholds, check_levels, check_sens_params,
+                                            emergence_plan, exposure_plan, posterior_predictive, sites_plan)
+    sens = None
+    if args.sensitivity is not None:     # bad --sensitivity names fail before any work
+        sens = check_sens_params([n.strip() for n in args.sensitivity.split(',') if n.strip()] or None)
     levels = check_levels([float(q) for q in args.quantiles.split(',') if q.strip()])
     bins = tuple(float(b) for b in args.bins.split(','))
     bin_edges(bins)                      # a bad --bins fails before any work
@@ -116,11 +125,12 @@ def main():
     res = posterior_predictive(pms if len(pms) > 1 else pm, chains, burn=args.burn, thin=args.thin,
                                thresholds=thr, locinfo=li, cell_area=cell_area, seed=args.seed,
                                quantiles=levels or None, bins=bins, arrival=arrival or None, arrival_levels=a_levels,
-                               emergence=emergence, exposure=exposure, sites=sites)
+                               emergence=emergence, exposure=exposure, sites=sites, sensitivity=sens)
     dt = time.perf_counter() - t0
     # accumulate-kernel time: the same members once more with HIP events around every add
-    from parasitoids_amd.predictive import (ArrivalMaps, Projection, ReleaseSites, SpreadHistogram, SpreadSummary,
-                                            load_chain, runs)
+    from parasitoids_amd.predictive import (ArrivalMaps, Projection, ReleaseSites, SensitivityMaps, SpreadHistogram,
+                                            SpreadSummary, load_chain, runs)
+    X = SensitivityMaps(pm, sens) if sens else None
     RS = ReleaseSites.with_lagged_models(pm, sites['sites'], sites['days']) if sites else None
     projections = [Projection(pm, W, in_days) for W, in_days, _labels in plans]
     H = SpreadHistogram(pm, None, bins) if levels else None
@@ -131,6 +141,8 @@ def main():
             H.profile(True)
         if A is not None:
             A.profile(True)
+        if X is not None:
+            X.profile(True)
         for P in projections:
             P.profile(True)
         if RS is not None:
@@ -148,6 +160,8 @@ def main():
                 except Exception:
                     continue
                 S.add(length)
+                if X is not None:
+                    X.add(rows[first, cols], length)
                 if H is not None:
                     H.add(length)
                 if A is not None:
@@ -166,6 +180,10 @@ def main():
         a_ms, a_launches = A.profile()[:2]
         A.close()
         res.arrival.profile(True)       # every map launch of the save
+    if X is not None:
+        x_ms, x_launches = X.profile()
+        x_bytes = X.nbytes
+        X.close()
     p_ms = sum(P.profile()[0] for P in projections)
     p_launches = sum(P.profile()[1] for P in projections)
     p_bytes = sum(P.nbytes for P in projections)
@@ -197,6 +215,16 @@ def main():
         out['arrival_add_ms_per_member'] = round(a_ms / max(a_launches, 1), 4)
         out['arrival_maps_ms_total'] = round(res.arrival.profile()[2], 3)
         out['arrival_bytes'] = res.arrival.nbytes
+    if sens:
+        x_per = x_ms / max(x_launches, 1)
+        out['sensitivity_add_ms_per_member'] = round(x_per, 4)
+        out['sensitivity_launches_timed'] = x_launches
+        # nominal: every pair of cells updated; pairs the member does not move skip their co-moments
+        out['sensitivity_add_nominal_GBps'] = round((8 + 32 + 16 * len(sens)) * ncell * nday / (x_per * 1e-3) / 1e9, 1) \
+            if x_per > 0 else None
+        out['sensitivity_bytes'] = x_bytes
+        out['sensitivity_params'] = len(sens)
+        out['outputs'] += ['%s_sens.npz' % args.out]
     if projections:
         out['project_ms_per_member'] = round(p_ms / max(n, 1), 4)       # every projection's apply of one member
         out['project_launches_timed'] = p_launches
@@ -215,6 +243,8 @@ def main():
         res.histogram.close()
     if res.arrival is not None:
         res.arrival.close()
+    if res.sensitivity is not None:
+        res.sensitivity.close()
     for pr in (res.emergence, res.exposure, res.sites):
         if pr is not None:
             pr.close()
