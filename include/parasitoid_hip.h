@@ -653,6 +653,49 @@ int ps_sens_reset(ps_sens* h);
 int ps_sens_prof(ps_sens* h, int enable, double* total_ms, int64_t* launches);
 void ps_sens_destroy(ps_sens* h);
 
+/* ---- paired contrast of two release plans (or two projections): A - B member by member ----
+ * (no reference counterpart.)  Both plans are driven by the same member, so the posterior of their
+ * difference -- its variance, P(A beats B) at a cell, P(A covers more than B) -- needs the pairing and cannot
+ * be rebuilt from the two plans' own maps.  The handle lives on one device and holds nslot slots of N x N
+ * cells (pitch as ps_summary): mean[slot], M2[slot] (fp64) of d = a - b, and uint32 counts
+ * cnt[slot][2 + 2 nthr]: plane 0 the weight of the members with d > 0, plane 1 with d < 0, plane 2 + 2k with
+ * a >= t_k && b < t_k (gain_k), plane 3 + 2k with b >= t_k && a < t_k (loss_k); and with nthr > 0 per member,
+ * in add order, one row uint32 [2][nthr][nslot]: the cells with a >= t_k, then those with b >= t_k, per slot
+ * -- the area each plan covers, paired -- with the member's weight (the rows grow by doubling, as ps_arrival's).
+ * 0 <= nthr <= 4, the thresholds finite, > 0 and strictly increasing; nslot >= 1.  The footprint,
+ * (16 + 4 (2 + 2 nthr)) * nslot * pitch bytes and the first rows, is checked against the free device memory
+ * first: PS_ERR_OOM before anything is allocated.  Host side: the total weight W (< 2^32) and the member
+ * count.  Every mean, M2 and count cell has one writer; the rows are integer sums (ballot popcounts kept in
+ * a register, summed over the block's waves in LDS, one integer atomic per block and counter): no
+ * floating-point atomics, and no order of adds or merges changes a bit of a count. */
+typedef struct ps_contrast ps_contrast;
+int ps_contrast_create(int device, int N, int nslot, int nthr, const double* thr, ps_contrast** out);
+/* One member with weight >= 1: slot e takes a = A.Y_e and b = B.Y_e of the two sources' current outputs.  Per
+ * cell d = a - b (one rounded subtraction), then with W' = W + w the statements of ps_summary_add on d:
+ *   d == mean: nothing stored; else mean += (d - mean) w / W',  M2 += w (d - mean_before) (d - mean)
+ * and the counts above.  On the handle's stream behind both sources' last operation; their next apply waits
+ * for the read.  PS_ERR_BAD_ARG (nothing enqueued): a == b, a source whose device, N or number of outputs is
+ * not the handle's, weight 0 or a total weight past 2^32 - 1.  PS_ERR_STATE: a source without finished
+ * fields (never applied, or a release plan mid-pass over its groups). */
+int ps_contrast_add_sites(ps_contrast* h, ps_sites* a, ps_sites* b, uint32_t weight);
+int ps_contrast_add_project(ps_contrast* h, ps_project* a, ps_project* b, uint32_t weight);
+/* dst += src (mean and M2 as ps_summary_merge, counts added, src's rows appended after dst's), same device,
+ * N, slots and thresholds; src stays as it is.  Into an empty dst it is a device copy, bit for bit. */
+int ps_contrast_merge(ps_contrast* dst, ps_contrast* src);
+int ps_contrast_info(ps_contrast* h, double* total_weight, int64_t* members);
+/* one slot to the host (synchronises): what 0 mean, 1 variance M2 / W, 2 P(d > 0), 3 P(d < 0), 4 + 2k P(gain_k),
+ * 5 + 2k P(loss_k) (count / W).  PS_ERR_STATE at W = 0. */
+int ps_contrast_fetch(ps_contrast* h, int slot, int what, double* out /* N*N */);
+/* the raw count plane which = what - 2 of ps_contrast_fetch */
+int ps_contrast_fetch_counts(ps_contrast* h, int slot, int which, uint32_t* out /* N*N */);
+/* the rows of the members first .. first + count - 1 in add order and their weights (either may be null) */
+int ps_contrast_fetch_coverage(ps_contrast* h, int64_t first, int64_t count,
+                               uint32_t* cells /* [count][2][nthr][nslot] */, uint32_t* weights);
+int ps_contrast_reset(ps_contrast* h);
+/* measurement: HIP-event timing of the add launches, as ps_summary_prof */
+int ps_contrast_prof(ps_contrast* h, int enable, double* total_ms, int64_t* launches);
+void ps_contrast_destroy(ps_contrast* h);
+
 #ifdef __cplusplus
 }
 #endif

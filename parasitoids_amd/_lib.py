@@ -192,6 +192,18 @@ SIGNATURES = {
     'ps_sens_reset': (C.c_int, [_VP]),
     'ps_sens_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P]),
     'ps_sens_destroy': (None, [_VP]),
+    'ps_contrast_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _F64P, C.POINTER(_VP)]),
+    'ps_contrast_add_sites': (C.c_int, [_VP, _VP, _VP, C.c_uint32]),
+    'ps_contrast_add_project': (C.c_int, [_VP, _VP, _VP, C.c_uint32]),
+    'ps_contrast_merge': (C.c_int, [_VP, _VP]),
+    'ps_contrast_info': (C.c_int, [_VP, _F64P, _I64P]),
+    'ps_contrast_fetch': (C.c_int, [_VP, C.c_int, C.c_int, _F64P]),
+    'ps_contrast_fetch_counts': (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(C.c_uint32)]),
+    'ps_contrast_fetch_coverage': (C.c_int, [_VP, C.c_int64, C.c_int64, C.POINTER(C.c_uint32),
+                                             C.POINTER(C.c_uint32)]),
+    'ps_contrast_reset': (C.c_int, [_VP]),
+    'ps_contrast_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P]),
+    'ps_contrast_destroy': (None, [_VP]),
 }
 
 _lib = None

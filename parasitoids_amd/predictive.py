@@ -1165,6 +1165,245 @@ class ReleaseSites():
             pass
 
 
+# ------------------------------------------------------------------ paired contrast of two plans
+MAX_CONTRAST_THRESHOLDS = 4
+
+
+def check_contrast_thresholds(thresholds):
+    '''a contrast's thresholds as a list of floats: 0..4 of them, each finite and > 0, strictly increasing;
+    ValueError otherwise'''
+    try:
+        thr = [float(t) for t in thresholds]
+    except (TypeError, ValueError):
+        raise ValueError('contrast thresholds must be numbers, got %r' % (thresholds,))
+    if len(thr) > MAX_CONTRAST_THRESHOLDS:
+        raise ValueError('%d contrast thresholds; at most %d are kept' % (len(thr), MAX_CONTRAST_THRESHOLDS))
+    if not all(np.isfinite(t) and t > 0 for t in thr):
+        raise ValueError('every contrast threshold must be finite and > 0: %r' % (thr,))
+    if any(b <= a for a, b in zip(thr, thr[1:])):
+        raise ValueError('contrast thresholds must be strictly increasing: %r' % (thr,))
+    return thr
+
+
+def coverage_difference(cells_a, cells_b, weights, cell_area, levels=(0.05, 0.5, 0.95)):
+    '''Per output the posterior of the difference of the areas two plans cover, from the paired per-member cell
+    counts cells_a, cells_b [members, nout] and the members' integer weights: [{'mean', 'quantiles',
+    'p_a_larger', 'p_b_larger'}, ...].  Areas in m^2 (cells x cell_area), signed A - B: the weighted mean (from
+    integers, as ArrivalMaps.reached_area), the weighted lower quantiles (weighted_lower_quantile) at `levels`,
+    and the weight of the members with a > b (b > a) over W.  ValueError at W = 0.'''
+    levels = check_levels(levels)
+    a = np.asarray(cells_a, dtype=np.int64)
+    b = np.asarray(cells_b, dtype=np.int64)
+    w = np.asarray(weights, dtype=np.int64).ravel()
+    if a.ndim != 2 or a.shape != b.shape or a.shape[0] != w.size:
+        raise ValueError('cell counts %r and %r with %d weights' % (a.shape, b.shape, w.size))
+    if w.size and w.min() < 0:
+        raise ValueError('weights must be >= 0')
+    W = int(w.sum())
+    if W == 0:
+        raise ValueError('nothing accumulated')
+    out = []
+    for s in range(a.shape[1]):
+        d = a[:, s] - b[:, s]
+        out.append({'mean': float(int((d * w).sum())) / float(W) * float(cell_area),
+                    'quantiles': [float(weighted_lower_quantile(d, w, p)) * float(cell_area) for p in levels],
+                    'p_a_larger': float(int(w[d > 0].sum())) / float(W),
+                    'p_b_larger': float(int(w[d < 0].sum())) / float(W)})
+    return out
+
+
+def contrast_plan(arg, sites_arg, pop_model=None):
+    '''posterior_predictive's compare= argument, dict(sites=[(east_m, north_m, amount[, lag_days]), ...]): plan B,
+    compared with the plan A of the sites= argument `sites_arg` on A's output days, as (sites, days, lags) of B
+    (sites_plan).  ValueError for a bad plan, for a compare= without sites=, or for output days of its own.'''
+    if not isinstance(arg, dict) or 'sites' not in arg or set(arg) - {'sites'}:
+        raise ValueError('compare must be dict(sites=[(east_m, north_m, amount[, lag_days]), ...]), got %r' % (arg,))
+    if sites_arg is None:
+        raise ValueError('compare= names plan B and needs plan A: give sites= too')
+    a_sites, a_days, _lags = sites_plan(sites_arg, pop_model)
+    return sites_plan(dict(sites=arg['sites'], days=a_days), pop_model)
+
+
+class PlanContrast():
+    '''The posterior of the difference of two plans, member by member, on the device: `a` and `b` are two
+    ReleaseSites or two Projection on the same device and domain with the same outputs (nout, live; of two
+    ReleaseSites also the same output days -- outputs are paired by index and labelled by A's days; of two
+    Projection the caller sees to it that output e means the same in both).
+    After both were applied to one member, `add(weight)` accumulates per output and cell d = a - b (one rounded
+    subtraction): its weighted mean and M2 by SpreadSummary's step, the weight of the members with d > 0 and
+    with d < 0, per threshold t_k (0..4, finite, > 0, strictly increasing) the weight of those with
+    a >= t_k > b (gain) and b >= t_k > a (loss), and per member the cells either plan covers at t_k on every
+    output -- the pairing the two plans' own maps have lost.  The accessors take the output index; outputs
+    kept off the device read as zeros.  Counts are integers: the order of adds and merges changes no bit.'''
+
+    def __init__(self, a, b, thresholds=()):
+        self._h = L._VP()
+        if a is b:
+            raise ValueError('a plan is compared with another one, not with itself')
+        if type(a) is not type(b) or not isinstance(a, (ReleaseSites, Projection)):
+            raise ValueError('two ReleaseSites or two Projection expected, got %s and %s'
+                             % (type(a).__name__, type(b).__name__))
+        if a.pm.device != b.pm.device:
+            raise ValueError('the plans\' models are on devices %r and %r' % (a.pm.device, b.pm.device))
+        for name in ('device', 'N', 'nout', 'live') + (('days',) if isinstance(a, ReleaseSites) else ()):
+            if getattr(a, name) != getattr(b, name):
+                raise ValueError('the plans differ in %s: %r and %r' % (name, getattr(a, name), getattr(b, name)))
+        self.thresholds = check_contrast_thresholds(thresholds)
+        self.a, self.b = a, b
+        self.pm = a.pm
+        self.N, self.device, self.nout, self.live = a.N, a.device, a.nout, list(a.live)
+        self.labels = list(getattr(a, 'days', range(a.nout)))
+        self.cell_area = (float(a.pm.rad_dist) / int(a.pm.rad_res)) ** 2
+        self._slot = {e: i for i, e in enumerate(self.live)}
+        self._lib = L.load()
+        pitch = (self.N * self.N + 63) // 64 * 64
+        self.nbytes = len(self.live) * pitch * (16 + 4 * (2 + 2 * len(self.thresholds)))   # moments and counts
+        thr = L.f64(self.thresholds if self.thresholds else [0.0])
+        L.check(self._lib.ps_contrast_create(self.device, self.N, len(self.live), len(self.thresholds), L.p_f64(thr),
+                                             C.byref(self._h)))
+
+    def add(self, weight=1):
+        '''Accumulate the last apply of both plans with integer weight >= 1 (on the handle's stream behind both;
+        no host synchronisation)'''
+        w = int(weight)
+        if w < 1:
+            raise ValueError('weight must be a positive integer')
+        L.check(getattr(self._lib, 'ps_contrast_add_' + self.a.fields_kind)(self._h, self.a._h, self.b._h, w))
+
+    def merge(self, other):
+        '''self += other (same device, domain, outputs and thresholds); other's members follow self's'''
+        if other.live != self.live or other.nout != self.nout or list(other.labels) != self.labels:
+            raise ValueError('contrasts over different outputs')
+        L.check(self._lib.ps_contrast_merge(self._h, other._h))
+
+    def reset(self):
+        L.check(self._lib.ps_contrast_reset(self._h))
+
+    def _info(self):
+        w, m = C.c_double(), C.c_int64()
+        L.check(self._lib.ps_contrast_info(self._h, C.byref(w), C.byref(m)))
+        return w.value, m.value
+
+    @property
+    def total_weight(self):
+        return self._info()[0]
+
+    @property
+    def members(self):
+        return self._info()[1]
+
+    def _e(self, e):
+        if not 0 <= int(e) < self.nout:
+            raise ValueError('output %r of %d' % (e, self.nout))
+        return int(e)
+
+    def _k(self, k):
+        if not 0 <= int(k) < len(self.thresholds):
+            raise ValueError('threshold %r of %d' % (k, len(self.thresholds)))
+        return int(k)
+
+    def _fetch(self, e, what):
+        e = self._e(e)
+        if e not in self._slot:
+            return np.zeros((self.N, self.N), dtype=np.float64)
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        L.check(self._lib.ps_contrast_fetch(self._h, self._slot[e], int(what), L.p_f64(out)))
+        return out
+
+    def mean(self, e):
+        '''[N, N] float64: the posterior mean of A - B on output e'''
+        return self._fetch(e, 0)
+
+    def variance(self, e):
+        return self._fetch(e, 1)
+
+    def sd(self, e):
+        return np.sqrt(self.variance(e))
+
+    def prob_positive(self, e):
+        '''P(A > B) per cell'''
+        return self._fetch(e, 2)
+
+    def prob_negative(self, e):
+        '''P(A < B) per cell'''
+        return self._fetch(e, 3)
+
+    def gain(self, e, k):
+        '''P(A >= thresholds[k] > B) per cell: plan A reaches the threshold where plan B does not'''
+        return self._fetch(e, 4 + 2 * self._k(k))
+
+    def loss(self, e, k):
+        '''P(B >= thresholds[k] > A) per cell'''
+        return self._fetch(e, 5 + 2 * self._k(k))
+
+    def counts(self, e, which):
+        '''[N, N] uint32: the raw count plane (0 d > 0, 1 d < 0, 2 + 2k gain_k, 3 + 2k loss_k) of output e'''
+        e = self._e(e)
+        if not 0 <= int(which) < 2 + 2 * len(self.thresholds):
+            raise ValueError('count plane %r of %d' % (which, 2 + 2 * len(self.thresholds)))
+        if e not in self._slot:
+            return np.zeros((self.N, self.N), dtype=np.uint32)
+        out = np.empty((self.N, self.N), dtype=np.uint32)
+        L.check(self._lib.ps_contrast_fetch_counts(self._h, self._slot[e], int(which),
+                                                   out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def _coverage(self):
+        m = self.members
+        cells = np.zeros((m, 2, len(self.thresholds), len(self.live)), dtype=np.uint32)
+        w = np.zeros(m, dtype=np.uint32)
+        u32 = C.POINTER(C.c_uint32)
+        L.check(self._lib.ps_contrast_fetch_coverage(self._h, 0, m, cells.ctypes.data_as(u32), w.ctypes.data_as(u32)))
+        return cells, w
+
+    @property
+    def weights(self):
+        '''[members] int64: the members' weights in add order'''
+        return self._coverage()[1].astype(np.int64)
+
+    def coverage(self, k):
+        '''(cells_a [members, nout] int64, cells_b, weights [members] int64): per member in add order the number
+        of cells where plan A (plan B) is >= thresholds[k] on every output'''
+        k = self._k(k)
+        cells, w = self._coverage()
+        out = np.zeros((2, cells.shape[0], self.nout), dtype=np.int64)
+        out[:, :, self.live] = cells[:, :, k, :].transpose(1, 0, 2)
+        return out[0], out[1], w.astype(np.int64)
+
+    def coverage_difference(self, k, levels=(0.05, 0.5, 0.95)):
+        '''Per output the posterior of the covered area of A minus that of B at thresholds[k]
+        (coverage_difference of the paired rows), each entry with its output `label`'''
+        ca, cb, w = self.coverage(k)
+        out = coverage_difference(ca, cb, w, self.cell_area, levels)
+        for label, rec in zip(self.labels, out):
+            rec['label'] = label
+        return out
+
+    def profile(self, enable=None):
+        '''HIP-event time of the add launches: (total ms, adds); enable switches it'''
+        ms, n = C.c_double(), C.c_int64()
+        L.check(self._lib.ps_contrast_prof(self._h, -1 if enable is None else int(bool(enable)), C.byref(ms),
+                                           C.byref(n)))
+        return ms.value, n.value
+
+    def close(self):
+        if self._h:
+            self._lib.ps_contrast_destroy(self._h)
+            self._h = L._VP()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ------------------------------------------------------------------ sensitivity
 MAX_SENS_PARAMS = 16       # ps_sens: the scalars of one handle
 
@@ -1675,12 +1914,15 @@ class PredictiveResult():
     emergence and cumulative-exposure projections, None where not asked for; `sites`: ProjectedMaps of the
     release plan (with `plan` and, with arrival thresholds, `arrival`), None where not asked for;
     `sensitivity`: SensitivityMaps over the summary's days, None where not asked for (the projections and the
-    plan then carry one of their own).'''
+    plan then carry one of their own); `contrast`: the PlanContrast of the release plan against the plan of
+    compare= and `compare_plan` that plan (ReleaseSites.describe()), both None where not asked for.'''
 
     def __init__(self, summary, rows, evaluations, failed, seconds, runs, observations, provenance, days,
                  histogram=None, quantiles=None, arrival=None, arrival_levels=None, emergence=None, exposure=None,
-                 sites=None, sensitivity=None):
+                 sites=None, sensitivity=None, contrast=None, compare_plan=None):
         self.summary = summary
+        self.contrast = contrast
+        self.compare_plan = compare_plan
         self.sensitivity = sensitivity
         self.emergence = emergence
         self.exposure = exposure
@@ -1723,6 +1965,11 @@ class PredictiveResult():
         `predictive.sensitivity` (`predictive.NAME.sensitivity`) of the json the parameter names, their
         posterior means, sds and correlation matrix, rank and dropped eigenvalues, members and weight, and
         where finalize refused -- too few members -- the reason, the correlations alone being saved.
+        A contrast of two plans goes into outfile_contrast.npz: per output day `{label}_*` signed CSR triplets
+        (|value| >= 1e-8) of the mean of A - B, `{label}_sd_*`, `{label}_ppos_*` / `{label}_pneg_*` (P(A > B),
+        P(A < B)), `{label}_pgain{k}_*` / `{label}_ploss{k}_*`, and `coverage{k}_a` / `coverage{k}_b` [members,
+        outputs] with `contrast_weights`; under `predictive.contrast` of the json plan B, the thresholds, labels,
+        members, weight, cell area, levels and per threshold the coverage difference.
         -> (npz path, json path)'''
         s = self.summary
         if s is None:
@@ -1802,19 +2049,40 @@ class PredictiveResult():
             if pr.sensitivity is not None:
                 meta['predictive'][name]['sensitivity'] = save_sensitivity(
                     '%s_%s_sens' % (outfile, name), pr.sensitivity, list(range(len(pr.labels))), pr.labels)
+        X = self.contrast
+        if X is not None:
+            x_levels = list(self.arrival_levels or (0.05, 0.5, 0.95))
+            nk = len(X.thresholds)
+            xmaps = []
+            for e, label in enumerate(X.labels):
+                out_maps = [('', X.mean(e)), ('_sd', X.sd(e)), ('_ppos', X.prob_positive(e)),
+                            ('_pneg', X.prob_negative(e))]
+                for k in range(nk):
+                    out_maps += [('_pgain%d' % k, X.gain(e, k)), ('_ploss%d' % k, X.loss(e, k))]
+                xmaps.append((label, out_maps))
+            xextra = {'contrast_weights': X.weights}
+            for k in range(nk):
+                xextra['coverage%d_a' % k], xextra['coverage%d_b' % k], _w = X.coverage(k)
+            save_maps('%s_contrast' % outfile, xmaps, xextra, signed=True)
+            meta['predictive']['contrast'] = {
+                'plan_b': self.compare_plan, 'thresholds': list(X.thresholds), 'labels': list(X.labels),
+                'members': X.members, 'total_weight': X.total_weight, 'cell_area': X.cell_area, 'levels': x_levels,
+                'coverage_difference': [X.coverage_difference(k, x_levels) for k in range(nk)]}
         with open(str(outfile) + '.json', 'w') as fobj:
             json.dump(meta, fobj, default=str)
         return str(outfile) + '.npz', str(outfile) + '.json'
 
 
 def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, locinfo, histogram=None,
-                   arrival=None, projected=(), plan=None, sens=None):
+                   arrival=None, projected=(), plan=None, sens=None, compare=None):
     '''one chain: evaluate every run, add it to the summary (and the histogram, the arrival maps; projected:
     (Projection, ProjectedMaps) pairs, applied and then added; plan: a (ReleaseSites, ProjectedMaps) pair, the
     models of its later release days evaluated with the base model -- a member for which any of them fails is
     a failed member and is added nowhere -- applied and added last; sens: the chain's SensitivityMaps, and
-    every ProjectedMaps' own, fed the run's theta after the summary beside it) -> (expected per run or None,
-    failed)'''
+    every ProjectedMaps' own, fed the run's theta after the summary beside it; compare: a (ReleaseSites of plan
+    B, PlanContrast, {lag: model} of both plans' later release days) triple -- every model of that union is
+    evaluated once per member, and after the plan's own adds plan B is applied and the contrast added)
+    -> (expected per run or None, failed)'''
     expected = []
     failed = 0
     for first, length in run_list:
@@ -1827,7 +2095,10 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
             continue
         try:
             pm.evaluate(*mcmc.model_args(theta), want_stats=False)
-            if plan is not None:
+            if compare is not None:
+                for lag, m in sorted(compare[2].items()):
+                    m.evaluate(*mcmc.model_args(theta), ndays=plan[0].days[-1] - lag + 1, want_stats=False)
+            elif plan is not None:
                 plan[0].evaluate_lagged(*mcmc.model_args(theta))
         except (AssertionError, ValueError):
             failed += 1
@@ -1861,6 +2132,9 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
             for acc in (plan[1].histogram, plan[1].arrival):
                 if acc is not None:
                     acc.add(length)
+        if compare is not None:
+            compare[0].apply()
+            compare[1].add(length)
         expected.append(mcmc.expected_observations(pm, locinfo) if want_obs else True)
     return expected, failed
 
@@ -1868,7 +2142,7 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
 def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, thresholds=(), locinfo=None,
                          cell_area=None, seed=0, evaluate=None, quantiles=None, bins=DEFAULT_BINS, edges=None,
                          arrival=None, arrival_levels=(0.05, 0.5, 0.95), emergence=None, exposure=None, sites=None,
-                         sensitivity=None):
+                         sensitivity=None, compare=None):
     '''Posterior predictive spread of one or more chains (`Sampler.save` files or (trace, names)
     pairs).  Burn and thin apply per chain; consecutive rows with identical model parameters are one
     evaluation weighted by the run's length.  pop_model: one PopModel or a list -- with several, one
@@ -1893,7 +2167,13 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     (ProjectedMaps with `plan` and `arrival`).  sensitivity: True (all 15 model parameters) or names from
     mcmc.MODEL_BLOCK (check_sens_params); each chain then also fills a SensitivityMaps over the summary's days
     with every run's theta and length, after the summary, merged in chain order into `sensitivity`, and every
-    projection and plan asked for gets a SensitivityMaps.for_projection of its own, fed after its summary.'''
+    projection and plan asked for gets a SensitivityMaps.for_projection of its own, fed after its summary.
+    compare: dict(sites=[...]) (contrast_plan), a second release plan B on the output days of sites= (plan A,
+    required); each chain then also builds a ReleaseSites for B and one PlanContrast(A, B, thresholds) -- the
+    thresholds then have to be finite, > 0 and strictly increasing -- the models of the later release days built
+    once per model for the union of both plans' lags and each evaluated once per member; after A's applies and
+    adds B is applied and the contrast added with the same weight, merged in chain order into `contrast`
+    (`compare_plan`: plan B).'''
     t0 = time.perf_counter()
     s_names = check_sens_params(sensitivity) if sensitivity is not None and sensitivity is not False else None
     levels = (check_levels(quantiles) if quantiles is not None else []) or None
@@ -1914,6 +2194,13 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         site_plan = sites_plan(sites, pm0)
         if pm0 is None:
             site_plan = None
+    cmp_plan = None
+    if compare is not None:           # and a bad plan B, or one without a plan A to compare with
+        pm0 = (pop_model[0] if pop_model else None) if isinstance(pop_model, (list, tuple)) else pop_model
+        cmp_plan = contrast_plan(compare, sites, pm0)
+        check_contrast_thresholds(thresholds)
+        if pm0 is None:
+            cmp_plan = None
     if isinstance(chains, (str, os.PathLike)) or (isinstance(chains, tuple) and len(chains) == 2
                                                    and not isinstance(chains[0], (str, os.PathLike, tuple))):
         chains = [chains]
@@ -1943,6 +2230,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     senses = [None] * nch
     projected = [[] for _ in range(nch)]       # per chain (Projection, ProjectedMaps) of every plan
     site_maps = [None] * nch                   # per chain (ReleaseSites, ProjectedMaps)
+    cmp_maps = [None] * nch                    # per chain (ReleaseSites of plan B, PlanContrast, the lagged models)
     late = {}                                  # per model the models of the plan's later release days
     results = [None] * nch
     errs = []
@@ -1972,7 +2260,8 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                             maps.sensitivity = SensitivityMaps.for_projection(proj, s_names)
                     if site_plan is not None:
                         if p not in late:
-                            late[p] = lagged_models(pm, site_plan[2])
+                            # once per model, for the union of both plans' release days
+                            late[p] = lagged_models(pm, sorted(set(site_plan[2]) | set(cmp_plan[2] if cmp_plan else ())))
                         rs = ReleaseSites(pm, sites['sites'], site_plan[1], late[p])
                         site_maps[ci] = (rs, None)
                         maps = ProjectedMaps(None, None, list(rs.days), SpreadSummary.for_projection(rs, thresholds),
@@ -1984,8 +2273,12 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                             maps.arrival = ArrivalMaps.for_projection(rs, a_thr)
                         if s_names:
                             maps.sensitivity = SensitivityMaps.for_projection(rs, s_names)
+                        if cmp_plan is not None:
+                            rb = ReleaseSites(pm, compare['sites'], site_plan[1], late[p])
+                            cmp_maps[ci] = (rb, None, late[p])
+                            cmp_maps[ci] = (rb, PlanContrast(rs, rb, thresholds), late[p])
                 results[ci] = _evaluate_runs(pm, summ, rows, rl, mcols, evaluate, want_obs, locinfo, hist, arr,
-                                             projected[ci], site_maps[ci], sens)
+                                             projected[ci], site_maps[ci], sens, cmp_maps[ci])
         except BaseException as e:       # re-raised in the caller's thread
             errs.append((p, e))
 
@@ -2002,6 +2295,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     if errs:
         for s in summaries + histograms + arrivals + senses + [x for pl in projected for pair in pl for x in pair] \
                 + [x for pair in site_maps if pair is not None for x in pair] \
+                + [x for tri in cmp_maps if tri is not None for x in tri[:2]] \
                 + [m for made in late.values() for m in made.values()]:
             if s is not None:
                 s.close()
@@ -2040,11 +2334,20 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         for proj, _maps in pl:
             proj.close()
     merged_sites = None
+    contrast = compare_desc = None
     if evaluate is None and site_plan is not None:
         merged_sites = site_maps[0][1]
         for _rs, maps in site_maps[1:]:
             merged_sites.merge(maps)
             maps.close()
+        if cmp_plan is not None:
+            contrast = cmp_maps[0][1]
+            compare_desc = cmp_maps[0][0].describe()
+            for _rb, x, _late in cmp_maps[1:]:
+                contrast.merge(x)
+                x.close()
+            for rb, _x, _late in cmp_maps:
+                rb.close()
         for rs, _maps in site_maps:      # and the plans with the models of their later release days
             rs.close()
         for made in late.values():
@@ -2071,7 +2374,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                            time.perf_counter() - t0, run_rec, observations, prov,
                            None if summary is None else summary.days, histogram, levels, arrival_maps,
                            a_levels if a_thr else None, merged.get('emergence'), merged.get('exposure'),
-                           merged_sites, sens_maps)
+                           merged_sites, sens_maps, contrast, compare_desc)
     if cell_area is not None:
         res.cell_area = float(cell_area)
     return res

@@ -11,7 +11,10 @@ release sites, some released days later -- saved as PREFIX_sites.npz (with --arr
 and, in the json, its reached-area curve); with --sensitivity also the posterior sensitivity maps -- per day and
 cell the correlation of the population with every listed model parameter (default: all 15), the share of the
 posterior variance a linear dependence on them explains and the dominant parameter -- saved as PREFIX_sens.npz
-(and PREFIX_NAME_sens.npz for every projection and plan asked for).  Kalbar wind and
+(and PREFIX_NAME_sens.npz for every projection and plan asked for); with --compare-sites (and --sites) also the
+paired contrast of the two release plans, member by member -- the posterior mean and spread of A - B, P(A > B),
+P(A < B), per threshold where A reaches it and B does not (and the reverse), and the posterior of the difference
+of the covered areas -- saved as PREFIX_contrast.npz.  Kalbar wind and
 LocInfo as scripts/run_mcmc.py loads them; --synthetic uses the synthetic Kalbar-like observations.
 Without --chain a short chain is sampled first (--samples) and saved next to --out.
 
@@ -20,6 +23,7 @@ Without --chain a short chain is sampled first (--samples) and saved next to --o
         [--quantiles 0.05,0.5,0.95] [--bins 1e-8,1e6,16] [--arrival 1,10] [--arrival-levels 0.05,0.5,0.95]
         [--emergence C[:d1,d2,...]] [--exposure d1,d2,...]
         [--sites 'E,N,AMOUNT[,LAG];...'] [--sites-days d1,d2,...] [--sensitivity [name,name,...]]
+        [--compare-sites 'E,N,AMOUNT[,LAG];...']
 """
 import argparse
 import json
@@ -59,16 +63,21 @@ def main():
                                                 'first release (default: off)')
     ap.add_argument('--sites-days', default='', help='output model days d1,d2,... of the release plan '
                                                      '(default: all, at most 32)')
+    ap.add_argument('--compare-sites', default='', help="a second release plan 'E,N,AMOUNT[,LAG];...' compared with "
+                                                        '--sites member by member on its output days (default: off)')
     ap.add_argument('--sensitivity', nargs='?', const='', default=None,
                     help='posterior sensitivity maps to the listed model parameters, e.g. sig_x,sig_y,mu_r '
                          '(no list: all 15; default: off)')
     args = ap.parse_args()
+    if args.compare_sites and not args.sites:
+        ap.error('--compare-sites names plan B and needs plan A: give --sites too')
     warnings.simplefilter('ignore', RuntimeWarning)
     from parasitoids_amd import ParasitoidModel as PM
     from parasitoids_amd import mcmc
     from parasitoids_amd.pop_model import PopModel
-    from parasitoids_amd.predictive import (bin_edges, check_arrival_thresholds, check_levels, check_sens_params,
-                                            emergence_plan, exposure_plan, posterior_predictive, sites_plan)
+    from parasitoids_amd.predictive import (bin_edges, check_arrival_thresholds, check_contrast_thresholds,
+                                            check_levels, check_sens_params, contrast_plan, emergence_plan,
+                                            exposure_plan, posterior_predictive, sites_plan)
     sens = None
     if args.sensitivity is not None:     # bad --sensitivity names fail before any work
         sens = check_sens_params([n.strip() for n in args.sensitivity.split(',') if n.strip()] or None)
@@ -91,6 +100,12 @@ def main():
                             for site in args.sites.split(';') if site.strip()],
                      days=[int(d) for d in args.sites_days.split(',') if d.strip()] or None)
         sites_plan(sites)                # a bad --sites fails before any work; against the model below
+    compare = None
+    if args.compare_sites:
+        compare = dict(sites=[tuple(float(v) if n < 3 else int(v) for n, v in enumerate(site.split(',')))
+                              for site in args.compare_sites.split(';') if site.strip()])
+        contrast_plan(compare, sites)    # as does a bad --compare-sites
+        check_contrast_thresholds([float(t) for t in args.thresholds.split(',') if t.strip()])
     wd, days = PM.get_wind_data(os.path.join(ROOT, 'parasitoids_amd', 'data', 'kalbar'), 30, '00:00')
 
     def make_pm():
@@ -102,6 +117,8 @@ def main():
         if sites['days'] is None:
             sites['days'] = list(range(min(len(days), 32)))
         sites_plan(sites, pm)
+        if compare:
+            contrast_plan(compare, sites, pm)
     if args.synthetic:
         li = mcmc.synthetic_locinfo(pm, args.rad_res, seed=9)
     else:
@@ -125,13 +142,26 @@ def main():
     res = posterior_predictive(pms if len(pms) > 1 else pm, chains, burn=args.burn, thin=args.thin,
                                thresholds=thr, locinfo=li, cell_area=cell_area, seed=args.seed,
                                quantiles=levels or None, bins=bins, arrival=arrival or None, arrival_levels=a_levels,
-                               emergence=emergence, exposure=exposure, sites=sites, sensitivity=sens)
+                               emergence=emergence, exposure=exposure, sites=sites, sensitivity=sens,
+                               compare=compare)
     dt = time.perf_counter() - t0
     # accumulate-kernel time: the same members once more with HIP events around every add
-    from parasitoids_amd.predictive import (ArrivalMaps, Projection, ReleaseSites, SensitivityMaps, SpreadHistogram,
-                                            SpreadSummary, load_chain, runs)
+    from parasitoids_amd.predictive import (ArrivalMaps, PlanContrast, Projection, ReleaseSites, SensitivityMaps,
+                                            SpreadHistogram, SpreadSummary, lagged_models, load_chain, runs)
     X = SensitivityMaps(pm, sens) if sens else None
-    RS = ReleaseSites.with_lagged_models(pm, sites['sites'], sites['days']) if sites else None
+    RB = XC = SC = None
+    union = {}
+    if compare:                          # as the driver: one model per release day of either plan, shared by both
+        union = lagged_models(pm, sorted(set(sites_plan(sites, pm)[2]) | set(contrast_plan(compare, sites, pm)[2])))
+        RS = ReleaseSites(pm, sites['sites'], sites['days'], union)
+        RB = ReleaseSites(pm, compare['sites'], sites['days'], union)
+    else:
+        RS = ReleaseSites.with_lagged_models(pm, sites['sites'], sites['days']) if sites else None
+    if compare:                          # and the plan's own summary to set the contrast's add against
+        XC = PlanContrast(RS, RB, thr)
+        SC = SpreadSummary.for_projection(RS, thr)
+        XC.profile(True)
+        SC.profile(True)
     projections = [Projection(pm, W, in_days) for W, in_days, _labels in plans]
     H = SpreadHistogram(pm, None, bins) if levels else None
     A = ArrivalMaps(pm, arrival) if arrival else None
@@ -155,7 +185,11 @@ def main():
             for first, length in rl[:8]:
                 try:
                     pm.evaluate(*mcmc.model_args(rows[first, cols]), want_stats=False)
-                    if RS is not None:
+                    if union:
+                        for lag, m in sorted(union.items()):       # each once per member, not once per plan
+                            m.evaluate(*mcmc.model_args(rows[first, cols]), ndays=sites['days'][-1] - lag + 1,
+                                       want_stats=False)
+                    elif RS is not None:
                         RS.evaluate_lagged(*mcmc.model_args(rows[first, cols]))
                 except Exception:
                     continue
@@ -170,6 +204,10 @@ def main():
                     P.apply()
                 if RS is not None:
                     RS.apply()
+                if XC is not None:
+                    RB.apply()
+                    SC.add(length)
+                    XC.add(length)
                 n += 1
         ms, launches = S.profile()
     if H is not None:
@@ -192,6 +230,13 @@ def main():
     if RS is not None:
         s_ms, s_launches = RS.profile()
         s_bytes, s_groups, s_nsite = RS.nbytes, len(RS.groups), len(RS.sites)
+    if XC is not None:
+        c_ms, c_launches = XC.profile()
+        cs_ms, cs_launches = SC.profile()
+        c_bytes = XC.nbytes
+        for h in (XC, SC, RB) + tuple(union.values()):
+            h.close()
+    if RS is not None:
         RS.close()
     npz, js = res.save(args.out, {'chains': chains, 'burn': args.burn, 'thin': args.thin, 'rad_res': args.rad_res,
                                   'mode': args.mode, 'synthetic': bool(args.synthetic)})
@@ -237,6 +282,15 @@ def main():
         out['sites_bytes'] = s_bytes                                    # the output fields
         out['sites'] = {'sites': s_nsite, 'groups': s_groups, 'days': len(sites['days'])}
         out['outputs'] += ['%s_sites.npz' % args.out]
+    if compare:
+        out['contrast_add_ms_per_member'] = round(c_ms / max(c_launches, 1), 4)
+        out['contrast_launches_timed'] = c_launches
+        out['contrast_plan_summary_add_ms_per_member'] = round(cs_ms / max(cs_launches, 1), 4)
+        # what every add must move: both plans' fields, 16 B per cell and output
+        out['contrast_read_GBps'] = round(16 * ncell * len(sites['days']) / (c_ms / max(c_launches, 1) * 1e-3) / 1e9, 1) \
+            if c_ms > 0 else None
+        out['contrast_bytes'] = c_bytes
+        out['outputs'] += ['%s_contrast.npz' % args.out]
     print(json.dumps(out))
     res.summary.close()
     if res.histogram is not None:
@@ -245,7 +299,7 @@ def main():
         res.arrival.close()
     if res.sensitivity is not None:
         res.sensitivity.close()
-    for pr in (res.emergence, res.exposure, res.sites):
+    for pr in (res.emergence, res.exposure, res.sites, res.contrast):
         if pr is not None:
             pr.close()
     for p in pms:
