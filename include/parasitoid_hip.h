@@ -696,6 +696,65 @@ int ps_contrast_reset(ps_contrast* h);
 int ps_contrast_prof(ps_contrast* h, int enable, double* total_ms, int64_t* launches);
 void ps_contrast_destroy(ps_contrast* h);
 
+/* ---- Monte Carlo error of the posterior maps: batch means of one sequence of members ----
+ * (no reference counterpart: it calls pm.gelman_rubin on scalar parameters only.)  Every map above is a Monte
+ * Carlo estimate from a correlated chain; its error needs the order of the chain at every cell and cannot be
+ * rebuilt from the saved maps.  One handle is one sequence -- a chain, or half of one -- cut into batches of
+ * exactly b = batch_weight rows of weight (1 .. 2^32 - 1, fixed at create).  It lives on one device and holds
+ * nslot slots of N x N cells (pitch as ps_summary): fp64 bmean, bM2 (the open batch), gmean, gM2 (Welford over
+ * the closed batches' means, weight 1 each), wM2 (the sum of the closed batches' own M2), and per threshold
+ * uint32 bcnt (the open batch's weight with value >= t_k), uint32 s1 (the sum of the closed batches' counts)
+ * and uint64 s2 (the sum of their squares).  0 <= nthr <= 4, the thresholds finite and strictly increasing.
+ * The footprint, (40 + 16 nthr) * nslot * pitch bytes and one plane for the R-hat, is checked against the free
+ * device memory first: PS_ERR_OOM before anything is allocated.  Every plane is zero after create and reset.
+ * Host side: the closed batches B, the open batch's weight, the discarded weight and the member count; the
+ * total weight added stays <= 2^32 - 1, so s2 <= n b < 2^64 with n = b B.  Every cell has one writer: no atomics
+ * of either kind, and the counts are exact. */
+typedef struct ps_mcerr ps_mcerr;
+int ps_mcerr_create(int device, int N, int nslot, int nthr, const double* thr, uint32_t batch_weight,
+                    ps_mcerr** out);
+/* One member with weight >= 1, value and arguments as ps_summary_add (same value bit for bit).  The library
+ * splits the weight at the batch boundaries: it fills the open batch and closes it, then whole batches of b,
+ * then the rest, one launch of the add kernel per piece on the same source -- a caller that splits the weight
+ * itself gets the same bits.  A piece of weight w into an open batch of weight Wo: with W' = Wo + w the
+ * statements of ps_summary_add on (bmean, bM2), and bcnt_k += w where value >= t_k.  A batch that reaches b is
+ * closed on the same stream, per cell: the Welford step of (gmean, gM2) with value bmean, weight 1 and B + 1
+ * batches; wM2 += bM2; s1_k += bcnt_k, s2_k += bcnt_k^2; the batch planes zero again.  PS_ERR_BAD_ARG (nothing
+ * enqueued): as ps_summary_add, and a total weight past 2^32 - 1. */
+int ps_mcerr_add(ps_mcerr* h, ps_solver* s, int nslot, const int32_t* kind, const int32_t* idx,
+                 const double* stat_scale, const double* post_scale, const int32_t* use_delta, double negval,
+                 uint32_t weight);
+/* the same for the current outputs of a projection or a release plan, as ps_summary_add_project /
+ * ps_summary_add_sites take them */
+int ps_mcerr_add_project(ps_mcerr* h, ps_project* p, uint32_t weight);
+int ps_mcerr_add_sites(ps_mcerr* h, ps_sites* p, uint32_t weight);
+/* discard the open batch: its planes zero, its weight onto the discarded weight */
+int ps_mcerr_finish(ps_mcerr* h);
+/* dst += src, pooling the closed batches: (gmean, gM2) by the expressions of ps_summary_merge with the batch
+ * counts, wM2, s1 and s2 added; discarded weight and members add.  Into a dst without batches it is a device
+ * copy, bit for bit.  PS_ERR_BAD_ARG: dst == src, another device, N, slot count, batch weight or thresholds;
+ * PS_ERR_STATE: either handle has an open batch. */
+int ps_mcerr_merge(ps_mcerr* dst, ps_mcerr* src);
+/* closed batches B, b, the used weight n = b B, the open and the discarded weight, members (any may be null) */
+int ps_mcerr_info(ps_mcerr* h, int64_t* batches, int64_t* batch_weight, int64_t* used_weight,
+                  int64_t* open_weight, int64_t* discarded_weight, int64_t* members);
+/* one raw plane of one slot to the host (synchronises): what 0 gmean, 1 gM2, 2 wM2.  PS_ERR_STATE with fewer
+ * than 2 closed batches. */
+int ps_mcerr_fetch(ps_mcerr* h, int slot, int what, double* out /* N*N */);
+/* s1 and s2 of threshold k (either may be null); PS_ERR_STATE with fewer than 2 closed batches */
+int ps_mcerr_fetch_counts(ps_mcerr* h, int slot, int k, uint32_t* s1 /* N*N */, uint64_t* s2 /* N*N */);
+/* Split R-hat of one slot over 2 <= nh <= 16 sequences of the same device, N, slot count and b, each without an
+ * open batch and with >= 2 closed batches (else PS_ERR_STATE); the batch counts may differ.  Per cell, the
+ * sequences in argument order: mu_j = gmean_j, s2_j = (wM2_j + b gM2_j) / (n_j - 1), W = mean s2_j,
+ * Bv = sum (mu_j - mean mu)^2 / (nh - 1), nbar = mean n_j, R = sqrt(((nbar - 1) / nbar W + Bv) / W), 0 where
+ * W == 0.  Computed into a device plane of the first handle, one copy to the host (synchronises). */
+int ps_mcerr_rhat(ps_mcerr* const* handles, int nh, int slot, double* out /* N*N */);
+int ps_mcerr_reset(ps_mcerr* h);
+/* measurement: HIP-event timing of the add launches (one pair per piece) and of the close launches */
+int ps_mcerr_prof(ps_mcerr* h, int enable, double* add_ms, int64_t* add_launches, double* close_ms,
+                  int64_t* close_launches);
+void ps_mcerr_destroy(ps_mcerr* h);
+
 #ifdef __cplusplus
 }
 #endif

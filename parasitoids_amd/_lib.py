@@ -204,6 +204,19 @@ SIGNATURES = {
     'ps_contrast_reset': (C.c_int, [_VP]),
     'ps_contrast_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P]),
     'ps_contrast_destroy': (None, [_VP]),
+    'ps_mcerr_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _F64P, C.c_uint32, C.POINTER(_VP)]),
+    'ps_mcerr_add': (C.c_int, [_VP, _VP, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P, C.c_double, C.c_uint32]),
+    'ps_mcerr_add_project': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_mcerr_add_sites': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_mcerr_finish': (C.c_int, [_VP]),
+    'ps_mcerr_merge': (C.c_int, [_VP, _VP]),
+    'ps_mcerr_info': (C.c_int, [_VP, _I64P, _I64P, _I64P, _I64P, _I64P, _I64P]),
+    'ps_mcerr_fetch': (C.c_int, [_VP, C.c_int, C.c_int, _F64P]),
+    'ps_mcerr_fetch_counts': (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    'ps_mcerr_rhat': (C.c_int, [C.POINTER(_VP), C.c_int, C.c_int, _F64P]),
+    'ps_mcerr_reset': (C.c_int, [_VP]),
+    'ps_mcerr_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P, _F64P, _I64P]),
+    'ps_mcerr_destroy': (None, [_VP]),
 }
 
 _lib = None

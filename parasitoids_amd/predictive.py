@@ -26,6 +26,10 @@ parameters of the member behind them (ps_sens_*, csrc/ps_sens.hip; `ParamMoments
 host): which parameter the spread at a cell comes from, as correlation maps, the share of the variance a linear
 dependence on the parameters explains, and the dominant parameter -- a chain stores no fields, so this
 covariance cannot be formed after the run.
+`MonteCarloError` keeps, on the device, one sequence of members -- a chain, or half of one -- as batch means of
+exactly b rows of weight (ps_mcerr_*, csrc/ps_mcerr.hip): the Monte Carlo standard error of the posterior mean and
+of the exceedance probabilities, the effective sample size and, over several sequences, the split R-hat
+(`split_rhat`) per cell -- they need the order of the chain at every cell, which no saved map keeps.
 """
 import ctypes as C
 import json
@@ -843,11 +847,14 @@ class ProjectedMaps():
     plan (`posterior_predictive(sites=...)`): `weights` and `in_days` are None, `labels` are the output days,
     `plan` is ReleaseSites.describe() and `arrival` the ArrivalMaps.for_projection (None without arrival
     thresholds), whose accessors take the output day.  `sensitivity`: the SensitivityMaps.for_projection (None
-    unless asked for), which takes the output index.'''
+    unless asked for), which takes the output index.  `mc_error`: the MonteCarloError.for_projection pooled over
+    all chains, with `rhat` (None unless asked for; while the chains run, one chain's two sequences), which takes
+    the output index.'''
 
     def __init__(self, weights, in_days, labels, summary, histogram=None, arrival=None, plan=None,
-                 sensitivity=None):
+                 sensitivity=None, mc_error=None):
         self.sensitivity = sensitivity
+        self.mc_error = mc_error
         self.weights = weights
         self.in_days = in_days
         self.labels = labels
@@ -873,6 +880,9 @@ class ProjectedMaps():
             self.arrival.close()
         if self.sensitivity is not None:
             self.sensitivity.close()
+        if self.mc_error is not None:
+            for s in (self.mc_error if isinstance(self.mc_error, (list, tuple)) else [self.mc_error]):
+                s.close()
 
 
 # ------------------------------------------------------------------ release plans
@@ -1758,6 +1768,308 @@ class SensitivityMaps():
             pass
 
 
+# ------------------------------------------------------------------ Monte Carlo error
+MAX_MC_THRESHOLDS = 4
+MAX_MC_SEQUENCES = 16      # ps_mcerr_rhat: the sequences of one launch's plane pointers
+MAX_MC_WEIGHT = 2 ** 32 - 1
+
+
+def check_mc_thresholds(thresholds):
+    '''0..4 thresholds, finite and strictly increasing -> [float]'''
+    thr = [float(t) for t in thresholds]
+    if len(thr) > MAX_MC_THRESHOLDS:
+        raise ValueError('at most %d thresholds, got %d' % (MAX_MC_THRESHOLDS, len(thr)))
+    if not all(np.isfinite(t) for t in thr) or any(b <= a for a, b in zip(thr, thr[1:])):
+        raise ValueError('thresholds must be finite and strictly increasing, got %r' % (thr,))
+    return thr
+
+
+def mc_batch_plan(rows_per_chain, batches):
+    '''How posterior_predictive cuts its chains for the Monte Carlo error: rows_per_chain, the kept rows of
+    every chain; batches, the batches a chain of the shortest length gives (even and >= 4, so that either half
+    has at least two) -> (b, [(half, rows), ...]): the batch weight b = min(rows_per_chain) // batches, one for
+    all chains, and per chain the row `half` = rows // 2 at which its second sequence starts -- rows [0, half)
+    feed the first, [half, rows) the second.  ValueError where a chain has fewer than `batches` rows.'''
+    rows = [int(n) for n in rows_per_chain]
+    if int(batches) != batches or batches < 4 or batches % 2:
+        raise ValueError('batches must be an even integer >= 4, got %r' % (batches,))
+    if not rows:
+        raise ValueError('no chains')
+    b = min(rows) // int(batches)
+    if b < 1:
+        raise ValueError('a chain of %d rows is shorter than %d batches' % (min(rows), batches))
+    if max(rows) > MAX_MC_WEIGHT:
+        raise ValueError('a chain of %d rows is past the weight 2^32 - 1 of one sequence' % max(rows))
+    return b, [(n // 2, n) for n in rows]
+
+
+def mc_split(first, length, half):
+    '''the weight of the run of rows [first, first + length) before and from the row `half` on'''
+    head = max(0, min(first + length, half) - first)
+    return head, length - head
+
+
+def mc_error_plan(mc_error):
+    '''the mc_error= argument of posterior_predictive -> the batches per chain: True -> 20, dict(batches=B)'''
+    if mc_error is True:
+        return 20
+    if not isinstance(mc_error, dict) or set(mc_error) - {'batches'}:
+        raise ValueError('mc_error must be True or dict(batches=B), got %r' % (mc_error,))
+    batches = mc_error.get('batches', 20)
+    mc_batch_plan([batches], batches)
+    return int(batches)
+
+
+class MonteCarloError():
+    '''Batch means of one sequence of members -- a chain, or half of one -- on the device (ps_mcerr_*,
+    csrc/ps_mcerr.hip): how far the posterior mean and the exceedance probabilities of `SpreadSummary` are from
+    what a longer chain would give.  The sequence is cut into batches of exactly `batch_weight` rows of weight;
+    `add(weight)` takes the value `SpreadSummary.add` takes and splits the weight at the batch boundaries.
+    `finish()` discards the open batch, so the maps are those of the used rows n = b B alone.  days, thresholds
+    (0..4, finite, strictly increasing) as SpreadSummary; the accessors take a model day, of `for_projection`
+    the output index.  `rhat`: {day: split R-hat map} where posterior_predictive pooled the sequences, else None.'''
+
+    rhat = None
+
+    def __init__(self, pop_model, batch_weight, days=None, thresholds=()):
+        self._h = L._VP()
+        days = list(range(len(pop_model.days)) if days is None else days)
+        if not days or min(days) < 0:
+            raise ValueError('days must be a non-empty list of model days >= 0')
+        self._setup(pop_model, batch_weight, days, thresholds, None)
+
+    @classmethod
+    def for_projection(cls, projection, batch_weight, thresholds=()):
+        '''The batch means of the outputs of `projection` (a Projection or a ReleaseSites), one slot per output
+        that carries weight: `add(weight)` takes the outputs of its last `apply()`.'''
+        self = cls.__new__(cls)
+        self._h = L._VP()
+        self._setup(projection.pm, batch_weight, list(range(projection.nout)), thresholds, projection)
+        return self
+
+    def _setup(self, pop_model, batch_weight, days, thresholds, projection):
+        self._lib = L.load()
+        self.pm = pop_model
+        self.days = days
+        self.thresholds = check_mc_thresholds(thresholds)
+        b = int(batch_weight)
+        if b != batch_weight or not 1 <= b <= MAX_MC_WEIGHT:
+            raise ValueError('batch_weight must be an integer in 1 .. 2^32 - 1, got %r' % (batch_weight,))
+        self.N = 2 * int(pop_model.rad_res) + 1
+        self.device = L.default_device() if pop_model.device is None else int(pop_model.device)
+        self._proj = projection
+        keys = days if projection is None else projection.live
+        self._slot = {d: i for i, d in enumerate(keys)}
+        self._n = len(self._slot)
+        pitch = (self.N * self.N + 63) // 64 * 64
+        self.nbytes = self._n * pitch * (40 + 16 * len(self.thresholds))     # five fp64 planes, counts per threshold
+        thr = L.f64(self.thresholds if self.thresholds else [0.0])
+        L.check(self._lib.ps_mcerr_create(self.device, self.N, self._n, len(self.thresholds), L.p_f64(thr), b,
+                                          C.byref(self._h)))
+        if projection is None:
+            self._kind, self._idx, self._delta = _day_slots(self.days)
+
+    def add(self, weight=1):
+        '''Accumulate the last evaluation of the model (of a projection: its last apply) with integer weight
+        >= 1, split at the batch boundaries; a batch that fills up is closed.  No host synchronisation.'''
+        w = int(weight)
+        if w < 1:
+            raise ValueError('weight must be a positive integer')
+        if self._proj is not None:
+            L.check(getattr(self._lib, 'ps_mcerr_add_' + self._proj.fields_kind)(self._h, self._proj._h, w))
+            return
+        pm = self.pm
+        _check_evaluated(pm, self.days, 'Monte Carlo error')
+        stat, post = _day_scales(pm, self.days)
+        L.check(self._lib.ps_mcerr_add(self._h, pm.solver._h, self._n, L.p_i32(self._kind), L.p_i32(self._idx),
+                                       L.p_f64(stat), L.p_f64(post), L.p_i32(self._delta), NEGVAL, w))
+
+    def finish(self):
+        '''discard the open batch (its weight goes to `discarded_weight`)'''
+        L.check(self._lib.ps_mcerr_finish(self._h))
+
+    def merge(self, other):
+        '''self += other: the closed batches of both pooled (same device, domain, days, thresholds and batch
+        weight; both finished)'''
+        if list(other.days) != self.days or other._slot != self._slot:
+            raise ValueError('sequences over different days')
+        L.check(self._lib.ps_mcerr_merge(self._h, other._h))
+
+    def reset(self):
+        L.check(self._lib.ps_mcerr_reset(self._h))
+        self.rhat = None
+
+    def _info(self):
+        v = [C.c_int64() for _ in range(6)]
+        L.check(self._lib.ps_mcerr_info(self._h, *[C.byref(x) for x in v]))
+        return [x.value for x in v]
+
+    @property
+    def batches(self):
+        return self._info()[0]
+
+    @property
+    def batch_weight(self):
+        return self._info()[1]
+
+    @property
+    def used_weight(self):
+        return self._info()[2]
+
+    @property
+    def open_weight(self):
+        return self._info()[3]
+
+    @property
+    def discarded_weight(self):
+        return self._info()[4]
+
+    @property
+    def members(self):
+        return self._info()[5]
+
+    def _slot_of(self, day):
+        '''the slot of a day, None for an output without weight'''
+        if day not in self._slot:
+            if self._proj is not None and day in self.days:
+                return None
+            raise ValueError('day %r is not in the sequence %s' % (day, self.days))
+        return self._slot[day]
+
+    def plane(self, day, what):
+        '''[N, N] float64: a raw plane (0 gmean, 1 gM2, 2 wM2)'''
+        slot = self._slot_of(day)
+        if slot is None:
+            return np.zeros((self.N, self.N), dtype=np.float64)
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        L.check(self._lib.ps_mcerr_fetch(self._h, slot, int(what), L.p_f64(out)))
+        return out
+
+    def counts(self, day, k):
+        '''(s1 [N, N] uint32, s2 [N, N] uint64): over the closed batches the sum of the weight with value >=
+        thresholds[k] and the sum of its squares'''
+        if not 0 <= int(k) < len(self.thresholds):
+            raise ValueError('threshold %r of %d' % (k, len(self.thresholds)))
+        slot = self._slot_of(day)
+        s1 = np.zeros((self.N, self.N), dtype=np.uint32)
+        s2 = np.zeros((self.N, self.N), dtype=np.uint64)
+        if slot is not None:
+            L.check(self._lib.ps_mcerr_fetch_counts(self._h, slot, int(k), s1.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                    s2.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return s1, s2
+
+    def mean(self, day):
+        '''The mean over the used rows n = b B.  It differs from `SpreadSummary.mean` only by the discarded
+        remainder -- the rows of the open batch `finish()` dropped.'''
+        return self.plane(day, 0)
+
+    def mcse(self, day):
+        '''the Monte Carlo standard error of `mean`: sqrt(gM2 / (B - 1) / B), the batch means' standard error'''
+        B = float(self.batches)
+        return np.sqrt(self.plane(day, 1) / (B - 1.0) / B)
+
+    def variance(self, day):
+        '''(wM2 + b gM2) / n: the variance over the used rows'''
+        _B, b, n = self._info()[:3]
+        return (self.plane(day, 2) + float(b) * self.plane(day, 1)) / float(n)
+
+    def ess(self, day):
+        '''The effective sample size n variance / (b gM2 / (B - 1)); 0 where gM2 == 0.  Not capped at n:
+        antithetic chains exceed it.'''
+        B, b, n = self._info()[:3]
+        g = self.plane(day, 1)
+        num = float(n) * ((self.plane(day, 2) + float(b) * g) / float(n))
+        out = np.zeros_like(g)
+        np.divide(num, float(b) * (g / (B - 1.0)), out=out, where=g != 0.0)
+        return out
+
+    def prob(self, day, k):
+        '''P(value >= thresholds[k]) over the used rows: s1 / n'''
+        return self.counts(day, k)[0] / float(self.used_weight)
+
+    def _batch_count_variance(self, day, k):
+        '''(s1, B s2 - s1^2 in exact integer arithmetic (B s2 <= n^2 < 2^64) as float64)'''
+        s1, s2 = self.counts(day, k)
+        q = s1.astype(np.uint64)
+        return s1, (np.uint64(self.batches) * s2 - q * q).astype(np.float64)
+
+    def prob_mcse(self, day, k):
+        '''the Monte Carlo standard error of `prob`: sqrt((B s2 - s1^2) / (B (B - 1)) / b^2 / B)'''
+        B, b = float(self.batches), float(self.batch_weight)
+        return np.sqrt(self._batch_count_variance(day, k)[1] / (B * (B - 1.0)) / (b * b) / B)
+
+    def prob_ess(self, day, k):
+        '''the effective sample size of `prob`: n p (1 - p) / (b var), var the batch proportions' sample
+        variance; 0 where that is 0'''
+        B, b, n = [float(x) for x in self._info()[:3]]
+        s1, num = self._batch_count_variance(day, k)
+        p = s1 / n
+        out = np.zeros(p.shape)
+        np.divide(n * (p * (1.0 - p)), b * (num / (B * (B - 1.0)) / (b * b)), out=out, where=num != 0.0)
+        return out
+
+    def profile(self, enable=None):
+        '''HIP-event time of the add launches, one per piece, and of the close launches: (add ms, add launches,
+        close ms, close launches); enable switches it'''
+        ms, n, cms, cn = C.c_double(), C.c_int64(), C.c_double(), C.c_int64()
+        L.check(self._lib.ps_mcerr_prof(self._h, -1 if enable is None else int(bool(enable)), C.byref(ms),
+                                        C.byref(n), C.byref(cms), C.byref(cn)))
+        return ms.value, n.value, cms.value, cn.value
+
+    def close(self):
+        if self._h:
+            self._lib.ps_mcerr_destroy(self._h)
+            self._h = L._VP()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def split_rhat(sequences, day):
+    '''[N, N] float64: the split R-hat of 2..16 finished MonteCarloError sequences (same days and batch weight,
+    each with >= 2 batches, which may differ in number) at a day, on the device (ps_mcerr_rhat); 0 where
+    every sequence is constant'''
+    seqs = list(sequences)
+    if not 2 <= len(seqs) <= MAX_MC_SEQUENCES:
+        raise ValueError('2..%d sequences, got %d' % (MAX_MC_SEQUENCES, len(seqs)))
+    s0 = seqs[0]
+    if any(list(s.days) != s0.days or s._slot != s0._slot for s in seqs[1:]):
+        raise ValueError('sequences over different days')
+    slot = s0._slot_of(day)
+    out = np.zeros((s0.N, s0.N), dtype=np.float64)
+    if slot is not None:
+        hs = (L._VP * len(seqs))(*[s._h.value for s in seqs])
+        L.check(s0._lib.ps_mcerr_rhat(hs, len(seqs), slot, L.p_f64(out)))
+    return out
+
+
+def pool_mc_error(pairs):
+    '''pairs: per chain its two sequences.  Finishes them all, takes the split R-hat maps of all of them
+    together (None where there are more than 16, or one has fewer than 2 batches -- failed members), then merges
+    them in chain order into the first, which is returned with `rhat` set; the others are closed.'''
+    seqs = [s for pair in pairs for s in pair]
+    for s in seqs:
+        s.finish()
+    first = seqs[0]
+    rhat = None
+    if len(seqs) <= MAX_MC_SEQUENCES and all(s.batches >= 2 for s in seqs):
+        rhat = {d: split_rhat(seqs, d) for d in first.days}
+    for s in seqs[1:]:
+        first.merge(s)
+        s.close()
+    first.rhat = rhat
+    return first
+
+
 # ------------------------------------------------------------------ traces
 def model_names():
     return [m[0] for m in mcmc.MODEL_BLOCK]
@@ -1903,6 +2215,31 @@ def save_sensitivity(outfile, sens, keys, labels):
     return block
 
 
+def mc_error_block(mc, keys, labels, prefix, maps):
+    '''the maps of one pooled MonteCarloError appended to `maps` for save_maps (keys: its days or output
+    indices, labels: theirs in the file behind `prefix`) -> its block for the json'''
+    nk = len(mc.thresholds)
+    outputs = []
+    for key, label in zip(keys, labels):
+        ess = mc.ess(key)
+        rhat = None if mc.rhat is None else mc.rhat[key]
+        day_maps = [('_mcse', mc.mcse(key)), ('_ess', ess)]
+        if rhat is not None:
+            day_maps.append(('_rhat', rhat))
+        day_maps += [('_pmcse%d' % k, mc.prob_mcse(key, k)) for k in range(nk)]
+        maps.append(('%s%s' % (prefix, label), day_maps))
+        live = mc.counts(key, 0)[0] > 0 if nk else mc.mean(key) > 0
+        rec = {'label': label, 'cells': int(live.sum()), 'ess_min': None, 'ess_median': None, 'rhat_max': None}
+        if live.any():
+            rec['ess_min'] = float(ess[live].min())
+            rec['ess_median'] = float(np.median(ess[live]))
+            if rhat is not None:
+                rec['rhat_max'] = float(rhat[live].max())
+        outputs.append(rec)
+    return {'thresholds': list(mc.thresholds), 'batches_pooled': mc.batches, 'used_weight': mc.used_weight,
+            'discarded_weight': mc.discarded_weight, 'members': mc.members, 'outputs': outputs}
+
+
 # ------------------------------------------------------------------ driver
 class PredictiveResult():
     '''What posterior_predictive returns: `summary` (a SpreadSummary, None without a device),
@@ -1915,12 +2252,17 @@ class PredictiveResult():
     release plan (with `plan` and, with arrival thresholds, `arrival`), None where not asked for;
     `sensitivity`: SensitivityMaps over the summary's days, None where not asked for (the projections and the
     plan then carry one of their own); `contrast`: the PlanContrast of the release plan against the plan of
-    compare= and `compare_plan` that plan (ReleaseSites.describe()), both None where not asked for.'''
+    compare= and `compare_plan` that plan (ReleaseSites.describe()), both None where not asked for; `mc_error`:
+    the MonteCarloError over the summary's days, all chains' half sequences pooled in chain order, its `rhat`
+    their split R-hat maps, and `mc_plan` = dict(batches, batch_weight, sequences), both None where not asked for
+    (the projections and the plan then carry an `mc_error` of their own).'''
 
     def __init__(self, summary, rows, evaluations, failed, seconds, runs, observations, provenance, days,
                  histogram=None, quantiles=None, arrival=None, arrival_levels=None, emergence=None, exposure=None,
-                 sites=None, sensitivity=None, contrast=None, compare_plan=None):
+                 sites=None, sensitivity=None, contrast=None, compare_plan=None, mc_error=None, mc_plan=None):
         self.summary = summary
+        self.mc_error = mc_error
+        self.mc_plan = mc_plan
         self.contrast = contrast
         self.compare_plan = compare_plan
         self.sensitivity = sensitivity
@@ -1970,6 +2312,13 @@ class PredictiveResult():
         P(A < B)), `{label}_pgain{k}_*` / `{label}_ploss{k}_*`, and `coverage{k}_a` / `coverage{k}_b` [members,
         outputs] with `contrast_weights`; under `predictive.contrast` of the json plan B, the thresholds, labels,
         members, weight, cell area, levels and per threshold the coverage difference.
+        The Monte Carlo error goes into outfile_mcerr.npz: per day `{label}_mcse_*` (the standard error of the
+        posterior mean), `{label}_ess_*`, `{label}_rhat_*` (where there are R-hat maps) and per threshold
+        `{label}_pmcse{k}_*` (the standard error of the exceedance probability); those of a projection or a plan
+        in the same file under the labels `NAME_{label}`; under `predictive.mc_error` of the json the batches
+        per chain, the batch weight, the sequences, the used and the discarded weight and per output `ess_min`,
+        `ess_median` and `rhat_max` over the cells whose threshold-0 count is > 0 (without thresholds: whose mean
+        is > 0), null where there are none; `predictive.mc_error.NAME` the same for a projection or a plan.
         -> (npz path, json path)'''
         s = self.summary
         if s is None:
@@ -2068,23 +2417,41 @@ class PredictiveResult():
                 'plan_b': self.compare_plan, 'thresholds': list(X.thresholds), 'labels': list(X.labels),
                 'members': X.members, 'total_weight': X.total_weight, 'cell_area': X.cell_area, 'levels': x_levels,
                 'coverage_difference': [X.coverage_difference(k, x_levels) for k in range(nk)]}
+        if self.mc_error is not None:
+            mmaps = []
+            labels = [s.pm.days[d] if d < len(s.pm.days) else d for d in s.days]
+            block = dict(self.mc_plan or {})
+            block.update(mc_error_block(self.mc_error, s.days, labels, '', mmaps))
+            for name, pr in (('emergence', self.emergence), ('exposure', self.exposure), ('sites', self.sites)):
+                if pr is not None and pr.mc_error is not None:
+                    block[name] = mc_error_block(pr.mc_error, list(range(len(pr.labels))), pr.labels, name + '_',
+                                                 mmaps)
+            save_maps('%s_mcerr' % outfile, mmaps)
+            meta['predictive']['mc_error'] = block
         with open(str(outfile) + '.json', 'w') as fobj:
             json.dump(meta, fobj, default=str)
         return str(outfile) + '.npz', str(outfile) + '.json'
 
 
 def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, locinfo, histogram=None,
-                   arrival=None, projected=(), plan=None, sens=None, compare=None):
+                   arrival=None, projected=(), plan=None, sens=None, compare=None, mc=None):
     '''one chain: evaluate every run, add it to the summary (and the histogram, the arrival maps; projected:
     (Projection, ProjectedMaps) pairs, applied and then added; plan: a (ReleaseSites, ProjectedMaps) pair, the
     models of its later release days evaluated with the base model -- a member for which any of them fails is
     a failed member and is added nowhere -- applied and added last; sens: the chain's SensitivityMaps, and
     every ProjectedMaps' own, fed the run's theta after the summary beside it; compare: a (ReleaseSites of plan
     B, PlanContrast, {lag: model} of both plans' later release days) triple -- every model of that union is
-    evaluated once per member, and after the plan's own adds plan B is applied and the contrast added)
+    evaluated once per member, and after the plan's own adds plan B is applied and the contrast added; mc: (the
+    chain's two MonteCarloError sequences, its half boundary row) -- after every summary's add the run's length
+    is split at that row and added to the sequence or sequences it falls in, those of every ProjectedMaps too)
     -> (expected per run or None, failed)'''
     expected = []
     failed = 0
+
+    def mc_add(pair, first, length):
+        for seq, w in zip(pair, mc_split(first, length, mc[1])):
+            if w:
+                seq.add(w)
     for first, length in run_list:
         theta = rows[first, model_cols]
         if evaluate is not None:
@@ -2111,6 +2478,8 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
             expected.append(None)
             continue
         summary.add(length)
+        if mc is not None:
+            mc_add(mc[0], first, length)
         if sens is not None:
             sens.add(theta, length)
         if histogram is not None:
@@ -2120,6 +2489,8 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
         for proj, maps in projected:
             proj.apply()
             maps.summary.add(length)
+            if maps.mc_error is not None:
+                mc_add(maps.mc_error, first, length)
             if maps.sensitivity is not None:
                 maps.sensitivity.add(theta, length)
             if maps.histogram is not None:
@@ -2127,6 +2498,8 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
         if plan is not None:
             plan[0].apply()
             plan[1].summary.add(length)
+            if plan[1].mc_error is not None:
+                mc_add(plan[1].mc_error, first, length)
             if plan[1].sensitivity is not None:
                 plan[1].sensitivity.add(theta, length)
             for acc in (plan[1].histogram, plan[1].arrival):
@@ -2142,7 +2515,7 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
 def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, thresholds=(), locinfo=None,
                          cell_area=None, seed=0, evaluate=None, quantiles=None, bins=DEFAULT_BINS, edges=None,
                          arrival=None, arrival_levels=(0.05, 0.5, 0.95), emergence=None, exposure=None, sites=None,
-                         sensitivity=None, compare=None):
+                         sensitivity=None, compare=None, mc_error=None):
     '''Posterior predictive spread of one or more chains (`Sampler.save` files or (trace, names)
     pairs).  Burn and thin apply per chain; consecutive rows with identical model parameters are one
     evaluation weighted by the run's length.  pop_model: one PopModel or a list -- with several, one
@@ -2173,8 +2546,21 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     thresholds then have to be finite, > 0 and strictly increasing -- the models of the later release days built
     once per model for the union of both plans' lags and each evaluated once per member; after A's applies and
     adds B is applied and the contrast added with the same weight, merged in chain order into `contrast`
-    (`compare_plan`: plan B).'''
+    (`compare_plan`: plan B).  mc_error: True (20 batches per chain) or dict(batches=B), B even and >= 4
+    (mc_batch_plan; not with evaluate=, and every chain needs at least B rows after burn and thin); each chain
+    then also fills two MonteCarloError sequences beside its summary, same days and thresholds (finite, strictly
+    increasing), the rows before the chain's half into the first and the rest into the second, a run that
+    straddles the half split there -- and two per projection and plan asked for; at the end every sequence is
+    finished, the split R-hat maps taken over all 2 x chains sequences and the sequences merged in chain order
+    into `mc_error` (`mc_error.rhat`: the R-hat maps; None with more than 8 chains or a sequence left with fewer
+    than two batches by failed members).  The contrast gets none.'''
     t0 = time.perf_counter()
+    mc_batches = None
+    if mc_error is not None and mc_error is not False:       # bad Monte Carlo error arguments fail first too
+        if evaluate is not None:
+            raise ValueError('mc_error= needs the device: not with evaluate=')
+        mc_batches = mc_error_plan(mc_error)
+        check_mc_thresholds(thresholds)
     s_names = check_sens_params(sensitivity) if sensitivity is not None and sensitivity is not False else None
     levels = (check_levels(quantiles) if quantiles is not None else []) or None
     if levels:
@@ -2216,6 +2602,9 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         ocols = _columns(names, obs_want) if want_obs else None
         rows, rl = runs(trace, mcols, burn, thin)
         prepared.append((rows, rl, mcols, ocols, src))
+    mc_b = mc_halves = None
+    if mc_batches:                    # a chain shorter than the batches asked for
+        mc_b, mc_halves = mc_batch_plan([len(p[0]) for p in prepared], mc_batches)
     pms = list(pop_model) if isinstance(pop_model, (list, tuple)) else [pop_model]
     if evaluate is None and (not pms or pms[0] is None):
         raise ValueError('a PopModel is needed without evaluate=')
@@ -2228,6 +2617,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     histograms = [None] * nch
     arrivals = [None] * nch
     senses = [None] * nch
+    mcs = [None] * nch                         # per chain its two MonteCarloError sequences
     projected = [[] for _ in range(nch)]       # per chain (Projection, ProjectedMaps) of every plan
     site_maps = [None] * nch                   # per chain (ReleaseSites, ProjectedMaps)
     cmp_maps = [None] * nch                    # per chain (ReleaseSites of plan B, PlanContrast, the lagged models)
@@ -2248,6 +2638,10 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                 arrivals[ci] = arr
                 sens = SensitivityMaps(pm, s_names, summ.days) if evaluate is None and s_names else None
                 senses[ci] = sens
+                if mc_b:
+                    mcs[ci] = []
+                    for _half in range(2):
+                        mcs[ci].append(MonteCarloError(pm, mc_b, summ.days, thresholds))
                 if evaluate is None:
                     for _name, W, in_days, labels in plans:
                         proj = Projection(pm, W, in_days)
@@ -2258,6 +2652,10 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                             maps.histogram = SpreadHistogram.for_projection(proj, bins, edges)
                         if s_names:
                             maps.sensitivity = SensitivityMaps.for_projection(proj, s_names)
+                        if mc_b:
+                            maps.mc_error = []
+                            for _half in range(2):
+                                maps.mc_error.append(MonteCarloError.for_projection(proj, mc_b, thresholds))
                     if site_plan is not None:
                         if p not in late:
                             # once per model, for the union of both plans' release days
@@ -2273,12 +2671,17 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                             maps.arrival = ArrivalMaps.for_projection(rs, a_thr)
                         if s_names:
                             maps.sensitivity = SensitivityMaps.for_projection(rs, s_names)
+                        if mc_b:
+                            maps.mc_error = []
+                            for _half in range(2):
+                                maps.mc_error.append(MonteCarloError.for_projection(rs, mc_b, thresholds))
                         if cmp_plan is not None:
                             rb = ReleaseSites(pm, compare['sites'], site_plan[1], late[p])
                             cmp_maps[ci] = (rb, None, late[p])
                             cmp_maps[ci] = (rb, PlanContrast(rs, rb, thresholds), late[p])
                 results[ci] = _evaluate_runs(pm, summ, rows, rl, mcols, evaluate, want_obs, locinfo, hist, arr,
-                                             projected[ci], site_maps[ci], sens, cmp_maps[ci])
+                                             projected[ci], site_maps[ci], sens, cmp_maps[ci],
+                                             (mcs[ci], mc_halves[ci][0]) if mc_b else None)
         except BaseException as e:       # re-raised in the caller's thread
             errs.append((p, e))
 
@@ -2293,7 +2696,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         pms = pms[:1]
         work(0)
     if errs:
-        for s in summaries + histograms + arrivals + senses + [x for pl in projected for pair in pl for x in pair] \
+        for s in summaries + histograms + arrivals + senses + [x for pair in mcs if pair for x in pair] + [x for pl in projected for pair in pl for x in pair] \
                 + [x for pair in site_maps if pair is not None for x in pair] \
                 + [x for tri in cmp_maps if tri is not None for x in tri[:2]] \
                 + [m for made in late.values() for m in made.values()]:
@@ -2324,8 +2727,17 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
             for a in senses[1:]:
                 sens_maps.merge(a)
                 a.close()
+    mc_pooled = mc_desc = None
+    if mc_b:
+        mc_pooled = pool_mc_error(mcs)
+        mc_desc = {'batches': mc_batches, 'batch_weight': mc_b, 'sequences': 2 * nch}
     merged = {}
     for k, plan in enumerate(plans if evaluate is None else []):
+        if mc_b:                         # before the merge closes the other chains' maps
+            pooled = pool_mc_error([pl[k][1].mc_error for pl in projected])
+            for pl in projected:
+                pl[k][1].mc_error = None
+            projected[0][k][1].mc_error = pooled
         merged[plan[0]] = projected[0][k][1]
         for pl in projected[1:]:
             merged[plan[0]].merge(pl[k][1])
@@ -2336,6 +2748,11 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     merged_sites = None
     contrast = compare_desc = None
     if evaluate is None and site_plan is not None:
+        if mc_b:
+            pooled = pool_mc_error([maps.mc_error for _rs, maps in site_maps])
+            for _rs, maps in site_maps:
+                maps.mc_error = None
+            site_maps[0][1].mc_error = pooled
         merged_sites = site_maps[0][1]
         for _rs, maps in site_maps[1:]:
             merged_sites.merge(maps)
@@ -2374,7 +2791,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                            time.perf_counter() - t0, run_rec, observations, prov,
                            None if summary is None else summary.days, histogram, levels, arrival_maps,
                            a_levels if a_thr else None, merged.get('emergence'), merged.get('exposure'),
-                           merged_sites, sens_maps, contrast, compare_desc)
+                           merged_sites, sens_maps, contrast, compare_desc, mc_pooled, mc_desc)
     if cell_area is not None:
         res.cell_area = float(cell_area)
     return res

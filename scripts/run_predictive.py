@@ -68,6 +68,9 @@ def main():
     ap.add_argument('--sensitivity', nargs='?', const='', default=None,
                     help='posterior sensitivity maps to the listed model parameters, e.g. sig_x,sig_y,mu_r '
                          '(no list: all 15; default: off)')
+    ap.add_argument('--mc-error', nargs='?', const=20, default=None, type=int, metavar='B',
+                    help='Monte Carlo error maps (MCSE, ESS, split R-hat) from B batches per chain, B even and >= 4 '
+                         '(no number: 20; default: off)')
     args = ap.parse_args()
     if args.compare_sites and not args.sites:
         ap.error('--compare-sites names plan B and needs plan A: give --sites too')
@@ -77,7 +80,11 @@ def main():
     from parasitoids_amd.pop_model import PopModel
     from parasitoids_amd.predictive import (bin_edges, check_arrival_thresholds, check_contrast_thresholds,
                                             check_levels, check_sens_params, contrast_plan, emergence_plan,
-                                            exposure_plan, posterior_predictive, sites_plan)
+                                            exposure_plan, mc_error_plan, posterior_predictive, sites_plan)
+    mc_error = None
+    if args.mc_error is not None:        # a bad --mc-error fails before any work
+        mc_error = dict(batches=args.mc_error)
+        mc_error_plan(mc_error)
     sens = None
     if args.sensitivity is not None:     # bad --sensitivity names fail before any work
         sens = check_sens_params([n.strip() for n in args.sensitivity.split(',') if n.strip()] or None)
@@ -143,11 +150,13 @@ def main():
                                thresholds=thr, locinfo=li, cell_area=cell_area, seed=args.seed,
                                quantiles=levels or None, bins=bins, arrival=arrival or None, arrival_levels=a_levels,
                                emergence=emergence, exposure=exposure, sites=sites, sensitivity=sens,
-                               compare=compare)
+                               compare=compare, mc_error=mc_error)
     dt = time.perf_counter() - t0
     # accumulate-kernel time: the same members once more with HIP events around every add
-    from parasitoids_amd.predictive import (ArrivalMaps, PlanContrast, Projection, ReleaseSites, SensitivityMaps,
-                                            SpreadHistogram, SpreadSummary, lagged_models, load_chain, runs)
+    from parasitoids_amd.predictive import (ArrivalMaps, MonteCarloError, PlanContrast, Projection, ReleaseSites,
+                                            SensitivityMaps, SpreadHistogram, SpreadSummary, lagged_models,
+                                            load_chain, runs)
+    ME = MonteCarloError(pm, res.mc_plan['batch_weight'], None, thr) if mc_error else None
     X = SensitivityMaps(pm, sens) if sens else None
     RB = XC = SC = None
     union = {}
@@ -173,6 +182,8 @@ def main():
             A.profile(True)
         if X is not None:
             X.profile(True)
+        if ME is not None:
+            ME.profile(True)
         for P in projections:
             P.profile(True)
         if RS is not None:
@@ -194,6 +205,8 @@ def main():
                 except Exception:
                     continue
                 S.add(length)
+                if ME is not None:
+                    ME.add(length)
                 if X is not None:
                     X.add(rows[first, cols], length)
                 if H is not None:
@@ -222,6 +235,10 @@ def main():
         x_ms, x_launches = X.profile()
         x_bytes = X.nbytes
         X.close()
+    if ME is not None:
+        me_ms, me_launches, me_close_ms, me_closes = ME.profile()
+        me_members, me_bytes = ME.members, ME.nbytes
+        ME.close()
     p_ms = sum(P.profile()[0] for P in projections)
     p_launches = sum(P.profile()[1] for P in projections)
     p_bytes = sum(P.nbytes for P in projections)
@@ -270,6 +287,18 @@ def main():
         out['sensitivity_bytes'] = x_bytes
         out['sensitivity_params'] = len(sens)
         out['outputs'] += ['%s_sens.npz' % args.out]
+    if mc_error:
+        # the add launches of one member (one per piece of its weight) and its share of the close launches
+        out['mcerr_add_ms_per_member'] = round(me_ms / max(me_members, 1), 4)
+        out['mcerr_close_ms_per_member'] = round(me_close_ms / max(me_members, 1), 4)
+        out['mcerr_add_launches_timed'] = me_launches
+        out['mcerr_close_launches_timed'] = me_closes
+        out['mcerr_close_ms_per_launch'] = round(me_close_ms / max(me_closes, 1), 4)
+        out['mcerr_bytes'] = me_bytes
+        out['mc_error'] = dict(res.mc_plan, used_weight=res.mc_error.used_weight,
+                               discarded_weight=res.mc_error.discarded_weight,
+                               rhat=res.mc_error.rhat is not None)
+        out['outputs'] += ['%s_mcerr.npz' % args.out]
     if projections:
         out['project_ms_per_member'] = round(p_ms / max(n, 1), 4)       # every projection's apply of one member
         out['project_launches_timed'] = p_launches
@@ -299,6 +328,8 @@ def main():
         res.arrival.close()
     if res.sensitivity is not None:
         res.sensitivity.close()
+    if res.mc_error is not None:
+        res.mc_error.close()
     for pr in (res.emergence, res.exposure, res.sites, res.contrast):
         if pr is not None:
             pr.close()
