@@ -755,6 +755,71 @@ int ps_mcerr_prof(ps_mcerr* h, int enable, double* add_ms, int64_t* add_launches
                   int64_t* close_launches);
 void ps_mcerr_destroy(ps_mcerr* h);
 
+/* ---- posterior peak maps: how high each cell gets, on which day, and for how many days it stays above ----
+ * (no reference counterpart).  Per member reductions along time: max_s v_s is not linear, so neither E[max] nor
+ * the distribution of the peak day or of the days above a density can be rebuilt from the per-day maps.  A handle
+ * lives on one device and holds nslot day slots (1..32, ascending) of N x N cells and 0..4 strictly increasing
+ * thresholds t_0 < ... < t_{K-1}, each finite and > 0.  For one member, v_s(c) is the value ps_summary_add adds
+ * for slot s (same arguments, same value bit for bit), and
+ *   peak value   m(c) = max(+0.0, max_s v_s(c)): from m = +0.0, updated in slot order by the strict test v > m
+ *   peak slot    p(c) = the first slot that attains m; "none" where m == 0 (not stored)
+ *   duration     dur_k(c) = #{s : v_s(c) >= t_k}, 0..nslot: the listed slots, days only if they are consecutive
+ * State (pitch as ps_summary): Y[pitch] fp64, the peak field of the last member added (every add rewrites it,
+ * zeros included); pk[slot][pitch] uint32, the weight of the members whose peak falls on that slot;
+ * du[k][n - 1][pitch] uint32, n = 1..nslot, the weight of the members with dur_k = n (n = 0 is W - the rest, not
+ * stored).  The whole size, (1 + K) * nslot * pitch * 4 B plus two fp64 planes, is checked against the free
+ * device memory first: PS_ERR_OOM before anything is allocated.  Host side: W (< 2^32) and the member count.
+ * Counts are integers and every cell has one writer, no atomics: neither the order of adds, nor that of merges,
+ * nor the launch configuration changes a bit.  Every operation records an event the next one waits on, whichever
+ * stream it runs on (the solver's for add, the handle's own otherwise). */
+typedef struct ps_peak ps_peak;
+int ps_peak_create(int device, int N, int nslot, int nthr, const double* thr, ps_peak** out);
+/* One member with weight >= 1 (arguments and refusals as ps_arrival_add): one launch on the solver's stream walks
+ * every slot of every cell pair -- no early exit, the maximum needs them all -- no host synchronisation.  Every
+ * descriptor is resolved first, so an add with a bad slot enqueues nothing. */
+int ps_peak_add(ps_peak* a, ps_solver* s, int nslot, const int32_t* kind, const int32_t* idx,
+                const double* stat_scale, const double* post_scale, const int32_t* use_delta, double negval,
+                uint32_t weight);
+/* The same for the current outputs of a projection or a release plan, as ps_arrival_add_project /
+ * ps_arrival_add_sites: slot e takes Y_e (nslot must equal nout), on the handle's stream. */
+int ps_peak_add_project(ps_peak* a, ps_project* p, uint32_t weight);
+int ps_peak_add_sites(ps_peak* a, ps_sites* p, uint32_t weight);
+/* dst += src (an integer plane add), same device, N, slots and thresholds; src unchanged, dst's Y untouched */
+int ps_peak_merge(ps_peak* dst, ps_peak* src);
+int ps_peak_info(ps_peak* a, double* total_weight, int64_t* members);
+/* zero counts, W and members; the peak field is PS_ERR_STATE again until the next add */
+int ps_peak_reset(ps_peak* a);
+/* the last member's peak field (synchronises).  PS_ERR_STATE before the first add. */
+int ps_peak_fetch_field(ps_peak* a, double* out /* N*N */);
+/* count plane pk[slot] (synchronises) */
+int ps_peak_fetch_day_counts(ps_peak* a, int slot, uint32_t* out /* N*N */);
+/* count plane of threshold k and duration n in 0..nslot; n == 0: W - the rest (synchronises) */
+int ps_peak_fetch_duration_counts(ps_peak* a, int k, int n, uint32_t* out /* N*N */);
+/* P(peak by slot) = (double)C[slot] / (double)W per cell, C[s] = sum over s' <= s of pk (synchronises; cells that
+ * never hold anything stay below 1).  PS_ERR_STATE at W = 0, as every map below. */
+int ps_peak_day_prob(ps_peak* a, int slot, double* out /* N*N */);
+/* the smallest slot s with (double)C[s] >= p * (double)W per cell, -1 where even the last slot falls short;
+ * p in (0, 1] (synchronises) */
+int ps_peak_day_quantile(ps_peak* a, double p, int32_t* out /* N*N */);
+/* P(dur_k >= n) = (double)(sum over n' >= n of du[k][n']) / (double)W, n in 1..nslot (synchronises) */
+int ps_peak_duration_prob(ps_peak* a, int k, int n, double* out /* N*N */);
+/* the smallest n in 0..nslot whose cumulative count, the implied n = 0 plane included, reaches p W by the same
+ * rule; p in (0, 1] (synchronises) */
+int ps_peak_duration_quantile(ps_peak* a, int k, double p, int32_t* out /* N*N */);
+/* (double)(sum over n of n * du[k][n]) / (double)W, the sum exact in 64-bit integers (synchronises) */
+int ps_peak_duration_mean(ps_peak* a, int k, double* out /* N*N */);
+/* measurement: HIP-event timing of the add launches and of the map launches (prob, quantile, mean, n = 0 counts).
+ * enable 1 on, 0 off, < 0 unchanged; the totals so far go to the non-NULL outputs (synchronises).  Finished
+ * event pairs are folded into running totals, on every read and once 256 are pending, so a profiled handle
+ * holds a bounded number of events however long it lives. */
+int ps_peak_prof(ps_peak* a, int enable, double* add_ms, int64_t* adds, double* map_ms, int64_t* maps);
+void ps_peak_destroy(ps_peak* a);
+/* One member with weight >= 1 whose value is the peak field of the handle's last add, as the add_project entry
+ * points take a projection's outputs: the accumulator must have one slot; on the accumulator's stream behind the
+ * peak add, and the next peak add waits for it.  PS_ERR_STATE before the first add. */
+int ps_summary_add_peak(ps_summary* a, ps_peak* p, uint32_t weight);
+int ps_hist_add_peak(ps_hist* h, ps_peak* p, uint32_t weight);
+
 #ifdef __cplusplus
 }
 #endif

@@ -217,6 +217,25 @@ SIGNATURES = {
     'ps_mcerr_reset': (C.c_int, [_VP]),
     'ps_mcerr_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P, _F64P, _I64P]),
     'ps_mcerr_destroy': (None, [_VP]),
+    'ps_peak_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _F64P, C.POINTER(_VP)]),
+    'ps_peak_add': (C.c_int, [_VP, _VP, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P, C.c_double, C.c_uint32]),
+    'ps_peak_add_project': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_peak_add_sites': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_peak_merge': (C.c_int, [_VP, _VP]),
+    'ps_peak_info': (C.c_int, [_VP, _F64P, _I64P]),
+    'ps_peak_reset': (C.c_int, [_VP]),
+    'ps_peak_fetch_field': (C.c_int, [_VP, _F64P]),
+    'ps_peak_fetch_day_counts': (C.c_int, [_VP, C.c_int, C.POINTER(C.c_uint32)]),
+    'ps_peak_fetch_duration_counts': (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(C.c_uint32)]),
+    'ps_peak_day_prob': (C.c_int, [_VP, C.c_int, _F64P]),
+    'ps_peak_day_quantile': (C.c_int, [_VP, C.c_double, _I32P]),
+    'ps_peak_duration_prob': (C.c_int, [_VP, C.c_int, C.c_int, _F64P]),
+    'ps_peak_duration_quantile': (C.c_int, [_VP, C.c_int, C.c_double, _I32P]),
+    'ps_peak_duration_mean': (C.c_int, [_VP, C.c_int, _F64P]),
+    'ps_peak_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P, _F64P, _I64P]),
+    'ps_peak_destroy': (None, [_VP]),
+    'ps_summary_add_peak': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_hist_add_peak': (C.c_int, [_VP, _VP, C.c_uint32]),
 }
 
 _lib = None

@@ -30,6 +30,11 @@ covariance cannot be formed after the run.
 exactly b rows of weight (ps_mcerr_*, csrc/ps_mcerr.hip): the Monte Carlo standard error of the posterior mean and
 of the exceedance probabilities, the effective sample size and, over several sequences, the split R-hat
 (`split_rhat`) per cell -- they need the order of the chain at every cell, which no saved map keeps.
+`PeakMaps` keeps, on the device, per member the peak of every cell's curve over the listed days and, over the
+members, the weighted counts of the day of the peak and of the number of days at or above each threshold
+(ps_peak_*, csrc/ps_peak.hip): the peak field feeds `SpreadSummary.for_projection` / `SpreadHistogram.for_projection`
+(E[max], its spread and quantiles), the counts give peak-day and duration probabilities, quantile maps and the
+mean duration -- max over days is not linear, so none of them can be rebuilt from the per-day maps.
 """
 import ctypes as C
 import json
@@ -634,6 +639,250 @@ class ArrivalMaps():
             pass
 
 
+def check_peak_thresholds(thresholds):
+    '''the duration thresholds of peak maps as a list of floats: 0..4 of them by the rules of
+    check_arrival_thresholds; an empty list keeps the peak value and the peak day only'''
+    try:
+        thr = list(thresholds)
+    except TypeError:
+        raise ValueError('peak thresholds must be a list of numbers, got %r' % (thresholds,))
+    return check_arrival_thresholds(thr) if thr else []
+
+
+def check_peak(peak):
+    '''the peak= argument of posterior_predictive -> (thresholds, levels): a list of thresholds, or
+    dict(thresholds=[...], levels=(0.05, 0.5, 0.95)); ValueError otherwise'''
+    levels = (0.05, 0.5, 0.95)
+    if isinstance(peak, dict):
+        unknown = set(peak) - {'thresholds', 'levels'}
+        if unknown:
+            raise ValueError('peak: unknown keys %r' % (sorted(unknown),))
+        levels = peak.get('levels', levels)
+        peak = peak.get('thresholds', ())
+    return check_peak_thresholds(peak), check_levels(levels)
+
+
+class PeakMaps():
+    '''The shape of each cell's curve over the listed days, per member and then over the members: the peak value
+    m = max(+0.0, max_d v_d) (v_d the value SpreadSummary adds for day d), the peak day -- the first listed day
+    that attains m, none where m == 0 -- and per threshold t_k (0..4, finite, > 0, strictly increasing) the number
+    of listed days with v_d >= t_k.  On the device: the last member's peak field, the weighted counts of the peak
+    day and of every duration.  The peak field is a fields source like a Projection's outputs (one output):
+    SpreadSummary.for_projection(peak, thresholds) and SpreadHistogram.for_projection(peak, ...) accumulate it, so
+    E[max], its spread, P(peak >= t) and its quantiles come from the existing accumulators.  A duration counts
+    listed days: it is a number of days only where they are consecutive model days (`consecutive`).  Counts are
+    integers: the order of adds and merges changes no bit.'''
+    fields_kind = 'peak'         # the accumulators' entry points for the peak field: ps_*_add_peak
+    nout = 1
+    live = [0]
+
+    def __init__(self, pop_model, thresholds=(), days=None):
+        self._h = L._VP()
+        self.thresholds = check_peak_thresholds(thresholds)
+        self.days = check_arrival_days(range(len(pop_model.days)) if days is None else days)
+        self._setup(pop_model, None)
+
+    @classmethod
+    def for_projection(cls, projection, thresholds=()):
+        '''Peak maps of the outputs of `projection` (a ReleaseSites or a Projection), the slots its outputs that
+        carry weight in ascending order: `add(weight)` accumulates the outputs of its last `apply()`.  `days`
+        holds the output labels -- the plan's output days, or the projection's output indices.'''
+        self = cls.__new__(cls)
+        self._h = L._VP()
+        self.thresholds = check_peak_thresholds(thresholds)
+        labels = list(getattr(projection, 'days', range(projection.nout)))
+        self.days = check_arrival_days([labels[e] for e in projection.live])
+        self._setup(projection.pm, projection)
+        return self
+
+    def _setup(self, pop_model, projection):
+        self._proj = projection
+        self._lib = L.load()
+        self.pm = pop_model
+        self.N = 2 * int(pop_model.rad_res) + 1
+        self.device = L.default_device() if pop_model.device is None else int(pop_model.device)
+        self.consecutive = all(b == a + 1 for a, b in zip(self.days, self.days[1:]))
+        pitch = (self.N * self.N + 63) // 64 * 64
+        self.nbytes = (1 + len(self.thresholds)) * len(self.days) * pitch * 4 + 2 * pitch * 8   # counts + peak field + map scratch
+        thr = L.f64(self.thresholds if self.thresholds else [0.0])
+        L.check(self._lib.ps_peak_create(self.device, self.N, len(self.days), len(self.thresholds), L.p_f64(thr),
+                                         C.byref(self._h)))
+        if projection is None:
+            self._kind, self._idx, self._delta = _day_slots(self.days)
+        self._slot = {d: i for i, d in enumerate(self.days)}
+
+    def add(self, weight=1):
+        '''Accumulate the last evaluation of the model with integer weight >= 1 (enqueued on the
+        solver's stream; no host synchronisation).  On a projection or a plan: its last apply, on the
+        handle's stream.'''
+        w = int(weight)
+        if self._proj is not None:
+            if w < 1:
+                raise ValueError('weight must be a positive integer')
+            L.check(getattr(self._lib, 'ps_peak_add_' + self._proj.fields_kind)(self._h, self._proj._h, w))
+            return
+        pm = self.pm
+        _check_evaluated(pm, self.days, 'peak maps')
+        stat, post = _day_scales(pm, self.days)
+        if w < 1:
+            raise ValueError('weight must be a positive integer')
+        L.check(self._lib.ps_peak_add(self._h, pm.solver._h, len(self.days), L.p_i32(self._kind), L.p_i32(self._idx),
+                                      L.p_f64(stat), L.p_f64(post), L.p_i32(self._delta), NEGVAL, w))
+
+    def merge(self, other):
+        '''self += other (same device, domain, days and thresholds); the peak field stays self's'''
+        if list(other.days) != self.days:
+            raise ValueError('peak maps over different days')
+        L.check(self._lib.ps_peak_merge(self._h, other._h))
+
+    def reset(self):
+        L.check(self._lib.ps_peak_reset(self._h))
+
+    def _info(self):
+        w, m = C.c_double(), C.c_int64()
+        L.check(self._lib.ps_peak_info(self._h, C.byref(w), C.byref(m)))
+        return w.value, m.value
+
+    @property
+    def total_weight(self):
+        return self._info()[0]
+
+    @property
+    def members(self):
+        return self._info()[1]
+
+    def _k(self, k):
+        if not 0 <= int(k) < len(self.thresholds):
+            raise ValueError('threshold %r of %d' % (k, len(self.thresholds)))
+        return int(k)
+
+    def _slot_of(self, day):
+        if day not in self._slot:
+            raise ValueError('day %r is not in the peak maps %s' % (day, self.days))
+        return self._slot[day]
+
+    def _n(self, n, lo):
+        if not lo <= int(n) <= len(self.days):
+            raise ValueError('duration %r is not in %d..%d' % (n, lo, len(self.days)))
+        return int(n)
+
+    def field(self):
+        '''[N, N] float64: the peak field of the last member added'''
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        L.check(self._lib.ps_peak_fetch_field(self._h, L.p_f64(out)))
+        return out
+
+    def day_counts(self, day):
+        '''[N, N] uint32: the weight of the members whose peak falls on `day`'''
+        out = np.empty((self.N, self.N), dtype=np.uint32)
+        L.check(self._lib.ps_peak_fetch_day_counts(self._h, self._slot_of(day), out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def day_prob(self, day):
+        '''[N, N] float64: P(peaked by `day`) = C / W, C the weight of the peaks up to `day`'''
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        L.check(self._lib.ps_peak_day_prob(self._h, self._slot_of(day), L.p_f64(out)))
+        return out
+
+    def day_quantile(self, p):
+        '''[N, N] int32 map of model days: the first day whose C reaches p W ((double)C >= p * (double)W), -1
+        where even the last day falls short (too few members ever hold anything there)'''
+        if not 0.0 < float(p) <= 1.0:
+            raise ValueError('quantile level %r is not in (0, 1]' % (p,))
+        slot = np.empty((self.N, self.N), dtype=np.int32)
+        L.check(self._lib.ps_peak_day_quantile(self._h, float(p), L.p_i32(slot)))
+        day = np.append(np.asarray(self.days, dtype=np.int32), np.int32(-1))
+        return day[slot]          # slot -1 picks the appended -1
+
+    def duration_counts(self, k, n):
+        '''[N, N] uint32: the weight of the members with exactly n listed days at or above t_k, n in 0..len(days)'''
+        out = np.empty((self.N, self.N), dtype=np.uint32)
+        L.check(self._lib.ps_peak_fetch_duration_counts(self._h, self._k(k), self._n(n, 0),
+                                                        out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def duration_prob(self, k, n):
+        '''[N, N] float64: P(at least n listed days at or above t_k), n in 1..len(days)'''
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        L.check(self._lib.ps_peak_duration_prob(self._h, self._k(k), self._n(n, 1), L.p_f64(out)))
+        return out
+
+    def duration_quantile(self, k, p):
+        '''[N, N] int32: the smallest n in 0..len(days) whose cumulative weight reaches p W (same rule)'''
+        if not 0.0 < float(p) <= 1.0:
+            raise ValueError('quantile level %r is not in (0, 1]' % (p,))
+        out = np.empty((self.N, self.N), dtype=np.int32)
+        L.check(self._lib.ps_peak_duration_quantile(self._h, self._k(k), float(p), L.p_i32(out)))
+        return out
+
+    def duration_mean(self, k):
+        '''[N, N] float64: the posterior mean of the listed days at or above t_k'''
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        L.check(self._lib.ps_peak_duration_mean(self._h, self._k(k), L.p_f64(out)))
+        return out
+
+    def profile(self, enable=None):
+        '''HIP-event time of the add and map launches: (add ms, adds, map ms, map launches); enable
+        switches it'''
+        am, an, qm, qn = C.c_double(), C.c_int64(), C.c_double(), C.c_int64()
+        L.check(self._lib.ps_peak_prof(self._h, -1 if enable is None else int(bool(enable)), C.byref(am),
+                                       C.byref(an), C.byref(qm), C.byref(qn)))
+        return am.value, an.value, qm.value, qn.value
+
+    def close(self):
+        if self._h:
+            self._lib.ps_peak_destroy(self._h)
+            self._h = L._VP()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PeakPosterior():
+    '''The peak maps of one source as posterior_predictive fills and returns them: `maps` (PeakMaps), `summary`
+    (SpreadSummary.for_projection of the peak field: E[max], its spread and P(peak >= t), output index 0),
+    `histogram` (SpreadHistogram.for_projection of it, None without quantile levels) and `levels` (the levels of
+    the saved peak-day and duration quantile maps).  `add` feeds the three in that order.'''
+
+    def __init__(self, maps, thresholds=(), levels=(0.05, 0.5, 0.95), bins=None, edges=None):
+        self.maps = maps
+        self.levels = list(levels)
+        self.summary = self.histogram = None
+        try:
+            self.summary = SpreadSummary.for_projection(maps, thresholds)
+            if bins is not None or edges is not None:
+                self.histogram = SpreadHistogram.for_projection(maps, bins, edges)
+        except BaseException:
+            self.close()
+            raise
+
+    def add(self, weight=1):
+        self.maps.add(weight)
+        self.summary.add(weight)
+        if self.histogram is not None:
+            self.histogram.add(weight)
+
+    def merge(self, other):
+        self.maps.merge(other.maps)
+        self.summary.merge(other.summary)
+        if self.histogram is not None:
+            self.histogram.merge(other.histogram)
+
+    def close(self):
+        for a in (self.histogram, self.summary, self.maps):
+            if a is not None:
+                a.close()
+
+
 def check_weights(weights, nin=None, zero_rows=False):
     '''A projection's weight matrix as a float64 [nout, nin] array, by the rules of ps_project_create: 1..32
     outputs, 1..32 inputs (nin if given), every weight finite and >= 0, and no row of all zeros unless
@@ -849,10 +1098,12 @@ class ProjectedMaps():
     thresholds), whose accessors take the output day.  `sensitivity`: the SensitivityMaps.for_projection (None
     unless asked for), which takes the output index.  `mc_error`: the MonteCarloError.for_projection pooled over
     all chains, with `rhat` (None unless asked for; while the chains run, one chain's two sequences), which takes
-    the output index.'''
+    the output index.  `peak`: the PeakPosterior of a release plan's outputs (None unless asked for), whose maps
+    take the output day.'''
 
     def __init__(self, weights, in_days, labels, summary, histogram=None, arrival=None, plan=None,
-                 sensitivity=None, mc_error=None):
+                 sensitivity=None, mc_error=None, peak=None):
+        self.peak = peak
         self.sensitivity = sensitivity
         self.mc_error = mc_error
         self.weights = weights
@@ -871,9 +1122,13 @@ class ProjectedMaps():
             self.arrival.merge(other.arrival)
         if self.sensitivity is not None:
             self.sensitivity.merge(other.sensitivity)
+        if self.peak is not None:
+            self.peak.merge(other.peak)
 
     def close(self):
         self.summary.close()
+        if self.peak is not None:
+            self.peak.close()
         if self.histogram is not None:
             self.histogram.close()
         if self.arrival is not None:
@@ -2215,6 +2470,43 @@ def save_sensitivity(outfile, sens, keys, labels):
     return block
 
 
+def save_peak(outfile, peak, quantiles=()):
+    '''outfile.npz of one PeakPosterior through save_maps: under the label `peak` the CSR triplets `peak_*` of the
+    posterior mean of the peak value, `peak_sd_*`, `peak_pexc{k}_*` (P(peak >= t_k)) and, with a histogram,
+    `peak_q{tag}_*` at the levels `quantiles`; per threshold k under the label `days{k}` the triplet
+    `days{k}_mean_*` of the posterior mean duration; dense int16 `peakday_q{tag}` model-day maps (-1: too few
+    members ever hold anything there) and `days{k}_q{tag}` duration maps at the peak's own levels (dense because
+    the CSR writer drops day 0); the count planes `peakday_counts` [days, N, N] and `days{k}_counts`
+    [days + 1, N, N] (n = 0 first; uint16 where the total weight fits, else uint32), `peak_thresholds` and
+    `peak_days` -> its block for the json'''
+    P, S, H = peak.maps, peak.summary, peak.histogram
+    nk = len(P.thresholds)
+    W = int(P.total_weight)
+    ctype = np.uint16 if W <= 0xffff else np.uint32
+    day_maps = [('', S.mean(0)), ('_sd', S.sd(0))]
+    day_maps += [('_pexc%d' % k, S.exceedance(0, k)) for k in range(len(S.thresholds))]
+    if H is not None:
+        day_maps += [('_' + quantile_tag(p), H.quantile(0, p)) for p in quantiles]
+    maps = [('peak', day_maps)]
+    extra = {'peak_thresholds': np.asarray(P.thresholds, dtype=np.float64), 'peak_days': np.asarray(P.days),
+             'peakday_counts': np.stack([P.day_counts(d) for d in P.days]).astype(ctype)}
+    for p in peak.levels:
+        extra['peakday_%s' % quantile_tag(p)] = P.day_quantile(p).astype(np.int16)
+    longest = []
+    for k in range(nk):
+        mean = P.duration_mean(k)
+        longest.append(float(mean.max()))
+        maps.append(('days%d' % k, [('_mean', mean)]))
+        for p in peak.levels:
+            extra['days%d_%s' % (k, quantile_tag(p))] = P.duration_quantile(k, p).astype(np.int16)
+        extra['days%d_counts' % k] = np.stack([P.duration_counts(k, n)
+                                               for n in range(len(P.days) + 1)]).astype(ctype)
+    save_maps(outfile, maps, extra)
+    return {'thresholds': list(P.thresholds), 'days': list(P.days), 'levels': list(peak.levels),
+            'consecutive': bool(P.consecutive), 'members': P.members, 'total_weight': P.total_weight,
+            'summary_thresholds': list(S.thresholds), 'max_mean_duration': longest}
+
+
 def mc_error_block(mc, keys, labels, prefix, maps):
     '''the maps of one pooled MonteCarloError appended to `maps` for save_maps (keys: its days or output
     indices, labels: theirs in the file behind `prefix`) -> its block for the json'''
@@ -2255,11 +2547,14 @@ class PredictiveResult():
     compare= and `compare_plan` that plan (ReleaseSites.describe()), both None where not asked for; `mc_error`:
     the MonteCarloError over the summary's days, all chains' half sequences pooled in chain order, its `rhat`
     their split R-hat maps, and `mc_plan` = dict(batches, batch_weight, sequences), both None where not asked for
-    (the projections and the plan then carry an `mc_error` of their own).'''
+    (the projections and the plan then carry an `mc_error` of their own); `peak`: the PeakPosterior over the
+    summary's days, None where not asked for (the plan then carries a `peak` of its own).'''
 
     def __init__(self, summary, rows, evaluations, failed, seconds, runs, observations, provenance, days,
                  histogram=None, quantiles=None, arrival=None, arrival_levels=None, emergence=None, exposure=None,
-                 sites=None, sensitivity=None, contrast=None, compare_plan=None, mc_error=None, mc_plan=None):
+                 sites=None, sensitivity=None, contrast=None, compare_plan=None, mc_error=None, mc_plan=None,
+                 peak=None):
+        self.peak = peak
         self.summary = summary
         self.mc_error = mc_error
         self.mc_plan = mc_plan
@@ -2319,6 +2614,8 @@ class PredictiveResult():
         per chain, the batch weight, the sequences, the used and the discarded weight and per output `ess_min`,
         `ess_median` and `rhat_max` over the cells whose threshold-0 count is > 0 (without thresholds: whose mean
         is > 0), null where there are none; `predictive.mc_error.NAME` the same for a projection or a plan.
+        Peak maps go into outfile_peak.npz (save_peak; those of a release plan into outfile_sites_peak.npz), their
+        block under `predictive.peak` (`predictive.sites.peak`) of the json.
         -> (npz path, json path)'''
         s = self.summary
         if s is None:
@@ -2398,6 +2695,11 @@ class PredictiveResult():
             if pr.sensitivity is not None:
                 meta['predictive'][name]['sensitivity'] = save_sensitivity(
                     '%s_%s_sens' % (outfile, name), pr.sensitivity, list(range(len(pr.labels))), pr.labels)
+            if pr.peak is not None:
+                meta['predictive'][name]['peak'] = save_peak('%s_%s_peak' % (outfile, name), pr.peak,
+                                                             list(self.quantiles or ()))
+        if self.peak is not None:
+            meta['predictive']['peak'] = save_peak('%s_peak' % outfile, self.peak, list(self.quantiles or ()))
         X = self.contrast
         if X is not None:
             x_levels = list(self.arrival_levels or (0.05, 0.5, 0.95))
@@ -2434,7 +2736,7 @@ class PredictiveResult():
 
 
 def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, locinfo, histogram=None,
-                   arrival=None, projected=(), plan=None, sens=None, compare=None, mc=None):
+                   arrival=None, projected=(), plan=None, sens=None, compare=None, mc=None, peak=None):
     '''one chain: evaluate every run, add it to the summary (and the histogram, the arrival maps; projected:
     (Projection, ProjectedMaps) pairs, applied and then added; plan: a (ReleaseSites, ProjectedMaps) pair, the
     models of its later release days evaluated with the base model -- a member for which any of them fails is
@@ -2443,7 +2745,8 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
     B, PlanContrast, {lag: model} of both plans' later release days) triple -- every model of that union is
     evaluated once per member, and after the plan's own adds plan B is applied and the contrast added; mc: (the
     chain's two MonteCarloError sequences, its half boundary row) -- after every summary's add the run's length
-    is split at that row and added to the sequence or sequences it falls in, those of every ProjectedMaps too)
+    is split at that row and added to the sequence or sequences it falls in, those of every ProjectedMaps too;
+    peak: the chain's PeakPosterior, fed last of the day-based accumulators -- the plan's own after the plan's)
     -> (expected per run or None, failed)'''
     expected = []
     failed = 0
@@ -2486,6 +2789,8 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
             histogram.add(length)
         if arrival is not None:
             arrival.add(length)
+        if peak is not None:
+            peak.add(length)
         for proj, maps in projected:
             proj.apply()
             maps.summary.add(length)
@@ -2502,7 +2807,7 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
                 mc_add(plan[1].mc_error, first, length)
             if plan[1].sensitivity is not None:
                 plan[1].sensitivity.add(theta, length)
-            for acc in (plan[1].histogram, plan[1].arrival):
+            for acc in (plan[1].histogram, plan[1].arrival, plan[1].peak):
                 if acc is not None:
                     acc.add(length)
         if compare is not None:
@@ -2515,7 +2820,7 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
 def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, thresholds=(), locinfo=None,
                          cell_area=None, seed=0, evaluate=None, quantiles=None, bins=DEFAULT_BINS, edges=None,
                          arrival=None, arrival_levels=(0.05, 0.5, 0.95), emergence=None, exposure=None, sites=None,
-                         sensitivity=None, compare=None, mc_error=None):
+                         sensitivity=None, compare=None, mc_error=None, peak=None):
     '''Posterior predictive spread of one or more chains (`Sampler.save` files or (trace, names)
     pairs).  Burn and thin apply per chain; consecutive rows with identical model parameters are one
     evaluation weighted by the run's length.  pop_model: one PopModel or a list -- with several, one
@@ -2553,8 +2858,22 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     straddles the half split there -- and two per projection and plan asked for; at the end every sequence is
     finished, the split R-hat maps taken over all 2 x chains sequences and the sequences merged in chain order
     into `mc_error` (`mc_error.rhat`: the R-hat maps; None with more than 8 chains or a sequence left with fewer
-    than two batches by failed members).  The contrast gets none.'''
+    than two batches by failed members).  The contrast gets none.  peak: thresholds [t_0, ...] (0..4, finite,
+    > 0, strictly increasing) or dict(thresholds=[...], levels=(0.05, 0.5, 0.95)) (check_peak; not with
+    evaluate=); each chain then also fills a PeakPosterior over the summary's days (strictly increasing, at most
+    32) with the same weights -- per member the PeakMaps add, then a SpreadSummary.for_projection of the peak
+    field (the summary's thresholds) and with quantiles a SpreadHistogram.for_projection of it (same edges) --
+    merged in chain order into `peak`; with sites= the plan gets a PeakPosterior of its own outputs, fed after
+    the plan's apply (`sites.peak`).  Emergence and exposure get none here (PeakMaps.for_projection takes them);
+    sensitivity, contrast and Monte Carlo error of the peak maps are not computed.'''
     t0 = time.perf_counter()
+    pk_thr = pk_levels = None
+    if peak is not None and peak is not False:               # bad peak arguments fail before any evaluation too
+        if evaluate is not None:
+            raise ValueError('peak= needs the device: not with evaluate=')
+        pk_thr, pk_levels = check_peak(peak)
+        if days is not None:
+            check_arrival_days(days)
     mc_batches = None
     if mc_error is not None and mc_error is not False:       # bad Monte Carlo error arguments fail first too
         if evaluate is not None:
@@ -2608,7 +2927,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     pms = list(pop_model) if isinstance(pop_model, (list, tuple)) else [pop_model]
     if evaluate is None and (not pms or pms[0] is None):
         raise ValueError('a PopModel is needed without evaluate=')
-    if a_thr and evaluate is None and days is None:
+    if (a_thr or pk_thr is not None) and evaluate is None and days is None:
         check_arrival_days(range(len(pms[0].days)))
     if evaluate is None:              # as do projections past the model's days
         plans = [(name,) + plan(arg, len(pms[0].days)) for name, arg, plan in wanted]
@@ -2617,6 +2936,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     histograms = [None] * nch
     arrivals = [None] * nch
     senses = [None] * nch
+    peaks = [None] * nch                       # per chain its PeakPosterior
     mcs = [None] * nch                         # per chain its two MonteCarloError sequences
     projected = [[] for _ in range(nch)]       # per chain (Projection, ProjectedMaps) of every plan
     site_maps = [None] * nch                   # per chain (ReleaseSites, ProjectedMaps)
@@ -2638,6 +2958,9 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                 arrivals[ci] = arr
                 sens = SensitivityMaps(pm, s_names, summ.days) if evaluate is None and s_names else None
                 senses[ci] = sens
+                if pk_thr is not None:
+                    peaks[ci] = PeakPosterior(PeakMaps(pm, pk_thr, summ.days), thresholds, pk_levels,
+                                              bins if levels else None, edges if levels else None)
                 if mc_b:
                     mcs[ci] = []
                     for _half in range(2):
@@ -2671,6 +2994,9 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                             maps.arrival = ArrivalMaps.for_projection(rs, a_thr)
                         if s_names:
                             maps.sensitivity = SensitivityMaps.for_projection(rs, s_names)
+                        if pk_thr is not None:
+                            maps.peak = PeakPosterior(PeakMaps.for_projection(rs, pk_thr), thresholds, pk_levels,
+                                                      bins if levels else None, edges if levels else None)
                         if mc_b:
                             maps.mc_error = []
                             for _half in range(2):
@@ -2681,7 +3007,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                             cmp_maps[ci] = (rb, PlanContrast(rs, rb, thresholds), late[p])
                 results[ci] = _evaluate_runs(pm, summ, rows, rl, mcols, evaluate, want_obs, locinfo, hist, arr,
                                              projected[ci], site_maps[ci], sens, cmp_maps[ci],
-                                             (mcs[ci], mc_halves[ci][0]) if mc_b else None)
+                                             (mcs[ci], mc_halves[ci][0]) if mc_b else None, peaks[ci])
         except BaseException as e:       # re-raised in the caller's thread
             errs.append((p, e))
 
@@ -2696,7 +3022,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         pms = pms[:1]
         work(0)
     if errs:
-        for s in summaries + histograms + arrivals + senses + [x for pair in mcs if pair for x in pair] + [x for pl in projected for pair in pl for x in pair] \
+        for s in summaries + histograms + arrivals + senses + peaks + [x for pair in mcs if pair for x in pair] + [x for pl in projected for pair in pl for x in pair] \
                 + [x for pair in site_maps if pair is not None for x in pair] \
                 + [x for tri in cmp_maps if tri is not None for x in tri[:2]] \
                 + [m for made in late.values() for m in made.values()]:
@@ -2707,6 +3033,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     histogram = None
     arrival_maps = None
     sens_maps = None
+    peak_maps = None
     if evaluate is None:
         summary = summaries[0]
         for s in summaries[1:]:
@@ -2726,6 +3053,11 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
             sens_maps = senses[0]
             for a in senses[1:]:
                 sens_maps.merge(a)
+                a.close()
+        if pk_thr is not None:
+            peak_maps = peaks[0]
+            for a in peaks[1:]:
+                peak_maps.merge(a)
                 a.close()
     mc_pooled = mc_desc = None
     if mc_b:
@@ -2791,7 +3123,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                            time.perf_counter() - t0, run_rec, observations, prov,
                            None if summary is None else summary.days, histogram, levels, arrival_maps,
                            a_levels if a_thr else None, merged.get('emergence'), merged.get('exposure'),
-                           merged_sites, sens_maps, contrast, compare_desc, mc_pooled, mc_desc)
+                           merged_sites, sens_maps, contrast, compare_desc, mc_pooled, mc_desc, peak_maps)
     if cell_area is not None:
         res.cell_area = float(cell_area)
     return res

@@ -14,7 +14,10 @@ posterior variance a linear dependence on them explains and the dominant paramet
 (and PREFIX_NAME_sens.npz for every projection and plan asked for); with --compare-sites (and --sites) also the
 paired contrast of the two release plans, member by member -- the posterior mean and spread of A - B, P(A > B),
 P(A < B), per threshold where A reaches it and B does not (and the reverse), and the posterior of the difference
-of the covered areas -- saved as PREFIX_contrast.npz.  Kalbar wind and
+of the covered areas -- saved as PREFIX_contrast.npz; with --peak also the posterior peak maps -- per cell the
+highest density within the window, the day of the peak and the number of days at or above each listed density
+(--peak-levels: the levels of the peak-day and duration quantile maps) -- saved as PREFIX_peak.npz (and, with
+--sites, PREFIX_sites_peak.npz for the plan).  Kalbar wind and
 LocInfo as scripts/run_mcmc.py loads them; --synthetic uses the synthetic Kalbar-like observations.
 Without --chain a short chain is sampled first (--samples) and saved next to --out.
 
@@ -23,7 +26,7 @@ Without --chain a short chain is sampled first (--samples) and saved next to --o
         [--quantiles 0.05,0.5,0.95] [--bins 1e-8,1e6,16] [--arrival 1,10] [--arrival-levels 0.05,0.5,0.95]
         [--emergence C[:d1,d2,...]] [--exposure d1,d2,...]
         [--sites 'E,N,AMOUNT[,LAG];...'] [--sites-days d1,d2,...] [--sensitivity [name,name,...]]
-        [--compare-sites 'E,N,AMOUNT[,LAG];...']
+        [--compare-sites 'E,N,AMOUNT[,LAG];...'] [--peak 1,10] [--peak-levels 0.05,0.5,0.95]
 """
 import argparse
 import json
@@ -71,6 +74,11 @@ def main():
     ap.add_argument('--mc-error', nargs='?', const=20, default=None, type=int, metavar='B',
                     help='Monte Carlo error maps (MCSE, ESS, split R-hat) from B batches per chain, B even and >= 4 '
                          '(no number: 20; default: off)')
+    ap.add_argument('--peak', nargs='?', const='', default=None,
+                    help='posterior peak maps with the listed duration thresholds, e.g. 1,10 (no list: peak value '
+                         'and peak day only; default: off)')
+    ap.add_argument('--peak-levels', default='0.05,0.5,0.95',
+                    help='levels in (0, 1] of the peak-day and duration quantile maps (with --peak)')
     args = ap.parse_args()
     if args.compare_sites and not args.sites:
         ap.error('--compare-sites names plan B and needs plan A: give --sites too')
@@ -79,8 +87,9 @@ def main():
     from parasitoids_amd import mcmc
     from parasitoids_amd.pop_model import PopModel
     from parasitoids_amd.predictive import (bin_edges, check_arrival_thresholds, check_contrast_thresholds,
-                                            check_levels, check_sens_params, contrast_plan, emergence_plan,
-                                            exposure_plan, mc_error_plan, posterior_predictive, sites_plan)
+                                            check_levels, check_peak, check_sens_params, contrast_plan,
+                                            emergence_plan, exposure_plan, mc_error_plan, posterior_predictive,
+                                            sites_plan)
     mc_error = None
     if args.mc_error is not None:        # a bad --mc-error fails before any work
         mc_error = dict(batches=args.mc_error)
@@ -95,6 +104,11 @@ def main():
     a_levels = check_levels([float(q) for q in args.arrival_levels.split(',') if q.strip()])
     if arrival:
         check_arrival_thresholds(arrival)   # as do bad --arrival thresholds
+    peak = None
+    if args.peak is not None:            # as do bad --peak thresholds or levels
+        peak = dict(thresholds=[float(t) for t in args.peak.split(',') if t.strip()],
+                    levels=[float(q) for q in args.peak_levels.split(',') if q.strip()])
+        check_peak(peak)
     emergence = exposure = None
     if args.emergence:
         cday, _, obs = args.emergence.partition(':')
@@ -150,12 +164,12 @@ def main():
                                thresholds=thr, locinfo=li, cell_area=cell_area, seed=args.seed,
                                quantiles=levels or None, bins=bins, arrival=arrival or None, arrival_levels=a_levels,
                                emergence=emergence, exposure=exposure, sites=sites, sensitivity=sens,
-                               compare=compare, mc_error=mc_error)
+                               compare=compare, mc_error=mc_error, peak=peak)
     dt = time.perf_counter() - t0
     # accumulate-kernel time: the same members once more with HIP events around every add
-    from parasitoids_amd.predictive import (ArrivalMaps, MonteCarloError, PlanContrast, Projection, ReleaseSites,
-                                            SensitivityMaps, SpreadHistogram, SpreadSummary, lagged_models,
-                                            load_chain, runs)
+    from parasitoids_amd.predictive import (ArrivalMaps, MonteCarloError, PeakMaps, PlanContrast, Projection,
+                                            ReleaseSites, SensitivityMaps, SpreadHistogram, SpreadSummary,
+                                            lagged_models, load_chain, runs)
     ME = MonteCarloError(pm, res.mc_plan['batch_weight'], None, thr) if mc_error else None
     X = SensitivityMaps(pm, sens) if sens else None
     RB = XC = SC = None
@@ -174,12 +188,15 @@ def main():
     projections = [Projection(pm, W, in_days) for W, in_days, _labels in plans]
     H = SpreadHistogram(pm, None, bins) if levels else None
     A = ArrivalMaps(pm, arrival) if arrival else None
+    PK = PeakMaps(pm, peak['thresholds']) if peak else None
     with SpreadSummary(pm, None, thr) as S:
         S.profile(True)
         if H is not None:
             H.profile(True)
         if A is not None:
             A.profile(True)
+        if PK is not None:
+            PK.profile(True)
         if X is not None:
             X.profile(True)
         if ME is not None:
@@ -213,6 +230,8 @@ def main():
                     H.add(length)
                 if A is not None:
                     A.add(length)
+                if PK is not None:
+                    PK.add(length)
                 for P in projections:
                     P.apply()
                 if RS is not None:
@@ -231,6 +250,11 @@ def main():
         a_ms, a_launches = A.profile()[:2]
         A.close()
         res.arrival.profile(True)       # every map launch of the save
+    if PK is not None:
+        pk_ms, pk_launches = PK.profile()[:2]
+        pk_bytes = PK.nbytes
+        PK.close()
+        res.peak.maps.profile(True)     # every map launch of the save
     if X is not None:
         x_ms, x_launches = X.profile()
         x_bytes = X.nbytes
@@ -277,6 +301,12 @@ def main():
         out['arrival_add_ms_per_member'] = round(a_ms / max(a_launches, 1), 4)
         out['arrival_maps_ms_total'] = round(res.arrival.profile()[2], 3)
         out['arrival_bytes'] = res.arrival.nbytes
+    if peak:
+        out['peak_ms_per_member'] = round(pk_ms / max(pk_launches, 1), 4)
+        out['peak_launches_timed'] = pk_launches
+        out['peak_maps_ms_total'] = round(res.peak.maps.profile()[2], 3)
+        out['peak_bytes'] = pk_bytes
+        out['outputs'] += ['%s_peak.npz' % args.out] + (['%s_sites_peak.npz' % args.out] if sites else [])
     if sens:
         x_per = x_ms / max(x_launches, 1)
         out['sensitivity_add_ms_per_member'] = round(x_per, 4)
@@ -330,7 +360,7 @@ def main():
         res.sensitivity.close()
     if res.mc_error is not None:
         res.mc_error.close()
-    for pr in (res.emergence, res.exposure, res.sites, res.contrast):
+    for pr in (res.emergence, res.exposure, res.sites, res.contrast, res.peak):
         if pr is not None:
             pr.close()
     for p in pms:
