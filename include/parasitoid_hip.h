@@ -820,6 +820,77 @@ void ps_peak_destroy(ps_peak* a);
 int ps_summary_add_peak(ps_summary* a, ps_peak* p, uint32_t weight);
 int ps_hist_add_peak(ps_hist* h, ps_peak* p, uint32_t weight);
 
+/* ---- joint excursion sets and contour credible bands: where all cells exceed t at the same time ----
+ * (no reference counterpart; Bolin & Lindgren 2015, on the parametric family of the marginal level sets.)  Every
+ * other map is marginal in space; the probability that all cells of a region hold >= t jointly needs each
+ * member's exceedance pattern, which the per-day maps have lost.  A handle lives on one device and holds nslot
+ * day slots (1..32, ascending) of N x N cells and 1..4 strictly increasing thresholds, each finite and > 0.
+ * For one plane (k, slot), members m in add order with weights w_m, W their sum, v the value ps_summary_add adds:
+ *   mask     B_m(c) = [v_slot^m(c) >= t_k]
+ *   count    C(c) = sum_m w_m B_m(c)                               (W x the summary's exceedance)
+ *   bounds   hi_m = max{C(c) : B_m(c) = 0}, 0 if there is no such cell with C > 0
+ *            lo_m = min{C(c) : B_m(c) = 1}, 0xffffffff if the mask is empty
+ *   above    A+(c) = sum_m w_m [hi_m < C(c)] where C(c) > 0, else 0
+ *   below    A-(c) = sum_m w_m [lo_m > C(c)]
+ *   contour  u = min(C, W - C); Ac(c) = sum_m w_m [hi_m < W - u and lo_m > u] where 2u < W, else 0
+ * and every map is (double)A / (double)W.  Member m exceeds on the whole level set {C >= n} iff hi_m < n and is
+ * below on the whole of {C <= n} iff lo_m > n, so {A+ / W >= level} is the largest level set of C on which all
+ * cells exceed t jointly with probability >= level, {A- / W >= level} its mirror image, and {Ac / W < level}
+ * the credible band of the t-contour.  State (pitch as ps_summary, nword = pitch / 64): cnt[k][slot][pitch]
+ * uint32; mask[member][k][slot][nword] uint64, bit l of word j the cell 64 j + l (pad bits 0), which grows by
+ * doubling; the weights on the host.  The counts and one fp64 plane are checked against the free device memory
+ * at create, every growth of the masks when it happens: PS_ERR_OOM before anything is allocated.  W < 2^32 - 1
+ * (the value 0xffffffff is lo's "no cell").  Counts and masks have one writer per word, the bounds are integer
+ * maxima and minima (integer atomics): neither the order of adds, nor that of merges, nor the launch
+ * configuration changes a bit; only the order of the members in the fetches follows the adds.  Every operation
+ * records an event the next one waits on, whichever stream it runs on (the solver's for add, the handle's own
+ * otherwise). */
+#define PS_EXCUR_ABOVE 0
+#define PS_EXCUR_BELOW 1
+#define PS_EXCUR_CONTOUR 2
+typedef struct ps_excur ps_excur;
+int ps_excur_create(int device, int N, int nslot, int nthr, const double* thr, ps_excur** out);
+/* room for `members` members' masks now (a growth synchronises; never shrinks) */
+int ps_excur_reserve(ps_excur* a, int64_t members);
+/* One member with weight >= 1 (arguments and refusals as ps_arrival_add, and a total weight past 2^32 - 2): one
+ * launch on the solver's stream, one thread per cell, every slot of every cell and every mask word of the member
+ * written, zeros included; no host synchronisation unless the masks have to grow.  Every descriptor is resolved
+ * first, so an add with a bad slot enqueues nothing. */
+int ps_excur_add(ps_excur* a, ps_solver* s, int nslot, const int32_t* kind, const int32_t* idx,
+                 const double* stat_scale, const double* post_scale, const int32_t* use_delta, double negval,
+                 uint32_t weight);
+/* The same for the current outputs of a projection, a release plan or the peak field of a ps_peak, as
+ * ps_arrival_add_project / ps_arrival_add_sites / ps_summary_add_peak: slot e takes Y_e (nslot must equal nout),
+ * on the handle's stream. */
+int ps_excur_add_project(ps_excur* a, ps_project* p, uint32_t weight);
+int ps_excur_add_sites(ps_excur* a, ps_sites* p, uint32_t weight);
+int ps_excur_add_peak(ps_excur* a, ps_peak* p, uint32_t weight);
+/* dst += src: the counts by an integer plane add, src's members and weights appended after dst's (a device copy);
+ * same device, N, slots and thresholds; src unchanged */
+int ps_excur_merge(ps_excur* dst, ps_excur* src);
+/* any pointer may be NULL; capacity: the members the masks hold room for; bytes: the device memory held now */
+int ps_excur_info(ps_excur* a, double* total_weight, int64_t* members, int64_t* capacity, int64_t* bytes);
+/* zero counts, W and members; the masks keep their room */
+int ps_excur_reset(ps_excur* a);
+/* hi and lo of every (member, k, slot) from the counts as they are now and the stored masks, kept on the host
+ * (synchronises).  The maps and ps_excur_fetch_bounds call it themselves; it does nothing while its result is
+ * current, and any add, merge or reset makes it stale.  PS_ERR_STATE before the first add. */
+int ps_excur_finalize(ps_excur* a);
+/* one map of plane (k, slot), what = PS_EXCUR_ABOVE / _BELOW / _CONTOUR (synchronises): the host sorts the
+ * members' bounds into a step table of breakpoints and exact integer cumulative weights, one thread per cell
+ * searches it with C (or u).  PS_ERR_STATE before the first add. */
+int ps_excur_map(ps_excur* a, int k, int slot, int what, double* out /* N*N */);
+int ps_excur_fetch_counts(ps_excur* a, int k, int slot, uint32_t* out /* N*N */);
+/* the mask words of one member, the pad bits included */
+int ps_excur_fetch_mask(ps_excur* a, int64_t member, int k, int slot, uint64_t* out /* pitch / 64 */);
+/* the bounds of plane (k, slot) and the weights, per member in add order (any pointer may be NULL) */
+int ps_excur_fetch_bounds(ps_excur* a, int k, int slot, uint32_t* hi, uint32_t* lo, uint32_t* weights /* members */);
+/* measurement: HIP-event timing of the add launches [0], the finalize launches [1] and the map launches [2];
+ * enable 1 on, 0 off, < 0 unchanged; ms[3] / launches[3] (either may be NULL) receive the totals so far
+ * (synchronises).  Finished event pairs are folded into running totals as in ps_peak_prof. */
+int ps_excur_prof(ps_excur* a, int enable, double* ms /* 3 */, int64_t* launches /* 3 */);
+void ps_excur_destroy(ps_excur* a);
+
 #ifdef __cplusplus
 }
 #endif

@@ -236,6 +236,23 @@ SIGNATURES = {
     'ps_peak_destroy': (None, [_VP]),
     'ps_summary_add_peak': (C.c_int, [_VP, _VP, C.c_uint32]),
     'ps_hist_add_peak': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_excur_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _F64P, C.POINTER(_VP)]),
+    'ps_excur_reserve': (C.c_int, [_VP, C.c_int64]),
+    'ps_excur_add': (C.c_int, [_VP, _VP, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P, C.c_double, C.c_uint32]),
+    'ps_excur_add_project': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_excur_add_sites': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_excur_add_peak': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_excur_merge': (C.c_int, [_VP, _VP]),
+    'ps_excur_info': (C.c_int, [_VP, _F64P, _I64P, _I64P, _I64P]),
+    'ps_excur_reset': (C.c_int, [_VP]),
+    'ps_excur_finalize': (C.c_int, [_VP]),
+    'ps_excur_map': (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, _F64P]),
+    'ps_excur_fetch_counts': (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(C.c_uint32)]),
+    'ps_excur_fetch_mask': (C.c_int, [_VP, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
+    'ps_excur_fetch_bounds': (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                        C.POINTER(C.c_uint32)]),
+    'ps_excur_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P]),
+    'ps_excur_destroy': (None, [_VP]),
 }
 
 _lib = None

@@ -35,6 +35,10 @@ members, the weighted counts of the day of the peak and of the number of days at
 (ps_peak_*, csrc/ps_peak.hip): the peak field feeds `SpreadSummary.for_projection` / `SpreadHistogram.for_projection`
 (E[max], its spread and quantiles), the counts give peak-day and duration probabilities, quantile maps and the
 mean duration -- max over days is not linear, so none of them can be rebuilt from the per-day maps.
+`ExcursionMaps` keeps, on the device, per threshold and day the weighted exceedance counts and per member the bit
+mask of the cells at or above the threshold (ps_excur_*, csrc/ps_excur.hip): the joint excursion sets "surely
+reached" / "surely not reached" and the credible band of the contour between them (Bolin & Lindgren 2015) --
+every other map is marginal in space and cannot say with which probability all cells of a region exceed at once.
 """
 import ctypes as C
 import json
@@ -883,6 +887,241 @@ class PeakPosterior():
                 a.close()
 
 
+def check_excursion_levels(levels):
+    '''credible levels of the excursion regions as a list of floats, each in (0.5, 1] -- above 0.5 "surely
+    reached" and "surely not reached" cannot hold at one cell; ValueError otherwise'''
+    try:
+        lv = [float(p) for p in levels]
+    except (TypeError, ValueError):
+        raise ValueError('excursion levels must be numbers, got %r' % (levels,))
+    bad = [p for p in lv if not 0.5 < p <= 1.0]
+    if bad or not lv:
+        raise ValueError('excursion levels must lie in (0.5, 1], at least one: %r' % (bad or lv,))
+    return lv
+
+
+def check_excursion(excursion):
+    '''the excursion= argument of posterior_predictive -> (thresholds, levels): a list of thresholds (1..4, by the
+    rules of check_arrival_thresholds), or dict(thresholds=[...], levels=(0.9, 0.95)) with every level in
+    (0.5, 1]; ValueError otherwise'''
+    levels = (0.9, 0.95)
+    if isinstance(excursion, dict):
+        unknown = set(excursion) - {'thresholds', 'levels'}
+        if unknown:
+            raise ValueError('excursion: unknown keys %r' % (sorted(unknown),))
+        if 'thresholds' not in excursion:
+            raise ValueError('excursion: thresholds are needed')
+        levels = excursion.get('levels', levels)
+        excursion = excursion['thresholds']
+    try:
+        thr = list(excursion)
+    except TypeError:
+        raise ValueError('excursion thresholds must be a list of numbers, got %r' % (excursion,))
+    return check_arrival_thresholds(thr), check_excursion_levels(levels)
+
+
+def level_tag(p):
+    '''the key suffix of credible level p: 0.95 -> l95, 0.975 -> l97p5'''
+    return 'l' + ('%g' % (100 * p)).replace('.', 'p')
+
+
+class ExcursionMaps():
+    '''Joint statements about where `pop_model`'s members hold >= t_k on a listed day (Bolin & Lindgren 2015, on
+    the level sets of the marginal probability): thresholds t_0 < ... < t_{K-1} (1..4, finite, > 0), model days
+    `days` (strictly increasing, at most 32, default all).  On the device per (k, day) the weighted count C of the
+    members at or above t_k (W x SpreadSummary.exceedance) and per member the bit mask of the cells where it is.
+    From them `above` F+ -- {F+ >= level} is the largest level set of C on which all cells hold >= t_k at the same
+    time with probability >= level, "surely reached" -- its mirror image `below` F- ("surely not reached") and
+    `contour` Fc, whose {Fc < level} is the credible band of the t_k-contour, the front.  Counts and bounds are
+    integers: the order of adds and merges changes no bit of a map.'''
+
+    ABOVE, BELOW, CONTOUR = 0, 1, 2
+
+    def __init__(self, pop_model, thresholds, days=None):
+        self._h = L._VP()
+        self.thresholds = check_arrival_thresholds(thresholds)
+        self.days = check_arrival_days(range(len(pop_model.days)) if days is None else days)
+        self._setup(pop_model, None)
+
+    @classmethod
+    def for_projection(cls, projection, thresholds):
+        '''Excursion maps of the outputs of `projection` (a ReleaseSites, a Projection or a PeakMaps), the slots
+        its outputs that carry weight in ascending order: `add(weight)` accumulates the outputs of its last
+        `apply()` (the peak field of its last add).  `days` holds the output labels -- the plan's output days,
+        or the output indices.'''
+        self = cls.__new__(cls)
+        self._h = L._VP()
+        self.thresholds = check_arrival_thresholds(thresholds)
+        if projection.fields_kind == 'peak':      # one output, the peak field: its `days` are those it peaks over
+            labels = [0]
+        else:
+            labels = list(getattr(projection, 'days', range(projection.nout)))
+        self.days = check_arrival_days([labels[e] for e in projection.live])
+        self._setup(projection.pm, projection)
+        return self
+
+    def _setup(self, pop_model, projection):
+        self._proj = projection
+        self._lib = L.load()
+        self.pm = pop_model
+        self.N = 2 * int(pop_model.rad_res) + 1
+        self.cell_area = (float(pop_model.rad_dist) / int(pop_model.rad_res)) ** 2
+        self.device = L.default_device() if pop_model.device is None else int(pop_model.device)
+        self.pitch = (self.N * self.N + 63) // 64 * 64
+        self.member_nbytes = len(self.thresholds) * len(self.days) * self.pitch // 8     # one member's masks
+        thr = L.f64(self.thresholds)
+        L.check(self._lib.ps_excur_create(self.device, self.N, len(self.days), len(self.thresholds), L.p_f64(thr),
+                                          C.byref(self._h)))
+        if projection is None:
+            self._kind, self._idx, self._delta = _day_slots(self.days)
+        self._slot = {d: i for i, d in enumerate(self.days)}
+
+    def reserve(self, n):
+        '''room for n members' masks now, so that no add has to grow them'''
+        L.check(self._lib.ps_excur_reserve(self._h, int(n)))
+
+    def add(self, weight=1):
+        '''Accumulate the last evaluation of the model with integer weight >= 1 (enqueued on the
+        solver's stream; no host synchronisation unless the masks grow).  On a projection or a plan: its last
+        apply, on the handle's stream.'''
+        w = int(weight)
+        if w < 1:
+            raise ValueError('weight must be a positive integer')
+        if self._proj is not None:
+            L.check(getattr(self._lib, 'ps_excur_add_' + self._proj.fields_kind)(self._h, self._proj._h, w))
+            return
+        pm = self.pm
+        _check_evaluated(pm, self.days, 'excursion maps')
+        stat, post = _day_scales(pm, self.days)
+        L.check(self._lib.ps_excur_add(self._h, pm.solver._h, len(self.days), L.p_i32(self._kind), L.p_i32(self._idx),
+                                       L.p_f64(stat), L.p_f64(post), L.p_i32(self._delta), NEGVAL, w))
+
+    def merge(self, other):
+        '''self += other (same device, domain, days and thresholds); other's members follow self's'''
+        if list(other.days) != self.days:
+            raise ValueError('excursion maps over different days')
+        L.check(self._lib.ps_excur_merge(self._h, other._h))
+
+    def reset(self):
+        L.check(self._lib.ps_excur_reset(self._h))
+
+    def _info(self):
+        w, m, c, b = C.c_double(), C.c_int64(), C.c_int64(), C.c_int64()
+        L.check(self._lib.ps_excur_info(self._h, C.byref(w), C.byref(m), C.byref(c), C.byref(b)))
+        return w.value, m.value, c.value, b.value
+
+    @property
+    def total_weight(self):
+        return self._info()[0]
+
+    @property
+    def members(self):
+        return self._info()[1]
+
+    @property
+    def capacity(self):
+        '''the members the masks hold room for'''
+        return self._info()[2]
+
+    @property
+    def nbytes(self):
+        '''the device memory the handle holds now'''
+        return self._info()[3]
+
+    def _k(self, k):
+        if not 0 <= int(k) < len(self.thresholds):
+            raise ValueError('threshold %r of %d' % (k, len(self.thresholds)))
+        return int(k)
+
+    def _slot_of(self, day):
+        if day not in self._slot:
+            raise ValueError('day %r is not in the excursion maps %s' % (day, self.days))
+        return self._slot[day]
+
+    def counts(self, k, day):
+        '''[N, N] uint32: the weight of the members at or above t_k on `day`'''
+        out = np.empty((self.N, self.N), dtype=np.uint32)
+        L.check(self._lib.ps_excur_fetch_counts(self._h, self._k(k), self._slot_of(day),
+                                                out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def mask(self, member, k, day):
+        '''[pitch / 64] uint64: the mask words of one member (in add order), bit l of word j the cell 64 j + l
+        of the flattened domain, the pad bits 0'''
+        out = np.empty(self.pitch // 64, dtype=np.uint64)
+        L.check(self._lib.ps_excur_fetch_mask(self._h, int(member), self._k(k), self._slot_of(day),
+                                              out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return out
+
+    def bounds(self, k, day):
+        '''(hi, lo, weights), each [members] uint32 in add order: hi the largest count outside the member's mask
+        (0: none), lo the smallest inside it (0xffffffff: the mask is empty)'''
+        m = self.members
+        hi, lo, w = (np.empty(m, dtype=np.uint32) for _ in range(3))
+        u32 = C.POINTER(C.c_uint32)
+        L.check(self._lib.ps_excur_fetch_bounds(self._h, self._k(k), self._slot_of(day), hi.ctypes.data_as(u32),
+                                                lo.ctypes.data_as(u32), w.ctypes.data_as(u32)))
+        return hi, lo, w
+
+    def _map(self, k, day, what):
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        L.check(self._lib.ps_excur_map(self._h, self._k(k), self._slot_of(day), what, L.p_f64(out)))
+        return out
+
+    def above(self, k, day):
+        '''[N, N] float64 F+: the posterior weight of the members at or above t_k on all of {C >= C(c)}'''
+        return self._map(k, day, self.ABOVE)
+
+    def below(self, k, day):
+        '''[N, N] float64 F-: the posterior weight of the members below t_k on all of {C <= C(c)}; 1 where no
+        member holds anything'''
+        return self._map(k, day, self.BELOW)
+
+    def contour(self, k, day):
+        '''[N, N] float64 Fc: the posterior weight of the members whose t_k-contour avoids the cell's level pair'''
+        return self._map(k, day, self.CONTOUR)
+
+    def region(self, k, day, level=0.95):
+        '''[N, N] int8: +1 where F+ >= level (surely reached), -1 where F- >= level (surely not), else 0;
+        0.5 < level <= 1'''
+        level, = check_excursion_levels([level])
+        return ((self.above(k, day) >= level).astype(np.int8) - (self.below(k, day) >= level).astype(np.int8))
+
+    def areas(self, k, day, levels):
+        '''[{'level', 'above', 'below', 'band'}, ...] in m^2: the cells x cell_area of {F+ >= level},
+        {F- >= level} and the contour's credible band {Fc < level}'''
+        levels = check_excursion_levels(levels)
+        Fp, Fm, Fc = self.above(k, day), self.below(k, day), self.contour(k, day)
+        return [{'level': p, 'above': float(int((Fp >= p).sum())) * self.cell_area,
+                 'below': float(int((Fm >= p).sum())) * self.cell_area,
+                 'band': float(int((Fc < p).sum())) * self.cell_area} for p in levels]
+
+    def profile(self, enable=None):
+        '''HIP-event time of the add, finalize and map launches: (add ms, adds, finalize ms, finalizes, map ms,
+        map launches); enable switches it'''
+        ms = np.zeros(3, dtype=np.float64)
+        n = np.zeros(3, dtype=np.int64)
+        L.check(self._lib.ps_excur_prof(self._h, -1 if enable is None else int(bool(enable)), L.p_f64(ms), L.p_i64(n)))
+        return float(ms[0]), int(n[0]), float(ms[1]), int(n[1]), float(ms[2]), int(n[2])
+
+    def close(self):
+        if self._h:
+            self._lib.ps_excur_destroy(self._h)
+            self._h = L._VP()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def check_weights(weights, nin=None, zero_rows=False):
     '''A projection's weight matrix as a float64 [nout, nin] array, by the rules of ps_project_create: 1..32
     outputs, 1..32 inputs (nin if given), every weight finite and >= 0, and no row of all zeros unless
@@ -1099,11 +1338,13 @@ class ProjectedMaps():
     unless asked for), which takes the output index.  `mc_error`: the MonteCarloError.for_projection pooled over
     all chains, with `rhat` (None unless asked for; while the chains run, one chain's two sequences), which takes
     the output index.  `peak`: the PeakPosterior of a release plan's outputs (None unless asked for), whose maps
-    take the output day.'''
+    take the output day.  `excursion`: the ExcursionMaps.for_projection of a release plan's outputs (None unless
+    asked for), whose maps take the output day.'''
 
     def __init__(self, weights, in_days, labels, summary, histogram=None, arrival=None, plan=None,
-                 sensitivity=None, mc_error=None, peak=None):
+                 sensitivity=None, mc_error=None, peak=None, excursion=None):
         self.peak = peak
+        self.excursion = excursion
         self.sensitivity = sensitivity
         self.mc_error = mc_error
         self.weights = weights
@@ -1124,9 +1365,13 @@ class ProjectedMaps():
             self.sensitivity.merge(other.sensitivity)
         if self.peak is not None:
             self.peak.merge(other.peak)
+        if self.excursion is not None:
+            self.excursion.merge(other.excursion)
 
     def close(self):
         self.summary.close()
+        if self.excursion is not None:
+            self.excursion.close()
         if self.peak is not None:
             self.peak.close()
         if self.histogram is not None:
@@ -2507,6 +2752,42 @@ def save_peak(outfile, peak, quantiles=()):
             'summary_thresholds': list(S.thresholds), 'max_mean_duration': longest}
 
 
+def save_excursion(outfile, exc, levels=(0.9, 0.95)):
+    '''outfile.npz of one ExcursionMaps through save_maps: per day of the maps, under the label `{day}`, the CSR
+    triplets `{day}_above{k}_*`, `{day}_below{k}_*` and `{day}_contour{k}_*` of the three functions; dense int8
+    `{day}_region{k}_{tag}` per level (+1 surely reached, -1 surely not, 0 neither; dense because the CSR writer
+    cannot keep a zero that means something; level_tag: l90, l95); the count planes `excur_counts`
+    [thresholds, days, N, N] (uint16 where the total weight fits, else uint32), the bounds `excur_hi` / `excur_lo`
+    [thresholds, days, members] uint32, `excur_weights` [members], `excur_thresholds` and `excur_days` -> its
+    block for the json: thresholds, days, levels, members, weight, cell area and per threshold and day the areas
+    of ExcursionMaps.areas'''
+    levels = check_excursion_levels(levels)
+    nk = len(exc.thresholds)
+    W = int(exc.total_weight)
+    ctype = np.uint16 if W <= 0xffff else np.uint32
+    maps, extra, areas = [], {}, []
+    for d in exc.days:
+        day_maps = []
+        for k in range(nk):
+            Fp, Fm, Fc = exc.above(k, d), exc.below(k, d), exc.contour(k, d)
+            day_maps += [('_above%d' % k, Fp), ('_below%d' % k, Fm), ('_contour%d' % k, Fc)]
+            for p in levels:
+                extra['%s_region%d_%s' % (d, k, level_tag(p))] = (Fp >= p).astype(np.int8) - (Fm >= p).astype(np.int8)
+        maps.append((d, day_maps))
+    for k in range(nk):
+        areas.append([{'day': d, 'levels': exc.areas(k, d, levels)} for d in exc.days])
+    extra['excur_counts'] = np.array([[exc.counts(k, d) for d in exc.days] for k in range(nk)]).astype(ctype)
+    b = [[exc.bounds(k, d) for d in exc.days] for k in range(nk)]
+    extra['excur_hi'] = np.array([[x[0] for x in row] for row in b], dtype=np.uint32)
+    extra['excur_lo'] = np.array([[x[1] for x in row] for row in b], dtype=np.uint32)
+    extra['excur_weights'] = np.asarray(b[0][0][2], dtype=np.uint32)
+    extra['excur_thresholds'] = np.asarray(exc.thresholds, dtype=np.float64)
+    extra['excur_days'] = np.asarray(exc.days)
+    save_maps(outfile, maps, extra)
+    return {'thresholds': list(exc.thresholds), 'days': list(exc.days), 'levels': levels, 'members': exc.members,
+            'total_weight': exc.total_weight, 'cell_area': exc.cell_area, 'areas': areas}
+
+
 def mc_error_block(mc, keys, labels, prefix, maps):
     '''the maps of one pooled MonteCarloError appended to `maps` for save_maps (keys: its days or output
     indices, labels: theirs in the file behind `prefix`) -> its block for the json'''
@@ -2548,13 +2829,17 @@ class PredictiveResult():
     the MonteCarloError over the summary's days, all chains' half sequences pooled in chain order, its `rhat`
     their split R-hat maps, and `mc_plan` = dict(batches, batch_weight, sequences), both None where not asked for
     (the projections and the plan then carry an `mc_error` of their own); `peak`: the PeakPosterior over the
-    summary's days, None where not asked for (the plan then carries a `peak` of its own).'''
+    summary's days, None where not asked for (the plan then carries a `peak` of its own); `excursion`: the
+    ExcursionMaps over the summary's days and `excursion_levels` the credible levels of its saved regions, both
+    None where not asked for (the plan then carries an `excursion` of its own).'''
 
     def __init__(self, summary, rows, evaluations, failed, seconds, runs, observations, provenance, days,
                  histogram=None, quantiles=None, arrival=None, arrival_levels=None, emergence=None, exposure=None,
                  sites=None, sensitivity=None, contrast=None, compare_plan=None, mc_error=None, mc_plan=None,
-                 peak=None):
+                 peak=None, excursion=None, excursion_levels=None):
         self.peak = peak
+        self.excursion = excursion
+        self.excursion_levels = excursion_levels
         self.summary = summary
         self.mc_error = mc_error
         self.mc_plan = mc_plan
@@ -2616,6 +2901,8 @@ class PredictiveResult():
         is > 0), null where there are none; `predictive.mc_error.NAME` the same for a projection or a plan.
         Peak maps go into outfile_peak.npz (save_peak; those of a release plan into outfile_sites_peak.npz), their
         block under `predictive.peak` (`predictive.sites.peak`) of the json.
+        Excursion maps go into outfile_excur.npz (save_excursion; those of a release plan into
+        outfile_sites_excur.npz), their block under `predictive.excursion` (`predictive.sites.excursion`).
         -> (npz path, json path)'''
         s = self.summary
         if s is None:
@@ -2698,6 +2985,12 @@ class PredictiveResult():
             if pr.peak is not None:
                 meta['predictive'][name]['peak'] = save_peak('%s_%s_peak' % (outfile, name), pr.peak,
                                                              list(self.quantiles or ()))
+            if pr.excursion is not None:
+                meta['predictive'][name]['excursion'] = save_excursion('%s_%s_excur' % (outfile, name), pr.excursion,
+                                                                       self.excursion_levels)
+        if self.excursion is not None:
+            meta['predictive']['excursion'] = save_excursion('%s_excur' % outfile, self.excursion,
+                                                             self.excursion_levels)
         if self.peak is not None:
             meta['predictive']['peak'] = save_peak('%s_peak' % outfile, self.peak, list(self.quantiles or ()))
         X = self.contrast
@@ -2736,7 +3029,8 @@ class PredictiveResult():
 
 
 def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, locinfo, histogram=None,
-                   arrival=None, projected=(), plan=None, sens=None, compare=None, mc=None, peak=None):
+                   arrival=None, projected=(), plan=None, sens=None, compare=None, mc=None, peak=None,
+                   excursion=None):
     '''one chain: evaluate every run, add it to the summary (and the histogram, the arrival maps; projected:
     (Projection, ProjectedMaps) pairs, applied and then added; plan: a (ReleaseSites, ProjectedMaps) pair, the
     models of its later release days evaluated with the base model -- a member for which any of them fails is
@@ -2746,8 +3040,9 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
     evaluated once per member, and after the plan's own adds plan B is applied and the contrast added; mc: (the
     chain's two MonteCarloError sequences, its half boundary row) -- after every summary's add the run's length
     is split at that row and added to the sequence or sequences it falls in, those of every ProjectedMaps too;
-    peak: the chain's PeakPosterior, fed last of the day-based accumulators -- the plan's own after the plan's)
-    -> (expected per run or None, failed)'''
+    peak: the chain's PeakPosterior, fed last of the day-based accumulators -- the plan's own after the plan's;
+    excursion: the chain's ExcursionMaps, fed the run's weight right after the summary -- the plan's own after the
+    plan's other accumulators) -> (expected per run or None, failed)'''
     expected = []
     failed = 0
 
@@ -2781,6 +3076,8 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
             expected.append(None)
             continue
         summary.add(length)
+        if excursion is not None:
+            excursion.add(length)
         if mc is not None:
             mc_add(mc[0], first, length)
         if sens is not None:
@@ -2807,7 +3104,7 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
                 mc_add(plan[1].mc_error, first, length)
             if plan[1].sensitivity is not None:
                 plan[1].sensitivity.add(theta, length)
-            for acc in (plan[1].histogram, plan[1].arrival, plan[1].peak):
+            for acc in (plan[1].histogram, plan[1].arrival, plan[1].peak, plan[1].excursion):
                 if acc is not None:
                     acc.add(length)
         if compare is not None:
@@ -2820,7 +3117,7 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
 def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, thresholds=(), locinfo=None,
                          cell_area=None, seed=0, evaluate=None, quantiles=None, bins=DEFAULT_BINS, edges=None,
                          arrival=None, arrival_levels=(0.05, 0.5, 0.95), emergence=None, exposure=None, sites=None,
-                         sensitivity=None, compare=None, mc_error=None, peak=None):
+                         sensitivity=None, compare=None, mc_error=None, peak=None, excursion=None):
     '''Posterior predictive spread of one or more chains (`Sampler.save` files or (trace, names)
     pairs).  Burn and thin apply per chain; consecutive rows with identical model parameters are one
     evaluation weighted by the run's length.  pop_model: one PopModel or a list -- with several, one
@@ -2865,8 +3162,22 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     field (the summary's thresholds) and with quantiles a SpreadHistogram.for_projection of it (same edges) --
     merged in chain order into `peak`; with sites= the plan gets a PeakPosterior of its own outputs, fed after
     the plan's apply (`sites.peak`).  Emergence and exposure get none here (PeakMaps.for_projection takes them);
-    sensitivity, contrast and Monte Carlo error of the peak maps are not computed.'''
+    sensitivity, contrast and Monte Carlo error of the peak maps are not computed.  excursion: thresholds
+    [t_0, ...] (1..4, finite, > 0, strictly increasing) or dict(thresholds=[...], levels=(0.9, 0.95)), the levels
+    in (0.5, 1] (check_excursion; not with evaluate=); each chain then also fills one ExcursionMaps over the
+    summary's days (strictly increasing, at most 32), reserved to the chain's number of runs and fed the same
+    weights after the summary, merged in chain order into `excursion` (`excursion_levels`: the levels of its saved
+    regions and areas); with sites= the plan gets an ExcursionMaps.for_projection of its own outputs
+    (`sites.excursion`).  Emergence and exposure get none here (ExcursionMaps.for_projection takes them);
+    sensitivity, contrast, Monte Carlo error and quantiles of the excursion maps are not computed.'''
     t0 = time.perf_counter()
+    ex_thr = ex_levels = None
+    if excursion is not None and excursion is not False:     # bad excursion arguments fail before any evaluation
+        if evaluate is not None:
+            raise ValueError('excursion= needs the device: not with evaluate=')
+        ex_thr, ex_levels = check_excursion(excursion)
+        if days is not None:
+            check_arrival_days(days)
     pk_thr = pk_levels = None
     if peak is not None and peak is not False:               # bad peak arguments fail before any evaluation too
         if evaluate is not None:
@@ -2927,7 +3238,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     pms = list(pop_model) if isinstance(pop_model, (list, tuple)) else [pop_model]
     if evaluate is None and (not pms or pms[0] is None):
         raise ValueError('a PopModel is needed without evaluate=')
-    if (a_thr or pk_thr is not None) and evaluate is None and days is None:
+    if (a_thr or pk_thr is not None or ex_thr) and evaluate is None and days is None:
         check_arrival_days(range(len(pms[0].days)))
     if evaluate is None:              # as do projections past the model's days
         plans = [(name,) + plan(arg, len(pms[0].days)) for name, arg, plan in wanted]
@@ -2937,6 +3248,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     arrivals = [None] * nch
     senses = [None] * nch
     peaks = [None] * nch                       # per chain its PeakPosterior
+    excurs = [None] * nch                      # per chain its ExcursionMaps
     mcs = [None] * nch                         # per chain its two MonteCarloError sequences
     projected = [[] for _ in range(nch)]       # per chain (Projection, ProjectedMaps) of every plan
     site_maps = [None] * nch                   # per chain (ReleaseSites, ProjectedMaps)
@@ -2961,6 +3273,9 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                 if pk_thr is not None:
                     peaks[ci] = PeakPosterior(PeakMaps(pm, pk_thr, summ.days), thresholds, pk_levels,
                                               bins if levels else None, edges if levels else None)
+                if ex_thr:
+                    excurs[ci] = ExcursionMaps(pm, ex_thr, summ.days)
+                    excurs[ci].reserve(len(rl))
                 if mc_b:
                     mcs[ci] = []
                     for _half in range(2):
@@ -2997,6 +3312,9 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                         if pk_thr is not None:
                             maps.peak = PeakPosterior(PeakMaps.for_projection(rs, pk_thr), thresholds, pk_levels,
                                                       bins if levels else None, edges if levels else None)
+                        if ex_thr:
+                            maps.excursion = ExcursionMaps.for_projection(rs, ex_thr)
+                            maps.excursion.reserve(len(rl))
                         if mc_b:
                             maps.mc_error = []
                             for _half in range(2):
@@ -3007,7 +3325,8 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                             cmp_maps[ci] = (rb, PlanContrast(rs, rb, thresholds), late[p])
                 results[ci] = _evaluate_runs(pm, summ, rows, rl, mcols, evaluate, want_obs, locinfo, hist, arr,
                                              projected[ci], site_maps[ci], sens, cmp_maps[ci],
-                                             (mcs[ci], mc_halves[ci][0]) if mc_b else None, peaks[ci])
+                                             (mcs[ci], mc_halves[ci][0]) if mc_b else None, peaks[ci],
+                                             excursion=excurs[ci])
         except BaseException as e:       # re-raised in the caller's thread
             errs.append((p, e))
 
@@ -3022,7 +3341,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         pms = pms[:1]
         work(0)
     if errs:
-        for s in summaries + histograms + arrivals + senses + peaks + [x for pair in mcs if pair for x in pair] + [x for pl in projected for pair in pl for x in pair] \
+        for s in summaries + histograms + arrivals + senses + peaks + excurs + [x for pair in mcs if pair for x in pair] + [x for pl in projected for pair in pl for x in pair] \
                 + [x for pair in site_maps if pair is not None for x in pair] \
                 + [x for tri in cmp_maps if tri is not None for x in tri[:2]] \
                 + [m for made in late.values() for m in made.values()]:
@@ -3034,6 +3353,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     arrival_maps = None
     sens_maps = None
     peak_maps = None
+    excur_maps = None
     if evaluate is None:
         summary = summaries[0]
         for s in summaries[1:]:
@@ -3058,6 +3378,11 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
             peak_maps = peaks[0]
             for a in peaks[1:]:
                 peak_maps.merge(a)
+                a.close()
+        if ex_thr:
+            excur_maps = excurs[0]
+            for a in excurs[1:]:
+                excur_maps.merge(a)
                 a.close()
     mc_pooled = mc_desc = None
     if mc_b:
@@ -3123,7 +3448,8 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                            time.perf_counter() - t0, run_rec, observations, prov,
                            None if summary is None else summary.days, histogram, levels, arrival_maps,
                            a_levels if a_thr else None, merged.get('emergence'), merged.get('exposure'),
-                           merged_sites, sens_maps, contrast, compare_desc, mc_pooled, mc_desc, peak_maps)
+                           merged_sites, sens_maps, contrast, compare_desc, mc_pooled, mc_desc, peak_maps,
+                           excur_maps, ex_levels if ex_thr else None)
     if cell_area is not None:
         res.cell_area = float(cell_area)
     return res

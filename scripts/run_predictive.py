@@ -17,7 +17,11 @@ P(A < B), per threshold where A reaches it and B does not (and the reverse), and
 of the covered areas -- saved as PREFIX_contrast.npz; with --peak also the posterior peak maps -- per cell the
 highest density within the window, the day of the peak and the number of days at or above each listed density
 (--peak-levels: the levels of the peak-day and duration quantile maps) -- saved as PREFIX_peak.npz (and, with
---sites, PREFIX_sites_peak.npz for the plan).  Kalbar wind and
+--sites, PREFIX_sites_peak.npz for the plan); with --excursion also the joint excursion sets -- per listed
+density and day the region all of which is reached at the same time with a given probability, the region surely
+not reached and the credible band of the contour between them (--excursion-levels: the credible levels of the saved
+regions and areas, each in (0.5, 1]) -- saved as PREFIX_excur.npz (and, with --sites, PREFIX_sites_excur.npz for the
+plan).  Kalbar wind and
 LocInfo as scripts/run_mcmc.py loads them; --synthetic uses the synthetic Kalbar-like observations.
 Without --chain a short chain is sampled first (--samples) and saved next to --out.
 
@@ -27,6 +31,7 @@ Without --chain a short chain is sampled first (--samples) and saved next to --o
         [--emergence C[:d1,d2,...]] [--exposure d1,d2,...]
         [--sites 'E,N,AMOUNT[,LAG];...'] [--sites-days d1,d2,...] [--sensitivity [name,name,...]]
         [--compare-sites 'E,N,AMOUNT[,LAG];...'] [--peak 1,10] [--peak-levels 0.05,0.5,0.95]
+        [--excursion 1,10] [--excursion-levels 0.9,0.95]
 """
 import argparse
 import json
@@ -79,6 +84,10 @@ def main():
                          'and peak day only; default: off)')
     ap.add_argument('--peak-levels', default='0.05,0.5,0.95',
                     help='levels in (0, 1] of the peak-day and duration quantile maps (with --peak)')
+    ap.add_argument('--excursion', default='', help='joint excursion sets at the listed densities, e.g. 1,10 '
+                                                    '(default: off)')
+    ap.add_argument('--excursion-levels', default='0.9,0.95',
+                    help='credible levels in (0.5, 1] of the saved excursion regions and areas (with --excursion)')
     args = ap.parse_args()
     if args.compare_sites and not args.sites:
         ap.error('--compare-sites names plan B and needs plan A: give --sites too')
@@ -87,7 +96,7 @@ def main():
     from parasitoids_amd import mcmc
     from parasitoids_amd.pop_model import PopModel
     from parasitoids_amd.predictive import (bin_edges, check_arrival_thresholds, check_contrast_thresholds,
-                                            check_levels, check_peak, check_sens_params, contrast_plan,
+                                            check_excursion, check_levels, check_peak, check_sens_params, contrast_plan,
                                             emergence_plan, exposure_plan, mc_error_plan, posterior_predictive,
                                             sites_plan)
     mc_error = None
@@ -109,6 +118,11 @@ def main():
         peak = dict(thresholds=[float(t) for t in args.peak.split(',') if t.strip()],
                     levels=[float(q) for q in args.peak_levels.split(',') if q.strip()])
         check_peak(peak)
+    excursion = None
+    if args.excursion:                   # as do bad --excursion thresholds or levels
+        excursion = dict(thresholds=[float(t) for t in args.excursion.split(',') if t.strip()],
+                         levels=[float(q) for q in args.excursion_levels.split(',') if q.strip()])
+        check_excursion(excursion)
     emergence = exposure = None
     if args.emergence:
         cday, _, obs = args.emergence.partition(':')
@@ -164,10 +178,10 @@ def main():
                                thresholds=thr, locinfo=li, cell_area=cell_area, seed=args.seed,
                                quantiles=levels or None, bins=bins, arrival=arrival or None, arrival_levels=a_levels,
                                emergence=emergence, exposure=exposure, sites=sites, sensitivity=sens,
-                               compare=compare, mc_error=mc_error, peak=peak)
+                               compare=compare, mc_error=mc_error, peak=peak, excursion=excursion)
     dt = time.perf_counter() - t0
     # accumulate-kernel time: the same members once more with HIP events around every add
-    from parasitoids_amd.predictive import (ArrivalMaps, MonteCarloError, PeakMaps, PlanContrast, Projection,
+    from parasitoids_amd.predictive import (ArrivalMaps, ExcursionMaps, MonteCarloError, PeakMaps, PlanContrast, Projection,
                                             ReleaseSites, SensitivityMaps, SpreadHistogram, SpreadSummary,
                                             lagged_models, load_chain, runs)
     ME = MonteCarloError(pm, res.mc_plan['batch_weight'], None, thr) if mc_error else None
@@ -189,6 +203,7 @@ def main():
     H = SpreadHistogram(pm, None, bins) if levels else None
     A = ArrivalMaps(pm, arrival) if arrival else None
     PK = PeakMaps(pm, peak['thresholds']) if peak else None
+    EX = ExcursionMaps(pm, excursion['thresholds']) if excursion else None
     with SpreadSummary(pm, None, thr) as S:
         S.profile(True)
         if H is not None:
@@ -197,6 +212,9 @@ def main():
             A.profile(True)
         if PK is not None:
             PK.profile(True)
+        if EX is not None:
+            EX.reserve(8)
+            EX.profile(True)
         if X is not None:
             X.profile(True)
         if ME is not None:
@@ -232,6 +250,8 @@ def main():
                     A.add(length)
                 if PK is not None:
                     PK.add(length)
+                if EX is not None:
+                    EX.add(length)
                 for P in projections:
                     P.apply()
                 if RS is not None:
@@ -255,6 +275,10 @@ def main():
         pk_bytes = PK.nbytes
         PK.close()
         res.peak.maps.profile(True)     # every map launch of the save
+    if EX is not None:
+        ex_ms, ex_launches = EX.profile()[:2]
+        EX.close()
+        res.excursion.profile(True)     # the finalize and every map launch of the save
     if X is not None:
         x_ms, x_launches = X.profile()
         x_bytes = X.nbytes
@@ -307,6 +331,16 @@ def main():
         out['peak_maps_ms_total'] = round(res.peak.maps.profile()[2], 3)
         out['peak_bytes'] = pk_bytes
         out['outputs'] += ['%s_peak.npz' % args.out] + (['%s_sites_peak.npz' % args.out] if sites else [])
+    if excursion:
+        ex_prof = res.excursion.profile()
+        out['excur_ms_per_member'] = round(ex_ms / max(ex_launches, 1), 4)
+        out['excur_launches_timed'] = ex_launches
+        out['excur_finalize_ms'] = round(ex_prof[2], 3)          # once, over all res.excursion.members members
+        out['excur_members'] = res.excursion.members
+        out['excur_maps_ms_total'] = round(ex_prof[4], 3)
+        out['excur_map_launches'] = ex_prof[5]
+        out['excur_bytes'] = res.excursion.nbytes
+        out['outputs'] += ['%s_excur.npz' % args.out] + (['%s_sites_excur.npz' % args.out] if sites else [])
     if sens:
         x_per = x_ms / max(x_launches, 1)
         out['sensitivity_add_ms_per_member'] = round(x_per, 4)
@@ -360,7 +394,7 @@ def main():
         res.sensitivity.close()
     if res.mc_error is not None:
         res.mc_error.close()
-    for pr in (res.emergence, res.exposure, res.sites, res.contrast, res.peak):
+    for pr in (res.emergence, res.exposure, res.sites, res.contrast, res.peak, res.excursion):
         if pr is not None:
             pr.close()
     for p in pms:
