@@ -891,6 +891,64 @@ int ps_excur_fetch_bounds(ps_excur* a, int k, int slot, uint32_t* hi, uint32_t* 
 int ps_excur_prof(ps_excur* a, int enable, double* ms /* 3 */, int64_t* launches /* 3 */);
 void ps_excur_destroy(ps_excur* a);
 
+/* ---- reweighted posterior summaries: the maps under new observations, without a new chain ----
+ * (no reference counterpart.)  Every other accumulator weights a member by its run length, an integer: the maps
+ * are conditional on the data the chain was fitted to.  Importance reweighting gives member m the real weight
+ * n_m L_m, L_m the likelihood of new observations under the member's own fields -- which the saved maps have
+ * lost.  A handle lives on one device and holds J scenarios (1..4), nslot slots (1..32) of N x N cells and K
+ * thresholds (0..4, each finite and > 0, strictly increasing).  Per scenario j on the device, all fp64 (pitch as
+ * ps_summary):
+ *   mean[j][slot][pitch], m2[j][slot][pitch], S[j][slot][k][pitch]   (S_k: the weight of the members with v >= t_k)
+ * and on the host W_j (a double, 0 while empty), members_j and skipped_j.  The whole block,
+ * J * (2 + K) * 8 B * nslot * pitch, is checked against the free device memory first: PS_ERR_OOM before anything
+ * is allocated.  At R = 400 (N = 801, pitch 641 664), 18 days and K = 2 one scenario takes
+ * 641 664 x 18 x 32 B = 370 MB.  The likelihoods may span hundreds of orders of magnitude: the caller keeps a
+ * log-scale reference per scenario and passes, per member, a rescale r in [0, 1] of what is held so far and a
+ * weight omega >= 0 on the new scale, so no weight ever exceeds the run length.  One thread owns a pair of
+ * cells: no atomics, the same calls in the same order give the same bits.  Every operation records an event
+ * that the next one waits on, on whatever stream it runs (the solver's for add, the handle's own otherwise). */
+typedef struct ps_wsum ps_wsum;
+int ps_wsum_create(int device, int N, int nscen, int nslot, int nthr, const double* thr, ps_wsum** out);
+/* One member from the records of solver s: the slot descriptors and the value v of a cell are those of
+ * ps_summary_add (same arguments, same value bit for bit).  rescale[nscen] (r, in [0, 1]) and omega[nscen]
+ * (>= 0, finite); nscen the handle's.  omega_j == 0: the member leaves scenario j untouched and skipped_j grows
+ * by one.  For a scenario with omega > 0, every step a statement of its own (one rounding each, but for the
+ * two statements of ps_summary_add, which contract as they do there):
+ *   host:      W = W * r;  W = W + omega;
+ *   per cell:  q = q * r;  S_k = S_k * r (every k);  d = v - m;
+ *              d != 0:  m += d omega / W,  q += omega d (v - m)        (the statements of ps_summary_add)
+ *              S_k = S_k + omega   (every k with v >= t_k)
+ * so a host loop with one rounded operation per statement reproduces mean and every S_k bit for bit, and with
+ * r = 1 and integer omega the handle holds the bits of a ps_summary fed alongside.  A value is stored only
+ * where its bits changed, and with r == 1 a pair of cells with v == m below t_0 reads its means alone.  One launch per member on the solver's stream, no host synchronisation; the thread
+ * reads the record once and walks the scenarios.  PS_ERR_BAD_ARG (every descriptor and argument is checked
+ * before anything is enqueued; a refused add changes nothing): a wrong nscen or nslot, r outside [0, 1], omega
+ * NaN, negative or infinite, a solver of another device or domain. */
+int ps_wsum_add(ps_wsum* h, ps_solver* s, int nslot, const int32_t* kind, const int32_t* idx,
+                const double* stat_scale, const double* post_scale, const int32_t* use_delta, double negval,
+                int nscen, const double* rescale, const double* omega);
+/* The same member whose values are the current outputs of a projection, a release plan or the peak field of a
+ * ps_peak, as ps_summary_add_project / _add_sites / _add_peak take them: slot e takes Y_e, on the handle's stream
+ * behind the source's last operation; its next apply waits for the read. */
+int ps_wsum_add_project(ps_wsum* h, ps_project* p, int nscen, const double* rescale, const double* omega);
+int ps_wsum_add_sites(ps_wsum* h, ps_sites* p, int nscen, const double* rescale, const double* omega);
+int ps_wsum_add_peak(ps_wsum* h, ps_peak* p, int nscen, const double* rescale, const double* omega);
+/* dst += src per scenario, same device, N, scenarios, slots and thresholds; src stays as it is.  ra[j], rb[j] in
+ * [0, 1] bring both sides to a common scale (the caller's): Wa' = Wa ra, Wb' = Wb rb, W = Wa' + Wb',
+ *   d = mean_b - mean_a;  mean = mean_a + d (Wb' / W);  m2 = m2a ra + m2b rb + d^2 (Wa' Wb' / W);  S = Sa ra + Sb rb.
+ * A scenario empty in src adds its skipped count alone; into a scenario empty in dst it is a device copy, bit
+ * for bit, W included (ra, rb unused). */
+int ps_wsum_merge(ps_wsum* dst, ps_wsum* src, const double* ra, const double* rb);
+/* per scenario (any pointer may be NULL): W, members (adds with omega > 0) and skipped (adds with omega == 0) */
+int ps_wsum_info(ps_wsum* h, double* total_weight /* nscen */, int64_t* members, int64_t* skipped);
+/* one slot of one scenario to the host (synchronises): what 0 mean, 1 variance m2 / W, 2 + k min(S_k / W, 1.0).
+ * PS_ERR_STATE while the scenario has W = 0. */
+int ps_wsum_fetch(ps_wsum* h, int scen, int slot, int what, double* out /* N*N */);
+int ps_wsum_reset(ps_wsum* h);
+/* measurement: HIP-event timing of the add launches, as ps_summary_prof */
+int ps_wsum_prof(ps_wsum* h, int enable, double* total_ms, int64_t* launches);
+void ps_wsum_destroy(ps_wsum* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -253,6 +253,18 @@ SIGNATURES = {
                                         C.POINTER(C.c_uint32)]),
     'ps_excur_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P]),
     'ps_excur_destroy': (None, [_VP]),
+    'ps_wsum_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F64P, C.POINTER(_VP)]),
+    'ps_wsum_add': (C.c_int, [_VP, _VP, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P, C.c_double, C.c_int, _F64P,
+                              _F64P]),
+    'ps_wsum_add_project': (C.c_int, [_VP, _VP, C.c_int, _F64P, _F64P]),
+    'ps_wsum_add_sites': (C.c_int, [_VP, _VP, C.c_int, _F64P, _F64P]),
+    'ps_wsum_add_peak': (C.c_int, [_VP, _VP, C.c_int, _F64P, _F64P]),
+    'ps_wsum_merge': (C.c_int, [_VP, _VP, _F64P, _F64P]),
+    'ps_wsum_info': (C.c_int, [_VP, _F64P, _I64P, _I64P]),
+    'ps_wsum_fetch': (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, _F64P]),
+    'ps_wsum_reset': (C.c_int, [_VP]),
+    'ps_wsum_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P]),
+    'ps_wsum_destroy': (None, [_VP]),
 }
 
 _lib = None

@@ -1339,12 +1339,14 @@ class ProjectedMaps():
     all chains, with `rhat` (None unless asked for; while the chains run, one chain's two sequences), which takes
     the output index.  `peak`: the PeakPosterior of a release plan's outputs (None unless asked for), whose maps
     take the output day.  `excursion`: the ExcursionMaps.for_projection of a release plan's outputs (None unless
-    asked for), whose maps take the output day.'''
+    asked for), whose maps take the output day.  `reweight`: the
+    ReweightedSummary.for_projection (None unless asked for), which takes the scenario's name and the output index.'''
 
     def __init__(self, weights, in_days, labels, summary, histogram=None, arrival=None, plan=None,
-                 sensitivity=None, mc_error=None, peak=None, excursion=None):
+                 sensitivity=None, mc_error=None, peak=None, excursion=None, reweight=None):
         self.peak = peak
         self.excursion = excursion
+        self.reweight = reweight
         self.sensitivity = sensitivity
         self.mc_error = mc_error
         self.weights = weights
@@ -1367,9 +1369,13 @@ class ProjectedMaps():
             self.peak.merge(other.peak)
         if self.excursion is not None:
             self.excursion.merge(other.excursion)
+        if self.reweight is not None:
+            self.reweight.merge(other.reweight)
 
     def close(self):
         self.summary.close()
+        if self.reweight is not None:
+            self.reweight.close()
         if self.excursion is not None:
             self.excursion.close()
         if self.peak is not None:
@@ -2570,6 +2576,455 @@ def pool_mc_error(pairs):
     return first
 
 
+# ------------------------------------------------------------------ reweighting for new observations
+MAX_REWEIGHT_SCENARIOS = 4
+MAX_REWEIGHT_SLOTS = 32    # ps_wsum: the slots of one launch's descriptors
+PROBE_KINDS = ('count', 'none', 'found')
+DEFAULT_MIN_ESS = 50.0
+
+
+def check_scenarios(scenarios):
+    '''the scenario names of a ReweightedSummary as a list of strings: 1..4 distinct names; ValueError otherwise'''
+    if isinstance(scenarios, str):
+        raise ValueError('scenarios must be a list of names, got %r' % (scenarios,))
+    try:
+        names = [str(n) for n in scenarios]
+    except TypeError:
+        raise ValueError('scenarios must be a list of names, got %r' % (scenarios,))
+    if not 1 <= len(names) <= MAX_REWEIGHT_SCENARIOS:
+        raise ValueError('%d reweighting scenarios; 1..%d fit one handle' % (len(names), MAX_REWEIGHT_SCENARIOS))
+    if len(set(names)) != len(names):
+        raise ValueError('duplicate scenario names in %r' % (names,))
+    return names
+
+
+def check_probes(probes, rad_dist, rad_res, ndays=None):
+    '''Probe observations as a list of dicts, one per probe in the order given.  A probe is
+    (east_m, north_m, day, kind, rate[, n]): the position in metres from the domain centre, resolved to a cell as
+    check_sites resolves a site (col = rad_res + round(east / res), row = rad_res - round(north / res),
+    res = rad_dist / rad_res; the cell has to lie inside the domain), a model day (a whole number >= 0, below
+    ndays if given), the kind -- 'count' (n wasps found, a whole number >= 0), 'none' (looked, nothing found) or
+    'found' (at least one found) -- and rate, finite and > 0: the expected number found per wasp in the cell.
+    rad_res=None skips the cells (no model at hand).  ValueError otherwise.'''
+    try:
+        rows = [tuple(p) for p in probes]
+    except TypeError:
+        raise ValueError('probes must be a list of (east_m, north_m, day, kind, rate[, n]), got %r' % (probes,))
+    if not rows:
+        raise ValueError('a probe scenario needs at least one probe')
+    out = []
+    for k, p in enumerate(rows):
+        if len(p) not in (5, 6):
+            raise ValueError('probe %d: (east_m, north_m, day, kind, rate[, n]) expected, got %r' % (k, p))
+        kind = p[3]
+        if kind not in PROBE_KINDS:
+            raise ValueError('probe %d: kind %r is not one of %r' % (k, kind, PROBE_KINDS))
+        try:
+            east, north, rate = float(p[0]), float(p[1]), float(p[4])
+            if int(p[2]) != p[2]:
+                raise ValueError
+            day = int(p[2])
+        except (TypeError, ValueError):
+            raise ValueError('probe %d: numbers and a whole model day expected, got %r' % (k, p))
+        if not (np.isfinite(east) and np.isfinite(north)):
+            raise ValueError('probe %d: position %r is not finite' % (k, p[:2]))
+        if day < 0 or (ndays is not None and day >= ndays):
+            raise ValueError('probe %d: day %d is not a model day%s' % (k, day, '' if ndays is None else
+                                                                       ' (0..%d)' % (ndays - 1)))
+        if not (np.isfinite(rate) and rate > 0):
+            raise ValueError('probe %d: rate %r is not finite and > 0' % (k, p[4]))
+        n = None
+        if kind == 'count':
+            if len(p) != 6:
+                raise ValueError("probe %d: a 'count' probe needs the number found" % k)
+            try:
+                if int(p[5]) != p[5] or int(p[5]) < 0:
+                    raise ValueError
+                n = int(p[5])
+            except (TypeError, ValueError):
+                raise ValueError('probe %d: the number found must be a whole number >= 0, got %r' % (k, p[5]))
+        elif len(p) == 6 and p[5] is not None:
+            raise ValueError('probe %d: a %r probe takes no number found' % (k, kind))
+        rec = {'east': east, 'north': north, 'day': day, 'kind': kind, 'rate': rate, 'n': n}
+        if rad_res is not None:
+            res = float(rad_dist) / int(rad_res)
+            rec['col'] = int(rad_res) + int(np.around(east / res))
+            rec['row'] = int(rad_res) - int(np.around(north / res))
+            if not (0 <= rec['row'] <= 2 * int(rad_res) and 0 <= rec['col'] <= 2 * int(rad_res)):
+                raise ValueError('probe %d: cell (%d, %d) lies outside the %d x %d domain'
+                                 % (k, rec['row'], rec['col'], 2 * int(rad_res) + 1, 2 * int(rad_res) + 1))
+        out.append(rec)
+    return out
+
+
+def probe_loglik(kind, rate, v, n=None):
+    '''log-likelihood of one probe where the member holds the density v (what PopModel.gather_days returns at the
+    probe's cell and day), mu = rate * v, by the math module:
+    'count': n log(mu) - mu - lgamma(n + 1), at mu = 0: 0 if n == 0 else -inf;  'none': -mu;
+    'found': log(1 - exp(-mu)), at mu = 0: -inf -- as log(-expm1(-mu)) up to mu = log 2 and as log1p(-exp(-mu))
+    above it, where 1 - exp(-mu) is close to 1 and the first form would lose the digits of a small result'''
+    import math
+    mu = float(rate) * float(v)
+    if kind == 'none':
+        return -mu
+    if kind == 'found':
+        if mu == 0.0:
+            return -math.inf
+        return math.log(-math.expm1(-mu)) if mu <= math.log(2.0) else math.log1p(-math.exp(-mu))
+    if kind == 'count':
+        if mu == 0.0:
+            return 0.0 if n == 0 else -math.inf
+        return n * math.log(mu) - mu - math.lgamma(n + 1)
+    raise ValueError('kind %r is not one of %r' % (kind, PROBE_KINDS))
+
+
+def probes_loglik(probes, values):
+    '''the sum of probe_loglik over checked probes and their values, in list order, from 0.0'''
+    lam = 0.0
+    for p, v in zip(probes, values):
+        lam = lam + probe_loglik(p['kind'], p['rate'], v, p['n'])
+    return lam
+
+
+def run_log_weight(row_log_weights):
+    '''the log-weight of a run of rows sharing one member: mx + log(sum(exp(l - mx)) / n), mx their maximum (the
+    log of the rows' mean weight); -inf if every row is -inf; equal rows give their value exactly'''
+    import math
+    ls = [float(v) for v in row_log_weights]
+    mx = max(ls)
+    if mx == -math.inf:
+        return -math.inf
+    s = 0.0
+    for v in ls:
+        s = s + math.exp(v - mx)
+    return mx + math.log(s / len(ls))
+
+
+def reweight_diagnostics(row_log_weights):
+    '''what a scenario's weights did to the sample, from the log-weight of every row (of the members that
+    evaluated): rows; skipped_rows, those whose weight is 0 next to the largest; ess, the Kish effective sample
+    size (sum e)^2 / sum e^2; max_share, the largest row's share of the total; log_mean_weight =
+    logsumexp - log(rows), for a probe scenario the log predictive density of the new observations.  With every
+    row at -inf: ess 0, max_share nan, log_mean_weight -inf.'''
+    l = np.asarray(row_log_weights, dtype=np.float64).ravel()
+    rows = int(l.size)
+    mx = l.max() if rows else -np.inf
+    if not np.isfinite(mx):
+        return {'rows': rows, 'skipped_rows': rows, 'ess': 0.0, 'max_share': float('nan'),
+                'log_mean_weight': float('-inf')}
+    e = np.exp(l - mx)
+    s1, s2 = float(e.sum()), float((e * e).sum())
+    return {'rows': rows, 'skipped_rows': int((e == 0.0).sum()), 'ess': s1 * s1 / s2, 'max_share': float(e.max()) / s1,
+            'log_mean_weight': float(mx + np.log(s1) - np.log(rows))}
+
+
+def check_reweight(reweight, rad_dist=None, rad_res=None, ndays=None):
+    '''the reweight= argument of posterior_predictive -> dict(names, kinds, probes, given, log_weights, min_ess):
+    {name: dict(probes=[...]) or dict(log_weights=[one 1-D array per chain]), ...} with 1..4 names, and
+    optionally 'options': dict(min_ess=50).  Per scenario `kinds` is 'probes' or 'log_weights', `probes` the
+    checked probes (check_probes) or None, `given` the probes as given, `log_weights` the float64 arrays or None
+    (every entry finite or -inf).  ValueError otherwise.'''
+    if not isinstance(reweight, dict):
+        raise ValueError('reweight must be a dict {name: dict(probes=[...]) or dict(log_weights=[...])}, got %r'
+                         % (reweight,))
+    specs = dict(reweight)
+    options = specs.pop('options', None) or {}
+    if not isinstance(options, dict) or set(options) - {'min_ess'}:
+        raise ValueError("reweight: 'options' takes dict(min_ess=...), got %r" % (options,))
+    min_ess = float(options.get('min_ess', DEFAULT_MIN_ESS))
+    if not (np.isfinite(min_ess) and min_ess >= 0):
+        raise ValueError('reweight: min_ess %r is not finite and >= 0' % (options.get('min_ess'),))
+    names = check_scenarios(list(specs))
+    out = {'names': names, 'kinds': [], 'probes': [], 'given': [], 'log_weights': [], 'min_ess': min_ess}
+    for name in names:
+        spec = specs[name]
+        if not isinstance(spec, dict) or len(set(spec) & {'probes', 'log_weights'}) != 1 \
+                or set(spec) - {'probes', 'log_weights'}:
+            raise ValueError('reweight[%r] must be dict(probes=[...]) or dict(log_weights=[...]), got %r'
+                             % (name, spec))
+        if 'probes' in spec:
+            try:
+                checked = check_probes(spec['probes'], rad_dist, rad_res, ndays)
+            except ValueError as e:
+                raise ValueError('reweight[%r]: %s' % (name, e))
+            out['kinds'].append('probes')
+            out['probes'].append(checked)
+            out['given'].append([list(p) for p in spec['probes']])
+            out['log_weights'].append(None)
+        else:
+            try:
+                arrs = [np.array(a, dtype=np.float64) for a in spec['log_weights']]
+            except (TypeError, ValueError):
+                raise ValueError('reweight[%r]: log_weights must be a list of one 1-D array per chain' % name)
+            for c, a in enumerate(arrs):
+                if a.ndim != 1:
+                    raise ValueError('reweight[%r]: the log-weights of chain %d are not 1-D' % (name, c))
+                if np.isnan(a).any() or (a == np.inf).any():
+                    raise ValueError('reweight[%r]: the log-weights of chain %d hold NaN or +inf' % (name, c))
+            out['kinds'].append('log_weights')
+            out['probes'].append(None)
+            out['given'].append(None)
+            out['log_weights'].append(arrs)
+    return out
+
+
+def check_reweight_rows(plan, chain_rows):
+    '''the row log-weights of a checked reweight= against the chains' rows after burn and thin; ValueError on a
+    wrong number of chains or rows'''
+    for name, arrs in zip(plan['names'], plan['log_weights']):
+        if arrs is None:
+            continue
+        if len(arrs) != len(chain_rows):
+            raise ValueError('reweight[%r]: log-weights for %d chains, %d chains given' % (name, len(arrs),
+                                                                                           len(chain_rows)))
+        for c, (a, n) in enumerate(zip(arrs, chain_rows)):
+            if a.size != n:
+                raise ValueError('reweight[%r]: %d log-weights for chain %d, which has %d rows after burn and thin'
+                                 % (name, a.size, c, n))
+
+
+class ReweightedSummary():
+    '''The maps of a SpreadSummary under up to 4 reweighting scenarios at once, on the device (ps_wsum_*,
+    csrc/ps_wsum.hip): member m counts with the real weight weight_m exp(lambda_m), lambda_m the log-weight the
+    caller gives per scenario -- the log-likelihood of new observations under the member (probes_loglik), or any
+    other per-member log-weight.  scenarios: 1..4 distinct names; days, thresholds as SpreadSummary (at most 32
+    days; thresholds finite, > 0, strictly increasing).  The class keeps the log scale: per scenario `ref`, the
+    largest log-weight so far (-inf while the scenario is empty), so that the device only sees weights
+    <= weight_m however many orders of magnitude the likelihoods span.  A scenario whose log-weights are all 0
+    holds the bits of a SpreadSummary fed alongside.  Importance reweighting degrades as the new data disagree with
+    the posterior: watch reweight_diagnostics' ess.'''
+
+    def __init__(self, pop_model, scenarios, days=None, thresholds=()):
+        self._h = L._VP()
+        days = list(range(len(pop_model.days)) if days is None else days)
+        if not days or min(days) < 0:
+            raise ValueError('days must be a non-empty list of model days >= 0')
+        self._setup(pop_model, scenarios, days, thresholds, None)
+
+    @classmethod
+    def for_projection(cls, source, scenarios, thresholds=()):
+        '''Reweighted maps of the outputs of `source` (a Projection, a ReleaseSites or a PeakMaps), one slot per
+        output: `add(log_weights, weight)` accumulates the outputs of its last `apply()`, and the accessors take
+        the output index where the day-based maps take a day.'''
+        self = cls.__new__(cls)
+        self._h = L._VP()
+        nout = getattr(source, 'nout', 1)
+        self._setup(source.pm, scenarios, list(range(nout)), thresholds, source)
+        return self
+
+    def _setup(self, pop_model, scenarios, days, thresholds, projection):
+        import math
+        self.scenarios = check_scenarios(scenarios)
+        self.thresholds = check_peak_thresholds(thresholds)
+        self._lib = L.load()
+        self.pm = pop_model
+        self.days = days
+        self.N = 2 * int(pop_model.rad_res) + 1
+        self.device = L.default_device() if pop_model.device is None else int(pop_model.device)
+        self._proj = projection
+        keys = days if projection is None else getattr(projection, 'live', days)
+        self._slot = {d: i for i, d in enumerate(keys)}
+        self._n = len(self._slot)
+        if not 1 <= self._n <= MAX_REWEIGHT_SLOTS:
+            raise ValueError('%d slots; 1..%d fit one handle' % (self._n, MAX_REWEIGHT_SLOTS))
+        self.ref = [-math.inf] * len(self.scenarios)
+        pitch = (self.N * self.N + 63) // 64 * 64
+        self.nbytes = len(self.scenarios) * (2 + len(self.thresholds)) * 8 * self._n * pitch
+        thr = L.f64(self.thresholds if self.thresholds else [0.0])
+        L.check(self._lib.ps_wsum_create(self.device, self.N, len(self.scenarios), self._n, len(self.thresholds),
+                                         L.p_f64(thr), C.byref(self._h)))
+        if projection is None:
+            self._kind, self._idx, self._delta = _day_slots(self.days)
+
+    def _j(self, name):
+        if name not in self.scenarios:
+            raise ValueError('scenario %r is not one of %r' % (name, self.scenarios))
+        return self.scenarios.index(name)
+
+    def scale(self, log_weights, weight=1):
+        '''(r, omega, ref) per scenario that add() would pass for these log-weights, without adding:
+        lambda = -inf: omega 0;  an empty scenario: ref = lambda, r 1, omega = weight;  lambda > ref:
+        r = exp(ref - lambda), ref = lambda, omega = weight;  else r 1, omega = weight * exp(lambda - ref), which
+        may underflow to 0 (the member is then skipped).  ValueError for NaN, +inf or a wrong number.'''
+        import math
+        if isinstance(log_weights, dict):
+            if set(log_weights) != set(self.scenarios):
+                raise ValueError('log-weights for %r, the scenarios are %r' % (sorted(log_weights), self.scenarios))
+            log_weights = [log_weights[n] for n in self.scenarios]
+        try:
+            lam = [float(v) for v in log_weights]
+        except TypeError:
+            raise ValueError('log_weights must be one number per scenario, got %r' % (log_weights,))
+        if len(lam) != len(self.scenarios):
+            raise ValueError('%d log-weights given, the handle has %d scenarios' % (len(lam), len(self.scenarios)))
+        w = float(weight)
+        if not (math.isfinite(w) and w > 0):
+            raise ValueError('weight must be finite and > 0')
+        r, om, ref = [], [], []
+        for lj, rj in zip(lam, self.ref):
+            if math.isnan(lj) or lj == math.inf:
+                raise ValueError('log-weight %r is NaN or +inf' % (lj,))
+            if lj == -math.inf:
+                r.append(1.0), om.append(0.0), ref.append(rj)
+            elif rj == -math.inf:
+                r.append(1.0), om.append(w), ref.append(lj)
+            elif lj > rj:
+                r.append(math.exp(rj - lj)), om.append(w), ref.append(lj)
+            else:
+                r.append(1.0), om.append(w * math.exp(lj - rj)), ref.append(rj)
+        return r, om, ref
+
+    def add(self, log_weights, weight=1):
+        '''Accumulate the last evaluation of the model (on a projection, a plan or a peak: its last apply) with
+        weight `weight` (the run length) times exp(log_weights[j]) in scenario j; enqueued, no host
+        synchronisation.  A refused add changes nothing.'''
+        r, om, ref = self.scale(log_weights, weight)
+        n = len(self.scenarios)
+        if self._proj is not None:
+            L.check(getattr(self._lib, 'ps_wsum_add_' + self._proj.fields_kind)(
+                self._h, self._proj._h, n, L.p_f64(L.f64(r)), L.p_f64(L.f64(om))))
+        else:
+            _check_evaluated(self.pm, self.days, 'reweighted summary')
+            stat, post = _day_scales(self.pm, self.days)
+            L.check(self._lib.ps_wsum_add(self._h, self.pm.solver._h, self._n, L.p_i32(self._kind), L.p_i32(self._idx),
+                                          L.p_f64(stat), L.p_f64(post), L.p_i32(self._delta), NEGVAL, n,
+                                          L.p_f64(L.f64(r)), L.p_f64(L.f64(om))))
+        # a member whose weight underflowed is skipped and moves no reference
+        self.ref = [b if o > 0.0 else a for a, b, o in zip(self.ref, ref, om)]
+
+    def merge(self, other):
+        '''self += other (same device, domain, scenarios, days and thresholds), both brought to the larger of the
+        two references per scenario: L = max(ref_a, ref_b), ra = exp(ref_a - L), rb = exp(ref_b - L)'''
+        import math
+        if list(other.days) != self.days or other._slot != self._slot or other.scenarios != self.scenarios:
+            raise ValueError('reweighted summaries over different days or scenarios')
+        ra, rb, ref = [], [], []
+        for a, b in zip(self.ref, other.ref):
+            top = max(a, b)
+            ref.append(top)
+            ra.append(1.0 if top == -math.inf else math.exp(a - top))
+            rb.append(1.0 if top == -math.inf else math.exp(b - top))
+        L.check(self._lib.ps_wsum_merge(self._h, other._h, L.p_f64(L.f64(ra)), L.p_f64(L.f64(rb))))
+        self.ref = ref
+
+    def reset(self):
+        import math
+        L.check(self._lib.ps_wsum_reset(self._h))
+        self.ref = [-math.inf] * len(self.scenarios)
+
+    def _info(self):
+        n = len(self.scenarios)
+        w, m, s = np.zeros(n), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+        L.check(self._lib.ps_wsum_info(self._h, L.p_f64(w), m.ctypes.data_as(C.POINTER(C.c_int64)),
+                                       s.ctypes.data_as(C.POINTER(C.c_int64))))
+        return w, m, s
+
+    def total_weight(self, name):
+        '''W of the scenario on its own scale exp(ref)'''
+        return float(self._info()[0][self._j(name)])
+
+    def log_total_weight(self, name):
+        '''ref + log W: the log of the scenario's total weight (-inf while it is empty)'''
+        import math
+        j = self._j(name)
+        W = float(self._info()[0][j])
+        return -math.inf if W == 0.0 else self.ref[j] + math.log(W)
+
+    def members(self, name):
+        return int(self._info()[1][self._j(name)])
+
+    def skipped(self, name):
+        return int(self._info()[2][self._j(name)])
+
+    def _fetch(self, name, day, what):
+        j = self._j(name)
+        if day not in self._slot:
+            if self._proj is not None and day in self.days:      # an output without weight
+                return np.zeros((self.N, self.N), dtype=np.float64)
+            raise ValueError('day %r is not in the reweighted summary %s' % (day, self.days))
+        return self.fetch_slot(j, self._slot[day], what)
+
+    def fetch_slot(self, scen, slot, what):
+        '''raw access by scenario and slot index (0 mean, 1 variance, 2 + k exceedance)'''
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        L.check(self._lib.ps_wsum_fetch(self._h, int(scen), int(slot), int(what), L.p_f64(out)))
+        return out
+
+    def mean(self, name, day):
+        return self._fetch(name, day, 0)
+
+    def variance(self, name, day):
+        return self._fetch(name, day, 1)
+
+    def sd(self, name, day):
+        return np.sqrt(self.variance(name, day))
+
+    def exceedance(self, name, day, k):
+        '''P(population >= thresholds[k]) per cell under the scenario'''
+        if not 0 <= k < len(self.thresholds):
+            raise ValueError('threshold %r of %d' % (k, len(self.thresholds)))
+        return self._fetch(name, day, 2 + k)
+
+    def profile(self, enable=None):
+        '''HIP-event time of the add launches: (total ms, launches); enable switches it'''
+        ms, n = C.c_double(), C.c_int64()
+        L.check(self._lib.ps_wsum_prof(self._h, -1 if enable is None else int(bool(enable)), C.byref(ms),
+                                       C.byref(n)))
+        return ms.value, n.value
+
+    def close(self):
+        if self._h:
+            self._lib.ps_wsum_destroy(self._h)
+            self._h = L._VP()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _ReweightFeed():
+    '''one chain's side of posterior_predictive(reweight=): the log-weights of every run, by one device gather of
+    all probes of all scenarios, and the row log-weights the diagnostics are taken from'''
+
+    def __init__(self, plan, chain):
+        self.plan = plan
+        self.chain = chain
+        self.rows = [[] for _ in plan['names']]        # per scenario the log-weight of every evaluated row
+        flat = [p for ps in plan['probes'] if ps is not None for p in ps]
+        self.days = sorted({p['day'] for p in flat})
+        self.prow = L.i32([p['row'] for p in flat])
+        self.pcol = L.i32([p['col'] for p in flat])
+        self.pday = [self.days.index(p['day']) for p in flat]
+
+    def log_weights(self, pm, first, length):
+        lam = []
+        vals = None
+        if self.pday:
+            got = pm.gather_days(self.days, self.prow, self.pcol)
+            vals = [float(got[d, k]) for k, d in enumerate(self.pday)]
+        at = 0
+        for j, kind in enumerate(self.plan['kinds']):
+            if kind == 'probes':
+                ps = self.plan['probes'][j]
+                lj = probes_loglik(ps, vals[at:at + len(ps)])
+                at += len(ps)
+                self.rows[j].extend([lj] * length)
+            else:
+                l = self.plan['log_weights'][j][self.chain][first:first + length]
+                lj = run_log_weight(l)
+                self.rows[j].extend(float(v) for v in l)
+            lam.append(lj)
+        return lam
+
+
 # ------------------------------------------------------------------ traces
 def model_names():
     return [m[0] for m in mcmc.MODEL_BLOCK]
@@ -2715,6 +3170,19 @@ def save_sensitivity(outfile, sens, keys, labels):
     return block
 
 
+def save_reweight(outfile, rw, keys, labels):
+    '''outfile.npz of one ReweightedSummary through save_maps (keys: its days or output indices, labels: theirs in
+    the file): per scenario index j and label the CSR triplets `s{j}_{label}_*` of the reweighted mean,
+    `s{j}_{label}_sd_*` and `s{j}_{label}_pexc{k}_*`; `scenarios` the names, `labels` the labels'''
+    maps = []
+    for j, name in enumerate(rw.scenarios):
+        for k, label in zip(keys, labels):
+            day_maps = [('', rw.mean(name, k)), ('_sd', rw.sd(name, k))]
+            day_maps += [('_pexc%d' % t, rw.exceedance(name, k, t)) for t in range(len(rw.thresholds))]
+            maps.append(('s%d_%s' % (j, label), day_maps))
+    save_maps(outfile, maps, {'scenarios': np.array(rw.scenarios), 'labels': np.array(labels)})
+
+
 def save_peak(outfile, peak, quantiles=()):
     '''outfile.npz of one PeakPosterior through save_maps: under the label `peak` the CSR triplets `peak_*` of the
     posterior mean of the peak value, `peak_sd_*`, `peak_pexc{k}_*` (P(peak >= t_k)) and, with a histogram,
@@ -2831,15 +3299,21 @@ class PredictiveResult():
     (the projections and the plan then carry an `mc_error` of their own); `peak`: the PeakPosterior over the
     summary's days, None where not asked for (the plan then carries a `peak` of its own); `excursion`: the
     ExcursionMaps over the summary's days and `excursion_levels` the credible levels of its saved regions, both
-    None where not asked for (the plan then carries an `excursion` of its own).'''
+    None where not asked for (the plan then carries an `excursion` of its own); `reweight`: the ReweightedSummary
+    over the summary's days and thresholds, and `reweight_info` = dict(names, probes -- as given, None for a
+    scenario of row log-weights --, min_ess, diagnostics: {name: reweight_diagnostics + members, skipped,
+    log_total_weight}), both None where not asked for (the projections and the plan then carry a `reweight` of
+    their own).'''
 
     def __init__(self, summary, rows, evaluations, failed, seconds, runs, observations, provenance, days,
                  histogram=None, quantiles=None, arrival=None, arrival_levels=None, emergence=None, exposure=None,
                  sites=None, sensitivity=None, contrast=None, compare_plan=None, mc_error=None, mc_plan=None,
-                 peak=None, excursion=None, excursion_levels=None):
+                 peak=None, excursion=None, excursion_levels=None, reweight=None, reweight_info=None):
         self.peak = peak
         self.excursion = excursion
         self.excursion_levels = excursion_levels
+        self.reweight = reweight
+        self.reweight_info = reweight_info
         self.summary = summary
         self.mc_error = mc_error
         self.mc_plan = mc_plan
@@ -3012,6 +3486,17 @@ class PredictiveResult():
                 'plan_b': self.compare_plan, 'thresholds': list(X.thresholds), 'labels': list(X.labels),
                 'members': X.members, 'total_weight': X.total_weight, 'cell_area': X.cell_area, 'levels': x_levels,
                 'coverage_difference': [X.coverage_difference(k, x_levels) for k in range(nk)]}
+        R = self.reweight
+        if R is not None:
+            labels = [s.pm.days[d] if d < len(s.pm.days) else d for d in s.days]
+            save_reweight('%s_reweight' % outfile, R, s.days, labels)
+            meta['predictive']['reweight'] = dict(self.reweight_info or {})
+            meta['predictive']['reweight'].update({'days': list(s.days), 'labels': labels,
+                                                   'thresholds': list(R.thresholds)})
+            for name, pr in (('emergence', self.emergence), ('exposure', self.exposure), ('sites', self.sites)):
+                if pr is not None and pr.reweight is not None:
+                    save_reweight('%s_%s_reweight' % (outfile, name), pr.reweight, list(range(len(pr.labels))),
+                                  pr.labels)
         if self.mc_error is not None:
             mmaps = []
             labels = [s.pm.days[d] if d < len(s.pm.days) else d for d in s.days]
@@ -3030,7 +3515,7 @@ class PredictiveResult():
 
 def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, locinfo, histogram=None,
                    arrival=None, projected=(), plan=None, sens=None, compare=None, mc=None, peak=None,
-                   excursion=None):
+                   excursion=None, reweight=None):
     '''one chain: evaluate every run, add it to the summary (and the histogram, the arrival maps; projected:
     (Projection, ProjectedMaps) pairs, applied and then added; plan: a (ReleaseSites, ProjectedMaps) pair, the
     models of its later release days evaluated with the base model -- a member for which any of them fails is
@@ -3042,7 +3527,9 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
     is split at that row and added to the sequence or sequences it falls in, those of every ProjectedMaps too;
     peak: the chain's PeakPosterior, fed last of the day-based accumulators -- the plan's own after the plan's;
     excursion: the chain's ExcursionMaps, fed the run's weight right after the summary -- the plan's own after the
-    plan's other accumulators) -> (expected per run or None, failed)'''
+    plan's other accumulators; reweight: (the chain's ReweightedSummary, its _ReweightFeed) -- right after the
+    summary the run's log-weights are taken, by one gather of all probes, and the member added with them and the
+    run's length, to every ProjectedMaps' own after its summary too) -> (expected per run or None, failed)'''
     expected = []
     failed = 0
 
@@ -3076,6 +3563,10 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
             expected.append(None)
             continue
         summary.add(length)
+        lam = None
+        if reweight is not None:
+            lam = reweight[1].log_weights(pm, first, length)
+            reweight[0].add(lam, length)
         if excursion is not None:
             excursion.add(length)
         if mc is not None:
@@ -3091,6 +3582,8 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
         for proj, maps in projected:
             proj.apply()
             maps.summary.add(length)
+            if maps.reweight is not None:
+                maps.reweight.add(lam, length)
             if maps.mc_error is not None:
                 mc_add(maps.mc_error, first, length)
             if maps.sensitivity is not None:
@@ -3100,6 +3593,8 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
         if plan is not None:
             plan[0].apply()
             plan[1].summary.add(length)
+            if plan[1].reweight is not None:
+                plan[1].reweight.add(lam, length)
             if plan[1].mc_error is not None:
                 mc_add(plan[1].mc_error, first, length)
             if plan[1].sensitivity is not None:
@@ -3117,7 +3612,7 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
 def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, thresholds=(), locinfo=None,
                          cell_area=None, seed=0, evaluate=None, quantiles=None, bins=DEFAULT_BINS, edges=None,
                          arrival=None, arrival_levels=(0.05, 0.5, 0.95), emergence=None, exposure=None, sites=None,
-                         sensitivity=None, compare=None, mc_error=None, peak=None, excursion=None):
+                         sensitivity=None, compare=None, mc_error=None, peak=None, excursion=None, reweight=None):
     '''Posterior predictive spread of one or more chains (`Sampler.save` files or (trace, names)
     pairs).  Burn and thin apply per chain; consecutive rows with identical model parameters are one
     evaluation weighted by the run's length.  pop_model: one PopModel or a list -- with several, one
@@ -3169,8 +3664,33 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     weights after the summary, merged in chain order into `excursion` (`excursion_levels`: the levels of its saved
     regions and areas); with sites= the plan gets an ExcursionMaps.for_projection of its own outputs
     (`sites.excursion`).  Emergence and exposure get none here (ExcursionMaps.for_projection takes them);
-    sensitivity, contrast, Monte Carlo error and quantiles of the excursion maps are not computed.'''
+    sensitivity, contrast, Monte Carlo error and quantiles of the excursion maps are not computed.  reweight:
+    {name: spec, ...} with 1..4 names (check_reweight; not with evaluate=), the maps under new observations by
+    importance reweighting of the members, without a new chain.  spec = dict(probes=[(east_m, north_m, day, kind,
+    rate[, n]), ...]) (check_probes): the member's log-weight is the log-likelihood of the probes under its own
+    fields (probes_loglik on one gather of all probes of all scenarios per member); or
+    dict(log_weights=[one 1-D array per chain]), one entry per row after burn and thin: a run's log-weight is the
+    log of its rows' mean weight (run_log_weight).  Bad cells, days, kinds, rates and lengths fail before any
+    evaluation.  Each chain then also fills one ReweightedSummary over the summary's days (at most 32) and
+    thresholds (finite, > 0, strictly increasing), fed right after the summary with the run's length, merged in
+    chain order into `reweight`; every emergence=, exposure= and sites= asked for gets a
+    ReweightedSummary.for_projection of its own, fed after its summary.  Histogram, arrival, peak, excursion,
+    contrast and Monte Carlo error get none.  `reweight_info` carries per scenario the diagnostics of the row
+    weights (reweight_diagnostics); a UserWarning where ess < min_ess (reweight['options'] = dict(min_ess=50)) --
+    importance reweighting degrades as the new data disagree with the posterior -- and a ValueError naming a
+    scenario that is left without weight.  Without reweight= no call is added and `reweight` is None.'''
     t0 = time.perf_counter()
+    rw_plan = None
+    if reweight is not None:          # bad reweighting arguments fail before any evaluation
+        if evaluate is not None:
+            raise ValueError('reweight= needs the device: not with evaluate=')
+        pm0 = (pop_model[0] if pop_model else None) if isinstance(pop_model, (list, tuple)) else pop_model
+        rw_plan = check_reweight(reweight, None if pm0 is None else pm0.rad_dist,
+                                 None if pm0 is None else pm0.rad_res, None if pm0 is None else len(pm0.days))
+        check_peak_thresholds(thresholds)
+        nd = len(days) if days is not None else (len(pm0.days) if pm0 is not None else 1)
+        if not 1 <= nd <= MAX_REWEIGHT_SLOTS:
+            raise ValueError('reweight= takes 1..%d days, got %d' % (MAX_REWEIGHT_SLOTS, nd))
     ex_thr = ex_levels = None
     if excursion is not None and excursion is not False:     # bad excursion arguments fail before any evaluation
         if evaluate is not None:
@@ -3232,6 +3752,8 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         ocols = _columns(names, obs_want) if want_obs else None
         rows, rl = runs(trace, mcols, burn, thin)
         prepared.append((rows, rl, mcols, ocols, src))
+    if rw_plan is not None:           # row log-weights that do not fit the chains
+        check_reweight_rows(rw_plan, [len(p[0]) for p in prepared])
     mc_b = mc_halves = None
     if mc_batches:                    # a chain shorter than the batches asked for
         mc_b, mc_halves = mc_batch_plan([len(p[0]) for p in prepared], mc_batches)
@@ -3250,6 +3772,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     peaks = [None] * nch                       # per chain its PeakPosterior
     excurs = [None] * nch                      # per chain its ExcursionMaps
     mcs = [None] * nch                         # per chain its two MonteCarloError sequences
+    rws = [None] * nch                         # per chain (ReweightedSummary, _ReweightFeed)
     projected = [[] for _ in range(nch)]       # per chain (Projection, ProjectedMaps) of every plan
     site_maps = [None] * nch                   # per chain (ReleaseSites, ProjectedMaps)
     cmp_maps = [None] * nch                    # per chain (ReleaseSites of plan B, PlanContrast, the lagged models)
@@ -3280,6 +3803,9 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                     mcs[ci] = []
                     for _half in range(2):
                         mcs[ci].append(MonteCarloError(pm, mc_b, summ.days, thresholds))
+                if rw_plan is not None:
+                    rws[ci] = (ReweightedSummary(pm, rw_plan['names'], summ.days, thresholds),
+                               _ReweightFeed(rw_plan, ci))
                 if evaluate is None:
                     for _name, W, in_days, labels in plans:
                         proj = Projection(pm, W, in_days)
@@ -3290,6 +3816,8 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                             maps.histogram = SpreadHistogram.for_projection(proj, bins, edges)
                         if s_names:
                             maps.sensitivity = SensitivityMaps.for_projection(proj, s_names)
+                        if rw_plan is not None:
+                            maps.reweight = ReweightedSummary.for_projection(proj, rw_plan['names'], thresholds)
                         if mc_b:
                             maps.mc_error = []
                             for _half in range(2):
@@ -3309,6 +3837,8 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                             maps.arrival = ArrivalMaps.for_projection(rs, a_thr)
                         if s_names:
                             maps.sensitivity = SensitivityMaps.for_projection(rs, s_names)
+                        if rw_plan is not None:
+                            maps.reweight = ReweightedSummary.for_projection(rs, rw_plan['names'], thresholds)
                         if pk_thr is not None:
                             maps.peak = PeakPosterior(PeakMaps.for_projection(rs, pk_thr), thresholds, pk_levels,
                                                       bins if levels else None, edges if levels else None)
@@ -3326,7 +3856,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                 results[ci] = _evaluate_runs(pm, summ, rows, rl, mcols, evaluate, want_obs, locinfo, hist, arr,
                                              projected[ci], site_maps[ci], sens, cmp_maps[ci],
                                              (mcs[ci], mc_halves[ci][0]) if mc_b else None, peaks[ci],
-                                             excursion=excurs[ci])
+                                             excursion=excurs[ci], reweight=rws[ci])
         except BaseException as e:       # re-raised in the caller's thread
             errs.append((p, e))
 
@@ -3341,7 +3871,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         pms = pms[:1]
         work(0)
     if errs:
-        for s in summaries + histograms + arrivals + senses + peaks + excurs + [x for pair in mcs if pair for x in pair] + [x for pl in projected for pair in pl for x in pair] \
+        for s in summaries + histograms + arrivals + senses + peaks + excurs + [pair[0] for pair in rws if pair] + [x for pair in mcs if pair for x in pair] + [x for pl in projected for pair in pl for x in pair] \
                 + [x for pair in site_maps if pair is not None for x in pair] \
                 + [x for tri in cmp_maps if tri is not None for x in tri[:2]] \
                 + [m for made in late.values() for m in made.values()]:
@@ -3384,6 +3914,12 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
             for a in excurs[1:]:
                 excur_maps.merge(a)
                 a.close()
+    rw_maps = rw_info = None
+    if rw_plan is not None:
+        rw_maps = rws[0][0]
+        for a, _feed in rws[1:]:
+            rw_maps.merge(a)
+            a.close()
     mc_pooled = mc_desc = None
     if mc_b:
         mc_pooled = pool_mc_error(mcs)
@@ -3427,6 +3963,29 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         for made in late.values():
             for m in made.values():
                 m.close()
+    if rw_plan is not None:
+        import warnings
+        diag = {}
+        for j, name in enumerate(rw_plan['names']):
+            d = reweight_diagnostics([v for _a, feed in rws for v in feed.rows[j]])
+            d.update({'members': rw_maps.members(name), 'skipped': rw_maps.skipped(name),
+                      'log_total_weight': rw_maps.log_total_weight(name)})
+            diag[name] = d
+        rw_info = {'names': list(rw_plan['names']), 'probes': list(rw_plan['given']), 'min_ess': rw_plan['min_ess'],
+                   'diagnostics': diag}
+        empty = [n for n in rw_plan['names'] if diag[n]['members'] == 0]
+        if empty:
+            for m in [summary, histogram, arrival_maps, sens_maps, peak_maps, excur_maps, rw_maps, mc_pooled,
+                      contrast] + list(merged.values()) + [merged_sites]:
+                if m is not None:
+                    m.close()
+            raise ValueError('reweight: scenario %r is left without weight (W = 0): no member is compatible with it'
+                             % empty[0])
+        for n in rw_plan['names']:
+            if diag[n]['ess'] < rw_plan['min_ess']:
+                warnings.warn('reweight: scenario %r has an effective sample size of %.3g rows (min_ess %g): the '
+                              'new data disagree with the posterior, the reweighted maps rest on few members'
+                              % (n, diag[n]['ess'], rw_plan['min_ess']), UserWarning)
     evaluations = sum(len(p[1]) for p in prepared)
     failed = sum(r[1] for r in results)
     run_rec = [(ci, first, length) for ci, p in enumerate(prepared)
@@ -3449,7 +4008,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                            None if summary is None else summary.days, histogram, levels, arrival_maps,
                            a_levels if a_thr else None, merged.get('emergence'), merged.get('exposure'),
                            merged_sites, sens_maps, contrast, compare_desc, mc_pooled, mc_desc, peak_maps,
-                           excur_maps, ex_levels if ex_thr else None)
+                           excur_maps, ex_levels if ex_thr else None, rw_maps, rw_info)
     if cell_area is not None:
         res.cell_area = float(cell_area)
     return res

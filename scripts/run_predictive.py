@@ -21,7 +21,12 @@ highest density within the window, the day of the peak and the number of days at
 density and day the region all of which is reached at the same time with a given probability, the region surely
 not reached and the credible band of the contour between them (--excursion-levels: the credible levels of the saved
 regions and areas, each in (0.5, 1]) -- saved as PREFIX_excur.npz (and, with --sites, PREFIX_sites_excur.npz for the
-plan).  Kalbar wind and
+plan); with --reweight / --reweight-file also the maps under new observations without a new chain -- up to four
+named scenarios, each a list of probe observations 'east,north,day,kind,rate[,n]' (kind: count with the number
+found n, none, found; rate: the expected number found per wasp in the cell) or a .npy file of one log-weight per
+chain row after burn and thin (several chains: concatenated in chain order), by importance reweighting of the
+members, with the effective sample size of every scenario in the json -- saved as PREFIX_reweight.npz (and
+PREFIX_NAME_reweight.npz for every projection and plan asked for).  Kalbar wind and
 LocInfo as scripts/run_mcmc.py loads them; --synthetic uses the synthetic Kalbar-like observations.
 Without --chain a short chain is sampled first (--samples) and saved next to --out.
 
@@ -32,6 +37,7 @@ Without --chain a short chain is sampled first (--samples) and saved next to --o
         [--sites 'E,N,AMOUNT[,LAG];...'] [--sites-days d1,d2,...] [--sensitivity [name,name,...]]
         [--compare-sites 'E,N,AMOUNT[,LAG];...'] [--peak 1,10] [--peak-levels 0.05,0.5,0.95]
         [--excursion 1,10] [--excursion-levels 0.9,0.95]
+        [--reweight 'NAME:east,north,day,kind,rate[,n];...'] [--reweight-file NAME=weights.npy]
 """
 import argparse
 import json
@@ -42,6 +48,41 @@ import warnings
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+def parse_reweight(ap, probes, files):
+    '''the --reweight / --reweight-file flags -> ({name: dict(probes=[...])}, {name: path}); a malformed flag is an
+    argument error (the cells, days and rates are checked against the model later)'''
+    specs, paths = {}, {}
+    for text in probes or []:
+        name, sep, body = text.partition(':')
+        if not sep or not name.strip() or not body.strip():
+            ap.error("--reweight takes 'NAME:east,north,day,kind,rate[,n];...', got %r" % text)
+        if name.strip() in specs:
+            ap.error('--reweight names scenario %r twice' % name.strip())
+        rows = []
+        for item in body.split(';'):
+            if not item.strip():
+                continue
+            f = [v.strip() for v in item.split(',')]
+            if len(f) not in (5, 6) or f[3] not in ('count', 'none', 'found') or (f[3] == 'count') != (len(f) == 6):
+                ap.error("--reweight probe %r: east,north,day,kind,rate[,n] with kind count (and n), none or found"
+                         % item)
+            try:
+                rows.append((float(f[0]), float(f[1]), int(f[2]), f[3], float(f[4])) + ((int(f[5]),) if len(f) == 6 else ()))
+            except ValueError:
+                ap.error('--reweight probe %r: numbers expected' % item)
+        specs[name.strip()] = dict(probes=rows)
+    for text in files or []:
+        name, sep, path = text.partition('=')
+        if not sep or not name.strip() or not path.strip():
+            ap.error('--reweight-file takes NAME=weights.npy, got %r' % text)
+        if name.strip() in specs or name.strip() in paths:
+            ap.error('--reweight-file names scenario %r twice (reweight)' % name.strip())
+        paths[name.strip()] = path.strip()
+    if len(specs) + len(paths) > 4:
+        ap.error('at most 4 --reweight / --reweight-file scenarios')
+    return specs, paths
 
 
 def main():
@@ -88,7 +129,14 @@ def main():
                                                     '(default: off)')
     ap.add_argument('--excursion-levels', default='0.9,0.95',
                     help='credible levels in (0.5, 1] of the saved excursion regions and areas (with --excursion)')
+    ap.add_argument('--reweight', action='append', default=None, metavar='NAME:PROBES',
+                    help="a reweighting scenario of probe observations 'NAME:east,north,day,kind,rate[,n];...' "
+                         '(repeatable; at most 4 scenarios with --reweight-file; default: off)')
+    ap.add_argument('--reweight-file', action='append', default=None, metavar='NAME=NPY',
+                    help='a reweighting scenario from a .npy of one log-weight per chain row after burn and thin '
+                         '(repeatable)')
     args = ap.parse_args()
+    rw_specs, rw_files = parse_reweight(ap, args.reweight, args.reweight_file)
     if args.compare_sites and not args.sites:
         ap.error('--compare-sites names plan B and needs plan A: give --sites too')
     warnings.simplefilter('ignore', RuntimeWarning)
@@ -173,12 +221,26 @@ def main():
         smp.save(chains[0])
     pms = [pm] + ([make_pm() for _ in chains[1:]] if args.chains_parallel else [])
     thr = [float(t) for t in args.thresholds.split(',') if t.strip()]
+    reweight = None
+    if rw_specs or rw_files:             # a bad probe fails before any evaluation; a file is split by the chains' rows
+        import numpy as np
+        from parasitoids_amd.predictive import check_reweight, load_chain as _load
+        reweight = dict(rw_specs)
+        nrows = [len(_load(c)[0][args.burn::args.thin]) for c in chains]
+        for name, path in rw_files.items():
+            lw = np.asarray(np.load(path), dtype=np.float64).ravel()
+            if lw.size != sum(nrows):
+                ap.error('--reweight-file %s: %d log-weights, the chains have %d rows after burn and thin'
+                         % (path, lw.size, sum(nrows)))
+            reweight[name] = dict(log_weights=np.split(lw, np.cumsum(nrows)[:-1]))
+        rw_plan = check_reweight(reweight, pm.rad_dist, pm.rad_res, len(days))
     t0 = time.perf_counter()
     res = posterior_predictive(pms if len(pms) > 1 else pm, chains, burn=args.burn, thin=args.thin,
                                thresholds=thr, locinfo=li, cell_area=cell_area, seed=args.seed,
                                quantiles=levels or None, bins=bins, arrival=arrival or None, arrival_levels=a_levels,
                                emergence=emergence, exposure=exposure, sites=sites, sensitivity=sens,
-                               compare=compare, mc_error=mc_error, peak=peak, excursion=excursion)
+                               compare=compare, mc_error=mc_error, peak=peak, excursion=excursion,
+                               **({'reweight': reweight} if reweight else {}))
     dt = time.perf_counter() - t0
     # accumulate-kernel time: the same members once more with HIP events around every add
     from parasitoids_amd.predictive import (ArrivalMaps, ExcursionMaps, MonteCarloError, PeakMaps, PlanContrast, Projection,
@@ -204,6 +266,12 @@ def main():
     A = ArrivalMaps(pm, arrival) if arrival else None
     PK = PeakMaps(pm, peak['thresholds']) if peak else None
     EX = ExcursionMaps(pm, excursion['thresholds']) if excursion else None
+    RW = RWF = None
+    if reweight:
+        from parasitoids_amd.predictive import ReweightedSummary, _ReweightFeed
+        RW = ReweightedSummary(pm, rw_plan['names'], None, thr)
+        RWF = _ReweightFeed(rw_plan, 0)
+        RW.profile(True)
     with SpreadSummary(pm, None, thr) as S:
         S.profile(True)
         if H is not None:
@@ -240,6 +308,8 @@ def main():
                 except Exception:
                     continue
                 S.add(length)
+                if RW is not None:
+                    RW.add(RWF.log_weights(pm, first, length), length)
                 if ME is not None:
                     ME.add(length)
                 if X is not None:
@@ -279,6 +349,10 @@ def main():
         ex_ms, ex_launches = EX.profile()[:2]
         EX.close()
         res.excursion.profile(True)     # the finalize and every map launch of the save
+    if RW is not None:
+        rw_ms, rw_launches = RW.profile()
+        rw_bytes = RW.nbytes
+        RW.close()
     if X is not None:
         x_ms, x_launches = X.profile()
         x_bytes = X.nbytes
@@ -317,6 +391,15 @@ def main():
            'days': nday, 'thresholds': thr, 'chains': len(chains), 'chains_parallel': len(pms) > 1,
            'bayes_evaluations_per_hour': None if bayes_rate is None else round(bayes_rate, 1),
            'outputs': [npz, js]}
+    if reweight:
+        out['reweight_ms_per_member'] = round(rw_ms / max(rw_launches, 1), 4)
+        out['reweight_launches_timed'] = rw_launches
+        out['reweight_scenarios'] = list(res.reweight.scenarios)
+        out['reweight_bytes'] = rw_bytes
+        out['reweight_diagnostics'] = res.reweight_info['diagnostics']
+        out['outputs'] += ['%s_reweight.npz' % args.out] + ['%s_%s_reweight.npz' % (args.out, n) for n, on in
+                                                            (('emergence', emergence), ('exposure', exposure),
+                                                             ('sites', sites)) if on]
     if levels:
         out['histogram_add_ms_per_member'] = round(h_ms / max(h_launches, 1), 4)
         out['quantile_ms_total'] = round(res.histogram.profile()[2], 3)
