@@ -949,6 +949,65 @@ int ps_wsum_reset(ps_wsum* h);
 int ps_wsum_prof(ps_wsum* h, int enable, double* total_ms, int64_t* launches);
 void ps_wsum_destroy(ps_wsum* h);
 
+/* ---- catch-probability fields: what a trap at each cell would find in one member's field ----
+ * (no reference counterpart; the Poisson model is that of the package's own likelihood, mcmc.loglik_parts.)
+ * A handle lives on one device and holds nout outputs (1..32) over nin inputs (1..32): output e is
+ * (input[e], rate[e], count[e]) with 0 <= input[e] < nin, rate finite and > 0 and count a whole number in 1..16
+ * (PS_ERR_BAD_ARG otherwise), and nout fp64 fields Y[e][pitch] (pitch as ps_summary), whose size, nout * pitch
+ * * 8 B, is checked against the free device memory first: PS_ERR_OOM before anything is allocated.  With v the
+ * value of input[e] at a cell, an apply overwrites every cell of every output, zeros included, with
+ *   Y_e(c) = P(Poisson(mu) >= n),   mu = rate[e] * v   (one rounded product),   n = count[e]
+ * evaluated by these statements, one IEEE double rounding each (never fused), exp and expm1 the device library's:
+ *   not (mu > 0):   Y = +0.0               (so Y is exactly +0.0 where v == 0; every other value lies in [0, 1])
+ *   mu >= 800:      Y = 1.0                (exp(-mu) is 0 from 746 on)
+ *   n == 1:         x = expm1(-mu);  Y = -x
+ *   mu < n:         t = 1;  for i = 1..n:  t = t * mu;  t = t / i               (mu^n / n! as a running product)
+ *                   s = 1;  u = 1;  for j = 1..56:  r = mu / (n + j);  u = u * r;  s = s + u
+ *                   t = t * s;  e = exp(-mu);  Y = t * e;  Y > 1: Y = 1
+ *   mu >= n:        u = 1;  q = 1;  for i = 1..n-1:  u = u * mu;  u = u / i;  q = q + u
+ *                   e = exp(-mu);  p = e * q;  Y = 1 - p;  Y < 0: Y = 0        (Y >= about 0.45: nothing cancels)
+ * The device leaves the series at the first term that does not change s; every later term is smaller, so the
+ * 56 terms give the same bits, and the stop depends on the cell's own (mu, n) alone: neither grid nor block
+ * shape changes a bit.  One thread owns a pair of cells (the tail cell of an odd N * N alone); the outputs are
+ * grouped by input, so a record is read once however many outputs use it; a pair whose values are both zero
+ * writes zeros without touching the exponential path.  No atomics, one writer per cell.  Every operation
+ * records an event the next one waits on, whichever stream it runs on (the solver's for ps_catch_apply, the
+ * handle's own for the other applies, fetch and gather, the accumulator's for the _add_catch entry points). */
+typedef struct ps_catch ps_catch;
+int ps_catch_create(int device, int N, int nin, int nout, const int32_t* input /* nout */,
+                    const double* rate /* nout */, const int32_t* count /* nout */, ps_catch** out);
+/* The inputs are records of solver s (same device, same N; arguments as ps_project_apply, nin must equal the
+ * handle's; v is the value ps_summary_add adds, bit for bit): one launch on the solver's stream, no host
+ * synchronisation, nothing copied or allocated. */
+int ps_catch_apply(ps_catch* c, ps_solver* s, int nin, const int32_t* kind, const int32_t* idx,
+                   const double* stat_scale, const double* post_scale, const int32_t* use_delta, double negval);
+/* The inputs are the current outputs of a projection or a release plan: input i is the source's output i, so
+ * nin must equal its nout, and device and N must agree (PS_ERR_BAD_ARG, nothing enqueued); PS_ERR_STATE before
+ * the source's first apply.  One launch on the handle's stream behind the source's last operation; the source's
+ * next apply waits for the read. */
+int ps_catch_apply_project(ps_catch* c, ps_project* p);
+int ps_catch_apply_sites(ps_catch* c, ps_sites* p);
+/* one output field to the host (synchronises).  PS_ERR_STATE before the first apply. */
+int ps_catch_fetch(ps_catch* c, int e, double* out /* N*N */);
+/* the outputs at n listed cells: out[e * n + k] = Y_e(rows[k], cols[k]) (synchronises).  PS_ERR_BAD_ARG for
+ * a cell outside the domain, PS_ERR_STATE before the first apply. */
+int ps_catch_gather(ps_catch* c, int64_t n, const int32_t* rows, const int32_t* cols, double* out /* nout x n */);
+/* any pointer may be NULL */
+int ps_catch_info(ps_catch* c, int* N, int* nin, int* nout, int64_t* applies);
+/* measurement: HIP-event timing of the apply launches.  enable 1 on, 0 off, < 0 unchanged; total_ms /
+ * launches (either may be NULL) receive the timed launches so far (synchronises).  Finished event pairs are
+ * folded into running totals as in ps_peak_prof. */
+int ps_catch_prof(ps_catch* c, int enable, double* total_ms, int64_t* launches);
+void ps_catch_destroy(ps_catch* c);
+/* One member whose values are the handle's current outputs, as ps_summary_add_project / ps_mcerr_add_project /
+ * ps_wsum_add_project take a projection's: slot e takes Y_e, through the accumulator's own add kernel, on the
+ * accumulator's stream behind the handle's last operation; the next apply waits for the read.  The
+ * accumulator's slot count must equal nout, device and N must agree (PS_ERR_BAD_ARG, nothing enqueued);
+ * PS_ERR_STATE before the first apply. */
+int ps_summary_add_catch(ps_summary* a, ps_catch* c, uint32_t weight);
+int ps_mcerr_add_catch(ps_mcerr* h, ps_catch* c, uint32_t weight);
+int ps_wsum_add_catch(ps_wsum* h, ps_catch* c, int nscen, const double* rescale, const double* omega);
+
 #ifdef __cplusplus
 }
 #endif

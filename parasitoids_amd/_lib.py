@@ -265,6 +265,18 @@ SIGNATURES = {
     'ps_wsum_reset': (C.c_int, [_VP]),
     'ps_wsum_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P]),
     'ps_wsum_destroy': (None, [_VP]),
+    'ps_catch_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _I32P, _F64P, _I32P, C.POINTER(_VP)]),
+    'ps_catch_apply': (C.c_int, [_VP, _VP, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P, C.c_double]),
+    'ps_catch_apply_project': (C.c_int, [_VP, _VP]),
+    'ps_catch_apply_sites': (C.c_int, [_VP, _VP]),
+    'ps_catch_fetch': (C.c_int, [_VP, C.c_int, _F64P]),
+    'ps_catch_gather': (C.c_int, [_VP, C.c_int64, _I32P, _I32P, _F64P]),
+    'ps_catch_info': (C.c_int, [_VP, _I32P, _I32P, _I32P, _I64P]),
+    'ps_catch_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P]),
+    'ps_catch_destroy': (None, [_VP]),
+    'ps_summary_add_catch': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_mcerr_add_catch': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_wsum_add_catch': (C.c_int, [_VP, _VP, C.c_int, _F64P, _F64P]),
 }
 
 _lib = None

@@ -144,6 +144,7 @@ struct PsFieldsOps {
 PsFieldsOps ps_project_fields();
 PsFieldsOps ps_sites_fields();
 PsFieldsOps ps_peak_fields();    // the last member's peak field of a ps_peak (ps_peak.hip): nout = 1
+PsFieldsOps ps_catch_fields();   // the catch-probability fields of a ps_catch (ps_catch.hip)
 
 // the value one solver record holds at a cell, as ps_record_fetch_* returns it (k_compact_rows,
 // chain_kernels.h), 0 where it returns no entry; shared by ps_summary.hip and ps_linspread.hip

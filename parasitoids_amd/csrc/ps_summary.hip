@@ -276,6 +276,10 @@ extern "C" int ps_summary_add_peak(ps_summary* a, ps_peak* p, uint32_t weight) {
   return sum_add_fields(a, p, ps_peak_fields(), "summary_add_peak", weight);
 }
 
+extern "C" int ps_summary_add_catch(ps_summary* a, ps_catch* p, uint32_t weight) {
+  return sum_add_fields(a, p, ps_catch_fields(), "summary_add_catch", weight);
+}
+
 extern "C" int ps_summary_merge(ps_summary* dst, ps_summary* src) {
   if (!dst || !src || dst == src) return ps_fail(PS_ERR_BAD_ARG, "summary_merge: bad arguments");
   if (dst->device != src->device || dst->N != src->N || dst->nslot != src->nslot || dst->nthr != src->nthr)

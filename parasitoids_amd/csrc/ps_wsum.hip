@@ -387,6 +387,10 @@ extern "C" int ps_wsum_add_peak(ps_wsum* a, ps_peak* p, int nscen, const double*
   return ws_add_fields(a, p, ps_peak_fields(), "wsum_add_peak", nscen, rescale, omega);
 }
 
+extern "C" int ps_wsum_add_catch(ps_wsum* a, ps_catch* p, int nscen, const double* rescale, const double* omega) {
+  return ws_add_fields(a, p, ps_catch_fields(), "wsum_add_catch", nscen, rescale, omega);
+}
+
 extern "C" int ps_wsum_merge(ps_wsum* dst, ps_wsum* src, const double* ra, const double* rb) {
   if (!dst || !src || !ra || !rb) return ps_fail(PS_ERR_BAD_ARG, "wsum_merge: bad arguments");
   if (dst == src) return ps_fail(PS_ERR_BAD_ARG, "wsum_merge: dst and src are the same handle");

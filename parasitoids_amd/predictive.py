@@ -39,6 +39,10 @@ mean duration -- max over days is not linear, so none of them can be rebuilt fro
 mask of the cells at or above the threshold (ps_excur_*, csrc/ps_excur.hip): the joint excursion sets "surely
 reached" / "surely not reached" and the credible band of the contour between them (Bolin & Lindgren 2015) --
 every other map is marginal in space and cannot say with which probability all cells of a region exceed at once.
+`CatchFields` turns, on the device, one member's field into the probability that a trap of a given effort catches at
+least n wasps at every cell (ps_catch_*, csrc/ps_catch.hip), under the Poisson model of the package's own likelihood;
+`SpreadSummary.for_projection`, `MonteCarloError.for_projection` and `ReweightedSummary.for_projection` accumulate it
+per member (`CatchPosterior`) -- the transform is not linear in the density, so no saved map gives it.
 """
 import ctypes as C
 import json
@@ -1340,10 +1344,12 @@ class ProjectedMaps():
     the output index.  `peak`: the PeakPosterior of a release plan's outputs (None unless asked for), whose maps
     take the output day.  `excursion`: the ExcursionMaps.for_projection of a release plan's outputs (None unless
     asked for), whose maps take the output day.  `reweight`: the
-    ReweightedSummary.for_projection (None unless asked for), which takes the scenario's name and the output index.'''
+    ReweightedSummary.for_projection (None unless asked for), which takes the scenario's name and the output index.
+    `catch`: the CatchPosterior over the outputs (None unless asked for), whose traps name an output label.'''
 
     def __init__(self, weights, in_days, labels, summary, histogram=None, arrival=None, plan=None,
-                 sensitivity=None, mc_error=None, peak=None, excursion=None, reweight=None):
+                 sensitivity=None, mc_error=None, peak=None, excursion=None, reweight=None, catch=None):
+        self.catch = catch
         self.peak = peak
         self.excursion = excursion
         self.reweight = reweight
@@ -1371,9 +1377,13 @@ class ProjectedMaps():
             self.excursion.merge(other.excursion)
         if self.reweight is not None:
             self.reweight.merge(other.reweight)
+        if self.catch is not None and other.catch is not None:       # the driver merges the chains' catches itself
+            self.catch.merge(other.catch)
 
     def close(self):
         self.summary.close()
+        if self.catch is not None:
+            self.catch.close()
         if self.reweight is not None:
             self.reweight.close()
         if self.excursion is not None:
@@ -3025,6 +3035,343 @@ class _ReweightFeed():
         return lam
 
 
+# ------------------------------------------------------------------ catch probability: what a trap would find
+MAX_CATCH_IN = 32          # ps_catch: the input records of one launch's descriptors
+MAX_CATCH_OUT = 32
+MAX_CATCH_COUNT = 16       # the largest count n of P(N >= n) the kernel's series is stated for
+
+
+def check_traps(traps, what='day'):
+    '''traps [(key, rate[, n=1]), ...] as [(key, rate, n), ...]: 1..32 traps, the key (a model day, or the output
+    label of a projection or plan) a whole number >= 0, rate finite and > 0, n a whole number in 1..16;
+    ValueError otherwise'''
+    import math
+    try:
+        rows = [tuple(t) for t in traps]
+    except TypeError:
+        raise ValueError('traps must be a list of (%s, rate[, n]), got %r' % (what, traps))
+    if not 1 <= len(rows) <= MAX_CATCH_OUT:
+        raise ValueError('%d traps; 1..%d fit one handle' % (len(rows), MAX_CATCH_OUT))
+    out = []
+    for t in rows:
+        if len(t) not in (2, 3):
+            raise ValueError('a trap is (%s, rate[, n]), got %r' % (what, t))
+        try:
+            key, rate, n = float(t[0]), float(t[1]), float(t[2]) if len(t) == 3 else 1.0
+        except (TypeError, ValueError):
+            raise ValueError('a trap is (%s, rate[, n]) of numbers, got %r' % (what, t))
+        if not (math.isfinite(key) and key == int(key) and key >= 0):
+            raise ValueError('trap %r: the %s must be a whole number >= 0' % (t, what))
+        if not (math.isfinite(rate) and rate > 0):
+            raise ValueError('trap %r: the rate must be finite and > 0' % (t,))
+        if not (math.isfinite(n) and n == int(n) and 1 <= n <= MAX_CATCH_COUNT):
+            raise ValueError('trap %r: the count must be a whole number in 1..%d' % (t, MAX_CATCH_COUNT))
+        out.append((int(key), rate, int(n)))
+    return out
+
+
+def check_catch_levels(levels):
+    '''the levels of a catch summary's `sure` maps as a list: 0..4 probabilities in (0, 1], strictly increasing'''
+    try:
+        lv = [float(p) for p in levels]
+    except TypeError:
+        raise ValueError('catch levels must be a list of probabilities, got %r' % (levels,))
+    if len(lv) > 4 or any(not 0.0 < p <= 1.0 for p in lv) or any(b <= a for a, b in zip(lv, lv[1:])):
+        raise ValueError('catch levels must be at most 4 probabilities in (0, 1], strictly increasing: %r' % (lv,))
+    return lv
+
+
+def check_catch(catch, ndays=None, emergence=None, evaluate=None):
+    '''posterior_predictive's catch= argument, dict(traps=[(day, rate[, n]), ...], levels=(0.5, 0.95),
+    emergence=[(obs_day, rate[, n]), ...]) -> dict(traps, levels, emergence, given): the checked traps
+    (check_traps) over model days < ndays, at most 32 distinct ones; the levels (check_catch_levels); the traps
+    over the outputs of the emergence projection, whose key is one of its labels that carries weight -- they
+    need posterior_predictive's emergence= argument, passed here -- or None; and the argument as given for the
+    json.  evaluate: posterior_predictive's evaluate=, which has no device fields.  ValueError otherwise.'''
+    if not isinstance(catch, dict) or 'traps' not in catch or set(catch) - {'traps', 'levels', 'emergence'}:
+        raise ValueError('catch must be dict(traps=[(day, rate[, n]), ...], levels=(0.5, 0.95), emergence=None), '
+                         'got %r' % (catch,))
+    if evaluate is not None:
+        raise ValueError('catch= needs the device: not with evaluate=')
+    traps = check_traps(catch['traps'])
+    for t in traps:
+        if ndays is not None and t[0] >= ndays:
+            raise ValueError('trap %r: the model has %d days' % (t, ndays))
+    if len({t[0] for t in traps}) > MAX_CATCH_IN:
+        raise ValueError('the traps name more than %d days' % MAX_CATCH_IN)
+    levels = check_catch_levels(catch.get('levels', (0.5, 0.95)))
+    em = None
+    if catch.get('emergence') is not None:
+        if emergence is None:
+            raise ValueError('catch[\'emergence\'] needs the emergence= projection')
+        em = check_traps(catch['emergence'], 'emergence day')
+        W, _in_days, labels = emergence_plan(emergence)
+        for t in em:
+            if t[0] not in labels or not np.any(W[labels.index(t[0])] != 0):
+                raise ValueError('trap %r: %d is not an emergence day that carries weight (%r)' % (t, t[0], labels))
+    given = {k: [list(t) for t in v] if k != 'levels' else list(v) for k, v in catch.items() if v is not None}
+    return {'traps': traps, 'levels': levels, 'emergence': em, 'given': given}
+
+
+def parse_traps(text):
+    '''the command line's 'KEY,RATE[,N];...' as [(key, rate[, n]), ...] (format_traps is its inverse); the
+    values are checked by check_traps, here only the shape'''
+    out = []
+    for part in str(text).split(';'):
+        if not part.strip():
+            continue
+        f = [x.strip() for x in part.split(',')]
+        if len(f) not in (2, 3):
+            raise ValueError('a trap is KEY,RATE[,N], got %r' % (part,))
+        try:
+            out.append((int(f[0]), float(f[1])) + ((int(f[2]),) if len(f) == 3 else ()))
+        except ValueError:
+            raise ValueError('a trap is KEY,RATE[,N] with whole KEY and N, got %r' % (part,))
+    return out
+
+
+def format_traps(traps):
+    return ';'.join(','.join(repr(x) for x in t) for t in traps)
+
+
+def required_rate(traps, means, day, n, level):
+    '''Per cell the smallest listed rate among the traps (key, rate, n) with this (day, n) whose mean catch
+    probability means[e] is >= level, NaN where none reaches it: a step function over the ladder of rates the
+    user listed, not a search.  Traps of another day or count are ignored; of two traps with the same rate
+    either may answer.  ValueError where no trap has this (day, n).'''
+    rungs = sorted(((t[1], e) for e, t in enumerate(traps) if t[0] == int(day) and t[2] == int(n)), reverse=True)
+    if not rungs:
+        raise ValueError('no trap with day %r and count %r' % (day, n))
+    out = None
+    for rate, e in rungs:                       # descending: the smallest rate that suffices is written last
+        m = np.asarray(means[e], dtype=np.float64)
+        if out is None:
+            out = np.full(m.shape, np.nan)
+        out = np.where(m >= level, rate, out)
+    return out
+
+
+class CatchFields():
+    '''Y_e(c) = P(Poisson(rate_e v(c)) >= n_e) of `pop_model`'s last evaluation, on the device (ps_catch_*,
+    csrc/ps_catch.hip): what a trap of effort rate_e on model day day_e would find at every cell, under the
+    package's own observation model (mcmc.loglik_parts).  traps: [(day, rate[, n=1]), ...] (check_traps), v the
+    value SpreadSummary adds for that day; days: the model days the handle reads, default the traps' own (at
+    most 32).  `for_projection` reads the outputs of a Projection or a ReleaseSites instead.  The statements of
+    the evaluation are fixed in include/parasitoid_hip.h (tests/catch_ref.py restates them): Y is exactly 0
+    where v is 0 and lies in [0, 1] elsewhere; P(N = 0) is 1 - Y of an n = 1 trap.  The handle holds
+    len(traps) x pitch x 8 B.  SpreadSummary.for_projection, MonteCarloError.for_projection and
+    ReweightedSummary.for_projection accept it.'''
+    fields_kind = 'catch'        # the accumulators' entry points for these fields: ps_*_add_catch
+
+    def __init__(self, pop_model, traps, days=None):
+        self._h = L._VP()
+        self.traps = check_traps(traps)
+        used = sorted({t[0] for t in self.traps})
+        self.in_days = used if days is None else check_in_days(days)
+        if len(self.in_days) > MAX_CATCH_IN:
+            raise ValueError('%d input days; at most %d fit one handle' % (len(self.in_days), MAX_CATCH_IN))
+        missing = [d for d in used if d not in self.in_days]
+        if missing:
+            raise ValueError('trap days %r are not among the days %r' % (missing, self.in_days))
+        self._source = None
+        self._setup(pop_model, [self.in_days.index(t[0]) for t in self.traps], len(self.in_days))
+        self._kind, self._idx, self._delta = _day_slots(self.in_days)
+
+    @classmethod
+    def for_projection(cls, source, traps, labels=None):
+        '''The catch fields of the outputs of `source` (a Projection or a ReleaseSites): a trap's first entry is
+        the source's output label (labels: one per output, default a ReleaseSites' output days, else the output
+        indices); `apply()` reads the outputs of the source's last apply.  An output without weight is
+        refused.'''
+        self = cls.__new__(cls)
+        self._h = L._VP()
+        self.traps = check_traps(traps, 'output')
+        if labels is None:
+            labels = getattr(source, 'days', None) if source.fields_kind == 'sites' else None
+        labels = list(range(source.nout)) if labels is None else [int(x) for x in labels]
+        if len(labels) != source.nout:
+            raise ValueError('%d labels for %d outputs' % (len(labels), source.nout))
+        slot = {e: i for i, e in enumerate(source.live)}        # the source's device slot of every output
+        inputs = []
+        for t in self.traps:
+            if t[0] not in labels or labels.index(t[0]) not in slot:
+                raise ValueError('trap %r: %d is not an output that carries weight (%r)' % (t, t[0], labels))
+            inputs.append(slot[labels.index(t[0])])
+        self.in_days = None
+        self._source = source
+        self._setup(source.pm, inputs, len(source.live))
+        return self
+
+    def _setup(self, pop_model, inputs, nin):
+        self._lib = L.load()
+        self.pm = pop_model
+        self.nout = len(self.traps)
+        self.live = list(range(self.nout))
+        self.rates = [t[1] for t in self.traps]
+        self.counts = [t[2] for t in self.traps]
+        self.N = 2 * int(pop_model.rad_res) + 1
+        self.device = L.default_device() if pop_model.device is None else int(pop_model.device)
+        pitch = (self.N * self.N + 63) // 64 * 64
+        self.nbytes = self.nout * pitch * 8                 # the output fields
+        L.check(self._lib.ps_catch_create(self.device, self.N, int(nin), self.nout, L.p_i32(L.i32(inputs)),
+                                          L.p_f64(L.f64(self.rates)), L.p_i32(L.i32(self.counts)), C.byref(self._h)))
+
+    def apply(self):
+        '''The catch fields of the last evaluation of the model (enqueued on the solver's stream), or of the
+        source's last apply (on the handle's stream); no host synchronisation; the outputs of the previous apply
+        are overwritten.'''
+        if self._source is not None:
+            L.check(getattr(self._lib, 'ps_catch_apply_' + self._source.fields_kind)(self._h, self._source._h))
+            return
+        pm = self.pm
+        _check_evaluated(pm, self.in_days, 'catch fields')
+        stat, post = _day_scales(pm, self.in_days)
+        L.check(self._lib.ps_catch_apply(self._h, pm.solver._h, len(self.in_days), L.p_i32(self._kind),
+                                         L.p_i32(self._idx), L.p_f64(stat), L.p_f64(post), L.p_i32(self._delta),
+                                         NEGVAL))
+
+    @property
+    def applies(self):
+        n = C.c_int64()
+        L.check(self._lib.ps_catch_info(self._h, None, None, None, C.byref(n)))
+        return n.value
+
+    def field(self, e):
+        '''[N, N] float64: output e of the last apply'''
+        if not 0 <= int(e) < self.nout:
+            raise ValueError('output %r of %d' % (e, self.nout))
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        L.check(self._lib.ps_catch_fetch(self._h, int(e), L.p_f64(out)))
+        return out
+
+    def gather(self, rows, cols):
+        '''[nout, n] float64: every output of the last apply at the cells (rows[k], cols[k])'''
+        rows, cols = L.i32(np.asarray(rows).ravel()), L.i32(np.asarray(cols).ravel())
+        if rows.size != cols.size:
+            raise ValueError('%d rows and %d columns' % (rows.size, cols.size))
+        out = np.zeros((self.nout, rows.size), dtype=np.float64)
+        L.check(self._lib.ps_catch_gather(self._h, rows.size, L.p_i32(rows), L.p_i32(cols), L.p_f64(out)))
+        return out
+
+    def profile(self, enable=None):
+        '''HIP-event time of the apply launches: (total ms, launches); enable switches it'''
+        ms, n = C.c_double(), C.c_int64()
+        L.check(self._lib.ps_catch_prof(self._h, -1 if enable is None else int(bool(enable)), C.byref(ms),
+                                        C.byref(n)))
+        return ms.value, n.value
+
+    def close(self):
+        if self._h:
+            self._lib.ps_catch_destroy(self._h)
+            self._h = L._VP()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CatchPosterior():
+    '''The posterior of catch fields, as posterior_predictive returns it: `fields` (the CatchFields; closed once
+    the chains have run), `traps` [(key, rate, n)], `levels` and `summary`, the
+    SpreadSummary.for_projection(fields, levels), which takes the trap's index; `mc_error`: the
+    MonteCarloError.for_projection (while the chains run, one chain's two sequences) and `reweight`: the
+    ReweightedSummary.for_projection, both None unless asked for; `given`: the driver's catch= argument.'''
+
+    def __init__(self, fields, levels=(0.5, 0.95), mc_batch=None, scenarios=None):
+        self.fields = fields
+        self.traps = list(fields.traps)
+        self.levels = check_catch_levels(levels)
+        self.mc_error = None
+        self.reweight = None
+        self.given = None
+        self.summary = SpreadSummary.for_projection(fields, self.levels)
+        if mc_batch:
+            self.mc_error = [MonteCarloError.for_projection(fields, mc_batch, self.levels) for _half in range(2)]
+        if scenarios:
+            self.reweight = ReweightedSummary.for_projection(fields, scenarios, self.levels)
+
+    def add(self, weight=1, log_weights=None):
+        '''apply the fields to the last evaluation (or the source's last apply) and add them to the summary and,
+        with the run's log-weights, to the reweighted summary; the Monte Carlo error sequences are the caller's
+        to feed (the run is split between them)'''
+        self.fields.apply()
+        self.summary.add(weight)
+        if self.reweight is not None:
+            self.reweight.add(log_weights, weight)
+
+    def merge(self, other):
+        if other.traps != self.traps or other.levels != self.levels:
+            raise ValueError('catch posteriors over different traps or levels')
+        self.summary.merge(other.summary)
+        if self.reweight is not None:
+            self.reweight.merge(other.reweight)
+
+    def _e(self, e):
+        if not 0 <= int(e) < len(self.traps):
+            raise ValueError('trap %r of %d' % (e, len(self.traps)))
+        return int(e)
+
+    def prob(self, e):
+        '''the posterior mean of the catch probability of trap e'''
+        return self.summary.mean(self._e(e))
+
+    def sd(self, e):
+        '''the posterior sd of the catch probability of trap e (a variance that rounding left below 0 reads as 0)'''
+        return np.sqrt(np.maximum(self.summary.variance(self._e(e)), 0.0))
+
+    def sure(self, e, k):
+        '''the posterior probability that the member's catch probability of trap e is >= levels[k]'''
+        return self.summary.exceedance(self._e(e), k)
+
+    def required_rate(self, day, n=1, level=0.95):
+        '''per cell the smallest listed rate of the traps with this (day, n) whose prob() is >= level, NaN where
+        none reaches it (required_rate)'''
+        use = [e for e, t in enumerate(self.traps) if t[0] == int(day) and t[2] == int(n)]
+        means = {e: self.prob(e) for e in use}
+        return required_rate(self.traps, means, day, n, level)
+
+    def close(self):
+        self.fields.close()
+        self.summary.close()
+        if self.reweight is not None:
+            self.reweight.close()
+        if self.mc_error is not None:
+            for s in (self.mc_error if isinstance(self.mc_error, (list, tuple)) else [self.mc_error]):
+                s.close()
+
+
+def save_catch(outfile, catch, cell_area=None):
+    '''outfile.npz of one CatchPosterior through save_maps: per trap e under the label `c{e}` the CSR triplets
+    `c{e}_*` of the posterior mean catch probability, `c{e}_sd_*` and `c{e}_sure{k}_*`; `days` (the traps' days
+    or output labels), `rates`, `counts` and `levels` -> its block for
+    the json: the traps, levels, members, weight and per trap the largest mean probability and, with a cell
+    area, the m^2 where it is >= each level'''
+    maps, outs = [], []
+    for e, t in enumerate(catch.traps):
+        mean = catch.prob(e)
+        day_maps = [('', mean), ('_sd', catch.sd(e))]
+        day_maps += [('_sure%d' % k, catch.sure(e, k)) for k in range(len(catch.levels))]
+        maps.append(('c%d' % e, day_maps))
+        outs.append({'trap': list(t), 'max_prob': float(mean.max()),
+                     'area': [None if cell_area is None else float((mean >= p).sum() * cell_area)
+                              for p in catch.levels]})
+    extra = {'days': np.array([t[0] for t in catch.traps], dtype=np.int32),      # in place of save_maps' labels
+             'rates': np.array([t[1] for t in catch.traps], dtype=np.float64),
+             'counts': np.array([t[2] for t in catch.traps], dtype=np.int32),
+             'levels': np.array(catch.levels, dtype=np.float64)}
+    save_maps(outfile, maps, extra)
+    return {'traps': [list(t) for t in catch.traps], 'levels': list(catch.levels),
+            'members': catch.summary.members, 'total_weight': catch.summary.total_weight, 'outputs': outs}
+
+
 # ------------------------------------------------------------------ traces
 def model_names():
     return [m[0] for m in mcmc.MODEL_BLOCK]
@@ -3117,7 +3464,7 @@ def save_maps(outfile, maps, extra=None, signed=False):
     '''outfile.npz in the layout of Run.save_result (Run.py:490-516 of the reference), which
     Plot_Result.main reads.  maps: [(day label, [(suffix, N x N array), ...]), ...] -> per day and
     suffix the CSR triplet `{label}{suffix}_data/_ind/_indptr` of the array thresholded at 1e-8,
-    and `days` = the labels; extra: {key: array} written as given.  signed: keep the entries with
+    and `days` = the labels; extra: {key: array} written as given (a `days` of its own replaces the labels).  signed: keep the entries with
     |value| >= 1e-8, for maps that take either sign.  The directory is created if needed.'''
     from scipy import sparse
     out = dict(extra or {})
@@ -3129,7 +3476,7 @@ def save_maps(outfile, maps, extra=None, signed=False):
             out['%s%s_data' % (label, suffix)] = csr.data
             out['%s%s_ind' % (label, suffix)] = csr.indices
             out['%s%s_indptr' % (label, suffix)] = csr.indptr
-    out['days'] = np.array(labels)
+    out.setdefault('days', np.array(labels))
     d = os.path.dirname(str(outfile))
     if d and not os.path.exists(d):
         os.makedirs(d)
@@ -3303,12 +3650,14 @@ class PredictiveResult():
     over the summary's days and thresholds, and `reweight_info` = dict(names, probes -- as given, None for a
     scenario of row log-weights --, min_ess, diagnostics: {name: reweight_diagnostics + members, skipped,
     log_total_weight}), both None where not asked for (the projections and the plan then carry a `reweight` of
-    their own).'''
+    their own); `catch`: the CatchPosterior of the traps over the model's day fields, None where not asked for
+    (the emergence projection and the plan then carry a `catch` of their own where asked for).'''
 
     def __init__(self, summary, rows, evaluations, failed, seconds, runs, observations, provenance, days,
                  histogram=None, quantiles=None, arrival=None, arrival_levels=None, emergence=None, exposure=None,
                  sites=None, sensitivity=None, contrast=None, compare_plan=None, mc_error=None, mc_plan=None,
-                 peak=None, excursion=None, excursion_levels=None, reweight=None, reweight_info=None):
+                 peak=None, excursion=None, excursion_levels=None, reweight=None, reweight_info=None, catch=None):
+        self.catch = catch
         self.peak = peak
         self.excursion = excursion
         self.excursion_levels = excursion_levels
@@ -3377,6 +3726,10 @@ class PredictiveResult():
         block under `predictive.peak` (`predictive.sites.peak`) of the json.
         Excursion maps go into outfile_excur.npz (save_excursion; those of a release plan into
         outfile_sites_excur.npz), their block under `predictive.excursion` (`predictive.sites.excursion`).
+        Catch-probability maps go into outfile_catch.npz (save_catch; those of the emergence projection and of a
+        release plan into outfile_NAME_catch.npz), their block under `predictive.catch` (`predictive.NAME.catch`),
+        with the traps as given; their reweighted maps into outfile_catch_reweight.npz (save_reweight) and their
+        Monte Carlo error into outfile_mcerr.npz under the labels `catch_c{e}`.
         -> (npz path, json path)'''
         s = self.summary
         if s is None:
@@ -3497,6 +3850,17 @@ class PredictiveResult():
                 if pr is not None and pr.reweight is not None:
                     save_reweight('%s_%s_reweight' % (outfile, name), pr.reweight, list(range(len(pr.labels))),
                                   pr.labels)
+        area = getattr(self, 'cell_area', None)
+        for name, cp in [('', self.catch)] + [(n + '_', pr.catch) for n, pr in (
+                ('emergence', self.emergence), ('sites', self.sites)) if pr is not None]:
+            if cp is None:
+                continue
+            block = save_catch('%s_%scatch' % (outfile, name), cp, area)
+            block['given'] = cp.given
+            keys, labels = list(range(len(cp.traps))), ['c%d' % e for e in range(len(cp.traps))]
+            if cp.reweight is not None:
+                save_reweight('%s_%scatch_reweight' % (outfile, name), cp.reweight, keys, labels)
+            (meta['predictive'][name[:-1]] if name else meta['predictive'])['catch'] = block
         if self.mc_error is not None:
             mmaps = []
             labels = [s.pm.days[d] if d < len(s.pm.days) else d for d in s.days]
@@ -3506,6 +3870,12 @@ class PredictiveResult():
                 if pr is not None and pr.mc_error is not None:
                     block[name] = mc_error_block(pr.mc_error, list(range(len(pr.labels))), pr.labels, name + '_',
                                                  mmaps)
+            for name, cp in (('catch', self.catch),
+                             ('emergence_catch', None if self.emergence is None else self.emergence.catch),
+                             ('sites_catch', None if self.sites is None else self.sites.catch)):
+                if cp is not None and cp.mc_error is not None:
+                    block[name] = mc_error_block(cp.mc_error, list(range(len(cp.traps))),
+                                                 ['c%d' % e for e in range(len(cp.traps))], name + '_', mmaps)
             save_maps('%s_mcerr' % outfile, mmaps)
             meta['predictive']['mc_error'] = block
         with open(str(outfile) + '.json', 'w') as fobj:
@@ -3515,7 +3885,7 @@ class PredictiveResult():
 
 def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, locinfo, histogram=None,
                    arrival=None, projected=(), plan=None, sens=None, compare=None, mc=None, peak=None,
-                   excursion=None, reweight=None):
+                   excursion=None, reweight=None, catch=None):
     '''one chain: evaluate every run, add it to the summary (and the histogram, the arrival maps; projected:
     (Projection, ProjectedMaps) pairs, applied and then added; plan: a (ReleaseSites, ProjectedMaps) pair, the
     models of its later release days evaluated with the base model -- a member for which any of them fails is
@@ -3529,7 +3899,10 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
     excursion: the chain's ExcursionMaps, fed the run's weight right after the summary -- the plan's own after the
     plan's other accumulators; reweight: (the chain's ReweightedSummary, its _ReweightFeed) -- right after the
     summary the run's log-weights are taken, by one gather of all probes, and the member added with them and the
-    run's length, to every ProjectedMaps' own after its summary too) -> (expected per run or None, failed)'''
+    run's length, to every ProjectedMaps' own after its summary too; catch: the chain's CatchPosterior -- right after the summary and the
+    reweighted summary, whose log-weights it shares, its fields are applied and added with the run's length, its
+    Monte Carlo error sequences fed like the others; every ProjectedMaps' own after its other accumulators)
+    -> (expected per run or None, failed)'''
     expected = []
     failed = 0
 
@@ -3537,6 +3910,11 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
         for seq, w in zip(pair, mc_split(first, length, mc[1])):
             if w:
                 seq.add(w)
+
+    def catch_add(cp, first, length, lam):
+        cp.add(length, lam)
+        if cp.mc_error is not None and mc is not None:
+            mc_add(cp.mc_error, first, length)
     for first, length in run_list:
         theta = rows[first, model_cols]
         if evaluate is not None:
@@ -3567,6 +3945,8 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
         if reweight is not None:
             lam = reweight[1].log_weights(pm, first, length)
             reweight[0].add(lam, length)
+        if catch is not None:
+            catch_add(catch, first, length, lam)
         if excursion is not None:
             excursion.add(length)
         if mc is not None:
@@ -3590,6 +3970,8 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
                 maps.sensitivity.add(theta, length)
             if maps.histogram is not None:
                 maps.histogram.add(length)
+            if maps.catch is not None:
+                catch_add(maps.catch, first, length, lam)
         if plan is not None:
             plan[0].apply()
             plan[1].summary.add(length)
@@ -3602,6 +3984,8 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
             for acc in (plan[1].histogram, plan[1].arrival, plan[1].peak, plan[1].excursion):
                 if acc is not None:
                     acc.add(length)
+            if plan[1].catch is not None:
+                catch_add(plan[1].catch, first, length, lam)
         if compare is not None:
             compare[0].apply()
             compare[1].add(length)
@@ -3612,7 +3996,8 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
 def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, thresholds=(), locinfo=None,
                          cell_area=None, seed=0, evaluate=None, quantiles=None, bins=DEFAULT_BINS, edges=None,
                          arrival=None, arrival_levels=(0.05, 0.5, 0.95), emergence=None, exposure=None, sites=None,
-                         sensitivity=None, compare=None, mc_error=None, peak=None, excursion=None, reweight=None):
+                         sensitivity=None, compare=None, mc_error=None, peak=None, excursion=None, reweight=None,
+                         catch=None):
     '''Posterior predictive spread of one or more chains (`Sampler.save` files or (trace, names)
     pairs).  Burn and thin apply per chain; consecutive rows with identical model parameters are one
     evaluation weighted by the run's length.  pop_model: one PopModel or a list -- with several, one
@@ -3678,8 +4063,24 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     contrast and Monte Carlo error get none.  `reweight_info` carries per scenario the diagnostics of the row
     weights (reweight_diagnostics); a UserWarning where ess < min_ess (reweight['options'] = dict(min_ess=50)) --
     importance reweighting degrades as the new data disagree with the posterior -- and a ValueError naming a
-    scenario that is left without weight.  Without reweight= no call is added and `reweight` is None.'''
+    scenario that is left without weight.  Without reweight= no call is added and `reweight` is None.  catch:
+    dict(traps=[(day, rate[, n]), ...], levels=(0.5, 0.95), emergence=[(obs_day, rate[, n]), ...]) (check_catch;
+    not with evaluate=; bad arguments fail before any evaluation), the probability that a trap of effort `rate` on
+    model day `day` catches at least n, per cell, under the package's Poisson observation model.  Each chain then
+    also applies one CatchFields over the traps right after the summary's add and adds its fields, with the run's
+    length, to a SpreadSummary.for_projection whose thresholds are the levels; with mc_error= to two
+    MonteCarloError.for_projection of its own, with reweight= to a ReweightedSummary.for_projection fed the same
+    log-weights; merged in chain order into `catch` (a CatchPosterior).  The `emergence` key needs emergence= and
+    puts a CatchPosterior over the emergence projection's outputs, the trap's day one of its labels, into
+    `emergence.catch`: sentinel fields measure emergence, so this is the forward map of the data the chain was
+    fitted to.  With sites= the plan gets one of its own over the same traps, whose days have to be output days
+    of the plan, in `sites.catch`.  Histogram, arrival, peak, excursion, sensitivity and contrast of the catch
+    fields are not computed.  Without catch= no call is added and `catch` is None.'''
     t0 = time.perf_counter()
+    ct_plan = None
+    if catch is not None:             # bad catch arguments fail before any evaluation
+        pm0 = (pop_model[0] if pop_model else None) if isinstance(pop_model, (list, tuple)) else pop_model
+        ct_plan = check_catch(catch, None if pm0 is None else len(pm0.days), emergence, evaluate)
     rw_plan = None
     if reweight is not None:          # bad reweighting arguments fail before any evaluation
         if evaluate is not None:
@@ -3730,6 +4131,11 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         site_plan = sites_plan(sites, pm0)
         if pm0 is None:
             site_plan = None
+        elif ct_plan is not None:
+            off = [t for t in ct_plan['traps'] if t[0] not in site_plan[1]]
+            if off:
+                raise ValueError('catch: trap %r is not on an output day of the release plan %r'
+                                 % (off[0], list(site_plan[1])))
     cmp_plan = None
     if compare is not None:           # and a bad plan B, or one without a plan A to compare with
         pm0 = (pop_model[0] if pop_model else None) if isinstance(pop_model, (list, tuple)) else pop_model
@@ -3773,6 +4179,8 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     excurs = [None] * nch                      # per chain its ExcursionMaps
     mcs = [None] * nch                         # per chain its two MonteCarloError sequences
     rws = [None] * nch                         # per chain (ReweightedSummary, _ReweightFeed)
+    catches = [None] * nch                     # per chain its CatchPosterior over the day fields
+    rw_names = rw_plan['names'] if rw_plan is not None else None
     projected = [[] for _ in range(nch)]       # per chain (Projection, ProjectedMaps) of every plan
     site_maps = [None] * nch                   # per chain (ReleaseSites, ProjectedMaps)
     cmp_maps = [None] * nch                    # per chain (ReleaseSites of plan B, PlanContrast, the lagged models)
@@ -3806,6 +4214,8 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                 if rw_plan is not None:
                     rws[ci] = (ReweightedSummary(pm, rw_plan['names'], summ.days, thresholds),
                                _ReweightFeed(rw_plan, ci))
+                if ct_plan is not None:
+                    catches[ci] = CatchPosterior(CatchFields(pm, ct_plan['traps']), ct_plan['levels'], mc_b, rw_names)
                 if evaluate is None:
                     for _name, W, in_days, labels in plans:
                         proj = Projection(pm, W, in_days)
@@ -3822,6 +4232,9 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                             maps.mc_error = []
                             for _half in range(2):
                                 maps.mc_error.append(MonteCarloError.for_projection(proj, mc_b, thresholds))
+                        if _name == 'emergence' and ct_plan is not None and ct_plan['emergence']:
+                            maps.catch = CatchPosterior(CatchFields.for_projection(proj, ct_plan['emergence'], labels),
+                                                        ct_plan['levels'], mc_b, rw_names)
                     if site_plan is not None:
                         if p not in late:
                             # once per model, for the union of both plans' release days
@@ -3849,6 +4262,9 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                             maps.mc_error = []
                             for _half in range(2):
                                 maps.mc_error.append(MonteCarloError.for_projection(rs, mc_b, thresholds))
+                        if ct_plan is not None:
+                            maps.catch = CatchPosterior(CatchFields.for_projection(rs, ct_plan['traps']),
+                                                        ct_plan['levels'], mc_b, rw_names)
                         if cmp_plan is not None:
                             rb = ReleaseSites(pm, compare['sites'], site_plan[1], late[p])
                             cmp_maps[ci] = (rb, None, late[p])
@@ -3856,7 +4272,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                 results[ci] = _evaluate_runs(pm, summ, rows, rl, mcols, evaluate, want_obs, locinfo, hist, arr,
                                              projected[ci], site_maps[ci], sens, cmp_maps[ci],
                                              (mcs[ci], mc_halves[ci][0]) if mc_b else None, peaks[ci],
-                                             excursion=excurs[ci], reweight=rws[ci])
+                                             excursion=excurs[ci], reweight=rws[ci], catch=catches[ci])
         except BaseException as e:       # re-raised in the caller's thread
             errs.append((p, e))
 
@@ -3871,7 +4287,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         pms = pms[:1]
         work(0)
     if errs:
-        for s in summaries + histograms + arrivals + senses + peaks + excurs + [pair[0] for pair in rws if pair] + [x for pair in mcs if pair for x in pair] + [x for pl in projected for pair in pl for x in pair] \
+        for s in summaries + histograms + arrivals + senses + peaks + excurs + catches + [pair[0] for pair in rws if pair] + [x for pair in mcs if pair for x in pair] + [x for pl in projected for pair in pl for x in pair] \
                 + [x for pair in site_maps if pair is not None for x in pair] \
                 + [x for tri in cmp_maps if tri is not None for x in tri[:2]] \
                 + [m for made in late.values() for m in made.values()]:
@@ -3920,6 +4336,26 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         for a, _feed in rws[1:]:
             rw_maps.merge(a)
             a.close()
+
+    def merge_catch(cps):
+        '''the chains' CatchPosteriors merged in chain order into the first: the Monte Carlo error sequences
+        pooled, the fields -- the accumulators hold what they need -- and the other chains' accumulators closed'''
+        if not cps or cps[0] is None:
+            return None
+        first = cps[0]
+        first.given = ct_plan['given']
+        if mc_b:
+            pooled = pool_mc_error([c.mc_error for c in cps])
+            for c in cps:
+                c.mc_error = None
+            first.mc_error = pooled
+        for c in cps:
+            c.fields.close()
+        for c in cps[1:]:
+            first.merge(c)
+            c.close()
+        return first
+    catch_maps = merge_catch(catches) if ct_plan is not None else None
     mc_pooled = mc_desc = None
     if mc_b:
         mc_pooled = pool_mc_error(mcs)
@@ -3932,6 +4368,11 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                 pl[k][1].mc_error = None
             projected[0][k][1].mc_error = pooled
         merged[plan[0]] = projected[0][k][1]
+        if projected[0][k][1].catch is not None:      # before the projections close: it reads their fields
+            cps = [pl[k][1].catch for pl in projected]
+            for pl in projected[1:]:
+                pl[k][1].catch = None
+            merged[plan[0]].catch = merge_catch(cps)
         for pl in projected[1:]:
             merged[plan[0]].merge(pl[k][1])
             pl[k][1].close()
@@ -3947,6 +4388,11 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                 maps.mc_error = None
             site_maps[0][1].mc_error = pooled
         merged_sites = site_maps[0][1]
+        if merged_sites.catch is not None:
+            cps = [maps.catch for _rs, maps in site_maps]
+            for _rs, maps in site_maps[1:]:
+                maps.catch = None
+            merged_sites.catch = merge_catch(cps)
         for _rs, maps in site_maps[1:]:
             merged_sites.merge(maps)
             maps.close()
@@ -3976,7 +4422,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         empty = [n for n in rw_plan['names'] if diag[n]['members'] == 0]
         if empty:
             for m in [summary, histogram, arrival_maps, sens_maps, peak_maps, excur_maps, rw_maps, mc_pooled,
-                      contrast] + list(merged.values()) + [merged_sites]:
+                      contrast, catch_maps] + list(merged.values()) + [merged_sites]:
                 if m is not None:
                     m.close()
             raise ValueError('reweight: scenario %r is left without weight (W = 0): no member is compatible with it'
@@ -4008,7 +4454,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                            None if summary is None else summary.days, histogram, levels, arrival_maps,
                            a_levels if a_thr else None, merged.get('emergence'), merged.get('exposure'),
                            merged_sites, sens_maps, contrast, compare_desc, mc_pooled, mc_desc, peak_maps,
-                           excur_maps, ex_levels if ex_thr else None, rw_maps, rw_info)
+                           excur_maps, ex_levels if ex_thr else None, rw_maps, rw_info, catch_maps)
     if cell_area is not None:
         res.cell_area = float(cell_area)
     return res

@@ -26,7 +26,10 @@ named scenarios, each a list of probe observations 'east,north,day,kind,rate[,n]
 found n, none, found; rate: the expected number found per wasp in the cell) or a .npy file of one log-weight per
 chain row after burn and thin (several chains: concatenated in chain order), by importance reweighting of the
 members, with the effective sample size of every scenario in the json -- saved as PREFIX_reweight.npz (and
-PREFIX_NAME_reweight.npz for every projection and plan asked for).  Kalbar wind and
+PREFIX_NAME_reweight.npz for every projection and plan asked for); with --catch also the catch-probability maps --
+per trap 'DAY,RATE[,N]' and cell the posterior mean, sd and the probability (--catch-levels) that a trap of effort
+RATE on model day DAY catches at least N wasps; --catch-emergence: traps over the emergence days of --emergence --
+saved as PREFIX_catch.npz (and PREFIX_emergence_catch.npz, PREFIX_sites_catch.npz).  Kalbar wind and
 LocInfo as scripts/run_mcmc.py loads them; --synthetic uses the synthetic Kalbar-like observations.
 Without --chain a short chain is sampled first (--samples) and saved next to --out.
 
@@ -38,6 +41,7 @@ Without --chain a short chain is sampled first (--samples) and saved next to --o
         [--compare-sites 'E,N,AMOUNT[,LAG];...'] [--peak 1,10] [--peak-levels 0.05,0.5,0.95]
         [--excursion 1,10] [--excursion-levels 0.9,0.95]
         [--reweight 'NAME:east,north,day,kind,rate[,n];...'] [--reweight-file NAME=weights.npy]
+        [--catch 'DAY,RATE[,N];...'] [--catch-levels 0.5,0.95] [--catch-emergence 'OBSDAY,RATE[,N];...']
 """
 import argparse
 import json
@@ -129,6 +133,11 @@ def main():
                                                     '(default: off)')
     ap.add_argument('--excursion-levels', default='0.9,0.95',
                     help='credible levels in (0.5, 1] of the saved excursion regions and areas (with --excursion)')
+    ap.add_argument('--catch', default='', help="traps 'DAY,RATE[,N];...': per cell the probability that a trap of "
+                    'effort RATE on model day DAY catches at least N (default 1) (default: off)')
+    ap.add_argument('--catch-levels', default='0.5,0.95', help='levels of the catch maps (with --catch)')
+    ap.add_argument('--catch-emergence', default='', help="traps 'OBSDAY,RATE[,N];...' over the emergence days of "
+                    '--emergence (with --catch)')
     ap.add_argument('--reweight', action='append', default=None, metavar='NAME:PROBES',
                     help="a reweighting scenario of probe observations 'NAME:east,north,day,kind,rate[,n];...' "
                          '(repeatable; at most 4 scenarios with --reweight-file; default: off)')
@@ -189,6 +198,16 @@ def main():
                               for site in args.compare_sites.split(';') if site.strip()])
         contrast_plan(compare, sites)    # as does a bad --compare-sites
         check_contrast_thresholds([float(t) for t in args.thresholds.split(',') if t.strip()])
+    catch = None
+    if args.catch:                       # as do bad --catch traps or levels
+        from parasitoids_amd.predictive import check_catch, parse_traps
+        catch = dict(traps=parse_traps(args.catch),
+                     levels=[float(q) for q in args.catch_levels.split(',') if q.strip()])
+        if args.catch_emergence:
+            catch['emergence'] = parse_traps(args.catch_emergence)
+        check_catch(catch, None, emergence)
+    elif args.catch_emergence:
+        ap.error('--catch-emergence needs --catch')
     wd, days = PM.get_wind_data(os.path.join(ROOT, 'parasitoids_amd', 'data', 'kalbar'), 30, '00:00')
 
     def make_pm():
@@ -240,7 +259,8 @@ def main():
                                quantiles=levels or None, bins=bins, arrival=arrival or None, arrival_levels=a_levels,
                                emergence=emergence, exposure=exposure, sites=sites, sensitivity=sens,
                                compare=compare, mc_error=mc_error, peak=peak, excursion=excursion,
-                               **({'reweight': reweight} if reweight else {}))
+                               **({'reweight': reweight} if reweight else {}),
+                               **({'catch': catch} if catch else {}))
     dt = time.perf_counter() - t0
     # accumulate-kernel time: the same members once more with HIP events around every add
     from parasitoids_amd.predictive import (ArrivalMaps, ExcursionMaps, MonteCarloError, PeakMaps, PlanContrast, Projection,
@@ -272,6 +292,16 @@ def main():
         RW = ReweightedSummary(pm, rw_plan['names'], None, thr)
         RWF = _ReweightFeed(rw_plan, 0)
         RW.profile(True)
+    CF = CP = None
+    if catch:                            # and a Projection of as many outputs: the same bytes, a plain streaming pass
+        from parasitoids_amd.predictive import CatchFields
+        import numpy as np
+        CF = CatchFields(pm, catch['traps'])
+        Wc = np.zeros((CF.nout, len(CF.in_days)))
+        Wc[np.arange(CF.nout), [CF.in_days.index(t[0]) for t in CF.traps]] = 1.0
+        CP = Projection(pm, Wc, CF.in_days)
+        CF.profile(True)
+        CP.profile(True)
     with SpreadSummary(pm, None, thr) as S:
         S.profile(True)
         if H is not None:
@@ -308,6 +338,9 @@ def main():
                 except Exception:
                     continue
                 S.add(length)
+                if CF is not None:
+                    CF.apply()
+                    CP.apply()
                 if RW is not None:
                     RW.add(RWF.log_weights(pm, first, length), length)
                 if ME is not None:
@@ -349,6 +382,12 @@ def main():
         ex_ms, ex_launches = EX.profile()[:2]
         EX.close()
         res.excursion.profile(True)     # the finalize and every map launch of the save
+    if CF is not None:
+        cf_ms, cf_launches = CF.profile()
+        cp_ms, cp_launches = CP.profile()
+        cf_bytes = CF.nbytes
+        CF.close()
+        CP.close()
     if RW is not None:
         rw_ms, rw_launches = RW.profile()
         rw_bytes = RW.nbytes
@@ -391,6 +430,15 @@ def main():
            'days': nday, 'thresholds': thr, 'chains': len(chains), 'chains_parallel': len(pms) > 1,
            'bayes_evaluations_per_hour': None if bayes_rate is None else round(bayes_rate, 1),
            'outputs': [npz, js]}
+    if catch:
+        out['catch_ms_per_member'] = round(cf_ms / max(cf_launches, 1), 4)
+        out['catch_launches_timed'] = cf_launches
+        out['catch_outputs'] = len(catch['traps'])
+        out['catch_projection_ms_per_member'] = round(cp_ms / max(cp_launches, 1), 4)   # same nout, same bytes
+        out['catch_bytes'] = cf_bytes
+        out['outputs'] += ['%s_catch.npz' % args.out] \
+            + (['%s_emergence_catch.npz' % args.out] if catch.get('emergence') else []) \
+            + (['%s_sites_catch.npz' % args.out] if sites else [])
     if reweight:
         out['reweight_ms_per_member'] = round(rw_ms / max(rw_launches, 1), 4)
         out['reweight_launches_timed'] = rw_launches
@@ -477,7 +525,7 @@ def main():
         res.sensitivity.close()
     if res.mc_error is not None:
         res.mc_error.close()
-    for pr in (res.emergence, res.exposure, res.sites, res.contrast, res.peak, res.excursion):
+    for pr in (res.emergence, res.exposure, res.sites, res.contrast, res.peak, res.excursion, res.catch):
         if pr is not None:
             pr.close()
     for p in pms:
