@@ -1008,6 +1008,82 @@ int ps_summary_add_catch(ps_summary* a, ps_catch* c, uint32_t weight);
 int ps_mcerr_add_catch(ps_mcerr* h, ps_catch* c, uint32_t weight);
 int ps_wsum_add_catch(ps_wsum* h, ps_catch* c, int nscen, const double* rescale, const double* omega);
 
+/* ---- trap information fields: how much a catch at each cell would teach ----
+ * (no reference counterpart; the Poisson model is that of the package's own likelihood, mcmc.loglik_parts.)
+ * The mutual information between a trap's count and the identity of the ensemble member: where it is large a
+ * reading separates the members, where it is 0 -- on the release point as outside every plume -- it separates
+ * none.  It equals the expected Kullback-Leibler divergence from today's posterior to the reweighted posterior
+ * (ps_wsum) after the reading.  A handle lives on one device and holds ntrap traps over nin inputs (1..32): trap
+ * e is (input[e], rate[e], ymax[e]) with 0 <= input[e] < nin, rate finite and > 0 and ymax a whole number in
+ * 0..15 (PS_ERR_BAD_ARG otherwise).  The trap's count is observed as the classes 0, 1, .., ymax and
+ * ">= ymax + 1"; ymax = 0 is the found / none trap.  Trap e owns ymax[e] + 3 consecutive fp64 planes [pitch]
+ * (pitch as ps_summary), in the caller's order; at most 32 planes in all, the slots of one accumulator
+ * (PS_ERR_BAD_ARG beyond).  The planes and three result maps per trap, (nplane + 3 ntrap) * pitch * 8 B, are
+ * checked against the free device memory first: PS_ERR_OOM before anything is allocated.  With v the value of
+ * input[e] at a cell and mu = rate[e] * v (one rounded product), an apply overwrites every cell of every plane
+ * of the trap by these statements, one IEEE double rounding each (never fused), exp, expm1 and log the device
+ * library's, catch_value the statements of the ps_catch block above:
+ *   not (mu > 0):  every plane +0.0
+ *   mu >= 800:     d0 = 1;  p_y = 0;  tail = 1;  h = 0
+ *   else:          nm = -mu;  x = expm1(nm);  d0 = -x;  e = exp(nm);  h = e * mu;  t = e
+ *                  for y = 1..ymax:  t = t * mu;  t = t / y;  p_y = t;
+ *                                    if t > 0:  l = log(t);  x = t * l;  h = h - x
+ *                  q = catch_value(mu, ymax + 1);  tail = q
+ *                  if q > 0:  l = log(q);  x = q * l;  h = h - x
+ * The planes in order: d0 = 1 - P(count = 0), stored as this deficit so that every plane is exactly +0.0 where
+ * v == 0; p_1 .. p_ymax; tail = P(count >= ymax + 1); h, the entropy in nats of this member's class
+ * distribution.  One thread owns a pair of cells (the tail cell of an odd N * N alone); the traps are grouped by
+ * input, so a record is read once however many traps use it; a pair whose values are both zero writes zeros
+ * without touching the transcendental path.  No atomics, one writer per cell; neither grid nor block shape
+ * changes a bit.  Every operation records an event the next one waits on, whichever stream it runs on (the
+ * solver's for ps_gain_apply, the handle's own for the other applies, finish, fetch and gather, the
+ * accumulator's for the _add_gain entry points). */
+typedef struct ps_gain ps_gain;
+int ps_gain_create(int device, int N, int nin, int ntrap, const int32_t* input /* ntrap */,
+                   const double* rate /* ntrap */, const int32_t* ymax /* ntrap */, ps_gain** out);
+/* The inputs are records of solver s (same device, same N; arguments as ps_project_apply, nin must equal the
+ * handle's; v is the value ps_summary_add adds, bit for bit): one launch on the solver's stream, no host
+ * synchronisation, nothing copied or allocated. */
+int ps_gain_apply(ps_gain* c, ps_solver* s, int nin, const int32_t* kind, const int32_t* idx,
+                  const double* stat_scale, const double* post_scale, const int32_t* use_delta, double negval);
+/* The inputs are the current outputs of a projection or a release plan: input i is the source's output i, so
+ * nin must equal its nout, and device and N must agree (PS_ERR_BAD_ARG, nothing enqueued); PS_ERR_STATE before
+ * the source's first apply.  One launch on the handle's stream behind the source's last operation; the source's
+ * next apply waits for the read. */
+int ps_gain_apply_project(ps_gain* c, ps_project* p);
+int ps_gain_apply_sites(ps_gain* c, ps_sites* p);
+/* One member whose values are the handle's current planes: slot k takes plane k, through the accumulator's own
+ * add kernel, as ps_summary_add_catch / ps_wsum_add_catch; the accumulator's slot count must equal the number
+ * of planes.  The posterior mean of a p_y plane is then the posterior predictive probability of that class, the
+ * mean of h is H(count | member). */
+int ps_summary_add_gain(ps_summary* a, ps_gain* c, uint32_t weight);
+int ps_wsum_add_gain(ps_wsum* h, ps_gain* c, int nscen, const double* rescale, const double* omega);
+/* The three maps of every trap from the mean planes m_k of an accumulator fed by the _add_gain entry points
+ * (of a ps_wsum: those of one scenario), read on the device -- slots, device and N must agree (PS_ERR_BAD_ARG,
+ * nothing enqueued), PS_ERR_STATE while the accumulator is empty.  Per cell and trap, m_0 .. m_{ymax+2} the
+ * trap's planes, every line a statement of its own:
+ *   P0 = 1 - m_0;  HY = 0;  for P in (P0, m_1, .., m_{ymax+1}):  if P > 0:  l = log(P);  x = P * l;  HY = HY - x
+ *   HYM = m_{ymax+2};  G = HY - HYM;  if not (G > 0):  G = +0.0
+ * One launch on the handle's stream behind the accumulator's last operation; the accumulator's next operation
+ * waits for the read.  The maps of an earlier finish are overwritten. */
+int ps_gain_finish_summary(ps_gain* c, ps_summary* a);
+int ps_gain_finish_wsum(ps_gain* c, ps_wsum* h, int scenario);
+/* one plane of the last apply to the host, 0 <= plane < the number of planes (synchronises).  PS_ERR_STATE
+ * before the first apply. */
+int ps_gain_fetch(ps_gain* c, int plane, double* out /* N*N */);
+/* one map of the last finish to the host: what 0 the gain G (the mutual information in nats), 1 the entropy HY
+ * of the posterior predictive class distribution, 2 the conditional entropy HYM (synchronises).  PS_ERR_STATE
+ * before the first finish. */
+int ps_gain_fetch_result(ps_gain* c, int trap, int what, double* out /* N*N */);
+/* the planes at n listed cells: out[k * n + i] = plane k at (rows[i], cols[i]) (synchronises).
+ * PS_ERR_BAD_ARG for a cell outside the domain, PS_ERR_STATE before the first apply. */
+int ps_gain_gather(ps_gain* c, int64_t n, const int32_t* rows, const int32_t* cols, double* out /* nplane x n */);
+/* any pointer may be NULL */
+int ps_gain_info(ps_gain* c, int* N, int* nin, int* ntrap, int* nplane, int64_t* applies);
+/* measurement: HIP-event timing of the apply launches, as ps_catch_prof */
+int ps_gain_prof(ps_gain* c, int enable, double* total_ms, int64_t* launches);
+void ps_gain_destroy(ps_gain* c);
+
 #ifdef __cplusplus
 }
 #endif

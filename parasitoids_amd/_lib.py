@@ -277,6 +277,20 @@ SIGNATURES = {
     'ps_summary_add_catch': (C.c_int, [_VP, _VP, C.c_uint32]),
     'ps_mcerr_add_catch': (C.c_int, [_VP, _VP, C.c_uint32]),
     'ps_wsum_add_catch': (C.c_int, [_VP, _VP, C.c_int, _F64P, _F64P]),
+    'ps_gain_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _I32P, _F64P, _I32P, C.POINTER(_VP)]),
+    'ps_gain_apply': (C.c_int, [_VP, _VP, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P, C.c_double]),
+    'ps_gain_apply_project': (C.c_int, [_VP, _VP]),
+    'ps_gain_apply_sites': (C.c_int, [_VP, _VP]),
+    'ps_summary_add_gain': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_wsum_add_gain': (C.c_int, [_VP, _VP, C.c_int, _F64P, _F64P]),
+    'ps_gain_finish_summary': (C.c_int, [_VP, _VP]),
+    'ps_gain_finish_wsum': (C.c_int, [_VP, _VP, C.c_int]),
+    'ps_gain_fetch': (C.c_int, [_VP, C.c_int, _F64P]),
+    'ps_gain_fetch_result': (C.c_int, [_VP, C.c_int, C.c_int, _F64P]),
+    'ps_gain_gather': (C.c_int, [_VP, C.c_int64, _I32P, _I32P, _F64P]),
+    'ps_gain_info': (C.c_int, [_VP, _I32P, _I32P, _I32P, _I32P, _I64P]),
+    'ps_gain_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P]),
+    'ps_gain_destroy': (None, [_VP]),
 }
 
 _lib = None

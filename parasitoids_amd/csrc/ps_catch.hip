@@ -14,13 +14,11 @@
 #include <utility>
 #include <vector>
 
+#include "ps_catch_value.h"   // catch_value: P(Poisson(mu) >= n), shared with ps_gain.hip
 #include "ps_common.h"
 
 #define PS_CATCH_MAX_IN 32     // one launch's descriptors: 32 x 32 B of kernel arguments
 #define PS_CATCH_MAX_OUT 32
-#define PS_CATCH_MAX_COUNT 16
-#define PS_CATCH_TERMS 56      // of the upper series: enough for count <= 16 at mu -> count
-#define PS_CATCH_SURE 800.0    // exp(-mu) == 0 from 746 on: the value is 1.0 exactly
 #define PS_CATCH_THREADS 256
 
 namespace {
@@ -42,47 +40,6 @@ struct CatchTab {
   int gstart[PS_CATCH_MAX_OUT + 1];
   int ngroup, pad_;
 };
-
-// P(Poisson(mu) >= n), n in 1..16; every step a statement of its own (one rounding each), as the header states
-// them and tests/catch_ref.py repeats them.  The series stops where a term no longer changes the sum: every
-// later term is smaller (mu < n), so the 56 terms of the restatement give the same bits.
-__device__ inline double catch_value(double mu, int n) {
-  if (!(mu > 0.0)) return 0.0;
-  if (mu >= PS_CATCH_SURE) return 1.0;
-  const double nm = -mu;
-  if (n == 1) {
-    const double x = expm1(nm);
-    return -x;
-  }
-  const double e = exp(nm);
-  if (mu < (double)n) {
-    double t = 1.0;
-    for (int i = 1; i <= n; ++i) {
-      t = t * mu;
-      t = t / (double)i;
-    }
-    double s = 1.0, u = 1.0;
-    for (int j = 1; j <= PS_CATCH_TERMS; ++j) {
-      const double r = mu / (double)(n + j);
-      u = u * r;
-      const double s1 = s + u;
-      if (s1 == s) break;
-      s = s1;
-    }
-    t = t * s;
-    const double y = t * e;
-    return y > 1.0 ? 1.0 : y;
-  }
-  double u = 1.0, q = 1.0;
-  for (int i = 1; i < n; ++i) {
-    u = u * mu;
-    u = u / (double)i;
-    q = q + u;
-  }
-  const double p = e * q;
-  const double y = 1.0 - p;
-  return y < 0.0 ? 0.0 : y;
-}
 
 // thread j owns the cells 2j, 2j + 1 (j == npair: the tail cell of an odd N*N alone)
 __global__ void __launch_bounds__(PS_CATCH_THREADS) k_catch_apply(CatchSlots desc, CatchTab tab, double* __restrict__ Y,

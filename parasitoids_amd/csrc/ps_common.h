@@ -145,6 +145,22 @@ PsFieldsOps ps_project_fields();
 PsFieldsOps ps_sites_fields();
 PsFieldsOps ps_peak_fields();    // the last member's peak field of a ps_peak (ps_peak.hip): nout = 1
 PsFieldsOps ps_catch_fields();   // the catch-probability fields of a ps_catch (ps_catch.hip)
+PsFieldsOps ps_gain_fields();    // the class-probability and entropy planes of a ps_gain (ps_gain.hip)
+
+// the mean planes of an accumulator as ps_gain.hip's finish reads them on the device (ps_summary.hip; ps_wsum.hip
+// per scenario); PS_ERR_STATE while nothing is accumulated.  The reader orders its stream behind the accumulator's
+// last operation (wait) and the accumulator's next operation behind the read (done).
+struct PsMeanView {
+  const double* mean;           // [nslot][pitch], device
+  int64_t pitch;
+  int N, nslot, device;
+};
+int ps_summary_mean_internal(ps_summary* a, PsMeanView* out);
+int ps_summary_mean_wait_internal(ps_summary* a, hipStream_t stream);
+int ps_summary_mean_done_internal(ps_summary* a, hipStream_t stream);
+int ps_wsum_mean_internal(ps_wsum* a, int scenario, PsMeanView* out);
+int ps_wsum_mean_wait_internal(ps_wsum* a, hipStream_t stream);
+int ps_wsum_mean_done_internal(ps_wsum* a, hipStream_t stream);
 
 // the value one solver record holds at a cell, as ps_record_fetch_* returns it (k_compact_rows,
 // chain_kernels.h), 0 where it returns no entry; shared by ps_summary.hip and ps_linspread.hip

@@ -280,6 +280,20 @@ extern "C" int ps_summary_add_catch(ps_summary* a, ps_catch* p, uint32_t weight)
   return sum_add_fields(a, p, ps_catch_fields(), "summary_add_catch", weight);
 }
 
+extern "C" int ps_summary_add_gain(ps_summary* a, ps_gain* p, uint32_t weight) {
+  return sum_add_fields(a, p, ps_gain_fields(), "summary_add_gain", weight);
+}
+
+// the mean planes for ps_gain.hip's finish: nothing is computed or changed here
+int ps_summary_mean_internal(ps_summary* a, PsMeanView* out) {
+  if (!a || !out) return ps_fail(PS_ERR_BAD_ARG, "summary mean view: null handle");
+  if (a->W == 0) return ps_fail(PS_ERR_STATE, "nothing accumulated (W = 0): add members to the summary first");
+  *out = PsMeanView{a->mean, a->pitch, a->N, a->nslot, a->device};
+  return PS_OK;
+}
+int ps_summary_mean_wait_internal(ps_summary* a, hipStream_t stream) { return after_last(a, stream); }
+int ps_summary_mean_done_internal(ps_summary* a, hipStream_t stream) { return mark_last(a, stream); }
+
 extern "C" int ps_summary_merge(ps_summary* dst, ps_summary* src) {
   if (!dst || !src || dst == src) return ps_fail(PS_ERR_BAD_ARG, "summary_merge: bad arguments");
   if (dst->device != src->device || dst->N != src->N || dst->nslot != src->nslot || dst->nthr != src->nthr)

@@ -391,6 +391,23 @@ extern "C" int ps_wsum_add_catch(ps_wsum* a, ps_catch* p, int nscen, const doubl
   return ws_add_fields(a, p, ps_catch_fields(), "wsum_add_catch", nscen, rescale, omega);
 }
 
+extern "C" int ps_wsum_add_gain(ps_wsum* a, ps_gain* p, int nscen, const double* rescale, const double* omega) {
+  return ws_add_fields(a, p, ps_gain_fields(), "wsum_add_gain", nscen, rescale, omega);
+}
+
+// one scenario's mean planes for ps_gain.hip's finish: nothing is computed or changed here
+int ps_wsum_mean_internal(ps_wsum* a, int scenario, PsMeanView* out) {
+  if (!a || !out) return ps_fail(PS_ERR_BAD_ARG, "wsum mean view: null handle");
+  if (scenario < 0 || scenario >= a->nscen)
+    return ps_fail(PS_ERR_BAD_ARG, "wsum mean view: scenario %d of %d", scenario, a->nscen);
+  if (a->W[scenario] == 0.0)
+    return ps_fail(PS_ERR_STATE, "nothing accumulated in scenario %d (W = 0): add members first", scenario);
+  *out = PsMeanView{ws_mean(a, scenario), a->pitch, a->N, a->nslot, a->device};
+  return PS_OK;
+}
+int ps_wsum_mean_wait_internal(ps_wsum* a, hipStream_t stream) { return ws_after_last(a, stream); }
+int ps_wsum_mean_done_internal(ps_wsum* a, hipStream_t stream) { return ws_mark_last(a, stream); }
+
 extern "C" int ps_wsum_merge(ps_wsum* dst, ps_wsum* src, const double* ra, const double* rb) {
   if (!dst || !src || !ra || !rb) return ps_fail(PS_ERR_BAD_ARG, "wsum_merge: bad arguments");
   if (dst == src) return ps_fail(PS_ERR_BAD_ARG, "wsum_merge: dst and src are the same handle");

@@ -43,6 +43,9 @@ every other map is marginal in space and cannot say with which probability all c
 least n wasps at every cell (ps_catch_*, csrc/ps_catch.hip), under the Poisson model of the package's own likelihood;
 `SpreadSummary.for_projection`, `MonteCarloError.for_projection` and `ReweightedSummary.for_projection` accumulate it
 per member (`CatchPosterior`) -- the transform is not linear in the density, so no saved map gives it.
+`InformationFields` turns one member's field into the whole class distribution of a described trap's count and its
+entropy (ps_gain_*, csrc/ps_gain.hip); from the accumulated means the device forms the mutual information between the
+count and the identity of the member (`InformationPosterior`): where a reading would change what we believe.
 """
 import ctypes as C
 import json
@@ -1345,11 +1348,14 @@ class ProjectedMaps():
     take the output day.  `excursion`: the ExcursionMaps.for_projection of a release plan's outputs (None unless
     asked for), whose maps take the output day.  `reweight`: the
     ReweightedSummary.for_projection (None unless asked for), which takes the scenario's name and the output index.
-    `catch`: the CatchPosterior over the outputs (None unless asked for), whose traps name an output label.'''
+    `catch`: the CatchPosterior over the outputs (None unless asked for), whose traps name an output label.
+    `information`: the InformationPosterior over the outputs (None unless asked for), likewise.'''
 
     def __init__(self, weights, in_days, labels, summary, histogram=None, arrival=None, plan=None,
-                 sensitivity=None, mc_error=None, peak=None, excursion=None, reweight=None, catch=None):
+                 sensitivity=None, mc_error=None, peak=None, excursion=None, reweight=None, catch=None,
+                 information=None):
         self.catch = catch
+        self.information = information
         self.peak = peak
         self.excursion = excursion
         self.reweight = reweight
@@ -1379,9 +1385,13 @@ class ProjectedMaps():
             self.reweight.merge(other.reweight)
         if self.catch is not None and other.catch is not None:       # the driver merges the chains' catches itself
             self.catch.merge(other.catch)
+        if self.information is not None and other.information is not None:   # as the catches
+            self.information.merge(other.information)
 
     def close(self):
         self.summary.close()
+        if self.information is not None:
+            self.information.close()
         if self.catch is not None:
             self.catch.close()
         if self.reweight is not None:
@@ -3372,6 +3382,354 @@ def save_catch(outfile, catch, cell_area=None):
             'members': catch.summary.members, 'total_weight': catch.summary.total_weight, 'outputs': outs}
 
 
+# ------------------------------------------------------------------ trap information: what a catch would teach
+MAX_GAIN_IN = 32           # ps_gain: the input records of one launch's descriptors
+MAX_GAIN_PLANES = 32       # the planes of all traps of one handle: the slots of one accumulator
+MAX_GAIN_YMAX = 15         # the largest count a trap resolves: the classes 0 .. ymax and ">= ymax + 1"
+
+
+def check_info_traps(traps, what='day'):
+    '''traps [(key, rate[, ymax=0]), ...] as [(key, rate, ymax), ...]: at least one trap, the key (a model day, or
+    the output label of a projection or plan) a whole number >= 0, rate finite and > 0, ymax a whole number in
+    0..15, and at most 32 planes in all, ymax + 3 per trap; ValueError otherwise'''
+    import math
+    try:
+        rows = [tuple(t) for t in traps]
+    except TypeError:
+        raise ValueError('traps must be a list of (%s, rate[, ymax]), got %r' % (what, traps))
+    if not rows:
+        raise ValueError('no traps; at least one is needed')
+    out = []
+    for t in rows:
+        if len(t) not in (2, 3):
+            raise ValueError('a trap is (%s, rate[, ymax]), got %r' % (what, t))
+        try:
+            key, rate, ymax = float(t[0]), float(t[1]), float(t[2]) if len(t) == 3 else 0.0
+        except (TypeError, ValueError):
+            raise ValueError('a trap is (%s, rate[, ymax]) of numbers, got %r' % (what, t))
+        if not (math.isfinite(key) and key == int(key) and key >= 0):
+            raise ValueError('trap %r: the %s must be a whole number >= 0' % (t, what))
+        if not (math.isfinite(rate) and rate > 0):
+            raise ValueError('trap %r: the rate must be finite and > 0' % (t,))
+        if not (math.isfinite(ymax) and ymax == int(ymax) and 0 <= ymax <= MAX_GAIN_YMAX):
+            raise ValueError('trap %r: ymax must be a whole number in 0..%d' % (t, MAX_GAIN_YMAX))
+        out.append((int(key), rate, int(ymax)))
+    planes = sum(t[2] + 3 for t in out)
+    if planes > MAX_GAIN_PLANES:
+        raise ValueError('the traps own %d planes (ymax + 3 each); at most %d fit one handle'
+                         % (planes, MAX_GAIN_PLANES))
+    return out
+
+
+def check_information(information, ndays=None, evaluate=None):
+    '''posterior_predictive's information= argument, dict(traps=[(day, rate[, ymax]), ...]) -> dict(traps, given):
+    the checked traps (check_info_traps) over model days < ndays and the argument as given for the json.
+    evaluate: posterior_predictive's evaluate=, which has no device fields.  ValueError otherwise.'''
+    if not isinstance(information, dict) or set(information) != {'traps'}:
+        raise ValueError('information must be dict(traps=[(day, rate[, ymax]), ...]), got %r' % (information,))
+    if evaluate is not None:
+        raise ValueError('information= needs the device: not with evaluate=')
+    traps = check_info_traps(information['traps'])
+    for t in traps:
+        if ndays is not None and t[0] >= ndays:
+            raise ValueError('trap %r: the model has %d days' % (t, ndays))
+    if len({t[0] for t in traps}) > MAX_GAIN_IN:
+        raise ValueError('the traps name more than %d days' % MAX_GAIN_IN)
+    return {'traps': traps, 'given': {'traps': [list(t) for t in information['traps']]}}
+
+
+def weight_entropy(weights):
+    '''-sum (w / W) log (w / W) of the member weights, in nats: the most any map of the ensemble can tell about
+    which member is true, so no information map can exceed it'''
+    w = np.asarray([x for x in weights if x > 0], dtype=np.float64)
+    if w.size == 0:
+        return 0.0
+    q = w / w.sum()
+    return float(-(q * np.log(q)).sum())
+
+
+class InformationFields():
+    '''One member's whole count distribution at every cell for traps the user describes, on the device
+    (ps_gain_*, csrc/ps_gain.hip): trap e = (day, rate[, ymax=0]) observes Poisson(rate v) as the classes 0, 1,
+    .., ymax and ">= ymax + 1" (ymax = 0: found / none), v the value SpreadSummary adds for that day, under the
+    package's own observation model (mcmc.loglik_parts).  Trap e owns ymax + 3 planes: 'd0' = 1 - P(0), 'p1' ..
+    'p{ymax}', 'tail' = P(>= ymax + 1) and 'h', the entropy of the class distribution in nats; every plane is
+    exactly 0 where v is 0.  At most 32 planes in all.  days: the model days the handle reads, default the traps'
+    own.  `for_projection` reads the outputs of a Projection or a ReleaseSites instead.  The statements are fixed
+    in include/parasitoid_hip.h (tests/gain_ref.py restates them).  SpreadSummary.for_projection and
+    ReweightedSummary.for_projection accept it, one slot per plane; InformationPosterior turns their means into
+    the information maps.'''
+    fields_kind = 'gain'         # the accumulators' entry points for these fields: ps_*_add_gain
+
+    def __init__(self, pop_model, traps, days=None):
+        self._h = L._VP()
+        self.traps = check_info_traps(traps)
+        used = sorted({t[0] for t in self.traps})
+        self.in_days = used if days is None else check_in_days(days)
+        if len(self.in_days) > MAX_GAIN_IN:
+            raise ValueError('%d input days; at most %d fit one handle' % (len(self.in_days), MAX_GAIN_IN))
+        missing = [d for d in used if d not in self.in_days]
+        if missing:
+            raise ValueError('trap days %r are not among the days %r' % (missing, self.in_days))
+        self._source = None
+        self._setup(pop_model, [self.in_days.index(t[0]) for t in self.traps], len(self.in_days))
+        self._kind, self._idx, self._delta = _day_slots(self.in_days)
+
+    @classmethod
+    def for_projection(cls, source, traps, labels=None):
+        '''The information fields of the outputs of `source` (a Projection or a ReleaseSites): a trap's first
+        entry is the source's output label (labels: one per output, default a ReleaseSites' output days, else the
+        output indices); `apply()` reads the outputs of the source's last apply.  An output without weight is
+        refused.'''
+        self = cls.__new__(cls)
+        self._h = L._VP()
+        self.traps = check_info_traps(traps, 'output')
+        if labels is None:
+            labels = getattr(source, 'days', None) if source.fields_kind == 'sites' else None
+        labels = list(range(source.nout)) if labels is None else [int(x) for x in labels]
+        if len(labels) != source.nout:
+            raise ValueError('%d labels for %d outputs' % (len(labels), source.nout))
+        slot = {e: i for i, e in enumerate(source.live)}        # the source's device slot of every output
+        inputs = []
+        for t in self.traps:
+            if t[0] not in labels or labels.index(t[0]) not in slot:
+                raise ValueError('trap %r: %d is not an output that carries weight (%r)' % (t, t[0], labels))
+            inputs.append(slot[labels.index(t[0])])
+        self.in_days = None
+        self._source = source
+        self._setup(source.pm, inputs, len(source.live))
+        return self
+
+    def _setup(self, pop_model, inputs, nin):
+        self._lib = L.load()
+        self.pm = pop_model
+        self.ntrap = len(self.traps)
+        self.rates = [t[1] for t in self.traps]
+        self.ymax = [t[2] for t in self.traps]
+        self.base = [sum(y + 3 for y in self.ymax[:e]) for e in range(self.ntrap)]
+        self.nout = sum(y + 3 for y in self.ymax)           # the planes: the slots of an accumulator over them
+        self.live = list(range(self.nout))
+        self.N = 2 * int(pop_model.rad_res) + 1
+        self.device = L.default_device() if pop_model.device is None else int(pop_model.device)
+        pitch = (self.N * self.N + 63) // 64 * 64
+        self.nbytes = (self.nout + 3 * self.ntrap) * pitch * 8      # the planes and three maps per trap
+        L.check(self._lib.ps_gain_create(self.device, self.N, int(nin), self.ntrap, L.p_i32(L.i32(inputs)),
+                                         L.p_f64(L.f64(self.rates)), L.p_i32(L.i32(self.ymax)), C.byref(self._h)))
+
+    def apply(self):
+        '''The planes of the last evaluation of the model (enqueued on the solver's stream), or of the source's
+        last apply (on the handle's stream); no host synchronisation; the planes of the previous apply are
+        overwritten.'''
+        if self._source is not None:
+            L.check(getattr(self._lib, 'ps_gain_apply_' + self._source.fields_kind)(self._h, self._source._h))
+            return
+        pm = self.pm
+        _check_evaluated(pm, self.in_days, 'information fields')
+        stat, post = _day_scales(pm, self.in_days)
+        L.check(self._lib.ps_gain_apply(self._h, pm.solver._h, len(self.in_days), L.p_i32(self._kind),
+                                        L.p_i32(self._idx), L.p_f64(stat), L.p_f64(post), L.p_i32(self._delta),
+                                        NEGVAL))
+
+    @property
+    def applies(self):
+        n = C.c_int64()
+        L.check(self._lib.ps_gain_info(self._h, None, None, None, None, C.byref(n)))
+        return n.value
+
+    def _e(self, e):
+        if not 0 <= int(e) < self.ntrap:
+            raise ValueError('trap %r of %d' % (e, self.ntrap))
+        return int(e)
+
+    def plane_names(self, e):
+        '''the names of trap e's planes: 'd0', 'p1' .. 'p{ymax}', 'tail' and 'h', in this order'''
+        return ['d0'] + ['p%d' % y for y in range(1, self.ymax[self._e(e)] + 1)] + ['tail', 'h']
+
+    def plane_index(self, e, name):
+        '''the handle's plane (an accumulator's slot) of trap e's plane `name`'''
+        names = self.plane_names(e)
+        if name not in names:
+            raise ValueError('plane %r of trap %d is not one of %r' % (name, e, names))
+        return self.base[int(e)] + names.index(name)
+
+    def plane(self, e, name):
+        '''[N, N] float64: plane `name` ('d0', 'p1' .., 'tail', 'h') of trap e of the last apply'''
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        L.check(self._lib.ps_gain_fetch(self._h, self.plane_index(e, name), L.p_f64(out)))
+        return out
+
+    def gather(self, rows, cols):
+        '''[planes, n] float64: every plane of the last apply at the cells (rows[k], cols[k])'''
+        rows, cols = L.i32(np.asarray(rows).ravel()), L.i32(np.asarray(cols).ravel())
+        if rows.size != cols.size:
+            raise ValueError('%d rows and %d columns' % (rows.size, cols.size))
+        out = np.zeros((self.nout, rows.size), dtype=np.float64)
+        L.check(self._lib.ps_gain_gather(self._h, rows.size, L.p_i32(rows), L.p_i32(cols), L.p_f64(out)))
+        return out
+
+    def finish(self, accumulator, scenario=None):
+        '''the information maps of every trap from the mean planes of `accumulator`, a
+        SpreadSummary.for_projection(self) or, with the scenario's name, a ReweightedSummary.for_projection(self);
+        on the device, no host synchronisation; `result` fetches them'''
+        if scenario is None:
+            L.check(self._lib.ps_gain_finish_summary(self._h, accumulator._h))
+        else:
+            L.check(self._lib.ps_gain_finish_wsum(self._h, accumulator._h, accumulator._j(scenario)))
+
+    def result(self, e, what):
+        '''[N, N] float64 of the last finish: what 'gain' (the mutual information in nats), 'entropy' (of the
+        posterior predictive class distribution) or 'conditional' (the mean entropy of the members')'''
+        names = ('gain', 'entropy', 'conditional')
+        if what not in names:
+            raise ValueError('%r is not one of %r' % (what, names))
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        L.check(self._lib.ps_gain_fetch_result(self._h, self._e(e), names.index(what), L.p_f64(out)))
+        return out
+
+    def profile(self, enable=None):
+        '''HIP-event time of the apply launches: (total ms, launches); enable switches it'''
+        ms, n = C.c_double(), C.c_int64()
+        L.check(self._lib.ps_gain_prof(self._h, -1 if enable is None else int(bool(enable)), C.byref(ms),
+                                       C.byref(n)))
+        return ms.value, n.value
+
+    def close(self):
+        if self._h:
+            self._lib.ps_gain_destroy(self._h)
+            self._h = L._VP()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class InformationPosterior():
+    '''The information maps of described traps, as posterior_predictive returns them: `fields` (the
+    InformationFields, which also holds the finished maps), `traps` [(key, rate, ymax)], `summary`, the
+    SpreadSummary.for_projection(fields) without thresholds, whose slots are the fields' planes; `reweight`: the
+    ReweightedSummary.for_projection, None unless asked for; `weights`: the weight of every member added, in
+    order, and `cap`, their entropy (weight_entropy): no finite ensemble can show a larger gain, and near it the
+    gain is an upper-biased estimate bounded by the ensemble, not by the trap; `given`: the driver's
+    information= argument.  The gain is in nats and a lower bound of the uncoarsened count's information.'''
+
+    def __init__(self, fields, scenarios=None):
+        self.fields = fields
+        self.traps = list(fields.traps)
+        self.reweight = None
+        self.given = None
+        self.weights = []
+        self.summary = SpreadSummary.for_projection(fields)
+        if scenarios:
+            self.reweight = ReweightedSummary.for_projection(fields, scenarios)
+        self._finished = ()            # the source of the fields' finished maps: (scenario,), () for none
+
+    def add(self, weight=1, log_weights=None):
+        '''apply the fields to the last evaluation (or the source's last apply) and add the planes to the summary
+        and, with the run's log-weights, to the reweighted summary'''
+        self.fields.apply()
+        self.summary.add(weight)
+        if self.reweight is not None:
+            self.reweight.add(log_weights, weight)
+        self.weights.append(int(weight))
+        self._finished = ()
+
+    def merge(self, other):
+        if other.traps != self.traps:
+            raise ValueError('information posteriors over different traps')
+        self.summary.merge(other.summary)
+        if self.reweight is not None:
+            self.reweight.merge(other.reweight)
+        self.weights.extend(other.weights)
+        self._finished = ()
+
+    @property
+    def cap(self):
+        return weight_entropy(self.weights)
+
+    def pmf(self, e, y):
+        '''the posterior predictive probability that trap e's count is y (y = ymax + 1: at least that)'''
+        f = self.fields
+        ymax = f.ymax[f._e(e)]
+        if not (y == int(y) and 0 <= y <= ymax + 1):
+            raise ValueError('class %r of trap %d is not in 0..%d' % (y, e, ymax + 1))
+        m = self.summary.mean(f.base[int(e)] + int(y))
+        return 1.0 - m if int(y) == 0 else m
+
+    def _result(self, e, what, scenario=None):
+        if scenario is not None and self.reweight is None:
+            raise ValueError('no reweighted maps: scenario %r needs reweight=' % (scenario,))
+        if self._finished != (scenario,):
+            self.fields.finish(self.summary if scenario is None else self.reweight, scenario)
+            self._finished = (scenario,)
+        return self.fields.result(e, what)
+
+    def gain(self, e, scenario=None):
+        '''the mutual information in nats between trap e's count and the identity of the member, per cell: the
+        expected Kullback-Leibler divergence from this posterior to the reweighted one after the reading; with a
+        scenario's name from the reweighted means -- after that scenario's observations'''
+        return self._result(e, 'gain', scenario)
+
+    def entropy(self, e):
+        '''the entropy of the posterior predictive class distribution of trap e'''
+        return self._result(e, 'entropy')
+
+    def conditional(self, e):
+        '''the posterior mean of the entropy of the member's own class distribution, H(count | member)'''
+        return self._result(e, 'conditional')
+
+    def close(self):
+        self.fields.close()
+        self.summary.close()
+        if self.reweight is not None:
+            self.reweight.close()
+
+
+def save_information(outfile, info, cell_area=None):
+    '''outfile.npz of one InformationPosterior through save_maps: per trap e under the label `i{e}` the CSR
+    triplets `i{e}_gain_*`, `i{e}_entropy_*`, `i{e}_d0_*` (1 - P(count = 0), the deficit, so that the triplets stay
+    sparse) and `i{e}_p{y}_*` for y = 1 .. ymax + 1 (the last: at least that); `days` (the traps' days or output
+    labels), `rates`, `ymax` -> its block for the json: the traps, members, weight, `cap` and per trap the largest
+    gain and, with a cell area, the m^2 where the gain reaches half of it'''
+    maps, outs = [], []
+    for e, t in enumerate(info.traps):
+        g = info.gain(e)
+        trap_maps = [('_gain', g), ('_entropy', info.entropy(e)), ('_d0', 1.0 - info.pmf(e, 0))]
+        trap_maps += [('_p%d' % y, info.pmf(e, y)) for y in range(1, t[2] + 2)]
+        maps.append(('i%d' % e, trap_maps))
+        top = float(g.max())
+        outs.append({'trap': list(t), 'max_gain': top,
+                     'half_area': None if cell_area is None or not top > 0
+                     else float((g >= 0.5 * top).sum() * cell_area)})
+    extra = {'days': np.array([t[0] for t in info.traps], dtype=np.int32),
+             'rates': np.array([t[1] for t in info.traps], dtype=np.float64),
+             'ymax': np.array([t[2] for t in info.traps], dtype=np.int32)}
+    save_maps(outfile, maps, extra)
+    return {'traps': [list(t) for t in info.traps], 'members': info.summary.members,
+            'total_weight': info.summary.total_weight, 'cap': info.cap, 'units': 'nats', 'outputs': outs}
+
+
+def warn_information(info, what='information'):
+    '''a UserWarning where a trap's largest gain exceeds cap / 2: the map is then bounded by the ensemble, not by
+    the trap -> the largest gain per trap'''
+    import warnings
+    cap = info.cap
+    tops = [float(info.gain(e).max()) for e in range(len(info.traps))]
+    for e, top in enumerate(tops):
+        if top > 0.5 * cap:
+            warnings.warn('%s: the largest gain of trap %r, %.3g nats, exceeds half the ensemble\'s cap of %.3g nats '
+                          '(%d members): the map is bounded by the ensemble, not by the trap'
+                          % (what, info.traps[e], top, cap, len(info.weights)), UserWarning, stacklevel=3)
+    return tops
+
+
 # ------------------------------------------------------------------ traces
 def model_names():
     return [m[0] for m in mcmc.MODEL_BLOCK]
@@ -3651,13 +4009,17 @@ class PredictiveResult():
     scenario of row log-weights --, min_ess, diagnostics: {name: reweight_diagnostics + members, skipped,
     log_total_weight}), both None where not asked for (the projections and the plan then carry a `reweight` of
     their own); `catch`: the CatchPosterior of the traps over the model's day fields, None where not asked for
-    (the emergence projection and the plan then carry a `catch` of their own where asked for).'''
+    (the emergence projection and the plan then carry a `catch` of their own where asked for); `information`: the
+    InformationPosterior of the described traps over the model's day fields, None where not asked for (the plan then
+    carries an `information` of its own).'''
 
     def __init__(self, summary, rows, evaluations, failed, seconds, runs, observations, provenance, days,
                  histogram=None, quantiles=None, arrival=None, arrival_levels=None, emergence=None, exposure=None,
                  sites=None, sensitivity=None, contrast=None, compare_plan=None, mc_error=None, mc_plan=None,
-                 peak=None, excursion=None, excursion_levels=None, reweight=None, reweight_info=None, catch=None):
+                 peak=None, excursion=None, excursion_levels=None, reweight=None, reweight_info=None, catch=None,
+                 information=None):
         self.catch = catch
+        self.information = information
         self.peak = peak
         self.excursion = excursion
         self.excursion_levels = excursion_levels
@@ -3730,6 +4092,9 @@ class PredictiveResult():
         release plan into outfile_NAME_catch.npz), their block under `predictive.catch` (`predictive.NAME.catch`),
         with the traps as given; their reweighted maps into outfile_catch_reweight.npz (save_reweight) and their
         Monte Carlo error into outfile_mcerr.npz under the labels `catch_c{e}`.
+        Information maps go into outfile_information.npz (save_information; those of a release plan into
+        outfile_sites_information.npz), their block under `predictive.information` (`predictive.sites.information`),
+        with the traps as given.
         -> (npz path, json path)'''
         s = self.summary
         if s is None:
@@ -3861,6 +4226,13 @@ class PredictiveResult():
             if cp.reweight is not None:
                 save_reweight('%s_%scatch_reweight' % (outfile, name), cp.reweight, keys, labels)
             (meta['predictive'][name[:-1]] if name else meta['predictive'])['catch'] = block
+        for name, ip in (('', self.information),
+                         ('sites_', None if self.sites is None else self.sites.information)):
+            if ip is None:
+                continue
+            block = save_information('%s_%sinformation' % (outfile, name), ip, area)
+            block['given'] = ip.given
+            (meta['predictive'][name[:-1]] if name else meta['predictive'])['information'] = block
         if self.mc_error is not None:
             mmaps = []
             labels = [s.pm.days[d] if d < len(s.pm.days) else d for d in s.days]
@@ -3885,7 +4257,7 @@ class PredictiveResult():
 
 def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, locinfo, histogram=None,
                    arrival=None, projected=(), plan=None, sens=None, compare=None, mc=None, peak=None,
-                   excursion=None, reweight=None, catch=None):
+                   excursion=None, reweight=None, catch=None, information=None):
     '''one chain: evaluate every run, add it to the summary (and the histogram, the arrival maps; projected:
     (Projection, ProjectedMaps) pairs, applied and then added; plan: a (ReleaseSites, ProjectedMaps) pair, the
     models of its later release days evaluated with the base model -- a member for which any of them fails is
@@ -3901,7 +4273,9 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
     summary the run's log-weights are taken, by one gather of all probes, and the member added with them and the
     run's length, to every ProjectedMaps' own after its summary too; catch: the chain's CatchPosterior -- right after the summary and the
     reweighted summary, whose log-weights it shares, its fields are applied and added with the run's length, its
-    Monte Carlo error sequences fed like the others; every ProjectedMaps' own after its other accumulators)
+    Monte Carlo error sequences fed like the others; every ProjectedMaps' own after its other accumulators;
+    information: the chain's InformationPosterior, applied and added with the run's length and the same log-weights
+    right after the catch; the plan's own after the plan's catch)
     -> (expected per run or None, failed)'''
     expected = []
     failed = 0
@@ -3947,6 +4321,8 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
             reweight[0].add(lam, length)
         if catch is not None:
             catch_add(catch, first, length, lam)
+        if information is not None:
+            information.add(length, lam)
         if excursion is not None:
             excursion.add(length)
         if mc is not None:
@@ -3986,6 +4362,8 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
                     acc.add(length)
             if plan[1].catch is not None:
                 catch_add(plan[1].catch, first, length, lam)
+            if plan[1].information is not None:
+                plan[1].information.add(length, lam)
         if compare is not None:
             compare[0].apply()
             compare[1].add(length)
@@ -3997,7 +4375,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                          cell_area=None, seed=0, evaluate=None, quantiles=None, bins=DEFAULT_BINS, edges=None,
                          arrival=None, arrival_levels=(0.05, 0.5, 0.95), emergence=None, exposure=None, sites=None,
                          sensitivity=None, compare=None, mc_error=None, peak=None, excursion=None, reweight=None,
-                         catch=None):
+                         catch=None, information=None):
     '''Posterior predictive spread of one or more chains (`Sampler.save` files or (trace, names)
     pairs).  Burn and thin apply per chain; consecutive rows with identical model parameters are one
     evaluation weighted by the run's length.  pop_model: one PopModel or a list -- with several, one
@@ -4075,8 +4453,24 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     `emergence.catch`: sentinel fields measure emergence, so this is the forward map of the data the chain was
     fitted to.  With sites= the plan gets one of its own over the same traps, whose days have to be output days
     of the plan, in `sites.catch`.  Histogram, arrival, peak, excursion, sensitivity and contrast of the catch
-    fields are not computed.  Without catch= no call is added and `catch` is None.'''
+    fields are not computed.  Without catch= no call is added and `catch` is None.  information:
+    dict(traps=[(day, rate[, ymax]), ...]) (check_information; not with evaluate=; bad arguments fail before any
+    evaluation): per described trap -- effort `rate` on model day `day`, its count observed as 0, 1, .., ymax and
+    ">= ymax + 1" -- and cell the mutual information in nats between the count and the identity of the member:
+    where a reading would change the posterior, and where it would tell nothing.  Each chain then also applies one
+    InformationFields right after the summary's add and adds its planes, with the run's length, to a
+    SpreadSummary.for_projection without thresholds; with reweight= to a ReweightedSummary.for_projection fed the
+    same log-weights (`information.gain(e, scenario=name)`: after that scenario's observations); merged in chain
+    order into `information` (an InformationPosterior).  With sites= the plan gets one of its own over the same
+    traps, whose days have to be output days of the plan, in `sites.information`.  A UserWarning where a trap's
+    largest gain exceeds half of `cap`, the entropy of the member weights: the map is then bounded by the
+    ensemble, not by the trap.  Histogram, arrival, peak, excursion, contrast, sensitivity and Monte Carlo error of
+    these maps are not computed.  Without information= no call is added and `information` is None.'''
     t0 = time.perf_counter()
+    in_plan = None
+    if information is not None:       # bad information arguments fail before any evaluation
+        pm0 = (pop_model[0] if pop_model else None) if isinstance(pop_model, (list, tuple)) else pop_model
+        in_plan = check_information(information, None if pm0 is None else len(pm0.days), evaluate)
     ct_plan = None
     if catch is not None:             # bad catch arguments fail before any evaluation
         pm0 = (pop_model[0] if pop_model else None) if isinstance(pop_model, (list, tuple)) else pop_model
@@ -4131,11 +4525,12 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         site_plan = sites_plan(sites, pm0)
         if pm0 is None:
             site_plan = None
-        elif ct_plan is not None:
-            off = [t for t in ct_plan['traps'] if t[0] not in site_plan[1]]
-            if off:
-                raise ValueError('catch: trap %r is not on an output day of the release plan %r'
-                                 % (off[0], list(site_plan[1])))
+        else:
+            for what, tp in (('catch', ct_plan), ('information', in_plan)):
+                off = [t for t in tp['traps'] if t[0] not in site_plan[1]] if tp is not None else []
+                if off:
+                    raise ValueError('%s: trap %r is not on an output day of the release plan %r'
+                                     % (what, off[0], list(site_plan[1])))
     cmp_plan = None
     if compare is not None:           # and a bad plan B, or one without a plan A to compare with
         pm0 = (pop_model[0] if pop_model else None) if isinstance(pop_model, (list, tuple)) else pop_model
@@ -4180,6 +4575,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     mcs = [None] * nch                         # per chain its two MonteCarloError sequences
     rws = [None] * nch                         # per chain (ReweightedSummary, _ReweightFeed)
     catches = [None] * nch                     # per chain its CatchPosterior over the day fields
+    infos = [None] * nch                       # per chain its InformationPosterior over the day fields
     rw_names = rw_plan['names'] if rw_plan is not None else None
     projected = [[] for _ in range(nch)]       # per chain (Projection, ProjectedMaps) of every plan
     site_maps = [None] * nch                   # per chain (ReleaseSites, ProjectedMaps)
@@ -4216,6 +4612,8 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                                _ReweightFeed(rw_plan, ci))
                 if ct_plan is not None:
                     catches[ci] = CatchPosterior(CatchFields(pm, ct_plan['traps']), ct_plan['levels'], mc_b, rw_names)
+                if in_plan is not None:
+                    infos[ci] = InformationPosterior(InformationFields(pm, in_plan['traps']), rw_names)
                 if evaluate is None:
                     for _name, W, in_days, labels in plans:
                         proj = Projection(pm, W, in_days)
@@ -4265,6 +4663,9 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                         if ct_plan is not None:
                             maps.catch = CatchPosterior(CatchFields.for_projection(rs, ct_plan['traps']),
                                                         ct_plan['levels'], mc_b, rw_names)
+                        if in_plan is not None:
+                            maps.information = InformationPosterior(
+                                InformationFields.for_projection(rs, in_plan['traps']), rw_names)
                         if cmp_plan is not None:
                             rb = ReleaseSites(pm, compare['sites'], site_plan[1], late[p])
                             cmp_maps[ci] = (rb, None, late[p])
@@ -4272,7 +4673,8 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                 results[ci] = _evaluate_runs(pm, summ, rows, rl, mcols, evaluate, want_obs, locinfo, hist, arr,
                                              projected[ci], site_maps[ci], sens, cmp_maps[ci],
                                              (mcs[ci], mc_halves[ci][0]) if mc_b else None, peaks[ci],
-                                             excursion=excurs[ci], reweight=rws[ci], catch=catches[ci])
+                                             excursion=excurs[ci], reweight=rws[ci], catch=catches[ci],
+                                             information=infos[ci])
         except BaseException as e:       # re-raised in the caller's thread
             errs.append((p, e))
 
@@ -4287,7 +4689,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         pms = pms[:1]
         work(0)
     if errs:
-        for s in summaries + histograms + arrivals + senses + peaks + excurs + catches + [pair[0] for pair in rws if pair] + [x for pair in mcs if pair for x in pair] + [x for pl in projected for pair in pl for x in pair] \
+        for s in summaries + histograms + arrivals + senses + peaks + excurs + catches + infos + [pair[0] for pair in rws if pair] + [x for pair in mcs if pair for x in pair] + [x for pl in projected for pair in pl for x in pair] \
                 + [x for pair in site_maps if pair is not None for x in pair] \
                 + [x for tri in cmp_maps if tri is not None for x in tri[:2]] \
                 + [m for made in late.values() for m in made.values()]:
@@ -4356,6 +4758,19 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
             c.close()
         return first
     catch_maps = merge_catch(catches) if ct_plan is not None else None
+
+    def merge_info(ips):
+        '''the chains' InformationPosteriors merged in chain order into the first, whose fields stay open -- they
+        hold the finished maps --; the other chains' fields and accumulators closed'''
+        if not ips or ips[0] is None:
+            return None
+        first = ips[0]
+        first.given = in_plan['given']
+        for c in ips[1:]:
+            first.merge(c)
+            c.close()
+        return first
+    info_maps = merge_info(infos) if in_plan is not None else None
     mc_pooled = mc_desc = None
     if mc_b:
         mc_pooled = pool_mc_error(mcs)
@@ -4393,6 +4808,11 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
             for _rs, maps in site_maps[1:]:
                 maps.catch = None
             merged_sites.catch = merge_catch(cps)
+        if merged_sites.information is not None:
+            ips = [maps.information for _rs, maps in site_maps]
+            for _rs, maps in site_maps[1:]:
+                maps.information = None
+            merged_sites.information = merge_info(ips)
         for _rs, maps in site_maps[1:]:
             merged_sites.merge(maps)
             maps.close()
@@ -4422,7 +4842,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         empty = [n for n in rw_plan['names'] if diag[n]['members'] == 0]
         if empty:
             for m in [summary, histogram, arrival_maps, sens_maps, peak_maps, excur_maps, rw_maps, mc_pooled,
-                      contrast, catch_maps] + list(merged.values()) + [merged_sites]:
+                      contrast, catch_maps, info_maps] + list(merged.values()) + [merged_sites]:
                 if m is not None:
                     m.close()
             raise ValueError('reweight: scenario %r is left without weight (W = 0): no member is compatible with it'
@@ -4454,7 +4874,11 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                            None if summary is None else summary.days, histogram, levels, arrival_maps,
                            a_levels if a_thr else None, merged.get('emergence'), merged.get('exposure'),
                            merged_sites, sens_maps, contrast, compare_desc, mc_pooled, mc_desc, peak_maps,
-                           excur_maps, ex_levels if ex_thr else None, rw_maps, rw_info, catch_maps)
+                           excur_maps, ex_levels if ex_thr else None, rw_maps, rw_info, catch_maps, info_maps)
+    if info_maps is not None:         # the stated convention: past cap / 2 the ensemble bounds the map
+        warn_information(info_maps)
+        if merged_sites is not None and merged_sites.information is not None:
+            warn_information(merged_sites.information, 'information (release plan)')
     if cell_area is not None:
         res.cell_area = float(cell_area)
     return res

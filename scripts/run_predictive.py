@@ -29,7 +29,10 @@ members, with the effective sample size of every scenario in the json -- saved a
 PREFIX_NAME_reweight.npz for every projection and plan asked for); with --catch also the catch-probability maps --
 per trap 'DAY,RATE[,N]' and cell the posterior mean, sd and the probability (--catch-levels) that a trap of effort
 RATE on model day DAY catches at least N wasps; --catch-emergence: traps over the emergence days of --emergence --
-saved as PREFIX_catch.npz (and PREFIX_emergence_catch.npz, PREFIX_sites_catch.npz).  Kalbar wind and
+saved as PREFIX_catch.npz (and PREFIX_emergence_catch.npz, PREFIX_sites_catch.npz); with --information also the
+information maps -- per described trap 'DAY,RATE[,YMAX]' and cell the mutual information in nats between the trap's
+count (observed as 0, 1, .., YMAX and more) and the identity of the member: where a reading would change what we
+believe -- saved as PREFIX_information.npz (and PREFIX_sites_information.npz).  Kalbar wind and
 LocInfo as scripts/run_mcmc.py loads them; --synthetic uses the synthetic Kalbar-like observations.
 Without --chain a short chain is sampled first (--samples) and saved next to --out.
 
@@ -42,6 +45,7 @@ Without --chain a short chain is sampled first (--samples) and saved next to --o
         [--excursion 1,10] [--excursion-levels 0.9,0.95]
         [--reweight 'NAME:east,north,day,kind,rate[,n];...'] [--reweight-file NAME=weights.npy]
         [--catch 'DAY,RATE[,N];...'] [--catch-levels 0.5,0.95] [--catch-emergence 'OBSDAY,RATE[,N];...']
+        [--information 'DAY,RATE[,YMAX];...']
 """
 import argparse
 import json
@@ -138,6 +142,9 @@ def main():
     ap.add_argument('--catch-levels', default='0.5,0.95', help='levels of the catch maps (with --catch)')
     ap.add_argument('--catch-emergence', default='', help="traps 'OBSDAY,RATE[,N];...' over the emergence days of "
                     '--emergence (with --catch)')
+    ap.add_argument('--information', default='', help="described traps 'DAY,RATE[,YMAX];...': per cell the mutual "
+                    'information in nats between the count of a trap of effort RATE on model day DAY, observed as '
+                    '0, 1, .., YMAX (default 0) and more, and the identity of the member (default: off)')
     ap.add_argument('--reweight', action='append', default=None, metavar='NAME:PROBES',
                     help="a reweighting scenario of probe observations 'NAME:east,north,day,kind,rate[,n];...' "
                          '(repeatable; at most 4 scenarios with --reweight-file; default: off)')
@@ -208,6 +215,11 @@ def main():
         check_catch(catch, None, emergence)
     elif args.catch_emergence:
         ap.error('--catch-emergence needs --catch')
+    information = None
+    if args.information:                 # as do bad --information traps
+        from parasitoids_amd.predictive import check_information, parse_traps
+        information = dict(traps=parse_traps(args.information))
+        check_information(information)
     wd, days = PM.get_wind_data(os.path.join(ROOT, 'parasitoids_amd', 'data', 'kalbar'), 30, '00:00')
 
     def make_pm():
@@ -260,7 +272,8 @@ def main():
                                emergence=emergence, exposure=exposure, sites=sites, sensitivity=sens,
                                compare=compare, mc_error=mc_error, peak=peak, excursion=excursion,
                                **({'reweight': reweight} if reweight else {}),
-                               **({'catch': catch} if catch else {}))
+                               **({'catch': catch} if catch else {}),
+                               **({'information': information} if information else {}))
     dt = time.perf_counter() - t0
     # accumulate-kernel time: the same members once more with HIP events around every add
     from parasitoids_amd.predictive import (ArrivalMaps, ExcursionMaps, MonteCarloError, PeakMaps, PlanContrast, Projection,
@@ -302,6 +315,13 @@ def main():
         CP = Projection(pm, Wc, CF.in_days)
         CF.profile(True)
         CP.profile(True)
+    IF = IC = None
+    if information:                      # and a CatchFields of as many planes over the same days: the same bytes
+        from parasitoids_amd.predictive import CatchFields, InformationFields
+        IF = InformationFields(pm, information['traps'])
+        IC = CatchFields(pm, [(t[0], t[1], 1 + k % 16) for e, t in enumerate(IF.traps) for k in range(t[2] + 3)][:32])
+        IF.profile(True)
+        IC.profile(True)
     with SpreadSummary(pm, None, thr) as S:
         S.profile(True)
         if H is not None:
@@ -341,6 +361,9 @@ def main():
                 if CF is not None:
                     CF.apply()
                     CP.apply()
+                if IF is not None:
+                    IF.apply()
+                    IC.apply()
                 if RW is not None:
                     RW.add(RWF.log_weights(pm, first, length), length)
                 if ME is not None:
@@ -388,6 +411,12 @@ def main():
         cf_bytes = CF.nbytes
         CF.close()
         CP.close()
+    if IF is not None:
+        if_ms, if_launches = IF.profile()
+        ic_ms, ic_launches = IC.profile()
+        if_bytes, if_planes = IF.nbytes, IF.nout
+        IF.close()
+        IC.close()
     if RW is not None:
         rw_ms, rw_launches = RW.profile()
         rw_bytes = RW.nbytes
@@ -439,6 +468,15 @@ def main():
         out['outputs'] += ['%s_catch.npz' % args.out] \
             + (['%s_emergence_catch.npz' % args.out] if catch.get('emergence') else []) \
             + (['%s_sites_catch.npz' % args.out] if sites else [])
+    if information:
+        out['information_ms_per_member'] = round(if_ms / max(if_launches, 1), 4)
+        out['information_launches_timed'] = if_launches
+        out['information_planes'] = if_planes
+        out['information_catch_ms_per_member'] = round(ic_ms / max(ic_launches, 1), 4)   # as many catch outputs
+        out['information_bytes'] = if_bytes
+        out['information_cap'] = res.information.cap
+        out['information_max_gain'] = [float(res.information.gain(e).max()) for e in range(len(res.information.traps))]
+        out['outputs'] += ['%s_information.npz' % args.out] + (['%s_sites_information.npz' % args.out] if sites else [])
     if reweight:
         out['reweight_ms_per_member'] = round(rw_ms / max(rw_launches, 1), 4)
         out['reweight_launches_timed'] = rw_launches
@@ -525,7 +563,7 @@ def main():
         res.sensitivity.close()
     if res.mc_error is not None:
         res.mc_error.close()
-    for pr in (res.emergence, res.exposure, res.sites, res.contrast, res.peak, res.excursion, res.catch):
+    for pr in (res.emergence, res.exposure, res.sites, res.contrast, res.peak, res.excursion, res.catch, res.information):
         if pr is not None:
             pr.close()
     for p in pms:
