@@ -1084,6 +1084,64 @@ int ps_gain_info(ps_gain* c, int* N, int* nin, int* ntrap, int* nplane, int64_t*
 int ps_gain_prof(ps_gain* c, int enable, double* total_ms, int64_t* launches);
 void ps_gain_destroy(ps_gain* c);
 
+/* ---- core-range maps: where each member holds most of its wasps ----
+ * (no reference counterpart.)  Every other map cuts a member's field at an absolute density.  Here the cut is the
+ * member's own: for fractions p_0 < ... < p_{J-1} (1..4, each a finite double in (0, 1)) and nslot slots (1..32) of
+ * N x N cells (N * N < 2^25) the smallest region that holds the share p_j of the member's mass, the highest-density
+ * region {v >= lambda_j} -- the 50 % "core" and the 95 % "range" of the utilisation distribution.  v is the value
+ * ps_summary_add adds for the slot; a cell whose value is not > 0, or not finite, has mass 0 and lies in no set.  Per member and
+ * slot, every line a statement of its own:
+ *   vmax = max v;  not (vmax > 0): the slot is empty, lambda_j = +inf, n_j = 0, Q = 0, nothing is counted
+ *   E = floor(log2 vmax), from the exponent field;  q(c) = (uint64) floor(scalbn(v(c), 36 - E)) < 2^37, exact
+ *   Q = sum of q (an integer < 2^62);  need_j = the smallest integer >= p_j Q, p_j at its exact binary value
+ *   lambda_j = the largest x with sum of q over {v >= x} >= need_j (a value the field holds; ties enter whole)
+ *   B_j = {v >= lambda_j};  n_j = the cells of B_j;  B_0 in B_1 in ...
+ * State (pitch as ps_summary): cnt[j][slot][pitch] uint32, C_j += w_m B_j; per member in add order
+ * lambda[j][slot] fp64, n[j][slot] uint32, Q[slot] uint64, E[slot] int32 (grow by doubling, 12 B per member,
+ * fraction and slot plus 12 B per member and slot); the weights on the host; about 1 MB of pass scratch.  No masks
+ * are kept.  Every allocation is checked against the free device memory first: PS_ERR_OOM before it is made.
+ * lambda is found on the device by a radix select over the 64-bit pattern of v weighted by q (positive doubles
+ * order as their patterns): six passes of 10 bits over key = bits(v) - bits(2^(E-36)) < 2^60, each a histogram of
+ * integer mass per digit in LDS folded to global memory and a pick kernel that extends every (slot, fraction)
+ * prefix; no value comes back to the host during an add.  Integer atomics only: neither the order of adds, nor
+ * that of merges, nor the launch configuration changes a bit; only the order of the members in the fetches follows
+ * the adds.  Every operation records an event the next one waits on, whichever stream it runs on (the solver's
+ * for add, the handle's own otherwise). */
+typedef struct ps_range ps_range;
+/* PS_ERR_BAD_ARG for fractions outside (0, 1), NaN, not strictly increasing, more than 4, or slots outside 1..32 */
+int ps_range_create(int device, int N, int nslot, int nfrac, const double* frac, ps_range** out);
+/* room for `members` members' rows now (a growth synchronises; never shrinks) */
+int ps_range_reserve(ps_range* a, int64_t members);
+/* One member with weight >= 1 (arguments and refusals as ps_arrival_add; a total weight past 2^32 - 1 is refused):
+ * fourteen launches on the solver's stream, every slot in each; no host synchronisation unless the rows have to
+ * grow.  Every descriptor is resolved first, so an add with a bad slot enqueues nothing. */
+int ps_range_add(ps_range* a, ps_solver* s, int nslot, const int32_t* kind, const int32_t* idx,
+                 const double* stat_scale, const double* post_scale, const int32_t* use_delta, double negval,
+                 uint32_t weight);
+/* The same for the current outputs of a projection or a release plan, as ps_arrival_add_project /
+ * ps_arrival_add_sites: slot e takes Y_e (nslot must equal nout), on the handle's stream. */
+int ps_range_add_project(ps_range* a, ps_project* p, uint32_t weight);
+int ps_range_add_sites(ps_range* a, ps_sites* p, uint32_t weight);
+/* dst += src: the counts by an integer plane add, src's member rows and weights appended after dst's (device
+ * copies); same device, N, slots and fractions; src unchanged */
+int ps_range_merge(ps_range* dst, ps_range* src);
+/* any pointer may be NULL; capacity: the members the rows hold room for; bytes: the device memory held now */
+int ps_range_info(ps_range* a, double* total_weight, int64_t* members, int64_t* capacity, int64_t* bytes);
+/* zero counts, W and members and drop the timings of ps_range_prof; the rows keep their room */
+int ps_range_reset(ps_range* a);
+/* (double)C_j[slot] / (double)W: the posterior probability that the cell lies in the member's p_j range
+ * (synchronises).  PS_ERR_STATE before the first add, as the fetches below. */
+int ps_range_prob(ps_range* a, int j, int slot, double* out /* N*N */);
+int ps_range_fetch_counts(ps_range* a, int j, int slot, uint32_t* out /* N*N */);
+/* per member in add order the level, the cells of the set and the weight (any pointer may be NULL) */
+int ps_range_fetch_members(ps_range* a, int j, int slot, double* lambda, uint32_t* cells, uint32_t* weights);
+/* per member in add order the integer mass Q and the exponent E of the slot (either may be NULL) */
+int ps_range_fetch_mass(ps_range* a, int slot, uint64_t* Q, int32_t* E /* members */);
+/* measurement: HIP-event timing of the adds and the map launches, as ps_arrival_prof; while enabled every add and
+ * map keeps one event pair until ps_range_reset or ps_range_destroy */
+int ps_range_prof(ps_range* a, int enable, double* add_ms, int64_t* adds, double* map_ms, int64_t* maps);
+void ps_range_destroy(ps_range* a);
+
 #ifdef __cplusplus
 }
 #endif

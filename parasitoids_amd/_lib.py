@@ -291,6 +291,21 @@ SIGNATURES = {
     'ps_gain_info': (C.c_int, [_VP, _I32P, _I32P, _I32P, _I32P, _I64P]),
     'ps_gain_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P]),
     'ps_gain_destroy': (None, [_VP]),
+    'ps_range_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _F64P, C.POINTER(_VP)]),
+    'ps_range_reserve': (C.c_int, [_VP, C.c_int64]),
+    'ps_range_add': (C.c_int, [_VP, _VP, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P, C.c_double, C.c_uint32]),
+    'ps_range_add_project': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_range_add_sites': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_range_merge': (C.c_int, [_VP, _VP]),
+    'ps_range_info': (C.c_int, [_VP, _F64P, _I64P, _I64P, _I64P]),
+    'ps_range_reset': (C.c_int, [_VP]),
+    'ps_range_prob': (C.c_int, [_VP, C.c_int, C.c_int, _F64P]),
+    'ps_range_fetch_counts': (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(C.c_uint32)]),
+    'ps_range_fetch_members': (C.c_int, [_VP, C.c_int, C.c_int, _F64P, C.POINTER(C.c_uint32),
+                                         C.POINTER(C.c_uint32)]),
+    'ps_range_fetch_mass': (C.c_int, [_VP, C.c_int, C.POINTER(C.c_uint64), _I32P]),
+    'ps_range_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P, _F64P, _I64P]),
+    'ps_range_destroy': (None, [_VP]),
 }
 
 _lib = None

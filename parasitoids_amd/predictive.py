@@ -46,6 +46,10 @@ per member (`CatchPosterior`) -- the transform is not linear in the density, so 
 `InformationFields` turns one member's field into the whole class distribution of a described trap's count and its
 entropy (ps_gain_*, csrc/ps_gain.hip); from the accumulated means the device forms the mutual information between the
 count and the identity of the member (`InformationPosterior`): where a reading would change what we believe.
+`RangeMaps` keeps, on the device, per mass fraction and day the weighted count of the members whose own
+highest-density region holding that share of their wasps contains the cell, and per member the region's level, cell
+count and integer mass (ps_range_*, csrc/ps_range.hip): the 50 % core and the 95 % range as probability maps and the
+posterior of their area -- the level is each member's own, so no map cut at an absolute density gives them.
 """
 import ctypes as C
 import json
@@ -1129,6 +1133,258 @@ class ExcursionMaps():
             pass
 
 
+MAX_RANGE_FRACTIONS = 4
+
+
+def check_range_fractions(fractions):
+    '''mass fractions of the core-range maps as a list of floats: 1..4 of them, each a finite number in (0, 1),
+    strictly increasing; ValueError otherwise'''
+    try:
+        fr = [float(p) for p in fractions]
+    except (TypeError, ValueError):
+        raise ValueError('core-range fractions must be numbers, got %r' % (fractions,))
+    if not 1 <= len(fr) <= MAX_RANGE_FRACTIONS:
+        raise ValueError('%d core-range fractions; 1..%d are kept' % (len(fr), MAX_RANGE_FRACTIONS))
+    if not all(0.0 < p < 1.0 for p in fr):
+        raise ValueError('every core-range fraction must lie in (0, 1): %r' % (fr,))
+    if any(b <= a for a, b in zip(fr, fr[1:])):
+        raise ValueError('core-range fractions must be strictly increasing: %r' % (fr,))
+    return fr
+
+
+def check_core_range(core_range, days=None):
+    '''the core_range= argument of posterior_predictive -> (fractions, levels): a list of fractions (1..4, each in
+    (0, 1), strictly increasing), or dict(fractions=[...], levels=(0.5, 0.9)), the consensus levels -- the
+    posterior probabilities at which the saved consensus range {prob >= level} is cut -- each in (0, 1]; `days`,
+    where given, by the rules of check_arrival_days; ValueError otherwise'''
+    levels = (0.5, 0.9)
+    if isinstance(core_range, dict):
+        unknown = set(core_range) - {'fractions', 'levels'}
+        if unknown:
+            raise ValueError('core_range: unknown keys %r' % (sorted(unknown),))
+        if 'fractions' not in core_range:
+            raise ValueError('core_range: fractions are needed')
+        levels = core_range.get('levels', levels)
+        core_range = core_range['fractions']
+    try:
+        fr = list(core_range)
+    except TypeError:
+        raise ValueError('core-range fractions must be a list of numbers, got %r' % (core_range,))
+    try:
+        lv = [float(p) for p in levels]
+    except (TypeError, ValueError):
+        raise ValueError('core-range consensus levels must be numbers, got %r' % (levels,))
+    if not lv or not all(0.0 < p <= 1.0 for p in lv):
+        raise ValueError('core-range consensus levels must lie in (0, 1], at least one: %r' % (lv,))
+    if days is not None:
+        check_arrival_days(days)
+    return check_range_fractions(fr), lv
+
+
+class RangeMaps():
+    '''Where each of `pop_model`'s members holds most of its wasps: for mass fractions p_0 < ... < p_{J-1} (1..4,
+    each in (0, 1)) and the model days `days` (strictly increasing, at most 32, default all) the member's own
+    highest-density region {v >= lambda_j}, the smallest set of cells that holds the share p_j of the member's
+    population on that day -- 0.5 the "core", 0.95 the "range" of the utilisation distribution.  On the device per
+    (j, day) the weighted count C of the members whose region holds the cell, and per member the level lambda_j,
+    the cells n_j of the region, the integer mass Q and its exponent E (ps_range_*; the statements are those of
+    include/parasitoid_hip.h, restated in tests/range_ref.py).  The level is the member's own, so the maps do not
+    change with the release number.  Counts are integers: the order of adds and merges changes no bit.'''
+
+    def __init__(self, pop_model, fractions, days=None):
+        self._h = L._VP()
+        self.fractions = check_range_fractions(fractions)
+        self.days = check_arrival_days(range(len(pop_model.days)) if days is None else days)
+        self._setup(pop_model, None)
+
+    @classmethod
+    def for_projection(cls, projection, fractions):
+        '''Core-range maps of the outputs of `projection` (a ReleaseSites or a Projection), the slots its outputs
+        that carry weight in ascending order: `add(weight)` accumulates the outputs of its last `apply()`.
+        `days` holds the output labels -- the plan's output days, or the projection's output indices.'''
+        self = cls.__new__(cls)
+        self._h = L._VP()
+        self.fractions = check_range_fractions(fractions)
+        labels = list(getattr(projection, 'days', range(projection.nout)))
+        self.days = check_arrival_days([labels[e] for e in projection.live])
+        self._setup(projection.pm, projection)
+        return self
+
+    def _setup(self, pop_model, projection):
+        self._proj = projection
+        self._lib = L.load()
+        self.pm = pop_model
+        self.N = 2 * int(pop_model.rad_res) + 1
+        self.cell_area = (float(pop_model.rad_dist) / int(pop_model.rad_res)) ** 2
+        self.device = L.default_device() if pop_model.device is None else int(pop_model.device)
+        fr = L.f64(self.fractions)
+        L.check(self._lib.ps_range_create(self.device, self.N, len(self.days), len(self.fractions), L.p_f64(fr),
+                                          C.byref(self._h)))
+        if projection is None:
+            self._kind, self._idx, self._delta = _day_slots(self.days)
+        self._slot = {d: i for i, d in enumerate(self.days)}
+
+    def reserve(self, n):
+        '''room for n members' rows now, so that no add has to grow them'''
+        L.check(self._lib.ps_range_reserve(self._h, int(n)))
+
+    def add(self, weight=1):
+        '''Accumulate the last evaluation of the model with integer weight >= 1 (enqueued on the solver's stream;
+        no host synchronisation unless the member rows grow).  On a projection or a plan: its last apply, on the
+        handle's stream.'''
+        w = int(weight)
+        if w < 1:
+            raise ValueError('weight must be a positive integer')
+        if self._proj is not None:
+            L.check(getattr(self._lib, 'ps_range_add_' + self._proj.fields_kind)(self._h, self._proj._h, w))
+            return
+        pm = self.pm
+        _check_evaluated(pm, self.days, 'core-range maps')
+        stat, post = _day_scales(pm, self.days)
+        L.check(self._lib.ps_range_add(self._h, pm.solver._h, len(self.days), L.p_i32(self._kind), L.p_i32(self._idx),
+                                       L.p_f64(stat), L.p_f64(post), L.p_i32(self._delta), NEGVAL, w))
+
+    def merge(self, other):
+        '''self += other (same device, domain, days and fractions); other's members follow self's'''
+        if list(other.days) != self.days:
+            raise ValueError('core-range maps over different days')
+        L.check(self._lib.ps_range_merge(self._h, other._h))
+
+    def reset(self):
+        L.check(self._lib.ps_range_reset(self._h))
+
+    def _info(self):
+        w, m, c, b = C.c_double(), C.c_int64(), C.c_int64(), C.c_int64()
+        L.check(self._lib.ps_range_info(self._h, C.byref(w), C.byref(m), C.byref(c), C.byref(b)))
+        return w.value, m.value, c.value, b.value
+
+    @property
+    def total_weight(self):
+        return self._info()[0]
+
+    @property
+    def members(self):
+        return self._info()[1]
+
+    @property
+    def capacity(self):
+        '''the members the rows hold room for'''
+        return self._info()[2]
+
+    @property
+    def nbytes(self):
+        '''the device memory the handle holds now'''
+        return self._info()[3]
+
+    def _j(self, j):
+        if not 0 <= int(j) < len(self.fractions):
+            raise ValueError('fraction %r of %d' % (j, len(self.fractions)))
+        return int(j)
+
+    def _slot_of(self, day):
+        if day not in self._slot:
+            raise ValueError('day %r is not in the core-range maps %s' % (day, self.days))
+        return self._slot[day]
+
+    def counts(self, j, day):
+        '''[N, N] uint32: the weight of the members whose p_j region on `day` holds the cell'''
+        out = np.empty((self.N, self.N), dtype=np.uint32)
+        L.check(self._lib.ps_range_fetch_counts(self._h, self._j(j), self._slot_of(day),
+                                                out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def prob(self, j, day):
+        '''[N, N] float64: the posterior probability C / W that the cell lies in the member's p_j region'''
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        L.check(self._lib.ps_range_prob(self._h, self._j(j), self._slot_of(day), L.p_f64(out)))
+        return out
+
+    def range(self, j, day, level=0.5):
+        '''[N, N] bool: the consensus region {prob >= level}, 0 < level <= 1'''
+        level, = check_levels([level])
+        return self.prob(j, day) >= level
+
+    def _members(self, j, day):
+        m = self.members
+        lam = np.empty(m, dtype=np.float64)
+        n, w = np.empty(m, dtype=np.uint32), np.empty(m, dtype=np.uint32)
+        u32 = C.POINTER(C.c_uint32)
+        L.check(self._lib.ps_range_fetch_members(self._h, self._j(j), self._slot_of(day), L.p_f64(lam),
+                                                 n.ctypes.data_as(u32), w.ctypes.data_as(u32)))
+        return lam, n, w
+
+    @property
+    def weights(self):
+        '''[members] int64: the members' weights in add order'''
+        return self._members(0, self.days[0])[2].astype(np.int64)
+
+    def levels(self, j, day):
+        '''[members] float64 in add order: the member's own level lambda_j on `day`, +inf where it holds nothing'''
+        return self._members(j, day)[0]
+
+    def cells(self, j, day):
+        '''[members] int64 in add order: the cells of the member's p_j region on `day`'''
+        return self._members(j, day)[1].astype(np.int64)
+
+    def mass(self, day):
+        '''(Q [members] uint64, E [members] int32) in add order: the member's integer mass on `day`, the sum of
+        floor(v 2^(36 - E)), and E = floor(log2 max v); both 0 where it holds nothing'''
+        m = self.members
+        Q, E = np.empty(m, dtype=np.uint64), np.empty(m, dtype=np.int32)
+        L.check(self._lib.ps_range_fetch_mass(self._h, self._slot_of(day), Q.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                              L.p_i32(E)))
+        return Q, E
+
+    def area(self, j, day, levels=(0.05, 0.5, 0.95)):
+        '''The posterior of the area of the p_j region on `day`: {'day', 'mean', 'quantiles', 'radius_mean',
+        'radius_quantiles'}, as one entry of ArrivalMaps.reached_area.  Areas in m^2 (cells x (rad_dist /
+        rad_res)^2): the weighted mean and the weighted lower quantiles (weighted_lower_quantile) at `levels`;
+        radii sqrt(A / pi) in m.'''
+        levels = check_levels(levels)
+        _lam, n, w = self._members(j, day)
+        return range_area(n, w, self.cell_area, levels, day)
+
+    def profile(self, enable=None):
+        '''HIP-event time of the adds and the map launches: (add ms, adds, map ms, map launches); enable
+        switches it'''
+        am, an, qm, qn = C.c_double(), C.c_int64(), C.c_double(), C.c_int64()
+        L.check(self._lib.ps_range_prof(self._h, -1 if enable is None else int(bool(enable)), C.byref(am),
+                                        C.byref(an), C.byref(qm), C.byref(qn)))
+        return am.value, an.value, qm.value, qn.value
+
+    def close(self):
+        if self._h:
+            self._lib.ps_range_destroy(self._h)
+            self._h = L._VP()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def range_area(cells, weights, cell_area, levels=(0.05, 0.5, 0.95), day=None):
+    '''the posterior of a region's area from the members' cell counts and integer weights, as RangeMaps.area
+    returns it (no device)'''
+    levels = check_levels(levels)
+    n = np.asarray(cells).astype(np.int64)
+    w = np.asarray(weights).astype(np.int64)
+    W = int(w.sum())
+    if W == 0:
+        raise ValueError('nothing accumulated')
+    mean = float(int((n * w).sum())) / float(W) * cell_area
+    q = [float(weighted_lower_quantile(n, w, p)) * cell_area for p in levels]
+    return {'day': day, 'mean': mean, 'quantiles': q, 'radius_mean': float(np.sqrt(mean / np.pi)),
+            'radius_quantiles': [float(np.sqrt(a / np.pi)) for a in q]}
+
+
 def check_weights(weights, nin=None, zero_rows=False):
     '''A projection's weight matrix as a float64 [nout, nin] array, by the rules of ps_project_create: 1..32
     outputs, 1..32 inputs (nin if given), every weight finite and >= 0, and no row of all zeros unless
@@ -1349,13 +1605,15 @@ class ProjectedMaps():
     asked for), whose maps take the output day.  `reweight`: the
     ReweightedSummary.for_projection (None unless asked for), which takes the scenario's name and the output index.
     `catch`: the CatchPosterior over the outputs (None unless asked for), whose traps name an output label.
-    `information`: the InformationPosterior over the outputs (None unless asked for), likewise.'''
+    `information`: the InformationPosterior over the outputs (None unless asked for), likewise.  `core_range`: the
+    RangeMaps.for_projection of a release plan's outputs (None unless asked for), whose maps take the output day.'''
 
     def __init__(self, weights, in_days, labels, summary, histogram=None, arrival=None, plan=None,
                  sensitivity=None, mc_error=None, peak=None, excursion=None, reweight=None, catch=None,
-                 information=None):
+                 information=None, core_range=None):
         self.catch = catch
         self.information = information
+        self.core_range = core_range
         self.peak = peak
         self.excursion = excursion
         self.reweight = reweight
@@ -1381,6 +1639,8 @@ class ProjectedMaps():
             self.peak.merge(other.peak)
         if self.excursion is not None:
             self.excursion.merge(other.excursion)
+        if self.core_range is not None:
+            self.core_range.merge(other.core_range)
         if self.reweight is not None:
             self.reweight.merge(other.reweight)
         if self.catch is not None and other.catch is not None:       # the driver merges the chains' catches itself
@@ -1398,6 +1658,8 @@ class ProjectedMaps():
             self.reweight.close()
         if self.excursion is not None:
             self.excursion.close()
+        if self.core_range is not None:
+            self.core_range.close()
         if self.peak is not None:
             self.peak.close()
         if self.histogram is not None:
@@ -3961,6 +4223,44 @@ def save_excursion(outfile, exc, levels=(0.9, 0.95)):
             'total_weight': exc.total_weight, 'cell_area': exc.cell_area, 'areas': areas}
 
 
+def save_range(outfile, rng, levels=(0.5, 0.9)):
+    '''outfile.npz of one RangeMaps through save_maps: per day of the maps, under the label `{day}`, the CSR
+    triplets `{day}_prange{j}_*` of the probability that the cell lies in the member's p_j region; the count planes
+    `range_counts` [fractions, days, N, N] (uint16 where the total weight fits, else uint32), the members' rows
+    `range_lambda` (fp64) and `range_cells` (uint32) [fractions, days, members], `range_Q` (uint64) and `range_E`
+    (int32) [days, members], `range_weights` [members], `range_fractions` and `range_days` -> its block for the
+    json: fractions, days, levels, members, weight, cell area and per fraction and day the mean and quantiles of
+    the region's area (RangeMaps.area at 0.05, 0.5, 0.95) and the m^2 of the consensus region {prob >= level} at
+    each level'''
+    levels = check_levels(levels)
+    nj = len(rng.fractions)
+    W = int(rng.total_weight)
+    ctype = np.uint16 if W <= 0xffff else np.uint32
+    q_levels = [0.05, 0.5, 0.95]
+    maps, areas = [], [[] for _ in range(nj)]
+    for d in rng.days:
+        day_maps = []
+        for j in range(nj):
+            P = rng.prob(j, d)
+            day_maps.append(('_prange%d' % j, P))
+            rec = rng.area(j, d, q_levels)
+            rec['consensus'] = [{'level': p, 'area': float(int((P >= p).sum())) * rng.cell_area} for p in levels]
+            areas[j].append(rec)
+        maps.append((d, day_maps))
+    rows = [[rng._members(j, d) for d in rng.days] for j in range(nj)]
+    mass = [rng.mass(d) for d in rng.days]
+    extra = {'range_counts': np.array([[rng.counts(j, d) for d in rng.days] for j in range(nj)]).astype(ctype),
+             'range_lambda': np.array([[x[0] for x in row] for row in rows], dtype=np.float64),
+             'range_cells': np.array([[x[1] for x in row] for row in rows], dtype=np.uint32),
+             'range_Q': np.array([x[0] for x in mass], dtype=np.uint64),
+             'range_E': np.array([x[1] for x in mass], dtype=np.int32),
+             'range_weights': np.asarray(rows[0][0][2], dtype=np.uint32),
+             'range_fractions': np.asarray(rng.fractions, dtype=np.float64), 'range_days': np.asarray(rng.days)}
+    save_maps(outfile, maps, extra)
+    return {'fractions': list(rng.fractions), 'days': list(rng.days), 'levels': levels, 'area_levels': q_levels,
+            'members': rng.members, 'total_weight': rng.total_weight, 'cell_area': rng.cell_area, 'areas': areas}
+
+
 def mc_error_block(mc, keys, labels, prefix, maps):
     '''the maps of one pooled MonteCarloError appended to `maps` for save_maps (keys: its days or output
     indices, labels: theirs in the file behind `prefix`) -> its block for the json'''
@@ -4011,15 +4311,19 @@ class PredictiveResult():
     their own); `catch`: the CatchPosterior of the traps over the model's day fields, None where not asked for
     (the emergence projection and the plan then carry a `catch` of their own where asked for); `information`: the
     InformationPosterior of the described traps over the model's day fields, None where not asked for (the plan then
-    carries an `information` of its own).'''
+    carries an `information` of its own); `core_range`: the RangeMaps over the summary's days and
+    `core_range_levels` the consensus levels of its saved regions, both None where not asked for (the plan then
+    carries a `core_range` of its own).'''
 
     def __init__(self, summary, rows, evaluations, failed, seconds, runs, observations, provenance, days,
                  histogram=None, quantiles=None, arrival=None, arrival_levels=None, emergence=None, exposure=None,
                  sites=None, sensitivity=None, contrast=None, compare_plan=None, mc_error=None, mc_plan=None,
                  peak=None, excursion=None, excursion_levels=None, reweight=None, reweight_info=None, catch=None,
-                 information=None):
+                 information=None, core_range=None, core_range_levels=None):
         self.catch = catch
         self.information = information
+        self.core_range = core_range
+        self.core_range_levels = core_range_levels
         self.peak = peak
         self.excursion = excursion
         self.excursion_levels = excursion_levels
@@ -4095,6 +4399,8 @@ class PredictiveResult():
         Information maps go into outfile_information.npz (save_information; those of a release plan into
         outfile_sites_information.npz), their block under `predictive.information` (`predictive.sites.information`),
         with the traps as given.
+        Core-range maps go into outfile_range.npz (save_range; those of a release plan into
+        outfile_sites_range.npz), their block under `predictive.core_range` (`predictive.sites.core_range`).
         -> (npz path, json path)'''
         s = self.summary
         if s is None:
@@ -4180,6 +4486,12 @@ class PredictiveResult():
             if pr.excursion is not None:
                 meta['predictive'][name]['excursion'] = save_excursion('%s_%s_excur' % (outfile, name), pr.excursion,
                                                                        self.excursion_levels)
+            if pr.core_range is not None:
+                meta['predictive'][name]['core_range'] = save_range('%s_%s_range' % (outfile, name), pr.core_range,
+                                                                    self.core_range_levels)
+        if self.core_range is not None:
+            meta['predictive']['core_range'] = save_range('%s_range' % outfile, self.core_range,
+                                                          self.core_range_levels)
         if self.excursion is not None:
             meta['predictive']['excursion'] = save_excursion('%s_excur' % outfile, self.excursion,
                                                              self.excursion_levels)
@@ -4257,7 +4569,7 @@ class PredictiveResult():
 
 def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, locinfo, histogram=None,
                    arrival=None, projected=(), plan=None, sens=None, compare=None, mc=None, peak=None,
-                   excursion=None, reweight=None, catch=None, information=None):
+                   excursion=None, reweight=None, catch=None, information=None, core_range=None):
     '''one chain: evaluate every run, add it to the summary (and the histogram, the arrival maps; projected:
     (Projection, ProjectedMaps) pairs, applied and then added; plan: a (ReleaseSites, ProjectedMaps) pair, the
     models of its later release days evaluated with the base model -- a member for which any of them fails is
@@ -4275,7 +4587,8 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
     reweighted summary, whose log-weights it shares, its fields are applied and added with the run's length, its
     Monte Carlo error sequences fed like the others; every ProjectedMaps' own after its other accumulators;
     information: the chain's InformationPosterior, applied and added with the run's length and the same log-weights
-    right after the catch; the plan's own after the plan's catch)
+    right after the catch; the plan's own after the plan's catch; core_range: the chain's RangeMaps, fed the run's
+    weight right after the summary's add -- the plan's own after the plan's other accumulators)
     -> (expected per run or None, failed)'''
     expected = []
     failed = 0
@@ -4315,6 +4628,8 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
             expected.append(None)
             continue
         summary.add(length)
+        if core_range is not None:
+            core_range.add(length)
         lam = None
         if reweight is not None:
             lam = reweight[1].log_weights(pm, first, length)
@@ -4357,7 +4672,7 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
                 mc_add(plan[1].mc_error, first, length)
             if plan[1].sensitivity is not None:
                 plan[1].sensitivity.add(theta, length)
-            for acc in (plan[1].histogram, plan[1].arrival, plan[1].peak, plan[1].excursion):
+            for acc in (plan[1].histogram, plan[1].arrival, plan[1].peak, plan[1].excursion, plan[1].core_range):
                 if acc is not None:
                     acc.add(length)
             if plan[1].catch is not None:
@@ -4375,7 +4690,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                          cell_area=None, seed=0, evaluate=None, quantiles=None, bins=DEFAULT_BINS, edges=None,
                          arrival=None, arrival_levels=(0.05, 0.5, 0.95), emergence=None, exposure=None, sites=None,
                          sensitivity=None, compare=None, mc_error=None, peak=None, excursion=None, reweight=None,
-                         catch=None, information=None):
+                         catch=None, information=None, core_range=None):
     '''Posterior predictive spread of one or more chains (`Sampler.save` files or (trace, names)
     pairs).  Burn and thin apply per chain; consecutive rows with identical model parameters are one
     evaluation weighted by the run's length.  pop_model: one PopModel or a list -- with several, one
@@ -4465,8 +4780,22 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     traps, whose days have to be output days of the plan, in `sites.information`.  A UserWarning where a trap's
     largest gain exceeds half of `cap`, the entropy of the member weights: the map is then bounded by the
     ensemble, not by the trap.  Histogram, arrival, peak, excursion, contrast, sensitivity and Monte Carlo error of
-    these maps are not computed.  Without information= no call is added and `information` is None.'''
+    these maps are not computed.  Without information= no call is added and `information` is None.  core_range:
+    mass fractions [p_0, ...] (1..4, each in (0, 1), strictly increasing) or dict(fractions=[...], levels=(0.5, 0.9)),
+    the consensus levels in (0, 1] (check_core_range; not with evaluate=; bad arguments fail before any evaluation):
+    per member its own highest-density regions, 0.5 the core and 0.95 the range.  Each chain then also fills one
+    RangeMaps over the summary's days (strictly increasing, at most 32), reserved to the chain's number of runs and
+    fed the run's weight right after the summary's add, merged in chain order into `core_range`
+    (`core_range_levels`: the consensus levels of its saved regions); with sites= the plan gets a
+    RangeMaps.for_projection of its own outputs (`sites.core_range`).  Emergence and exposure get none here
+    (RangeMaps.for_projection takes them); sensitivity, contrast, Monte Carlo error and reweighting of these maps are
+    not computed.  Without core_range= no call is added and `core_range` is None.'''
     t0 = time.perf_counter()
+    cr_frac = cr_levels = None
+    if core_range is not None and core_range is not False:   # bad core-range arguments fail before any evaluation
+        if evaluate is not None:
+            raise ValueError('core_range= needs the device: not with evaluate=')
+        cr_frac, cr_levels = check_core_range(core_range, days)
     in_plan = None
     if information is not None:       # bad information arguments fail before any evaluation
         pm0 = (pop_model[0] if pop_model else None) if isinstance(pop_model, (list, tuple)) else pop_model
@@ -4561,7 +4890,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     pms = list(pop_model) if isinstance(pop_model, (list, tuple)) else [pop_model]
     if evaluate is None and (not pms or pms[0] is None):
         raise ValueError('a PopModel is needed without evaluate=')
-    if (a_thr or pk_thr is not None or ex_thr) and evaluate is None and days is None:
+    if (a_thr or pk_thr is not None or ex_thr or cr_frac) and evaluate is None and days is None:
         check_arrival_days(range(len(pms[0].days)))
     if evaluate is None:              # as do projections past the model's days
         plans = [(name,) + plan(arg, len(pms[0].days)) for name, arg, plan in wanted]
@@ -4572,6 +4901,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     senses = [None] * nch
     peaks = [None] * nch                       # per chain its PeakPosterior
     excurs = [None] * nch                      # per chain its ExcursionMaps
+    ranges = [None] * nch                      # per chain its RangeMaps
     mcs = [None] * nch                         # per chain its two MonteCarloError sequences
     rws = [None] * nch                         # per chain (ReweightedSummary, _ReweightFeed)
     catches = [None] * nch                     # per chain its CatchPosterior over the day fields
@@ -4603,6 +4933,9 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                 if ex_thr:
                     excurs[ci] = ExcursionMaps(pm, ex_thr, summ.days)
                     excurs[ci].reserve(len(rl))
+                if cr_frac:
+                    ranges[ci] = RangeMaps(pm, cr_frac, summ.days)
+                    ranges[ci].reserve(len(rl))
                 if mc_b:
                     mcs[ci] = []
                     for _half in range(2):
@@ -4656,6 +4989,9 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                         if ex_thr:
                             maps.excursion = ExcursionMaps.for_projection(rs, ex_thr)
                             maps.excursion.reserve(len(rl))
+                        if cr_frac:
+                            maps.core_range = RangeMaps.for_projection(rs, cr_frac)
+                            maps.core_range.reserve(len(rl))
                         if mc_b:
                             maps.mc_error = []
                             for _half in range(2):
@@ -4674,7 +5010,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                                              projected[ci], site_maps[ci], sens, cmp_maps[ci],
                                              (mcs[ci], mc_halves[ci][0]) if mc_b else None, peaks[ci],
                                              excursion=excurs[ci], reweight=rws[ci], catch=catches[ci],
-                                             information=infos[ci])
+                                             information=infos[ci], core_range=ranges[ci])
         except BaseException as e:       # re-raised in the caller's thread
             errs.append((p, e))
 
@@ -4689,7 +5025,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         pms = pms[:1]
         work(0)
     if errs:
-        for s in summaries + histograms + arrivals + senses + peaks + excurs + catches + infos + [pair[0] for pair in rws if pair] + [x for pair in mcs if pair for x in pair] + [x for pl in projected for pair in pl for x in pair] \
+        for s in summaries + histograms + arrivals + senses + peaks + excurs + ranges + catches + infos + [pair[0] for pair in rws if pair] + [x for pair in mcs if pair for x in pair] + [x for pl in projected for pair in pl for x in pair] \
                 + [x for pair in site_maps if pair is not None for x in pair] \
                 + [x for tri in cmp_maps if tri is not None for x in tri[:2]] \
                 + [m for made in late.values() for m in made.values()]:
@@ -4702,6 +5038,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     sens_maps = None
     peak_maps = None
     excur_maps = None
+    range_maps = None
     if evaluate is None:
         summary = summaries[0]
         for s in summaries[1:]:
@@ -4731,6 +5068,11 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
             excur_maps = excurs[0]
             for a in excurs[1:]:
                 excur_maps.merge(a)
+                a.close()
+        if cr_frac:
+            range_maps = ranges[0]
+            for a in ranges[1:]:
+                range_maps.merge(a)
                 a.close()
     rw_maps = rw_info = None
     if rw_plan is not None:
@@ -4841,7 +5183,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                    'diagnostics': diag}
         empty = [n for n in rw_plan['names'] if diag[n]['members'] == 0]
         if empty:
-            for m in [summary, histogram, arrival_maps, sens_maps, peak_maps, excur_maps, rw_maps, mc_pooled,
+            for m in [summary, histogram, arrival_maps, sens_maps, peak_maps, excur_maps, range_maps, rw_maps, mc_pooled,
                       contrast, catch_maps, info_maps] + list(merged.values()) + [merged_sites]:
                 if m is not None:
                     m.close()
@@ -4874,7 +5216,8 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                            None if summary is None else summary.days, histogram, levels, arrival_maps,
                            a_levels if a_thr else None, merged.get('emergence'), merged.get('exposure'),
                            merged_sites, sens_maps, contrast, compare_desc, mc_pooled, mc_desc, peak_maps,
-                           excur_maps, ex_levels if ex_thr else None, rw_maps, rw_info, catch_maps, info_maps)
+                           excur_maps, ex_levels if ex_thr else None, rw_maps, rw_info, catch_maps, info_maps,
+                           range_maps, cr_levels if cr_frac else None)
     if info_maps is not None:         # the stated convention: past cap / 2 the ensemble bounds the map
         warn_information(info_maps)
         if merged_sites is not None and merged_sites.information is not None:

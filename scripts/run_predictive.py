@@ -21,7 +21,10 @@ highest density within the window, the day of the peak and the number of days at
 density and day the region all of which is reached at the same time with a given probability, the region surely
 not reached and the credible band of the contour between them (--excursion-levels: the credible levels of the saved
 regions and areas, each in (0.5, 1]) -- saved as PREFIX_excur.npz (and, with --sites, PREFIX_sites_excur.npz for the
-plan); with --reweight / --reweight-file also the maps under new observations without a new chain -- up to four
+plan); with --core-range also the core-range maps -- per listed mass fraction and day the probability that a cell lies
+in the member's own highest-density region holding that share of its wasps, 0.5 the core and 0.95 the range
+(--core-range-levels: the consensus levels of the saved regions' areas, each in (0, 1]) -- saved as PREFIX_range.npz
+(and, with --sites, PREFIX_sites_range.npz for the plan); with --reweight / --reweight-file also the maps under new observations without a new chain -- up to four
 named scenarios, each a list of probe observations 'east,north,day,kind,rate[,n]' (kind: count with the number
 found n, none, found; rate: the expected number found per wasp in the cell) or a .npy file of one log-weight per
 chain row after burn and thin (several chains: concatenated in chain order), by importance reweighting of the
@@ -43,6 +46,7 @@ Without --chain a short chain is sampled first (--samples) and saved next to --o
         [--sites 'E,N,AMOUNT[,LAG];...'] [--sites-days d1,d2,...] [--sensitivity [name,name,...]]
         [--compare-sites 'E,N,AMOUNT[,LAG];...'] [--peak 1,10] [--peak-levels 0.05,0.5,0.95]
         [--excursion 1,10] [--excursion-levels 0.9,0.95]
+        [--core-range 0.5,0.95] [--core-range-levels 0.5,0.9]
         [--reweight 'NAME:east,north,day,kind,rate[,n];...'] [--reweight-file NAME=weights.npy]
         [--catch 'DAY,RATE[,N];...'] [--catch-levels 0.5,0.95] [--catch-emergence 'OBSDAY,RATE[,N];...']
         [--information 'DAY,RATE[,YMAX];...']
@@ -137,6 +141,10 @@ def main():
                                                     '(default: off)')
     ap.add_argument('--excursion-levels', default='0.9,0.95',
                     help='credible levels in (0.5, 1] of the saved excursion regions and areas (with --excursion)')
+    ap.add_argument('--core-range', default='', help='core-range maps at the listed mass fractions in (0, 1), e.g. '
+                                                     '0.5,0.95 (default: off)')
+    ap.add_argument('--core-range-levels', default='0.5,0.9',
+                    help='consensus levels in (0, 1] of the saved core-range areas (with --core-range)')
     ap.add_argument('--catch', default='', help="traps 'DAY,RATE[,N];...': per cell the probability that a trap of "
                     'effort RATE on model day DAY catches at least N (default 1) (default: off)')
     ap.add_argument('--catch-levels', default='0.5,0.95', help='levels of the catch maps (with --catch)')
@@ -160,7 +168,7 @@ def main():
     from parasitoids_amd import mcmc
     from parasitoids_amd.pop_model import PopModel
     from parasitoids_amd.predictive import (bin_edges, check_arrival_thresholds, check_contrast_thresholds,
-                                            check_excursion, check_levels, check_peak, check_sens_params, contrast_plan,
+                                            check_core_range, check_excursion, check_levels, check_peak, check_sens_params, contrast_plan,
                                             emergence_plan, exposure_plan, mc_error_plan, posterior_predictive,
                                             sites_plan)
     mc_error = None
@@ -187,6 +195,11 @@ def main():
         excursion = dict(thresholds=[float(t) for t in args.excursion.split(',') if t.strip()],
                          levels=[float(q) for q in args.excursion_levels.split(',') if q.strip()])
         check_excursion(excursion)
+    core_range = None
+    if args.core_range:                  # as do bad --core-range fractions or levels
+        core_range = dict(fractions=[float(t) for t in args.core_range.split(',') if t.strip()],
+                          levels=[float(q) for q in args.core_range_levels.split(',') if q.strip()])
+        check_core_range(core_range)
     emergence = exposure = None
     if args.emergence:
         cday, _, obs = args.emergence.partition(':')
@@ -273,7 +286,8 @@ def main():
                                compare=compare, mc_error=mc_error, peak=peak, excursion=excursion,
                                **({'reweight': reweight} if reweight else {}),
                                **({'catch': catch} if catch else {}),
-                               **({'information': information} if information else {}))
+                               **({'information': information} if information else {}),
+                               **({'core_range': core_range} if core_range else {}))
     dt = time.perf_counter() - t0
     # accumulate-kernel time: the same members once more with HIP events around every add
     from parasitoids_amd.predictive import (ArrivalMaps, ExcursionMaps, MonteCarloError, PeakMaps, PlanContrast, Projection,
@@ -299,6 +313,10 @@ def main():
     A = ArrivalMaps(pm, arrival) if arrival else None
     PK = PeakMaps(pm, peak['thresholds']) if peak else None
     EX = ExcursionMaps(pm, excursion['thresholds']) if excursion else None
+    RG = None
+    if core_range:
+        from parasitoids_amd.predictive import RangeMaps
+        RG = RangeMaps(pm, core_range['fractions'])
     RW = RWF = None
     if reweight:
         from parasitoids_amd.predictive import ReweightedSummary, _ReweightFeed
@@ -333,6 +351,9 @@ def main():
         if EX is not None:
             EX.reserve(8)
             EX.profile(True)
+        if RG is not None:
+            RG.reserve(8)
+            RG.profile(True)
         if X is not None:
             X.profile(True)
         if ME is not None:
@@ -358,6 +379,8 @@ def main():
                 except Exception:
                     continue
                 S.add(length)
+                if RG is not None:
+                    RG.add(length)
                 if CF is not None:
                     CF.apply()
                     CP.apply()
@@ -405,6 +428,10 @@ def main():
         ex_ms, ex_launches = EX.profile()[:2]
         EX.close()
         res.excursion.profile(True)     # the finalize and every map launch of the save
+    if RG is not None:
+        rg_ms, rg_launches = RG.profile()[:2]
+        RG.close()
+        res.core_range.profile(True)    # every map launch of the save
     if CF is not None:
         cf_ms, cf_launches = CF.profile()
         cp_ms, cp_launches = CP.profile()
@@ -510,6 +537,14 @@ def main():
         out['excur_map_launches'] = ex_prof[5]
         out['excur_bytes'] = res.excursion.nbytes
         out['outputs'] += ['%s_excur.npz' % args.out] + (['%s_sites_excur.npz' % args.out] if sites else [])
+    if core_range:
+        out['range_ms_per_member'] = round(rg_ms / max(rg_launches, 1), 4)
+        out['range_launches_timed'] = rg_launches
+        out['range_fractions'] = core_range['fractions']
+        out['range_members'] = res.core_range.members
+        out['range_maps_ms_total'] = round(res.core_range.profile()[2], 3)
+        out['range_bytes'] = res.core_range.nbytes
+        out['outputs'] += ['%s_range.npz' % args.out] + (['%s_sites_range.npz' % args.out] if sites else [])
     if sens:
         x_per = x_ms / max(x_launches, 1)
         out['sensitivity_add_ms_per_member'] = round(x_per, 4)
@@ -563,7 +598,8 @@ def main():
         res.sensitivity.close()
     if res.mc_error is not None:
         res.mc_error.close()
-    for pr in (res.emergence, res.exposure, res.sites, res.contrast, res.peak, res.excursion, res.catch, res.information):
+    for pr in (res.emergence, res.exposure, res.sites, res.contrast, res.peak, res.excursion, res.catch, res.information,
+               res.core_range):
         if pr is not None:
             pr.close()
     for p in pms:
