@@ -56,6 +56,7 @@ import json
 import os
 import threading
 import time
+import types
 
 import numpy as np
 
@@ -1591,7 +1592,223 @@ def exposure_plan(exposure, ndays=None):
     return check_weights(exposure_weights(in_days, upto), len(in_days)), in_days, upto
 
 
-class ProjectedMaps():
+# ------------------------------------------------------------------ the accumulators fed from one source of fields
+# The order in which posterior_predictive feeds one member to the accumulators of one source of fields, per kind of
+# source: the model's day fields, a Projection, the ReleaseSites of sites= and, after it, plan B of compare=.
+# 'apply' is the source's own.  The three orders differ for no better reason than the history of the maps.
+FEED_ORDER = {
+    'days': ('summary', 'core_range', 'reweight', 'catch', 'information', 'excursion', 'mc_error', 'sensitivity',
+             'histogram', 'arrival', 'peak'),
+    'projection': ('apply', 'summary', 'reweight', 'mc_error', 'sensitivity', 'histogram', 'catch'),
+    'sites': ('apply', 'summary', 'reweight', 'mc_error', 'sensitivity', 'histogram', 'arrival', 'peak', 'excursion',
+              'core_range', 'catch', 'information'),
+    'compare': ('apply', 'contrast'),
+}
+
+
+def _add_length(acc, fs, m):
+    acc.add(m.length)
+
+
+def _add_halves(seqs, fs, m):
+    '''the run's length, split at the chain's half boundary row, to the chain's two MonteCarloError sequences'''
+    for seq, w in zip(seqs, mc_split(m.first, m.length, fs._half)):
+        if w:
+            seq.add(w)
+
+
+def _add_reweighted(acc, fs, m):
+    if fs._rw_feed is not None:        # the day fields': one gather of all probes; the later sets share the log-weights
+        m.lam = fs._rw_feed.log_weights(fs._source, m.first, m.length)
+    acc.add(m.lam, m.length)
+
+
+def _add_catch(acc, fs, m):
+    acc.add(m.length, m.lam)
+    if acc.mc_error is not None:
+        _add_halves(acc.mc_error, fs, m)
+
+
+# Every accumulator a _FieldSet can hold, and how it takes a member m (theta, first row, length, lam: the run's
+# log-weights or None) of the set fs.
+FEED = {
+    'apply': lambda acc, fs, m: fs._source.apply(),
+    'summary': _add_length,
+    'histogram': _add_length,
+    'arrival': _add_length,
+    'sensitivity': lambda acc, fs, m: acc.add(m.theta, m.length),
+    'peak': _add_length,
+    'excursion': _add_length,
+    'core_range': _add_length,
+    'reweight': _add_reweighted,
+    'catch': _add_catch,
+    'information': lambda acc, fs, m: acc.add(m.length, m.lam),
+    'mc_error': _add_halves,
+    'contrast': _add_length,
+}
+ACCUMULATORS = tuple(name for name in FEED if name != 'apply')
+
+
+def _owned_by(inner, wrap, *args):
+    '''wrap(inner, *args), which then owns inner; where that fails inner is closed'''
+    try:
+        return wrap(inner, *args)
+    except BaseException:
+        inner.close()
+        raise
+
+
+def _build_mc_error(fs, q):
+    if q.mc_b:
+        fs.mc_error = []
+        for _half in range(2):
+            fs.mc_error.append(fs._over(MonteCarloError, (q.mc_b, fs._days, q.thresholds), (q.mc_b, q.thresholds)))
+    return fs.mc_error
+
+
+def _build_reweight(fs, q):
+    if q.rw_plan is not None:
+        names = q.rw_plan['names']
+        fs.reweight = fs._over(ReweightedSummary, (names, fs._days, q.thresholds), (names, q.thresholds))
+        if fs._kind == 'days':
+            fs._rw_feed = _ReweightFeed(q.rw_plan, fs._chain)
+    return fs.reweight
+
+
+def _build_catch(fs, q):
+    traps = fs._traps.get('catch')
+    if traps:
+        cp = _owned_by(fs._over(CatchFields, traps, traps), CatchPosterior, q.ct_plan['levels'], q.mc_b, q.rw_names)
+        cp.given = q.ct_plan['given']
+        return cp
+
+
+def _build_information(fs, q):
+    traps = fs._traps.get('information')
+    if traps:
+        ip = _owned_by(fs._over(InformationFields, traps, traps), InformationPosterior, q.rw_names)
+        ip.given = q.in_plan['given']
+        return ip
+
+
+# How each accumulator is built for the set fs from the checked request q (None or empty: not asked for).  The choice
+# between the model's day fields and a source's outputs is _FieldSet._over's.
+BUILD = {
+    'summary': lambda fs, q: fs._over(SpreadSummary, (q.days, q.thresholds), (q.thresholds,)),
+    'histogram': lambda fs, q: q.levels and fs._over(SpreadHistogram, (q.days, q.bins, q.edges), (q.bins, q.edges)),
+    'arrival': lambda fs, q: q.a_thr and fs._over(ArrivalMaps, (q.a_thr, fs._days), (q.a_thr,)),
+    'sensitivity': lambda fs, q: q.s_names and fs._over(SensitivityMaps, (q.s_names, fs._days), (q.s_names,)),
+    'peak': lambda fs, q: q.pk_thr is not None and _owned_by(
+        fs._over(PeakMaps, (q.pk_thr, fs._days), (q.pk_thr,)), PeakPosterior, q.thresholds, q.pk_levels,
+        q.bins if q.levels else None, q.edges if q.levels else None),
+    'excursion': lambda fs, q: q.ex_thr and fs._over(ExcursionMaps, (q.ex_thr, fs._days), (q.ex_thr,)),
+    'core_range': lambda fs, q: q.cr_frac and fs._over(RangeMaps, (q.cr_frac, fs._days), (q.cr_frac,)),
+    'reweight': _build_reweight,
+    'catch': _build_catch,
+    'information': _build_information,
+    'mc_error': _build_mc_error,
+    'contrast': lambda fs, q: PlanContrast(fs._against, fs._source, q.thresholds),
+}
+
+
+class _FieldSet():
+    '''The accumulators posterior_predictive feeds from one source of fields -- the model's day fields, a Projection
+    or a ReleaseSites -- for one chain: one attribute per name of ACCUMULATORS, None where not asked for (`mc_error`:
+    while the chains run the chain's two sequences).  `fed_from` names the source, `build` constructs what the
+    request asks for, `feed` adds one member in FEED_ORDER, `merge` takes another chain's set, `close` closes the
+    accumulators and `release` the source.'''
+
+    def __init__(self, **accumulators):
+        for name in ACCUMULATORS:
+            setattr(self, name, accumulators.get(name))
+        self.plan = None
+        self._kind = self._name = self._source = self._against = self._days = self._half = self._rw_feed = None
+        self._chain = None
+        self._owns = False
+        self._traps = {}
+
+    def fed_from(self, kind, source, name=None, owns=True, against=None, **traps):
+        '''kind: a key of FEED_ORDER; name: the driver's name of the source (default: the kind); owns: release()
+        closes the source; against: plan A of a 'compare' set; traps: per 'catch' / 'information' the arguments of its
+        fields after the source, None for none'''
+        self._kind, self._name, self._source, self._owns = kind, name or kind, source, owns
+        self._against, self._traps = against, traps
+        return self
+
+    def _over(self, cls, day_args, out_args):
+        '''cls over this set's source: the model's day fields or, for_projection, a source's outputs'''
+        if self._kind == 'days':
+            return cls(self._source, *day_args)
+        return cls.for_projection(self._source, *out_args)
+
+    def build(self, q, chain, nruns):
+        '''every accumulator of this kind of source that the request q asks for, for chain `chain` of nruns runs;
+        what is built is on the set at once, so that close() finds it whatever fails later'''
+        self._chain = chain
+        self._half = q.mc_halves[chain][0] if q.mc_b else None
+        for name in FEED_ORDER[self._kind]:
+            if name == 'apply':
+                continue
+            acc = BUILD[name](self, q) or None
+            setattr(self, name, acc)
+            if name == 'summary' and self._kind == 'days':
+                self._days = acc.days
+            if name in ('excursion', 'core_range') and acc is not None:
+                acc.reserve(nruns)
+        return self
+
+    def feed(self, m):
+        for name in FEED_ORDER[self._kind]:
+            acc = getattr(self, name, None)
+            if acc is not None or name == 'apply':
+                FEED[name](acc, self, m)
+
+    def merge(self, other):
+        for name in ACCUMULATORS:
+            mine, theirs = getattr(self, name), getattr(other, name)
+            # the Monte Carlo error sequences are pooled (_merge_chains), as are a catch's own, not merged
+            if name != 'mc_error' and mine is not None and theirs is not None:
+                mine.merge(theirs)
+
+    def close(self):
+        for name in ACCUMULATORS:
+            acc = getattr(self, name)
+            for a in (acc if isinstance(acc, (list, tuple)) else [acc]):
+                if a is not None:
+                    a.close()
+
+    def release(self):
+        '''close the source, where it is this set's: the accumulators hold what they need'''
+        if self._owns and self._source is not None:
+            self._source.close()
+        self._source = self._against = None
+
+
+def _pool_halves(owners):
+    '''the Monte Carlo error sequences of every chain's owner (a _FieldSet or a CatchPosterior) pooled in chain order
+    into the first's `mc_error` (pool_mc_error, which closes the others)'''
+    if owners[0].mc_error is not None:
+        pooled = pool_mc_error([o.mc_error for o in owners])
+        for o in owners:
+            o.mc_error = None
+        owners[0].mc_error = pooled
+
+
+def _merge_chains(sets):
+    '''one source's sets, one per chain, merged in chain order into the first, which is returned; the others'
+    accumulators are closed.  The sources stay open: a catch reads its source's fields, a contrast both plans'.'''
+    first = sets[0]
+    _pool_halves(sets)
+    if first.catch is not None:
+        _pool_halves([fs.catch for fs in sets])
+        first.catch.fields.close()     # the accumulators hold what they need; an information's fields hold its maps
+    for other in sets[1:]:
+        first.merge(other)
+        other.close()
+    return first
+
+
+class ProjectedMaps(_FieldSet):
     '''The posterior of one projection, as posterior_predictive returns it: `weights` [nout, nin], `in_days`,
     `labels` (one per output), `summary` (SpreadSummary.for_projection) and `histogram`
     (SpreadHistogram.for_projection, None without quantile levels); both take the output index.  Of a release
@@ -1606,71 +1823,19 @@ class ProjectedMaps():
     ReweightedSummary.for_projection (None unless asked for), which takes the scenario's name and the output index.
     `catch`: the CatchPosterior over the outputs (None unless asked for), whose traps name an output label.
     `information`: the InformationPosterior over the outputs (None unless asked for), likewise.  `core_range`: the
-    RangeMaps.for_projection of a release plan's outputs (None unless asked for), whose maps take the output day.'''
+    RangeMaps.for_projection of a release plan's outputs (None unless asked for), whose maps take the output day.
+    `merge` and `close` take every accumulator there is (ACCUMULATORS).'''
 
     def __init__(self, weights, in_days, labels, summary, histogram=None, arrival=None, plan=None,
                  sensitivity=None, mc_error=None, peak=None, excursion=None, reweight=None, catch=None,
                  information=None, core_range=None):
-        self.catch = catch
-        self.information = information
-        self.core_range = core_range
-        self.peak = peak
-        self.excursion = excursion
-        self.reweight = reweight
-        self.sensitivity = sensitivity
-        self.mc_error = mc_error
+        super().__init__(summary=summary, histogram=histogram, arrival=arrival, sensitivity=sensitivity,
+                         mc_error=mc_error, peak=peak, excursion=excursion, reweight=reweight, catch=catch,
+                         information=information, core_range=core_range)
         self.weights = weights
         self.in_days = in_days
         self.labels = labels
-        self.summary = summary
-        self.histogram = histogram
-        self.arrival = arrival
         self.plan = plan
-
-    def merge(self, other):
-        self.summary.merge(other.summary)
-        if self.histogram is not None:
-            self.histogram.merge(other.histogram)
-        if self.arrival is not None:
-            self.arrival.merge(other.arrival)
-        if self.sensitivity is not None:
-            self.sensitivity.merge(other.sensitivity)
-        if self.peak is not None:
-            self.peak.merge(other.peak)
-        if self.excursion is not None:
-            self.excursion.merge(other.excursion)
-        if self.core_range is not None:
-            self.core_range.merge(other.core_range)
-        if self.reweight is not None:
-            self.reweight.merge(other.reweight)
-        if self.catch is not None and other.catch is not None:       # the driver merges the chains' catches itself
-            self.catch.merge(other.catch)
-        if self.information is not None and other.information is not None:   # as the catches
-            self.information.merge(other.information)
-
-    def close(self):
-        self.summary.close()
-        if self.information is not None:
-            self.information.close()
-        if self.catch is not None:
-            self.catch.close()
-        if self.reweight is not None:
-            self.reweight.close()
-        if self.excursion is not None:
-            self.excursion.close()
-        if self.core_range is not None:
-            self.core_range.close()
-        if self.peak is not None:
-            self.peak.close()
-        if self.histogram is not None:
-            self.histogram.close()
-        if self.arrival is not None:
-            self.arrival.close()
-        if self.sensitivity is not None:
-            self.sensitivity.close()
-        if self.mc_error is not None:
-            for s in (self.mc_error if isinstance(self.mc_error, (list, tuple)) else [self.mc_error]):
-                s.close()
 
 
 # ------------------------------------------------------------------ release plans
@@ -4567,41 +4732,15 @@ class PredictiveResult():
         return str(outfile) + '.npz', str(outfile) + '.json'
 
 
-def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, locinfo, histogram=None,
-                   arrival=None, projected=(), plan=None, sens=None, compare=None, mc=None, peak=None,
-                   excursion=None, reweight=None, catch=None, information=None, core_range=None):
-    '''one chain: evaluate every run, add it to the summary (and the histogram, the arrival maps; projected:
-    (Projection, ProjectedMaps) pairs, applied and then added; plan: a (ReleaseSites, ProjectedMaps) pair, the
-    models of its later release days evaluated with the base model -- a member for which any of them fails is
-    a failed member and is added nowhere -- applied and added last; sens: the chain's SensitivityMaps, and
-    every ProjectedMaps' own, fed the run's theta after the summary beside it; compare: a (ReleaseSites of plan
-    B, PlanContrast, {lag: model} of both plans' later release days) triple -- every model of that union is
-    evaluated once per member, and after the plan's own adds plan B is applied and the contrast added; mc: (the
-    chain's two MonteCarloError sequences, its half boundary row) -- after every summary's add the run's length
-    is split at that row and added to the sequence or sequences it falls in, those of every ProjectedMaps too;
-    peak: the chain's PeakPosterior, fed last of the day-based accumulators -- the plan's own after the plan's;
-    excursion: the chain's ExcursionMaps, fed the run's weight right after the summary -- the plan's own after the
-    plan's other accumulators; reweight: (the chain's ReweightedSummary, its _ReweightFeed) -- right after the
-    summary the run's log-weights are taken, by one gather of all probes, and the member added with them and the
-    run's length, to every ProjectedMaps' own after its summary too; catch: the chain's CatchPosterior -- right after the summary and the
-    reweighted summary, whose log-weights it shares, its fields are applied and added with the run's length, its
-    Monte Carlo error sequences fed like the others; every ProjectedMaps' own after its other accumulators;
-    information: the chain's InformationPosterior, applied and added with the run's length and the same log-weights
-    right after the catch; the plan's own after the plan's catch; core_range: the chain's RangeMaps, fed the run's
-    weight right after the summary's add -- the plan's own after the plan's other accumulators)
-    -> (expected per run or None, failed)'''
+def _evaluate_runs(pm, rows, run_list, model_cols, evaluate, want_obs, locinfo, sets=()):
+    '''one chain: evaluate every run and feed it to the chain's sets (_FieldSet) in the order given, each in the
+    FEED_ORDER of its kind.  With a 'sites' set the models of the plan's later release days are evaluated with the
+    base model -- with a 'compare' set those of both plans' (its `lagged`), each once -- and a member for which any
+    of them fails is a failed member and is added nowhere.  -> (expected per run or None, failed)'''
     expected = []
     failed = 0
-
-    def mc_add(pair, first, length):
-        for seq, w in zip(pair, mc_split(first, length, mc[1])):
-            if w:
-                seq.add(w)
-
-    def catch_add(cp, first, length, lam):
-        cp.add(length, lam)
-        if cp.mc_error is not None and mc is not None:
-            mc_add(cp.mc_error, first, length)
+    kinds = {fs._kind: fs for fs in sets}
+    plan, both = kinds.get('sites'), kinds.get('compare')
     for first, length in run_list:
         theta = rows[first, model_cols]
         if evaluate is not None:
@@ -4612,11 +4751,11 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
             continue
         try:
             pm.evaluate(*mcmc.model_args(theta), want_stats=False)
-            if compare is not None:
-                for lag, m in sorted(compare[2].items()):
-                    m.evaluate(*mcmc.model_args(theta), ndays=plan[0].days[-1] - lag + 1, want_stats=False)
+            if both is not None:
+                for lag, m in sorted(both.lagged.items()):
+                    m.evaluate(*mcmc.model_args(theta), ndays=plan._source.days[-1] - lag + 1, want_stats=False)
             elif plan is not None:
-                plan[0].evaluate_lagged(*mcmc.model_args(theta))
+                plan._source.evaluate_lagged(*mcmc.model_args(theta))
         except (AssertionError, ValueError):
             failed += 1
             expected.append(None)
@@ -4627,63 +4766,156 @@ def _evaluate_runs(pm, summary, rows, run_list, model_cols, evaluate, want_obs, 
             failed += 1
             expected.append(None)
             continue
-        summary.add(length)
-        if core_range is not None:
-            core_range.add(length)
-        lam = None
-        if reweight is not None:
-            lam = reweight[1].log_weights(pm, first, length)
-            reweight[0].add(lam, length)
-        if catch is not None:
-            catch_add(catch, first, length, lam)
-        if information is not None:
-            information.add(length, lam)
-        if excursion is not None:
-            excursion.add(length)
-        if mc is not None:
-            mc_add(mc[0], first, length)
-        if sens is not None:
-            sens.add(theta, length)
-        if histogram is not None:
-            histogram.add(length)
-        if arrival is not None:
-            arrival.add(length)
-        if peak is not None:
-            peak.add(length)
-        for proj, maps in projected:
-            proj.apply()
-            maps.summary.add(length)
-            if maps.reweight is not None:
-                maps.reweight.add(lam, length)
-            if maps.mc_error is not None:
-                mc_add(maps.mc_error, first, length)
-            if maps.sensitivity is not None:
-                maps.sensitivity.add(theta, length)
-            if maps.histogram is not None:
-                maps.histogram.add(length)
-            if maps.catch is not None:
-                catch_add(maps.catch, first, length, lam)
-        if plan is not None:
-            plan[0].apply()
-            plan[1].summary.add(length)
-            if plan[1].reweight is not None:
-                plan[1].reweight.add(lam, length)
-            if plan[1].mc_error is not None:
-                mc_add(plan[1].mc_error, first, length)
-            if plan[1].sensitivity is not None:
-                plan[1].sensitivity.add(theta, length)
-            for acc in (plan[1].histogram, plan[1].arrival, plan[1].peak, plan[1].excursion, plan[1].core_range):
-                if acc is not None:
-                    acc.add(length)
-            if plan[1].catch is not None:
-                catch_add(plan[1].catch, first, length, lam)
-            if plan[1].information is not None:
-                plan[1].information.add(length, lam)
-        if compare is not None:
-            compare[0].apply()
-            compare[1].add(length)
+        member = types.SimpleNamespace(theta=theta, first=first, length=length, lam=None)
+        for fs in sets:
+            fs.feed(member)
         expected.append(mcmc.expected_observations(pm, locinfo) if want_obs else True)
     return expected, failed
+
+
+def _check_request(q):
+    '''Everything of posterior_predictive's arguments (q: a namespace of them) that can fail before any evaluation,
+    in a fixed order -- of two bad arguments the earlier one is reported.  -> q, with the checked plans beside the
+    arguments: cr_frac / cr_levels, in_plan, ct_plan, rw_plan / rw_names, ex_thr / ex_levels, pk_thr / pk_levels,
+    mc_batches, mc_b / mc_halves, s_names, levels, a_thr / a_levels, plans [(name, W, in_days, labels)], site_plan,
+    cmp_plan, the loaded chains `prepared` [(rows, runs, model columns, observation columns, source)], `pms` (the
+    models) and want_obs.'''
+    pm0 = (q.pop_model[0] if q.pop_model else None) if isinstance(q.pop_model, (list, tuple)) else q.pop_model
+    days, thresholds = q.days, q.thresholds
+    q.cr_frac = q.cr_levels = q.in_plan = q.ct_plan = q.rw_plan = q.ex_thr = q.ex_levels = None
+    q.pk_thr = q.pk_levels = q.mc_batches = None
+
+    def ndays0():                     # the model is touched only where an option needs it
+        return None if pm0 is None else len(pm0.days)
+
+    def check_core_range_arg():
+        q.cr_frac, q.cr_levels = check_core_range(q.core_range, days)
+
+    def check_information_arg():
+        q.in_plan = check_information(q.information, ndays0(), q.evaluate)
+
+    def check_catch_arg():
+        q.ct_plan = check_catch(q.catch, ndays0(), q.emergence, q.evaluate)
+
+    def check_reweight_arg():
+        q.rw_plan = check_reweight(q.reweight, None if pm0 is None else pm0.rad_dist,
+                                   None if pm0 is None else pm0.rad_res, ndays0())
+        check_peak_thresholds(thresholds)
+        nd = len(days) if days is not None else (ndays0() if pm0 is not None else 1)
+        if not 1 <= nd <= MAX_REWEIGHT_SLOTS:
+            raise ValueError('reweight= takes 1..%d days, got %d' % (MAX_REWEIGHT_SLOTS, nd))
+
+    def check_excursion_arg():
+        q.ex_thr, q.ex_levels = check_excursion(q.excursion)
+        if days is not None:
+            check_arrival_days(days)
+
+    def check_peak_arg():
+        q.pk_thr, q.pk_levels = check_peak(q.peak)
+        if days is not None:
+            check_arrival_days(days)
+
+    def check_mc_error_arg():
+        q.mc_batches = mc_error_plan(q.mc_error)
+        check_mc_thresholds(thresholds)
+    # the options that need the device, in the order in which they are checked: (name, False switches it off too,
+    # its check).  check_information and check_catch refuse evaluate= themselves, after the argument's shape.
+    for name, or_false, check in (('core_range', True, check_core_range_arg),
+                                  ('information', False, check_information_arg), ('catch', False, check_catch_arg),
+                                  ('reweight', False, check_reweight_arg), ('excursion', True, check_excursion_arg),
+                                  ('peak', True, check_peak_arg), ('mc_error', True, check_mc_error_arg)):
+        arg = getattr(q, name)
+        if arg is None or (or_false and arg is False):
+            continue
+        if q.evaluate is not None and name not in ('information', 'catch'):
+            raise ValueError('%s= needs the device: not with evaluate=' % name)
+        check()
+    q.rw_names = q.rw_plan['names'] if q.rw_plan is not None else None
+    q.s_names = check_sens_params(q.sensitivity) if q.sensitivity is not None and q.sensitivity is not False else None
+    q.levels = (check_levels(q.quantiles) if q.quantiles is not None else []) or None
+    if q.levels:
+        bin_edges(q.bins, q.edges)    # a bad edge definition
+    q.a_thr = q.a_levels = None
+    if q.arrival is not None:
+        q.a_thr = check_arrival_thresholds(q.arrival)
+        q.a_levels = check_levels(q.arrival_levels)
+        if days is not None:
+            check_arrival_days(days)
+    wanted = [(name, arg, plan) for name, arg, plan in (('emergence', q.emergence, emergence_plan),
+                                                        ('exposure', q.exposure, exposure_plan)) if arg is not None]
+    q.plans = [(name,) + plan(arg) for name, arg, plan in wanted]      # bad projection arguments
+    q.site_plan = None
+    if q.sites is not None:           # a bad release plan: its cells, days and lags against the model if there is one
+        q.site_plan = sites_plan(q.sites, pm0)
+        if pm0 is None:
+            q.site_plan = None
+        else:
+            for what, tp in (('catch', q.ct_plan), ('information', q.in_plan)):
+                off = [t for t in tp['traps'] if t[0] not in q.site_plan[1]] if tp is not None else []
+                if off:
+                    raise ValueError('%s: trap %r is not on an output day of the release plan %r'
+                                     % (what, off[0], list(q.site_plan[1])))
+    q.cmp_plan = None
+    if q.compare is not None:         # a bad plan B, or one without a plan A to compare with
+        q.cmp_plan = contrast_plan(q.compare, q.sites, pm0)
+        check_contrast_thresholds(thresholds)
+        if pm0 is None:
+            q.cmp_plan = None
+    chains = q.chains
+    if isinstance(chains, (str, os.PathLike)) or (isinstance(chains, tuple) and len(chains) == 2
+                                                   and not isinstance(chains[0], (str, os.PathLike, tuple))):
+        chains = [chains]
+    loaded = [load_chain(c) for c in chains]
+    q.want_obs = q.locinfo is not None
+    model_want = model_names()
+    obs_want = nuisance_names()
+    if q.want_obs:
+        obs_want = obs_want + ['sent_obs_probs_{}'.format(k) for k in q.locinfo.sent_ids]
+    q.prepared = []
+    for trace, names, src in loaded:
+        mcols = _columns(names, model_want)
+        ocols = _columns(names, obs_want) if q.want_obs else None
+        rows, rl = runs(trace, mcols, q.burn, q.thin)
+        q.prepared.append((rows, rl, mcols, ocols, src))
+    if q.rw_plan is not None:         # row log-weights that do not fit the chains
+        check_reweight_rows(q.rw_plan, [len(p[0]) for p in q.prepared])
+    q.mc_b = q.mc_halves = None
+    if q.mc_batches:                  # a chain shorter than the batches asked for
+        q.mc_b, q.mc_halves = mc_batch_plan([len(p[0]) for p in q.prepared], q.mc_batches)
+    q.pms = list(q.pop_model) if isinstance(q.pop_model, (list, tuple)) else [q.pop_model]
+    if q.evaluate is None and (not q.pms or q.pms[0] is None):
+        raise ValueError('a PopModel is needed without evaluate=')
+    if (q.a_thr or q.pk_thr is not None or q.ex_thr or q.cr_frac) and q.evaluate is None and days is None:
+        check_arrival_days(range(len(q.pms[0].days)))
+    if q.evaluate is None:            # projections past the model's days
+        q.plans = [(name,) + plan(arg, len(q.pms[0].days)) for name, arg, plan in wanted]
+    return q
+
+
+def _build_sets(sets, q, pm, chain, nruns, late):
+    '''the sets of one chain on the model pm, appended to `sets` in the order in which a member is fed to them: the
+    day fields', one per projection, the release plan's and the contrast's.  A set is in `sets` before it is built,
+    so that the caller can close whatever a failure leaves.  late: {lag: model} of the later release days or None.'''
+    def begin(fs, kind, source, name=None, **kw):
+        sets.append(fs.fed_from(kind, source, name, **kw))
+        return fs
+    ct, info = q.ct_plan, q.in_plan
+    day_traps = dict(catch=ct and (ct['traps'],), information=info and (info['traps'],))
+    begin(_FieldSet(), 'days', pm, owns=False, **day_traps).build(q, chain, nruns)
+    for name, W, in_days, labels in q.plans:
+        traps = (ct['emergence'], labels) if name == 'emergence' and ct is not None and ct['emergence'] else None
+        begin(ProjectedMaps(W, in_days, labels, None), 'projection', Projection(pm, W, in_days), name,
+              catch=traps).build(q, chain, nruns)
+    if q.site_plan is not None:
+        rs = ReleaseSites(pm, q.sites['sites'], q.site_plan[1], late)
+        fs = begin(ProjectedMaps(None, None, None, None), 'sites', rs, **day_traps)
+        fs.labels, fs.plan = list(rs.days), rs.describe()
+        fs.build(q, chain, nruns)
+        if q.cmp_plan is not None:
+            rb = ReleaseSites(pm, q.compare['sites'], q.site_plan[1], late)
+            fs = begin(_FieldSet(), 'compare', rb, against=rs)
+            fs.lagged, fs.plan = late, rb.describe()
+            fs.build(q, chain, nruns)
 
 
 def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, thresholds=(), locinfo=None,
@@ -4691,226 +4923,137 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                          arrival=None, arrival_levels=(0.05, 0.5, 0.95), emergence=None, exposure=None, sites=None,
                          sensitivity=None, compare=None, mc_error=None, peak=None, excursion=None, reweight=None,
                          catch=None, information=None, core_range=None):
-    '''Posterior predictive spread of one or more chains (`Sampler.save` files or (trace, names)
-    pairs).  Burn and thin apply per chain; consecutive rows with identical model parameters are one
-    evaluation weighted by the run's length.  pop_model: one PopModel or a list -- with several, one
-    host thread per model runs its chains, each chain into its own summary, and the summaries are
-    merged in chain order (the result does not depend on the interleaving).  locinfo: observations
-    for the observation-level predictive (every row: the rates of its run's evaluation with its own
-    nuisance parameters).  evaluate(theta) -> expected observations or None: no device, no summary.
-    quantiles: levels in (0, 1]; each chain then also fills a SpreadHistogram (bins / edges as
-    bin_edges) with the same weights, merged in chain order into `histogram`.  arrival: thresholds (1..4,
-    finite, > 0, strictly increasing); each chain then also fills ArrivalMaps over the summary's days
-    (strictly increasing, at most 32) with the same weights, merged in chain order into `arrival`;
-    arrival_levels: the levels of its saved arrival-day quantile maps.  emergence: dict(collection_day=C,
-    obs_days=None) (emergence_plan); exposure: model days [D1, D2, ...] (exposure_plan); each chain then also
-    applies that Projection after every evaluation and adds its outputs, with the same weights, to a
-    SpreadSummary.for_projection (same thresholds) and, with quantiles, a SpreadHistogram.for_projection
-    (same edges), merged in chain order into `emergence` / `exposure` (ProjectedMaps).  sites:
-    dict(sites=[(east_m, north_m, amount[, lag_days]), ...], days=None) (sites_plan); each chain then also
-    builds one ReleaseSites (the models of the later release days, lagged_models, once per model), evaluates those models
-    with every member, applies the plan and adds its outputs, with the same weights, to a
-    SpreadSummary.for_projection (same thresholds), with quantiles a SpreadHistogram.for_projection (same
-    edges) and with arrival an ArrivalMaps.for_projection (same thresholds), merged in chain order into `sites`
-    (ProjectedMaps with `plan` and `arrival`).  sensitivity: True (all 15 model parameters) or names from
-    mcmc.MODEL_BLOCK (check_sens_params); each chain then also fills a SensitivityMaps over the summary's days
-    with every run's theta and length, after the summary, merged in chain order into `sensitivity`, and every
-    projection and plan asked for gets a SensitivityMaps.for_projection of its own, fed after its summary.
+    '''Posterior predictive spread of one or more chains (`Sampler.save` files or (trace, names) pairs). Burn and
+    thin apply per chain; consecutive rows with identical model parameters are one evaluation weighted by the
+    run's length.
+
+    pop_model: one PopModel or a list -- with several, one host thread per model runs its chains, each chain into
+        its own summary, and the summaries are merged in chain order (the result does not depend on the
+        interleaving).
+
+    locinfo: observations for the observation-level predictive (every row: the rates of its run's evaluation with
+        its own nuisance parameters).
+
+    evaluate(theta) -> expected observations or None: no device, no summary.
+
+    quantiles: levels in (0, 1]; each chain then also fills a SpreadHistogram (bins / edges as bin_edges) with the
+        same weights, merged in chain order into `histogram`.
+
+    arrival: thresholds (1..4, finite, > 0, strictly increasing); each chain then also fills ArrivalMaps over the
+        summary's days (strictly increasing, at most 32) with the same weights, merged in chain order into
+        `arrival`; arrival_levels: the levels of its saved arrival-day quantile maps.
+
+    emergence: dict(collection_day=C, obs_days=None) (emergence_plan); exposure: model days [D1, D2, ...]
+        (exposure_plan); each chain then also applies that Projection after every evaluation and adds its outputs,
+        with the same weights, to a SpreadSummary.for_projection (same thresholds) and, with quantiles, a
+        SpreadHistogram.for_projection (same edges), merged in chain order into `emergence` / `exposure`
+        (ProjectedMaps).
+
+    sites: dict(sites=[(east_m, north_m, amount[, lag_days]), ...], days=None) (sites_plan); each chain then also
+        builds one ReleaseSites (the models of the later release days, lagged_models, once per model), evaluates
+        those models with every member, applies the plan and adds its outputs, with the same weights, to a
+        SpreadSummary.for_projection (same thresholds), with quantiles a SpreadHistogram.for_projection (same
+        edges) and with arrival an ArrivalMaps.for_projection (same thresholds), merged in chain order into
+        `sites` (ProjectedMaps with `plan` and `arrival`).
+
+    sensitivity: True (all 15 model parameters) or names from mcmc.MODEL_BLOCK (check_sens_params); each chain
+        then also fills a SensitivityMaps over the summary's days with every run's theta and length, after the
+        summary, merged in chain order into `sensitivity`, and every projection and plan asked for gets a
+        SensitivityMaps.for_projection of its own, fed after its summary.
+
     compare: dict(sites=[...]) (contrast_plan), a second release plan B on the output days of sites= (plan A,
-    required); each chain then also builds a ReleaseSites for B and one PlanContrast(A, B, thresholds) -- the
-    thresholds then have to be finite, > 0 and strictly increasing -- the models of the later release days built
-    once per model for the union of both plans' lags and each evaluated once per member; after A's applies and
-    adds B is applied and the contrast added with the same weight, merged in chain order into `contrast`
-    (`compare_plan`: plan B).  mc_error: True (20 batches per chain) or dict(batches=B), B even and >= 4
-    (mc_batch_plan; not with evaluate=, and every chain needs at least B rows after burn and thin); each chain
-    then also fills two MonteCarloError sequences beside its summary, same days and thresholds (finite, strictly
-    increasing), the rows before the chain's half into the first and the rest into the second, a run that
-    straddles the half split there -- and two per projection and plan asked for; at the end every sequence is
-    finished, the split R-hat maps taken over all 2 x chains sequences and the sequences merged in chain order
-    into `mc_error` (`mc_error.rhat`: the R-hat maps; None with more than 8 chains or a sequence left with fewer
-    than two batches by failed members).  The contrast gets none.  peak: thresholds [t_0, ...] (0..4, finite,
-    > 0, strictly increasing) or dict(thresholds=[...], levels=(0.05, 0.5, 0.95)) (check_peak; not with
-    evaluate=); each chain then also fills a PeakPosterior over the summary's days (strictly increasing, at most
-    32) with the same weights -- per member the PeakMaps add, then a SpreadSummary.for_projection of the peak
-    field (the summary's thresholds) and with quantiles a SpreadHistogram.for_projection of it (same edges) --
-    merged in chain order into `peak`; with sites= the plan gets a PeakPosterior of its own outputs, fed after
-    the plan's apply (`sites.peak`).  Emergence and exposure get none here (PeakMaps.for_projection takes them);
-    sensitivity, contrast and Monte Carlo error of the peak maps are not computed.  excursion: thresholds
-    [t_0, ...] (1..4, finite, > 0, strictly increasing) or dict(thresholds=[...], levels=(0.9, 0.95)), the levels
-    in (0.5, 1] (check_excursion; not with evaluate=); each chain then also fills one ExcursionMaps over the
-    summary's days (strictly increasing, at most 32), reserved to the chain's number of runs and fed the same
-    weights after the summary, merged in chain order into `excursion` (`excursion_levels`: the levels of its saved
-    regions and areas); with sites= the plan gets an ExcursionMaps.for_projection of its own outputs
-    (`sites.excursion`).  Emergence and exposure get none here (ExcursionMaps.for_projection takes them);
-    sensitivity, contrast, Monte Carlo error and quantiles of the excursion maps are not computed.  reweight:
-    {name: spec, ...} with 1..4 names (check_reweight; not with evaluate=), the maps under new observations by
-    importance reweighting of the members, without a new chain.  spec = dict(probes=[(east_m, north_m, day, kind,
-    rate[, n]), ...]) (check_probes): the member's log-weight is the log-likelihood of the probes under its own
-    fields (probes_loglik on one gather of all probes of all scenarios per member); or
-    dict(log_weights=[one 1-D array per chain]), one entry per row after burn and thin: a run's log-weight is the
-    log of its rows' mean weight (run_log_weight).  Bad cells, days, kinds, rates and lengths fail before any
-    evaluation.  Each chain then also fills one ReweightedSummary over the summary's days (at most 32) and
-    thresholds (finite, > 0, strictly increasing), fed right after the summary with the run's length, merged in
-    chain order into `reweight`; every emergence=, exposure= and sites= asked for gets a
-    ReweightedSummary.for_projection of its own, fed after its summary.  Histogram, arrival, peak, excursion,
-    contrast and Monte Carlo error get none.  `reweight_info` carries per scenario the diagnostics of the row
-    weights (reweight_diagnostics); a UserWarning where ess < min_ess (reweight['options'] = dict(min_ess=50)) --
-    importance reweighting degrades as the new data disagree with the posterior -- and a ValueError naming a
-    scenario that is left without weight.  Without reweight= no call is added and `reweight` is None.  catch:
-    dict(traps=[(day, rate[, n]), ...], levels=(0.5, 0.95), emergence=[(obs_day, rate[, n]), ...]) (check_catch;
-    not with evaluate=; bad arguments fail before any evaluation), the probability that a trap of effort `rate` on
-    model day `day` catches at least n, per cell, under the package's Poisson observation model.  Each chain then
-    also applies one CatchFields over the traps right after the summary's add and adds its fields, with the run's
-    length, to a SpreadSummary.for_projection whose thresholds are the levels; with mc_error= to two
-    MonteCarloError.for_projection of its own, with reweight= to a ReweightedSummary.for_projection fed the same
-    log-weights; merged in chain order into `catch` (a CatchPosterior).  The `emergence` key needs emergence= and
-    puts a CatchPosterior over the emergence projection's outputs, the trap's day one of its labels, into
-    `emergence.catch`: sentinel fields measure emergence, so this is the forward map of the data the chain was
-    fitted to.  With sites= the plan gets one of its own over the same traps, whose days have to be output days
-    of the plan, in `sites.catch`.  Histogram, arrival, peak, excursion, sensitivity and contrast of the catch
-    fields are not computed.  Without catch= no call is added and `catch` is None.  information:
-    dict(traps=[(day, rate[, ymax]), ...]) (check_information; not with evaluate=; bad arguments fail before any
-    evaluation): per described trap -- effort `rate` on model day `day`, its count observed as 0, 1, .., ymax and
-    ">= ymax + 1" -- and cell the mutual information in nats between the count and the identity of the member:
-    where a reading would change the posterior, and where it would tell nothing.  Each chain then also applies one
-    InformationFields right after the summary's add and adds its planes, with the run's length, to a
-    SpreadSummary.for_projection without thresholds; with reweight= to a ReweightedSummary.for_projection fed the
-    same log-weights (`information.gain(e, scenario=name)`: after that scenario's observations); merged in chain
-    order into `information` (an InformationPosterior).  With sites= the plan gets one of its own over the same
-    traps, whose days have to be output days of the plan, in `sites.information`.  A UserWarning where a trap's
-    largest gain exceeds half of `cap`, the entropy of the member weights: the map is then bounded by the
-    ensemble, not by the trap.  Histogram, arrival, peak, excursion, contrast, sensitivity and Monte Carlo error of
-    these maps are not computed.  Without information= no call is added and `information` is None.  core_range:
-    mass fractions [p_0, ...] (1..4, each in (0, 1), strictly increasing) or dict(fractions=[...], levels=(0.5, 0.9)),
-    the consensus levels in (0, 1] (check_core_range; not with evaluate=; bad arguments fail before any evaluation):
-    per member its own highest-density regions, 0.5 the core and 0.95 the range.  Each chain then also fills one
-    RangeMaps over the summary's days (strictly increasing, at most 32), reserved to the chain's number of runs and
-    fed the run's weight right after the summary's add, merged in chain order into `core_range`
-    (`core_range_levels`: the consensus levels of its saved regions); with sites= the plan gets a
-    RangeMaps.for_projection of its own outputs (`sites.core_range`).  Emergence and exposure get none here
-    (RangeMaps.for_projection takes them); sensitivity, contrast, Monte Carlo error and reweighting of these maps are
-    not computed.  Without core_range= no call is added and `core_range` is None.'''
+        required); each chain then also builds a ReleaseSites for B and one PlanContrast(A, B, thresholds) -- the
+        thresholds then have to be finite, > 0 and strictly increasing -- the models of the later release days
+        built once per model for the union of both plans' lags and each evaluated once per member; after A's
+        applies and adds B is applied and the contrast added with the same weight, merged in chain order into
+        `contrast` (`compare_plan`: plan B).
+
+    mc_error: True (20 batches per chain) or dict(batches=B), B even and >= 4 (mc_batch_plan; not with evaluate=,
+        and every chain needs at least B rows after burn and thin); each chain then also fills two MonteCarloError
+        sequences beside its summary, same days and thresholds (finite, strictly increasing), the rows before the
+        chain's half into the first and the rest into the second, a run that straddles the half split there -- and
+        two per projection and plan asked for; at the end every sequence is finished, the split R-hat maps taken
+        over all 2 x chains sequences and the sequences merged in chain order into `mc_error` (`mc_error.rhat`:
+        the R-hat maps; None with more than 8 chains or a sequence left with fewer than two batches by failed
+        members). The contrast gets none.
+
+    peak: thresholds [t_0, ...] (0..4, finite, > 0, strictly increasing) or dict(thresholds=[...], levels=(0.05,
+        0.5, 0.95)) (check_peak; not with evaluate=); each chain then also fills a PeakPosterior over the
+        summary's days (strictly increasing, at most 32) with the same weights -- per member the PeakMaps add,
+        then a SpreadSummary.for_projection of the peak field (the summary's thresholds) and with quantiles a
+        SpreadHistogram.for_projection of it (same edges) -- merged in chain order into `peak`; with sites= the
+        plan gets a PeakPosterior of its own outputs, fed after the plan's apply (`sites.peak`). Emergence and
+        exposure get none here (PeakMaps.for_projection takes them); sensitivity, contrast and Monte Carlo error
+        of the peak maps are not computed.
+
+    excursion: thresholds [t_0, ...] (1..4, finite, > 0, strictly increasing) or dict(thresholds=[...],
+        levels=(0.9, 0.95)), the levels in (0.5, 1] (check_excursion; not with evaluate=); each chain then also
+        fills one ExcursionMaps over the summary's days (strictly increasing, at most 32), reserved to the chain's
+        number of runs and fed the same weights after the summary, merged in chain order into `excursion`
+        (`excursion_levels`: the levels of its saved regions and areas); with sites= the plan gets an
+        ExcursionMaps.for_projection of its own outputs (`sites.excursion`). Emergence and exposure get none here
+        (ExcursionMaps.for_projection takes them); sensitivity, contrast, Monte Carlo error and quantiles of the
+        excursion maps are not computed.
+
+    reweight: {name: spec, ...} with 1..4 names (check_reweight; not with evaluate=), the maps under new
+        observations by importance reweighting of the members, without a new chain. spec = dict(probes=[(east_m,
+        north_m, day, kind, rate[, n]), ...]) (check_probes): the member's log-weight is the log-likelihood of the
+        probes under its own fields (probes_loglik on one gather of all probes of all scenarios per member); or
+        dict(log_weights=[one 1-D array per chain]), one entry per row after burn and thin: a run's log-weight is
+        the log of its rows' mean weight (run_log_weight). Bad cells, days, kinds, rates and lengths fail before
+        any evaluation. Each chain then also fills one ReweightedSummary over the summary's days (at most 32) and
+        thresholds (finite, > 0, strictly increasing), fed right after the summary with the run's length, merged
+        in chain order into `reweight`; every emergence=, exposure= and sites= asked for gets a
+        ReweightedSummary.for_projection of its own, fed after its summary. Histogram, arrival, peak, excursion,
+        contrast and Monte Carlo error get none. `reweight_info` carries per scenario the diagnostics of the row
+        weights (reweight_diagnostics); a UserWarning where ess < min_ess (reweight['options'] = dict(min_ess=50))
+        -- importance reweighting degrades as the new data disagree with the posterior -- and a ValueError naming
+        a scenario that is left without weight. Without reweight= no call is added and `reweight` is None.
+
+    catch: dict(traps=[(day, rate[, n]), ...], levels=(0.5, 0.95), emergence=[(obs_day, rate[, n]), ...])
+        (check_catch; not with evaluate=; bad arguments fail before any evaluation), the probability that a trap
+        of effort `rate` on model day `day` catches at least n, per cell, under the package's Poisson observation
+        model. Each chain then also applies one CatchFields over the traps right after the summary's add and adds
+        its fields, with the run's length, to a SpreadSummary.for_projection whose thresholds are the levels; with
+        mc_error= to two MonteCarloError.for_projection of its own, with reweight= to a
+        ReweightedSummary.for_projection fed the same log-weights; merged in chain order into `catch` (a
+        CatchPosterior). The `emergence` key needs emergence= and puts a CatchPosterior over the emergence
+        projection's outputs, the trap's day one of its labels, into `emergence.catch`: sentinel fields measure
+        emergence, so this is the forward map of the data the chain was fitted to. With sites= the plan gets one
+        of its own over the same traps, whose days have to be output days of the plan, in `sites.catch`.
+        Histogram, arrival, peak, excursion, sensitivity and contrast of the catch fields are not computed.
+        Without catch= no call is added and `catch` is None.
+
+    information: dict(traps=[(day, rate[, ymax]), ...]) (check_information; not with evaluate=; bad arguments fail
+        before any evaluation): per described trap -- effort `rate` on model day `day`, its count observed as 0,
+        1, .., ymax and ">= ymax + 1" -- and cell the mutual information in nats between the count and the
+        identity of the member: where a reading would change the posterior, and where it would tell nothing. Each
+        chain then also applies one InformationFields right after the summary's add and adds its planes, with the
+        run's length, to a SpreadSummary.for_projection without thresholds; with reweight= to a
+        ReweightedSummary.for_projection fed the same log-weights (`information.gain(e, scenario=name)`: after
+        that scenario's observations); merged in chain order into `information` (an InformationPosterior). With
+        sites= the plan gets one of its own over the same traps, whose days have to be output days of the plan, in
+        `sites.information`. A UserWarning where a trap's largest gain exceeds half of `cap`, the entropy of the
+        member weights: the map is then bounded by the ensemble, not by the trap. Histogram, arrival, peak,
+        excursion, contrast, sensitivity and Monte Carlo error of these maps are not computed. Without
+        information= no call is added and `information` is None.
+
+    core_range: mass fractions [p_0, ...] (1..4, each in (0, 1), strictly increasing) or dict(fractions=[...],
+        levels=(0.5, 0.9)), the consensus levels in (0, 1] (check_core_range; not with evaluate=; bad arguments
+        fail before any evaluation): per member its own highest-density regions, 0.5 the core and 0.95 the range.
+        Each chain then also fills one RangeMaps over the summary's days (strictly increasing, at most 32),
+        reserved to the chain's number of runs and fed the run's weight right after the summary's add, merged in
+        chain order into `core_range` (`core_range_levels`: the consensus levels of its saved regions); with
+        sites= the plan gets a RangeMaps.for_projection of its own outputs (`sites.core_range`). Emergence and
+        exposure get none here (RangeMaps.for_projection takes them); sensitivity, contrast, Monte Carlo error and
+        reweighting of these maps are not computed. Without core_range= no call is added and `core_range` is None.'''
+    q = types.SimpleNamespace(**locals())
     t0 = time.perf_counter()
-    cr_frac = cr_levels = None
-    if core_range is not None and core_range is not False:   # bad core-range arguments fail before any evaluation
-        if evaluate is not None:
-            raise ValueError('core_range= needs the device: not with evaluate=')
-        cr_frac, cr_levels = check_core_range(core_range, days)
-    in_plan = None
-    if information is not None:       # bad information arguments fail before any evaluation
-        pm0 = (pop_model[0] if pop_model else None) if isinstance(pop_model, (list, tuple)) else pop_model
-        in_plan = check_information(information, None if pm0 is None else len(pm0.days), evaluate)
-    ct_plan = None
-    if catch is not None:             # bad catch arguments fail before any evaluation
-        pm0 = (pop_model[0] if pop_model else None) if isinstance(pop_model, (list, tuple)) else pop_model
-        ct_plan = check_catch(catch, None if pm0 is None else len(pm0.days), emergence, evaluate)
-    rw_plan = None
-    if reweight is not None:          # bad reweighting arguments fail before any evaluation
-        if evaluate is not None:
-            raise ValueError('reweight= needs the device: not with evaluate=')
-        pm0 = (pop_model[0] if pop_model else None) if isinstance(pop_model, (list, tuple)) else pop_model
-        rw_plan = check_reweight(reweight, None if pm0 is None else pm0.rad_dist,
-                                 None if pm0 is None else pm0.rad_res, None if pm0 is None else len(pm0.days))
-        check_peak_thresholds(thresholds)
-        nd = len(days) if days is not None else (len(pm0.days) if pm0 is not None else 1)
-        if not 1 <= nd <= MAX_REWEIGHT_SLOTS:
-            raise ValueError('reweight= takes 1..%d days, got %d' % (MAX_REWEIGHT_SLOTS, nd))
-    ex_thr = ex_levels = None
-    if excursion is not None and excursion is not False:     # bad excursion arguments fail before any evaluation
-        if evaluate is not None:
-            raise ValueError('excursion= needs the device: not with evaluate=')
-        ex_thr, ex_levels = check_excursion(excursion)
-        if days is not None:
-            check_arrival_days(days)
-    pk_thr = pk_levels = None
-    if peak is not None and peak is not False:               # bad peak arguments fail before any evaluation too
-        if evaluate is not None:
-            raise ValueError('peak= needs the device: not with evaluate=')
-        pk_thr, pk_levels = check_peak(peak)
-        if days is not None:
-            check_arrival_days(days)
-    mc_batches = None
-    if mc_error is not None and mc_error is not False:       # bad Monte Carlo error arguments fail first too
-        if evaluate is not None:
-            raise ValueError('mc_error= needs the device: not with evaluate=')
-        mc_batches = mc_error_plan(mc_error)
-        check_mc_thresholds(thresholds)
-    s_names = check_sens_params(sensitivity) if sensitivity is not None and sensitivity is not False else None
-    levels = (check_levels(quantiles) if quantiles is not None else []) or None
-    if levels:
-        bin_edges(bins, edges)        # a bad edge definition fails before any evaluation
-    a_thr = a_levels = None
-    if arrival is not None:           # bad arrival arguments fail before any evaluation too
-        a_thr = check_arrival_thresholds(arrival)
-        a_levels = check_levels(arrival_levels)
-        if days is not None:
-            check_arrival_days(days)
-    wanted = [(name, arg, plan) for name, arg, plan in (('emergence', emergence, emergence_plan),
-                                                        ('exposure', exposure, exposure_plan)) if arg is not None]
-    plans = [(name,) + plan(arg) for name, arg, plan in wanted]      # and bad projection arguments
-    site_plan = None
-    if sites is not None:             # and a bad release plan: its cells, days and lags against the model if there is one
-        pm0 = (pop_model[0] if pop_model else None) if isinstance(pop_model, (list, tuple)) else pop_model
-        site_plan = sites_plan(sites, pm0)
-        if pm0 is None:
-            site_plan = None
-        else:
-            for what, tp in (('catch', ct_plan), ('information', in_plan)):
-                off = [t for t in tp['traps'] if t[0] not in site_plan[1]] if tp is not None else []
-                if off:
-                    raise ValueError('%s: trap %r is not on an output day of the release plan %r'
-                                     % (what, off[0], list(site_plan[1])))
-    cmp_plan = None
-    if compare is not None:           # and a bad plan B, or one without a plan A to compare with
-        pm0 = (pop_model[0] if pop_model else None) if isinstance(pop_model, (list, tuple)) else pop_model
-        cmp_plan = contrast_plan(compare, sites, pm0)
-        check_contrast_thresholds(thresholds)
-        if pm0 is None:
-            cmp_plan = None
-    if isinstance(chains, (str, os.PathLike)) or (isinstance(chains, tuple) and len(chains) == 2
-                                                   and not isinstance(chains[0], (str, os.PathLike, tuple))):
-        chains = [chains]
-    loaded = [load_chain(c) for c in chains]
-    want_obs = locinfo is not None
-    model_want = model_names()
-    obs_want = nuisance_names()
-    if want_obs:
-        obs_want = obs_want + ['sent_obs_probs_{}'.format(k) for k in locinfo.sent_ids]
-    prepared = []
-    for trace, names, src in loaded:
-        mcols = _columns(names, model_want)
-        ocols = _columns(names, obs_want) if want_obs else None
-        rows, rl = runs(trace, mcols, burn, thin)
-        prepared.append((rows, rl, mcols, ocols, src))
-    if rw_plan is not None:           # row log-weights that do not fit the chains
-        check_reweight_rows(rw_plan, [len(p[0]) for p in prepared])
-    mc_b = mc_halves = None
-    if mc_batches:                    # a chain shorter than the batches asked for
-        mc_b, mc_halves = mc_batch_plan([len(p[0]) for p in prepared], mc_batches)
-    pms = list(pop_model) if isinstance(pop_model, (list, tuple)) else [pop_model]
-    if evaluate is None and (not pms or pms[0] is None):
-        raise ValueError('a PopModel is needed without evaluate=')
-    if (a_thr or pk_thr is not None or ex_thr or cr_frac) and evaluate is None and days is None:
-        check_arrival_days(range(len(pms[0].days)))
-    if evaluate is None:              # as do projections past the model's days
-        plans = [(name,) + plan(arg, len(pms[0].days)) for name, arg, plan in wanted]
+    _check_request(q)                 # bad arguments fail before any evaluation
+    prepared, pms = q.prepared, q.pms
     nch = len(prepared)
-    summaries = [None] * nch
-    histograms = [None] * nch
-    arrivals = [None] * nch
-    senses = [None] * nch
-    peaks = [None] * nch                       # per chain its PeakPosterior
-    excurs = [None] * nch                      # per chain its ExcursionMaps
-    ranges = [None] * nch                      # per chain its RangeMaps
-    mcs = [None] * nch                         # per chain its two MonteCarloError sequences
-    rws = [None] * nch                         # per chain (ReweightedSummary, _ReweightFeed)
-    catches = [None] * nch                     # per chain its CatchPosterior over the day fields
-    infos = [None] * nch                       # per chain its InformationPosterior over the day fields
-    rw_names = rw_plan['names'] if rw_plan is not None else None
-    projected = [[] for _ in range(nch)]       # per chain (Projection, ProjectedMaps) of every plan
-    site_maps = [None] * nch                   # per chain (ReleaseSites, ProjectedMaps)
-    cmp_maps = [None] * nch                    # per chain (ReleaseSites of plan B, PlanContrast, the lagged models)
-    late = {}                                  # per model the models of the plan's later release days
+    chain_sets = [[] for _ in range(nch)]      # per chain its _FieldSets, in the order a member is fed to them
+    late = {}                                  # per model the models of the plans' later release days
     results = [None] * nch
     errs = []
 
@@ -4919,98 +5062,13 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
             pm = pms[p]
             for ci in range(p, nch, len(pms)):
                 rows, rl, mcols, _o, _s = prepared[ci]
-                summ = SpreadSummary(pm, days, thresholds) if evaluate is None else None
-                summaries[ci] = summ
-                hist = SpreadHistogram(pm, days, bins, edges) if evaluate is None and levels else None
-                histograms[ci] = hist
-                arr = ArrivalMaps(pm, a_thr, summ.days) if evaluate is None and a_thr else None
-                arrivals[ci] = arr
-                sens = SensitivityMaps(pm, s_names, summ.days) if evaluate is None and s_names else None
-                senses[ci] = sens
-                if pk_thr is not None:
-                    peaks[ci] = PeakPosterior(PeakMaps(pm, pk_thr, summ.days), thresholds, pk_levels,
-                                              bins if levels else None, edges if levels else None)
-                if ex_thr:
-                    excurs[ci] = ExcursionMaps(pm, ex_thr, summ.days)
-                    excurs[ci].reserve(len(rl))
-                if cr_frac:
-                    ranges[ci] = RangeMaps(pm, cr_frac, summ.days)
-                    ranges[ci].reserve(len(rl))
-                if mc_b:
-                    mcs[ci] = []
-                    for _half in range(2):
-                        mcs[ci].append(MonteCarloError(pm, mc_b, summ.days, thresholds))
-                if rw_plan is not None:
-                    rws[ci] = (ReweightedSummary(pm, rw_plan['names'], summ.days, thresholds),
-                               _ReweightFeed(rw_plan, ci))
-                if ct_plan is not None:
-                    catches[ci] = CatchPosterior(CatchFields(pm, ct_plan['traps']), ct_plan['levels'], mc_b, rw_names)
-                if in_plan is not None:
-                    infos[ci] = InformationPosterior(InformationFields(pm, in_plan['traps']), rw_names)
                 if evaluate is None:
-                    for _name, W, in_days, labels in plans:
-                        proj = Projection(pm, W, in_days)
-                        projected[ci].append((proj, None))
-                        maps = ProjectedMaps(W, in_days, labels, SpreadSummary.for_projection(proj, thresholds))
-                        projected[ci][-1] = (proj, maps)
-                        if levels:
-                            maps.histogram = SpreadHistogram.for_projection(proj, bins, edges)
-                        if s_names:
-                            maps.sensitivity = SensitivityMaps.for_projection(proj, s_names)
-                        if rw_plan is not None:
-                            maps.reweight = ReweightedSummary.for_projection(proj, rw_plan['names'], thresholds)
-                        if mc_b:
-                            maps.mc_error = []
-                            for _half in range(2):
-                                maps.mc_error.append(MonteCarloError.for_projection(proj, mc_b, thresholds))
-                        if _name == 'emergence' and ct_plan is not None and ct_plan['emergence']:
-                            maps.catch = CatchPosterior(CatchFields.for_projection(proj, ct_plan['emergence'], labels),
-                                                        ct_plan['levels'], mc_b, rw_names)
-                    if site_plan is not None:
-                        if p not in late:
-                            # once per model, for the union of both plans' release days
-                            late[p] = lagged_models(pm, sorted(set(site_plan[2]) | set(cmp_plan[2] if cmp_plan else ())))
-                        rs = ReleaseSites(pm, sites['sites'], site_plan[1], late[p])
-                        site_maps[ci] = (rs, None)
-                        maps = ProjectedMaps(None, None, list(rs.days), SpreadSummary.for_projection(rs, thresholds),
-                                             plan=rs.describe())
-                        site_maps[ci] = (rs, maps)
-                        if levels:
-                            maps.histogram = SpreadHistogram.for_projection(rs, bins, edges)
-                        if a_thr:
-                            maps.arrival = ArrivalMaps.for_projection(rs, a_thr)
-                        if s_names:
-                            maps.sensitivity = SensitivityMaps.for_projection(rs, s_names)
-                        if rw_plan is not None:
-                            maps.reweight = ReweightedSummary.for_projection(rs, rw_plan['names'], thresholds)
-                        if pk_thr is not None:
-                            maps.peak = PeakPosterior(PeakMaps.for_projection(rs, pk_thr), thresholds, pk_levels,
-                                                      bins if levels else None, edges if levels else None)
-                        if ex_thr:
-                            maps.excursion = ExcursionMaps.for_projection(rs, ex_thr)
-                            maps.excursion.reserve(len(rl))
-                        if cr_frac:
-                            maps.core_range = RangeMaps.for_projection(rs, cr_frac)
-                            maps.core_range.reserve(len(rl))
-                        if mc_b:
-                            maps.mc_error = []
-                            for _half in range(2):
-                                maps.mc_error.append(MonteCarloError.for_projection(rs, mc_b, thresholds))
-                        if ct_plan is not None:
-                            maps.catch = CatchPosterior(CatchFields.for_projection(rs, ct_plan['traps']),
-                                                        ct_plan['levels'], mc_b, rw_names)
-                        if in_plan is not None:
-                            maps.information = InformationPosterior(
-                                InformationFields.for_projection(rs, in_plan['traps']), rw_names)
-                        if cmp_plan is not None:
-                            rb = ReleaseSites(pm, compare['sites'], site_plan[1], late[p])
-                            cmp_maps[ci] = (rb, None, late[p])
-                            cmp_maps[ci] = (rb, PlanContrast(rs, rb, thresholds), late[p])
-                results[ci] = _evaluate_runs(pm, summ, rows, rl, mcols, evaluate, want_obs, locinfo, hist, arr,
-                                             projected[ci], site_maps[ci], sens, cmp_maps[ci],
-                                             (mcs[ci], mc_halves[ci][0]) if mc_b else None, peaks[ci],
-                                             excursion=excurs[ci], reweight=rws[ci], catch=catches[ci],
-                                             information=infos[ci], core_range=ranges[ci])
+                    if q.site_plan is not None and p not in late:
+                        # once per model, for the union of both plans' release days
+                        lags = set(q.site_plan[2]) | set(q.cmp_plan[2] if q.cmp_plan else ())
+                        late[p] = lagged_models(pm, sorted(lags))
+                    _build_sets(chain_sets[ci], q, pm, ci, len(rl), late.get(p))
+                results[ci] = _evaluate_runs(pm, rows, rl, mcols, evaluate, q.want_obs, locinfo, chain_sets[ci])
         except BaseException as e:       # re-raised in the caller's thread
             errs.append((p, e))
 
@@ -5025,157 +5083,26 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         pms = pms[:1]
         work(0)
     if errs:
-        for s in summaries + histograms + arrivals + senses + peaks + excurs + ranges + catches + infos + [pair[0] for pair in rws if pair] + [x for pair in mcs if pair for x in pair] + [x for pl in projected for pair in pl for x in pair] \
-                + [x for pair in site_maps if pair is not None for x in pair] \
-                + [x for tri in cmp_maps if tri is not None for x in tri[:2]] \
-                + [m for made in late.values() for m in made.values()]:
-            if s is not None:
-                s.close()
+        for fs in [fs for sets in chain_sets for fs in sets]:
+            fs.close()
+    else:                                # per source the chains' sets, merged in chain order into the first chain's
+        merged = {sets[0]._name: _merge_chains(sets) for sets in zip(*chain_sets)}
+    for sets in chain_sets:              # the accumulators hold what they need: the output fields go, and the plans
+        for fs in sets:                  # with the models of their later release days
+            fs.release()
+    for made in late.values():
+        for m in made.values():
+            m.close()
+    if errs:
         raise errs[0][1]
-    summary = None
-    histogram = None
-    arrival_maps = None
-    sens_maps = None
-    peak_maps = None
-    excur_maps = None
-    range_maps = None
-    if evaluate is None:
-        summary = summaries[0]
-        for s in summaries[1:]:
-            summary.merge(s)
-            s.close()
-        if levels:
-            histogram = histograms[0]
-            for h in histograms[1:]:
-                histogram.merge(h)
-                h.close()
-        if a_thr:
-            arrival_maps = arrivals[0]
-            for a in arrivals[1:]:
-                arrival_maps.merge(a)
-                a.close()
-        if s_names:
-            sens_maps = senses[0]
-            for a in senses[1:]:
-                sens_maps.merge(a)
-                a.close()
-        if pk_thr is not None:
-            peak_maps = peaks[0]
-            for a in peaks[1:]:
-                peak_maps.merge(a)
-                a.close()
-        if ex_thr:
-            excur_maps = excurs[0]
-            for a in excurs[1:]:
-                excur_maps.merge(a)
-                a.close()
-        if cr_frac:
-            range_maps = ranges[0]
-            for a in ranges[1:]:
-                range_maps.merge(a)
-                a.close()
-    rw_maps = rw_info = None
-    if rw_plan is not None:
-        rw_maps = rws[0][0]
-        for a, _feed in rws[1:]:
-            rw_maps.merge(a)
-            a.close()
-
-    def merge_catch(cps):
-        '''the chains' CatchPosteriors merged in chain order into the first: the Monte Carlo error sequences
-        pooled, the fields -- the accumulators hold what they need -- and the other chains' accumulators closed'''
-        if not cps or cps[0] is None:
-            return None
-        first = cps[0]
-        first.given = ct_plan['given']
-        if mc_b:
-            pooled = pool_mc_error([c.mc_error for c in cps])
-            for c in cps:
-                c.mc_error = None
-            first.mc_error = pooled
-        for c in cps:
-            c.fields.close()
-        for c in cps[1:]:
-            first.merge(c)
-            c.close()
-        return first
-    catch_maps = merge_catch(catches) if ct_plan is not None else None
-
-    def merge_info(ips):
-        '''the chains' InformationPosteriors merged in chain order into the first, whose fields stay open -- they
-        hold the finished maps --; the other chains' fields and accumulators closed'''
-        if not ips or ips[0] is None:
-            return None
-        first = ips[0]
-        first.given = in_plan['given']
-        for c in ips[1:]:
-            first.merge(c)
-            c.close()
-        return first
-    info_maps = merge_info(infos) if in_plan is not None else None
-    mc_pooled = mc_desc = None
-    if mc_b:
-        mc_pooled = pool_mc_error(mcs)
-        mc_desc = {'batches': mc_batches, 'batch_weight': mc_b, 'sequences': 2 * nch}
-    merged = {}
-    for k, plan in enumerate(plans if evaluate is None else []):
-        if mc_b:                         # before the merge closes the other chains' maps
-            pooled = pool_mc_error([pl[k][1].mc_error for pl in projected])
-            for pl in projected:
-                pl[k][1].mc_error = None
-            projected[0][k][1].mc_error = pooled
-        merged[plan[0]] = projected[0][k][1]
-        if projected[0][k][1].catch is not None:      # before the projections close: it reads their fields
-            cps = [pl[k][1].catch for pl in projected]
-            for pl in projected[1:]:
-                pl[k][1].catch = None
-            merged[plan[0]].catch = merge_catch(cps)
-        for pl in projected[1:]:
-            merged[plan[0]].merge(pl[k][1])
-            pl[k][1].close()
-    for pl in projected:                 # the accumulators hold what they need: the output fields go
-        for proj, _maps in pl:
-            proj.close()
-    merged_sites = None
-    contrast = compare_desc = None
-    if evaluate is None and site_plan is not None:
-        if mc_b:
-            pooled = pool_mc_error([maps.mc_error for _rs, maps in site_maps])
-            for _rs, maps in site_maps:
-                maps.mc_error = None
-            site_maps[0][1].mc_error = pooled
-        merged_sites = site_maps[0][1]
-        if merged_sites.catch is not None:
-            cps = [maps.catch for _rs, maps in site_maps]
-            for _rs, maps in site_maps[1:]:
-                maps.catch = None
-            merged_sites.catch = merge_catch(cps)
-        if merged_sites.information is not None:
-            ips = [maps.information for _rs, maps in site_maps]
-            for _rs, maps in site_maps[1:]:
-                maps.information = None
-            merged_sites.information = merge_info(ips)
-        for _rs, maps in site_maps[1:]:
-            merged_sites.merge(maps)
-            maps.close()
-        if cmp_plan is not None:
-            contrast = cmp_maps[0][1]
-            compare_desc = cmp_maps[0][0].describe()
-            for _rb, x, _late in cmp_maps[1:]:
-                contrast.merge(x)
-                x.close()
-            for rb, _x, _late in cmp_maps:
-                rb.close()
-        for rs, _maps in site_maps:      # and the plans with the models of their later release days
-            rs.close()
-        for made in late.values():
-            for m in made.values():
-                m.close()
-    if rw_plan is not None:
+    day = merged.get('days', _FieldSet())
+    rw_info = None
+    if q.rw_plan is not None:
         import warnings
+        rw_plan, rw_maps = q.rw_plan, day.reweight
         diag = {}
         for j, name in enumerate(rw_plan['names']):
-            d = reweight_diagnostics([v for _a, feed in rws for v in feed.rows[j]])
+            d = reweight_diagnostics([v for sets in chain_sets for v in sets[0]._rw_feed.rows[j]])
             d.update({'members': rw_maps.members(name), 'skipped': rw_maps.skipped(name),
                       'log_total_weight': rw_maps.log_total_weight(name)})
             diag[name] = d
@@ -5183,10 +5110,8 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                    'diagnostics': diag}
         empty = [n for n in rw_plan['names'] if diag[n]['members'] == 0]
         if empty:
-            for m in [summary, histogram, arrival_maps, sens_maps, peak_maps, excur_maps, range_maps, rw_maps, mc_pooled,
-                      contrast, catch_maps, info_maps] + list(merged.values()) + [merged_sites]:
-                if m is not None:
-                    m.close()
+            for fs in merged.values():
+                fs.close()
             raise ValueError('reweight: scenario %r is left without weight (W = 0): no member is compatible with it'
                              % empty[0])
         for n in rw_plan['names']:
@@ -5194,12 +5119,10 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                 warnings.warn('reweight: scenario %r has an effective sample size of %.3g rows (min_ess %g): the '
                               'new data disagree with the posterior, the reweighted maps rest on few members'
                               % (n, diag[n]['ess'], rw_plan['min_ess']), UserWarning)
-    evaluations = sum(len(p[1]) for p in prepared)
-    failed = sum(r[1] for r in results)
     run_rec = [(ci, first, length) for ci, p in enumerate(prepared)
                for (first, length), e in zip(p[1], results[ci][0]) if e is not None]
     observations = None
-    if want_obs:
+    if q.want_obs:
         rates = []
         for ci, (rows, rl, mcols, ocols, _s) in enumerate(prepared):
             for (first, length), exp in zip(rl, results[ci][0]):
@@ -5211,17 +5134,22 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         observations = observation_predictive(rates, locinfo, seed)
     prov = [{'source': p[4], 'rows': int(len(p[0])), 'runs': len(p[1]), 'burn': int(burn), 'thin': int(thin)}
             for p in prepared]
-    res = PredictiveResult(summary, int(sum(len(p[0]) for p in prepared)), evaluations, failed,
-                           time.perf_counter() - t0, run_rec, observations, prov,
-                           None if summary is None else summary.days, histogram, levels, arrival_maps,
-                           a_levels if a_thr else None, merged.get('emergence'), merged.get('exposure'),
-                           merged_sites, sens_maps, contrast, compare_desc, mc_pooled, mc_desc, peak_maps,
-                           excur_maps, ex_levels if ex_thr else None, rw_maps, rw_info, catch_maps, info_maps,
-                           range_maps, cr_levels if cr_frac else None)
-    if info_maps is not None:         # the stated convention: past cap / 2 the ensemble bounds the map
-        warn_information(info_maps)
-        if merged_sites is not None and merged_sites.information is not None:
-            warn_information(merged_sites.information, 'information (release plan)')
+    plan_b = merged.get('compare', _FieldSet())
+    res = PredictiveResult(
+        summary=day.summary, rows=int(sum(len(p[0]) for p in prepared)), evaluations=sum(len(p[1]) for p in prepared),
+        failed=sum(r[1] for r in results), seconds=time.perf_counter() - t0, runs=run_rec, observations=observations,
+        provenance=prov, days=None if day.summary is None else day.summary.days, histogram=day.histogram,
+        quantiles=q.levels, arrival=day.arrival, arrival_levels=q.a_levels if q.a_thr else None,
+        emergence=merged.get('emergence'), exposure=merged.get('exposure'), sites=merged.get('sites'),
+        sensitivity=day.sensitivity, contrast=plan_b.contrast, compare_plan=plan_b.plan, mc_error=day.mc_error,
+        mc_plan={'batches': q.mc_batches, 'batch_weight': q.mc_b, 'sequences': 2 * nch} if q.mc_b else None,
+        peak=day.peak, excursion=day.excursion, excursion_levels=q.ex_levels if q.ex_thr else None,
+        reweight=day.reweight, reweight_info=rw_info, catch=day.catch, information=day.information,
+        core_range=day.core_range, core_range_levels=q.cr_levels if q.cr_frac else None)
+    if day.information is not None:   # the stated convention: past cap / 2 the ensemble bounds the map
+        warn_information(day.information)
+        if 'sites' in merged:
+            warn_information(merged['sites'].information, 'information (release plan)')
     if cell_area is not None:
         res.cell_area = float(cell_area)
     return res
