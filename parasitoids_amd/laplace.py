@@ -32,6 +32,7 @@ import numpy as np
 from . import _lib as L
 from . import mcmc
 from . import predictive as PP
+from ._handle import _Handle
 
 NEGVAL = PP.NEGVAL
 NEG_INF = float('-inf')
@@ -71,16 +72,14 @@ HELD_STEP = 1e-3       # a step shrunk below HELD_STEP * prior_eps holds the par
 
 
 # ------------------------------------------------------------------ the device accumulator
-class LinearisedSpread():
+class LinearisedSpread(_Handle):
     '''Delta-method spread of `pop_model`'s days around one evaluation (ps_linspread_*).  days: model
     days (0 = release day) to keep, default all; nparam: sensitivities kept (<= 16); thresholds: up to 4
     population densities whose exceedance probability under the normal approximation is kept; names:
     optional parameter names for `sensitivity`.'''
+    _prefix, _noun, _prof_pairs = 'ps_linspread', 'spread', 2
 
     def __init__(self, pop_model, days=None, nparam=len(FREE_MODEL), thresholds=(), names=None):
-        self._lib = L.load()
-        self._h = L._VP()
-        self.pm = pop_model
         self.days = list(range(len(pop_model.days)) if days is None else days)
         if not self.days or min(self.days) < 0:
             raise ValueError('days must be a non-empty list of model days >= 0')
@@ -88,67 +87,43 @@ class LinearisedSpread():
         self.names = list(FREE_MODEL_NAMES if names is None and self.nparam == len(FREE_MODEL) else
                           (names or range(self.nparam)))
         self.thresholds = [float(t) for t in thresholds]
-        self.N = 2 * int(pop_model.rad_res) + 1
-        self.device = L.default_device() if pop_model.device is None else int(pop_model.device)
+        self._attach(pop_model)
         thr = L.f64(self.thresholds if self.thresholds else [0.0])
-        L.check(self._lib.ps_linspread_create(self.device, self.N, len(self.days), self.nparam,
-                                              len(self.thresholds), L.p_f64(thr), C.byref(self._h)))
-        self._kind = L.i32([L.REC_STATE if d == 0 else L.REC_CHAIN for d in self.days])
-        self._idx = L.i32([0 if d == 0 else d - 1 for d in self.days])
-        self._delta = L.i32([0 if d == 0 else 1 for d in self.days])
-        self._slot = {d: i for i, d in enumerate(self.days)}
-        self._n = len(self.days)
-
-    def _slots(self):
-        pm = self.pm
-        nd = getattr(pm, '_nd', 0)
-        if pm.solver is None or max(self.days) >= nd:
-            raise ValueError('the last evaluation has %d days; the spread needs day %d' % (nd, max(self.days)))
-        r = float(pm.r_number)
-        stat = L.f64([1.0 if d == 0 else r for d in self.days])
-        post = L.f64([r if d == 0 else 1.0 for d in self.days])
-        return (pm.solver._h, self._n, L.p_i32(self._kind), L.p_i32(self._idx), L.p_f64(stat), L.p_f64(post),
-                L.p_i32(self._delta), NEGVAL)
+        self._create(len(self.days), self.nparam, len(self.thresholds), L.p_f64(thr))
+        self._set_source(None, self.days)
 
     def set_center(self):
         '''centre = the last evaluation's days (enqueued on the solver's stream)'''
-        a = self._slots()
-        L.check(self._lib.ps_linspread_set_center(self._h, *a))
+        self._from_model('set_center')
 
     def add(self, param, coef):
         '''J[param] += coef * the last evaluation's days (enqueued on the solver's stream)'''
-        s, n, kind, idx, stat, post, delta, negval = self._slots()
-        L.check(self._lib.ps_linspread_add(self._h, s, int(param), float(coef), n, kind, idx, stat, post, delta,
-                                           negval))
+        self._from_model('add', head=(int(param), float(coef)))
 
     def finalize(self, F):
         '''Sigma = F F' (F: nparam x rank): per cell variance and exceedances'''
         F = L.f64(np.atleast_2d(F))
         if F.ndim != 2 or F.shape[0] != self.nparam:
             raise ValueError('F must be %d x rank, got %s' % (self.nparam, F.shape))
-        L.check(self._lib.ps_linspread_finalize(self._h, self.nparam, F.shape[1], L.p_f64(F)))
+        self._call('finalize', self.nparam, F.shape[1], L.p_f64(F))
 
     def reset(self):
-        L.check(self._lib.ps_linspread_reset(self._h))
+        self._call('reset')
 
     def info(self):
         '''(centre set, finalized, adds per parameter)'''
         c, f = C.c_int32(), C.c_int32()
         adds = np.zeros(self.nparam, dtype=np.int64)
-        L.check(self._lib.ps_linspread_info(self._h, C.byref(c), C.byref(f), L.p_i64(adds)))
+        self._call('info', C.byref(c), C.byref(f), L.p_i64(adds))
         return bool(c.value), bool(f.value), adds
 
     def _fetch(self, day, what):
-        if day not in self._slot:
-            raise ValueError('day %r is not in the spread %s' % (day, self.days))
-        out = np.empty((self.N, self.N), dtype=np.float64)
-        L.check(self._lib.ps_linspread_fetch(self._h, self._slot[day], int(what), L.p_f64(out)))
-        return out
+        return self.fetch_slot(self._slot_of(day), what)
 
     def fetch_slot(self, slot, what):
         '''raw access by slot index (0 centre, 1 variance, 2 + k exceedance, 16 + i sensitivity)'''
         out = np.empty((self.N, self.N), dtype=np.float64)
-        L.check(self._lib.ps_linspread_fetch(self._h, int(slot), int(what), L.p_f64(out)))
+        self._call('fetch', int(slot), int(what), L.p_f64(out))
         return out
 
     def mean(self, day):
@@ -175,28 +150,7 @@ class LinearisedSpread():
 
     def profile(self, enable=None):
         '''HIP-event time of the add and finalize launches; enable switches it'''
-        am, an, fm, fn = C.c_double(), C.c_int64(), C.c_double(), C.c_int64()
-        L.check(self._lib.ps_linspread_prof(self._h, -1 if enable is None else int(bool(enable)), C.byref(am),
-                                            C.byref(an), C.byref(fm), C.byref(fn)))
-        return {'add_ms': am.value, 'add_launches': an.value, 'finalize_ms': fm.value,
-                'finalize_launches': fn.value}
-
-    def close(self):
-        if self._h:
-            self._lib.ps_linspread_destroy(self._h)
-            self._h = L._VP()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return dict(zip(('add_ms', 'add_launches', 'finalize_ms', 'finalize_launches'), self._profile(enable)))
 
 
 # ------------------------------------------------------------------ the objective

@@ -63,8 +63,8 @@ import numpy as np
 from . import Bayes_funcs as BF
 from . import _lib as L
 from . import mcmc
+from ._handle import NEGVAL, _Accumulator, _Handle, _check_evaluated, _day_scales, _day_slots
 
-NEGVAL = 1e-8          # r_small_vals threshold of the daily solutions (CalcSol.py:126-132)
 DEFAULT_BINS = (1e-8, 1e6, 16)   # NEGVAL .. above any r_number, 16 bins per decade: 225 edges
 MAX_EDGES = 1024
 MAX_ARRIVAL_SLOTS = 32     # ps_arrival: the day slots of one launch's descriptors
@@ -76,37 +76,22 @@ MAX_SITE_GROUPS = 8
 MAX_SITE_OUT = 32
 
 
-def _day_slots(days):
-    '''record (kind, idx, use_delta) of every model day: day 0 the state, day d chain record d - 1'''
-    kind = L.i32([L.REC_STATE if d == 0 else L.REC_CHAIN for d in days])
-    idx = L.i32([0 if d == 0 else d - 1 for d in days])
-    delta = L.i32([0 if d == 0 else 1 for d in days])
-    return kind, idx, delta
+def _model_days(pop_model, days):
+    '''the model days an accumulator keeps: `days`, default all of the model's'''
+    days = list(range(len(pop_model.days)) if days is None else days)
+    if not days or min(days) < 0:
+        raise ValueError('days must be a non-empty list of model days >= 0')
+    return days
 
 
-def _day_scales(pm, days):
-    '''(stat_scale, post_scale) per day: what PopModel.population applies to each record'''
-    r = float(pm.r_number)
-    return L.f64([1.0 if d == 0 else r for d in days]), L.f64([r if d == 0 else 1.0 for d in days])
-
-
-def _check_evaluated(pm, days, what):
-    nd = getattr(pm, '_nd', 0)
-    if pm.solver is None or max(days) >= nd:
-        raise ValueError('the last evaluation has %d days; the %s needs day %d' % (nd, what, max(days)))
-
-
-class SpreadSummary():
+class SpreadSummary(_Accumulator):
     '''Weighted per-cell moments of `pop_model`'s days over the members added.  days: model days
     (0 = release day) to keep, default all; thresholds: up to 4 population densities whose
     exceedance probability is kept.'''
+    _prefix, _noun = 'ps_summary', 'summary'
 
     def __init__(self, pop_model, days=None, thresholds=()):
-        self._h = L._VP()
-        days = list(range(len(pop_model.days)) if days is None else days)
-        if not days or min(days) < 0:
-            raise ValueError('days must be a non-empty list of model days >= 0')
-        self._setup(pop_model, days, thresholds, None)
+        self._setup(pop_model, _model_days(pop_model, days), thresholds, None)
 
     @classmethod
     def for_projection(cls, projection, thresholds=()):
@@ -114,80 +99,38 @@ class SpreadSummary():
         the projection's last `apply()`, and the accessors take the output index where the day-based summary
         takes a day.'''
         self = cls.__new__(cls)
-        self._h = L._VP()
         self._setup(projection.pm, list(range(projection.nout)), thresholds, projection)
         return self
 
     def _setup(self, pop_model, days, thresholds, projection):
-        self._lib = L.load()
-        self.pm = pop_model
-        self.days = days
         self.thresholds = [float(t) for t in thresholds]
-        self.N = 2 * int(pop_model.rad_res) + 1
-        self.device = L.default_device() if pop_model.device is None else int(pop_model.device)
-        self._proj = projection
+        self._attach(pop_model)
         # slot of every day; of a projection the outputs that carry weight (the others are zero throughout)
-        keys = days if projection is None else projection.live
-        self._slot = {d: i for i, d in enumerate(keys)}
-        self._n = len(self._slot)
+        self._set_source(projection, days, projection and projection.live)
         thr = L.f64(self.thresholds if self.thresholds else [0.0])
-        L.check(self._lib.ps_summary_create(self.device, self.N, self._n, len(self.thresholds),
-                                            L.p_f64(thr), C.byref(self._h)))
-        if projection is None:
-            self._kind, self._idx, self._delta = _day_slots(self.days)
+        self._create(len(self._slot), len(self.thresholds), L.p_f64(thr))
 
     def add(self, weight=1):
         '''Accumulate the last evaluation of the model with integer weight >= 1 (enqueued on the
         solver's stream; no host synchronisation).  On a projection: its last apply, on the summary's stream.'''
-        w = int(weight)
-        if self._proj is not None:
-            if w < 1:
-                raise ValueError('weight must be a positive integer')
-            L.check(getattr(self._lib, 'ps_summary_add_' + self._proj.fields_kind)(self._h, self._proj._h, w))
-            return
-        pm = self.pm
-        _check_evaluated(pm, self.days, 'summary')
-        stat, post = _day_scales(pm, self.days)
-        if w < 1:
-            raise ValueError('weight must be a positive integer')
-        L.check(self._lib.ps_summary_add(self._h, pm.solver._h, self._n, L.p_i32(self._kind), L.p_i32(self._idx),
-                                         L.p_f64(stat), L.p_f64(post), L.p_i32(self._delta), NEGVAL, w))
+        self._add(weight)
 
     def merge(self, other):
         '''self += other (same device, domain, days and thresholds)'''
         if list(other.days) != self.days or other._slot != self._slot:
             raise ValueError('summaries over different days')
-        L.check(self._lib.ps_summary_merge(self._h, other._h))
-
-    def reset(self):
-        L.check(self._lib.ps_summary_reset(self._h))
-
-    def _info(self):
-        w, m = C.c_double(), C.c_int64()
-        L.check(self._lib.ps_summary_info(self._h, C.byref(w), C.byref(m)))
-        return w.value, m.value
-
-    @property
-    def total_weight(self):
-        return self._info()[0]
-
-    @property
-    def members(self):
-        return self._info()[1]
+        self._call('merge', other._h)
 
     def _fetch(self, day, what):
-        if day not in self._slot:
-            if self._proj is not None and day in self.days:      # an output without weight
-                return np.zeros((self.N, self.N), dtype=np.float64)
-            raise ValueError('day %r is not in the summary %s' % (day, self.days))
-        out = np.empty((self.N, self.N), dtype=np.float64)
-        L.check(self._lib.ps_summary_fetch(self._h, self._slot[day], int(what), L.p_f64(out)))
-        return out
+        slot = self._slot_of(day)
+        if slot is None:                                          # an output without weight
+            return np.zeros((self.N, self.N), dtype=np.float64)
+        return self.fetch_slot(slot, what)
 
     def fetch_slot(self, slot, what):
         '''raw access by slot index (0 mean, 1 variance, 2 + k exceedance)'''
         out = np.empty((self.N, self.N), dtype=np.float64)
-        L.check(self._lib.ps_summary_fetch(self._h, int(slot), int(what), L.p_f64(out)))
+        self._call('fetch', int(slot), int(what), L.p_f64(out))
         return out
 
     def mean(self, day):
@@ -207,27 +150,8 @@ class SpreadSummary():
 
     def profile(self, enable=None):
         '''HIP-event time of the accumulate launches: (total ms, launches); enable switches it'''
-        ms, n = C.c_double(), C.c_int64()
-        L.check(self._lib.ps_summary_prof(self._h, -1 if enable is None else int(bool(enable)), C.byref(ms),
-                                          C.byref(n)))
-        return ms.value, n.value
+        return self._profile(enable)
 
-    def close(self):
-        if self._h:
-            self._lib.ps_summary_destroy(self._h)
-            self._h = L._VP()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def bin_edges(bins=DEFAULT_BINS, edges=None):
@@ -273,17 +197,15 @@ def quantile_tag(p):
     return 'q' + ('%g' % (100 * p)).replace('.', 'p')
 
 
-class SpreadHistogram():
+class SpreadHistogram(_Accumulator):
     '''Weighted per-cell histograms of `pop_model`'s days over the members added, on fixed bin edges
     (`bin_edges(bins, edges)`).  days: model days to keep, default all.  The value of a cell is the one
     SpreadSummary adds; bin b = searchsorted(edges, v, side='right'), b = 0 .. B + 1.'''
+    _prefix, _noun, _prof_pairs = 'ps_hist', 'histogram', 2
+    _info_types = (C.c_double, C.c_int64, C.c_int32)
 
     def __init__(self, pop_model, days=None, bins=DEFAULT_BINS, edges=None):
-        self._h = L._VP()
-        days = list(range(len(pop_model.days)) if days is None else days)
-        if not days or min(days) < 0:
-            raise ValueError('days must be a non-empty list of model days >= 0')
-        self._setup(pop_model, days, bins, edges, None)
+        self._setup(pop_model, _model_days(pop_model, days), bins, edges, None)
 
     @classmethod
     def for_projection(cls, projection, bins=DEFAULT_BINS, edges=None):
@@ -291,28 +213,17 @@ class SpreadHistogram():
         of the projection's last `apply()`, and the accessors take the output index where the day-based
         histogram takes a day.'''
         self = cls.__new__(cls)
-        self._h = L._VP()
         self._setup(projection.pm, list(range(projection.nout)), bins, edges, projection)
         return self
 
     def _setup(self, pop_model, days, bins, edges, projection):
-        self._lib = L.load()
-        self.pm = pop_model
-        self.days = days
         self._edges = bin_edges(bins, edges)
         self.bins = None if edges is not None else tuple(float(b) for b in bins)
-        self.N = 2 * int(pop_model.rad_res) + 1
-        self.device = L.default_device() if pop_model.device is None else int(pop_model.device)
-        self._proj = projection
+        self._attach(pop_model)
         # slot of every day; of a projection the outputs that carry weight (the others are zero throughout)
-        keys = days if projection is None else projection.live
-        self._slot = {d: i for i, d in enumerate(keys)}
-        pitch = (self.N * self.N + 63) // 64 * 64
-        self.nbytes = len(self._slot) * pitch * (self._edges.size + 1) * 4   # count planes + range words
-        L.check(self._lib.ps_hist_create(self.device, self.N, len(self._slot), self._edges.size,
-                                         L.p_f64(self._edges), C.byref(self._h)))
-        if projection is None:
-            self._kind, self._idx, self._delta = _day_slots(self.days)
+        self._set_source(projection, days, projection and projection.live)
+        self.nbytes = len(self._slot) * self.pitch * (self._edges.size + 1) * 4   # count planes + range words
+        self._create(len(self._slot), self._edges.size, L.p_f64(self._edges))
 
     @property
     def edges(self):
@@ -321,50 +232,13 @@ class SpreadHistogram():
     def add(self, weight=1):
         '''Accumulate the last evaluation of the model with integer weight >= 1 (enqueued on the
         solver's stream; no host synchronisation).'''
-        w = int(weight)
-        if self._proj is not None:       # the projection's last apply, on the histogram's stream
-            if w < 1:
-                raise ValueError('weight must be a positive integer')
-            L.check(getattr(self._lib, 'ps_hist_add_' + self._proj.fields_kind)(self._h, self._proj._h, w))
-            return
-        pm = self.pm
-        _check_evaluated(pm, self.days, 'histogram')
-        stat, post = _day_scales(pm, self.days)
-        if w < 1:
-            raise ValueError('weight must be a positive integer')
-        L.check(self._lib.ps_hist_add(self._h, pm.solver._h, len(self.days), L.p_i32(self._kind),
-                                      L.p_i32(self._idx), L.p_f64(stat), L.p_f64(post), L.p_i32(self._delta),
-                                      NEGVAL, w))
+        self._add(weight)                # of a projection: its last apply, on the histogram's stream
 
     def merge(self, other):
         '''self += other (same device, domain, days and edges)'''
         if list(other.days) != self.days or other._slot != self._slot:
             raise ValueError('histograms over different days')
-        L.check(self._lib.ps_hist_merge(self._h, other._h))
-
-    def reset(self):
-        L.check(self._lib.ps_hist_reset(self._h))
-
-    def _info(self):
-        w, m, n = C.c_double(), C.c_int64(), C.c_int32()
-        L.check(self._lib.ps_hist_info(self._h, C.byref(w), C.byref(m), C.byref(n)))
-        return w.value, m.value
-
-    @property
-    def total_weight(self):
-        return self._info()[0]
-
-    @property
-    def members(self):
-        return self._info()[1]
-
-    def _slot_of(self, day):
-        '''the device slot of a day; None for a projection's output without weight (zero throughout)'''
-        if day not in self._slot:
-            if self._proj is not None and day in self.days:
-                return None
-            raise ValueError('day %r is not in the histogram %s' % (day, self.days))
-        return self._slot[day]
+        self._call('merge', other._h)
 
     def counts(self, day):
         '''[B + 2, N, N] uint32: the weight of every bin per cell, bin 0 = W - the others'''
@@ -375,7 +249,7 @@ class SpreadHistogram():
             out[0] = np.uint32(self.total_weight)
             return out
         for b in range(out.shape[0]):
-            L.check(self._lib.ps_hist_fetch_counts(self._h, s, b, out[b].ctypes.data_as(C.POINTER(C.c_uint32))))
+            self._call('fetch_counts', s, b, out[b].ctypes.data_as(C.POINTER(C.c_uint32)))
         return out
 
     def _quantile(self, day, p, value, lower, upper):
@@ -388,7 +262,7 @@ class SpreadHistogram():
                     a[:] = v
             return
         ptr = [None if a is None else L.p_f64(a) for a in (value, lower, upper)]
-        L.check(self._lib.ps_hist_quantile(self._h, s, float(p), *ptr))
+        self._call('quantile', s, float(p), *ptr)
 
     def quantile(self, day, p):
         '''N x N point map of the weighted lower quantile at level p (log-interpolated inside its bin)'''
@@ -413,33 +287,14 @@ class SpreadHistogram():
         if s is None:
             out[:] = 0.0
             return out
-        L.check(self._lib.ps_hist_exceed(self._h, s, int(k[0]), L.p_f64(out)))
+        self._call('exceed', s, int(k[0]), L.p_f64(out))
         return out
 
     def profile(self, enable=None):
         '''HIP-event time of the add and quantile launches: (add ms, adds, quantile ms, quantile
         launches); enable switches it'''
-        am, an, qm, qn = C.c_double(), C.c_int64(), C.c_double(), C.c_int64()
-        L.check(self._lib.ps_hist_prof(self._h, -1 if enable is None else int(bool(enable)), C.byref(am),
-                                       C.byref(an), C.byref(qm), C.byref(qn)))
-        return am.value, an.value, qm.value, qn.value
+        return self._profile(enable)
 
-    def close(self):
-        if self._h:
-            self._lib.ps_hist_destroy(self._h)
-            self._h = L._VP()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def check_arrival_thresholds(thresholds):
@@ -478,18 +333,27 @@ def weighted_lower_quantile(values, weights, p):
     return v[order][j]
 
 
-class ArrivalMaps():
+def _output_labels(projection):
+    '''the labels of the outputs of a fields source that carry weight, in ascending order: a plan's output days,
+    else the output indices; the one output of a PeakMaps, whose `days` are those it peaks over, is 0'''
+    if projection.fields_kind == 'peak':
+        labels = [0]
+    else:
+        labels = list(getattr(projection, 'days', range(projection.nout)))
+    return [labels[e] for e in projection.live]
+
+
+class ArrivalMaps(_Accumulator):
     '''When `pop_model`'s members reach each cell: for thresholds t_0 < ... < t_{K-1} (1..4, finite, > 0)
     and the model days `days` (strictly increasing, at most 32, default all), per threshold and cell the
     weighted distribution of the arrival day a_k = the first listed day whose value (the one SpreadSummary
     adds) is >= t_k, "never" if none; and per member the cells reached by each day.  Counts are integers:
     the order of adds and merges changes no bit.'''
+    _prefix, _noun, _prof_pairs = 'ps_arrival', 'arrival maps', 2
 
     def __init__(self, pop_model, thresholds, days=None):
-        self._h = L._VP()
         self.thresholds = check_arrival_thresholds(thresholds)
-        self.days = check_arrival_days(range(len(pop_model.days)) if days is None else days)
-        self._setup(pop_model, None)
+        self._setup(pop_model, None, check_arrival_days(range(len(pop_model.days)) if days is None else days))
 
     @classmethod
     def for_projection(cls, projection, thresholds):
@@ -498,92 +362,39 @@ class ArrivalMaps():
         `days` holds the output labels -- the plan's output days, or the projection's output indices -- and
         `reached_area` is the coverage curve of the plan.'''
         self = cls.__new__(cls)
-        self._h = L._VP()
         self.thresholds = check_arrival_thresholds(thresholds)
-        labels = list(getattr(projection, 'days', range(projection.nout)))
-        self.days = check_arrival_days([labels[e] for e in projection.live])
-        self._setup(projection.pm, projection)
+        self._setup(projection.pm, projection, check_arrival_days(_output_labels(projection)))
         return self
 
-    def _setup(self, pop_model, projection):
-        self._proj = projection
-        self._lib = L.load()
-        self.pm = pop_model
-        self.N = 2 * int(pop_model.rad_res) + 1
-        self.cell_area = (float(pop_model.rad_dist) / int(pop_model.rad_res)) ** 2
-        self.device = L.default_device() if pop_model.device is None else int(pop_model.device)
-        pitch = (self.N * self.N + 63) // 64 * 64
-        self.nbytes = len(self.thresholds) * len(self.days) * pitch * 4     # the count planes
-        thr = L.f64(self.thresholds)
-        L.check(self._lib.ps_arrival_create(self.device, self.N, len(self.days), len(self.thresholds), L.p_f64(thr),
-                                            C.byref(self._h)))
-        if projection is None:
-            self._kind, self._idx, self._delta = _day_slots(self.days)
-        self._slot = {d: i for i, d in enumerate(self.days)}
+    def _setup(self, pop_model, projection, days):
+        self._attach(pop_model)
+        self._set_source(projection, days)
+        self.nbytes = len(self.thresholds) * len(self.days) * self.pitch * 4     # the count planes
+        self._create(len(self.days), len(self.thresholds), L.p_f64(L.f64(self.thresholds)))
 
     def add(self, weight=1):
         '''Accumulate the last evaluation of the model with integer weight >= 1 (enqueued on the
         solver's stream; no host synchronisation).  On a projection or a plan: its last apply, on the
         handle's stream.'''
-        if self._proj is not None:
-            w = int(weight)
-            if w < 1:
-                raise ValueError('weight must be a positive integer')
-            L.check(getattr(self._lib, 'ps_arrival_add_' + self._proj.fields_kind)(self._h, self._proj._h, w))
-            return
-        pm = self.pm
-        _check_evaluated(pm, self.days, 'arrival maps')
-        stat, post = _day_scales(pm, self.days)
-        w = int(weight)
-        if w < 1:
-            raise ValueError('weight must be a positive integer')
-        L.check(self._lib.ps_arrival_add(self._h, pm.solver._h, len(self.days), L.p_i32(self._kind),
-                                         L.p_i32(self._idx), L.p_f64(stat), L.p_f64(post), L.p_i32(self._delta),
-                                         NEGVAL, w))
+        self._add(weight)
 
     def merge(self, other):
         '''self += other (same device, domain, days and thresholds); other's members follow self's'''
         if list(other.days) != self.days:
             raise ValueError('arrival maps over different days')
-        L.check(self._lib.ps_arrival_merge(self._h, other._h))
-
-    def reset(self):
-        L.check(self._lib.ps_arrival_reset(self._h))
-
-    def _info(self):
-        w, m = C.c_double(), C.c_int64()
-        L.check(self._lib.ps_arrival_info(self._h, C.byref(w), C.byref(m)))
-        return w.value, m.value
-
-    @property
-    def total_weight(self):
-        return self._info()[0]
-
-    @property
-    def members(self):
-        return self._info()[1]
-
-    def _k(self, k):
-        if not 0 <= int(k) < len(self.thresholds):
-            raise ValueError('threshold %r of %d' % (k, len(self.thresholds)))
-        return int(k)
-
-    def _slot_of(self, day):
-        if day not in self._slot:
-            raise ValueError('day %r is not in the arrival maps %s' % (day, self.days))
-        return self._slot[day]
+        self._call('merge', other._h)
 
     def counts(self, k, day):
         '''[N, N] uint32: the weight of the members whose arrival day at t_k is `day`; day=None: never'''
         s = len(self.days) if day is None else self._slot_of(day)
         out = np.empty((self.N, self.N), dtype=np.uint32)
-        L.check(self._lib.ps_arrival_fetch_counts(self._h, self._k(k), s, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        self._call('fetch_counts', self._k(k), s, out.ctypes.data_as(C.POINTER(C.c_uint32)))
         return out
 
     def prob_by(self, k, day):
         '''[N, N] float64: P(arrived at t_k by `day`) = C_k / W, C_k the weight of the arrivals up to `day`'''
         out = np.empty((self.N, self.N), dtype=np.float64)
-        L.check(self._lib.ps_arrival_prob(self._h, self._k(k), self._slot_of(day), L.p_f64(out)))
+        self._call('prob', self._k(k), self._slot_of(day), L.p_f64(out))
         return out
 
     def quantile(self, k, p):
@@ -592,7 +403,7 @@ class ArrivalMaps():
         if not 0.0 < float(p) <= 1.0:
             raise ValueError('quantile level %r is not in (0, 1]' % (p,))
         slot = np.empty((self.N, self.N), dtype=np.int32)
-        L.check(self._lib.ps_arrival_quantile(self._h, self._k(k), float(p), L.p_i32(slot)))
+        self._call('quantile', self._k(k), float(p), L.p_i32(slot))
         day = np.append(np.asarray(self.days, dtype=np.int32), np.int32(-1))
         return day[slot]          # slot -1 picks the appended -1
 
@@ -601,7 +412,7 @@ class ArrivalMaps():
         cells = np.empty((m, len(self.thresholds), len(self.days)), dtype=np.uint32)
         w = np.empty(m, dtype=np.uint32)
         u32 = C.POINTER(C.c_uint32)
-        L.check(self._lib.ps_arrival_fetch_reached(self._h, 0, m, cells.ctypes.data_as(u32), w.ctypes.data_as(u32)))
+        self._call('fetch_reached', 0, m, cells.ctypes.data_as(u32), w.ctypes.data_as(u32))
         return cells, w
 
     def reached(self, k):
@@ -632,27 +443,8 @@ class ArrivalMaps():
     def profile(self, enable=None):
         '''HIP-event time of the add and map launches: (add ms, adds, map ms, map launches); enable
         switches it'''
-        am, an, qm, qn = C.c_double(), C.c_int64(), C.c_double(), C.c_int64()
-        L.check(self._lib.ps_arrival_prof(self._h, -1 if enable is None else int(bool(enable)), C.byref(am),
-                                          C.byref(an), C.byref(qm), C.byref(qn)))
-        return am.value, an.value, qm.value, qn.value
+        return self._profile(enable)
 
-    def close(self):
-        if self._h:
-            self._lib.ps_arrival_destroy(self._h)
-            self._h = L._VP()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def check_peak_thresholds(thresholds):
@@ -678,7 +470,7 @@ def check_peak(peak):
     return check_peak_thresholds(peak), check_levels(levels)
 
 
-class PeakMaps():
+class PeakMaps(_Accumulator):
     '''The shape of each cell's curve over the listed days, per member and then over the members: the peak value
     m = max(+0.0, max_d v_d) (v_d the value SpreadSummary adds for day d), the peak day -- the first listed day
     that attains m, none where m == 0 -- and per threshold t_k (0..4, finite, > 0, strictly increasing) the number
@@ -688,15 +480,14 @@ class PeakMaps():
     E[max], its spread, P(peak >= t) and its quantiles come from the existing accumulators.  A duration counts
     listed days: it is a number of days only where they are consecutive model days (`consecutive`).  Counts are
     integers: the order of adds and merges changes no bit.'''
+    _prefix, _noun, _prof_pairs = 'ps_peak', 'peak maps', 2
     fields_kind = 'peak'         # the accumulators' entry points for the peak field: ps_*_add_peak
     nout = 1
     live = [0]
 
     def __init__(self, pop_model, thresholds=(), days=None):
-        self._h = L._VP()
         self.thresholds = check_peak_thresholds(thresholds)
-        self.days = check_arrival_days(range(len(pop_model.days)) if days is None else days)
-        self._setup(pop_model, None)
+        self._setup(pop_model, None, check_arrival_days(range(len(pop_model.days)) if days is None else days))
 
     @classmethod
     def for_projection(cls, projection, thresholds=()):
@@ -704,78 +495,29 @@ class PeakMaps():
         carry weight in ascending order: `add(weight)` accumulates the outputs of its last `apply()`.  `days`
         holds the output labels -- the plan's output days, or the projection's output indices.'''
         self = cls.__new__(cls)
-        self._h = L._VP()
         self.thresholds = check_peak_thresholds(thresholds)
-        labels = list(getattr(projection, 'days', range(projection.nout)))
-        self.days = check_arrival_days([labels[e] for e in projection.live])
-        self._setup(projection.pm, projection)
+        self._setup(projection.pm, projection, check_arrival_days(_output_labels(projection)))
         return self
 
-    def _setup(self, pop_model, projection):
-        self._proj = projection
-        self._lib = L.load()
-        self.pm = pop_model
-        self.N = 2 * int(pop_model.rad_res) + 1
-        self.device = L.default_device() if pop_model.device is None else int(pop_model.device)
+    def _setup(self, pop_model, projection, days):
+        self._attach(pop_model)
+        self._set_source(projection, days)
         self.consecutive = all(b == a + 1 for a, b in zip(self.days, self.days[1:]))
-        pitch = (self.N * self.N + 63) // 64 * 64
-        self.nbytes = (1 + len(self.thresholds)) * len(self.days) * pitch * 4 + 2 * pitch * 8   # counts + peak field + map scratch
+        self.nbytes = (1 + len(self.thresholds)) * len(self.days) * self.pitch * 4 + 2 * self.pitch * 8   # counts + peak field + map scratch
         thr = L.f64(self.thresholds if self.thresholds else [0.0])
-        L.check(self._lib.ps_peak_create(self.device, self.N, len(self.days), len(self.thresholds), L.p_f64(thr),
-                                         C.byref(self._h)))
-        if projection is None:
-            self._kind, self._idx, self._delta = _day_slots(self.days)
-        self._slot = {d: i for i, d in enumerate(self.days)}
+        self._create(len(self.days), len(self.thresholds), L.p_f64(thr))
 
     def add(self, weight=1):
         '''Accumulate the last evaluation of the model with integer weight >= 1 (enqueued on the
         solver's stream; no host synchronisation).  On a projection or a plan: its last apply, on the
         handle's stream.'''
-        w = int(weight)
-        if self._proj is not None:
-            if w < 1:
-                raise ValueError('weight must be a positive integer')
-            L.check(getattr(self._lib, 'ps_peak_add_' + self._proj.fields_kind)(self._h, self._proj._h, w))
-            return
-        pm = self.pm
-        _check_evaluated(pm, self.days, 'peak maps')
-        stat, post = _day_scales(pm, self.days)
-        if w < 1:
-            raise ValueError('weight must be a positive integer')
-        L.check(self._lib.ps_peak_add(self._h, pm.solver._h, len(self.days), L.p_i32(self._kind), L.p_i32(self._idx),
-                                      L.p_f64(stat), L.p_f64(post), L.p_i32(self._delta), NEGVAL, w))
+        self._add(weight)
 
     def merge(self, other):
         '''self += other (same device, domain, days and thresholds); the peak field stays self's'''
         if list(other.days) != self.days:
             raise ValueError('peak maps over different days')
-        L.check(self._lib.ps_peak_merge(self._h, other._h))
-
-    def reset(self):
-        L.check(self._lib.ps_peak_reset(self._h))
-
-    def _info(self):
-        w, m = C.c_double(), C.c_int64()
-        L.check(self._lib.ps_peak_info(self._h, C.byref(w), C.byref(m)))
-        return w.value, m.value
-
-    @property
-    def total_weight(self):
-        return self._info()[0]
-
-    @property
-    def members(self):
-        return self._info()[1]
-
-    def _k(self, k):
-        if not 0 <= int(k) < len(self.thresholds):
-            raise ValueError('threshold %r of %d' % (k, len(self.thresholds)))
-        return int(k)
-
-    def _slot_of(self, day):
-        if day not in self._slot:
-            raise ValueError('day %r is not in the peak maps %s' % (day, self.days))
-        return self._slot[day]
+        self._call('merge', other._h)
 
     def _n(self, n, lo):
         if not lo <= int(n) <= len(self.days):
@@ -785,19 +527,19 @@ class PeakMaps():
     def field(self):
         '''[N, N] float64: the peak field of the last member added'''
         out = np.empty((self.N, self.N), dtype=np.float64)
-        L.check(self._lib.ps_peak_fetch_field(self._h, L.p_f64(out)))
+        self._call('fetch_field', L.p_f64(out))
         return out
 
     def day_counts(self, day):
         '''[N, N] uint32: the weight of the members whose peak falls on `day`'''
         out = np.empty((self.N, self.N), dtype=np.uint32)
-        L.check(self._lib.ps_peak_fetch_day_counts(self._h, self._slot_of(day), out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        self._call('fetch_day_counts', self._slot_of(day), out.ctypes.data_as(C.POINTER(C.c_uint32)))
         return out
 
     def day_prob(self, day):
         '''[N, N] float64: P(peaked by `day`) = C / W, C the weight of the peaks up to `day`'''
         out = np.empty((self.N, self.N), dtype=np.float64)
-        L.check(self._lib.ps_peak_day_prob(self._h, self._slot_of(day), L.p_f64(out)))
+        self._call('day_prob', self._slot_of(day), L.p_f64(out))
         return out
 
     def day_quantile(self, p):
@@ -806,21 +548,20 @@ class PeakMaps():
         if not 0.0 < float(p) <= 1.0:
             raise ValueError('quantile level %r is not in (0, 1]' % (p,))
         slot = np.empty((self.N, self.N), dtype=np.int32)
-        L.check(self._lib.ps_peak_day_quantile(self._h, float(p), L.p_i32(slot)))
+        self._call('day_quantile', float(p), L.p_i32(slot))
         day = np.append(np.asarray(self.days, dtype=np.int32), np.int32(-1))
         return day[slot]          # slot -1 picks the appended -1
 
     def duration_counts(self, k, n):
         '''[N, N] uint32: the weight of the members with exactly n listed days at or above t_k, n in 0..len(days)'''
         out = np.empty((self.N, self.N), dtype=np.uint32)
-        L.check(self._lib.ps_peak_fetch_duration_counts(self._h, self._k(k), self._n(n, 0),
-                                                        out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        self._call('fetch_duration_counts', self._k(k), self._n(n, 0), out.ctypes.data_as(C.POINTER(C.c_uint32)))
         return out
 
     def duration_prob(self, k, n):
         '''[N, N] float64: P(at least n listed days at or above t_k), n in 1..len(days)'''
         out = np.empty((self.N, self.N), dtype=np.float64)
-        L.check(self._lib.ps_peak_duration_prob(self._h, self._k(k), self._n(n, 1), L.p_f64(out)))
+        self._call('duration_prob', self._k(k), self._n(n, 1), L.p_f64(out))
         return out
 
     def duration_quantile(self, k, p):
@@ -828,39 +569,20 @@ class PeakMaps():
         if not 0.0 < float(p) <= 1.0:
             raise ValueError('quantile level %r is not in (0, 1]' % (p,))
         out = np.empty((self.N, self.N), dtype=np.int32)
-        L.check(self._lib.ps_peak_duration_quantile(self._h, self._k(k), float(p), L.p_i32(out)))
+        self._call('duration_quantile', self._k(k), float(p), L.p_i32(out))
         return out
 
     def duration_mean(self, k):
         '''[N, N] float64: the posterior mean of the listed days at or above t_k'''
         out = np.empty((self.N, self.N), dtype=np.float64)
-        L.check(self._lib.ps_peak_duration_mean(self._h, self._k(k), L.p_f64(out)))
+        self._call('duration_mean', self._k(k), L.p_f64(out))
         return out
 
     def profile(self, enable=None):
         '''HIP-event time of the add and map launches: (add ms, adds, map ms, map launches); enable
         switches it'''
-        am, an, qm, qn = C.c_double(), C.c_int64(), C.c_double(), C.c_int64()
-        L.check(self._lib.ps_peak_prof(self._h, -1 if enable is None else int(bool(enable)), C.byref(am),
-                                       C.byref(an), C.byref(qm), C.byref(qn)))
-        return am.value, an.value, qm.value, qn.value
+        return self._profile(enable)
 
-    def close(self):
-        if self._h:
-            self._lib.ps_peak_destroy(self._h)
-            self._h = L._VP()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class PeakPosterior():
@@ -937,7 +659,7 @@ def level_tag(p):
     return 'l' + ('%g' % (100 * p)).replace('.', 'p')
 
 
-class ExcursionMaps():
+class ExcursionMaps(_Accumulator):
     '''Joint statements about where `pop_model`'s members hold >= t_k on a listed day (Bolin & Lindgren 2015, on
     the level sets of the marginal probability): thresholds t_0 < ... < t_{K-1} (1..4, finite, > 0), model days
     `days` (strictly increasing, at most 32, default all).  On the device per (k, day) the weighted count C of the
@@ -946,14 +668,14 @@ class ExcursionMaps():
     time with probability >= level, "surely reached" -- its mirror image `below` F- ("surely not reached") and
     `contour` Fc, whose {Fc < level} is the credible band of the t_k-contour, the front.  Counts and bounds are
     integers: the order of adds and merges changes no bit of a map.'''
+    _prefix, _noun = 'ps_excur', 'excursion maps'
+    _info_types = (C.c_double, C.c_int64, C.c_int64, C.c_int64)      # weight, members, capacity, bytes
 
     ABOVE, BELOW, CONTOUR = 0, 1, 2
 
     def __init__(self, pop_model, thresholds, days=None):
-        self._h = L._VP()
         self.thresholds = check_arrival_thresholds(thresholds)
-        self.days = check_arrival_days(range(len(pop_model.days)) if days is None else days)
-        self._setup(pop_model, None)
+        self._setup(pop_model, None, check_arrival_days(range(len(pop_model.days)) if days is None else days))
 
     @classmethod
     def for_projection(cls, projection, thresholds):
@@ -962,73 +684,31 @@ class ExcursionMaps():
         `apply()` (the peak field of its last add).  `days` holds the output labels -- the plan's output days,
         or the output indices.'''
         self = cls.__new__(cls)
-        self._h = L._VP()
         self.thresholds = check_arrival_thresholds(thresholds)
-        if projection.fields_kind == 'peak':      # one output, the peak field: its `days` are those it peaks over
-            labels = [0]
-        else:
-            labels = list(getattr(projection, 'days', range(projection.nout)))
-        self.days = check_arrival_days([labels[e] for e in projection.live])
-        self._setup(projection.pm, projection)
+        self._setup(projection.pm, projection, check_arrival_days(_output_labels(projection)))
         return self
 
-    def _setup(self, pop_model, projection):
-        self._proj = projection
-        self._lib = L.load()
-        self.pm = pop_model
-        self.N = 2 * int(pop_model.rad_res) + 1
-        self.cell_area = (float(pop_model.rad_dist) / int(pop_model.rad_res)) ** 2
-        self.device = L.default_device() if pop_model.device is None else int(pop_model.device)
-        self.pitch = (self.N * self.N + 63) // 64 * 64
+    def _setup(self, pop_model, projection, days):
+        self._attach(pop_model)
+        self._set_source(projection, days)
         self.member_nbytes = len(self.thresholds) * len(self.days) * self.pitch // 8     # one member's masks
-        thr = L.f64(self.thresholds)
-        L.check(self._lib.ps_excur_create(self.device, self.N, len(self.days), len(self.thresholds), L.p_f64(thr),
-                                          C.byref(self._h)))
-        if projection is None:
-            self._kind, self._idx, self._delta = _day_slots(self.days)
-        self._slot = {d: i for i, d in enumerate(self.days)}
+        self._create(len(self.days), len(self.thresholds), L.p_f64(L.f64(self.thresholds)))
 
     def reserve(self, n):
         '''room for n members' masks now, so that no add has to grow them'''
-        L.check(self._lib.ps_excur_reserve(self._h, int(n)))
+        self._call('reserve', int(n))
 
     def add(self, weight=1):
         '''Accumulate the last evaluation of the model with integer weight >= 1 (enqueued on the
         solver's stream; no host synchronisation unless the masks grow).  On a projection or a plan: its last
         apply, on the handle's stream.'''
-        w = int(weight)
-        if w < 1:
-            raise ValueError('weight must be a positive integer')
-        if self._proj is not None:
-            L.check(getattr(self._lib, 'ps_excur_add_' + self._proj.fields_kind)(self._h, self._proj._h, w))
-            return
-        pm = self.pm
-        _check_evaluated(pm, self.days, 'excursion maps')
-        stat, post = _day_scales(pm, self.days)
-        L.check(self._lib.ps_excur_add(self._h, pm.solver._h, len(self.days), L.p_i32(self._kind), L.p_i32(self._idx),
-                                       L.p_f64(stat), L.p_f64(post), L.p_i32(self._delta), NEGVAL, w))
+        self._add(weight)
 
     def merge(self, other):
         '''self += other (same device, domain, days and thresholds); other's members follow self's'''
         if list(other.days) != self.days:
             raise ValueError('excursion maps over different days')
-        L.check(self._lib.ps_excur_merge(self._h, other._h))
-
-    def reset(self):
-        L.check(self._lib.ps_excur_reset(self._h))
-
-    def _info(self):
-        w, m, c, b = C.c_double(), C.c_int64(), C.c_int64(), C.c_int64()
-        L.check(self._lib.ps_excur_info(self._h, C.byref(w), C.byref(m), C.byref(c), C.byref(b)))
-        return w.value, m.value, c.value, b.value
-
-    @property
-    def total_weight(self):
-        return self._info()[0]
-
-    @property
-    def members(self):
-        return self._info()[1]
+        self._call('merge', other._h)
 
     @property
     def capacity(self):
@@ -1040,29 +720,18 @@ class ExcursionMaps():
         '''the device memory the handle holds now'''
         return self._info()[3]
 
-    def _k(self, k):
-        if not 0 <= int(k) < len(self.thresholds):
-            raise ValueError('threshold %r of %d' % (k, len(self.thresholds)))
-        return int(k)
-
-    def _slot_of(self, day):
-        if day not in self._slot:
-            raise ValueError('day %r is not in the excursion maps %s' % (day, self.days))
-        return self._slot[day]
-
     def counts(self, k, day):
         '''[N, N] uint32: the weight of the members at or above t_k on `day`'''
         out = np.empty((self.N, self.N), dtype=np.uint32)
-        L.check(self._lib.ps_excur_fetch_counts(self._h, self._k(k), self._slot_of(day),
-                                                out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        self._call('fetch_counts', self._k(k), self._slot_of(day), out.ctypes.data_as(C.POINTER(C.c_uint32)))
         return out
 
     def mask(self, member, k, day):
         '''[pitch / 64] uint64: the mask words of one member (in add order), bit l of word j the cell 64 j + l
         of the flattened domain, the pad bits 0'''
         out = np.empty(self.pitch // 64, dtype=np.uint64)
-        L.check(self._lib.ps_excur_fetch_mask(self._h, int(member), self._k(k), self._slot_of(day),
-                                              out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        self._call('fetch_mask', int(member), self._k(k), self._slot_of(day),
+                                 out.ctypes.data_as(C.POINTER(C.c_uint64)))
         return out
 
     def bounds(self, k, day):
@@ -1071,13 +740,13 @@ class ExcursionMaps():
         m = self.members
         hi, lo, w = (np.empty(m, dtype=np.uint32) for _ in range(3))
         u32 = C.POINTER(C.c_uint32)
-        L.check(self._lib.ps_excur_fetch_bounds(self._h, self._k(k), self._slot_of(day), hi.ctypes.data_as(u32),
-                                                lo.ctypes.data_as(u32), w.ctypes.data_as(u32)))
+        self._call('fetch_bounds', self._k(k), self._slot_of(day), hi.ctypes.data_as(u32), lo.ctypes.data_as(u32),
+                                   w.ctypes.data_as(u32))
         return hi, lo, w
 
     def _map(self, k, day, what):
         out = np.empty((self.N, self.N), dtype=np.float64)
-        L.check(self._lib.ps_excur_map(self._h, self._k(k), self._slot_of(day), what, L.p_f64(out)))
+        self._call('map', self._k(k), self._slot_of(day), what, L.p_f64(out))
         return out
 
     def above(self, k, day):
@@ -1113,25 +782,9 @@ class ExcursionMaps():
         map launches); enable switches it'''
         ms = np.zeros(3, dtype=np.float64)
         n = np.zeros(3, dtype=np.int64)
-        L.check(self._lib.ps_excur_prof(self._h, -1 if enable is None else int(bool(enable)), L.p_f64(ms), L.p_i64(n)))
+        self._call('prof', -1 if enable is None else int(bool(enable)), L.p_f64(ms), L.p_i64(n))
         return float(ms[0]), int(n[0]), float(ms[1]), int(n[1]), float(ms[2]), int(n[2])
 
-    def close(self):
-        if self._h:
-            self._lib.ps_excur_destroy(self._h)
-            self._h = L._VP()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 MAX_RANGE_FRACTIONS = 4
@@ -1182,7 +835,7 @@ def check_core_range(core_range, days=None):
     return check_range_fractions(fr), lv
 
 
-class RangeMaps():
+class RangeMaps(_Accumulator):
     '''Where each of `pop_model`'s members holds most of its wasps: for mass fractions p_0 < ... < p_{J-1} (1..4,
     each in (0, 1)) and the model days `days` (strictly increasing, at most 32, default all) the member's own
     highest-density region {v >= lambda_j}, the smallest set of cells that holds the share p_j of the member's
@@ -1191,12 +844,12 @@ class RangeMaps():
     the cells n_j of the region, the integer mass Q and its exponent E (ps_range_*; the statements are those of
     include/parasitoid_hip.h, restated in tests/range_ref.py).  The level is the member's own, so the maps do not
     change with the release number.  Counts are integers: the order of adds and merges changes no bit.'''
+    _prefix, _noun, _prof_pairs = 'ps_range', 'core-range maps', 2
+    _info_types = (C.c_double, C.c_int64, C.c_int64, C.c_int64)      # weight, members, capacity, bytes
 
     def __init__(self, pop_model, fractions, days=None):
-        self._h = L._VP()
         self.fractions = check_range_fractions(fractions)
-        self.days = check_arrival_days(range(len(pop_model.days)) if days is None else days)
-        self._setup(pop_model, None)
+        self._setup(pop_model, None, check_arrival_days(range(len(pop_model.days)) if days is None else days))
 
     @classmethod
     def for_projection(cls, projection, fractions):
@@ -1204,68 +857,30 @@ class RangeMaps():
         that carry weight in ascending order: `add(weight)` accumulates the outputs of its last `apply()`.
         `days` holds the output labels -- the plan's output days, or the projection's output indices.'''
         self = cls.__new__(cls)
-        self._h = L._VP()
         self.fractions = check_range_fractions(fractions)
-        labels = list(getattr(projection, 'days', range(projection.nout)))
-        self.days = check_arrival_days([labels[e] for e in projection.live])
-        self._setup(projection.pm, projection)
+        self._setup(projection.pm, projection, check_arrival_days(_output_labels(projection)))
         return self
 
-    def _setup(self, pop_model, projection):
-        self._proj = projection
-        self._lib = L.load()
-        self.pm = pop_model
-        self.N = 2 * int(pop_model.rad_res) + 1
-        self.cell_area = (float(pop_model.rad_dist) / int(pop_model.rad_res)) ** 2
-        self.device = L.default_device() if pop_model.device is None else int(pop_model.device)
-        fr = L.f64(self.fractions)
-        L.check(self._lib.ps_range_create(self.device, self.N, len(self.days), len(self.fractions), L.p_f64(fr),
-                                          C.byref(self._h)))
-        if projection is None:
-            self._kind, self._idx, self._delta = _day_slots(self.days)
-        self._slot = {d: i for i, d in enumerate(self.days)}
+    def _setup(self, pop_model, projection, days):
+        self._attach(pop_model)
+        self._set_source(projection, days)
+        self._create(len(self.days), len(self.fractions), L.p_f64(L.f64(self.fractions)))
 
     def reserve(self, n):
         '''room for n members' rows now, so that no add has to grow them'''
-        L.check(self._lib.ps_range_reserve(self._h, int(n)))
+        self._call('reserve', int(n))
 
     def add(self, weight=1):
         '''Accumulate the last evaluation of the model with integer weight >= 1 (enqueued on the solver's stream;
         no host synchronisation unless the member rows grow).  On a projection or a plan: its last apply, on the
         handle's stream.'''
-        w = int(weight)
-        if w < 1:
-            raise ValueError('weight must be a positive integer')
-        if self._proj is not None:
-            L.check(getattr(self._lib, 'ps_range_add_' + self._proj.fields_kind)(self._h, self._proj._h, w))
-            return
-        pm = self.pm
-        _check_evaluated(pm, self.days, 'core-range maps')
-        stat, post = _day_scales(pm, self.days)
-        L.check(self._lib.ps_range_add(self._h, pm.solver._h, len(self.days), L.p_i32(self._kind), L.p_i32(self._idx),
-                                       L.p_f64(stat), L.p_f64(post), L.p_i32(self._delta), NEGVAL, w))
+        self._add(weight)
 
     def merge(self, other):
         '''self += other (same device, domain, days and fractions); other's members follow self's'''
         if list(other.days) != self.days:
             raise ValueError('core-range maps over different days')
-        L.check(self._lib.ps_range_merge(self._h, other._h))
-
-    def reset(self):
-        L.check(self._lib.ps_range_reset(self._h))
-
-    def _info(self):
-        w, m, c, b = C.c_double(), C.c_int64(), C.c_int64(), C.c_int64()
-        L.check(self._lib.ps_range_info(self._h, C.byref(w), C.byref(m), C.byref(c), C.byref(b)))
-        return w.value, m.value, c.value, b.value
-
-    @property
-    def total_weight(self):
-        return self._info()[0]
-
-    @property
-    def members(self):
-        return self._info()[1]
+        self._call('merge', other._h)
 
     @property
     def capacity(self):
@@ -1282,22 +897,16 @@ class RangeMaps():
             raise ValueError('fraction %r of %d' % (j, len(self.fractions)))
         return int(j)
 
-    def _slot_of(self, day):
-        if day not in self._slot:
-            raise ValueError('day %r is not in the core-range maps %s' % (day, self.days))
-        return self._slot[day]
-
     def counts(self, j, day):
         '''[N, N] uint32: the weight of the members whose p_j region on `day` holds the cell'''
         out = np.empty((self.N, self.N), dtype=np.uint32)
-        L.check(self._lib.ps_range_fetch_counts(self._h, self._j(j), self._slot_of(day),
-                                                out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        self._call('fetch_counts', self._j(j), self._slot_of(day), out.ctypes.data_as(C.POINTER(C.c_uint32)))
         return out
 
     def prob(self, j, day):
         '''[N, N] float64: the posterior probability C / W that the cell lies in the member's p_j region'''
         out = np.empty((self.N, self.N), dtype=np.float64)
-        L.check(self._lib.ps_range_prob(self._h, self._j(j), self._slot_of(day), L.p_f64(out)))
+        self._call('prob', self._j(j), self._slot_of(day), L.p_f64(out))
         return out
 
     def range(self, j, day, level=0.5):
@@ -1310,8 +919,8 @@ class RangeMaps():
         lam = np.empty(m, dtype=np.float64)
         n, w = np.empty(m, dtype=np.uint32), np.empty(m, dtype=np.uint32)
         u32 = C.POINTER(C.c_uint32)
-        L.check(self._lib.ps_range_fetch_members(self._h, self._j(j), self._slot_of(day), L.p_f64(lam),
-                                                 n.ctypes.data_as(u32), w.ctypes.data_as(u32)))
+        self._call('fetch_members', self._j(j), self._slot_of(day), L.p_f64(lam), n.ctypes.data_as(u32),
+                                    w.ctypes.data_as(u32))
         return lam, n, w
 
     @property
@@ -1332,8 +941,7 @@ class RangeMaps():
         floor(v 2^(36 - E)), and E = floor(log2 max v); both 0 where it holds nothing'''
         m = self.members
         Q, E = np.empty(m, dtype=np.uint64), np.empty(m, dtype=np.int32)
-        L.check(self._lib.ps_range_fetch_mass(self._h, self._slot_of(day), Q.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                              L.p_i32(E)))
+        self._call('fetch_mass', self._slot_of(day), Q.ctypes.data_as(C.POINTER(C.c_uint64)), L.p_i32(E))
         return Q, E
 
     def area(self, j, day, levels=(0.05, 0.5, 0.95)):
@@ -1348,27 +956,8 @@ class RangeMaps():
     def profile(self, enable=None):
         '''HIP-event time of the adds and the map launches: (add ms, adds, map ms, map launches); enable
         switches it'''
-        am, an, qm, qn = C.c_double(), C.c_int64(), C.c_double(), C.c_int64()
-        L.check(self._lib.ps_range_prof(self._h, -1 if enable is None else int(bool(enable)), C.byref(am),
-                                        C.byref(an), C.byref(qm), C.byref(qn)))
-        return am.value, an.value, qm.value, qn.value
+        return self._profile(enable)
 
-    def close(self):
-        if self._h:
-            self._lib.ps_range_destroy(self._h)
-            self._h = L._VP()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def range_area(cells, weights, cell_area, levels=(0.05, 0.5, 0.95), day=None):
@@ -1462,16 +1051,16 @@ def exposure_weights(in_days, upto):
     return (d[None, :] <= u[:, None]).astype(np.float64)
 
 
-class Projection():
+class Projection(_Handle):
     '''Y_e(c) = sum_d weights[e][d] v_d(c) of `pop_model`'s last evaluation, on the device: v_d the value
     SpreadSummary adds for model day in_days[d] (strictly increasing, at most 32), weights [nout, nin] finite
     and >= 0 (check_weights), at most 32 outputs.  The sum runs in ascending d from +0.0 with the product and
     the sum rounded separately, so a numpy loop reproduces every bit.  An output whose weights are all zero
     is zero throughout: it is kept off the device (`live` lists the others) and reads as zeros.'''
     fields_kind = 'project'      # the accumulators' entry points for these fields: ps_*_add_project
+    _prefix, _noun = 'ps_project', 'projection'
 
     def __init__(self, pop_model, weights, in_days):
-        self._h = L._VP()
         self.in_days = check_in_days(in_days)
         self.weights = check_weights(weights, len(self.in_days), zero_rows=True)
         self.nout = self.weights.shape[0]
@@ -1479,37 +1068,22 @@ class Projection():
         if not self.live:
             raise ValueError('the projection has no non-zero weight')
         self._slot = {e: i for i, e in enumerate(self.live)}
-        self._lib = L.load()
-        self.pm = pop_model
-        self.N = 2 * int(pop_model.rad_res) + 1
-        self.device = L.default_device() if pop_model.device is None else int(pop_model.device)
-        pitch = (self.N * self.N + 63) // 64 * 64
-        self.nbytes = len(self.live) * pitch * 8            # the output fields
+        self._attach(pop_model)
+        self.nbytes = len(self.live) * self.pitch * 8       # the output fields
         W = np.ascontiguousarray(self.weights[self.live])
-        L.check(self._lib.ps_project_create(self.device, self.N, len(self.in_days), len(self.live), L.p_f64(W),
-                                            C.byref(self._h)))
-        self._kind, self._idx, self._delta = _day_slots(self.in_days)
+        self._create(len(self.in_days), len(self.live), L.p_f64(W))
+        self._set_days(self.in_days)
 
     def apply(self):
         '''Project the last evaluation of the model (enqueued on the solver's stream; no host
         synchronisation); the outputs of the previous apply are overwritten.'''
-        pm = self.pm
-        _check_evaluated(pm, self.in_days, 'projection')
-        stat, post = _day_scales(pm, self.in_days)
-        L.check(self._lib.ps_project_apply(self._h, pm.solver._h, len(self.in_days), L.p_i32(self._kind),
-                                           L.p_i32(self._idx), L.p_f64(stat), L.p_f64(post), L.p_i32(self._delta),
-                                           NEGVAL))
+        self._from_model('apply')
 
     @property
     def applies(self):
         n = C.c_int64()
-        L.check(self._lib.ps_project_info(self._h, None, None, None, C.byref(n)))
+        self._call('info', None, None, None, C.byref(n))
         return n.value
-
-    def _e(self, e):
-        if not 0 <= int(e) < self.nout:
-            raise ValueError('output %r of %d' % (e, self.nout))
-        return int(e)
 
     def field(self, e):
         '''[N, N] float64: output e of the last apply'''
@@ -1517,7 +1091,7 @@ class Projection():
         if e not in self._slot:
             return np.zeros((self.N, self.N), dtype=np.float64)
         out = np.empty((self.N, self.N), dtype=np.float64)
-        L.check(self._lib.ps_project_fetch(self._h, self._slot[e], L.p_f64(out)))
+        self._call('fetch', self._slot[e], L.p_f64(out))
         return out
 
     def gather(self, rows, cols):
@@ -1526,34 +1100,15 @@ class Projection():
         if rows.size != cols.size:
             raise ValueError('%d rows and %d columns' % (rows.size, cols.size))
         got = np.zeros((len(self.live), rows.size), dtype=np.float64)
-        L.check(self._lib.ps_project_gather(self._h, rows.size, L.p_i32(rows), L.p_i32(cols), L.p_f64(got)))
+        self._call('gather', rows.size, L.p_i32(rows), L.p_i32(cols), L.p_f64(got))
         out = np.zeros((self.nout, rows.size), dtype=np.float64)
         out[self.live] = got
         return out
 
     def profile(self, enable=None):
         '''HIP-event time of the apply launches: (total ms, launches); enable switches it'''
-        ms, n = C.c_double(), C.c_int64()
-        L.check(self._lib.ps_project_prof(self._h, -1 if enable is None else int(bool(enable)), C.byref(ms),
-                                          C.byref(n)))
-        return ms.value, n.value
+        return self._profile(enable)
 
-    def close(self):
-        if self._h:
-            self._lib.ps_project_destroy(self._h)
-            self._h = L._VP()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def emergence_plan(emergence, ndays=None):
@@ -1981,7 +1536,7 @@ def sites_plan(arg, pop_model=None):
     return sites, days, lags
 
 
-class ReleaseSites():
+class ReleaseSites(_Handle):
     '''The field of a whole release plan, member by member, on the device: Y_e = sum over the sites of
     amount * (the field of that site's release on output day days[e], translated to the site).  sites:
     [(east_m, north_m, amount[, lag_days=0]), ...] (check_sites); days: output model days counted from the first
@@ -1993,9 +1548,10 @@ class ReleaseSites():
     every bit.  Every output carries weight (`live`), so SpreadSummary.for_projection,
     SpreadHistogram.for_projection and ArrivalMaps.for_projection accept a plan.'''
     fields_kind = 'sites'        # the accumulators' entry points for these fields: ps_*_add_sites
+    _prefix = 'ps_sites'
+    _owned = ()                  # the lagged models with_lagged_models built: closed with the plan
 
     def __init__(self, pop_model, sites, days=None, lagged=None):
-        self._h = L._VP()
         self.sites = check_sites(sites, pop_model.rad_dist, pop_model.rad_res)
         self.days = check_site_days(range(len(pop_model.days)) if days is None else days, len(pop_model.days))
         self.groups = site_groups(self.sites)
@@ -2004,19 +1560,14 @@ class ReleaseSites():
         self.lagged = check_lagged(pop_model, self.lags, lagged)
         self.nout = len(self.days)
         self.live = list(range(self.nout))
-        self._lib = L.load()
-        self.pm = pop_model
-        self.N = 2 * int(pop_model.rad_res) + 1
-        self.device = L.default_device() if pop_model.device is None else int(pop_model.device)
-        pitch = (self.N * self.N + 63) // 64 * 64
-        self.nbytes = self.nout * pitch * 8                 # the output fields
+        self._attach(pop_model)
+        self.nbytes = self.nout * self.pitch * 8            # the output fields
         order = [k for _lag, ks in self.groups for k in ks]
         nsite = L.i32([len(ks) for _lag, ks in self.groups])
         drow = L.i32([self.sites[k]['drow'] for k in order])
         dcol = L.i32([self.sites[k]['dcol'] for k in order])
         amount = L.f64([self.sites[k]['amount'] for k in order])
-        L.check(self._lib.ps_sites_create(self.device, self.N, self.nout, len(self.groups), L.p_i32(nsite),
-                                          L.p_i32(drow), L.p_i32(dcol), L.p_f64(amount), C.byref(self._h)))
+        self._create(self.nout, len(self.groups), L.p_i32(nsite), L.p_i32(drow), L.p_i32(dcol), L.p_f64(amount))
 
     @classmethod
     def with_lagged_models(cls, pop_model, sites, days=None, wind_data=None):
@@ -2056,7 +1607,7 @@ class ReleaseSites():
         enqueued on its solver's stream; no host synchronisation); the outputs of the previous apply are
         overwritten.'''
         for call in self._calls():                             # every model checked before the first launch
-            L.check(self._lib.ps_sites_apply(self._h, *call))
+            self._call('apply', *call)
 
     def _calls(self):
         '''the arguments of ps_sites_apply behind the handle, group by group, from each model's last evaluation'''
@@ -2076,15 +1627,13 @@ class ReleaseSites():
     def applies(self):
         '''complete passes over the plan's groups'''
         n = C.c_int64()
-        L.check(self._lib.ps_sites_info(self._h, None, None, None, None, C.byref(n)))
+        self._call('info', None, None, None, None, C.byref(n))
         return n.value
 
     def field(self, e):
         '''[N, N] float64: output e (model day days[e]) of the last apply'''
-        if not 0 <= int(e) < self.nout:
-            raise ValueError('output %r of %d' % (e, self.nout))
         out = np.empty((self.N, self.N), dtype=np.float64)
-        L.check(self._lib.ps_sites_fetch(self._h, int(e), L.p_f64(out)))
+        self._call('fetch', self._e(e), L.p_f64(out))
         return out
 
     def gather(self, rows, cols):
@@ -2093,39 +1642,22 @@ class ReleaseSites():
         if rows.size != cols.size:
             raise ValueError('%d rows and %d columns' % (rows.size, cols.size))
         out = np.zeros((self.nout, rows.size), dtype=np.float64)
-        L.check(self._lib.ps_sites_gather(self._h, rows.size, L.p_i32(rows), L.p_i32(cols), L.p_f64(out)))
+        self._call('gather', rows.size, L.p_i32(rows), L.p_i32(cols), L.p_f64(out))
         return out
 
     def profile(self, enable=None):
         '''HIP-event time of the apply launches, one per group: (total ms, launches); enable switches it'''
-        ms, n = C.c_double(), C.c_int64()
-        L.check(self._lib.ps_sites_prof(self._h, -1 if enable is None else int(bool(enable)), C.byref(ms),
-                                        C.byref(n)))
-        return ms.value, n.value
+        return self._profile(enable)
 
     def describe(self):
         '''the plan for a result file: sites in metres and cells, release days, output days'''
         return {'sites': [dict(s) for s in self.sites], 'lags': list(self.lags), 'days': list(self.days)}
 
     def close(self):
-        if self._h:
-            self._lib.ps_sites_destroy(self._h)
-            self._h = L._VP()
-        for m in getattr(self, '_owned', []):
+        super().close()
+        for m in self._owned:
             m.close()
         self._owned = []
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ------------------------------------------------------------------ paired contrast of two plans
@@ -2187,7 +1719,7 @@ def contrast_plan(arg, sites_arg, pop_model=None):
     return sites_plan(dict(sites=arg['sites'], days=a_days), pop_model)
 
 
-class PlanContrast():
+class PlanContrast(_Accumulator):
     '''The posterior of the difference of two plans, member by member, on the device: `a` and `b` are two
     ReleaseSites or two Projection on the same device and domain with the same outputs (nout, live; of two
     ReleaseSites also the same output days -- outputs are paired by index and labelled by A's days; of two
@@ -2199,8 +1731,9 @@ class PlanContrast():
     output -- the pairing the two plans' own maps have lost.  The accessors take the output index; outputs
     kept off the device read as zeros.  Counts are integers: the order of adds and merges changes no bit.'''
 
+    _prefix = 'ps_contrast'
+
     def __init__(self, a, b, thresholds=()):
-        self._h = L._VP()
         if a is b:
             raise ValueError('a plan is compared with another one, not with itself')
         if type(a) is not type(b) or not isinstance(a, (ReleaseSites, Projection)):
@@ -2213,64 +1746,31 @@ class PlanContrast():
                 raise ValueError('the plans differ in %s: %r and %r' % (name, getattr(a, name), getattr(b, name)))
         self.thresholds = check_contrast_thresholds(thresholds)
         self.a, self.b = a, b
-        self.pm = a.pm
-        self.N, self.device, self.nout, self.live = a.N, a.device, a.nout, list(a.live)
+        self._attach(a.pm)
+        self.device, self.nout, self.live = a.device, a.nout, list(a.live)
         self.labels = list(getattr(a, 'days', range(a.nout)))
-        self.cell_area = (float(a.pm.rad_dist) / int(a.pm.rad_res)) ** 2
         self._slot = {e: i for i, e in enumerate(self.live)}
-        self._lib = L.load()
-        pitch = (self.N * self.N + 63) // 64 * 64
-        self.nbytes = len(self.live) * pitch * (16 + 4 * (2 + 2 * len(self.thresholds)))   # moments and counts
+        self.nbytes = len(self.live) * self.pitch * (16 + 4 * (2 + 2 * len(self.thresholds)))   # moments and counts
         thr = L.f64(self.thresholds if self.thresholds else [0.0])
-        L.check(self._lib.ps_contrast_create(self.device, self.N, len(self.live), len(self.thresholds), L.p_f64(thr),
-                                             C.byref(self._h)))
+        self._create(len(self.live), len(self.thresholds), L.p_f64(thr))
 
     def add(self, weight=1):
         '''Accumulate the last apply of both plans with integer weight >= 1 (on the handle's stream behind both;
         no host synchronisation)'''
-        w = int(weight)
-        if w < 1:
-            raise ValueError('weight must be a positive integer')
-        L.check(getattr(self._lib, 'ps_contrast_add_' + self.a.fields_kind)(self._h, self.a._h, self.b._h, w))
+        self._from_fields('add', self.a, self.b._h, self._weight(weight))
 
     def merge(self, other):
         '''self += other (same device, domain, outputs and thresholds); other's members follow self's'''
         if other.live != self.live or other.nout != self.nout or list(other.labels) != self.labels:
             raise ValueError('contrasts over different outputs')
-        L.check(self._lib.ps_contrast_merge(self._h, other._h))
-
-    def reset(self):
-        L.check(self._lib.ps_contrast_reset(self._h))
-
-    def _info(self):
-        w, m = C.c_double(), C.c_int64()
-        L.check(self._lib.ps_contrast_info(self._h, C.byref(w), C.byref(m)))
-        return w.value, m.value
-
-    @property
-    def total_weight(self):
-        return self._info()[0]
-
-    @property
-    def members(self):
-        return self._info()[1]
-
-    def _e(self, e):
-        if not 0 <= int(e) < self.nout:
-            raise ValueError('output %r of %d' % (e, self.nout))
-        return int(e)
-
-    def _k(self, k):
-        if not 0 <= int(k) < len(self.thresholds):
-            raise ValueError('threshold %r of %d' % (k, len(self.thresholds)))
-        return int(k)
+        self._call('merge', other._h)
 
     def _fetch(self, e, what):
         e = self._e(e)
         if e not in self._slot:
             return np.zeros((self.N, self.N), dtype=np.float64)
         out = np.empty((self.N, self.N), dtype=np.float64)
-        L.check(self._lib.ps_contrast_fetch(self._h, self._slot[e], int(what), L.p_f64(out)))
+        self._call('fetch', self._slot[e], int(what), L.p_f64(out))
         return out
 
     def mean(self, e):
@@ -2307,8 +1807,7 @@ class PlanContrast():
         if e not in self._slot:
             return np.zeros((self.N, self.N), dtype=np.uint32)
         out = np.empty((self.N, self.N), dtype=np.uint32)
-        L.check(self._lib.ps_contrast_fetch_counts(self._h, self._slot[e], int(which),
-                                                   out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        self._call('fetch_counts', self._slot[e], int(which), out.ctypes.data_as(C.POINTER(C.c_uint32)))
         return out
 
     def _coverage(self):
@@ -2316,7 +1815,7 @@ class PlanContrast():
         cells = np.zeros((m, 2, len(self.thresholds), len(self.live)), dtype=np.uint32)
         w = np.zeros(m, dtype=np.uint32)
         u32 = C.POINTER(C.c_uint32)
-        L.check(self._lib.ps_contrast_fetch_coverage(self._h, 0, m, cells.ctypes.data_as(u32), w.ctypes.data_as(u32)))
+        self._call('fetch_coverage', 0, m, cells.ctypes.data_as(u32), w.ctypes.data_as(u32))
         return cells, w
 
     @property
@@ -2344,27 +1843,8 @@ class PlanContrast():
 
     def profile(self, enable=None):
         '''HIP-event time of the add launches: (total ms, adds); enable switches it'''
-        ms, n = C.c_double(), C.c_int64()
-        L.check(self._lib.ps_contrast_prof(self._h, -1 if enable is None else int(bool(enable)), C.byref(ms),
-                                           C.byref(n)))
-        return ms.value, n.value
+        return self._profile(enable)
 
-    def close(self):
-        if self._h:
-            self._lib.ps_contrast_destroy(self._h)
-            self._h = L._VP()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ------------------------------------------------------------------ sensitivity
@@ -2523,7 +2003,7 @@ def finalize_factor(moments):
     return L.f64(F), rank, lam, L.f64(moments.inv_sd())
 
 
-class SensitivityMaps():
+class SensitivityMaps(_Accumulator):
     '''Which parameter drives the posterior spread where: per cell of `pop_model`'s days the weighted
     covariance between the value SpreadSummary adds and each of `params` (names from mcmc.MODEL_BLOCK, default
     all 15) over the members added, on the device (ps_sens_*, csrc/ps_sens.hip), next to the mean and the
@@ -2533,12 +2013,10 @@ class SensitivityMaps():
     posterior-weighted measure, not a Sobol index, and 1 by construction when members <= rank + 1, which
     `finalize` therefore refuses -- and `dominant(day)`, the parameter with the largest |correlation|.'''
 
+    _prefix, _noun = 'ps_sens', 'sensitivity maps'
+
     def __init__(self, pop_model, params=None, days=None):
-        self._h = L._VP()
-        days = list(range(len(pop_model.days)) if days is None else days)
-        if not days or min(days) < 0:
-            raise ValueError('days must be a non-empty list of model days >= 0')
-        self._setup(pop_model, params, days, None)
+        self._setup(pop_model, params, _model_days(pop_model, days), None)
 
     @classmethod
     def for_projection(cls, projection, params=None):
@@ -2546,7 +2024,6 @@ class SensitivityMaps():
         output: `add(theta, weight)` accumulates the outputs of its last `apply()`, and the accessors take the
         output index where the day-based maps take a day.'''
         self = cls.__new__(cls)
-        self._h = L._VP()
         self._setup(projection.pm, params, list(range(projection.nout)), projection)
         return self
 
@@ -2556,22 +2033,12 @@ class SensitivityMaps():
         self._cols = [known.index(n) for n in self.params]
         self._nblock = len(known)
         self.moments = ParamMoments(self.params)
-        self._lib = L.load()
-        self.pm = pop_model
-        self.days = days
-        self.N = 2 * int(pop_model.rad_res) + 1
-        self.device = L.default_device() if pop_model.device is None else int(pop_model.device)
-        self._proj = projection
-        keys = days if projection is None else projection.live
-        self._slot = {d: i for i, d in enumerate(keys)}
-        self._n = len(self._slot)
-        pitch = (self.N * self.N + 63) // 64 * 64
-        self.nbytes = self._n * pitch * ((len(self.params) + 3) * 8 + 1)
+        self._attach(pop_model)
+        self._set_source(projection, days, projection and projection.live)
+        self.nbytes = len(self._slot) * self.pitch * ((len(self.params) + 3) * 8 + 1)
         self.rank = None
         self.eigenvalues = None
-        L.check(self._lib.ps_sens_create(self.device, self.N, self._n, len(self.params), C.byref(self._h)))
-        if projection is None:
-            self._kind, self._idx, self._delta = _day_slots(self.days)
+        self._create(len(self._slot), len(self.params))
 
     def add(self, theta, weight=1):
         '''Accumulate the last evaluation of the model (on a projection or a plan: its last apply), whose
@@ -2579,20 +2046,10 @@ class SensitivityMaps():
         t = np.array(theta, dtype=np.float64).ravel()
         if t.size != self._nblock:
             raise ValueError('theta has %d entries, the model block %d' % (t.size, self._nblock))
-        if self._proj is None:
-            _check_evaluated(self.pm, self.days, 'sensitivity maps')
         state = self.moments._state()
-        e = L.f64(self.moments.update(t[self._cols], weight))
-        w = int(weight)
+        e = L.f64(self.moments.update(t[self._cols], weight))          # refuses a weight below 1
         try:
-            if self._proj is not None:
-                L.check(getattr(self._lib, 'ps_sens_add_' + self._proj.fields_kind)(
-                    self._h, self._proj._h, e.size, L.p_f64(e), w))
-            else:
-                stat, post = _day_scales(self.pm, self.days)
-                L.check(self._lib.ps_sens_add(self._h, self.pm.solver._h, self._n, L.p_i32(self._kind),
-                                              L.p_i32(self._idx), L.p_f64(stat), L.p_f64(post), L.p_i32(self._delta),
-                                              NEGVAL, e.size, L.p_f64(e), w))
+            self._read('add', self._proj, e.size, L.p_f64(e), int(weight))
         except Exception:
             self.moments._restore(state)       # a refused add is added nowhere
             raise
@@ -2605,51 +2062,37 @@ class SensitivityMaps():
         state = self.moments._state()
         dtheta = L.f64(self.moments.merge(other.moments))
         try:
-            L.check(self._lib.ps_sens_merge(self._h, other._h, dtheta.size, L.p_f64(dtheta)))
+            self._call('merge', other._h, dtheta.size, L.p_f64(dtheta))
         except Exception:
             self.moments._restore(state)
             raise
         self.rank = None
 
     def reset(self):
-        L.check(self._lib.ps_sens_reset(self._h))
+        super().reset()
         self.moments.reset()
         self.rank = None
-
-    def _info(self):
-        w, m = C.c_double(), C.c_int64()
-        L.check(self._lib.ps_sens_info(self._h, C.byref(w), C.byref(m)))
-        return w.value, m.value
-
-    @property
-    def total_weight(self):
-        return self._info()[0]
-
-    @property
-    def members(self):
-        return self._info()[1]
 
     def finalize(self):
         '''Compute `explained` and `dominant` from the members so far -> (rank, dropped eigenvalues).
         ValueError when nothing varies or members < rank + 2: a regression through that few members fits
         exactly and would report explained == 1 everywhere; the correlation maps stay available.'''
         F, rank, lam, isd = finalize_factor(self.moments)
-        L.check(self._lib.ps_sens_finalize(self._h, len(self.params), rank, L.p_f64(F), L.p_f64(isd)))
+        self._call('finalize', len(self.params), rank, L.p_f64(F), L.p_f64(isd))
         self.rank, self.eigenvalues = rank, lam
         self.F, self.isd = F, isd
         return rank, lam[rank:]
 
     def _fetch(self, day, what):
-        if day not in self._slot:
-            if self._proj is not None and day in self.days:      # an output without weight
-                return np.full((self.N, self.N), -1.0 if what == 3 else 0.0)
-            raise ValueError('day %r is not in the sensitivity maps %s' % (day, self.days))
-        return self.fetch_slot(self._slot[day], what)
+        slot = self._slot_of(day)
+        if slot is None:                                          # an output without weight
+            return np.full((self.N, self.N), -1.0 if what == 3 else 0.0)
+        return self.fetch_slot(slot, what)
 
     def fetch_slot(self, slot, what):
         '''raw access by slot index (0 mean, 1 variance, 2 explained, 3 dominant, 16 + i covariance)'''
         out = np.empty((self.N, self.N), dtype=np.float64)
-        L.check(self._lib.ps_sens_fetch(self._h, int(slot), int(what), L.p_f64(out)))
+        self._call('fetch', int(slot), int(what), L.p_f64(out))
         return out
 
     def _i(self, name):
@@ -2698,27 +2141,8 @@ class SensitivityMaps():
 
     def profile(self, enable=None):
         '''HIP-event time of the accumulate launches: (total ms, launches); enable switches it'''
-        ms, n = C.c_double(), C.c_int64()
-        L.check(self._lib.ps_sens_prof(self._h, -1 if enable is None else int(bool(enable)), C.byref(ms),
-                                       C.byref(n)))
-        return ms.value, n.value
+        return self._profile(enable)
 
-    def close(self):
-        if self._h:
-            self._lib.ps_sens_destroy(self._h)
-            self._h = L._VP()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ------------------------------------------------------------------ Monte Carlo error
@@ -2773,7 +2197,7 @@ def mc_error_plan(mc_error):
     return int(batches)
 
 
-class MonteCarloError():
+class MonteCarloError(_Handle):
     '''Batch means of one sequence of members -- a chain, or half of one -- on the device (ps_mcerr_*,
     csrc/ps_mcerr.hip): how far the posterior mean and the exceedance probabilities of `SpreadSummary` are from
     what a longer chain would give.  The sequence is cut into batches of exactly `batch_weight` rows of weight;
@@ -2783,79 +2207,51 @@ class MonteCarloError():
     the output index.  `rhat`: {day: split R-hat map} where posterior_predictive pooled the sequences, else None.'''
 
     rhat = None
+    _prefix, _noun, _prof_pairs = 'ps_mcerr', 'Monte Carlo error', 2
+    _info_types = (C.c_int64,) * 6     # batches, batch weight, used, open and discarded weight, members
 
     def __init__(self, pop_model, batch_weight, days=None, thresholds=()):
-        self._h = L._VP()
-        days = list(range(len(pop_model.days)) if days is None else days)
-        if not days or min(days) < 0:
-            raise ValueError('days must be a non-empty list of model days >= 0')
-        self._setup(pop_model, batch_weight, days, thresholds, None)
+        self._setup(pop_model, batch_weight, _model_days(pop_model, days), thresholds, None)
 
     @classmethod
     def for_projection(cls, projection, batch_weight, thresholds=()):
         '''The batch means of the outputs of `projection` (a Projection or a ReleaseSites), one slot per output
         that carries weight: `add(weight)` takes the outputs of its last `apply()`.'''
         self = cls.__new__(cls)
-        self._h = L._VP()
         self._setup(projection.pm, batch_weight, list(range(projection.nout)), thresholds, projection)
         return self
 
     def _setup(self, pop_model, batch_weight, days, thresholds, projection):
-        self._lib = L.load()
-        self.pm = pop_model
-        self.days = days
         self.thresholds = check_mc_thresholds(thresholds)
         b = int(batch_weight)
         if b != batch_weight or not 1 <= b <= MAX_MC_WEIGHT:
             raise ValueError('batch_weight must be an integer in 1 .. 2^32 - 1, got %r' % (batch_weight,))
-        self.N = 2 * int(pop_model.rad_res) + 1
-        self.device = L.default_device() if pop_model.device is None else int(pop_model.device)
-        self._proj = projection
-        keys = days if projection is None else projection.live
-        self._slot = {d: i for i, d in enumerate(keys)}
-        self._n = len(self._slot)
-        pitch = (self.N * self.N + 63) // 64 * 64
-        self.nbytes = self._n * pitch * (40 + 16 * len(self.thresholds))     # five fp64 planes, counts per threshold
+        self._attach(pop_model)
+        self._set_source(projection, days, projection and projection.live)
+        n = len(self._slot)
+        self.nbytes = n * self.pitch * (40 + 16 * len(self.thresholds))     # five fp64 planes, counts per threshold
         thr = L.f64(self.thresholds if self.thresholds else [0.0])
-        L.check(self._lib.ps_mcerr_create(self.device, self.N, self._n, len(self.thresholds), L.p_f64(thr), b,
-                                          C.byref(self._h)))
-        if projection is None:
-            self._kind, self._idx, self._delta = _day_slots(self.days)
+        self._create(n, len(self.thresholds), L.p_f64(thr), b)
 
     def add(self, weight=1):
         '''Accumulate the last evaluation of the model (of a projection: its last apply) with integer weight
         >= 1, split at the batch boundaries; a batch that fills up is closed.  No host synchronisation.'''
-        w = int(weight)
-        if w < 1:
-            raise ValueError('weight must be a positive integer')
-        if self._proj is not None:
-            L.check(getattr(self._lib, 'ps_mcerr_add_' + self._proj.fields_kind)(self._h, self._proj._h, w))
-            return
-        pm = self.pm
-        _check_evaluated(pm, self.days, 'Monte Carlo error')
-        stat, post = _day_scales(pm, self.days)
-        L.check(self._lib.ps_mcerr_add(self._h, pm.solver._h, self._n, L.p_i32(self._kind), L.p_i32(self._idx),
-                                       L.p_f64(stat), L.p_f64(post), L.p_i32(self._delta), NEGVAL, w))
+        self._read('add', self._proj, self._weight(weight))
 
     def finish(self):
         '''discard the open batch (its weight goes to `discarded_weight`)'''
-        L.check(self._lib.ps_mcerr_finish(self._h))
+        self._call('finish')
 
     def merge(self, other):
         '''self += other: the closed batches of both pooled (same device, domain, days, thresholds and batch
         weight; both finished)'''
         if list(other.days) != self.days or other._slot != self._slot:
             raise ValueError('sequences over different days')
-        L.check(self._lib.ps_mcerr_merge(self._h, other._h))
+        self._call('merge', other._h)
 
     def reset(self):
-        L.check(self._lib.ps_mcerr_reset(self._h))
+        self._call('reset')
         self.rhat = None
-
-    def _info(self):
-        v = [C.c_int64() for _ in range(6)]
-        L.check(self._lib.ps_mcerr_info(self._h, *[C.byref(x) for x in v]))
-        return [x.value for x in v]
 
     @property
     def batches(self):
@@ -2883,11 +2279,7 @@ class MonteCarloError():
 
     def _slot_of(self, day):
         '''the slot of a day, None for an output without weight'''
-        if day not in self._slot:
-            if self._proj is not None and day in self.days:
-                return None
-            raise ValueError('day %r is not in the sequence %s' % (day, self.days))
-        return self._slot[day]
+        return super()._slot_of(day, 'sequence')
 
     def plane(self, day, what):
         '''[N, N] float64: a raw plane (0 gmean, 1 gM2, 2 wM2)'''
@@ -2895,7 +2287,7 @@ class MonteCarloError():
         if slot is None:
             return np.zeros((self.N, self.N), dtype=np.float64)
         out = np.empty((self.N, self.N), dtype=np.float64)
-        L.check(self._lib.ps_mcerr_fetch(self._h, slot, int(what), L.p_f64(out)))
+        self._call('fetch', slot, int(what), L.p_f64(out))
         return out
 
     def counts(self, day, k):
@@ -2907,8 +2299,8 @@ class MonteCarloError():
         s1 = np.zeros((self.N, self.N), dtype=np.uint32)
         s2 = np.zeros((self.N, self.N), dtype=np.uint64)
         if slot is not None:
-            L.check(self._lib.ps_mcerr_fetch_counts(self._h, slot, int(k), s1.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                    s2.ctypes.data_as(C.POINTER(C.c_uint64))))
+            self._call('fetch_counts', slot, int(k), s1.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                       s2.ctypes.data_as(C.POINTER(C.c_uint64)))
         return s1, s2
 
     def mean(self, day):
@@ -2964,27 +2356,8 @@ class MonteCarloError():
     def profile(self, enable=None):
         '''HIP-event time of the add launches, one per piece, and of the close launches: (add ms, add launches,
         close ms, close launches); enable switches it'''
-        ms, n, cms, cn = C.c_double(), C.c_int64(), C.c_double(), C.c_int64()
-        L.check(self._lib.ps_mcerr_prof(self._h, -1 if enable is None else int(bool(enable)), C.byref(ms),
-                                        C.byref(n), C.byref(cms), C.byref(cn)))
-        return ms.value, n.value, cms.value, cn.value
+        return self._profile(enable)
 
-    def close(self):
-        if self._h:
-            self._lib.ps_mcerr_destroy(self._h)
-            self._h = L._VP()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def split_rhat(sequences, day):
@@ -3230,7 +2603,7 @@ def check_reweight_rows(plan, chain_rows):
                                  % (name, a.size, c, n))
 
 
-class ReweightedSummary():
+class ReweightedSummary(_Handle):
     '''The maps of a SpreadSummary under up to 4 reweighting scenarios at once, on the device (ps_wsum_*,
     csrc/ps_wsum.hip): member m counts with the real weight weight_m exp(lambda_m), lambda_m the log-weight the
     caller gives per scenario -- the log-likelihood of new observations under the member (probes_loglik), or any
@@ -3241,12 +2614,10 @@ class ReweightedSummary():
     holds the bits of a SpreadSummary fed alongside.  Importance reweighting degrades as the new data disagree with
     the posterior: watch reweight_diagnostics' ess.'''
 
+    _prefix, _noun = 'ps_wsum', 'reweighted summary'
+
     def __init__(self, pop_model, scenarios, days=None, thresholds=()):
-        self._h = L._VP()
-        days = list(range(len(pop_model.days)) if days is None else days)
-        if not days or min(days) < 0:
-            raise ValueError('days must be a non-empty list of model days >= 0')
-        self._setup(pop_model, scenarios, days, thresholds, None)
+        self._setup(pop_model, scenarios, _model_days(pop_model, days), thresholds, None)
 
     @classmethod
     def for_projection(cls, source, scenarios, thresholds=()):
@@ -3254,7 +2625,6 @@ class ReweightedSummary():
         output: `add(log_weights, weight)` accumulates the outputs of its last `apply()`, and the accessors take
         the output index where the day-based maps take a day.'''
         self = cls.__new__(cls)
-        self._h = L._VP()
         nout = getattr(source, 'nout', 1)
         self._setup(source.pm, scenarios, list(range(nout)), thresholds, source)
         return self
@@ -3263,25 +2633,15 @@ class ReweightedSummary():
         import math
         self.scenarios = check_scenarios(scenarios)
         self.thresholds = check_peak_thresholds(thresholds)
-        self._lib = L.load()
-        self.pm = pop_model
-        self.days = days
-        self.N = 2 * int(pop_model.rad_res) + 1
-        self.device = L.default_device() if pop_model.device is None else int(pop_model.device)
-        self._proj = projection
-        keys = days if projection is None else getattr(projection, 'live', days)
-        self._slot = {d: i for i, d in enumerate(keys)}
-        self._n = len(self._slot)
-        if not 1 <= self._n <= MAX_REWEIGHT_SLOTS:
-            raise ValueError('%d slots; 1..%d fit one handle' % (self._n, MAX_REWEIGHT_SLOTS))
+        self._set_source(projection, days, projection and getattr(projection, 'live', days))
+        n = len(self._slot)
+        if not 1 <= n <= MAX_REWEIGHT_SLOTS:
+            raise ValueError('%d slots; 1..%d fit one handle' % (n, MAX_REWEIGHT_SLOTS))
+        self._attach(pop_model)
         self.ref = [-math.inf] * len(self.scenarios)
-        pitch = (self.N * self.N + 63) // 64 * 64
-        self.nbytes = len(self.scenarios) * (2 + len(self.thresholds)) * 8 * self._n * pitch
+        self.nbytes = len(self.scenarios) * (2 + len(self.thresholds)) * 8 * n * self.pitch
         thr = L.f64(self.thresholds if self.thresholds else [0.0])
-        L.check(self._lib.ps_wsum_create(self.device, self.N, len(self.scenarios), self._n, len(self.thresholds),
-                                         L.p_f64(thr), C.byref(self._h)))
-        if projection is None:
-            self._kind, self._idx, self._delta = _day_slots(self.days)
+        self._create(len(self.scenarios), n, len(self.thresholds), L.p_f64(thr))
 
     def _j(self, name):
         if name not in self.scenarios:
@@ -3326,16 +2686,7 @@ class ReweightedSummary():
         weight `weight` (the run length) times exp(log_weights[j]) in scenario j; enqueued, no host
         synchronisation.  A refused add changes nothing.'''
         r, om, ref = self.scale(log_weights, weight)
-        n = len(self.scenarios)
-        if self._proj is not None:
-            L.check(getattr(self._lib, 'ps_wsum_add_' + self._proj.fields_kind)(
-                self._h, self._proj._h, n, L.p_f64(L.f64(r)), L.p_f64(L.f64(om))))
-        else:
-            _check_evaluated(self.pm, self.days, 'reweighted summary')
-            stat, post = _day_scales(self.pm, self.days)
-            L.check(self._lib.ps_wsum_add(self._h, self.pm.solver._h, self._n, L.p_i32(self._kind), L.p_i32(self._idx),
-                                          L.p_f64(stat), L.p_f64(post), L.p_i32(self._delta), NEGVAL, n,
-                                          L.p_f64(L.f64(r)), L.p_f64(L.f64(om))))
+        self._read('add', self._proj, len(self.scenarios), L.p_f64(L.f64(r)), L.p_f64(L.f64(om)))
         # a member whose weight underflowed is skipped and moves no reference
         self.ref = [b if o > 0.0 else a for a, b, o in zip(self.ref, ref, om)]
 
@@ -3351,19 +2702,18 @@ class ReweightedSummary():
             ref.append(top)
             ra.append(1.0 if top == -math.inf else math.exp(a - top))
             rb.append(1.0 if top == -math.inf else math.exp(b - top))
-        L.check(self._lib.ps_wsum_merge(self._h, other._h, L.p_f64(L.f64(ra)), L.p_f64(L.f64(rb))))
+        self._call('merge', other._h, L.p_f64(L.f64(ra)), L.p_f64(L.f64(rb)))
         self.ref = ref
 
     def reset(self):
         import math
-        L.check(self._lib.ps_wsum_reset(self._h))
+        self._call('reset')
         self.ref = [-math.inf] * len(self.scenarios)
 
     def _info(self):
         n = len(self.scenarios)
         w, m, s = np.zeros(n), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
-        L.check(self._lib.ps_wsum_info(self._h, L.p_f64(w), m.ctypes.data_as(C.POINTER(C.c_int64)),
-                                       s.ctypes.data_as(C.POINTER(C.c_int64))))
+        self._call('info', L.p_f64(w), L.p_i64(m), L.p_i64(s))
         return w, m, s
 
     def total_weight(self, name):
@@ -3385,16 +2735,15 @@ class ReweightedSummary():
 
     def _fetch(self, name, day, what):
         j = self._j(name)
-        if day not in self._slot:
-            if self._proj is not None and day in self.days:      # an output without weight
-                return np.zeros((self.N, self.N), dtype=np.float64)
-            raise ValueError('day %r is not in the reweighted summary %s' % (day, self.days))
-        return self.fetch_slot(j, self._slot[day], what)
+        slot = self._slot_of(day)
+        if slot is None:                                          # an output without weight
+            return np.zeros((self.N, self.N), dtype=np.float64)
+        return self.fetch_slot(j, slot, what)
 
     def fetch_slot(self, scen, slot, what):
         '''raw access by scenario and slot index (0 mean, 1 variance, 2 + k exceedance)'''
         out = np.empty((self.N, self.N), dtype=np.float64)
-        L.check(self._lib.ps_wsum_fetch(self._h, int(scen), int(slot), int(what), L.p_f64(out)))
+        self._call('fetch', int(scen), int(slot), int(what), L.p_f64(out))
         return out
 
     def mean(self, name, day):
@@ -3414,27 +2763,8 @@ class ReweightedSummary():
 
     def profile(self, enable=None):
         '''HIP-event time of the add launches: (total ms, launches); enable switches it'''
-        ms, n = C.c_double(), C.c_int64()
-        L.check(self._lib.ps_wsum_prof(self._h, -1 if enable is None else int(bool(enable)), C.byref(ms),
-                                       C.byref(n)))
-        return ms.value, n.value
+        return self._profile(enable)
 
-    def close(self):
-        if self._h:
-            self._lib.ps_wsum_destroy(self._h)
-            self._h = L._VP()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class _ReweightFeed():
@@ -3588,7 +2918,7 @@ def required_rate(traps, means, day, n, level):
     return out
 
 
-class CatchFields():
+class CatchFields(_Handle):
     '''Y_e(c) = P(Poisson(rate_e v(c)) >= n_e) of `pop_model`'s last evaluation, on the device (ps_catch_*,
     csrc/ps_catch.hip): what a trap of effort rate_e on model day day_e would find at every cell, under the
     package's own observation model (mcmc.loglik_parts).  traps: [(day, rate[, n=1]), ...] (check_traps), v the
@@ -3599,9 +2929,9 @@ class CatchFields():
     len(traps) x pitch x 8 B.  SpreadSummary.for_projection, MonteCarloError.for_projection and
     ReweightedSummary.for_projection accept it.'''
     fields_kind = 'catch'        # the accumulators' entry points for these fields: ps_*_add_catch
+    _prefix, _noun = 'ps_catch', 'catch fields'
 
     def __init__(self, pop_model, traps, days=None):
-        self._h = L._VP()
         self.traps = check_traps(traps)
         used = sorted({t[0] for t in self.traps})
         self.in_days = used if days is None else check_in_days(days)
@@ -3612,7 +2942,7 @@ class CatchFields():
             raise ValueError('trap days %r are not among the days %r' % (missing, self.in_days))
         self._source = None
         self._setup(pop_model, [self.in_days.index(t[0]) for t in self.traps], len(self.in_days))
-        self._kind, self._idx, self._delta = _day_slots(self.in_days)
+        self._set_days(self.in_days)
 
     @classmethod
     def for_projection(cls, source, traps, labels=None):
@@ -3621,7 +2951,6 @@ class CatchFields():
         indices); `apply()` reads the outputs of the source's last apply.  An output without weight is
         refused.'''
         self = cls.__new__(cls)
-        self._h = L._VP()
         self.traps = check_traps(traps, 'output')
         if labels is None:
             labels = getattr(source, 'days', None) if source.fields_kind == 'sites' else None
@@ -3640,45 +2969,31 @@ class CatchFields():
         return self
 
     def _setup(self, pop_model, inputs, nin):
-        self._lib = L.load()
-        self.pm = pop_model
+        self._attach(pop_model)
         self.nout = len(self.traps)
         self.live = list(range(self.nout))
         self.rates = [t[1] for t in self.traps]
         self.counts = [t[2] for t in self.traps]
-        self.N = 2 * int(pop_model.rad_res) + 1
-        self.device = L.default_device() if pop_model.device is None else int(pop_model.device)
-        pitch = (self.N * self.N + 63) // 64 * 64
-        self.nbytes = self.nout * pitch * 8                 # the output fields
-        L.check(self._lib.ps_catch_create(self.device, self.N, int(nin), self.nout, L.p_i32(L.i32(inputs)),
-                                          L.p_f64(L.f64(self.rates)), L.p_i32(L.i32(self.counts)), C.byref(self._h)))
+        self.nbytes = self.nout * self.pitch * 8                 # the output fields
+        self._create(int(nin), self.nout, L.p_i32(L.i32(inputs)), L.p_f64(L.f64(self.rates)),
+                     L.p_i32(L.i32(self.counts)))
 
     def apply(self):
         '''The catch fields of the last evaluation of the model (enqueued on the solver's stream), or of the
         source's last apply (on the handle's stream); no host synchronisation; the outputs of the previous apply
         are overwritten.'''
-        if self._source is not None:
-            L.check(getattr(self._lib, 'ps_catch_apply_' + self._source.fields_kind)(self._h, self._source._h))
-            return
-        pm = self.pm
-        _check_evaluated(pm, self.in_days, 'catch fields')
-        stat, post = _day_scales(pm, self.in_days)
-        L.check(self._lib.ps_catch_apply(self._h, pm.solver._h, len(self.in_days), L.p_i32(self._kind),
-                                         L.p_i32(self._idx), L.p_f64(stat), L.p_f64(post), L.p_i32(self._delta),
-                                         NEGVAL))
+        self._read('apply', self._source)
 
     @property
     def applies(self):
         n = C.c_int64()
-        L.check(self._lib.ps_catch_info(self._h, None, None, None, C.byref(n)))
+        self._call('info', None, None, None, C.byref(n))
         return n.value
 
     def field(self, e):
         '''[N, N] float64: output e of the last apply'''
-        if not 0 <= int(e) < self.nout:
-            raise ValueError('output %r of %d' % (e, self.nout))
         out = np.empty((self.N, self.N), dtype=np.float64)
-        L.check(self._lib.ps_catch_fetch(self._h, int(e), L.p_f64(out)))
+        self._call('fetch', self._e(e), L.p_f64(out))
         return out
 
     def gather(self, rows, cols):
@@ -3687,32 +3002,13 @@ class CatchFields():
         if rows.size != cols.size:
             raise ValueError('%d rows and %d columns' % (rows.size, cols.size))
         out = np.zeros((self.nout, rows.size), dtype=np.float64)
-        L.check(self._lib.ps_catch_gather(self._h, rows.size, L.p_i32(rows), L.p_i32(cols), L.p_f64(out)))
+        self._call('gather', rows.size, L.p_i32(rows), L.p_i32(cols), L.p_f64(out))
         return out
 
     def profile(self, enable=None):
         '''HIP-event time of the apply launches: (total ms, launches); enable switches it'''
-        ms, n = C.c_double(), C.c_int64()
-        L.check(self._lib.ps_catch_prof(self._h, -1 if enable is None else int(bool(enable)), C.byref(ms),
-                                        C.byref(n)))
-        return ms.value, n.value
+        return self._profile(enable)
 
-    def close(self):
-        if self._h:
-            self._lib.ps_catch_destroy(self._h)
-            self._h = L._VP()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class CatchPosterior():
@@ -3875,7 +3171,7 @@ def weight_entropy(weights):
     return float(-(q * np.log(q)).sum())
 
 
-class InformationFields():
+class InformationFields(_Handle):
     '''One member's whole count distribution at every cell for traps the user describes, on the device
     (ps_gain_*, csrc/ps_gain.hip): trap e = (day, rate[, ymax=0]) observes Poisson(rate v) as the classes 0, 1,
     .., ymax and ">= ymax + 1" (ymax = 0: found / none), v the value SpreadSummary adds for that day, under the
@@ -3887,9 +3183,9 @@ class InformationFields():
     ReweightedSummary.for_projection accept it, one slot per plane; InformationPosterior turns their means into
     the information maps.'''
     fields_kind = 'gain'         # the accumulators' entry points for these fields: ps_*_add_gain
+    _prefix, _noun = 'ps_gain', 'information fields'
 
     def __init__(self, pop_model, traps, days=None):
-        self._h = L._VP()
         self.traps = check_info_traps(traps)
         used = sorted({t[0] for t in self.traps})
         self.in_days = used if days is None else check_in_days(days)
@@ -3900,7 +3196,7 @@ class InformationFields():
             raise ValueError('trap days %r are not among the days %r' % (missing, self.in_days))
         self._source = None
         self._setup(pop_model, [self.in_days.index(t[0]) for t in self.traps], len(self.in_days))
-        self._kind, self._idx, self._delta = _day_slots(self.in_days)
+        self._set_days(self.in_days)
 
     @classmethod
     def for_projection(cls, source, traps, labels=None):
@@ -3909,7 +3205,6 @@ class InformationFields():
         output indices); `apply()` reads the outputs of the source's last apply.  An output without weight is
         refused.'''
         self = cls.__new__(cls)
-        self._h = L._VP()
         self.traps = check_info_traps(traps, 'output')
         if labels is None:
             labels = getattr(source, 'days', None) if source.fields_kind == 'sites' else None
@@ -3928,45 +3223,31 @@ class InformationFields():
         return self
 
     def _setup(self, pop_model, inputs, nin):
-        self._lib = L.load()
-        self.pm = pop_model
+        self._attach(pop_model)
         self.ntrap = len(self.traps)
         self.rates = [t[1] for t in self.traps]
         self.ymax = [t[2] for t in self.traps]
         self.base = [sum(y + 3 for y in self.ymax[:e]) for e in range(self.ntrap)]
         self.nout = sum(y + 3 for y in self.ymax)           # the planes: the slots of an accumulator over them
         self.live = list(range(self.nout))
-        self.N = 2 * int(pop_model.rad_res) + 1
-        self.device = L.default_device() if pop_model.device is None else int(pop_model.device)
-        pitch = (self.N * self.N + 63) // 64 * 64
-        self.nbytes = (self.nout + 3 * self.ntrap) * pitch * 8      # the planes and three maps per trap
-        L.check(self._lib.ps_gain_create(self.device, self.N, int(nin), self.ntrap, L.p_i32(L.i32(inputs)),
-                                         L.p_f64(L.f64(self.rates)), L.p_i32(L.i32(self.ymax)), C.byref(self._h)))
+        self.nbytes = (self.nout + 3 * self.ntrap) * self.pitch * 8      # the planes and three maps per trap
+        self._create(int(nin), self.ntrap, L.p_i32(L.i32(inputs)), L.p_f64(L.f64(self.rates)),
+                     L.p_i32(L.i32(self.ymax)))
 
     def apply(self):
         '''The planes of the last evaluation of the model (enqueued on the solver's stream), or of the source's
         last apply (on the handle's stream); no host synchronisation; the planes of the previous apply are
         overwritten.'''
-        if self._source is not None:
-            L.check(getattr(self._lib, 'ps_gain_apply_' + self._source.fields_kind)(self._h, self._source._h))
-            return
-        pm = self.pm
-        _check_evaluated(pm, self.in_days, 'information fields')
-        stat, post = _day_scales(pm, self.in_days)
-        L.check(self._lib.ps_gain_apply(self._h, pm.solver._h, len(self.in_days), L.p_i32(self._kind),
-                                        L.p_i32(self._idx), L.p_f64(stat), L.p_f64(post), L.p_i32(self._delta),
-                                        NEGVAL))
+        self._read('apply', self._source)
 
     @property
     def applies(self):
         n = C.c_int64()
-        L.check(self._lib.ps_gain_info(self._h, None, None, None, None, C.byref(n)))
+        self._call('info', None, None, None, None, C.byref(n))
         return n.value
 
     def _e(self, e):
-        if not 0 <= int(e) < self.ntrap:
-            raise ValueError('trap %r of %d' % (e, self.ntrap))
-        return int(e)
+        return self._index(e, self.ntrap, 'trap')
 
     def plane_names(self, e):
         '''the names of trap e's planes: 'd0', 'p1' .. 'p{ymax}', 'tail' and 'h', in this order'''
@@ -3982,7 +3263,7 @@ class InformationFields():
     def plane(self, e, name):
         '''[N, N] float64: plane `name` ('d0', 'p1' .., 'tail', 'h') of trap e of the last apply'''
         out = np.empty((self.N, self.N), dtype=np.float64)
-        L.check(self._lib.ps_gain_fetch(self._h, self.plane_index(e, name), L.p_f64(out)))
+        self._call('fetch', self.plane_index(e, name), L.p_f64(out))
         return out
 
     def gather(self, rows, cols):
@@ -3991,7 +3272,7 @@ class InformationFields():
         if rows.size != cols.size:
             raise ValueError('%d rows and %d columns' % (rows.size, cols.size))
         out = np.zeros((self.nout, rows.size), dtype=np.float64)
-        L.check(self._lib.ps_gain_gather(self._h, rows.size, L.p_i32(rows), L.p_i32(cols), L.p_f64(out)))
+        self._call('gather', rows.size, L.p_i32(rows), L.p_i32(cols), L.p_f64(out))
         return out
 
     def finish(self, accumulator, scenario=None):
@@ -3999,9 +3280,9 @@ class InformationFields():
         SpreadSummary.for_projection(self) or, with the scenario's name, a ReweightedSummary.for_projection(self);
         on the device, no host synchronisation; `result` fetches them'''
         if scenario is None:
-            L.check(self._lib.ps_gain_finish_summary(self._h, accumulator._h))
+            self._call('finish_summary', accumulator._h)
         else:
-            L.check(self._lib.ps_gain_finish_wsum(self._h, accumulator._h, accumulator._j(scenario)))
+            self._call('finish_wsum', accumulator._h, accumulator._j(scenario))
 
     def result(self, e, what):
         '''[N, N] float64 of the last finish: what 'gain' (the mutual information in nats), 'entropy' (of the
@@ -4010,32 +3291,13 @@ class InformationFields():
         if what not in names:
             raise ValueError('%r is not one of %r' % (what, names))
         out = np.empty((self.N, self.N), dtype=np.float64)
-        L.check(self._lib.ps_gain_fetch_result(self._h, self._e(e), names.index(what), L.p_f64(out)))
+        self._call('fetch_result', self._e(e), names.index(what), L.p_f64(out))
         return out
 
     def profile(self, enable=None):
         '''HIP-event time of the apply launches: (total ms, launches); enable switches it'''
-        ms, n = C.c_double(), C.c_int64()
-        L.check(self._lib.ps_gain_prof(self._h, -1 if enable is None else int(bool(enable)), C.byref(ms),
-                                       C.byref(n)))
-        return ms.value, n.value
+        return self._profile(enable)
 
-    def close(self):
-        if self._h:
-            self._lib.ps_gain_destroy(self._h)
-            self._h = L._VP()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class InformationPosterior():
