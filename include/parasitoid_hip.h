@@ -1142,6 +1142,71 @@ int ps_range_fetch_mass(ps_range* a, int slot, uint64_t* Q, int32_t* E /* member
 int ps_range_prof(ps_range* a, int enable, double* add_ms, int64_t* adds, double* map_ms, int64_t* maps);
 void ps_range_destroy(ps_range* a);
 
+/* ---- patch maps: is the reached area one front or separate foci? ----
+ * (no reference counterpart.)  Every other map has lost the pairing of cells within a member; connectivity is a
+ * joint statement in space about one member's field.  Inputs: thresholds t_0 < ... < t_{K-1} (K in 1..4, each finite
+ * and > 0, strictly increasing), nslot slots (1..32) of N x N cells (N * N < 2^25), connectivity 4 or 8 on the grid
+ * (no wrap at the domain edge), one member m with integer weight w >= 1.  For every k and slot, every line a
+ * statement of its own:
+ *   v(c) = the value ps_summary_add adds for the slot (ps_record_value)
+ *   O = {c : v(c) >= t_k}
+ *   a patch is a connected component of O; its label is the smallest linear index row * N + col of its cells
+ *   the main patch is the patch with the most cells, among equals the one with the smallest label
+ *   per member, in add order (uint32 each): npatch;  cells = |O|;  main_cells;  main_label (0xffffffff where O is
+ *     empty);  sat_cells_max, the cells of the largest patch that is not the main one, 0 if there is none
+ *   main[k][slot][c] += w where c lies in the main patch;  sat[k][slot][c] += w where c is in O outside it
+ *   so main + sat is the weighted exceedance count of ps_excur;  an empty O gives an all-zero row (but for the
+ *     label) and counts nothing
+ * State (pitch as ps_summary): cnt[which][k][slot][pitch] uint32, 2 * K * nslot * pitch * 4 B (184.8 MB at R = 400,
+ * 18 days, K = 2); rows[member][k][slot][5] uint32, 20 B per member, threshold and slot, grown by doubling; the
+ * weights on the host.  Scratch: parent[k][slot][pitch] and size[k][slot][pitch] uint32 and one 64-bit key per plane
+ * -- all K * nslot planes of a member are in flight at once (plane on grid.y), which costs 8 B per cell and plane, as
+ * much again as the counts.  Every allocation is checked against the free device memory first: PS_ERR_OOM before it
+ * is made.  The labelling is union-find on parent: init (c in O, a NONE value outside), link (each cell of O joined
+ * to its occupied left and upper neighbours, with 8-connectivity also the upper-left and upper-right ones; a join is
+ * one compare-and-swap on a root, always from the larger root to the smaller, so parent[c] <= c throughout, every
+ * loop pass returns or strictly lowers an index and no thread waits for another), flatten (every cell gets its
+ * root, the patch's smallest index), sizes (integer adds on size[root] aggregated per wave; npatch and cells), pick
+ * (a 64-bit maximum of (size << 32) | (0xffffffff - label) over the roots), count (one writer per cell; the largest
+ * size among the other roots).  Integer atomics only and a canonical label: neither the order of adds, nor that of
+ * merges, nor the launch configuration, nor the order in which the device joins cells changes a bit; only the order
+ * of the members in the fetches follows the adds.  Every operation records an event the next one waits on,
+ * whichever stream it runs on (the solver's for add, the handle's own otherwise). */
+typedef struct ps_patch ps_patch;
+/* PS_ERR_BAD_ARG for thresholds not finite, not > 0, not strictly increasing, more than 4, a connectivity other than
+ * 4 or 8, slots outside 1..32 or N * N >= 2^25 */
+int ps_patch_create(int device, int N, int nslot, int nthr, const double* thr, int connectivity, ps_patch** out);
+/* room for `members` members' rows now (a growth synchronises; never shrinks) */
+int ps_patch_reserve(ps_patch* a, int64_t members);
+/* One member with weight >= 1 (arguments and refusals as ps_range_add; a total weight past 2^32 - 1 is refused): two
+ * small memsets and six launches on the solver's stream, every plane in each; no host synchronisation unless the
+ * rows have to grow.  Every descriptor is resolved first, so an add with a bad slot enqueues nothing. */
+int ps_patch_add(ps_patch* a, ps_solver* s, int nslot, const int32_t* kind, const int32_t* idx,
+                 const double* stat_scale, const double* post_scale, const int32_t* use_delta, double negval,
+                 uint32_t weight);
+/* The same for the current outputs of a projection or a release plan, as ps_range_add_project /
+ * ps_range_add_sites: slot e takes Y_e (nslot must equal nout), on the handle's stream. */
+int ps_patch_add_project(ps_patch* a, ps_project* p, uint32_t weight);
+int ps_patch_add_sites(ps_patch* a, ps_sites* p, uint32_t weight);
+/* dst += src: the counts by an integer plane add, src's member rows and weights appended after dst's (a device
+ * copy); same device, N, slots, thresholds and connectivity; src unchanged */
+int ps_patch_merge(ps_patch* dst, ps_patch* src);
+/* any pointer may be NULL; capacity: the members the rows hold room for; bytes: the device memory held now */
+int ps_patch_info(ps_patch* a, double* total_weight, int64_t* members, int64_t* capacity, int64_t* bytes);
+/* zero counts, W and members and drop the timings of ps_patch_prof; the rows keep their room */
+int ps_patch_reset(ps_patch* a);
+/* (double)cnt[which][k][slot] / (double)W, which 0: the posterior probability that the cell lies in the member's
+ * main patch, 1: in O outside it (synchronises).  PS_ERR_STATE before the first add, as the fetches below. */
+int ps_patch_prob(ps_patch* a, int k, int slot, int which, double* out /* N*N */);
+int ps_patch_fetch_counts(ps_patch* a, int k, int slot, int which, uint32_t* out /* N*N */);
+/* per member in add order the row of (k, slot) and the weight (any pointer may be NULL) */
+int ps_patch_fetch_members(ps_patch* a, int k, int slot, uint32_t* npatch, uint32_t* cells, uint32_t* main_cells,
+                           uint32_t* main_label, uint32_t* sat_cells_max, uint32_t* weights);
+/* measurement: HIP-event timing of the adds and the map launches, as ps_range_prof; while enabled every add and
+ * map keeps one event pair until ps_patch_reset or ps_patch_destroy */
+int ps_patch_prof(ps_patch* a, int enable, double* add_ms, int64_t* adds, double* map_ms, int64_t* maps);
+void ps_patch_destroy(ps_patch* a);
+
 #ifdef __cplusplus
 }
 #endif

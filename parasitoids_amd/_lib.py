@@ -306,6 +306,19 @@ SIGNATURES = {
     'ps_range_fetch_mass': (C.c_int, [_VP, C.c_int, C.POINTER(C.c_uint64), _I32P]),
     'ps_range_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P, _F64P, _I64P]),
     'ps_range_destroy': (None, [_VP]),
+    'ps_patch_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _F64P, C.c_int, C.POINTER(_VP)]),
+    'ps_patch_reserve': (C.c_int, [_VP, C.c_int64]),
+    'ps_patch_add': (C.c_int, [_VP, _VP, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P, C.c_double, C.c_uint32]),
+    'ps_patch_add_project': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_patch_add_sites': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_patch_merge': (C.c_int, [_VP, _VP]),
+    'ps_patch_info': (C.c_int, [_VP, _F64P, _I64P, _I64P, _I64P]),
+    'ps_patch_reset': (C.c_int, [_VP]),
+    'ps_patch_prob': (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, _F64P]),
+    'ps_patch_fetch_counts': (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32)]),
+    'ps_patch_fetch_members': (C.c_int, [_VP, C.c_int, C.c_int] + [C.POINTER(C.c_uint32)] * 6),
+    'ps_patch_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P, _F64P, _I64P]),
+    'ps_patch_destroy': (None, [_VP]),
 }
 
 _lib = None

@@ -50,6 +50,9 @@ count and the identity of the member (`InformationPosterior`): where a reading w
 highest-density region holding that share of their wasps contains the cell, and per member the region's level, cell
 count and integer mass (ps_range_*, csrc/ps_range.hip): the 50 % core and the 95 % range as probability maps and the
 posterior of their area -- the level is each member's own, so no map cut at an absolute density gives them.
+`PatchMaps` labels, on the device, the connected components of each member's set {v >= t} per threshold and day
+(ps_patch_*, csrc/ps_patch.hip) and keeps the weighted count of the members whose main patch, or another patch, holds
+the cell, and per member the number of patches and their sizes: is the reached area one front or separate foci?
 """
 import ctypes as C
 import json
@@ -975,6 +978,247 @@ def range_area(cells, weights, cell_area, levels=(0.05, 0.5, 0.95), day=None):
             'radius_quantiles': [float(np.sqrt(a / np.pi)) for a in q]}
 
 
+MAX_PATCH_THRESHOLDS = 4
+PATCH_WHICH = ('main', 'satellite')
+
+
+def check_patch_connectivity(connectivity):
+    '''4 or 8 as an int; ValueError otherwise'''
+    if isinstance(connectivity, bool) or connectivity not in (4, 8):
+        raise ValueError('patch connectivity must be 4 or 8, got %r' % (connectivity,))
+    return int(connectivity)
+
+
+def check_patches(patches, days=None):
+    '''the patches= argument of posterior_predictive -> (thresholds, connectivity, levels): a list of thresholds
+    (1..4, finite, > 0, strictly increasing), or dict(thresholds=[...], connectivity=8, levels=(0.05, 0.5, 0.95)),
+    the connectivity 4 (default) or 8 and the levels, each in (0, 1], those of the saved quantiles of the patch count
+    and of the areas; `days`, where given, by the rules of check_arrival_days; ValueError otherwise'''
+    connectivity, levels = 4, (0.05, 0.5, 0.95)
+    if isinstance(patches, dict):
+        unknown = set(patches) - {'thresholds', 'connectivity', 'levels'}
+        if unknown:
+            raise ValueError('patches: unknown keys %r' % (sorted(unknown),))
+        if 'thresholds' not in patches:
+            raise ValueError('patches: thresholds are needed')
+        connectivity = patches.get('connectivity', connectivity)
+        levels = patches.get('levels', levels)
+        patches = patches['thresholds']
+    try:
+        thr = [float(t) for t in patches]
+    except (TypeError, ValueError):
+        raise ValueError('patch thresholds must be a list of numbers, got %r' % (patches,))
+    if not 1 <= len(thr) <= MAX_PATCH_THRESHOLDS:
+        raise ValueError('%d patch thresholds; 1..%d are kept' % (len(thr), MAX_PATCH_THRESHOLDS))
+    if not all(np.isfinite(t) and t > 0.0 for t in thr):
+        raise ValueError('every patch threshold must be finite and > 0: %r' % (thr,))
+    if any(b <= a for a, b in zip(thr, thr[1:])):
+        raise ValueError('patch thresholds must be strictly increasing: %r' % (thr,))
+    connectivity = check_patch_connectivity(connectivity)
+    levels = check_levels(levels)
+    if days is not None:
+        check_arrival_days(days)
+    return thr, connectivity, levels
+
+
+def patch_number(npatch, weights, levels=(0.05, 0.5, 0.95), day=None):
+    '''the posterior of the patch count from the members' counts and integer weights, as PatchMaps.number returns
+    it (no device): {'day', 'mean', 'p_fragmented' = P(npatch >= 2), 'p_empty' = P(npatch = 0), 'quantiles'}'''
+    levels = check_levels(levels)
+    n = np.asarray(npatch).astype(np.int64)
+    w = np.asarray(weights).astype(np.int64)
+    W = int(w.sum())
+    if W == 0:
+        raise ValueError('nothing accumulated')
+    return {'day': day, 'mean': float(int((n * w).sum())) / float(W),
+            'p_fragmented': float(int(w[n >= 2].sum())) / float(W), 'p_empty': float(int(w[n == 0].sum())) / float(W),
+            'quantiles': [float(weighted_lower_quantile(n, w, p)) for p in levels]}
+
+
+def patch_satellite_share(cells, main_cells, weights):
+    '''the weighted mean, over the members that hold any cell, of the share of their occupied cells that lies
+    outside the main patch; None where no member holds a cell'''
+    n = np.asarray(cells).astype(np.int64)
+    m = np.asarray(main_cells).astype(np.int64)
+    w = np.asarray(weights).astype(np.int64)
+    live = n > 0
+    if not live.any():
+        return None
+    share = (n[live] - m[live]) / n[live].astype(np.float64)
+    return float((share * w[live]).sum() / float(int(w[live].sum())))
+
+
+class PatchMaps(_Accumulator):
+    '''Whether the area `pop_model`'s members reach is one front or separate foci: for thresholds t_0 < ... <
+    t_{K-1} (1..4, finite, > 0) and the model days `days` (strictly increasing, at most 32, default all) the
+    patches of each member's set {v >= t_k}, its connected components under `connectivity` 4 or 8 (no wrap at the
+    domain edge).  The main patch is the one with the most cells, among equals the one whose smallest linear index
+    row * N + col (its label) is smallest -- not the one at the release point.  On the device per (k, day) the
+    weighted count of the members whose main patch holds the cell ('main') and of those that hold it in another
+    patch ('satellite'), and per member the number of patches, the cells of the set, of the main patch and of the
+    largest other patch, and the main patch's label (ps_patch_*; the statements are those of
+    include/parasitoid_hip.h, restated in tests/patch_ref.py).  main + satellite is ExcursionMaps.counts.  Every
+    number is an integer and the label canonical: the order of adds and merges changes no bit.'''
+    _prefix, _noun, _prof_pairs = 'ps_patch', 'patch maps', 2
+    _info_types = (C.c_double, C.c_int64, C.c_int64, C.c_int64)      # weight, members, capacity, bytes
+
+    def __init__(self, pop_model, thresholds, days=None, connectivity=4):
+        self.thresholds, self.connectivity, _lv = check_patches(dict(thresholds=thresholds, connectivity=connectivity))
+        self._setup(pop_model, None, check_arrival_days(range(len(pop_model.days)) if days is None else days))
+
+    @classmethod
+    def for_projection(cls, source, thresholds, connectivity=4):
+        '''Patch maps of the outputs of `source` (a ReleaseSites or a Projection), the slots its outputs that
+        carry weight in ascending order: `add(weight)` accumulates the outputs of its last `apply()`.  `days` holds
+        the output labels -- the plan's output days, or the projection's output indices.'''
+        self = cls.__new__(cls)
+        self.thresholds, self.connectivity, _lv = check_patches(dict(thresholds=thresholds, connectivity=connectivity))
+        self._setup(source.pm, source, check_arrival_days(_output_labels(source)))
+        return self
+
+    def _setup(self, pop_model, projection, days):
+        self._attach(pop_model)
+        self._set_source(projection, days)
+        self._create(len(self.days), len(self.thresholds), L.p_f64(L.f64(self.thresholds)), self.connectivity)
+
+    def reserve(self, n):
+        '''room for n members' rows now, so that no add has to grow them'''
+        self._call('reserve', int(n))
+
+    def add(self, weight=1):
+        '''Accumulate the last evaluation of the model with integer weight >= 1 (enqueued on the solver's stream;
+        no host synchronisation unless the member rows grow).  On a projection or a plan: its last apply, on the
+        handle's stream.'''
+        self._add(weight)
+
+    def merge(self, other):
+        '''self += other (same device, domain, days, thresholds and connectivity); other's members follow self's'''
+        if list(other.days) != self.days:
+            raise ValueError('patch maps over different days')
+        self._call('merge', other._h)
+
+    @property
+    def capacity(self):
+        '''the members the rows hold room for'''
+        return self._info()[2]
+
+    @property
+    def nbytes(self):
+        '''the device memory the handle holds now'''
+        return self._info()[3]
+
+    @staticmethod
+    def _which(which):
+        if which not in PATCH_WHICH:
+            raise ValueError('which must be one of %r, got %r' % (PATCH_WHICH, which))
+        return PATCH_WHICH.index(which)
+
+    def counts(self, k, day, which):
+        '''[N, N] uint32: the weight of the members whose main patch at t_k on `day` holds the cell ('main'), or
+        that hold it in another patch ('satellite')'''
+        out = np.empty((self.N, self.N), dtype=np.uint32)
+        self._call('fetch_counts', self._k(k), self._slot_of(day), self._which(which),
+                   out.ctypes.data_as(C.POINTER(C.c_uint32)))
+        return out
+
+    def prob(self, k, day, which):
+        '''[N, N] float64: counts / W, the posterior probability of the same'''
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        self._call('prob', self._k(k), self._slot_of(day), self._which(which), L.p_f64(out))
+        return out
+
+    def _members(self, k, day):
+        '''(npatch, cells, main_cells, main_label, sat_cells_max, weights), [members] uint32 each, in add order'''
+        out = [np.empty(self.members, dtype=np.uint32) for _ in range(6)]
+        self._call('fetch_members', self._k(k), self._slot_of(day),
+                   *[a.ctypes.data_as(C.POINTER(C.c_uint32)) for a in out])
+        return tuple(out)
+
+    @property
+    def weights(self):
+        '''[members] int64: the members' weights in add order'''
+        return self._members(0, self.days[0])[5].astype(np.int64)
+
+    def patches(self, k, day):
+        '''[members] int64 in add order: the number of patches of {v >= t_k} on `day`'''
+        return self._members(k, day)[0].astype(np.int64)
+
+    def cells(self, k, day):
+        '''[members] int64 in add order: the cells of {v >= t_k} on `day`'''
+        return self._members(k, day)[1].astype(np.int64)
+
+    def main_cells(self, k, day):
+        '''[members] int64 in add order: the cells of the main patch'''
+        return self._members(k, day)[2].astype(np.int64)
+
+    def main_label(self, k, day):
+        '''[members] int64 in add order: the main patch's smallest linear index row * N + col, -1 where the set
+        is empty'''
+        lab = self._members(k, day)[3]
+        return np.where(lab == 0xffffffff, -1, lab.astype(np.int64))
+
+    def largest_satellite(self, k, day):
+        '''[members] int64 in add order: the cells of the largest patch other than the main one, 0 without one'''
+        return self._members(k, day)[4].astype(np.int64)
+
+    def number(self, k, day, levels=(0.05, 0.5, 0.95)):
+        '''The posterior of the patch count at t_k on `day`: {'day', 'mean', 'p_fragmented', 'p_empty',
+        'quantiles'} (patch_number): the weighted mean, P(npatch >= 2), P(npatch = 0) and the weighted lower
+        quantiles (weighted_lower_quantile) at `levels`.'''
+        rows = self._members(k, day)
+        return patch_number(rows[0], rows[5], levels, day)
+
+    def area(self, k, day, which='main', levels=(0.05, 0.5, 0.95)):
+        '''The posterior of the area of the main patch ('main'), of the occupied cells outside it ('satellite') or
+        of the whole set ('all') at t_k on `day`, in m^2, as RangeMaps.area (range_area).'''
+        if which not in PATCH_WHICH + ('all',):
+            raise ValueError('which must be one of %r, got %r' % (PATCH_WHICH + ('all',), which))
+        rows = self._members(k, day)
+        n, m = rows[1].astype(np.int64), rows[2].astype(np.int64)
+        return range_area({'main': m, 'satellite': n - m, 'all': n}[which], rows[5], self.cell_area, levels, day)
+
+    def profile(self, enable=None):
+        '''HIP-event time of the adds and the map launches: (add ms, adds, map ms, map launches); enable
+        switches it'''
+        return self._profile(enable)
+
+
+def save_patches(outfile, pat, levels=(0.05, 0.5, 0.95)):
+    '''outfile.npz of one PatchMaps through save_maps: per day of the maps, under the label `{day}`, the CSR triplets
+    `{day}_pmain{k}_*` and `{day}_psat{k}_*` of the probability that the cell lies in the member's main patch, or in
+    its set outside it; the members' rows `patch_npatch`, `patch_cells`, `patch_main_cells`, `patch_sat_cells_max`
+    (uint32) and `patch_main_label` (int64, -1 where the set is empty) [thresholds, days, members],
+    `patch_weights` [members], `patch_thresholds`, `patch_connectivity` and `patch_days` -> its block for the json:
+    thresholds, connectivity, days, levels, members, weight, cell area and per threshold and day `p_fragmented`,
+    the mean patch count `mean_patches`, its quantiles, `p_empty` and `satellite_share`, the mean share of the
+    occupied cells that lies in satellites (null where no member holds a cell)'''
+    levels = check_levels(levels)
+    nk = len(pat.thresholds)
+    maps, number = [], [[] for _ in range(nk)]
+    rows = [[pat._members(k, d) for d in pat.days] for k in range(nk)]
+    for di, d in enumerate(pat.days):
+        day_maps = []
+        for k in range(nk):
+            day_maps += [('_pmain%d' % k, pat.prob(k, d, 'main')), ('_psat%d' % k, pat.prob(k, d, 'satellite'))]
+            r = rows[k][di]
+            rec = patch_number(r[0], r[5], levels, d)
+            number[k].append({'day': d, 'p_fragmented': rec['p_fragmented'], 'mean_patches': rec['mean'],
+                              'quantiles': rec['quantiles'], 'p_empty': rec['p_empty'],
+                              'satellite_share': patch_satellite_share(r[1], r[2], r[5])})
+        maps.append((d, day_maps))
+    extra = {}
+    for f, name in enumerate(('npatch', 'cells', 'main_cells', 'main_label', 'sat_cells_max')):
+        a = np.array([[x[f] for x in row] for row in rows], dtype=np.uint32)
+        extra['patch_' + name] = np.where(a == 0xffffffff, -1, a.astype(np.int64)) if name == 'main_label' else a
+    extra.update({'patch_weights': np.asarray(rows[0][0][5], dtype=np.uint32),
+                  'patch_thresholds': np.asarray(pat.thresholds, dtype=np.float64),
+                  'patch_connectivity': np.asarray(pat.connectivity), 'patch_days': np.asarray(pat.days)})
+    save_maps(outfile, maps, extra)
+    return {'thresholds': list(pat.thresholds), 'connectivity': pat.connectivity, 'days': list(pat.days),
+            'levels': levels, 'members': pat.members, 'total_weight': pat.total_weight, 'cell_area': pat.cell_area,
+            'number': number}
+
+
 def check_weights(weights, nin=None, zero_rows=False):
     '''A projection's weight matrix as a float64 [nout, nin] array, by the rules of ps_project_create: 1..32
     outputs, 1..32 inputs (nin if given), every weight finite and >= 0, and no row of all zeros unless
@@ -1153,10 +1397,10 @@ def exposure_plan(exposure, ndays=None):
 # 'apply' is the source's own.  The three orders differ for no better reason than the history of the maps.
 FEED_ORDER = {
     'days': ('summary', 'core_range', 'reweight', 'catch', 'information', 'excursion', 'mc_error', 'sensitivity',
-             'histogram', 'arrival', 'peak'),
+             'histogram', 'arrival', 'peak', 'patches'),
     'projection': ('apply', 'summary', 'reweight', 'mc_error', 'sensitivity', 'histogram', 'catch'),
     'sites': ('apply', 'summary', 'reweight', 'mc_error', 'sensitivity', 'histogram', 'arrival', 'peak', 'excursion',
-              'core_range', 'catch', 'information'),
+              'core_range', 'catch', 'information', 'patches'),
     'compare': ('apply', 'contrast'),
 }
 
@@ -1200,6 +1444,7 @@ FEED = {
     'information': lambda acc, fs, m: acc.add(m.length, m.lam),
     'mc_error': _add_halves,
     'contrast': _add_length,
+    'patches': _add_length,
 }
 ACCUMULATORS = tuple(name for name in FEED if name != 'apply')
 
@@ -1263,6 +1508,7 @@ BUILD = {
     'information': _build_information,
     'mc_error': _build_mc_error,
     'contrast': lambda fs, q: PlanContrast(fs._against, fs._source, q.thresholds),
+    'patches': lambda fs, q: q.pt_thr and fs._over(PatchMaps, (q.pt_thr, fs._days, q.pt_conn), (q.pt_thr, q.pt_conn)),
 }
 
 
@@ -1308,7 +1554,7 @@ class _FieldSet():
             setattr(self, name, acc)
             if name == 'summary' and self._kind == 'days':
                 self._days = acc.days
-            if name in ('excursion', 'core_range') and acc is not None:
+            if name in ('excursion', 'core_range', 'patches') and acc is not None:
                 acc.reserve(nruns)
         return self
 
@@ -1379,14 +1625,15 @@ class ProjectedMaps(_FieldSet):
     `catch`: the CatchPosterior over the outputs (None unless asked for), whose traps name an output label.
     `information`: the InformationPosterior over the outputs (None unless asked for), likewise.  `core_range`: the
     RangeMaps.for_projection of a release plan's outputs (None unless asked for), whose maps take the output day.
+    `patches`: the PatchMaps.for_projection of a release plan's outputs (None unless asked for), likewise.
     `merge` and `close` take every accumulator there is (ACCUMULATORS).'''
 
     def __init__(self, weights, in_days, labels, summary, histogram=None, arrival=None, plan=None,
                  sensitivity=None, mc_error=None, peak=None, excursion=None, reweight=None, catch=None,
-                 information=None, core_range=None):
+                 information=None, core_range=None, patches=None):
         super().__init__(summary=summary, histogram=histogram, arrival=arrival, sensitivity=sensitivity,
                          mc_error=mc_error, peak=peak, excursion=excursion, reweight=reweight, catch=catch,
-                         information=information, core_range=core_range)
+                         information=information, core_range=core_range, patches=patches)
         self.weights = weights
         self.in_days = in_days
         self.labels = labels
@@ -3740,13 +3987,16 @@ class PredictiveResult():
     InformationPosterior of the described traps over the model's day fields, None where not asked for (the plan then
     carries an `information` of its own); `core_range`: the RangeMaps over the summary's days and
     `core_range_levels` the consensus levels of its saved regions, both None where not asked for (the plan then
-    carries a `core_range` of its own).'''
+    carries a `core_range` of its own); `patches`: the PatchMaps over the summary's days and `patch_levels` the
+    levels of its saved quantiles, both None where not asked for (the plan then carries a `patches` of its own).'''
 
     def __init__(self, summary, rows, evaluations, failed, seconds, runs, observations, provenance, days,
                  histogram=None, quantiles=None, arrival=None, arrival_levels=None, emergence=None, exposure=None,
                  sites=None, sensitivity=None, contrast=None, compare_plan=None, mc_error=None, mc_plan=None,
                  peak=None, excursion=None, excursion_levels=None, reweight=None, reweight_info=None, catch=None,
-                 information=None, core_range=None, core_range_levels=None):
+                 information=None, core_range=None, core_range_levels=None, patches=None, patch_levels=None):
+        self.patches = patches
+        self.patch_levels = patch_levels
         self.catch = catch
         self.information = information
         self.core_range = core_range
@@ -3828,6 +4078,8 @@ class PredictiveResult():
         with the traps as given.
         Core-range maps go into outfile_range.npz (save_range; those of a release plan into
         outfile_sites_range.npz), their block under `predictive.core_range` (`predictive.sites.core_range`).
+        Patch maps go into outfile_patch.npz (save_patches; those of a release plan into outfile_sites_patch.npz),
+        their block under `predictive.patches` (`predictive.sites.patches`).
         -> (npz path, json path)'''
         s = self.summary
         if s is None:
@@ -3916,6 +4168,11 @@ class PredictiveResult():
             if pr.core_range is not None:
                 meta['predictive'][name]['core_range'] = save_range('%s_%s_range' % (outfile, name), pr.core_range,
                                                                     self.core_range_levels)
+            if pr.patches is not None:
+                meta['predictive'][name]['patches'] = save_patches('%s_%s_patch' % (outfile, name), pr.patches,
+                                                                   self.patch_levels)
+        if self.patches is not None:
+            meta['predictive']['patches'] = save_patches('%s_patch' % outfile, self.patches, self.patch_levels)
         if self.core_range is not None:
             meta['predictive']['core_range'] = save_range('%s_range' % outfile, self.core_range,
                                                           self.core_range_levels)
@@ -4039,13 +4296,13 @@ def _check_request(q):
     '''Everything of posterior_predictive's arguments (q: a namespace of them) that can fail before any evaluation,
     in a fixed order -- of two bad arguments the earlier one is reported.  -> q, with the checked plans beside the
     arguments: cr_frac / cr_levels, in_plan, ct_plan, rw_plan / rw_names, ex_thr / ex_levels, pk_thr / pk_levels,
-    mc_batches, mc_b / mc_halves, s_names, levels, a_thr / a_levels, plans [(name, W, in_days, labels)], site_plan,
+    mc_batches, mc_b / mc_halves, pt_thr / pt_conn / pt_levels, s_names, levels, a_thr / a_levels, plans [(name, W, in_days, labels)], site_plan,
     cmp_plan, the loaded chains `prepared` [(rows, runs, model columns, observation columns, source)], `pms` (the
     models) and want_obs.'''
     pm0 = (q.pop_model[0] if q.pop_model else None) if isinstance(q.pop_model, (list, tuple)) else q.pop_model
     days, thresholds = q.days, q.thresholds
     q.cr_frac = q.cr_levels = q.in_plan = q.ct_plan = q.rw_plan = q.ex_thr = q.ex_levels = None
-    q.pk_thr = q.pk_levels = q.mc_batches = None
+    q.pk_thr = q.pk_levels = q.mc_batches = q.pt_thr = q.pt_conn = q.pt_levels = None
 
     def ndays0():                     # the model is touched only where an option needs it
         return None if pm0 is None else len(pm0.days)
@@ -4151,6 +4408,12 @@ def _check_request(q):
         check_arrival_days(range(len(q.pms[0].days)))
     if q.evaluate is None:            # projections past the model's days
         q.plans = [(name,) + plan(arg, len(q.pms[0].days)) for name, arg, plan in wanted]
+    if q.patches is not None and q.patches is not False:       # after every other check
+        if q.evaluate is not None:
+            raise ValueError('patches= needs the device: not with evaluate=')
+        q.pt_thr, q.pt_conn, q.pt_levels = check_patches(q.patches, days)
+        if days is None:
+            check_arrival_days(range(len(q.pms[0].days)))
     return q
 
 
@@ -4184,7 +4447,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                          cell_area=None, seed=0, evaluate=None, quantiles=None, bins=DEFAULT_BINS, edges=None,
                          arrival=None, arrival_levels=(0.05, 0.5, 0.95), emergence=None, exposure=None, sites=None,
                          sensitivity=None, compare=None, mc_error=None, peak=None, excursion=None, reweight=None,
-                         catch=None, information=None, core_range=None):
+                         catch=None, information=None, core_range=None, patches=None):
     '''Posterior predictive spread of one or more chains (`Sampler.save` files or (trace, names) pairs). Burn and
     thin apply per chain; consecutive rows with identical model parameters are one evaluation weighted by the
     run's length.
@@ -4308,7 +4571,19 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         chain order into `core_range` (`core_range_levels`: the consensus levels of its saved regions); with
         sites= the plan gets a RangeMaps.for_projection of its own outputs (`sites.core_range`). Emergence and
         exposure get none here (RangeMaps.for_projection takes them); sensitivity, contrast, Monte Carlo error and
-        reweighting of these maps are not computed. Without core_range= no call is added and `core_range` is None.'''
+        reweighting of these maps are not computed. Without core_range= no call is added and `core_range` is None.
+
+    patches: thresholds [t_0, ...] (1..4, finite, > 0, strictly increasing) or dict(thresholds=[...],
+        connectivity=8, levels=(0.05, 0.5, 0.95)) (check_patches; not with evaluate=; bad arguments fail before any
+        evaluation, after every other argument's): per member the connected components of {v >= t_k} under 4-
+        (default) or 8-connectivity -- is the reached area one front or separate foci? Each chain then also fills
+        one PatchMaps over the summary's days (strictly increasing, at most 32), reserved to the chain's number of
+        runs and fed the run's weight last, merged in chain order into `patches` (`patch_levels`: the levels of
+        its saved quantiles); with sites= the plan gets a PatchMaps.for_projection of its own outputs
+        (`sites.patches`). Emergence and exposure get none here (PatchMaps.for_projection takes them);
+        sensitivity, contrast, Monte Carlo error and reweighting of these maps are not computed. The main patch is
+        the largest one, not the one at the release point. Without patches= no call is added and `patches` is
+        None.'''
     q = types.SimpleNamespace(**locals())
     t0 = time.perf_counter()
     _check_request(q)                 # bad arguments fail before any evaluation
@@ -4407,7 +4682,8 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         mc_plan={'batches': q.mc_batches, 'batch_weight': q.mc_b, 'sequences': 2 * nch} if q.mc_b else None,
         peak=day.peak, excursion=day.excursion, excursion_levels=q.ex_levels if q.ex_thr else None,
         reweight=day.reweight, reweight_info=rw_info, catch=day.catch, information=day.information,
-        core_range=day.core_range, core_range_levels=q.cr_levels if q.cr_frac else None)
+        core_range=day.core_range, core_range_levels=q.cr_levels if q.cr_frac else None,
+        patches=day.patches, patch_levels=q.pt_levels if q.pt_thr else None)
     if day.information is not None:   # the stated convention: past cap / 2 the ensemble bounds the map
         warn_information(day.information)
         if 'sites' in merged:

@@ -24,7 +24,11 @@ regions and areas, each in (0.5, 1]) -- saved as PREFIX_excur.npz (and, with --s
 plan); with --core-range also the core-range maps -- per listed mass fraction and day the probability that a cell lies
 in the member's own highest-density region holding that share of its wasps, 0.5 the core and 0.95 the range
 (--core-range-levels: the consensus levels of the saved regions' areas, each in (0, 1]) -- saved as PREFIX_range.npz
-(and, with --sites, PREFIX_sites_range.npz for the plan); with --reweight / --reweight-file also the maps under new observations without a new chain -- up to four
+(and, with --sites, PREFIX_sites_range.npz for the plan); with --patches also the patch maps -- per listed density
+and day the probability that a cell lies in the member's main patch (the largest connected component of the cells at
+or above the density) or in a satellite, and the posterior of the patch count (--patch-connectivity 4 or 8,
+--patch-levels: the levels of the saved quantiles) -- saved as PREFIX_patch.npz (and, with --sites,
+PREFIX_sites_patch.npz for the plan); with --reweight / --reweight-file also the maps under new observations without a new chain -- up to four
 named scenarios, each a list of probe observations 'east,north,day,kind,rate[,n]' (kind: count with the number
 found n, none, found; rate: the expected number found per wasp in the cell) or a .npy file of one log-weight per
 chain row after burn and thin (several chains: concatenated in chain order), by importance reweighting of the
@@ -47,6 +51,7 @@ Without --chain a short chain is sampled first (--samples) and saved next to --o
         [--compare-sites 'E,N,AMOUNT[,LAG];...'] [--peak 1,10] [--peak-levels 0.05,0.5,0.95]
         [--excursion 1,10] [--excursion-levels 0.9,0.95]
         [--core-range 0.5,0.95] [--core-range-levels 0.5,0.9]
+        [--patches 1,10] [--patch-connectivity 8] [--patch-levels 0.05,0.5,0.95]
         [--reweight 'NAME:east,north,day,kind,rate[,n];...'] [--reweight-file NAME=weights.npy]
         [--catch 'DAY,RATE[,N];...'] [--catch-levels 0.5,0.95] [--catch-emergence 'OBSDAY,RATE[,N];...']
         [--information 'DAY,RATE[,YMAX];...']
@@ -145,6 +150,10 @@ def main():
                                                      '0.5,0.95 (default: off)')
     ap.add_argument('--core-range-levels', default='0.5,0.9',
                     help='consensus levels in (0, 1] of the saved core-range areas (with --core-range)')
+    ap.add_argument('--patches', default='', help='patch maps at the listed densities, e.g. 1,10 (default: off)')
+    ap.add_argument('--patch-connectivity', type=int, default=4, help='4 or 8 neighbours (with --patches)')
+    ap.add_argument('--patch-levels', default='0.05,0.5,0.95',
+                    help='levels in (0, 1] of the saved patch-count and area quantiles (with --patches)')
     ap.add_argument('--catch', default='', help="traps 'DAY,RATE[,N];...': per cell the probability that a trap of "
                     'effort RATE on model day DAY catches at least N (default 1) (default: off)')
     ap.add_argument('--catch-levels', default='0.5,0.95', help='levels of the catch maps (with --catch)')
@@ -200,6 +209,13 @@ def main():
         core_range = dict(fractions=[float(t) for t in args.core_range.split(',') if t.strip()],
                           levels=[float(q) for q in args.core_range_levels.split(',') if q.strip()])
         check_core_range(core_range)
+    patches = None
+    if args.patches:                     # as do bad --patches thresholds, connectivity or levels
+        from parasitoids_amd.predictive import check_patches
+        patches = dict(thresholds=[float(t) for t in args.patches.split(',') if t.strip()],
+                       connectivity=args.patch_connectivity,
+                       levels=[float(q) for q in args.patch_levels.split(',') if q.strip()])
+        check_patches(patches)
     emergence = exposure = None
     if args.emergence:
         cday, _, obs = args.emergence.partition(':')
@@ -287,7 +303,8 @@ def main():
                                **({'reweight': reweight} if reweight else {}),
                                **({'catch': catch} if catch else {}),
                                **({'information': information} if information else {}),
-                               **({'core_range': core_range} if core_range else {}))
+                               **({'core_range': core_range} if core_range else {}),
+                               **({'patches': patches} if patches else {}))
     dt = time.perf_counter() - t0
     # accumulate-kernel time: the same members once more with HIP events around every add
     from parasitoids_amd.predictive import (ArrivalMaps, ExcursionMaps, MonteCarloError, PeakMaps, PlanContrast, Projection,
@@ -545,6 +562,12 @@ def main():
         out['range_maps_ms_total'] = round(res.core_range.profile()[2], 3)
         out['range_bytes'] = res.core_range.nbytes
         out['outputs'] += ['%s_range.npz' % args.out] + (['%s_sites_range.npz' % args.out] if sites else [])
+    if patches:
+        out['patch_thresholds'] = patches['thresholds']
+        out['patch_connectivity'] = patches['connectivity']
+        out['patch_members'] = res.patches.members
+        out['patch_bytes'] = res.patches.nbytes
+        out['outputs'] += ['%s_patch.npz' % args.out] + (['%s_sites_patch.npz' % args.out] if sites else [])
     if sens:
         x_per = x_ms / max(x_launches, 1)
         out['sensitivity_add_ms_per_member'] = round(x_per, 4)
@@ -599,7 +622,7 @@ def main():
     if res.mc_error is not None:
         res.mc_error.close()
     for pr in (res.emergence, res.exposure, res.sites, res.contrast, res.peak, res.excursion, res.catch, res.information,
-               res.core_range):
+               res.core_range, res.patches):
         if pr is not None:
             pr.close()
     for p in pms:
