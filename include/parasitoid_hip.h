@@ -71,6 +71,17 @@ int ps_device_count(void);             /* < 0 on error */
 const char* ps_last_error(void);
 /* device properties for reports: name[<=n], CU count, total HBM bytes */
 int ps_device_info(int device, char* name, int n, int* cus, int64_t* hbm_bytes);
+/* The unit list of the persistent forward row pass over kernel batches (no device needed): on a torus
+ * of P rows whose day kernels wrap around row 0 with centre M (source row s sits at torus row
+ * (s - M) mod P), a unit is np consecutive row pairs and is live when one of its rows holds a source
+ * row of its entry's inclusive range ranges[2 d] .. ranges[2 d + 1] (empty when lo > hi).  Writes entry
+ * and unit index of the first `cap` live units in list order; returns their total number, < 0 on
+ * bad arguments. */
+int ps_row_live_units(int P, int M, int np, int nd, const int32_t* ranges, int32_t* day, int32_t* unit, int cap);
+/* Row pairs per workgroup (np) of the register-resident forward row kernels at FFT size fft_len, and whether
+ * kernel batches of the full-column pipeline go to the persistent kernel there (no device needed); < 0 when
+ * the size has no register-resident kernels. */
+int ps_row_fwd_info(int fft_len, int* np, int* persistent);
 
 /* ---- solver: replaces class cuda_lib.CudaSolve (cuda_lib.py:16-221) and the
  *      CPU primitives CalcSol.fft2/fftconv2/ifft2/back_solve (CalcSol.py:11-109) */

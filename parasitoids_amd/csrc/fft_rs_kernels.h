@@ -4,6 +4,7 @@
 #pragma once
 #include "fft_kernels.h"
 #include "fft_rs.h"
+#include "row_live_units.h"
 #include <type_traits>
 
 
@@ -915,11 +916,70 @@ __global__ void __launch_bounds__((2 * Rs<R1, R2, R3>::NTHR)) k_row_inv_rs2(RowI
 // parts, then imaginary parts), then coalesced 16-byte stores of the half spectra (k <= L/2).
 // Row pairs without a live source row are neither transformed nor written (the column pass
 // is told the same live-row window), exactly like k_row_fwd.
+//
+// The work on one row pair, shared by the one-shot kernel (k_row_fwd_rs) and the persistent one
+// (k_row_fwd_rsp) so that both round alike by construction:
+//   rs_fwd_load    the first stage's loads, always in bounds (pa / pb show at row 0 for a dead row), zero
+//                  outside the column map and for a dead row
+//   rs_fwd_finish  three stages, the mirrored-element exchange, the stores of the half spectra (`live`
+//                  false: none -- a dead pair that shares a persistent workgroup's unit with a live one)
+template <class S, int R1>
+__device__ __forceinline__ void rs_fwd_load(cplx* x, const double* pa, const double* pb, const SrcMap& cmap, int j, bool la, bool lb) {
+#pragma unroll
+  for (int q = 0; q < R1; ++q) {
+    const int sc = src_map(cmap, j + q * S::T1);
+    const bool ok = sc >= 0;
+    const int c = ok ? sc : 0;
+    const double va = pa[c], vb = pb[c];          // always in bounds; masked below
+    x[q] = make_double2((ok && la) ? va : 0.0, (ok && lb) ? vb : 0.0);
+  }
+}
+template <class S, int R1, int R2, int R3>
+__device__ __forceinline__ void rs_fwd_finish(cplx* x, double* ex, const int j, const cplx w2, const cplx w3,
+                                              cplx* da, cplx* db, const int64_t kst, const bool live, const bool hasb) {
+  constexpr int L = S::L;
+  if (j < S::T1) bfly<R1, PS_FWD>(x);
+  rs_tail<S, R1, R2, R3, PS_FWD>(x, ex, j, w2, w3);
+  // mirrored elements through LDS: Z_k of thread j sits at word k = j + q T3
+  cplx zm[R3 / 2 + 1];
+  constexpr int NQ = R3 / 2 + 1;   // slots q with j + q T3 <= L/2 for some j
+  __syncthreads();
+  if (j < S::T3) {
+#pragma unroll
+    for (int q = 0; q < R3; ++q) ex[j + q * S::T3] = x[q].x;
+  }
+  __syncthreads();
+  if (j < S::T3) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int k = j + q * S::T3;
+      zm[q].x = ex[k ? L - k : 0];
+    }
+  }
+  __syncthreads();
+  if (j < S::T3) {
+#pragma unroll
+    for (int q = 0; q < R3; ++q) ex[j + q * S::T3] = x[q].y;
+  }
+  __syncthreads();
+  if (j < S::T3 && live) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int k = j + q * S::T3;
+      zm[q].y = ex[k ? L - k : 0];
+      if (k <= L / 2) {
+        const cplx zk = x[q];
+        da[k * kst] = make_double2(0.5 * (zk.x + zm[q].x), 0.5 * (zk.y - zm[q].y));
+        if (hasb) db[k * kst] = make_double2(0.5 * (zk.y + zm[q].y), -0.5 * (zk.x - zm[q].x));
+      }
+    }
+  }
+}
+
 template <int R1, int R2, int R3, int NP>
 __global__ void __launch_bounds__((Rs<R1, R2, R3>::NTHR * NP)) k_row_fwd_rs(RowFwdArgs a) {
   using S = Rs<R1, R2, R3>;
   using Y = RsInvLds<R1, R2, R3>;
-  constexpr int L = S::L;
   if (pred_skip(a.pred)) return;
   const int half = threadIdx.x / S::NTHR;
   int unit = (int)blockIdx.x;
@@ -973,6 +1033,8 @@ __global__ void __launch_bounds__((Rs<R1, R2, R3>::NTHR * NP)) k_row_fwd_rs(RowF
   if (j < S::T1) {
     const double* pa = src + (int64_t)(sa >= 0 ? sa : 0) * a.src_ld;
     const double* pb = src + (int64_t)(sb >= 0 ? sb : 0) * a.src_ld;
+    // (= rs_fwd_load, written out: through the function call the compiler turns the map's selects into
+    // branches here, 2 us more on the state's 16 us row pass at 5184)
 #pragma unroll
     for (int q = 0; q < R1; ++q) {
       const int sc = src_map(cmap, j + q * S::T1);
@@ -981,41 +1043,102 @@ __global__ void __launch_bounds__((Rs<R1, R2, R3>::NTHR * NP)) k_row_fwd_rs(RowF
       const double va = pa[c], vb = pb[c];          // always in bounds; masked below
       x[q] = make_double2((ok && sa >= 0) ? va : 0.0, (ok && sb >= 0) ? vb : 0.0);
     }
-    bfly<R1, PS_FWD>(x);
   }
-  rs_tail<S, R1, R2, R3, PS_FWD>(x, ex, j, w2, w3);
-  // mirrored elements through LDS: Z_k of thread j sits at word k = j + q T3
-  cplx zm[R3 / 2 + 1];
-  constexpr int NQ = R3 / 2 + 1;   // slots q with j + q T3 <= L/2 for some j
-  __syncthreads();
-  if (j < S::T3) {
-#pragma unroll
-    for (int q = 0; q < R3; ++q) ex[j + q * S::T3] = x[q].x;
+  rs_fwd_finish<S, R1, R2, R3>(x, ex, j, w2, w3, da, db, kst, true, hasb);
+}
+
+
+// ------------------------------------------------------------ forward rows of kernel batches, persistent
+// The day kernels of a batch are blobs inside their K x K boxes: on the 5184 torus of the headline stack
+// ~7 % of the row pairs are live, and k_row_fwd_rs still launches a workgroup for every NP pairs of every
+// day.  With one resident workgroup per CU, a live one holds its CU until its column-major stores (one
+// line per lane) have drained, and the next one starts from nothing.  Here a workgroup stays and walks
+// the LIVE units of all `count` batch entries (row_live_units.h: at most two runs per entry, found from
+// a.rowrange on the device -- no table from the host).
+// Same unit code as k_row_fwd_rs (above), same workgroup shape and LDS; column-major output, skip_zero,
+// no pred / trunc_pred (the launcher sends everything else to k_row_fwd_rs).
+// List position i -> group i / KL of 2 NP KL rows (NP = 1, 2, 4: the 8 rows of a 128-byte line of the
+// output; NP = 3: KL = 1 and the group is one unit of 6 rows, as in k_row_fwd_rs) and unit i % KL inside it: with the block remapping of k_row_fwd_rs and a grid that is a multiple of
+// 8 KL, the KL units of a line run in the same round on one XCD.  Speed only: every unit is complete in
+// itself and nothing is handed from one workgroup to another.  Units of a line without a live row (run
+// edges) are walked past.
+template <int R1, int R2, int R3, int NP>
+__global__ void __launch_bounds__((Rs<R1, R2, R3>::NTHR * NP)) k_row_fwd_rsp(RowFwdArgs a, int count, int total) {
+  using S = Rs<R1, R2, R3>;
+  using Y = RsInvLds<R1, R2, R3>;
+  constexpr int KL = NP >= 4 ? 1 : 4 / NP;
+  constexpr int G = 2 * NP * KL;                       // rows of a list group
+  const int half = __builtin_amdgcn_readfirstlane((int)threadIdx.x / S::NTHR);
+  const int j0 = (int)threadIdx.x - half * S::NTHR;
+  double* ex = reinterpret_cast<double*>(ps_lds_raw) + half * (Y::XW + Y::RED);
+  int wg = (int)blockIdx.x;
+  {
+    const int xcd = wg & 7, q = wg >> 3;
+    wg = ((q / KL) * 8 + xcd) * KL + (q % KL);
   }
-  __syncthreads();
-  if (j < S::T3) {
+  const FftProg& P = a.prog;
+  const cplx w2c = tw_lookup(P.tw_lo, P.tw_hi, P.tw_shift, S::tw2(j0));
+  const cplx w3c = tw_lookup(P.tw_lo, P.tw_hi, P.tw_shift, j0 < S::T3 ? S::tw3(j0) : 0);
+  const SrcMap rm = a.rmap;
+  const int64_t kst = (int64_t)a.tstride;
+  // the live-row ranges come through the scalar cache (constant address space): a vector load of them
+  // inside the loop would make the wave wait for its own stores of the round before
+  typedef const __attribute__((address_space(4))) int* ps_const_int_ptr;
+  const ps_const_int_ptr rr = (ps_const_int_ptr)a.rowrange;
+
+  struct Pair {   // what this half of the workgroup does in a round (uniform per wave)
+    const double *pa, *pb;
+    cplx *da, *db;
+    int sa, sb;
+    bool hasb;
+  };
+  auto srow = [&](int r, int rlo, int rhi) {
+    const int sr = r < a.P ? src_map(rm, r) : -1;
+    return (sr < rlo || sr > rhi) ? -1 : sr;
+  };
+  // next list position >= i (in steps of the grid) whose unit has a live row; `total` when there is none
+  LiveCursor cur = live_cursor(rm.n1, rm.off1, rm.lo2, rm.off2, a.P, rr, count, G);
+  auto next_unit = [&](int i, Pair& p) {
+    for (; i < total; i += (int)gridDim.x) {
+      if (!live_advance(cur, i / KL, rm.n1, rm.off1, rm.lo2, rm.off2, a.P, rr, count, G)) return total;
+      const int day = __builtin_amdgcn_readfirstlane(cur.day);
+      const int unit = live_unit(cur.runs, i / KL - cur.base) * KL + i % KL;
+      const int rlo = rr[2 * day], rhi = rr[2 * day + 1];
+      bool any = false;
 #pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-      const int k = j + q * S::T3;
-      zm[q].x = ex[k ? L - k : 0];
-    }
-  }
-  __syncthreads();
-  if (j < S::T3) {
-#pragma unroll
-    for (int q = 0; q < R3; ++q) ex[j + q * S::T3] = x[q].y;
-  }
-  __syncthreads();
-  if (j < S::T3) {
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-      const int k = j + q * S::T3;
-      zm[q].y = ex[k ? L - k : 0];
-      if (k <= L / 2) {
-        const cplx zk = x[q];
-        da[k * kst] = make_double2(0.5 * (zk.x + zm[q].x), 0.5 * (zk.y - zm[q].y));
-        if (hasb) db[k * kst] = make_double2(0.5 * (zk.y + zm[q].y), -0.5 * (zk.x - zm[q].x));
+      for (int h = 0; h < NP; ++h) {
+        const int r = 2 * (unit * NP + h);
+        any = any || srow(r, rlo, rhi) >= 0 || srow(r + 1, rlo, rhi) >= 0;
       }
+      if (!any) continue;
+      // (everything here is the same in every lane of a wave; readfirstlane says so to the compiler)
+      const int ra = __builtin_amdgcn_readfirstlane(2 * (unit * NP + half)), rb = ra + 1;
+      p.sa = __builtin_amdgcn_readfirstlane(srow(ra, rlo, rhi));
+      p.sb = __builtin_amdgcn_readfirstlane(srow(rb, rlo, rhi));
+      const double* src = a.src + (int64_t)day * a.src_bstride;
+      cplx* dst = a.dst + (int64_t)day * a.dst_bstride;
+      p.pa = src + (int64_t)(p.sa >= 0 ? p.sa : 0) * a.src_ld;
+      p.pb = src + (int64_t)(p.sb >= 0 ? p.sb : 0) * a.src_ld;
+      p.da = dst + ra;
+      p.db = dst + rb;
+      p.hasb = rb < a.P;
+      return i;
     }
+    return total;
+  };
+
+  Pair c;
+  for (int i = next_unit(wg, c); i < total; i = next_unit(i + (int)gridDim.x, c)) {   // uniform per workgroup
+    // opaque per-round copies: see k_row_inv_rsp
+    int j = j0;
+    cplx w2 = w2c, w3 = w3c;
+    asm volatile("" : "+v"(j), "+v"(w2.x), "+v"(w2.y), "+v"(w3.x), "+v"(w3.y));
+    __syncthreads();                                   // the last round's mirrored elements have been read
+    // a dead pair in a live unit (run edges) goes through the transform on zeros and stores nothing: one
+    // code path, the same barriers for every wave
+    cplx x[S::RMAX];
+    if (j < S::T1) rs_fwd_load<S, R1>(x, c.pa, c.pb, a.cmap, j, c.sa >= 0, c.sb >= 0);
+    __builtin_amdgcn_sched_barrier(0);                 // every load of the round is issued before the first butterfly
+    rs_fwd_finish<S, R1, R2, R3>(x, ex, j, w2, w3, c.da, c.db, kst, c.sa >= 0 || c.sb >= 0, c.hasb);
   }
 }

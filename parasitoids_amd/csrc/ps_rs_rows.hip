@@ -32,6 +32,21 @@ bool rs_info(int r2, int r3, RsInfo* out) {
   return false;
 }
 
+// k_row_fwd_rsp serves the sizes that put two or more row pairs into a workgroup (NP >= 2: up to six waves per
+// pair).  The NP = 1 sizes (seven waves and more per pair; 5600, 6912 and 8400 among them) keep
+// k_row_fwd_rs: measured on the Carnarvon 10 km chain at 5600 points, whose kernels are 1650-2780 rows wide, the
+// batch launch was 10 % slower with the persistent kernel and the chain 2 %.  Neither instance
+// spills there (149 against 142 VGPRs at 16 x 25 x 14, NP = 1); the cause is not known.
+template <int R2, int R3>
+constexpr bool rs_fwd_live_ok() { return RsCfg<R2, R3>::NP >= 2; }
+
+bool rs_row_fwd_info(int r2, int r3, int* np, int* persistent) {
+#define X(A, B) if (r2 == A && r3 == B) { *np = RsCfg<A, B>::NP; *persistent = rs_fwd_live_ok<A, B>() ? 1 : 0; return true; }
+  PS_RS_SIZES(X)
+#undef X
+  return false;
+}
+
 int rs_rows_set_attrs() {
 #define X(A, B)                                                                                              \
   {                                                                                                          \
@@ -57,6 +72,10 @@ int rs_rows_set_attrs() {
       auto kf = k_row_fwd_rs<16, A, B, np>;                                                                  \
       if (hipFuncSetAttribute((const void*)ki, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS) != hipSuccess) return -1; \
       if (hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS) != hipSuccess) return -1; \
+      if constexpr (rs_fwd_live_ok<A, B>()) {                                                                \
+        auto kl = k_row_fwd_rsp<16, A, B, np>;                                                               \
+        if (hipFuncSetAttribute((const void*)kl, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS) != hipSuccess) return -1; \
+      }                                                                                                      \
     }                                                                                                        \
   }
   PS_RS_SIZES(X)
@@ -100,6 +119,47 @@ int rs_launch_row_fwd(int r2, int r3, const RowFwdArgs& a, int npairs, int batch
   PS_RS_SIZES(X)
 #undef X
   return 0;
+}
+
+// Kernel batches of the full-column pipeline: one persistent workgroup per CU slot over the live units
+// (k_row_fwd_rsp).  hranges: host copy of a.rowrange, [batch][2].
+int rs_launch_row_fwd_live(int r2, int r3, const RowFwdArgs& a, const int* hranges, int batch, hipStream_t st) {
+#define X(A, B)                                                                                              \
+  if (r2 == A && r3 == B) {                                                                                  \
+    using C = RsCfg<A, B>;                                                                                   \
+    constexpr int np = C::NP;                                                                                \
+    if constexpr (!rs_fwd_live_ok<A, B>()) return rs_launch_row_fwd(r2, r3, a, (a.P + 1) / 2, batch, st);    \
+    else {                                                                                                   \
+    constexpr int kl = np >= 4 ? 1 : 4 / np;                                                                 \
+    const int total = kl * live_total(a.rmap.n1, a.rmap.off1, a.rmap.lo2, a.rmap.off2, a.P, hranges, batch, 2 * np * kl); \
+    if (total == 0) return 1;   /* every kernel of the batch is empty */                                     \
+    /* resident workgroups per CU: 12 wave slots at the kernel's <= 168 registers, 160 KB of LDS */          \
+    constexpr int W = C::S::NTHR / 64 * np;                                                                  \
+    constexpr int kw = 12 / W < 1 ? 1 : 12 / W, kld = (int)((size_t)160 * 1024 / C::LDS);                    \
+    constexpr int per_cu = kw < kld ? kw : (kld < 1 ? 1 : kld);                                              \
+    const int m = 8 * kl;                                                                                    \
+    const int wgs = (std::min(total, device_cus() * per_cu) + m - 1) / m * m;                                \
+    auto kern = k_row_fwd_rsp<16, A, B, np>;                                                                 \
+    hipLaunchKernelGGL(kern, dim3(wgs), dim3(C::S::NTHR * np), C::LDS, st, a, batch, total);                 \
+    return 1;                                                                                                \
+    }                                                                                                        \
+  }
+  PS_RS_SIZES(X)
+#undef X
+  return 0;
+}
+
+int rs_row_live_units(int P, int M, int np, int nd, const int* ranges, int* day, int* unit, int cap) {
+  if (P < 1 || M < 0 || np < 1 || nd < 0 || 2 * M + 1 > P) return -1;
+  const int n1 = M + 1, off1 = M, lo2 = P - M, off2 = 0, g = 2 * np;   // map_wrap(M, P)
+  const int total = live_total(n1, off1, lo2, off2, P, ranges, nd, g);
+  LiveCursor cur = live_cursor(n1, off1, lo2, off2, P, ranges, nd, g);
+  for (int k = 0; k < total && k < cap; ++k) {
+    if (!live_advance(cur, k, n1, off1, lo2, off2, P, ranges, nd, g)) return -1;
+    day[k] = cur.day;
+    unit[k] = live_unit(cur.runs, k - cur.base);
+  }
+  return total;
 }
 
 int rs_launch_row_fold(int r2, int r3, const RowFoldArgs& a, int units, hipStream_t st) {

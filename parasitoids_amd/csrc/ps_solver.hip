@@ -14,6 +14,18 @@ thread_local std::string ps_tls_error;
 
 extern "C" const char* ps_last_error(void) { return ps_tls_error.c_str(); }
 extern "C" int ps_version(void) { return 100; }
+extern "C" int ps_row_live_units(int P, int M, int np, int nd, const int32_t* ranges, int32_t* day, int32_t* unit, int cap) {
+  if (!ranges && nd > 0) return -1;
+  if (cap > 0 && (!day || !unit)) return -1;
+  return rs_row_live_units(P, M, np, nd, ranges, day, unit, cap);
+}
+extern "C" int ps_row_fwd_info(int fft_len, int* np, int* persistent) {
+  int r2 = 0, r3 = 0, n = 0, p = 0;
+  if (!rs_lookup(fft_len, &r2, &r3) || !rs_row_fwd_info(r2, r3, &n, &p)) return -1;
+  if (np) *np = n;
+  if (persistent) *persistent = p;
+  return 0;
+}
 
 extern "C" int ps_device_count(void) {
   int n = 0;
@@ -410,7 +422,8 @@ static int set_lds_attr() {
 static int launch_row_fwd(ps_solver* s, const double* src, int64_t src_bstride, int src_ld,
                           SrcMap rmap, SrcMap cmap, cplx* dst, int batch,
                           const unsigned long long* pred, int skip_zero = 0, const int* rowrange = nullptr,
-                          const unsigned long long* trunc_pred = nullptr, int trunc_n = 0) {
+                          const unsigned long long* trunc_pred = nullptr, int trunc_n = 0, int kfirst = -1) {
+  // kfirst >= 0: a kernel batch, rowrange = krange + 2 kfirst (fwd2d_partial)
   RowFwdArgs a;
   if (trunc_pred && s->rs_r2 == 0) return ps_fail(PS_ERR_STATE, "row pass: only the register-resident kernels truncate on the fly");
   a.trunc_pred = trunc_pred; a.trunc_n = trunc_n;
@@ -431,7 +444,15 @@ static int launch_row_fwd(ps_solver* s, const double* src, int64_t src_bstride, 
   const size_t lds = ((size_t)a.rp * row_pitch(a.prog) + a.prog.n_lo + a.prog.n_hi + a.prog.n_gen) * sizeof(cplx);
   if (lds > (size_t)kMaxLds) return ps_fail(PS_ERR_UNSUPPORTED, "row pass needs %zu B LDS", lds);
   ProfScope prof(s, pred ? PS_PROF_REFFT : PS_PROF_ROW_FWD);
-  if (s->rs_r2 != 0 && !s->cfg.no_rs_fwd) {
+  // kernel batches of the full-column pipeline (fwd2d_partial): persistent workgroups over the live units,
+  // sized from the host copy of the live-row ranges.  PS_NO_FWD_PERSIST=1: A/B knob (the one-shot kernel).
+  const bool live_list = s->rs_r2 != 0 && !s->cfg.no_rs_fwd && a.tstride && skip_zero && !pred && !trunc_pred &&
+                         !s->cfg.no_fwd_persist && kfirst >= 0 && rowrange &&
+                         2 * ((size_t)kfirst + batch) <= s->hkrange.size();
+  if (live_list) {
+    if (!rs_launch_row_fwd_live(s->rs_r2, s->rs_r3, a, s->hkrange.data() + 2 * kfirst, batch, s->stream))
+      return ps_fail(PS_ERR_STATE, "no register-resident row kernel for 16 x %d x %d", s->rs_r2, s->rs_r3);
+  } else if (s->rs_r2 != 0 && !s->cfg.no_rs_fwd) {
     if (!rs_launch_row_fwd(s->rs_r2, s->rs_r3, a, npairs, batch, s->stream))
       return ps_fail(PS_ERR_STATE, "no register-resident row kernel for 16 x %d x %d", s->rs_r2, s->rs_r3);
   } else if (s->row_plan.generic)
@@ -690,13 +711,14 @@ static int inv2d(ps_solver* s, const cplx* A, const cplx* B, cplx* prod, double*
 // one is fused with the spectral product and the first inverse sub-pass (k_col_fused)
 static int fwd2d_partial(ps_solver* s, const double* src, int64_t src_bstride, int src_ld,
                          SrcMap rmap, SrcMap cmap, cplx* out, int batch, const int* rowrange = nullptr,
-                         bool direct = false) {
+                         bool direct = false, int kfirst = -1) {
+  // kfirst >= 0: the batch is day kernels kfirst .. kfirst + batch - 1 and rowrange their krange entries
   const RowLive live{1, rmap, rowrange};
   s->kt_live = RowLive{0, {0, 0, 0, 0}, nullptr};
   s->kt_direct = s->split && direct && !s->tpipe;
   if (s->tpipe) {   // the day step's full-column pass reads the (column-major) row-pass output itself
     s->kt_live = live;
-    return launch_row_fwd(s, src, src_bstride, src_ld, rmap, cmap, out, batch, nullptr, 1, rowrange);
+    return launch_row_fwd(s, src, src_bstride, src_ld, rmap, cmap, out, batch, nullptr, 1, rowrange, nullptr, 0, kfirst);
   }
   if (!s->split || direct) {
     s->kt_live = live;  // the fused pass reads the row-pass output directly (one day at a time)
@@ -1514,7 +1536,7 @@ static int transform_kernels(ps_solver* s, int first, int count, int slot0, int 
   if (direct_chunk >= 0) direct = direct && direct_chunk != 0;
   else for (int d = first; d < first + count && direct; ++d) direct = day_is_compact(s, d);
   PS_TRY(fwd2d_partial(s, kd, (int64_t)K * K, K, map_wrap(M, s->Pf), map_wrap(M, s->Pf), s->Bhat.p + (size_t)slot0 * spec, count,
-                       s->krange.p + 2 * first, direct));
+                       s->krange.p + 2 * first, direct, first));
   s->bhat_first = first - slot0;
   s->bhat_count = slot0 + count;
   return PS_OK;

@@ -24,6 +24,17 @@ int rs_colfull_set_attrs();    // ... and every full-column kernel
 // launches; return 0 when (r2, r3) is not a served size
 int rs_launch_row_fwd(int r2, int r3, const RowFwdArgs& a, int npairs, int batch, hipStream_t st);
 int rs_launch_row_inv(int r2, int r3, const RowInvArgs& a, int npairs, int batch, hipStream_t st);
+// kernel batches of the full-column pipeline (a.tstride, a.rowrange, a.skip_zero; no pred / trunc_pred):
+// persistent workgroups over the live units only (k_row_fwd_rsp); hranges = host copy of a.rowrange.
+// An all-empty batch launches nothing.  Sizes with one row pair per workgroup (5600 points among them) keep
+// k_row_fwd_rs (rs_fwd_live_ok, ps_rs_rows.hip): the launcher sends them to rs_launch_row_fwd itself.
+// rs_row_fwd_info: row pairs per workgroup of the forward row kernels of a size and whether its kernel
+// batches go to k_row_fwd_rsp; false when (r2, r3) is not served.
+bool rs_row_fwd_info(int r2, int r3, int* np, int* persistent);
+int rs_launch_row_fwd_live(int r2, int r3, const RowFwdArgs& a, const int* hranges, int batch, hipStream_t st);
+// live units (np row pairs each) of `nd` entries with source-row ranges [nd][2] under map_wrap(M, P), in
+// list order: entry and unit of the first `cap`; returns their number (host only, see ps_row_live_units)
+int rs_row_live_units(int P, int M, int np, int nd, const int* ranges, int* day, int* unit, int cap);
 // mode 0 (nd >= 1 days), 1, 2, 3 as in fft_colfull_kernels.h; lines8 = 128-byte lines per XCD
 int rs_launch_colfull(int r2, int r3, const ColFullArgs& a, int lines8, int batch, hipStream_t st);
 // inverse row pass + fold onto the reference torus (PS_MODE_FOLD; k_row_inv_fold), one workgroup per unit
