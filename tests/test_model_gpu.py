@@ -162,7 +162,9 @@ def test_prob_mass_bad_parameters(PM, kalbar):
 def test_prob_mass_random_parameters_against_oracle(PM, kalbar, carnarvon):
     '''Twelve random draws of the model parameters (flight/wind logistic parameters, diffusion
     with correlations of both signs, mu_r, n_periods, grid resolution, start time) on random
-    days of both wind files against the oracle: identical COO pattern, values to 5e-15.'''
+    days of both wind files against the oracle: identical COO pattern, values to 5e-15.
+    The correlations stay below |rho| = 0.6 (in-flow) and 0.5 (out-of-flow): the 10-node rule and the
+    |rho| >= 0.925 instance are run by tests/test_model_corr_gpu.py.'''
     rng = np.random.default_rng(314159)
     for case in range(12):
         wd, days = kalbar if case % 2 == 0 else carnarvon
