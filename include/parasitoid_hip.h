@@ -1218,6 +1218,63 @@ int ps_patch_fetch_members(ps_patch* a, int k, int slot, uint32_t* npatch, uint3
 int ps_patch_prof(ps_patch* a, int enable, double* add_ms, int64_t* adds, double* map_ms, int64_t* maps);
 void ps_patch_destroy(ps_patch* a);
 
+/* ---- representative members: pairwise overlap of the members' excursion sets ----
+ * (no reference counterpart.)  The mean, the quantiles and the excursion sets are maps no member produces.  Which
+ * single member is the most typical one, between which two outlines the middle half of the members lies (the contour
+ * boxplot of Whitaker, Mirzargar & Kirby 2013) and whether the members fall into a few scenarios depend on how the
+ * members' sets relate pairwise, which the count plane has lost.  Setting: one plane (threshold k, slot) of a
+ * ps_excur; members m = 0..M-1 in add order, B_m the cells whose mask bit is 1, integer weight w_m >= 1, W = sum w_m.
+ * Device:
+ *   I[i][j] = |B_i & B_j| as uint32, the full symmetric M x M table, the diagonal n_i = |B_i|; pad bits are 0 in the
+ *     masks and do not count
+ *   Cs(c) = sum_m s_m bit_m(c) as uint32 for a selection s (uint32 per member, 0: not selected), sum s_m < 2^32 - 1
+ * Host (parasitoids_amd/predictive.py, integers only), every line a statement of its own:
+ *   out_ij = n_i - I_ij
+ *   i is eps-included in j  <=>  1000 out_ij <= e n_i,  e = round(1000 eps), eps a multiple of 0.001 in [0, 0.5]
+ *     (Chaves-de-Plaza et al. 2024, the relaxed inclusion); an empty set lies inside every set
+ *   in_i = sum_j w_j [i in j];  cont_i = sum_j w_j [j in i], both with j = i;  depth_i = min(in_i, cont_i) in
+ *     [w_i, W], reported as depth_i / W
+ *   the median member has the largest depth, among equals the smallest index
+ *   the central set is the shortest prefix of the members sorted by (-depth, index) whose weight cum satisfies
+ *     1000 cum >= c W,  c = round(1000 central), central a multiple of 0.001 in (0, 1]
+ *   the band is Cs of the central set with s = w (Wc its weight): +1 where Cs == Wc, 0 where 0 < Cs < Wc, -1 where
+ *     Cs == 0
+ *   d_ij = n_i + n_j - 2 I_ij, the cells of the symmetric difference
+ *   scenarios are weighted k-medoids on d, cost(Med) = sum_i w_i min_{m in Med} d_im, by deterministic PAM (Kaufman
+ *     & Rousseeuw): BUILD takes argmin_m sum_i w_i d_im, then the candidate that lowers the cost most, among equals
+ *     the smallest index; SWAP takes over every (medoid position, other member) the swap with the largest strict
+ *     improvement, among equals the smallest position, then the smallest member, until none improves; a member
+ *     goes to its nearest medoid, among equals the one with the smallest index; clusters by descending weight, then
+ *     medoid index
+ *   the plane 'all' takes I and n summed over the slots in int64
+ * State: the handle borrows the ps_excur -- the caller keeps it alive -- and reads its masks, counts and members at
+ * every call, so the members present at the call are the members of the answer.  It owns a stream, the M x M table
+ * (M * M * 4 B, 25 MB at 2500 members; grown on demand, the free memory checked first: PS_ERR_OOM before it is
+ * made), one uint32 plane, the selection vector and two words for the live window.  Every call orders its stream
+ * behind the accumulator's last operation and the accumulator's next operation behind its read, and synchronises.
+ * The pair kernel works on member tiles of ps_overlap_info's `tile` on or above the diagonal and mirrors when it
+ * writes; the word range may be split over workgroups, which then add with integer atomics: neither the grid nor
+ * the order changes a bit.  With use_window != 0 it visits only the words from the first to the last one in which
+ * the count plane is non-zero (outside them every mask word is zero); the table is the same either way. */
+typedef struct ps_overlap ps_overlap;
+/* PS_ERR_BAD_ARG unless e is on `device` with domain N */
+int ps_overlap_create(int device, int N, ps_excur* e, ps_overlap** out);
+/* PS_ERR_STATE while e holds no member; PS_ERR_BAD_ARG for a plane out of range or members_expected != e's members
+ * (a caller's buffer is never too small) */
+int ps_overlap_pairs(ps_overlap* h, int k, int slot, int64_t members_expected, int use_window,
+                     uint32_t* out /* M*M */);
+/* sel: `members` entries, NULL for every member with its own weight (Cs is then the count plane); PS_ERR_BAD_ARG
+ * for members != e's members or a selection that sums to 2^32 - 1 or more; PS_ERR_STATE while e holds no member */
+int ps_overlap_subset(ps_overlap* h, int k, int slot, int64_t members, const uint32_t* sel, uint32_t* out /* N*N */);
+/* any pointer may be NULL; members: those of the last pairs call; bytes: the device memory held now; tile: the
+ * member-tile edge of the pair kernel */
+int ps_overlap_info(ps_overlap* h, int64_t* members, int64_t* bytes, int32_t* tile);
+/* measurement: HIP-event timing of the pairs calls (memset, window, pair kernel) and the subset launches, as
+ * ps_arrival_prof; while enabled every call keeps one event pair, folded into the totals past 256 */
+int ps_overlap_prof(ps_overlap* h, int enable, double* pairs_ms, int64_t* pairs_n, double* subset_ms,
+                    int64_t* subset_n);
+void ps_overlap_destroy(ps_overlap* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -321,6 +321,13 @@ SIGNATURES = {
     'ps_patch_fetch_members': (C.c_int, [_VP, C.c_int, C.c_int] + [C.POINTER(C.c_uint32)] * 6),
     'ps_patch_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P, _F64P, _I64P]),
     'ps_patch_destroy': (None, [_VP]),
+    'ps_overlap_create': (C.c_int, [C.c_int, C.c_int, _VP, C.POINTER(_VP)]),
+    'ps_overlap_pairs': (C.c_int, [_VP, C.c_int, C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_uint32)]),
+    'ps_overlap_subset': (C.c_int, [_VP, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_uint32),
+                                    C.POINTER(C.c_uint32)]),
+    'ps_overlap_info': (C.c_int, [_VP, _I64P, _I64P, _I32P]),
+    'ps_overlap_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P, _F64P, _I64P]),
+    'ps_overlap_destroy': (None, [_VP]),
 }
 
 _lib = None

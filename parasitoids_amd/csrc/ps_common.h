@@ -147,6 +147,20 @@ PsFieldsOps ps_peak_fields();    // the last member's peak field of a ps_peak (p
 PsFieldsOps ps_catch_fields();   // the catch-probability fields of a ps_catch (ps_catch.hip)
 PsFieldsOps ps_gain_fields();    // the class-probability and entropy planes of a ps_gain (ps_gain.hip)
 
+// the members' masks and the count planes of a ps_excur as ps_overlap.hip reads them on the device (ps_excur.hip).
+// The mask block moves when it grows, so a reader takes the view at every call; it orders its stream behind the
+// accumulator's last operation (wait) and the accumulator's next operation behind its read (mark).
+struct PsExcurView {
+  const uint64_t* mask;         // [members][nthr][nslot][pitch / 64], device
+  const uint32_t* cnt;          // [nthr][nslot][pitch], device
+  const uint32_t* weights;      // [members], host, in add order
+  int64_t pitch, members;
+  int N, nthr, nslot, device;
+};
+int ps_excur_view_internal(ps_excur* a, PsExcurView* out);
+int ps_excur_wait_internal(ps_excur* a, hipStream_t stream);
+int ps_excur_mark_internal(ps_excur* a, hipStream_t stream);
+
 // the mean planes of an accumulator as ps_gain.hip's finish reads them on the device (ps_summary.hip; ps_wsum.hip
 // per scenario); PS_ERR_STATE while nothing is accumulated.  The reader orders its stream behind the accumulator's
 // last operation (wait) and the accumulator's next operation behind the read (done).

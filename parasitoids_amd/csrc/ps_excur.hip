@@ -631,3 +631,12 @@ extern "C" int ps_excur_prof(ps_excur* a, int enable, double* ms, int64_t* launc
   }
   return PS_OK;
 }
+
+// what ps_overlap.hip reads (ps_common.h): the masks and counts as they are now, and the handle's event
+int ps_excur_view_internal(ps_excur* a, PsExcurView* out) {
+  if (!a || !out) return ps_fail(PS_ERR_BAD_ARG, "excur_view: bad arguments");
+  *out = PsExcurView{a->mask, a->cnt, a->weights.data(), a->pitch, a->members, a->N, a->nthr, a->nslot, a->device};
+  return PS_OK;
+}
+int ps_excur_wait_internal(ps_excur* a, hipStream_t stream) { return exc_after_last(a, stream); }
+int ps_excur_mark_internal(ps_excur* a, hipStream_t stream) { return exc_mark_last(a, stream); }

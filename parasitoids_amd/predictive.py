@@ -53,6 +53,10 @@ posterior of their area -- the level is each member's own, so no map cut at an a
 `PatchMaps` labels, on the device, the connected components of each member's set {v >= t} per threshold and day
 (ps_patch_*, csrc/ps_patch.hip) and keeps the weighted count of the members whose main patch, or another patch, holds
 the cell, and per member the number of patches and their sizes: is the reached area one front or separate foci?
+`MemberOverlap` forms, on the device, the table of pairwise intersections of the members' reached sets from the masks
+of an `ExcursionMaps`, and the count plane of any selection of members (ps_overlap_*, csrc/ps_overlap.hip);
+`RepresentativeMembers` reads from it, in integers on the host, the inclusion depth of every member, the deepest
+member, the central band and k-medoids scenarios -- which single outcome is typical, which no summary map can say.
 """
 import ctypes as C
 import json
@@ -789,6 +793,396 @@ class ExcursionMaps(_Accumulator):
         return float(ms[0]), int(n[0]), float(ms[1]), int(n[1]), float(ms[2]), int(n[2])
 
 
+MAX_CLUSTERS = 8
+
+
+def _thousandths(value, name, lo, hi, open_lo=False):
+    '''round(1000 * value) for a value that is a multiple of 0.001 (within 1e-9) in [lo, hi] (open_lo: (lo, hi]);
+    ValueError otherwise'''
+    try:
+        x = float(value)
+    except (TypeError, ValueError):
+        raise ValueError('%s must be a number, got %r' % (name, value))
+    e = int(round(1000.0 * x)) if np.isfinite(x) else 0
+    if not np.isfinite(x) or abs(x - e / 1000.0) > 1e-9:
+        raise ValueError('%s must be a multiple of 0.001, got %r' % (name, value))
+    if not (lo < x if open_lo else lo <= x) or not x <= hi:
+        raise ValueError('%s must lie in %s%g, %g], got %r' % (name, '(' if open_lo else '[', lo, hi, value))
+    return e
+
+
+def check_clusters(clusters):
+    '''the number of scenarios as an int in 1..8; ValueError otherwise'''
+    if isinstance(clusters, bool) or not isinstance(clusters, (int, np.integer)) or not 1 <= clusters <= MAX_CLUSTERS:
+        raise ValueError('clusters must be an integer in 1..%d, got %r' % (MAX_CLUSTERS, clusters))
+    return int(clusters)
+
+
+def check_representative(arg):
+    '''the representative= argument of posterior_predictive -> dict(epsilon, central, clusters, days): True for the
+    defaults, or dict(epsilon=0.02, central=0.5, clusters=3, days='all') with any of the keys; epsilon a multiple of
+    0.001 in [0, 0.5], central one in (0, 1], clusters in 1..8, days 'all' (the space-time plane) or a non-empty list
+    of days >= 0 (one plane each); ValueError otherwise'''
+    out = dict(epsilon=0.02, central=0.5, clusters=3, days='all')
+    if arg is not True:
+        if not isinstance(arg, dict):
+            raise ValueError('representative must be True or a dict, got %r' % (arg,))
+        unknown = set(arg) - set(out)
+        if unknown:
+            raise ValueError('representative: unknown keys %r' % (sorted(unknown),))
+        out.update(arg)
+    _thousandths(out['epsilon'], 'epsilon', 0.0, 0.5)
+    _thousandths(out['central'], 'central', 0.0, 1.0, open_lo=True)
+    out['epsilon'], out['central'] = float(out['epsilon']), float(out['central'])
+    out['clusters'] = check_clusters(out['clusters'])
+    if not (isinstance(out['days'], str) and out['days'] == 'all'):
+        try:
+            days = [int(d) for d in out['days']]
+        except (TypeError, ValueError):
+            raise ValueError("representative: days must be 'all' or a list of days, got %r" % (out['days'],))
+        if not days or min(days) < 0 or len(set(days)) != len(days):
+            raise ValueError("representative: days must be 'all' or a non-empty list of distinct days >= 0, got %r"
+                             % (out['days'],))
+        out['days'] = days
+    return out
+
+
+def _pair_table(I, weights=None):
+    '''(I as [M, M] int64, the weights as [M] int64 or None)'''
+    I = np.asarray(I).astype(np.int64)
+    if I.ndim != 2 or I.shape[0] != I.shape[1] or I.shape[0] < 1:
+        raise ValueError('the pair table must be [M, M] with M >= 1, got shape %r' % (I.shape,))
+    if weights is None:
+        return I, None
+    w = np.asarray(weights).astype(np.int64)
+    if w.shape != (I.shape[0],) or (w < 1).any():
+        raise ValueError('weights must be %d integers >= 1' % I.shape[0])
+    return I, w
+
+
+def inclusion_depth(I, weights, epsilon):
+    '''(depth, in, cont), each [M] int64, of the pair table I [M, M] (I_ij = |B_i & B_j|, the diagonal n_i): with
+    out_ij = n_i - I_ij member i is eps-included in j where 1000 out_ij <= round(1000 epsilon) n_i (an empty set in
+    every set); in_i = the weight of the members i lies in, cont_i of those that lie in i, both with i itself;
+    depth = min(in, cont), in [w_i, W].  Integers throughout.'''
+    I, w = _pair_table(I, weights)
+    e = _thousandths(epsilon, 'epsilon', 0.0, 0.5)
+    n = np.diagonal(I)
+    inc = 1000 * (n[:, None] - I) <= e * n[:, None]        # [i, j]: i lies in j
+    w_in = (inc * w[None, :]).sum(1)
+    w_cont = (inc * w[:, None]).sum(0)
+    return np.minimum(w_in, w_cont), w_in, w_cont
+
+
+def median_member(depth):
+    '''the member with the largest depth, among equals the smallest index'''
+    return int(np.argmax(np.asarray(depth)))
+
+
+def central_members(depth, weights, central=0.5):
+    '''the members of the central set in the order (-depth, index): the shortest prefix whose weight cum satisfies
+    1000 cum >= round(1000 central) W'''
+    depth = np.asarray(depth).astype(np.int64)
+    w = np.asarray(weights).astype(np.int64)
+    c = _thousandths(central, 'central', 0.0, 1.0, open_lo=True)
+    W = int(w.sum())
+    out, cum = [], 0
+    for m in sorted(range(len(depth)), key=lambda i: (-int(depth[i]), i)):
+        out.append(m)
+        cum += int(w[m])
+        if 1000 * cum >= c * W:
+            break
+    return out
+
+
+def set_distance(I):
+    '''[M, M] int64 d_ij = n_i + n_j - 2 I_ij: the cells on which members i and j disagree'''
+    I, _w = _pair_table(I)
+    n = np.diagonal(I)
+    return n[:, None] + n[None, :] - 2 * I
+
+
+def _pam(D, w, K):
+    '''the medoids of deterministic PAM in BUILD order, and their cost'''
+    M = len(w)
+    big = np.iinfo(np.int64).max
+    first = int(np.argmin((w[:, None] * D).sum(0)))
+    med = [first]
+    near = D[:, first].copy()
+    while len(med) < K:                                     # BUILD: the candidate that lowers the cost most
+        cost = (w[:, None] * np.minimum(near[:, None], D)).sum(0)
+        cost[med] = big
+        c = int(np.argmin(cost))
+        med.append(c)
+        near = np.minimum(near, D[:, c])
+    cost = int((w * near).sum())
+    while True:                                             # SWAP: the best strict improvement, until there is none
+        best = (cost, None, None)
+        for p in range(K):
+            others = [m for q, m in enumerate(med) if q != p]
+            base = D[:, others].min(1) if others else np.full(M, big)
+            cand = (w[:, None] * np.minimum(base[:, None], D)).sum(0)
+            cand[med] = big
+            c = int(np.argmin(cand))
+            if int(cand[c]) < best[0]:
+                best = (int(cand[c]), p, c)
+        if best[1] is None:
+            return med, cost
+        cost, med[best[1]] = best[0], best[2]
+
+
+def k_medoids(D, weights, K):
+    '''Weighted k-medoids of the members on the integer distances D [M, M] by deterministic PAM (Kaufman &
+    Rousseeuw), K in 1..min(8, M): cost(Med) = sum_i w_i min_{m in Med} D[i, m].  BUILD: argmin_m sum_i w_i D[i, m],
+    then the candidate that lowers the cost most, among equals the smallest index; SWAP: over every (medoid
+    position, other member) the swap with the largest strict improvement, among equals the smallest position, then
+    the smallest member, until none improves; a member goes to its nearest medoid, among equals the one with the
+    smallest index; clusters by descending weight, then medoid index.  -> dict(medoids [K], assignment [M] (the
+    cluster of every member), cluster_weight [K], cost, costs_by_k [K]: the cost PAM reaches with 1..K medoids)'''
+    D = np.asarray(D).astype(np.int64)
+    if D.ndim != 2 or D.shape[0] != D.shape[1] or D.shape[0] < 1:
+        raise ValueError('the distances must be [M, M] with M >= 1, got shape %r' % (D.shape,))
+    w = np.asarray(weights).astype(np.int64)
+    if w.shape != (D.shape[0],) or (w < 1).any():
+        raise ValueError('weights must be %d integers >= 1' % D.shape[0])
+    K = check_clusters(K)
+    if K > len(w):
+        raise ValueError('%d clusters of %d members' % (K, len(w)))
+    runs = [_pam(D, w, k) for k in range(1, K + 1)]
+    med, cost = runs[-1]
+    by_index = sorted(med)
+    near = np.argmin(D[:, by_index], axis=1)                # the first minimum: the medoid with the smallest index
+    weight = [int(w[near == c].sum()) for c in range(K)]
+    order = sorted(range(K), key=lambda c: (-weight[c], by_index[c]))
+    rank = np.empty(K, dtype=np.int64)
+    rank[order] = np.arange(K)
+    return {'medoids': [by_index[c] for c in order], 'assignment': rank[near],
+            'cluster_weight': [weight[c] for c in order], 'cost': cost, 'costs_by_k': [c for _m, c in runs]}
+
+
+class MemberOverlap(_Handle):
+    '''The pairwise overlap of the members of an ExcursionMaps, on the device (ps_overlap_*, csrc/ps_overlap.hip):
+    per threshold and day the table I[i][j] = |B_i & B_j| of the members' reached sets, and the weighted count
+    plane of any selection of members.  The handle borrows the maps and reads them at every call: members added
+    later are in the next answer.  Integers throughout; no order changes a bit.'''
+    _prefix, _noun = 'ps_overlap', 'member overlap'
+    _info_types = (C.c_int64, C.c_int64, C.c_int32)        # members of the last pairs call, bytes, tile
+    _prof_pairs = 2
+
+    def __init__(self, excursion):
+        if not isinstance(excursion, ExcursionMaps):
+            raise ValueError('the member overlap is taken over an ExcursionMaps, got %r' % (type(excursion).__name__,))
+        self.excursion = excursion
+        self._maps()
+        self._attach(excursion.pm)
+        self.thresholds, self.days = excursion.thresholds, excursion.days
+        self._create(excursion._h)
+
+    def _maps(self):
+        if not self.excursion._h:
+            raise ValueError('the ExcursionMaps of this member overlap are closed')
+        return self.excursion
+
+    @property
+    def tile(self):
+        '''the member-tile edge of the pair kernel'''
+        return self._info()[2]
+
+    @property
+    def nbytes(self):
+        '''the device memory the handle holds now'''
+        return self._info()[1]
+
+    def pairs(self, k, day, window=True):
+        '''[M, M] uint32: I[i][j] = the cells where members i and j (in add order) both hold >= t_k on `day`, the
+        diagonal each member's own cells.  window: visit only the mask words between the first and the last one in
+        which any member holds anything; the table is the same without.'''
+        E = self._maps()
+        M = E.members
+        out = np.empty((M, M), dtype=np.uint32)
+        self._call('pairs', E._k(k), E._slot_of(day), M, int(bool(window)), out.ctypes.data_as(C.POINTER(C.c_uint32)))
+        return out
+
+    def subset_counts(self, k, day, sel):
+        '''[N, N] uint32: sum_m sel[m] [member m holds >= t_k at the cell on `day`]; sel: one integer in
+        0..2^32 - 1 per member, their sum below 2^32 - 1'''
+        E = self._maps()
+        s = np.asarray(sel)
+        if s.ndim != 1 or s.shape[0] != E.members or not np.issubdtype(s.dtype, np.integer):
+            raise ValueError('the selection must be %d integers, got %r' % (E.members, s.shape))
+        if s.size and (s.min() < 0 or int(s.astype(np.int64).sum()) >= 0xffffffff):
+            raise ValueError('the selection must be >= 0 and sum to less than 2^32 - 1')
+        s = np.ascontiguousarray(s, dtype=np.uint32)
+        out = np.empty((self.N, self.N), dtype=np.uint32)
+        u32 = C.POINTER(C.c_uint32)
+        self._call('subset', E._k(k), E._slot_of(day), s.shape[0], s.ctypes.data_as(u32), out.ctypes.data_as(u32))
+        return out
+
+    def profile(self, enable=None):
+        '''HIP-event time of the pairs calls and the subset launches: (pairs ms, calls, subset ms, launches);
+        enable switches it'''
+        return self._profile(enable)
+
+
+class RepresentativeMembers():
+    '''Which members of an ExcursionMaps are typical, on their reached sets {v >= t_k}: the inclusion depth of every
+    member (Chaves-de-Plaza et al. 2024), the deepest member, the central set and its band (the contour boxplot of
+    Whitaker et al. 2013), and weighted k-medoids scenarios on the area two members disagree on.  `day` is a day of
+    the maps, or 'all' for the space-time set (the tables summed over the days).  Holds the maps (not owned), a
+    MemberOverlap of its own and the settings; the table of a plane is fetched once and kept on the host, until the
+    maps gain members.  Members are numbered in add order, as PredictiveResult.runs.'''
+
+    def __init__(self, excursion, epsilon=0.02, central=0.5, clusters=3):
+        checked = check_representative(dict(epsilon=epsilon, central=central, clusters=clusters))
+        self.settings = {n: checked[n] for n in ('epsilon', 'central', 'clusters')}
+        self.epsilon, self.central_level, self.clusters = (checked[n] for n in ('epsilon', 'central', 'clusters'))
+        self.overlap = MemberOverlap(excursion)
+        self.excursion = excursion
+        self.thresholds, self.days, self.N, self.cell_area = (excursion.thresholds, excursion.days, excursion.N,
+                                                              excursion.cell_area)
+        self._tables, self._members, self._weights = {}, -1, None
+
+    def close(self):
+        self.overlap.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _fresh(self):
+        M = self.overlap._maps().members
+        if M != self._members:
+            self._tables, self._members = {}, M
+            self._weights = self.excursion.bounds(0, self.days[0])[2].astype(np.int64) if M else None
+        if not M:
+            raise ValueError('the excursion maps hold no member')
+
+    @property
+    def weights(self):
+        '''[members] int64, in add order'''
+        self._fresh()
+        return self._weights
+
+    def pairs(self, k, day):
+        '''the pair table of a plane: [M, M] uint32 of a day, int64 of 'all' (the sum over the days)'''
+        self._fresh()
+        key = (self.excursion._k(k), day)
+        if key not in self._tables:
+            if isinstance(day, str) and day == 'all':
+                self._tables[key] = sum(self.pairs(k, d).astype(np.int64) for d in self.days)
+            else:
+                self._tables[key] = self.overlap.pairs(k, day)
+        return self._tables[key]
+
+    def depth_counts(self, k, day):
+        '''(depth, in, cont) [members] int64 (inclusion_depth)'''
+        return inclusion_depth(self.pairs(k, day), self.weights, self.epsilon)
+
+    def depth(self, k, day):
+        '''[members] float64: depth / W, in (0, 1]'''
+        return self.depth_counts(k, day)[0].astype(np.float64) / float(int(self.weights.sum()))
+
+    def median(self, k, day):
+        '''the deepest member'''
+        return median_member(self.depth_counts(k, day)[0])
+
+    def central(self, k, day):
+        '''the members of the central set, deepest first'''
+        return central_members(self.depth_counts(k, day)[0], self.weights, self.central_level)
+
+    def _subset(self, k, day_of_map, members):
+        sel = np.zeros(self._members, dtype=np.int64)
+        sel[members] = self._weights[members]
+        return self.overlap.subset_counts(k, day_of_map, sel), int(sel.sum())
+
+    def band(self, k, day_of_map, plane=None):
+        '''[N, N] int8 on `day_of_map`, the central set that of `plane` (default: the day itself): +1 inside every
+        central member, 0 inside some (the band), -1 outside all'''
+        Cs, Wc = self._subset(k, day_of_map, self.central(k, day_of_map if plane is None else plane))
+        return (Cs == Wc).astype(np.int8) - (Cs == 0).astype(np.int8)
+
+    def scenarios(self, k, day, K=None):
+        '''k_medoids of the plane with K (default: the setting) clusters, at most the members; besides its keys
+        `share` [K], the clusters' weight / W, and `members` [K], every cluster's members'''
+        K = min(check_clusters(self.clusters if K is None else K), len(self.weights))
+        out = k_medoids(set_distance(self.pairs(k, day)), self.weights, K)
+        W = float(int(self.weights.sum()))
+        out['share'] = [cw / W for cw in out['cluster_weight']]
+        out['members'] = [np.flatnonzero(out['assignment'] == c).tolist() for c in range(K)]
+        return out
+
+    def scenario_map(self, k, day_of_map, cluster, plane=None, K=None):
+        '''[N, N] float64 on `day_of_map`: the probability of >= t_k given scenario `cluster` of `plane` (default:
+        the day itself)'''
+        sc = self.scenarios(k, day_of_map if plane is None else plane, K)
+        c = _Handle._index(cluster, len(sc['medoids']), 'cluster')
+        Cs, Wc = self._subset(k, day_of_map, sc['members'][c])
+        return Cs.astype(np.float64) / float(Wc)
+
+    def jaccard(self, k, day):
+        '''[M, M] float64 I / (n_i + n_j - I), 1 where both sets are empty; nothing is decided on it'''
+        I = self.pairs(k, day).astype(np.int64)
+        n = np.diagonal(I)
+        union = n[:, None] + n[None, :] - I
+        return np.where(union > 0, I / np.maximum(union, 1), 1.0)
+
+    def planes(self, days='all'):
+        """the planes of the setting `days` that these maps have: ['all'], or the listed days among the maps'"""
+        return ['all'] if isinstance(days, str) else [d for d in days if d in self.days]
+
+
+def save_representative(outfile, rep, runs=None, chains=None, days='all'):
+    '''outfile.npz of one RepresentativeMembers through save_maps, for every threshold k and plane p of `days` ('all',
+    or the listed days the maps have): `repr_depth_{k}_{p}`, `repr_in_{k}_{p}`, `repr_cont_{k}_{p}` [members] int64,
+    `repr_median_{k}_{p}`, `repr_central_{k}_{p}` (deepest first), `repr_medoids_{k}_{p}`, `repr_assign_{k}_{p}`
+    [members], `repr_cluster_weight_{k}_{p}`, `repr_costs_{k}_{p}` (by the number of clusters) and the table itself,
+    `repr_pairs_{k}_{p}` (uint32 of a day, int64 of 'all'); `repr_weights`, `repr_thresholds`, `repr_days`; per day
+    of the maps that a plane covers dense int8 `{day}_band{k}` (dense because a zero means the band) and the CSR
+    triplets `{day}_scen{k}_{c}_*` of scenario c's conditional probability.  runs: [(chain, first row, length)]
+    per member and chains: per chain the [rows, parameters] array of the model parameters -> its block for the json:
+    the settings and per threshold and plane the median, the central set, the medoids with their shares and the
+    costs, every median and medoid with its run (chain, first_row, length, params) where runs are given'''
+    w = rep.weights
+    extra = {'repr_weights': w, 'repr_thresholds': np.asarray(rep.thresholds, dtype=np.float64),
+             'repr_days': np.asarray(rep.days)}
+    names = model_names()
+
+    def run_of(m):
+        if runs is None:
+            return None
+        ci, first, length = runs[m]
+        block = {'chain': int(ci), 'first_row': int(first), 'length': int(length)}
+        if chains is not None:
+            block['params'] = {n: float(v) for n, v in zip(names, np.asarray(chains[ci])[first])}
+        return block
+    planes, day_maps = [], {}
+    for k in range(len(rep.thresholds)):
+        for p in rep.planes(days):
+            tag = '%d_%s' % (k, p)
+            depth, w_in, w_cont = rep.depth_counts(k, p)
+            med, cen, sc = median_member(depth), rep.central(k, p), rep.scenarios(k, p)
+            extra.update({'repr_depth_' + tag: depth, 'repr_in_' + tag: w_in, 'repr_cont_' + tag: w_cont,
+                          'repr_median_' + tag: np.int64(med), 'repr_central_' + tag: np.asarray(cen, dtype=np.int64),
+                          'repr_pairs_' + tag: rep.pairs(k, p),
+                          'repr_medoids_' + tag: np.asarray(sc['medoids'], dtype=np.int64),
+                          'repr_assign_' + tag: sc['assignment'],
+                          'repr_cluster_weight_' + tag: np.asarray(sc['cluster_weight'], dtype=np.int64),
+                          'repr_costs_' + tag: np.asarray(sc['costs_by_k'], dtype=np.int64)})
+            for d in (rep.days if p == 'all' else [p]):
+                extra['%s_band%d' % (d, k)] = rep.band(k, d, p)
+                day_maps.setdefault(d, [])
+                day_maps[d] += [('_scen%d_%d' % (k, c), rep.scenario_map(k, d, c, p))
+                                for c in range(len(sc['medoids']))]
+            planes.append({'threshold': k, 'plane': p, 'median': {'member': med, 'run': run_of(med)},
+                           'central': cen, 'costs_by_k': sc['costs_by_k'],
+                           'medoids': [{'member': m, 'share': s, 'weight': cw, 'run': run_of(m)}
+                                       for m, s, cw in zip(sc['medoids'], sc['share'], sc['cluster_weight'])]})
+    save_maps(outfile, [(d, day_maps[d]) for d in rep.days if d in day_maps], extra)
+    return {'epsilon': rep.epsilon, 'central': rep.central_level, 'clusters': rep.clusters,
+            'days': days if isinstance(days, str) else list(days), 'thresholds': list(rep.thresholds),
+            'members': int(len(w)), 'total_weight': int(w.sum()), 'cell_area': rep.cell_area, 'planes': planes}
 
 MAX_RANGE_FRACTIONS = 4
 
@@ -1523,6 +1917,7 @@ class _FieldSet():
         for name in ACCUMULATORS:
             setattr(self, name, accumulators.get(name))
         self.plan = None
+        self.representative = None     # the RepresentativeMembers over `excursion`, built once the chains are merged
         self._kind = self._name = self._source = self._against = self._days = self._half = self._rw_feed = None
         self._chain = None
         self._owns = False
@@ -1572,6 +1967,8 @@ class _FieldSet():
                 mine.merge(theirs)
 
     def close(self):
+        if self.representative is not None:    # it reads the excursion maps: first
+            self.representative.close()
         for name in ACCUMULATORS:
             acc = getattr(self, name)
             for a in (acc if isinstance(acc, (list, tuple)) else [acc]):
@@ -1626,6 +2023,7 @@ class ProjectedMaps(_FieldSet):
     `information`: the InformationPosterior over the outputs (None unless asked for), likewise.  `core_range`: the
     RangeMaps.for_projection of a release plan's outputs (None unless asked for), whose maps take the output day.
     `patches`: the PatchMaps.for_projection of a release plan's outputs (None unless asked for), likewise.
+    `representative`: the RepresentativeMembers over a release plan's `excursion` (None unless asked for).
     `merge` and `close` take every accumulator there is (ACCUMULATORS).'''
 
     def __init__(self, weights, in_days, labels, summary, histogram=None, arrival=None, plan=None,
@@ -3988,13 +4386,20 @@ class PredictiveResult():
     carries an `information` of its own); `core_range`: the RangeMaps over the summary's days and
     `core_range_levels` the consensus levels of its saved regions, both None where not asked for (the plan then
     carries a `core_range` of its own); `patches`: the PatchMaps over the summary's days and `patch_levels` the
-    levels of its saved quantiles, both None where not asked for (the plan then carries a `patches` of its own).'''
+    levels of its saved quantiles, both None where not asked for (the plan then carries a `patches` of its own);
+    `representative`: the RepresentativeMembers over `excursion`, `representative_days` the planes of its saved
+    outputs ('all' or a list of days) and `representative_chains` per chain the model parameters of its rows, all
+    None where not asked for (the plan then carries a `representative` of its own).'''
 
     def __init__(self, summary, rows, evaluations, failed, seconds, runs, observations, provenance, days,
                  histogram=None, quantiles=None, arrival=None, arrival_levels=None, emergence=None, exposure=None,
                  sites=None, sensitivity=None, contrast=None, compare_plan=None, mc_error=None, mc_plan=None,
                  peak=None, excursion=None, excursion_levels=None, reweight=None, reweight_info=None, catch=None,
-                 information=None, core_range=None, core_range_levels=None, patches=None, patch_levels=None):
+                 information=None, core_range=None, core_range_levels=None, patches=None, patch_levels=None,
+                 representative=None, representative_days=None, representative_chains=None):
+        self.representative = representative
+        self.representative_days = representative_days
+        self.representative_chains = representative_chains
         self.patches = patches
         self.patch_levels = patch_levels
         self.catch = catch
@@ -4080,6 +4485,8 @@ class PredictiveResult():
         outfile_sites_range.npz), their block under `predictive.core_range` (`predictive.sites.core_range`).
         Patch maps go into outfile_patch.npz (save_patches; those of a release plan into outfile_sites_patch.npz),
         their block under `predictive.patches` (`predictive.sites.patches`).
+        Representative members go into outfile_repr.npz (save_representative; those of a release plan into
+        outfile_sites_repr.npz), their block under `predictive.representative` (`predictive.sites.representative`).
         -> (npz path, json path)'''
         s = self.summary
         if s is None:
@@ -4171,6 +4578,12 @@ class PredictiveResult():
             if pr.patches is not None:
                 meta['predictive'][name]['patches'] = save_patches('%s_%s_patch' % (outfile, name), pr.patches,
                                                                    self.patch_levels)
+        for name, rp in (('', self.representative),
+                         ('sites_', None if self.sites is None else self.sites.representative)):
+            if rp is not None:
+                block = save_representative('%s_%srepr' % (outfile, name), rp, self.runs, self.representative_chains,
+                                            self.representative_days)
+                (meta['predictive'][name[:-1]] if name else meta['predictive'])['representative'] = block
         if self.patches is not None:
             meta['predictive']['patches'] = save_patches('%s_patch' % outfile, self.patches, self.patch_levels)
         if self.core_range is not None:
@@ -4296,13 +4709,13 @@ def _check_request(q):
     '''Everything of posterior_predictive's arguments (q: a namespace of them) that can fail before any evaluation,
     in a fixed order -- of two bad arguments the earlier one is reported.  -> q, with the checked plans beside the
     arguments: cr_frac / cr_levels, in_plan, ct_plan, rw_plan / rw_names, ex_thr / ex_levels, pk_thr / pk_levels,
-    mc_batches, mc_b / mc_halves, pt_thr / pt_conn / pt_levels, s_names, levels, a_thr / a_levels, plans [(name, W, in_days, labels)], site_plan,
+    mc_batches, mc_b / mc_halves, pt_thr / pt_conn / pt_levels, rp_plan, s_names, levels, a_thr / a_levels, plans [(name, W, in_days, labels)], site_plan,
     cmp_plan, the loaded chains `prepared` [(rows, runs, model columns, observation columns, source)], `pms` (the
     models) and want_obs.'''
     pm0 = (q.pop_model[0] if q.pop_model else None) if isinstance(q.pop_model, (list, tuple)) else q.pop_model
     days, thresholds = q.days, q.thresholds
     q.cr_frac = q.cr_levels = q.in_plan = q.ct_plan = q.rw_plan = q.ex_thr = q.ex_levels = None
-    q.pk_thr = q.pk_levels = q.mc_batches = q.pt_thr = q.pt_conn = q.pt_levels = None
+    q.pk_thr = q.pk_levels = q.mc_batches = q.pt_thr = q.pt_conn = q.pt_levels = q.rp_plan = None
 
     def ndays0():                     # the model is touched only where an option needs it
         return None if pm0 is None else len(pm0.days)
@@ -4349,6 +4762,12 @@ def _check_request(q):
         if q.evaluate is not None and name not in ('information', 'catch'):
             raise ValueError('%s= needs the device: not with evaluate=' % name)
         check()
+    if q.representative is not None and q.representative is not False:
+        if q.evaluate is not None:
+            raise ValueError('representative= needs the device: not with evaluate=')
+        if not q.ex_thr:
+            raise ValueError('representative= compares the members of the excursion maps: it needs excursion=')
+        q.rp_plan = check_representative(q.representative)
     q.rw_names = q.rw_plan['names'] if q.rw_plan is not None else None
     q.s_names = check_sens_params(q.sensitivity) if q.sensitivity is not None and q.sensitivity is not False else None
     q.levels = (check_levels(q.quantiles) if q.quantiles is not None else []) or None
@@ -4447,7 +4866,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                          cell_area=None, seed=0, evaluate=None, quantiles=None, bins=DEFAULT_BINS, edges=None,
                          arrival=None, arrival_levels=(0.05, 0.5, 0.95), emergence=None, exposure=None, sites=None,
                          sensitivity=None, compare=None, mc_error=None, peak=None, excursion=None, reweight=None,
-                         catch=None, information=None, core_range=None, patches=None):
+                         catch=None, information=None, core_range=None, patches=None, representative=None):
     '''Posterior predictive spread of one or more chains (`Sampler.save` files or (trace, names) pairs). Burn and
     thin apply per chain; consecutive rows with identical model parameters are one evaluation weighted by the
     run's length.
@@ -4583,7 +5002,18 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         (`sites.patches`). Emergence and exposure get none here (PatchMaps.for_projection takes them);
         sensitivity, contrast, Monte Carlo error and reweighting of these maps are not computed. The main patch is
         the largest one, not the one at the release point. Without patches= no call is added and `patches` is
-        None.'''
+        None.
+
+    representative: True or dict(epsilon=0.02, central=0.5, clusters=3, days='all') (check_representative; needs
+        excursion=, not with evaluate=; bad arguments fail before any evaluation): which of the members is the most
+        typical one, between which outlines the central share of them lies and which scenarios they fall into, on
+        their reached sets {v >= t_k} of the excursion maps. Once the chains are merged one RepresentativeMembers
+        is built over `excursion` (`representative`; members in the order of `runs`) and, with sites=, one over
+        the plan's (`sites.representative`); nothing is added to the evaluation of a member. days: 'all' for the
+        space-time set, or the days whose own planes are saved. It compares members the chain produced: no search
+        over plans, no zones and no distance curves; depth variants, outlier fences, other distances and the Monte
+        Carlo error of these outputs are not computed. Without representative= no call is added and
+        `representative` is None.'''
     q = types.SimpleNamespace(**locals())
     t0 = time.perf_counter()
     _check_request(q)                 # bad arguments fail before any evaluation
@@ -4633,6 +5063,16 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     if errs:
         raise errs[0][1]
     day = merged.get('days', _FieldSet())
+    if q.rp_plan is not None:         # over the merged excursion maps: the members are those of run_rec below
+        settings = {n: q.rp_plan[n] for n in ('epsilon', 'central', 'clusters')}
+        try:
+            for fs in (day, merged.get('sites')):
+                if fs is not None and fs.excursion is not None:
+                    fs.representative = RepresentativeMembers(fs.excursion, **settings)
+        except BaseException:
+            for fs in merged.values():
+                fs.close()
+            raise
     rw_info = None
     if q.rw_plan is not None:
         import warnings
@@ -4683,7 +5123,9 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         peak=day.peak, excursion=day.excursion, excursion_levels=q.ex_levels if q.ex_thr else None,
         reweight=day.reweight, reweight_info=rw_info, catch=day.catch, information=day.information,
         core_range=day.core_range, core_range_levels=q.cr_levels if q.cr_frac else None,
-        patches=day.patches, patch_levels=q.pt_levels if q.pt_thr else None)
+        patches=day.patches, patch_levels=q.pt_levels if q.pt_thr else None,
+        representative=day.representative, representative_days=q.rp_plan['days'] if q.rp_plan else None,
+        representative_chains=[p[0][:, p[2]] for p in prepared] if q.rp_plan else None)
     if day.information is not None:   # the stated convention: past cap / 2 the ensemble bounds the map
         warn_information(day.information)
         if 'sites' in merged:

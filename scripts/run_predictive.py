@@ -28,7 +28,12 @@ in the member's own highest-density region holding that share of its wasps, 0.5 
 and day the probability that a cell lies in the member's main patch (the largest connected component of the cells at
 or above the density) or in a satellite, and the posterior of the patch count (--patch-connectivity 4 or 8,
 --patch-levels: the levels of the saved quantiles) -- saved as PREFIX_patch.npz (and, with --sites,
-PREFIX_sites_patch.npz for the plan); with --reweight / --reweight-file also the maps under new observations without a new chain -- up to four
+PREFIX_sites_patch.npz for the plan); with --representative (and --excursion) also the representative members -- on
+the members' reached sets at the excursion densities, over all days at once, every member's inclusion depth, the
+deepest member, the central band that holds --representative-central of the weight, and K scenarios by k-medoids on
+the area two members disagree on, each with its share and its conditional probability map; the run behind the
+deepest member and behind every medoid goes into the json -- saved as PREFIX_repr.npz (and, with --sites,
+PREFIX_sites_repr.npz for the plan); with --reweight / --reweight-file also the maps under new observations without a new chain -- up to four
 named scenarios, each a list of probe observations 'east,north,day,kind,rate[,n]' (kind: count with the number
 found n, none, found; rate: the expected number found per wasp in the cell) or a .npy file of one log-weight per
 chain row after burn and thin (several chains: concatenated in chain order), by importance reweighting of the
@@ -52,6 +57,7 @@ Without --chain a short chain is sampled first (--samples) and saved next to --o
         [--excursion 1,10] [--excursion-levels 0.9,0.95]
         [--core-range 0.5,0.95] [--core-range-levels 0.5,0.9]
         [--patches 1,10] [--patch-connectivity 8] [--patch-levels 0.05,0.5,0.95]
+        [--representative [K]] [--representative-epsilon 0.02] [--representative-central 0.5]
         [--reweight 'NAME:east,north,day,kind,rate[,n];...'] [--reweight-file NAME=weights.npy]
         [--catch 'DAY,RATE[,N];...'] [--catch-levels 0.5,0.95] [--catch-emergence 'OBSDAY,RATE[,N];...']
         [--information 'DAY,RATE[,YMAX];...']
@@ -154,6 +160,15 @@ def main():
     ap.add_argument('--patch-connectivity', type=int, default=4, help='4 or 8 neighbours (with --patches)')
     ap.add_argument('--patch-levels', default='0.05,0.5,0.95',
                     help='levels in (0, 1] of the saved patch-count and area quantiles (with --patches)')
+    ap.add_argument('--representative', nargs='?', const=3, type=int, default=None, metavar='K',
+                    help='representative members on the excursion sets: inclusion depth, the deepest member, the '
+                         'central band and K scenarios (default 3, 1..8); needs --excursion (default: off)')
+    ap.add_argument('--representative-epsilon', type=float, default=0.02,
+                    help='share of its own cells a member may have outside another and still count as inside it, a '
+                         'multiple of 0.001 in [0, 0.5] (with --representative)')
+    ap.add_argument('--representative-central', type=float, default=0.5,
+                    help='share of the weight the central band holds, a multiple of 0.001 in (0, 1] (with '
+                         '--representative)')
     ap.add_argument('--catch', default='', help="traps 'DAY,RATE[,N];...': per cell the probability that a trap of "
                     'effort RATE on model day DAY catches at least N (default 1) (default: off)')
     ap.add_argument('--catch-levels', default='0.5,0.95', help='levels of the catch maps (with --catch)')
@@ -209,6 +224,13 @@ def main():
         core_range = dict(fractions=[float(t) for t in args.core_range.split(',') if t.strip()],
                           levels=[float(q) for q in args.core_range_levels.split(',') if q.strip()])
         check_core_range(core_range)
+    representative = None
+    if args.representative is not None:  # as do bad --representative settings, or none without --excursion
+        from parasitoids_amd.predictive import check_representative
+        if not excursion:
+            ap.error('--representative needs --excursion')
+        representative = check_representative(dict(clusters=args.representative, epsilon=args.representative_epsilon,
+                                                   central=args.representative_central))
     patches = None
     if args.patches:                     # as do bad --patches thresholds, connectivity or levels
         from parasitoids_amd.predictive import check_patches
@@ -304,7 +326,8 @@ def main():
                                **({'catch': catch} if catch else {}),
                                **({'information': information} if information else {}),
                                **({'core_range': core_range} if core_range else {}),
-                               **({'patches': patches} if patches else {}))
+                               **({'patches': patches} if patches else {}),
+                               **({'representative': representative} if representative else {}))
     dt = time.perf_counter() - t0
     # accumulate-kernel time: the same members once more with HIP events around every add
     from parasitoids_amd.predictive import (ArrivalMaps, ExcursionMaps, MonteCarloError, PeakMaps, PlanContrast, Projection,
@@ -445,6 +468,8 @@ def main():
         ex_ms, ex_launches = EX.profile()[:2]
         EX.close()
         res.excursion.profile(True)     # the finalize and every map launch of the save
+    if representative:
+        res.representative.overlap.profile(True)     # every pair table and subset plane of the save
     if RG is not None:
         rg_ms, rg_launches = RG.profile()[:2]
         RG.close()
@@ -562,6 +587,15 @@ def main():
         out['range_maps_ms_total'] = round(res.core_range.profile()[2], 3)
         out['range_bytes'] = res.core_range.nbytes
         out['outputs'] += ['%s_range.npz' % args.out] + (['%s_sites_range.npz' % args.out] if sites else [])
+    if representative:
+        rp_prof = res.representative.overlap.profile()
+        out['repr_pairs_ms'] = round(rp_prof[0], 3)              # over repr_pairs_calls planes, the save's
+        out['repr_pairs_calls'] = rp_prof[1]
+        out['repr_subset_ms'] = round(rp_prof[2], 3)
+        out['repr_subset_launches'] = rp_prof[3]
+        out['repr_members'] = res.excursion.members
+        out['repr_bytes'] = res.representative.overlap.nbytes
+        out['outputs'] += ['%s_repr.npz' % args.out] + (['%s_sites_repr.npz' % args.out] if sites else [])
     if patches:
         out['patch_thresholds'] = patches['thresholds']
         out['patch_connectivity'] = patches['connectivity']
@@ -621,7 +655,7 @@ def main():
         res.sensitivity.close()
     if res.mc_error is not None:
         res.mc_error.close()
-    for pr in (res.emergence, res.exposure, res.sites, res.contrast, res.peak, res.excursion, res.catch, res.information,
+    for pr in (res.representative, res.emergence, res.exposure, res.sites, res.contrast, res.peak, res.excursion, res.catch, res.information,
                res.core_range, res.patches):
         if pr is not None:
             pr.close()
