@@ -82,6 +82,21 @@ int ps_row_live_units(int P, int M, int np, int nd, const int32_t* ranges, int32
  * kernel batches of the full-column pipeline go to the persistent kernel there (no device needed); < 0 when
  * the size has no register-resident kernels. */
 int ps_row_fwd_info(int fft_len, int* np, int* persistent);
+/* Whether kernel batches with K x K boxes can go to the STAGED persistent kernel at FFT size fft_len (the next
+ * unit's source rows copied to LDS while one is transformed; option PS_FWD_STAGE, off by default): its exchange
+ * buffers and 2 np rows of K doubles in whole 1 KB chunks must fit in 160 KB together, else the plain
+ * persistent kernel runs (no device needed);
+ * < 0 when the size has no register-resident kernels.  ps_row_fwd_stage_lds: that kernel's LDS bytes (0: the
+ * size keeps the one-shot kernel); ps_row_fwd_stage_bytes: the staged rows' share for np row pairs. */
+int ps_row_fwd_stage_info(int fft_len, int K, int* staged);
+int64_t ps_row_fwd_stage_lds(int fft_len, int K);
+int64_t ps_row_fwd_stage_bytes(int np, int K);
+/* The staging layout, for tests (no device needed).  slot: the double of the staging area that holds source
+ * column col of staged row r when the source row starts at parity e (address / 8 mod 2); walk: the copy of
+ * source row `row` of a 16-byte aligned buffer of rows x K doubles (K odd) into staged row r of nstaged --
+ * image[slot] = index of the source element the copy puts there (untouched where it writes nothing). */
+int ps_row_fwd_stage_slot(int K, int r, int e, int col);
+int ps_row_fwd_stage_walk(int K, int64_t rows, int64_t row, int r, int nstaged, int64_t* image);
 
 /* ---- solver: replaces class cuda_lib.CudaSolve (cuda_lib.py:16-221) and the
  *      CPU primitives CalcSol.fft2/fftconv2/ifft2/back_solve (CalcSol.py:11-109) */

@@ -58,6 +58,11 @@ SIGNATURES = {
     'ps_device_info': (C.c_int, [C.c_int, C.c_char_p, C.c_int, _I32P, _I64P]),
     'ps_row_live_units': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _I32P, _I32P, _I32P, C.c_int]),
     'ps_row_fwd_info': (C.c_int, [C.c_int, _I32P, _I32P]),
+    'ps_row_fwd_stage_info': (C.c_int, [C.c_int, C.c_int, _I32P]),
+    'ps_row_fwd_stage_lds': (C.c_int64, [C.c_int, C.c_int]),
+    'ps_row_fwd_stage_bytes': (C.c_int64, [C.c_int, C.c_int]),
+    'ps_row_fwd_stage_slot': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    'ps_row_fwd_stage_walk': (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, _I64P]),
     'ps_solver_create': (C.c_int, [C.POINTER(_VP), C.c_int, C.c_int, C.c_int, C.c_int]),
     'ps_solver_destroy': (C.c_int, [_VP]),
     'ps_solver_info': (C.c_int, [_VP, _I32P, _I32P, _I32P, _I32P]),

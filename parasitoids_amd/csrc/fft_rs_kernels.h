@@ -5,6 +5,7 @@
 #include "fft_kernels.h"
 #include "fft_rs.h"
 #include "row_live_units.h"
+#include "row_fwd_stage.h"
 #include <type_traits>
 
 
@@ -922,7 +923,9 @@ __global__ void __launch_bounds__((2 * Rs<R1, R2, R3>::NTHR)) k_row_inv_rs2(RowI
 //   rs_fwd_load    the first stage's loads, always in bounds (pa / pb show at row 0 for a dead row), zero
 //                  outside the column map and for a dead row
 //   rs_fwd_finish  three stages, the mirrored-element exchange, the stores of the half spectra (`live`
-//                  false: none -- a dead pair that shares a persistent workgroup's unit with a live one)
+//                  false: none -- a dead pair that shares a persistent workgroup's unit with a live one);
+//                  RAW: barriers without the memory fence and one wait for vector memory before the stores
+//                  (k_row_fwd_rsps, whose copy of the next unit's rows is in flight meanwhile)
 template <class S, int R1>
 __device__ __forceinline__ void rs_fwd_load(cplx* x, const double* pa, const double* pb, const SrcMap& cmap, int j, bool la, bool lb) {
 #pragma unroll
@@ -934,21 +937,21 @@ __device__ __forceinline__ void rs_fwd_load(cplx* x, const double* pa, const dou
     x[q] = make_double2((ok && la) ? va : 0.0, (ok && lb) ? vb : 0.0);
   }
 }
-template <class S, int R1, int R2, int R3>
+template <class S, int R1, int R2, int R3, bool RAW = false>
 __device__ __forceinline__ void rs_fwd_finish(cplx* x, double* ex, const int j, const cplx w2, const cplx w3,
                                               cplx* da, cplx* db, const int64_t kst, const bool live, const bool hasb) {
   constexpr int L = S::L;
   if (j < S::T1) bfly<R1, PS_FWD>(x);
-  rs_tail<S, R1, R2, R3, PS_FWD>(x, ex, j, w2, w3);
+  rs_tail<S, R1, R2, R3, PS_FWD, RAW>(x, ex, j, w2, w3);
   // mirrored elements through LDS: Z_k of thread j sits at word k = j + q T3
   cplx zm[R3 / 2 + 1];
   constexpr int NQ = R3 / 2 + 1;   // slots q with j + q T3 <= L/2 for some j
-  __syncthreads();
+  rs_bar<RAW>();
   if (j < S::T3) {
 #pragma unroll
     for (int q = 0; q < R3; ++q) ex[j + q * S::T3] = x[q].x;
   }
-  __syncthreads();
+  rs_bar<RAW>();
   if (j < S::T3) {
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
@@ -956,12 +959,15 @@ __device__ __forceinline__ void rs_fwd_finish(cplx* x, double* ex, const int j, 
       zm[q].x = ex[k ? L - k : 0];
     }
   }
-  __syncthreads();
+  rs_bar<RAW>();
   if (j < S::T3) {
 #pragma unroll
     for (int q = 0; q < R3; ++q) ex[j + q * S::T3] = x[q].y;
   }
-  __syncthreads();
+  rs_bar<RAW>();
+  // RAW (k_row_fwd_rsps): the copy of the next unit's rows has had the whole transform to land; waiting
+  // for it HERE, before this unit's stores are issued, keeps the stores out of every later wait
+  if (RAW) PS_WAIT_VM0();
   if (j < S::T3 && live) {
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
@@ -1062,8 +1068,26 @@ __global__ void __launch_bounds__((Rs<R1, R2, R3>::NTHR * NP)) k_row_fwd_rs(RowF
 // 8 KL, the KL units of a line run in the same round on one XCD.  Speed only: every unit is complete in
 // itself and nothing is handed from one workgroup to another.  Units of a line without a live row (run
 // edges) are walked past.
-template <int R1, int R2, int R3, int NP>
-__global__ void __launch_bounds__((Rs<R1, R2, R3>::NTHR * NP)) k_row_fwd_rsp(RowFwdArgs a, int count, int total) {
+//
+// STAGE (k_row_fwd_rsps): the 2 NP source rows of the NEXT live unit are copied HBM -> LDS by the load unit
+// (global_load_lds_dwordx4, row_fwd_stage.h) while this unit is transformed, as in k_row_inv_rsp.  Loads and
+// stores retire through one in-order counter, so the plain kernel's first-stage loads of a unit cannot
+// return before the column-major stores of the unit before (one 128-byte line per lane) have drained, and
+// its __syncthreads() at the top of the round drains them too: the stores are fully exposed.  Here a round is
+//   barrier (chunks visible, last round's mirrored reads done) -> first stage from LDS -> barrier (staging
+//   free) -> issue the copy for the next unit -> three stages and the mirrored exchange on raw barriers ->
+//   wait for the copy -> stores,
+// so the only wait on vector memory stands BEFORE the stores are issued and finds a copy that has had a whole
+// transform to land and stores that are a transform old.  Nothing with a vector-register destination is
+// loaded from global memory while a copy is outstanding (the row ranges are scalar loads).  The staging area
+// lies behind the NP exchange buffers in the one dynamic array: RsCfg::LDS + fstage_bytes(NP, src_ld), the
+// launcher's fit test.  A dead row of a live unit is not copied (wave-uniform) and masked in the first stage
+// exactly as rs_fwd_load masks it.  The arithmetic is rs_fwd_finish either way.
+// Measured: 15-20 us of the 30-day launch at 5184 points and nothing on the stack -- what the
+// stores cost is the rate at which they are TAKEN, not their latency -- so the launcher takes this kernel on
+// request only (PS_FWD_STAGE=1).
+template <int R1, int R2, int R3, int NP, bool STAGE>
+__device__ __forceinline__ void row_fwd_rsp_body(const RowFwdArgs& a, int count, int total, const double* src_end) {
   using S = Rs<R1, R2, R3>;
   using Y = RsInvLds<R1, R2, R3>;
   constexpr int KL = NP >= 4 ? 1 : 4 / NP;
@@ -1127,6 +1151,62 @@ __global__ void __launch_bounds__((Rs<R1, R2, R3>::NTHR * NP)) k_row_fwd_rsp(Row
     return total;
   };
 
+  if constexpr (STAGE) {
+    constexpr int NW = S::NTHR / 64;
+    const int K = a.src_ld, nch = fstage_chunks(K);
+    double* stage = reinterpret_cast<double*>(ps_lds_raw) + NP * (Y::XW + Y::RED);
+    const int wv = __builtin_amdgcn_readfirstlane(j0 >> 6);
+    // rows a and b of this half -> staged rows 2 half, 2 half + 1; its waves copy the chunks wv, wv + NW, ...
+    auto copy = [&](const Pair& p, int lane) {
+      for (int id = wv; id < 2 * nch; id += NW) {       // wave-uniform
+        const int which = id >= nch ? 1 : 0, ch = id - which * nch;
+        if ((which ? p.sb : p.sa) < 0) continue;        // a dead row is not read at all
+        const double* row = which ? p.pb : p.pa;
+        const int e = (int)(((uintptr_t)row >> 3) & 1);
+        const double* base = row - e;                   // 16-byte aligned
+        const int64_t room = src_end - base;
+        const int w = fstage_word(K, e, room, ch, lane);
+        double* d = stage + fstage_slot(K, 2 * half + which, 0, 0) + ch * 128;   // + lane * 16 B by the instruction
+        if (w >= 0) __builtin_amdgcn_global_load_lds(base + 2 * w, (ps_lds_ptr)d, 16, 0, 0);
+        if (fstage_tail(K, e, room) && ch == fstage_last(K, e) / 64 && lane < 2) {
+          // the row that ends the buffer: its last element as two 4-byte words (+ lane * 4 B by the instruction)
+          const unsigned* g = reinterpret_cast<const unsigned*>(row + (K - 1)) + lane;
+          __builtin_amdgcn_global_load_lds(g, (ps_lds_ptr)(stage + fstage_slot(K, 2 * half + which, e, K - 1)), 4, 0, 0);
+        }
+      }
+    };
+    Pair c, n;
+    int i = next_unit(wg, c), ni = total;
+    if (i < total) copy(c, j0 & 63);
+    PS_WAIT_VM0();
+    for (; i < total; i = ni, c = n) {                    // uniform per workgroup
+      ni = next_unit(i + (int)gridDim.x, n);
+      // opaque per-round copies: see k_row_inv_rsp
+      int j = j0;
+      cplx w2 = w2c, w3 = w3c;
+      asm volatile("" : "+v"(j), "+v"(w2.x), "+v"(w2.y), "+v"(w3.x), "+v"(w3.y));
+      PS_BAR_LDS();                                       // every wave's chunks of this unit are visible; the last
+                                                          // round's mirrored elements have been read
+      cplx x[S::RMAX];
+      if (j < S::T1) {
+        const bool la = c.sa >= 0, lb = c.sb >= 0;
+        const double* ra = stage + fstage_slot(K, 2 * half, (int)(((uintptr_t)c.pa >> 3) & 1), 0);
+        const double* rb = stage + fstage_slot(K, 2 * half + 1, (int)(((uintptr_t)c.pb >> 3) & 1), 0);
+#pragma unroll
+        for (int q = 0; q < R1; ++q) {                    // = rs_fwd_load, from the staged rows
+          const int sc = src_map(a.cmap, j + q * S::T1);
+          const bool ok = sc >= 0;
+          const int cc = ok ? sc : 0;
+          const double va = ra[cc], vb = rb[cc];          // always inside the staged row; masked below
+          x[q] = make_double2((ok && la) ? va : 0.0, (ok && lb) ? vb : 0.0);
+        }
+      }
+      PS_BAR_LDS();                                       // staging is free again
+      if (ni < total) copy(n, j & 63);
+      rs_fwd_finish<S, R1, R2, R3, true>(x, ex, j, w2, w3, c.da, c.db, kst, c.sa >= 0 || c.sb >= 0, c.hasb);
+    }
+    return;
+  }
   Pair c;
   for (int i = next_unit(wg, c); i < total; i = next_unit(i + (int)gridDim.x, c)) {   // uniform per workgroup
     // opaque per-round copies: see k_row_inv_rsp
@@ -1141,4 +1221,13 @@ __global__ void __launch_bounds__((Rs<R1, R2, R3>::NTHR * NP)) k_row_fwd_rsp(Row
     __builtin_amdgcn_sched_barrier(0);                 // every load of the round is issued before the first butterfly
     rs_fwd_finish<S, R1, R2, R3>(x, ex, j, w2, w3, c.da, c.db, kst, c.sa >= 0 || c.sb >= 0, c.hasb);
   }
+}
+template <int R1, int R2, int R3, int NP>
+__global__ void __launch_bounds__((Rs<R1, R2, R3>::NTHR * NP)) k_row_fwd_rsp(RowFwdArgs a, int count, int total) {
+  row_fwd_rsp_body<R1, R2, R3, NP, false>(a, count, total, nullptr);
+}
+// src_end: end of the last source slot of the batch (a.src + count * a.src_bstride); nothing is read from there on
+template <int R1, int R2, int R3, int NP>
+__global__ void __launch_bounds__((Rs<R1, R2, R3>::NTHR * NP)) k_row_fwd_rsps(RowFwdArgs a, int count, int total, const double* src_end) {
+  row_fwd_rsp_body<R1, R2, R3, NP, true>(a, count, total, src_end);
 }

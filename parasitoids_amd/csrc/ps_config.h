@@ -55,6 +55,8 @@
   X("PS_NO_PAD_QUIET", no_pad_quiet, 0, FLAG, R)                                                    \
   X("PS_NO_TAIL_SPLIT", no_tail_split, 0, FLAG, R)                                                  \
   X("PS_NO_FWD_PERSIST", no_fwd_persist, 0, FLAG, R)                                                \
+  X("PS_NO_FWD_SOLO", no_fwd_solo, 0, FLAG, R)                                                      \
+  X("PS_FWD_STAGE", fwd_stage, 0, FLAG, R)                                                          \
   X("PS_NO_DEFER_REFFT", no_defer_refft, 0, FLAG, R)                                                \
   X("PS_NO_FILTER_CACHE", no_filter_cache, 0, FLAG, R)                                              \
   X("PS_NO_FOLD_FUSE", no_fold_fuse, 0, FLAG, R)                                                    \

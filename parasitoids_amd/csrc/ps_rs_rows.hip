@@ -40,11 +40,34 @@ bool rs_info(int r2, int r3, RsInfo* out) {
 template <int R2, int R3>
 constexpr bool rs_fwd_live_ok() { return RsCfg<R2, R3>::NP >= 2; }
 
+// The sizes with TWO pairs per workgroup (five or six waves per pair; the headline's 5184 and 4608 among them)
+// run the persistent kernel with ONE pair per workgroup, two workgroups resident per CU: the two
+// halves of a two-pair workgroup pass the same barriers, so both issue their column-major stores at the same
+// time and both wait while they are taken; two workgroups drift into anti-phase.  Measured at 5184 only; the
+// three- and four-pair sizes keep their workgroups.
+template <int R2, int R3>
+constexpr bool rs_fwd_solo() { return RsCfg<R2, R3>::NP == 2; }
+
 bool rs_row_fwd_info(int r2, int r3, int* np, int* persistent) {
 #define X(A, B) if (r2 == A && r3 == B) { *np = RsCfg<A, B>::NP; *persistent = rs_fwd_live_ok<A, B>() ? 1 : 0; return true; }
   PS_RS_SIZES(X)
 #undef X
   return false;
+}
+
+// The staged kernel (k_row_fwd_rsps) needs the exchange buffers and 2 NP source rows of src_ld doubles in
+// whole 1 KB chunks side by side in LDS (row_fwd_stage.h): a question of the kernel box, not of the size alone.
+// 0 when (r2, r3) is not served or keeps the one-shot kernel.
+static const size_t kRsMaxLds = (size_t)160 * 1024;
+size_t rs_row_fwd_stage_lds(int r2, int r3, int src_ld) {
+#define X(A, B) if (r2 == A && r3 == B) return rs_fwd_live_ok<A, B>() && src_ld > 0 ? RsCfg<A, B>::LDS + fstage_bytes(RsCfg<A, B>::NP, src_ld) : 0;
+  PS_RS_SIZES(X)
+#undef X
+  return 0;
+}
+bool rs_row_fwd_staged(int r2, int r3, int src_ld) {
+  const size_t b = rs_row_fwd_stage_lds(r2, r3, src_ld);
+  return b > 0 && b <= kRsMaxLds;
 }
 
 int rs_rows_set_attrs() {
@@ -76,6 +99,15 @@ int rs_rows_set_attrs() {
         auto kl = k_row_fwd_rsp<16, A, B, np>;                                                               \
         if (hipFuncSetAttribute((const void*)kl, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS) != hipSuccess) return -1; \
       }                                                                                                      \
+    }                                                                                                        \
+    if constexpr (rs_fwd_live_ok<A, B>()) {   /* exchange buffers + staged rows: up to the whole CU */       \
+      auto ks = k_row_fwd_rsps<16, A, B, np>;                                                                \
+      if (hipFuncSetAttribute((const void*)ks, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRsMaxLds) != hipSuccess) return -1; \
+    }                                                                                                        \
+    if constexpr (rs_fwd_solo<A, B>()) {                                                                     \
+      auto k1 = k_row_fwd_rsp<16, A, B, 1>;                                                                  \
+      if (C::LDSC1 > 48 * 1024 &&                                                                            \
+          hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDSC1) != hipSuccess) return -1; \
     }                                                                                                        \
   }
   PS_RS_SIZES(X)
@@ -123,7 +155,10 @@ int rs_launch_row_fwd(int r2, int r3, const RowFwdArgs& a, int npairs, int batch
 
 // Kernel batches of the full-column pipeline: one persistent workgroup per CU slot over the live units
 // (k_row_fwd_rsp).  hranges: host copy of a.rowrange, [batch][2].
-int rs_launch_row_fwd_live(int r2, int r3, const RowFwdArgs& a, const int* hranges, int batch, hipStream_t st) {
+// stage: take k_row_fwd_rsps where its staging area fits (rs_row_fwd_staged) and every source column of the
+// column map lies inside a staged row.
+int rs_launch_row_fwd_live(int r2, int r3, const RowFwdArgs& a, const int* hranges, int batch, hipStream_t st,
+                           bool stage, bool solo) {
 #define X(A, B)                                                                                              \
   if (r2 == A && r3 == B) {                                                                                  \
     using C = RsCfg<A, B>;                                                                                   \
@@ -138,6 +173,25 @@ int rs_launch_row_fwd_live(int r2, int r3, const RowFwdArgs& a, const int* hrang
     constexpr int kw = 12 / W < 1 ? 1 : 12 / W, kld = (int)((size_t)160 * 1024 / C::LDS);                    \
     constexpr int per_cu = kw < kld ? kw : (kld < 1 ? 1 : kld);                                              \
     const int m = 8 * kl;                                                                                    \
+    const int cmax = std::max(a.cmap.n1 - 1 + a.cmap.off1, a.P - 1 - a.cmap.lo2 + a.cmap.off2);             \
+    if (stage && rs_row_fwd_staged(r2, r3, a.src_ld) && cmax < a.src_ld && a.cmap.off1 >= 0 && a.cmap.off2 >= 0) { \
+      const size_t lds = C::LDS + fstage_bytes(np, a.src_ld);                                                \
+      const int kls = (int)(kRsMaxLds / lds), per_cu_s = kw < kls ? kw : kls;                                \
+      const int wgs = (std::min(total, device_cus() * per_cu_s) + m - 1) / m * m;                            \
+      auto ks = k_row_fwd_rsps<16, A, B, np>;                                                                \
+      hipLaunchKernelGGL(ks, dim3(wgs), dim3(C::S::NTHR * np), lds, st, a, batch, total,                     \
+                         a.src + (int64_t)batch * a.src_bstride);                                            \
+      return 1;                                                                                              \
+    }                                                                                                        \
+    if constexpr (rs_fwd_solo<A, B>()) {                                                                     \
+      if (solo) {   /* one pair per workgroup: four units per output line, two workgroups per CU */          \
+        const int total1 = 4 * live_total(a.rmap.n1, a.rmap.off1, a.rmap.lo2, a.rmap.off2, a.P, hranges, batch, 8); \
+        const int wgs1 = (std::min(total1, device_cus() * 2) + 31) / 32 * 32;                                \
+        auto k1 = k_row_fwd_rsp<16, A, B, 1>;                                                                \
+        hipLaunchKernelGGL(k1, dim3(wgs1), dim3(C::S::NTHR), C::LDSC1, st, a, batch, total1);                \
+        return 1;                                                                                            \
+      }                                                                                                      \
+    }                                                                                                        \
     const int wgs = (std::min(total, device_cus() * per_cu) + m - 1) / m * m;                                \
     auto kern = k_row_fwd_rsp<16, A, B, np>;                                                                 \
     hipLaunchKernelGGL(kern, dim3(wgs), dim3(C::S::NTHR * np), C::LDS, st, a, batch, total);                 \

@@ -7,6 +7,7 @@
 #include "fft_kernels.h"
 #include "fft_colfull_kernels.h"   // ColFullArgs (the kernels are instantiated in ps_colfull.hip)
 #include "rs_launch.h"
+#include "row_fwd_stage.h"
 #include "ps_common.h"
 #include "ps_config.h"
 
@@ -24,6 +25,36 @@ extern "C" int ps_row_fwd_info(int fft_len, int* np, int* persistent) {
   if (!rs_lookup(fft_len, &r2, &r3) || !rs_row_fwd_info(r2, r3, &n, &p)) return -1;
   if (np) *np = n;
   if (persistent) *persistent = p;
+  return 0;
+}
+
+extern "C" int ps_row_fwd_stage_info(int fft_len, int K, int* staged) {
+  int r2 = 0, r3 = 0, n = 0, p = 0;
+  if (K < 1 || !rs_lookup(fft_len, &r2, &r3) || !rs_row_fwd_info(r2, r3, &n, &p)) return -1;
+  if (staged) *staged = p && rs_row_fwd_staged(r2, r3, K) ? 1 : 0;
+  return 0;
+}
+extern "C" int64_t ps_row_fwd_stage_bytes(int np, int K) { return np < 1 || K < 1 ? -1 : (int64_t)fstage_bytes(np, K); }
+extern "C" int64_t ps_row_fwd_stage_lds(int fft_len, int K) {
+  int r2 = 0, r3 = 0;
+  if (K < 1 || !rs_lookup(fft_len, &r2, &r3)) return -1;
+  return (int64_t)rs_row_fwd_stage_lds(r2, r3, K);
+}
+extern "C" int ps_row_fwd_stage_slot(int K, int r, int e, int col) {
+  return K < 1 || r < 0 || (e != 0 && e != 1) || col < 0 || col >= K ? -1 : fstage_slot(K, r, e, col);
+}
+extern "C" int ps_row_fwd_stage_walk(int K, int64_t rows, int64_t row, int r, int nstaged, int64_t* image) {
+  if (K < 1 || !(K & 1) || rows < 1 || row < 0 || row >= rows || r < 0 || r >= nstaged || !image) return -1;
+  // what the kernel's copy does for one row, element indices instead of values
+  const int e = (int)((row * K) & 1);
+  const int64_t base = row * K - e, room = rows * K - base;
+  for (int ch = 0; ch < fstage_chunks(K); ++ch)
+    for (int lane = 0; lane < 64; ++lane) {
+      const int w = fstage_word(K, e, room, ch, lane);
+      const int d = fstage_slot(K, r, 0, 0) + ch * 128 + 2 * lane;
+      if (w >= 0) { image[d] = base + 2 * (int64_t)w; image[d + 1] = base + 2 * (int64_t)w + 1; }
+      if (fstage_tail(K, e, room) && ch == fstage_last(K, e) / 64 && lane == 0) image[fstage_slot(K, r, e, K - 1)] = row * K + K - 1;
+    }
   return 0;
 }
 
@@ -449,8 +480,10 @@ static int launch_row_fwd(ps_solver* s, const double* src, int64_t src_bstride, 
   const bool live_list = s->rs_r2 != 0 && !s->cfg.no_rs_fwd && a.tstride && skip_zero && !pred && !trunc_pred &&
                          !s->cfg.no_fwd_persist && kfirst >= 0 && rowrange &&
                          2 * ((size_t)kfirst + batch) <= s->hkrange.size();
+  // PS_NO_FWD_SOLO=1: A/B knob (workgroups of RsCfg::NP row pairs at the two-pair sizes, as at the others);
+  // PS_FWD_STAGE=1: the staged kernel where its LDS fits (measured, not the default: DESIGN 4.1h).
   if (live_list) {
-    if (!rs_launch_row_fwd_live(s->rs_r2, s->rs_r3, a, s->hkrange.data() + 2 * kfirst, batch, s->stream))
+    if (!rs_launch_row_fwd_live(s->rs_r2, s->rs_r3, a, s->hkrange.data() + 2 * kfirst, batch, s->stream, s->cfg.fwd_stage != 0, !s->cfg.no_fwd_solo))
       return ps_fail(PS_ERR_STATE, "no register-resident row kernel for 16 x %d x %d", s->rs_r2, s->rs_r3);
   } else if (s->rs_r2 != 0 && !s->cfg.no_rs_fwd) {
     if (!rs_launch_row_fwd(s->rs_r2, s->rs_r3, a, npairs, batch, s->stream))

@@ -31,7 +31,17 @@ int rs_launch_row_inv(int r2, int r3, const RowInvArgs& a, int npairs, int batch
 // rs_row_fwd_info: row pairs per workgroup of the forward row kernels of a size and whether its kernel
 // batches go to k_row_fwd_rsp; false when (r2, r3) is not served.
 bool rs_row_fwd_info(int r2, int r3, int* np, int* persistent);
-int rs_launch_row_fwd_live(int r2, int r3, const RowFwdArgs& a, const int* hranges, int batch, hipStream_t st);
+// solo: at the sizes with two row pairs per workgroup (5184 and 4608 points among them) launch workgroups of ONE
+// pair, two resident per CU, which drift into anti-phase: one transforms while the other's stores are taken.
+// stage: the staged kernel (k_row_fwd_rsps: the next unit's source rows copied HBM -> LDS while one is
+// transformed) where rs_row_fwd_staged says its LDS fits for rows of a.src_ld doubles; it keeps the workgroup
+// of RsCfg::NP pairs and goes before `solo`.
+int rs_launch_row_fwd_live(int r2, int r3, const RowFwdArgs& a, const int* hranges, int batch, hipStream_t st,
+                           bool stage, bool solo);
+// LDS of the staged kernel for source rows of src_ld doubles (0: size not served by the persistent kernels),
+// and whether the launcher takes it (<= 160 KB)
+size_t rs_row_fwd_stage_lds(int r2, int r3, int src_ld);
+bool rs_row_fwd_staged(int r2, int r3, int src_ld);
 // live units (np row pairs each) of `nd` entries with source-row ranges [nd][2] under map_wrap(M, P), in
 // list order: entry and unit of the first `cap`; returns their number (host only, see ps_row_live_units)
 int rs_row_live_units(int P, int M, int np, int nd, const int* ranges, int* day, int* unit, int cap);
