@@ -1290,6 +1290,66 @@ int ps_overlap_prof(ps_overlap* h, int enable, double* pairs_ms, int64_t* pairs_
                     int64_t* subset_n);
 void ps_overlap_destroy(ps_overlap* h);
 
+/* ---- neighbourhood fields: the largest value of one member's field within r of each cell ----
+ * (no reference counterpart; the neighbourhood maximum of Schwartz & Sobash 2017, whose ensemble statistics the
+ * accumulators below then take.)  A handle lives on one device and holds nout outputs (1..32) over nin inputs
+ * (1..32): output e is (input[e], r2[e]) with 0 <= input[e] < nin and r2[e] a whole squared radius in cells with
+ * H = floor(sqrt(r2[e])) <= PS_NBHD_MAX_HALF = 32, i.e. 0 <= r2[e] <= 1088 (PS_ERR_BAD_ARG otherwise), and nout fp64
+ * fields Z[e][pitch] (pitch as ps_summary).  With v the value of input[e], an apply overwrites every cell of every
+ * output, zeros included, with
+ *   Z_e(y, x) = max { v(y', x') : 0 <= y', x' < N,  (y' - y)^2 + (x' - x)^2 <= r2[e] }.
+ * Cells outside the domain do not exist: nothing wraps and no padding value takes part.  r2 = 0 gives Z = v.  A
+ * maximum is exact, so Z is the same whatever the tile, the launch shape or the order of the comparisons.
+ * The disc is a stack of horizontal chords of half-width w(dy) = floor(sqrt(r2 - dy^2)), |dy| <= H; the maximum
+ * over a chord clipped to the domain, len cells from column a, is max(L_k(a), L_k(a + len - 2^k)) with
+ * k = floor(log2(len)) and L_k(y, x) = max v(y, x .. x + 2^k - 1).  One workgroup owns a tile of 32 x 64 cells of
+ * one input and up to 8 of the outputs that read it (the outputs are grouped by input): it stages v of the tile
+ * and a halo of the largest H among them -- only the cells of the domain -- in LDS ((32 + 2H)(64 + 2H) 8 B, 98304 B
+ * at H = 32), folds at every level k the chords of that level into register accumulators that start from the
+ * centre cell, and doubles the windows in place between two barriers.  Work per cell grows like H, not H^2.  One
+ * writer per cell, no atomics.  Unless switched off (ps_nbhd_set_skip), a pre-pass writes per input and tile
+ * whether the tile holds a value != 0, and a tile whose own and eight neighbouring tiles are all empty stores zeros
+ * without staging; the outputs are the same either way.  The handle holds nout * pitch * 8 B and nin int32 flags
+ * per tile (nin * ceil(N / 32) * ceil(N / 64) * 4 B), checked against the free device memory first: PS_ERR_OOM
+ * before anything is allocated.  Every operation records an event the next one waits on, whichever stream it runs
+ * on (the solver's for ps_nbhd_apply, the handle's own for the other applies, fetch and gather, the accumulator's
+ * for the _add_nbhd entry points). */
+#define PS_NBHD_MAX_HALF 32
+typedef struct ps_nbhd ps_nbhd;
+int ps_nbhd_create(int device, int N, int nin, int nout, const int32_t* input /* nout */,
+                   const int32_t* r2 /* nout */, ps_nbhd** out);
+/* on != 0 (the default): the empty-tile pre-pass; 0: every tile is staged.  Takes effect at the next apply. */
+int ps_nbhd_set_skip(ps_nbhd* c, int on);
+/* The inputs are records of solver s (same device, same N; arguments as ps_catch_apply, nin must equal the
+ * handle's; v is the value ps_summary_add adds, bit for bit): on the solver's stream, no host synchronisation,
+ * nothing copied or allocated.  Every descriptor is resolved before anything is enqueued. */
+int ps_nbhd_apply(ps_nbhd* c, ps_solver* s, int nin, const int32_t* kind, const int32_t* idx,
+                  const double* stat_scale, const double* post_scale, const int32_t* use_delta, double negval);
+/* The inputs are the current outputs of a projection or a release plan: input i is the source's output i, so
+ * nin must equal its nout, and device and N must agree (PS_ERR_BAD_ARG, nothing enqueued); PS_ERR_STATE before
+ * the source's first apply.  On the handle's stream behind the source's last operation; the source's next apply
+ * waits for the read. */
+int ps_nbhd_apply_project(ps_nbhd* c, ps_project* p);
+int ps_nbhd_apply_sites(ps_nbhd* c, ps_sites* p);
+/* one output field to the host (synchronises).  PS_ERR_STATE before the first apply. */
+int ps_nbhd_fetch(ps_nbhd* c, int e, double* out /* N*N */);
+/* the outputs at n listed cells: out[e * n + k] = Z_e(rows[k], cols[k]) (synchronises).  PS_ERR_BAD_ARG for
+ * a cell outside the domain, PS_ERR_STATE before the first apply. */
+int ps_nbhd_gather(ps_nbhd* c, int64_t n, const int32_t* rows, const int32_t* cols, double* out /* nout x n */);
+/* any pointer may be NULL */
+int ps_nbhd_info(ps_nbhd* c, int* N, int* nin, int* nout, int64_t* applies);
+/* measurement: HIP-event timing of the applies (pre-pass and transform together), as ps_catch_prof */
+int ps_nbhd_prof(ps_nbhd* c, int enable, double* total_ms, int64_t* launches);
+void ps_nbhd_destroy(ps_nbhd* c);
+/* One member whose values are the handle's current outputs, as ps_summary_add_catch takes a catch handle's: slot
+ * e takes Z_e, through the accumulator's own add kernel, on the accumulator's stream behind the handle's last
+ * operation; the next apply waits for the read.  The accumulator's slot count must equal nout, device and N must
+ * agree (PS_ERR_BAD_ARG, nothing enqueued); PS_ERR_STATE before the first apply. */
+int ps_summary_add_nbhd(ps_summary* a, ps_nbhd* c, uint32_t weight);
+int ps_hist_add_nbhd(ps_hist* h, ps_nbhd* c, uint32_t weight);
+int ps_mcerr_add_nbhd(ps_mcerr* h, ps_nbhd* c, uint32_t weight);
+int ps_wsum_add_nbhd(ps_wsum* h, ps_nbhd* c, int nscen, const double* rescale, const double* omega);
+
 #ifdef __cplusplus
 }
 #endif

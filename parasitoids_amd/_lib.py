@@ -284,6 +284,20 @@ SIGNATURES = {
     'ps_summary_add_catch': (C.c_int, [_VP, _VP, C.c_uint32]),
     'ps_mcerr_add_catch': (C.c_int, [_VP, _VP, C.c_uint32]),
     'ps_wsum_add_catch': (C.c_int, [_VP, _VP, C.c_int, _F64P, _F64P]),
+    'ps_nbhd_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _I32P, _I32P, C.POINTER(_VP)]),
+    'ps_nbhd_set_skip': (C.c_int, [_VP, C.c_int]),
+    'ps_nbhd_apply': (C.c_int, [_VP, _VP, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P, C.c_double]),
+    'ps_nbhd_apply_project': (C.c_int, [_VP, _VP]),
+    'ps_nbhd_apply_sites': (C.c_int, [_VP, _VP]),
+    'ps_nbhd_fetch': (C.c_int, [_VP, C.c_int, _F64P]),
+    'ps_nbhd_gather': (C.c_int, [_VP, C.c_int64, _I32P, _I32P, _F64P]),
+    'ps_nbhd_info': (C.c_int, [_VP, _I32P, _I32P, _I32P, _I64P]),
+    'ps_nbhd_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P]),
+    'ps_nbhd_destroy': (None, [_VP]),
+    'ps_summary_add_nbhd': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_hist_add_nbhd': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_mcerr_add_nbhd': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_wsum_add_nbhd': (C.c_int, [_VP, _VP, C.c_int, _F64P, _F64P]),
     'ps_gain_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _I32P, _F64P, _I32P, C.POINTER(_VP)]),
     'ps_gain_apply': (C.c_int, [_VP, _VP, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P, C.c_double]),
     'ps_gain_apply_project': (C.c_int, [_VP, _VP]),

@@ -284,6 +284,10 @@ extern "C" int ps_summary_add_gain(ps_summary* a, ps_gain* p, uint32_t weight) {
   return sum_add_fields(a, p, ps_gain_fields(), "summary_add_gain", weight);
 }
 
+extern "C" int ps_summary_add_nbhd(ps_summary* a, ps_nbhd* p, uint32_t weight) {
+  return sum_add_fields(a, p, ps_nbhd_fields(), "summary_add_nbhd", weight);
+}
+
 // the mean planes for ps_gain.hip's finish: nothing is computed or changed here
 int ps_summary_mean_internal(ps_summary* a, PsMeanView* out) {
   if (!a || !out) return ps_fail(PS_ERR_BAD_ARG, "summary mean view: null handle");

@@ -57,6 +57,9 @@ the cell, and per member the number of patches and their sizes: is the reached a
 of an `ExcursionMaps`, and the count plane of any selection of members (ps_overlap_*, csrc/ps_overlap.hip);
 `RepresentativeMembers` reads from it, in integers on the host, the inclusion depth of every member, the deepest
 member, the central band and k-medoids scenarios -- which single outcome is typical, which no summary map can say.
+`NeighbourhoodFields` turns, on the device, one member's field into its largest value within a disc of each cell
+(ps_nbhd_*, csrc/ps_nbhd.hip); the existing accumulators take it per member (`NeighbourhoodPosterior`): the
+probability of at least t wasps somewhere within r metres, which no per-cell map gives.
 """
 import ctypes as C
 import json
@@ -1790,11 +1793,11 @@ def exposure_plan(exposure, ndays=None):
 # source: the model's day fields, a Projection, the ReleaseSites of sites= and, after it, plan B of compare=.
 # 'apply' is the source's own.  The three orders differ for no better reason than the history of the maps.
 FEED_ORDER = {
-    'days': ('summary', 'core_range', 'reweight', 'catch', 'information', 'excursion', 'mc_error', 'sensitivity',
-             'histogram', 'arrival', 'peak', 'patches'),
+    'days': ('summary', 'core_range', 'reweight', 'catch', 'neighbourhood', 'information', 'excursion', 'mc_error',
+             'sensitivity', 'histogram', 'arrival', 'peak', 'patches'),
     'projection': ('apply', 'summary', 'reweight', 'mc_error', 'sensitivity', 'histogram', 'catch'),
     'sites': ('apply', 'summary', 'reweight', 'mc_error', 'sensitivity', 'histogram', 'arrival', 'peak', 'excursion',
-              'core_range', 'catch', 'information', 'patches'),
+              'core_range', 'catch', 'neighbourhood', 'information', 'patches'),
     'compare': ('apply', 'contrast'),
 }
 
@@ -1835,6 +1838,7 @@ FEED = {
     'core_range': _add_length,
     'reweight': _add_reweighted,
     'catch': _add_catch,
+    'neighbourhood': _add_catch,
     'information': lambda acc, fs, m: acc.add(m.length, m.lam),
     'mc_error': _add_halves,
     'contrast': _add_length,
@@ -1877,6 +1881,15 @@ def _build_catch(fs, q):
         return cp
 
 
+def _build_neighbourhood(fs, q):
+    windows = fs._traps.get('neighbourhood')
+    if windows:
+        nf = fs._over(NeighbourhoodFields, windows, windows)
+        npost = _owned_by(nf, NeighbourhoodPosterior, q.thresholds, q.levels, q.bins, q.edges, q.mc_b, q.rw_names)
+        npost.given = q.nb_plan['given']
+        return npost
+
+
 def _build_information(fs, q):
     traps = fs._traps.get('information')
     if traps:
@@ -1899,6 +1912,7 @@ BUILD = {
     'core_range': lambda fs, q: q.cr_frac and fs._over(RangeMaps, (q.cr_frac, fs._days), (q.cr_frac,)),
     'reweight': _build_reweight,
     'catch': _build_catch,
+    'neighbourhood': _build_neighbourhood,
     'information': _build_information,
     'mc_error': _build_mc_error,
     'contrast': lambda fs, q: PlanContrast(fs._against, fs._source, q.thresholds),
@@ -1925,8 +1939,8 @@ class _FieldSet():
 
     def fed_from(self, kind, source, name=None, owns=True, against=None, **traps):
         '''kind: a key of FEED_ORDER; name: the driver's name of the source (default: the kind); owns: release()
-        closes the source; against: plan A of a 'compare' set; traps: per 'catch' / 'information' the arguments of its
-        fields after the source, None for none'''
+        closes the source; against: plan A of a 'compare' set; traps: per 'catch' / 'information' / 'neighbourhood' the
+        arguments of its fields after the source, None for none'''
         self._kind, self._name, self._source, self._owns = kind, name or kind, source, owns
         self._against, self._traps = against, traps
         return self
@@ -1983,7 +1997,7 @@ class _FieldSet():
 
 
 def _pool_halves(owners):
-    '''the Monte Carlo error sequences of every chain's owner (a _FieldSet or a CatchPosterior) pooled in chain order
+    '''the Monte Carlo error sequences of every chain's owner (a _FieldSet or a posterior of its own) pooled in chain order
     into the first's `mc_error` (pool_mc_error, which closes the others)'''
     if owners[0].mc_error is not None:
         pooled = pool_mc_error([o.mc_error for o in owners])
@@ -1997,9 +2011,11 @@ def _merge_chains(sets):
     accumulators are closed.  The sources stay open: a catch reads its source's fields, a contrast both plans'.'''
     first = sets[0]
     _pool_halves(sets)
-    if first.catch is not None:
-        _pool_halves([fs.catch for fs in sets])
-        first.catch.fields.close()     # the accumulators hold what they need; an information's fields hold its maps
+    for own in ('catch', 'neighbourhood'):
+        if getattr(first, own) is not None:
+            _pool_halves([getattr(fs, own) for fs in sets])
+            # the accumulators hold what they need; an information's fields hold its maps
+            getattr(first, own).fields.close()
     for other in sets[1:]:
         first.merge(other)
         other.close()
@@ -2020,6 +2036,8 @@ class ProjectedMaps(_FieldSet):
     asked for), whose maps take the output day.  `reweight`: the
     ReweightedSummary.for_projection (None unless asked for), which takes the scenario's name and the output index.
     `catch`: the CatchPosterior over the outputs (None unless asked for), whose traps name an output label.
+    `neighbourhood`: the NeighbourhoodPosterior over a release plan's outputs (None unless asked for), whose windows
+    name an output day.
     `information`: the InformationPosterior over the outputs (None unless asked for), likewise.  `core_range`: the
     RangeMaps.for_projection of a release plan's outputs (None unless asked for), whose maps take the output day.
     `patches`: the PatchMaps.for_projection of a release plan's outputs (None unless asked for), likewise.
@@ -2028,10 +2046,11 @@ class ProjectedMaps(_FieldSet):
 
     def __init__(self, weights, in_days, labels, summary, histogram=None, arrival=None, plan=None,
                  sensitivity=None, mc_error=None, peak=None, excursion=None, reweight=None, catch=None,
-                 information=None, core_range=None, patches=None):
+                 information=None, core_range=None, patches=None, neighbourhood=None):
         super().__init__(summary=summary, histogram=histogram, arrival=arrival, sensitivity=sensitivity,
                          mc_error=mc_error, peak=peak, excursion=excursion, reweight=reweight, catch=catch,
-                         information=information, core_range=core_range, patches=patches)
+                         information=information, core_range=core_range, patches=patches,
+                         neighbourhood=neighbourhood)
         self.weights = weights
         self.in_days = in_days
         self.labels = labels
@@ -3750,6 +3769,310 @@ def save_catch(outfile, catch, cell_area=None):
             'members': catch.summary.members, 'total_weight': catch.summary.total_weight, 'outputs': outs}
 
 
+# ------------------------------------------------------------------ neighbourhood maxima: t wasps within r of a cell?
+MAX_NBHD_IN = 32           # ps_nbhd: the input records of one launch's descriptors
+MAX_NBHD_OUT = 32
+MAX_NBHD_HALF = 32         # PS_NBHD_MAX_HALF: the largest half-width of a disc in cells
+
+
+def check_windows(windows, what='day'):
+    '''windows [(key, radius_m), ...] as [(key, radius_m), ...]: 1..32 windows, the key (a model day, or the output
+    label of a projection or plan) a whole number >= 0, the radius finite and >= 0; ValueError otherwise'''
+    import math
+    try:
+        rows = [tuple(t) for t in windows]
+    except TypeError:
+        raise ValueError('windows must be a list of (%s, radius_m), got %r' % (what, windows))
+    if not 1 <= len(rows) <= MAX_NBHD_OUT:
+        raise ValueError('%d windows; 1..%d fit one handle' % (len(rows), MAX_NBHD_OUT))
+    out = []
+    for t in rows:
+        if len(t) != 2:
+            raise ValueError('a window is (%s, radius_m), got %r' % (what, t))
+        try:
+            key, radius = float(t[0]), float(t[1])
+        except (TypeError, ValueError):
+            raise ValueError('a window is (%s, radius_m) of numbers, got %r' % (what, t))
+        if not (math.isfinite(key) and key == int(key) and key >= 0):
+            raise ValueError('window %r: the %s must be a whole number >= 0' % (t, what))
+        if not (math.isfinite(radius) and radius >= 0):
+            raise ValueError('window %r: the radius must be finite and >= 0' % (t,))
+        out.append((int(key), radius))
+    return out
+
+
+def parse_windows(text):
+    '''the command line's 'KEY,RADIUS_M;...' as [(key, radius_m), ...]; the values are checked by check_windows,
+    here only the shape'''
+    out = []
+    for part in str(text).split(';'):
+        if not part.strip():
+            continue
+        f = [x.strip() for x in part.split(',')]
+        if len(f) != 2:
+            raise ValueError('a window is KEY,RADIUS_M, got %r' % (part,))
+        try:
+            out.append((int(f[0]), float(f[1])))
+        except ValueError:
+            raise ValueError('a window is KEY,RADIUS_M with a whole KEY, got %r' % (part,))
+    return out
+
+
+def window_cells(radius_m, cell_m):
+    '''(r2, H, ncells) of a disc of radius_m on a grid of cell_m: rho = radius_m / cell_m, r2 = floor(rho^2 + 1e-9)
+    -- the 1e-9 keeps a radius of exactly k cells at r2 = k^2 where the quotient rounds below k --, H =
+    floor(sqrt(r2)) the half-width and ncells the cells (dy, dx) with dy^2 + dx^2 <= r2.  ValueError where
+    H > 32, the largest half-width ps_nbhd stages.'''
+    import math
+    rho = float(radius_m) / float(cell_m)
+    if not (math.isfinite(rho) and rho >= 0):
+        raise ValueError('radius %r m on cells of %r m' % (radius_m, cell_m))
+    if rho >= MAX_NBHD_HALF + 2:      # far out: the square below need not fit an int
+        r2 = None
+    else:
+        r2 = int(math.floor(rho * rho + 1e-9))
+    H = None if r2 is None else math.isqrt(r2)
+    if H is None or H > MAX_NBHD_HALF:
+        raise ValueError('a radius of %g m is %.4g cells of %g m: at most a half-width of %d cells, radii below %g m '
+                         'on this grid' % (radius_m, rho, cell_m, MAX_NBHD_HALF, (MAX_NBHD_HALF + 1) * float(cell_m)))
+    ncells = sum(2 * math.isqrt(r2 - dy * dy) + 1 for dy in range(-H, H + 1))
+    return r2, H, ncells
+
+
+def check_neighbourhood(neighbourhood, ndays=None, cell_m=None, evaluate=None):
+    '''posterior_predictive's neighbourhood= argument, [(day, radius_m), ...] or dict(windows=[...]) ->
+    dict(windows, given): the checked windows (check_windows) over model days < ndays, at most 32 distinct ones,
+    every radius within the largest disc of a grid of cell_m (window_cells; None: no model at hand), and the
+    argument as given for the json.  evaluate: posterior_predictive's evaluate=, which has no device fields.
+    ValueError otherwise.'''
+    arg = neighbourhood
+    if isinstance(arg, dict):
+        if 'windows' not in arg or set(arg) - {'windows'}:
+            raise ValueError('neighbourhood must be [(day, radius_m), ...] or dict(windows=[...]), got %r' % (arg,))
+        arg = arg['windows']
+    if evaluate is not None:
+        raise ValueError('neighbourhood= needs the device: not with evaluate=')
+    windows = check_windows(arg)
+    for t in windows:
+        if ndays is not None and t[0] >= ndays:
+            raise ValueError('window %r: the model has %d days' % (t, ndays))
+        if cell_m is not None:
+            window_cells(t[1], cell_m)
+    if len({t[0] for t in windows}) > MAX_NBHD_IN:
+        raise ValueError('the windows name more than %d days' % MAX_NBHD_IN)
+    return {'windows': windows, 'given': [list(t) for t in windows]}
+
+
+class NeighbourhoodFields(_Handle):
+    '''Z_e(y, x) = max of v over the cells of the domain within radius_e of (y, x), of `pop_model`'s last
+    evaluation, on the device (ps_nbhd_*, csrc/ps_nbhd.hip): per member the largest density a search within
+    radius_e metres of the cell would meet on model day day_e.  windows: [(day, radius_m), ...] (check_windows),
+    v the value SpreadSummary adds for that day; the disc holds the cells with dy^2 + dx^2 <= r2, r2 =
+    floor((radius_m / cell_m)^2 + 1e-9) (window_cells; at most a half-width of 32 cells); days: the model days
+    the handle reads, default the windows' own (at most 32).  `for_projection` reads the outputs of a Projection
+    or a ReleaseSites instead.  Cells outside the domain do not exist; a radius of 0 returns v; the maximum is
+    exact, so the fields equal tests/nbhd_ref.py's bit for bit.  The handle holds len(windows) x pitch x 8 B and
+    one int32 flag per input and tile of 32 x 64 cells (`nbytes`); `set_skip(False)` stages every tile, which
+    changes no output.  SpreadSummary.for_projection, SpreadHistogram.for_projection,
+    MonteCarloError.for_projection and ReweightedSummary.for_projection accept it.'''
+    fields_kind = 'nbhd'         # the accumulators' entry points for these fields: ps_*_add_nbhd
+    _prefix, _noun = 'ps_nbhd', 'neighbourhood fields'
+
+    def __init__(self, pop_model, windows, days=None):
+        self.windows = check_windows(windows)
+        used = sorted({t[0] for t in self.windows})
+        self.in_days = used if days is None else check_in_days(days)
+        if len(self.in_days) > MAX_NBHD_IN:
+            raise ValueError('%d input days; at most %d fit one handle' % (len(self.in_days), MAX_NBHD_IN))
+        missing = [d for d in used if d not in self.in_days]
+        if missing:
+            raise ValueError('window days %r are not among the days %r' % (missing, self.in_days))
+        self._source = None
+        self._setup(pop_model, [self.in_days.index(t[0]) for t in self.windows], len(self.in_days))
+        self._set_days(self.in_days)
+
+    @classmethod
+    def for_projection(cls, source, windows, labels=None):
+        '''The neighbourhood fields of the outputs of `source` (a Projection or a ReleaseSites): a window's first
+        entry is the source's output label (labels: one per output, default a ReleaseSites' output days, else the
+        output indices); `apply()` reads the outputs of the source's last apply.  An output without weight is
+        refused.'''
+        self = cls.__new__(cls)
+        self.windows = check_windows(windows, 'output')
+        if labels is None:
+            labels = getattr(source, 'days', None) if source.fields_kind == 'sites' else None
+        labels = list(range(source.nout)) if labels is None else [int(x) for x in labels]
+        if len(labels) != source.nout:
+            raise ValueError('%d labels for %d outputs' % (len(labels), source.nout))
+        slot = {e: i for i, e in enumerate(source.live)}        # the source's device slot of every output
+        inputs = []
+        for t in self.windows:
+            if t[0] not in labels or labels.index(t[0]) not in slot:
+                raise ValueError('window %r: %d is not an output that carries weight (%r)' % (t, t[0], labels))
+            inputs.append(slot[labels.index(t[0])])
+        self.in_days = None
+        self._source = source
+        self._setup(source.pm, inputs, len(source.live))
+        return self
+
+    def _setup(self, pop_model, inputs, nin):
+        self._attach(pop_model)
+        self.nout = len(self.windows)
+        self.live = list(range(self.nout))
+        self.radii_m = [t[1] for t in self.windows]
+        cell_m = float(pop_model.rad_dist) / int(pop_model.rad_res)
+        cells = [window_cells(r, cell_m) for r in self.radii_m]
+        self.r2 = [c[0] for c in cells]
+        self.half = [c[1] for c in cells]
+        self.cells = [c[2] for c in cells]
+        tiles = ((self.N + 31) // 32) * ((self.N + 63) // 64)
+        self.nbytes = self.nout * self.pitch * 8 + int(nin) * tiles * 4      # the output fields and the tile flags
+        self._create(int(nin), self.nout, L.p_i32(L.i32(inputs)), L.p_i32(L.i32(self.r2)))
+
+    def set_skip(self, on=True):
+        '''the empty-tile pre-pass of the next applies: on (the default) or off; the outputs are the same'''
+        self._call('set_skip', int(bool(on)))
+
+    def apply(self):
+        '''The neighbourhood fields of the last evaluation of the model (enqueued on the solver's stream), or of
+        the source's last apply (on the handle's stream); no host synchronisation; the outputs of the previous
+        apply are overwritten.'''
+        self._read('apply', self._source)
+
+    @property
+    def applies(self):
+        n = C.c_int64()
+        self._call('info', None, None, None, C.byref(n))
+        return n.value
+
+    def field(self, e):
+        '''[N, N] float64: output e of the last apply'''
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        self._call('fetch', self._e(e), L.p_f64(out))
+        return out
+
+    def gather(self, rows, cols):
+        '''[nout, n] float64: every output of the last apply at the cells (rows[k], cols[k])'''
+        rows, cols = L.i32(np.asarray(rows).ravel()), L.i32(np.asarray(cols).ravel())
+        if rows.size != cols.size:
+            raise ValueError('%d rows and %d columns' % (rows.size, cols.size))
+        out = np.zeros((self.nout, rows.size), dtype=np.float64)
+        self._call('gather', rows.size, L.p_i32(rows), L.p_i32(cols), L.p_f64(out))
+        return out
+
+    def profile(self, enable=None):
+        '''HIP-event time of the applies, pre-pass included: (total ms, applies); enable switches it'''
+        return self._profile(enable)
+
+
+class NeighbourhoodPosterior():
+    '''The posterior of neighbourhood fields, as posterior_predictive returns it: `fields` (the
+    NeighbourhoodFields; closed once the chains have run), `windows` [(key, radius_m)], `thresholds` and `summary`,
+    the SpreadSummary.for_projection(fields, thresholds), which takes the window's index; `histogram`: the
+    SpreadHistogram.for_projection, None without quantile `levels`; `mc_error`: the MonteCarloError.for_projection
+    (while the chains run, one chain's two sequences) and `reweight`: the ReweightedSummary.for_projection, both
+    None unless asked for; `given`: the driver's neighbourhood= argument.'''
+
+    def __init__(self, fields, thresholds=(), levels=None, bins=DEFAULT_BINS, edges=None, mc_batch=None,
+                 scenarios=None):
+        self.fields = fields
+        self.windows = list(fields.windows)
+        self.radii_m, self.r2, self.cells = list(fields.radii_m), list(fields.r2), list(fields.cells)
+        self.thresholds = [float(t) for t in thresholds]
+        self.levels = list(levels) if levels else None
+        self.histogram = self.mc_error = self.reweight = self.given = None
+        self.summary = SpreadSummary.for_projection(fields, self.thresholds)
+        try:
+            if self.levels:
+                self.histogram = SpreadHistogram.for_projection(fields, bins, edges)
+            if mc_batch:
+                self.mc_error = [MonteCarloError.for_projection(fields, mc_batch, self.thresholds)
+                                 for _half in range(2)]
+            if scenarios:
+                self.reweight = ReweightedSummary.for_projection(fields, scenarios, self.thresholds)
+        except BaseException:
+            self.fields = None           # the caller's (_owned_by) to close
+            self.close()
+            raise
+
+    def add(self, weight=1, log_weights=None):
+        '''apply the fields to the last evaluation (or the source's last apply) and add them to the summary, the
+        histogram and, with the run's log-weights, to the reweighted summary; the Monte Carlo error sequences are
+        the caller's to feed (the run is split between them)'''
+        self.fields.apply()
+        self.summary.add(weight)
+        if self.histogram is not None:
+            self.histogram.add(weight)
+        if self.reweight is not None:
+            self.reweight.add(log_weights, weight)
+
+    def merge(self, other):
+        if other.windows != self.windows or other.thresholds != self.thresholds:
+            raise ValueError('neighbourhood posteriors over different windows or thresholds')
+        self.summary.merge(other.summary)
+        if self.histogram is not None:
+            self.histogram.merge(other.histogram)
+        if self.reweight is not None:
+            self.reweight.merge(other.reweight)
+
+    def _e(self, e):
+        if not 0 <= int(e) < len(self.windows):
+            raise ValueError('window %r of %d' % (e, len(self.windows)))
+        return int(e)
+
+    def maximum(self, e):
+        '''the posterior mean of the largest value within the radius of window e'''
+        return self.summary.mean(self._e(e))
+
+    def sd(self, e):
+        '''its posterior sd (a variance that rounding left below 0 reads as 0)'''
+        return np.sqrt(np.maximum(self.summary.variance(self._e(e)), 0.0))
+
+    def prob(self, e, k):
+        '''the posterior probability of at least thresholds[k] somewhere within the radius of window e'''
+        return self.summary.exceedance(self._e(e), k)
+
+    def quantile(self, e, p):
+        '''the weighted lower quantile at level p of the neighbourhood maximum of window e (SpreadHistogram)'''
+        if self.histogram is None:
+            raise ValueError('no quantile levels were asked for: there is no histogram')
+        return self.histogram.quantile(self._e(e), p)
+
+    def close(self):
+        accs = [self.fields, self.summary, self.histogram, self.reweight]
+        accs += list(self.mc_error) if isinstance(self.mc_error, (list, tuple)) else [self.mc_error]
+        for a in accs:
+            if a is not None:
+                a.close()
+
+
+def save_neighbourhood(outfile, post, cell_area=None):
+    '''outfile.npz of one NeighbourhoodPosterior through save_maps: per window e under the label `n{e}` the CSR
+    triplets `n{e}_*` of the posterior mean of the neighbourhood maximum, `n{e}_sd_*`, `n{e}_pexc{k}_*` (the
+    probability of at least thresholds[k] within the radius) and, with levels, `n{e}_q{tag}_*`; `days` (the
+    windows' days or output labels), `radii_m`, `r2`, `cells` and `thresholds` -> its block for the json: the
+    windows, members, weight and per window and threshold, with a cell area, the m^2 where that probability is
+    >= 0.5'''
+    maps, outs = [], []
+    nk = len(post.thresholds)
+    for e, t in enumerate(post.windows):
+        probs = [post.prob(e, k) for k in range(nk)]
+        day_maps = [('', post.maximum(e)), ('_sd', post.sd(e))]
+        day_maps += [('_pexc%d' % k, probs[k]) for k in range(nk)]
+        day_maps += [('_' + quantile_tag(p), post.quantile(e, p)) for p in (post.levels or ())]
+        maps.append(('n%d' % e, day_maps))
+        outs.append({'window': list(t), 'r2': post.r2[e], 'cells': post.cells[e],
+                     'area': [None if cell_area is None else float((pr >= 0.5).sum() * cell_area) for pr in probs]})
+    extra = {'days': np.array([t[0] for t in post.windows], dtype=np.int32),     # in place of save_maps' labels
+             'radii_m': np.array(post.radii_m, dtype=np.float64), 'r2': np.array(post.r2, dtype=np.int32),
+             'cells': np.array(post.cells, dtype=np.int32),
+             'thresholds': np.array(post.thresholds, dtype=np.float64)}
+    save_maps(outfile, maps, extra)
+    return {'windows': [list(t) for t in post.windows], 'thresholds': list(post.thresholds),
+            'levels': list(post.levels or ()), 'members': post.summary.members,
+            'total_weight': post.summary.total_weight, 'outputs': outs}
+
+
 # ------------------------------------------------------------------ trap information: what a catch would teach
 MAX_GAIN_IN = 32           # ps_gain: the input records of one launch's descriptors
 MAX_GAIN_PLANES = 32       # the planes of all traps of one handle: the slots of one accumulator
@@ -4389,14 +4712,17 @@ class PredictiveResult():
     levels of its saved quantiles, both None where not asked for (the plan then carries a `patches` of its own);
     `representative`: the RepresentativeMembers over `excursion`, `representative_days` the planes of its saved
     outputs ('all' or a list of days) and `representative_chains` per chain the model parameters of its rows, all
-    None where not asked for (the plan then carries a `representative` of its own).'''
+    None where not asked for (the plan then carries a `representative` of its own); `neighbourhood`: the
+    NeighbourhoodPosterior of the windows over the model's day fields, None where not asked for (the plan then
+    carries a `neighbourhood` of its own over the windows on its output days).'''
 
     def __init__(self, summary, rows, evaluations, failed, seconds, runs, observations, provenance, days,
                  histogram=None, quantiles=None, arrival=None, arrival_levels=None, emergence=None, exposure=None,
                  sites=None, sensitivity=None, contrast=None, compare_plan=None, mc_error=None, mc_plan=None,
                  peak=None, excursion=None, excursion_levels=None, reweight=None, reweight_info=None, catch=None,
                  information=None, core_range=None, core_range_levels=None, patches=None, patch_levels=None,
-                 representative=None, representative_days=None, representative_chains=None):
+                 representative=None, representative_days=None, representative_chains=None, neighbourhood=None):
+        self.neighbourhood = neighbourhood
         self.representative = representative
         self.representative_days = representative_days
         self.representative_chains = representative_chains
@@ -4635,6 +4961,16 @@ class PredictiveResult():
             if cp.reweight is not None:
                 save_reweight('%s_%scatch_reweight' % (outfile, name), cp.reweight, keys, labels)
             (meta['predictive'][name[:-1]] if name else meta['predictive'])['catch'] = block
+        for name, nb in (('', self.neighbourhood),
+                         ('sites_', None if self.sites is None else self.sites.neighbourhood)):
+            if nb is None:
+                continue
+            block = save_neighbourhood('%s_%snbhd' % (outfile, name), nb, area)
+            block['given'] = nb.given
+            if nb.reweight is not None:
+                save_reweight('%s_%snbhd_reweight' % (outfile, name), nb.reweight, list(range(len(nb.windows))),
+                              ['n%d' % e for e in range(len(nb.windows))])
+            (meta['predictive'][name[:-1]] if name else meta['predictive'])['neighbourhood'] = block
         for name, ip in (('', self.information),
                          ('sites_', None if self.sites is None else self.sites.information)):
             if ip is None:
@@ -4657,6 +4993,11 @@ class PredictiveResult():
                 if cp is not None and cp.mc_error is not None:
                     block[name] = mc_error_block(cp.mc_error, list(range(len(cp.traps))),
                                                  ['c%d' % e for e in range(len(cp.traps))], name + '_', mmaps)
+            for name, nb in (('neighbourhood', self.neighbourhood),
+                             ('sites_neighbourhood', None if self.sites is None else self.sites.neighbourhood)):
+                if nb is not None and nb.mc_error is not None:
+                    block[name] = mc_error_block(nb.mc_error, list(range(len(nb.windows))),
+                                                 ['n%d' % e for e in range(len(nb.windows))], name + '_', mmaps)
             save_maps('%s_mcerr' % outfile, mmaps)
             meta['predictive']['mc_error'] = block
         with open(str(outfile) + '.json', 'w') as fobj:
@@ -4708,14 +5049,14 @@ def _evaluate_runs(pm, rows, run_list, model_cols, evaluate, want_obs, locinfo, 
 def _check_request(q):
     '''Everything of posterior_predictive's arguments (q: a namespace of them) that can fail before any evaluation,
     in a fixed order -- of two bad arguments the earlier one is reported.  -> q, with the checked plans beside the
-    arguments: cr_frac / cr_levels, in_plan, ct_plan, rw_plan / rw_names, ex_thr / ex_levels, pk_thr / pk_levels,
+    arguments: cr_frac / cr_levels, in_plan, ct_plan, nb_plan, rw_plan / rw_names, ex_thr / ex_levels, pk_thr / pk_levels,
     mc_batches, mc_b / mc_halves, pt_thr / pt_conn / pt_levels, rp_plan, s_names, levels, a_thr / a_levels, plans [(name, W, in_days, labels)], site_plan,
     cmp_plan, the loaded chains `prepared` [(rows, runs, model columns, observation columns, source)], `pms` (the
     models) and want_obs.'''
     pm0 = (q.pop_model[0] if q.pop_model else None) if isinstance(q.pop_model, (list, tuple)) else q.pop_model
     days, thresholds = q.days, q.thresholds
     q.cr_frac = q.cr_levels = q.in_plan = q.ct_plan = q.rw_plan = q.ex_thr = q.ex_levels = None
-    q.pk_thr = q.pk_levels = q.mc_batches = q.pt_thr = q.pt_conn = q.pt_levels = q.rp_plan = None
+    q.pk_thr = q.pk_levels = q.mc_batches = q.pt_thr = q.pt_conn = q.pt_levels = q.rp_plan = q.nb_plan = None
 
     def ndays0():                     # the model is touched only where an option needs it
         return None if pm0 is None else len(pm0.days)
@@ -4750,16 +5091,22 @@ def _check_request(q):
     def check_mc_error_arg():
         q.mc_batches = mc_error_plan(q.mc_error)
         check_mc_thresholds(thresholds)
+
+    def check_neighbourhood_arg():
+        cell_m = None if pm0 is None else float(pm0.rad_dist) / int(pm0.rad_res)
+        q.nb_plan = check_neighbourhood(q.neighbourhood, ndays0(), cell_m, q.evaluate)
     # the options that need the device, in the order in which they are checked: (name, False switches it off too,
-    # its check).  check_information and check_catch refuse evaluate= themselves, after the argument's shape.
+    # its check).  check_information, check_catch and check_neighbourhood refuse evaluate= themselves, after the
+    # argument's shape.
     for name, or_false, check in (('core_range', True, check_core_range_arg),
                                   ('information', False, check_information_arg), ('catch', False, check_catch_arg),
                                   ('reweight', False, check_reweight_arg), ('excursion', True, check_excursion_arg),
-                                  ('peak', True, check_peak_arg), ('mc_error', True, check_mc_error_arg)):
+                                  ('peak', True, check_peak_arg), ('mc_error', True, check_mc_error_arg),
+                                  ('neighbourhood', False, check_neighbourhood_arg)):
         arg = getattr(q, name)
         if arg is None or (or_false and arg is False):
             continue
-        if q.evaluate is not None and name not in ('information', 'catch'):
+        if q.evaluate is not None and name not in ('information', 'catch', 'neighbourhood'):
             raise ValueError('%s= needs the device: not with evaluate=' % name)
         check()
     if q.representative is not None and q.representative is not False:
@@ -4843,8 +5190,9 @@ def _build_sets(sets, q, pm, chain, nruns, late):
     def begin(fs, kind, source, name=None, **kw):
         sets.append(fs.fed_from(kind, source, name, **kw))
         return fs
-    ct, info = q.ct_plan, q.in_plan
-    day_traps = dict(catch=ct and (ct['traps'],), information=info and (info['traps'],))
+    ct, info, nb = q.ct_plan, q.in_plan, q.nb_plan
+    day_traps = dict(catch=ct and (ct['traps'],), information=info and (info['traps'],),
+                     neighbourhood=nb and (nb['windows'],))
     begin(_FieldSet(), 'days', pm, owns=False, **day_traps).build(q, chain, nruns)
     for name, W, in_days, labels in q.plans:
         traps = (ct['emergence'], labels) if name == 'emergence' and ct is not None and ct['emergence'] else None
@@ -4852,7 +5200,10 @@ def _build_sets(sets, q, pm, chain, nruns, late):
               catch=traps).build(q, chain, nruns)
     if q.site_plan is not None:
         rs = ReleaseSites(pm, q.sites['sites'], q.site_plan[1], late)
-        fs = begin(ProjectedMaps(None, None, None, None), 'sites', rs, **day_traps)
+        # the plan's own neighbourhood maps: over the windows whose day is one of its output days
+        on_plan = [t for t in nb['windows'] if t[0] in rs.days] if nb else []
+        fs = begin(ProjectedMaps(None, None, None, None), 'sites', rs,
+                   **dict(day_traps, neighbourhood=(on_plan,) if on_plan else None))
         fs.labels, fs.plan = list(rs.days), rs.describe()
         fs.build(q, chain, nruns)
         if q.cmp_plan is not None:
@@ -4866,7 +5217,8 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                          cell_area=None, seed=0, evaluate=None, quantiles=None, bins=DEFAULT_BINS, edges=None,
                          arrival=None, arrival_levels=(0.05, 0.5, 0.95), emergence=None, exposure=None, sites=None,
                          sensitivity=None, compare=None, mc_error=None, peak=None, excursion=None, reweight=None,
-                         catch=None, information=None, core_range=None, patches=None, representative=None):
+                         catch=None, information=None, core_range=None, patches=None, representative=None,
+                         neighbourhood=None):
     '''Posterior predictive spread of one or more chains (`Sampler.save` files or (trace, names) pairs). Burn and
     thin apply per chain; consecutive rows with identical model parameters are one evaluation weighted by the
     run's length.
@@ -5013,7 +5365,22 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         space-time set, or the days whose own planes are saved. It compares members the chain produced: no search
         over plans, no zones and no distance curves; depth variants, outlier fences, other distances and the Monte
         Carlo error of these outputs are not computed. Without representative= no call is added and
-        `representative` is None.'''
+        `representative` is None.
+
+    neighbourhood: [(day, radius_m), ...] or dict(windows=[...]) (check_neighbourhood; not with evaluate=; bad
+        arguments fail before any evaluation): per window and member the largest value within radius_m of each
+        cell on model day `day` -- the disc of the cells with dy^2 + dx^2 <= floor((radius_m / cell_m)^2 + 1e-9),
+        at most a half-width of 32 cells, clipped to the domain -- and its ensemble statistics (Schwartz & Sobash
+        2017): "are there at least t wasps somewhere within r of this point?". Each chain then also applies one
+        NeighbourhoodFields over the windows right after the catch's add and adds its fields, with the run's
+        length, to a SpreadSummary.for_projection over `thresholds`; with quantile levels to a
+        SpreadHistogram.for_projection, with mc_error= to two MonteCarloError.for_projection of its own, with
+        reweight= to a ReweightedSummary.for_projection fed the same log-weights; merged in chain order into
+        `neighbourhood` (a NeighbourhoodPosterior; `prob(e, k)` is the map). With sites= the plan gets one of its
+        own over the windows whose day is an output day of the plan, in `sites.neighbourhood`; emergence and
+        exposure get none. Sums or means over the disc, other footprints, and neighbourhood versions of the
+        arrival, peak, excursion, range, patch, sensitivity and contrast maps are not computed. Without
+        neighbourhood= no call is added and `neighbourhood` is None.'''
     q = types.SimpleNamespace(**locals())
     t0 = time.perf_counter()
     _check_request(q)                 # bad arguments fail before any evaluation
@@ -5125,7 +5492,8 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         core_range=day.core_range, core_range_levels=q.cr_levels if q.cr_frac else None,
         patches=day.patches, patch_levels=q.pt_levels if q.pt_thr else None,
         representative=day.representative, representative_days=q.rp_plan['days'] if q.rp_plan else None,
-        representative_chains=[p[0][:, p[2]] for p in prepared] if q.rp_plan else None)
+        representative_chains=[p[0][:, p[2]] for p in prepared] if q.rp_plan else None,
+        neighbourhood=day.neighbourhood)
     if day.information is not None:   # the stated convention: past cap / 2 the ensemble bounds the map
         warn_information(day.information)
         if 'sites' in merged:

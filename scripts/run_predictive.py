@@ -41,7 +41,10 @@ members, with the effective sample size of every scenario in the json -- saved a
 PREFIX_NAME_reweight.npz for every projection and plan asked for); with --catch also the catch-probability maps --
 per trap 'DAY,RATE[,N]' and cell the posterior mean, sd and the probability (--catch-levels) that a trap of effort
 RATE on model day DAY catches at least N wasps; --catch-emergence: traps over the emergence days of --emergence --
-saved as PREFIX_catch.npz (and PREFIX_emergence_catch.npz, PREFIX_sites_catch.npz); with --information also the
+saved as PREFIX_catch.npz (and PREFIX_emergence_catch.npz, PREFIX_sites_catch.npz); with --neighbourhood also the
+neighbourhood maps -- per window 'DAY,RADIUS_M' and cell the posterior mean, sd and, per threshold, the probability
+that at least that many wasps stand somewhere within RADIUS_M of the cell on model day DAY -- saved as
+PREFIX_nbhd.npz (and PREFIX_sites_nbhd.npz over the windows on the plan's output days); with --information also the
 information maps -- per described trap 'DAY,RATE[,YMAX]' and cell the mutual information in nats between the trap's
 count (observed as 0, 1, .., YMAX and more) and the identity of the member: where a reading would change what we
 believe -- saved as PREFIX_information.npz (and PREFIX_sites_information.npz).  Kalbar wind and
@@ -60,7 +63,7 @@ Without --chain a short chain is sampled first (--samples) and saved next to --o
         [--representative [K]] [--representative-epsilon 0.02] [--representative-central 0.5]
         [--reweight 'NAME:east,north,day,kind,rate[,n];...'] [--reweight-file NAME=weights.npy]
         [--catch 'DAY,RATE[,N];...'] [--catch-levels 0.5,0.95] [--catch-emergence 'OBSDAY,RATE[,N];...']
-        [--information 'DAY,RATE[,YMAX];...']
+        [--information 'DAY,RATE[,YMAX];...'] [--neighbourhood 'DAY,RADIUS_M;...']
 """
 import argparse
 import json
@@ -106,6 +109,9 @@ def parse_reweight(ap, probes, files):
     if len(specs) + len(paths) > 4:
         ap.error('at most 4 --reweight / --reweight-file scenarios')
     return specs, paths
+
+
+NB_REPS = 5          # timed applies of the neighbourhood handles per member
 
 
 def main():
@@ -174,6 +180,8 @@ def main():
     ap.add_argument('--catch-levels', default='0.5,0.95', help='levels of the catch maps (with --catch)')
     ap.add_argument('--catch-emergence', default='', help="traps 'OBSDAY,RATE[,N];...' over the emergence days of "
                     '--emergence (with --catch)')
+    ap.add_argument('--neighbourhood', default='', help="windows 'DAY,RADIUS_M;...': per cell the probability of at "
+                    'least each of --thresholds somewhere within RADIUS_M of it on model day DAY (default: off)')
     ap.add_argument('--information', default='', help="described traps 'DAY,RATE[,YMAX];...': per cell the mutual "
                     'information in nats between the count of a trap of effort RATE on model day DAY, observed as '
                     '0, 1, .., YMAX (default 0) and more, and the identity of the member (default: off)')
@@ -271,6 +279,11 @@ def main():
         from parasitoids_amd.predictive import check_information, parse_traps
         information = dict(traps=parse_traps(args.information))
         check_information(information)
+    neighbourhood = None
+    if args.neighbourhood:               # as do bad --neighbourhood windows or radii beyond the largest disc
+        from parasitoids_amd.predictive import check_neighbourhood, parse_windows
+        neighbourhood = parse_windows(args.neighbourhood)
+        check_neighbourhood(neighbourhood, None, 10000.0 / args.rad_res)
     wd, days = PM.get_wind_data(os.path.join(ROOT, 'parasitoids_amd', 'data', 'kalbar'), 30, '00:00')
 
     def make_pm():
@@ -325,6 +338,7 @@ def main():
                                **({'reweight': reweight} if reweight else {}),
                                **({'catch': catch} if catch else {}),
                                **({'information': information} if information else {}),
+                               **({'neighbourhood': neighbourhood} if neighbourhood else {}),
                                **({'core_range': core_range} if core_range else {}),
                                **({'patches': patches} if patches else {}),
                                **({'representative': representative} if representative else {}))
@@ -373,6 +387,16 @@ def main():
         CP = Projection(pm, Wc, CF.in_days)
         CF.profile(True)
         CP.profile(True)
+    NF = NP = None
+    NW = []
+    if neighbourhood:                    # and a Projection of as many outputs: the same bytes, a plain streaming pass;
+        from parasitoids_amd.predictive import NeighbourhoodFields      # and every window alone: cost against radius
+        import numpy as np
+        NF = NeighbourhoodFields(pm, neighbourhood)
+        Wn = np.zeros((NF.nout, len(NF.in_days)))
+        Wn[np.arange(NF.nout), [NF.in_days.index(t[0]) for t in NF.windows]] = 1.0
+        NP = Projection(pm, Wn, NF.in_days)
+        NW = [NeighbourhoodFields(pm, [t]) for t in NF.windows]
     IF = IC = None
     if information:                      # and a CatchFields of as many planes over the same days: the same bytes
         from parasitoids_amd.predictive import CatchFields, InformationFields
@@ -427,6 +451,15 @@ def main():
                 if IF is not None:
                     IF.apply()
                     IC.apply()
+                if NF is not None:
+                    # the first member warms the kernels up untimed; every later one is timed NB_REPS times, the
+                    # handles taking turns
+                    for rep in range(NB_REPS if n else 1):
+                        for h in [NF, NP] + NW:
+                            h.apply()
+                    if n == 0:
+                        for h in [NF, NP] + NW:
+                            h.profile(True)
                 if RW is not None:
                     RW.add(RWF.log_weights(pm, first, length), length)
                 if ME is not None:
@@ -486,6 +519,13 @@ def main():
         if_bytes, if_planes = IF.nbytes, IF.nout
         IF.close()
         IC.close()
+    if NF is not None:
+        nf_ms, nf_launches = NF.profile()
+        np_ms, np_launches = NP.profile()
+        nw_ms = [h.profile() for h in NW]
+        nf_bytes, nf_cells = NF.nbytes, list(NF.cells)
+        for h in [NF, NP] + NW:
+            h.close()
     if RW is not None:
         rw_ms, rw_launches = RW.profile()
         rw_bytes = RW.nbytes
@@ -537,6 +577,16 @@ def main():
         out['outputs'] += ['%s_catch.npz' % args.out] \
             + (['%s_emergence_catch.npz' % args.out] if catch.get('emergence') else []) \
             + (['%s_sites_catch.npz' % args.out] if sites else [])
+    if neighbourhood:
+        out['nbhd_ms_per_member'] = round(nf_ms / max(nf_launches, 1), 4)
+        out['nbhd_launches_timed'] = nf_launches
+        out['nbhd_windows'] = [list(t) for t in neighbourhood]
+        out['nbhd_cells'] = nf_cells
+        out['nbhd_projection_ms_per_member'] = round(np_ms / max(np_launches, 1), 4)     # same nout, same bytes
+        out['nbhd_window_ms'] = [round(ms_ / max(k_, 1), 4) for ms_, k_ in nw_ms]        # every window alone
+        out['nbhd_bytes'] = nf_bytes
+        out['outputs'] += ['%s_nbhd.npz' % args.out] \
+            + (['%s_sites_nbhd.npz' % args.out] if res.sites is not None and res.sites.neighbourhood is not None else [])
     if information:
         out['information_ms_per_member'] = round(if_ms / max(if_launches, 1), 4)
         out['information_launches_timed'] = if_launches
@@ -656,7 +706,7 @@ def main():
     if res.mc_error is not None:
         res.mc_error.close()
     for pr in (res.representative, res.emergence, res.exposure, res.sites, res.contrast, res.peak, res.excursion, res.catch, res.information,
-               res.core_range, res.patches):
+               res.core_range, res.patches, res.neighbourhood):
         if pr is not None:
             pr.close()
     for p in pms:
