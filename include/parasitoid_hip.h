@@ -1350,6 +1350,79 @@ int ps_hist_add_nbhd(ps_hist* h, ps_nbhd* c, uint32_t weight);
 int ps_mcerr_add_nbhd(ps_mcerr* h, ps_nbhd* c, uint32_t weight);
 int ps_wsum_add_nbhd(ps_wsum* h, ps_nbhd* c, int nscen, const double* rescale, const double* omega);
 
+/* ---- ensemble modes: the weighted principal components of the members' fields ----
+ * (no reference counterpart; the EOFs of ensemble forecasting, and with the square root the Hellinger-type PCA of
+ * Legendre & Gallagher 2001.)  The spread map says how much the members differ at a cell, not which cells vary
+ * together.  That needs the inner product of every pair of members' real-valued fields, which no accumulator keeps.
+ * A handle lives on one device and holds, for N x N cells and nslot day slots (1..8, ascending), the members'
+ * transformed fields X[member][slot][pitch] as fp64 (pitch as ps_summary, the pad cells 0) in add order, and on the
+ * host an integer weight w_m >= 1 per member, W = sum w_m < 2^32 - 1.  With v the value ps_summary_add adds for the
+ * slot (>= 0), X = v (PS_MODES_RAW) or X = sqrt(v), the IEEE round-to-nearest square root (PS_MODES_SQRT).  Per slot:
+ *   mu(c)   = (sum_m w_m X_m(c)) / W: acc = acc + w_m * X_m(c) over m in add order, the product and the sum each
+ *             rounded once, then one division -- bit for bit the numpy loop acc += w * X[m]; acc / W
+ *   A_m     = X_m - mu (centred, one IEEE subtraction per cell) or X_m
+ *   G_ij    = sum_c A_i(c) A_j(c), the full symmetric M x M table
+ *   out_k(c) = sum_m coef_km A_m(c) over m in add order, product and sum rounded separately: bit for bit a numpy loop
+ * The table is a symmetric fp64 product on the matrix units (v_mfma_f64_16x16x4_f64): a workgroup owns a pair of
+ * 64-member tiles on or above the diagonal and a share of the cell axis, stages both tiles through LDS (the mean
+ * subtracted, members past M and cells past the range zeroed) and mirrors when it writes.  The splits of the cell
+ * axis -- their number depends on M and N only -- write partial tables that a second kernel adds in split order: no
+ * floating-point atomics, two calls on one handle return the same bits, and G is symmetric to the bit.  Any summation
+ * order satisfies |G_ij - exact| <= gamma_P sqrt(G_ii G_jj), P = N * N.  Unless switched off (ps_modes_set_window) the
+ * table visits only the cells from the first to the last word of 64 cells in which mu != 0: outside them every X_m is
+ * 0 (X >= 0, w >= 1), so the terms left out are zeros, though the splits then fall elsewhere and the last bits may
+ * differ from the unwindowed table.  The eigen-decomposition is the host's (parasitoids_amd/predictive.py,
+ * mode_decomposition).  The handle holds cap * nslot * pitch * 8 B of fields (5.13 MB per member and slot at N = 801),
+ * nslot mean planes, the partial tables and, after the first combine, 8 planes; every allocation is checked against
+ * the free device memory first: PS_ERR_OOM before it is made.  The fields grow by doubling (copied, never shrunk).
+ * Every operation records an event the next one waits on, whichever stream it runs on (the solver's for ps_modes_add,
+ * the handle's own for everything else). */
+#define PS_MODES_RAW 0
+#define PS_MODES_SQRT 1
+typedef struct ps_modes ps_modes;
+/* PS_ERR_BAD_ARG for slots outside 1..8 or a transform that is neither PS_MODES_RAW nor PS_MODES_SQRT */
+int ps_modes_create(int device, int N, int nslot, int transform, ps_modes** out);
+/* room for `members` members now (exactly; PS_ERR_OOM with nothing allocated if the device has not that much free) */
+int ps_modes_reserve(ps_modes* a, int64_t members);
+/* on != 0 (the default): the table visits the live window only; 0: the whole plane */
+int ps_modes_set_window(ps_modes* a, int on);
+/* One member from records of solver s with the arguments and refusals of ps_excur_add: one launch on the solver's
+ * stream, every cell of every slot of the member written, zeros and pad included; weight >= 1. */
+int ps_modes_add(ps_modes* a, ps_solver* s, int nslot, const int32_t* kind, const int32_t* idx,
+                 const double* stat_scale, const double* post_scale, const int32_t* use_delta, double negval,
+                 uint32_t weight);
+/* One member whose slots are the current outputs of a projection or a release plan, as ps_excur_add_project. */
+int ps_modes_add_project(ps_modes* a, ps_project* p, uint32_t weight);
+int ps_modes_add_sites(ps_modes* a, ps_sites* p, uint32_t weight);
+/* One member from host arrays v[nslot][N*N]; the transform is applied.  A negative or non-finite value is
+ * PS_ERR_BAD_ARG with nothing stored (synchronises). */
+int ps_modes_add_host(ps_modes* a, const double* fields /* nslot x N*N */, uint32_t weight);
+/* dst's members, then src's, by a device copy; device, N, slots and transform must match (PS_ERR_BAD_ARG); src is
+ * unchanged */
+int ps_modes_merge(ps_modes* dst, ps_modes* src);
+/* any pointer may be NULL; capacity: the members the fields hold room for; bytes: the device memory held now */
+int ps_modes_info(ps_modes* a, double* total_weight, int64_t* members, int64_t* capacity, int64_t* bytes);
+/* the members' weights in add order; PS_ERR_BAD_ARG for members_expected != the handle's members */
+int ps_modes_weights(ps_modes* a, int64_t members_expected, uint32_t* out /* members */);
+/* forget every member (the room stays) */
+int ps_modes_reset(ps_modes* a);
+/* mu of one slot (synchronises); the plane stays on the device until the next add, merge or reset.  PS_ERR_STATE
+ * before the first add, as table, combine and fetch_member. */
+int ps_modes_mean(ps_modes* a, int slot, double* out /* N*N */);
+/* G of one slot (synchronises).  PS_ERR_BAD_ARG for members_expected != the handle's members (a caller's buffer is
+ * never too small). */
+int ps_modes_table(ps_modes* a, int slot, int centred, int64_t members_expected, double* out /* M*M */);
+/* ncoef (1..8) linear combinations of the members' (centred) fields, the members read once for all of them
+ * (synchronises) */
+int ps_modes_combine(ps_modes* a, int slot, int centred, int ncoef, const double* coef /* ncoef x M */,
+                     double* out /* ncoef x N*N */);
+/* the stored X of one member (synchronises) */
+int ps_modes_fetch_member(ps_modes* a, int64_t member, int slot, double* out /* N*N */);
+/* measurement: HIP-event timing of 0 the adds, 1 the mean launches, 2 the table calls (window, product, sum of the
+ * splits) and 3 the combine launches, as ps_excur_prof */
+int ps_modes_prof(ps_modes* a, int enable, double* ms /* 4 */, int64_t* launches /* 4 */);
+void ps_modes_destroy(ps_modes* a);
+
 #ifdef __cplusplus
 }
 #endif

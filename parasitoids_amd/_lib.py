@@ -347,6 +347,23 @@ SIGNATURES = {
     'ps_overlap_info': (C.c_int, [_VP, _I64P, _I64P, _I32P]),
     'ps_overlap_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P, _F64P, _I64P]),
     'ps_overlap_destroy': (None, [_VP]),
+    'ps_modes_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_VP)]),
+    'ps_modes_reserve': (C.c_int, [_VP, C.c_int64]),
+    'ps_modes_set_window': (C.c_int, [_VP, C.c_int]),
+    'ps_modes_add': (C.c_int, [_VP, _VP, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P, C.c_double, C.c_uint32]),
+    'ps_modes_add_project': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_modes_add_sites': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_modes_add_host': (C.c_int, [_VP, _F64P, C.c_uint32]),
+    'ps_modes_merge': (C.c_int, [_VP, _VP]),
+    'ps_modes_info': (C.c_int, [_VP, _F64P, _I64P, _I64P, _I64P]),
+    'ps_modes_weights': (C.c_int, [_VP, C.c_int64, C.POINTER(C.c_uint32)]),
+    'ps_modes_reset': (C.c_int, [_VP]),
+    'ps_modes_mean': (C.c_int, [_VP, C.c_int, _F64P]),
+    'ps_modes_table': (C.c_int, [_VP, C.c_int, C.c_int, C.c_int64, _F64P]),
+    'ps_modes_combine': (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, _F64P, _F64P]),
+    'ps_modes_fetch_member': (C.c_int, [_VP, C.c_int64, C.c_int, _F64P]),
+    'ps_modes_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P]),
+    'ps_modes_destroy': (None, [_VP]),
 }
 
 _lib = None

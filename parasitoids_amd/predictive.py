@@ -1187,6 +1187,423 @@ def save_representative(outfile, rep, runs=None, chains=None, days='all'):
             'days': days if isinstance(days, str) else list(days), 'thresholds': list(rep.thresholds),
             'members': int(len(w)), 'total_weight': int(w.sum()), 'cell_area': rep.cell_area, 'planes': planes}
 
+
+# ------------------------------------------------------------------ ensemble modes: in what ways do the members differ?
+MAX_MODES = 8              # ps_modes: the coefficient rows of one combine
+MAX_MODE_DAYS = 8          # ps_modes: the day slots of one handle
+MODE_TRANSFORMS = {'raw': 0, 'sqrt': 1}
+
+
+def check_modes(arg, days):
+    '''posterior_predictive's modes= argument, True or dict(days=[...] | 'all', count=4, transform='sqrt' | 'raw'),
+    against `days`, the days the fields have (a list, or their number) -> dict(days, count, transform).  days: the
+    listed days get a decomposition each; 'all' (the default) is the space-time decomposition over every day.
+    ValueError for anything else, a day the fields do not have, a count outside 1..8 and more than 8 days.'''
+    if arg is True:
+        arg = {}
+    if not isinstance(arg, dict):
+        raise ValueError("modes must be True or dict(days=[...] | 'all', count=4, transform='sqrt'), got %r" % (arg,))
+    unknown = set(arg) - {'days', 'count', 'transform'}
+    if unknown:
+        raise ValueError('modes: unknown keys %r' % (sorted(unknown),))
+    count, transform, want = arg.get('count', 4), arg.get('transform', 'sqrt'), arg.get('days', 'all')
+    if isinstance(count, bool) or not isinstance(count, (int, np.integer)) or not 1 <= count <= MAX_MODES:
+        raise ValueError('modes: count must be a whole number in 1..%d, got %r' % (MAX_MODES, count))
+    if transform not in MODE_TRANSFORMS:
+        raise ValueError("modes: transform must be 'sqrt' or 'raw', got %r" % (transform,))
+    have = list(range(days)) if isinstance(days, (int, np.integer)) else (None if days is None else list(days))
+    if isinstance(want, str):
+        if want != 'all':
+            raise ValueError("modes: days must be a list of days or 'all', got %r" % (want,))
+        if have is not None and len(have) > MAX_MODE_DAYS:
+            raise ValueError("modes: 'all' covers %d days, at most %d fit (list the days)" % (len(have), MAX_MODE_DAYS))
+    else:
+        try:
+            want = [int(d) for d in want]
+        except (TypeError, ValueError):
+            raise ValueError("modes: days must be a list of days or 'all', got %r" % (arg.get('days'),))
+        if not want or len(want) > MAX_MODE_DAYS:
+            raise ValueError('modes: 1..%d days, got %d' % (MAX_MODE_DAYS, len(want)))
+        if any(b <= a for a, b in zip(want, want[1:])):
+            raise ValueError('modes: days must be strictly increasing, got %r' % (want,))
+        if have is not None and [d for d in want if d not in have]:
+            raise ValueError('modes: day %r is not among the days %r' % ([d for d in want if d not in have][0], have))
+    return {'days': want, 'count': int(count), 'transform': transform}
+
+
+def mode_decomposition(G, weights, count):
+    '''The weighted principal components of an ensemble from its table G [M, M] of inner products of the centred
+    fields and the members' integer weights: B = D^1/2 G D^1/2 / W with D = diag(w), numpy.linalg.eigh, the
+    eigenvalues descending, `count` (1..8) eigenpairs (lambda_k, u_k) kept.  The entry of u_k of largest magnitude is
+    positive, among equal magnitudes the one of smallest index.  A lambda_k at or below M 2^-52 trace B is absent:
+    count shrinks and nothing is divided by it.  -> dict(count, eigenvalues [K], explained [K] = lambda_k / trace B,
+    total_variance = trace B, spectrum (every eigenvalue, descending), vectors [M, K], scores [M, K] with
+    z_mk = u_mk sqrt(W / w_m) (weighted mean 0, variance 1) and coef [K, M], c_km = sqrt(w_m) u_mk / sqrt(W lambda_k),
+    the rows EnsembleModes.combine turns into the unit-norm patterns e_k)'''
+    G = np.asarray(G, dtype=np.float64)
+    w = np.asarray(weights, dtype=np.float64)
+    M = len(w)
+    if G.shape != (M, M) or M < 1:
+        raise ValueError('a table of %r for %d weights' % (G.shape, M))
+    if isinstance(count, bool) or not 1 <= int(count) <= MAX_MODES:
+        raise ValueError('count must lie in 1..%d, got %r' % (MAX_MODES, count))
+    if np.any(w < 1) or np.any(w != np.floor(w)):
+        raise ValueError('weights must be whole numbers >= 1')
+    W = w.sum()
+    r = np.sqrt(w)
+    B = r[:, None] * G * r[None, :] / W
+    lam, U = np.linalg.eigh(B)
+    order = np.argsort(-lam, kind='stable')
+    lam, U = lam[order], U[:, order]
+    total = float(np.trace(B))
+    floor = M * 2.0 ** -52 * total
+    K = min(int(count), int(np.sum(lam > floor))) if total > 0 else 0
+    lam_k, U = lam[:K], U[:, :K].copy()
+    for k in range(K):
+        mag = np.abs(U[:, k])
+        if U[int(np.argmax(mag == mag.max())), k] < 0:
+            U[:, k] = -U[:, k]
+    return {'count': K, 'eigenvalues': lam_k, 'explained': lam_k / total if K else lam_k, 'total_variance': total,
+            'spectrum': lam, 'vectors': U, 'scores': U * np.sqrt(W / w)[:, None],
+            'coef': np.ascontiguousarray((r[:, None] * U / np.sqrt(W * lam_k)[None, :]).T)}
+
+
+def effective_members(weights):
+    '''Kish's effective sample size W^2 / sum w_m^2'''
+    w = np.asarray(weights, dtype=np.float64)
+    return float(w.sum() ** 2 / (w * w).sum())
+
+
+def separated(eigenvalues, weights):
+    '''North et al.'s (1982) rule of thumb per mode: the sampling error of lambda_k is about lambda_k sqrt(2 / n_eff),
+    n_eff = W^2 / sum w_m^2; mode k is separated when its distance to both neighbours among `eigenvalues` (descending;
+    the first and the last have one) exceeds it.  A pair that is not separated spans a plane, not two patterns.
+    -> [K] bool'''
+    lam = np.asarray(eigenvalues, dtype=np.float64)
+    err = lam * np.sqrt(2.0 / effective_members(weights))
+    out = np.ones(len(lam), dtype=bool)
+    for k in range(len(lam)):
+        for j in (k - 1, k + 1):
+            if 0 <= j < len(lam) and not abs(lam[k] - lam[j]) > err[k]:
+                out[k] = False
+    return out
+
+
+def score_drivers(scores, thetas, weights, names):
+    '''the weighted correlation of every mode's scores [M, K] with every model parameter of the members' runs, thetas
+    [M, P] named `names`; a parameter (or a score) that never moves gets 0 -> dict(names, corr [K, P], strongest:
+    per mode the name of the parameter of largest |corr|, None where all are 0)'''
+    z = np.asarray(scores, dtype=np.float64)
+    th = np.asarray(thetas, dtype=np.float64)
+    w = np.asarray(weights, dtype=np.float64)
+    if z.shape[0] != len(w) or th.shape != (len(w), len(names)):
+        raise ValueError('scores %r, parameters %r, %d weights, %d names' % (z.shape, th.shape, len(w), len(names)))
+    W = w.sum()
+    zc = z - (w[:, None] * z).sum(0) / W
+    tc = th - (w[:, None] * th).sum(0) / W
+    sz = np.sqrt((w[:, None] * zc * zc).sum(0) / W)
+    st = np.sqrt((w[:, None] * tc * tc).sum(0) / W)
+    still = st <= 1e-14 * np.maximum(np.abs(th).max(0), 1e-300)      # the chain never moved it
+    cov = (w[:, None] * zc).T @ tc / W
+    den = sz[:, None] * st[None, :]
+    corr = np.where((den > 0) & ~still[None, :], cov / np.where(den > 0, den, 1.0), 0.0)
+    strongest = [names[int(np.argmax(np.abs(c)))] if np.any(c != 0) else None for c in corr]
+    return {'names': list(names), 'corr': corr, 'strongest': strongest}
+
+
+class EnsembleModes(_Accumulator):
+    '''The members' transformed fields of `pop_model` on the listed model days (strictly increasing, at most 8,
+    default all) kept on the device as fp64 -- X = v ('raw') or sqrt(v) ('sqrt', the default: the Hellinger-type
+    transform of Legendre & Gallagher 2001 for count-like fields) -- with an integer weight per member, and from
+    them the weighted mean plane, the M x M table of inner products of the (centred) fields, a symmetric fp64 product
+    on the matrix units, and linear combinations of the (centred) fields.  mean and combine are bit for bit numpy
+    loops in add order; the table is symmetric to the bit, the same bits on every call, and within
+    2 N^2 2^-53 sqrt(G_ii G_jj) of the exact product.  day 'all' of `table` is the space-time table, the per-day
+    tables added in slot order on the host.'''
+    _prefix, _noun = 'ps_modes', 'ensemble modes'
+    _info_types = (C.c_double, C.c_int64, C.c_int64, C.c_int64)      # weight, members, capacity, bytes
+    _prof_pairs = 4
+
+    def __init__(self, pop_model, days=None, transform='sqrt'):
+        self._setup(pop_model, None, range(len(pop_model.days)) if days is None else days, transform)
+
+    @classmethod
+    def for_projection(cls, source, transform='sqrt'):
+        '''The modes of the outputs of `source` (a ReleaseSites or a Projection; at most 8 outputs), the slots its
+        outputs in ascending order: `add(weight)` stores the outputs of its last `apply()`.  `days` holds the output
+        labels.'''
+        self = cls.__new__(cls)
+        self._setup(source.pm, source, _output_labels(source), transform)
+        return self
+
+    def _setup(self, pop_model, projection, days, transform):
+        if transform not in MODE_TRANSFORMS:
+            raise ValueError("transform must be 'sqrt' or 'raw', got %r" % (transform,))
+        days = check_arrival_days(days)
+        if len(days) > MAX_MODE_DAYS:
+            raise ValueError('ensemble modes take at most %d days, got %d' % (MAX_MODE_DAYS, len(days)))
+        self.transform = transform
+        self._attach(pop_model)
+        self._set_source(projection, days)
+        self.member_nbytes = len(self.days) * self.pitch * 8
+        self._create(len(self.days), MODE_TRANSFORMS[transform])
+
+    def reserve(self, n):
+        '''room for n members' fields now, so that no add has to grow them'''
+        self._call('reserve', int(n))
+
+    def add(self, weight=1):
+        '''Store the last evaluation of the model with integer weight >= 1 (one launch on the solver's stream; no host
+        synchronisation unless the fields grow).  On a projection or a plan: its last apply, on the handle's stream.'''
+        self._add(weight)
+
+    def add_fields(self, fields, weight=1):
+        '''Store one member from host arrays [days, N, N] of values >= 0 (fields saved by Run); the transform is
+        applied.  ValueError for a shape that does not fit; a negative or non-finite value is refused, nothing stored.'''
+        f = np.ascontiguousarray(fields, dtype=np.float64)
+        if f.shape != (len(self.days), self.N, self.N):
+            raise ValueError('fields of shape %r, the ensemble modes hold %r' % (f.shape, (len(self.days), self.N, self.N)))
+        self._call('add_host', L.p_f64(f), self._weight(weight))
+
+    def merge(self, other):
+        '''self's members, then other's (same device, domain, days and transform); other is unchanged'''
+        if list(other.days) != self.days:
+            raise ValueError('ensemble modes over different days')
+        self._call('merge', other._h)
+
+    def window(self, on):
+        '''on (the default): the table visits only the live window of the mean plane; off: every cell'''
+        self._call('set_window', int(bool(on)))
+
+    @property
+    def capacity(self):
+        '''the members the fields hold room for'''
+        return self._info()[2]
+
+    @property
+    def nbytes(self):
+        '''the device memory the handle holds now'''
+        return self._info()[3]
+
+    @property
+    def weights(self):
+        '''[members] uint32 in add order'''
+        out = np.empty(self.members, dtype=np.uint32)
+        self._call('weights', len(out), out.ctypes.data_as(C.POINTER(C.c_uint32)))
+        return out
+
+    def mean(self, day):
+        '''[N, N] float64: the weighted mean of the transformed fields'''
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        self._call('mean', self._slot_of(day), L.p_f64(out))
+        return out
+
+    def table(self, day, centred=True):
+        '''[members, members] float64: G_ij = sum_c A_i(c) A_j(c) with A = X - mean (centred) or X; day 'all': the
+        sum over the days in slot order'''
+        M = self.members
+        if isinstance(day, str) and day == 'all':
+            total = np.zeros((M, M), dtype=np.float64)
+            for d in self.days:
+                total += self.table(d, centred)
+            return total
+        out = np.empty((M, M), dtype=np.float64)
+        self._call('table', self._slot_of(day), int(bool(centred)), M, L.p_f64(out))
+        return out
+
+    def combine(self, day, coef, centred=True):
+        '''[ncoef, N, N] float64: out_k = sum_m coef[k, m] A_m over the members in add order, coef [ncoef (1..8),
+        members]'''
+        c = np.ascontiguousarray(coef, dtype=np.float64)
+        if c.ndim != 2 or not 1 <= c.shape[0] <= MAX_MODES or c.shape[1] != self.members:
+            raise ValueError('coefficients of shape %r for %d members (1..%d rows)' % (c.shape, self.members, MAX_MODES))
+        out = np.empty((c.shape[0], self.N, self.N), dtype=np.float64)
+        self._call('combine', self._slot_of(day), int(bool(centred)), c.shape[0], L.p_f64(c), L.p_f64(out))
+        return out
+
+    def member(self, m, day):
+        '''[N, N] float64: the stored transformed field of member m (in add order)'''
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        self._call('fetch_member', int(m), self._slot_of(day), L.p_f64(out))
+        return out
+
+    def profile(self, enable=None):
+        '''HIP-event time of the add, mean, table and combine launches: (add ms, adds, mean ms, means, table ms,
+        tables, combine ms, combines); enable switches it'''
+        ms = np.zeros(4, dtype=np.float64)
+        n = np.zeros(4, dtype=np.int64)
+        self._call('prof', -1 if enable is None else int(bool(enable)), L.p_f64(ms), L.p_i64(n))
+        return tuple(v for k in range(4) for v in (float(ms[k]), int(n[k])))
+
+
+class ModesPosterior():
+    '''The ensemble modes as posterior_predictive returns them: `modes` (the EnsembleModes, which it owns), `count`,
+    `planes` (the decompositions it saves: listed days, or ['all']) and `given`.  A decomposition belongs to a plane
+    -- a day of the handle or 'all', the space-time table -- and is cached until members are added; a map belongs to a
+    day and, by default, to that day's own decomposition.  `runs` [(chain, first row, length)] per member and
+    `chains` (per chain the [rows, parameters] array of the model parameters) are set by the driver; `drivers` and
+    `extremes` need them.'''
+
+    def __init__(self, modes, count=4, days='all'):
+        self.modes, self.count = modes, int(count)
+        self.planes = ['all'] if isinstance(days, str) else [d for d in days if d in modes.days]
+        self.given = None
+        self.runs = self.chains = None
+        self._cache = {}
+        self._members = -1
+
+    days = property(lambda self: self.modes.days)
+    transform = property(lambda self: self.modes.transform)
+
+    def reserve(self, n):
+        self.modes.reserve(n)
+
+    def add(self, weight=1):
+        self.modes.add(weight)
+        self._members = -1
+
+    def merge(self, other):
+        self.modes.merge(other.modes)
+        self._members = -1
+
+    def close(self):
+        self.modes.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def weights(self):
+        return self.modes.weights
+
+    def decomposition(self, plane):
+        '''mode_decomposition of the centred table of `plane` (a day or 'all'), cached until members are added.
+        Centring leaves M - 1 directions, so at most that many modes are kept: the last eigenvalue of a centred
+        table is rounding error of the table's size, which may lie above the floor of mode_decomposition.'''
+        if self._members != self.modes.members:
+            self._cache, self._members = {}, self.modes.members
+        if plane not in self._cache:
+            count = max(1, min(self.count, self._members - 1))
+            self._cache[plane] = mode_decomposition(self.modes.table(plane, True), self.weights, count)
+        return self._cache[plane]
+
+    def eigenvalues(self, day):
+        return self.decomposition(day)['eigenvalues']
+
+    def explained(self, day):
+        return self.decomposition(day)['explained']
+
+    def separated(self, day):
+        '''per kept mode North's rule against its neighbours in the whole spectrum'''
+        dec = self.decomposition(day)
+        return separated(dec['spectrum'], self.weights)[:dec['count']]
+
+    def scores(self, day):
+        '''[members, K]: the standardised scores'''
+        return self.decomposition(day)['scores']
+
+    def _mode(self, k, plane):
+        dec = self.decomposition(plane)
+        return dec, _Handle._index(k, dec['count'], 'mode')
+
+    def unit_patterns(self, day, plane=None):
+        '''[K, N, N]: e_k of the decomposition of `plane` (default: the day's own) on `day`, every kept mode from one
+        pass over the members'''
+        dec = self.decomposition(day if plane is None else plane)
+        if not dec['count']:
+            return np.zeros((0, self.modes.N, self.modes.N))
+        return self.modes.combine(day, dec['coef'], True)
+
+    def unit_pattern(self, k, day, plane=None):
+        '''[N, N]: e_k, of unit norm over its plane'''
+        dec, k = self._mode(k, day if plane is None else plane)
+        return self.modes.combine(day, dec['coef'][k:k + 1], True)[0]
+
+    def pattern(self, k, day, plane=None):
+        '''[N, N]: sqrt(lambda_k) e_k, the change of the transformed field per +1 sd of the score'''
+        dec, k = self._mode(k, day if plane is None else plane)
+        return np.sqrt(dec['eigenvalues'][k]) * self.unit_pattern(k, day, plane)
+
+    def thetas(self):
+        '''[members, parameters]: the model parameters of the members' runs'''
+        if self.runs is None or self.chains is None:
+            raise ValueError('the runs of the members are not known')
+        return np.array([np.asarray(self.chains[ci])[first] for ci, first, _l in self.runs], dtype=np.float64)
+
+    def drivers(self, day):
+        '''score_drivers of the plane's scores against the model parameters of the members' runs'''
+        return score_drivers(self.scores(day), self.thetas(), self.weights, model_names())
+
+    def extremes(self, k, day):
+        '''the members with the lowest and the highest score on mode k, each with its score and, where the runs are
+        known, its run (chain, first_row, length, params), among equals the smallest index'''
+        dec, k = self._mode(k, day)
+        z = dec['scores'][:, k]
+        out = {}
+        for name, m in (('low', int(np.argmin(z))), ('high', int(np.argmax(z)))):
+            out[name] = {'member': m, 'score': float(z[m]), 'run': None}
+            if self.runs is not None:
+                ci, first, length = self.runs[m]
+                out[name]['run'] = {'chain': int(ci), 'first_row': int(first), 'length': int(length)}
+                if self.chains is not None:
+                    out[name]['run']['params'] = {n: float(v) for n, v in
+                                                  zip(model_names(), np.asarray(self.chains[ci])[first])}
+        return out
+
+    def reconstruct(self, m, day, modes=None, plane=None):
+        '''[N, N]: mean + sum over the first `modes` (default all kept) of score x pattern, the transformed field of
+        member m as the modes see it'''
+        dec = self.decomposition(day if plane is None else plane)
+        K = dec['count'] if modes is None else min(int(modes), dec['count'])
+        out = self.modes.mean(day)
+        if K:
+            e = self.modes.combine(day, dec['coef'][:K], True)
+            for k in range(K):
+                out = out + dec['scores'][m, k] * np.sqrt(dec['eigenvalues'][k]) * e[k]
+        return out
+
+
+def save_modes(outfile, post):
+    '''outfile.npz of one ModesPosterior: per plane p of its planes (a day, or 'all') `{p}_eigenvalues`,
+    `{p}_explained`, `{p}_separated`, `{p}_scores` [M, K] and, where the runs are known, `{p}_drivers` [K, nparam];
+    per day of a plane dense `{day}_mean` and `{day}_mode{k}` (sqrt(lambda_k) e_k; dense because the patterns are
+    signed and nowhere sparse); `weights`, `transform`, `days`.  -> its block for the json: the settings, the members,
+    n_eff and per plane the explained shares, the separated flags, the strongest driver of each mode and the runs of
+    the extremes'''
+    w = post.weights
+    out = {'weights': w, 'transform': np.asarray(post.transform), 'days': np.asarray(post.days)}
+    planes = []
+    known = post.runs is not None and post.chains is not None
+    for p in post.planes:
+        dec = post.decomposition(p)
+        K = dec['count']
+        sep = post.separated(p)
+        out.update({'%s_eigenvalues' % p: dec['eigenvalues'], '%s_explained' % p: dec['explained'],
+                    '%s_separated' % p: sep, '%s_scores' % p: dec['scores']})
+        drv = post.drivers(p) if known else None
+        if drv is not None:
+            out['%s_drivers' % p] = drv['corr']
+        for d in (post.days if p == 'all' else [p]):
+            out['%s_mean' % d] = post.modes.mean(d)
+            e = post.unit_patterns(d, p)
+            for k in range(K):
+                out['%s_mode%d' % (d, k)] = np.sqrt(dec['eigenvalues'][k]) * e[k]
+        planes.append({'plane': p, 'count': K, 'total_variance': dec['total_variance'],
+                       'explained': [float(v) for v in dec['explained']],
+                       'separated': [bool(v) for v in sep],
+                       'planes_not_patterns': [k for k in range(K) if not sep[k]],
+                       'strongest_driver': None if drv is None else drv['strongest'],
+                       'extremes': [post.extremes(k, p) for k in range(K)]})
+    os.makedirs(os.path.dirname(os.path.abspath(str(outfile))), exist_ok=True)
+    np.savez(str(outfile), **out)
+    return {'count': post.count, 'transform': post.transform, 'days': list(post.days),
+            'planes_given': 'all' if post.planes == ['all'] else list(post.planes), 'members': int(len(w)),
+            'total_weight': int(w.sum()), 'n_eff': effective_members(w), 'planes': planes}
+
+
 MAX_RANGE_FRACTIONS = 4
 
 
@@ -1794,10 +2211,10 @@ def exposure_plan(exposure, ndays=None):
 # 'apply' is the source's own.  The three orders differ for no better reason than the history of the maps.
 FEED_ORDER = {
     'days': ('summary', 'core_range', 'reweight', 'catch', 'neighbourhood', 'information', 'excursion', 'mc_error',
-             'sensitivity', 'histogram', 'arrival', 'peak', 'patches'),
+             'sensitivity', 'histogram', 'arrival', 'peak', 'patches', 'modes'),
     'projection': ('apply', 'summary', 'reweight', 'mc_error', 'sensitivity', 'histogram', 'catch'),
     'sites': ('apply', 'summary', 'reweight', 'mc_error', 'sensitivity', 'histogram', 'arrival', 'peak', 'excursion',
-              'core_range', 'catch', 'neighbourhood', 'information', 'patches'),
+              'core_range', 'catch', 'neighbourhood', 'information', 'patches', 'modes'),
     'compare': ('apply', 'contrast'),
 }
 
@@ -1843,6 +2260,7 @@ FEED = {
     'mc_error': _add_halves,
     'contrast': _add_length,
     'patches': _add_length,
+    'modes': _add_length,
 }
 ACCUMULATORS = tuple(name for name in FEED if name != 'apply')
 
@@ -1898,6 +2316,32 @@ def _build_information(fs, q):
         return ip
 
 
+def _build_modes(fs, q):
+    plan = q.md_plan
+    if plan is not None:
+        if fs._kind == 'days':
+            days = fs._days if isinstance(plan['days'], str) else plan['days']
+            em = EnsembleModes(fs._source, days, plan['transform'])
+        else:
+            em = EnsembleModes.for_projection(fs._source, plan['transform'])
+        mp = _owned_by(em, ModesPosterior, plan['count'], plan['days'])
+        mp.given = q.modes
+        return mp
+
+
+def _reserve_modes(mp, nruns):
+    '''room for a chain's runs before its first evaluation; where the device has not that much free, a ValueError
+    that names the figure'''
+    try:
+        mp.reserve(nruns)
+    except L.HipError as e:
+        if e.code != L.PS_ERR_OOM:
+            raise
+        em = mp.modes
+        raise ValueError('modes: %d members x %d days x %d cells x 8 B = %.3g GB do not fit the free device memory (%s)'
+                         % (nruns, len(em.days), em.pitch, nruns * len(em.days) * em.pitch * 8e-9, e))
+
+
 # How each accumulator is built for the set fs from the checked request q (None or empty: not asked for).  The choice
 # between the model's day fields and a source's outputs is _FieldSet._over's.
 BUILD = {
@@ -1917,6 +2361,7 @@ BUILD = {
     'mc_error': _build_mc_error,
     'contrast': lambda fs, q: PlanContrast(fs._against, fs._source, q.thresholds),
     'patches': lambda fs, q: q.pt_thr and fs._over(PatchMaps, (q.pt_thr, fs._days, q.pt_conn), (q.pt_thr, q.pt_conn)),
+    'modes': _build_modes,
 }
 
 
@@ -1965,6 +2410,8 @@ class _FieldSet():
                 self._days = acc.days
             if name in ('excursion', 'core_range', 'patches') and acc is not None:
                 acc.reserve(nruns)
+            if name == 'modes' and acc is not None:
+                _reserve_modes(acc, nruns)
         return self
 
     def feed(self, m):
@@ -4714,14 +5161,17 @@ class PredictiveResult():
     outputs ('all' or a list of days) and `representative_chains` per chain the model parameters of its rows, all
     None where not asked for (the plan then carries a `representative` of its own); `neighbourhood`: the
     NeighbourhoodPosterior of the windows over the model's day fields, None where not asked for (the plan then
-    carries a `neighbourhood` of its own over the windows on its output days).'''
+    carries a `neighbourhood` of its own over the windows on its output days); `modes`: the ModesPosterior over the
+    listed days of the model's day fields, None where not asked for (the plan then carries a `modes` of its own).'''
 
     def __init__(self, summary, rows, evaluations, failed, seconds, runs, observations, provenance, days,
                  histogram=None, quantiles=None, arrival=None, arrival_levels=None, emergence=None, exposure=None,
                  sites=None, sensitivity=None, contrast=None, compare_plan=None, mc_error=None, mc_plan=None,
                  peak=None, excursion=None, excursion_levels=None, reweight=None, reweight_info=None, catch=None,
                  information=None, core_range=None, core_range_levels=None, patches=None, patch_levels=None,
-                 representative=None, representative_days=None, representative_chains=None, neighbourhood=None):
+                 representative=None, representative_days=None, representative_chains=None, neighbourhood=None,
+                 modes=None):
+        self.modes = modes
         self.neighbourhood = neighbourhood
         self.representative = representative
         self.representative_days = representative_days
@@ -4813,6 +5263,8 @@ class PredictiveResult():
         their block under `predictive.patches` (`predictive.sites.patches`).
         Representative members go into outfile_repr.npz (save_representative; those of a release plan into
         outfile_sites_repr.npz), their block under `predictive.representative` (`predictive.sites.representative`).
+        Ensemble modes go into outfile_modes.npz (save_modes; those of a release plan into outfile_sites_modes.npz),
+        their block under `predictive.modes` (`predictive.sites.modes`).
         -> (npz path, json path)'''
         s = self.summary
         if s is None:
@@ -4910,6 +5362,11 @@ class PredictiveResult():
                 block = save_representative('%s_%srepr' % (outfile, name), rp, self.runs, self.representative_chains,
                                             self.representative_days)
                 (meta['predictive'][name[:-1]] if name else meta['predictive'])['representative'] = block
+        for name, mp in (('', self.modes), ('sites_', None if self.sites is None else self.sites.modes)):
+            if mp is not None:
+                block = save_modes('%s_%smodes' % (outfile, name), mp)
+                block['given'] = mp.given
+                (meta['predictive'][name[:-1]] if name else meta['predictive'])['modes'] = block
         if self.patches is not None:
             meta['predictive']['patches'] = save_patches('%s_patch' % outfile, self.patches, self.patch_levels)
         if self.core_range is not None:
@@ -5057,6 +5514,7 @@ def _check_request(q):
     days, thresholds = q.days, q.thresholds
     q.cr_frac = q.cr_levels = q.in_plan = q.ct_plan = q.rw_plan = q.ex_thr = q.ex_levels = None
     q.pk_thr = q.pk_levels = q.mc_batches = q.pt_thr = q.pt_conn = q.pt_levels = q.rp_plan = q.nb_plan = None
+    q.md_plan = None
 
     def ndays0():                     # the model is touched only where an option needs it
         return None if pm0 is None else len(pm0.days)
@@ -5180,6 +5638,16 @@ def _check_request(q):
         q.pt_thr, q.pt_conn, q.pt_levels = check_patches(q.patches, days)
         if days is None:
             check_arrival_days(range(len(q.pms[0].days)))
+    if q.modes is not None and q.modes is not False:           # after every other check
+        if q.evaluate is not None:
+            raise ValueError('modes= needs the device: not with evaluate=')
+        nd = len(q.pms[0].days)
+        q.md_plan = check_modes(q.modes, nd)
+        if isinstance(q.md_plan['days'], str):
+            check_modes(q.modes, list(range(nd)) if days is None else list(days))     # 'all': the summary's days
+        if q.site_plan is not None and len(q.site_plan[1]) > MAX_MODE_DAYS:
+            raise ValueError('modes: the release plan has %d output days, at most %d fit'
+                             % (len(q.site_plan[1]), MAX_MODE_DAYS))
     return q
 
 
@@ -5218,7 +5686,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                          arrival=None, arrival_levels=(0.05, 0.5, 0.95), emergence=None, exposure=None, sites=None,
                          sensitivity=None, compare=None, mc_error=None, peak=None, excursion=None, reweight=None,
                          catch=None, information=None, core_range=None, patches=None, representative=None,
-                         neighbourhood=None):
+                         neighbourhood=None, modes=None):
     '''Posterior predictive spread of one or more chains (`Sampler.save` files or (trace, names) pairs). Burn and
     thin apply per chain; consecutive rows with identical model parameters are one evaluation weighted by the
     run's length.
@@ -5380,7 +5848,19 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         own over the windows whose day is an output day of the plan, in `sites.neighbourhood`; emergence and
         exposure get none. Sums or means over the disc, other footprints, and neighbourhood versions of the
         arrival, peak, excursion, range, patch, sensitivity and contrast maps are not computed. Without
-        neighbourhood= no call is added and `neighbourhood` is None.'''
+        neighbourhood= no call is added and `neighbourhood` is None.
+
+    modes: True or dict(days=[...] | 'all', count=4, transform='sqrt' | 'raw') (check_modes; not with evaluate=; bad
+        arguments fail before any evaluation): in what ways do the members differ?  Each chain then also keeps every
+        member's transformed day fields on the device (EnsembleModes over the listed days, or over the summary's
+        days for 'all'; at most 8), reserved for the chain's runs before its first evaluation -- a ValueError names
+        members x days x cells x 8 B where the device has not that much free -- and fed the run's weight last,
+        merged in chain order into `modes` (a ModesPosterior: `explained`, `pattern`, `scores`, `drivers`,
+        `extremes`, `reconstruct`; members in the order of `runs`).  Listed days get a decomposition each, 'all' the
+        space-time one.  With sites= the plan's outputs (at most 8) get one of their own (`sites.modes`), its planes
+        the listed days that are output days.  Rotated or sparse modes, modes of the peak, catch or neighbourhood
+        fields and the Monte Carlo error or reweighting of the modes are not computed.  Without modes= no call is
+        added and `modes` is None.'''
     q = types.SimpleNamespace(**locals())
     t0 = time.perf_counter()
     _check_request(q)                 # bad arguments fail before any evaluation
@@ -5440,6 +5920,12 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
             for fs in merged.values():
                 fs.close()
             raise
+    if q.md_plan is not None:         # the members are those of run_rec below
+        md_runs = [(ci, first, length) for ci, p in enumerate(prepared)
+                   for (first, length), e in zip(p[1], results[ci][0]) if e is not None]
+        for fs in (day, merged.get('sites')):
+            if fs is not None and fs.modes is not None:
+                fs.modes.runs, fs.modes.chains = md_runs, [p[0][:, p[2]] for p in prepared]
     rw_info = None
     if q.rw_plan is not None:
         import warnings
@@ -5493,7 +5979,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         patches=day.patches, patch_levels=q.pt_levels if q.pt_thr else None,
         representative=day.representative, representative_days=q.rp_plan['days'] if q.rp_plan else None,
         representative_chains=[p[0][:, p[2]] for p in prepared] if q.rp_plan else None,
-        neighbourhood=day.neighbourhood)
+        neighbourhood=day.neighbourhood, modes=day.modes)
     if day.information is not None:   # the stated convention: past cap / 2 the ensemble bounds the map
         warn_information(day.information)
         if 'sites' in merged:

@@ -64,6 +64,7 @@ Without --chain a short chain is sampled first (--samples) and saved next to --o
         [--reweight 'NAME:east,north,day,kind,rate[,n];...'] [--reweight-file NAME=weights.npy]
         [--catch 'DAY,RATE[,N];...'] [--catch-levels 0.5,0.95] [--catch-emergence 'OBSDAY,RATE[,N];...']
         [--information 'DAY,RATE[,YMAX];...'] [--neighbourhood 'DAY,RADIUS_M;...']
+        [--modes [K]] [--modes-days d1,d2|all] [--modes-transform sqrt|raw]
 """
 import argparse
 import json
@@ -180,6 +181,13 @@ def main():
     ap.add_argument('--catch-levels', default='0.5,0.95', help='levels of the catch maps (with --catch)')
     ap.add_argument('--catch-emergence', default='', help="traps 'OBSDAY,RATE[,N];...' over the emergence days of "
                     '--emergence (with --catch)')
+    ap.add_argument('--modes', nargs='?', const=4, type=int, default=None, metavar='K',
+                    help='ensemble modes: the K (1..8, default 4) leading weighted principal components of the '
+                         "members' transformed day fields, saved as PREFIX_modes.npz")
+    ap.add_argument('--modes-days', default='all', help="days 'd1,d2,...' (at most 8) with a decomposition each, or "
+                                                        "'all': the space-time decomposition (with --modes)")
+    ap.add_argument('--modes-transform', default='sqrt', choices=('sqrt', 'raw'),
+                    help='the transform of the fields before the modes are taken (with --modes)')
     ap.add_argument('--neighbourhood', default='', help="windows 'DAY,RADIUS_M;...': per cell the probability of at "
                     'least each of --thresholds somewhere within RADIUS_M of it on model day DAY (default: off)')
     ap.add_argument('--information', default='', help="described traps 'DAY,RATE[,YMAX];...': per cell the mutual "
@@ -285,6 +293,11 @@ def main():
         neighbourhood = parse_windows(args.neighbourhood)
         check_neighbourhood(neighbourhood, None, 10000.0 / args.rad_res)
     wd, days = PM.get_wind_data(os.path.join(ROOT, 'parasitoids_amd', 'data', 'kalbar'), 30, '00:00')
+    modes = None
+    if args.modes is not None:           # as do bad --modes settings
+        from parasitoids_amd.predictive import check_modes
+        md_days = args.modes_days if args.modes_days == 'all' else [int(d) for d in args.modes_days.split(',') if d.strip()]
+        modes = check_modes(dict(count=args.modes, days=md_days, transform=args.modes_transform), len(days))
 
     def make_pm():
         return PopModel(wd, days, domain_info=(10000.0, args.rad_res), r_number=130000, mode=args.mode)
@@ -341,6 +354,7 @@ def main():
                                **({'neighbourhood': neighbourhood} if neighbourhood else {}),
                                **({'core_range': core_range} if core_range else {}),
                                **({'patches': patches} if patches else {}),
+                               **({'modes': modes} if modes else {}),
                                **({'representative': representative} if representative else {}))
     dt = time.perf_counter() - t0
     # accumulate-kernel time: the same members once more with HIP events around every add
@@ -503,6 +517,15 @@ def main():
         res.excursion.profile(True)     # the finalize and every map launch of the save
     if representative:
         res.representative.overlap.profile(True)     # every pair table and subset plane of the save
+    if modes:
+        from parasitoids_amd.predictive import EnsembleModes
+        res.modes.modes.profile(True)                # every table and combine of the save
+        with EnsembleModes(pm, res.modes.days, modes['transform']) as MD:    # the add alone: the last member, 5 times
+            MD.reserve(5)
+            MD.profile(True)
+            for _ in range(5):
+                MD.add(1)
+            md_add_ms, md_adds = MD.profile()[:2]
     if RG is not None:
         rg_ms, rg_launches = RG.profile()[:2]
         RG.close()
@@ -646,6 +669,16 @@ def main():
         out['repr_members'] = res.excursion.members
         out['repr_bytes'] = res.representative.overlap.nbytes
         out['outputs'] += ['%s_repr.npz' % args.out] + (['%s_sites_repr.npz' % args.out] if sites else [])
+    if modes:
+        md_prof = res.modes.modes.profile()
+        out['modes_table_ms'] = round(md_prof[4] / max(md_prof[5], 1), 3)     # per table call of the save, by HIP events
+        out['modes_table_calls'] = md_prof[5]
+        out['modes_combine_ms'] = round(md_prof[6] / max(md_prof[7], 1), 3)
+        out['modes_add_ms_per_member'] = round(md_add_ms / max(md_adds, 1), 4)
+        out['modes_members'] = res.modes.modes.members
+        out['modes_bytes'] = res.modes.modes.nbytes
+        out['modes'] = modes
+        out['outputs'] += ['%s_modes.npz' % args.out] + (['%s_sites_modes.npz' % args.out] if sites else [])
     if patches:
         out['patch_thresholds'] = patches['thresholds']
         out['patch_connectivity'] = patches['connectivity']
@@ -706,7 +739,7 @@ def main():
     if res.mc_error is not None:
         res.mc_error.close()
     for pr in (res.representative, res.emergence, res.exposure, res.sites, res.contrast, res.peak, res.excursion, res.catch, res.information,
-               res.core_range, res.patches, res.neighbourhood):
+               res.core_range, res.patches, res.neighbourhood, res.modes):
         if pr is not None:
             pr.close()
     for p in pms:
