@@ -679,6 +679,71 @@ int ps_sens_reset(ps_sens* h);
 int ps_sens_prof(ps_sens* h, int enable, double* total_ms, int64_t* launches);
 void ps_sens_destroy(ps_sens* h);
 
+/* ---- posterior dependence maps: the correlation ratio of each cell on each scalar of the members ----
+ * (no reference counterpart; where ps_sens measures a linear dependence, this measures any dependence of the
+ * cell on ONE scalar at a time: eta2_p = Var_b(E[v | scalar p in bin b]) / Var(v), Pearson's correlation ratio,
+ * the given-data estimator of the first-order variance-based index.)  A generic accumulator of per-bin sums
+ * of fields: the caller bins every scalar of a member and passes the bin indices -- the handle does not know
+ * what the scalars or the bin edges are.  It lives on one device and holds nslot slots of N x N cells (pitch
+ * as ps_summary), all fp64: mean[slot], M2[slot], S[param][bin][slot] with S_pb = the sum of w v over the
+ * members whose scalar p fell in bin b, and after finalisation eta[param][slot] (fp64) and dom[slot] (uint8).
+ * Limits: 1 <= nparam <= 16, 2 <= nbin <= 16, nslot >= 1.  The whole block,
+ * ((2 + nparam * nbin + nparam) * 8 + 1) * nslot * pitch bytes, is checked against the free device memory
+ * first: PS_ERR_OOM before anything is allocated.  Host side: the total weight W (< 2^32) and the member
+ * count.  One thread owns a pair of cells: no atomics, the same calls in the same order give the same bits.
+ * Every operation records an event that the next one waits on, on whatever stream it runs (the solver's for
+ * add, the handle's own otherwise). */
+typedef struct ps_depend ps_depend;
+int ps_depend_create(int device, int N, int nslot, int nparam, int nbin, ps_depend** out);
+/* Accumulate one member with integer weight w >= 1 from the records of solver s: the slot descriptors and
+ * the value v of a cell are those of ps_summary_add (same arguments, same value bit for bit).  bin[nparam]:
+ * the member's bin of every scalar, each in 0..nbin - 1, nparam the handle's.  Per cell, with W' = W + w:
+ *   d = v - mean;  where d != 0:  mean += d w / W',  M2 += w d (v - mean)
+ *                                                  (the statements of ps_summary_add: the same bits)
+ *   wv = w v;  S[p][bin[p]] = S[p][bin[p]] + wv    for every p (the product and the sum each rounded on its own)
+ * so a host loop with one rounded operation per statement reproduces mean and every S plane bit for bit.  A
+ * pair of cells with v == 0 in both reads the record and the two moments and touches no S.  One launch per 32
+ * slots on the solver's stream, no host synchronisation; every descriptor is resolved before anything is
+ * enqueued.  A bin out of range, a weight of 0, another nparam or nslot than the handle's, or a total weight
+ * that would reach 2^32: PS_ERR_BAD_ARG, nothing is added anywhere. */
+int ps_depend_add(ps_depend* h, ps_solver* s, int nslot, const int32_t* kind, const int32_t* idx,
+                  const double* stat_scale, const double* post_scale, const int32_t* use_delta, double negval,
+                  int nparam, const int32_t* bin, uint32_t weight);
+/* The same member whose values are the current outputs of a projection or a release plan, as
+ * ps_summary_add_project / ps_summary_add_sites take them: slot k takes Y_k, on the handle's stream behind the
+ * source's last operation; its next apply waits for the read.  PS_ERR_STATE where the source has no finished
+ * fields. */
+int ps_depend_add_project(ps_depend* h, ps_project* p, int nparam, const int32_t* bin, uint32_t weight);
+int ps_depend_add_sites(ps_depend* h, ps_sites* p, int nparam, const int32_t* bin, uint32_t weight);
+/* dst += src, same device, N, slots, nparam and nbin (the caller answers for equal bin edges); src stays as it
+ * is.  Every operation rounded on its own, in this order, W = Wa + Wb:
+ *   fb = Wb / W;  fab = (Wa Wb) / W;  d = mean_b - mean_a
+ *   mean = mean_a + d fb;  M2 = (M2_a + M2_b) + (d d) fab        (Chan et al., the formulas of ps_summary_merge)
+ *   S_pb = S_pb,a + S_pb,b                                       plane by plane
+ * Into an empty dst (W = 0) it is a device copy, bit for bit. */
+int ps_depend_merge(ps_depend* dst, ps_depend* src);
+/* Wb: nparam x nbin, row-major, the weight of the members per scalar and bin: integers in 0..2^32 - 1 held
+ * exactly as doubles, every row summing to W (PS_ERR_BAD_ARG otherwise); nparam and nbin the handle's.  Per cell,
+ * every product, sum and quotient rounded on its own, W the total weight:
+ *   M2 == 0:  eta_p = 0 for every p, dom = 255
+ *   else      var = M2 / W;  per p, s = +0.0 and over the bins with Wb > 0 in ascending order
+ *               mb = S_pb / Wb;  d = mb - mean;  q = d d;  q = Wb q;  s = s + q
+ *             eta_p = min((s / W) / var, 1), and exactly 0 where fewer than two bins of p have Wb > 0 (a scalar
+ *             that never left one bin: nothing lies between bins, and S / W is not the mean bit for bit)
+ *             dom = the lowest p that maximises eta_p, compared by a strict > in index order (255 where every
+ *             eta_p is 0)
+ * PS_ERR_STATE at W = 0.  Any later add, merge or reset invalidates the result. */
+int ps_depend_finalize(ps_depend* h, int nparam, int nbin, const double* Wb);
+/* one slot to the host (synchronises): what 0 mean, 1 variance M2 / W, 2 dom as doubles (-1 for 255), 3 M2 as
+ * it is, 16 + p eta_p, 256 + 16 p + b the plane S[p][b] as it is.  PS_ERR_STATE at W = 0, and for 2 and 16 + p
+ * unless finalized since the last change. */
+int ps_depend_fetch(ps_depend* h, int slot, int what, double* out /* N*N */);
+int ps_depend_info(ps_depend* h, double* total_weight, int64_t* members);
+int ps_depend_reset(ps_depend* h);
+/* measurement: HIP-event timing of the add launches, as ps_summary_prof */
+int ps_depend_prof(ps_depend* h, int enable, double* total_ms, int64_t* launches);
+void ps_depend_destroy(ps_depend* h);
+
 /* ---- paired contrast of two release plans (or two projections): A - B member by member ----
  * (no reference counterpart.)  Both plans are driven by the same member, so the posterior of their
  * difference -- its variance, P(A beats B) at a cell, P(A covers more than B) -- needs the pairing and cannot

@@ -199,6 +199,18 @@ SIGNATURES = {
     'ps_sens_reset': (C.c_int, [_VP]),
     'ps_sens_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P]),
     'ps_sens_destroy': (None, [_VP]),
+    'ps_depend_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_VP)]),
+    'ps_depend_add': (C.c_int, [_VP, _VP, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P, C.c_double, C.c_int, _I32P,
+                                C.c_uint32]),
+    'ps_depend_add_project': (C.c_int, [_VP, _VP, C.c_int, _I32P, C.c_uint32]),
+    'ps_depend_add_sites': (C.c_int, [_VP, _VP, C.c_int, _I32P, C.c_uint32]),
+    'ps_depend_merge': (C.c_int, [_VP, _VP]),
+    'ps_depend_finalize': (C.c_int, [_VP, C.c_int, C.c_int, _F64P]),
+    'ps_depend_fetch': (C.c_int, [_VP, C.c_int, C.c_int, _F64P]),
+    'ps_depend_info': (C.c_int, [_VP, _F64P, _I64P]),
+    'ps_depend_reset': (C.c_int, [_VP]),
+    'ps_depend_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P]),
+    'ps_depend_destroy': (None, [_VP]),
     'ps_contrast_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _F64P, C.POINTER(_VP)]),
     'ps_contrast_add_sites': (C.c_int, [_VP, _VP, _VP, C.c_uint32]),
     'ps_contrast_add_project': (C.c_int, [_VP, _VP, _VP, C.c_uint32]),

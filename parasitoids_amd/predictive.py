@@ -26,6 +26,10 @@ parameters of the member behind them (ps_sens_*, csrc/ps_sens.hip; `ParamMoments
 host): which parameter the spread at a cell comes from, as correlation maps, the share of the variance a linear
 dependence on the parameters explains, and the dominant parameter -- a chain stores no fields, so this
 covariance cannot be formed after the run.
+`DependenceMaps` keeps, on the device, per cell the sums of the same values over the bins of each model parameter
+(ps_depend_*, csrc/ps_depend.hip): the correlation ratio eta^2 of every cell on every parameter, which also sees a
+dependence that is not linear -- the ring around the plume where the density first rises and then falls with the
+diffusion scale, and the correlation is nearly 0.
 `MonteCarloError` keeps, on the device, one sequence of members -- a chain, or half of one -- as batch means of
 exactly b rows of weight (ps_mcerr_*, csrc/ps_mcerr.hip): the Monte Carlo standard error of the posterior mean and
 of the exceedance probabilities, the effective sample size and, over several sequences, the split R-hat
@@ -2211,10 +2215,10 @@ def exposure_plan(exposure, ndays=None):
 # 'apply' is the source's own.  The three orders differ for no better reason than the history of the maps.
 FEED_ORDER = {
     'days': ('summary', 'core_range', 'reweight', 'catch', 'neighbourhood', 'information', 'excursion', 'mc_error',
-             'sensitivity', 'histogram', 'arrival', 'peak', 'patches', 'modes'),
-    'projection': ('apply', 'summary', 'reweight', 'mc_error', 'sensitivity', 'histogram', 'catch'),
-    'sites': ('apply', 'summary', 'reweight', 'mc_error', 'sensitivity', 'histogram', 'arrival', 'peak', 'excursion',
-              'core_range', 'catch', 'neighbourhood', 'information', 'patches', 'modes'),
+             'sensitivity', 'dependence', 'histogram', 'arrival', 'peak', 'patches', 'modes'),
+    'projection': ('apply', 'summary', 'reweight', 'mc_error', 'sensitivity', 'dependence', 'histogram', 'catch'),
+    'sites': ('apply', 'summary', 'reweight', 'mc_error', 'sensitivity', 'dependence', 'histogram', 'arrival', 'peak',
+              'excursion', 'core_range', 'catch', 'neighbourhood', 'information', 'patches', 'modes'),
     'compare': ('apply', 'contrast'),
 }
 
@@ -2250,6 +2254,7 @@ FEED = {
     'histogram': _add_length,
     'arrival': _add_length,
     'sensitivity': lambda acc, fs, m: acc.add(m.theta, m.length),
+    'dependence': lambda acc, fs, m: acc.add(m.theta, m.length),
     'peak': _add_length,
     'excursion': _add_length,
     'core_range': _add_length,
@@ -2329,6 +2334,31 @@ def _build_modes(fs, q):
         return mp
 
 
+def _build_dependence(fs, q):
+    '''one DependenceMaps over the pooled edges; where the device has not that much free, a ValueError that names
+    the figure'''
+    plan = getattr(q, 'dp_plan', None)
+    if plan is None:
+        return None
+    names, edges = plan['params'], q.dp_edges
+    try:
+        if fs._kind == 'days':
+            dm = DependenceMaps(fs._source, names, edges, plan['days'] or fs._days)
+        else:
+            dm = DependenceMaps.for_projection(fs._source, names, edges)
+    except L.HipError as e:
+        if e.code != L.PS_ERR_OOM:
+            raise
+        nbin = max(2, max(len(x) for x in edges) + 1)
+        nslot = len(plan['days'] or fs._days) if fs._kind == 'days' else fs._source.nout
+        raise ValueError('dependence: %d parameters x %d bins x %d slots need %.3g GB, which do not fit the free '
+                         'device memory; days= and a shorter parameter list cut it (%s)'
+                         % (len(names), nbin, nslot,
+                            ((2 + len(names) * nbin + len(names)) * 8 + 1) * nslot * fs._source_pitch() * 1e-9, e))
+    dm.bins_asked = plan['bins']
+    return dm
+
+
 def _reserve_modes(mp, nruns):
     '''room for a chain's runs before its first evaluation; where the device has not that much free, a ValueError
     that names the figure'''
@@ -2349,6 +2379,7 @@ BUILD = {
     'histogram': lambda fs, q: q.levels and fs._over(SpreadHistogram, (q.days, q.bins, q.edges), (q.bins, q.edges)),
     'arrival': lambda fs, q: q.a_thr and fs._over(ArrivalMaps, (q.a_thr, fs._days), (q.a_thr,)),
     'sensitivity': lambda fs, q: q.s_names and fs._over(SensitivityMaps, (q.s_names, fs._days), (q.s_names,)),
+    'dependence': _build_dependence,
     'peak': lambda fs, q: q.pk_thr is not None and _owned_by(
         fs._over(PeakMaps, (q.pk_thr, fs._days), (q.pk_thr,)), PeakPosterior, q.thresholds, q.pk_levels,
         q.bins if q.levels else None, q.edges if q.levels else None),
@@ -2389,6 +2420,12 @@ class _FieldSet():
         self._kind, self._name, self._source, self._owns = kind, name or kind, source, owns
         self._against, self._traps = against, traps
         return self
+
+    def _source_pitch(self):
+        '''the cells of one slot of an accumulator over this set's source, padded as the device pads them'''
+        pm = self._source if self._kind == 'days' else self._source.pm
+        n = (2 * int(pm.rad_res) + 1) ** 2
+        return (n + 63) // 64 * 64
 
     def _over(self, cls, day_args, out_args):
         '''cls over this set's source: the model's day fields or, for_projection, a source's outputs'''
@@ -2476,7 +2513,8 @@ class ProjectedMaps(_FieldSet):
     plan (`posterior_predictive(sites=...)`): `weights` and `in_days` are None, `labels` are the output days,
     `plan` is ReleaseSites.describe() and `arrival` the ArrivalMaps.for_projection (None without arrival
     thresholds), whose accessors take the output day.  `sensitivity`: the SensitivityMaps.for_projection (None
-    unless asked for), which takes the output index.  `mc_error`: the MonteCarloError.for_projection pooled over
+    unless asked for), which takes the output index.  `dependence`: the DependenceMaps.for_projection (None unless
+    asked for), likewise.  `mc_error`: the MonteCarloError.for_projection pooled over
     all chains, with `rhat` (None unless asked for; while the chains run, one chain's two sequences), which takes
     the output index.  `peak`: the PeakPosterior of a release plan's outputs (None unless asked for), whose maps
     take the output day.  `excursion`: the ExcursionMaps.for_projection of a release plan's outputs (None unless
@@ -2493,8 +2531,9 @@ class ProjectedMaps(_FieldSet):
 
     def __init__(self, weights, in_days, labels, summary, histogram=None, arrival=None, plan=None,
                  sensitivity=None, mc_error=None, peak=None, excursion=None, reweight=None, catch=None,
-                 information=None, core_range=None, patches=None, neighbourhood=None):
+                 information=None, core_range=None, patches=None, neighbourhood=None, dependence=None):
         super().__init__(summary=summary, histogram=histogram, arrival=arrival, sensitivity=sensitivity,
+                         dependence=dependence,
                          mc_error=mc_error, peak=peak, excursion=excursion, reweight=reweight, catch=catch,
                          information=information, core_range=core_range, patches=patches,
                          neighbourhood=neighbourhood)
@@ -3253,6 +3292,286 @@ class SensitivityMaps(_Accumulator):
     def profile(self, enable=None):
         '''HIP-event time of the accumulate launches: (total ms, launches); enable switches it'''
         return self._profile(enable)
+
+
+
+# ------------------------------------------------------------------ dependence
+MAX_DEP_BINS = 16          # ps_depend: the bins of one scalar
+DEFAULT_DEP_BINS = 8
+
+
+def dependence_edges(values, weights, bins):
+    '''The interior cut points of one parameter for DependenceMaps: `values` per member, `weights` their positive
+    integer weights (run lengths), `bins` 2..16 -> a strictly increasing float64 array of at most bins - 1 edges;
+    a member's bin is np.searchsorted(edges, value, side='right').  The bins have as nearly equal weight as the
+    distinct values allow, decided in integers: cut j = 1 .. bins - 1 goes behind the distinct value whose
+    cumulative weight c minimises |c bins - j total| (the lower one on a tie), and lies at the midpoint between
+    that value and the next distinct one -- equal values always share a bin and no value sits on an edge.  Cuts
+    that fall together are one: a parameter with fewer distinct values than bins uses fewer bins, a constant
+    one a single bin (no edge).'''
+    if int(bins) != bins or not 2 <= int(bins) <= MAX_DEP_BINS:
+        raise ValueError('dependence bins must be an integer in 2..%d, got %r' % (MAX_DEP_BINS, bins))
+    v = np.array(values, dtype=np.float64).ravel()
+    w = np.asarray(weights).ravel()
+    if v.size == 0 or v.size != w.size:
+        raise ValueError('%d values and %d weights' % (v.size, w.size))
+    if not np.all(np.isfinite(v)):
+        raise ValueError('every value must be finite')
+    if np.any(w != np.floor(w)) or np.any(w < 1):
+        raise ValueError('weights must be positive integers')
+    u, inv = np.unique(v, return_inverse=True)
+    cw = np.cumsum(np.bincount(inv.ravel(), weights=w.astype(np.float64)).astype(np.int64))
+    total, nb = int(cw[-1]), int(bins)
+    edges = []
+    last = -1
+    for j in range(1, nb):
+        if u.size < 2:
+            break
+        i = int(np.argmin(np.abs(cw[:-1] * nb - j * total)))      # the first of equals: the lower value
+        if i == last:
+            continue
+        last = i
+        mid = u[i] + 0.5 * (u[i + 1] - u[i])
+        edges.append(mid if mid > u[i] else u[i + 1])             # neighbouring doubles: the upper one goes right
+    return np.array(edges, dtype=np.float64)
+
+
+def check_dependence(arg):
+    '''posterior_predictive's dependence= argument -> dict(params=[names], bins=B, days=None | [model days]):
+    True (all 15 model parameters, 8 bins), a list of names from mcmc.MODEL_BLOCK (check_sens_params), or
+    dict(params=..., bins=8, days=...) with bins in 2..16 and days a strictly increasing list of model days
+    (default: the summary's); ValueError otherwise'''
+    if isinstance(arg, dict):
+        unknown = sorted(set(arg) - {'params', 'bins', 'days'})
+        if unknown:
+            raise ValueError('dependence: unknown keys %r (params, bins, days)' % (unknown,))
+        params, bins, days = arg.get('params'), arg.get('bins', DEFAULT_DEP_BINS), arg.get('days')
+    else:
+        params, bins, days = arg, DEFAULT_DEP_BINS, None
+    if params is False or (params is not None and params is not True and not isinstance(params, (str, list, tuple))):
+        raise ValueError('dependence parameters must be True or a list of names, got %r' % (params,))
+    names = check_sens_params(params)
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 2 <= int(bins) <= MAX_DEP_BINS:
+        raise ValueError('dependence bins must be an integer in 2..%d, got %r' % (MAX_DEP_BINS, bins))
+    if days is not None:
+        try:
+            days = [int(d) for d in days]
+        except (TypeError, ValueError):
+            raise ValueError('dependence days must be a list of model days, got %r' % (days,))
+        if not days or days[0] < 0 or any(b <= a for a, b in zip(days, days[1:])):
+            raise ValueError('dependence days must be model days >= 0, strictly increasing: %r' % (days,))
+    return {'params': names, 'bins': int(bins), 'days': days}
+
+
+def adjusted_ratio(eta2, members, bins_used):
+    '''max(0, 1 - (1 - eta2)(members - 1) / (members - bins_used)): the epsilon^2 adjustment of a correlation
+    ratio over `bins_used` non-empty bins of `members` members'''
+    n, k = int(members), int(bins_used)
+    if n <= k:
+        raise ValueError('%d members in %d bins: nothing is left to adjust with' % (n, k))
+    return np.maximum(0.0, 1.0 - (1.0 - np.asarray(eta2, dtype=np.float64)) * ((n - 1) / (n - k)))
+
+
+def finalize_bin_weights(params, bin_weights, members):
+    '''Wb [nparam, nbin] contiguous float64 for ps_depend_finalize from the integer bin weights of `members`
+    members.  ValueError when nothing is accumulated or, for any parameter, members < 2 x (its non-empty bins):
+    bins of single members reproduce every member and give eta^2 = 1 by construction -- the argument of
+    finalize_factor's members < rank + 2.'''
+    if int(members) < 1:
+        raise ValueError('nothing accumulated')
+    for n, row in zip(params, np.asarray(bin_weights)):
+        used = int(np.count_nonzero(row))
+        if members < 2 * used:
+            raise ValueError('%d members in %d bins of %r: with fewer than two members per bin on average '
+                             'the bin means reproduce the members and eta^2 is 1 by construction'
+                             % (members, used, n))
+    return L.f64(bin_weights)
+
+
+class DependenceMaps(_Accumulator):
+    '''On which parameter a cell depends, linearly or not: per cell of `pop_model`'s days and per parameter of
+    `params` (names from mcmc.MODEL_BLOCK) the correlation ratio eta^2 = Var_b(E[v | parameter in bin b]) / Var(v)
+    of the value SpreadSummary adds, over the members added, on the device (ps_depend_*, csrc/ps_depend.hip),
+    next to the mean and the variance (the same bits as a SpreadSummary fed alongside).  `edges`: per parameter
+    the interior cut points (dependence_edges), at most 15 each.  `add(theta, weight)` takes the member's full
+    model block and bins the columns.  After `finalize()`: `ratio(day, name)`, `dominant(day)`, `adjusted`,
+    `excess`.  eta^2 is the given-data estimator of the first-order variance-based index (Plischke 2010): a
+    statement about one parameter at a time, like SensitivityMaps.correlation; where the parameters are
+    correlated, as in a posterior, it credits a parameter with what its correlates do.  It holds no interaction
+    or total-effect index, and a parameter without any influence shows `floor(name)` on average, not 0.'''
+
+    _prefix, _noun = 'ps_depend', 'dependence maps'
+
+    def __init__(self, pop_model, params, edges, days=None):
+        self._setup(pop_model, params, edges, _model_days(pop_model, days), None)
+
+    @classmethod
+    def for_projection(cls, projection, params, edges):
+        '''Dependence maps of the outputs of `projection` (a Projection or a ReleaseSites), one slot per output:
+        `add(theta, weight)` accumulates the outputs of its last `apply()`, and the accessors take the output
+        index where the day-based maps take a day.'''
+        self = cls.__new__(cls)
+        self._setup(projection.pm, params, edges, list(range(projection.nout)), projection)
+        return self
+
+    def _setup(self, pop_model, params, edges, days, projection):
+        self.params = check_sens_params(params)
+        known = [m[0] for m in mcmc.MODEL_BLOCK]
+        self._cols = [known.index(n) for n in self.params]
+        self._nblock = len(known)
+        if isinstance(edges, dict):
+            edges = [edges[n] for n in self.params]
+        self.edges = [np.array(e, dtype=np.float64).ravel() for e in edges]
+        if len(self.edges) != len(self.params):
+            raise ValueError('%d lists of edges for %d parameters' % (len(self.edges), len(self.params)))
+        for n, e in zip(self.params, self.edges):
+            if e.size > MAX_DEP_BINS - 1 or not np.all(np.isfinite(e)) or np.any(np.diff(e) <= 0):
+                raise ValueError('the edges of %r must be finite, strictly increasing and at most %d: %r'
+                                 % (n, MAX_DEP_BINS - 1, e.tolist()))
+        self.nbin = max(2, max(e.size for e in self.edges) + 1)
+        self.bins_asked = self.nbin
+        self._attach(pop_model)
+        self._set_source(projection, days, projection and projection.live)
+        self.nbytes = len(self._slot) * self.pitch * ((2 + len(self.params) * self.nbin + len(self.params)) * 8 + 1)
+        self._zero()
+        self._create(len(self._slot), len(self.params), self.nbin)
+
+    def _zero(self):
+        self.bin_weights = np.zeros((len(self.params), self.nbin), dtype=np.int64)
+        self._members = 0
+        self.finalized = False
+
+    def bins_of(self, theta):
+        '''the bin of every listed parameter of the model block `theta` -> int32 [nparam]'''
+        t = np.array(theta, dtype=np.float64).ravel()
+        if t.size != self._nblock:
+            raise ValueError('theta has %d entries, the model block %d' % (t.size, self._nblock))
+        if not np.all(np.isfinite(t[self._cols])):
+            raise ValueError('every listed parameter must be finite: %r' % (t[self._cols].tolist(),))
+        return L.i32([np.searchsorted(e, t[c], side='right') for e, c in zip(self.edges, self._cols)])
+
+    def add(self, theta, weight=1):
+        '''Accumulate the last evaluation of the model (on a projection or a plan: its last apply), whose
+        model block is `theta`, with integer weight >= 1; enqueued, no host synchronisation.'''
+        b = self.bins_of(theta)
+        w = self._weight(weight)
+        state = (self.bin_weights.copy(), self._members)
+        self.bin_weights[np.arange(b.size), b] += w
+        self._members += 1
+        try:
+            self._read('add', self._proj, b.size, L.p_i32(b), w)
+        except Exception:
+            self.bin_weights, self._members = state       # a refused add is added nowhere
+            raise
+        self.finalized = False
+
+    def merge(self, other):
+        '''self += other (same device, domain, days, parameters and edges)'''
+        if (list(other.days) != self.days or other._slot != self._slot or other.params != self.params
+                or len(other.edges) != len(self.edges)
+                or not all(np.array_equal(a, b) for a, b in zip(self.edges, other.edges))):
+            raise ValueError('dependence maps over different days, parameters or edges')
+        self._call('merge', other._h)
+        self.bin_weights = self.bin_weights + other.bin_weights
+        self._members += other._members
+        self.finalized = False
+
+    def reset(self):
+        super().reset()
+        self._zero()
+
+    def bins_used(self, name):
+        '''the bins of parameter `name` that hold a member'''
+        return int(np.count_nonzero(self.bin_weights[self._i(name)]))
+
+    def finalize(self):
+        '''Compute the ratios and `dominant` from the members so far.  ValueError when nothing is accumulated or,
+        for any listed parameter, members < 2 x (its non-empty bins): bins of single members reproduce every
+        member and give eta^2 = 1 by construction.'''
+        Wb = finalize_bin_weights(self.params, self.bin_weights, self._members)
+        self._call('finalize', len(self.params), self.nbin, L.p_f64(Wb))
+        self.finalized = True
+
+    def _fetch(self, day, what):
+        slot = self._slot_of(day)
+        if slot is None:                                          # an output without weight
+            return np.full((self.N, self.N), -1.0 if what == 2 else 0.0)
+        return self.fetch_slot(slot, what)
+
+    def fetch_slot(self, slot, what):
+        '''raw access by slot index (0 mean, 1 variance, 2 dominant, 3 M2, 16 + p eta^2, 256 + 16 p + b the sum
+        of w v over the members of bin b of parameter p)'''
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        self._call('fetch', int(slot), int(what), L.p_f64(out))
+        return out
+
+    def _i(self, name):
+        if name not in self.params:
+            raise ValueError('parameter %r is not among %r' % (name, self.params))
+        return self.params.index(name)
+
+    def mean(self, day):
+        return self._fetch(day, 0)
+
+    def variance(self, day):
+        return self._fetch(day, 1)
+
+    def bin_sum(self, day, name, b):
+        '''the sum of w v over the members whose parameter `name` fell in bin b'''
+        return self._fetch(day, 256 + 16 * self._i(name) + self._index(b, self.nbin, 'bin'))
+
+    def ratio(self, day, name):
+        '''eta^2 of the cell on parameter `name`: the share of the cell's posterior variance that lies between
+        the bin means, in [0, 1], 0 where the cell does not vary'''
+        return self._fetch(day, 16 + self._i(name))
+
+    def dominant(self, day):
+        '''int8 index into `params` of the parameter with the largest eta^2, -1 where nothing varies'''
+        return self._fetch(day, 2).astype(np.int8)
+
+    def floor(self, name):
+        '''(bins used - 1) / (members - 1): what eta^2 of a parameter without any influence shows on average'''
+        if self._members < 2:
+            raise ValueError('the floor needs two members')
+        return (self.bins_used(name) - 1) / (self._members - 1)
+
+    def adjusted(self, day, name):
+        '''max(0, 1 - (1 - eta^2)(members - 1) / (members - bins used)), the classical epsilon^2 adjustment of
+        eta^2 for its floor.  It assumes independent, equally weighted members, which the runs of a chain are
+        not: a guide to what is above the floor, not an interval.'''
+        return adjusted_ratio(self.ratio(day, name), self._members, self.bins_used(name))
+
+    def excess(self, day, name, sensitivity):
+        '''max(0, adjusted - r^2), r the correlation of `sensitivity` (a SensitivityMaps over the same members)
+        with the same parameter: the share that only a non-linear dependence explains.  The binned eta^2 is not
+        >= r^2 in general -- a bin loses the trend inside it -- hence the clip at 0.'''
+        r = sensitivity.correlation(day, name)
+        return np.maximum(0.0, self.adjusted(day, name) - r * r)
+
+    def describe(self):
+        '''the parameter block of a result file'''
+        n = self._members
+        return {'params': list(self.params), 'bins': int(self.bins_asked),
+                'bins_used': [self.bins_used(p) for p in self.params],
+                'edges': [e.tolist() for e in self.edges],
+                'bin_weights': [[int(x) for x in row[:e.size + 1]] for row, e in zip(self.bin_weights, self.edges)],
+                'members': int(n), 'total_weight': int(self.bin_weights[0].sum()),
+                'floor': [self.floor(p) if n >= 2 else None for p in self.params]}
+
+    def profile(self, enable=None):
+        '''HIP-event time of the accumulate launches: (total ms, launches); enable switches it'''
+        return self._profile(enable)
+
+
+def pooled_dependence_edges(prepared, names, bins):
+    '''the edges of every parameter of `names` over the runs of all chains (prepared: per chain (rows, runs, model
+    columns, ...) as _check_request loads them), shared by every chain's DependenceMaps'''
+    known = [m[0] for m in mcmc.MODEL_BLOCK]
+    thetas = np.array([rows[first, mcols] for rows, rl, mcols, *_rest in prepared for first, _n in rl])
+    lengths = np.array([n for _rows, rl, *_rest in prepared for _first, n in rl], dtype=np.int64)
+    if not lengths.size:
+        raise ValueError('dependence: the chains hold no rows')
+    return [dependence_edges(thetas[:, known.index(n)], lengths, bins) for n in names]
 
 
 
@@ -4979,6 +5298,33 @@ def save_sensitivity(outfile, sens, keys, labels):
     return block
 
 
+def save_dependence(outfile, dep, keys, labels, sensitivity=None):
+    '''outfile.npz of one DependenceMaps through save_maps (keys: its days or output indices, labels: theirs in the
+    file), finalized here if it can be: per label `{label}_eta2_{name}` as CSR triplets, dense int8 `{label}_dom`
+    and, with a SensitivityMaps over the same members that lists the name, `{label}_excess_{name}` -> its block for
+    the json (DependenceMaps.describe, `finalized` and, where finalize refused, `reason`; no ratio maps are written
+    then)'''
+    block = dep.describe()
+    try:
+        if not dep.finalized:
+            dep.finalize()
+        block['finalized'] = True
+    except ValueError as e:
+        block['finalized'] = False
+        block['reason'] = str(e)
+    maps, extra = [], {}
+    shared = [n for n in dep.params if sensitivity is not None and n in sensitivity.params]
+    for k, label in zip(keys, labels):
+        if not block['finalized']:
+            break
+        day_maps = [('_eta2_%s' % n, dep.ratio(k, n)) for n in dep.params]
+        day_maps += [('_excess_%s' % n, dep.excess(k, n, sensitivity)) for n in shared]
+        extra['%s_dom' % label] = dep.dominant(k)
+        maps.append((label, day_maps))
+    save_maps(outfile, maps, dict(extra, days=np.array(labels)))
+    return block
+
+
 def save_reweight(outfile, rw, keys, labels):
     '''outfile.npz of one ReweightedSummary through save_maps (keys: its days or output indices, labels: theirs in
     the file): per scenario index j and label the CSR triplets `s{j}_{label}_*` of the reweighted mean,
@@ -5162,7 +5508,9 @@ class PredictiveResult():
     None where not asked for (the plan then carries a `representative` of its own); `neighbourhood`: the
     NeighbourhoodPosterior of the windows over the model's day fields, None where not asked for (the plan then
     carries a `neighbourhood` of its own over the windows on its output days); `modes`: the ModesPosterior over the
-    listed days of the model's day fields, None where not asked for (the plan then carries a `modes` of its own).'''
+    listed days of the model's day fields, None where not asked for (the plan then carries a `modes` of its own);
+    `dependence`: the DependenceMaps over the summary's days (or the days asked for), None where not asked for (the
+    projections and the plan then carry one of their own).'''
 
     def __init__(self, summary, rows, evaluations, failed, seconds, runs, observations, provenance, days,
                  histogram=None, quantiles=None, arrival=None, arrival_levels=None, emergence=None, exposure=None,
@@ -5170,7 +5518,8 @@ class PredictiveResult():
                  peak=None, excursion=None, excursion_levels=None, reweight=None, reweight_info=None, catch=None,
                  information=None, core_range=None, core_range_levels=None, patches=None, patch_levels=None,
                  representative=None, representative_days=None, representative_chains=None, neighbourhood=None,
-                 modes=None):
+                 modes=None, dependence=None):
+        self.dependence = dependence
         self.modes = modes
         self.neighbourhood = neighbourhood
         self.representative = representative
@@ -5234,6 +5583,12 @@ class PredictiveResult():
         `predictive.sensitivity` (`predictive.NAME.sensitivity`) of the json the parameter names, their
         posterior means, sds and correlation matrix, rank and dropped eigenvalues, members and weight, and
         where finalize refused -- too few members -- the reason, the correlations alone being saved.
+        Dependence maps go into outfile_depend.npz (save_dependence; those of a projection or a plan into
+        outfile_NAME_depend.npz): per day `{day}_eta2_{name}_*` CSR triplets of the correlation ratio, dense int8
+        `{day}_dom` and, with sensitivity maps over the same names, `{day}_excess_{name}_*`; their block --
+        parameters, bins asked and used, edges, bin weights, members, weight and floors -- under
+        `predictive.dependence` (`predictive.NAME.dependence`), and where finalize refused the reason, no ratio
+        map being saved.
         A contrast of two plans goes into outfile_contrast.npz: per output day `{label}_*` signed CSR triplets
         (|value| >= 1e-8) of the mean of A - B, `{label}_sd_*`, `{label}_ppos_*` / `{label}_pneg_*` (P(A > B),
         P(A < B)), `{label}_pgain{k}_*` / `{label}_ploss{k}_*`, and `coverage{k}_a` / `coverage{k}_b` [members,
@@ -5308,6 +5663,11 @@ class PredictiveResult():
         if self.sensitivity is not None:
             labels = [s.pm.days[d] if d < len(s.pm.days) else d for d in s.days]
             meta['predictive']['sensitivity'] = save_sensitivity('%s_sens' % outfile, self.sensitivity, s.days, labels)
+        if self.dependence is not None:
+            dm = self.dependence
+            labels = [s.pm.days[d] if d < len(s.pm.days) else d for d in dm.days]
+            meta['predictive']['dependence'] = save_dependence('%s_depend' % outfile, dm, dm.days, labels,
+                                                               self.sensitivity)
         for name, pr in (('emergence', self.emergence), ('exposure', self.exposure), ('sites', self.sites)):
             if pr is None:
                 continue
@@ -5344,6 +5704,10 @@ class PredictiveResult():
             if pr.sensitivity is not None:
                 meta['predictive'][name]['sensitivity'] = save_sensitivity(
                     '%s_%s_sens' % (outfile, name), pr.sensitivity, list(range(len(pr.labels))), pr.labels)
+            if pr.dependence is not None:
+                meta['predictive'][name]['dependence'] = save_dependence(
+                    '%s_%s_depend' % (outfile, name), pr.dependence, list(range(len(pr.labels))), pr.labels,
+                    pr.sensitivity)
             if pr.peak is not None:
                 meta['predictive'][name]['peak'] = save_peak('%s_%s_peak' % (outfile, name), pr.peak,
                                                              list(self.quantiles or ()))
@@ -5507,7 +5871,7 @@ def _check_request(q):
     '''Everything of posterior_predictive's arguments (q: a namespace of them) that can fail before any evaluation,
     in a fixed order -- of two bad arguments the earlier one is reported.  -> q, with the checked plans beside the
     arguments: cr_frac / cr_levels, in_plan, ct_plan, nb_plan, rw_plan / rw_names, ex_thr / ex_levels, pk_thr / pk_levels,
-    mc_batches, mc_b / mc_halves, pt_thr / pt_conn / pt_levels, rp_plan, s_names, levels, a_thr / a_levels, plans [(name, W, in_days, labels)], site_plan,
+    mc_batches, mc_b / mc_halves, pt_thr / pt_conn / pt_levels, rp_plan, s_names, dp_plan / dp_edges, levels, a_thr / a_levels, plans [(name, W, in_days, labels)], site_plan,
     cmp_plan, the loaded chains `prepared` [(rows, runs, model columns, observation columns, source)], `pms` (the
     models) and want_obs.'''
     pm0 = (q.pop_model[0] if q.pop_model else None) if isinstance(q.pop_model, (list, tuple)) else q.pop_model
@@ -5648,6 +6012,16 @@ def _check_request(q):
         if q.site_plan is not None and len(q.site_plan[1]) > MAX_MODE_DAYS:
             raise ValueError('modes: the release plan has %d output days, at most %d fit'
                              % (len(q.site_plan[1]), MAX_MODE_DAYS))
+    q.dp_plan = q.dp_edges = None
+    if q.dependence is not None and q.dependence is not False:           # after every other check
+        if q.evaluate is not None:
+            raise ValueError('dependence= needs the device: not with evaluate=')
+        q.dp_plan = check_dependence(q.dependence)
+        nd = len(q.pms[0].days)
+        if q.dp_plan['days'] is not None and q.dp_plan['days'][-1] >= nd:
+            raise ValueError('dependence: the model has %d days, day %d is not among them' % (nd, q.dp_plan['days'][-1]))
+        # one set of edges for every chain's handle: from the pooled runs of all chains
+        q.dp_edges = pooled_dependence_edges(q.prepared, q.dp_plan['params'], q.dp_plan['bins'])
     return q
 
 
@@ -5686,7 +6060,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                          arrival=None, arrival_levels=(0.05, 0.5, 0.95), emergence=None, exposure=None, sites=None,
                          sensitivity=None, compare=None, mc_error=None, peak=None, excursion=None, reweight=None,
                          catch=None, information=None, core_range=None, patches=None, representative=None,
-                         neighbourhood=None, modes=None):
+                         neighbourhood=None, modes=None, dependence=None):
     '''Posterior predictive spread of one or more chains (`Sampler.save` files or (trace, names) pairs). Burn and
     thin apply per chain; consecutive rows with identical model parameters are one evaluation weighted by the
     run's length.
@@ -5860,7 +6234,22 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         space-time one.  With sites= the plan's outputs (at most 8) get one of their own (`sites.modes`), its planes
         the listed days that are output days.  Rotated or sparse modes, modes of the peak, catch or neighbourhood
         fields and the Monte Carlo error or reweighting of the modes are not computed.  Without modes= no call is
-        added and `modes` is None.'''
+        added and `modes` is None.
+
+    dependence: True (all 15 model parameters, 8 bins), names from mcmc.MODEL_BLOCK, or dict(params=..., bins=8,
+        days=...) with bins in 2..16 (check_dependence; not with evaluate=; bad arguments fail before any
+        evaluation, after every other argument's): on which parameter does a cell depend, linearly or not?  The bin
+        edges of every listed parameter are computed once from the pooled runs of all chains after burn and thin
+        (dependence_edges: bins of as nearly equal weight as the distinct values allow) and shared by every chain's
+        handle.  Each chain then also fills one DependenceMaps over the summary's days (or `days`) with every run's
+        theta and length, right after the sensitivity maps, merged in chain order into `dependence`; every
+        emergence=, exposure= and sites= asked for gets a DependenceMaps.for_projection of its own.  A handle holds
+        ((2 + params x bins + params) x 8 + 1) bytes per cell and day -- 12.7 GB at R = 400, 18 days, 15 parameters
+        and 8 bins -- and a ValueError names the figure where the device has not that much free: `days` and a
+        shorter parameter list cut it.  First-order ratios only: interaction, total-effect and Shapley indices,
+        two-parameter bins, ratios of the peak, catch, neighbourhood or information fields and the Monte Carlo error
+        or reweighting of the ratios are not computed.  Without dependence= no call is added and `dependence` is
+        None.'''
     q = types.SimpleNamespace(**locals())
     t0 = time.perf_counter()
     _check_request(q)                 # bad arguments fail before any evaluation
@@ -5979,7 +6368,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         patches=day.patches, patch_levels=q.pt_levels if q.pt_thr else None,
         representative=day.representative, representative_days=q.rp_plan['days'] if q.rp_plan else None,
         representative_chains=[p[0][:, p[2]] for p in prepared] if q.rp_plan else None,
-        neighbourhood=day.neighbourhood, modes=day.modes)
+        neighbourhood=day.neighbourhood, modes=day.modes, dependence=day.dependence)
     if day.information is not None:   # the stated convention: past cap / 2 the ensemble bounds the map
         warn_information(day.information)
         if 'sites' in merged:

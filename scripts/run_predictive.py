@@ -56,6 +56,7 @@ Without --chain a short chain is sampled first (--samples) and saved next to --o
         [--quantiles 0.05,0.5,0.95] [--bins 1e-8,1e6,16] [--arrival 1,10] [--arrival-levels 0.05,0.5,0.95]
         [--emergence C[:d1,d2,...]] [--exposure d1,d2,...]
         [--sites 'E,N,AMOUNT[,LAG];...'] [--sites-days d1,d2,...] [--sensitivity [name,name,...]]
+        [--dependence [name,name,...]] [--dependence-bins 8]
         [--compare-sites 'E,N,AMOUNT[,LAG];...'] [--peak 1,10] [--peak-levels 0.05,0.5,0.95]
         [--excursion 1,10] [--excursion-levels 0.9,0.95]
         [--core-range 0.5,0.95] [--core-range-levels 0.5,0.9]
@@ -147,6 +148,12 @@ def main():
     ap.add_argument('--sensitivity', nargs='?', const='', default=None,
                     help='posterior sensitivity maps to the listed model parameters, e.g. sig_x,sig_y,mu_r '
                          '(no list: all 15; default: off)')
+    ap.add_argument('--dependence', nargs='?', const='', default=None,
+                    help='posterior dependence maps -- the correlation ratio eta^2 of every cell on each listed model '
+                         'parameter, e.g. sig_x,sig_y (no list: all 15; default: off); a handle holds '
+                         '((2 + params x bins + params) x 8 + 1) B per cell and day')
+    ap.add_argument('--dependence-bins', type=int, default=8, metavar='B',
+                    help='bins per parameter of --dependence, 2..16 (default: 8)')
     ap.add_argument('--mc-error', nargs='?', const=20, default=None, type=int, metavar='B',
                     help='Monte Carlo error maps (MCSE, ESS, split R-hat) from B batches per chain, B even and >= 4 '
                          '(no number: 20; default: off)')
@@ -208,7 +215,8 @@ def main():
     from parasitoids_amd import mcmc
     from parasitoids_amd.pop_model import PopModel
     from parasitoids_amd.predictive import (bin_edges, check_arrival_thresholds, check_contrast_thresholds,
-                                            check_core_range, check_excursion, check_levels, check_peak, check_sens_params, contrast_plan,
+                                            check_core_range, check_dependence, check_excursion, check_levels, check_peak,
+                                            check_sens_params, contrast_plan,
                                             emergence_plan, exposure_plan, mc_error_plan, posterior_predictive,
                                             sites_plan)
     mc_error = None
@@ -218,6 +226,10 @@ def main():
     sens = None
     if args.sensitivity is not None:     # bad --sensitivity names fail before any work
         sens = check_sens_params([n.strip() for n in args.sensitivity.split(',') if n.strip()] or None)
+    depend = None
+    if args.dependence is not None:      # bad --dependence names or bins fail before any work
+        depend = check_dependence(dict(params=[n.strip() for n in args.dependence.split(',') if n.strip()] or None,
+                                       bins=args.dependence_bins))
     levels = check_levels([float(q) for q in args.quantiles.split(',') if q.strip()])
     bins = tuple(float(b) for b in args.bins.split(','))
     bin_edges(bins)                      # a bad --bins fails before any work
@@ -355,6 +367,7 @@ def main():
                                **({'core_range': core_range} if core_range else {}),
                                **({'patches': patches} if patches else {}),
                                **({'modes': modes} if modes else {}),
+                               **({'dependence': depend} if depend else {}),
                                **({'representative': representative} if representative else {}))
     dt = time.perf_counter() - t0
     # accumulate-kernel time: the same members once more with HIP events around every add
@@ -363,6 +376,10 @@ def main():
                                             lagged_models, load_chain, runs)
     ME = MonteCarloError(pm, res.mc_plan['batch_weight'], None, thr) if mc_error else None
     X = SensitivityMaps(pm, sens) if sens else None
+    DM = None
+    if depend:                           # the result's own edges: the same planes are written
+        from parasitoids_amd.predictive import DependenceMaps
+        DM = DependenceMaps(pm, depend['params'], res.dependence.edges)
     RB = XC = SC = None
     union = {}
     if compare:                          # as the driver: one model per release day of either plan, shared by both
@@ -434,6 +451,8 @@ def main():
             RG.profile(True)
         if X is not None:
             X.profile(True)
+        if DM is not None:
+            DM.profile(True)
         if ME is not None:
             ME.profile(True)
         for P in projections:
@@ -480,6 +499,8 @@ def main():
                     ME.add(length)
                 if X is not None:
                     X.add(rows[first, cols], length)
+                if DM is not None:
+                    DM.add(rows[first, cols], length)
                 if H is not None:
                     H.add(length)
                 if A is not None:
@@ -557,6 +578,9 @@ def main():
         x_ms, x_launches = X.profile()
         x_bytes = X.nbytes
         X.close()
+    if DM is not None:
+        dm_ms, dm_launches = DM.profile()
+        DM.close()
     if ME is not None:
         me_ms, me_launches, me_close_ms, me_closes = ME.profile()
         me_members, me_bytes = ME.members, ME.nbytes
@@ -695,6 +719,17 @@ def main():
         out['sensitivity_bytes'] = x_bytes
         out['sensitivity_params'] = len(sens)
         out['outputs'] += ['%s_sens.npz' % args.out]
+    if depend:
+        dm_per = dm_ms / max(dm_launches, 1)
+        out['dependence_add_ms_per_member'] = round(dm_per, 4)
+        out['dependence_launches_timed'] = dm_launches
+        # nominal: every pair of cells updated; pairs that are 0 in the member skip their planes
+        out['dependence_add_nominal_GBps'] = round((8 + 32 + 16 * len(depend['params'])) * ncell * nday
+                                                   / (dm_per * 1e-3) / 1e9, 1) if dm_per > 0 else None
+        out['dependence_bytes'] = res.dependence.nbytes
+        out['dependence_params'] = len(depend['params'])
+        out['dependence_bins'] = res.dependence.nbin
+        out['outputs'] += ['%s_depend.npz' % args.out]
     if mc_error:
         # the add launches of one member (one per piece of its weight) and its share of the close launches
         out['mcerr_add_ms_per_member'] = round(me_ms / max(me_members, 1), 4)
@@ -736,6 +771,8 @@ def main():
         res.arrival.close()
     if res.sensitivity is not None:
         res.sensitivity.close()
+    if res.dependence is not None:
+        res.dependence.close()
     if res.mc_error is not None:
         res.mc_error.close()
     for pr in (res.representative, res.emergence, res.exposure, res.sites, res.contrast, res.peak, res.excursion, res.catch, res.information,
