@@ -1298,6 +1298,77 @@ int ps_patch_fetch_members(ps_patch* a, int k, int slot, uint32_t* npatch, uint3
 int ps_patch_prof(ps_patch* a, int enable, double* add_ms, int64_t* adds, double* map_ms, int64_t* maps);
 void ps_patch_destroy(ps_patch* a);
 
+/* ---- pathway maps: reached by the advancing front or by a jump? ----
+ * (no reference counterpart.)  A day kernel is local diffusion plus wind-borne flights, so a member spreads by
+ * stratified dispersal (Shigesada, Kawasaki & Takeda 1995): a contiguous patch creeps outward from the release,
+ * detached foci are founded downwind, and each grows on its own until the front swallows it.  The arrival maps know
+ * a member's first day at a cell but not what the cell was connected to; the patch maps label one day's patches and
+ * have no memory of earlier days.  The pairing of "newly reached" with "connected to ground reached before" lives
+ * inside one member's sequence of days.  Inputs: the slots s = 0 .. nslot - 1 (1..32) in ascending time, N x N cells
+ * each (N * N < 2^25); thresholds t_0 < ... < t_{K-1} (K in 1..4, finite, > 0); connectivity 4 or 8 (no wrap at the
+ * domain edge); anchor cells (1..32, on the grid); one member with integer weight w >= 1.  Per threshold t, every line
+ * a statement of its own:
+ *   v_s(c) = the value ps_summary_add adds for slot s (ps_record_value);  O_s = {c : v_s(c) >= t}
+ *   the patches of O_s and their labels are those of ps_patch: connected components, label = smallest linear index
+ *   every cell carries a state: 0 unreached, 1 front, 2 jump, 3 secondary; all start at 0
+ *   for s = 0, 1, ... in order, with the states as they stood before slot s, for every patch Q of O_s:
+ *     origin(Q) = Q holds an anchor, or a cell in state 1
+ *     seeded(Q) = Q holds a cell in a non-zero state
+ *     every cell of Q still in state 0 becomes 1 if origin(Q), else 3 if seeded(Q), else 2 -- the founding cells of
+ *       a new focus, and Q counts as one focus founded in slot s
+ *   a state is never changed once set: a focus that merges with the origin patch hands its later cells to the front,
+ *     and ground a vanished focus once held seeds secondary growth, not a new focus
+ *   after the last slot cnt[k][class][c] += w where the state of c equals the class (0: front, 1: jump, 2: secondary)
+ *   rows[member][k][s] = (cells newly classed front, jump, secondary in slot s; foci founded in slot s)
+ * so per threshold front + jump + secondary is the arrival count of ps_arrival summed over the slots.
+ * State (pitch as ps_summary): cnt[k][3][pitch] uint32; rows[member][k][slot][4] uint32, 16 B per member, threshold
+ * and slot, grown by doubling; the weights on the host.  Scratch: parent[k][slot][pitch] and flags[k][slot][pitch]
+ * uint32 -- all K * nslot planes of a member are labelled at once (plane on grid.y) -- and state[k][pitch] uint8.
+ * bytes = 12 K pitch (counts) + 4 K nslot pitch (parent) + 4 K nslot pitch (flags) + K pitch (states) + 16 K nslot
+ * capacity (rows): 201.5 MB at R = 400, 18 days, K = 2.  Every allocation is checked against the free device memory
+ * first: PS_ERR_OOM, with the figure, before it is made.  One add: two memsets, init / link / flatten as ps_patch
+ * over all planes (ps_patch_core.h), then per slot two launches over the K thresholds -- flag (every cell of O_s
+ * whose state is set, and every anchor in O_s, ORs its bits into the flags word at its root, aggregated per wave)
+ * and class (one writer per cell; the three classes and the founded roots by ballots, one integer atomic per block
+ * and word) -- and one launch that adds w into the count planes.  Nothing a launch writes is read in that launch,
+ * but for the link kernel's own atomics.  Integer atomics only and a canonical label: neither the order of adds, nor
+ * that of merges, nor the launch configuration, nor the order in which the device joins cells changes a bit; only
+ * the order of the members in the fetches follows the adds.  Every operation records an event the next one waits
+ * on, whichever stream it runs on (the solver's for add, the handle's own otherwise). */
+typedef struct ps_pathway ps_pathway;
+/* PS_ERR_BAD_ARG for thresholds not finite, not > 0, not strictly increasing, more than 4, a connectivity other than
+ * 4 or 8, slots outside 1..32, anchors outside 1..32 or off the grid, or N * N >= 2^25 */
+int ps_pathway_create(int device, int N, int nslot, int nthr, const double* thr, int connectivity, int nanchor,
+                      const int32_t* anchor_row, const int32_t* anchor_col, ps_pathway** out);
+/* room for `members` members' rows now (a growth synchronises; never shrinks) */
+int ps_pathway_reserve(ps_pathway* a, int64_t members);
+/* One member with weight >= 1 (arguments and refusals as ps_patch_add; the slots in ascending time): two memsets
+ * and 4 + 2 nslot launches on the solver's stream; no host synchronisation unless the rows have to grow.  Every
+ * descriptor is resolved first, so an add with a bad slot enqueues nothing. */
+int ps_pathway_add(ps_pathway* a, ps_solver* s, int nslot, const int32_t* kind, const int32_t* idx,
+                   const double* stat_scale, const double* post_scale, const int32_t* use_delta, double negval,
+                   uint32_t weight);
+/* The same for the current outputs of a release plan, as ps_patch_add_sites: slot e takes Y_e (nslot must equal
+ * nout), on the handle's stream. */
+int ps_pathway_add_sites(ps_pathway* a, ps_sites* p, uint32_t weight);
+/* dst += src: the counts by an integer plane add, src's member rows and weights appended after dst's (a device
+ * copy); same device, N, slots, thresholds, connectivity and anchors; src unchanged */
+int ps_pathway_merge(ps_pathway* dst, ps_pathway* src);
+/* any pointer may be NULL; capacity: the members the rows hold room for; bytes: the device memory held now */
+int ps_pathway_info(ps_pathway* a, double* total_weight, int64_t* members, int64_t* capacity, int64_t* bytes);
+/* zero counts, W and members and drop the timings of ps_pathway_prof; the rows keep their room */
+int ps_pathway_reset(ps_pathway* a);
+/* cnt[k][which], which 0: front, 1: jump, 2: secondary (synchronises).  PS_ERR_STATE before the first add, as
+ * ps_pathway_fetch_members. */
+int ps_pathway_fetch_counts(ps_pathway* a, int k, int which, uint32_t* out /* N*N */);
+/* per member in add order the row of (k, slot) and the weight (any pointer may be NULL) */
+int ps_pathway_fetch_members(ps_pathway* a, int k, int slot, uint32_t* front, uint32_t* jump, uint32_t* secondary,
+                             uint32_t* foci, uint32_t* weights);
+/* measurement: HIP-event timing of the adds; while enabled every add keeps one event pair until ps_pathway_reset or
+ * ps_pathway_destroy */
+int ps_pathway_prof(ps_pathway* a, int enable, double* add_ms, int64_t* adds);
+void ps_pathway_destroy(ps_pathway* a);
+
 /* ---- representative members: pairwise overlap of the members' excursion sets ----
  * (no reference counterpart.)  The mean, the quantiles and the excursion sets are maps no member produces.  Which
  * single member is the most typical one, between which two outlines the middle half of the members lies (the contour

@@ -352,6 +352,18 @@ SIGNATURES = {
     'ps_patch_fetch_members': (C.c_int, [_VP, C.c_int, C.c_int] + [C.POINTER(C.c_uint32)] * 6),
     'ps_patch_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P, _F64P, _I64P]),
     'ps_patch_destroy': (None, [_VP]),
+    'ps_pathway_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _F64P, C.c_int, C.c_int, _I32P, _I32P,
+                                    C.POINTER(_VP)]),
+    'ps_pathway_reserve': (C.c_int, [_VP, C.c_int64]),
+    'ps_pathway_add': (C.c_int, [_VP, _VP, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P, C.c_double, C.c_uint32]),
+    'ps_pathway_add_sites': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_pathway_merge': (C.c_int, [_VP, _VP]),
+    'ps_pathway_info': (C.c_int, [_VP, _F64P, _I64P, _I64P, _I64P]),
+    'ps_pathway_reset': (C.c_int, [_VP]),
+    'ps_pathway_fetch_counts': (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(C.c_uint32)]),
+    'ps_pathway_fetch_members': (C.c_int, [_VP, C.c_int, C.c_int] + [C.POINTER(C.c_uint32)] * 5),
+    'ps_pathway_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P]),
+    'ps_pathway_destroy': (None, [_VP]),
     'ps_overlap_create': (C.c_int, [C.c_int, C.c_int, _VP, C.POINTER(_VP)]),
     'ps_overlap_pairs': (C.c_int, [_VP, C.c_int, C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_uint32)]),
     'ps_overlap_subset': (C.c_int, [_VP, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_uint32),

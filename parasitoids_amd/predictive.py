@@ -57,6 +57,9 @@ posterior of their area -- the level is each member's own, so no map cut at an a
 `PatchMaps` labels, on the device, the connected components of each member's set {v >= t} per threshold and day
 (ps_patch_*, csrc/ps_patch.hip) and keeps the weighted count of the members whose main patch, or another patch, holds
 the cell, and per member the number of patches and their sizes: is the reached area one front or separate foci?
+`PathwayMaps` follows those patches through a member's days in order (ps_pathway_*, csrc/ps_pathway.hip) and keeps
+the weighted count of the members that reached the cell by the front that grew from the release, as a founding cell
+of a detached focus, or by the growth of such a focus, and per member and day the cells so classed and the foci founded.
 `MemberOverlap` forms, on the device, the table of pairwise intersections of the members' reached sets from the masks
 of an `ExcursionMaps`, and the count plane of any selection of members (ps_overlap_*, csrc/ps_overlap.hip);
 `RepresentativeMembers` reads from it, in integers on the host, the inclusion depth of every member, the deepest
@@ -2037,6 +2040,268 @@ def save_patches(outfile, pat, levels=(0.05, 0.5, 0.95)):
             'number': number}
 
 
+MAX_PATHWAY_THRESHOLDS = 4
+MAX_PATHWAY_ANCHORS = 32
+PATHWAY_WHICH = ('front', 'jump', 'secondary')
+
+
+def check_pathway_anchors(anchors, N):
+    '''anchor cells as a list of (row, col) ints: 1..32 cells on the N x N grid; None: the centre cell, where
+    the model releases; ValueError otherwise'''
+    if anchors is None:
+        return [(N // 2, N // 2)]
+    try:
+        cells = [(int(r), int(c)) for r, c in anchors]
+    except (TypeError, ValueError):
+        raise ValueError('pathway anchors must be a list of (row, col) cells, got %r' % (anchors,))
+    if not 1 <= len(cells) <= MAX_PATHWAY_ANCHORS:
+        raise ValueError('%d pathway anchors; 1..%d are kept' % (len(cells), MAX_PATHWAY_ANCHORS))
+    for r, c in cells:
+        if not (0 <= r < N and 0 <= c < N):
+            raise ValueError('pathway anchor (%d, %d) is off the %d x %d grid' % (r, c, N, N))
+    return cells
+
+
+def check_pathways(pathways, days=None):
+    '''the pathways= argument of posterior_predictive -> (thresholds, connectivity, days, levels): a list of
+    thresholds (1..4, finite, > 0, strictly increasing), or dict(thresholds=[...], connectivity=8, days=None,
+    levels=(0.05, 0.5, 0.95)): the connectivity 4 (default) or 8, the model days of the window by the rules of
+    check_arrival_days (None: the `days` given here, the summary's) and the levels, each in (0, 1], of the saved
+    quantiles of the foci and of the areas; ValueError otherwise'''
+    connectivity, levels, own_days = 4, (0.05, 0.5, 0.95), None
+    if isinstance(pathways, dict):
+        unknown = set(pathways) - {'thresholds', 'connectivity', 'days', 'levels'}
+        if unknown:
+            raise ValueError('pathways: unknown keys %r' % (sorted(unknown),))
+        if 'thresholds' not in pathways:
+            raise ValueError('pathways: thresholds are needed')
+        connectivity = pathways.get('connectivity', connectivity)
+        levels = pathways.get('levels', levels)
+        own_days = pathways.get('days')
+        pathways = pathways['thresholds']
+    try:
+        thr = [float(t) for t in pathways]
+    except (TypeError, ValueError):
+        raise ValueError('pathway thresholds must be a list of numbers, got %r' % (pathways,))
+    if not 1 <= len(thr) <= MAX_PATHWAY_THRESHOLDS:
+        raise ValueError('%d pathway thresholds; 1..%d are kept' % (len(thr), MAX_PATHWAY_THRESHOLDS))
+    if not all(np.isfinite(t) and t > 0.0 for t in thr):
+        raise ValueError('every pathway threshold must be finite and > 0: %r' % (thr,))
+    if any(b <= a for a, b in zip(thr, thr[1:])):
+        raise ValueError('pathway thresholds must be strictly increasing: %r' % (thr,))
+    connectivity = check_patch_connectivity(connectivity)
+    levels = check_levels(levels)
+    if own_days is not None:
+        own_days = check_arrival_days(own_days)
+        if days is not None and not set(own_days) <= set(int(d) for d in days):
+            raise ValueError('pathway days %r are not among the days %r' % (own_days, list(days)))
+    elif days is not None:
+        own_days = check_arrival_days(days)
+    return thr, connectivity, own_days, levels
+
+
+def pathway_founded(foci, weights, levels=(0.05, 0.5, 0.95)):
+    '''the posterior of the number of foci founded over the window from the members' totals and integer weights,
+    as PathwayMaps.founded returns it (no device): {'mean', 'p_any' = P(foci >= 1), 'quantiles'}'''
+    levels = check_levels(levels)
+    n = np.asarray(foci).astype(np.int64)
+    w = np.asarray(weights).astype(np.int64)
+    W = int(w.sum())
+    if W == 0:
+        raise ValueError('nothing accumulated')
+    return {'mean': float(int((n * w).sum())) / float(W), 'p_any': float(int(w[n >= 1].sum())) / float(W),
+            'quantiles': [float(weighted_lower_quantile(n, w, p)) for p in levels]}
+
+
+class PathwayMaps(_Accumulator):
+    '''How `pop_model`'s members reached each cell: by the advancing front, by a jump, or by the growth of a focus
+    a jump founded (stratified dispersal).  For thresholds t_0 < ... < t_{K-1} (1..4, finite, > 0), the model days
+    `days` (strictly increasing, at most 32, default all) taken in order, `connectivity` 4 or 8 (no wrap) and the
+    anchor cells `anchors` ([(row, col), ...], 1..32, default the centre cell): the patches of {v >= t_k} on each
+    day are those of PatchMaps; a patch is `origin` if it holds an anchor or a cell classed front before that day,
+    `seeded` if it holds any cell classed before; its cells not classed yet become 'front' if origin, else
+    'secondary' if seeded, else 'jump' -- the founding cells of a new focus.  A class is never changed once set.
+    On the device the weighted count of the members per class and cell, and per member and day the cells newly
+    classed and the foci founded (ps_pathway_*; the statements are those of include/parasitoid_hip.h, restated in
+    tests/pathway_ref.py).  front + jump + secondary is ArrivalMaps.counts summed over the days.  Every number is
+    an integer and the label canonical: the order of adds and merges changes no bit.'''
+    _prefix, _noun, _prof_pairs = 'ps_pathway', 'pathway maps', 1
+    _info_types = (C.c_double, C.c_int64, C.c_int64, C.c_int64)      # weight, members, capacity, bytes
+
+    def __init__(self, pop_model, thresholds, days=None, connectivity=4, anchors=None):
+        self.thresholds, self.connectivity, _d, _lv = check_pathways(dict(thresholds=thresholds,
+                                                                          connectivity=connectivity))
+        self._setup(pop_model, None, check_arrival_days(range(len(pop_model.days)) if days is None else days), anchors)
+
+    @classmethod
+    def for_projection(cls, release_sites, thresholds, connectivity=4):
+        '''Pathway maps of the outputs of a ReleaseSites in ascending output day, the anchors the cells of the
+        plan's sites: `add(weight)` accumulates the outputs of its last `apply()`.  `days` holds the plan's output
+        days.  A Projection is no source: its outputs are not a sequence of days.'''
+        if getattr(release_sites, 'fields_kind', None) != 'sites':
+            raise ValueError('pathway maps take a release plan as their source: the outputs of a projection are '
+                             'not a sequence of days')
+        self = cls.__new__(cls)
+        self.thresholds, self.connectivity, _d, _lv = check_pathways(dict(thresholds=thresholds,
+                                                                          connectivity=connectivity))
+        R = int(release_sites.pm.rad_res)
+        anchors = []
+        for s in release_sites.sites:
+            cell = (R + s['drow'], R + s['dcol'])
+            if cell not in anchors:
+                anchors.append(cell)
+        self._setup(release_sites.pm, release_sites, check_arrival_days(_output_labels(release_sites)), anchors)
+        return self
+
+    def _setup(self, pop_model, projection, days, anchors):
+        self._attach(pop_model)
+        self.anchors = check_pathway_anchors(anchors, self.N)
+        self._set_source(projection, days)
+        self._create(len(self.days), len(self.thresholds), L.p_f64(L.f64(self.thresholds)), self.connectivity,
+                     len(self.anchors), L.p_i32(L.i32([r for r, _c in self.anchors])),
+                     L.p_i32(L.i32([c for _r, c in self.anchors])))
+
+    def reserve(self, n):
+        '''room for n members' rows now, so that no add has to grow them'''
+        self._call('reserve', int(n))
+
+    def add(self, weight=1):
+        '''Accumulate the last evaluation of the model with integer weight >= 1 (enqueued on the solver's stream;
+        no host synchronisation unless the member rows grow).  On a plan: its last apply, on the handle's stream.'''
+        self._add(weight)
+
+    def merge(self, other):
+        '''self += other (same device, domain, days, thresholds, connectivity and anchors); other's members follow
+        self's'''
+        if list(other.days) != self.days:
+            raise ValueError('pathway maps over different days')
+        self._call('merge', other._h)
+
+    @property
+    def capacity(self):
+        '''the members the rows hold room for'''
+        return self._info()[2]
+
+    @property
+    def nbytes(self):
+        '''the device memory the handle holds now: counts, parent scratch, flags, states and rows'''
+        return self._info()[3]
+
+    @staticmethod
+    def _which(which):
+        if which not in PATHWAY_WHICH:
+            raise ValueError('which must be one of %r, got %r' % (PATHWAY_WHICH, which))
+        return PATHWAY_WHICH.index(which)
+
+    def counts(self, k, which):
+        '''[N, N] uint32: the weight of the members that reached the cell at t_k within the window by the front
+        ('front'), as a founding cell of a new focus ('jump') or by the growth of a focus ('secondary')'''
+        out = np.empty((self.N, self.N), dtype=np.uint32)
+        self._call('fetch_counts', self._k(k), self._which(which), out.ctypes.data_as(C.POINTER(C.c_uint32)))
+        return out
+
+    def prob(self, k, which):
+        '''[N, N] float64: counts / W, the posterior probability of the same'''
+        return self.counts(k, which).astype(np.float64) / float(self.total_weight)
+
+    def share(self, k, which):
+        '''[N, N] float64: counts / (front + jump + secondary), among the members that reached the cell the share
+        that did so this way; NaN where nobody reached it'''
+        c = [self.counts(k, w).astype(np.float64) for w in PATHWAY_WHICH]
+        total = c[0] + c[1] + c[2]
+        with np.errstate(invalid='ignore', divide='ignore'):
+            return np.where(total > 0, c[self._which(which)] / total, np.nan)
+
+    def _members(self, k, day):
+        '''(front, jump, secondary, foci, weights), [members] uint32 each, in add order'''
+        out = [np.empty(self.members, dtype=np.uint32) for _ in range(5)]
+        self._call('fetch_members', self._k(k), self._slot_of(day),
+                   *[a.ctypes.data_as(C.POINTER(C.c_uint32)) for a in out])
+        return tuple(out)
+
+    def _window(self, k):
+        '''([members, days, 4] int64: the rows of t_k over the window, weights [members] int64)'''
+        rows = [self._members(k, d) for d in self.days]
+        return (np.array([[r[f] for f in range(4)] for r in rows], dtype=np.int64).transpose(2, 0, 1),
+                rows[0][4].astype(np.int64))
+
+    @property
+    def weights(self):
+        '''[members] int64: the members' weights in add order'''
+        return self._members(0, self.days[0])[4].astype(np.int64)
+
+    def new_cells(self, k, day, which):
+        '''[members] int64 in add order: the cells newly classed `which` at t_k on `day`'''
+        return self._members(k, day)[self._which(which)].astype(np.int64)
+
+    def foci(self, k, day):
+        '''[members] int64 in add order: the foci founded at t_k on `day`'''
+        return self._members(k, day)[3].astype(np.int64)
+
+    def founded(self, k, levels=(0.05, 0.5, 0.95)):
+        '''The posterior of the number of foci founded at t_k over the window: {'mean', 'p_any', 'quantiles'}
+        (pathway_founded): the weighted mean, P(foci >= 1) and the weighted lower quantiles at `levels`.'''
+        rows, w = self._window(k)
+        return pathway_founded(rows[:, :, 3].sum(axis=1), w, levels)
+
+    def area(self, k, which, levels=(0.05, 0.5, 0.95)):
+        '''The posterior of the area taken by one pathway at t_k over the window, in m^2, as RangeMaps.area
+        (range_area)'''
+        rows, w = self._window(k)
+        return range_area(rows[:, :, self._which(which)].sum(axis=1), w, self.cell_area, levels)
+
+    def profile(self, enable=None):
+        '''HIP-event time of the adds: (add ms, adds); enable switches it'''
+        return self._profile(enable)
+
+
+def pathway_block(thresholds, connectivity, days, anchors, levels, rows, weights, cell_area):
+    '''the json block of save_pathways from the members' rows [thresholds, days, 4, members] and weights (no
+    device): thresholds, connectivity, days, anchors, levels, members, weight, cell area and per threshold
+    `founded` (pathway_founded) and per class `area` (range_area)'''
+    levels = check_levels(levels)
+    rows = np.asarray(rows).astype(np.int64)
+    w = np.asarray(weights).astype(np.int64)
+    per = []
+    for k in range(len(thresholds)):
+        rec = {'founded': pathway_founded(rows[k, :, 3].sum(axis=0), w, levels)}
+        for j, which in enumerate(PATHWAY_WHICH):
+            rec['area_' + which] = range_area(rows[k, :, j].sum(axis=0), w, cell_area, levels)
+        per.append(rec)
+    return {'thresholds': [float(t) for t in thresholds], 'connectivity': int(connectivity),
+            'days': [int(d) for d in days], 'anchors': [[int(r), int(c)] for r, c in anchors], 'levels': levels,
+            'members': int(w.size), 'total_weight': float(int(w.sum())), 'cell_area': float(cell_area),
+            'pathways': per}
+
+
+def pathway_arrays(thresholds, connectivity, days, anchors, rows, weights):
+    '''the arrays save_pathways adds to its npz: the members' rows `pathway_front`, `pathway_jump`,
+    `pathway_secondary`, `pathway_foci` (uint32) [thresholds, days, members], `pathway_weights` [members],
+    `pathway_thresholds`, `pathway_connectivity`, `pathway_days` and `pathway_anchors` [anchors, 2]'''
+    rows = np.asarray(rows)
+    extra = {'pathway_' + name: rows[:, :, f].astype(np.uint32)
+             for f, name in enumerate(PATHWAY_WHICH + ('foci',))}
+    extra.update({'pathway_weights': np.asarray(weights, dtype=np.uint32),
+                  'pathway_thresholds': np.asarray(thresholds, dtype=np.float64),
+                  'pathway_connectivity': np.asarray(int(connectivity)), 'pathway_days': np.asarray(list(days)),
+                  'pathway_anchors': np.asarray(anchors, dtype=np.int64).reshape(-1, 2)})
+    return extra
+
+
+def save_pathways(outfile, pw, levels=(0.05, 0.5, 0.95)):
+    '''outfile.npz of one PathwayMaps through save_maps: under the label `window` the CSR triplets
+    `window_pfront{k}_*`, `window_pjump{k}_*` and `window_psecondary{k}_*` of the probability that the cell was
+    reached that way within the window, and the arrays of pathway_arrays -> its block for the json
+    (pathway_block)'''
+    levels = check_levels(levels)
+    nk = len(pw.thresholds)
+    rows = np.array([[pw._members(k, d)[:4] for d in pw.days] for k in range(nk)])      # [K, days, 4, members]
+    weights = pw.weights
+    maps = [('window', [('_p%s%d' % (which, k), pw.prob(k, which)) for k in range(nk) for which in PATHWAY_WHICH])]
+    save_maps(outfile, maps, pathway_arrays(pw.thresholds, pw.connectivity, pw.days, pw.anchors, rows, weights))
+    return pathway_block(pw.thresholds, pw.connectivity, pw.days, pw.anchors, levels, rows, weights, pw.cell_area)
+
+
 def check_weights(weights, nin=None, zero_rows=False):
     '''A projection's weight matrix as a float64 [nout, nin] array, by the rules of ps_project_create: 1..32
     outputs, 1..32 inputs (nin if given), every weight finite and >= 0, and no row of all zeros unless
@@ -2215,10 +2480,10 @@ def exposure_plan(exposure, ndays=None):
 # 'apply' is the source's own.  The three orders differ for no better reason than the history of the maps.
 FEED_ORDER = {
     'days': ('summary', 'core_range', 'reweight', 'catch', 'neighbourhood', 'information', 'excursion', 'mc_error',
-             'sensitivity', 'dependence', 'histogram', 'arrival', 'peak', 'patches', 'modes'),
+             'sensitivity', 'dependence', 'histogram', 'arrival', 'peak', 'patches', 'pathways', 'modes'),
     'projection': ('apply', 'summary', 'reweight', 'mc_error', 'sensitivity', 'dependence', 'histogram', 'catch'),
     'sites': ('apply', 'summary', 'reweight', 'mc_error', 'sensitivity', 'dependence', 'histogram', 'arrival', 'peak',
-              'excursion', 'core_range', 'catch', 'neighbourhood', 'information', 'patches', 'modes'),
+              'excursion', 'core_range', 'catch', 'neighbourhood', 'information', 'patches', 'pathways', 'modes'),
     'compare': ('apply', 'contrast'),
 }
 
@@ -2265,6 +2530,7 @@ FEED = {
     'mc_error': _add_halves,
     'contrast': _add_length,
     'patches': _add_length,
+    'pathways': _add_length,
     'modes': _add_length,
 }
 ACCUMULATORS = tuple(name for name in FEED if name != 'apply')
@@ -2392,6 +2658,8 @@ BUILD = {
     'mc_error': _build_mc_error,
     'contrast': lambda fs, q: PlanContrast(fs._against, fs._source, q.thresholds),
     'patches': lambda fs, q: q.pt_thr and fs._over(PatchMaps, (q.pt_thr, fs._days, q.pt_conn), (q.pt_thr, q.pt_conn)),
+    'pathways': lambda fs, q: q.pw_thr and fs._over(PathwayMaps, (q.pw_thr, q.pw_days or fs._days, q.pw_conn),
+                                                   (q.pw_thr, q.pw_conn)),
     'modes': _build_modes,
 }
 
@@ -2445,7 +2713,7 @@ class _FieldSet():
             setattr(self, name, acc)
             if name == 'summary' and self._kind == 'days':
                 self._days = acc.days
-            if name in ('excursion', 'core_range', 'patches') and acc is not None:
+            if name in ('excursion', 'core_range', 'patches', 'pathways') and acc is not None:
                 acc.reserve(nruns)
             if name == 'modes' and acc is not None:
                 _reserve_modes(acc, nruns)
@@ -2526,6 +2794,8 @@ class ProjectedMaps(_FieldSet):
     `information`: the InformationPosterior over the outputs (None unless asked for), likewise.  `core_range`: the
     RangeMaps.for_projection of a release plan's outputs (None unless asked for), whose maps take the output day.
     `patches`: the PatchMaps.for_projection of a release plan's outputs (None unless asked for), likewise.
+    `pathways`: the PathwayMaps.for_projection of a release plan's outputs (None unless asked for), its anchors the
+    cells of the plan's sites.
     `representative`: the RepresentativeMembers over a release plan's `excursion` (None unless asked for).
     `merge` and `close` take every accumulator there is (ACCUMULATORS).'''
 
@@ -5503,6 +5773,8 @@ class PredictiveResult():
     `core_range_levels` the consensus levels of its saved regions, both None where not asked for (the plan then
     carries a `core_range` of its own); `patches`: the PatchMaps over the summary's days and `patch_levels` the
     levels of its saved quantiles, both None where not asked for (the plan then carries a `patches` of its own);
+    `pathways`: the PathwayMaps over the summary's days (or the days asked for) and `pathway_levels` the levels of
+    its saved quantiles, both None where not asked for (the plan then carries a `pathways` of its own);
     `representative`: the RepresentativeMembers over `excursion`, `representative_days` the planes of its saved
     outputs ('all' or a list of days) and `representative_chains` per chain the model parameters of its rows, all
     None where not asked for (the plan then carries a `representative` of its own); `neighbourhood`: the
@@ -5518,7 +5790,9 @@ class PredictiveResult():
                  peak=None, excursion=None, excursion_levels=None, reweight=None, reweight_info=None, catch=None,
                  information=None, core_range=None, core_range_levels=None, patches=None, patch_levels=None,
                  representative=None, representative_days=None, representative_chains=None, neighbourhood=None,
-                 modes=None, dependence=None):
+                 modes=None, dependence=None, pathways=None, pathway_levels=None):
+        self.pathways = pathways
+        self.pathway_levels = pathway_levels
         self.dependence = dependence
         self.modes = modes
         self.neighbourhood = neighbourhood
@@ -5616,6 +5890,8 @@ class PredictiveResult():
         outfile_sites_range.npz), their block under `predictive.core_range` (`predictive.sites.core_range`).
         Patch maps go into outfile_patch.npz (save_patches; those of a release plan into outfile_sites_patch.npz),
         their block under `predictive.patches` (`predictive.sites.patches`).
+        Pathway maps go into outfile_pathway.npz (save_pathways; those of a release plan into
+        outfile_sites_pathway.npz), their block under `predictive.pathways` (`predictive.sites.pathways`).
         Representative members go into outfile_repr.npz (save_representative; those of a release plan into
         outfile_sites_repr.npz), their block under `predictive.representative` (`predictive.sites.representative`).
         Ensemble modes go into outfile_modes.npz (save_modes; those of a release plan into outfile_sites_modes.npz),
@@ -5720,6 +5996,9 @@ class PredictiveResult():
             if pr.patches is not None:
                 meta['predictive'][name]['patches'] = save_patches('%s_%s_patch' % (outfile, name), pr.patches,
                                                                    self.patch_levels)
+            if pr.pathways is not None:
+                meta['predictive'][name]['pathways'] = save_pathways('%s_%s_pathway' % (outfile, name), pr.pathways,
+                                                                     self.pathway_levels)
         for name, rp in (('', self.representative),
                          ('sites_', None if self.sites is None else self.sites.representative)):
             if rp is not None:
@@ -5731,6 +6010,8 @@ class PredictiveResult():
                 block = save_modes('%s_%smodes' % (outfile, name), mp)
                 block['given'] = mp.given
                 (meta['predictive'][name[:-1]] if name else meta['predictive'])['modes'] = block
+        if self.pathways is not None:
+            meta['predictive']['pathways'] = save_pathways('%s_pathway' % outfile, self.pathways, self.pathway_levels)
         if self.patches is not None:
             meta['predictive']['patches'] = save_patches('%s_patch' % outfile, self.patches, self.patch_levels)
         if self.core_range is not None:
@@ -5871,14 +6152,14 @@ def _check_request(q):
     '''Everything of posterior_predictive's arguments (q: a namespace of them) that can fail before any evaluation,
     in a fixed order -- of two bad arguments the earlier one is reported.  -> q, with the checked plans beside the
     arguments: cr_frac / cr_levels, in_plan, ct_plan, nb_plan, rw_plan / rw_names, ex_thr / ex_levels, pk_thr / pk_levels,
-    mc_batches, mc_b / mc_halves, pt_thr / pt_conn / pt_levels, rp_plan, s_names, dp_plan / dp_edges, levels, a_thr / a_levels, plans [(name, W, in_days, labels)], site_plan,
+    mc_batches, mc_b / mc_halves, pt_thr / pt_conn / pt_levels, pw_thr / pw_conn / pw_days / pw_levels, rp_plan, s_names, dp_plan / dp_edges, levels, a_thr / a_levels, plans [(name, W, in_days, labels)], site_plan,
     cmp_plan, the loaded chains `prepared` [(rows, runs, model columns, observation columns, source)], `pms` (the
     models) and want_obs.'''
     pm0 = (q.pop_model[0] if q.pop_model else None) if isinstance(q.pop_model, (list, tuple)) else q.pop_model
     days, thresholds = q.days, q.thresholds
     q.cr_frac = q.cr_levels = q.in_plan = q.ct_plan = q.rw_plan = q.ex_thr = q.ex_levels = None
     q.pk_thr = q.pk_levels = q.mc_batches = q.pt_thr = q.pt_conn = q.pt_levels = q.rp_plan = q.nb_plan = None
-    q.md_plan = None
+    q.md_plan = q.pw_thr = q.pw_conn = q.pw_days = q.pw_levels = None
 
     def ndays0():                     # the model is touched only where an option needs it
         return None if pm0 is None else len(pm0.days)
@@ -6012,6 +6293,15 @@ def _check_request(q):
         if q.site_plan is not None and len(q.site_plan[1]) > MAX_MODE_DAYS:
             raise ValueError('modes: the release plan has %d output days, at most %d fit'
                              % (len(q.site_plan[1]), MAX_MODE_DAYS))
+    if q.pathways is not None and q.pathways is not False:     # after every other check
+        if q.evaluate is not None:
+            raise ValueError('pathways= needs the device: not with evaluate=')
+        q.pw_thr, q.pw_conn, q.pw_days, q.pw_levels = check_pathways(q.pathways)
+        nd = len(q.pms[0].days)
+        if q.pw_days is not None and q.pw_days[-1] >= nd:
+            raise ValueError('pathways: the model has %d days, day %d is not among them' % (nd, q.pw_days[-1]))
+        if q.pw_days is None:                                  # the summary's days
+            check_arrival_days(range(nd) if days is None else days)
     q.dp_plan = q.dp_edges = None
     if q.dependence is not None and q.dependence is not False:           # after every other check
         if q.evaluate is not None:
@@ -6060,7 +6350,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                          arrival=None, arrival_levels=(0.05, 0.5, 0.95), emergence=None, exposure=None, sites=None,
                          sensitivity=None, compare=None, mc_error=None, peak=None, excursion=None, reweight=None,
                          catch=None, information=None, core_range=None, patches=None, representative=None,
-                         neighbourhood=None, modes=None, dependence=None):
+                         neighbourhood=None, modes=None, dependence=None, pathways=None):
     '''Posterior predictive spread of one or more chains (`Sampler.save` files or (trace, names) pairs). Burn and
     thin apply per chain; consecutive rows with identical model parameters are one evaluation weighted by the
     run's length.
@@ -6249,7 +6539,19 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         shorter parameter list cut it.  First-order ratios only: interaction, total-effect and Shapley indices,
         two-parameter bins, ratios of the peak, catch, neighbourhood or information fields and the Monte Carlo error
         or reweighting of the ratios are not computed.  Without dependence= no call is added and `dependence` is
-        None.'''
+        None.
+
+    pathways: thresholds [t_0, ...] (1..4, finite, > 0, strictly increasing) or dict(thresholds=[...],
+        connectivity=8, days=None, levels=(0.05, 0.5, 0.95)) (check_pathways; not with evaluate=; bad arguments fail
+        before any evaluation, after every other argument's): was a cell reached by the advancing front, by a jump,
+        or by the growth of a focus a jump founded?  Each chain then also fills one PathwayMaps over the summary's
+        days (or `days`; strictly increasing, at most 32) with the centre cell as its anchor, reserved to the
+        chain's number of runs and fed the run's weight right after the patch maps, merged in chain order into
+        `pathways` (`pathway_levels`: the levels of its saved quantiles); with sites= the plan gets a
+        PathwayMaps.for_projection of its own outputs, anchored at its sites (`sites.pathways`).  Emergence and
+        exposure get none: their outputs are not a sequence of days.  Jump distances, zones, a lineage beyond the
+        three classes, per-day class planes and the Monte Carlo error, reweighting, sensitivity or contrast of
+        these maps are not computed.  Without pathways= no call is added and `pathways` is None.'''
     q = types.SimpleNamespace(**locals())
     t0 = time.perf_counter()
     _check_request(q)                 # bad arguments fail before any evaluation
@@ -6368,7 +6670,8 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         patches=day.patches, patch_levels=q.pt_levels if q.pt_thr else None,
         representative=day.representative, representative_days=q.rp_plan['days'] if q.rp_plan else None,
         representative_chains=[p[0][:, p[2]] for p in prepared] if q.rp_plan else None,
-        neighbourhood=day.neighbourhood, modes=day.modes, dependence=day.dependence)
+        neighbourhood=day.neighbourhood, modes=day.modes, dependence=day.dependence, pathways=day.pathways,
+        pathway_levels=q.pw_levels if q.pw_thr else None)
     if day.information is not None:   # the stated convention: past cap / 2 the ensemble bounds the map
         warn_information(day.information)
         if 'sites' in merged:

@@ -28,7 +28,11 @@ in the member's own highest-density region holding that share of its wasps, 0.5 
 and day the probability that a cell lies in the member's main patch (the largest connected component of the cells at
 or above the density) or in a satellite, and the posterior of the patch count (--patch-connectivity 4 or 8,
 --patch-levels: the levels of the saved quantiles) -- saved as PREFIX_patch.npz (and, with --sites,
-PREFIX_sites_patch.npz for the plan); with --representative (and --excursion) also the representative members -- on
+PREFIX_sites_patch.npz for the plan); with --pathways also the pathway maps -- per listed density the probability
+that a cell was reached by the front that grew from the release, as a founding cell of a detached focus (a jump) or by
+the growth of such a focus, and the posterior of the number of foci founded and of the area each pathway took
+(--pathway-connectivity 4 or 8, --pathway-levels: the levels of the saved quantiles) -- saved as PREFIX_pathway.npz
+(and, with --sites, PREFIX_sites_pathway.npz for the plan, anchored at its sites); with --representative (and --excursion) also the representative members -- on
 the members' reached sets at the excursion densities, over all days at once, every member's inclusion depth, the
 deepest member, the central band that holds --representative-central of the weight, and K scenarios by k-medoids on
 the area two members disagree on, each with its share and its conditional probability map; the run behind the
@@ -61,6 +65,7 @@ Without --chain a short chain is sampled first (--samples) and saved next to --o
         [--excursion 1,10] [--excursion-levels 0.9,0.95]
         [--core-range 0.5,0.95] [--core-range-levels 0.5,0.9]
         [--patches 1,10] [--patch-connectivity 8] [--patch-levels 0.05,0.5,0.95]
+        [--pathways 1,10] [--pathway-connectivity 8] [--pathway-levels 0.05,0.5,0.95]
         [--representative [K]] [--representative-epsilon 0.02] [--representative-central 0.5]
         [--reweight 'NAME:east,north,day,kind,rate[,n];...'] [--reweight-file NAME=weights.npy]
         [--catch 'DAY,RATE[,N];...'] [--catch-levels 0.5,0.95] [--catch-emergence 'OBSDAY,RATE[,N];...']
@@ -174,6 +179,10 @@ def main():
     ap.add_argument('--patch-connectivity', type=int, default=4, help='4 or 8 neighbours (with --patches)')
     ap.add_argument('--patch-levels', default='0.05,0.5,0.95',
                     help='levels in (0, 1] of the saved patch-count and area quantiles (with --patches)')
+    ap.add_argument('--pathways', default='', help='pathway maps at the listed densities, e.g. 1,10 (default: off)')
+    ap.add_argument('--pathway-connectivity', type=int, default=4, help='4 or 8 neighbours (with --pathways)')
+    ap.add_argument('--pathway-levels', default='0.05,0.5,0.95',
+                    help='levels in (0, 1] of the saved foci and area quantiles (with --pathways)')
     ap.add_argument('--representative', nargs='?', const=3, type=int, default=None, metavar='K',
                     help='representative members on the excursion sets: inclusion depth, the deepest member, the '
                          'central band and K scenarios (default 3, 1..8); needs --excursion (default: off)')
@@ -266,6 +275,13 @@ def main():
                        connectivity=args.patch_connectivity,
                        levels=[float(q) for q in args.patch_levels.split(',') if q.strip()])
         check_patches(patches)
+    pathways = None
+    if args.pathways:                    # as do bad --pathways thresholds, connectivity or levels
+        from parasitoids_amd.predictive import check_pathways
+        pathways = dict(thresholds=[float(t) for t in args.pathways.split(',') if t.strip()],
+                        connectivity=args.pathway_connectivity,
+                        levels=[float(q) for q in args.pathway_levels.split(',') if q.strip()])
+        check_pathways(pathways)
     emergence = exposure = None
     if args.emergence:
         cday, _, obs = args.emergence.partition(':')
@@ -366,6 +382,7 @@ def main():
                                **({'neighbourhood': neighbourhood} if neighbourhood else {}),
                                **({'core_range': core_range} if core_range else {}),
                                **({'patches': patches} if patches else {}),
+                               **({'pathways': pathways} if pathways else {}),
                                **({'modes': modes} if modes else {}),
                                **({'dependence': depend} if depend else {}),
                                **({'representative': representative} if representative else {}))
@@ -709,6 +726,12 @@ def main():
         out['patch_members'] = res.patches.members
         out['patch_bytes'] = res.patches.nbytes
         out['outputs'] += ['%s_patch.npz' % args.out] + (['%s_sites_patch.npz' % args.out] if sites else [])
+    if pathways:
+        out['pathway_thresholds'] = pathways['thresholds']
+        out['pathway_connectivity'] = pathways['connectivity']
+        out['pathway_members'] = res.pathways.members
+        out['pathway_bytes'] = res.pathways.nbytes
+        out['outputs'] += ['%s_pathway.npz' % args.out] + (['%s_sites_pathway.npz' % args.out] if sites else [])
     if sens:
         x_per = x_ms / max(x_launches, 1)
         out['sensitivity_add_ms_per_member'] = round(x_per, 4)
@@ -776,7 +799,7 @@ def main():
     if res.mc_error is not None:
         res.mc_error.close()
     for pr in (res.representative, res.emergence, res.exposure, res.sites, res.contrast, res.peak, res.excursion, res.catch, res.information,
-               res.core_range, res.patches, res.neighbourhood, res.modes):
+               res.core_range, res.patches, res.pathways, res.neighbourhood, res.modes):
         if pr is not None:
             pr.close()
     for p in pms:
