@@ -1559,6 +1559,67 @@ int ps_modes_fetch_member(ps_modes* a, int64_t member, int slot, double* out /* 
 int ps_modes_prof(ps_modes* a, int enable, double* ms /* 4 */, int64_t* launches /* 4 */);
 void ps_modes_destroy(ps_modes* a);
 
+/* ---- proximity fields: how far from each cell is the nearest ground that holds t wasps ----
+ * (no reference counterpart; the exact Euclidean distance transform of Danielsson 1980 in the two-pass form of
+ * Meijster, Roerdink & Hesselink 2000, whose ensemble statistics the accumulators below then take.)  A handle lives
+ * on one device and holds nout outputs (1..32) over nin inputs (1..32) on a domain of N <= 32767 cells a side, so
+ * that every squared distance fits 32 bits (PS_ERR_BAD_ARG otherwise): output e is (input[e], thr[e], side[e]) with
+ * 0 <= input[e] < nin, thr[e] not a NaN and side[e] 0 or 1; cell_m > 0 and finite.  With v the value of input[e]
+ * and S = {(y, x) : 0 <= y, x < N, v(y, x) >= thr[e]}, an apply overwrites every cell of every output with
+ *   side 0 ("to"):  d2_e(y, x) = min { (y - y')^2 + (x - x')^2 : (y', x') in S }, 0 on S
+ *   side 1 ("in"):  the same with S replaced by its complement within the domain: the depth of a reached cell
+ *                   inside the reached ground, 0 off S
+ *   where the set searched for is empty: d2 = far2 = 2 (N - 1)^2 + 1, one more than the domain can hold
+ *   Z_e(y, x) = fl(fl(sqrt((double) d2)) * cell_m), in metres; the IEEE round-to-nearest square root
+ * Nothing wraps; cells outside the domain do not exist and the domain's edge is not unreached ground.  d2 is an
+ * exact integer, so both planes are the same whatever the strip, the launch shape or the order of the search.
+ * Three launches.  The set as 64-bit words, bit c & 63 of word c >> 6 for cell c = y N + x (pitch / 64 words per
+ * output, the layout of ps_excur): one thread per cell, one ballot per wave.  The row pass: one thread per cell
+ * takes g(y, x), the distance along its own row to the nearest set bit, from the leading and trailing zeros of its
+ * own word and a walk over the row's words outwards; uint16, 0xffff where the row holds none.  The column pass:
+ * d2(y, x) = min over y' of (y - y')^2 + g(y', x)^2; a workgroup owns a strip of W columns of one output and a share
+ * of its rows, stages g of the whole strip in LDS (W N 2 B: 102528 B at N = 801) and every thread searches
+ * dy = 0, 1, 2, .. on both sides until dy^2 >= its best, so the work per cell grows like its distance; d2 and Z are
+ * written in the same pass.  W is the widest power of two <= 64 with W N 2 B <= the LDS one workgroup may hold
+ * (at 160 KiB: 64 up to N = 1280, 32 up to 2560, 16 up to 5120, .., 2 up to 32767); the rows of a strip are shared
+ * among floor(CUs / (strips x nout)) workgroups, 1..64.  One writer per cell, no atomics, no hand-off between
+ * workgroups.  The handle holds nout * pitch * (8 + 4 + 2 + 1/8) B (Z, d2, g, the words), checked against the free
+ * device memory first: PS_ERR_OOM before anything is allocated.  Every operation records an event the next one waits
+ * on, whichever stream it runs on (the solver's for ps_prox_apply, the handle's own for the other applies, fetch and
+ * gather, the accumulator's for the _add_prox entry points). */
+typedef struct ps_prox ps_prox;
+int ps_prox_create(int device, int N, int nin, int nout, const int32_t* input /* nout */,
+                   const double* thr /* nout */, const int32_t* side /* nout */, double cell_m, ps_prox** out);
+/* testing: the strip of the next applies, a power of two <= the default; 0: the default.  PS_ERR_BAD_ARG otherwise.
+ * The outputs are the same. */
+int ps_prox_set_strip(ps_prox* c, int width);
+/* The inputs are records of solver s, with the arguments and refusals of ps_nbhd_apply: on the solver's stream, no
+ * host synchronisation, nothing copied or allocated.  Every descriptor is resolved before anything is enqueued. */
+int ps_prox_apply(ps_prox* c, ps_solver* s, int nin, const int32_t* kind, const int32_t* idx,
+                  const double* stat_scale, const double* post_scale, const int32_t* use_delta, double negval);
+/* The inputs are the current outputs of a projection or a release plan, as ps_nbhd_apply_project. */
+int ps_prox_apply_project(ps_prox* c, ps_project* p);
+int ps_prox_apply_sites(ps_prox* c, ps_sites* p);
+/* one output to the host, in metres or as the squared distance in cells (synchronises).  PS_ERR_STATE before the
+ * first apply. */
+int ps_prox_fetch(ps_prox* c, int e, double* out /* N*N */);
+int ps_prox_fetch_d2(ps_prox* c, int e, uint32_t* out /* N*N */);
+/* the outputs at n listed cells: out[e * n + k] = Z_e(rows[k], cols[k]) (synchronises).  PS_ERR_BAD_ARG for
+ * a cell outside the domain, PS_ERR_STATE before the first apply. */
+int ps_prox_gather(ps_prox* c, int64_t n, const int32_t* rows, const int32_t* cols, double* out /* nout x n */);
+/* any pointer may be NULL; strip: the width W in use */
+int ps_prox_info(ps_prox* c, int* N, int* nin, int* nout, int64_t* applies, int* strip);
+/* measurement: HIP-event timing of the applies, the set and the row pass apart from the column pass; both counts
+ * are the applies timed */
+int ps_prox_prof(ps_prox* c, int enable, double* row_ms, int64_t* row_n, double* col_ms, int64_t* col_n);
+void ps_prox_destroy(ps_prox* c);
+/* One member whose values are the handle's current outputs in metres, as ps_summary_add_nbhd takes a
+ * neighbourhood handle's. */
+int ps_summary_add_prox(ps_summary* a, ps_prox* c, uint32_t weight);
+int ps_hist_add_prox(ps_hist* h, ps_prox* c, uint32_t weight);
+int ps_mcerr_add_prox(ps_mcerr* h, ps_prox* c, uint32_t weight);
+int ps_wsum_add_prox(ps_wsum* h, ps_prox* c, int nscen, const double* rescale, const double* omega);
+
 #ifdef __cplusplus
 }
 #endif

@@ -310,6 +310,21 @@ SIGNATURES = {
     'ps_hist_add_nbhd': (C.c_int, [_VP, _VP, C.c_uint32]),
     'ps_mcerr_add_nbhd': (C.c_int, [_VP, _VP, C.c_uint32]),
     'ps_wsum_add_nbhd': (C.c_int, [_VP, _VP, C.c_int, _F64P, _F64P]),
+    'ps_prox_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _I32P, _F64P, _I32P, C.c_double, C.POINTER(_VP)]),
+    'ps_prox_set_strip': (C.c_int, [_VP, C.c_int]),
+    'ps_prox_apply': (C.c_int, [_VP, _VP, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P, C.c_double]),
+    'ps_prox_apply_project': (C.c_int, [_VP, _VP]),
+    'ps_prox_apply_sites': (C.c_int, [_VP, _VP]),
+    'ps_prox_fetch': (C.c_int, [_VP, C.c_int, _F64P]),
+    'ps_prox_fetch_d2': (C.c_int, [_VP, C.c_int, C.POINTER(C.c_uint32)]),
+    'ps_prox_gather': (C.c_int, [_VP, C.c_int64, _I32P, _I32P, _F64P]),
+    'ps_prox_info': (C.c_int, [_VP, _I32P, _I32P, _I32P, _I64P, _I32P]),
+    'ps_prox_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P, _F64P, _I64P]),
+    'ps_prox_destroy': (None, [_VP]),
+    'ps_summary_add_prox': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_hist_add_prox': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_mcerr_add_prox': (C.c_int, [_VP, _VP, C.c_uint32]),
+    'ps_wsum_add_prox': (C.c_int, [_VP, _VP, C.c_int, _F64P, _F64P]),
     'ps_gain_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _I32P, _F64P, _I32P, C.POINTER(_VP)]),
     'ps_gain_apply': (C.c_int, [_VP, _VP, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P, C.c_double]),
     'ps_gain_apply_project': (C.c_int, [_VP, _VP]),

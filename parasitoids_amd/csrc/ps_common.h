@@ -147,6 +147,7 @@ PsFieldsOps ps_peak_fields();    // the last member's peak field of a ps_peak (p
 PsFieldsOps ps_catch_fields();   // the catch-probability fields of a ps_catch (ps_catch.hip)
 PsFieldsOps ps_gain_fields();    // the class-probability and entropy planes of a ps_gain (ps_gain.hip)
 PsFieldsOps ps_nbhd_fields();    // the neighbourhood maxima of a ps_nbhd (ps_nbhd.hip)
+PsFieldsOps ps_prox_fields();    // the distances in metres of a ps_prox (ps_prox.hip)
 
 // the members' masks and the count planes of a ps_excur as ps_overlap.hip reads them on the device (ps_excur.hip).
 // The mask block moves when it grows, so a reader takes the view at every call; it orders its stream behind the

@@ -380,6 +380,10 @@ extern "C" int ps_hist_add_nbhd(ps_hist* a, ps_nbhd* p, uint32_t weight) {
   return hist_add_fields(a, p, ps_nbhd_fields(), "hist_add_nbhd", weight);
 }
 
+extern "C" int ps_hist_add_prox(ps_hist* a, ps_prox* p, uint32_t weight) {
+  return hist_add_fields(a, p, ps_prox_fields(), "hist_add_prox", weight);
+}
+
 extern "C" int ps_hist_merge(ps_hist* dst, ps_hist* src) {
   if (!dst || !src || dst == src) return ps_fail(PS_ERR_BAD_ARG, "hist_merge: bad arguments");
   if (dst->device != src->device || dst->N != src->N || dst->nslot != src->nslot || dst->edges != src->edges)

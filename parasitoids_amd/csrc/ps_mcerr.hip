@@ -454,6 +454,10 @@ extern "C" int ps_mcerr_add_nbhd(ps_mcerr* h, ps_nbhd* p, uint32_t weight) {
   return mce_add_fields(h, p, ps_nbhd_fields(), "mcerr_add_nbhd", weight);
 }
 
+extern "C" int ps_mcerr_add_prox(ps_mcerr* h, ps_prox* p, uint32_t weight) {
+  return mce_add_fields(h, p, ps_prox_fields(), "mcerr_add_prox", weight);
+}
+
 extern "C" int ps_mcerr_finish(ps_mcerr* h) {
   if (!h) return ps_fail(PS_ERR_BAD_ARG, "mcerr_finish: null handle");
   if (h->open == 0) return PS_OK;

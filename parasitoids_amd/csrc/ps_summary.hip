@@ -288,6 +288,10 @@ extern "C" int ps_summary_add_nbhd(ps_summary* a, ps_nbhd* p, uint32_t weight) {
   return sum_add_fields(a, p, ps_nbhd_fields(), "summary_add_nbhd", weight);
 }
 
+extern "C" int ps_summary_add_prox(ps_summary* a, ps_prox* p, uint32_t weight) {
+  return sum_add_fields(a, p, ps_prox_fields(), "summary_add_prox", weight);
+}
+
 // the mean planes for ps_gain.hip's finish: nothing is computed or changed here
 int ps_summary_mean_internal(ps_summary* a, PsMeanView* out) {
   if (!a || !out) return ps_fail(PS_ERR_BAD_ARG, "summary mean view: null handle");

@@ -399,6 +399,10 @@ extern "C" int ps_wsum_add_nbhd(ps_wsum* a, ps_nbhd* p, int nscen, const double*
   return ws_add_fields(a, p, ps_nbhd_fields(), "wsum_add_nbhd", nscen, rescale, omega);
 }
 
+extern "C" int ps_wsum_add_prox(ps_wsum* a, ps_prox* p, int nscen, const double* rescale, const double* omega) {
+  return ws_add_fields(a, p, ps_prox_fields(), "wsum_add_prox", nscen, rescale, omega);
+}
+
 // one scenario's mean planes for ps_gain.hip's finish: nothing is computed or changed here
 int ps_wsum_mean_internal(ps_wsum* a, int scenario, PsMeanView* out) {
   if (!a || !out) return ps_fail(PS_ERR_BAD_ARG, "wsum mean view: null handle");

@@ -67,6 +67,10 @@ member, the central band and k-medoids scenarios -- which single outcome is typi
 `NeighbourhoodFields` turns, on the device, one member's field into its largest value within a disc of each cell
 (ps_nbhd_*, csrc/ps_nbhd.hip); the existing accumulators take it per member (`NeighbourhoodPosterior`): the
 probability of at least t wasps somewhere within r metres, which no per-cell map gives.
+`ProximityFields` turns, on the device, one member's field into the exact Euclidean distance from each cell to the
+member's own ground with at least t wasps, or the depth inside it (ps_prox_*, csrc/ps_prox.hip); the existing
+accumulators take it per member (`ProximityPosterior`): the mean, spread and quantiles of that distance and the
+probability of such ground within any radius, which no map for one radius gives.
 """
 import ctypes as C
 import json
@@ -2479,11 +2483,12 @@ def exposure_plan(exposure, ndays=None):
 # source: the model's day fields, a Projection, the ReleaseSites of sites= and, after it, plan B of compare=.
 # 'apply' is the source's own.  The three orders differ for no better reason than the history of the maps.
 FEED_ORDER = {
-    'days': ('summary', 'core_range', 'reweight', 'catch', 'neighbourhood', 'information', 'excursion', 'mc_error',
+    'days': ('summary', 'core_range', 'reweight', 'catch', 'neighbourhood', 'proximity', 'information', 'excursion', 'mc_error',
              'sensitivity', 'dependence', 'histogram', 'arrival', 'peak', 'patches', 'pathways', 'modes'),
     'projection': ('apply', 'summary', 'reweight', 'mc_error', 'sensitivity', 'dependence', 'histogram', 'catch'),
     'sites': ('apply', 'summary', 'reweight', 'mc_error', 'sensitivity', 'dependence', 'histogram', 'arrival', 'peak',
-              'excursion', 'core_range', 'catch', 'neighbourhood', 'information', 'patches', 'pathways', 'modes'),
+              'excursion', 'core_range', 'catch', 'neighbourhood', 'proximity', 'information', 'patches', 'pathways',
+              'modes'),
     'compare': ('apply', 'contrast'),
 }
 
@@ -2526,6 +2531,7 @@ FEED = {
     'reweight': _add_reweighted,
     'catch': _add_catch,
     'neighbourhood': _add_catch,
+    'proximity': _add_catch,
     'information': lambda acc, fs, m: acc.add(m.length, m.lam),
     'mc_error': _add_halves,
     'contrast': _add_length,
@@ -2577,6 +2583,16 @@ def _build_neighbourhood(fs, q):
         npost = _owned_by(nf, NeighbourhoodPosterior, q.thresholds, q.levels, q.bins, q.edges, q.mc_b, q.rw_names)
         npost.given = q.nb_plan['given']
         return npost
+
+
+def _build_proximity(fs, q):
+    windows = fs._traps.get('proximity')
+    if windows:
+        plan = q.px_plan
+        pf = fs._over(ProximityFields, windows, windows)
+        ppost = _owned_by(pf, ProximityPosterior, plan['radii_m'], plan['levels'], plan['ladder'], q.mc_b, q.rw_names)
+        ppost.given = plan['given']
+        return ppost
 
 
 def _build_information(fs, q):
@@ -2654,6 +2670,7 @@ BUILD = {
     'reweight': _build_reweight,
     'catch': _build_catch,
     'neighbourhood': _build_neighbourhood,
+    'proximity': _build_proximity,
     'information': _build_information,
     'mc_error': _build_mc_error,
     'contrast': lambda fs, q: PlanContrast(fs._against, fs._source, q.thresholds),
@@ -2683,8 +2700,8 @@ class _FieldSet():
 
     def fed_from(self, kind, source, name=None, owns=True, against=None, **traps):
         '''kind: a key of FEED_ORDER; name: the driver's name of the source (default: the kind); owns: release()
-        closes the source; against: plan A of a 'compare' set; traps: per 'catch' / 'information' / 'neighbourhood' the
-        arguments of its fields after the source, None for none'''
+        closes the source; against: plan A of a 'compare' set; traps: per 'catch' / 'information' / 'neighbourhood' /
+        'proximity' the arguments of its fields after the source, None for none'''
         self._kind, self._name, self._source, self._owns = kind, name or kind, source, owns
         self._against, self._traps = against, traps
         return self
@@ -2763,7 +2780,7 @@ def _merge_chains(sets):
     accumulators are closed.  The sources stay open: a catch reads its source's fields, a contrast both plans'.'''
     first = sets[0]
     _pool_halves(sets)
-    for own in ('catch', 'neighbourhood'):
+    for own in ('catch', 'neighbourhood', 'proximity'):
         if getattr(first, own) is not None:
             _pool_halves([getattr(fs, own) for fs in sets])
             # the accumulators hold what they need; an information's fields hold its maps
@@ -2790,7 +2807,8 @@ class ProjectedMaps(_FieldSet):
     ReweightedSummary.for_projection (None unless asked for), which takes the scenario's name and the output index.
     `catch`: the CatchPosterior over the outputs (None unless asked for), whose traps name an output label.
     `neighbourhood`: the NeighbourhoodPosterior over a release plan's outputs (None unless asked for), whose windows
-    name an output day.
+    name an output day.  `proximity`: the ProximityPosterior over a release plan's outputs (None unless asked for),
+    likewise.
     `information`: the InformationPosterior over the outputs (None unless asked for), likewise.  `core_range`: the
     RangeMaps.for_projection of a release plan's outputs (None unless asked for), whose maps take the output day.
     `patches`: the PatchMaps.for_projection of a release plan's outputs (None unless asked for), likewise.
@@ -2801,12 +2819,13 @@ class ProjectedMaps(_FieldSet):
 
     def __init__(self, weights, in_days, labels, summary, histogram=None, arrival=None, plan=None,
                  sensitivity=None, mc_error=None, peak=None, excursion=None, reweight=None, catch=None,
-                 information=None, core_range=None, patches=None, neighbourhood=None, dependence=None):
+                 information=None, core_range=None, patches=None, neighbourhood=None, dependence=None,
+                 proximity=None):
         super().__init__(summary=summary, histogram=histogram, arrival=arrival, sensitivity=sensitivity,
                          dependence=dependence,
                          mc_error=mc_error, peak=peak, excursion=excursion, reweight=reweight, catch=catch,
                          information=information, core_range=core_range, patches=patches,
-                         neighbourhood=neighbourhood)
+                         neighbourhood=neighbourhood, proximity=proximity)
         self.weights = weights
         self.in_days = in_days
         self.labels = labels
@@ -5109,6 +5128,398 @@ def save_neighbourhood(outfile, post, cell_area=None):
             'total_weight': post.summary.total_weight, 'outputs': outs}
 
 
+# ------------------------------------------------------------------ proximity: how far is the nearest ground with t?
+MAX_PROX_IN = 32           # ps_prox: the input records of one launch's descriptors
+MAX_PROX_OUT = 32
+MAX_PROX_RADII = 3         # the summary keeps four thresholds; the fourth is far_m (the empty share)
+PROX_SIDES = ('to', 'in')
+
+
+def check_prox_windows(windows, what='day'):
+    '''windows [(key, t[, 'to' | 'in']), ...] as [(key, t, side), ...]: 1..32 windows, the key (a model day, or the
+    output label of a projection or plan) a whole number >= 0, t finite and > 0, the side 'to' (the distance to
+    the ground with at least t, the default) or 'in' (the depth inside it); ValueError otherwise'''
+    import math
+    try:
+        rows = [tuple(t) for t in windows]
+    except TypeError:
+        raise ValueError("windows must be a list of (%s, t[, 'to' | 'in']), got %r" % (what, windows))
+    if not 1 <= len(rows) <= MAX_PROX_OUT:
+        raise ValueError('%d windows; 1..%d fit one handle' % (len(rows), MAX_PROX_OUT))
+    out = []
+    for t in rows:
+        if len(t) not in (2, 3):
+            raise ValueError("a window is (%s, t[, 'to' | 'in']), got %r" % (what, t))
+        try:
+            key, thr = float(t[0]), float(t[1])
+        except (TypeError, ValueError):
+            raise ValueError("a window is (%s, t[, 'to' | 'in']) with numbers first, got %r" % (what, t))
+        side = t[2] if len(t) == 3 else 'to'
+        if not (math.isfinite(key) and key == int(key) and key >= 0):
+            raise ValueError('window %r: the %s must be a whole number >= 0' % (t, what))
+        if not (math.isfinite(thr) and thr > 0):
+            raise ValueError('window %r: t must be finite and > 0' % (t,))
+        if side not in PROX_SIDES:
+            raise ValueError("window %r: the side is 'to' or 'in'" % (t,))
+        out.append((int(key), thr, side))
+    return out
+
+
+def parse_prox_windows(text):
+    '''the command line's 'DAY,T[,in];...' as [(day, t[, side]), ...]; the values are checked by check_prox_windows,
+    here only the shape'''
+    out = []
+    for part in str(text).split(';'):
+        if not part.strip():
+            continue
+        f = [x.strip() for x in part.split(',')]
+        if len(f) not in (2, 3):
+            raise ValueError('a window is DAY,T[,in], got %r' % (part,))
+        try:
+            out.append((int(f[0]), float(f[1])) + tuple(f[2:]))
+        except ValueError:
+            raise ValueError('a window is DAY,T[,in] with a whole DAY, got %r' % (part,))
+    return out
+
+
+def check_ascending(values, what, limit=None):
+    '''values as a list of floats, every one finite and > 0, strictly increasing, at most `limit` of them;
+    ValueError otherwise'''
+    import math
+    try:
+        out = [float(v) for v in values]
+    except (TypeError, ValueError):
+        raise ValueError('%s must be a list of numbers, got %r' % (what, values))
+    if limit is not None and len(out) > limit:
+        raise ValueError('%d %s; at most %d' % (len(out), what, limit))
+    if any(not (math.isfinite(v) and v > 0) for v in out):
+        raise ValueError('%s must be finite and > 0: %r' % (what, out))
+    if any(b <= a for a, b in zip(out, out[1:])):
+        raise ValueError('%s must be strictly increasing: %r' % (what, out))
+    return out
+
+
+def prox_far(N, cell_m):
+    '''(far2, far_m) of a domain of N cells a side: far2 = 2 (N - 1)^2 + 1, one more than any squared distance
+    the domain holds, and its field value sqrt(far2) * cell_m as the device rounds it'''
+    far2 = 2 * (int(N) - 1) ** 2 + 1
+    return far2, float(np.sqrt(np.float64(far2)) * np.float64(cell_m))
+
+
+def default_ladder(cell_m, far_m):
+    '''cell_m * 2^(j / 4), j = 0, 1, .. up to the first entry above far_m: a quarter octave per rung, about 45
+    rungs at R = 400'''
+    out, j = [], 0
+    while True:
+        out.append(float(cell_m) * 2.0 ** (j / 4.0))
+        if out[-1] > far_m:
+            return out
+        j += 1
+
+
+def check_proximity(proximity, ndays=None, cell_m=None, evaluate=None):
+    '''posterior_predictive's proximity= argument, [(day, t[, 'to' | 'in']), ...] or dict(windows=[...],
+    radii_m=[...], levels=(...), ladder=[...]) -> dict(windows, radii_m, levels, ladder, given): the checked windows
+    (check_prox_windows) over model days < ndays, at most 32 distinct ones; at most 3 radii_m, finite, > 0 and
+    strictly increasing (the summary's fourth threshold is far_m); quantile levels in (0, 1] or None; a ladder of
+    radii, finite, > 0 and strictly increasing (2..1024), or None for default_ladder; and the argument as given for
+    the json.  evaluate: posterior_predictive's evaluate=, which has no device fields.  cell_m is accepted for the
+    symmetry with check_neighbourhood: no radius is too large.  ValueError otherwise.'''
+    arg, radii, levels, ladder = proximity, (), None, None
+    if isinstance(arg, dict):
+        if 'windows' not in arg or set(arg) - {'windows', 'radii_m', 'levels', 'ladder'}:
+            raise ValueError("proximity must be [(day, t[, 'to' | 'in']), ...] or dict(windows=[...], radii_m=[...], "
+                             'levels=(...), ladder=[...]), got %r' % (arg,))
+        radii, levels, ladder = arg.get('radii_m') or (), arg.get('levels'), arg.get('ladder')
+        arg = arg['windows']
+    if evaluate is not None:
+        raise ValueError('proximity= needs the device: not with evaluate=')
+    windows = check_prox_windows(arg)
+    for t in windows:
+        if ndays is not None and t[0] >= ndays:
+            raise ValueError('window %r: the model has %d days' % (t, ndays))
+    if len({t[0] for t in windows}) > MAX_PROX_IN:
+        raise ValueError('the windows name more than %d days' % MAX_PROX_IN)
+    radii = check_ascending(radii, 'radii_m', MAX_PROX_RADII)
+    levels = (check_levels(levels) if levels is not None else []) or None
+    if ladder is not None:
+        ladder = check_ascending(ladder, 'ladder entries')
+        bin_edges(edges=ladder)
+    return {'windows': windows, 'radii_m': radii, 'levels': levels, 'ladder': ladder,
+            'given': {'windows': [list(t) for t in windows], 'radii_m': radii, 'levels': levels, 'ladder': ladder}}
+
+
+class ProximityFields(_Handle):
+    '''Z_e(y, x) = the distance in metres from (y, x) to the nearest cell of the set S_e = {v >= t_e} of
+    `pop_model`'s last evaluation, on the device (ps_prox_*, csrc/ps_prox.hip): per member how far from each cell
+    the nearest ground lies that holds at least t_e on model day day_e.  windows: [(day, t[, 'to' | 'in']), ...]
+    (check_prox_windows), v the value SpreadSummary adds for that day; 'in' measures to the complement of S_e within
+    the domain instead: the depth of a reached cell inside the reached ground.  days: the model days the handle
+    reads, default the windows' own (at most 32).  `for_projection` reads the outputs of a Projection or a
+    ReleaseSites instead.  The squared distance in cells is an exact integer (`d2`), far2 = 2 (N - 1)^2 + 1 where
+    the set searched for is empty, and Z = sqrt(d2) * cell_m (`field`; `far_m` at far2): both equal
+    tests/prox_ref.py's bit for bit.  Nothing wraps and the domain's edge is not unreached ground.  N <= 32767.  The
+    handle holds len(windows) x pitch x 14.125 B (`nbytes`: the metres, d2, the row distances and the set's words);
+    `set_strip(w)` narrows the column pass's strip for testing, which changes no output.
+    SpreadSummary.for_projection, SpreadHistogram.for_projection, MonteCarloError.for_projection and
+    ReweightedSummary.for_projection accept it.'''
+    fields_kind = 'prox'         # the accumulators' entry points for these fields: ps_*_add_prox
+    _prefix, _noun, _prof_pairs = 'ps_prox', 'proximity fields', 2
+
+    def __init__(self, pop_model, windows, days=None):
+        self.windows = check_prox_windows(windows)
+        used = sorted({t[0] for t in self.windows})
+        self.in_days = used if days is None else check_in_days(days)
+        if len(self.in_days) > MAX_PROX_IN:
+            raise ValueError('%d input days; at most %d fit one handle' % (len(self.in_days), MAX_PROX_IN))
+        missing = [d for d in used if d not in self.in_days]
+        if missing:
+            raise ValueError('window days %r are not among the days %r' % (missing, self.in_days))
+        self._source = None
+        self._setup(pop_model, [self.in_days.index(t[0]) for t in self.windows], len(self.in_days))
+        self._set_days(self.in_days)
+
+    @classmethod
+    def for_projection(cls, source, windows, labels=None):
+        '''The proximity fields of the outputs of `source` (a Projection or a ReleaseSites): a window's first entry
+        is the source's output label (labels: one per output, default a ReleaseSites' output days, else the output
+        indices); `apply()` reads the outputs of the source's last apply.  An output without weight is refused.'''
+        self = cls.__new__(cls)
+        self.windows = check_prox_windows(windows, 'output')
+        if labels is None:
+            labels = getattr(source, 'days', None) if source.fields_kind == 'sites' else None
+        labels = list(range(source.nout)) if labels is None else [int(x) for x in labels]
+        if len(labels) != source.nout:
+            raise ValueError('%d labels for %d outputs' % (len(labels), source.nout))
+        slot = {e: i for i, e in enumerate(source.live)}        # the source's device slot of every output
+        inputs = []
+        for t in self.windows:
+            if t[0] not in labels or labels.index(t[0]) not in slot:
+                raise ValueError('window %r: %d is not an output that carries weight (%r)' % (t, t[0], labels))
+            inputs.append(slot[labels.index(t[0])])
+        self.in_days = None
+        self._source = source
+        self._setup(source.pm, inputs, len(source.live))
+        return self
+
+    def _setup(self, pop_model, inputs, nin):
+        self._attach(pop_model)
+        self.nout = len(self.windows)
+        self.live = list(range(self.nout))
+        self.thresholds = [t[1] for t in self.windows]
+        self.sides = [t[2] for t in self.windows]
+        self.cell_m = float(pop_model.rad_dist) / int(pop_model.rad_res)
+        self.far2, self.far_m = prox_far(self.N, self.cell_m)
+        self.nbytes = self.nout * self.pitch * 14 + self.nout * self.pitch // 8
+        self._create(int(nin), self.nout, L.p_i32(L.i32(inputs)), L.p_f64(L.f64(self.thresholds)),
+                     L.p_i32(L.i32([PROX_SIDES.index(s) for s in self.sides])), self.cell_m)
+
+    def set_strip(self, width=0):
+        '''testing: the columns of one workgroup's strip in the next applies, a power of two up to the default; 0:
+        the default; the outputs are the same'''
+        self._call('set_strip', int(width))
+
+    def apply(self):
+        '''The proximity fields of the last evaluation of the model (enqueued on the solver's stream), or of the
+        source's last apply (on the handle's stream); no host synchronisation; the outputs of the previous apply
+        are overwritten.'''
+        self._read('apply', self._source)
+
+    def _counter(self, k):
+        out = [C.c_int(), C.c_int(), C.c_int(), C.c_int64(), C.c_int()]
+        self._call('info', *[C.byref(v) for v in out])
+        return out[k].value
+
+    @property
+    def applies(self):
+        return self._counter(3)
+
+    @property
+    def strip(self):
+        '''the columns of one workgroup's strip in the column pass'''
+        return self._counter(4)
+
+    def field(self, e):
+        '''[N, N] float64: output e of the last apply, in metres'''
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        self._call('fetch', self._e(e), L.p_f64(out))
+        return out
+
+    def d2(self, e):
+        '''[N, N] uint32: the squared distance of output e in cells, far2 where the set searched for is empty'''
+        out = np.empty((self.N, self.N), dtype=np.uint32)
+        self._call('fetch_d2', self._e(e), out.ctypes.data_as(C.POINTER(C.c_uint32)))
+        return out
+
+    def gather(self, rows, cols):
+        '''[nout, n] float64: every output of the last apply at the cells (rows[k], cols[k]), in metres'''
+        rows, cols = L.i32(np.asarray(rows).ravel()), L.i32(np.asarray(cols).ravel())
+        if rows.size != cols.size:
+            raise ValueError('%d rows and %d columns' % (rows.size, cols.size))
+        out = np.zeros((self.nout, rows.size), dtype=np.float64)
+        self._call('gather', rows.size, L.p_i32(rows), L.p_i32(cols), L.p_f64(out))
+        return out
+
+    def profile(self, enable=None):
+        '''HIP-event time of the applies: (ms of the set and the row pass, applies, ms of the column pass,
+        applies); enable switches it'''
+        return self._profile(enable)
+
+
+def ladder_radius(edges, exceed, level):
+    '''Per cell the smallest edge r with P(d < r) = 1 - exceed(r) >= level, NaN where none reaches it: a step
+    function over the ladder, read off the exact exceedance at the edges as required_rate reads the ladder of
+    rates.  exceed(r) -> the N x N map P(d >= r).'''
+    out = None
+    for r in sorted((float(x) for x in edges), reverse=True):   # descending: the smallest that suffices is written last
+        near = 1.0 - np.asarray(exceed(r), dtype=np.float64)
+        if out is None:
+            out = np.full(near.shape, np.nan)
+        out = np.where(near >= level, r, out)
+    return out
+
+
+class ProximityPosterior():
+    '''The posterior of proximity fields, as posterior_predictive returns it: `fields` (the ProximityFields; closed
+    once the chains have run), `windows` [(key, t, side)], `radii_m` (at most 3) and `summary`, the
+    SpreadSummary.for_projection(fields, radii_m + [far_m]), which takes the window's index; `histogram`: the
+    SpreadHistogram.for_projection on the `ladder` of radii (default_ladder unless given), None without quantile
+    `levels`; `mc_error`: the MonteCarloError.for_projection (while the chains run, one chain's two sequences) and
+    `reweight`: the ReweightedSummary.for_projection, both None unless asked for; `given`: the driver's proximity=
+    argument.  A member whose set is empty enters every cell at `far_m`, one step beyond the domain's diagonal:
+    `mean` and `sd` include those members at far_m, and `empty_share` is their share of the weight.'''
+
+    def __init__(self, fields, radii_m=(), levels=None, ladder=None, mc_batch=None, scenarios=None):
+        self.fields = fields
+        self.windows = list(fields.windows)
+        self.far_m, self.far2, self.cell_m = fields.far_m, fields.far2, fields.cell_m
+        self.radii_m = check_ascending(radii_m, 'radii_m', MAX_PROX_RADII)
+        self.thresholds = self.radii_m + [self.far_m]
+        self.levels = list(levels) if levels else None
+        self.ladder = None
+        self.histogram = self.mc_error = self.reweight = self.given = None
+        self.summary = SpreadSummary.for_projection(fields, self.thresholds)
+        try:
+            if self.levels:
+                self.ladder = (default_ladder(self.cell_m, self.far_m) if ladder is None
+                               else check_ascending(ladder, 'ladder entries'))
+                self.histogram = SpreadHistogram.for_projection(fields, edges=self.ladder)
+            if mc_batch:
+                self.mc_error = [MonteCarloError.for_projection(fields, mc_batch, self.thresholds)
+                                 for _half in range(2)]
+            if scenarios:
+                self.reweight = ReweightedSummary.for_projection(fields, scenarios, self.thresholds)
+        except BaseException:
+            self.fields = None           # the caller's (_owned_by) to close
+            self.close()
+            raise
+
+    def add(self, weight=1, log_weights=None):
+        '''apply the fields to the last evaluation (or the source's last apply) and add them to the summary, the
+        histogram and, with the run's log-weights, to the reweighted summary; the Monte Carlo error sequences are
+        the caller's to feed (the run is split between them)'''
+        self.fields.apply()
+        self.summary.add(weight)
+        if self.histogram is not None:
+            self.histogram.add(weight)
+        if self.reweight is not None:
+            self.reweight.add(log_weights, weight)
+
+    def merge(self, other):
+        if other.windows != self.windows or other.thresholds != self.thresholds or other.ladder != self.ladder:
+            raise ValueError('proximity posteriors over different windows, radii or ladders')
+        self.summary.merge(other.summary)
+        if self.histogram is not None:
+            self.histogram.merge(other.histogram)
+        if self.reweight is not None:
+            self.reweight.merge(other.reweight)
+
+    def _e(self, e):
+        if not 0 <= int(e) < len(self.windows):
+            raise ValueError('window %r of %d' % (e, len(self.windows)))
+        return int(e)
+
+    def _k(self, k):
+        if not 0 <= int(k) < len(self.radii_m):
+            raise ValueError('radius %r of %d' % (k, len(self.radii_m)))
+        return int(k)
+
+    def mean(self, e):
+        '''the posterior mean of the distance of window e in metres, the members without such ground at far_m'''
+        return self.summary.mean(self._e(e))
+
+    def sd(self, e):
+        '''its posterior sd (a variance that rounding left below 0 reads as 0)'''
+        return np.sqrt(np.maximum(self.summary.variance(self._e(e)), 0.0))
+
+    def beyond(self, e, k):
+        '''P(d >= radii_m[k]): the posterior probability that no such ground lies within radii_m[k] of the cell'''
+        return self.summary.exceedance(self._e(e), self._k(k))
+
+    def nearer(self, e, k):
+        '''P(d < radii_m[k]) = 1 - beyond'''
+        return 1.0 - self.beyond(e, k)
+
+    def empty_share(self, e):
+        '''the share of the weight of the members whose set was empty: the summary's exceedance at far_m, the same
+        at every cell'''
+        return float(self.summary.exceedance(self._e(e), len(self.radii_m))[0, 0])
+
+    def quantile(self, e, p):
+        '''the weighted lower quantile at level p of the distance of window e (SpreadHistogram, on the ladder)'''
+        if self.histogram is None:
+            raise ValueError('no quantile levels were asked for: there is no histogram')
+        return self.histogram.quantile(self._e(e), p)
+
+    def radius(self, e, level):
+        '''per cell the smallest ladder radius r with P(d < r) >= level, NaN where none reaches it
+        (ladder_radius over the histogram's exact exceedance at its edges).  The last rung of the default ladder
+        lies beyond far_m: a cell that reads it has no such ground within the domain at that level.'''
+        if self.histogram is None:
+            raise ValueError('no quantile levels were asked for: there is no histogram')
+        if not 0.0 < float(level) <= 1.0:
+            raise ValueError('level %r is not in (0, 1]' % (level,))
+        e = self._e(e)
+        return ladder_radius(self.histogram.edges, lambda r: self.histogram.exceedance(e, r), float(level))
+
+    def close(self):
+        accs = [self.fields, self.summary, self.histogram, self.reweight]
+        accs += list(self.mc_error) if isinstance(self.mc_error, (list, tuple)) else [self.mc_error]
+        for a in accs:
+            if a is not None:
+                a.close()
+
+
+def save_proximity(outfile, post, cell_area=None):
+    '''outfile.npz of one ProximityPosterior through save_maps: per window e under the label `x{e}` the CSR
+    triplets `x{e}_*` of the posterior mean of the distance in metres, `x{e}_sd_*`, `x{e}_pnear{k}_*` (the
+    probability of such ground within radii_m[k]) and, with levels, `x{e}_q{tag}_*`; `days` (the windows' days or
+    output labels), `thresholds`, `sides`, `radii_m`, `ladder`, `far_m` and `empty_share` -> its block for the
+    json: the windows, members, weight and per window the empty share and, with a cell area, per radius the m^2
+    where that probability is >= 0.5'''
+    maps, outs = [], []
+    nk = len(post.radii_m)
+    shares = [post.empty_share(e) for e in range(len(post.windows))]
+    for e, t in enumerate(post.windows):
+        near = [post.nearer(e, k) for k in range(nk)]
+        day_maps = [('', post.mean(e)), ('_sd', post.sd(e))]
+        day_maps += [('_pnear%d' % k, near[k]) for k in range(nk)]
+        day_maps += [('_' + quantile_tag(p), post.quantile(e, p)) for p in (post.levels or ())]
+        maps.append(('x%d' % e, day_maps))
+        outs.append({'window': list(t), 'empty_share': shares[e],
+                     'area': [None if cell_area is None else float((pr >= 0.5).sum() * cell_area) for pr in near]})
+    extra = {'days': np.array([t[0] for t in post.windows], dtype=np.int32),     # in place of save_maps' labels
+             'thresholds': np.array([t[1] for t in post.windows], dtype=np.float64),
+             'sides': np.array([t[2] for t in post.windows]),
+             'radii_m': np.array(post.radii_m, dtype=np.float64),
+             'ladder': np.array(post.ladder or (), dtype=np.float64),
+             'far_m': np.float64(post.far_m), 'empty_share': np.array(shares, dtype=np.float64)}
+    save_maps(outfile, maps, extra)
+    return {'windows': [list(t) for t in post.windows], 'radii_m': list(post.radii_m),
+            'levels': list(post.levels or ()), 'far_m': post.far_m, 'members': post.summary.members,
+            'total_weight': post.summary.total_weight, 'outputs': outs}
+
+
 # ------------------------------------------------------------------ trap information: what a catch would teach
 MAX_GAIN_IN = 32           # ps_gain: the input records of one launch's descriptors
 MAX_GAIN_PLANES = 32       # the planes of all traps of one handle: the slots of one accumulator
@@ -5782,7 +6193,9 @@ class PredictiveResult():
     carries a `neighbourhood` of its own over the windows on its output days); `modes`: the ModesPosterior over the
     listed days of the model's day fields, None where not asked for (the plan then carries a `modes` of its own);
     `dependence`: the DependenceMaps over the summary's days (or the days asked for), None where not asked for (the
-    projections and the plan then carry one of their own).'''
+    projections and the plan then carry one of their own); `proximity`: the ProximityPosterior of the windows over
+    the model's day fields, None where not asked for (the plan then carries a `proximity` of its own over the
+    windows on its output days).'''
 
     def __init__(self, summary, rows, evaluations, failed, seconds, runs, observations, provenance, days,
                  histogram=None, quantiles=None, arrival=None, arrival_levels=None, emergence=None, exposure=None,
@@ -5790,7 +6203,8 @@ class PredictiveResult():
                  peak=None, excursion=None, excursion_levels=None, reweight=None, reweight_info=None, catch=None,
                  information=None, core_range=None, core_range_levels=None, patches=None, patch_levels=None,
                  representative=None, representative_days=None, representative_chains=None, neighbourhood=None,
-                 modes=None, dependence=None, pathways=None, pathway_levels=None):
+                 modes=None, dependence=None, pathways=None, pathway_levels=None, proximity=None):
+        self.proximity = proximity
         self.pathways = pathways
         self.pathway_levels = pathway_levels
         self.dependence = dependence
@@ -6073,6 +6487,16 @@ class PredictiveResult():
                 save_reweight('%s_%snbhd_reweight' % (outfile, name), nb.reweight, list(range(len(nb.windows))),
                               ['n%d' % e for e in range(len(nb.windows))])
             (meta['predictive'][name[:-1]] if name else meta['predictive'])['neighbourhood'] = block
+        for name, px in (('', self.proximity),
+                         ('sites_', None if self.sites is None else self.sites.proximity)):
+            if px is None:
+                continue
+            block = save_proximity('%s_%sprox' % (outfile, name), px, area)
+            block['given'] = px.given
+            if px.reweight is not None:
+                save_reweight('%s_%sprox_reweight' % (outfile, name), px.reweight, list(range(len(px.windows))),
+                              ['x%d' % e for e in range(len(px.windows))])
+            (meta['predictive'][name[:-1]] if name else meta['predictive'])['proximity'] = block
         for name, ip in (('', self.information),
                          ('sites_', None if self.sites is None else self.sites.information)):
             if ip is None:
@@ -6100,6 +6524,11 @@ class PredictiveResult():
                 if nb is not None and nb.mc_error is not None:
                     block[name] = mc_error_block(nb.mc_error, list(range(len(nb.windows))),
                                                  ['n%d' % e for e in range(len(nb.windows))], name + '_', mmaps)
+            for name, px in (('proximity', self.proximity),
+                             ('sites_proximity', None if self.sites is None else self.sites.proximity)):
+                if px is not None and px.mc_error is not None:
+                    block[name] = mc_error_block(px.mc_error, list(range(len(px.windows))),
+                                                 ['x%d' % e for e in range(len(px.windows))], name + '_', mmaps)
             save_maps('%s_mcerr' % outfile, mmaps)
             meta['predictive']['mc_error'] = block
         with open(str(outfile) + '.json', 'w') as fobj:
@@ -6151,7 +6580,7 @@ def _evaluate_runs(pm, rows, run_list, model_cols, evaluate, want_obs, locinfo, 
 def _check_request(q):
     '''Everything of posterior_predictive's arguments (q: a namespace of them) that can fail before any evaluation,
     in a fixed order -- of two bad arguments the earlier one is reported.  -> q, with the checked plans beside the
-    arguments: cr_frac / cr_levels, in_plan, ct_plan, nb_plan, rw_plan / rw_names, ex_thr / ex_levels, pk_thr / pk_levels,
+    arguments: cr_frac / cr_levels, in_plan, ct_plan, nb_plan, px_plan, rw_plan / rw_names, ex_thr / ex_levels, pk_thr / pk_levels,
     mc_batches, mc_b / mc_halves, pt_thr / pt_conn / pt_levels, pw_thr / pw_conn / pw_days / pw_levels, rp_plan, s_names, dp_plan / dp_edges, levels, a_thr / a_levels, plans [(name, W, in_days, labels)], site_plan,
     cmp_plan, the loaded chains `prepared` [(rows, runs, model columns, observation columns, source)], `pms` (the
     models) and want_obs.'''
@@ -6159,7 +6588,7 @@ def _check_request(q):
     days, thresholds = q.days, q.thresholds
     q.cr_frac = q.cr_levels = q.in_plan = q.ct_plan = q.rw_plan = q.ex_thr = q.ex_levels = None
     q.pk_thr = q.pk_levels = q.mc_batches = q.pt_thr = q.pt_conn = q.pt_levels = q.rp_plan = q.nb_plan = None
-    q.md_plan = q.pw_thr = q.pw_conn = q.pw_days = q.pw_levels = None
+    q.md_plan = q.pw_thr = q.pw_conn = q.pw_days = q.pw_levels = q.px_plan = None
 
     def ndays0():                     # the model is touched only where an option needs it
         return None if pm0 is None else len(pm0.days)
@@ -6198,18 +6627,23 @@ def _check_request(q):
     def check_neighbourhood_arg():
         cell_m = None if pm0 is None else float(pm0.rad_dist) / int(pm0.rad_res)
         q.nb_plan = check_neighbourhood(q.neighbourhood, ndays0(), cell_m, q.evaluate)
+
+    def check_proximity_arg():
+        cell_m = None if pm0 is None else float(pm0.rad_dist) / int(pm0.rad_res)
+        q.px_plan = check_proximity(q.proximity, ndays0(), cell_m, q.evaluate)
     # the options that need the device, in the order in which they are checked: (name, False switches it off too,
-    # its check).  check_information, check_catch and check_neighbourhood refuse evaluate= themselves, after the
-    # argument's shape.
+    # its check).  check_information, check_catch, check_neighbourhood and check_proximity refuse evaluate= themselves,
+    # after the argument's shape.
     for name, or_false, check in (('core_range', True, check_core_range_arg),
                                   ('information', False, check_information_arg), ('catch', False, check_catch_arg),
                                   ('reweight', False, check_reweight_arg), ('excursion', True, check_excursion_arg),
                                   ('peak', True, check_peak_arg), ('mc_error', True, check_mc_error_arg),
-                                  ('neighbourhood', False, check_neighbourhood_arg)):
-        arg = getattr(q, name)
+                                  ('neighbourhood', False, check_neighbourhood_arg),
+                                  ('proximity', False, check_proximity_arg)):
+        arg = getattr(q, name, None)  # a request put together by hand may not know the later options
         if arg is None or (or_false and arg is False):
             continue
-        if q.evaluate is not None and name not in ('information', 'catch', 'neighbourhood'):
+        if q.evaluate is not None and name not in ('information', 'catch', 'neighbourhood', 'proximity'):
             raise ValueError('%s= needs the device: not with evaluate=' % name)
         check()
     if q.representative is not None and q.representative is not False:
@@ -6322,9 +6756,9 @@ def _build_sets(sets, q, pm, chain, nruns, late):
     def begin(fs, kind, source, name=None, **kw):
         sets.append(fs.fed_from(kind, source, name, **kw))
         return fs
-    ct, info, nb = q.ct_plan, q.in_plan, q.nb_plan
+    ct, info, nb, px = q.ct_plan, q.in_plan, q.nb_plan, q.px_plan
     day_traps = dict(catch=ct and (ct['traps'],), information=info and (info['traps'],),
-                     neighbourhood=nb and (nb['windows'],))
+                     neighbourhood=nb and (nb['windows'],), proximity=px and (px['windows'],))
     begin(_FieldSet(), 'days', pm, owns=False, **day_traps).build(q, chain, nruns)
     for name, W, in_days, labels in q.plans:
         traps = (ct['emergence'], labels) if name == 'emergence' and ct is not None and ct['emergence'] else None
@@ -6334,8 +6768,10 @@ def _build_sets(sets, q, pm, chain, nruns, late):
         rs = ReleaseSites(pm, q.sites['sites'], q.site_plan[1], late)
         # the plan's own neighbourhood maps: over the windows whose day is one of its output days
         on_plan = [t for t in nb['windows'] if t[0] in rs.days] if nb else []
+        px_plan = [t for t in px['windows'] if t[0] in rs.days] if px else []     # the proximity maps likewise
         fs = begin(ProjectedMaps(None, None, None, None), 'sites', rs,
-                   **dict(day_traps, neighbourhood=(on_plan,) if on_plan else None))
+                   **dict(day_traps, neighbourhood=(on_plan,) if on_plan else None,
+                          proximity=(px_plan,) if px_plan else None))
         fs.labels, fs.plan = list(rs.days), rs.describe()
         fs.build(q, chain, nruns)
         if q.cmp_plan is not None:
@@ -6350,7 +6786,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                          arrival=None, arrival_levels=(0.05, 0.5, 0.95), emergence=None, exposure=None, sites=None,
                          sensitivity=None, compare=None, mc_error=None, peak=None, excursion=None, reweight=None,
                          catch=None, information=None, core_range=None, patches=None, representative=None,
-                         neighbourhood=None, modes=None, dependence=None, pathways=None):
+                         neighbourhood=None, modes=None, dependence=None, pathways=None, proximity=None):
     '''Posterior predictive spread of one or more chains (`Sampler.save` files or (trace, names) pairs). Burn and
     thin apply per chain; consecutive rows with identical model parameters are one evaluation weighted by the
     run's length.
@@ -6551,7 +6987,23 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         PathwayMaps.for_projection of its own outputs, anchored at its sites (`sites.pathways`).  Emergence and
         exposure get none: their outputs are not a sequence of days.  Jump distances, zones, a lineage beyond the
         three classes, per-day class planes and the Monte Carlo error, reweighting, sensitivity or contrast of
-        these maps are not computed.  Without pathways= no call is added and `pathways` is None.'''
+        these maps are not computed.  Without pathways= no call is added and `pathways` is None.
+
+    proximity: [(day, t[, 'to' | 'in']), ...] or dict(windows=[...], radii_m=[...], levels=(...), ladder=[...])
+        (check_proximity; not with evaluate=; bad arguments fail before any evaluation): how far from each cell is
+        the nearest ground that holds at least t on model day `day`, and how sure is that?  Per window and member
+        the exact Euclidean distance in metres from every cell to the member's own set {v >= t} ('in': to its
+        complement, the depth inside the reached ground), far_m = sqrt(2 (N - 1)^2 + 1) cell_m where that set is
+        empty.  Each chain then also applies one ProximityFields over the windows right after the neighbourhood's
+        add and adds its fields, with the run's length, to a SpreadSummary.for_projection over radii_m (at most 3)
+        and far_m; with levels to a SpreadHistogram.for_projection on the ladder of radii (default cell_m 2^(j/4)
+        up to the first above far_m), with mc_error= to two MonteCarloError.for_projection of its own, with
+        reweight= to a ReweightedSummary.for_projection fed the same log-weights; merged in chain order into
+        `proximity` (a ProximityPosterior: `mean`, `sd`, `nearer(e, k)`, `beyond`, `empty_share`, `quantile`,
+        `radius(e, level)`).  With sites= the plan gets one of its own over the windows whose day is an output day
+        of the plan, in `sites.proximity`; emergence and exposure get none.  A radial profile from the release
+        point, mean displacement or dispersal-distance curves, distances between named places, zone totals and a
+        search are not computed.  Without proximity= no call is added and `proximity` is None.'''
     q = types.SimpleNamespace(**locals())
     t0 = time.perf_counter()
     _check_request(q)                 # bad arguments fail before any evaluation
@@ -6671,7 +7123,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         representative=day.representative, representative_days=q.rp_plan['days'] if q.rp_plan else None,
         representative_chains=[p[0][:, p[2]] for p in prepared] if q.rp_plan else None,
         neighbourhood=day.neighbourhood, modes=day.modes, dependence=day.dependence, pathways=day.pathways,
-        pathway_levels=q.pw_levels if q.pw_thr else None)
+        pathway_levels=q.pw_levels if q.pw_thr else None, proximity=day.proximity)
     if day.information is not None:   # the stated convention: past cap / 2 the ensemble bounds the map
         warn_information(day.information)
         if 'sites' in merged:

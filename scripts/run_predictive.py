@@ -48,7 +48,11 @@ RATE on model day DAY catches at least N wasps; --catch-emergence: traps over th
 saved as PREFIX_catch.npz (and PREFIX_emergence_catch.npz, PREFIX_sites_catch.npz); with --neighbourhood also the
 neighbourhood maps -- per window 'DAY,RADIUS_M' and cell the posterior mean, sd and, per threshold, the probability
 that at least that many wasps stand somewhere within RADIUS_M of the cell on model day DAY -- saved as
-PREFIX_nbhd.npz (and PREFIX_sites_nbhd.npz over the windows on the plan's output days); with --information also the
+PREFIX_nbhd.npz (and PREFIX_sites_nbhd.npz over the windows on the plan's output days); with --proximity also the
+proximity maps -- per window 'DAY,T[,in]' and cell the posterior mean and sd of the distance in metres to the nearest
+ground that holds at least T wasps on model day DAY ('in': the depth inside it), per --proximity-radii the
+probability of such ground within that radius and per --proximity-levels the quantiles -- saved as PREFIX_prox.npz
+(and PREFIX_sites_prox.npz over the windows on the plan's output days); with --information also the
 information maps -- per described trap 'DAY,RATE[,YMAX]' and cell the mutual information in nats between the trap's
 count (observed as 0, 1, .., YMAX and more) and the identity of the member: where a reading would change what we
 believe -- saved as PREFIX_information.npz (and PREFIX_sites_information.npz).  Kalbar wind and
@@ -70,6 +74,7 @@ Without --chain a short chain is sampled first (--samples) and saved next to --o
         [--reweight 'NAME:east,north,day,kind,rate[,n];...'] [--reweight-file NAME=weights.npy]
         [--catch 'DAY,RATE[,N];...'] [--catch-levels 0.5,0.95] [--catch-emergence 'OBSDAY,RATE[,N];...']
         [--information 'DAY,RATE[,YMAX];...'] [--neighbourhood 'DAY,RADIUS_M;...']
+        [--proximity 'DAY,T[,in];...'] [--proximity-radii 100,400,1600] [--proximity-levels 0.05,0.5,0.95]
         [--modes [K]] [--modes-days d1,d2|all] [--modes-transform sqrt|raw]
 """
 import argparse
@@ -206,6 +211,13 @@ def main():
                     help='the transform of the fields before the modes are taken (with --modes)')
     ap.add_argument('--neighbourhood', default='', help="windows 'DAY,RADIUS_M;...': per cell the probability of at "
                     'least each of --thresholds somewhere within RADIUS_M of it on model day DAY (default: off)')
+    ap.add_argument('--proximity', default='', help="windows 'DAY,T[,in];...': per cell the distance in metres to the "
+                    "nearest ground that holds at least T wasps on model day DAY, 'in': the depth inside it "
+                    '(default: off)')
+    ap.add_argument('--proximity-radii', default='', help='up to 3 radii in metres, increasing: per cell the '
+                    'probability of such ground within each (with --proximity)')
+    ap.add_argument('--proximity-levels', default='', help='quantile levels of the distance, e.g. 0.05,0.5,0.95 '
+                    '(with --proximity)')
     ap.add_argument('--information', default='', help="described traps 'DAY,RATE[,YMAX];...': per cell the mutual "
                     'information in nats between the count of a trap of effort RATE on model day DAY, observed as '
                     '0, 1, .., YMAX (default 0) and more, and the identity of the member (default: off)')
@@ -320,6 +332,13 @@ def main():
         from parasitoids_amd.predictive import check_neighbourhood, parse_windows
         neighbourhood = parse_windows(args.neighbourhood)
         check_neighbourhood(neighbourhood, None, 10000.0 / args.rad_res)
+    proximity = None
+    if args.proximity:                   # as do bad --proximity windows, radii or levels
+        from parasitoids_amd.predictive import check_proximity, parse_prox_windows
+        proximity = dict(windows=parse_prox_windows(args.proximity),
+                         radii_m=[float(x) for x in args.proximity_radii.split(',') if x.strip()],
+                         levels=[float(x) for x in args.proximity_levels.split(',') if x.strip()] or None)
+        check_proximity(proximity, None, 10000.0 / args.rad_res)
     wd, days = PM.get_wind_data(os.path.join(ROOT, 'parasitoids_amd', 'data', 'kalbar'), 30, '00:00')
     modes = None
     if args.modes is not None:           # as do bad --modes settings
@@ -380,6 +399,7 @@ def main():
                                **({'catch': catch} if catch else {}),
                                **({'information': information} if information else {}),
                                **({'neighbourhood': neighbourhood} if neighbourhood else {}),
+                               **({'proximity': proximity} if proximity else {}),
                                **({'core_range': core_range} if core_range else {}),
                                **({'patches': patches} if patches else {}),
                                **({'pathways': pathways} if pathways else {}),
@@ -445,6 +465,10 @@ def main():
         Wn[np.arange(NF.nout), [NF.in_days.index(t[0]) for t in NF.windows]] = 1.0
         NP = Projection(pm, Wn, NF.in_days)
         NW = [NeighbourhoodFields(pm, [t]) for t in NF.windows]
+    PF = None
+    if proximity:                        # the set and the row pass apart from the column pass
+        from parasitoids_amd.predictive import ProximityFields
+        PF = ProximityFields(pm, proximity['windows'])
     IF = IC = None
     if information:                      # and a CatchFields of as many planes over the same days: the same bytes
         from parasitoids_amd.predictive import CatchFields, InformationFields
@@ -510,6 +534,10 @@ def main():
                     if n == 0:
                         for h in [NF, NP] + NW:
                             h.profile(True)
+                if PF is not None:       # the first member warms the kernels up untimed
+                    PF.apply()
+                    if n == 0:
+                        PF.profile(True)
                 if RW is not None:
                     RW.add(RWF.log_weights(pm, first, length), length)
                 if ME is not None:
@@ -587,6 +615,10 @@ def main():
         nf_bytes, nf_cells = NF.nbytes, list(NF.cells)
         for h in [NF, NP] + NW:
             h.close()
+    if PF is not None:
+        pf_row_ms, pf_launches, pf_col_ms, _ = PF.profile()
+        pf_bytes, pf_strip = PF.nbytes, PF.strip
+        PF.close()
     if RW is not None:
         rw_ms, rw_launches = RW.profile()
         rw_bytes = RW.nbytes
@@ -651,6 +683,15 @@ def main():
         out['nbhd_bytes'] = nf_bytes
         out['outputs'] += ['%s_nbhd.npz' % args.out] \
             + (['%s_sites_nbhd.npz' % args.out] if res.sites is not None and res.sites.neighbourhood is not None else [])
+    if proximity:
+        out['prox_row_ms_per_member'] = round(pf_row_ms / max(pf_launches, 1), 4)
+        out['prox_col_ms_per_member'] = round(pf_col_ms / max(pf_launches, 1), 4)
+        out['prox_launches_timed'] = pf_launches
+        out['prox_windows'] = [list(t) for t in proximity['windows']]
+        out['prox_strip'] = pf_strip
+        out['prox_bytes'] = pf_bytes
+        out['outputs'] += ['%s_prox.npz' % args.out] \
+            + (['%s_sites_prox.npz' % args.out] if res.sites is not None and res.sites.proximity is not None else [])
     if information:
         out['information_ms_per_member'] = round(if_ms / max(if_launches, 1), 4)
         out['information_launches_timed'] = if_launches
@@ -799,7 +840,7 @@ def main():
     if res.mc_error is not None:
         res.mc_error.close()
     for pr in (res.representative, res.emergence, res.exposure, res.sites, res.contrast, res.peak, res.excursion, res.catch, res.information,
-               res.core_range, res.patches, res.pathways, res.neighbourhood, res.modes):
+               res.core_range, res.patches, res.pathways, res.neighbourhood, res.modes, res.proximity):
         if pr is not None:
             pr.close()
     for p in pms:
