@@ -1620,6 +1620,83 @@ int ps_hist_add_prox(ps_hist* h, ps_prox* c, uint32_t weight);
 int ps_mcerr_add_prox(ps_mcerr* h, ps_prox* c, uint32_t weight);
 int ps_wsum_add_prox(ps_wsum* h, ps_prox* c, int nscen, const double* rescale, const double* omega);
 
+/* ---- origin maps: from where, when and in what number did the wasps in these traps start ----
+ * (no reference counterpart; Bayesian source-term estimation by exhaustive evaluation over every candidate cell,
+ * the parameter uncertainty integrated out over the members.)  Inference about an unknown of the past: it
+ * recommends nothing and chooses no plan.  Statement by statement, with N = 2 R + 1 odd:
+ *   findings   o = 0 .. O - 1, 1 <= O <= 64: cell (row_o, col_o) inside the domain, day slot slot_o in 0 .. nslot - 1
+ *              (the distinct calendar days of the findings, 1 <= nslot <= 32), kind_o 0 'count' / 1 'none' / 2 'found',
+ *              rate_o finite and > 0, n_o a whole number >= 0 ('count' only)
+ *   hypotheses h = 0 .. H - 1, 1 <= H <= 8: amount_h finite and > 0 in multiples of the release number, and the
+ *              group hgroup_h in 0 .. ngroup - 1 of its release day (1 <= ngroup <= 4, every group with at least one
+ *              hypothesis); a group is one lag, as in ps_sites, and the handle never sees the lag itself: the
+ *              caller's slots of group g name model day d - lag_g of that lag's solver, or PS_REC_NONE where d < lag_g
+ *   field      for the candidate origin s = (r, c): v = V_slot(row_o + R - r, col_o + R - c), V the value
+ *              ps_summary_add adds for the slot's record (ps_record_value: same arguments, same bits); v = 0 where
+ *              the source row or the source column leaves [0, N) -- nothing wraps -- and v = 0 under PS_REC_NONE
+ *   mu         = ra * v with ra = rate_o * amount_h, one fp64 product formed on the host at create
+ *   term       'none', and 'count' with n = 0: -mu.  Otherwise -inf at mu = 0, and at mu > 0
+ *              'count': n log(mu) - mu - lgamma(n + 1), the lgamma a host constant per finding;
+ *              'found': log(-expm1(-mu)) up to mu = log 2, log1p(-exp(-mu)) above it
+ *   l_h(s)     the sum of the terms from +0.0 in the kernel's order, fixed at create: the findings that can give
+ *              -inf ('found', 'count' with n > 0) first, each class in the order given.  -inf once a term is -inf.
+ *              Compared with a reference within a bound, not bit for bit: log, exp, expm1 and log1p
+ *              are the device library's.  The set {l = -inf} is exact.
+ *   prior      an optional plane log pi of N * N fp64, finite or -inf (NaN, +inf: PS_ERR_BAD_ARG), NULL: zeros.
+ *              A cell at -inf gathers nothing, its l is -inf and it never becomes finite.
+ *   (A, S)     per hypothesis and cell, fp64, (-inf, 0) after create and reset.  A member of weight w with l = x:
+ *              x = -inf: nothing;  A = -inf: A = x, S = w;  x <= A: S = S + w exp(x - A);
+ *              otherwise S = S exp(A - x) + w, A = x.  merge applies the same rule with (x, w) = the other
+ *              handle's (A, S).  E_h(s) = A + log S - log W is the caller's, W the total weight.
+ *   rows       per member and hypothesis (mx, sum): mx = max over s of l + log pi, sum = sum over s of
+ *              exp(l + log pi - mx); (-inf, 0) where no cell is finite.  Two stages: every block of 256 cells
+ *              leaves (max, sum) of its own cells, its four waves added in wave order after a butterfly within
+ *              the wave; one wave per hypothesis then takes the maximum of the partials, lane k adds
+ *              sum_b exp(max_b - mx) over its ceil(nblk / 64) consecutive partials in index order, and lane 0 adds
+ *              the 64 lane sums in lane order.  No floating-point atomics: the same calls give the same bits.
+ * One writer per cell, no atomics.  The accumulator is floating point, unlike the integer maps: another order of
+ * adds or merges moves E within the bound of DESIGN 7y, and changes no -inf.  Memory: 3 H pitch 8 B (A, S, the last
+ * member's l), the prior plane where given, H ceil(N N / 256) 16 B of partials, the tables, and the member rows
+ * (H 16 B each, grown by doubling from 64), checked against the free device memory before anything is allocated:
+ * PS_ERR_OOM.  Every operation records an event the next one waits on, whichever stream it runs on; add does
+ * not synchronise the host unless the rows grow. */
+typedef struct ps_origin ps_origin;
+int ps_origin_create(int device, int N, int nfind, const int32_t* row /* nfind */, const int32_t* col /* nfind */,
+                     const int32_t* slot /* nfind */, const int32_t* kind /* nfind */, const double* rate /* nfind */,
+                     const double* n /* nfind */, int nslot, int nhyp, const double* amount /* nhyp */,
+                     const int32_t* hgroup /* nhyp */, int ngroup, const double* log_prior /* N*N or NULL */,
+                     ps_origin** out);
+/* room for `members` member rows now, so that no add has to grow them */
+int ps_origin_reserve(ps_origin* p, int64_t members);
+/* One group of one member from the records of solver s, on the solver's stream: the arguments of ps_sites_apply,
+ * one slot per distinct day, PS_REC_NONE included (a group whose every slot is PS_REC_NONE: PS_ERR_BAD_ARG), and
+ * the member's integer weight >= 1, the same for every group of the member.  Groups come 0 .. ngroup - 1 in
+ * order, any other order is PS_ERR_STATE -- group 0 may not come early, since the groups already in have changed
+ * (A, S).  The launch computes l of the group's hypotheses, updates their (A, S) and leaves their rows; the member
+ * counts once its last group is in.  Every descriptor is resolved before anything is enqueued. */
+int ps_origin_add(ps_origin* p, ps_solver* s, int group, int nslot, const int32_t* kind, const int32_t* idx,
+                  const double* stat_scale, const double* post_scale, const int32_t* use_delta, double negval,
+                  uint32_t weight);
+/* dst takes src's (A, S) by the rule above and appends src's rows and weights; src is unchanged.  Device, N,
+ * findings, hypotheses, slots and the presence of a prior must agree (PS_ERR_BAD_ARG); PS_ERR_STATE while either
+ * handle has a member under way. */
+int ps_origin_merge(ps_origin* dst, ps_origin* src);
+/* (A, S) back to (-inf, 0), W, the members and a member under way dropped */
+int ps_origin_reset(ps_origin* p);
+/* one plane of hypothesis h to the host (synchronises): what 0 A, 1 S, 2 the last member's l.  PS_ERR_STATE before
+ * the first member and while a member is under way. */
+int ps_origin_fetch(ps_origin* p, int what, int h, double* out /* N*N */);
+/* the members' rows [members][nhyp][2] and weights in add order (either may be NULL; synchronises); PS_ERR_BAD_ARG
+ * for members_expected != the handle's members */
+int ps_origin_members(ps_origin* p, int64_t members_expected, double* rows, uint32_t* weights);
+/* any pointer may be NULL; bytes: the device memory the handle holds now */
+int ps_origin_info(ps_origin* p, double* total_weight, int64_t* members, int64_t* capacity, int64_t* bytes);
+/* measurement: HIP-event timing per kernel class: the likelihood-and-accumulate launches, the row reductions, the
+ * merges */
+int ps_origin_prof(ps_origin* p, int enable, double* add_ms, int64_t* adds, double* rows_ms, int64_t* rows_n,
+                   double* merge_ms, int64_t* merges);
+void ps_origin_destroy(ps_origin* p);
+
 #ifdef __cplusplus
 }
 #endif

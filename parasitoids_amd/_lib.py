@@ -321,6 +321,17 @@ SIGNATURES = {
     'ps_prox_info': (C.c_int, [_VP, _I32P, _I32P, _I32P, _I64P, _I32P]),
     'ps_prox_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P, _F64P, _I64P]),
     'ps_prox_destroy': (None, [_VP]),
+    'ps_origin_create': (C.c_int, [C.c_int, C.c_int, C.c_int, _I32P, _I32P, _I32P, _I32P, _F64P, _F64P, C.c_int, C.c_int,
+                                   _F64P, _I32P, C.c_int, _F64P, C.POINTER(_VP)]),
+    'ps_origin_reserve': (C.c_int, [_VP, C.c_int64]),
+    'ps_origin_add': (C.c_int, [_VP, _VP, C.c_int, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P, C.c_double, C.c_uint32]),
+    'ps_origin_merge': (C.c_int, [_VP, _VP]),
+    'ps_origin_reset': (C.c_int, [_VP]),
+    'ps_origin_fetch': (C.c_int, [_VP, C.c_int, C.c_int, _F64P]),
+    'ps_origin_members': (C.c_int, [_VP, C.c_int64, _F64P, C.POINTER(C.c_uint32)]),
+    'ps_origin_info': (C.c_int, [_VP, _F64P, _I64P, _I64P, _I64P]),
+    'ps_origin_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P, _F64P, _I64P, _F64P, _I64P]),
+    'ps_origin_destroy': (None, [_VP]),
     'ps_summary_add_prox': (C.c_int, [_VP, _VP, C.c_uint32]),
     'ps_hist_add_prox': (C.c_int, [_VP, _VP, C.c_uint32]),
     'ps_mcerr_add_prox': (C.c_int, [_VP, _VP, C.c_uint32]),

@@ -71,6 +71,10 @@ probability of at least t wasps somewhere within r metres, which no per-cell map
 member's own ground with at least t wasps, or the depth inside it (ps_prox_*, csrc/ps_prox.hip); the existing
 accumulators take it per member (`ProximityPosterior`): the mean, spread and quantiles of that distance and the
 probability of such ground within any radius, which no map for one radius gives.
+`OriginMaps` runs the other way (ps_origin_*, csrc/ps_origin.hip): given findings -- probes as `check_probes` takes
+them -- the likelihood of every candidate origin cell at once, per member on the device, for a ladder of founding
+numbers and release days; the posterior of the origin with the parameter uncertainty integrated out, and the
+members' own evidence as row log-weights for `reweight=`.  Inference about the past: it recommends nothing.
 """
 import ctypes as C
 import json
@@ -2483,7 +2487,7 @@ def exposure_plan(exposure, ndays=None):
 # source: the model's day fields, a Projection, the ReleaseSites of sites= and, after it, plan B of compare=.
 # 'apply' is the source's own.  The three orders differ for no better reason than the history of the maps.
 FEED_ORDER = {
-    'days': ('summary', 'core_range', 'reweight', 'catch', 'neighbourhood', 'proximity', 'information', 'excursion', 'mc_error',
+    'days': ('summary', 'origin', 'core_range', 'reweight', 'catch', 'neighbourhood', 'proximity', 'information', 'excursion', 'mc_error',
              'sensitivity', 'dependence', 'histogram', 'arrival', 'peak', 'patches', 'pathways', 'modes'),
     'projection': ('apply', 'summary', 'reweight', 'mc_error', 'sensitivity', 'dependence', 'histogram', 'catch'),
     'sites': ('apply', 'summary', 'reweight', 'mc_error', 'sensitivity', 'dependence', 'histogram', 'arrival', 'peak',
@@ -2538,6 +2542,7 @@ FEED = {
     'patches': _add_length,
     'pathways': _add_length,
     'modes': _add_length,
+    'origin': _add_length,
 }
 ACCUMULATORS = tuple(name for name in FEED if name != 'apply')
 
@@ -2641,6 +2646,12 @@ def _build_dependence(fs, q):
     return dm
 
 
+def _build_origin(fs, q):
+    '''the OriginMaps of the model's day fields; the models of its later release days are the driver's (fs._late)'''
+    if getattr(q, 'or_plan', None) is not None and fs._kind == 'days':
+        return OriginMaps(fs._source, q.origin, fs._late)
+
+
 def _reserve_modes(mp, nruns):
     '''room for a chain's runs before its first evaluation; where the device has not that much free, a ValueError
     that names the figure'''
@@ -2678,6 +2689,7 @@ BUILD = {
     'pathways': lambda fs, q: q.pw_thr and fs._over(PathwayMaps, (q.pw_thr, q.pw_days or fs._days, q.pw_conn),
                                                    (q.pw_thr, q.pw_conn)),
     'modes': _build_modes,
+    'origin': _build_origin,
 }
 
 
@@ -2694,7 +2706,7 @@ class _FieldSet():
         self.plan = None
         self.representative = None     # the RepresentativeMembers over `excursion`, built once the chains are merged
         self._kind = self._name = self._source = self._against = self._days = self._half = self._rw_feed = None
-        self._chain = None
+        self._chain = self._late = None
         self._owns = False
         self._traps = {}
 
@@ -2730,7 +2742,7 @@ class _FieldSet():
             setattr(self, name, acc)
             if name == 'summary' and self._kind == 'days':
                 self._days = acc.days
-            if name in ('excursion', 'core_range', 'patches', 'pathways') and acc is not None:
+            if name in ('excursion', 'core_range', 'patches', 'pathways', 'origin') and acc is not None:
                 acc.reserve(nruns)
             if name == 'modes' and acc is not None:
                 _reserve_modes(acc, nruns)
@@ -5834,6 +5846,475 @@ def warn_information(info, what='information'):
     return tops
 
 
+# ------------------------------------------------------------------ origin maps: where did these wasps come from?
+MAX_ORIGIN_FINDINGS = 64   # ps_origin: the findings, their distinct days, the hypotheses and their distinct lags
+MAX_ORIGIN_DAYS = 32
+MAX_ORIGIN_HYPOTHESES = 8
+MAX_ORIGIN_LAGS = 4
+ORIGIN_KIND_CODE = {'count': 0, 'none': 1, 'found': 2}
+
+
+def parse_origin(text):
+    '''"east,north,day,kind,rate[,n];..." -> [(east_m, north_m, day, kind, rate[, n]), ...]; ValueError if malformed'''
+    out = []
+    for item in str(text).split(';'):
+        parts = [s.strip() for s in item.split(',')]
+        if not item.strip():
+            continue
+        if len(parts) not in (5, 6):
+            raise ValueError('finding %r is not east,north,day,kind,rate[,n]' % item)
+        try:
+            row = (float(parts[0]), float(parts[1]), int(parts[2]), parts[3], float(parts[4]))
+            if len(parts) == 6:
+                row = row + (int(parts[5]),)
+        except ValueError:
+            raise ValueError('finding %r is not east,north,day,kind,rate[,n]' % item)
+        out.append(row)
+    if not out:
+        raise ValueError('no finding in %r' % (text,))
+    return out
+
+
+def origin_request(findings, amounts='', lags='', levels='', prior='', rad_dist=None, rad_res=None):
+    '''the origin= argument from the command line's strings: findings 'east,north,day,kind,rate[,n];...', amounts
+    '0.1,1,10', lags '0,2', levels '0.5,0.95', prior the path of an .npy plane; empty strings leave the defaults.
+    Checked (check_origin) before it is returned; ValueError otherwise.'''
+    def numbers(text, kind, what):
+        try:
+            return [kind(x) for x in str(text).split(',') if x.strip()]
+        except ValueError:
+            raise ValueError('%s %r is not a list of numbers' % (what, text))
+    arg = {'findings': parse_origin(findings)}
+    if amounts:
+        arg['amounts'] = numbers(amounts, float, 'amounts')
+    if lags:
+        arg['lags'] = numbers(lags, int, 'lags')
+    if levels:
+        arg['levels'] = numbers(levels, float, 'levels')
+    if prior:
+        arg['prior'] = np.load(prior)
+    check_origin(arg, rad_dist, rad_res)
+    return arg
+
+
+def check_origin(arg, rad_dist, rad_res, ndays=None):
+    '''The origin= argument as a plan.  arg: a list of findings, probes in the format of check_probes,
+    (east_m, north_m, day, kind, rate[, n]), or dict(findings=[...], amounts=[0.1, 1, 10], lags=[0, 2],
+    hypotheses=None, prior=None, levels=(0.5, 0.95)).  A hypothesis is (amount, lag): amount finite and > 0 in
+    multiples of the model's release number, lag a whole number of days >= 0 after the model's first day; amounts x
+    lags in that order is the default product, an explicit `hypotheses` list overrides it, [(1.0, 0)] where neither
+    is given.  1..64 findings on at most 32 distinct days, 1..8 distinct hypotheses with at most 4 distinct lags,
+    every lag below ndays and no later than the last finding (a release after every finding explains none).
+    prior: an N x N float64 log-prior plane, finite or -inf (a cell that cannot be the origin), not all -inf.
+    levels in (0, 1].  -> dict(findings, given, days, slots, hypotheses, lags, groups, prior, levels).
+    ValueError with the offender named.  rad_res=None skips the cells and the prior's shape.'''
+    keys = {'findings', 'amounts', 'lags', 'hypotheses', 'prior', 'levels'}
+    if isinstance(arg, dict):
+        if 'findings' not in arg or set(arg) - keys:
+            raise ValueError('origin must be a list of findings or dict(findings=[...], amounts=, lags=, hypotheses=, '
+                             'prior=, levels=), got keys %r' % (sorted(arg),))
+        spec = dict(arg)
+    else:
+        spec = {'findings': arg}
+    try:
+        findings = check_probes(spec['findings'], rad_dist, rad_res, ndays)
+    except ValueError as e:
+        raise ValueError('origin: %s' % str(e).replace('probe', 'finding'))
+    if len(findings) > MAX_ORIGIN_FINDINGS:
+        raise ValueError('origin: %d findings; 1..%d fit one handle' % (len(findings), MAX_ORIGIN_FINDINGS))
+    days = sorted({f['day'] for f in findings})
+    if len(days) > MAX_ORIGIN_DAYS:
+        raise ValueError('origin: findings on %d different days; at most %d fit one handle' % (len(days), MAX_ORIGIN_DAYS))
+    hyp = spec.get('hypotheses')
+    if hyp is None:
+        amounts = [1.0] if spec.get('amounts') is None else list(spec['amounts'])
+        lags = [0] if spec.get('lags') is None else list(spec['lags'])
+        hyp = [(a, g) for a in amounts for g in lags]
+    elif spec.get('amounts') is not None or spec.get('lags') is not None:
+        raise ValueError('origin: give hypotheses, or amounts and lags, not both')
+    try:
+        hyp = [tuple(h) for h in hyp]
+    except TypeError:
+        raise ValueError('origin: hypotheses must be a list of (amount, lag_days), got %r' % (hyp,))
+    if not 1 <= len(hyp) <= MAX_ORIGIN_HYPOTHESES:
+        raise ValueError('origin: %d hypotheses; 1..%d fit one handle' % (len(hyp), MAX_ORIGIN_HYPOTHESES))
+    out = []
+    for k, h in enumerate(hyp):
+        try:
+            if len(h) != 2:
+                raise ValueError
+            amount = float(h[0])
+            if int(h[1]) != h[1]:
+                raise ValueError
+            lag = int(h[1])
+        except (TypeError, ValueError):
+            raise ValueError('origin: hypothesis %d: (amount, whole lag days) expected, got %r' % (k, h))
+        if not (np.isfinite(amount) and amount > 0):
+            raise ValueError('origin: hypothesis %d: amount %r is not finite and > 0' % (k, h[0]))
+        if lag < 0:
+            raise ValueError('origin: hypothesis %d: lag %d is negative' % (k, lag))
+        if ndays is not None and lag >= ndays:
+            raise ValueError('origin: hypothesis %d: a release %d days after the first lies beyond the model\'s %d days'
+                             % (k, lag, ndays))
+        if lag > days[-1]:
+            raise ValueError('origin: hypothesis %d: a release on day %d comes after the last finding (day %d) and '
+                             'explains none' % (k, lag, days[-1]))
+        if (amount, lag) in out:
+            raise ValueError('origin: hypothesis %d repeats (%g, %d)' % (k, amount, lag))
+        out.append((amount, lag))
+    lags = sorted({g for _a, g in out})
+    if len(lags) > MAX_ORIGIN_LAGS:
+        raise ValueError('origin: %d different lags; at most %d fit one handle' % (len(lags), MAX_ORIGIN_LAGS))
+    prior = spec.get('prior')
+    if prior is not None:
+        try:
+            prior = np.ascontiguousarray(prior, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError('origin: the prior must be an N x N array of log-prior values')
+        if rad_res is not None and prior.shape != (2 * int(rad_res) + 1,) * 2:
+            raise ValueError('origin: the prior has shape %r, the domain is %d x %d'
+                             % (prior.shape, 2 * int(rad_res) + 1, 2 * int(rad_res) + 1))
+        if np.isnan(prior).any() or (prior == np.inf).any():
+            raise ValueError('origin: the prior holds NaN or +inf (finite or -inf expected)')
+        if not np.isfinite(prior).any():
+            raise ValueError('origin: the prior excludes every cell')
+    try:
+        levels = check_levels(spec.get('levels', (0.5, 0.95)))
+    except (TypeError, ValueError) as e:
+        raise ValueError('origin: %s' % e)
+    if not levels:
+        raise ValueError('origin: at least one level expected')
+    return {'findings': findings, 'given': [list(p) for p in spec['findings']], 'days': days,
+            'slots': [days.index(f['day']) for f in findings], 'hypotheses': out, 'lags': lags,
+            'groups': [lags.index(g) for _a, g in out], 'prior': prior, 'levels': levels}
+
+
+def origin_log_evidence(A, S, W):
+    '''E = A + log S - log W per cell from the fetched planes; -inf where A is (no member makes the cell possible)'''
+    A, S = np.asarray(A, dtype=np.float64), np.asarray(S, dtype=np.float64)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        E = A + np.log(S) - np.log(float(W))
+    return np.where(A == -np.inf, -np.inf, E)
+
+
+def origin_posterior(E, log_prior=None):
+    '''[H, N, N] posterior mass of (hypothesis, origin cell) from E [H, N, N]: proportional to pi(s) exp E_h(s) with
+    equal hypothesis priors, normalised over every cell and hypothesis; summed in a fixed order.  ValueError where
+    no cell of any hypothesis is possible.'''
+    E = np.asarray(E, dtype=np.float64)
+    x = E if log_prior is None else E + np.asarray(log_prior, dtype=np.float64)[None]
+    x = np.where(np.isnan(x), -np.inf, x)               # -inf evidence under a -inf prior
+    mx = x.max()
+    if mx == -np.inf:
+        raise ValueError('no candidate cell explains the findings under any hypothesis')
+    p = np.exp(x - mx)
+    return p / p.sum()
+
+
+def origin_region(mass, level):
+    '''int8 [N, N]: the smallest set of cells holding `level` of the mass of `mass` [N, N] -- cells in descending
+    mass, ties by the smaller linear index, until the running sum reaches level x the total'''
+    level, = check_levels([level])
+    m = np.asarray(mass, dtype=np.float64)
+    flat = m.ravel()
+    order = np.lexsort((np.arange(flat.size), -flat))
+    cs = np.cumsum(flat[order])
+    k = int(np.searchsorted(cs, level * cs[-1], side='left')) + 1
+    out = np.zeros(flat.size, dtype=np.int8)
+    out[order[:min(k, flat.size)]] = 1
+    return out.reshape(m.shape)
+
+
+def origin_hypothesis_masses(P, hypotheses):
+    '''the posterior mass per (amount, lag) and its marginals per amount and per lag, from P [H, N, N]'''
+    mass = [float(P[h].sum()) for h in range(len(hypotheses))]
+    amounts = sorted({a for a, _g in hypotheses})
+    lags = sorted({g for _a, g in hypotheses})
+    return {'hypotheses': [{'amount': a, 'lag': g, 'mass': m} for (a, g), m in zip(hypotheses, mass)],
+            'amounts': [{'amount': a, 'mass': sum(m for (b, _g), m in zip(hypotheses, mass) if b == a)} for a in amounts],
+            'lags': [{'lag': g, 'mass': sum(m for (_a, k), m in zip(hypotheses, mass) if k == g)} for g in lags]}
+
+
+def origin_log_prior_mass(log_prior, ncell):
+    '''log of the prior's total mass: log(ncell) for the default of zeros, else the logsumexp of the plane'''
+    if log_prior is None:
+        return float(np.log(float(ncell)))
+    lp = np.asarray(log_prior, dtype=np.float64)
+    return float(lp.max() + np.log(np.exp(lp - lp.max()).sum()))
+
+
+def origin_member_log_evidence(rows, log_prior_mass=0.0):
+    '''[members] float64: log of the member's marginal likelihood of the findings with the origin and the
+    hypothesis integrated out, from its rows [members, H, 2]: logsumexp over h of (mx + log sum) - log H - the log of
+    the prior's total mass (origin_log_prior_mass); -inf where no cell of any hypothesis is possible'''
+    rows = np.asarray(rows, dtype=np.float64)
+    rows = rows.reshape(-1, rows.shape[-2], 2)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        lm = np.where(rows[..., 0] == -np.inf, -np.inf, rows[..., 0] + np.log(rows[..., 1]))
+        mx = lm.max(axis=1) if lm.shape[0] else np.zeros(0)
+        out = mx + np.log(np.exp(lm - mx[:, None]).sum(axis=1)) - np.log(lm.shape[1]) - log_prior_mass
+    return np.where(mx == -np.inf, -np.inf, out)
+
+
+class OriginMaps(_Accumulator):
+    '''Where, when and in what number did the wasps in these traps start?  For findings in the format of the
+    reweighting probes and up to 8 hypotheses (amount, lag) the likelihood of every candidate origin cell at once,
+    member by member on the device (ps_origin_*, csrc/ps_origin.hip; the statements are those of
+    include/parasitoid_hip.h, restated in tests/origin_ref.py): one wind station and a homogeneous landscape make the
+    field of a release elsewhere the centre release translated, the chain is linear in the released number, and a
+    later release day is a model of its own (`lagged`, as ReleaseSites).  Per hypothesis and cell the handle keeps the
+    streaming log-sum-exp pair (A, S) of the members' log-likelihoods, per member and hypothesis the evidence with the
+    origin integrated out.  The accumulator is floating point, unlike the integer maps: another order of adds or
+    merges moves the evidence within the bound of DESIGN 7y; the same calls give the same bits.  Everything below
+    `log_evidence` is numpy on fetched planes; `pairs` lists the (amount, lag) of every hypothesis in the order of the
+    planes.  It is inference about the past: it recommends nothing.  There is no
+    `for_projection`: an unknown origin of a release plan or of a projection over days is not defined.'''
+    _prefix, _noun, _prof_pairs = 'ps_origin', 'origin maps', 3
+    _info_types = (C.c_double, C.c_int64, C.c_int64, C.c_int64)      # weight, members, capacity, bytes
+    _owned = ()
+
+    def __init__(self, pop_model, origin, lagged=None):
+        self.plan = check_origin(origin, pop_model.rad_dist, pop_model.rad_res, len(pop_model.days))
+        self.findings, self.pairs = self.plan['findings'], self.plan['hypotheses']
+        self.days, self.lags, self.levels = self.plan['days'], self.plan['lags'], self.plan['levels']
+        self.log_prior = self.plan['prior']
+        self.lagged = check_lagged(pop_model, self.lags, lagged)
+        self.slots = site_slots(self.lags, self.days)
+        self._attach(pop_model)
+        f = self.findings
+        prior = None if self.log_prior is None else L.p_f64(self.log_prior)
+        self._create(len(f), L.p_i32(L.i32([p['row'] for p in f])), L.p_i32(L.i32([p['col'] for p in f])),
+                     L.p_i32(L.i32(self.plan['slots'])), L.p_i32(L.i32([ORIGIN_KIND_CODE[p['kind']] for p in f])),
+                     L.p_f64(L.f64([p['rate'] for p in f])), L.p_f64(L.f64([p['n'] or 0 for p in f])), len(self.days),
+                     len(self.pairs), L.p_f64(L.f64([a for a, _g in self.pairs])),
+                     L.p_i32(L.i32(self.plan['groups'])), len(self.lags), prior)
+
+    @classmethod
+    def with_lagged_models(cls, pop_model, origin, wind_data=None):
+        '''the maps with the models of the later release days built here (lagged_models); `close()` closes them'''
+        plan = check_origin(origin, pop_model.rad_dist, pop_model.rad_res, len(pop_model.days))
+        made = lagged_models(pop_model, plan['lags'], wind_data)
+        try:
+            self = cls(pop_model, origin, made)
+        except Exception:
+            for m in made.values():
+                m.close()
+            raise
+        self._owned = list(made.values())
+        return self
+
+    def models(self):
+        '''[(lag, model), ...] in group order'''
+        return [(lag, self.pm if lag == 0 else self.lagged[lag]) for lag in self.lags]
+
+    def evaluate_lagged(self, *model_args):
+        '''evaluate the model of every later release day over the days the findings need, enqueued only'''
+        for lag, m in self.models():
+            if lag:
+                m.evaluate(*model_args, ndays=self.days[-1] - lag + 1, want_stats=False)
+
+    def _calls(self, w):
+        calls = []
+        for g, (lag, m) in enumerate(self.models()):
+            md = self.slots[g]
+            _check_evaluated(m, [d for d in md if d is not None], 'origin maps (lag %d)' % lag)
+            days = [0 if d is None else d for d in md]
+            kind, idx, delta = _day_slots(days)
+            kind[np.array([d is None for d in md], dtype=bool)] = L.REC_NONE
+            stat, post = _day_scales(m, days)
+            calls.append((m.solver._h, g, len(days), L.p_i32(kind), L.p_i32(idx), L.p_f64(stat), L.p_f64(post),
+                          L.p_i32(delta), NEGVAL, w))
+        return calls
+
+    def reserve(self, n):
+        '''room for n members' rows now, so that no add has to grow them'''
+        self._call('reserve', int(n))
+
+    def add(self, weight=1):
+        '''Accumulate the last evaluation of the model -- and of every lagged model (`evaluate_lagged`) -- with
+        integer weight >= 1: one launch pair per lag, each on its solver's stream, no host synchronisation unless
+        the member rows grow.  Every model is checked before the first launch.'''
+        for call in self._calls(self._weight(weight)):
+            self._call('add', *call)
+
+    def merge(self, other):
+        '''self += other (same device, domain, findings, hypotheses and prior); other's members follow self's'''
+        self._call('merge', other._h)
+
+    @property
+    def capacity(self):
+        return self._info()[2]
+
+    @property
+    def nbytes(self):
+        '''the device memory the handle holds now'''
+        return self._info()[3]
+
+    def profile(self, enable=None):
+        '''HIP-event time per kernel class: (add ms, adds, row-reduction ms, reductions, merge ms, merges)'''
+        return self._profile(enable)
+
+    def _h_index(self, h):
+        return self._index(h, len(self.pairs), 'hypothesis')
+
+    def plane(self, what, h):
+        '''[N, N] float64 as the device holds it: what 'A', 'S' or 'l' (the last member's log-likelihood)'''
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        self._call('fetch', {'A': 0, 'S': 1, 'l': 2}[what], self._h_index(h), L.p_f64(out))
+        return out
+
+    def member_rows(self):
+        '''(rows [members, H, 2] float64, weights [members] int64) in add order: per member and hypothesis
+        (mx, sum) over the cells of l + log prior'''
+        m = self.members
+        rows, w = np.empty((m, len(self.pairs), 2), dtype=np.float64), np.empty(m, dtype=np.uint32)
+        self._call('members', m, L.p_f64(rows), w.ctypes.data_as(C.POINTER(C.c_uint32)))
+        return rows, w.astype(np.int64)
+
+    # ---------------------------------------------------------------- numpy on fetched planes, deterministic
+    def log_evidence(self, h):
+        '''[N, N]: E_h = A + log S - log W, the log of the members' mean likelihood of the findings for an origin at
+        each cell; -inf where no member makes the cell possible'''
+        return origin_log_evidence(self.plane('A', h), self.plane('S', h), self.total_weight)
+
+    def _posterior(self):
+        E = np.stack([self.log_evidence(h) for h in range(len(self.pairs))])
+        return origin_posterior(E, self.log_prior)
+
+    def posterior(self, h=None):
+        '''[N, N]: the posterior mass of the origin, normalised over all cells and hypotheses with the prior pi and
+        equal hypothesis priors; h=None: the marginal over the hypotheses, else the share of hypothesis h'''
+        P = self._posterior()
+        return P.sum(axis=0) if h is None else P[self._h_index(h)]
+
+    def hypotheses(self):
+        '''posterior mass per (amount, lag) and its marginals per amount and per lag'''
+        return origin_hypothesis_masses(self._posterior(), self.pairs)
+
+    def region(self, level):
+        '''int8 [N, N]: the smallest set of cells holding `level` of the marginal posterior; ties by linear index'''
+        return origin_region(self.posterior(), level)
+
+    def area(self, level):
+        '''the area of region(level) in m^2'''
+        return float(self.region(level).sum()) * self.cell_area
+
+    def _metres(self, row, col):
+        res = float(self.pm.rad_dist) / int(self.pm.rad_res)
+        R = int(self.pm.rad_res)
+        return (col - R) * res, (R - row) * res
+
+    def mode(self):
+        '''the most probable (hypothesis, cell): a summary of the posterior, not a recommendation.  A UserWarning
+        where it sits on the outermost rung of an amounts ladder of three or more: the ladder may be too short.'''
+        import warnings
+        P = self._posterior()
+        h, row, col = (int(v) for v in np.unravel_index(int(np.argmax(P)), P.shape))
+        east, north = self._metres(row, col)
+        amounts = sorted({a for a, _g in self.pairs})
+        if len(amounts) >= 3 and self.pairs[h][0] in (amounts[0], amounts[-1]):
+            warnings.warn('origin: the mode sits on the outermost amount %g of the ladder %r: the founding number may '
+                          'lie beyond it' % (self.pairs[h][0], amounts), UserWarning, stacklevel=2)
+        return {'row': row, 'col': col, 'east': east, 'north': north, 'hypothesis': h,
+                'amount': self.pairs[h][0], 'lag': self.pairs[h][1], 'mass': float(P[h, row, col]),
+                'cell_mass': float(P[:, row, col].sum())}
+
+    def _cell(self, east_m, north_m):
+        p, = check_probes([(east_m, north_m, 0, 'none', 1.0)], self.pm.rad_dist, self.pm.rad_res)
+        return p['row'], p['col']
+
+    def at(self, east_m, north_m):
+        '''the marginal posterior mass at the cell that holds (east_m, north_m)'''
+        row, col = self._cell(east_m, north_m)
+        return float(self.posterior()[row, col])
+
+    def log_bayes_factor(self, a, b):
+        '''log of (evidence for an origin at a) / (evidence for an origin at b), a and b (east_m, north_m), the
+        hypotheses averaged with equal priors and the cell prior left out: "our site or theirs?"'''
+        E = np.stack([self.log_evidence(h) for h in range(len(self.pairs))])
+        out = []
+        for east, north in (a, b):
+            row, col = self._cell(east, north)
+            x = E[:, row, col]
+            mx = x.max()
+            out.append(-np.inf if mx == -np.inf else float(mx + np.log(np.exp(x - mx).sum())))
+        if out[0] == -np.inf and out[1] == -np.inf:
+            return float('nan')
+        return out[0] - out[1]
+
+    def member_log_evidence(self):
+        '''[members]: log of each member's marginal likelihood of the findings, origin and hypothesis integrated out
+        (origin_member_log_evidence)'''
+        return origin_member_log_evidence(self.member_rows()[0], origin_log_prior_mass(self.log_prior, self.N * self.N))
+
+    def log_weights(self):
+        '''the members' log-evidence in chain-row form, one entry per row of the chain (a member of weight w is w
+        equal rows): what posterior_predictive(reweight={name: dict(log_weights=[...])}) takes per chain, to update
+        every forward map for the findings under an unknown origin'''
+        rows, w = self.member_rows()
+        return np.repeat(origin_member_log_evidence(rows, origin_log_prior_mass(self.log_prior, self.N * self.N)), w)
+
+    def diagnostics(self, min_ess=DEFAULT_MIN_ESS):
+        '''reweight_diagnostics of the rows' contributions to the total evidence (Kish ESS, the largest share); a
+        UserWarning below min_ess: an inversion that hangs on a few members of the chain needs saying'''
+        import warnings
+        d = reweight_diagnostics(self.log_weights())
+        if d['ess'] < min_ess:
+            warnings.warn('origin: the evidence rests on an effective sample of %.1f rows of %d (largest share %.2f); '
+                          'below %g the posterior of the origin is that of a few members'
+                          % (d['ess'], d['rows'], d['max_share'], min_ess), UserWarning, stacklevel=2)
+        return d
+
+    def describe(self):
+        '''the request for a result file'''
+        return {'findings': self.plan['given'], 'hypotheses': [list(h) for h in self.pairs],
+                'levels': list(self.levels), 'prior': self.log_prior is not None}
+
+    def close(self):
+        super().close()
+        for m in self._owned:
+            m.close()
+        self._owned = []
+
+
+def origin_block(om):
+    '''the json block of an OriginMaps: request, hypothesis masses, mode, areas and diagnostics'''
+    import warnings
+    with warnings.catch_warnings(record=True) as caught:
+        warnings.simplefilter('always')
+        block = dict(om.describe(), members=int(om.members), total_weight=float(om.total_weight),
+                     diagnostics=om.diagnostics())
+        try:
+            block.update(masses=om.hypotheses(), mode=om.mode(), areas={level_tag(p): om.area(p) for p in om.levels})
+        except ValueError as e:        # no member makes any cell possible: said in the block, the files are still written
+            block.update(masses=None, mode=None, areas=None, impossible=str(e))
+    block['warnings'] = [str(w.message) for w in caught]
+    for w in caught:
+        warnings.warn(w.message, w.category, stacklevel=2)
+    return block
+
+
+def save_origin(outfile, om):
+    '''PREFIX_origin.npz: E_h per hypothesis (log_evidence_h<h>), the marginal posterior, the regions at the
+    request's levels (region_<tag>), the member rows and weights, the hypotheses; -> (path, json block).  Where no
+    member makes any cell possible the posterior is all zero, the regions are empty and the block says so
+    (`impossible`).'''
+    arrays = {'log_evidence_h%d' % h: om.log_evidence(h) for h in range(len(om.pairs))}
+    try:
+        arrays['posterior'] = om.posterior()
+        for p in om.levels:
+            arrays['region_' + level_tag(p)] = om.region(p)
+    except ValueError:                 # no candidate cell explains the findings: zero mass, empty regions
+        arrays['posterior'] = np.zeros((om.N, om.N), dtype=np.float64)
+        for p in om.levels:
+            arrays['region_' + level_tag(p)] = np.zeros((om.N, om.N), dtype=np.int8)
+    rows, w = om.member_rows()
+    arrays.update(member_rows=rows, member_weights=w, hypotheses=np.array(om.pairs, dtype=np.float64))
+    path = outfile + '_origin.npz'
+    np.savez_compressed(path, **arrays)
+    return path, origin_block(om)
+
+
 # ------------------------------------------------------------------ traces
 def model_names():
     return [m[0] for m in mcmc.MODEL_BLOCK]
@@ -6195,7 +6676,8 @@ class PredictiveResult():
     `dependence`: the DependenceMaps over the summary's days (or the days asked for), None where not asked for (the
     projections and the plan then carry one of their own); `proximity`: the ProximityPosterior of the windows over
     the model's day fields, None where not asked for (the plan then carries a `proximity` of its own over the
-    windows on its output days).'''
+    windows on its output days); `origin`: the OriginMaps of the findings over the model's day records, None where
+    not asked for.'''
 
     def __init__(self, summary, rows, evaluations, failed, seconds, runs, observations, provenance, days,
                  histogram=None, quantiles=None, arrival=None, arrival_levels=None, emergence=None, exposure=None,
@@ -6203,7 +6685,8 @@ class PredictiveResult():
                  peak=None, excursion=None, excursion_levels=None, reweight=None, reweight_info=None, catch=None,
                  information=None, core_range=None, core_range_levels=None, patches=None, patch_levels=None,
                  representative=None, representative_days=None, representative_chains=None, neighbourhood=None,
-                 modes=None, dependence=None, pathways=None, pathway_levels=None, proximity=None):
+                 modes=None, dependence=None, pathways=None, pathway_levels=None, proximity=None, origin=None):
+        self.origin = origin
         self.proximity = proximity
         self.pathways = pathways
         self.pathway_levels = pathway_levels
@@ -6504,6 +6987,8 @@ class PredictiveResult():
             block = save_information('%s_%sinformation' % (outfile, name), ip, area)
             block['given'] = ip.given
             (meta['predictive'][name[:-1]] if name else meta['predictive'])['information'] = block
+        if self.origin is not None:       # outfile_origin.npz (save_origin), the block under predictive.origin
+            _path, meta['predictive']['origin'] = save_origin(str(outfile), self.origin)
         if self.mc_error is not None:
             mmaps = []
             labels = [s.pm.days[d] if d < len(s.pm.days) else d for d in s.days]
@@ -6540,11 +7025,16 @@ def _evaluate_runs(pm, rows, run_list, model_cols, evaluate, want_obs, locinfo, 
     '''one chain: evaluate every run and feed it to the chain's sets (_FieldSet) in the order given, each in the
     FEED_ORDER of its kind.  With a 'sites' set the models of the plan's later release days are evaluated with the
     base model -- with a 'compare' set those of both plans' (its `lagged`), each once -- and a member for which any
-    of them fails is a failed member and is added nowhere.  -> (expected per run or None, failed)'''
+    of them fails is a failed member and is added nowhere.  With an origin= on the 'days' set the models of its
+    hypotheses' later release days are evaluated too; a model the plan shares is evaluated once, over the days its
+    longest reader needs.  The solver's FFT size follows the days evaluated, so where the findings reach further than
+    the plan's output days the plan's maps can differ in their last bits from a run without origin= (never where
+    the plan needs at least as many days).  -> (expected per run or None, failed)'''
     expected = []
     failed = 0
     kinds = {fs._kind: fs for fs in sets}
     plan, both = kinds.get('sites'), kinds.get('compare')
+    origin = getattr(kinds.get('days'), 'origin', None)
     for first, length in run_list:
         theta = rows[first, model_cols]
         if evaluate is not None:
@@ -6555,7 +7045,16 @@ def _evaluate_runs(pm, rows, run_list, model_cols, evaluate, want_obs, locinfo, 
             continue
         try:
             pm.evaluate(*mcmc.model_args(theta), want_stats=False)
-            if both is not None:
+            if origin is not None:     # each later release day's model once, over the days its longest reader needs
+                need = {lag: origin.days[-1] - lag + 1 for lag in origin.lagged}
+                if plan is not None:
+                    for lag in (both.lagged if both is not None else plan._source.lagged):
+                        need[lag] = max(need.get(lag, 0), plan._source.days[-1] - lag + 1)
+                models = dict(both.lagged if both is not None else plan._source.lagged if plan is not None else {})
+                models.update(origin.lagged)
+                for lag, n in sorted(need.items()):
+                    models[lag].evaluate(*mcmc.model_args(theta), ndays=n, want_stats=False)
+            elif both is not None:
                 for lag, m in sorted(both.lagged.items()):
                     m.evaluate(*mcmc.model_args(theta), ndays=plan._source.days[-1] - lag + 1, want_stats=False)
             elif plan is not None:
@@ -6588,7 +7087,7 @@ def _check_request(q):
     days, thresholds = q.days, q.thresholds
     q.cr_frac = q.cr_levels = q.in_plan = q.ct_plan = q.rw_plan = q.ex_thr = q.ex_levels = None
     q.pk_thr = q.pk_levels = q.mc_batches = q.pt_thr = q.pt_conn = q.pt_levels = q.rp_plan = q.nb_plan = None
-    q.md_plan = q.pw_thr = q.pw_conn = q.pw_days = q.pw_levels = q.px_plan = None
+    q.md_plan = q.pw_thr = q.pw_conn = q.pw_days = q.pw_levels = q.px_plan = q.or_plan = None
 
     def ndays0():                     # the model is touched only where an option needs it
         return None if pm0 is None else len(pm0.days)
@@ -6631,6 +7130,10 @@ def _check_request(q):
     def check_proximity_arg():
         cell_m = None if pm0 is None else float(pm0.rad_dist) / int(pm0.rad_res)
         q.px_plan = check_proximity(q.proximity, ndays0(), cell_m, q.evaluate)
+
+    def check_origin_arg():
+        q.or_plan = check_origin(q.origin, None if pm0 is None else pm0.rad_dist, None if pm0 is None else pm0.rad_res,
+                                 ndays0())
     # the options that need the device, in the order in which they are checked: (name, False switches it off too,
     # its check).  check_information, check_catch, check_neighbourhood and check_proximity refuse evaluate= themselves,
     # after the argument's shape.
@@ -6639,7 +7142,7 @@ def _check_request(q):
                                   ('reweight', False, check_reweight_arg), ('excursion', True, check_excursion_arg),
                                   ('peak', True, check_peak_arg), ('mc_error', True, check_mc_error_arg),
                                   ('neighbourhood', False, check_neighbourhood_arg),
-                                  ('proximity', False, check_proximity_arg)):
+                                  ('proximity', False, check_proximity_arg), ('origin', False, check_origin_arg)):
         arg = getattr(q, name, None)  # a request put together by hand may not know the later options
         if arg is None or (or_false and arg is False):
             continue
@@ -6759,7 +7262,9 @@ def _build_sets(sets, q, pm, chain, nruns, late):
     ct, info, nb, px = q.ct_plan, q.in_plan, q.nb_plan, q.px_plan
     day_traps = dict(catch=ct and (ct['traps'],), information=info and (info['traps'],),
                      neighbourhood=nb and (nb['windows'],), proximity=px and (px['windows'],))
-    begin(_FieldSet(), 'days', pm, owns=False, **day_traps).build(q, chain, nruns)
+    day = begin(_FieldSet(), 'days', pm, owns=False, **day_traps)
+    day._late = late                   # the origin maps read the models of their later release days from here
+    day.build(q, chain, nruns)
     for name, W, in_days, labels in q.plans:
         traps = (ct['emergence'], labels) if name == 'emergence' and ct is not None and ct['emergence'] else None
         begin(ProjectedMaps(W, in_days, labels, None), 'projection', Projection(pm, W, in_days), name,
@@ -6786,7 +7291,8 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                          arrival=None, arrival_levels=(0.05, 0.5, 0.95), emergence=None, exposure=None, sites=None,
                          sensitivity=None, compare=None, mc_error=None, peak=None, excursion=None, reweight=None,
                          catch=None, information=None, core_range=None, patches=None, representative=None,
-                         neighbourhood=None, modes=None, dependence=None, pathways=None, proximity=None):
+                         neighbourhood=None, modes=None, dependence=None, pathways=None, proximity=None,
+                         origin=None):
     '''Posterior predictive spread of one or more chains (`Sampler.save` files or (trace, names) pairs). Burn and
     thin apply per chain; consecutive rows with identical model parameters are one evaluation weighted by the
     run's length.
@@ -7003,7 +7509,20 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         `radius(e, level)`).  With sites= the plan gets one of its own over the windows whose day is an output day
         of the plan, in `sites.proximity`; emergence and exposure get none.  A radial profile from the release
         point, mean displacement or dispersal-distance curves, distances between named places, zone totals and a
-        search are not computed.  Without proximity= no call is added and `proximity` is None.'''
+        search are not computed.  Without proximity= no call is added and `proximity` is None.
+    origin: a list of findings (east_m, north_m, day, kind, rate[, n]) or dict(findings=[...], amounts=[...],
+        lags=[...], hypotheses=None, prior=None, levels=(0.5, 0.95)) (check_origin; not with evaluate=; bad arguments
+        fail before any evaluation): from where, when and in what number did the wasps in these findings start?
+        One OriginMaps per chain over the model's day records, fed after the summary with the run's length -- the
+        models of the later release days are built once per model, as for sites=, and evaluated with the base
+        model -- merged in chain order into `origin`: `log_evidence(h)`, `posterior(h)`, `hypotheses()`,
+        `region(level)`, `area(level)`, `mode()`, `at`, `log_bayes_factor`, `log_weights()`, `diagnostics()`.
+        Inference about the past by exhaustive evaluation: no plan is chosen, nothing is recommended; a spatially
+        varying wind or landscape, several sources at once, the rates themselves, a histogram, arrival or Monte
+        Carlo error of these maps and a search for where to put a trap are not computed.  With sites= a lagged
+        model that the plan shares is evaluated once over the days its longest reader needs; where the findings
+        reach further than the plan, the plan's maps can differ in their last bits from a run without origin=.
+        Without origin= nothing is built and `origin` is None.'''
     q = types.SimpleNamespace(**locals())
     t0 = time.perf_counter()
     _check_request(q)                 # bad arguments fail before any evaluation
@@ -7020,9 +7539,10 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
             for ci in range(p, nch, len(pms)):
                 rows, rl, mcols, _o, _s = prepared[ci]
                 if evaluate is None:
-                    if q.site_plan is not None and p not in late:
-                        # once per model, for the union of both plans' release days
-                        lags = set(q.site_plan[2]) | set(q.cmp_plan[2] if q.cmp_plan else ())
+                    if (q.site_plan is not None or q.or_plan is not None) and p not in late:
+                        # once per model, for the union of both plans' release days and the origin hypotheses'
+                        lags = set(q.site_plan[2] if q.site_plan else ()) | set(q.cmp_plan[2] if q.cmp_plan else ())
+                        lags |= set(q.or_plan['lags'] if q.or_plan else ())
                         late[p] = lagged_models(pm, sorted(lags))
                     _build_sets(chain_sets[ci], q, pm, ci, len(rl), late.get(p))
                 results[ci] = _evaluate_runs(pm, rows, rl, mcols, evaluate, q.want_obs, locinfo, chain_sets[ci])
@@ -7123,7 +7643,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         representative=day.representative, representative_days=q.rp_plan['days'] if q.rp_plan else None,
         representative_chains=[p[0][:, p[2]] for p in prepared] if q.rp_plan else None,
         neighbourhood=day.neighbourhood, modes=day.modes, dependence=day.dependence, pathways=day.pathways,
-        pathway_levels=q.pw_levels if q.pw_thr else None, proximity=day.proximity)
+        pathway_levels=q.pw_levels if q.pw_thr else None, proximity=day.proximity, origin=day.origin)
     if day.information is not None:   # the stated convention: past cap / 2 the ensemble bounds the map
         warn_information(day.information)
         if 'sites' in merged:

@@ -76,6 +76,14 @@ Without --chain a short chain is sampled first (--samples) and saved next to --o
         [--information 'DAY,RATE[,YMAX];...'] [--neighbourhood 'DAY,RADIUS_M;...']
         [--proximity 'DAY,T[,in];...'] [--proximity-radii 100,400,1600] [--proximity-levels 0.05,0.5,0.95]
         [--modes [K]] [--modes-days d1,d2|all] [--modes-transform sqrt|raw]
+        [--origin 'EAST,NORTH,DAY,KIND,RATE[,N];...'] [--origin-amounts 0.1,1,10] [--origin-lags 0,2]
+        [--origin-levels 0.5,0.95] [--origin-prior file.npy]
+
+With --origin the origin maps: for findings 'EAST,NORTH,DAY,KIND,RATE[,N]' (metres from the domain centre, model day,
+count | none | found, the rate and for a count the number found) the posterior of where, when (--origin-lags) and in
+what number (--origin-amounts, multiples of the release number) the population started, saved as PREFIX_origin.npz
+with the hypothesis masses, the mode, the areas of the regions at --origin-levels and the diagnostics under
+predictive.origin of the json.
 """
 import argparse
 import json
@@ -218,6 +226,16 @@ def main():
                     'probability of such ground within each (with --proximity)')
     ap.add_argument('--proximity-levels', default='', help='quantile levels of the distance, e.g. 0.05,0.5,0.95 '
                     '(with --proximity)')
+    ap.add_argument('--origin', default='', help="findings 'EAST,NORTH,DAY,KIND,RATE[,N];...' (KIND count | none | "
+                    'found): the posterior of the origin of the population they come from (default: off)')
+    ap.add_argument('--origin-amounts', default='', help='the ladder of founding numbers in multiples of the release '
+                    'number, e.g. 0.1,1,10 (with --origin; default 1)')
+    ap.add_argument('--origin-lags', default='', help='release days after the first model day, e.g. 0,2 (with '
+                    '--origin; default 0)')
+    ap.add_argument('--origin-levels', default='', help='posterior mass of the saved regions, e.g. 0.5,0.95 (with '
+                    '--origin)')
+    ap.add_argument('--origin-prior', default='', help='an N x N .npy log-prior plane, -inf where the origin cannot '
+                    'be (with --origin; default flat)')
     ap.add_argument('--information', default='', help="described traps 'DAY,RATE[,YMAX];...': per cell the mutual "
                     'information in nats between the count of a trap of effort RATE on model day DAY, observed as '
                     '0, 1, .., YMAX (default 0) and more, and the identity of the member (default: off)')
@@ -339,6 +357,14 @@ def main():
                          radii_m=[float(x) for x in args.proximity_radii.split(',') if x.strip()],
                          levels=[float(x) for x in args.proximity_levels.split(',') if x.strip()] or None)
         check_proximity(proximity, None, 10000.0 / args.rad_res)
+    origin = None
+    if args.origin:                      # as do bad --origin findings, amounts, lags, levels or prior
+        from parasitoids_amd.predictive import origin_request
+        try:
+            origin = origin_request(args.origin, args.origin_amounts, args.origin_lags, args.origin_levels,
+                                    args.origin_prior, 10000.0, args.rad_res)
+        except ValueError as e:
+            ap.error('--origin: %s' % e)
     wd, days = PM.get_wind_data(os.path.join(ROOT, 'parasitoids_amd', 'data', 'kalbar'), 30, '00:00')
     modes = None
     if args.modes is not None:           # as do bad --modes settings
@@ -400,6 +426,7 @@ def main():
                                **({'information': information} if information else {}),
                                **({'neighbourhood': neighbourhood} if neighbourhood else {}),
                                **({'proximity': proximity} if proximity else {}),
+                               **({'origin': origin} if origin else {}),
                                **({'core_range': core_range} if core_range else {}),
                                **({'patches': patches} if patches else {}),
                                **({'pathways': pathways} if pathways else {}),
@@ -692,6 +719,10 @@ def main():
         out['prox_bytes'] = pf_bytes
         out['outputs'] += ['%s_prox.npz' % args.out] \
             + (['%s_sites_prox.npz' % args.out] if res.sites is not None and res.sites.proximity is not None else [])
+    if origin:
+        out['origin_hypotheses'] = [list(h) for h in res.origin.pairs]
+        out['origin_bytes'] = int(res.origin.nbytes)
+        out['outputs'] += ['%s_origin.npz' % args.out]
     if information:
         out['information_ms_per_member'] = round(if_ms / max(if_launches, 1), 4)
         out['information_launches_timed'] = if_launches
@@ -840,7 +871,7 @@ def main():
     if res.mc_error is not None:
         res.mc_error.close()
     for pr in (res.representative, res.emergence, res.exposure, res.sites, res.contrast, res.peak, res.excursion, res.catch, res.information,
-               res.core_range, res.patches, res.pathways, res.neighbourhood, res.modes, res.proximity):
+               res.core_range, res.patches, res.pathways, res.neighbourhood, res.modes, res.proximity, res.origin):
         if pr is not None:
             pr.close()
     for p in pms:
