@@ -504,7 +504,14 @@ struct RsDual {
   static_assert(S::T2 % 16 == 0 && S::T3 % 16 == 0, "half-pass offsets assume whole padding groups");
 };
 
-template <int R1, int R2, int R3>
+// SF ("state fused", k_colfull_dual<..., true>): the run's first window after a set_state.  The state's spectrum is
+// not in a.state yet -- only the row half of its transform has run, into a.alt_src (column-major, live rows
+// a.alt_live) -- and role A, idle in slot 0 otherwise, transforms the state column itself: the same body
+// WITHOUT the two conjugations, X[j + q T3] parked in the LDS state column where role B multiplies it at
+// the end of the same slot (one more barrier, slot 0 only).  The state's forward column pass (a launch over
+// all H columns, one spectrum written and read back) does not exist then.  A separate instance: the plain
+// one keeps its code.
+template <int R1, int R2, int R3, bool SF = false>
 __global__ void __launch_bounds__((2 * Rs<R1, R2, R3>::NTHR)) k_colfull_dual(ColFullArgs a) {
   using S = Rs<R1, R2, R3>;
   using D = RsDual<R1, R2, R3>;
@@ -556,6 +563,7 @@ __global__ void __launch_bounds__((2 * Rs<R1, R2, R3>::NTHR)) k_colfull_dual(Col
 
   // prologue: kernel column of day 0 -> staging (role B); role A brings the state column in during
   // slot 0, where it has no transform to run (role B needs it only for the product at the slot's end)
+  // -- or, SF, transforms it there
   if (role == 1) {
     stage_column(0);
     PS_WAIT_VM0();
@@ -563,7 +571,7 @@ __global__ void __launch_bounds__((2 * Rs<R1, R2, R3>::NTHR)) k_colfull_dual(Col
   PS_BAR_LDS();
 
   for (int slot = 0; slot <= nd; ++slot) {
-    const bool act = role == 0 ? slot >= 1 : slot < nd;        // wave-uniform
+    const bool act = role == 0 ? (SF || slot >= 1) : slot < nd;   // wave-uniform
     cplx x[S::RMAX];
     int j = j0;
     cplx w2 = w2c, w3 = w3c;
@@ -572,12 +580,20 @@ __global__ void __launch_bounds__((2 * Rs<R1, R2, R3>::NTHR)) k_colfull_dual(Col
     // ---- first-stage inputs.  Role A's inverse transform runs through the FORWARD code on
     // conjugated data (inverse(x) == conj(forward(conj(x))) bit for bit, see rs_stage): one
     // transform body for both roles, one set of data registers.
-    if (role == 0 && slot == 0) {        // state column -> LDS, coalesced
+    if (!SF && role == 0 && slot == 0) {        // state column -> LDS, coalesced
 #pragma unroll 7
       for (int k = j; k < L; k += S::NTHR) sst[k] = st[k];
     }
     if (act && j < S::T1) {
-      if (role == 0) {
+      if (SF && role == 0 && slot == 0) {  // the state's row-pass output, not conjugated: a forward transform
+        const cplx* ss = a.alt_src + (int64_t)c * L;
+#pragma unroll
+        for (int q = 0; q < R1; ++q) {
+          const int n = j + q * S::T1;
+          x[q] = make_double2(0.0, 0.0);
+          if (row_live(a.alt_live, n, 0)) x[q] = ss[n];
+        }
+      } else if (role == 0) {
 #pragma unroll
         for (int q = 0; q < R1; ++q) x[q] = cconj(sst[j + q * S::T1]);
       } else {
@@ -680,7 +696,14 @@ __global__ void __launch_bounds__((2 * Rs<R1, R2, R3>::NTHR)) k_colfull_dual(Col
     }
     asm volatile("" : "+v"(w3.x), "+v"(w3.y));
     if (act && j < S::T3) rs_stage<R3, PS_FWD>(x, w3, true);
-    if (act && j < S::T3) {
+    if (SF && slot == 0) {                                 // uniform over the workgroup
+      if (role == 0 && j < S::T3) {                        // X[j + q T3] of the state column
+#pragma unroll
+        for (int q = 0; q < R3; ++q) sst[j + q * S::T3] = x[q];
+      }
+      PS_BAR_LDS();                                        // role B keeps its x[] across it
+    }
+    if (act && j < S::T3 && !(SF && slot == 0 && role == 0)) {
       if (role == 0) {                                     // conj: spatial rows j + q T3 of day slot - 1
         const int64_t rst = a.dst_rst;
         cplx* d = a.dst + (int64_t)blockIdx.y * a.dst_bstride + (int64_t)(slot - 1) * a.dst_dstride + PS_COLFULL_OFF(a, c, j);
@@ -701,7 +724,7 @@ __global__ void __launch_bounds__((2 * Rs<R1, R2, R3>::NTHR)) k_colfull_dual(Col
     }
     if (role == 0 && a.pad_energy) {                       // wave sums -> the slack words behind role A's exchange buffer
       double pe = 0.0;                                     // (after the stores: x is all that is live here)
-      if (act && j < S::T3) {
+      if (act && j < S::T3 && !(SF && slot == 0)) {
         const int qlo = a.pad_row0 / S::T3;                // uniform: only the last few q hold pad-only rows
 #pragma unroll
         for (int q = 0; q < R3; ++q) {

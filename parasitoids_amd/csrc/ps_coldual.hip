@@ -12,6 +12,9 @@ struct DualCfg {
   using C = RsCfg<A, B>;
   // worth it only where one chained workgroup fills the CU's LDS (two of them do not fit)
   static constexpr bool on = D::ok && C::CHAIN && C::LDSC > (size_t)80 * 1024;
+  // the state-fused instance (k_colfull_dual<..., true>): every size whose instance compiles without scratch,
+  // i.e. all but the two radix-20 sizes (20 x 14 and 20 x 16 spill 1 and 5 registers, as their plain instances do)
+  static constexpr bool sf = on && D::S::RMAX <= 18;
 };
 
 bool rs_dual_ok(int r2, int r3) {
@@ -22,25 +25,50 @@ bool rs_dual_ok(int r2, int r3) {
   return false;
 }
 
+bool rs_dual_state_ok(int r2, int r3) {
+#define X(A, B) \
+  if (r2 == A && r3 == B) return DualCfg<A, B>::sf;
+  PS_RS_SIZES(X)
+#undef X
+  return false;
+}
+
+static int dual_set_attr(const void* kern, size_t bytes) {
+  return hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess ? 0 : -1;
+}
+
 int rs_coldual_set_attrs() {
 #define X(A, B)                                                                                         \
   if constexpr (DualCfg<A, B>::on) {                                                                    \
     using DD = RsDual<16, A, B>;                                                                        \
     auto kern = k_colfull_dual<16, A, B>;                                                               \
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DD::bytes) != hipSuccess) \
-      return -1;                                                                                        \
+    if (dual_set_attr((const void*)kern, DD::bytes) != 0) return -1;                                    \
+    if constexpr (DualCfg<A, B>::sf) {                                                                  \
+      auto kern_sf = k_colfull_dual<16, A, B, true>;                                                    \
+      if (dual_set_attr((const void*)kern_sf, DD::bytes) != 0) return -1;                               \
+    }                                                                                                   \
   }
   PS_RS_SIZES(X)
 #undef X
   return 0;
 }
 
+// a.alt_src set: the state-fused instance (the state column from the row-pass output a.alt_src)
 int rs_launch_coldual(int r2, int r3, const ColFullArgs& a, int lines8, int batch, hipStream_t st) {
   const dim3 grid((unsigned)(lines8 * 64), batch);
 #define X(A, B)                                                                                         \
   if (r2 == A && r3 == B) {                                                                             \
     if constexpr (DualCfg<A, B>::on) {                                                                  \
       using DD = RsDual<16, A, B>;                                                                      \
+      if (a.alt_src) {                                                                                  \
+        if constexpr (DualCfg<A, B>::sf) {                                                              \
+          if (batch != 1 || a.pred) return 0;                                                           \
+          auto kern_sf = k_colfull_dual<16, A, B, true>;                                                \
+          hipLaunchKernelGGL(kern_sf, grid, dim3(2 * DD::S::NTHR), DD::bytes, st, a);                   \
+          return 1;                                                                                     \
+        }                                                                                               \
+        return 0;                                                                                       \
+      }                                                                                                 \
       auto kern = k_colfull_dual<16, A, B>;                                                             \
       hipLaunchKernelGGL(kern, grid, dim3(2 * DD::S::NTHR), DD::bytes, st, a);                          \
       return 1;                                                                                         \

@@ -54,6 +54,7 @@
   X("PS_NO_ROW_BATCH", no_row_batch, 0, FLAG, R)                                                    \
   X("PS_NO_PAD_QUIET", no_pad_quiet, 0, FLAG, R)                                                    \
   X("PS_NO_TAIL_SPLIT", no_tail_split, 0, FLAG, R)                                                  \
+  X("PS_NO_STATE_FUSE", no_state_fuse, 0, FLAG, R)                                                  \
   X("PS_NO_FWD_PERSIST", no_fwd_persist, 0, FLAG, R)                                                \
   X("PS_NO_FWD_SOLO", no_fwd_solo, 0, FLAG, R)                                                      \
   X("PS_FWD_STAGE", fwd_stage, 0, FLAG, R)                                                          \

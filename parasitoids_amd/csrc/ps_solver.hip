@@ -649,9 +649,12 @@ static int launch_colfull(ps_solver* s, int mode, const cplx* src, cplx* state, 
   ColFullArgs a;
   a.pad_energy = nullptr;
   a.alt_src = nullptr; a.alt_pred = nullptr; a.alt_live = RowLive{0, {0, 0, 0, 0}, nullptr};
-  if (alt) {   // PS_MODE_FOLD: the state column always comes from the row pass of the torus
-    if (!(mode == 0 && nd == 1 && batch == 1 && !pred) || s->refft_pending)
-      return ps_fail(PS_ERR_STATE, "full-column pass: an alternative state source needs a plain single-day pass");
+  if (alt) {   // PS_MODE_FOLD: the state column always comes from the row pass of the torus; a run's first
+               // two-role window after a set_state: from the row pass of the state record (state_fuse_ok)
+    const bool fused_window = nd > 1 && store_prod && colfull_dual(s, nd) && rs_dual_state_ok(s->rs_r2, s->rs_r3);
+    if (!(mode == 0 && (nd == 1 || fused_window) && batch == 1 && !pred) || s->refft_pending)
+      return ps_fail(PS_ERR_STATE, "full-column pass: an alternative state source needs a plain single-day pass "
+                                   "or a two-role window");
     a.alt_src = alt->src; a.alt_pred = alt->pred; a.alt_live = alt->live;
   }
   if (s->refft_pending) {
@@ -942,11 +945,26 @@ static int conv_inv(ps_solver* s, const cplx* kt, cplx* state, int store_prod, d
   return launch_row_inv(s, s->T2.p, rec, stat_slot, 1, negval, stat_scale);
 }
 
+static int ensure_spectrum(ps_solver* s);
+// A chain run that opens with a two-role window of nd days does not build the state's spectrum first: only the
+// row half of the state's transform runs (into Trow, free while no re-transform is pending), and role A of the
+// window's pass transforms each state column in its idle first slot (k_colfull_dual<..., true>) -- no forward
+// column launch over all H columns, one spectrum neither written nor read back.  Fast mode on the full-column
+// pipeline, one batch entry, sizes whose instance compiles without scratch.  PS_NO_STATE_FUSE=1: A/B knob.
+static bool state_fuse_ok(const ps_solver* s, int nd) {
+  return s->tpipe && s->mode == PS_MODE_FAST && !s->auto_exact && !s->borrowed && !s->refft_pending && !s->tinv &&
+         !s->cfg.no_state_fuse && colfull_dual(s, nd) && rs_dual_state_ok(s->rs_r2, s->rs_r3) &&
+         !s->recs[PS_REC_STATE].empty() && s->recs[PS_REC_STATE][0];
+}
+
 // nd un-flagged day steps with one fused pass; recs/stat slots of days d0 .. d0+nd-1
+// (the state's spectrum may still be unbuilt when a chain run comes here first: see state_fuse_ok)
 static int conv_inv_multi(ps_solver* s, const cplx* kt, int nd, cplx* state, double* const* recs, int d0,
                           double negval, double stat_scale, const int* rowrange, int* done) {
   const size_t spec = (size_t)s->Pf * s->ld;
   PS_TRY(s->T1.ensure(spec * nd));
+  const bool fuse_state = !s->spec_valid && state == s->Ahat.p && colfull_chains(s) && state_fuse_ok(s, nd);
+  if (!fuse_state) PS_TRY(ensure_spectrum(s));
   if (s->tpipe) {   // nd days chained on chip by the full-column pass, then the row passes
     *done = 0;
     if (!colfull_chains(s)) return PS_OK;
@@ -977,7 +995,17 @@ static int conv_inv_multi(ps_solver* s, const cplx* kt, int nd, cplx* state, dou
       const int rem = s->H % s->ncu;
       if (rem > 0 && rem * 3 <= s->ncu) hmain = s->H - rem;
     }
-    PS_TRY(launch_colfull(s, 0, kt, state, 1, s->T1.p, 1, live, nullptr, nd, quiet ? s->pad_energy.p : nullptr, 0, hmain));
+    ColAlt salt{nullptr, nullptr, RowLive{0, {0, 0, 0, 0}, nullptr}};
+    if (fuse_state) {   // the row half of the state's transform, as ensure_spectrum would run it
+      PS_TRY(s->Trow.ensure(spec));
+      const SrcMap m = map_plain(s->N, s->Pf);
+      const int* srows = s->srange_valid ? s->srange.p : nullptr;
+      PS_TRY(launch_row_fwd(s, s->recs[PS_REC_STATE][0], 0, s->N, m, m, s->Trow.p, 1, nullptr, 1, srows));
+      salt = ColAlt{s->Trow.p, nullptr, RowLive{1, m, srows}};
+    }
+    PS_TRY(launch_colfull(s, 0, kt, state, 1, s->T1.p, 1, live, nullptr, nd, quiet ? s->pad_energy.p : nullptr, 0, hmain,
+                          -1, true, fuse_state ? &salt : nullptr));
+    if (fuse_state) s->spec_valid = true;   // Ahat holds the state after day d0 + nd - 1 once the pass has run
     if (hmain < s->H) {
       const int rem = s->H - hmain;
       PS_TRY(s->tail_hat.ensure((size_t)nd * rem * s->Pf));
@@ -985,6 +1013,9 @@ static int conv_inv_multi(ps_solver* s, const cplx* kt, int nd, cplx* state, dou
       cplx* th = s->tail_hat.p - (int64_t)hmain * s->Pf;
       {
         ProfScope prof(s, PS_PROF_COL_TAIL, nd);
+        // the state columns k_prefix_cols starts from: they did not go through the two-role pass
+        if (fuse_state)
+          PS_TRY(launch_colfull(s, 1, s->Trow.p, state, 0, nullptr, 1, salt.live, nullptr, 1, nullptr, hmain, s->H, -1, false));
         PS_TRY(launch_colfull(s, 1, kt, th, 0, nullptr, nd, live, nullptr, 1, nullptr, hmain, s->H, (int64_t)rem * s->Pf, false));
         hipLaunchKernelGGL(k_prefix_cols, dim3((s->Pf + 255) / 256, rem), dim3(256), 0, s->stream,
                            state + (int64_t)hmain * s->Pf, s->tail_hat.p, s->Pf, rem, nd);
@@ -2289,7 +2320,6 @@ static int chain_run_body(ps_solver* s, int first, int count, double negval, dou
   // everything else -- broad prob_mass kernels, flagged days -- in the full-column pipeline
   // (Carnarvon R = 2048: 1040 -> 1440 grid-days/s).
   if (s->tpipe_ok && !s->spec_valid) set_pipeline(s, want_full_column(s, first, count));
-  PS_TRY(ensure_spectrum(s));
   if (s->speculate && s->tpipe && colfull_chains(s) && hint >= count && count >= 4 && !s->cfg.no_window_hint) {
     // windows of up to PS_MAX_GROUP_DAYS days, the whole run if it fits.  Measured on the 30-day stack
     // (PS_FIRST_WINDOW): 6 / 8 / 10 / 15 days first and the rest behind -- with the later windows'
@@ -2300,6 +2330,14 @@ static int chain_run_body(ps_solver* s, int first, int count, double negval, dou
     w0 = std::max(2, std::min(std::min(w0, count), PS_MAX_GROUP_DAYS));
     s->spec_window = w0;
     hinted = true;
+  }
+  // The state's spectrum: built here, unless the run opens with a two-role window, whose pass transforms the
+  // state's columns itself (state_fuse_ok; conv_inv_multi decides, and every other consumer of Ahat in this
+  // run -- single days, windows that do not reach the two-role pass -- builds it the usual way first).
+  {
+    const int w1 = std::min(std::min(s->spec_window, std::min(s->chunk_days, count)),
+                            std::min(PS_MAX_GROUP_DAYS, std::max(1, s->cfg.tpipe_days)));
+    if (!(hinted && !s->spec_valid && s->fused_days >= 8 && state_fuse_ok(s, w1))) PS_TRY(ensure_spectrum(s));
   }
   // A solver that has seen a flag no longer speculates blindly, but sampler chains and repeated runs raise
   // their flags on much the same days every time: with the previous run's flags at hand, the stretches of
@@ -2362,7 +2400,10 @@ static int chain_run_body(ps_solver* s, int first, int count, double negval, dou
     } else {
       PS_TRY(transform_kernels(s, c0, cn));
     }
-    auto day = [&](int d, bool with_refft) -> int { return run_day(s, d, with_refft, negval, stat_scale); };
+    auto day = [&](int d, bool with_refft) -> int {
+      PS_TRY(ensure_spectrum(s));   // (a run whose first window was to carry the state's column pass may come here first)
+      return run_day(s, d, with_refft, negval, stat_scale);
+    };
     // Speculation on the boundary flag (CalcSol.py:200-201): windows of days are enqueued
     // WITHOUT the three flag-conditional re-FFT launches (~6 us each even when they do
     // nothing) and their pad maxima are copied to pinned host memory behind them.  The host

@@ -54,5 +54,8 @@ int rs_launch_row_fold(int r2, int r3, const RowFoldArgs& a, int units, hipStrea
 bool rs_colfull_alt_ok(int r2, int r3);
 // two-role chained pass (k_colfull_dual; mode 0, nd >= 2): sizes for which rs_dual_ok
 bool rs_dual_ok(int r2, int r3);
+// ... and its state-fused instance (ColFullArgs::alt_src set: role A transforms the state column in slot 0
+// from the state's row-pass output; one batch entry, no predicate): the sizes that compile it without scratch
+bool rs_dual_state_ok(int r2, int r3);
 int rs_coldual_set_attrs();
 int rs_launch_coldual(int r2, int r3, const ColFullArgs& a, int lines8, int batch, hipStream_t st);
