@@ -394,7 +394,11 @@ int ps_summary_info(ps_summary* a, double* total_weight, int64_t* members);
 int ps_summary_fetch(ps_summary* a, int slot, int what, double* out /* N*N */);
 int ps_summary_reset(ps_summary* a);
 /* measurement: HIP-event timing of the ps_summary_add launches.  enable 1 on, 0 off, < 0 unchanged;
- * total_ms / launches (either may be NULL) receive the timed launches so far (synchronises). */
+ * total_ms / launches (either may be NULL) receive the timed launches since creation (synchronises).
+ * Every ps_*_prof of an accumulator or fields handle below works alike: while enabled a launch keeps one
+ * event pair; finished pairs are folded into running totals and their events destroyed on every read and,
+ * with one host synchronisation, once 256 are pending on a channel, so a profiled handle holds a bounded
+ * number of events however long it lives.  Nothing of this runs while profiling is off. */
 int ps_summary_prof(ps_summary* a, int enable, double* total_ms, int64_t* launches);
 void ps_summary_destroy(ps_summary* a);
 
@@ -1228,8 +1232,8 @@ int ps_range_fetch_counts(ps_range* a, int j, int slot, uint32_t* out /* N*N */)
 int ps_range_fetch_members(ps_range* a, int j, int slot, double* lambda, uint32_t* cells, uint32_t* weights);
 /* per member in add order the integer mass Q and the exponent E of the slot (either may be NULL) */
 int ps_range_fetch_mass(ps_range* a, int slot, uint64_t* Q, int32_t* E /* members */);
-/* measurement: HIP-event timing of the adds and the map launches, as ps_arrival_prof; while enabled every add and
- * map keeps one event pair until ps_range_reset or ps_range_destroy */
+/* measurement: HIP-event timing of the adds and the map launches, as ps_arrival_prof; the totals count from
+ * the last ps_range_reset */
 int ps_range_prof(ps_range* a, int enable, double* add_ms, int64_t* adds, double* map_ms, int64_t* maps);
 void ps_range_destroy(ps_range* a);
 
@@ -1293,8 +1297,8 @@ int ps_patch_fetch_counts(ps_patch* a, int k, int slot, int which, uint32_t* out
 /* per member in add order the row of (k, slot) and the weight (any pointer may be NULL) */
 int ps_patch_fetch_members(ps_patch* a, int k, int slot, uint32_t* npatch, uint32_t* cells, uint32_t* main_cells,
                            uint32_t* main_label, uint32_t* sat_cells_max, uint32_t* weights);
-/* measurement: HIP-event timing of the adds and the map launches, as ps_range_prof; while enabled every add and
- * map keeps one event pair until ps_patch_reset or ps_patch_destroy */
+/* measurement: HIP-event timing of the adds and the map launches, as ps_range_prof; the totals count from
+ * the last ps_patch_reset */
 int ps_patch_prof(ps_patch* a, int enable, double* add_ms, int64_t* adds, double* map_ms, int64_t* maps);
 void ps_patch_destroy(ps_patch* a);
 
@@ -1364,8 +1368,7 @@ int ps_pathway_fetch_counts(ps_pathway* a, int k, int which, uint32_t* out /* N*
 /* per member in add order the row of (k, slot) and the weight (any pointer may be NULL) */
 int ps_pathway_fetch_members(ps_pathway* a, int k, int slot, uint32_t* front, uint32_t* jump, uint32_t* secondary,
                              uint32_t* foci, uint32_t* weights);
-/* measurement: HIP-event timing of the adds; while enabled every add keeps one event pair until ps_pathway_reset or
- * ps_pathway_destroy */
+/* measurement: HIP-event timing of the adds, as ps_summary_prof; the totals count from the last ps_pathway_reset */
 int ps_pathway_prof(ps_pathway* a, int enable, double* add_ms, int64_t* adds);
 void ps_pathway_destroy(ps_pathway* a);
 
@@ -1421,7 +1424,7 @@ int ps_overlap_subset(ps_overlap* h, int k, int slot, int64_t members, const uin
  * member-tile edge of the pair kernel */
 int ps_overlap_info(ps_overlap* h, int64_t* members, int64_t* bytes, int32_t* tile);
 /* measurement: HIP-event timing of the pairs calls (memset, window, pair kernel) and the subset launches, as
- * ps_arrival_prof; while enabled every call keeps one event pair, folded into the totals past 256 */
+ * ps_arrival_prof */
 int ps_overlap_prof(ps_overlap* h, int enable, double* pairs_ms, int64_t* pairs_n, double* subset_ms,
                     int64_t* subset_n);
 void ps_overlap_destroy(ps_overlap* h);
@@ -1609,8 +1612,8 @@ int ps_prox_fetch_d2(ps_prox* c, int e, uint32_t* out /* N*N */);
 int ps_prox_gather(ps_prox* c, int64_t n, const int32_t* rows, const int32_t* cols, double* out /* nout x n */);
 /* any pointer may be NULL; strip: the width W in use */
 int ps_prox_info(ps_prox* c, int* N, int* nin, int* nout, int64_t* applies, int* strip);
-/* measurement: HIP-event timing of the applies, the set and the row pass apart from the column pass; both counts
- * are the applies timed */
+/* measurement: HIP-event timing of the applies, the set and the row pass apart from the column pass (an event
+ * pair each); both counts are the applies timed */
 int ps_prox_prof(ps_prox* c, int enable, double* row_ms, int64_t* row_n, double* col_ms, int64_t* col_n);
 void ps_prox_destroy(ps_prox* c);
 /* One member whose values are the handle's current outputs in metres, as ps_summary_add_nbhd takes a

@@ -190,36 +190,12 @@ struct ps_arrival {
   int64_t members = 0;
   std::vector<uint32_t> weights;   // per member, in row order
   hipStream_t stream = nullptr;    // reset / merge / maps / fetch / row growth
-  hipEvent_t ev = nullptr;         // the last operation, on whatever stream it ran
-  bool ev_live = false;
-  bool prof_on = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_add, prof_map;
+  PsLastOp last;                   // the last operation, on whatever stream it ran
+  PsProf prof;                     // channel 0: the adds, 1: the maps
 };
 
 static int64_t arr_row_len(const ps_arrival* a) { return (int64_t)a->nthr * a->nslot; }
 static size_t arr_cnt_bytes(const ps_arrival* a) { return (size_t)arr_row_len(a) * a->pitch * sizeof(uint32_t); }
-
-static int arr_after_last(ps_arrival* a, hipStream_t stream) {
-  if (a->ev_live) PS_HIP(hipStreamWaitEvent(stream, a->ev, 0));
-  return PS_OK;
-}
-static int arr_mark_last(ps_arrival* a, hipStream_t stream) {
-  PS_HIP(hipEventRecord(a->ev, stream));
-  a->ev_live = true;
-  return PS_OK;
-}
-static int arr_prof_begin(ps_arrival* a, std::vector<std::pair<hipEvent_t, hipEvent_t>>& v, hipStream_t stream,
-                          hipEvent_t* end) {
-  *end = nullptr;
-  if (!a->prof_on) return PS_OK;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  PS_HIP(hipEventCreate(&e0));
-  PS_HIP(hipEventCreate(&e1));
-  v.push_back({e0, e1});
-  PS_HIP(hipEventRecord(e0, stream));
-  *end = e1;
-  return PS_OK;
-}
 
 // room for `need` member rows: a doubling copies the rows so far on the handle's stream and synchronises
 // once before the old block is freed
@@ -232,7 +208,7 @@ static int arr_reserve_rows(ps_arrival* a, int64_t need) {
   PS_HIP(hipMalloc((void**)&p, (size_t)cap * row_b));
   if (a->rows) {
     hipError_t e = hipSuccess;
-    if (a->ev_live) e = hipStreamWaitEvent(a->stream, a->ev, 0);
+    if (a->last.live) e = hipStreamWaitEvent(a->stream, a->last.ev, 0);
     if (e == hipSuccess && a->members > 0)
       e = hipMemcpyAsync(p, a->rows, (size_t)a->members * row_b, hipMemcpyDeviceToDevice, a->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(a->stream);
@@ -250,16 +226,12 @@ static int arr_reserve_rows(ps_arrival* a, int64_t need) {
 extern "C" void ps_arrival_destroy(ps_arrival* a) {
   if (!a) return;
   (void)hipSetDevice(a->device);
-  if (a->ev_live) (void)hipEventSynchronize(a->ev);
+  a->last.sync();
   if (a->stream) (void)hipStreamSynchronize(a->stream);
-  for (auto* v : {&a->prof_add, &a->prof_map})
-    for (auto& p : *v) {
-      (void)hipEventDestroy(p.first);
-      (void)hipEventDestroy(p.second);
-    }
+  a->prof.release();
   for (void* p : {(void*)a->cnt, (void*)a->part, (void*)a->rows, (void*)a->map})
     if (p) (void)hipFree(p);
-  if (a->ev) (void)hipEventDestroy(a->ev);
+  a->last.destroy();
   if (a->stream) (void)hipStreamDestroy(a->stream);
   delete a;
 }
@@ -267,9 +239,9 @@ extern "C" void ps_arrival_destroy(ps_arrival* a) {
 extern "C" int ps_arrival_reset(ps_arrival* a) {
   if (!a) return ps_fail(PS_ERR_BAD_ARG, "arrival_reset: null handle");
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(arr_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   PS_HIP(hipMemsetAsync(a->cnt, 0, arr_cnt_bytes(a), a->stream));
-  PS_TRY(arr_mark_last(a, a->stream));
+  PS_TRY(a->last.mark(a->stream));
   a->W = 0;
   a->members = 0;
   a->weights.clear();
@@ -314,7 +286,7 @@ extern "C" int ps_arrival_create(int device, int N, int nslot, int nthr, const d
     return rc;
   };
   hipError_t e = hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&a->ev, hipEventDisableTiming);
+  if (e == hipSuccess) e = a->last.create();
   if (e == hipSuccess) e = hipMalloc((void**)&a->cnt, arr_cnt_bytes(a));
   if (e == hipSuccess) e = hipMalloc((void**)&a->part, (size_t)arr_row_len(a) * nblk * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMalloc((void**)&a->map, (size_t)pitch * sizeof(double));
@@ -332,9 +304,9 @@ static int arr_launch(ps_arrival* a, const ArrSlots& desc, hipStream_t stream, d
   ArrThr thr;
   for (int k = 0; k < PS_ARR_MAX_THR; ++k) thr.t[k] = k < a->nthr ? a->thr[(size_t)k] : 0.0;
   PS_TRY(arr_reserve_rows(a, a->members + 1));
-  PS_TRY(arr_after_last(a, stream));
+  PS_TRY(a->last.wait(stream));
   hipEvent_t e1 = nullptr;
-  PS_TRY(arr_prof_begin(a, a->prof_add, stream, &e1));
+  PS_TRY(a->prof.begin(0, stream, &e1));
   hipLaunchKernelGGL(k_arrival_add, dim3(a->nblk), dim3(PS_ARR_THREADS), 0, stream, desc, thr, a->nslot, a->nthr,
                      a->cnt, a->part, a->ncell, a->pitch, negval, weight);
   PS_HIP(hipGetLastError());
@@ -342,8 +314,8 @@ static int arr_launch(ps_arrival* a, const ArrSlots& desc, hipStream_t stream, d
   hipLaunchKernelGGL(k_arrival_rows, dim3(nks), dim3(PS_ARR_THREADS), 0, stream, a->part, a->nblk,
                      a->rows + a->members * nks);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, stream));
-  PS_TRY(arr_mark_last(a, stream));
+  PS_TRY(a->prof.end(stream, e1));
+  PS_TRY(a->last.mark(stream));
   a->W += weight;
   a->members += 1;
   a->weights.push_back(weight);
@@ -419,16 +391,16 @@ extern "C" int ps_arrival_merge(ps_arrival* dst, ps_arrival* src) {
   if (src->members == 0) return PS_OK;
   PS_HIP(hipSetDevice(dst->device));
   PS_TRY(arr_reserve_rows(dst, dst->members + src->members));
-  PS_TRY(arr_after_last(dst, dst->stream));
-  PS_TRY(arr_after_last(src, dst->stream));
+  PS_TRY(dst->last.wait(dst->stream));
+  PS_TRY(src->last.wait(dst->stream));
   hipLaunchKernelGGL(k_arrival_merge, dim3(2048), dim3(256), 0, dst->stream, dst->cnt, src->cnt,
                      arr_row_len(dst) * dst->pitch);
   PS_HIP(hipGetLastError());
   const int64_t nks = arr_row_len(dst);
   PS_HIP(hipMemcpyAsync(dst->rows + dst->members * nks, src->rows, (size_t)(src->members * nks) * sizeof(uint32_t),
                         hipMemcpyDeviceToDevice, dst->stream));
-  PS_TRY(arr_mark_last(dst, dst->stream));
-  PS_TRY(arr_mark_last(src, dst->stream));   // src is read until then
+  PS_TRY(dst->last.mark(dst->stream));
+  PS_TRY(src->last.mark(dst->stream));   // src is read until then
   dst->W += src->W;
   dst->members += src->members;
   dst->weights.insert(dst->weights.end(), src->weights.begin(), src->weights.end());
@@ -451,15 +423,15 @@ static int arr_check(ps_arrival* a, int k, const char* who) {
 // planes 0 .. nplane - 1 of threshold k summed into the map scratch (as prob = C / W, or as uint32 C)
 static int arr_cum(ps_arrival* a, int k, int nplane, bool prob) {
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(arr_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   hipEvent_t e1 = nullptr;
-  PS_TRY(arr_prof_begin(a, a->prof_map, a->stream, &e1));
+  PS_TRY(a->prof.begin(1, a->stream, &e1));
   const uint32_t* ck = a->cnt + (int64_t)k * a->nslot * a->pitch;
   hipLaunchKernelGGL(k_arrival_cum, dim3((unsigned)((a->ncell + 255) / 256)), dim3(256), 0, a->stream, ck, nplane,
                      a->ncell, a->pitch, (double)a->W, prob ? a->map : nullptr, prob ? nullptr : (uint32_t*)a->map);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, a->stream));
-  PS_TRY(arr_mark_last(a, a->stream));
+  PS_TRY(a->prof.end(a->stream, e1));
+  PS_TRY(a->last.mark(a->stream));
   return PS_OK;
 }
 
@@ -478,15 +450,15 @@ extern "C" int ps_arrival_quantile(ps_arrival* a, int k, double p, int32_t* out)
   if (!(p > 0.0 && p <= 1.0)) return ps_fail(PS_ERR_BAD_ARG, "arrival_quantile: p = %g is not in (0, 1]", p);
   PS_TRY(arr_check(a, k, "arrival_quantile"));
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(arr_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   hipEvent_t e1 = nullptr;
-  PS_TRY(arr_prof_begin(a, a->prof_map, a->stream, &e1));
+  PS_TRY(a->prof.begin(1, a->stream, &e1));
   const uint32_t* ck = a->cnt + (int64_t)k * a->nslot * a->pitch;
   hipLaunchKernelGGL(k_arrival_quantile, dim3((unsigned)((a->ncell + 255) / 256)), dim3(256), 0, a->stream, ck,
                      a->nslot, a->ncell, a->pitch, p * (double)a->W, (int32_t*)a->map);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, a->stream));
-  PS_TRY(arr_mark_last(a, a->stream));
+  PS_TRY(a->prof.end(a->stream, e1));
+  PS_TRY(a->last.mark(a->stream));
   PS_HIP(hipMemcpyAsync(out, a->map, (size_t)a->ncell * sizeof(int32_t), hipMemcpyDeviceToHost, a->stream));
   PS_HIP(hipStreamSynchronize(a->stream));
   return PS_OK;
@@ -507,7 +479,7 @@ extern "C" int ps_arrival_fetch_counts(ps_arrival* a, int k, int slot, uint32_t*
     return PS_OK;
   }
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(arr_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   const uint32_t* src = a->cnt + ((int64_t)k * a->nslot + slot) * a->pitch;
   PS_HIP(hipMemcpyAsync(out, src, n * sizeof(uint32_t), hipMemcpyDeviceToHost, a->stream));
   PS_HIP(hipStreamSynchronize(a->stream));
@@ -524,7 +496,7 @@ extern "C" int ps_arrival_fetch_reached(ps_arrival* a, int64_t first, int64_t co
     for (int64_t m = 0; m < count; ++m) weights[m] = a->weights[(size_t)(first + m)];
   if (!cells || count == 0) return PS_OK;
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(arr_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   const int64_t nks = arr_row_len(a);
   PS_HIP(hipMemcpyAsync(cells, a->rows + first * nks, (size_t)(count * nks) * sizeof(uint32_t),
                         hipMemcpyDeviceToHost, a->stream));
@@ -536,21 +508,10 @@ extern "C" int ps_arrival_prof(ps_arrival* a, int enable, double* add_ms, int64_
                                int64_t* maps) {
   if (!a) return ps_fail(PS_ERR_BAD_ARG, "arrival_prof: null handle");
   PS_HIP(hipSetDevice(a->device));
-  if (enable >= 0) a->prof_on = enable != 0;
+  a->prof.set(enable);
   double* ms_out[2] = {add_ms, map_ms};
   int64_t* n_out[2] = {adds, maps};
-  std::vector<std::pair<hipEvent_t, hipEvent_t>>* lists[2] = {&a->prof_add, &a->prof_map};
-  for (int k = 0; k < 2; ++k) {
-    if (!ms_out[k] && !n_out[k]) continue;
-    double ms = 0.0;
-    for (auto& p : *lists[k]) {
-      PS_HIP(hipEventSynchronize(p.second));
-      float t = 0.f;
-      PS_HIP(hipEventElapsedTime(&t, p.first, p.second));
-      ms += t;
-    }
-    if (ms_out[k]) *ms_out[k] = ms;
-    if (n_out[k]) *n_out[k] = (int64_t)lists[k]->size();
-  }
+  for (int k = 0; k < 2; ++k)
+    if (ms_out[k] || n_out[k]) PS_TRY(a->prof.totals(k, ms_out[k], n_out[k]));
   return PS_OK;
 }

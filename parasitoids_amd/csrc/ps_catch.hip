@@ -105,54 +105,19 @@ struct ps_catch {
   int64_t g_cap = 0;
   int64_t applies = 0;
   hipStream_t stream = nullptr;    // fetch / gather / apply of another fields source
-  hipEvent_t ev = nullptr;         // the last operation on Y, on whatever stream it ran
-  bool ev_live = false;
-  bool prof_on = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof;
-  double prof_ms = 0.0;            // apply launches already folded out of the list above
-  int64_t prof_n = 0;
+  PsLastOp last;                   // the last operation on Y, on whatever stream it ran
+  PsProf prof;                     // channel 0: the applies
 };
-
-static int catch_after_last(ps_catch* c, hipStream_t stream) {
-  if (c->ev_live) PS_HIP(hipStreamWaitEvent(stream, c->ev, 0));
-  return PS_OK;
-}
-static int catch_mark_last(ps_catch* c, hipStream_t stream) {
-  PS_HIP(hipEventRecord(c->ev, stream));
-  c->ev_live = true;
-  return PS_OK;
-}
-// the finished pairs into the handle's totals, their events destroyed (as ps_peak_prof): a profiled handle holds
-// at most CATCH_PROF_PENDING pairs however long it lives
-static const size_t CATCH_PROF_PENDING = 256;
-static int catch_prof_fold(ps_catch* c) {
-  for (auto& p : c->prof) {
-    PS_HIP(hipEventSynchronize(p.second));
-    float t = 0.f;
-    PS_HIP(hipEventElapsedTime(&t, p.first, p.second));
-    c->prof_ms += t;
-    c->prof_n += 1;
-  }
-  for (auto& p : c->prof) {
-    (void)hipEventDestroy(p.first);
-    (void)hipEventDestroy(p.second);
-  }
-  c->prof.clear();
-  return PS_OK;
-}
 
 extern "C" void ps_catch_destroy(ps_catch* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  if (c->ev_live) (void)hipEventSynchronize(c->ev);
+  c->last.sync();
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  for (auto& e : c->prof) {
-    (void)hipEventDestroy(e.first);
-    (void)hipEventDestroy(e.second);
-  }
+  c->prof.release();
   for (void* q : {(void*)c->Y, (void*)c->g_cell, (void*)c->g_out})
     if (q) (void)hipFree(q);
-  if (c->ev) (void)hipEventDestroy(c->ev);
+  c->last.destroy();
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
@@ -215,7 +180,7 @@ extern "C" int ps_catch_create(int device, int N, int nin, int nout, const int32
   };
   const size_t y_b = (size_t)nout * pitch * sizeof(double);
   hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev, hipEventDisableTiming);
+  if (e == hipSuccess) e = c->last.create();
   if (e == hipSuccess) e = hipMalloc((void**)&c->Y, y_b);
   if (e == hipSuccess) e = hipMemsetAsync(c->Y, 0, y_b, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -227,20 +192,14 @@ extern "C" int ps_catch_create(int device, int N, int nin, int nout, const int32
 
 // one launch over the resolved descriptors on `stream`, behind the handle's last operation
 static int catch_launch(ps_catch* c, const CatchSlots& desc, hipStream_t stream, double negval) {
-  PS_TRY(catch_after_last(c, stream));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (c->prof_on) {
-    if (c->prof.size() >= CATCH_PROF_PENDING) PS_TRY(catch_prof_fold(c));
-    PS_HIP(hipEventCreate(&e0));
-    PS_HIP(hipEventCreate(&e1));
-    c->prof.push_back({e0, e1});
-    PS_HIP(hipEventRecord(e0, stream));
-  }
+  PS_TRY(c->last.wait(stream));
+  hipEvent_t e1 = nullptr;
+  PS_TRY(c->prof.begin(0, stream, &e1));
   hipLaunchKernelGGL(k_catch_apply, dim3(c->nblk), dim3(PS_CATCH_THREADS), 0, stream, desc, c->tab, c->Y, c->ncell,
                      c->pitch, negval);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, stream));
-  PS_TRY(catch_mark_last(c, stream));
+  PS_TRY(c->prof.end(stream, e1));
+  PS_TRY(c->last.mark(stream));
   c->applies += 1;
   return PS_OK;
 }
@@ -302,7 +261,7 @@ extern "C" int ps_catch_fetch(ps_catch* c, int e, double* out) {
   if (e < 0 || e >= c->nout) return ps_fail(PS_ERR_BAD_ARG, "catch_fetch: output %d of %d", e, c->nout);
   if (c->applies == 0) return ps_fail(PS_ERR_STATE, "catch_fetch: nothing applied yet");
   PS_HIP(hipSetDevice(c->device));
-  PS_TRY(catch_after_last(c, c->stream));
+  PS_TRY(c->last.wait(c->stream));
   PS_HIP(hipMemcpyAsync(out, c->Y + (int64_t)e * c->pitch, (size_t)c->ncell * sizeof(double), hipMemcpyDeviceToHost,
                         c->stream));
   PS_HIP(hipStreamSynchronize(c->stream));
@@ -331,7 +290,7 @@ extern "C" int ps_catch_gather(ps_catch* c, int64_t n, const int32_t* rows, cons
     PS_HIP(hipMalloc((void**)&c->g_out, (size_t)n * c->nout * sizeof(double)));
     c->g_cap = n;
   }
-  PS_TRY(catch_after_last(c, c->stream));
+  PS_TRY(c->last.wait(c->stream));
   PS_HIP(hipMemcpyAsync(c->g_cell, cell.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
   const int64_t total = n * c->nout;
   hipLaunchKernelGGL(k_catch_gather, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, c->Y, c->pitch,
@@ -354,12 +313,8 @@ extern "C" int ps_catch_info(ps_catch* c, int* N, int* nin, int* nout, int64_t* 
 extern "C" int ps_catch_prof(ps_catch* c, int enable, double* total_ms, int64_t* launches) {
   if (!c) return ps_fail(PS_ERR_BAD_ARG, "catch_prof: null handle");
   PS_HIP(hipSetDevice(c->device));
-  if (enable >= 0) c->prof_on = enable != 0;
-  if (total_ms || launches) {
-    PS_TRY(catch_prof_fold(c));
-    if (total_ms) *total_ms = c->prof_ms;
-    if (launches) *launches = c->prof_n;
-  }
+  c->prof.set(enable);
+  if (total_ms || launches) PS_TRY(c->prof.totals(0, total_ms, launches));
   return PS_OK;
 }
 
@@ -374,6 +329,6 @@ static int catch_view(void* h, PsProjectView* out) {
   out->device = c->device;
   return PS_OK;
 }
-static int catch_wait(void* h, hipStream_t stream) { return catch_after_last(static_cast<ps_catch*>(h), stream); }
-static int catch_mark(void* h, hipStream_t stream) { return catch_mark_last(static_cast<ps_catch*>(h), stream); }
+static int catch_wait(void* h, hipStream_t stream) { return static_cast<ps_catch*>(h)->last.wait(stream); }
+static int catch_mark(void* h, hipStream_t stream) { return static_cast<ps_catch*>(h)->last.mark(stream); }
 PsFieldsOps ps_catch_fields() { return PsFieldsOps{"catch fields", catch_view, catch_wait, catch_mark}; }

@@ -6,6 +6,7 @@
 #include <stdio.h>
 
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/parasitoid_hip.h"
@@ -38,6 +39,111 @@ inline int ps_fail(int code, const char* fmt, ...) {
     int rc_ = (expr);           \
     if (rc_ != PS_OK) return rc_; \
   } while (0)
+
+// The last operation on a handle's device data, on whatever stream it ran: an untimed event and whether it was ever
+// recorded.  An operation on another stream first waits for it and then marks itself as the last one, so the
+// operations of one handle run in call order across streams without a host synchronise.
+struct PsLastOp {
+  hipEvent_t ev = nullptr;
+  bool live = false;
+  hipError_t create() { return hipEventCreateWithFlags(&ev, hipEventDisableTiming); }
+  int wait(hipStream_t stream) {   // order `stream` behind the last operation; nothing before the first mark
+    if (live) PS_HIP(hipStreamWaitEvent(stream, ev, 0));
+    return PS_OK;
+  }
+  int mark(hipStream_t stream) {
+    PS_HIP(hipEventRecord(ev, stream));
+    live = true;
+    return PS_OK;
+  }
+  void sync() {   // destroy paths: the last operation has finished when this returns
+    if (live) (void)hipEventSynchronize(ev);
+  }
+  void destroy() {
+    if (ev) (void)hipEventDestroy(ev);
+    ev = nullptr;
+    live = false;
+  }
+};
+
+// Launch profiling of a handle (its ps_xxx_prof): while `on`, begin/end bracket a launch sequence with a pair of
+// timed events on one of up to PS_PROF_CHANNELS channels.  Finished pairs are folded into the channel's totals and
+// their events destroyed at every report and whenever PS_PROF_PENDING pairs are pending -- the one host
+// synchronise, with profiling on only -- so a profiled handle holds a bounded number of events however long it
+// lives.  The totals count from the handle's creation.
+#define PS_PROF_CHANNELS 4
+#define PS_PROF_PENDING 256
+struct PsProf {
+  bool on = false;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending[PS_PROF_CHANNELS];
+  double ms[PS_PROF_CHANNELS] = {0.0, 0.0, 0.0, 0.0};
+  int64_t n[PS_PROF_CHANNELS] = {0, 0, 0, 0};
+  // *end: the event to hand to end() after the launches, nullptr while profiling is off
+  int begin(int channel, hipStream_t stream, hipEvent_t* end) {
+    *end = nullptr;
+    if (!on) return PS_OK;
+    if (pending[channel].size() >= PS_PROF_PENDING) PS_TRY(fold(channel));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    PS_HIP(hipEventCreate(&e0));
+    hipError_t e = hipEventCreate(&e1);
+    if (e != hipSuccess) {
+      (void)hipEventDestroy(e0);
+      PS_HIP(e);
+    }
+    pending[channel].push_back({e0, e1});
+    PS_HIP(hipEventRecord(e0, stream));
+    *end = e1;
+    return PS_OK;
+  }
+  int end(hipStream_t stream, hipEvent_t e1) {
+    if (e1) PS_HIP(hipEventRecord(e1, stream));
+    return PS_OK;
+  }
+  // the pending pairs into the totals in list order, their events destroyed
+  int fold(int channel) {
+    auto& list = pending[channel];
+    for (auto& p : list) {
+      PS_HIP(hipEventSynchronize(p.second));
+      float t = 0.f;
+      PS_HIP(hipEventElapsedTime(&t, p.first, p.second));
+      ms[channel] += t;
+      n[channel] += 1;
+    }
+    for (auto& p : list) {
+      (void)hipEventDestroy(p.first);
+      (void)hipEventDestroy(p.second);
+    }
+    list.clear();
+    return PS_OK;
+  }
+  int totals(int channel, double* total_ms, int64_t* launches) {
+    PS_TRY(fold(channel));
+    if (total_ms) *total_ms = ms[channel];
+    if (launches) *launches = n[channel];
+    return PS_OK;
+  }
+  void set(int enable) {   // < 0: leave as it is
+    if (enable >= 0) on = enable != 0;
+  }
+  bool idle() const {   // no pair pending on any channel
+    for (auto& list : pending)
+      if (!list.empty()) return false;
+    return true;
+  }
+  // destroy paths, and the reset of a handle whose timings go with its members: the pending events destroyed,
+  // the totals zero
+  void release() {
+    for (int c = 0; c < PS_PROF_CHANNELS; ++c) {
+      for (auto& p : pending[c]) {
+        (void)hipEventDestroy(p.first);
+        (void)hipEventDestroy(p.second);
+      }
+      pending[c].clear();
+      ms[c] = 0.0;
+      n[c] = 0;
+    }
+  }
+};
 
 // Device memory goes through a small caching allocator (ps_solver.hip): an MCMC run creates
 // and destroys a solver whenever the kernel extent changes, and hipMalloc/hipFree of its

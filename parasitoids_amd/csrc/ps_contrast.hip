@@ -171,10 +171,8 @@ struct ps_contrast {
   int64_t members = 0;
   std::vector<uint32_t> weights;   // per member, in row order
   hipStream_t stream = nullptr;    // every operation of the handle
-  hipEvent_t ev = nullptr;         // the last operation
-  bool ev_live = false;
-  bool prof_on = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof;
+  PsLastOp last;                   // the last operation
+  PsProf prof;                     // channel 0: the adds
 };
 
 static int con_planes(const ps_contrast* h) { return 2 + 2 * h->nthr; }
@@ -182,16 +180,6 @@ static int64_t con_row_len(const ps_contrast* h) { return (int64_t)2 * h->nthr *
 static size_t con_val_bytes(const ps_contrast* h) { return (size_t)h->nslot * h->pitch * sizeof(double); }
 static size_t con_cnt_bytes(const ps_contrast* h) {
   return (size_t)h->nslot * con_planes(h) * h->pitch * sizeof(uint32_t);
-}
-
-static int con_after_last(ps_contrast* h, hipStream_t stream) {
-  if (h->ev_live) PS_HIP(hipStreamWaitEvent(stream, h->ev, 0));
-  return PS_OK;
-}
-static int con_mark_last(ps_contrast* h, hipStream_t stream) {
-  PS_HIP(hipEventRecord(h->ev, stream));
-  h->ev_live = true;
-  return PS_OK;
 }
 
 // room for `need` member rows: a doubling copies the rows so far on the handle's stream and synchronises once
@@ -205,7 +193,7 @@ static int con_reserve_rows(ps_contrast* h, int64_t need) {
   PS_HIP(hipMalloc((void**)&p, (size_t)cap * row_b));
   if (h->rows) {
     hipError_t e = hipSuccess;
-    if (h->ev_live) e = hipStreamWaitEvent(h->stream, h->ev, 0);
+    if (h->last.live) e = hipStreamWaitEvent(h->stream, h->last.ev, 0);
     if (e == hipSuccess && h->members > 0)
       e = hipMemcpyAsync(p, h->rows, (size_t)h->members * row_b, hipMemcpyDeviceToDevice, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
@@ -223,15 +211,12 @@ static int con_reserve_rows(ps_contrast* h, int64_t need) {
 extern "C" void ps_contrast_destroy(ps_contrast* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
-  if (h->ev_live) (void)hipEventSynchronize(h->ev);
+  h->last.sync();
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (auto& p : h->prof) {
-    (void)hipEventDestroy(p.first);
-    (void)hipEventDestroy(p.second);
-  }
+  h->prof.release();
   for (void* p : {(void*)h->mean, (void*)h->m2, (void*)h->cnt, (void*)h->rows})
     if (p) (void)hipFree(p);
-  if (h->ev) (void)hipEventDestroy(h->ev);
+  h->last.destroy();
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }
@@ -239,11 +224,11 @@ extern "C" void ps_contrast_destroy(ps_contrast* h) {
 extern "C" int ps_contrast_reset(ps_contrast* h) {
   if (!h) return ps_fail(PS_ERR_BAD_ARG, "contrast_reset: null handle");
   PS_HIP(hipSetDevice(h->device));
-  PS_TRY(con_after_last(h, h->stream));
+  PS_TRY(h->last.wait(h->stream));
   PS_HIP(hipMemsetAsync(h->mean, 0, con_val_bytes(h), h->stream));
   PS_HIP(hipMemsetAsync(h->m2, 0, con_val_bytes(h), h->stream));
   PS_HIP(hipMemsetAsync(h->cnt, 0, con_cnt_bytes(h), h->stream));
-  PS_TRY(con_mark_last(h, h->stream));
+  PS_TRY(h->last.mark(h->stream));
   h->W = 0;
   h->members = 0;
   h->weights.clear();
@@ -285,7 +270,7 @@ extern "C" int ps_contrast_create(int device, int N, int nslot, int nthr, const 
     return rc;
   };
   hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev, hipEventDisableTiming);
+  if (e == hipSuccess) e = h->last.create();
   if (e == hipSuccess) e = hipMalloc((void**)&h->mean, con_val_bytes(h));
   if (e == hipSuccess) e = hipMalloc((void**)&h->m2, con_val_bytes(h));
   if (e == hipSuccess) e = hipMalloc((void**)&h->cnt, con_cnt_bytes(h));
@@ -325,26 +310,16 @@ static int con_add_fields(ps_contrast* h, void* a, void* b, const PsFieldsOps& s
   hipStream_t stream = h->stream;
   PS_TRY(src.wait(a, stream));
   PS_TRY(src.wait(b, stream));
-  PS_TRY(con_after_last(h, stream));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  auto drop = [&](int rc) {   // a timing pair is kept only once both of its events are recorded
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    return rc;
-  };
-  if (h->prof_on) {
-    hipError_t e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipEventRecord(e0, stream);
-    if (e != hipSuccess) return drop(ps_fail(PS_ERR_HIP, "%s: timing events: %s", who, hipGetErrorString(e)));
-  }
+  PS_TRY(h->last.wait(stream));
+  hipEvent_t e1 = nullptr;
+  PS_TRY(h->prof.begin(0, stream, &e1));
   ConThr thr;
   for (int k = 0; k < PS_CON_MAX_THR; ++k) thr.t[k] = k < h->nthr ? h->thr[(size_t)k] : 0.0;
   uint32_t* row = nullptr;
   if (h->nthr) {   // the member's row: integer sums over the blocks, from zero
     row = h->rows + h->members * con_row_len(h);
     hipError_t e = hipMemsetAsync(row, 0, (size_t)con_row_len(h) * sizeof(uint32_t), stream);
-    if (e != hipSuccess) return drop(ps_fail(PS_ERR_HIP, "%s: clearing the member's row: %s", who, hipGetErrorString(e)));
+    if (e != hipSuccess) return ps_fail(PS_ERR_HIP, "%s: clearing the member's row: %s", who, hipGetErrorString(e));
   }
   const double Wn = (double)(h->W + weight);
   const int64_t nitem = h->ncell / 2 + (h->ncell & 1);
@@ -360,14 +335,10 @@ static int con_add_fields(ps_contrast* h, void* a, void* b, const PsFieldsOps& s
     hipLaunchKernelGGL(k_contrast_add, dim3(bx, n), dim3(PS_CON_THREADS), 0, stream, desc, h->mean, h->m2, h->cnt, row,
                        h->ncell, h->pitch, h->nslot, h->nthr, thr, (double)weight, Wn, weight);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return drop(ps_fail(PS_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e)));
+    if (e != hipSuccess) return ps_fail(PS_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
   }
-  if (e1) {
-    hipError_t e = hipEventRecord(e1, stream);
-    if (e != hipSuccess) return drop(ps_fail(PS_ERR_HIP, "%s: timing events: %s", who, hipGetErrorString(e)));
-    h->prof.push_back({e0, e1});
-  }
-  PS_TRY(con_mark_last(h, stream));
+  PS_TRY(h->prof.end(stream, e1));
+  PS_TRY(h->last.mark(stream));
   h->W += weight;
   h->members += 1;
   h->weights.push_back(weight);
@@ -391,8 +362,8 @@ extern "C" int ps_contrast_merge(ps_contrast* dst, ps_contrast* src) {
   if (src->members == 0) return PS_OK;
   PS_HIP(hipSetDevice(dst->device));
   PS_TRY(con_reserve_rows(dst, dst->members + src->members));
-  PS_TRY(con_after_last(dst, dst->stream));
-  PS_TRY(con_after_last(src, dst->stream));
+  PS_TRY(dst->last.wait(dst->stream));
+  PS_TRY(src->last.wait(dst->stream));
   if (dst->W == 0) {   // a copy: the merged handle is src bit for bit
     PS_HIP(hipMemcpyAsync(dst->mean, src->mean, con_val_bytes(dst), hipMemcpyDeviceToDevice, dst->stream));
     PS_HIP(hipMemcpyAsync(dst->m2, src->m2, con_val_bytes(dst), hipMemcpyDeviceToDevice, dst->stream));
@@ -408,8 +379,8 @@ extern "C" int ps_contrast_merge(ps_contrast* dst, ps_contrast* src) {
     PS_HIP(hipMemcpyAsync(dst->rows + dst->members * len, src->rows, (size_t)(src->members * len) * sizeof(uint32_t),
                           hipMemcpyDeviceToDevice, dst->stream));
   }
-  PS_TRY(con_mark_last(dst, dst->stream));
-  PS_TRY(con_mark_last(src, dst->stream));   // src is read until then
+  PS_TRY(dst->last.mark(dst->stream));
+  PS_TRY(src->last.mark(dst->stream));   // src is read until then
   dst->W += src->W;
   dst->members += src->members;
   dst->weights.insert(dst->weights.end(), src->weights.begin(), src->weights.end());
@@ -432,7 +403,7 @@ extern "C" int ps_contrast_fetch_counts(ps_contrast* h, int slot, int which, uin
                    which, con_planes(h));
   if (h->W == 0) return ps_fail(PS_ERR_STATE, "contrast_fetch_counts: nothing accumulated (W = 0)");
   PS_HIP(hipSetDevice(h->device));
-  PS_TRY(con_after_last(h, h->stream));
+  PS_TRY(h->last.wait(h->stream));
   const uint32_t* src = h->cnt + ((int64_t)slot * con_planes(h) + which) * h->pitch;
   PS_HIP(hipMemcpyAsync(out, src, (size_t)h->ncell * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
   PS_HIP(hipStreamSynchronize(h->stream));
@@ -455,7 +426,7 @@ extern "C" int ps_contrast_fetch(ps_contrast* h, int slot, int what, double* out
     return PS_OK;
   }
   PS_HIP(hipSetDevice(h->device));
-  PS_TRY(con_after_last(h, h->stream));
+  PS_TRY(h->last.wait(h->stream));
   const double* src = (what == 0 ? h->mean : h->m2) + (int64_t)slot * h->pitch;
   PS_HIP(hipMemcpyAsync(out, src, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   PS_HIP(hipStreamSynchronize(h->stream));
@@ -474,7 +445,7 @@ extern "C" int ps_contrast_fetch_coverage(ps_contrast* h, int64_t first, int64_t
     for (int64_t m = 0; m < count; ++m) weights[m] = h->weights[(size_t)(first + m)];
   if (!cells || count == 0 || h->nthr == 0) return PS_OK;
   PS_HIP(hipSetDevice(h->device));
-  PS_TRY(con_after_last(h, h->stream));
+  PS_TRY(h->last.wait(h->stream));
   const int64_t len = con_row_len(h);
   PS_HIP(hipMemcpyAsync(cells, h->rows + first * len, (size_t)(count * len) * sizeof(uint32_t), hipMemcpyDeviceToHost,
                         h->stream));
@@ -485,17 +456,7 @@ extern "C" int ps_contrast_fetch_coverage(ps_contrast* h, int64_t first, int64_t
 extern "C" int ps_contrast_prof(ps_contrast* h, int enable, double* total_ms, int64_t* launches) {
   if (!h) return ps_fail(PS_ERR_BAD_ARG, "contrast_prof: null handle");
   PS_HIP(hipSetDevice(h->device));
-  if (enable >= 0) h->prof_on = enable != 0;
-  if (total_ms || launches) {
-    double ms = 0.0;
-    for (auto& p : h->prof) {
-      PS_HIP(hipEventSynchronize(p.second));
-      float t = 0.f;
-      PS_HIP(hipEventElapsedTime(&t, p.first, p.second));
-      ms += t;
-    }
-    if (total_ms) *total_ms = ms;
-    if (launches) *launches = (int64_t)h->prof.size();
-  }
+  h->prof.set(enable);
+  if (total_ms || launches) PS_TRY(h->prof.totals(0, total_ms, launches));
   return PS_OK;
 }

@@ -238,10 +238,8 @@ struct ps_depend {
   int64_t members = 0;
   bool finalized = false;
   hipStream_t stream = nullptr;   // reset / merge / finalize / fetch, and the adds from fields
-  hipEvent_t ev = nullptr;        // the last operation, on whatever stream it ran
-  bool ev_live = false;
-  bool prof_on = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof;
+  PsLastOp last;                  // the last operation, on whatever stream it ran
+  PsProf prof;                    // channel 0: the adds
 };
 
 static int64_t dep_total(const ps_depend* a) { return (int64_t)a->nslot * a->pitch; }
@@ -252,27 +250,14 @@ static double dep_block_bytes(int nparam, int nbin, int nslot, int64_t pitch) {
   return ((double)(2 + nparam * nbin + nparam) * sizeof(double) + 1.0) * (double)nslot * (double)pitch;
 }
 
-static int dep_after_last(ps_depend* a, hipStream_t stream) {
-  if (a->ev_live) PS_HIP(hipStreamWaitEvent(stream, a->ev, 0));
-  return PS_OK;
-}
-static int dep_mark_last(ps_depend* a, hipStream_t stream) {
-  PS_HIP(hipEventRecord(a->ev, stream));
-  a->ev_live = true;
-  return PS_OK;
-}
-
 extern "C" void ps_depend_destroy(ps_depend* a) {
   if (!a) return;
   (void)hipSetDevice(a->device);
-  if (a->ev_live) (void)hipEventSynchronize(a->ev);
+  a->last.sync();
   if (a->stream) (void)hipStreamSynchronize(a->stream);
-  for (auto& p : a->prof) {
-    (void)hipEventDestroy(p.first);
-    (void)hipEventDestroy(p.second);
-  }
+  a->prof.release();
   if (a->block) (void)hipFree(a->block);
-  if (a->ev) (void)hipEventDestroy(a->ev);
+  a->last.destroy();
   if (a->stream) (void)hipStreamDestroy(a->stream);
   delete a;
 }
@@ -280,9 +265,9 @@ extern "C" void ps_depend_destroy(ps_depend* a) {
 extern "C" int ps_depend_reset(ps_depend* a) {
   if (!a) return ps_fail(PS_ERR_BAD_ARG, "depend_reset: null handle");
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(dep_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   PS_HIP(hipMemsetAsync(a->block, 0, (size_t)dep_block_bytes(a->nparam, a->nbin, a->nslot, a->pitch), a->stream));
-  PS_TRY(dep_mark_last(a, a->stream));
+  PS_TRY(a->last.mark(a->stream));
   a->W = 0;
   a->members = 0;
   a->finalized = false;
@@ -318,7 +303,7 @@ extern "C" int ps_depend_create(int device, int N, int nslot, int nparam, int nb
     return rc;
   };
   hipError_t e = hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&a->ev, hipEventDisableTiming);
+  if (e == hipSuccess) e = a->last.create();
   if (e == hipSuccess) e = hipMalloc((void**)&a->block, (size_t)need);
   if (e != hipSuccess)
     return fail(ps_fail(e == hipErrorOutOfMemory ? PS_ERR_OOM : PS_ERR_HIP, "depend_create: %s", hipGetErrorString(e)));
@@ -352,14 +337,9 @@ static int dep_check_add(ps_depend* a, const char* who, int nparam, const int32_
 static int dep_launch(ps_depend* a, const std::vector<DepSlot>& d, hipStream_t stream, double negval,
                       const int32_t* bin, uint32_t weight) {
   const int nslot = a->nslot;
-  PS_TRY(dep_after_last(a, stream));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (a->prof_on) {
-    PS_HIP(hipEventCreate(&e0));
-    PS_HIP(hipEventCreate(&e1));
-    a->prof.push_back({e0, e1});
-    PS_HIP(hipEventRecord(e0, stream));
-  }
+  PS_TRY(a->last.wait(stream));
+  hipEvent_t e1 = nullptr;
+  PS_TRY(a->prof.begin(0, stream, &e1));
   DepPlanes pl;
   for (int i = 0; i < PS_DEP_MAX_PARAM; ++i) pl.plane[i] = i < a->nparam ? i * a->nbin + bin[i] : 0;
   const double Wn = (double)(a->W + weight);
@@ -374,8 +354,8 @@ static int dep_launch(ps_depend* a, const std::vector<DepSlot>& d, hipStream_t s
                        a->S, a->ncell, a->pitch, dep_total(a), pl, negval, (double)weight, Wn);
     PS_HIP(hipGetLastError());
   }
-  if (e1) PS_HIP(hipEventRecord(e1, stream));
-  PS_TRY(dep_mark_last(a, stream));
+  PS_TRY(a->prof.end(stream, e1));
+  PS_TRY(a->last.mark(stream));
   a->W += weight;
   a->members += 1;
   a->finalized = false;
@@ -452,8 +432,8 @@ extern "C" int ps_depend_merge(ps_depend* dst, ps_depend* src) {
   dst->finalized = false;
   if (src->W == 0) return PS_OK;
   PS_HIP(hipSetDevice(dst->device));
-  PS_TRY(dep_after_last(dst, dst->stream));
-  PS_TRY(dep_after_last(src, dst->stream));
+  PS_TRY(dst->last.wait(dst->stream));
+  PS_TRY(src->last.wait(dst->stream));
   if (dst->W == 0) {   // a copy: the merged handle is src bit for bit
     PS_HIP(hipMemcpyAsync(dst->block, src->block, dep_acc_bytes(dst), hipMemcpyDeviceToDevice, dst->stream));
   } else {
@@ -461,8 +441,8 @@ extern "C" int ps_depend_merge(ps_depend* dst, ps_depend* src) {
                        src->m2, src->S, dep_total(dst), dep_planes(dst), (double)dst->W, (double)src->W);
     PS_HIP(hipGetLastError());
   }
-  PS_TRY(dep_mark_last(dst, dst->stream));
-  PS_TRY(dep_mark_last(src, dst->stream));   // src is read until then
+  PS_TRY(dst->last.mark(dst->stream));
+  PS_TRY(src->last.mark(dst->stream));   // src is read until then
   dst->W += src->W;
   dst->members += src->members;
   return PS_OK;
@@ -490,14 +470,14 @@ extern "C" int ps_depend_finalize(ps_depend* a, int nparam, int nbin, const doub
                      p, sum, (unsigned long long)a->W);
   }
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(dep_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   const int64_t total = dep_total(a);
   const int threads = 256;
   const int bx = (int)std::min<int64_t>((total / 2 + threads - 1) / threads, 8192);
   hipLaunchKernelGGL(k_dep_finalize, dim3(bx), dim3(threads), 0, a->stream, a->mean, a->m2, a->S, a->eta, a->dom,
                      total, a->nparam, a->nbin, f, (double)a->W);
   PS_HIP(hipGetLastError());
-  PS_TRY(dep_mark_last(a, a->stream));
+  PS_TRY(a->last.mark(a->stream));
   a->finalized = true;
   return PS_OK;
 }
@@ -516,7 +496,7 @@ extern "C" int ps_depend_fetch(ps_depend* a, int slot, int what, double* out) {
   if (fin && !a->finalized)
     return ps_fail(PS_ERR_STATE, "depend_fetch: quantity %d is not finalized since the last change", what);
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(dep_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   const double W = (double)a->W;
   const size_t n = (size_t)a->ncell;
   const int64_t off = (int64_t)slot * a->pitch;
@@ -548,17 +528,7 @@ extern "C" int ps_depend_info(ps_depend* a, double* total_weight, int64_t* membe
 extern "C" int ps_depend_prof(ps_depend* a, int enable, double* total_ms, int64_t* launches) {
   if (!a) return ps_fail(PS_ERR_BAD_ARG, "depend_prof: null handle");
   PS_HIP(hipSetDevice(a->device));
-  if (enable >= 0) a->prof_on = enable != 0;
-  if (total_ms || launches) {
-    double ms = 0.0;
-    for (auto& p : a->prof) {
-      PS_HIP(hipEventSynchronize(p.second));
-      float t = 0.f;
-      PS_HIP(hipEventElapsedTime(&t, p.first, p.second));
-      ms += t;
-    }
-    if (total_ms) *total_ms = ms;
-    if (launches) *launches = (int64_t)a->prof.size();
-  }
+  a->prof.set(enable);
+  if (total_ms || launches) PS_TRY(a->prof.totals(0, total_ms, launches));
   return PS_OK;
 }

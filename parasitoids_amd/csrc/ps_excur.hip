@@ -158,8 +158,6 @@ __global__ void k_excur_map(const uint32_t* __restrict__ cp, const uint32_t* __r
 
 }  // namespace
 
-typedef std::vector<std::pair<hipEvent_t, hipEvent_t>> ExcProfList;
-
 struct ps_excur {
   int device = 0, N = 0, nslot = 0, nthr = 0;
   std::vector<double> thr;
@@ -178,58 +176,13 @@ struct ps_excur {
   bool fin = false;                // h_hi / h_lo hold the bounds of the present members
   std::vector<uint32_t> h_hi, h_lo;   // [member][k][slot]
   hipStream_t stream = nullptr;    // reset / merge / finalize / maps / fetch / growth, and the adds of fields sources
-  hipEvent_t ev = nullptr;         // the last operation, on whatever stream it ran
-  bool ev_live = false;
-  bool prof_on = false;
-  ExcProfList prof[3];             // add / finalize / map
-  double prof_ms[3] = {0.0, 0.0, 0.0};   // launches already folded out of the lists above
-  int64_t prof_n[3] = {0, 0, 0};
+  PsLastOp last;                   // the last operation, on whatever stream it ran
+  PsProf prof;                     // channel 0: the adds, 1: the finalizes, 2: the maps
 };
 
 static int64_t exc_planes(const ps_excur* a) { return (int64_t)a->nthr * a->nslot; }
 static size_t exc_cnt_bytes(const ps_excur* a) { return (size_t)exc_planes(a) * a->pitch * sizeof(uint32_t); }
 static int64_t exc_member_words(const ps_excur* a) { return exc_planes(a) * (a->pitch >> 6); }
-
-static int exc_after_last(ps_excur* a, hipStream_t stream) {
-  if (a->ev_live) PS_HIP(hipStreamWaitEvent(stream, a->ev, 0));
-  return PS_OK;
-}
-static int exc_mark_last(ps_excur* a, hipStream_t stream) {
-  PS_HIP(hipEventRecord(a->ev, stream));
-  a->ev_live = true;
-  return PS_OK;
-}
-// the finished pairs of one list into the handle's totals, their events destroyed: a profiled handle holds at
-// most EXC_PROF_PENDING pairs per list however long it lives
-static const size_t EXC_PROF_PENDING = 256;
-static int exc_prof_fold(ps_excur* a, int which) {
-  ExcProfList& v = a->prof[which];
-  for (auto& p : v) {
-    PS_HIP(hipEventSynchronize(p.second));
-    float t = 0.f;
-    PS_HIP(hipEventElapsedTime(&t, p.first, p.second));
-    a->prof_ms[which] += t;
-    a->prof_n[which] += 1;
-  }
-  for (auto& p : v) {
-    (void)hipEventDestroy(p.first);
-    (void)hipEventDestroy(p.second);
-  }
-  v.clear();
-  return PS_OK;
-}
-static int exc_prof_begin(ps_excur* a, int which, hipStream_t stream, hipEvent_t* end) {
-  *end = nullptr;
-  if (!a->prof_on) return PS_OK;
-  if (a->prof[which].size() >= EXC_PROF_PENDING) PS_TRY(exc_prof_fold(a, which));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  PS_HIP(hipEventCreate(&e0));
-  PS_HIP(hipEventCreate(&e1));
-  a->prof[which].push_back({e0, e1});
-  PS_HIP(hipEventRecord(e0, stream));
-  *end = e1;
-  return PS_OK;
-}
 
 // a device block of `bytes`, checked against the free memory first (who / what: for the message)
 static int exc_alloc(void** p, size_t bytes, const char* who, const char* what) {
@@ -256,7 +209,7 @@ static int exc_reserve_members(ps_excur* a, int64_t need, bool exact, const char
   PS_TRY(exc_alloc((void**)&p, (size_t)cap * mem_b, who, "the member masks"));
   if (a->mask) {
     hipError_t e = hipSuccess;
-    if (a->ev_live) e = hipStreamWaitEvent(a->stream, a->ev, 0);
+    if (a->last.live) e = hipStreamWaitEvent(a->stream, a->last.ev, 0);
     if (e == hipSuccess && a->members > 0)
       e = hipMemcpyAsync(p, a->mask, (size_t)a->members * mem_b, hipMemcpyDeviceToDevice, a->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(a->stream);
@@ -291,16 +244,12 @@ static int exc_scratch(ps_excur* a, T** p, int64_t* cap, int64_t need, size_t el
 extern "C" void ps_excur_destroy(ps_excur* a) {
   if (!a) return;
   (void)hipSetDevice(a->device);
-  if (a->ev_live) (void)hipEventSynchronize(a->ev);
+  a->last.sync();
   if (a->stream) (void)hipStreamSynchronize(a->stream);
-  for (auto& v : a->prof)
-    for (auto& p : v) {
-      (void)hipEventDestroy(p.first);
-      (void)hipEventDestroy(p.second);
-    }
+  a->prof.release();
   for (void* p : {(void*)a->cnt, (void*)a->mask, (void*)a->bounds, (void*)a->table, (void*)a->map})
     if (p) (void)hipFree(p);
-  if (a->ev) (void)hipEventDestroy(a->ev);
+  a->last.destroy();
   if (a->stream) (void)hipStreamDestroy(a->stream);
   delete a;
 }
@@ -308,9 +257,9 @@ extern "C" void ps_excur_destroy(ps_excur* a) {
 extern "C" int ps_excur_reset(ps_excur* a) {
   if (!a) return ps_fail(PS_ERR_BAD_ARG, "excur_reset: null handle");
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(exc_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   PS_HIP(hipMemsetAsync(a->cnt, 0, exc_cnt_bytes(a), a->stream));
-  PS_TRY(exc_mark_last(a, a->stream));
+  PS_TRY(a->last.mark(a->stream));
   a->W = 0;
   a->members = 0;
   a->weights.clear();
@@ -354,7 +303,7 @@ extern "C" int ps_excur_create(int device, int N, int nslot, int nthr, const dou
     return rc;
   };
   hipError_t e = hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&a->ev, hipEventDisableTiming);
+  if (e == hipSuccess) e = a->last.create();
   if (e == hipSuccess) e = hipMalloc((void**)&a->cnt, exc_cnt_bytes(a));
   if (e == hipSuccess) e = hipMalloc((void**)&a->map, (size_t)pitch * sizeof(double));
   if (e != hipSuccess)
@@ -386,15 +335,15 @@ static int exc_launch(ps_excur* a, const ExcSlots& desc, hipStream_t stream, dou
   ExcThr thr;
   for (int k = 0; k < PS_EXC_MAX_THR; ++k) thr.t[k] = k < a->nthr ? a->thr[(size_t)k] : 0.0;
   PS_TRY(exc_reserve_members(a, a->members + 1, false, who));
-  PS_TRY(exc_after_last(a, stream));
+  PS_TRY(a->last.wait(stream));
   hipEvent_t e1 = nullptr;
-  PS_TRY(exc_prof_begin(a, 0, stream, &e1));
+  PS_TRY(a->prof.begin(0, stream, &e1));
   const unsigned nblk = (unsigned)((a->pitch + PS_EXC_THREADS - 1) / PS_EXC_THREADS);
   hipLaunchKernelGGL(k_excur_add, dim3(nblk), dim3(PS_EXC_THREADS), 0, stream, desc, thr, a->nslot, a->nthr, a->cnt,
                      a->mask + a->members * exc_member_words(a), a->ncell, a->pitch, negval, weight);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, stream));
-  PS_TRY(exc_mark_last(a, stream));
+  PS_TRY(a->prof.end(stream, e1));
+  PS_TRY(a->last.mark(stream));
   a->W += weight;
   a->members += 1;
   a->weights.push_back(weight);
@@ -469,16 +418,16 @@ extern "C" int ps_excur_merge(ps_excur* dst, ps_excur* src) {
   if (src->members == 0) return PS_OK;
   PS_HIP(hipSetDevice(dst->device));
   PS_TRY(exc_reserve_members(dst, dst->members + src->members, false, "excur_merge"));
-  PS_TRY(exc_after_last(dst, dst->stream));
-  PS_TRY(exc_after_last(src, dst->stream));
+  PS_TRY(dst->last.wait(dst->stream));
+  PS_TRY(src->last.wait(dst->stream));
   hipLaunchKernelGGL(k_excur_merge, dim3(2048), dim3(256), 0, dst->stream, dst->cnt, src->cnt,
                      exc_planes(dst) * dst->pitch);
   PS_HIP(hipGetLastError());
   const int64_t mw = exc_member_words(dst);
   PS_HIP(hipMemcpyAsync(dst->mask + dst->members * mw, src->mask, (size_t)(src->members * mw) * sizeof(uint64_t),
                         hipMemcpyDeviceToDevice, dst->stream));
-  PS_TRY(exc_mark_last(dst, dst->stream));
-  PS_TRY(exc_mark_last(src, dst->stream));   // src is read until then
+  PS_TRY(dst->last.mark(dst->stream));
+  PS_TRY(src->last.mark(dst->stream));   // src is read until then
   dst->W += src->W;
   dst->members += src->members;
   dst->weights.insert(dst->weights.end(), src->weights.begin(), src->weights.end());
@@ -506,9 +455,9 @@ extern "C" int ps_excur_finalize(ps_excur* a) {
   PS_TRY(exc_scratch(a, &a->bounds, &a->bounds_cap, a->members, (size_t)np * 2 * sizeof(uint32_t), "the member bounds"));
   uint32_t* hi = a->bounds;
   uint32_t* lo = a->bounds + a->bounds_cap * np;
-  PS_TRY(exc_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   hipEvent_t e1 = nullptr;
-  PS_TRY(exc_prof_begin(a, 1, a->stream, &e1));
+  PS_TRY(a->prof.begin(1, a->stream, &e1));
   PS_HIP(hipMemsetAsync(hi, 0, (size_t)n * sizeof(uint32_t), a->stream));
   PS_HIP(hipMemsetAsync(lo, 0xff, (size_t)n * sizeof(uint32_t), a->stream));
   const int64_t nword = a->pitch >> 6;
@@ -516,8 +465,8 @@ extern "C" int ps_excur_finalize(ps_excur* a) {
   hipLaunchKernelGGL(k_excur_bounds, dim3((unsigned)((nword + per_block - 1) / per_block), (unsigned)np),
                      dim3(PS_EXC_THREADS), 0, a->stream, a->cnt, a->mask, a->members, (int)np, a->pitch, hi, lo);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, a->stream));
-  PS_TRY(exc_mark_last(a, a->stream));
+  PS_TRY(a->prof.end(a->stream, e1));
+  PS_TRY(a->last.mark(a->stream));
   a->h_hi.resize((size_t)n);
   a->h_lo.resize((size_t)n);
   PS_HIP(hipMemcpyAsync(a->h_hi.data(), hi, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, a->stream));
@@ -566,15 +515,15 @@ extern "C" int ps_excur_map(ps_excur* a, int k, int slot, int what, double* out)
   }
   PS_HIP(hipSetDevice(a->device));
   PS_TRY(exc_scratch(a, &a->table, &a->table_cap, (int64_t)tab.size(), sizeof(uint32_t), "the step table"));
-  PS_TRY(exc_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   PS_HIP(hipMemcpyAsync(a->table, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice, a->stream));
   hipEvent_t e1 = nullptr;
-  PS_TRY(exc_prof_begin(a, 2, a->stream, &e1));
+  PS_TRY(a->prof.begin(2, a->stream, &e1));
   hipLaunchKernelGGL(k_excur_map, dim3((unsigned)((a->ncell + 255) / 256)), dim3(256), 0, a->stream,
                      a->cnt + p * a->pitch, a->table, a->table + M, (int)M, what, (uint32_t)a->W, a->ncell, a->map);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, a->stream));
-  PS_TRY(exc_mark_last(a, a->stream));
+  PS_TRY(a->prof.end(a->stream, e1));
+  PS_TRY(a->last.mark(a->stream));
   PS_HIP(hipMemcpyAsync(out, a->map, (size_t)a->ncell * sizeof(double), hipMemcpyDeviceToHost, a->stream));
   PS_HIP(hipStreamSynchronize(a->stream));   // tab is read until here
   return PS_OK;
@@ -584,7 +533,7 @@ extern "C" int ps_excur_fetch_counts(ps_excur* a, int k, int slot, uint32_t* out
   if (!a || !out) return ps_fail(PS_ERR_BAD_ARG, "excur_fetch_counts: bad arguments");
   PS_TRY(exc_check_plane(a, k, slot, "excur_fetch_counts"));
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(exc_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   PS_HIP(hipMemcpyAsync(out, a->cnt + ((int64_t)k * a->nslot + slot) * a->pitch, (size_t)a->ncell * sizeof(uint32_t),
                         hipMemcpyDeviceToHost, a->stream));
   PS_HIP(hipStreamSynchronize(a->stream));
@@ -597,7 +546,7 @@ extern "C" int ps_excur_fetch_mask(ps_excur* a, int64_t member, int k, int slot,
   if (member < 0 || member >= a->members)
     return ps_fail(PS_ERR_BAD_ARG, "excur_fetch_mask: member %lld of %lld", (long long)member, (long long)a->members);
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(exc_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   const int64_t nword = a->pitch >> 6;
   PS_HIP(hipMemcpyAsync(out, a->mask + member * exc_member_words(a) + ((int64_t)k * a->nslot + slot) * nword,
                         (size_t)nword * sizeof(uint64_t), hipMemcpyDeviceToHost, a->stream));
@@ -622,13 +571,9 @@ extern "C" int ps_excur_fetch_bounds(ps_excur* a, int k, int slot, uint32_t* hi,
 extern "C" int ps_excur_prof(ps_excur* a, int enable, double* ms, int64_t* launches) {
   if (!a) return ps_fail(PS_ERR_BAD_ARG, "excur_prof: null handle");
   PS_HIP(hipSetDevice(a->device));
-  if (enable >= 0) a->prof_on = enable != 0;
+  a->prof.set(enable);
   if (!ms && !launches) return PS_OK;
-  for (int k = 0; k < 3; ++k) {
-    PS_TRY(exc_prof_fold(a, k));
-    if (ms) ms[k] = a->prof_ms[k];
-    if (launches) launches[k] = a->prof_n[k];
-  }
+  for (int k = 0; k < 3; ++k) PS_TRY(a->prof.totals(k, ms ? ms + k : nullptr, launches ? launches + k : nullptr));
   return PS_OK;
 }
 
@@ -638,5 +583,5 @@ int ps_excur_view_internal(ps_excur* a, PsExcurView* out) {
   *out = PsExcurView{a->mask, a->cnt, a->weights.data(), a->pitch, a->members, a->N, a->nthr, a->nslot, a->device};
   return PS_OK;
 }
-int ps_excur_wait_internal(ps_excur* a, hipStream_t stream) { return exc_after_last(a, stream); }
-int ps_excur_mark_internal(ps_excur* a, hipStream_t stream) { return exc_mark_last(a, stream); }
+int ps_excur_wait_internal(ps_excur* a, hipStream_t stream) { return a->last.wait(stream); }
+int ps_excur_mark_internal(ps_excur* a, hipStream_t stream) { return a->last.mark(stream); }

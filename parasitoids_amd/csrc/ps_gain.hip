@@ -225,53 +225,19 @@ struct ps_gain {
   int64_t g_cap = 0;
   int64_t applies = 0, finishes = 0;
   hipStream_t stream = nullptr;    // fetch / gather / finish / apply of another fields source
-  hipEvent_t ev = nullptr;         // the last operation on Y or R, on whatever stream it ran
-  bool ev_live = false;
-  bool prof_on = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof;
-  double prof_ms = 0.0;            // apply launches already folded out of the list above
-  int64_t prof_n = 0;
+  PsLastOp last;                   // the last operation on Y or R, on whatever stream it ran
+  PsProf prof;                     // channel 0: the applies
 };
-
-static int gain_after_last(ps_gain* c, hipStream_t stream) {
-  if (c->ev_live) PS_HIP(hipStreamWaitEvent(stream, c->ev, 0));
-  return PS_OK;
-}
-static int gain_mark_last(ps_gain* c, hipStream_t stream) {
-  PS_HIP(hipEventRecord(c->ev, stream));
-  c->ev_live = true;
-  return PS_OK;
-}
-// the finished pairs into the handle's totals, their events destroyed (as ps_catch_prof)
-static const size_t GAIN_PROF_PENDING = 256;
-static int gain_prof_fold(ps_gain* c) {
-  for (auto& p : c->prof) {
-    PS_HIP(hipEventSynchronize(p.second));
-    float t = 0.f;
-    PS_HIP(hipEventElapsedTime(&t, p.first, p.second));
-    c->prof_ms += t;
-    c->prof_n += 1;
-  }
-  for (auto& p : c->prof) {
-    (void)hipEventDestroy(p.first);
-    (void)hipEventDestroy(p.second);
-  }
-  c->prof.clear();
-  return PS_OK;
-}
 
 extern "C" void ps_gain_destroy(ps_gain* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  if (c->ev_live) (void)hipEventSynchronize(c->ev);
+  c->last.sync();
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  for (auto& e : c->prof) {
-    (void)hipEventDestroy(e.first);
-    (void)hipEventDestroy(e.second);
-  }
+  c->prof.release();
   for (void* q : {(void*)c->Y, (void*)c->R, (void*)c->g_cell, (void*)c->g_out})
     if (q) (void)hipFree(q);
-  if (c->ev) (void)hipEventDestroy(c->ev);
+  c->last.destroy();
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
@@ -349,7 +315,7 @@ extern "C" int ps_gain_create(int device, int N, int nin, int ntrap, const int32
   const size_t y_b = (size_t)nplane * pitch * sizeof(double);
   const size_t r_b = (size_t)3 * ntrap * pitch * sizeof(double);
   hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev, hipEventDisableTiming);
+  if (e == hipSuccess) e = c->last.create();
   if (e == hipSuccess) e = hipMalloc((void**)&c->Y, y_b);
   if (e == hipSuccess) e = hipMalloc((void**)&c->R, r_b);
   if (e == hipSuccess) e = hipMemsetAsync(c->Y, 0, y_b, c->stream);
@@ -363,20 +329,14 @@ extern "C" int ps_gain_create(int device, int N, int nin, int ntrap, const int32
 
 // one launch over the resolved descriptors on `stream`, behind the handle's last operation
 static int gain_launch(ps_gain* c, const GainSlots& desc, hipStream_t stream, double negval) {
-  PS_TRY(gain_after_last(c, stream));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (c->prof_on) {
-    if (c->prof.size() >= GAIN_PROF_PENDING) PS_TRY(gain_prof_fold(c));
-    PS_HIP(hipEventCreate(&e0));
-    PS_HIP(hipEventCreate(&e1));
-    c->prof.push_back({e0, e1});
-    PS_HIP(hipEventRecord(e0, stream));
-  }
+  PS_TRY(c->last.wait(stream));
+  hipEvent_t e1 = nullptr;
+  PS_TRY(c->prof.begin(0, stream, &e1));
   hipLaunchKernelGGL(k_gain_apply, dim3(c->nblk), dim3(PS_GAIN_THREADS), 0, stream, desc, c->tab, c->Y, c->ncell,
                      c->pitch, negval);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, stream));
-  PS_TRY(gain_mark_last(c, stream));
+  PS_TRY(c->prof.end(stream, e1));
+  PS_TRY(c->last.mark(stream));
   c->applies += 1;
   return PS_OK;
 }
@@ -444,12 +404,12 @@ static int gain_finish_check(ps_gain* c, const PsMeanView& v, const char* who) {
   return PS_OK;
 }
 static int gain_finish_launch(ps_gain* c, const PsMeanView& v) {
-  PS_TRY(gain_after_last(c, c->stream));
+  PS_TRY(c->last.wait(c->stream));
   const unsigned nb = (unsigned)((c->ncell + PS_GAIN_THREADS - 1) / PS_GAIN_THREADS);
   hipLaunchKernelGGL(k_gain_finish, dim3(nb), dim3(PS_GAIN_THREADS), 0, c->stream, c->plan, v.mean, v.pitch, c->R,
                      c->ncell, c->pitch);
   PS_HIP(hipGetLastError());
-  PS_TRY(gain_mark_last(c, c->stream));
+  PS_TRY(c->last.mark(c->stream));
   c->finishes += 1;
   return PS_OK;
 }
@@ -479,7 +439,7 @@ extern "C" int ps_gain_finish_wsum(ps_gain* c, ps_wsum* a, int scenario) {
 
 static int gain_copy_out(ps_gain* c, const double* src, double* out) {
   PS_HIP(hipSetDevice(c->device));
-  PS_TRY(gain_after_last(c, c->stream));
+  PS_TRY(c->last.wait(c->stream));
   PS_HIP(hipMemcpyAsync(out, src, (size_t)c->ncell * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   PS_HIP(hipStreamSynchronize(c->stream));
   return PS_OK;
@@ -523,7 +483,7 @@ extern "C" int ps_gain_gather(ps_gain* c, int64_t n, const int32_t* rows, const 
     PS_HIP(hipMalloc((void**)&c->g_out, (size_t)n * c->nplane * sizeof(double)));
     c->g_cap = n;
   }
-  PS_TRY(gain_after_last(c, c->stream));
+  PS_TRY(c->last.wait(c->stream));
   PS_HIP(hipMemcpyAsync(c->g_cell, cell.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
   const int64_t total = n * c->nplane;
   hipLaunchKernelGGL(k_gain_gather, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, c->Y, c->pitch,
@@ -547,12 +507,8 @@ extern "C" int ps_gain_info(ps_gain* c, int* N, int* nin, int* ntrap, int* nplan
 extern "C" int ps_gain_prof(ps_gain* c, int enable, double* total_ms, int64_t* launches) {
   if (!c) return ps_fail(PS_ERR_BAD_ARG, "gain_prof: null handle");
   PS_HIP(hipSetDevice(c->device));
-  if (enable >= 0) c->prof_on = enable != 0;
-  if (total_ms || launches) {
-    PS_TRY(gain_prof_fold(c));
-    if (total_ms) *total_ms = c->prof_ms;
-    if (launches) *launches = c->prof_n;
-  }
+  c->prof.set(enable);
+  if (total_ms || launches) PS_TRY(c->prof.totals(0, total_ms, launches));
   return PS_OK;
 }
 
@@ -567,6 +523,6 @@ static int gain_view(void* h, PsProjectView* out) {
   out->device = c->device;
   return PS_OK;
 }
-static int gain_wait(void* h, hipStream_t stream) { return gain_after_last(static_cast<ps_gain*>(h), stream); }
-static int gain_mark(void* h, hipStream_t stream) { return gain_mark_last(static_cast<ps_gain*>(h), stream); }
+static int gain_wait(void* h, hipStream_t stream) { return static_cast<ps_gain*>(h)->last.wait(stream); }
+static int gain_mark(void* h, hipStream_t stream) { return static_cast<ps_gain*>(h)->last.mark(stream); }
 PsFieldsOps ps_gain_fields() { return PsFieldsOps{"information fields", gain_view, gain_wait, gain_mark}; }

@@ -180,50 +180,22 @@ struct ps_hist {
   uint64_t W = 0;
   int64_t members = 0;
   hipStream_t stream = nullptr;   // reset / merge / quantile / fetch
-  hipEvent_t ev = nullptr;        // the last operation, on whatever stream it ran
-  bool ev_live = false;
-  bool prof_on = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_add, prof_q;
+  PsLastOp last;                  // the last operation, on whatever stream it ran
+  PsProf prof;                    // channel 0: the adds, 1: the quantile calls
 };
 
 static size_t hist_cnt_bytes(const ps_hist* a) { return (size_t)a->nslot * a->nedge * a->pitch * sizeof(uint32_t); }
 static size_t hist_rng_bytes(const ps_hist* a) { return (size_t)a->nslot * a->pitch * sizeof(uint32_t); }
 
-static int hist_after_last(ps_hist* a, hipStream_t stream) {
-  if (a->ev_live) PS_HIP(hipStreamWaitEvent(stream, a->ev, 0));
-  return PS_OK;
-}
-static int hist_mark_last(ps_hist* a, hipStream_t stream) {
-  PS_HIP(hipEventRecord(a->ev, stream));
-  a->ev_live = true;
-  return PS_OK;
-}
-static int hist_prof_begin(ps_hist* a, std::vector<std::pair<hipEvent_t, hipEvent_t>>& v, hipStream_t stream,
-                           hipEvent_t* end) {
-  *end = nullptr;
-  if (!a->prof_on) return PS_OK;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  PS_HIP(hipEventCreate(&e0));
-  PS_HIP(hipEventCreate(&e1));
-  v.push_back({e0, e1});
-  PS_HIP(hipEventRecord(e0, stream));
-  *end = e1;
-  return PS_OK;
-}
-
 extern "C" void ps_hist_destroy(ps_hist* a) {
   if (!a) return;
   (void)hipSetDevice(a->device);
-  if (a->ev_live) (void)hipEventSynchronize(a->ev);
+  a->last.sync();
   if (a->stream) (void)hipStreamSynchronize(a->stream);
-  for (auto* v : {&a->prof_add, &a->prof_q})
-    for (auto& p : *v) {
-      (void)hipEventDestroy(p.first);
-      (void)hipEventDestroy(p.second);
-    }
+  a->prof.release();
   for (void* p : {(void*)a->cnt, (void*)a->rng, (void*)a->qval, (void*)a->qbin, (void*)a->d_edges})
     if (p) (void)hipFree(p);
-  if (a->ev) (void)hipEventDestroy(a->ev);
+  a->last.destroy();
   if (a->stream) (void)hipStreamDestroy(a->stream);
   delete a;
 }
@@ -231,10 +203,10 @@ extern "C" void ps_hist_destroy(ps_hist* a) {
 extern "C" int ps_hist_reset(ps_hist* a) {
   if (!a) return ps_fail(PS_ERR_BAD_ARG, "hist_reset: null histogram");
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(hist_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   PS_HIP(hipMemsetAsync(a->cnt, 0, hist_cnt_bytes(a), a->stream));
   PS_HIP(hipMemsetAsync(a->rng, 0, hist_rng_bytes(a), a->stream));
-  PS_TRY(hist_mark_last(a, a->stream));
+  PS_TRY(a->last.mark(a->stream));
   a->W = 0;
   a->members = 0;
   return PS_OK;
@@ -274,7 +246,7 @@ extern "C" int ps_hist_create(int device, int N, int nslot, int nedge, const dou
     return rc;
   };
   hipError_t e = hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&a->ev, hipEventDisableTiming);
+  if (e == hipSuccess) e = a->last.create();
   if (e == hipSuccess) e = hipMalloc((void**)&a->cnt, hist_cnt_bytes(a));
   if (e == hipSuccess) e = hipMalloc((void**)&a->rng, hist_rng_bytes(a));
   if (e == hipSuccess) e = hipMalloc((void**)&a->qval, (size_t)pitch * sizeof(double));
@@ -294,9 +266,9 @@ extern "C" int ps_hist_create(int device, int N, int nslot, int nedge, const dou
 static int hist_launch(ps_hist* a, const std::vector<HistSlot>& d, hipStream_t stream, double negval,
                        uint32_t weight) {
   const int nslot = a->nslot;
-  PS_TRY(hist_after_last(a, stream));
+  PS_TRY(a->last.wait(stream));
   hipEvent_t e1 = nullptr;
-  PS_TRY(hist_prof_begin(a, a->prof_add, stream, &e1));
+  PS_TRY(a->prof.begin(0, stream, &e1));
   const int64_t npair = a->ncell / 2 + 1;   // the pairs and the tail cell's thread
   const int threads = 256;
   const int bx = (int)((npair + threads - 1) / threads);
@@ -308,8 +280,8 @@ static int hist_launch(ps_hist* a, const std::vector<HistSlot>& d, hipStream_t s
                        a->ncell, a->pitch, negval, weight);
     PS_HIP(hipGetLastError());
   }
-  if (e1) PS_HIP(hipEventRecord(e1, stream));
-  PS_TRY(hist_mark_last(a, stream));
+  PS_TRY(a->prof.end(stream, e1));
+  PS_TRY(a->last.mark(stream));
   a->W += weight;
   a->members += 1;
   return PS_OK;
@@ -391,14 +363,14 @@ extern "C" int ps_hist_merge(ps_hist* dst, ps_hist* src) {
   if (dst->W + src->W > 0xffffffffull) return ps_fail(PS_ERR_BAD_ARG, "hist_merge: total weight would overflow");
   if (src->W == 0) return PS_OK;
   PS_HIP(hipSetDevice(dst->device));
-  PS_TRY(hist_after_last(dst, dst->stream));
-  PS_TRY(hist_after_last(src, dst->stream));
+  PS_TRY(dst->last.wait(dst->stream));
+  PS_TRY(src->last.wait(dst->stream));
   const int64_t nrng = (int64_t)dst->nslot * dst->pitch;
   hipLaunchKernelGGL(k_hist_merge, dim3(2048), dim3(256), 0, dst->stream, dst->cnt, src->cnt, nrng * dst->nedge,
                      dst->rng, src->rng, nrng);
   PS_HIP(hipGetLastError());
-  PS_TRY(hist_mark_last(dst, dst->stream));
-  PS_TRY(hist_mark_last(src, dst->stream));   // src is read until then
+  PS_TRY(dst->last.mark(dst->stream));
+  PS_TRY(src->last.mark(dst->stream));   // src is read until then
   dst->W += src->W;
   dst->members += src->members;
   return PS_OK;
@@ -421,12 +393,12 @@ static int hist_check(ps_hist* a, int slot, const char* who) {
 // sum of count_b over b >= b0 of one slot into qval (as uint32), on the handle's stream
 static int hist_tail(ps_hist* a, int slot, int b0) {
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(hist_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   const int64_t off = (int64_t)slot * a->pitch;
   hipLaunchKernelGGL(k_hist_tail, dim3((unsigned)((a->ncell + 255) / 256)), dim3(256), 0, a->stream,
                      a->cnt + off * a->nedge, a->rng + off, b0, a->ncell, a->pitch, (uint32_t*)a->qval);
   PS_HIP(hipGetLastError());
-  PS_TRY(hist_mark_last(a, a->stream));
+  PS_TRY(a->last.mark(a->stream));
   return PS_OK;
 }
 
@@ -435,16 +407,16 @@ extern "C" int ps_hist_quantile(ps_hist* a, int slot, double p, double* value, d
   if (!(p > 0.0 && p <= 1.0)) return ps_fail(PS_ERR_BAD_ARG, "hist_quantile: p = %g is not in (0, 1]", p);
   PS_TRY(hist_check(a, slot, "hist_quantile"));
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(hist_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   hipEvent_t e1 = nullptr;
-  PS_TRY(hist_prof_begin(a, a->prof_q, a->stream, &e1));
+  PS_TRY(a->prof.begin(1, a->stream, &e1));
   const int64_t off = (int64_t)slot * a->pitch;
   hipLaunchKernelGGL(k_hist_quantile, dim3((unsigned)((a->ncell + 255) / 256)), dim3(256), 0, a->stream,
                      a->cnt + off * a->nedge, a->rng + off, a->d_edges, a->nedge, a->ncell, a->pitch, p, (double)a->W,
                      (uint32_t)a->W, a->qval, a->qbin);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, a->stream));
-  PS_TRY(hist_mark_last(a, a->stream));
+  PS_TRY(a->prof.end(a->stream, e1));
+  PS_TRY(a->last.mark(a->stream));
   const size_t n = (size_t)a->ncell;
   if (value) PS_HIP(hipMemcpyAsync(value, a->qval, n * sizeof(double), hipMemcpyDeviceToHost, a->stream));
   std::vector<int32_t> b;
@@ -491,7 +463,7 @@ extern "C" int ps_hist_fetch_counts(ps_hist* a, int slot, int b, uint32_t* out) 
     return PS_OK;
   }
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(hist_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   const uint32_t* src = a->cnt + ((int64_t)slot * a->nedge + (b - 1)) * a->pitch;
   PS_HIP(hipMemcpyAsync(out, src, n * sizeof(uint32_t), hipMemcpyDeviceToHost, a->stream));
   PS_HIP(hipStreamSynchronize(a->stream));
@@ -502,21 +474,10 @@ extern "C" int ps_hist_prof(ps_hist* a, int enable, double* add_ms, int64_t* add
                             int64_t* q_launches) {
   if (!a) return ps_fail(PS_ERR_BAD_ARG, "hist_prof: null histogram");
   PS_HIP(hipSetDevice(a->device));
-  if (enable >= 0) a->prof_on = enable != 0;
+  a->prof.set(enable);
   double* ms_out[2] = {add_ms, q_ms};
   int64_t* n_out[2] = {add_launches, q_launches};
-  std::vector<std::pair<hipEvent_t, hipEvent_t>>* lists[2] = {&a->prof_add, &a->prof_q};
-  for (int k = 0; k < 2; ++k) {
-    if (!ms_out[k] && !n_out[k]) continue;
-    double ms = 0.0;
-    for (auto& p : *lists[k]) {
-      PS_HIP(hipEventSynchronize(p.second));
-      float t = 0.f;
-      PS_HIP(hipEventElapsedTime(&t, p.first, p.second));
-      ms += t;
-    }
-    if (ms_out[k]) *ms_out[k] = ms;
-    if (n_out[k]) *n_out[k] = (int64_t)lists[k]->size();
-  }
+  for (int k = 0; k < 2; ++k)
+    if (ms_out[k] || n_out[k]) PS_TRY(a->prof.totals(k, ms_out[k], n_out[k]));
   return PS_OK;
 }

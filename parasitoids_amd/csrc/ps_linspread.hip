@@ -134,49 +134,20 @@ struct ps_linspread {
   bool centered = false, finalized = false;
   std::vector<int64_t> adds;   // per parameter
   hipStream_t stream = nullptr;   // reset / finalize / fetch
-  hipEvent_t ev = nullptr;        // the last operation, on whatever stream it ran
-  bool ev_live = false;
-  bool prof_on = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_add, prof_fin;
+  PsLastOp last;                  // the last operation, on whatever stream it ran
+  PsProf prof;                    // channel 0: the adds, 1: the finalizes
 };
 
 static int64_t lin_total(const ps_linspread* a) { return (int64_t)a->nslot * a->pitch; }
 
-static int lin_after_last(ps_linspread* a, hipStream_t stream) {
-  if (a->ev_live) PS_HIP(hipStreamWaitEvent(stream, a->ev, 0));
-  return PS_OK;
-}
-static int lin_mark_last(ps_linspread* a, hipStream_t stream) {
-  PS_HIP(hipEventRecord(a->ev, stream));
-  a->ev_live = true;
-  return PS_OK;
-}
-
-static int lin_prof_begin(ps_linspread* a, std::vector<std::pair<hipEvent_t, hipEvent_t>>& v, hipStream_t stream,
-                          hipEvent_t* end) {
-  *end = nullptr;
-  if (!a->prof_on) return PS_OK;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  PS_HIP(hipEventCreate(&e0));
-  PS_HIP(hipEventCreate(&e1));
-  v.push_back({e0, e1});
-  PS_HIP(hipEventRecord(e0, stream));
-  *end = e1;
-  return PS_OK;
-}
-
 extern "C" void ps_linspread_destroy(ps_linspread* a) {
   if (!a) return;
   (void)hipSetDevice(a->device);
-  if (a->ev_live) (void)hipEventSynchronize(a->ev);
+  a->last.sync();
   if (a->stream) (void)hipStreamSynchronize(a->stream);
-  for (auto* v : {&a->prof_add, &a->prof_fin})
-    for (auto& p : *v) {
-      (void)hipEventDestroy(p.first);
-      (void)hipEventDestroy(p.second);
-    }
+  a->prof.release();
   if (a->block) (void)hipFree(a->block);
-  if (a->ev) (void)hipEventDestroy(a->ev);
+  a->last.destroy();
   if (a->stream) (void)hipStreamDestroy(a->stream);
   delete a;
 }
@@ -184,9 +155,9 @@ extern "C" void ps_linspread_destroy(ps_linspread* a) {
 extern "C" int ps_linspread_reset(ps_linspread* a) {
   if (!a) return ps_fail(PS_ERR_BAD_ARG, "linspread_reset: null handle");
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(lin_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   PS_HIP(hipMemsetAsync(a->block, 0, (size_t)(a->nparam + 2 + a->nthr) * lin_total(a) * sizeof(double), a->stream));
-  PS_TRY(lin_mark_last(a, a->stream));
+  PS_TRY(a->last.mark(a->stream));
   a->centered = a->finalized = false;
   a->adds.assign((size_t)a->nparam, 0);
   return PS_OK;
@@ -223,7 +194,7 @@ extern "C" int ps_linspread_create(int device, int N, int nslot, int nparam, int
     return rc;
   };
   hipError_t e = hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&a->ev, hipEventDisableTiming);
+  if (e == hipSuccess) e = a->last.create();
   if (e == hipSuccess) e = hipMalloc((void**)&a->block, (size_t)need);
   if (e != hipSuccess)
     return fail(ps_fail(e == hipErrorOutOfMemory ? PS_ERR_OOM : PS_ERR_HIP, "linspread_create: %s",
@@ -259,9 +230,9 @@ static int lin_record_pass(ps_linspread* a, ps_solver* s, int nslot, const int32
     d[i] = LinSlot{v.rec, v.stats, stat_scale[i], post_scale[i], i};
     stream = v.stream;
   }
-  PS_TRY(lin_after_last(a, stream));
+  PS_TRY(a->last.wait(stream));
   hipEvent_t e1 = nullptr;
-  if (!set) PS_TRY(lin_prof_begin(a, a->prof_add, stream, &e1));
+  if (!set) PS_TRY(a->prof.begin(0, stream, &e1));
   const int64_t npair = a->ncell / 2 + 1;
   const int threads = 256;
   const int bx = (int)std::min<int64_t>((npair + threads - 1) / threads, 4096);
@@ -273,8 +244,8 @@ static int lin_record_pass(ps_linspread* a, ps_solver* s, int nslot, const int32
                        coef, set);
     PS_HIP(hipGetLastError());
   }
-  if (e1) PS_HIP(hipEventRecord(e1, stream));
-  PS_TRY(lin_mark_last(a, stream));
+  PS_TRY(a->prof.end(stream, e1));
+  PS_TRY(a->last.mark(stream));
   return PS_OK;
 }
 
@@ -321,17 +292,17 @@ extern "C" int ps_linspread_finalize(ps_linspread* a, int nparam, int rank, cons
   LinThr thr;
   for (int k = 0; k < PS_LIN_MAX_THR; ++k) thr.t[k] = a->thr[k];
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(lin_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   hipEvent_t e1 = nullptr;
-  PS_TRY(lin_prof_begin(a, a->prof_fin, a->stream, &e1));
+  PS_TRY(a->prof.begin(1, a->stream, &e1));
   const int64_t total = lin_total(a);
   const int threads = 256;
   const int bx = (int)std::min<int64_t>((total / 2 + threads - 1) / threads, 8192);
   hipLaunchKernelGGL(k_linspread_finalize, dim3(bx), dim3(threads), 0, a->stream, a->center, a->J, a->var, a->exc,
                      total, a->nparam, rank, f, a->nthr, thr);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, a->stream));
-  PS_TRY(lin_mark_last(a, a->stream));
+  PS_TRY(a->prof.end(a->stream, e1));
+  PS_TRY(a->last.mark(a->stream));
   a->finalized = true;
   return PS_OK;
 }
@@ -354,7 +325,7 @@ extern "C" int ps_linspread_fetch(ps_linspread* a, int slot, int what, double* o
                    what, 1 + a->nthr, 15 + a->nparam);
   }
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(lin_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   PS_HIP(hipMemcpyAsync(out, src + (int64_t)slot * a->pitch, (size_t)a->ncell * sizeof(double), hipMemcpyDeviceToHost,
                         a->stream));
   PS_HIP(hipStreamSynchronize(a->stream));
@@ -370,25 +341,12 @@ extern "C" int ps_linspread_info(ps_linspread* a, int* centered, int* finalized,
   return PS_OK;
 }
 
-static int lin_prof_sum(std::vector<std::pair<hipEvent_t, hipEvent_t>>& v, double* ms, int64_t* n) {
-  double t = 0.0;
-  for (auto& p : v) {
-    PS_HIP(hipEventSynchronize(p.second));
-    float x = 0.f;
-    PS_HIP(hipEventElapsedTime(&x, p.first, p.second));
-    t += x;
-  }
-  if (ms) *ms = t;
-  if (n) *n = (int64_t)v.size();
-  return PS_OK;
-}
-
 extern "C" int ps_linspread_prof(ps_linspread* a, int enable, double* add_ms, int64_t* add_launches, double* fin_ms,
                                  int64_t* fin_launches) {
   if (!a) return ps_fail(PS_ERR_BAD_ARG, "linspread_prof: null handle");
   PS_HIP(hipSetDevice(a->device));
-  if (enable >= 0) a->prof_on = enable != 0;
-  if (add_ms || add_launches) PS_TRY(lin_prof_sum(a->prof_add, add_ms, add_launches));
-  if (fin_ms || fin_launches) PS_TRY(lin_prof_sum(a->prof_fin, fin_ms, fin_launches));
+  a->prof.set(enable);
+  if (add_ms || add_launches) PS_TRY(a->prof.totals(0, add_ms, add_launches));
+  if (fin_ms || fin_launches) PS_TRY(a->prof.totals(1, fin_ms, fin_launches));
   return PS_OK;
 }

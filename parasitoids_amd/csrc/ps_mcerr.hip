@@ -205,39 +205,23 @@ struct ps_mcerr {
   uint64_t W = 0;                 // every weight added: b B + open + discarded
   int64_t members = 0;
   hipStream_t stream = nullptr;   // reset / finish / merge / fetch / rhat
-  hipEvent_t ev = nullptr;        // the last operation, on whatever stream it ran
-  bool ev_live = false;
-  bool prof_on = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_add, prof_close;
+  PsLastOp last;                  // the last operation, on whatever stream it ran
+  PsProf prof;                    // channel 0: the adds, 1: the batch closes
 };
 
 static size_t mce_plane(const ps_mcerr* h) { return (size_t)h->nslot * h->pitch; }
 static double* mce_val(const ps_mcerr* h, int which) { return h->val + (size_t)which * mce_plane(h); }
 enum { MCE_BMEAN = 0, MCE_BM2 = 1, MCE_GMEAN = 2, MCE_GM2 = 3, MCE_WM2 = 4 };
 
-static int mce_after_last(ps_mcerr* h, hipStream_t stream) {
-  if (h->ev_live) PS_HIP(hipStreamWaitEvent(stream, h->ev, 0));
-  return PS_OK;
-}
-static int mce_mark_last(ps_mcerr* h, hipStream_t stream) {
-  PS_HIP(hipEventRecord(h->ev, stream));
-  h->ev_live = true;
-  return PS_OK;
-}
-
 extern "C" void ps_mcerr_destroy(ps_mcerr* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
-  if (h->ev_live) (void)hipEventSynchronize(h->ev);
+  h->last.sync();
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (auto* v : {&h->prof_add, &h->prof_close})
-    for (auto& p : *v) {
-      (void)hipEventDestroy(p.first);
-      (void)hipEventDestroy(p.second);
-    }
+  h->prof.release();
   for (void* p : {(void*)h->val, (void*)h->bcnt, (void*)h->s1, (void*)h->s2, (void*)h->scratch})
     if (p) (void)hipFree(p);
-  if (h->ev) (void)hipEventDestroy(h->ev);
+  h->last.destroy();
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }
@@ -252,14 +236,14 @@ static int mce_zero_batch(ps_mcerr* h, hipStream_t stream) {
 extern "C" int ps_mcerr_reset(ps_mcerr* h) {
   if (!h) return ps_fail(PS_ERR_BAD_ARG, "mcerr_reset: null handle");
   PS_HIP(hipSetDevice(h->device));
-  PS_TRY(mce_after_last(h, h->stream));
+  PS_TRY(h->last.wait(h->stream));
   PS_HIP(hipMemsetAsync(h->val, 0, 5 * mce_plane(h) * sizeof(double), h->stream));
   if (h->nthr) {
     PS_HIP(hipMemsetAsync(h->bcnt, 0, mce_plane(h) * h->nthr * sizeof(uint32_t), h->stream));
     PS_HIP(hipMemsetAsync(h->s1, 0, mce_plane(h) * h->nthr * sizeof(uint32_t), h->stream));
     PS_HIP(hipMemsetAsync(h->s2, 0, mce_plane(h) * h->nthr * sizeof(uint64_t), h->stream));
   }
-  PS_TRY(mce_mark_last(h, h->stream));
+  PS_TRY(h->last.mark(h->stream));
   h->B = h->open = h->discarded = h->W = 0;
   h->members = 0;
   return PS_OK;
@@ -302,7 +286,7 @@ extern "C" int ps_mcerr_create(int device, int N, int nslot, int nthr, const dou
     return rc;
   };
   hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev, hipEventDisableTiming);
+  if (e == hipSuccess) e = h->last.create();
   if (e == hipSuccess) e = hipMalloc((void**)&h->val, 5 * mce_plane(h) * sizeof(double));
   if (e == hipSuccess && nthr) e = hipMalloc((void**)&h->bcnt, mce_plane(h) * nthr * sizeof(uint32_t));
   if (e == hipSuccess && nthr) e = hipMalloc((void**)&h->s1, mce_plane(h) * nthr * sizeof(uint32_t));
@@ -315,31 +299,20 @@ extern "C" int ps_mcerr_create(int device, int N, int nslot, int nthr, const dou
   return PS_OK;
 }
 
-// a timing pair around what `body` enqueues on `stream`, kept in `into` (nothing without profiling)
+// a timing pair on `channel` around what `body` enqueues on `stream` (nothing without profiling)
 template <typename F>
-static int mce_timed(ps_mcerr* h, std::vector<std::pair<hipEvent_t, hipEvent_t>>& into, hipStream_t stream, F body) {
-  if (!h->prof_on) return body();
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  PS_HIP(hipEventCreate(&e0));
-  hipError_t e = hipEventCreate(&e1);
-  if (e == hipSuccess) e = hipEventRecord(e0, stream);
-  int rc = e == hipSuccess ? body() : ps_fail(PS_ERR_HIP, "mcerr: timing events: %s", hipGetErrorString(e));
-  if (rc == PS_OK && (e = hipEventRecord(e1, stream)) != hipSuccess)
-    rc = ps_fail(PS_ERR_HIP, "mcerr: timing events: %s", hipGetErrorString(e));
-  if (rc != PS_OK) {   // a pair is kept only once both of its events are recorded
-    (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    return rc;
-  }
-  into.push_back({e0, e1});
-  return PS_OK;
+static int mce_timed(ps_mcerr* h, int channel, hipStream_t stream, F body) {
+  hipEvent_t e1 = nullptr;
+  PS_TRY(h->prof.begin(channel, stream, &e1));
+  PS_TRY(body());
+  return h->prof.end(stream, e1);
 }
 
 // One member from the slot descriptors d (one per slot), enqueued on `stream`: the weight is split at the batch
 // boundaries -- the open batch is filled and closed, then whole batches of b, then the rest -- and every piece is
 // one launch of the add kernel on the same source.
 static int mce_launch(ps_mcerr* h, const std::vector<MceSlot>& d, hipStream_t stream, double negval, uint32_t weight) {
-  PS_TRY(mce_after_last(h, stream));
+  PS_TRY(h->last.wait(stream));
   MceThr thr;
   for (int k = 0; k < PS_MCE_MAX_THR; ++k) thr.t[k] = k < h->nthr ? h->thr[(size_t)k] : 0.0;
   const int64_t npair = h->ncell / 2 + 1;
@@ -352,7 +325,7 @@ static int mce_launch(ps_mcerr* h, const std::vector<MceSlot>& d, hipStream_t st
   while (left > 0 && rc == PS_OK) {
     const uint32_t piece = (uint32_t)std::min<uint64_t>(left, h->b - h->open);
     const double Wn = (double)(h->open + piece);
-    rc = mce_timed(h, h->prof_add, stream, [&]() {
+    rc = mce_timed(h, 0, stream, [&]() {
       for (int c0 = 0; c0 < h->nslot; c0 += PS_MCE_CHUNK) {
         const int n = std::min(PS_MCE_CHUNK, h->nslot - c0);
         MceSlots desc;
@@ -370,7 +343,7 @@ static int mce_launch(ps_mcerr* h, const std::vector<MceSlot>& d, hipStream_t st
     h->W += piece;
     left -= piece;
     if (h->open == h->b) {
-      rc = mce_timed(h, h->prof_close, stream, [&]() {
+      rc = mce_timed(h, 1, stream, [&]() {
         hipLaunchKernelGGL(k_mcerr_close, dim3(cbx), dim3(PS_MCE_THREADS), 0, stream, mce_val(h, MCE_BMEAN),
                            mce_val(h, MCE_BM2), mce_val(h, MCE_GMEAN), mce_val(h, MCE_GM2), mce_val(h, MCE_WM2), h->bcnt,
                            h->s1, h->s2, nval, ncnt, (double)(h->B + 1));
@@ -382,7 +355,7 @@ static int mce_launch(ps_mcerr* h, const std::vector<MceSlot>& d, hipStream_t st
       h->open = 0;
     }
   }
-  PS_TRY(mce_mark_last(h, stream));
+  PS_TRY(h->last.mark(stream));
   if (rc == PS_OK) h->members += 1;
   return rc;
 }
@@ -462,9 +435,9 @@ extern "C" int ps_mcerr_finish(ps_mcerr* h) {
   if (!h) return ps_fail(PS_ERR_BAD_ARG, "mcerr_finish: null handle");
   if (h->open == 0) return PS_OK;
   PS_HIP(hipSetDevice(h->device));
-  PS_TRY(mce_after_last(h, h->stream));
+  PS_TRY(h->last.wait(h->stream));
   PS_TRY(mce_zero_batch(h, h->stream));
-  PS_TRY(mce_mark_last(h, h->stream));
+  PS_TRY(h->last.mark(h->stream));
   h->discarded += h->open;
   h->open = 0;
   return PS_OK;
@@ -482,8 +455,8 @@ extern "C" int ps_mcerr_merge(ps_mcerr* dst, ps_mcerr* src) {
                    (unsigned long long)(dst->open ? dst->open : src->open));
   if (src->B > 0) {
     PS_HIP(hipSetDevice(dst->device));
-    PS_TRY(mce_after_last(dst, dst->stream));
-    PS_TRY(mce_after_last(src, dst->stream));
+    PS_TRY(dst->last.wait(dst->stream));
+    PS_TRY(src->last.wait(dst->stream));
     const size_t nval = mce_plane(dst), ncnt = nval * dst->nthr;
     if (dst->B == 0) {   // a copy: the merged handle is src bit for bit (the batch planes of both are zero)
       PS_HIP(hipMemcpyAsync(dst->val, src->val, 5 * nval * sizeof(double), hipMemcpyDeviceToDevice, dst->stream));
@@ -498,8 +471,8 @@ extern "C" int ps_mcerr_merge(ps_mcerr* dst, ps_mcerr* src) {
                          (double)dst->B, (double)src->B);
       PS_HIP(hipGetLastError());
     }
-    PS_TRY(mce_mark_last(dst, dst->stream));
-    PS_TRY(mce_mark_last(src, dst->stream));   // src is read until then
+    PS_TRY(dst->last.mark(dst->stream));
+    PS_TRY(src->last.mark(dst->stream));   // src is read until then
   }
   dst->B += src->B;
   dst->W += src->W;
@@ -531,7 +504,7 @@ extern "C" int ps_mcerr_fetch(ps_mcerr* h, int slot, int what, double* out) {
   if (what < 0 || what > 2) return ps_fail(PS_ERR_BAD_ARG, "mcerr_fetch: quantity %d (0 gmean, 1 gM2, 2 wM2)", what);
   if (h->B < 2) return ps_fail(PS_ERR_STATE, "mcerr_fetch: %llu closed batches, 2 needed", (unsigned long long)h->B);
   PS_HIP(hipSetDevice(h->device));
-  PS_TRY(mce_after_last(h, h->stream));
+  PS_TRY(h->last.wait(h->stream));
   const double* src = mce_val(h, MCE_GMEAN + what) + (int64_t)slot * h->pitch;
   PS_HIP(hipMemcpyAsync(out, src, (size_t)h->ncell * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   PS_HIP(hipStreamSynchronize(h->stream));
@@ -545,7 +518,7 @@ extern "C" int ps_mcerr_fetch_counts(ps_mcerr* h, int slot, int k, uint32_t* s1,
   if (h->B < 2)
     return ps_fail(PS_ERR_STATE, "mcerr_fetch_counts: %llu closed batches, 2 needed", (unsigned long long)h->B);
   PS_HIP(hipSetDevice(h->device));
-  PS_TRY(mce_after_last(h, h->stream));
+  PS_TRY(h->last.wait(h->stream));
   const int64_t off = ((int64_t)slot * h->nthr + k) * h->pitch;
   if (s1) PS_HIP(hipMemcpyAsync(s1, h->s1 + off, (size_t)h->ncell * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
   if (s2) PS_HIP(hipMemcpyAsync(s2, h->s2 + off, (size_t)h->ncell * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
@@ -587,13 +560,13 @@ extern "C" int ps_mcerr_rhat(ps_mcerr* const* handles, int nh, int slot, double*
     if (j < nh) nsum += seq.n[j];
   }
   hipStream_t stream = h0->stream;
-  for (int j = 0; j < nh; ++j) PS_TRY(mce_after_last(handles[j], stream));
+  for (int j = 0; j < nh; ++j) PS_TRY(handles[j]->last.wait(stream));
   const int bx = (int)std::min<int64_t>((h0->ncell + PS_MCE_THREADS - 1) / PS_MCE_THREADS, PS_MCE_MAX_BLOCKS);
   hipLaunchKernelGGL(k_mcerr_rhat, dim3(bx), dim3(PS_MCE_THREADS), 0, stream, seq, nh, (double)h0->b, nsum / (double)nh,
                      h0->ncell, h0->scratch);
   PS_HIP(hipGetLastError());
   PS_HIP(hipMemcpyAsync(out, h0->scratch, (size_t)h0->ncell * sizeof(double), hipMemcpyDeviceToHost, stream));
-  for (int j = 0; j < nh; ++j) PS_TRY(mce_mark_last(handles[j], stream));   // every sequence is read until then
+  for (int j = 0; j < nh; ++j) PS_TRY(handles[j]->last.mark(stream));   // every sequence is read until then
   PS_HIP(hipStreamSynchronize(stream));
   return PS_OK;
 }
@@ -602,20 +575,8 @@ extern "C" int ps_mcerr_prof(ps_mcerr* h, int enable, double* add_ms, int64_t* a
                              int64_t* close_launches) {
   if (!h) return ps_fail(PS_ERR_BAD_ARG, "mcerr_prof: null handle");
   PS_HIP(hipSetDevice(h->device));
-  if (enable >= 0) h->prof_on = enable != 0;
-  auto total = [](std::vector<std::pair<hipEvent_t, hipEvent_t>>& v, double* ms_out, int64_t* n_out) {
-    if (!ms_out && !n_out) return (int)PS_OK;
-    double ms = 0.0;
-    for (auto& p : v) {
-      PS_HIP(hipEventSynchronize(p.second));
-      float t = 0.f;
-      PS_HIP(hipEventElapsedTime(&t, p.first, p.second));
-      ms += t;
-    }
-    if (ms_out) *ms_out = ms;
-    if (n_out) *n_out = (int64_t)v.size();
-    return (int)PS_OK;
-  };
-  PS_TRY(total(h->prof_add, add_ms, add_launches));
-  return total(h->prof_close, close_ms, close_launches);
+  h->prof.set(enable);
+  if (add_ms || add_launches) PS_TRY(h->prof.totals(0, add_ms, add_launches));
+  if (close_ms || close_launches) PS_TRY(h->prof.totals(1, close_ms, close_launches));
+  return PS_OK;
 }

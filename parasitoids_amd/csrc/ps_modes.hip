@@ -218,8 +218,6 @@ __global__ void __launch_bounds__(PS_MOD_THREADS) k_modes_combine(const double* 
 
 }  // namespace
 
-typedef std::vector<std::pair<hipEvent_t, hipEvent_t>> ModProfList;
-
 struct ps_modes {
   int device = 0, N = 0, nslot = 0, transform = 0;
   int64_t ncell = 0, pitch = 0;
@@ -240,58 +238,15 @@ struct ps_modes {
   std::vector<uint32_t> weights;
   std::vector<double> host;     // staging of add_host and of the weights and coefficients
   hipStream_t stream = nullptr;
-  hipEvent_t ev = nullptr;
-  bool ev_live = false;
-  bool prof_on = false;
-  ModProfList prof[4];          // add / mean / table / combine
-  double prof_ms[4] = {0.0, 0.0, 0.0, 0.0};
-  int64_t prof_n[4] = {0, 0, 0, 0};
+  PsLastOp last;
+  PsProf prof;                  // channel 0: the adds, 1: the means, 2: the tables, 3: the combines
 };
 
 static int64_t mod_member_doubles(const ps_modes* a) { return (int64_t)a->nslot * a->pitch; }
 
-static int mod_after_last(ps_modes* a, hipStream_t stream) {
-  if (a->ev_live) PS_HIP(hipStreamWaitEvent(stream, a->ev, 0));
-  return PS_OK;
-}
-static int mod_mark_last(ps_modes* a, hipStream_t stream) {
-  PS_HIP(hipEventRecord(a->ev, stream));
-  a->ev_live = true;
-  return PS_OK;
-}
 static void mod_changed(ps_modes* a) {
   for (bool& v : a->mu_valid) v = false;
   a->wdev_valid = false;
-}
-
-static const size_t MOD_PROF_PENDING = 256;
-static int mod_prof_fold(ps_modes* a, int which) {
-  ModProfList& v = a->prof[which];
-  for (auto& p : v) {
-    PS_HIP(hipEventSynchronize(p.second));
-    float t = 0.f;
-    PS_HIP(hipEventElapsedTime(&t, p.first, p.second));
-    a->prof_ms[which] += t;
-    a->prof_n[which] += 1;
-  }
-  for (auto& p : v) {
-    (void)hipEventDestroy(p.first);
-    (void)hipEventDestroy(p.second);
-  }
-  v.clear();
-  return PS_OK;
-}
-static int mod_prof_begin(ps_modes* a, int which, hipStream_t stream, hipEvent_t* end) {
-  *end = nullptr;
-  if (!a->prof_on) return PS_OK;
-  if (a->prof[which].size() >= MOD_PROF_PENDING) PS_TRY(mod_prof_fold(a, which));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  PS_HIP(hipEventCreate(&e0));
-  PS_HIP(hipEventCreate(&e1));
-  a->prof[which].push_back({e0, e1});
-  PS_HIP(hipEventRecord(e0, stream));
-  *end = e1;
-  return PS_OK;
 }
 
 // a device block of `bytes`, checked against the free memory first (who / what: for the message)
@@ -318,7 +273,7 @@ static int mod_reserve_members(ps_modes* a, int64_t need, bool exact, const char
   PS_TRY(mod_alloc((void**)&p, (double)cap * mem_b, who, "the members' fields"));
   if (a->X) {
     hipError_t e = hipSuccess;
-    if (a->ev_live) e = hipStreamWaitEvent(a->stream, a->ev, 0);
+    if (a->last.live) e = hipStreamWaitEvent(a->stream, a->last.ev, 0);
     if (e == hipSuccess && a->members > 0)
       e = hipMemcpyAsync(p, a->X, (size_t)((double)a->members * mem_b), hipMemcpyDeviceToDevice, a->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(a->stream);
@@ -350,16 +305,12 @@ static int mod_scratch(ps_modes* a, double** p, int64_t* cap, int64_t need, cons
 extern "C" void ps_modes_destroy(ps_modes* a) {
   if (!a) return;
   (void)hipSetDevice(a->device);
-  if (a->ev_live) (void)hipEventSynchronize(a->ev);
+  a->last.sync();
   if (a->stream) (void)hipStreamSynchronize(a->stream);
-  for (auto& v : a->prof)
-    for (auto& p : v) {
-      (void)hipEventDestroy(p.first);
-      (void)hipEventDestroy(p.second);
-    }
+  a->prof.release();
   for (void* p : {(void*)a->X, (void*)a->mu, (void*)a->wdev, (void*)a->part, (void*)a->maps, (void*)a->win})
     if (p) (void)hipFree(p);
-  if (a->ev) (void)hipEventDestroy(a->ev);
+  a->last.destroy();
   if (a->stream) (void)hipStreamDestroy(a->stream);
   delete a;
 }
@@ -399,7 +350,7 @@ extern "C" int ps_modes_create(int device, int N, int nslot, int transform, ps_m
   a->ncell = ncell;
   a->pitch = pitch;
   hipError_t e = hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&a->ev, hipEventDisableTiming);
+  if (e == hipSuccess) e = a->last.create();
   if (e == hipSuccess) e = hipMalloc((void**)&a->mu, (size_t)nslot * pitch * sizeof(double));
   if (e == hipSuccess) e = hipMalloc((void**)&a->win, 2 * sizeof(uint32_t));
   if (e != hipSuccess) {
@@ -441,16 +392,16 @@ static void mod_added(ps_modes* a, uint32_t weight) {
 static int mod_launch(ps_modes* a, const ModSlots& desc, hipStream_t stream, double negval, uint32_t weight,
                       const char* who) {
   PS_TRY(mod_reserve_members(a, a->members + 1, false, who));
-  PS_TRY(mod_after_last(a, stream));
+  PS_TRY(a->last.wait(stream));
   hipEvent_t e1 = nullptr;
-  PS_TRY(mod_prof_begin(a, 0, stream, &e1));
+  PS_TRY(a->prof.begin(0, stream, &e1));
   const unsigned nblk = (unsigned)((a->pitch + PS_MOD_THREADS - 1) / PS_MOD_THREADS);
   hipLaunchKernelGGL(k_modes_add, dim3(nblk), dim3(PS_MOD_THREADS), 0, stream, desc, a->nslot,
                      a->X + a->members * mod_member_doubles(a), a->ncell, a->pitch, negval,
                      a->transform == PS_MODES_SQRT ? 1 : 0);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, stream));
-  PS_TRY(mod_mark_last(a, stream));
+  PS_TRY(a->prof.end(stream, e1));
+  PS_TRY(a->last.mark(stream));
   mod_added(a, weight);
   return PS_OK;
 }
@@ -526,10 +477,10 @@ extern "C" int ps_modes_add_host(ps_modes* a, const double* fields, uint32_t wei
       const double v = fields[(int64_t)s * a->ncell + i];
       a->host[(size_t)(s * a->pitch + i)] = a->transform == PS_MODES_SQRT ? sqrt(v) : v;
     }
-  PS_TRY(mod_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   PS_HIP(hipMemcpyAsync(a->X + a->members * mod_member_doubles(a), a->host.data(), a->host.size() * sizeof(double),
                         hipMemcpyHostToDevice, a->stream));
-  PS_TRY(mod_mark_last(a, a->stream));
+  PS_TRY(a->last.mark(a->stream));
   PS_HIP(hipStreamSynchronize(a->stream));   // the staging block is read until here
   mod_added(a, weight);
   return PS_OK;
@@ -543,13 +494,13 @@ extern "C" int ps_modes_merge(ps_modes* dst, ps_modes* src) {
   if (src->members == 0) return PS_OK;
   PS_HIP(hipSetDevice(dst->device));
   PS_TRY(mod_reserve_members(dst, dst->members + src->members, false, "modes_merge"));
-  PS_TRY(mod_after_last(dst, dst->stream));
-  PS_TRY(mod_after_last(src, dst->stream));
+  PS_TRY(dst->last.wait(dst->stream));
+  PS_TRY(src->last.wait(dst->stream));
   const int64_t md = mod_member_doubles(dst);
   PS_HIP(hipMemcpyAsync(dst->X + dst->members * md, src->X, (size_t)(src->members * md) * sizeof(double),
                         hipMemcpyDeviceToDevice, dst->stream));
-  PS_TRY(mod_mark_last(dst, dst->stream));
-  PS_TRY(mod_mark_last(src, dst->stream));   // src is read until then
+  PS_TRY(dst->last.mark(dst->stream));
+  PS_TRY(src->last.mark(dst->stream));   // src is read until then
   dst->W += src->W;
   dst->members += src->members;
   dst->weights.insert(dst->weights.end(), src->weights.begin(), src->weights.end());
@@ -605,17 +556,17 @@ static int mod_weights_dev(ps_modes* a, int64_t extra) {
 
 // the mean plane of `slot` on the device, current; the stream is ordered behind the last operation
 static int mod_mean_dev(ps_modes* a, int slot) {
-  PS_TRY(mod_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   if (a->mu_valid[slot]) return PS_OK;
   PS_TRY(mod_weights_dev(a, 0));
   hipEvent_t e1 = nullptr;
-  PS_TRY(mod_prof_begin(a, 1, a->stream, &e1));
+  PS_TRY(a->prof.begin(1, a->stream, &e1));
   const unsigned nblk = (unsigned)((a->pitch + PS_MOD_THREADS - 1) / PS_MOD_THREADS);
   hipLaunchKernelGGL(k_modes_mean, dim3(nblk), dim3(PS_MOD_THREADS), 0, a->stream, a->X + (int64_t)slot * a->pitch,
                      mod_member_doubles(a), a->members, a->wdev, (double)a->W, a->pitch, a->mu + (int64_t)slot * a->pitch);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, a->stream));
-  PS_TRY(mod_mark_last(a, a->stream));
+  PS_TRY(a->prof.end(a->stream, e1));
+  PS_TRY(a->last.mark(a->stream));
   a->mu_valid[slot] = true;
   return PS_OK;
 }
@@ -656,10 +607,10 @@ extern "C" int ps_modes_table(ps_modes* a, int slot, int centred, int64_t member
   if (centred || windowed)
     PS_TRY(mod_mean_dev(a, slot));
   else
-    PS_TRY(mod_after_last(a, a->stream));
+    PS_TRY(a->last.wait(a->stream));
   const double* mu = a->mu + (int64_t)slot * a->pitch;
   hipEvent_t e1 = nullptr;
-  PS_TRY(mod_prof_begin(a, 2, a->stream, &e1));
+  PS_TRY(a->prof.begin(2, a->stream, &e1));
   if (windowed) {
     PS_HIP(hipMemsetAsync(a->win, 0xff, sizeof(uint32_t), a->stream));
     PS_HIP(hipMemsetAsync(a->win + 1, 0, sizeof(uint32_t), a->stream));
@@ -674,8 +625,8 @@ extern "C" int ps_modes_table(ps_modes* a, int slot, int centred, int64_t member
   hipLaunchKernelGGL(k_modes_reduce, dim3((unsigned)((M * M + PS_MOD_THREADS - 1) / PS_MOD_THREADS)),
                      dim3(PS_MOD_THREADS), 0, a->stream, a->part, M * M, (int)split, tab);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, a->stream));
-  PS_TRY(mod_mark_last(a, a->stream));
+  PS_TRY(a->prof.end(a->stream, e1));
+  PS_TRY(a->last.mark(a->stream));
   PS_HIP(hipMemcpyAsync(out, tab, (size_t)(M * M) * sizeof(double), hipMemcpyDeviceToHost, a->stream));
   PS_HIP(hipStreamSynchronize(a->stream));
   return PS_OK;
@@ -693,19 +644,19 @@ extern "C" int ps_modes_combine(ps_modes* a, int slot, int centred, int ncoef, c
   if (centred)
     PS_TRY(mod_mean_dev(a, slot));
   else
-    PS_TRY(mod_after_last(a, a->stream));
+    PS_TRY(a->last.wait(a->stream));
   PS_TRY(mod_weights_dev(a, (int64_t)PS_MOD_MAX_COEF * M));   // after the mean: a regrown block loses the weights
   double* cdev = a->wdev + M;
   PS_HIP(hipMemcpyAsync(cdev, coef, (size_t)(ncoef * M) * sizeof(double), hipMemcpyHostToDevice, a->stream));
   hipEvent_t e1 = nullptr;
-  PS_TRY(mod_prof_begin(a, 3, a->stream, &e1));
+  PS_TRY(a->prof.begin(3, a->stream, &e1));
   const unsigned nblk = (unsigned)((a->pitch + PS_MOD_THREADS - 1) / PS_MOD_THREADS);
   hipLaunchKernelGGL(k_modes_combine, dim3(nblk), dim3(PS_MOD_THREADS), 0, a->stream, a->X + (int64_t)slot * a->pitch,
                      mod_member_doubles(a), centred ? a->mu + (int64_t)slot * a->pitch : (const double*)nullptr, M, cdev,
                      ncoef, a->pitch, a->maps);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, a->stream));
-  PS_TRY(mod_mark_last(a, a->stream));
+  PS_TRY(a->prof.end(a->stream, e1));
+  PS_TRY(a->last.mark(a->stream));
   for (int k = 0; k < ncoef; ++k)
     PS_HIP(hipMemcpyAsync(out + (int64_t)k * a->ncell, a->maps + (int64_t)k * a->pitch, (size_t)a->ncell * sizeof(double),
                           hipMemcpyDeviceToHost, a->stream));
@@ -719,7 +670,7 @@ extern "C" int ps_modes_fetch_member(ps_modes* a, int64_t member, int slot, doub
   if (member < 0 || member >= a->members)
     return ps_fail(PS_ERR_BAD_ARG, "modes_fetch_member: member %lld of %lld", (long long)member, (long long)a->members);
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(mod_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   PS_HIP(hipMemcpyAsync(out, a->X + member * mod_member_doubles(a) + (int64_t)slot * a->pitch,
                         (size_t)a->ncell * sizeof(double), hipMemcpyDeviceToHost, a->stream));
   PS_HIP(hipStreamSynchronize(a->stream));
@@ -729,12 +680,8 @@ extern "C" int ps_modes_fetch_member(ps_modes* a, int64_t member, int slot, doub
 extern "C" int ps_modes_prof(ps_modes* a, int enable, double* ms, int64_t* launches) {
   if (!a) return ps_fail(PS_ERR_BAD_ARG, "modes_prof: null handle");
   PS_HIP(hipSetDevice(a->device));
-  if (enable >= 0) a->prof_on = enable != 0;
+  a->prof.set(enable);
   if (!ms && !launches) return PS_OK;
-  for (int k = 0; k < 4; ++k) {
-    PS_TRY(mod_prof_fold(a, k));
-    if (ms) ms[k] = a->prof_ms[k];
-    if (launches) launches[k] = a->prof_n[k];
-  }
+  for (int k = 0; k < 4; ++k) PS_TRY(a->prof.totals(k, ms ? ms + k : nullptr, launches ? launches + k : nullptr));
   return PS_OK;
 }

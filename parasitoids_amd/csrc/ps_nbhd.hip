@@ -262,53 +262,19 @@ struct ps_nbhd {
   int64_t g_cap = 0;
   int64_t applies = 0;
   hipStream_t stream = nullptr;    // fetch / gather / apply of another fields source
-  hipEvent_t ev = nullptr;         // the last operation on Z, on whatever stream it ran
-  bool ev_live = false;
-  bool prof_on = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof;
-  double prof_ms = 0.0;            // applies already folded out of the list above
-  int64_t prof_n = 0;
+  PsLastOp last;                   // the last operation on Z, on whatever stream it ran
+  PsProf prof;                     // channel 0: the applies
 };
-
-static int nbhd_after_last(ps_nbhd* c, hipStream_t stream) {
-  if (c->ev_live) PS_HIP(hipStreamWaitEvent(stream, c->ev, 0));
-  return PS_OK;
-}
-static int nbhd_mark_last(ps_nbhd* c, hipStream_t stream) {
-  PS_HIP(hipEventRecord(c->ev, stream));
-  c->ev_live = true;
-  return PS_OK;
-}
-// the finished pairs into the handle's totals, their events destroyed (as ps_catch_prof)
-static const size_t NBHD_PROF_PENDING = 256;
-static int nbhd_prof_fold(ps_nbhd* c) {
-  for (auto& p : c->prof) {
-    PS_HIP(hipEventSynchronize(p.second));
-    float t = 0.f;
-    PS_HIP(hipEventElapsedTime(&t, p.first, p.second));
-    c->prof_ms += t;
-    c->prof_n += 1;
-  }
-  for (auto& p : c->prof) {
-    (void)hipEventDestroy(p.first);
-    (void)hipEventDestroy(p.second);
-  }
-  c->prof.clear();
-  return PS_OK;
-}
 
 extern "C" void ps_nbhd_destroy(ps_nbhd* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  if (c->ev_live) (void)hipEventSynchronize(c->ev);
+  c->last.sync();
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  for (auto& e : c->prof) {
-    (void)hipEventDestroy(e.first);
-    (void)hipEventDestroy(e.second);
-  }
+  c->prof.release();
   for (void* q : {(void*)c->Z, (void*)c->flag, (void*)c->g_cell, (void*)c->g_out})
     if (q) (void)hipFree(q);
-  if (c->ev) (void)hipEventDestroy(c->ev);
+  c->last.destroy();
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
@@ -391,7 +357,7 @@ extern "C" int ps_nbhd_create(int device, int N, int nin, int nout, const int32_
   hipError_t e = hipFuncSetAttribute((const void*)k_nbhd_apply, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (NB_TY + 2 * PS_NBHD_MAX_HALF) * (NB_TX + 2 * PS_NBHD_MAX_HALF) * 8);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev, hipEventDisableTiming);
+  if (e == hipSuccess) e = c->last.create();
   if (e == hipSuccess) e = hipMalloc((void**)&c->Z, z_b);
   if (e == hipSuccess) e = hipMalloc((void**)&c->flag, flag_b);
   if (e == hipSuccess) e = hipMemsetAsync(c->Z, 0, z_b, c->stream);
@@ -411,15 +377,9 @@ extern "C" int ps_nbhd_set_skip(ps_nbhd* c, int on) {
 
 // the pre-pass and the apply over the resolved descriptors on `stream`, behind the handle's last operation
 static int nbhd_launch(ps_nbhd* c, const NbhdSlots& desc, hipStream_t stream, double negval) {
-  PS_TRY(nbhd_after_last(c, stream));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (c->prof_on) {
-    if (c->prof.size() >= NBHD_PROF_PENDING) PS_TRY(nbhd_prof_fold(c));
-    PS_HIP(hipEventCreate(&e0));
-    PS_HIP(hipEventCreate(&e1));
-    c->prof.push_back({e0, e1});
-    PS_HIP(hipEventRecord(e0, stream));
-  }
+  PS_TRY(c->last.wait(stream));
+  hipEvent_t e1 = nullptr;
+  PS_TRY(c->prof.begin(0, stream, &e1));
   if (c->skip) {
     hipLaunchKernelGGL(k_nbhd_flags, dim3(c->ntx, c->nty, c->nin), dim3(256), 0, stream, desc, c->flag, c->N, c->ntx,
                        c->nty, negval);
@@ -428,8 +388,8 @@ static int nbhd_launch(ps_nbhd* c, const NbhdSlots& desc, hipStream_t stream, do
   hipLaunchKernelGGL(k_nbhd_apply, dim3(c->ntx, c->nty, c->tab.npass), dim3(NB_THREADS), c->lds, stream, desc, c->tab,
                      c->Z, c->skip ? c->flag : nullptr, c->N, c->pitch, c->ntx, c->nty, negval);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, stream));
-  PS_TRY(nbhd_mark_last(c, stream));
+  PS_TRY(c->prof.end(stream, e1));
+  PS_TRY(c->last.mark(stream));
   c->applies += 1;
   return PS_OK;
 }
@@ -491,7 +451,7 @@ extern "C" int ps_nbhd_fetch(ps_nbhd* c, int e, double* out) {
   if (e < 0 || e >= c->nout) return ps_fail(PS_ERR_BAD_ARG, "nbhd_fetch: output %d of %d", e, c->nout);
   if (c->applies == 0) return ps_fail(PS_ERR_STATE, "nbhd_fetch: nothing applied yet");
   PS_HIP(hipSetDevice(c->device));
-  PS_TRY(nbhd_after_last(c, c->stream));
+  PS_TRY(c->last.wait(c->stream));
   PS_HIP(hipMemcpyAsync(out, c->Z + (int64_t)e * c->pitch, (size_t)c->ncell * sizeof(double), hipMemcpyDeviceToHost,
                         c->stream));
   PS_HIP(hipStreamSynchronize(c->stream));
@@ -520,7 +480,7 @@ extern "C" int ps_nbhd_gather(ps_nbhd* c, int64_t n, const int32_t* rows, const 
     PS_HIP(hipMalloc((void**)&c->g_out, (size_t)n * c->nout * sizeof(double)));
     c->g_cap = n;
   }
-  PS_TRY(nbhd_after_last(c, c->stream));
+  PS_TRY(c->last.wait(c->stream));
   PS_HIP(hipMemcpyAsync(c->g_cell, cell.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
   const int64_t total = n * c->nout;
   hipLaunchKernelGGL(k_nbhd_gather, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, c->Z, c->pitch,
@@ -543,12 +503,8 @@ extern "C" int ps_nbhd_info(ps_nbhd* c, int* N, int* nin, int* nout, int64_t* ap
 extern "C" int ps_nbhd_prof(ps_nbhd* c, int enable, double* total_ms, int64_t* launches) {
   if (!c) return ps_fail(PS_ERR_BAD_ARG, "nbhd_prof: null handle");
   PS_HIP(hipSetDevice(c->device));
-  if (enable >= 0) c->prof_on = enable != 0;
-  if (total_ms || launches) {
-    PS_TRY(nbhd_prof_fold(c));
-    if (total_ms) *total_ms = c->prof_ms;
-    if (launches) *launches = c->prof_n;
-  }
+  c->prof.set(enable);
+  if (total_ms || launches) PS_TRY(c->prof.totals(0, total_ms, launches));
   return PS_OK;
 }
 
@@ -563,6 +519,6 @@ static int nbhd_view(void* h, PsProjectView* out) {
   out->device = c->device;
   return PS_OK;
 }
-static int nbhd_wait(void* h, hipStream_t stream) { return nbhd_after_last(static_cast<ps_nbhd*>(h), stream); }
-static int nbhd_mark(void* h, hipStream_t stream) { return nbhd_mark_last(static_cast<ps_nbhd*>(h), stream); }
+static int nbhd_wait(void* h, hipStream_t stream) { return static_cast<ps_nbhd*>(h)->last.wait(stream); }
+static int nbhd_mark(void* h, hipStream_t stream) { return static_cast<ps_nbhd*>(h)->last.mark(stream); }
 PsFieldsOps ps_nbhd_fields() { return PsFieldsOps{"neighbourhood fields", nbhd_view, nbhd_wait, nbhd_mark}; }

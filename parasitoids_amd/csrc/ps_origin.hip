@@ -187,8 +187,6 @@ __global__ void k_origin_merge(double* __restrict__ A, double* __restrict__ S, c
   }
 }
 
-typedef std::vector<std::pair<hipEvent_t, hipEvent_t>> ProfList;
-
 }  // namespace
 
 struct ps_origin {
@@ -210,12 +208,8 @@ struct ps_origin {
   int next_group = 0;              // the group the next add must name
   uint32_t pass_weight = 0;        // the weight group 0 of the pass under way came with
   hipStream_t stream = nullptr;    // reset / merge / fetch / row growth
-  hipEvent_t ev = nullptr;         // the last operation, on whatever stream it ran
-  bool ev_live = false;
-  bool prof_on = false;
-  ProfList prof[3];                // add, rows, merge
-  double prof_ms[3] = {0.0, 0.0, 0.0};
-  int64_t prof_n[3] = {0, 0, 0};
+  PsLastOp last;                   // the last operation, on whatever stream it ran
+  PsProf prof;                     // channel 0: the adds, 1: the rows, 2: the merges
 };
 
 static size_t org_plane_bytes(const ps_origin* p) { return (size_t)p->nhyp * p->pitch * sizeof(double); }
@@ -224,45 +218,6 @@ static size_t org_fixed_bytes(const ps_origin* p, bool prior) {
   return 3 * org_plane_bytes(p) + (prior ? (size_t)p->pitch * sizeof(double) : 0) +
          (size_t)p->nhyp * p->nblk * 2 * sizeof(double) + (size_t)p->nfind * sizeof(OriginFinding) +
          (size_t)p->nhyp * p->nfind * sizeof(double);
-}
-
-static int org_after_last(ps_origin* p, hipStream_t stream) {
-  if (p->ev_live) PS_HIP(hipStreamWaitEvent(stream, p->ev, 0));
-  return PS_OK;
-}
-static int org_mark_last(ps_origin* p, hipStream_t stream) {
-  PS_HIP(hipEventRecord(p->ev, stream));
-  p->ev_live = true;
-  return PS_OK;
-}
-// the finished pairs into the handle's totals, their events destroyed (as ps_catch_prof)
-static const size_t ORG_PROF_PENDING = 256;
-static int org_prof_fold(ps_origin* p, int cls) {
-  for (auto& e : p->prof[cls]) {
-    PS_HIP(hipEventSynchronize(e.second));
-    float t = 0.f;
-    PS_HIP(hipEventElapsedTime(&t, e.first, e.second));
-    p->prof_ms[cls] += t;
-    p->prof_n[cls] += 1;
-  }
-  for (auto& e : p->prof[cls]) {
-    (void)hipEventDestroy(e.first);
-    (void)hipEventDestroy(e.second);
-  }
-  p->prof[cls].clear();
-  return PS_OK;
-}
-static int org_prof_begin(ps_origin* p, int cls, hipStream_t stream, hipEvent_t* end) {
-  *end = nullptr;
-  if (!p->prof_on) return PS_OK;
-  if (p->prof[cls].size() >= ORG_PROF_PENDING) PS_TRY(org_prof_fold(p, cls));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  PS_HIP(hipEventCreate(&e0));
-  PS_HIP(hipEventCreate(&e1));
-  p->prof[cls].push_back({e0, e1});
-  PS_HIP(hipEventRecord(e0, stream));
-  *end = e1;
-  return PS_OK;
 }
 
 // room for `need` member rows: a doubling copies the rows so far on the handle's stream and synchronises once
@@ -281,7 +236,7 @@ static int org_reserve_rows(ps_origin* p, int64_t need) {
   PS_HIP(hipMalloc((void**)&q, bytes));
   if (p->rows) {
     hipError_t e = hipSuccess;
-    if (p->ev_live) e = hipStreamWaitEvent(p->stream, p->ev, 0);
+    if (p->last.live) e = hipStreamWaitEvent(p->stream, p->last.ev, 0);
     const int64_t keep = p->members + (p->next_group != 0 ? 1 : 0);   // the row of a pass under way too
     if (e == hipSuccess && keep > 0)
       e = hipMemcpyAsync(q, p->rows, (size_t)keep * org_row_bytes(p), hipMemcpyDeviceToDevice, p->stream);
@@ -300,17 +255,13 @@ static int org_reserve_rows(ps_origin* p, int64_t need) {
 extern "C" void ps_origin_destroy(ps_origin* p) {
   if (!p) return;
   (void)hipSetDevice(p->device);
-  if (p->ev_live) (void)hipEventSynchronize(p->ev);
+  p->last.sync();
   if (p->stream) (void)hipStreamSynchronize(p->stream);
-  for (auto& v : p->prof)
-    for (auto& e : v) {
-      (void)hipEventDestroy(e.first);
-      (void)hipEventDestroy(e.second);
-    }
+  p->prof.release();
   for (void* q : {(void*)p->find, (void*)p->ra, (void*)p->prior, (void*)p->A, (void*)p->S, (void*)p->L, (void*)p->part,
                   (void*)p->rows})
     if (q) (void)hipFree(q);
-  if (p->ev) (void)hipEventDestroy(p->ev);
+  p->last.destroy();
   if (p->stream) (void)hipStreamDestroy(p->stream);
   delete p;
 }
@@ -318,10 +269,10 @@ extern "C" void ps_origin_destroy(ps_origin* p) {
 extern "C" int ps_origin_reset(ps_origin* p) {
   if (!p) return ps_fail(PS_ERR_BAD_ARG, "origin_reset: null handle");
   PS_HIP(hipSetDevice(p->device));
-  PS_TRY(org_after_last(p, p->stream));
+  PS_TRY(p->last.wait(p->stream));
   hipLaunchKernelGGL(k_origin_fill, dim3(1024), dim3(256), 0, p->stream, p->A, p->S, (int64_t)p->nhyp * p->pitch);
   PS_HIP(hipGetLastError());
-  PS_TRY(org_mark_last(p, p->stream));
+  PS_TRY(p->last.mark(p->stream));
   p->W = 0;
   p->members = 0;
   p->weights.clear();
@@ -422,7 +373,7 @@ extern "C" int ps_origin_create(int device, int N, int nfind, const int32_t* row
   p->key_i.push_back(nslot);
   const size_t pl = org_plane_bytes(p);
   e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&p->ev, hipEventDisableTiming);
+  if (e == hipSuccess) e = p->last.create();
   if (e == hipSuccess) e = hipMalloc((void**)&p->find, find.size() * sizeof(OriginFinding));
   if (e == hipSuccess) e = hipMalloc((void**)&p->ra, ra.size() * sizeof(double));
   if (e == hipSuccess) e = hipMalloc((void**)&p->A, pl);
@@ -497,21 +448,21 @@ extern "C" int ps_origin_add(ps_origin* p, ps_solver* s, int group, int nslot, c
     return ps_fail(PS_ERR_BAD_ARG, "origin_add: group %d is released on no day of a finding (every slot is PS_REC_NONE)",
                    group);
   if (group == 0) PS_TRY(org_reserve_rows(p, p->members + 1));
-  PS_TRY(org_after_last(p, stream));
+  PS_TRY(p->last.wait(stream));
   const OrgGroup& G = p->groups[group];
   hipEvent_t e1 = nullptr;
-  PS_TRY(org_prof_begin(p, 0, stream, &e1));
+  PS_TRY(p->prof.begin(0, stream, &e1));
   hipLaunchKernelGGL(k_origin_add, dim3((unsigned)p->nblk), dim3(PS_ORIGIN_THREADS), 0, stream, desc, G, p->find, p->ra,
                      p->nfind, p->prior, p->L, p->A, p->S, p->part, p->N, p->ncell, p->pitch, p->nblk, negval,
                      (double)weight);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, stream));
-  PS_TRY(org_prof_begin(p, 1, stream, &e1));
+  PS_TRY(p->prof.end(stream, e1));
+  PS_TRY(p->prof.begin(1, stream, &e1));
   hipLaunchKernelGGL(k_origin_rows, dim3(G.nh), dim3(PS_ORIGIN_LANES), 0, stream, G, p->part, p->nblk,
                      p->rows + p->members * p->nhyp * 2);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, stream));
-  PS_TRY(org_mark_last(p, stream));
+  PS_TRY(p->prof.end(stream, e1));
+  PS_TRY(p->last.mark(stream));
   if (group == 0) p->pass_weight = weight;
   p->next_group = next;
   if (next == 0) {   // the member counts once its last group is in
@@ -541,18 +492,18 @@ extern "C" int ps_origin_merge(ps_origin* dst, ps_origin* src) {
   if (src->members == 0) return PS_OK;
   PS_HIP(hipSetDevice(dst->device));
   PS_TRY(org_reserve_rows(dst, dst->members + src->members));
-  PS_TRY(org_after_last(dst, dst->stream));
-  PS_TRY(org_after_last(src, dst->stream));
+  PS_TRY(dst->last.wait(dst->stream));
+  PS_TRY(src->last.wait(dst->stream));
   hipEvent_t e1 = nullptr;
-  PS_TRY(org_prof_begin(dst, 2, dst->stream, &e1));
+  PS_TRY(dst->prof.begin(2, dst->stream, &e1));
   hipLaunchKernelGGL(k_origin_merge, dim3(1024), dim3(256), 0, dst->stream, dst->A, dst->S, src->A, src->S,
                      (int64_t)dst->nhyp * dst->pitch);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, dst->stream));
+  PS_TRY(dst->prof.end(dst->stream, e1));
   PS_HIP(hipMemcpyAsync(dst->rows + dst->members * dst->nhyp * 2, src->rows, (size_t)src->members * org_row_bytes(src),
                         hipMemcpyDeviceToDevice, dst->stream));
-  PS_TRY(org_mark_last(dst, dst->stream));
-  PS_TRY(org_mark_last(src, dst->stream));   // src is read until then
+  PS_TRY(dst->last.mark(dst->stream));
+  PS_TRY(src->last.mark(dst->stream));   // src is read until then
   dst->W += src->W;
   dst->members += src->members;
   dst->weights.insert(dst->weights.end(), src->weights.begin(), src->weights.end());
@@ -568,7 +519,7 @@ extern "C" int ps_origin_fetch(ps_origin* p, int what, int h, double* out) {
     return ps_fail(PS_ERR_STATE, "origin_fetch: group %d of %d of the current member has not been added", p->next_group,
                    p->ngroup);
   PS_HIP(hipSetDevice(p->device));
-  PS_TRY(org_after_last(p, p->stream));
+  PS_TRY(p->last.wait(p->stream));
   const double* src = (what == 0 ? p->A : what == 1 ? p->S : p->L) + (int64_t)h * p->pitch;
   PS_HIP(hipMemcpyAsync(out, src, (size_t)p->ncell * sizeof(double), hipMemcpyDeviceToHost, p->stream));
   PS_HIP(hipStreamSynchronize(p->stream));
@@ -584,7 +535,7 @@ extern "C" int ps_origin_members(ps_origin* p, int64_t members_expected, double*
   if (weights) std::copy(p->weights.begin(), p->weights.end(), weights);
   if (rows) {
     PS_HIP(hipSetDevice(p->device));
-    PS_TRY(org_after_last(p, p->stream));
+    PS_TRY(p->last.wait(p->stream));
     PS_HIP(hipMemcpyAsync(rows, p->rows, (size_t)p->members * org_row_bytes(p), hipMemcpyDeviceToHost, p->stream));
     PS_HIP(hipStreamSynchronize(p->stream));
   }
@@ -604,14 +555,10 @@ extern "C" int ps_origin_prof(ps_origin* p, int enable, double* add_ms, int64_t*
                               double* merge_ms, int64_t* merges) {
   if (!p) return ps_fail(PS_ERR_BAD_ARG, "origin_prof: null handle");
   PS_HIP(hipSetDevice(p->device));
-  if (enable >= 0) p->prof_on = enable != 0;
+  p->prof.set(enable);
   double* ms[3] = {add_ms, rows_ms, merge_ms};
   int64_t* cnt[3] = {adds, rows_n, merges};
-  for (int k = 0; k < 3; ++k) {
-    if (!ms[k] && !cnt[k]) continue;
-    PS_TRY(org_prof_fold(p, k));
-    if (ms[k]) *ms[k] = p->prof_ms[k];
-    if (cnt[k]) *cnt[k] = p->prof_n[k];
-  }
+  for (int k = 0; k < 3; ++k)
+    if (ms[k] || cnt[k]) PS_TRY(p->prof.totals(k, ms[k], cnt[k]));
   return PS_OK;
 }

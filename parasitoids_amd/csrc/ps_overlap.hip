@@ -150,8 +150,6 @@ __global__ void __launch_bounds__(PS_OVL_THREADS) k_overlap_subset(const uint64_
 
 }  // namespace
 
-typedef std::vector<std::pair<hipEvent_t, hipEvent_t>> OvlProfList;
-
 struct ps_overlap {
   int device = 0, N = 0;
   ps_excur* e = nullptr;           // borrowed: the caller keeps it alive
@@ -164,41 +162,8 @@ struct ps_overlap {
   uint32_t* win = nullptr;         // [2]
   int64_t last_members = 0;        // of the last pairs call
   hipStream_t stream = nullptr;
-  bool prof_on = false;
-  OvlProfList prof[2];             // pairs / subset
-  double prof_ms[2] = {0.0, 0.0};
-  int64_t prof_n[2] = {0, 0};
+  PsProf prof;                     // channel 0: the pairs calls, 1: the subset calls
 };
-
-static const size_t OVL_PROF_PENDING = 256;
-static int ovl_prof_fold(ps_overlap* h, int which) {
-  OvlProfList& v = h->prof[which];
-  for (auto& p : v) {
-    PS_HIP(hipEventSynchronize(p.second));
-    float t = 0.f;
-    PS_HIP(hipEventElapsedTime(&t, p.first, p.second));
-    h->prof_ms[which] += t;
-    h->prof_n[which] += 1;
-  }
-  for (auto& p : v) {
-    (void)hipEventDestroy(p.first);
-    (void)hipEventDestroy(p.second);
-  }
-  v.clear();
-  return PS_OK;
-}
-static int ovl_prof_begin(ps_overlap* h, int which, hipEvent_t* end) {
-  *end = nullptr;
-  if (!h->prof_on) return PS_OK;
-  if (h->prof[which].size() >= OVL_PROF_PENDING) PS_TRY(ovl_prof_fold(h, which));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  PS_HIP(hipEventCreate(&e0));
-  PS_HIP(hipEventCreate(&e1));
-  h->prof[which].push_back({e0, e1});
-  PS_HIP(hipEventRecord(e0, h->stream));
-  *end = e1;
-  return PS_OK;
-}
 
 // a scratch block of at least `need` uint32, regrown (not copied) once the stream has drained; the free memory is
 // checked first
@@ -225,11 +190,7 @@ extern "C" void ps_overlap_destroy(ps_overlap* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (auto& v : h->prof)
-    for (auto& p : v) {
-      (void)hipEventDestroy(p.first);
-      (void)hipEventDestroy(p.second);
-    }
+  h->prof.release();
   for (void* p : {(void*)h->table, (void*)h->plane, (void*)h->sel, (void*)h->win})
     if (p) (void)hipFree(p);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -291,7 +252,7 @@ extern "C" int ps_overlap_pairs(ps_overlap* h, int k, int slot, int64_t members_
   const int64_t split = std::max<int64_t>(1, std::min<int64_t>(nchunk, PS_OVL_BLOCKS / npair));
   PS_TRY(ps_excur_wait_internal(h->e, h->stream));
   hipEvent_t e1 = nullptr;
-  PS_TRY(ovl_prof_begin(h, 0, &e1));
+  PS_TRY(h->prof.begin(0, h->stream, &e1));
   PS_HIP(hipMemsetAsync(h->table, 0, (size_t)(M * M) * sizeof(uint32_t), h->stream));
   if (use_window) {
     PS_HIP(hipMemsetAsync(h->win, 0xff, sizeof(uint32_t), h->stream));
@@ -305,7 +266,7 @@ extern "C" int ps_overlap_pairs(ps_overlap* h, int k, int slot, int64_t members_
                      v.mask, (int64_t)v.nthr * v.nslot * nword, p * nword, M, (int)ntile, h->win,
                      use_window ? (int64_t)0 : nword, h->table);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, h->stream));
+  PS_TRY(h->prof.end(h->stream, e1));
   PS_TRY(ps_excur_mark_internal(h->e, h->stream));
   PS_HIP(hipMemcpyAsync(out, h->table, (size_t)(M * M) * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
   PS_HIP(hipStreamSynchronize(h->stream));
@@ -333,12 +294,12 @@ extern "C" int ps_overlap_subset(ps_overlap* h, int k, int slot, int64_t members
   PS_TRY(ps_excur_wait_internal(h->e, h->stream));
   PS_HIP(hipMemcpyAsync(h->sel, s, (size_t)members * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
   hipEvent_t e1 = nullptr;
-  PS_TRY(ovl_prof_begin(h, 1, &e1));
+  PS_TRY(h->prof.begin(1, h->stream, &e1));
   hipLaunchKernelGGL(k_overlap_subset, dim3((unsigned)((nword + per_block - 1) / per_block)), dim3(PS_OVL_THREADS), 0,
                      h->stream, v.mask, (int64_t)v.nthr * v.nslot * nword, ((int64_t)k * v.nslot + slot) * nword,
                      members, nword, h->sel, h->plane);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, h->stream));
+  PS_TRY(h->prof.end(h->stream, e1));
   PS_TRY(ps_excur_mark_internal(h->e, h->stream));
   PS_HIP(hipMemcpyAsync(out, h->plane, (size_t)h->ncell * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
   PS_HIP(hipStreamSynchronize(h->stream));   // the selection is read until here
@@ -357,12 +318,8 @@ extern "C" int ps_overlap_prof(ps_overlap* h, int enable, double* pairs_ms, int6
                                int64_t* subset_n) {
   if (!h) return ps_fail(PS_ERR_BAD_ARG, "overlap_prof: null handle");
   PS_HIP(hipSetDevice(h->device));
-  if (enable >= 0) h->prof_on = enable != 0;
+  h->prof.set(enable);
   if (!pairs_ms && !pairs_n && !subset_ms && !subset_n) return PS_OK;
-  for (int w = 0; w < 2; ++w) PS_TRY(ovl_prof_fold(h, w));
-  if (pairs_ms) *pairs_ms = h->prof_ms[0];
-  if (pairs_n) *pairs_n = h->prof_n[0];
-  if (subset_ms) *subset_ms = h->prof_ms[1];
-  if (subset_n) *subset_n = h->prof_n[1];
-  return PS_OK;
+  PS_TRY(h->prof.totals(0, pairs_ms, pairs_n));
+  return h->prof.totals(1, subset_ms, subset_n);
 }

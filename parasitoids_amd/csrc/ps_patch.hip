@@ -209,10 +209,8 @@ struct ps_patch {
   int64_t members = 0;
   std::vector<uint32_t> weights;   // per member, in row order
   hipStream_t stream = nullptr;    // reset / merge / maps / fetch / row growth
-  hipEvent_t ev = nullptr;         // the last operation, on whatever stream it ran
-  bool ev_live = false;
-  bool prof_on = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_add, prof_map;
+  PsLastOp last;                   // the last operation, on whatever stream it ran
+  PsProf prof;                     // channel 0: the adds, 1: the maps
 };
 
 static int64_t pat_planes(const ps_patch* a) { return (int64_t)a->nthr * a->nslot; }
@@ -230,28 +228,6 @@ static int pat_alloc(void** p, size_t bytes, const char* what) {
   return PS_OK;
 }
 
-static int pat_after_last(ps_patch* a, hipStream_t stream) {
-  if (a->ev_live) PS_HIP(hipStreamWaitEvent(stream, a->ev, 0));
-  return PS_OK;
-}
-static int pat_mark_last(ps_patch* a, hipStream_t stream) {
-  PS_HIP(hipEventRecord(a->ev, stream));
-  a->ev_live = true;
-  return PS_OK;
-}
-static int pat_prof_begin(ps_patch* a, std::vector<std::pair<hipEvent_t, hipEvent_t>>& v, hipStream_t stream,
-                          hipEvent_t* end) {
-  *end = nullptr;
-  if (!a->prof_on) return PS_OK;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  PS_HIP(hipEventCreate(&e0));
-  PS_HIP(hipEventCreate(&e1));
-  v.push_back({e0, e1});
-  PS_HIP(hipEventRecord(e0, stream));
-  *end = e1;
-  return PS_OK;
-}
-
 // room for `need` member rows: a doubling copies the rows so far on the handle's stream and synchronises once
 // before the old block is freed
 static int pat_reserve_rows(ps_patch* a, int64_t need) {
@@ -263,7 +239,7 @@ static int pat_reserve_rows(ps_patch* a, int64_t need) {
   PS_TRY(pat_alloc(&p, (size_t)cap * row_b, "the member rows"));
   if (a->rows_cap > 0) {
     hipError_t e = hipSuccess;
-    if (a->ev_live) e = hipStreamWaitEvent(a->stream, a->ev, 0);
+    if (a->last.live) e = hipStreamWaitEvent(a->stream, a->last.ev, 0);
     if (e == hipSuccess && a->members > 0)
       e = hipMemcpyAsync(p, a->rows, (size_t)a->members * row_b, hipMemcpyDeviceToDevice, a->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(a->stream);
@@ -281,16 +257,12 @@ static int pat_reserve_rows(ps_patch* a, int64_t need) {
 extern "C" void ps_patch_destroy(ps_patch* a) {
   if (!a) return;
   (void)hipSetDevice(a->device);
-  if (a->ev_live) (void)hipEventSynchronize(a->ev);
+  a->last.sync();
   if (a->stream) (void)hipStreamSynchronize(a->stream);
-  for (auto* v : {&a->prof_add, &a->prof_map})
-    for (auto& p : *v) {
-      (void)hipEventDestroy(p.first);
-      (void)hipEventDestroy(p.second);
-    }
+  a->prof.release();
   for (void* p : {(void*)a->cnt, (void*)a->parent, (void*)a->size, (void*)a->key, (void*)a->rows, (void*)a->map})
     if (p) (void)hipFree(p);
-  if (a->ev) (void)hipEventDestroy(a->ev);
+  a->last.destroy();
   if (a->stream) (void)hipStreamDestroy(a->stream);
   delete a;
 }
@@ -298,22 +270,14 @@ extern "C" void ps_patch_destroy(ps_patch* a) {
 extern "C" int ps_patch_reset(ps_patch* a) {
   if (!a) return ps_fail(PS_ERR_BAD_ARG, "patch_reset: null handle");
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(pat_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   PS_HIP(hipMemsetAsync(a->cnt, 0, pat_cnt_bytes(a), a->stream));
-  PS_TRY(pat_mark_last(a, a->stream));
+  PS_TRY(a->last.mark(a->stream));
   a->W = 0;
   a->members = 0;
   a->weights.clear();
-  if (!a->prof_add.empty() || !a->prof_map.empty()) {   // the timings so far go with the members
-    PS_HIP(hipStreamSynchronize(a->stream));
-    for (auto* v : {&a->prof_add, &a->prof_map}) {
-      for (auto& p : *v) {
-        (void)hipEventDestroy(p.first);
-        (void)hipEventDestroy(p.second);
-      }
-      v->clear();
-    }
-  }
+  if (!a->prof.idle()) PS_HIP(hipStreamSynchronize(a->stream));
+  a->prof.release();   // the timings so far go with the members
   return PS_OK;
 }
 
@@ -349,7 +313,7 @@ extern "C" int ps_patch_create(int device, int N, int nslot, int nthr, const dou
     return rc;
   };
   hipError_t e = hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&a->ev, hipEventDisableTiming);
+  if (e == hipSuccess) e = a->last.create();
   if (e != hipSuccess) return fail(ps_fail(PS_ERR_HIP, "patch_create: %s", hipGetErrorString(e)));
   int rc = pat_alloc((void**)&a->cnt, pat_cnt_bytes(a), "the count planes");
   if (rc == PS_OK) rc = pat_alloc((void**)&a->parent, pat_plane_bytes(a), "the parent scratch");
@@ -372,9 +336,9 @@ extern "C" int ps_patch_reserve(ps_patch* a, int64_t members) {
 // one member from the slot descriptors (one per slot of the handle, the rest null), enqueued on `stream`
 static int pat_launch(ps_patch* a, const PatSlots& desc, hipStream_t stream, double negval, uint32_t weight) {
   PS_TRY(pat_reserve_rows(a, a->members + 1));
-  PS_TRY(pat_after_last(a, stream));
+  PS_TRY(a->last.wait(stream));
   hipEvent_t e1 = nullptr;
-  PS_TRY(pat_prof_begin(a, a->prof_add, stream, &e1));
+  PS_TRY(a->prof.begin(0, stream, &e1));
   const int64_t np = pat_planes(a);
   uint32_t* rows = a->rows + a->members * np * PS_PAT_ROW;
   PatThr thr;
@@ -398,8 +362,8 @@ static int pat_launch(ps_patch* a, const PatSlots& desc, hipStream_t stream, dou
   hipLaunchKernelGGL(k_patch_count, grid, block, 0, stream, a->parent, a->size, a->key, a->cnt, cnt_sat, rows, ncell,
                      a->pitch, weight);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, stream));
-  PS_TRY(pat_mark_last(a, stream));
+  PS_TRY(a->prof.end(stream, e1));
+  PS_TRY(a->last.mark(stream));
   a->W += weight;
   a->members += 1;
   a->weights.push_back(weight);
@@ -475,16 +439,16 @@ extern "C" int ps_patch_merge(ps_patch* dst, ps_patch* src) {
   if (src->members == 0) return PS_OK;
   PS_HIP(hipSetDevice(dst->device));
   PS_TRY(pat_reserve_rows(dst, dst->members + src->members));
-  PS_TRY(pat_after_last(dst, dst->stream));
-  PS_TRY(pat_after_last(src, dst->stream));
+  PS_TRY(dst->last.wait(dst->stream));
+  PS_TRY(src->last.wait(dst->stream));
   hipLaunchKernelGGL(k_patch_merge, dim3(2048), dim3(256), 0, dst->stream, dst->cnt, src->cnt,
                      2 * pat_planes(dst) * dst->pitch);
   PS_HIP(hipGetLastError());
   const size_t row_b = pat_member_bytes(dst);
   PS_HIP(hipMemcpyAsync(dst->rows + dst->members * pat_planes(dst) * PS_PAT_ROW, src->rows, (size_t)src->members * row_b,
                         hipMemcpyDeviceToDevice, dst->stream));
-  PS_TRY(pat_mark_last(dst, dst->stream));
-  PS_TRY(pat_mark_last(src, dst->stream));   // src is read until then
+  PS_TRY(dst->last.mark(dst->stream));
+  PS_TRY(src->last.mark(dst->stream));   // src is read until then
   dst->W += src->W;
   dst->members += src->members;
   dst->weights.insert(dst->weights.end(), src->weights.begin(), src->weights.end());
@@ -521,14 +485,14 @@ extern "C" int ps_patch_prob(ps_patch* a, int k, int slot, int which, double* ou
   PS_TRY(pat_check_which(which, "patch_prob"));
   PS_TRY(pat_check(a, k, slot, "patch_prob"));
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(pat_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   hipEvent_t e1 = nullptr;
-  PS_TRY(pat_prof_begin(a, a->prof_map, a->stream, &e1));
+  PS_TRY(a->prof.begin(1, a->stream, &e1));
   hipLaunchKernelGGL(k_patch_prob, dim3((unsigned)((a->ncell + 255) / 256)), dim3(256), 0, a->stream,
                      pat_plane(a, k, slot, which), a->ncell, (double)a->W, a->map);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, a->stream));
-  PS_TRY(pat_mark_last(a, a->stream));
+  PS_TRY(a->prof.end(a->stream, e1));
+  PS_TRY(a->last.mark(a->stream));
   PS_HIP(hipMemcpyAsync(out, a->map, (size_t)a->ncell * sizeof(double), hipMemcpyDeviceToHost, a->stream));
   PS_HIP(hipStreamSynchronize(a->stream));
   return PS_OK;
@@ -539,7 +503,7 @@ extern "C" int ps_patch_fetch_counts(ps_patch* a, int k, int slot, int which, ui
   PS_TRY(pat_check_which(which, "patch_fetch_counts"));
   PS_TRY(pat_check(a, k, slot, "patch_fetch_counts"));
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(pat_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   PS_HIP(hipMemcpyAsync(out, pat_plane(a, k, slot, which), (size_t)a->ncell * sizeof(uint32_t), hipMemcpyDeviceToHost,
                         a->stream));
   PS_HIP(hipStreamSynchronize(a->stream));
@@ -557,7 +521,7 @@ extern "C" int ps_patch_fetch_members(ps_patch* a, int k, int slot, uint32_t* np
   uint32_t* outs[PS_PAT_ROW] = {npatch, cells, main_cells, main_label, sat_cells_max};
   if (!npatch && !cells && !main_cells && !main_label && !sat_cells_max) return PS_OK;
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(pat_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   std::vector<uint32_t> h((size_t)(m * np * PS_PAT_ROW));
   PS_HIP(hipMemcpyAsync(h.data(), a->rows, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, a->stream));
   PS_HIP(hipStreamSynchronize(a->stream));
@@ -570,21 +534,10 @@ extern "C" int ps_patch_fetch_members(ps_patch* a, int k, int slot, uint32_t* np
 extern "C" int ps_patch_prof(ps_patch* a, int enable, double* add_ms, int64_t* adds, double* map_ms, int64_t* maps) {
   if (!a) return ps_fail(PS_ERR_BAD_ARG, "patch_prof: null handle");
   PS_HIP(hipSetDevice(a->device));
-  if (enable >= 0) a->prof_on = enable != 0;
+  a->prof.set(enable);
   double* ms_out[2] = {add_ms, map_ms};
   int64_t* n_out[2] = {adds, maps};
-  std::vector<std::pair<hipEvent_t, hipEvent_t>>* lists[2] = {&a->prof_add, &a->prof_map};
-  for (int k = 0; k < 2; ++k) {
-    if (!ms_out[k] && !n_out[k]) continue;
-    double ms = 0.0;
-    for (auto& p : *lists[k]) {
-      PS_HIP(hipEventSynchronize(p.second));
-      float t = 0.f;
-      PS_HIP(hipEventElapsedTime(&t, p.first, p.second));
-      ms += t;
-    }
-    if (ms_out[k]) *ms_out[k] = ms;
-    if (n_out[k]) *n_out[k] = (int64_t)lists[k]->size();
-  }
+  for (int k = 0; k < 2; ++k)
+    if (ms_out[k] || n_out[k]) PS_TRY(a->prof.totals(k, ms_out[k], n_out[k]));
   return PS_OK;
 }

@@ -212,10 +212,8 @@ struct ps_pathway {
   int64_t members = 0;
   std::vector<uint32_t> weights;   // per member, in row order
   hipStream_t stream = nullptr;    // reset / merge / fetch / row growth
-  hipEvent_t ev = nullptr;         // the last operation, on whatever stream it ran
-  bool ev_live = false;
-  bool prof_on = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_add;
+  PsLastOp last;                   // the last operation, on whatever stream it ran
+  PsProf prof;                     // channel 0: the adds
 };
 
 static int64_t pw_planes(const ps_pathway* a) { return (int64_t)a->nthr * a->nslot; }
@@ -234,16 +232,6 @@ static int pw_alloc(void** p, size_t bytes, const char* what) {
   return PS_OK;
 }
 
-static int pw_after_last(ps_pathway* a, hipStream_t stream) {
-  if (a->ev_live) PS_HIP(hipStreamWaitEvent(stream, a->ev, 0));
-  return PS_OK;
-}
-static int pw_mark_last(ps_pathway* a, hipStream_t stream) {
-  PS_HIP(hipEventRecord(a->ev, stream));
-  a->ev_live = true;
-  return PS_OK;
-}
-
 // room for `need` member rows: a doubling copies the rows so far on the handle's stream and synchronises once
 // before the old block is freed
 static int pw_reserve_rows(ps_pathway* a, int64_t need) {
@@ -255,7 +243,7 @@ static int pw_reserve_rows(ps_pathway* a, int64_t need) {
   PS_TRY(pw_alloc(&p, (size_t)cap * row_b, "the member rows"));
   if (a->rows_cap > 0) {
     hipError_t e = hipSuccess;
-    if (a->ev_live) e = hipStreamWaitEvent(a->stream, a->ev, 0);
+    if (a->last.live) e = hipStreamWaitEvent(a->stream, a->last.ev, 0);
     if (e == hipSuccess && a->members > 0)
       e = hipMemcpyAsync(p, a->rows, (size_t)a->members * row_b, hipMemcpyDeviceToDevice, a->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(a->stream);
@@ -270,23 +258,15 @@ static int pw_reserve_rows(ps_pathway* a, int64_t need) {
   return PS_OK;
 }
 
-static void pw_drop_timings(ps_pathway* a) {
-  for (auto& p : a->prof_add) {
-    (void)hipEventDestroy(p.first);
-    (void)hipEventDestroy(p.second);
-  }
-  a->prof_add.clear();
-}
-
 extern "C" void ps_pathway_destroy(ps_pathway* a) {
   if (!a) return;
   (void)hipSetDevice(a->device);
-  if (a->ev_live) (void)hipEventSynchronize(a->ev);
+  a->last.sync();
   if (a->stream) (void)hipStreamSynchronize(a->stream);
-  pw_drop_timings(a);
+  a->prof.release();
   for (void* p : {(void*)a->cnt, (void*)a->parent, (void*)a->flags, (void*)a->state, (void*)a->rows})
     if (p) (void)hipFree(p);
-  if (a->ev) (void)hipEventDestroy(a->ev);
+  a->last.destroy();
   if (a->stream) (void)hipStreamDestroy(a->stream);
   delete a;
 }
@@ -294,16 +274,14 @@ extern "C" void ps_pathway_destroy(ps_pathway* a) {
 extern "C" int ps_pathway_reset(ps_pathway* a) {
   if (!a) return ps_fail(PS_ERR_BAD_ARG, "pathway_reset: null handle");
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(pw_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   PS_HIP(hipMemsetAsync(a->cnt, 0, pw_cnt_bytes(a), a->stream));
-  PS_TRY(pw_mark_last(a, a->stream));
+  PS_TRY(a->last.mark(a->stream));
   a->W = 0;
   a->members = 0;
   a->weights.clear();
-  if (!a->prof_add.empty()) {   // the timings so far go with the members
-    PS_HIP(hipStreamSynchronize(a->stream));
-    pw_drop_timings(a);
-  }
+  if (!a->prof.idle()) PS_HIP(hipStreamSynchronize(a->stream));
+  a->prof.release();   // the timings so far go with the members
   return PS_OK;
 }
 
@@ -346,7 +324,7 @@ extern "C" int ps_pathway_create(int device, int N, int nslot, int nthr, const d
     return rc;
   };
   hipError_t e = hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&a->ev, hipEventDisableTiming);
+  if (e == hipSuccess) e = a->last.create();
   if (e != hipSuccess) return fail(ps_fail(PS_ERR_HIP, "pathway_create: %s", hipGetErrorString(e)));
   int rc = pw_alloc((void**)&a->cnt, pw_cnt_bytes(a), "the count planes");
   if (rc == PS_OK) rc = pw_alloc((void**)&a->parent, pw_plane_bytes(a), "the parent scratch");
@@ -368,15 +346,9 @@ extern "C" int ps_pathway_reserve(ps_pathway* a, int64_t members) {
 // one member from the slot descriptors (one per slot of the handle, the rest null), enqueued on `stream`
 static int pw_launch(ps_pathway* a, const PwSlots& desc, hipStream_t stream, double negval, uint32_t weight) {
   PS_TRY(pw_reserve_rows(a, a->members + 1));
-  PS_TRY(pw_after_last(a, stream));
+  PS_TRY(a->last.wait(stream));
   hipEvent_t e1 = nullptr;
-  if (a->prof_on) {
-    hipEvent_t e0 = nullptr;
-    PS_HIP(hipEventCreate(&e0));
-    PS_HIP(hipEventCreate(&e1));
-    a->prof_add.push_back({e0, e1});
-    PS_HIP(hipEventRecord(e0, stream));
-  }
+  PS_TRY(a->prof.begin(0, stream, &e1));
   const int64_t np = pw_planes(a);
   uint32_t* rows = a->rows + a->members * np * PS_PW_ROW;
   PwThr thr;
@@ -406,8 +378,8 @@ static int pw_launch(ps_pathway* a, const PwSlots& desc, hipStream_t stream, dou
   }
   hipLaunchKernelGGL(k_pathway_count, levels, block, 0, stream, a->state, a->cnt, ncell, a->pitch, weight);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, stream));
-  PS_TRY(pw_mark_last(a, stream));
+  PS_TRY(a->prof.end(stream, e1));
+  PS_TRY(a->last.mark(stream));
   a->W += weight;
   a->members += 1;
   a->weights.push_back(weight);
@@ -477,16 +449,16 @@ extern "C" int ps_pathway_merge(ps_pathway* dst, ps_pathway* src) {
   if (src->members == 0) return PS_OK;
   PS_HIP(hipSetDevice(dst->device));
   PS_TRY(pw_reserve_rows(dst, dst->members + src->members));
-  PS_TRY(pw_after_last(dst, dst->stream));
-  PS_TRY(pw_after_last(src, dst->stream));
+  PS_TRY(dst->last.wait(dst->stream));
+  PS_TRY(src->last.wait(dst->stream));
   hipLaunchKernelGGL(k_pathway_merge, dim3(2048), dim3(256), 0, dst->stream, dst->cnt, src->cnt,
                      (int64_t)dst->nthr * PS_PW_CLASSES * dst->pitch);
   PS_HIP(hipGetLastError());
   const size_t row_b = pw_member_bytes(dst);
   PS_HIP(hipMemcpyAsync(dst->rows + dst->members * pw_planes(dst) * PS_PW_ROW, src->rows, (size_t)src->members * row_b,
                         hipMemcpyDeviceToDevice, dst->stream));
-  PS_TRY(pw_mark_last(dst, dst->stream));
-  PS_TRY(pw_mark_last(src, dst->stream));   // src is read until then
+  PS_TRY(dst->last.mark(dst->stream));
+  PS_TRY(src->last.mark(dst->stream));   // src is read until then
   dst->W += src->W;
   dst->members += src->members;
   dst->weights.insert(dst->weights.end(), src->weights.begin(), src->weights.end());
@@ -516,7 +488,7 @@ extern "C" int ps_pathway_fetch_counts(ps_pathway* a, int k, int which, uint32_t
     return ps_fail(PS_ERR_BAD_ARG, "pathway_fetch_counts: which %d is none of 0 (front), 1 (jump), 2 (secondary)", which);
   PS_TRY(pw_check(a, k, "pathway_fetch_counts"));
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(pw_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   PS_HIP(hipMemcpyAsync(out, a->cnt + ((int64_t)k * PS_PW_CLASSES + which) * a->pitch, (size_t)a->ncell * sizeof(uint32_t),
                         hipMemcpyDeviceToHost, a->stream));
   PS_HIP(hipStreamSynchronize(a->stream));
@@ -534,7 +506,7 @@ extern "C" int ps_pathway_fetch_members(ps_pathway* a, int k, int slot, uint32_t
   uint32_t* outs[PS_PW_ROW] = {front, jump, secondary, foci};
   if (!front && !jump && !secondary && !foci) return PS_OK;
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(pw_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   std::vector<uint32_t> h((size_t)(m * np * PS_PW_ROW));
   PS_HIP(hipMemcpyAsync(h.data(), a->rows, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, a->stream));
   PS_HIP(hipStreamSynchronize(a->stream));
@@ -547,17 +519,7 @@ extern "C" int ps_pathway_fetch_members(ps_pathway* a, int k, int slot, uint32_t
 extern "C" int ps_pathway_prof(ps_pathway* a, int enable, double* add_ms, int64_t* adds) {
   if (!a) return ps_fail(PS_ERR_BAD_ARG, "pathway_prof: null handle");
   PS_HIP(hipSetDevice(a->device));
-  if (enable >= 0) a->prof_on = enable != 0;
-  if (add_ms) {
-    double ms = 0.0;
-    for (auto& p : a->prof_add) {
-      PS_HIP(hipEventSynchronize(p.second));
-      float t = 0.f;
-      PS_HIP(hipEventElapsedTime(&t, p.first, p.second));
-      ms += t;
-    }
-    *add_ms = ms;
-  }
-  if (adds) *adds = (int64_t)a->prof_add.size();
+  a->prof.set(enable);
+  if (add_ms || adds) PS_TRY(a->prof.totals(0, add_ms, adds));
   return PS_OK;
 }

@@ -181,73 +181,23 @@ struct ps_peak {
   int64_t members = 0;
   bool y_live = false;         // an add since create / reset wrote Y
   hipStream_t stream = nullptr;    // reset / merge / maps / fetch, and the adds of fields sources
-  hipEvent_t ev = nullptr;         // the last operation, on whatever stream it ran
-  bool ev_live = false;
-  bool prof_on = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_add, prof_map;
-  double prof_ms[2] = {0.0, 0.0};      // add / map launches already folded out of the lists above
-  int64_t prof_n[2] = {0, 0};
+  PsLastOp last;                   // the last operation, on whatever stream it ran
+  PsProf prof;                     // channel 0: the adds, 1: the maps
 };
 
 static int64_t peak_planes(const ps_peak* a) { return (int64_t)(1 + a->nthr) * a->nslot; }
 static size_t peak_cnt_bytes(const ps_peak* a) { return (size_t)peak_planes(a) * a->pitch * sizeof(uint32_t); }
 static uint32_t* peak_du(const ps_peak* a, int k) { return a->cnt + (int64_t)(1 + k) * a->nslot * a->pitch; }
 
-static int peak_after_last(ps_peak* a, hipStream_t stream) {
-  if (a->ev_live) PS_HIP(hipStreamWaitEvent(stream, a->ev, 0));
-  return PS_OK;
-}
-static int peak_mark_last(ps_peak* a, hipStream_t stream) {
-  PS_HIP(hipEventRecord(a->ev, stream));
-  a->ev_live = true;
-  return PS_OK;
-}
-// the finished pairs of one list into the handle's totals, their events destroyed: a profiled handle holds at
-// most PEAK_PROF_PENDING pairs however long it lives
-static const size_t PEAK_PROF_PENDING = 256;
-static int peak_prof_fold(ps_peak* a, std::vector<std::pair<hipEvent_t, hipEvent_t>>& v) {
-  const int k = &v == &a->prof_add ? 0 : 1;
-  for (auto& p : v) {
-    PS_HIP(hipEventSynchronize(p.second));
-    float t = 0.f;
-    PS_HIP(hipEventElapsedTime(&t, p.first, p.second));
-    a->prof_ms[k] += t;
-    a->prof_n[k] += 1;
-  }
-  for (auto& p : v) {
-    (void)hipEventDestroy(p.first);
-    (void)hipEventDestroy(p.second);
-  }
-  v.clear();
-  return PS_OK;
-}
-static int peak_prof_begin(ps_peak* a, std::vector<std::pair<hipEvent_t, hipEvent_t>>& v, hipStream_t stream,
-                           hipEvent_t* end) {
-  *end = nullptr;
-  if (!a->prof_on) return PS_OK;
-  if (v.size() >= PEAK_PROF_PENDING) PS_TRY(peak_prof_fold(a, v));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  PS_HIP(hipEventCreate(&e0));
-  PS_HIP(hipEventCreate(&e1));
-  v.push_back({e0, e1});
-  PS_HIP(hipEventRecord(e0, stream));
-  *end = e1;
-  return PS_OK;
-}
-
 extern "C" void ps_peak_destroy(ps_peak* a) {
   if (!a) return;
   (void)hipSetDevice(a->device);
-  if (a->ev_live) (void)hipEventSynchronize(a->ev);
+  a->last.sync();
   if (a->stream) (void)hipStreamSynchronize(a->stream);
-  for (auto* v : {&a->prof_add, &a->prof_map})
-    for (auto& p : *v) {
-      (void)hipEventDestroy(p.first);
-      (void)hipEventDestroy(p.second);
-    }
+  a->prof.release();
   for (void* p : {(void*)a->Y, (void*)a->cnt, (void*)a->map})
     if (p) (void)hipFree(p);
-  if (a->ev) (void)hipEventDestroy(a->ev);
+  a->last.destroy();
   if (a->stream) (void)hipStreamDestroy(a->stream);
   delete a;
 }
@@ -255,9 +205,9 @@ extern "C" void ps_peak_destroy(ps_peak* a) {
 extern "C" int ps_peak_reset(ps_peak* a) {
   if (!a) return ps_fail(PS_ERR_BAD_ARG, "peak_reset: null handle");
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(peak_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   PS_HIP(hipMemsetAsync(a->cnt, 0, peak_cnt_bytes(a), a->stream));
-  PS_TRY(peak_mark_last(a, a->stream));
+  PS_TRY(a->last.mark(a->stream));
   a->W = 0;
   a->members = 0;
   a->y_live = false;
@@ -302,7 +252,7 @@ extern "C" int ps_peak_create(int device, int N, int nslot, int nthr, const doub
     return rc;
   };
   hipError_t e = hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&a->ev, hipEventDisableTiming);
+  if (e == hipSuccess) e = a->last.create();
   if (e == hipSuccess) e = hipMalloc((void**)&a->cnt, peak_cnt_bytes(a));
   if (e == hipSuccess) e = hipMalloc((void**)&a->Y, (size_t)pitch * sizeof(double));
   if (e == hipSuccess) e = hipMalloc((void**)&a->map, (size_t)pitch * sizeof(double));
@@ -326,14 +276,14 @@ static int peak_check_weight(const ps_peak* a, const char* who, uint32_t weight)
 static int peak_launch(ps_peak* a, const PeakSlots& desc, hipStream_t stream, double negval, uint32_t weight) {
   PeakThr thr;
   for (int k = 0; k < PS_PEAK_MAX_THR; ++k) thr.t[k] = k < a->nthr ? a->thr[(size_t)k] : 0.0;
-  PS_TRY(peak_after_last(a, stream));
+  PS_TRY(a->last.wait(stream));
   hipEvent_t e1 = nullptr;
-  PS_TRY(peak_prof_begin(a, a->prof_add, stream, &e1));
+  PS_TRY(a->prof.begin(0, stream, &e1));
   hipLaunchKernelGGL(k_peak_add, dim3(a->nblk), dim3(PS_PEAK_THREADS), 0, stream, desc, thr, a->nslot, a->nthr, a->Y,
                      a->cnt, peak_du(a, 0), a->ncell, a->pitch, negval, weight);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, stream));
-  PS_TRY(peak_mark_last(a, stream));
+  PS_TRY(a->prof.end(stream, e1));
+  PS_TRY(a->last.mark(stream));
   a->W += weight;
   a->members += 1;
   a->y_live = true;
@@ -402,13 +352,13 @@ extern "C" int ps_peak_merge(ps_peak* dst, ps_peak* src) {
   if (dst->W + src->W > 0xffffffffull) return ps_fail(PS_ERR_BAD_ARG, "peak_merge: total weight would overflow");
   if (src->members == 0) return PS_OK;
   PS_HIP(hipSetDevice(dst->device));
-  PS_TRY(peak_after_last(dst, dst->stream));
-  PS_TRY(peak_after_last(src, dst->stream));
+  PS_TRY(dst->last.wait(dst->stream));
+  PS_TRY(src->last.wait(dst->stream));
   hipLaunchKernelGGL(k_peak_merge, dim3(2048), dim3(256), 0, dst->stream, dst->cnt, src->cnt,
                      peak_planes(dst) * dst->pitch);
   PS_HIP(hipGetLastError());
-  PS_TRY(peak_mark_last(dst, dst->stream));
-  PS_TRY(peak_mark_last(src, dst->stream));   // src is read until then
+  PS_TRY(dst->last.mark(dst->stream));
+  PS_TRY(src->last.mark(dst->stream));   // src is read until then
   dst->W += src->W;
   dst->members += src->members;
   return PS_OK;
@@ -425,7 +375,7 @@ extern "C" int ps_peak_fetch_field(ps_peak* a, double* out) {
   if (!a || !out) return ps_fail(PS_ERR_BAD_ARG, "peak_fetch_field: bad arguments");
   if (!a->y_live) return ps_fail(PS_ERR_STATE, "peak_fetch_field: no member added yet");
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(peak_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   PS_HIP(hipMemcpyAsync(out, a->Y, (size_t)a->ncell * sizeof(double), hipMemcpyDeviceToHost, a->stream));
   PS_HIP(hipStreamSynchronize(a->stream));
   return PS_OK;
@@ -450,26 +400,26 @@ static int peak_map_out(ps_peak* a, void* out, size_t elem) {
 // nplane planes from `planes` on summed into the map scratch (as prob = C / W, or as uint32 C)
 static int peak_cum(ps_peak* a, const uint32_t* planes, int nplane, bool prob) {
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(peak_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   hipEvent_t e1 = nullptr;
-  PS_TRY(peak_prof_begin(a, a->prof_map, a->stream, &e1));
+  PS_TRY(a->prof.begin(1, a->stream, &e1));
   hipLaunchKernelGGL(k_peak_cum, dim3((unsigned)((a->ncell + 255) / 256)), dim3(256), 0, a->stream, planes, nplane,
                      a->ncell, a->pitch, (double)a->W, prob ? a->map : nullptr, prob ? nullptr : (uint32_t*)a->map);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, a->stream));
-  return peak_mark_last(a, a->stream);
+  PS_TRY(a->prof.end(a->stream, e1));
+  return a->last.mark(a->stream);
 }
 
 static int peak_quantile(ps_peak* a, const uint32_t* planes, int implied0, double p, int32_t* out) {
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(peak_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   hipEvent_t e1 = nullptr;
-  PS_TRY(peak_prof_begin(a, a->prof_map, a->stream, &e1));
+  PS_TRY(a->prof.begin(1, a->stream, &e1));
   hipLaunchKernelGGL(k_peak_quantile, dim3((unsigned)((a->ncell + 255) / 256)), dim3(256), 0, a->stream, planes,
                      a->nslot, implied0, a->ncell, a->pitch, (uint32_t)a->W, p * (double)a->W, (int32_t*)a->map);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, a->stream));
-  PS_TRY(peak_mark_last(a, a->stream));
+  PS_TRY(a->prof.end(a->stream, e1));
+  PS_TRY(a->last.mark(a->stream));
   return peak_map_out(a, out, sizeof(int32_t));
 }
 
@@ -478,7 +428,7 @@ extern "C" int ps_peak_fetch_day_counts(ps_peak* a, int slot, uint32_t* out) {
   if (slot < 0 || slot >= a->nslot)
     return ps_fail(PS_ERR_BAD_ARG, "peak_fetch_day_counts: slot %d of %d", slot, a->nslot);
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(peak_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   PS_HIP(hipMemcpyAsync(out, a->cnt + (int64_t)slot * a->pitch, (size_t)a->ncell * sizeof(uint32_t),
                         hipMemcpyDeviceToHost, a->stream));
   PS_HIP(hipStreamSynchronize(a->stream));
@@ -499,7 +449,7 @@ extern "C" int ps_peak_fetch_duration_counts(ps_peak* a, int k, int n, uint32_t*
     return PS_OK;
   }
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(peak_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   PS_HIP(hipMemcpyAsync(out, peak_du(a, k) + (int64_t)(n - 1) * a->pitch, nc * sizeof(uint32_t), hipMemcpyDeviceToHost,
                         a->stream));
   PS_HIP(hipStreamSynchronize(a->stream));
@@ -543,30 +493,25 @@ extern "C" int ps_peak_duration_mean(ps_peak* a, int k, double* out) {
   PS_TRY(peak_check_k(a, k, "peak_duration_mean"));
   PS_TRY(peak_check_w(a, "peak_duration_mean"));
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(peak_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   hipEvent_t e1 = nullptr;
-  PS_TRY(peak_prof_begin(a, a->prof_map, a->stream, &e1));
+  PS_TRY(a->prof.begin(1, a->stream, &e1));
   hipLaunchKernelGGL(k_peak_dur_mean, dim3((unsigned)((a->ncell + 255) / 256)), dim3(256), 0, a->stream, peak_du(a, k),
                      a->nslot, a->ncell, a->pitch, (double)a->W, a->map);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, a->stream));
-  PS_TRY(peak_mark_last(a, a->stream));
+  PS_TRY(a->prof.end(a->stream, e1));
+  PS_TRY(a->last.mark(a->stream));
   return peak_map_out(a, out, sizeof(double));
 }
 
 extern "C" int ps_peak_prof(ps_peak* a, int enable, double* add_ms, int64_t* adds, double* map_ms, int64_t* maps) {
   if (!a) return ps_fail(PS_ERR_BAD_ARG, "peak_prof: null handle");
   PS_HIP(hipSetDevice(a->device));
-  if (enable >= 0) a->prof_on = enable != 0;
+  a->prof.set(enable);
   double* ms_out[2] = {add_ms, map_ms};
   int64_t* n_out[2] = {adds, maps};
-  std::vector<std::pair<hipEvent_t, hipEvent_t>>* lists[2] = {&a->prof_add, &a->prof_map};
-  for (int k = 0; k < 2; ++k) {
-    if (!ms_out[k] && !n_out[k]) continue;
-    PS_TRY(peak_prof_fold(a, *lists[k]));
-    if (ms_out[k]) *ms_out[k] = a->prof_ms[k];
-    if (n_out[k]) *n_out[k] = a->prof_n[k];
-  }
+  for (int k = 0; k < 2; ++k)
+    if (ms_out[k] || n_out[k]) PS_TRY(a->prof.totals(k, ms_out[k], n_out[k]));
   return PS_OK;
 }
 
@@ -582,6 +527,6 @@ static int peak_view(void* h, PsProjectView* out) {
   out->device = a->device;
   return PS_OK;
 }
-static int peak_wait(void* h, hipStream_t stream) { return peak_after_last(static_cast<ps_peak*>(h), stream); }
-static int peak_mark(void* h, hipStream_t stream) { return peak_mark_last(static_cast<ps_peak*>(h), stream); }
+static int peak_wait(void* h, hipStream_t stream) { return static_cast<ps_peak*>(h)->last.wait(stream); }
+static int peak_mark(void* h, hipStream_t stream) { return static_cast<ps_peak*>(h)->last.mark(stream); }
 PsFieldsOps ps_peak_fields() { return PsFieldsOps{"peak maps", peak_view, peak_wait, peak_mark}; }

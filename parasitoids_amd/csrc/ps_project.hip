@@ -127,34 +127,19 @@ struct ps_project {
   int64_t g_cap = 0;
   int64_t applies = 0;
   hipStream_t stream = nullptr;    // fetch / gather
-  hipEvent_t ev = nullptr;         // the last operation on Y, on whatever stream it ran
-  bool ev_live = false;
-  bool prof_on = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof;
+  PsLastOp last;                   // the last operation on Y, on whatever stream it ran
+  PsProf prof;                     // channel 0: the applies
 };
-
-static int proj_after_last(ps_project* p, hipStream_t stream) {
-  if (p->ev_live) PS_HIP(hipStreamWaitEvent(stream, p->ev, 0));
-  return PS_OK;
-}
-static int proj_mark_last(ps_project* p, hipStream_t stream) {
-  PS_HIP(hipEventRecord(p->ev, stream));
-  p->ev_live = true;
-  return PS_OK;
-}
 
 extern "C" void ps_project_destroy(ps_project* p) {
   if (!p) return;
   (void)hipSetDevice(p->device);
-  if (p->ev_live) (void)hipEventSynchronize(p->ev);
+  p->last.sync();
   if (p->stream) (void)hipStreamSynchronize(p->stream);
-  for (auto& e : p->prof) {
-    (void)hipEventDestroy(e.first);
-    (void)hipEventDestroy(e.second);
-  }
+  p->prof.release();
   for (void* q : {(void*)p->tiles, (void*)p->Y, (void*)p->g_cell, (void*)p->g_out})
     if (q) (void)hipFree(q);
-  if (p->ev) (void)hipEventDestroy(p->ev);
+  p->last.destroy();
   if (p->stream) (void)hipStreamDestroy(p->stream);
   delete p;
 }
@@ -220,7 +205,7 @@ extern "C" int ps_project_create(int device, int N, int nin, int nout, const dou
   };
   const size_t tile_b = (size_t)ntile * sizeof(ProjTile), y_b = (size_t)nout * pitch * sizeof(double);
   hipError_t e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&p->ev, hipEventDisableTiming);
+  if (e == hipSuccess) e = p->last.create();
   if (e == hipSuccess) e = hipMalloc((void**)&p->tiles, tile_b);
   if (e == hipSuccess) e = hipMalloc((void**)&p->Y, y_b);
   if (e == hipSuccess) e = hipMemcpyAsync(p->tiles, p->host_tiles.data(), tile_b, hipMemcpyHostToDevice, p->stream);
@@ -252,19 +237,14 @@ extern "C" int ps_project_apply(ps_project* p, ps_solver* s, int nin, const int3
     stream = v.stream;
   }
   for (int i = nin; i < PS_PROJ_MAX_IN; ++i) desc.s[i] = ProjSlot{nullptr, nullptr, 0.0, 0.0};
-  PS_TRY(proj_after_last(p, stream));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (p->prof_on) {
-    PS_HIP(hipEventCreate(&e0));
-    PS_HIP(hipEventCreate(&e1));
-    p->prof.push_back({e0, e1});
-    PS_HIP(hipEventRecord(e0, stream));
-  }
+  PS_TRY(p->last.wait(stream));
+  hipEvent_t e1 = nullptr;
+  PS_TRY(p->prof.begin(0, stream, &e1));
   hipLaunchKernelGGL(k_project_apply, dim3(p->nblk, p->ntile), dim3(PS_PROJ_THREADS), 0, stream, desc, p->tiles, p->Y,
                      p->nout, p->ncell, p->pitch, negval);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, stream));
-  PS_TRY(proj_mark_last(p, stream));
+  PS_TRY(p->prof.end(stream, e1));
+  PS_TRY(p->last.mark(stream));
   p->applies += 1;
   return PS_OK;
 }
@@ -274,7 +254,7 @@ extern "C" int ps_project_fetch(ps_project* p, int e, double* out) {
   if (e < 0 || e >= p->nout) return ps_fail(PS_ERR_BAD_ARG, "project_fetch: output %d of %d", e, p->nout);
   if (p->applies == 0) return ps_fail(PS_ERR_STATE, "project_fetch: nothing projected yet");
   PS_HIP(hipSetDevice(p->device));
-  PS_TRY(proj_after_last(p, p->stream));
+  PS_TRY(p->last.wait(p->stream));
   PS_HIP(hipMemcpyAsync(out, p->Y + (int64_t)e * p->pitch, (size_t)p->ncell * sizeof(double), hipMemcpyDeviceToHost,
                         p->stream));
   PS_HIP(hipStreamSynchronize(p->stream));
@@ -303,7 +283,7 @@ extern "C" int ps_project_gather(ps_project* p, int64_t n, const int32_t* rows, 
     PS_HIP(hipMalloc((void**)&p->g_out, (size_t)n * p->nout * sizeof(double)));
     p->g_cap = n;
   }
-  PS_TRY(proj_after_last(p, p->stream));
+  PS_TRY(p->last.wait(p->stream));
   PS_HIP(hipMemcpyAsync(p->g_cell, cell.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, p->stream));
   const int64_t total = n * p->nout;
   hipLaunchKernelGGL(k_project_gather, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, p->stream, p->Y, p->pitch,
@@ -326,18 +306,8 @@ extern "C" int ps_project_info(ps_project* p, int* N, int* nin, int* nout, int64
 extern "C" int ps_project_prof(ps_project* p, int enable, double* total_ms, int64_t* launches) {
   if (!p) return ps_fail(PS_ERR_BAD_ARG, "project_prof: null handle");
   PS_HIP(hipSetDevice(p->device));
-  if (enable >= 0) p->prof_on = enable != 0;
-  if (total_ms || launches) {
-    double ms = 0.0;
-    for (auto& e : p->prof) {
-      PS_HIP(hipEventSynchronize(e.second));
-      float t = 0.f;
-      PS_HIP(hipEventElapsedTime(&t, e.first, e.second));
-      ms += t;
-    }
-    if (total_ms) *total_ms = ms;
-    if (launches) *launches = (int64_t)p->prof.size();
-  }
+  p->prof.set(enable);
+  if (total_ms || launches) PS_TRY(p->prof.totals(0, total_ms, launches));
   return PS_OK;
 }
 
@@ -352,6 +322,6 @@ static int proj_view(void* h, PsProjectView* out) {
   out->device = p->device;
   return PS_OK;
 }
-static int proj_wait(void* h, hipStream_t stream) { return proj_after_last(static_cast<ps_project*>(h), stream); }
-static int proj_mark(void* h, hipStream_t stream) { return proj_mark_last(static_cast<ps_project*>(h), stream); }
+static int proj_wait(void* h, hipStream_t stream) { return static_cast<ps_project*>(h)->last.wait(stream); }
+static int proj_mark(void* h, hipStream_t stream) { return static_cast<ps_project*>(h)->last.mark(stream); }
 PsFieldsOps ps_project_fields() { return PsFieldsOps{"projection", proj_view, proj_wait, proj_mark}; }

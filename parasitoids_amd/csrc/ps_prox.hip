@@ -112,10 +112,6 @@ __global__ void k_prox_gather(const double* __restrict__ Z, int64_t pitch, int n
 
 }  // namespace
 
-struct ProxProf {
-  hipEvent_t e0, e1, e2;   // before the mask, between the row and the column pass, after
-};
-
 struct ps_prox {
   int device = 0, N = 0, nin = 0, nout = 0;
   int64_t ncell = 0, pitch = 0;
@@ -132,51 +128,19 @@ struct ps_prox {
   int64_t g_cap = 0;
   int64_t applies = 0;
   hipStream_t stream = nullptr;    // fetch / gather / apply of another fields source
-  hipEvent_t ev = nullptr;         // the last operation on the handle's buffers, on whatever stream it ran
-  bool ev_live = false;
-  bool prof_on = false;
-  std::vector<ProxProf> prof;
-  double prof_ms[2] = {0.0, 0.0};  // applies already folded out of the list above: the row pass, the column pass
-  int64_t prof_n = 0;
+  PsLastOp last;                   // the last operation on the handle's buffers, on whatever stream it ran
+  PsProf prof;                     // channel 0: the mask and the row pass, 1: the column pass
 };
-
-static int prox_after_last(ps_prox* c, hipStream_t stream) {
-  if (c->ev_live) PS_HIP(hipStreamWaitEvent(stream, c->ev, 0));
-  return PS_OK;
-}
-static int prox_mark_last(ps_prox* c, hipStream_t stream) {
-  PS_HIP(hipEventRecord(c->ev, stream));
-  c->ev_live = true;
-  return PS_OK;
-}
-// the finished triples into the handle's totals, their events destroyed (as ps_nbhd_prof)
-static const size_t PROX_PROF_PENDING = 256;
-static int prox_prof_fold(ps_prox* c) {
-  for (auto& p : c->prof) {
-    PS_HIP(hipEventSynchronize(p.e2));
-    float t = 0.f;
-    PS_HIP(hipEventElapsedTime(&t, p.e0, p.e1));
-    c->prof_ms[0] += t;
-    PS_HIP(hipEventElapsedTime(&t, p.e1, p.e2));
-    c->prof_ms[1] += t;
-    c->prof_n += 1;
-  }
-  for (auto& p : c->prof)
-    for (hipEvent_t e : {p.e0, p.e1, p.e2}) (void)hipEventDestroy(e);
-  c->prof.clear();
-  return PS_OK;
-}
 
 extern "C" void ps_prox_destroy(ps_prox* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  if (c->ev_live) (void)hipEventSynchronize(c->ev);
+  c->last.sync();
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  for (auto& p : c->prof)
-    for (hipEvent_t e : {p.e0, p.e1, p.e2}) (void)hipEventDestroy(e);
+  c->prof.release();
   for (void* q : {(void*)c->Z, (void*)c->d2, (void*)c->g, (void*)c->mask, (void*)c->g_cell, (void*)c->g_out})
     if (q) (void)hipFree(q);
-  if (c->ev) (void)hipEventDestroy(c->ev);
+  c->last.destroy();
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
@@ -237,7 +201,7 @@ extern "C" int ps_prox_create(int device, int N, int nin, int nout, const int32_
   // the device's limit, not this handle's need: the attribute is the kernel's, shared by every handle
   hipError_t e = hipFuncSetAttribute((const void*)k_prox_cols, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev, hipEventDisableTiming);
+  if (e == hipSuccess) e = c->last.create();
   if (e == hipSuccess) e = hipMalloc((void**)&c->Z, z_b);
   if (e == hipSuccess) e = hipMalloc((void**)&c->d2, d_b);
   if (e == hipSuccess) e = hipMalloc((void**)&c->g, g_b);
@@ -264,23 +228,17 @@ extern "C" int ps_prox_set_strip(ps_prox* c, int width) {
 
 // the three launches over the resolved descriptors on `stream`, behind the handle's last operation
 static int prox_launch(ps_prox* c, const ProxSlots& desc, hipStream_t stream, double negval) {
-  PS_TRY(prox_after_last(c, stream));
-  ProxProf pp{nullptr, nullptr, nullptr};
-  if (c->prof_on) {
-    if (c->prof.size() >= PROX_PROF_PENDING) PS_TRY(prox_prof_fold(c));
-    PS_HIP(hipEventCreate(&pp.e0));
-    PS_HIP(hipEventCreate(&pp.e1));
-    PS_HIP(hipEventCreate(&pp.e2));
-    c->prof.push_back(pp);
-    PS_HIP(hipEventRecord(pp.e0, stream));
-  }
+  PS_TRY(c->last.wait(stream));
+  hipEvent_t e1 = nullptr;
+  PS_TRY(c->prof.begin(0, stream, &e1));
   hipLaunchKernelGGL(k_prox_mask, dim3((unsigned)((c->pitch + 255) / 256), c->nout), dim3(256), 0, stream, desc, c->tab,
                      c->mask, c->ncell, c->pitch, negval);
   PS_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_prox_rows, dim3((unsigned)((c->ncell + 255) / 256), c->nout), dim3(256), 0, stream, c->mask, c->g,
                      c->N, c->ncell, c->pitch);
   PS_HIP(hipGetLastError());
-  if (pp.e1) PS_HIP(hipEventRecord(pp.e1, stream));
+  PS_TRY(c->prof.end(stream, e1));
+  PS_TRY(c->prof.begin(1, stream, &e1));
   const int W = c->width;
   const int nstrip = (c->N + W - 1) / W;
   // one workgroup per CU where the strips and outputs alone leave some idle; a share is whole passes of the
@@ -293,8 +251,8 @@ static int prox_launch(ps_prox* c, const ProxSlots& desc, hipStream_t stream, do
   hipLaunchKernelGGL(k_prox_cols, dim3(nstrip, shares, c->nout), dim3(PX_THREADS), (size_t)W * c->N * 2, stream, c->g,
                      c->d2, c->Z, c->N, c->pitch, W, rows, c->cell_m);
   PS_HIP(hipGetLastError());
-  if (pp.e2) PS_HIP(hipEventRecord(pp.e2, stream));
-  PS_TRY(prox_mark_last(c, stream));
+  PS_TRY(c->prof.end(stream, e1));
+  PS_TRY(c->last.mark(stream));
   c->applies += 1;
   return PS_OK;
 }
@@ -357,7 +315,7 @@ static int prox_fetch_plane(ps_prox* c, int e, const void* base, size_t cell_b, 
   if (e < 0 || e >= c->nout) return ps_fail(PS_ERR_BAD_ARG, "%s: output %d of %d", who, e, c->nout);
   if (c->applies == 0) return ps_fail(PS_ERR_STATE, "%s: nothing applied yet", who);
   PS_HIP(hipSetDevice(c->device));
-  PS_TRY(prox_after_last(c, c->stream));
+  PS_TRY(c->last.wait(c->stream));
   PS_HIP(hipMemcpyAsync(out, (const char*)base + (size_t)e * c->pitch * cell_b, (size_t)c->ncell * cell_b,
                         hipMemcpyDeviceToHost, c->stream));
   PS_HIP(hipStreamSynchronize(c->stream));
@@ -394,7 +352,7 @@ extern "C" int ps_prox_gather(ps_prox* c, int64_t n, const int32_t* rows, const 
     PS_HIP(hipMalloc((void**)&c->g_out, (size_t)n * c->nout * sizeof(double)));
     c->g_cap = n;
   }
-  PS_TRY(prox_after_last(c, c->stream));
+  PS_TRY(c->last.wait(c->stream));
   PS_HIP(hipMemcpyAsync(c->g_cell, cell.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
   const int64_t total = n * c->nout;
   hipLaunchKernelGGL(k_prox_gather, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, c->Z, c->pitch,
@@ -418,14 +376,9 @@ extern "C" int ps_prox_info(ps_prox* c, int* N, int* nin, int* nout, int64_t* ap
 extern "C" int ps_prox_prof(ps_prox* c, int enable, double* row_ms, int64_t* row_n, double* col_ms, int64_t* col_n) {
   if (!c) return ps_fail(PS_ERR_BAD_ARG, "prox_prof: null handle");
   PS_HIP(hipSetDevice(c->device));
-  if (enable >= 0) c->prof_on = enable != 0;
-  if (row_ms || row_n || col_ms || col_n) {
-    PS_TRY(prox_prof_fold(c));
-    if (row_ms) *row_ms = c->prof_ms[0];
-    if (col_ms) *col_ms = c->prof_ms[1];
-    if (row_n) *row_n = c->prof_n;
-    if (col_n) *col_n = c->prof_n;
-  }
+  c->prof.set(enable);
+  if (row_ms || row_n) PS_TRY(c->prof.totals(0, row_ms, row_n));
+  if (col_ms || col_n) PS_TRY(c->prof.totals(1, col_ms, col_n));
   return PS_OK;
 }
 
@@ -440,6 +393,6 @@ static int prox_view(void* h, PsProjectView* out) {
   out->device = c->device;
   return PS_OK;
 }
-static int prox_wait(void* h, hipStream_t stream) { return prox_after_last(static_cast<ps_prox*>(h), stream); }
-static int prox_mark(void* h, hipStream_t stream) { return prox_mark_last(static_cast<ps_prox*>(h), stream); }
+static int prox_wait(void* h, hipStream_t stream) { return static_cast<ps_prox*>(h)->last.wait(stream); }
+static int prox_mark(void* h, hipStream_t stream) { return static_cast<ps_prox*>(h)->last.mark(stream); }
 PsFieldsOps ps_prox_fields() { return PsFieldsOps{"proximity fields", prox_view, prox_wait, prox_mark}; }

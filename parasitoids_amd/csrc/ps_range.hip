@@ -287,10 +287,8 @@ struct ps_range {
   int64_t members = 0;
   std::vector<uint32_t> weights;   // per member, in row order
   hipStream_t stream = nullptr;    // reset / merge / maps / fetch / row growth
-  hipEvent_t ev = nullptr;         // the last operation, on whatever stream it ran
-  bool ev_live = false;
-  bool prof_on = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_add, prof_map;
+  PsLastOp last;                   // the last operation, on whatever stream it ran
+  PsProf prof;                     // channel 0: the adds, 1: the maps
 };
 
 static int64_t rng_row_len(const ps_range* a) { return (int64_t)a->nfrac * a->nslot; }
@@ -305,28 +303,6 @@ static int rng_alloc(void** p, size_t bytes, const char* what) {
   if (bytes > free_b)
     return ps_fail(PS_ERR_OOM, "range: %s needs %.3g GB, %.3g GB free", what, (double)bytes * 1e-9, (double)free_b * 1e-9);
   PS_HIP(hipMalloc(p, bytes));
-  return PS_OK;
-}
-
-static int rng_after_last(ps_range* a, hipStream_t stream) {
-  if (a->ev_live) PS_HIP(hipStreamWaitEvent(stream, a->ev, 0));
-  return PS_OK;
-}
-static int rng_mark_last(ps_range* a, hipStream_t stream) {
-  PS_HIP(hipEventRecord(a->ev, stream));
-  a->ev_live = true;
-  return PS_OK;
-}
-static int rng_prof_begin(ps_range* a, std::vector<std::pair<hipEvent_t, hipEvent_t>>& v, hipStream_t stream,
-                          hipEvent_t* end) {
-  *end = nullptr;
-  if (!a->prof_on) return PS_OK;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  PS_HIP(hipEventCreate(&e0));
-  PS_HIP(hipEventCreate(&e1));
-  v.push_back({e0, e1});
-  PS_HIP(hipEventRecord(e0, stream));
-  *end = e1;
   return PS_OK;
 }
 
@@ -353,7 +329,7 @@ static int rng_reserve_rows(ps_range* a, int64_t need) {
   }
   if (a->rows_cap > 0) {
     hipError_t e = hipSuccess;
-    if (a->ev_live) e = hipStreamWaitEvent(a->stream, a->ev, 0);
+    if (a->last.live) e = hipStreamWaitEvent(a->stream, a->last.ev, 0);
     for (int t = 0; t < 4 && e == hipSuccess && a->members > 0; ++t)
       e = hipMemcpyAsync(p[t], old[t], (size_t)a->members * row_b[t], hipMemcpyDeviceToDevice, a->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(a->stream);
@@ -374,16 +350,12 @@ static int rng_reserve_rows(ps_range* a, int64_t need) {
 extern "C" void ps_range_destroy(ps_range* a) {
   if (!a) return;
   (void)hipSetDevice(a->device);
-  if (a->ev_live) (void)hipEventSynchronize(a->ev);
+  a->last.sync();
   if (a->stream) (void)hipStreamSynchronize(a->stream);
-  for (auto* v : {&a->prof_add, &a->prof_map})
-    for (auto& p : *v) {
-      (void)hipEventDestroy(p.first);
-      (void)hipEventDestroy(p.second);
-    }
+  a->prof.release();
   for (void* p : {(void*)a->cnt, (void*)a->st, (void*)a->lam, (void*)a->n, (void*)a->Q, (void*)a->E, (void*)a->map})
     if (p) (void)hipFree(p);
-  if (a->ev) (void)hipEventDestroy(a->ev);
+  a->last.destroy();
   if (a->stream) (void)hipStreamDestroy(a->stream);
   delete a;
 }
@@ -391,23 +363,15 @@ extern "C" void ps_range_destroy(ps_range* a) {
 extern "C" int ps_range_reset(ps_range* a) {
   if (!a) return ps_fail(PS_ERR_BAD_ARG, "range_reset: null handle");
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(rng_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   PS_HIP(hipMemsetAsync(a->cnt, 0, rng_cnt_bytes(a), a->stream));
   PS_HIP(hipMemsetAsync(a->st, 0, sizeof(RangeState), a->stream));
-  PS_TRY(rng_mark_last(a, a->stream));
+  PS_TRY(a->last.mark(a->stream));
   a->W = 0;
   a->members = 0;
   a->weights.clear();
-  if (!a->prof_add.empty() || !a->prof_map.empty()) {   // the timings so far go with the members
-    PS_HIP(hipStreamSynchronize(a->stream));
-    for (auto* v : {&a->prof_add, &a->prof_map}) {
-      for (auto& p : *v) {
-        (void)hipEventDestroy(p.first);
-        (void)hipEventDestroy(p.second);
-      }
-      v->clear();
-    }
-  }
+  if (!a->prof.idle()) PS_HIP(hipStreamSynchronize(a->stream));
+  a->prof.release();   // the timings so far go with the members
   return PS_OK;
 }
 
@@ -450,7 +414,7 @@ extern "C" int ps_range_create(int device, int N, int nslot, int nfrac, const do
     return rc;
   };
   hipError_t e = hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&a->ev, hipEventDisableTiming);
+  if (e == hipSuccess) e = a->last.create();
   if (e != hipSuccess) return fail(ps_fail(PS_ERR_HIP, "range_create: %s", hipGetErrorString(e)));
   int rc = rng_alloc((void**)&a->cnt, rng_cnt_bytes(a), "the count planes");
   if (rc == PS_OK) rc = rng_alloc((void**)&a->st, sizeof(RangeState), "the pass scratch");
@@ -471,9 +435,9 @@ extern "C" int ps_range_reserve(ps_range* a, int64_t members) {
 // one member from the slot descriptors (one per slot of the handle, the rest null), enqueued on `stream`
 static int rng_launch(ps_range* a, const RngSlots& desc, hipStream_t stream, double negval, uint32_t weight) {
   PS_TRY(rng_reserve_rows(a, a->members + 1));
-  PS_TRY(rng_after_last(a, stream));
+  PS_TRY(a->last.wait(stream));
   hipEvent_t e1 = nullptr;
-  PS_TRY(rng_prof_begin(a, a->prof_add, stream, &e1));
+  PS_TRY(a->prof.begin(0, stream, &e1));
   const int64_t nks = rng_row_len(a);
   double* lam = a->lam + a->members * nks;
   uint32_t* n = a->n + a->members * nks;
@@ -494,8 +458,8 @@ static int rng_launch(ps_range* a, const RngSlots& desc, hipStream_t stream, dou
   hipLaunchKernelGGL(k_range_count, dim3(nbh, a->nslot), dim3(PS_RNG_THREADS), 0, stream, desc, a->st, a->nslot,
                      a->nfrac, a->cnt, n, a->ncell, a->pitch, negval, weight);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, stream));
-  PS_TRY(rng_mark_last(a, stream));
+  PS_TRY(a->prof.end(stream, e1));
+  PS_TRY(a->last.mark(stream));
   a->W += weight;
   a->members += 1;
   a->weights.push_back(weight);
@@ -570,8 +534,8 @@ extern "C" int ps_range_merge(ps_range* dst, ps_range* src) {
   if (src->members == 0) return PS_OK;
   PS_HIP(hipSetDevice(dst->device));
   PS_TRY(rng_reserve_rows(dst, dst->members + src->members));
-  PS_TRY(rng_after_last(dst, dst->stream));
-  PS_TRY(rng_after_last(src, dst->stream));
+  PS_TRY(dst->last.wait(dst->stream));
+  PS_TRY(src->last.wait(dst->stream));
   hipLaunchKernelGGL(k_range_merge, dim3(2048), dim3(256), 0, dst->stream, dst->cnt, src->cnt,
                      rng_row_len(dst) * dst->pitch);
   PS_HIP(hipGetLastError());
@@ -584,8 +548,8 @@ extern "C" int ps_range_merge(ps_range* dst, ps_range* src) {
                         dst->stream));
   PS_HIP(hipMemcpyAsync(dst->E + m0 * ns, src->E, (size_t)(m1 * ns) * sizeof(int32_t), hipMemcpyDeviceToDevice,
                         dst->stream));
-  PS_TRY(rng_mark_last(dst, dst->stream));
-  PS_TRY(rng_mark_last(src, dst->stream));   // src is read until then
+  PS_TRY(dst->last.mark(dst->stream));
+  PS_TRY(src->last.mark(dst->stream));   // src is read until then
   dst->W += src->W;
   dst->members += src->members;
   dst->weights.insert(dst->weights.end(), src->weights.begin(), src->weights.end());
@@ -614,15 +578,15 @@ extern "C" int ps_range_prob(ps_range* a, int j, int slot, double* out) {
   if (!a || !out) return ps_fail(PS_ERR_BAD_ARG, "range_prob: bad arguments");
   PS_TRY(rng_check(a, j, slot, "range_prob"));
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(rng_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   hipEvent_t e1 = nullptr;
-  PS_TRY(rng_prof_begin(a, a->prof_map, a->stream, &e1));
+  PS_TRY(a->prof.begin(1, a->stream, &e1));
   const uint32_t* c = a->cnt + ((int64_t)j * a->nslot + slot) * a->pitch;
   hipLaunchKernelGGL(k_range_prob, dim3((unsigned)((a->ncell + 255) / 256)), dim3(256), 0, a->stream, c, a->ncell,
                      (double)a->W, a->map);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, a->stream));
-  PS_TRY(rng_mark_last(a, a->stream));
+  PS_TRY(a->prof.end(a->stream, e1));
+  PS_TRY(a->last.mark(a->stream));
   PS_HIP(hipMemcpyAsync(out, a->map, (size_t)a->ncell * sizeof(double), hipMemcpyDeviceToHost, a->stream));
   PS_HIP(hipStreamSynchronize(a->stream));
   return PS_OK;
@@ -632,7 +596,7 @@ extern "C" int ps_range_fetch_counts(ps_range* a, int j, int slot, uint32_t* out
   if (!a || !out) return ps_fail(PS_ERR_BAD_ARG, "range_fetch_counts: bad arguments");
   PS_TRY(rng_check(a, j, slot, "range_fetch_counts"));
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(rng_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   const uint32_t* src = a->cnt + ((int64_t)j * a->nslot + slot) * a->pitch;
   PS_HIP(hipMemcpyAsync(out, src, (size_t)a->ncell * sizeof(uint32_t), hipMemcpyDeviceToHost, a->stream));
   PS_HIP(hipStreamSynchronize(a->stream));
@@ -647,7 +611,7 @@ extern "C" int ps_range_fetch_members(ps_range* a, int j, int slot, double* lamb
     for (int64_t r = 0; r < m; ++r) weights[r] = a->weights[(size_t)r];
   if (!lambda && !cells) return PS_OK;
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(rng_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   std::vector<double> hl;
   std::vector<uint32_t> hn;
   if (lambda) {
@@ -672,7 +636,7 @@ extern "C" int ps_range_fetch_mass(ps_range* a, int slot, uint64_t* Q, int32_t* 
   const int64_t m = a->members, ns = a->nslot;
   if (!Q && !E) return PS_OK;
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(rng_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   std::vector<uint64_t> hq((size_t)(m * ns));
   std::vector<int32_t> he((size_t)(m * ns));
   PS_HIP(hipMemcpyAsync(hq.data(), a->Q, hq.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, a->stream));
@@ -688,21 +652,10 @@ extern "C" int ps_range_fetch_mass(ps_range* a, int slot, uint64_t* Q, int32_t* 
 extern "C" int ps_range_prof(ps_range* a, int enable, double* add_ms, int64_t* adds, double* map_ms, int64_t* maps) {
   if (!a) return ps_fail(PS_ERR_BAD_ARG, "range_prof: null handle");
   PS_HIP(hipSetDevice(a->device));
-  if (enable >= 0) a->prof_on = enable != 0;
+  a->prof.set(enable);
   double* ms_out[2] = {add_ms, map_ms};
   int64_t* n_out[2] = {adds, maps};
-  std::vector<std::pair<hipEvent_t, hipEvent_t>>* lists[2] = {&a->prof_add, &a->prof_map};
-  for (int k = 0; k < 2; ++k) {
-    if (!ms_out[k] && !n_out[k]) continue;
-    double ms = 0.0;
-    for (auto& p : *lists[k]) {
-      PS_HIP(hipEventSynchronize(p.second));
-      float t = 0.f;
-      PS_HIP(hipEventElapsedTime(&t, p.first, p.second));
-      ms += t;
-    }
-    if (ms_out[k]) *ms_out[k] = ms;
-    if (n_out[k]) *n_out[k] = (int64_t)lists[k]->size();
-  }
+  for (int k = 0; k < 2; ++k)
+    if (ms_out[k] || n_out[k]) PS_TRY(a->prof.totals(k, ms_out[k], n_out[k]));
   return PS_OK;
 }

@@ -216,10 +216,8 @@ struct ps_sens {
   int64_t members = 0;
   bool finalized = false;
   hipStream_t stream = nullptr;   // reset / merge / finalize / fetch, and the adds from fields
-  hipEvent_t ev = nullptr;        // the last operation, on whatever stream it ran
-  bool ev_live = false;
-  bool prof_on = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof;
+  PsLastOp last;                  // the last operation, on whatever stream it ran
+  PsProf prof;                    // channel 0: the adds
 };
 
 static int64_t sens_total(const ps_sens* a) { return (int64_t)a->nslot * a->pitch; }
@@ -229,29 +227,16 @@ static double sens_block_bytes(int nparam, int nslot, int64_t pitch) {
   return ((double)(nparam + 3) * sizeof(double) + 1.0) * (double)nslot * (double)pitch;
 }
 
-static int sens_after_last(ps_sens* a, hipStream_t stream) {
-  if (a->ev_live) PS_HIP(hipStreamWaitEvent(stream, a->ev, 0));
-  return PS_OK;
-}
-static int sens_mark_last(ps_sens* a, hipStream_t stream) {
-  PS_HIP(hipEventRecord(a->ev, stream));
-  a->ev_live = true;
-  return PS_OK;
-}
-
 static bool sens_finite(double v) { return v == v && !isinf(v); }
 
 extern "C" void ps_sens_destroy(ps_sens* a) {
   if (!a) return;
   (void)hipSetDevice(a->device);
-  if (a->ev_live) (void)hipEventSynchronize(a->ev);
+  a->last.sync();
   if (a->stream) (void)hipStreamSynchronize(a->stream);
-  for (auto& p : a->prof) {
-    (void)hipEventDestroy(p.first);
-    (void)hipEventDestroy(p.second);
-  }
+  a->prof.release();
   if (a->block) (void)hipFree(a->block);
-  if (a->ev) (void)hipEventDestroy(a->ev);
+  a->last.destroy();
   if (a->stream) (void)hipStreamDestroy(a->stream);
   delete a;
 }
@@ -259,9 +244,9 @@ extern "C" void ps_sens_destroy(ps_sens* a) {
 extern "C" int ps_sens_reset(ps_sens* a) {
   if (!a) return ps_fail(PS_ERR_BAD_ARG, "sens_reset: null handle");
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(sens_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   PS_HIP(hipMemsetAsync(a->block, 0, (size_t)sens_block_bytes(a->nparam, a->nslot, a->pitch), a->stream));
-  PS_TRY(sens_mark_last(a, a->stream));
+  PS_TRY(a->last.mark(a->stream));
   a->W = 0;
   a->members = 0;
   a->finalized = false;
@@ -295,7 +280,7 @@ extern "C" int ps_sens_create(int device, int N, int nslot, int nparam, ps_sens*
     return rc;
   };
   hipError_t e = hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&a->ev, hipEventDisableTiming);
+  if (e == hipSuccess) e = a->last.create();
   if (e == hipSuccess) e = hipMalloc((void**)&a->block, (size_t)need);
   if (e != hipSuccess)
     return fail(ps_fail(e == hipErrorOutOfMemory ? PS_ERR_OOM : PS_ERR_HIP, "sens_create: %s", hipGetErrorString(e)));
@@ -328,14 +313,9 @@ static int sens_check_add(ps_sens* a, const char* who, int nparam, const double*
 static int sens_launch(ps_sens* a, const std::vector<SensSlot>& d, hipStream_t stream, double negval, const double* e,
                        uint32_t weight) {
   const int nslot = a->nslot;
-  PS_TRY(sens_after_last(a, stream));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (a->prof_on) {
-    PS_HIP(hipEventCreate(&e0));
-    PS_HIP(hipEventCreate(&e1));
-    a->prof.push_back({e0, e1});
-    PS_HIP(hipEventRecord(e0, stream));
-  }
+  PS_TRY(a->last.wait(stream));
+  hipEvent_t e1 = nullptr;
+  PS_TRY(a->prof.begin(0, stream, &e1));
   SensDev dev;
   for (int i = 0; i < PS_SENS_MAX_PARAM; ++i) dev.e[i] = i < a->nparam ? e[i] : 0.0;
   const double Wn = (double)(a->W + weight);
@@ -350,8 +330,8 @@ static int sens_launch(ps_sens* a, const std::vector<SensSlot>& d, hipStream_t s
                        a->C, a->ncell, a->pitch, sens_total(a), dev, negval, (double)weight, Wn);
     PS_HIP(hipGetLastError());
   }
-  if (e1) PS_HIP(hipEventRecord(e1, stream));
-  PS_TRY(sens_mark_last(a, stream));
+  PS_TRY(a->prof.end(stream, e1));
+  PS_TRY(a->last.mark(stream));
   a->W += weight;
   a->members += 1;
   a->finalized = false;
@@ -429,8 +409,8 @@ extern "C" int ps_sens_merge(ps_sens* dst, ps_sens* src, int nparam, const doubl
   dst->finalized = false;
   if (src->W == 0) return PS_OK;
   PS_HIP(hipSetDevice(dst->device));
-  PS_TRY(sens_after_last(dst, dst->stream));
-  PS_TRY(sens_after_last(src, dst->stream));
+  PS_TRY(dst->last.wait(dst->stream));
+  PS_TRY(src->last.wait(dst->stream));
   if (dst->W == 0) {   // a copy: the merged handle is src bit for bit
     PS_HIP(hipMemcpyAsync(dst->block, src->block, sens_acc_bytes(dst), hipMemcpyDeviceToDevice, dst->stream));
   } else {
@@ -440,8 +420,8 @@ extern "C" int ps_sens_merge(ps_sens* dst, ps_sens* src, int nparam, const doubl
                        src->m2, src->C, sens_total(dst), nparam, dt, (double)dst->W, (double)src->W);
     PS_HIP(hipGetLastError());
   }
-  PS_TRY(sens_mark_last(dst, dst->stream));
-  PS_TRY(sens_mark_last(src, dst->stream));   // src is read until then
+  PS_TRY(dst->last.mark(dst->stream));
+  PS_TRY(src->last.mark(dst->stream));   // src is read until then
   dst->W += src->W;
   dst->members += src->members;
   return PS_OK;
@@ -466,14 +446,14 @@ extern "C" int ps_sens_finalize(ps_sens* a, int nparam, int rank, const double* 
   }
   if (a->W == 0) return ps_fail(PS_ERR_STATE, "sens_finalize: nothing accumulated (W = 0)");
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(sens_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   const int64_t total = sens_total(a);
   const int threads = 256;
   const int bx = (int)std::min<int64_t>((total / 2 + threads - 1) / threads, 8192);
   hipLaunchKernelGGL(k_sens_finalize, dim3(bx), dim3(threads), 0, a->stream, a->m2, a->C, a->expl, a->dom, total,
                      a->nparam, rank, f, (double)a->W);
   PS_HIP(hipGetLastError());
-  PS_TRY(sens_mark_last(a, a->stream));
+  PS_TRY(a->last.mark(a->stream));
   a->finalized = true;
   return PS_OK;
 }
@@ -489,7 +469,7 @@ extern "C" int ps_sens_fetch(ps_sens* a, int slot, int what, double* out) {
   if (a->W == 0) return ps_fail(PS_ERR_STATE, "sens_fetch: nothing accumulated (W = 0)");
   if (fin && !a->finalized) return ps_fail(PS_ERR_STATE, "sens_fetch: quantity %d is not finalized since the last change", what);
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(sens_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   const double W = (double)a->W;
   const size_t n = (size_t)a->ncell;
   const int64_t off = (int64_t)slot * a->pitch;
@@ -519,17 +499,7 @@ extern "C" int ps_sens_info(ps_sens* a, double* total_weight, int64_t* members) 
 extern "C" int ps_sens_prof(ps_sens* a, int enable, double* total_ms, int64_t* launches) {
   if (!a) return ps_fail(PS_ERR_BAD_ARG, "sens_prof: null handle");
   PS_HIP(hipSetDevice(a->device));
-  if (enable >= 0) a->prof_on = enable != 0;
-  if (total_ms || launches) {
-    double ms = 0.0;
-    for (auto& p : a->prof) {
-      PS_HIP(hipEventSynchronize(p.second));
-      float t = 0.f;
-      PS_HIP(hipEventElapsedTime(&t, p.first, p.second));
-      ms += t;
-    }
-    if (total_ms) *total_ms = ms;
-    if (launches) *launches = (int64_t)a->prof.size();
-  }
+  a->prof.set(enable);
+  if (total_ms || launches) PS_TRY(a->prof.totals(0, total_ms, launches));
   return PS_OK;
 }

@@ -120,21 +120,10 @@ struct ps_sites {
   int64_t passes = 0;              // completed passes: the last group applied
   bool complete = false;           // Y holds a whole plan (no pass under way)
   hipStream_t stream = nullptr;    // fetch / gather
-  hipEvent_t ev = nullptr;         // the last operation on Y, on whatever stream it ran
-  bool ev_live = false;
-  bool prof_on = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof;
+  PsLastOp last;                   // the last operation on Y, on whatever stream it ran
+  PsProf prof;                     // channel 0: the applies
 };
 
-static int sites_after_last(ps_sites* p, hipStream_t stream) {
-  if (p->ev_live) PS_HIP(hipStreamWaitEvent(stream, p->ev, 0));
-  return PS_OK;
-}
-static int sites_mark_last(ps_sites* p, hipStream_t stream) {
-  PS_HIP(hipEventRecord(p->ev, stream));
-  p->ev_live = true;
-  return PS_OK;
-}
 // Y holds a whole plan: at least one pass done and none under way
 static int sites_whole(const ps_sites* p, const char* who) {
   if (p->passes == 0 && p->next_group == 0) return ps_fail(PS_ERR_STATE, "%s: no release plan applied yet", who);
@@ -147,15 +136,12 @@ static int sites_whole(const ps_sites* p, const char* who) {
 extern "C" void ps_sites_destroy(ps_sites* p) {
   if (!p) return;
   (void)hipSetDevice(p->device);
-  if (p->ev_live) (void)hipEventSynchronize(p->ev);
+  p->last.sync();
   if (p->stream) (void)hipStreamSynchronize(p->stream);
-  for (auto& e : p->prof) {
-    (void)hipEventDestroy(e.first);
-    (void)hipEventDestroy(e.second);
-  }
+  p->prof.release();
   for (void* q : {(void*)p->Y, (void*)p->g_cell, (void*)p->g_out})
     if (q) (void)hipFree(q);
-  if (p->ev) (void)hipEventDestroy(p->ev);
+  p->last.destroy();
   if (p->stream) (void)hipStreamDestroy(p->stream);
   delete p;
 }
@@ -219,7 +205,7 @@ extern "C" int ps_sites_create(int device, int N, int nout, int ngroup, const in
   };
   const size_t y_b = (size_t)nout * pitch * sizeof(double);
   hipError_t e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&p->ev, hipEventDisableTiming);
+  if (e == hipSuccess) e = p->last.create();
   if (e == hipSuccess) e = hipMalloc((void**)&p->Y, y_b);
   if (e == hipSuccess) e = hipMemsetAsync(p->Y, 0, y_b, p->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
@@ -262,20 +248,15 @@ extern "C" int ps_sites_apply(ps_sites* p, ps_solver* s, int group, int nout, co
   if (!any)   // such a group belongs in no plan, and no record names the stream to run on
     return ps_fail(PS_ERR_BAD_ARG, "sites_apply: group %d is released on no output day (every slot is PS_REC_NONE)",
                    group);
-  PS_TRY(sites_after_last(p, stream));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (p->prof_on) {
-    PS_HIP(hipEventCreate(&e0));
-    PS_HIP(hipEventCreate(&e1));
-    p->prof.push_back({e0, e1});
-    PS_HIP(hipEventRecord(e0, stream));
-  }
+  PS_TRY(p->last.wait(stream));
+  hipEvent_t e1 = nullptr;
+  PS_TRY(p->prof.begin(0, stream, &e1));
   hipLaunchKernelGGL(k_sites_apply, dim3(p->nblk, p->nout), dim3(PS_SITES_THREADS), 0, stream, desc,
                      p->tabs[(size_t)group], p->group_nsite[(size_t)group], group == 0 ? 1 : 0, p->Y, p->N, p->ncell,
                      p->pitch, negval);
   PS_HIP(hipGetLastError());
-  if (e1) PS_HIP(hipEventRecord(e1, stream));
-  PS_TRY(sites_mark_last(p, stream));
+  PS_TRY(p->prof.end(stream, e1));
+  PS_TRY(p->last.mark(stream));
   p->next_group = group + 1 == p->ngroup ? 0 : group + 1;
   p->complete = p->next_group == 0;
   if (p->complete) p->passes += 1;
@@ -287,7 +268,7 @@ extern "C" int ps_sites_fetch(ps_sites* p, int e, double* out) {
   if (e < 0 || e >= p->nout) return ps_fail(PS_ERR_BAD_ARG, "sites_fetch: output %d of %d", e, p->nout);
   PS_TRY(sites_whole(p, "sites_fetch"));
   PS_HIP(hipSetDevice(p->device));
-  PS_TRY(sites_after_last(p, p->stream));
+  PS_TRY(p->last.wait(p->stream));
   PS_HIP(hipMemcpyAsync(out, p->Y + (int64_t)e * p->pitch, (size_t)p->ncell * sizeof(double), hipMemcpyDeviceToHost,
                         p->stream));
   PS_HIP(hipStreamSynchronize(p->stream));
@@ -316,7 +297,7 @@ extern "C" int ps_sites_gather(ps_sites* p, int64_t n, const int32_t* rows, cons
     PS_HIP(hipMalloc((void**)&p->g_out, (size_t)n * p->nout * sizeof(double)));
     p->g_cap = n;
   }
-  PS_TRY(sites_after_last(p, p->stream));
+  PS_TRY(p->last.wait(p->stream));
   PS_HIP(hipMemcpyAsync(p->g_cell, cell.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, p->stream));
   const int64_t total = n * p->nout;
   hipLaunchKernelGGL(k_sites_gather, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, p->stream, p->Y, p->pitch,
@@ -340,18 +321,8 @@ extern "C" int ps_sites_info(ps_sites* p, int* N, int* nout, int* ngroup, int* n
 extern "C" int ps_sites_prof(ps_sites* p, int enable, double* total_ms, int64_t* launches) {
   if (!p) return ps_fail(PS_ERR_BAD_ARG, "sites_prof: null handle");
   PS_HIP(hipSetDevice(p->device));
-  if (enable >= 0) p->prof_on = enable != 0;
-  if (total_ms || launches) {
-    double ms = 0.0;
-    for (auto& e : p->prof) {
-      PS_HIP(hipEventSynchronize(e.second));
-      float t = 0.f;
-      PS_HIP(hipEventElapsedTime(&t, e.first, e.second));
-      ms += t;
-    }
-    if (total_ms) *total_ms = ms;
-    if (launches) *launches = (int64_t)p->prof.size();
-  }
+  p->prof.set(enable);
+  if (total_ms || launches) PS_TRY(p->prof.totals(0, total_ms, launches));
   return PS_OK;
 }
 
@@ -366,6 +337,6 @@ static int sites_view(void* h, PsProjectView* out) {
   out->device = p->device;
   return PS_OK;
 }
-static int sites_wait(void* h, hipStream_t stream) { return sites_after_last(static_cast<ps_sites*>(h), stream); }
-static int sites_mark(void* h, hipStream_t stream) { return sites_mark_last(static_cast<ps_sites*>(h), stream); }
+static int sites_wait(void* h, hipStream_t stream) { return static_cast<ps_sites*>(h)->last.wait(stream); }
+static int sites_mark(void* h, hipStream_t stream) { return static_cast<ps_sites*>(h)->last.mark(stream); }
 PsFieldsOps ps_sites_fields() { return PsFieldsOps{"release plan", sites_view, sites_wait, sites_mark}; }

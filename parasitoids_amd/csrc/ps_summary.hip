@@ -101,39 +101,23 @@ struct ps_summary {
   uint64_t W = 0;
   int64_t members = 0;
   hipStream_t stream = nullptr;   // reset / merge / fetch
-  hipEvent_t ev = nullptr;        // the summary's last operation, on whatever stream it ran
-  bool ev_live = false;
-  bool prof_on = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof;
+  PsLastOp last;                  // the summary's last operation, on whatever stream it ran
+  PsProf prof;                    // channel 0: the adds
 };
 
 static size_t val_bytes(const ps_summary* a) { return (size_t)a->nslot * a->pitch * sizeof(double); }
 static size_t cnt_bytes(const ps_summary* a) { return (size_t)a->nslot * a->nthr * a->pitch * sizeof(uint32_t); }
 
-// order `stream` behind the summary's previous operation
-static int after_last(ps_summary* a, hipStream_t stream) {
-  if (a->ev_live) PS_HIP(hipStreamWaitEvent(stream, a->ev, 0));
-  return PS_OK;
-}
-static int mark_last(ps_summary* a, hipStream_t stream) {
-  PS_HIP(hipEventRecord(a->ev, stream));
-  a->ev_live = true;
-  return PS_OK;
-}
-
 extern "C" void ps_summary_destroy(ps_summary* a) {
   if (!a) return;
   (void)hipSetDevice(a->device);
-  if (a->ev_live) (void)hipEventSynchronize(a->ev);
+  a->last.sync();
   if (a->stream) (void)hipStreamSynchronize(a->stream);
-  for (auto& p : a->prof) {
-    (void)hipEventDestroy(p.first);
-    (void)hipEventDestroy(p.second);
-  }
+  a->prof.release();
   if (a->mean) (void)hipFree(a->mean);
   if (a->m2) (void)hipFree(a->m2);
   if (a->cnt) (void)hipFree(a->cnt);
-  if (a->ev) (void)hipEventDestroy(a->ev);
+  a->last.destroy();
   if (a->stream) (void)hipStreamDestroy(a->stream);
   delete a;
 }
@@ -141,11 +125,11 @@ extern "C" void ps_summary_destroy(ps_summary* a) {
 extern "C" int ps_summary_reset(ps_summary* a) {
   if (!a) return ps_fail(PS_ERR_BAD_ARG, "summary_reset: null summary");
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   PS_HIP(hipMemsetAsync(a->mean, 0, val_bytes(a), a->stream));
   PS_HIP(hipMemsetAsync(a->m2, 0, val_bytes(a), a->stream));
   if (a->nthr) PS_HIP(hipMemsetAsync(a->cnt, 0, cnt_bytes(a), a->stream));
-  PS_TRY(mark_last(a, a->stream));
+  PS_TRY(a->last.mark(a->stream));
   a->W = 0;
   a->members = 0;
   return PS_OK;
@@ -170,7 +154,7 @@ extern "C" int ps_summary_create(int device, int N, int nslot, int nthr, const d
     return rc;
   };
   hipError_t e = hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&a->ev, hipEventDisableTiming);
+  if (e == hipSuccess) e = a->last.create();
   if (e == hipSuccess) e = hipMalloc((void**)&a->mean, val_bytes(a));
   if (e == hipSuccess) e = hipMalloc((void**)&a->m2, val_bytes(a));
   if (e == hipSuccess && nthr) e = hipMalloc((void**)&a->cnt, cnt_bytes(a));
@@ -186,14 +170,9 @@ extern "C" int ps_summary_create(int device, int N, int nslot, int nthr, const d
 static int sum_launch(ps_summary* a, const std::vector<SumSlot>& d, hipStream_t stream, double negval,
                       uint32_t weight) {
   const int nslot = a->nslot;
-  PS_TRY(after_last(a, stream));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (a->prof_on) {
-    PS_HIP(hipEventCreate(&e0));
-    PS_HIP(hipEventCreate(&e1));
-    a->prof.push_back({e0, e1});
-    PS_HIP(hipEventRecord(e0, stream));
-  }
+  PS_TRY(a->last.wait(stream));
+  hipEvent_t e1;
+  PS_TRY(a->prof.begin(0, stream, &e1));
   SumThr thr;
   for (int k = 0; k < PS_SUM_MAX_THR; ++k) thr.t[k] = a->thr[k];
   const double Wn = (double)(a->W + weight);
@@ -208,8 +187,8 @@ static int sum_launch(ps_summary* a, const std::vector<SumSlot>& d, hipStream_t 
                        a->pitch, a->nthr, thr, negval, (double)weight, Wn, weight);
     PS_HIP(hipGetLastError());
   }
-  if (e1) PS_HIP(hipEventRecord(e1, stream));
-  PS_TRY(mark_last(a, stream));
+  PS_TRY(a->prof.end(stream, e1));
+  PS_TRY(a->last.mark(stream));
   a->W += weight;
   a->members += 1;
   return PS_OK;
@@ -299,8 +278,8 @@ int ps_summary_mean_internal(ps_summary* a, PsMeanView* out) {
   *out = PsMeanView{a->mean, a->pitch, a->N, a->nslot, a->device};
   return PS_OK;
 }
-int ps_summary_mean_wait_internal(ps_summary* a, hipStream_t stream) { return after_last(a, stream); }
-int ps_summary_mean_done_internal(ps_summary* a, hipStream_t stream) { return mark_last(a, stream); }
+int ps_summary_mean_wait_internal(ps_summary* a, hipStream_t stream) { return a->last.wait(stream); }
+int ps_summary_mean_done_internal(ps_summary* a, hipStream_t stream) { return a->last.mark(stream); }
 
 extern "C" int ps_summary_merge(ps_summary* dst, ps_summary* src) {
   if (!dst || !src || dst == src) return ps_fail(PS_ERR_BAD_ARG, "summary_merge: bad arguments");
@@ -311,8 +290,8 @@ extern "C" int ps_summary_merge(ps_summary* dst, ps_summary* src) {
   if (dst->W + src->W > 0xffffffffull) return ps_fail(PS_ERR_BAD_ARG, "summary_merge: total weight would overflow");
   if (src->W == 0) return PS_OK;
   PS_HIP(hipSetDevice(dst->device));
-  PS_TRY(after_last(dst, dst->stream));
-  PS_TRY(after_last(src, dst->stream));
+  PS_TRY(dst->last.wait(dst->stream));
+  PS_TRY(src->last.wait(dst->stream));
   if (dst->W == 0) {   // a copy: the merged summary is src bit for bit
     PS_HIP(hipMemcpyAsync(dst->mean, src->mean, val_bytes(dst), hipMemcpyDeviceToDevice, dst->stream));
     PS_HIP(hipMemcpyAsync(dst->m2, src->m2, val_bytes(dst), hipMemcpyDeviceToDevice, dst->stream));
@@ -323,8 +302,8 @@ extern "C" int ps_summary_merge(ps_summary* dst, ps_summary* src) {
                        src->m2, src->cnt, nval, nval * dst->nthr, (double)dst->W, (double)src->W);
     PS_HIP(hipGetLastError());
   }
-  PS_TRY(mark_last(dst, dst->stream));
-  PS_TRY(mark_last(src, dst->stream));   // src is read until then
+  PS_TRY(dst->last.mark(dst->stream));
+  PS_TRY(src->last.mark(dst->stream));   // src is read until then
   dst->W += src->W;
   dst->members += src->members;
   return PS_OK;
@@ -344,7 +323,7 @@ extern "C" int ps_summary_fetch(ps_summary* a, int slot, int what, double* out) 
     return ps_fail(PS_ERR_BAD_ARG, "summary_fetch: quantity %d (0 mean, 1 variance, 2..%d exceedance)", what, 1 + a->nthr);
   if (a->W == 0) return ps_fail(PS_ERR_STATE, "summary_fetch: nothing accumulated (W = 0)");
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   const double W = (double)a->W;
   const size_t n = (size_t)a->ncell;
   if (what == 0) {
@@ -367,17 +346,7 @@ extern "C" int ps_summary_fetch(ps_summary* a, int slot, int what, double* out) 
 extern "C" int ps_summary_prof(ps_summary* a, int enable, double* total_ms, int64_t* launches) {
   if (!a) return ps_fail(PS_ERR_BAD_ARG, "summary_prof: null summary");
   PS_HIP(hipSetDevice(a->device));
-  if (enable >= 0) a->prof_on = enable != 0;
-  if (total_ms || launches) {
-    double ms = 0.0;
-    for (auto& p : a->prof) {
-      PS_HIP(hipEventSynchronize(p.second));
-      float t = 0.f;
-      PS_HIP(hipEventElapsedTime(&t, p.first, p.second));
-      ms += t;
-    }
-    if (total_ms) *total_ms = ms;
-    if (launches) *launches = (int64_t)a->prof.size();
-  }
+  a->prof.set(enable);
+  if (total_ms || launches) PS_TRY(a->prof.totals(0, total_ms, launches));
   return PS_OK;
 }

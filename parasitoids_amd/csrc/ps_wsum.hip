@@ -164,10 +164,8 @@ struct ps_wsum {
   int64_t members[PS_WSUM_MAX_SCEN] = {0, 0, 0, 0};
   int64_t skipped[PS_WSUM_MAX_SCEN] = {0, 0, 0, 0};
   hipStream_t stream = nullptr;   // reset / merge / fetch, and the adds from fields
-  hipEvent_t ev = nullptr;        // the last operation, on whatever stream it ran
-  bool ev_live = false;
-  bool prof_on = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof;
+  PsLastOp last;                  // the last operation, on whatever stream it ran
+  PsProf prof;                    // channel 0: the adds
 };
 
 static int64_t ws_plane(const ps_wsum* a) { return (int64_t)a->nslot * a->pitch; }
@@ -179,29 +177,16 @@ static double* ws_mean(const ps_wsum* a, int j) { return a->block + (int64_t)j *
 static double* ws_m2(const ps_wsum* a, int j) { return ws_mean(a, j) + ws_plane(a); }
 static double* ws_S(const ps_wsum* a, int j) { return ws_mean(a, j) + 2 * ws_plane(a); }
 
-static int ws_after_last(ps_wsum* a, hipStream_t stream) {
-  if (a->ev_live) PS_HIP(hipStreamWaitEvent(stream, a->ev, 0));
-  return PS_OK;
-}
-static int ws_mark_last(ps_wsum* a, hipStream_t stream) {
-  PS_HIP(hipEventRecord(a->ev, stream));
-  a->ev_live = true;
-  return PS_OK;
-}
-
 static bool ws_finite(double v) { return v == v && !isinf(v); }
 
 extern "C" void ps_wsum_destroy(ps_wsum* a) {
   if (!a) return;
   (void)hipSetDevice(a->device);
-  if (a->ev_live) (void)hipEventSynchronize(a->ev);
+  a->last.sync();
   if (a->stream) (void)hipStreamSynchronize(a->stream);
-  for (auto& p : a->prof) {
-    (void)hipEventDestroy(p.first);
-    (void)hipEventDestroy(p.second);
-  }
+  a->prof.release();
   if (a->block) (void)hipFree(a->block);
-  if (a->ev) (void)hipEventDestroy(a->ev);
+  a->last.destroy();
   if (a->stream) (void)hipStreamDestroy(a->stream);
   delete a;
 }
@@ -209,9 +194,9 @@ extern "C" void ps_wsum_destroy(ps_wsum* a) {
 extern "C" int ps_wsum_reset(ps_wsum* a) {
   if (!a) return ps_fail(PS_ERR_BAD_ARG, "wsum_reset: null handle");
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(ws_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   PS_HIP(hipMemsetAsync(a->block, 0, (size_t)ws_block_bytes(a->nscen, a->nslot, a->nthr, a->pitch), a->stream));
-  PS_TRY(ws_mark_last(a, a->stream));
+  PS_TRY(a->last.mark(a->stream));
   for (int j = 0; j < PS_WSUM_MAX_SCEN; ++j) {
     a->W[j] = 0.0;
     a->members[j] = 0;
@@ -256,7 +241,7 @@ extern "C" int ps_wsum_create(int device, int N, int nscen, int nslot, int nthr,
     return rc;
   };
   hipError_t e = hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&a->ev, hipEventDisableTiming);
+  if (e == hipSuccess) e = a->last.create();
   if (e == hipSuccess) e = hipMalloc((void**)&a->block, (size_t)need);
   if (e != hipSuccess)
     return fail(ps_fail(e == hipErrorOutOfMemory ? PS_ERR_OOM : PS_ERR_HIP, "wsum_create: %s", hipGetErrorString(e)));
@@ -299,14 +284,9 @@ static int ws_launch(ps_wsum* a, const std::vector<WsSlot>& d, hipStream_t strea
     }
   }
   if (any) {
-    PS_TRY(ws_after_last(a, stream));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (a->prof_on) {
-      PS_HIP(hipEventCreate(&e0));
-      PS_HIP(hipEventCreate(&e1));
-      a->prof.push_back({e0, e1});
-      PS_HIP(hipEventRecord(e0, stream));
-    }
+    PS_TRY(a->last.wait(stream));
+    hipEvent_t e1 = nullptr;
+    PS_TRY(a->prof.begin(0, stream, &e1));
     WsThr thr;
     for (int k = 0; k < PS_WSUM_MAX_THR; ++k) thr.t[k] = a->thr[k];
     WsSlots desc;
@@ -317,8 +297,8 @@ static int ws_launch(ps_wsum* a, const std::vector<WsSlot>& d, hipStream_t strea
     hipLaunchKernelGGL(ws_add_kernels[a->nscen - 1][a->nthr], dim3(bx, a->nslot), dim3(threads), 0, stream, desc,
                        a->block, a->ncell, a->pitch, ws_plane(a), thr, negval, sc);
     PS_HIP(hipGetLastError());
-    if (e1) PS_HIP(hipEventRecord(e1, stream));
-    PS_TRY(ws_mark_last(a, stream));
+    PS_TRY(a->prof.end(stream, e1));
+    PS_TRY(a->last.mark(stream));
   }
   for (int j = 0; j < a->nscen; ++j) {
     if (omega[j] > 0.0) {
@@ -413,8 +393,8 @@ int ps_wsum_mean_internal(ps_wsum* a, int scenario, PsMeanView* out) {
   *out = PsMeanView{ws_mean(a, scenario), a->pitch, a->N, a->nslot, a->device};
   return PS_OK;
 }
-int ps_wsum_mean_wait_internal(ps_wsum* a, hipStream_t stream) { return ws_after_last(a, stream); }
-int ps_wsum_mean_done_internal(ps_wsum* a, hipStream_t stream) { return ws_mark_last(a, stream); }
+int ps_wsum_mean_wait_internal(ps_wsum* a, hipStream_t stream) { return a->last.wait(stream); }
+int ps_wsum_mean_done_internal(ps_wsum* a, hipStream_t stream) { return a->last.mark(stream); }
 
 extern "C" int ps_wsum_merge(ps_wsum* dst, ps_wsum* src, const double* ra, const double* rb) {
   if (!dst || !src || !ra || !rb) return ps_fail(PS_ERR_BAD_ARG, "wsum_merge: bad arguments");
@@ -428,8 +408,8 @@ extern "C" int ps_wsum_merge(ps_wsum* dst, ps_wsum* src, const double* ra, const
     if (!(ra[j] >= 0.0 && ra[j] <= 1.0) || !(rb[j] >= 0.0 && rb[j] <= 1.0))
       return ps_fail(PS_ERR_BAD_ARG, "wsum_merge: scale (%g, %g) of scenario %d is not in [0, 1]", ra[j], rb[j], j);
   PS_HIP(hipSetDevice(dst->device));
-  PS_TRY(ws_after_last(dst, dst->stream));
-  PS_TRY(ws_after_last(src, dst->stream));
+  PS_TRY(dst->last.wait(dst->stream));
+  PS_TRY(src->last.wait(dst->stream));
   const int64_t nval = ws_plane(dst);
   const size_t scen_bytes = (size_t)ws_scen_cells(dst) * sizeof(double);
   for (int j = 0; j < dst->nscen; ++j) {
@@ -454,8 +434,8 @@ extern "C" int ps_wsum_merge(ps_wsum* dst, ps_wsum* src, const double* ra, const
     dst->members[j] += src->members[j];
     dst->skipped[j] += src->skipped[j];
   }
-  PS_TRY(ws_mark_last(dst, dst->stream));
-  PS_TRY(ws_mark_last(src, dst->stream));   // src is read until then
+  PS_TRY(dst->last.mark(dst->stream));
+  PS_TRY(src->last.mark(dst->stream));   // src is read until then
   return PS_OK;
 }
 
@@ -477,7 +457,7 @@ extern "C" int ps_wsum_fetch(ps_wsum* a, int scen, int slot, int what, double* o
     return ps_fail(PS_ERR_BAD_ARG, "wsum_fetch: quantity %d (0 mean, 1 variance, 2..%d exceedance)", what, 1 + a->nthr);
   if (a->W[scen] == 0.0) return ps_fail(PS_ERR_STATE, "wsum_fetch: nothing accumulated in scenario %d (W = 0)", scen);
   PS_HIP(hipSetDevice(a->device));
-  PS_TRY(ws_after_last(a, a->stream));
+  PS_TRY(a->last.wait(a->stream));
   const double W = a->W[scen];
   const size_t n = (size_t)a->ncell;
   const double* src = what == 0   ? ws_mean(a, scen) + (int64_t)slot * a->pitch
@@ -499,17 +479,7 @@ extern "C" int ps_wsum_fetch(ps_wsum* a, int scen, int slot, int what, double* o
 extern "C" int ps_wsum_prof(ps_wsum* a, int enable, double* total_ms, int64_t* launches) {
   if (!a) return ps_fail(PS_ERR_BAD_ARG, "wsum_prof: null handle");
   PS_HIP(hipSetDevice(a->device));
-  if (enable >= 0) a->prof_on = enable != 0;
-  if (total_ms || launches) {
-    double ms = 0.0;
-    for (auto& p : a->prof) {
-      PS_HIP(hipEventSynchronize(p.second));
-      float t = 0.f;
-      PS_HIP(hipEventElapsedTime(&t, p.first, p.second));
-      ms += t;
-    }
-    if (total_ms) *total_ms = ms;
-    if (launches) *launches = (int64_t)a->prof.size();
-  }
+  a->prof.set(enable);
+  if (total_ms || launches) PS_TRY(a->prof.totals(0, total_ms, launches));
   return PS_OK;
 }
