@@ -1700,6 +1700,53 @@ int ps_origin_prof(ps_origin* p, int enable, double* add_ms, int64_t* adds, doub
                    double* merge_ms, int64_t* merges);
 void ps_origin_destroy(ps_origin* p);
 
+/* ---- origin maps over a known release in the background: is there a second source? ----
+ * The findings also catch the wasps of releases that are facts, not hypotheses -- ours at the centre.  There is
+ * still one unknown origin, evaluated exhaustively; this is no multi-source inversion.  A handle without known
+ * releases behaves and computes as above, bit for bit.  Statement by statement:
+ *   known releases  k = 0 .. K - 1, 1 <= K <= 32: amount_k finite and > 0 in multiples of the release number, the
+ *              cell offset (drow_k, dcol_k) off the centre by the package's convention (|drow|, |dcol| <= N - 1),
+ *              and the known group kgroup_k in 0 .. nk - 1 of its lag (1 <= nk <= 4, ascending lag, the smallest 0,
+ *              every group with at least one release).  The known groups are numbered apart from the hypotheses'.
+ *   background per member and finding o: bg_o = the sum over k in index order, from +0.0, of
+ *              fl(fl(rate_o * amount_k) * v_k): the bracket formed once on the host at set-up, the product and the
+ *              sum rounded separately.  v_k is ps_record_value of the known lag's own model, with the arguments
+ *              ps_origin_add takes, read at day d_o - lag_k and cell (row_o - drow_k, col_o - dcol_k); 0 where
+ *              either axis leaves [0, N) -- per axis, never by the flat index -- and 0 before that release
+ *              (PS_REC_NONE).  A numpy loop gives the same bits.
+ *   likelihood for candidate s and hypothesis h: t = ra * v as above, then mu = bg_q + t -- two statements, two
+ *              roundings -- then the term above at mu, unchanged.  A finding excludes a cell only where bg_q == 0
+ *              and v == 0.  The order of the findings, (A, S), the partials and the rows are unchanged; mu is the
+ *              same fp64 number on the device and in the restatement, so the bounds of DESIGN 7y stand as written.
+ *   null row   per member l0 = the sum over q, from +0.0 in the kernel's order, of the term at mu = bg_q: "the
+ *              known releases alone".  One fixed-order sum of at most 64 terms, kept per member next to the
+ *              member rows in add order; its bound is that of l with O terms.
+ *   identity   at a candidate cell whose shifted reads are all 0 (and that the prior does not mask),
+ *              l_h(s) == l0 bit for bit.
+ * One member: ps_origin_background for known group 0 .. nk - 1 in order, then ps_origin_add for group
+ * 0 .. ngroup - 1 as above.  Each background call is one small launch on that lag's solver stream -- lane o owns
+ * finding o and walks the group's releases in index order; the last known group's launch also adds the terms to
+ * bg and forms l0, which one lane sums -- ordered against every other operation of the handle through its
+ * last-operation event, without a host synchronisation. */
+/* once, before the first member (PS_ERR_STATE afterwards, and for a second call); validated as ps_origin_create
+ * validates, each refusal with its offender named */
+int ps_origin_set_known(ps_origin* p, int nknown, const int32_t* drow /* nknown */, const int32_t* dcol /* nknown */,
+                        const double* amount /* nknown */, const int32_t* kgroup /* nknown */, int nkgroup);
+/* One known group of one member from the records of solver s (the arguments of ps_origin_add without the weight;
+ * a known group released after every finding may have every slot PS_REC_NONE and contributes 0).  PS_ERR_STATE
+ * for a handle without known releases, a call out of order, and a call while the adds of a member are under way.
+ * With known releases ps_origin_add(group 0) is PS_ERR_STATE until the member's backgrounds are complete. */
+int ps_origin_background(ps_origin* p, ps_solver* s, int kgroup, int nslot, const int32_t* kind, const int32_t* idx,
+                         const double* stat_scale, const double* post_scale, const int32_t* use_delta, double negval);
+/* the bg [nfind] of the last member added to this handle, in the order the findings were given, and its l0 (either
+ * may be NULL; synchronises; a merge appends null rows and leaves this pair alone).
+ * PS_ERR_STATE without known releases, before the first member and while a member is under way. */
+int ps_origin_fetch_background(ps_origin* p, double* bg /* nfind */, double* l0);
+/* the members' l0 [members] in add order (synchronises); PS_ERR_STATE without known releases, PS_ERR_BAD_ARG for
+ * members_expected != the handle's members.  merge requires equal known releases (PS_ERR_BAD_ARG) and appends the
+ * null rows; reset, reserve and the growth of the rows carry them along; info's bytes include them. */
+int ps_origin_null_rows(ps_origin* p, int64_t members_expected, double* rows /* members */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -332,6 +332,10 @@ SIGNATURES = {
     'ps_origin_info': (C.c_int, [_VP, _F64P, _I64P, _I64P, _I64P]),
     'ps_origin_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P, _F64P, _I64P, _F64P, _I64P]),
     'ps_origin_destroy': (None, [_VP]),
+    'ps_origin_set_known': (C.c_int, [_VP, C.c_int, _I32P, _I32P, _F64P, _I32P, C.c_int]),
+    'ps_origin_background': (C.c_int, [_VP, _VP, C.c_int, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P, C.c_double]),
+    'ps_origin_fetch_background': (C.c_int, [_VP, _F64P, _F64P]),
+    'ps_origin_null_rows': (C.c_int, [_VP, C.c_int64, _F64P]),
     'ps_summary_add_prox': (C.c_int, [_VP, _VP, C.c_uint32]),
     'ps_hist_add_prox': (C.c_int, [_VP, _VP, C.c_uint32]),
     'ps_mcerr_add_prox': (C.c_int, [_VP, _VP, C.c_uint32]),

@@ -18,6 +18,12 @@
 // atomics; -inf touches nothing -- and the block leaves its partial; k_origin_rows, one wave per hypothesis,
 // adds the partials in the fixed order of origin_lane_sum.  The same calls give the same bits.  The accumulator
 // is floating point: another order of adds or merges moves E = A + log S - log W within its stated bound.
+// Known releases (ps_origin_set_known): the findings also catch the wasps of releases that are facts, not
+// hypotheses.  Per member k_origin_background, one wave per known group on that lag's solver stream, leaves
+// term[k][q] = fl(rak * v_k) of the group's releases; the last group's launch adds them in index order k to bg[q],
+// forms the terms at mu = bg and one lane adds them in order q to the member's null row l0.  k_origin_add<true>
+// then reads bg[q] -- the same for every lane -- and forms mu = bg + ra * v with two roundings; k_origin_add<false>
+// is the code of a handle without known releases.
 #include <math.h>
 
 #include <algorithm>
@@ -55,12 +61,54 @@ __device__ inline double org_wave_sum(double x) {   // a butterfly: every lane e
   return x;
 }
 
-// find, ra: the findings and the products rate_o * amount_h, ra[h * nfind + q], both in kernel order q
+struct OrgKnown {
+  int n, last;                            // the group's releases; last: this launch also forms bg and l0
+  int32_t k[PS_ORIGIN_MAX_KNOWN];         // their indices, ascending
+  int32_t drow[PS_ORIGIN_MAX_KNOWN], dcol[PS_ORIGIN_MAX_KNOWN];
+};
+
+// One wave; lane q owns finding q (kernel order).  rak[k * nfind + q] = fl(rate * amount_k); term[k * nfind + q]
+// is left by the launch of k's group, and read by the last group's launch: the same lane, or an earlier launch.
+__global__ void __launch_bounds__(PS_ORIGIN_LANES)
+    k_origin_background(OrgSlots desc, OrgKnown kn, const OriginFinding* __restrict__ find,
+                        const double* __restrict__ rak, double* term, int nknown, int nfind, int N,
+                        double* __restrict__ bg, double* __restrict__ null_row, double negval) {
+  __shared__ double lterm[PS_ORIGIN_LANES];
+  const int q = threadIdx.x;
+  if (q < nfind) {
+    const OriginFinding f = find[q];
+    const OrgSlot sd = desc.s[f.slot];
+    const double delta = sd.rec && sd.stats ? sd.stats->delta : 0.0;
+    for (int j = 0; j < kn.n; ++j) {
+      double v = 0.0;
+      int64_t src;
+      if (sd.rec && origin_known_source(N, f.rowR, f.colR, kn.drow[j], kn.dcol[j], &src))
+        v = ps_record_value(sd.rec[src], sd.stat_scale, sd.post_scale, delta, negval);
+      term[(int64_t)kn.k[j] * nfind + q] = origin_bg_term(rak[(int64_t)kn.k[j] * nfind + q], v);
+    }
+    if (kn.last) {
+      const double b = origin_bg_sum(term, nknown, nfind, q);
+      bg[q] = b;
+      lterm[q] = origin_term(f.kind, b, f.n, f.lgam);
+    }
+  }
+  if (!kn.last) return;
+  __syncthreads();
+  if (q == 0) {
+    const double l0 = origin_null_sum(lterm, nfind);
+    *null_row = l0;
+    bg[nfind] = l0;   // next to the background it belongs to: a merge appends null rows, not backgrounds
+  }
+}
+
+// find, ra: the findings and the products rate_o * amount_h, ra[h * nfind + q], both in kernel order q; BG: bg[q],
+// the background of finding q, is added to every mu
+template <bool BG>
 __global__ void __launch_bounds__(PS_ORIGIN_THREADS)
     k_origin_add(OrgSlots desc, OrgGroup grp, const OriginFinding* __restrict__ find, const double* __restrict__ ra,
-                 int nfind, const double* __restrict__ prior, double* __restrict__ L, double* __restrict__ A,
-                 double* __restrict__ S, double* __restrict__ part, int N, int64_t ncell, int64_t pitch, int64_t nblk,
-                 double negval, double w) {
+                 const double* __restrict__ bg, int nfind, const double* __restrict__ prior, double* __restrict__ L,
+                 double* __restrict__ A, double* __restrict__ S, double* __restrict__ part, int N, int64_t ncell,
+                 int64_t pitch, int64_t nblk, double negval, double w) {
   __shared__ double smax[PS_ORIGIN_MAX_HYP][PS_ORIGIN_THREADS / 64];
   __shared__ double ssum[PS_ORIGIN_MAX_HYP][PS_ORIGIN_THREADS / 64];
   const int64_t i = blockIdx.x * (int64_t)PS_ORIGIN_THREADS + threadIdx.x;
@@ -86,11 +134,13 @@ __global__ void __launch_bounds__(PS_ORIGIN_THREADS)
       const double delta = sd.stats ? sd.stats->delta : 0.0;
       v = ps_record_value(sd.rec[src], sd.stat_scale, sd.post_scale, delta, negval);
     }
+    const double bq = BG ? bg[q] : 0.0;
     bool any = false;
 #pragma unroll
     for (int j = 0; j < PS_ORIGIN_MAX_HYP; ++j) {
       if (j < nh) {
-        const double mu = ra[(int64_t)grp.h[j] * nfind + q] * v;
+        const double rav = ra[(int64_t)grp.h[j] * nfind + q];
+        const double mu = BG ? origin_mu_bg(bq, rav, v) : rav * v;
         acc[j] = acc[j] + origin_term(f.kind, mu, f.n, f.lgam);
         any = any || acc[j] != -INFINITY;
       }
@@ -207,6 +257,18 @@ struct ps_origin {
   std::vector<uint32_t> weights;   // per member, in row order
   int next_group = 0;              // the group the next add must name
   uint32_t pass_weight = 0;        // the weight group 0 of the pass under way came with
+  // known releases (ps_origin_set_known); nknown == 0: none, and nothing below is allocated
+  int nknown = 0, nk = 0;          // the releases and their groups (lags)
+  OrgKnown kgroups[PS_ORIGIN_MAX_KGROUP];
+  std::vector<int32_t> known_i;    // what two handles must share to merge: offsets and groups, amounts
+  std::vector<double> known_d;
+  std::vector<int32_t> order;      // order[q] = the finding, in the order given, that the kernel reads q-th
+  std::vector<double> rate_q;      // the rates in kernel order
+  double* rak = nullptr;           // [nknown][nfind] fl(rate * amount_k)
+  double* term = nullptr;          // [nknown][nfind] the member's background terms
+  double* bg = nullptr;            // [nfind + 1] the member's background, kernel order, and its l0
+  double* null_rows = nullptr;     // [rows_cap] l0 per member, in add order
+  int next_bg = 0;                 // the known group the next background call must name; nk: complete
   hipStream_t stream = nullptr;    // reset / merge / fetch / row growth
   PsLastOp last;                   // the last operation, on whatever stream it ran
   PsProf prof;                     // channel 0: the adds, 1: the rows, 2: the merges
@@ -214,11 +276,17 @@ struct ps_origin {
 
 static size_t org_plane_bytes(const ps_origin* p) { return (size_t)p->nhyp * p->pitch * sizeof(double); }
 static size_t org_row_bytes(const ps_origin* p) { return (size_t)p->nhyp * 2 * sizeof(double); }
+// the tables of the known releases: rak, term, bg
+static size_t org_known_bytes(const ps_origin* p) {
+  return p->nknown ? (((size_t)2 * p->nknown + 1) * p->nfind + 1) * sizeof(double) : 0;
+}
 static size_t org_fixed_bytes(const ps_origin* p, bool prior) {
   return 3 * org_plane_bytes(p) + (prior ? (size_t)p->pitch * sizeof(double) : 0) +
          (size_t)p->nhyp * p->nblk * 2 * sizeof(double) + (size_t)p->nfind * sizeof(OriginFinding) +
-         (size_t)p->nhyp * p->nfind * sizeof(double);
+         (size_t)p->nhyp * p->nfind * sizeof(double) + org_known_bytes(p);
 }
+// a member under way holds a row (and a null row) past the members counted
+static bool org_under_way(const ps_origin* p) { return p->next_group != 0 || p->next_bg != 0; }
 
 // room for `need` member rows: a doubling copies the rows so far on the handle's stream and synchronises once
 // before the old block is freed (as ps_range.hip)
@@ -227,27 +295,40 @@ static int org_reserve_rows(ps_origin* p, int64_t need) {
   int64_t cap = std::max<int64_t>(p->rows_cap, PS_ORIGIN_ROWS0);
   while (cap < need) cap *= 2;
   const size_t bytes = (size_t)cap * org_row_bytes(p);
+  const size_t null_bytes = p->nknown ? (size_t)cap * sizeof(double) : 0;   // the null rows grow with the rows
   size_t free_b = 0, total_b = 0;
   PS_HIP(hipMemGetInfo(&free_b, &total_b));
-  if (bytes > free_b)
+  if (bytes + null_bytes > free_b)
     return ps_fail(PS_ERR_OOM, "origin: %lld member rows need %.3g GB, %.3g GB free", (long long)cap,
-                   (double)bytes * 1e-9, (double)free_b * 1e-9);
-  double* q = nullptr;
+                   (double)(bytes + null_bytes) * 1e-9, (double)free_b * 1e-9);
+  double *q = nullptr, *q0 = nullptr;
   PS_HIP(hipMalloc((void**)&q, bytes));
+  if (null_bytes) {
+    const hipError_t e0 = hipMalloc((void**)&q0, null_bytes);
+    if (e0 != hipSuccess) {
+      (void)hipFree(q);
+      return ps_fail(PS_ERR_HIP, "origin: growing the null rows: %s", hipGetErrorString(e0));
+    }
+  }
   if (p->rows) {
     hipError_t e = hipSuccess;
     if (p->last.live) e = hipStreamWaitEvent(p->stream, p->last.ev, 0);
-    const int64_t keep = p->members + (p->next_group != 0 ? 1 : 0);   // the row of a pass under way too
+    const int64_t keep = p->members + (org_under_way(p) ? 1 : 0);   // the row of a pass under way too
     if (e == hipSuccess && keep > 0)
       e = hipMemcpyAsync(q, p->rows, (size_t)keep * org_row_bytes(p), hipMemcpyDeviceToDevice, p->stream);
+    if (e == hipSuccess && keep > 0 && p->null_rows)
+      e = hipMemcpyAsync(q0, p->null_rows, (size_t)keep * sizeof(double), hipMemcpyDeviceToDevice, p->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
     if (e != hipSuccess) {
       (void)hipFree(q);
+      if (q0) (void)hipFree(q0);
       return ps_fail(PS_ERR_HIP, "origin: growing the member rows: %s", hipGetErrorString(e));
     }
     PS_HIP(hipFree(p->rows));
+    if (p->null_rows) PS_HIP(hipFree(p->null_rows));
   }
   p->rows = q;
+  p->null_rows = q0;
   p->rows_cap = cap;
   return PS_OK;
 }
@@ -259,7 +340,7 @@ extern "C" void ps_origin_destroy(ps_origin* p) {
   if (p->stream) (void)hipStreamSynchronize(p->stream);
   p->prof.release();
   for (void* q : {(void*)p->find, (void*)p->ra, (void*)p->prior, (void*)p->A, (void*)p->S, (void*)p->L, (void*)p->part,
-                  (void*)p->rows})
+                  (void*)p->rows, (void*)p->rak, (void*)p->term, (void*)p->bg, (void*)p->null_rows})
     if (q) (void)hipFree(q);
   p->last.destroy();
   if (p->stream) (void)hipStreamDestroy(p->stream);
@@ -277,6 +358,7 @@ extern "C" int ps_origin_reset(ps_origin* p) {
   p->members = 0;
   p->weights.clear();
   p->next_group = 0;
+  p->next_bg = 0;
   return PS_OK;
 }
 
@@ -361,7 +443,9 @@ extern "C" int ps_origin_create(int device, int N, int nfind, const int32_t* row
     const double cnt = kind[o] == PS_ORIGIN_COUNT ? n[o] : 0.0;
     find[(size_t)q] = OriginFinding{row[o] + R, col[o] + R, slot[o], kind[o], cnt, lgamma(cnt + 1.0)};
     for (int h = 0; h < nhyp; ++h) ra[(size_t)h * nfind + q] = rate[o] * amount[h];   // formed once, here
+    p->rate_q.push_back(rate[o]);
   }
+  p->order = order;
   for (int o = 0; o < nfind; ++o) {
     p->key_i.insert(p->key_i.end(), {row[o], col[o], slot[o], kind[o]});
     p->key_d.insert(p->key_d.end(), {rate[o], kind[o] == PS_ORIGIN_COUNT ? n[o] : 0.0});
@@ -414,6 +498,9 @@ extern "C" int ps_origin_add(ps_origin* p, ps_solver* s, int group, int nslot, c
   if (group < 0 || group >= p->ngroup) return ps_fail(PS_ERR_BAD_ARG, "origin_add: group %d of %d", group, p->ngroup);
   if (nslot != p->nslot) return ps_fail(PS_ERR_BAD_ARG, "origin_add: %d days given, the handle has %d", nslot, p->nslot);
   if (weight < 1) return ps_fail(PS_ERR_BAD_ARG, "origin_add: weight must be >= 1");
+  if (group == 0 && p->next_group == 0 && !origin_backgrounds_done(p->next_bg, p->nk))
+    return ps_fail(PS_ERR_STATE, "origin_add: the handle has known releases and background %d of %d of this member has "
+                   "not come (ps_origin_background)", p->next_bg, p->nk);
   const int next = origin_next_group(p->next_group, group, p->ngroup);
   if (next < 0)
     return ps_fail(PS_ERR_STATE, "origin_add: group %d given, the member is at group %d (groups go 0 .. %d in order)",
@@ -452,9 +539,14 @@ extern "C" int ps_origin_add(ps_origin* p, ps_solver* s, int group, int nslot, c
   const OrgGroup& G = p->groups[group];
   hipEvent_t e1 = nullptr;
   PS_TRY(p->prof.begin(0, stream, &e1));
-  hipLaunchKernelGGL(k_origin_add, dim3((unsigned)p->nblk), dim3(PS_ORIGIN_THREADS), 0, stream, desc, G, p->find, p->ra,
-                     p->nfind, p->prior, p->L, p->A, p->S, p->part, p->N, p->ncell, p->pitch, p->nblk, negval,
-                     (double)weight);
+  if (p->nknown)
+    hipLaunchKernelGGL(k_origin_add<true>, dim3((unsigned)p->nblk), dim3(PS_ORIGIN_THREADS), 0, stream, desc, G, p->find,
+                       p->ra, p->bg, p->nfind, p->prior, p->L, p->A, p->S, p->part, p->N, p->ncell, p->pitch, p->nblk,
+                       negval, (double)weight);
+  else
+    hipLaunchKernelGGL(k_origin_add<false>, dim3((unsigned)p->nblk), dim3(PS_ORIGIN_THREADS), 0, stream, desc, G, p->find,
+                       p->ra, (const double*)nullptr, p->nfind, p->prior, p->L, p->A, p->S, p->part, p->N, p->ncell,
+                       p->pitch, p->nblk, negval, (double)weight);
   PS_HIP(hipGetLastError());
   PS_TRY(p->prof.end(stream, e1));
   PS_TRY(p->prof.begin(1, stream, &e1));
@@ -466,6 +558,7 @@ extern "C" int ps_origin_add(ps_origin* p, ps_solver* s, int group, int nslot, c
   if (group == 0) p->pass_weight = weight;
   p->next_group = next;
   if (next == 0) {   // the member counts once its last group is in
+    p->next_bg = 0;
     p->W += weight;
     p->members += 1;
     p->weights.push_back(weight);
@@ -473,9 +566,159 @@ extern "C" int ps_origin_add(ps_origin* p, ps_solver* s, int group, int nslot, c
   return PS_OK;
 }
 
+extern "C" int ps_origin_set_known(ps_origin* p, int nknown, const int32_t* drow, const int32_t* dcol,
+                                   const double* amount, const int32_t* kgroup, int nkgroup) {
+  if (!p || !drow || !dcol || !amount || !kgroup || nknown < 1 || nknown > PS_ORIGIN_MAX_KNOWN || nkgroup < 1 ||
+      nkgroup > PS_ORIGIN_MAX_KGROUP)
+    return ps_fail(PS_ERR_BAD_ARG, "origin_set_known: %d known releases (1..%d), %d known groups (1..%d)", nknown,
+                   PS_ORIGIN_MAX_KNOWN, nkgroup, PS_ORIGIN_MAX_KGROUP);
+  if (p->nknown) return ps_fail(PS_ERR_STATE, "origin_set_known: the handle has its %d known releases already", p->nknown);
+  if (p->members != 0 || p->next_group != 0)
+    return ps_fail(PS_ERR_STATE, "origin_set_known: the known releases come before the first member (%lld are in)",
+                   (long long)p->members + (p->next_group != 0 ? 1 : 0));
+  std::vector<int> per_group((size_t)nkgroup, 0);
+  for (int k = 0; k < nknown; ++k) {
+    if (!isfinite(amount[k]) || !(amount[k] > 0.0))
+      return ps_fail(PS_ERR_BAD_ARG, "origin_set_known: amount %d = %g is not finite and > 0", k, amount[k]);
+    if (drow[k] <= -p->N || drow[k] >= p->N || dcol[k] <= -p->N || dcol[k] >= p->N)
+      return ps_fail(PS_ERR_BAD_ARG, "origin_set_known: known release %d at offset (%d, %d) lies beyond the %d x %d domain",
+                     k, drow[k], dcol[k], p->N, p->N);
+    if (kgroup[k] < 0 || kgroup[k] >= nkgroup)
+      return ps_fail(PS_ERR_BAD_ARG, "origin_set_known: known release %d belongs to known group %d of %d", k, kgroup[k],
+                     nkgroup);
+    per_group[(size_t)kgroup[k]] += 1;
+  }
+  for (int g = 0; g < nkgroup; ++g)
+    if (per_group[(size_t)g] == 0)
+      return ps_fail(PS_ERR_BAD_ARG, "origin_set_known: known group %d has no release", g);
+  PS_HIP(hipSetDevice(p->device));
+  std::vector<double> rak((size_t)nknown * p->nfind);
+  for (int k = 0; k < nknown; ++k)
+    for (int q = 0; q < p->nfind; ++q) rak[(size_t)k * p->nfind + q] = p->rate_q[(size_t)q] * amount[k];   // once, here
+  const size_t tb = rak.size() * sizeof(double);
+  double *d_rak = nullptr, *d_term = nullptr, *d_bg = nullptr, *d_null = nullptr;
+  hipError_t e = hipMalloc((void**)&d_rak, tb);
+  if (e == hipSuccess) e = hipMalloc((void**)&d_term, tb);
+  if (e == hipSuccess) e = hipMalloc((void**)&d_bg, ((size_t)p->nfind + 1) * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_null, (size_t)p->rows_cap * sizeof(double));
+  if (e == hipSuccess) e = p->last.live ? hipStreamWaitEvent(p->stream, p->last.ev, 0) : hipSuccess;
+  if (e == hipSuccess) e = hipMemcpyAsync(d_rak, rak.data(), tb, hipMemcpyHostToDevice, p->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(d_term, 0, tb, p->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(d_bg, 0, ((size_t)p->nfind + 1) * sizeof(double), p->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(p->stream);   // the host table is read until here
+  if (e != hipSuccess) {
+    for (void* q : {(void*)d_rak, (void*)d_term, (void*)d_bg, (void*)d_null})
+      if (q) (void)hipFree(q);
+    return ps_fail(e == hipErrorOutOfMemory ? PS_ERR_OOM : PS_ERR_HIP, "origin_set_known: %s", hipGetErrorString(e));
+  }
+  p->rak = d_rak;
+  p->term = d_term;
+  p->bg = d_bg;
+  p->null_rows = d_null;
+  for (int g = 0; g < nkgroup; ++g) {
+    OrgKnown& G = p->kgroups[g];
+    G = OrgKnown();
+    G.last = g + 1 == nkgroup;
+    for (int k = 0; k < nknown; ++k)
+      if (kgroup[k] == g) {
+        G.k[G.n] = k;
+        G.drow[G.n] = drow[k];
+        G.dcol[G.n] = dcol[k];
+        G.n += 1;
+      }
+  }
+  for (int k = 0; k < nknown; ++k) {
+    p->known_i.insert(p->known_i.end(), {drow[k], dcol[k], kgroup[k]});
+    p->known_d.push_back(amount[k]);
+  }
+  p->nknown = nknown;
+  p->nk = nkgroup;
+  p->next_bg = 0;
+  return PS_OK;
+}
+
+extern "C" int ps_origin_background(ps_origin* p, ps_solver* s, int kgroup, int nslot, const int32_t* kind,
+                                    const int32_t* idx, const double* stat_scale, const double* post_scale,
+                                    const int32_t* use_delta, double negval) {
+  if (!p || !s || !kind || !idx || !stat_scale || !post_scale || !use_delta)
+    return ps_fail(PS_ERR_BAD_ARG, "origin_background: bad arguments");
+  if (!p->nknown) return ps_fail(PS_ERR_STATE, "origin_background: the handle has no known releases (ps_origin_set_known)");
+  if (kgroup < 0 || kgroup >= p->nk)
+    return ps_fail(PS_ERR_BAD_ARG, "origin_background: known group %d of %d", kgroup, p->nk);
+  if (nslot != p->nslot)
+    return ps_fail(PS_ERR_BAD_ARG, "origin_background: %d days given, the handle has %d", nslot, p->nslot);
+  const int next = origin_next_background(p->next_bg, p->next_group, kgroup, p->nk);
+  if (next < 0) {
+    if (p->next_group != 0)
+      return ps_fail(PS_ERR_STATE, "origin_background: the adds of a member are under way (group %d of %d is next)",
+                     p->next_group, p->ngroup);
+    return ps_fail(PS_ERR_STATE, "origin_background: known group %d given, the member is at known group %d of %d (they "
+                   "go 0 .. %d in order, then the adds)", kgroup, p->next_bg, p->nk, p->nk - 1);
+  }
+  PS_HIP(hipSetDevice(p->device));
+  // every descriptor first: a call with a bad record enqueues nothing
+  OrgSlots desc;
+  hipStream_t stream = p->stream;   // a known group released after every finding reads no record: the handle's stream
+  for (int e = 0; e < nslot; ++e) {
+    if (kind[e] == PS_REC_NONE) {
+      desc.s[e] = OrgSlot{nullptr, nullptr, 0.0, 0.0};
+      continue;
+    }
+    PsRecordView v;
+    PS_TRY(ps_solver_record_internal(s, kind[e], idx[e], use_delta[e] != 0, &v));
+    if (v.device != p->device)
+      return ps_fail(PS_ERR_BAD_ARG, "origin_background: solver on device %d, handle on device %d", v.device, p->device);
+    if (v.N != p->N) return ps_fail(PS_ERR_BAD_ARG, "origin_background: solver domain %d, handle domain %d", v.N, p->N);
+    desc.s[e] = OrgSlot{v.rec, v.stats, stat_scale[e], post_scale[e]};
+    stream = v.stream;
+  }
+  for (int e = nslot; e < PS_ORIGIN_MAX_SLOT; ++e) desc.s[e] = OrgSlot{nullptr, nullptr, 0.0, 0.0};
+  if (kgroup == 0) PS_TRY(org_reserve_rows(p, p->members + 1));
+  PS_TRY(p->last.wait(stream));
+  hipLaunchKernelGGL(k_origin_background, dim3(1), dim3(PS_ORIGIN_LANES), 0, stream, desc, p->kgroups[kgroup], p->find,
+                     p->rak, p->term, p->nknown, p->nfind, p->N, p->bg, p->null_rows + p->members, negval);
+  PS_HIP(hipGetLastError());
+  PS_TRY(p->last.mark(stream));
+  p->next_bg = next;
+  return PS_OK;
+}
+
+extern "C" int ps_origin_fetch_background(ps_origin* p, double* bg, double* l0) {
+  if (!p) return ps_fail(PS_ERR_BAD_ARG, "origin_fetch_background: null handle");
+  if (!p->nknown) return ps_fail(PS_ERR_STATE, "origin_fetch_background: the handle has no known releases");
+  if (p->members == 0) return ps_fail(PS_ERR_STATE, "origin_fetch_background: no member added yet");
+  if (org_under_way(p)) return ps_fail(PS_ERR_STATE, "origin_fetch_background: a member is under way");
+  PS_HIP(hipSetDevice(p->device));
+  PS_TRY(p->last.wait(p->stream));
+  double q[PS_ORIGIN_MAX_FIND + 1];
+  PS_HIP(hipMemcpyAsync(q, p->bg, ((size_t)p->nfind + 1) * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+  PS_HIP(hipStreamSynchronize(p->stream));
+  if (bg)
+    for (int k = 0; k < p->nfind; ++k) bg[p->order[(size_t)k]] = q[k];   // back to the order given
+  if (l0) *l0 = q[p->nfind];
+  return PS_OK;
+}
+
+extern "C" int ps_origin_null_rows(ps_origin* p, int64_t members_expected, double* rows) {
+  if (!p) return ps_fail(PS_ERR_BAD_ARG, "origin_null_rows: null handle");
+  if (!p->nknown) return ps_fail(PS_ERR_STATE, "origin_null_rows: the handle has no known releases");
+  if (members_expected != p->members)
+    return ps_fail(PS_ERR_BAD_ARG, "origin_null_rows: room for %lld members given, the handle holds %lld",
+                   (long long)members_expected, (long long)p->members);
+  if (p->members == 0 || !rows) return PS_OK;
+  PS_HIP(hipSetDevice(p->device));
+  PS_TRY(p->last.wait(p->stream));
+  PS_HIP(hipMemcpyAsync(rows, p->null_rows, (size_t)p->members * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+  PS_HIP(hipStreamSynchronize(p->stream));
+  return PS_OK;
+}
+
 static bool org_same(const ps_origin* a, const ps_origin* b) {
   return a->device == b->device && a->N == b->N && a->key_i == b->key_i && a->key_d == b->key_d &&
          (a->prior == nullptr) == (b->prior == nullptr);
+}
+static bool org_same_known(const ps_origin* a, const ps_origin* b) {
+  return a->nknown == b->nknown && a->nk == b->nk && a->known_i == b->known_i && a->known_d == b->known_d;
 }
 
 extern "C" int ps_origin_merge(ps_origin* dst, ps_origin* src) {
@@ -485,9 +728,14 @@ extern "C" int ps_origin_merge(ps_origin* dst, ps_origin* src) {
   if (dst->N != src->N) return ps_fail(PS_ERR_BAD_ARG, "origin_merge: domains %d and %d", dst->N, src->N);
   if (!org_same(dst, src))
     return ps_fail(PS_ERR_BAD_ARG, "origin_merge: handles differ in findings, hypotheses, days or prior");
+  if (!org_same_known(dst, src))
+    return ps_fail(PS_ERR_BAD_ARG, "origin_merge: handles differ in their known releases (%d and %d of them)",
+                   dst->nknown, src->nknown);
   if (dst->next_group != 0 || src->next_group != 0)
     return ps_fail(PS_ERR_STATE, "origin_merge: a member is under way (group %d of %d is next)",
                    dst->next_group ? dst->next_group : src->next_group, dst->ngroup);
+  if (dst->next_bg != 0 || src->next_bg != 0)
+    return ps_fail(PS_ERR_STATE, "origin_merge: a member is under way (its backgrounds are in, its adds are not)");
   if (dst->W + src->W > 0xffffffffull) return ps_fail(PS_ERR_BAD_ARG, "origin_merge: total weight would pass 2^32 - 1");
   if (src->members == 0) return PS_OK;
   PS_HIP(hipSetDevice(dst->device));
@@ -502,6 +750,9 @@ extern "C" int ps_origin_merge(ps_origin* dst, ps_origin* src) {
   PS_TRY(dst->prof.end(dst->stream, e1));
   PS_HIP(hipMemcpyAsync(dst->rows + dst->members * dst->nhyp * 2, src->rows, (size_t)src->members * org_row_bytes(src),
                         hipMemcpyDeviceToDevice, dst->stream));
+  if (dst->nknown)
+    PS_HIP(hipMemcpyAsync(dst->null_rows + dst->members, src->null_rows, (size_t)src->members * sizeof(double),
+                          hipMemcpyDeviceToDevice, dst->stream));
   PS_TRY(dst->last.mark(dst->stream));
   PS_TRY(src->last.mark(dst->stream));   // src is read until then
   dst->W += src->W;
@@ -515,7 +766,7 @@ extern "C" int ps_origin_fetch(ps_origin* p, int what, int h, double* out) {
   if (what < 0 || what > 2) return ps_fail(PS_ERR_BAD_ARG, "origin_fetch: plane %d (0 A, 1 S, 2 the last member's l)", what);
   if (h < 0 || h >= p->nhyp) return ps_fail(PS_ERR_BAD_ARG, "origin_fetch: hypothesis %d of %d", h, p->nhyp);
   if (p->members == 0) return ps_fail(PS_ERR_STATE, "origin_fetch: no member added yet");
-  if (p->next_group != 0)
+  if (org_under_way(p))
     return ps_fail(PS_ERR_STATE, "origin_fetch: group %d of %d of the current member has not been added", p->next_group,
                    p->ngroup);
   PS_HIP(hipSetDevice(p->device));
@@ -547,7 +798,8 @@ extern "C" int ps_origin_info(ps_origin* p, double* total_weight, int64_t* membe
   if (total_weight) *total_weight = (double)p->W;
   if (members) *members = p->members;
   if (capacity) *capacity = p->rows_cap;
-  if (bytes) *bytes = (int64_t)(org_fixed_bytes(p, p->prior != nullptr) + (size_t)p->rows_cap * org_row_bytes(p));
+  if (bytes) *bytes = (int64_t)(org_fixed_bytes(p, p->prior != nullptr) + (size_t)p->rows_cap * org_row_bytes(p) +
+                             (p->nknown ? (size_t)p->rows_cap * sizeof(double) : 0));
   return PS_OK;
 }
 

@@ -87,6 +87,55 @@ PS_HD int origin_next_group(int next, int group, int ngroup) {
   return group + 1 == ngroup ? 0 : group + 1;
 }
 
+// ---- known releases in the background (ps_origin_set_known) ----
+#define PS_ORIGIN_MAX_KNOWN 32
+#define PS_ORIGIN_MAX_KGROUP 4
+
+// what finding (rowR, colR) sees of the known release k, drow / dcol cells off the centre: the centre release's
+// field at (r_o - drow, c_o - dcol), which is origin_source for the candidate cell (R + drow, R + dcol)
+PS_HD bool origin_known_source(int N, int rowR, int colR, int drow, int dcol, int64_t* src) {
+  const int R = N / 2;
+  return origin_source(N, rowR, colR, R + drow, R + dcol, src);
+}
+
+// one term of the background: fl(rak * v), rak = fl(rate_o * amount_k) formed on the host
+PS_HD double origin_bg_term(double rak, double v) { return rak * v; }
+
+// bg of one finding: the terms term[k * nfind + q] of every known release in index order, from +0.0
+PS_HD double origin_bg_sum(const double* term, int nknown, int nfind, int q) {
+  double s = 0.0;
+  for (int k = 0; k < nknown; ++k) {
+    const double t = term[(int64_t)k * nfind + q];
+    s = s + t;
+  }
+  return s;
+}
+
+// mu of candidate and hypothesis over a background: the product and the sum rounded separately
+PS_HD double origin_mu_bg(double bg, double ra, double v) {
+  const double t = ra * v;
+  const double mu = bg + t;
+  return mu;
+}
+
+// the null row: the terms at mu = bg in the kernel's order q, from +0.0
+PS_HD double origin_null_sum(const double* term, int nfind) {
+  double s = 0.0;
+  for (int q = 0; q < nfind; ++q) s = s + term[q];
+  return s;
+}
+
+// One member of a handle with nk known groups: the background calls 0 .. nk - 1 in order, then the adds.  next_bg
+// counts the background calls in (nk: complete), next_group is that of origin_next_group.  -> next_bg after the
+// background call for known group g, or -1 where it may not come now: out of order, after the backgrounds are
+// complete, or while the adds of a member are under way.
+PS_HD int origin_next_background(int next_bg, int next_group, int g, int nk) {
+  if (g < 0 || g >= nk || next_group != 0 || g != next_bg) return -1;
+  return g + 1;
+}
+// may group 0 of the adds come?  a handle without known releases: always; with: once the backgrounds are complete
+PS_HD bool origin_backgrounds_done(int next_bg, int nk) { return next_bg == nk; }
+
 // the member rows.  Stage one: block b of the likelihood launch owns the cells b * THREADS .. and leaves, per
 // hypothesis h, partial[(h * nblk + b) * 2 + {0, 1}] = (max, sum of exp(x - max)) of its cells.  Stage two: one
 // wave per hypothesis; lane l owns the partials l * chunk .. min((l + 1) * chunk, nblk) - 1 and adds them in

@@ -74,7 +74,9 @@ probability of such ground within any radius, which no map for one radius gives.
 `OriginMaps` runs the other way (ps_origin_*, csrc/ps_origin.hip): given findings -- probes as `check_probes` takes
 them -- the likelihood of every candidate origin cell at once, per member on the device, for a ladder of founding
 numbers and release days; the posterior of the origin with the parameter uncertainty integrated out, and the
-members' own evidence as row log-weights for `reweight=`.  Inference about the past: it recommends nothing.
+members' own evidence as row log-weights for `reweight=`.  Inference about the past: it recommends nothing.  With
+`known=` the releases that are facts lie in the background of every finding, and `second_source()` says whether the
+findings need a second source or the known releases explain them.
 """
 import ctypes as C
 import json
@@ -5875,9 +5877,33 @@ def parse_origin(text):
     return out
 
 
-def origin_request(findings, amounts='', lags='', levels='', prior='', rad_dist=None, rad_res=None):
+def parse_origin_known(text):
+    '''"east,north,amount[,lag];..." -> [(east_m, north_m, amount[, lag_days]), ...], or 'sites' for the word itself;
+    ValueError if malformed'''
+    if str(text).strip() == 'sites':
+        return 'sites'
+    out = []
+    for item in str(text).split(';'):
+        if not item.strip():
+            continue
+        parts = [x.strip() for x in item.split(',')]
+        try:
+            if len(parts) not in (3, 4):
+                raise ValueError
+            row = (float(parts[0]), float(parts[1]), float(parts[2])) + ((int(parts[3]),) if len(parts) == 4 else ())
+        except ValueError:
+            raise ValueError('known release %r is not east,north,amount[,lag]' % item)
+        out.append(row)
+    if not out:
+        raise ValueError('no known release in %r' % (text,))
+    return out
+
+
+def origin_request(findings, amounts='', lags='', levels='', prior='', rad_dist=None, rad_res=None, known='',
+                   sites=None):
     '''the origin= argument from the command line's strings: findings 'east,north,day,kind,rate[,n];...', amounts
-    '0.1,1,10', lags '0,2', levels '0.5,0.95', prior the path of an .npy plane; empty strings leave the defaults.
+    '0.1,1,10', lags '0,2', levels '0.5,0.95', prior the path of an .npy plane, known 'east,north,amount[,lag];...'
+    or 'sites' (the release sites of the run's own plan, `sites`); empty strings leave the defaults.
     Checked (check_origin) before it is returned; ValueError otherwise.'''
     def numbers(text, kind, what):
         try:
@@ -5893,11 +5919,44 @@ def origin_request(findings, amounts='', lags='', levels='', prior='', rad_dist=
         arg['levels'] = numbers(levels, float, 'levels')
     if prior:
         arg['prior'] = np.load(prior)
-    check_origin(arg, rad_dist, rad_res)
+    if known:
+        arg['known'] = parse_origin_known(known)
+    check_origin(arg, rad_dist, rad_res, sites=sites)
     return arg
 
 
-def check_origin(arg, rad_dist, rad_res, ndays=None):
+MAX_ORIGIN_KNOWN_LAGS = 4
+
+
+def check_origin_known(known, rad_dist, rad_res, ndays=None, sites=None):
+    '''The known= key of origin=: releases that are facts, not hypotheses -- [(east_m, north_m, amount[, lag_days]),
+    ...] as check_sites takes them (1..32, amount > 0 in multiples of the release number, the smallest lag 0), on at
+    most 4 distinct lags, each below ndays; or 'sites': the sites of the run's own plan, `sites` (the driver's).  A
+    known release after the last finding is allowed: it contributes 0.  -> the checked sites.  ValueError with the
+    offender named.'''
+    if isinstance(known, str):
+        if known != 'sites':
+            raise ValueError("origin: known must be a list of (east_m, north_m, amount[, lag_days]) or 'sites', got %r"
+                             % (known,))
+        if sites is None:
+            raise ValueError("origin: known='sites' takes the sites of the run's own sites= plan, and there is none")
+        known = sites
+    try:
+        out = check_sites(known, rad_dist, rad_res)
+    except ValueError as e:
+        raise ValueError('origin: known: %s' % str(e).replace('site ', 'known release '))
+    lags = sorted({r['lag'] for r in out})
+    if len(lags) > MAX_ORIGIN_KNOWN_LAGS:
+        raise ValueError('origin: known: %d different lags %r; at most %d fit one handle'
+                         % (len(lags), lags, MAX_ORIGIN_KNOWN_LAGS))
+    for k, r in enumerate(out):
+        if ndays is not None and r['lag'] >= ndays:
+            raise ValueError('origin: known release %d: a release %d days after the first lies beyond the model\'s %d days'
+                             % (k, r['lag'], ndays))
+    return out
+
+
+def check_origin(arg, rad_dist, rad_res, ndays=None, sites=None):
     '''The origin= argument as a plan.  arg: a list of findings, probes in the format of check_probes,
     (east_m, north_m, day, kind, rate[, n]), or dict(findings=[...], amounts=[0.1, 1, 10], lags=[0, 2],
     hypotheses=None, prior=None, levels=(0.5, 0.95)).  A hypothesis is (amount, lag): amount finite and > 0 in
@@ -5906,13 +5965,16 @@ def check_origin(arg, rad_dist, rad_res, ndays=None):
     is given.  1..64 findings on at most 32 distinct days, 1..8 distinct hypotheses with at most 4 distinct lags,
     every lag below ndays and no later than the last finding (a release after every finding explains none).
     prior: an N x N float64 log-prior plane, finite or -inf (a cell that cannot be the origin), not all -inf.
-    levels in (0, 1].  -> dict(findings, given, days, slots, hypotheses, lags, groups, prior, levels).
-    ValueError with the offender named.  rad_res=None skips the cells and the prior's shape.'''
-    keys = {'findings', 'amounts', 'lags', 'hypotheses', 'prior', 'levels'}
+    levels in (0, 1].  known: releases that are facts (check_origin_known; `sites`: the run's own release sites, for
+    known='sites'): every finding also catches their wasps, and the hypotheses are those of a second source.
+    -> dict(findings, given, days, slots, hypotheses, lags, groups, prior, levels, known, known_given, known_lags,
+    known_groups, model_lags); model_lags: the lags a model is needed for -- the hypotheses' and the known lags up to
+    the last finding's day.  ValueError with the offender named.  rad_res=None skips the cells and the prior's shape.'''
+    keys = {'findings', 'amounts', 'lags', 'hypotheses', 'prior', 'levels', 'known'}
     if isinstance(arg, dict):
         if 'findings' not in arg or set(arg) - keys:
             raise ValueError('origin must be a list of findings or dict(findings=[...], amounts=, lags=, hypotheses=, '
-                             'prior=, levels=), got keys %r' % (sorted(arg),))
+                             'prior=, levels=, known=), got keys %r' % (sorted(arg),))
         spec = dict(arg)
     else:
         spec = {'findings': arg}
@@ -5984,9 +6046,17 @@ def check_origin(arg, rad_dist, rad_res, ndays=None):
         raise ValueError('origin: %s' % e)
     if not levels:
         raise ValueError('origin: at least one level expected')
+    known, known_given, known_lags = None, None, []
+    if spec.get('known') is not None:
+        known = check_origin_known(spec['known'], rad_dist, rad_res, ndays, sites)
+        known_given = [[r['east'], r['north'], r['amount'], r['lag']] for r in known]
+        known_lags = sorted({r['lag'] for r in known})
     return {'findings': findings, 'given': [list(p) for p in spec['findings']], 'days': days,
             'slots': [days.index(f['day']) for f in findings], 'hypotheses': out, 'lags': lags,
-            'groups': [lags.index(g) for _a, g in out], 'prior': prior, 'levels': levels}
+            'groups': [lags.index(g) for _a, g in out], 'prior': prior, 'levels': levels,
+            'known': known, 'known_given': known_given, 'known_lags': known_lags,
+            'known_groups': [known_lags.index(r['lag']) for r in known or ()],
+            'model_lags': sorted(set(lags) | {g for g in known_lags if g <= days[-1]})}
 
 
 def origin_log_evidence(A, S, W):
@@ -6056,6 +6126,53 @@ def origin_member_log_evidence(rows, log_prior_mass=0.0):
     return np.where(mx == -np.inf, -np.inf, out)
 
 
+def _check_prior_second(prior):
+    try:
+        p = float(prior)
+    except (TypeError, ValueError):
+        raise ValueError('the prior probability of a second source must be a number in [0, 1], got %r' % (prior,))
+    if not 0.0 <= p <= 1.0:
+        raise ValueError('the prior probability of a second source must lie in [0, 1], got %r' % (prior,))
+    return p
+
+
+def origin_log_mean_exp(values, weights):
+    '''log(sum_m w_m exp(x_m) / sum_m w_m), summed in member order; -inf where every x is'''
+    x, w = np.asarray(values, dtype=np.float64), np.asarray(weights, dtype=np.float64)
+    mx = x.max() if x.size else -np.inf
+    if mx == -np.inf:
+        return float('-inf')
+    return float(mx + np.log((w * np.exp(x - mx)).sum()) - np.log(w.sum()))
+
+
+def origin_log_evidence_second(E, log_prior=None):
+    '''log of the prior-weighted mean over cells and hypotheses of exp E_h(s), from E [H, N, N]: the prior pi
+    normalised to 1 (zeros: the uniform prior), the hypotheses equally likely; -inf where no cell is possible'''
+    E = np.asarray(E, dtype=np.float64)
+    x = E if log_prior is None else E + np.asarray(log_prior, dtype=np.float64)[None]
+    x = np.where(np.isnan(x), -np.inf, x)
+    mx = x.max()
+    if mx == -np.inf:
+        return float('-inf')
+    return float(mx + np.log(np.exp(x - mx).sum()) - np.log(E.shape[0])
+                 - origin_log_prior_mass(log_prior, E.shape[1] * E.shape[2]))
+
+
+def origin_second_source(log_evidence_second, log_evidence_null, prior=0.5, ess_second=None, ess_null=None):
+    '''the summary of "second source or the known releases alone?" from the two log evidences: the log Bayes
+    factor second : alone (nan where both are -inf) and the posterior probability of a second source at `prior`'''
+    a, b = float(log_evidence_second), float(log_evidence_null)
+    if a == -np.inf and b == -np.inf:
+        lbf, prob = float('nan'), float('nan')
+    else:
+        lbf = a - b
+        with np.errstate(divide='ignore', over='ignore'):
+            lo = lbf + np.log(prior) - np.log1p(-prior)          # the posterior log-odds
+            prob = float(1.0 / (1.0 + np.exp(-lo)))
+    return {'log_bayes_factor': lbf, 'probability': prob, 'prior': float(prior), 'log_evidence_second': a,
+            'log_evidence_null': b, 'ess_second': ess_second, 'ess_null': ess_null}
+
+
 class OriginMaps(_Accumulator):
     '''Where, when and in what number did the wasps in these traps start?  For findings in the format of the
     reweighting probes and up to 8 hypotheses (amount, lag) the likelihood of every candidate origin cell at once,
@@ -6078,8 +6195,12 @@ class OriginMaps(_Accumulator):
         self.findings, self.pairs = self.plan['findings'], self.plan['hypotheses']
         self.days, self.lags, self.levels = self.plan['days'], self.plan['lags'], self.plan['levels']
         self.log_prior = self.plan['prior']
-        self.lagged = check_lagged(pop_model, self.lags, lagged)
+        self.known, self.known_lags = self.plan['known'], self.plan['known_lags']
+        self.model_lags = self.plan['model_lags']
+        self.lagged = check_lagged(pop_model, self.model_lags, lagged)
         self.slots = site_slots(self.lags, self.days)
+        # a known release after the last finding reads no day: every slot None, it contributes 0
+        self.known_slots = [[D - lag if D >= lag else None for D in self.days] for lag in self.known_lags]
         self._attach(pop_model)
         f = self.findings
         prior = None if self.log_prior is None else L.p_f64(self.log_prior)
@@ -6088,12 +6209,21 @@ class OriginMaps(_Accumulator):
                      L.p_f64(L.f64([p['rate'] for p in f])), L.p_f64(L.f64([p['n'] or 0 for p in f])), len(self.days),
                      len(self.pairs), L.p_f64(L.f64([a for a, _g in self.pairs])),
                      L.p_i32(L.i32(self.plan['groups'])), len(self.lags), prior)
+        if self.known:
+            try:
+                self._call('set_known', len(self.known), L.p_i32(L.i32([k['drow'] for k in self.known])),
+                           L.p_i32(L.i32([k['dcol'] for k in self.known])),
+                           L.p_f64(L.f64([k['amount'] for k in self.known])),
+                           L.p_i32(L.i32(self.plan['known_groups'])), len(self.known_lags))
+            except Exception:
+                self.close()
+                raise
 
     @classmethod
     def with_lagged_models(cls, pop_model, origin, wind_data=None):
         '''the maps with the models of the later release days built here (lagged_models); `close()` closes them'''
         plan = check_origin(origin, pop_model.rad_dist, pop_model.rad_res, len(pop_model.days))
-        made = lagged_models(pop_model, plan['lags'], wind_data)
+        made = lagged_models(pop_model, plan['model_lags'], wind_data)
         try:
             self = cls(pop_model, origin, made)
         except Exception:
@@ -6109,21 +6239,29 @@ class OriginMaps(_Accumulator):
 
     def evaluate_lagged(self, *model_args):
         '''evaluate the model of every later release day over the days the findings need, enqueued only'''
-        for lag, m in self.models():
-            if lag:
-                m.evaluate(*model_args, ndays=self.days[-1] - lag + 1, want_stats=False)
+        for lag, m in sorted(self.lagged.items()):
+            m.evaluate(*model_args, ndays=self.days[-1] - lag + 1, want_stats=False)
+
+    def _model(self, lag):
+        '''the model of a release `lag` days after the first; a known lag after the last finding reads no record and
+        takes the base model'''
+        return self.pm if lag == 0 or lag not in self.lagged else self.lagged[lag]
+
+    def _group_call(self, g, lag, md, what):
+        m = self._model(lag)
+        _check_evaluated(m, [d for d in md if d is not None], 'origin maps (%s %d)' % (what, lag))
+        days = [0 if d is None else d for d in md]
+        kind, idx, delta = _day_slots(days)
+        kind[np.array([d is None for d in md], dtype=bool)] = L.REC_NONE
+        stat, post = _day_scales(m, days)
+        return (m.solver._h, g, len(days), L.p_i32(kind), L.p_i32(idx), L.p_f64(stat), L.p_f64(post), L.p_i32(delta),
+                NEGVAL)
 
     def _calls(self, w):
-        calls = []
-        for g, (lag, m) in enumerate(self.models()):
-            md = self.slots[g]
-            _check_evaluated(m, [d for d in md if d is not None], 'origin maps (lag %d)' % lag)
-            days = [0 if d is None else d for d in md]
-            kind, idx, delta = _day_slots(days)
-            kind[np.array([d is None for d in md], dtype=bool)] = L.REC_NONE
-            stat, post = _day_scales(m, days)
-            calls.append((m.solver._h, g, len(days), L.p_i32(kind), L.p_i32(idx), L.p_f64(stat), L.p_f64(post),
-                          L.p_i32(delta), NEGVAL, w))
+        '''[(operation, arguments), ...] of one member: the backgrounds of the known groups, then the adds'''
+        calls = [('background', self._group_call(g, lag, self.known_slots[g], 'known lag'))
+                 for g, lag in enumerate(self.known_lags)]
+        calls += [('add', self._group_call(g, lag, self.slots[g], 'lag') + (w,)) for g, lag in enumerate(self.lags)]
         return calls
 
     def reserve(self, n):
@@ -6133,9 +6271,10 @@ class OriginMaps(_Accumulator):
     def add(self, weight=1):
         '''Accumulate the last evaluation of the model -- and of every lagged model (`evaluate_lagged`) -- with
         integer weight >= 1: one launch pair per lag, each on its solver's stream, no host synchronisation unless
-        the member rows grow.  Every model is checked before the first launch.'''
-        for call in self._calls(self._weight(weight)):
-            self._call('add', *call)
+        the member rows grow.  Every model is checked before the first launch.  With known releases the background
+        calls of the known lags come first, one small launch each.'''
+        for op, call in self._calls(self._weight(weight)):
+            self._call(op, *call)
 
     def merge(self, other):
         '''self += other (same device, domain, findings, hypotheses and prior); other's members follow self's'''
@@ -6247,12 +6386,65 @@ class OriginMaps(_Accumulator):
         (origin_member_log_evidence)'''
         return origin_member_log_evidence(self.member_rows()[0], origin_log_prior_mass(self.log_prior, self.N * self.N))
 
-    def log_weights(self):
+    def log_weights(self, prior_second=None):
         '''the members' log-evidence in chain-row form, one entry per row of the chain (a member of weight w is w
         equal rows): what posterior_predictive(reweight={name: dict(log_weights=[...])}) takes per chain, to update
-        every forward map for the findings under an unknown origin'''
+        every forward map for the findings under an unknown origin.  With known releases that is conditional on a
+        second source existing; prior_second, a probability in [0, 1], gives per row the mixture of both
+        explanations instead: log(p exp(second) + (1 - p) exp(l0)).'''
         rows, w = self.member_rows()
-        return np.repeat(origin_member_log_evidence(rows, origin_log_prior_mass(self.log_prior, self.N * self.N)), w)
+        lw = np.repeat(origin_member_log_evidence(rows, origin_log_prior_mass(self.log_prior, self.N * self.N)), w)
+        if prior_second is None:
+            return lw
+        p = _check_prior_second(prior_second)
+        l0 = np.repeat(self.null_rows(), w)
+        with np.errstate(divide='ignore'):
+            return np.logaddexp(np.log(p) + lw, np.log1p(-p) + l0)
+
+    # ---------------------------------------------------------------- known releases: is there a second source?
+    def _need_known(self, what):
+        if not getattr(self, 'known', None):
+            raise ValueError('%s: these origin maps have no known releases (origin=dict(known=[...]))' % what)
+
+    def background(self):
+        '''(bg [findings] in the order given, l0): the last member's background -- what the known releases alone put
+        into every trap, in the units of mu -- and its null row'''
+        self._need_known('background')
+        bg, l0 = np.empty(len(self.findings), dtype=np.float64), C.c_double()
+        self._call('fetch_background', L.p_f64(bg), C.byref(l0))
+        return bg, float(l0.value)
+
+    def null_rows(self):
+        '''[members] float64 in add order: l0, each member's log-likelihood of the findings under the known releases
+        alone'''
+        self._need_known('null_rows')
+        out = np.empty(self.members, dtype=np.float64)
+        self._call('null_rows', self.members, L.p_f64(out))
+        return out
+
+    def log_evidence_null(self):
+        '''log of the weighted mean over the members of exp(l0): the evidence for "the known releases alone"'''
+        self._need_known('log_evidence_null')
+        return origin_log_mean_exp(self.null_rows(), self.member_rows()[1])
+
+    def log_evidence_second(self):
+        '''log of the prior-weighted mean over cells and hypotheses of exp E_h(s): the evidence for "a second source
+        somewhere", the prior pi normalised and the hypotheses equally likely'''
+        self._need_known('log_evidence_second')
+        E = np.stack([self.log_evidence(h) for h in range(len(self.pairs))])
+        return origin_log_evidence_second(E, self.log_prior)
+
+    def second_source(self, prior=0.5):
+        '''Do the findings need a second source, or do the known releases explain them?  -> dict(log_bayes_factor:
+        second source : known releases alone, probability: the posterior probability of a second source at the prior
+        probability `prior`, prior, log_evidence_second, log_evidence_null, ess_second, ess_null: the Kish effective
+        sample of the chain's rows behind either evidence).  A summary; it recommends nothing.'''
+        self._need_known('second_source')
+        p = _check_prior_second(prior)
+        w = self.member_rows()[1]
+        second, null = self.log_evidence_second(), self.log_evidence_null()
+        return origin_second_source(second, null, p, reweight_diagnostics(self.log_weights())['ess'],
+                                    reweight_diagnostics(np.repeat(self.null_rows(), w))['ess'])
 
     def diagnostics(self, min_ess=DEFAULT_MIN_ESS):
         '''reweight_diagnostics of the rows' contributions to the total evidence (Kish ESS, the largest share); a
@@ -6267,8 +6459,11 @@ class OriginMaps(_Accumulator):
 
     def describe(self):
         '''the request for a result file'''
-        return {'findings': self.plan['given'], 'hypotheses': [list(h) for h in self.pairs],
-                'levels': list(self.levels), 'prior': self.log_prior is not None}
+        out = {'findings': self.plan['given'], 'hypotheses': [list(h) for h in self.pairs],
+               'levels': list(self.levels), 'prior': self.log_prior is not None}
+        if getattr(self, 'known', None):
+            out['known'] = self.plan['known_given']
+        return out
 
     def close(self):
         super().close()
@@ -6288,6 +6483,8 @@ def origin_block(om):
             block.update(masses=om.hypotheses(), mode=om.mode(), areas={level_tag(p): om.area(p) for p in om.levels})
         except ValueError as e:        # no member makes any cell possible: said in the block, the files are still written
             block.update(masses=None, mode=None, areas=None, impossible=str(e))
+        if getattr(om, 'known', None):     # second source or the known releases alone: a summary, no recommendation
+            block['second_source'] = om.second_source()
     block['warnings'] = [str(w.message) for w in caught]
     for w in caught:
         warnings.warn(w.message, w.category, stacklevel=2)
@@ -6296,7 +6493,8 @@ def origin_block(om):
 
 def save_origin(outfile, om):
     '''PREFIX_origin.npz: E_h per hypothesis (log_evidence_h<h>), the marginal posterior, the regions at the
-    request's levels (region_<tag>), the member rows and weights, the hypotheses; -> (path, json block).  Where no
+    request's levels (region_<tag>), the member rows and weights, the hypotheses -- with known releases also `known`,
+    `null_rows` and `background_last`, and a `second_source` entry in the block; -> (path, json block).  Where no
     member makes any cell possible the posterior is all zero, the regions are empty and the block says so
     (`impossible`).'''
     arrays = {'log_evidence_h%d' % h: om.log_evidence(h) for h in range(len(om.pairs))}
@@ -6310,6 +6508,9 @@ def save_origin(outfile, om):
             arrays['region_' + level_tag(p)] = np.zeros((om.N, om.N), dtype=np.int8)
     rows, w = om.member_rows()
     arrays.update(member_rows=rows, member_weights=w, hypotheses=np.array(om.pairs, dtype=np.float64))
+    if getattr(om, 'known', None):         # [K, 4] east, north, amount, lag; l0 per member; the last member's bg
+        arrays.update(known=np.array(om.plan['known_given'], dtype=np.float64), null_rows=om.null_rows(),
+                      background_last=om.background()[0])
     path = outfile + '_origin.npz'
     np.savez_compressed(path, **arrays)
     return path, origin_block(om)
@@ -7132,6 +7333,11 @@ def _check_request(q):
         q.px_plan = check_proximity(q.proximity, ndays0(), cell_m, q.evaluate)
 
     def check_origin_arg():
+        if isinstance(q.origin, dict) and isinstance(q.origin.get('known'), str) and q.origin['known'] == 'sites':
+            plan = getattr(q, 'sites', None)              # known='sites': the release sites of the run's own plan
+            if not isinstance(plan, dict) or 'sites' not in plan:
+                raise ValueError("origin: known='sites' takes the sites of the run's own sites= plan, and there is none")
+            q.origin = dict(q.origin, known=[tuple(s) for s in plan['sites']])
         q.or_plan = check_origin(q.origin, None if pm0 is None else pm0.rad_dist, None if pm0 is None else pm0.rad_res,
                                  ndays0())
     # the options that need the device, in the order in which they are checked: (name, False switches it off too,
@@ -7542,7 +7748,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                     if (q.site_plan is not None or q.or_plan is not None) and p not in late:
                         # once per model, for the union of both plans' release days and the origin hypotheses'
                         lags = set(q.site_plan[2] if q.site_plan else ()) | set(q.cmp_plan[2] if q.cmp_plan else ())
-                        lags |= set(q.or_plan['lags'] if q.or_plan else ())
+                        lags |= set(q.or_plan['model_lags'] if q.or_plan else ())   # the known lags among them
                         late[p] = lagged_models(pm, sorted(lags))
                     _build_sets(chain_sets[ci], q, pm, ci, len(rl), late.get(p))
                 results[ci] = _evaluate_runs(pm, rows, rl, mcols, evaluate, q.want_obs, locinfo, chain_sets[ci])

@@ -77,13 +77,16 @@ Without --chain a short chain is sampled first (--samples) and saved next to --o
         [--proximity 'DAY,T[,in];...'] [--proximity-radii 100,400,1600] [--proximity-levels 0.05,0.5,0.95]
         [--modes [K]] [--modes-days d1,d2|all] [--modes-transform sqrt|raw]
         [--origin 'EAST,NORTH,DAY,KIND,RATE[,N];...'] [--origin-amounts 0.1,1,10] [--origin-lags 0,2]
-        [--origin-levels 0.5,0.95] [--origin-prior file.npy]
+        [--origin-levels 0.5,0.95] [--origin-prior file.npy] [--origin-known 'EAST,NORTH,AMOUNT[,LAG];...' | sites]
 
 With --origin the origin maps: for findings 'EAST,NORTH,DAY,KIND,RATE[,N]' (metres from the domain centre, model day,
 count | none | found, the rate and for a count the number found) the posterior of where, when (--origin-lags) and in
 what number (--origin-amounts, multiples of the release number) the population started, saved as PREFIX_origin.npz
 with the hypothesis masses, the mode, the areas of the regions at --origin-levels and the diagnostics under
-predictive.origin of the json.
+predictive.origin of the json.  With --origin-known the releases that are facts -- 'EAST,NORTH,AMOUNT[,LAG];...', or
+the word sites for those of --sites -- lie in the background of every finding: the hypotheses are those of a second
+source, PREFIX_origin.npz gains known, null_rows and background_last, and the json a second_source entry (the log
+Bayes factor second source : known releases alone).
 """
 import argparse
 import json
@@ -236,6 +239,9 @@ def main():
                     '--origin)')
     ap.add_argument('--origin-prior', default='', help='an N x N .npy log-prior plane, -inf where the origin cannot '
                     'be (with --origin; default flat)')
+    ap.add_argument('--origin-known', default='', help="releases that are facts, 'EAST,NORTH,AMOUNT[,LAG];...' or the "
+                    'word sites for those of --sites: every finding also catches their wasps, and the hypotheses are '
+                    'those of a second source (with --origin; default none)')
     ap.add_argument('--information', default='', help="described traps 'DAY,RATE[,YMAX];...': per cell the mutual "
                     'information in nats between the count of a trap of effort RATE on model day DAY, observed as '
                     '0, 1, .., YMAX (default 0) and more, and the identity of the member (default: off)')
@@ -362,9 +368,12 @@ def main():
         from parasitoids_amd.predictive import origin_request
         try:
             origin = origin_request(args.origin, args.origin_amounts, args.origin_lags, args.origin_levels,
-                                    args.origin_prior, 10000.0, args.rad_res)
+                                    args.origin_prior, 10000.0, args.rad_res, args.origin_known,
+                                    sites['sites'] if sites else None)
         except ValueError as e:
             ap.error('--origin: %s' % e)
+    elif args.origin_known:
+        ap.error('--origin-known needs --origin')
     wd, days = PM.get_wind_data(os.path.join(ROOT, 'parasitoids_amd', 'data', 'kalbar'), 30, '00:00')
     modes = None
     if args.modes is not None:           # as do bad --modes settings
