@@ -1044,6 +1044,104 @@ int ps_wsum_reset(ps_wsum* h);
 int ps_wsum_prof(ps_wsum* h, int enable, double* total_ms, int64_t* launches);
 void ps_wsum_destroy(ps_wsum* h);
 
+/* ---- reweighted posterior histograms: quantiles and credible bands under new observations ----
+ * (no reference counterpart.)  ps_hist's per-cell histograms with the real weights of ps_wsum: J scenarios (1..4),
+ * nslot slots (1..32) of N x N cells and the edge table of a ps_hist: 2 <= nedge = B + 1 <= 1024 edges, finite,
+ * > 0, strictly increasing; bin b = searchsorted(edges, v, side='right'), bin 0 not stored.  Per scenario j fp64
+ * planes H[j][slot][b = 1 .. B+1][pitch] on the scale exp(ref_j) the caller keeps, and per slot and cell one
+ * range word of the lowest and highest touched bin as ps_hist's, shared by the scenarios (a superset is harmless:
+ * untouched planes hold +0.0).  Host side per scenario W_j (a double, 0 while empty), members_j and skipped_j.
+ * The full size, J * nslot * nedge * pitch * 8 B + nslot * pitch * 4 B plus scratch, is checked against the free
+ * device memory first: PS_ERR_OOM before anything is allocated.  One thread owns a pair of cells: no atomics, the
+ * same calls in the same order give the same bits; these are floating-point sums, so another order of adds or
+ * merges moves a plane within the rounding of its sums.  Every operation records an event that the next one waits
+ * on, on whatever stream it runs (the solver's for add, the handle's own otherwise). */
+typedef struct ps_whist ps_whist;
+int ps_whist_create(int device, int N, int nscen, int nslot, int nedge, const double* edges, ps_whist** out);
+/* One member from the records of solver s (slot descriptors and the value v of a cell as ps_summary_add; rescale,
+ * omega and their refusals as ps_wsum_add).  omega_j == 0: the member leaves scenario j untouched and skipped_j
+ * grows by one.  For a scenario with omega > 0, every step a statement of its own (one rounding each):
+ *   host:      W = W * r;  W = W + omega;
+ *   per cell:  H_b = H_b * r on every plane (r != 1 only: a launch of its own over each cell's touched planes);
+ *              H_b = H_b + omega for the cell's bin b >= 1
+ * so a host loop with one rounded operation per statement reproduces every plane bit for bit, and with r = 1 and
+ * integer omega the planes hold the counts of a ps_hist fed alongside.  The add is one launch on the solver's
+ * stream that reads the record once for all scenarios; no host synchronisation.  An add refused for its arguments
+ * (PS_ERR_BAD_ARG, every one checked before anything is enqueued) changes nothing; a HIP error of a launch or of a
+ * profiling event after the rescale was enqueued (PS_ERR_HIP) leaves the planes rescaled and W, the members and
+ * the caller's reference as they were: the handle is then to be reset. */
+int ps_whist_add(ps_whist* h, ps_solver* s, int nslot, const int32_t* kind, const int32_t* idx,
+                 const double* stat_scale, const double* post_scale, const int32_t* use_delta, double negval,
+                 int nscen, const double* rescale, const double* omega);
+/* The same member whose values are the current outputs of a projection or a release plan, as ps_hist_add_project /
+ * ps_hist_add_sites take them: slot e takes Y_e, on the handle's stream behind the source's last operation; its
+ * next apply waits for the read. */
+int ps_whist_add_project(ps_whist* h, ps_project* p, int nscen, const double* rescale, const double* omega);
+int ps_whist_add_sites(ps_whist* h, ps_sites* p, int nscen, const double* rescale, const double* omega);
+/* dst += src per scenario, same device, N, scenarios, slots and edges; src stays as it is.  ra[j], rb[j] in [0, 1]
+ * bring both sides to a common scale (the caller's): x = Ha ra; y = Hb rb; H = x + y (three statements), W
+ * likewise; the range words take the per-half maximum.  A scenario empty in src adds its skipped count alone; into
+ * a scenario empty in dst it is a device copy, bit for bit, W included. */
+int ps_whist_merge(ps_whist* dst, ps_whist* src, const double* ra, const double* rb);
+/* per scenario (any pointer may be NULL): W, members (adds with omega > 0) and skipped (adds with omega == 0) */
+int ps_whist_info(ps_whist* h, double* total_weight /* nscen */, int64_t* members, int64_t* skipped);
+/* One slot's quantile at p in (0, 1] under one scenario (synchronises; any output may be NULL).  From the cell's
+ * highest touched bin down T_b = T_{b+1} + H_b (one rounded add per plane, T above the top 0) and
+ * C_b = W - T_{b+1}; b* = the smallest b with C_b >= p W (bin, int32).  lower / upper: the bracket of b* as
+ * ps_hist_quantile's.  value: e_{b*-1} (e_{b*} / e_{b*-1})^f, f = (p W - C_{b*-1}) / H_{b*} clamped to [0, 1], for
+ * 1 <= b* <= B, 0 at b* = 0, e_B at b* = B + 1.  With integer weights every step is exact and the outputs are
+ * those of ps_hist_quantile bit for bit.  PS_ERR_STATE while the scenario has W = 0. */
+int ps_whist_quantile(ps_whist* h, int scen, int slot, double p, double* value, double* lower, double* upper,
+                      int32_t* bin);
+/* min(T_{k+1} / W, 1.0) per cell: P(v >= e_k) under the scenario, at any edge k (synchronises).  PS_ERR_STATE while
+ * the scenario has W = 0. */
+int ps_whist_exceed(ps_whist* h, int scen, int slot, int k, double* out /* N*N */);
+/* the raw plane of bin b (1 .. B + 1) of one scenario and slot, on the scale exp(ref) (synchronises) */
+int ps_whist_fetch(ps_whist* h, int scen, int slot, int b, double* out /* N*N */);
+int ps_whist_reset(ps_whist* h);
+/* measurement: HIP-event timing of the add launches, the quantile and exceedance launches and the rescale
+ * launches.  enable 1 on, 0 off, < 0 unchanged; the totals so far go to the non-NULL outputs (synchronises). */
+int ps_whist_prof(ps_whist* h, int enable, double* add_ms, int64_t* adds, double* q_ms, int64_t* q_launches,
+                  double* rescale_ms, int64_t* rescales);
+void ps_whist_destroy(ps_whist* h);
+
+/* ---- reweighted posterior arrival maps: when do they reach each cell under new observations ----
+ * (no reference counterpart.)  ps_arrival's arrival counts with the real weights of ps_wsum: J scenarios (1..4),
+ * nslot slots (1..32) and 1..4 thresholds as ps_arrival's; a_k(c) = min{s : v_s(c) >= t_k} exactly as there.  Per
+ * scenario j fp64 planes A[j][k][s][pitch]: the weight of the members with a_k(c) = s on the scale exp(ref_j);
+ * "never" is W - the rest, not stored.  Host side per scenario W_j, members_j, skipped_j.  The whole block,
+ * J * K * nslot * pitch * 8 B plus scratch, is checked against the free device memory first (PS_ERR_OOM).  The
+ * members' reached-cell rows stay with ps_arrival.  One writer per cell, no atomics; floating-point sums as
+ * ps_whist's.  Stream ordering as ps_whist. */
+typedef struct ps_warr ps_warr;
+int ps_warr_create(int device, int N, int nscen, int nslot, int nthr, const double* thr, ps_warr** out);
+/* One member (arguments and refusals as ps_whist_add): where r != 1, A = A * r over the scenario's planes in a
+ * launch of its own; then one launch walks the slots of every cell pair as ps_arrival_add does, the records read
+ * once for all scenarios, and A[j][k][a_k] = A + omega_j where a_k < nslot.  Host: W = W * r; W = W + omega.  After a
+ * HIP error behind an enqueued rescale the handle is to be reset, as ps_whist_add states. */
+int ps_warr_add(ps_warr* h, ps_solver* s, int nslot, const int32_t* kind, const int32_t* idx,
+                const double* stat_scale, const double* post_scale, const int32_t* use_delta, double negval,
+                int nscen, const double* rescale, const double* omega);
+/* The same for the current outputs of a projection or a release plan, as ps_arrival_add_project / _add_sites */
+int ps_warr_add_project(ps_warr* h, ps_project* p, int nscen, const double* rescale, const double* omega);
+int ps_warr_add_sites(ps_warr* h, ps_sites* p, int nscen, const double* rescale, const double* omega);
+/* dst += src per scenario as ps_whist_merge: x = Aa ra; y = Ab rb; A = x + y; a device copy into an empty one */
+int ps_warr_merge(ps_warr* dst, ps_warr* src, const double* ra, const double* rb);
+int ps_warr_info(ps_warr* h, double* total_weight /* nscen */, int64_t* members, int64_t* skipped);
+/* min(C_slot / W, 1.0) per cell, C_s = C_{s-1} + A_s ascending, one rounded add each (synchronises).  PS_ERR_STATE
+ * while the scenario has W = 0. */
+int ps_warr_prob(ps_warr* h, int scen, int k, int slot, double* out /* N*N */);
+/* the smallest slot s with C_s >= p W per cell, -1 where even the last slot falls short; p in (0, 1]
+ * (synchronises).  PS_ERR_STATE while the scenario has W = 0. */
+int ps_warr_quantile(ps_warr* h, int scen, int k, double p, int32_t* out /* N*N */);
+/* the raw plane of threshold k and slot 0 .. nslot - 1 of one scenario, on the scale exp(ref) (synchronises) */
+int ps_warr_fetch(ps_warr* h, int scen, int k, int slot, double* out /* N*N */);
+int ps_warr_reset(ps_warr* h);
+/* measurement: HIP-event timing of the add, map and rescale launches, as ps_whist_prof */
+int ps_warr_prof(ps_warr* h, int enable, double* add_ms, int64_t* adds, double* map_ms, int64_t* maps,
+                 double* rescale_ms, int64_t* rescales);
+void ps_warr_destroy(ps_warr* h);
+
 /* ---- catch-probability fields: what a trap at each cell would find in one member's field ----
  * (no reference counterpart; the Poisson model is that of the package's own likelihood, mcmc.loglik_parts.)
  * A handle lives on one device and holds nout outputs (1..32) over nin inputs (1..32): output e is

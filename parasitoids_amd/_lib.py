@@ -284,6 +284,32 @@ SIGNATURES = {
     'ps_wsum_reset': (C.c_int, [_VP]),
     'ps_wsum_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P]),
     'ps_wsum_destroy': (None, [_VP]),
+    'ps_whist_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F64P, C.POINTER(_VP)]),
+    'ps_whist_add': (C.c_int, [_VP, _VP, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P, C.c_double, C.c_int, _F64P,
+                               _F64P]),
+    'ps_whist_add_project': (C.c_int, [_VP, _VP, C.c_int, _F64P, _F64P]),
+    'ps_whist_add_sites': (C.c_int, [_VP, _VP, C.c_int, _F64P, _F64P]),
+    'ps_whist_merge': (C.c_int, [_VP, _VP, _F64P, _F64P]),
+    'ps_whist_info': (C.c_int, [_VP, _F64P, _I64P, _I64P]),
+    'ps_whist_quantile': (C.c_int, [_VP, C.c_int, C.c_int, C.c_double, _F64P, _F64P, _F64P, _I32P]),
+    'ps_whist_exceed': (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, _F64P]),
+    'ps_whist_fetch': (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, _F64P]),
+    'ps_whist_reset': (C.c_int, [_VP]),
+    'ps_whist_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P, _F64P, _I64P, _F64P, _I64P]),
+    'ps_whist_destroy': (None, [_VP]),
+    'ps_warr_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F64P, C.POINTER(_VP)]),
+    'ps_warr_add': (C.c_int, [_VP, _VP, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P, C.c_double, C.c_int, _F64P,
+                              _F64P]),
+    'ps_warr_add_project': (C.c_int, [_VP, _VP, C.c_int, _F64P, _F64P]),
+    'ps_warr_add_sites': (C.c_int, [_VP, _VP, C.c_int, _F64P, _F64P]),
+    'ps_warr_merge': (C.c_int, [_VP, _VP, _F64P, _F64P]),
+    'ps_warr_info': (C.c_int, [_VP, _F64P, _I64P, _I64P]),
+    'ps_warr_prob': (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, _F64P]),
+    'ps_warr_quantile': (C.c_int, [_VP, C.c_int, C.c_int, C.c_double, _I32P]),
+    'ps_warr_fetch': (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, _F64P]),
+    'ps_warr_reset': (C.c_int, [_VP]),
+    'ps_warr_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P, _F64P, _I64P, _F64P, _I64P]),
+    'ps_warr_destroy': (None, [_VP]),
     'ps_catch_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _I32P, _F64P, _I32P, C.POINTER(_VP)]),
     'ps_catch_apply': (C.c_int, [_VP, _VP, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P, C.c_double]),
     'ps_catch_apply_project': (C.c_int, [_VP, _VP]),

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "ps_common.h"
+#include "ps_hist_core.h"   // hist_bin, hist_range_add
 
 #define PS_HIST_MAX_EDGES 1024
 #define PS_HIST_CHUNK 32      // slots per launch: 32 descriptors = 1.3 kB of kernel arguments
@@ -30,27 +31,6 @@ struct HistSlot {
 struct HistSlots {
   HistSlot s[PS_HIST_CHUNK];
 };
-
-// searchsorted(e, v, side='right') over e[0..n): the number of edges <= v.  Comparisons only, no log.
-__device__ inline int hist_bin(const double* e, int n, double v) {
-  int lo = 0;
-  while (n > 0) {
-    const int half = n >> 1;
-    if (e[lo + half] <= v) {
-      lo += half + 1;
-      n -= half + 1;
-    } else {
-      n = half;
-    }
-  }
-  return lo;
-}
-
-__device__ inline uint32_t hist_range_add(uint32_t r, int b) {
-  const uint32_t hi = max(r >> 16, (uint32_t)b);
-  const uint32_t lo = max(r & 0xffffu, 0xffffu - (uint32_t)b);
-  return (hi << 16) | lo;
-}
 
 // blockIdx.y = slot of the chunk; thread j of the slot owns the pair of cells 2j, 2j + 1 (j == npair: the
 // tail cell of an odd N*N alone).  The record is read first; a block with no value >= e_0 returns before

@@ -351,10 +351,18 @@ def check_arrival_days(days):
 
 
 def weighted_lower_quantile(values, weights, p):
-    '''min{a : sum of w_m over a_m <= a >= p W}, compared as (double)(integer weight) >= p * (double)W'''
+    '''min{a : sum of w_m over a_m <= a >= p W}, compared as (double)(integer weight) >= p * (double)W; real
+    (floating-point) weights are summed as they are, in the order of the sorted values, and W is the last entry of
+    that running sum -- the sum taken in another order can differ from it by an ulp, and at p = 1 no entry would
+    reach it'''
     v = np.asarray(values)
-    w = np.asarray(weights, dtype=np.int64)
+    w = np.asarray(weights)
     order = np.argsort(v, kind='stable')
+    if w.dtype.kind == 'f':
+        cw = np.cumsum(w[order])
+        j = int(np.argmax(cw >= float(p) * cw[-1]))
+        return v[order][j]
+    w = w.astype(np.int64)
     cw = np.cumsum(w[order])
     j = int(np.argmax(cw.astype(np.float64) >= float(p) * float(w.sum())))
     return v[order][j]
@@ -2489,11 +2497,11 @@ def exposure_plan(exposure, ndays=None):
 # source: the model's day fields, a Projection, the ReleaseSites of sites= and, after it, plan B of compare=.
 # 'apply' is the source's own.  The three orders differ for no better reason than the history of the maps.
 FEED_ORDER = {
-    'days': ('summary', 'origin', 'core_range', 'reweight', 'catch', 'neighbourhood', 'proximity', 'information', 'excursion', 'mc_error',
+    'days': ('summary', 'origin', 'core_range', 'reweight', 'reweight_histogram', 'reweight_arrival', 'catch', 'neighbourhood', 'proximity', 'information', 'excursion', 'mc_error',
              'sensitivity', 'dependence', 'histogram', 'arrival', 'peak', 'patches', 'pathways', 'modes'),
-    'projection': ('apply', 'summary', 'reweight', 'mc_error', 'sensitivity', 'dependence', 'histogram', 'catch'),
-    'sites': ('apply', 'summary', 'reweight', 'mc_error', 'sensitivity', 'dependence', 'histogram', 'arrival', 'peak',
-              'excursion', 'core_range', 'catch', 'neighbourhood', 'proximity', 'information', 'patches', 'pathways',
+    'projection': ('apply', 'summary', 'reweight', 'reweight_histogram', 'mc_error', 'sensitivity', 'dependence', 'histogram', 'catch'),
+    'sites': ('apply', 'summary', 'reweight', 'reweight_histogram', 'reweight_arrival', 'mc_error', 'sensitivity',
+              'dependence', 'histogram', 'arrival', 'peak', 'excursion', 'core_range', 'catch', 'neighbourhood', 'proximity', 'information', 'patches', 'pathways',
               'modes'),
     'compare': ('apply', 'contrast'),
 }
@@ -2535,6 +2543,8 @@ FEED = {
     'excursion': _add_length,
     'core_range': _add_length,
     'reweight': _add_reweighted,
+    'reweight_histogram': lambda acc, fs, m: acc.add(m.lam, m.length),     # after 'reweight', which sets m.lam
+    'reweight_arrival': lambda acc, fs, m: acc.add(m.lam, m.length),
     'catch': _add_catch,
     'neighbourhood': _add_catch,
     'proximity': _add_catch,
@@ -2573,6 +2583,28 @@ def _build_reweight(fs, q):
         if fs._kind == 'days':
             fs._rw_feed = _ReweightFeed(q.rw_plan, fs._chain)
     return fs.reweight
+
+
+def _reweight_maps(q):
+    '''the 'maps' option of the checked reweight=, () where there is none'''
+    plan = getattr(q, 'rw_plan', None)
+    return plan.get('maps', ()) if plan is not None else ()
+
+
+def _build_reweight_histogram(fs, q):
+    '''the ReweightedHistogram on the edges of the request's quantiles=; None, and nothing built, without
+    maps=('quantiles', ...)'''
+    if 'quantiles' in _reweight_maps(q):
+        names = q.rw_plan['names']
+        return fs._over(ReweightedHistogram, (names, fs._days, q.bins, q.edges), (names, q.bins, q.edges))
+
+
+def _build_reweight_arrival(fs, q):
+    '''the ReweightedArrival on the thresholds of the request's arrival=; None, and nothing built, without
+    maps=(..., 'arrival')'''
+    if 'arrival' in _reweight_maps(q):
+        names = q.rw_plan['names']
+        return fs._over(ReweightedArrival, (names, q.a_thr, fs._days), (names, q.a_thr))
 
 
 def _build_catch(fs, q):
@@ -2681,6 +2713,8 @@ BUILD = {
     'excursion': lambda fs, q: q.ex_thr and fs._over(ExcursionMaps, (q.ex_thr, fs._days), (q.ex_thr,)),
     'core_range': lambda fs, q: q.cr_frac and fs._over(RangeMaps, (q.cr_frac, fs._days), (q.cr_frac,)),
     'reweight': _build_reweight,
+    'reweight_histogram': _build_reweight_histogram,
+    'reweight_arrival': _build_reweight_arrival,
     'catch': _build_catch,
     'neighbourhood': _build_neighbourhood,
     'proximity': _build_proximity,
@@ -2819,6 +2853,8 @@ class ProjectedMaps(_FieldSet):
     take the output day.  `excursion`: the ExcursionMaps.for_projection of a release plan's outputs (None unless
     asked for), whose maps take the output day.  `reweight`: the
     ReweightedSummary.for_projection (None unless asked for), which takes the scenario's name and the output index.
+    `reweight_histogram` / `reweight_arrival`: the ReweightedHistogram.for_projection and, of a release plan, the
+    ReweightedArrival.for_projection (None unless reweight's maps option asks for them).
     `catch`: the CatchPosterior over the outputs (None unless asked for), whose traps name an output label.
     `neighbourhood`: the NeighbourhoodPosterior over a release plan's outputs (None unless asked for), whose windows
     name an output day.  `proximity`: the ProximityPosterior over a release plan's outputs (None unless asked for),
@@ -2834,9 +2870,10 @@ class ProjectedMaps(_FieldSet):
     def __init__(self, weights, in_days, labels, summary, histogram=None, arrival=None, plan=None,
                  sensitivity=None, mc_error=None, peak=None, excursion=None, reweight=None, catch=None,
                  information=None, core_range=None, patches=None, neighbourhood=None, dependence=None,
-                 proximity=None):
+                 proximity=None, reweight_histogram=None, reweight_arrival=None):
         super().__init__(summary=summary, histogram=histogram, arrival=arrival, sensitivity=sensitivity,
-                         dependence=dependence,
+                         dependence=dependence, reweight_histogram=reweight_histogram,
+                         reweight_arrival=reweight_arrival,
                          mc_error=mc_error, peak=peak, excursion=excursion, reweight=reweight, catch=catch,
                          information=information, core_range=core_range, patches=patches,
                          neighbourhood=neighbourhood, proximity=proximity)
@@ -4134,6 +4171,7 @@ MAX_REWEIGHT_SCENARIOS = 4
 MAX_REWEIGHT_SLOTS = 32    # ps_wsum: the slots of one launch's descriptors
 PROBE_KINDS = ('count', 'none', 'found')
 DEFAULT_MIN_ESS = 50.0
+REWEIGHT_MAPS = ('quantiles', 'arrival')      # the 'maps' option of reweight=: what else is reweighted
 
 
 def check_scenarios(scenarios):
@@ -4271,10 +4309,28 @@ def reweight_diagnostics(row_log_weights):
             'log_mean_weight': float(mx + np.log(s1) - np.log(rows))}
 
 
+def check_reweight_maps(maps):
+    '''the 'maps' option of reweight=: a subset of REWEIGHT_MAPS ('quantiles', 'arrival') as a tuple in that order,
+    () for None; ValueError otherwise'''
+    if maps is None:
+        return ()
+    if isinstance(maps, str):
+        raise ValueError("reweight: maps takes a list of names out of %r, got %r" % (REWEIGHT_MAPS, maps))
+    try:
+        asked = [str(m) for m in maps]
+    except TypeError:
+        raise ValueError("reweight: maps takes a list of names out of %r, got %r" % (REWEIGHT_MAPS, maps))
+    bad = [m for m in asked if m not in REWEIGHT_MAPS]
+    if bad or len(set(asked)) != len(asked):
+        raise ValueError('reweight: maps %r is not a subset of %r' % (asked, REWEIGHT_MAPS))
+    return tuple(m for m in REWEIGHT_MAPS if m in asked)
+
+
 def check_reweight(reweight, rad_dist=None, rad_res=None, ndays=None):
     '''the reweight= argument of posterior_predictive -> dict(names, kinds, probes, given, log_weights, min_ess):
     {name: dict(probes=[...]) or dict(log_weights=[one 1-D array per chain]), ...} with 1..4 names, and
-    optionally 'options': dict(min_ess=50).  Per scenario `kinds` is 'probes' or 'log_weights', `probes` the
+    optionally 'options': dict(min_ess=50, maps=('quantiles', 'arrival')); with maps the plan also carries `maps`
+    (check_reweight_maps).  Per scenario `kinds` is 'probes' or 'log_weights', `probes` the
     checked probes (check_probes) or None, `given` the probes as given, `log_weights` the float64 arrays or None
     (every entry finite or -inf).  ValueError otherwise.'''
     if not isinstance(reweight, dict):
@@ -4282,13 +4338,16 @@ def check_reweight(reweight, rad_dist=None, rad_res=None, ndays=None):
                          % (reweight,))
     specs = dict(reweight)
     options = specs.pop('options', None) or {}
-    if not isinstance(options, dict) or set(options) - {'min_ess'}:
-        raise ValueError("reweight: 'options' takes dict(min_ess=...), got %r" % (options,))
+    if not isinstance(options, dict) or set(options) - {'min_ess', 'maps'}:
+        raise ValueError("reweight: 'options' takes dict(min_ess=..., maps=...), got %r" % (options,))
     min_ess = float(options.get('min_ess', DEFAULT_MIN_ESS))
     if not (np.isfinite(min_ess) and min_ess >= 0):
         raise ValueError('reweight: min_ess %r is not finite and >= 0' % (options.get('min_ess'),))
+    maps = check_reweight_maps(options.get('maps'))
     names = check_scenarios(list(specs))
     out = {'names': names, 'kinds': [], 'probes': [], 'given': [], 'log_weights': [], 'min_ess': min_ess}
+    if maps:                          # without the option the plan is what it was
+        out['maps'] = maps
     for name in names:
         spec = specs[name]
         if not isinstance(spec, dict) or len(set(spec) & {'probes', 'log_weights'}) != 1 \
@@ -4334,6 +4393,55 @@ def check_reweight_rows(plan, chain_rows):
             if a.size != n:
                 raise ValueError('reweight[%r]: %d log-weights for chain %d, which has %d rows after burn and thin'
                                  % (name, a.size, c, n))
+
+
+def reweight_scale(scenarios, refs, log_weights, weight=1):
+    '''(r, omega, ref) per scenario for a member with these log-weights (one per name of `scenarios`, or a dict by
+    name) and run length `weight`, `refs` the largest log-weight of every scenario so far -- the rule every
+    reweighted accumulator shares (ReweightedSummary, ReweightedHistogram, ReweightedArrival):
+    lambda = -inf: omega 0;  an empty scenario: ref = lambda, r 1, omega = weight;  lambda > ref:
+    r = exp(ref - lambda), ref = lambda, omega = weight;  else r 1, omega = weight * exp(lambda - ref), which
+    may underflow to 0 (the member is then skipped).  ValueError for NaN, +inf or a wrong number.'''
+    import math
+    if isinstance(log_weights, dict):
+        if set(log_weights) != set(scenarios):
+            raise ValueError('log-weights for %r, the scenarios are %r' % (sorted(log_weights), scenarios))
+        log_weights = [log_weights[n] for n in scenarios]
+    try:
+        lam = [float(v) for v in log_weights]
+    except TypeError:
+        raise ValueError('log_weights must be one number per scenario, got %r' % (log_weights,))
+    if len(lam) != len(scenarios):
+        raise ValueError('%d log-weights given, the handle has %d scenarios' % (len(lam), len(scenarios)))
+    w = float(weight)
+    if not (math.isfinite(w) and w > 0):
+        raise ValueError('weight must be finite and > 0')
+    r, om, ref = [], [], []
+    for lj, rj in zip(lam, refs):
+        if math.isnan(lj) or lj == math.inf:
+            raise ValueError('log-weight %r is NaN or +inf' % (lj,))
+        if lj == -math.inf:
+            r.append(1.0), om.append(0.0), ref.append(rj)
+        elif rj == -math.inf:
+            r.append(1.0), om.append(w), ref.append(lj)
+        elif lj > rj:
+            r.append(math.exp(rj - lj)), om.append(w), ref.append(lj)
+        else:
+            r.append(1.0), om.append(w * math.exp(lj - rj)), ref.append(rj)
+    return r, om, ref
+
+
+def reweight_merge_scale(ref_a, ref_b):
+    '''(ra, rb, ref) per scenario that bring two reweighted accumulators to the larger of their references:
+    L = max(ref_a, ref_b), ra = exp(ref_a - L), rb = exp(ref_b - L); 1 where both are empty'''
+    import math
+    ra, rb, ref = [], [], []
+    for a, b in zip(ref_a, ref_b):
+        top = max(a, b)
+        ref.append(top)
+        ra.append(1.0 if top == -math.inf else math.exp(a - top))
+        rb.append(1.0 if top == -math.inf else math.exp(b - top))
+    return ra, rb, ref
 
 
 class ReweightedSummary(_Handle):
@@ -4382,37 +4490,8 @@ class ReweightedSummary(_Handle):
         return self.scenarios.index(name)
 
     def scale(self, log_weights, weight=1):
-        '''(r, omega, ref) per scenario that add() would pass for these log-weights, without adding:
-        lambda = -inf: omega 0;  an empty scenario: ref = lambda, r 1, omega = weight;  lambda > ref:
-        r = exp(ref - lambda), ref = lambda, omega = weight;  else r 1, omega = weight * exp(lambda - ref), which
-        may underflow to 0 (the member is then skipped).  ValueError for NaN, +inf or a wrong number.'''
-        import math
-        if isinstance(log_weights, dict):
-            if set(log_weights) != set(self.scenarios):
-                raise ValueError('log-weights for %r, the scenarios are %r' % (sorted(log_weights), self.scenarios))
-            log_weights = [log_weights[n] for n in self.scenarios]
-        try:
-            lam = [float(v) for v in log_weights]
-        except TypeError:
-            raise ValueError('log_weights must be one number per scenario, got %r' % (log_weights,))
-        if len(lam) != len(self.scenarios):
-            raise ValueError('%d log-weights given, the handle has %d scenarios' % (len(lam), len(self.scenarios)))
-        w = float(weight)
-        if not (math.isfinite(w) and w > 0):
-            raise ValueError('weight must be finite and > 0')
-        r, om, ref = [], [], []
-        for lj, rj in zip(lam, self.ref):
-            if math.isnan(lj) or lj == math.inf:
-                raise ValueError('log-weight %r is NaN or +inf' % (lj,))
-            if lj == -math.inf:
-                r.append(1.0), om.append(0.0), ref.append(rj)
-            elif rj == -math.inf:
-                r.append(1.0), om.append(w), ref.append(lj)
-            elif lj > rj:
-                r.append(math.exp(rj - lj)), om.append(w), ref.append(lj)
-            else:
-                r.append(1.0), om.append(w * math.exp(lj - rj)), ref.append(rj)
-        return r, om, ref
+        '''(r, omega, ref) per scenario that add() would pass for these log-weights, without adding (reweight_scale)'''
+        return reweight_scale(self.scenarios, self.ref, log_weights, weight)
 
     def add(self, log_weights, weight=1):
         '''Accumulate the last evaluation of the model (on a projection, a plan or a peak: its last apply) with
@@ -4497,6 +4576,288 @@ class ReweightedSummary(_Handle):
     def profile(self, enable=None):
         '''HIP-event time of the add launches: (total ms, launches); enable switches it'''
         return self._profile(enable)
+
+
+
+class _ReweightedCounts(_Handle):
+    '''What ReweightedHistogram and ReweightedArrival share: the scenarios, the log scale of ReweightedSummary
+    (reweight_scale, reweight_merge_scale; per scenario `ref`, the largest log-weight so far), the add, the merge
+    and the host-side counters.  Fed alongside a ReweightedSummary with the same log-weights they report the same
+    ref, W, members and skipped, bit for bit.'''
+    _prof_pairs = 3
+
+    def _scenarios(self, scenarios):
+        import math
+        self.scenarios = check_scenarios(scenarios)
+        self.ref = [-math.inf] * len(self.scenarios)
+
+    def _slots(self):
+        n = len(self._slot)
+        if not 1 <= n <= MAX_REWEIGHT_SLOTS:
+            raise ValueError('%d slots; 1..%d fit one handle' % (n, MAX_REWEIGHT_SLOTS))
+        return n
+
+    def _j(self, name):
+        if name not in self.scenarios:
+            raise ValueError('scenario %r is not one of %r' % (name, self.scenarios))
+        return self.scenarios.index(name)
+
+    def scale(self, log_weights, weight=1):
+        '''(r, omega, ref) per scenario that add() would pass for these log-weights, without adding (reweight_scale)'''
+        return reweight_scale(self.scenarios, self.ref, log_weights, weight)
+
+    def add(self, log_weights, weight=1):
+        '''Accumulate the last evaluation of the model (on a projection or a plan: its last apply) with weight `weight`
+        (the run length) times exp(log_weights[j]) in scenario j; enqueued, no host synchronisation.  A refused add
+        changes nothing.'''
+        r, om, ref = self.scale(log_weights, weight)
+        self._read('add', self._proj, len(self.scenarios), L.p_f64(L.f64(r)), L.p_f64(L.f64(om)))
+        # a member whose weight underflowed is skipped and moves no reference
+        self.ref = [b if o > 0.0 else a for a, b, o in zip(self.ref, ref, om)]
+        return r, om
+
+    def _check_merge(self, other):
+        if list(other.days) != self.days or other._slot != self._slot or other.scenarios != self.scenarios:
+            raise ValueError('%ss over different days or scenarios' % self._noun)
+
+    def merge(self, other):
+        '''self += other (same device, domain, scenarios and days), both brought to the larger of the two references
+        per scenario (reweight_merge_scale); other is unchanged'''
+        self._check_merge(other)
+        ra, rb, ref = reweight_merge_scale(self.ref, other.ref)
+        self._call('merge', other._h, L.p_f64(L.f64(ra)), L.p_f64(L.f64(rb)))
+        self.ref = ref
+
+    def reset(self):
+        import math
+        self._call('reset')
+        self.ref = [-math.inf] * len(self.scenarios)
+
+    def _info(self):
+        n = len(self.scenarios)
+        w, m, s = np.zeros(n), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+        self._call('info', L.p_f64(w), L.p_i64(m), L.p_i64(s))
+        return w, m, s
+
+    def total_weight(self, name):
+        '''W of the scenario on its own scale exp(ref)'''
+        return float(self._info()[0][self._j(name)])
+
+    def log_total_weight(self, name):
+        '''ref + log W: the log of the scenario's total weight (-inf while it is empty)'''
+        import math
+        j = self._j(name)
+        W = float(self._info()[0][j])
+        return -math.inf if W == 0.0 else self.ref[j] + math.log(W)
+
+    def members(self, name):
+        return int(self._info()[1][self._j(name)])
+
+    def skipped(self, name):
+        return int(self._info()[2][self._j(name)])
+
+    def profile(self, enable=None):
+        '''HIP-event time of the add, read and rescale launches: (add ms, adds, read ms, reads, rescale ms, rescales);
+        enable switches it'''
+        return self._profile(enable)
+
+
+class ReweightedHistogram(_ReweightedCounts):
+    '''The histograms of a SpreadHistogram under up to 4 reweighting scenarios at once, on the device (ps_whist_*,
+    csrc/ps_whist.hip): member m counts with the real weight weight_m exp(lambda_m) in the bin of its value, by the
+    log scale of ReweightedSummary.  scenarios: 1..4 distinct names; days (at most 32), bins and edges as
+    SpreadHistogram.  From them the reweighted quantile (median, credible band) of every cell and the exceedance at
+    any edge, chosen after the run.  A scenario whose log-weights are all 0 holds the counts of a SpreadHistogram fed
+    alongside, and its quantiles and exceedances are that one's bit for bit.  With real weights these are
+    floating-point sums: the same calls give the same bits, another order of adds or merges moves a plane within
+    the rounding of its sums.'''
+    _prefix, _noun = 'ps_whist', 'reweighted histogram'
+
+    def __init__(self, pop_model, scenarios, days=None, bins=DEFAULT_BINS, edges=None):
+        self._setup(pop_model, scenarios, _model_days(pop_model, days), bins, edges, None)
+
+    @classmethod
+    def for_projection(cls, source, scenarios, bins=DEFAULT_BINS, edges=None):
+        '''Reweighted histograms of the outputs of `source` (a Projection or a ReleaseSites), one slot per output:
+        `add(log_weights, weight)` accumulates the outputs of its last `apply()`, and the accessors take the output
+        index where the day-based histograms take a day.'''
+        self = cls.__new__(cls)
+        self._setup(source.pm, scenarios, list(range(source.nout)), bins, edges, source)
+        return self
+
+    def _setup(self, pop_model, scenarios, days, bins, edges, projection):
+        self._edges = bin_edges(bins, edges)
+        self.bins = None if edges is not None else tuple(float(b) for b in bins)
+        self._scenarios(scenarios)
+        self._set_source(projection, days, projection and projection.live)
+        n = self._slots()
+        self._attach(pop_model)
+        J, nedge = len(self.scenarios), self._edges.size
+        self.nbytes = J * n * nedge * self.pitch * 8 + n * self.pitch * 4       # the planes + the range words
+        try:
+            self._create(J, n, nedge, L.p_f64(self._edges))
+        except L.HipError as e:
+            if e.code != L.PS_ERR_OOM:
+                raise
+            raise ValueError('reweighted histogram: %d scenarios x %d slots x %d edges x %d cells x 8 B = %.3g GB do '
+                             'not fit the free device memory; fewer days, scenarios or bins per decade cut it (%s)'
+                             % (J, n, nedge, self.pitch, self.nbytes * 1e-9, e))
+
+    @property
+    def edges(self):
+        return self._edges.copy()
+
+    def _level(self, p):
+        if not 0.0 < float(p) <= 1.0:
+            raise ValueError('quantile level %r is not in (0, 1]' % (p,))
+        return float(p)
+
+    def _quantile(self, name, day, p):
+        '''(value, lower, upper, bin) maps of one scenario and day'''
+        j, s, p = self._j(name), self._slot_of(day), self._level(p)
+        shape = (self.N, self.N)
+        if s is None:                    # an output without weight: every member's value is 0, bin 0 = [0, e_0)
+            return np.zeros(shape), np.zeros(shape), np.full(shape, self._edges[0]), np.zeros(shape, dtype=np.int32)
+        v, lo, hi = np.empty(shape), np.empty(shape), np.empty(shape)
+        b = np.empty(shape, dtype=np.int32)
+        self._call('quantile', j, s, p, L.p_f64(v), L.p_f64(lo), L.p_f64(hi), L.p_i32(b))
+        return v, lo, hi, b
+
+    def quantile(self, name, day, p):
+        '''(value, lower, upper): N x N maps of the scenario's weighted lower quantile at level p -- the point value,
+        log-interpolated inside its bin, and the bin [lower, upper) that holds it, as SpreadHistogram's'''
+        return self._quantile(name, day, p)[:3]
+
+    def quantile_bin(self, name, day, p):
+        '''N x N int32: b*, the smallest bin whose cumulated weight reaches p W'''
+        return self._quantile(name, day, p)[3]
+
+    def exceed(self, name, day, k):
+        '''P(population >= edges[k]) per cell under the scenario, at any edge'''
+        j, k, s = self._j(name), self._index(k, self._edges.size, 'edge'), self._slot_of(day)
+        out = np.zeros((self.N, self.N), dtype=np.float64)
+        if s is not None:
+            self._call('exceed', j, s, k, L.p_f64(out))
+        return out
+
+    def plane(self, name, day, b):
+        '''N x N float64: the raw weight of bin b (1 .. B + 1) on the scenario's own scale exp(ref)'''
+        j, s = self._j(name), self._slot_of(day)
+        if not 1 <= int(b) <= self._edges.size:
+            raise ValueError('bin %r of 1..%d' % (b, self._edges.size))
+        out = np.zeros((self.N, self.N), dtype=np.float64)
+        if s is not None:
+            self._call('fetch', j, s, int(b), L.p_f64(out))
+        return out
+
+
+class ReweightedArrival(_ReweightedCounts):
+    '''The arrival counts of an ArrivalMaps under up to 4 reweighting scenarios at once, on the device (ps_warr_*,
+    csrc/ps_warr.hip): when do they reach each cell, given the new observations?  scenarios: 1..4 distinct names;
+    thresholds and days as ArrivalMaps.  A scenario whose log-weights are all 0 holds the counts of an ArrivalMaps
+    fed alongside, and its probabilities and quantile days are that one's bit for bit.  The class keeps per scenario
+    the (log-weight, run length) of every member in add order, for the reached-area curve, which needs no device
+    work of its own (`reached_area`).  Floating-point sums as ReweightedHistogram's.'''
+    _prefix, _noun = 'ps_warr', 'reweighted arrival maps'
+
+    def __init__(self, pop_model, scenarios, thresholds, days=None):
+        self._setup(pop_model, scenarios, thresholds, None,
+                    check_arrival_days(range(len(pop_model.days)) if days is None else days))
+
+    @classmethod
+    def for_projection(cls, source, scenarios, thresholds):
+        '''Reweighted arrival maps of the outputs of `source` (a ReleaseSites or a Projection), the slots its outputs
+        that carry weight in ascending order; `days` holds the output labels, as ArrivalMaps.for_projection's.'''
+        self = cls.__new__(cls)
+        self._setup(source.pm, scenarios, thresholds, source, check_arrival_days(_output_labels(source)))
+        return self
+
+    def _setup(self, pop_model, scenarios, thresholds, projection, days):
+        self.thresholds = check_arrival_thresholds(thresholds)
+        self._scenarios(scenarios)
+        self._set_source(projection, days)
+        n = self._slots()
+        self._attach(pop_model)
+        self._member_lw = [[] for _ in self.scenarios]
+        self.nbytes = len(self.scenarios) * len(self.thresholds) * n * self.pitch * 8      # the planes
+        self._create(len(self.scenarios), n, len(self.thresholds), L.p_f64(L.f64(self.thresholds)))
+
+    def add(self, log_weights, weight=1):
+        scaled = super().add(log_weights, weight)      # a refused add raises here and records nothing
+        lam = [log_weights[n] for n in self.scenarios] if isinstance(log_weights, dict) else list(log_weights)
+        for rows, lj in zip(self._member_lw, lam):
+            rows.append((float(lj), float(weight)))
+        return scaled
+
+    add.__doc__ = _ReweightedCounts.add.__doc__
+
+    def merge(self, other):
+        '''self += other as ReweightedHistogram.merge; other's members follow self's'''
+        super().merge(other)
+        for rows, more in zip(self._member_lw, other._member_lw):
+            rows.extend(more)
+
+    def reset(self):
+        super().reset()
+        self._member_lw = [[] for _ in self.scenarios]
+
+    def member_log_weights(self, name):
+        '''[(log-weight, run length), ...] of every member of the scenario, in add order (the skipped ones too)'''
+        return list(self._member_lw[self._j(name)])
+
+    def plane(self, name, k, day):
+        '''N x N float64: the raw weight of the members whose arrival day at t_k is `day`, on the scale exp(ref)'''
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        self._call('fetch', self._j(name), self._k(k), self._slot_of(day), L.p_f64(out))
+        return out
+
+    def prob_by(self, name, k, day):
+        '''[N, N] float64: P(arrived at t_k by `day`) under the scenario = min(C / W, 1), C the weight of the
+        arrivals up to `day`'''
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        self._call('prob', self._j(name), self._k(k), self._slot_of(day), L.p_f64(out))
+        return out
+
+    def quantile(self, name, k, p):
+        '''[N, N] int32 map of model days: the first day whose C reaches p W under the scenario, -1 where even the
+        last day falls short'''
+        if not 0.0 < float(p) <= 1.0:
+            raise ValueError('quantile level %r is not in (0, 1]' % (p,))
+        slot = np.empty((self.N, self.N), dtype=np.int32)
+        self._call('quantile', self._j(name), self._k(k), float(p), L.p_i32(slot))
+        day = np.append(np.asarray(self.days, dtype=np.int32), np.int32(-1))
+        return day[slot]          # slot -1 picks the appended -1
+
+    def member_weights(self, name):
+        '''float64 [members]: n exp(lambda - ref) of every member of the scenario in add order, 0 at lambda = -inf'''
+        import math
+        j = self._j(name)
+        ref = self.ref[j]
+        return np.array([0.0 if l == -math.inf else n * math.exp(l - ref) for l, n in self._member_lw[j]],
+                        dtype=np.float64)
+
+    def reached_area(self, name, k, arrival_maps, levels=(0.05, 0.5, 0.95)):
+        '''The reached-area curve of ArrivalMaps.reached_area under the scenario: the members' reached-cell rows of
+        `arrival_maps` (the ArrivalMaps fed alongside, same add order) weighted by n exp(lambda - ref) with
+        weighted_lower_quantile.  ValueError where the rows and the members of this handle differ in number.'''
+        levels = check_levels(levels)
+        w = self.member_weights(name)
+        cells, _w = arrival_maps.reached(self._k(k))
+        if cells.shape[0] != w.size:
+            raise ValueError('%d reached-cell rows, the reweighted arrival maps hold %d members' % (cells.shape[0], w.size))
+        if list(arrival_maps.days) != list(self.days):
+            raise ValueError('arrival maps over different days')
+        W = float(w.sum())
+        if not W > 0.0:
+            raise ValueError('nothing accumulated')
+        out = []
+        for s, d in enumerate(self.days):
+            n = cells[:, s]
+            mean = float((n * w).sum()) / W * self.cell_area
+            q = [float(weighted_lower_quantile(n, w, p)) * self.cell_area for p in levels]
+            out.append({'day': d, 'mean': mean, 'quantiles': q, 'radius_mean': float(np.sqrt(mean / np.pi)),
+                        'radius_quantiles': [float(np.sqrt(a / np.pi)) for a in q]})
+        return out
 
 
 
@@ -6701,6 +7062,36 @@ def save_reweight(outfile, rw, keys, labels):
     save_maps(outfile, maps, {'scenarios': np.array(rw.scenarios), 'labels': np.array(labels)})
 
 
+def save_reweight_quantiles(outfile, rh, keys, labels, levels):
+    '''outfile.npz of one ReweightedHistogram through save_maps (keys: its days or output indices, labels: theirs in
+    the file): per scenario index j, label and level the CSR triplets `s{j}_{label}_q{tag}_*` of the reweighted
+    quantile point map (quantile_tag), as the main file's `{label}_q{tag}_*`; `scenarios`, `labels`, `levels` and
+    the edge table `edges`'''
+    maps = []
+    for j, name in enumerate(rh.scenarios):
+        for k, label in zip(keys, labels):
+            maps.append(('s%d_%s' % (j, label), [('_' + quantile_tag(p), rh.quantile(name, k, p)[0]) for p in levels]))
+    save_maps(outfile, maps, {'scenarios': np.array(rh.scenarios), 'labels': np.array(labels),
+                              'levels': np.array(levels, dtype=np.float64), 'edges': rh.edges})
+
+
+def save_reweight_arrival(outfile, ra, keys, labels, levels):
+    '''outfile.npz of one ReweightedArrival through save_maps (keys: its days, labels: theirs in the file): per
+    scenario index j, label and threshold k the CSR triplets `s{j}_{label}_parr{k}_*` (P(arrived at t_k by that day)
+    under the scenario) and per level the dense int16 model-day map `s{j}_arrival{k}_q{tag}` (-1: not within the
+    window), as the main file's `{label}_parr{k}_*` and `arrival{k}_q{tag}`; `scenarios`, `labels`, `thresholds`'''
+    maps, extra = [], {'scenarios': np.array(ra.scenarios), 'labels': np.array(labels),
+                       'thresholds': np.array(ra.thresholds, dtype=np.float64)}
+    nk = len(ra.thresholds)
+    for j, name in enumerate(ra.scenarios):
+        for d, label in zip(keys, labels):
+            maps.append(('s%d_%s' % (j, label), [('_parr%d' % k, ra.prob_by(name, k, d)) for k in range(nk)]))
+        for k in range(nk):
+            for p in levels:
+                extra['s%d_arrival%d_%s' % (j, k, quantile_tag(p))] = ra.quantile(name, k, p).astype(np.int16)
+    save_maps(outfile, maps, extra)
+
+
 def save_peak(outfile, peak, quantiles=()):
     '''outfile.npz of one PeakPosterior through save_maps: under the label `peak` the CSR triplets `peak_*` of the
     posterior mean of the peak value, `peak_sd_*`, `peak_pexc{k}_*` (P(peak >= t_k)) and, with a histogram,
@@ -6859,7 +7250,10 @@ class PredictiveResult():
     over the summary's days and thresholds, and `reweight_info` = dict(names, probes -- as given, None for a
     scenario of row log-weights --, min_ess, diagnostics: {name: reweight_diagnostics + members, skipped,
     log_total_weight}), both None where not asked for (the projections and the plan then carry a `reweight` of
-    their own); `catch`: the CatchPosterior of the traps over the model's day fields, None where not asked for
+    their own); `reweight_histogram` / `reweight_arrival`: the ReweightedHistogram and the ReweightedArrival over
+    the summary's days, on the edges of quantiles= and the thresholds of arrival=, None unless reweight's
+    options['maps'] names 'quantiles' / 'arrival' (the projections then carry a `reweight_histogram`, the plan both);
+    `catch`: the CatchPosterior of the traps over the model's day fields, None where not asked for
     (the emergence projection and the plan then carry a `catch` of their own where asked for); `information`: the
     InformationPosterior of the described traps over the model's day fields, None where not asked for (the plan then
     carries an `information` of its own); `core_range`: the RangeMaps over the summary's days and
@@ -6886,7 +7280,10 @@ class PredictiveResult():
                  peak=None, excursion=None, excursion_levels=None, reweight=None, reweight_info=None, catch=None,
                  information=None, core_range=None, core_range_levels=None, patches=None, patch_levels=None,
                  representative=None, representative_days=None, representative_chains=None, neighbourhood=None,
-                 modes=None, dependence=None, pathways=None, pathway_levels=None, proximity=None, origin=None):
+                 modes=None, dependence=None, pathways=None, pathway_levels=None, proximity=None, origin=None,
+                 reweight_histogram=None, reweight_arrival=None):
+        self.reweight_histogram = reweight_histogram
+        self.reweight_arrival = reweight_arrival
         self.origin = origin
         self.proximity = proximity
         self.pathways = pathways
@@ -6975,6 +7372,12 @@ class PredictiveResult():
         is > 0), null where there are none; `predictive.mc_error.NAME` the same for a projection or a plan.
         Peak maps go into outfile_peak.npz (save_peak; those of a release plan into outfile_sites_peak.npz), their
         block under `predictive.peak` (`predictive.sites.peak`) of the json.
+        Reweighted quantile and arrival maps (reweight's maps option) go into outfile_reweight_quantiles.npz
+        (save_reweight_quantiles: `s{j}_{label}_q{tag}_*`) and outfile_reweight_arrival.npz (save_reweight_arrival:
+        `s{j}_{label}_parr{k}_*`, dense `s{j}_arrival{k}_q{tag}`), those of a projection or a plan into
+        outfile_NAME_reweight_quantiles.npz / outfile_NAME_reweight_arrival.npz; `predictive.reweight` of the json
+        then carries `maps` and, with arrival maps, per scenario the reached-area curve `reached_area`
+        (`predictive.sites.reweight.reached_area` for a plan).
         Excursion maps go into outfile_excur.npz (save_excursion; those of a release plan into
         outfile_sites_excur.npz), their block under `predictive.excursion` (`predictive.sites.excursion`).
         Catch-probability maps go into outfile_catch.npz (save_catch; those of the emergence projection and of a
@@ -7150,6 +7553,24 @@ class PredictiveResult():
                 if pr is not None and pr.reweight is not None:
                     save_reweight('%s_%s_reweight' % (outfile, name), pr.reweight, list(range(len(pr.labels))),
                                   pr.labels)
+            # the maps option: outfile_reweight_quantiles.npz / outfile_reweight_arrival.npz, those of a projection
+            # or a plan outfile_NAME_reweight_*.npz; per scenario the reached-area curve into the json
+            for name, fs, keys, flabels in [('', self, s.days, labels)] + [
+                    (n + '_', pr, list(range(len(pr.labels))), pr.labels) for n, pr in (
+                        ('emergence', self.emergence), ('exposure', self.exposure), ('sites', self.sites))
+                    if pr is not None]:
+                rh, ra = fs.reweight_histogram, fs.reweight_arrival
+                if rh is not None:
+                    save_reweight_quantiles('%s_%sreweight_quantiles' % (outfile, name), rh, keys, flabels,
+                                            list(self.quantiles or ()))
+                if ra is not None:
+                    ra_levels = list(self.arrival_levels or ())
+                    save_reweight_arrival('%s_%sreweight_arrival' % (outfile, name), ra, ra.days,
+                                          flabels if not name else ra.days, ra_levels)     # a plan's days are its labels
+                    block = meta['predictive']['reweight'] if not name else \
+                        meta['predictive'][name[:-1]].setdefault('reweight', {})
+                    block['reached_area'] = {n: [ra.reached_area(n, k, fs.arrival, ra_levels)
+                                                 for k in range(len(ra.thresholds))] for n in ra.scenarios}
         area = getattr(self, 'cell_area', None)
         for name, cp in [('', self.catch)] + [(n + '_', pr.catch) for n, pr in (
                 ('emergence', self.emergence), ('sites', self.sites)) if pr is not None]:
@@ -7372,6 +7793,9 @@ def _check_request(q):
         q.a_levels = check_levels(q.arrival_levels)
         if days is not None:
             check_arrival_days(days)
+    for what, have in (('quantiles', q.levels), ('arrival', q.a_thr)):
+        if what in _reweight_maps(q) and not have:
+            raise ValueError("reweight: maps=%r reweights the maps of %s=, and there is none" % (what, what))
     wanted = [(name, arg, plan) for name, arg, plan in (('emergence', q.emergence, emergence_plan),
                                                         ('exposure', q.exposure, exposure_plan)) if arg is not None]
     q.plans = [(name,) + plan(arg) for name, arg, plan in wanted]      # bad projection arguments
@@ -7580,8 +8004,14 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         any evaluation. Each chain then also fills one ReweightedSummary over the summary's days (at most 32) and
         thresholds (finite, > 0, strictly increasing), fed right after the summary with the run's length, merged
         in chain order into `reweight`; every emergence=, exposure= and sites= asked for gets a
-        ReweightedSummary.for_projection of its own, fed after its summary. Histogram, arrival, peak, excursion,
-        contrast and Monte Carlo error get none. `reweight_info` carries per scenario the diagnostics of the row
+        ReweightedSummary.for_projection of its own, fed after its summary. reweight['options'] = dict(maps=
+        ('quantiles', 'arrival')) (a subset of the two; 'quantiles' needs quantiles=, 'arrival' needs arrival=)
+        also reweights the quantile and the arrival maps: each chain then fills a ReweightedHistogram on the edges of
+        quantiles= and a ReweightedArrival on the thresholds of arrival=, fed the same log-weights right after the
+        ReweightedSummary, merged in chain order into `reweight_histogram` / `reweight_arrival`; the projections get
+        a ReweightedHistogram.for_projection, the plan both. Without `maps` nothing of this is built or called.
+        Peak, excursion, contrast, range, patch, pathway and Monte Carlo error maps and the histograms inside the
+        neighbourhood and proximity posteriors get none. `reweight_info` carries per scenario the diagnostics of the row
         weights (reweight_diagnostics); a UserWarning where ess < min_ess (reweight['options'] = dict(min_ess=50))
         -- importance reweighting degrades as the new data disagree with the posterior -- and a ValueError naming
         a scenario that is left without weight. Without reweight= no call is added and `reweight` is None.
@@ -7807,6 +8237,8 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
             diag[name] = d
         rw_info = {'names': list(rw_plan['names']), 'probes': list(rw_plan['given']), 'min_ess': rw_plan['min_ess'],
                    'diagnostics': diag}
+        if rw_plan.get('maps'):
+            rw_info['maps'] = list(rw_plan['maps'])
         empty = [n for n in rw_plan['names'] if diag[n]['members'] == 0]
         if empty:
             for fs in merged.values():
@@ -7849,7 +8281,8 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         representative=day.representative, representative_days=q.rp_plan['days'] if q.rp_plan else None,
         representative_chains=[p[0][:, p[2]] for p in prepared] if q.rp_plan else None,
         neighbourhood=day.neighbourhood, modes=day.modes, dependence=day.dependence, pathways=day.pathways,
-        pathway_levels=q.pw_levels if q.pw_thr else None, proximity=day.proximity, origin=day.origin)
+        pathway_levels=q.pw_levels if q.pw_thr else None, proximity=day.proximity, origin=day.origin,
+        reweight_histogram=day.reweight_histogram, reweight_arrival=day.reweight_arrival)
     if day.information is not None:   # the stated convention: past cap / 2 the ensemble bounds the map
         warn_information(day.information)
         if 'sites' in merged:

@@ -42,7 +42,9 @@ named scenarios, each a list of probe observations 'east,north,day,kind,rate[,n]
 found n, none, found; rate: the expected number found per wasp in the cell) or a .npy file of one log-weight per
 chain row after burn and thin (several chains: concatenated in chain order), by importance reweighting of the
 members, with the effective sample size of every scenario in the json -- saved as PREFIX_reweight.npz (and
-PREFIX_NAME_reweight.npz for every projection and plan asked for); with --catch also the catch-probability maps --
+PREFIX_NAME_reweight.npz for every projection and plan asked for), and with --reweight-maps quantiles,arrival the
+reweighted quantile maps of --quantiles and arrival maps of --arrival as PREFIX_reweight_quantiles.npz and
+PREFIX_reweight_arrival.npz; with --catch also the catch-probability maps --
 per trap 'DAY,RATE[,N]' and cell the posterior mean, sd and the probability (--catch-levels) that a trap of effort
 RATE on model day DAY catches at least N wasps; --catch-emergence: traps over the emergence days of --emergence --
 saved as PREFIX_catch.npz (and PREFIX_emergence_catch.npz, PREFIX_sites_catch.npz); with --neighbourhood also the
@@ -72,6 +74,7 @@ Without --chain a short chain is sampled first (--samples) and saved next to --o
         [--pathways 1,10] [--pathway-connectivity 8] [--pathway-levels 0.05,0.5,0.95]
         [--representative [K]] [--representative-epsilon 0.02] [--representative-central 0.5]
         [--reweight 'NAME:east,north,day,kind,rate[,n];...'] [--reweight-file NAME=weights.npy]
+        [--reweight-maps quantiles,arrival]
         [--catch 'DAY,RATE[,N];...'] [--catch-levels 0.5,0.95] [--catch-emergence 'OBSDAY,RATE[,N];...']
         [--information 'DAY,RATE[,YMAX];...'] [--neighbourhood 'DAY,RADIUS_M;...']
         [--proximity 'DAY,T[,in];...'] [--proximity-radii 100,400,1600] [--proximity-levels 0.05,0.5,0.95]
@@ -251,8 +254,20 @@ def main():
     ap.add_argument('--reweight-file', action='append', default=None, metavar='NAME=NPY',
                     help='a reweighting scenario from a .npy of one log-weight per chain row after burn and thin '
                          '(repeatable)')
+    ap.add_argument('--reweight-maps', default='', metavar='quantiles,arrival',
+                    help='with --reweight / --reweight-file: also reweight the quantile maps (needs --quantiles) and '
+                         'the arrival maps (needs --arrival), saved as PREFIX_reweight_quantiles.npz / '
+                         'PREFIX_reweight_arrival.npz (default: off)')
     args = ap.parse_args()
     rw_specs, rw_files = parse_reweight(ap, args.reweight, args.reweight_file)
+    rw_maps = [m.strip() for m in args.reweight_maps.split(',') if m.strip()]
+    if rw_maps and not (rw_specs or rw_files):
+        ap.error('--reweight-maps reweights more maps of a scenario: give --reweight or --reweight-file too')
+    if [m for m in rw_maps if m not in ('quantiles', 'arrival')] or len(set(rw_maps)) != len(rw_maps):
+        ap.error("--reweight-maps takes a subset of 'quantiles,arrival', got %r" % args.reweight_maps)
+    for m in rw_maps:
+        if not getattr(args, m).strip():
+            ap.error('--reweight-maps %s reweights the maps of --%s: give --%s too' % (m, m, m))
     if args.compare_sites and not args.sites:
         ap.error('--compare-sites names plan B and needs plan A: give --sites too')
     warnings.simplefilter('ignore', RuntimeWarning)
@@ -423,6 +438,8 @@ def main():
                 ap.error('--reweight-file %s: %d log-weights, the chains have %d rows after burn and thin'
                          % (path, lw.size, sum(nrows)))
             reweight[name] = dict(log_weights=np.split(lw, np.cumsum(nrows)[:-1]))
+        if rw_maps:
+            reweight['options'] = dict(maps=tuple(rw_maps))
         rw_plan = check_reweight(reweight, pm.rad_dist, pm.rad_res, len(days))
     t0 = time.perf_counter()
     res = posterior_predictive(pms if len(pms) > 1 else pm, chains, burn=args.burn, thin=args.thin,
@@ -481,6 +498,15 @@ def main():
         RW = ReweightedSummary(pm, rw_plan['names'], None, thr)
         RWF = _ReweightFeed(rw_plan, 0)
         RW.profile(True)
+    RWM = []                             # the reweighted quantile and arrival maps, fed the same log-weights
+    if reweight and rw_maps:
+        from parasitoids_amd.predictive import ReweightedArrival, ReweightedHistogram
+        if 'quantiles' in rw_maps:
+            RWM.append(ReweightedHistogram(pm, rw_plan['names'], None, bins))
+        if 'arrival' in rw_maps:
+            RWM.append(ReweightedArrival(pm, rw_plan['names'], arrival))
+        for m in RWM:
+            m.profile(True)
     CF = CP = None
     if catch:                            # and a Projection of as many outputs: the same bytes, a plain streaming pass
         from parasitoids_amd.predictive import CatchFields
@@ -575,7 +601,10 @@ def main():
                     if n == 0:
                         PF.profile(True)
                 if RW is not None:
-                    RW.add(RWF.log_weights(pm, first, length), length)
+                    lam = RWF.log_weights(pm, first, length)
+                    RW.add(lam, length)
+                    for m in RWM:
+                        m.add(lam, length)
                 if ME is not None:
                     ME.add(length)
                 if X is not None:
@@ -659,6 +688,15 @@ def main():
         rw_ms, rw_launches = RW.profile()
         rw_bytes = RW.nbytes
         RW.close()
+    rwm_ms = rwm_members = 0
+    rwm_detail = {}
+    for m in RWM:                        # add and rescale launches of both handles, per member
+        add_ms, adds, _q, _n, sc_ms, scs = m.profile()
+        rwm_ms += add_ms + sc_ms
+        rwm_members = max(rwm_members, adds)
+        rwm_detail[m._prefix] = {'add_ms': round(add_ms / max(adds, 1), 4), 'rescales': scs,
+                                 'rescale_ms': round(sc_ms / max(scs, 1), 4), 'bytes': m.nbytes}
+        m.close()
     if X is not None:
         x_ms, x_launches = X.profile()
         x_bytes = X.nbytes
@@ -746,6 +784,11 @@ def main():
         out['reweight_launches_timed'] = rw_launches
         out['reweight_scenarios'] = list(res.reweight.scenarios)
         out['reweight_bytes'] = rw_bytes
+        if rw_maps:
+            out['reweight_maps'] = rw_maps
+            out['reweight_maps_ms_per_member'] = round(rwm_ms / max(rwm_members, 1), 4)
+            out['reweight_maps_detail'] = rwm_detail
+            out['outputs'] += ['%s_reweight_%s.npz' % (args.out, m) for m in rw_maps]
         out['reweight_diagnostics'] = res.reweight_info['diagnostics']
         out['outputs'] += ['%s_reweight.npz' % args.out] + ['%s_%s_reweight.npz' % (args.out, n) for n, on in
                                                             (('emergence', emergence), ('exposure', exposure),
