@@ -791,6 +791,50 @@ int ps_contrast_reset(ps_contrast* h);
 int ps_contrast_prof(ps_contrast* h, int enable, double* total_ms, int64_t* launches);
 void ps_contrast_destroy(ps_contrast* h);
 
+/* ---- ranking of several named release plans (or projections), member by member ----
+ * (no reference counterpart.)  P plans (2..8, fixed at create) are driven by the same member.  With a_j the
+ * value plan j holds at a cell (finite and >= 0 by construction of both sources), m = max_j a_j (exact) and
+ * n_max the number of plans with a_j == m, the handle keeps per slot and cell
+ *   best_j  += w where a_j == m and n_max == 1 (a tie counts for nobody: most of the domain is 0 for every plan),
+ *   the weighted mean and M2 of the regret r_j = m - a_j (one rounded subtraction, >= 0) by the step of
+ *   ps_summary_add, nothing stored where r_j equals its mean,
+ * and per threshold t_k (0..4, finite, > 0, strictly increasing), with n the number of plans with a_j >= t_k,
+ *   sole_kj += w where a_j >= t_k and n == 1,   any_k += w where n >= 1,   all_k += w where n == P,
+ * and per member one row [P][nthr][nslot] of uint32: the cells with a_j >= t_k, kept in add order with the
+ * member's weight (no rows without thresholds; the store grows by doubling).  The count planes of a slot, in
+ * order: best_0 .. best_{P-1}, then per k: sole_k0 .. sole_k,P-1, any_k, all_k -- Q = P + nthr (P + 2) planes.
+ * Device memory: nslot x pitch x (16 P + 4 Q) bytes, checked against the free memory before anything is
+ * allocated (PS_ERR_OOM).  Every mean, M2 and count cell has one writer; the rows are integer sums (ballot
+ * popcounts kept in registers, summed over the block's waves in LDS, one integer atomic per block and
+ * counter): no floating-point atomics, and no order of adds or merges changes a bit of a count.
+ * PS_ERR_BAD_ARG: nplan outside 2..8, nthr outside 0..4, bad thresholds. */
+typedef struct ps_rank ps_rank;
+int ps_rank_create(int device, int N, int nplan, int nslot, int nthr, const double* thr, ps_rank** out);
+/* One member with weight >= 1: slot e takes a_j = plans[j].Y_e of the sources' current outputs.  Enqueued on
+ * the handle's stream behind every source's last operation; the next apply of any source waits for the read.
+ * PS_ERR_BAD_ARG (nothing enqueued): nplan outside 2..8 or not the handle's, a null or repeated source, a source
+ * whose device, N or number of outputs is not the handle's, weight 0 or a total weight past 2^32 - 1.
+ * PS_ERR_STATE: a source without finished fields (never applied, or a release plan mid-pass over its groups). */
+int ps_rank_add_sites(ps_rank* h, ps_sites* const* plans, int nplan, uint32_t weight);
+int ps_rank_add_project(ps_rank* h, ps_project* const* plans, int nplan, uint32_t weight);
+/* dst += src (every mean and M2 as ps_summary_merge, counts added, src's rows appended after dst's), same
+ * device, N, plans, slots and thresholds; src stays as it is.  Into an empty dst it is a device copy, bit for
+ * bit. */
+int ps_rank_merge(ps_rank* dst, ps_rank* src);
+int ps_rank_info(ps_rank* h, double* total_weight, int64_t* members);
+/* one slot of one plan to the host (synchronises): what 0 regret mean, 1 regret variance M2 / W, 2 P(best)
+ * (best_j / W).  PS_ERR_BAD_ARG for a bad slot, plan or quantity; PS_ERR_STATE at W = 0. */
+int ps_rank_fetch(ps_rank* h, int slot, int plan, int what, double* out /* N*N */);
+/* the raw count plane `which` (0 .. Q - 1, in the order above) of a slot */
+int ps_rank_fetch_counts(ps_rank* h, int slot, int which, uint32_t* out /* N*N */);
+/* the rows of the members first .. first + count - 1 in add order and their weights (either may be null) */
+int ps_rank_fetch_coverage(ps_rank* h, int64_t first, int64_t count,
+                           uint32_t* cells /* [count][P][nthr][nslot] */, uint32_t* weights);
+int ps_rank_reset(ps_rank* h);
+/* measurement: HIP-event timing of the add launches, as ps_summary_prof */
+int ps_rank_prof(ps_rank* h, int enable, double* total_ms, int64_t* launches);
+void ps_rank_destroy(ps_rank* h);
+
 /* ---- Monte Carlo error of the posterior maps: batch means of one sequence of members ----
  * (no reference counterpart: it calls pm.gelman_rubin on scalar parameters only.)  Every map above is a Monte
  * Carlo estimate from a correlated chain; its error needs the order of the chain at every cell and cannot be

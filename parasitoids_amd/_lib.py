@@ -223,6 +223,17 @@ SIGNATURES = {
     'ps_contrast_reset': (C.c_int, [_VP]),
     'ps_contrast_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P]),
     'ps_contrast_destroy': (None, [_VP]),
+    'ps_rank_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F64P, C.POINTER(_VP)]),
+    'ps_rank_add_sites': (C.c_int, [_VP, C.POINTER(_VP), C.c_int, C.c_uint32]),
+    'ps_rank_add_project': (C.c_int, [_VP, C.POINTER(_VP), C.c_int, C.c_uint32]),
+    'ps_rank_merge': (C.c_int, [_VP, _VP]),
+    'ps_rank_info': (C.c_int, [_VP, _F64P, _I64P]),
+    'ps_rank_fetch': (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, _F64P]),
+    'ps_rank_fetch_counts': (C.c_int, [_VP, C.c_int, C.c_int, C.POINTER(C.c_uint32)]),
+    'ps_rank_fetch_coverage': (C.c_int, [_VP, C.c_int64, C.c_int64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    'ps_rank_reset': (C.c_int, [_VP]),
+    'ps_rank_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P]),
+    'ps_rank_destroy': (None, [_VP]),
     'ps_mcerr_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _F64P, C.c_uint32, C.POINTER(_VP)]),
     'ps_mcerr_add': (C.c_int, [_VP, _VP, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P, C.c_double, C.c_uint32]),
     'ps_mcerr_add_project': (C.c_int, [_VP, _VP, C.c_uint32]),

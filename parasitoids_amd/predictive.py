@@ -2494,7 +2494,8 @@ def exposure_plan(exposure, ndays=None):
 
 # ------------------------------------------------------------------ the accumulators fed from one source of fields
 # The order in which posterior_predictive feeds one member to the accumulators of one source of fields, per kind of
-# source: the model's day fields, a Projection, the ReleaseSites of sites= and, after it, plan B of compare=.
+# source: the model's day fields, a Projection, the ReleaseSites of sites=, after it plan B of compare= and, last,
+# the further plans of ranking=.
 # 'apply' is the source's own.  The three orders differ for no better reason than the history of the maps.
 FEED_ORDER = {
     'days': ('summary', 'origin', 'core_range', 'reweight', 'reweight_histogram', 'reweight_arrival', 'catch', 'neighbourhood', 'proximity', 'information', 'excursion', 'mc_error',
@@ -2504,6 +2505,7 @@ FEED_ORDER = {
               'dependence', 'histogram', 'arrival', 'peak', 'excursion', 'core_range', 'catch', 'neighbourhood', 'proximity', 'information', 'patches', 'pathways',
               'modes'),
     'compare': ('apply', 'contrast'),
+    'ranking': ('apply', 'ranking'),
 }
 
 
@@ -2551,6 +2553,7 @@ FEED = {
     'information': lambda acc, fs, m: acc.add(m.length, m.lam),
     'mc_error': _add_halves,
     'contrast': _add_length,
+    'ranking': _add_length,
     'patches': _add_length,
     'pathways': _add_length,
     'modes': _add_length,
@@ -2721,6 +2724,7 @@ BUILD = {
     'information': _build_information,
     'mc_error': _build_mc_error,
     'contrast': lambda fs, q: PlanContrast(fs._against, fs._source, q.thresholds),
+    'ranking': lambda fs, q: PlanRanking([fs._against] + fs._source.plans, q.thresholds, q.rk_plan['names']),
     'patches': lambda fs, q: q.pt_thr and fs._over(PatchMaps, (q.pt_thr, fs._days, q.pt_conn), (q.pt_thr, q.pt_conn)),
     'pathways': lambda fs, q: q.pw_thr and fs._over(PathwayMaps, (q.pw_thr, q.pw_days or fs._days, q.pw_conn),
                                                    (q.pw_thr, q.pw_conn)),
@@ -2748,7 +2752,7 @@ class _FieldSet():
 
     def fed_from(self, kind, source, name=None, owns=True, against=None, **traps):
         '''kind: a key of FEED_ORDER; name: the driver's name of the source (default: the kind); owns: release()
-        closes the source; against: plan A of a 'compare' set; traps: per 'catch' / 'information' / 'neighbourhood' /
+        closes the source; against: plan A of a 'compare' or 'ranking' set; traps: per 'catch' / 'information' / 'neighbourhood' /
         'proximity' the arguments of its fields after the source, None for none'''
         self._kind, self._name, self._source, self._owns = kind, name or kind, source, owns
         self._against, self._traps = against, traps
@@ -3335,6 +3339,292 @@ class PlanContrast(_Accumulator):
         '''HIP-event time of the add launches: (total ms, adds); enable switches it'''
         return self._profile(enable)
 
+
+# ------------------------------------------------------------------ ranking of several named plans
+MIN_RANKED_PLANS = 2
+MAX_RANKED_PLANS = 8       # ps_rank: the plans of one handle, plan A of sites= among them
+
+
+def coverage_ranking(cells, weights, cell_area, levels=(0.05, 0.5, 0.95)):
+    '''Per output the posterior of the areas P plans cover and of their order, from the joint per-member cell
+    counts cells [members, P, nout] and the members' integer weights: [{'plans': [{'mean', 'quantiles', 'p_most',
+    'mean_rank', 'mean_shortfall'}, ... one per plan], 'p_tied'}, ... one per output].  Areas in m^2 (cells x
+    cell_area).  mean: the weighted mean area (from integer sums with one division, as ArrivalMaps.reached_area);
+    quantiles: its weighted lower quantiles (weighted_lower_quantile) at `levels`; p_most: the weight of the
+    members in which the plan covers strictly the most, over W; mean_rank: the weighted mean mid-rank, 1 the
+    largest area, tied plans sharing the average of their ranks; mean_shortfall: the weighted mean of (the
+    member's largest count - the plan's) x cell_area; p_tied: the weight of the members whose largest area is
+    shared, over W.  Everything is computed from integers.  ValueError at W = 0.'''
+    levels = check_levels(levels)
+    c = np.asarray(cells, dtype=np.int64)
+    w = np.asarray(weights, dtype=np.int64).ravel()
+    if c.ndim != 3 or c.shape[1] < 1 or c.shape[0] != w.size:
+        raise ValueError('cell counts %r with %d weights' % (c.shape, w.size))
+    if w.size and w.min() < 0:
+        raise ValueError('weights must be >= 0')
+    W = int(w.sum())
+    if W == 0:
+        raise ValueError('nothing accumulated')
+    area = float(cell_area)
+    out = []
+    for s in range(c.shape[2]):
+        x = c[:, :, s]                                       # [members, P]
+        top = x.max(axis=1)
+        ntop = (x == top[:, None]).sum(axis=1)
+        plans = []
+        for j in range(x.shape[1]):
+            xj = x[:, j]
+            rank2 = 2 * (x > xj[:, None]).sum(axis=1) + (x == xj[:, None]).sum(axis=1) + 1     # twice the mid-rank
+            plans.append({'mean': float(int((xj * w).sum())) / float(W) * area,
+                          'quantiles': [float(weighted_lower_quantile(xj, w, p)) * area for p in levels],
+                          'p_most': float(int(w[(xj == top) & (ntop == 1)].sum())) / float(W),
+                          'mean_rank': float(int((rank2 * w).sum())) / float(2 * W),
+                          'mean_shortfall': float(int(((top - xj) * w).sum())) / float(W) * area})
+        out.append({'plans': plans, 'p_tied': float(int(w[ntop > 1].sum())) / float(W)})
+    return out
+
+
+def ranking_plan(arg, sites_arg, pop_model=None):
+    '''posterior_predictive's ranking= argument, dict(plans=[dict(sites=[(east_m, north_m, amount[, lag_days]),
+    ...]), ...], names=None, levels=(0.05, 0.5, 0.95)) or the bare list of plans: 1..7 further plans, ranked with
+    the plan A of the sites= argument `sites_arg` (plan 0) on A's output days -> dict(plans=[(sites, days, lags),
+    ...] of the further plans (sites_plan), names=[...] of all plans, A's first (default 'plan0', 'plan1', ...),
+    levels=[...]).  ValueError, in this order, for: an argument of another shape; a ranking= without sites=; fewer
+    than 1 or more than 7 plans; a plan that is no dict(sites=[...]) -- output days of its own among that; bad
+    names (not one string per plan, A included, or a name twice); bad levels; a bad plan A; a bad further plan
+    (its number in the message).'''
+    shape = ('ranking must be dict(plans=[dict(sites=[(east_m, north_m, amount[, lag_days]), ...]), ...], names=None, '
+             'levels=(0.05, 0.5, 0.95)) or the list of plans, got %r' % (arg,))
+    if isinstance(arg, (list, tuple)):
+        arg = dict(plans=list(arg))
+    if not isinstance(arg, dict) or 'plans' not in arg or set(arg) - {'plans', 'names', 'levels'} \
+            or not isinstance(arg['plans'], (list, tuple)):
+        raise ValueError(shape)
+    if sites_arg is None:
+        raise ValueError('ranking= names further plans and needs plan A: give sites= too')
+    plans = list(arg['plans'])
+    if not 1 <= len(plans) <= MAX_RANKED_PLANS - 1:
+        raise ValueError('%d further plans; 1..%d are ranked with plan A' % (len(plans), MAX_RANKED_PLANS - 1))
+    for j, p in enumerate(plans):
+        if not isinstance(p, dict) or 'sites' not in p or set(p) - {'sites'}:
+            raise ValueError('ranking: plan %d must be dict(sites=[(east_m, north_m, amount[, lag_days]), ...]) -- '
+                             'every plan is ranked on plan A\'s output days -- got %r' % (j + 1, p))
+    names = arg.get('names')
+    if names is None:
+        names = ['plan%d' % j for j in range(len(plans) + 1)]
+    else:
+        if isinstance(names, str) or not isinstance(names, (list, tuple)) or len(names) != len(plans) + 1 \
+                or not all(isinstance(n, str) and n for n in names):
+            raise ValueError('ranking: names must be %d non-empty strings, plan A\'s first, got %r'
+                             % (len(plans) + 1, names))
+        names = list(names)
+        if len(set(names)) != len(names):
+            raise ValueError('ranking: plan names listed twice: %r' % (names,))
+    levels = check_levels(arg.get('levels', (0.05, 0.5, 0.95)))
+    _a_sites, a_days, _lags = sites_plan(sites_arg, pop_model)
+    checked = []
+    for j, p in enumerate(plans):
+        try:
+            checked.append(sites_plan(dict(sites=p['sites'], days=a_days), pop_model))
+        except ValueError as e:
+            raise ValueError('ranking: plan %d: %s' % (j + 1, e))
+    return dict(plans=checked, names=names, levels=list(levels))
+
+
+class _RankedPlans():
+    '''the further plans of a ranking as one source of the driver: apply() applies each in order, close() closes
+    them'''
+
+    def __init__(self):
+        self.plans = []
+
+    def apply(self):
+        for p in self.plans:
+            p.apply()
+
+    def describe(self):
+        return [p.describe() for p in self.plans]
+
+    def close(self):
+        for p in self.plans:
+            p.close()
+
+
+class PlanRanking(_Accumulator):
+    '''The posterior of the order of several named plans, member by member, on the device: `plans` are 2..8
+    different ReleaseSites or 2..8 different Projection on the same device and domain with the same outputs (nout,
+    live; of ReleaseSites also the same output days -- outputs are paired by index and labelled by the first
+    plan's days; of Projection the caller sees to it that output e means the same in all).  After all were
+    applied to one member, `add(weight)` accumulates per output and cell, with a_j the value of plan j and
+    m = max_j a_j: the weight of the members in which plan j alone holds m (`prob_best`; a tie, the zeros of most
+    of the domain among them, counts for nobody: `prob_undecided`), the weighted mean and M2 of the regret
+    r_j = m - a_j (one rounded subtraction) by SpreadSummary's step, per threshold t_k (0..4, finite, > 0, strictly
+    increasing) the weight of those in which plan j alone reaches t_k (`sole`), some plan does (`any`) and every
+    plan does (`all`), and per member the cells every plan covers at t_k on every output (`coverage`,
+    `coverage_ranking`) -- joint statements over the plans inside one member, which no set of pairwise contrasts
+    holds.  The accessors take the output index and the plan's index; outputs kept off the device read as zeros.
+    Counts are integers: the order of adds and merges changes no bit.  The plans are the ones the caller names:
+    nothing is searched, proposed or recommended.'''
+
+    _prefix = 'ps_rank'
+
+    def __init__(self, plans, thresholds=(), names=None):
+        plans = list(plans)
+        if not MIN_RANKED_PLANS <= len(plans) <= MAX_RANKED_PLANS:
+            raise ValueError('%d plans; %d..%d are ranked' % (len(plans), MIN_RANKED_PLANS, MAX_RANKED_PLANS))
+        a = plans[0]
+        if any(type(p) is not type(a) for p in plans) or not isinstance(a, (ReleaseSites, Projection)):
+            raise ValueError('ReleaseSites only or Projection only expected, got %s'
+                             % ', '.join(type(p).__name__ for p in plans))
+        for j, p in enumerate(plans):
+            if any(p is o for o in plans[:j]):
+                raise ValueError('plan %d is listed twice: a plan is ranked with others, not with itself' % j)
+            if p.pm.device != a.pm.device:
+                raise ValueError('the plans\' models are on devices %r and %r' % (a.pm.device, p.pm.device))
+            for name in ('device', 'N', 'nout', 'live') + (('days',) if isinstance(a, ReleaseSites) else ()):
+                if getattr(p, name) != getattr(a, name):
+                    raise ValueError('plans 0 and %d differ in %s: %r and %r'
+                                     % (j, name, getattr(a, name), getattr(p, name)))
+        self.thresholds = check_contrast_thresholds(thresholds)
+        if names is None:
+            names = ['plan%d' % j for j in range(len(plans))]
+        names = [str(n) for n in names]
+        if len(names) != len(plans) or len(set(names)) != len(names):
+            raise ValueError('%d different names expected, one per plan, got %r' % (len(plans), names))
+        self.plans, self.names, self.nplan = plans, names, len(plans)
+        self._attach(a.pm)
+        self.device, self.nout, self.live = a.device, a.nout, list(a.live)
+        self.labels = list(getattr(a, 'days', range(a.nout)))
+        self._slot = {e: i for i, e in enumerate(self.live)}
+        self.nplanes = self.nplan + len(self.thresholds) * (self.nplan + 2)
+        self.nbytes = len(self.live) * self.pitch * (16 * self.nplan + 4 * self.nplanes)    # moments and counts
+        thr = L.f64(self.thresholds if self.thresholds else [0.0])
+        self._create(self.nplan, len(self.live), len(self.thresholds), L.p_f64(thr))
+
+    def add(self, weight=1):
+        '''Accumulate the last apply of every plan with integer weight >= 1 (on the handle's stream behind all of
+        them; no host synchronisation)'''
+        handles = (L._VP * self.nplan)(*[p._h.value for p in self.plans])
+        self._call('add_' + self.plans[0].fields_kind, handles, self.nplan, self._weight(weight))
+
+    def merge(self, other):
+        '''self += other (same device, domain, number of plans, outputs and thresholds); other's members follow
+        self's'''
+        if other.live != self.live or other.nout != self.nout or list(other.labels) != self.labels \
+                or other.nplan != self.nplan:
+            raise ValueError('rankings over different outputs or numbers of plans')
+        self._call('merge', other._h)
+
+    def _j(self, j):
+        return self._index(j, self.nplan, 'plan')
+
+    def _fetch(self, e, j, what):
+        e, j = self._e(e), self._j(j)
+        if e not in self._slot:
+            return np.zeros((self.N, self.N), dtype=np.float64)
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        self._call('fetch', self._slot[e], j, int(what), L.p_f64(out))
+        return out
+
+    def regret(self, e, j):
+        '''[N, N] float64: the posterior mean of max_i a_i - a_j on output e -- what choosing plan j gives away
+        at a cell against the best of the named plans there'''
+        return self._fetch(e, j, 0)
+
+    def regret_variance(self, e, j):
+        return self._fetch(e, j, 1)
+
+    def regret_sd(self, e, j):
+        return np.sqrt(self.regret_variance(e, j))
+
+    def prob_best(self, e, j):
+        '''P(plan j alone holds the largest value) per cell'''
+        return self._fetch(e, j, 2)
+
+    def counts(self, e, which):
+        '''[N, N] uint32: the raw count plane of output e -- j: best_j; P + k (P + 2) + j: sole_kj, then any_k and
+        all_k'''
+        e = self._e(e)
+        which = self._index(which, self.nplanes, 'count plane')
+        if e not in self._slot:
+            return np.zeros((self.N, self.N), dtype=np.uint32)
+        out = np.empty((self.N, self.N), dtype=np.uint32)
+        self._call('fetch_counts', self._slot[e], which, out.ctypes.data_as(C.POINTER(C.c_uint32)))
+        return out
+
+    def _share(self, e, which):
+        return self.counts(e, which).astype(np.float64) / float(self.total_weight)
+
+    def prob_undecided(self, e):
+        '''1 - sum_j best_j / W per cell: the share of the members in which no plan alone is best -- ties, and
+        the cells no plan reaches'''
+        e = self._e(e)
+        best = np.zeros((self.N, self.N), dtype=np.int64)
+        for j in range(self.nplan):
+            best += self.counts(e, j)
+        return 1.0 - best.astype(np.float64) / float(self.total_weight)
+
+    def leader(self, e):
+        '''[N, N] int8: the plan with the largest P(best) per cell, among equals the smallest index, -1 where every
+        P(best) is 0.  A summary of the posterior in the sense of OriginMaps.mode(), not a recommendation: it says
+        which of the named plans is most often alone on top at a cell, nothing about which plan to choose.'''
+        e = self._e(e)
+        best = np.stack([self.counts(e, j) for j in range(self.nplan)])
+        out = np.argmax(best, axis=0).astype(np.int8)
+        out[best.max(axis=0) == 0] = -1
+        return out
+
+    def _plane(self, k, j):
+        return self.nplan + self._k(k) * (self.nplan + 2) + j
+
+    def sole(self, e, k, j):
+        '''P(plan j reaches thresholds[k] and no other plan does) per cell: reached only if plan j is chosen'''
+        return self._share(e, self._plane(k, self._j(j)))
+
+    def any(self, e, k):
+        '''P(some plan reaches thresholds[k]) per cell'''
+        return self._share(e, self._plane(k, self.nplan))
+
+    def all(self, e, k):
+        '''P(every plan reaches thresholds[k]) per cell: reached whichever plan is chosen'''
+        return self._share(e, self._plane(k, self.nplan + 1))
+
+    def _coverage(self):
+        m = self.members
+        cells = np.zeros((m, self.nplan, len(self.thresholds), len(self.live)), dtype=np.uint32)
+        w = np.zeros(m, dtype=np.uint32)
+        u32 = C.POINTER(C.c_uint32)
+        self._call('fetch_coverage', 0, m, cells.ctypes.data_as(u32), w.ctypes.data_as(u32))
+        return cells, w
+
+    @property
+    def weights(self):
+        '''[members] int64: the members' weights in add order'''
+        return self._coverage()[1].astype(np.int64)
+
+    def coverage(self, k):
+        '''(cells [members, P, nout] int64, weights [members] int64): per member in add order the number of cells
+        where each plan is >= thresholds[k] on every output'''
+        k = self._k(k)
+        cells, w = self._coverage()
+        out = np.zeros((cells.shape[0], self.nplan, self.nout), dtype=np.int64)
+        out[:, :, self.live] = cells[:, :, k, :]
+        return out, w.astype(np.int64)
+
+    def coverage_ranking(self, k, levels=(0.05, 0.5, 0.95)):
+        '''Per output the posterior of the plans' covered areas and of their order at thresholds[k]
+        (coverage_ranking of the joint rows), each entry with its output `label` and each plan's with its `name`'''
+        cells, w = self.coverage(k)
+        out = coverage_ranking(cells, w, self.cell_area, levels)
+        for label, rec in zip(self.labels, out):
+            rec['label'] = label
+            for name, p in zip(self.names, rec['plans']):
+                p['name'] = name
+        return out
+
+    def profile(self, enable=None):
+        '''HIP-event time of the add launches: (total ms, adds); enable switches it'''
+        return self._profile(enable)
 
 
 # ------------------------------------------------------------------ sensitivity
@@ -7240,7 +7530,10 @@ class PredictiveResult():
     release plan (with `plan` and, with arrival thresholds, `arrival`), None where not asked for;
     `sensitivity`: SensitivityMaps over the summary's days, None where not asked for (the projections and the
     plan then carry one of their own); `contrast`: the PlanContrast of the release plan against the plan of
-    compare= and `compare_plan` that plan (ReleaseSites.describe()), both None where not asked for; `mc_error`:
+    compare= and `compare_plan` that plan (ReleaseSites.describe()), both None where not asked for; `ranking`: the
+    PlanRanking of the release plan and the further plans of ranking=, `ranking_plans` all of them, plan A's first
+    (ReleaseSites.describe()), and `ranking_levels` the levels of its saved area quantiles, all None where not
+    asked for; `mc_error`:
     the MonteCarloError over the summary's days, all chains' half sequences pooled in chain order, its `rhat`
     their split R-hat maps, and `mc_plan` = dict(batches, batch_weight, sequences), both None where not asked for
     (the projections and the plan then carry an `mc_error` of their own); `peak`: the PeakPosterior over the
@@ -7281,7 +7574,11 @@ class PredictiveResult():
                  information=None, core_range=None, core_range_levels=None, patches=None, patch_levels=None,
                  representative=None, representative_days=None, representative_chains=None, neighbourhood=None,
                  modes=None, dependence=None, pathways=None, pathway_levels=None, proximity=None, origin=None,
-                 reweight_histogram=None, reweight_arrival=None):
+                 reweight_histogram=None, reweight_arrival=None, ranking=None, ranking_plans=None,
+                 ranking_levels=None):
+        self.ranking = ranking
+        self.ranking_plans = ranking_plans
+        self.ranking_levels = ranking_levels
         self.reweight_histogram = reweight_histogram
         self.reweight_arrival = reweight_arrival
         self.origin = origin
@@ -7363,6 +7660,13 @@ class PredictiveResult():
         P(A < B)), `{label}_pgain{k}_*` / `{label}_ploss{k}_*`, and `coverage{k}_a` / `coverage{k}_b` [members,
         outputs] with `contrast_weights`; under `predictive.contrast` of the json plan B, the thresholds, labels,
         members, weight, cell area, levels and per threshold the coverage difference.
+        A ranking of several plans goes into outfile_ranking.npz: per output day and plan j `{label}_pbest{j}_*`
+        (P(plan j alone is best)), `{label}_regret{j}_*`, `{label}_regret_sd{j}_*` and per threshold
+        `{label}_psole{k}_{j}_*`; per output day and threshold `{label}_pany{k}_*` / `{label}_pall{k}_*`; dense int8
+        `{label}_leader` (PlanRanking.leader: -1 where no plan is ever alone on top; dense because the CSR writer
+        drops index 0), `coverage{k}` [members, plans, outputs] and `ranking_weights`; under `predictive.ranking`
+        of the json the plans, names, thresholds, labels, members, weight, cell area, levels and per threshold
+        the coverage ranking.
         The Monte Carlo error goes into outfile_mcerr.npz: per day `{label}_mcse_*` (the standard error of the
         posterior mean), `{label}_ess_*`, `{label}_rhat_*` (where there are R-hat maps) and per threshold
         `{label}_pmcse{k}_*` (the standard error of the exceedance probability); those of a projection or a plan
@@ -7542,6 +7846,30 @@ class PredictiveResult():
                 'plan_b': self.compare_plan, 'thresholds': list(X.thresholds), 'labels': list(X.labels),
                 'members': X.members, 'total_weight': X.total_weight, 'cell_area': X.cell_area, 'levels': x_levels,
                 'coverage_difference': [X.coverage_difference(k, x_levels) for k in range(nk)]}
+        K = self.ranking
+        if K is not None:
+            k_levels = list(self.ranking_levels or (0.05, 0.5, 0.95))
+            nk = len(K.thresholds)
+            kmaps = []
+            kextra = {'ranking_weights': K.weights}
+            for e, label in enumerate(K.labels):
+                out_maps = []
+                for j in range(K.nplan):
+                    out_maps += [('_pbest%d' % j, K.prob_best(e, j)), ('_regret%d' % j, K.regret(e, j)),
+                                 ('_regret_sd%d' % j, K.regret_sd(e, j))]
+                    out_maps += [('_psole%d_%d' % (k, j), K.sole(e, k, j)) for k in range(nk)]
+                for k in range(nk):
+                    out_maps += [('_pany%d' % k, K.any(e, k)), ('_pall%d' % k, K.all(e, k))]
+                kmaps.append((label, out_maps))
+                kextra['%s_leader' % label] = K.leader(e)
+            for k in range(nk):
+                kextra['coverage%d' % k] = K.coverage(k)[0]
+            save_maps('%s_ranking' % outfile, kmaps, kextra)
+            meta['predictive']['ranking'] = {
+                'plans': self.ranking_plans, 'names': list(K.names), 'thresholds': list(K.thresholds),
+                'labels': list(K.labels), 'members': K.members, 'total_weight': K.total_weight,
+                'cell_area': K.cell_area, 'levels': k_levels,
+                'coverage_ranking': [K.coverage_ranking(k, k_levels) for k in range(nk)]}
         R = self.reweight
         if R is not None:
             labels = [s.pm.days[d] if d < len(s.pm.days) else d for d in s.days]
@@ -7646,7 +7974,7 @@ class PredictiveResult():
 def _evaluate_runs(pm, rows, run_list, model_cols, evaluate, want_obs, locinfo, sets=()):
     '''one chain: evaluate every run and feed it to the chain's sets (_FieldSet) in the order given, each in the
     FEED_ORDER of its kind.  With a 'sites' set the models of the plan's later release days are evaluated with the
-    base model -- with a 'compare' set those of both plans' (its `lagged`), each once -- and a member for which any
+    base model -- with a 'compare' or 'ranking' set those of all plans' (its `lagged`), each once -- and a member for which any
     of them fails is a failed member and is added nowhere.  With an origin= on the 'days' set the models of its
     hypotheses' later release days are evaluated too; a model the plan shares is evaluated once, over the days its
     longest reader needs.  The solver's FFT size follows the days evaluated, so where the findings reach further than
@@ -7656,6 +7984,8 @@ def _evaluate_runs(pm, rows, run_list, model_cols, evaluate, want_obs, locinfo, 
     failed = 0
     kinds = {fs._kind: fs for fs in sets}
     plan, both = kinds.get('sites'), kinds.get('compare')
+    if both is None:                   # a 'ranking' set carries the same models: those of every plan's later days
+        both = kinds.get('ranking')
     origin = getattr(kinds.get('days'), 'origin', None)
     for first, length in run_list:
         theta = rows[first, model_cols]
@@ -7816,6 +8146,12 @@ def _check_request(q):
         check_contrast_thresholds(thresholds)
         if pm0 is None:
             q.cmp_plan = None
+    q.rk_plan = None
+    if getattr(q, 'ranking', None) is not None:       # bad further plans, or none to rank them with
+        q.rk_plan = ranking_plan(q.ranking, q.sites, pm0)
+        check_contrast_thresholds(thresholds)
+        if pm0 is None:
+            q.rk_plan = None
     chains = q.chains
     if isinstance(chains, (str, os.PathLike)) or (isinstance(chains, tuple) and len(chains) == 2
                                                    and not isinstance(chains[0], (str, os.PathLike, tuple))):
@@ -7884,7 +8220,7 @@ def _check_request(q):
 
 def _build_sets(sets, q, pm, chain, nruns, late):
     '''the sets of one chain on the model pm, appended to `sets` in the order in which a member is fed to them: the
-    day fields', one per projection, the release plan's and the contrast's.  A set is in `sets` before it is built,
+    day fields', one per projection, the release plan's, the contrast's and the ranking's.  A set is in `sets` before it is built,
     so that the caller can close whatever a failure leaves.  late: {lag: model} of the later release days or None.'''
     def begin(fs, kind, source, name=None, **kw):
         sets.append(fs.fed_from(kind, source, name, **kw))
@@ -7914,6 +8250,14 @@ def _build_sets(sets, q, pm, chain, nruns, late):
             fs = begin(_FieldSet(), 'compare', rb, against=rs)
             fs.lagged, fs.plan = late, rb.describe()
             fs.build(q, chain, nruns)
+        if getattr(q, 'rk_plan', None) is not None:
+            group = _RankedPlans()
+            fs = begin(_FieldSet(), 'ranking', group, against=rs)
+            plans = q.ranking['plans'] if isinstance(q.ranking, dict) else q.ranking
+            for p in plans:
+                group.plans.append(ReleaseSites(pm, p['sites'], q.site_plan[1], late))
+            fs.lagged, fs.plan = late, [rs.describe()] + group.describe()
+            fs.build(q, chain, nruns)
 
 
 def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, thresholds=(), locinfo=None,
@@ -7922,7 +8266,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                          sensitivity=None, compare=None, mc_error=None, peak=None, excursion=None, reweight=None,
                          catch=None, information=None, core_range=None, patches=None, representative=None,
                          neighbourhood=None, modes=None, dependence=None, pathways=None, proximity=None,
-                         origin=None):
+                         origin=None, ranking=None):
     '''Posterior predictive spread of one or more chains (`Sampler.save` files or (trace, names) pairs). Burn and
     thin apply per chain; consecutive rows with identical model parameters are one evaluation weighted by the
     run's length.
@@ -7967,6 +8311,19 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         built once per model for the union of both plans' lags and each evaluated once per member; after A's
         applies and adds B is applied and the contrast added with the same weight, merged in chain order into
         `contrast` (`compare_plan`: plan B).
+
+    ranking: dict(plans=[dict(sites=[...]), ...], names=None, levels=(0.05, 0.5, 0.95)) or the bare list of plans
+        (ranking_plan; bad arguments fail before any evaluation, directly after compare='s): 1..7 further release
+        plans on the output days of sites= (plan A, required, plan 0 of the ranking): which of the named plans does
+        best where, and how surely?  Each chain then also builds a ReleaseSites per further plan and one
+        PlanRanking([A, ...], thresholds, names) -- the thresholds then have to be finite, > 0, strictly increasing
+        and at most 4 -- the models of the later release days built once per model for the union of the lags of
+        sites=, compare= and every ranked plan and each evaluated once per member; after A's applies and adds and
+        the compare set the further plans are applied and the ranking added with the run's length, merged in
+        chain order into `ranking` (`ranking_plans`: every plan, A's first).  It ranks the plans the caller names:
+        no plan is searched for, proposed or recommended; pairwise planes for all pairs, per-rank count planes and
+        the Monte Carlo error, reweighting or sensitivity of these maps are not computed.  Without ranking=
+        nothing is built, called or written.
 
     mc_error: True (20 batches per chain) or dict(batches=B), B even and >= 4 (mc_batch_plan; not with evaluate=,
         and every chain needs at least B rows after burn and thin); each chain then also fills two MonteCarloError
@@ -8178,6 +8535,8 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                     if (q.site_plan is not None or q.or_plan is not None) and p not in late:
                         # once per model, for the union of both plans' release days and the origin hypotheses'
                         lags = set(q.site_plan[2] if q.site_plan else ()) | set(q.cmp_plan[2] if q.cmp_plan else ())
+                        for ranked in (q.rk_plan['plans'] if q.rk_plan else ()):
+                            lags |= set(ranked[2])
                         lags |= set(q.or_plan['model_lags'] if q.or_plan else ())   # the known lags among them
                         late[p] = lagged_models(pm, sorted(lags))
                     _build_sets(chain_sets[ci], q, pm, ci, len(rl), late.get(p))
@@ -8266,6 +8625,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     prov = [{'source': p[4], 'rows': int(len(p[0])), 'runs': len(p[1]), 'burn': int(burn), 'thin': int(thin)}
             for p in prepared]
     plan_b = merged.get('compare', _FieldSet())
+    ranked = merged.get('ranking', _FieldSet())
     res = PredictiveResult(
         summary=day.summary, rows=int(sum(len(p[0]) for p in prepared)), evaluations=sum(len(p[1]) for p in prepared),
         failed=sum(r[1] for r in results), seconds=time.perf_counter() - t0, runs=run_rec, observations=observations,
@@ -8282,7 +8642,9 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         representative_chains=[p[0][:, p[2]] for p in prepared] if q.rp_plan else None,
         neighbourhood=day.neighbourhood, modes=day.modes, dependence=day.dependence, pathways=day.pathways,
         pathway_levels=q.pw_levels if q.pw_thr else None, proximity=day.proximity, origin=day.origin,
-        reweight_histogram=day.reweight_histogram, reweight_arrival=day.reweight_arrival)
+        reweight_histogram=day.reweight_histogram, reweight_arrival=day.reweight_arrival,
+        ranking=ranked.ranking, ranking_plans=ranked.plan,
+        ranking_levels=q.rk_plan['levels'] if q.rk_plan else None)
     if day.information is not None:   # the stated convention: past cap / 2 the ensemble bounds the map
         warn_information(day.information)
         if 'sites' in merged:

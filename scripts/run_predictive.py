@@ -14,7 +14,10 @@ posterior variance a linear dependence on them explains and the dominant paramet
 (and PREFIX_NAME_sens.npz for every projection and plan asked for); with --compare-sites (and --sites) also the
 paired contrast of the two release plans, member by member -- the posterior mean and spread of A - B, P(A > B),
 P(A < B), per threshold where A reaches it and B does not (and the reverse), and the posterior of the difference
-of the covered areas -- saved as PREFIX_contrast.npz; with --peak also the posterior peak maps -- per cell the
+of the covered areas -- saved as PREFIX_contrast.npz; with --rank-sites (once per further plan, and --sites) also
+the ranking of the named plans, member by member -- per plan P(it alone is best) and its regret against the best,
+per threshold where it alone, some plan or every plan reaches it, and the posterior of the covered areas' order
+-- saved as PREFIX_ranking.npz; with --peak also the posterior peak maps -- per cell the
 highest density within the window, the day of the peak and the number of days at or above each listed density
 (--peak-levels: the levels of the peak-day and duration quantile maps) -- saved as PREFIX_peak.npz (and, with
 --sites, PREFIX_sites_peak.npz for the plan); with --excursion also the joint excursion sets -- per listed
@@ -67,7 +70,8 @@ Without --chain a short chain is sampled first (--samples) and saved next to --o
         [--emergence C[:d1,d2,...]] [--exposure d1,d2,...]
         [--sites 'E,N,AMOUNT[,LAG];...'] [--sites-days d1,d2,...] [--sensitivity [name,name,...]]
         [--dependence [name,name,...]] [--dependence-bins 8]
-        [--compare-sites 'E,N,AMOUNT[,LAG];...'] [--peak 1,10] [--peak-levels 0.05,0.5,0.95]
+        [--compare-sites 'E,N,AMOUNT[,LAG];...'] [--rank-sites 'E,N,AMOUNT[,LAG];...' ...] [--rank-names a,b,c]
+        [--peak 1,10] [--peak-levels 0.05,0.5,0.95]
         [--excursion 1,10] [--excursion-levels 0.9,0.95]
         [--core-range 0.5,0.95] [--core-range-levels 0.5,0.9]
         [--patches 1,10] [--patch-connectivity 8] [--patch-levels 0.05,0.5,0.95]
@@ -169,6 +173,11 @@ def main():
                                                      '(default: all, at most 32)')
     ap.add_argument('--compare-sites', default='', help="a second release plan 'E,N,AMOUNT[,LAG];...' compared with "
                                                         '--sites member by member on its output days (default: off)')
+    ap.add_argument('--rank-sites', action='append', default=[],
+                    help="a further release plan 'E,N,AMOUNT[,LAG];...' ranked with --sites member by member on its "
+                         'output days; may be repeated, one plan per use, at most 7 (default: off)')
+    ap.add_argument('--rank-names', default='', help='names a,b,c,... of the ranked plans, that of --sites first '
+                                                     '(default: plan0,plan1,...)')
     ap.add_argument('--sensitivity', nargs='?', const='', default=None,
                     help='posterior sensitivity maps to the listed model parameters, e.g. sig_x,sig_y,mu_r '
                          '(no list: all 15; default: off)')
@@ -270,6 +279,10 @@ def main():
             ap.error('--reweight-maps %s reweights the maps of --%s: give --%s too' % (m, m, m))
     if args.compare_sites and not args.sites:
         ap.error('--compare-sites names plan B and needs plan A: give --sites too')
+    if args.rank_sites and not args.sites:
+        ap.error('--rank-sites names further plans and needs plan A: give --sites too')
+    if args.rank_names and not args.rank_sites:
+        ap.error('--rank-names names the plans of --rank-sites: give --rank-sites too')
     warnings.simplefilter('ignore', RuntimeWarning)
     from parasitoids_amd import ParasitoidModel as PM
     from parasitoids_amd import mcmc
@@ -351,6 +364,18 @@ def main():
                               for site in args.compare_sites.split(';') if site.strip()])
         contrast_plan(compare, sites)    # as does a bad --compare-sites
         check_contrast_thresholds([float(t) for t in args.thresholds.split(',') if t.strip()])
+    ranking = None
+    if args.rank_sites:
+        from parasitoids_amd.predictive import ranking_plan
+        ranking = dict(plans=[dict(sites=[tuple(float(v) if n < 3 else int(v) for n, v in enumerate(site.split(',')))
+                                          for site in plan.split(';') if site.strip()]) for plan in args.rank_sites])
+        if args.rank_names:
+            ranking['names'] = [n.strip() for n in args.rank_names.split(',')]
+        try:
+            ranking_plan(ranking, sites)     # as do bad --rank-sites or --rank-names
+        except ValueError as e:
+            ap.error('--rank-sites: %s' % e)
+        check_contrast_thresholds([float(t) for t in args.thresholds.split(',') if t.strip()])
     catch = None
     if args.catch:                       # as do bad --catch traps or levels
         from parasitoids_amd.predictive import check_catch, parse_traps
@@ -407,6 +432,8 @@ def main():
         sites_plan(sites, pm)
         if compare:
             contrast_plan(compare, sites, pm)
+        if ranking:
+            ranking_plan(ranking, sites, pm)
     if args.synthetic:
         li = mcmc.synthetic_locinfo(pm, args.rad_res, seed=9)
     else:
@@ -448,6 +475,7 @@ def main():
                                emergence=emergence, exposure=exposure, sites=sites, sensitivity=sens,
                                compare=compare, mc_error=mc_error, peak=peak, excursion=excursion,
                                **({'reweight': reweight} if reweight else {}),
+                               **({'ranking': ranking} if ranking else {}),
                                **({'catch': catch} if catch else {}),
                                **({'information': information} if information else {}),
                                **({'neighbourhood': neighbourhood} if neighbourhood else {}),
@@ -472,10 +500,21 @@ def main():
         DM = DependenceMaps(pm, depend['params'], res.dependence.edges)
     RB = XC = SC = None
     union = {}
-    if compare:                          # as the driver: one model per release day of either plan, shared by both
-        union = lagged_models(pm, sorted(set(sites_plan(sites, pm)[2]) | set(contrast_plan(compare, sites, pm)[2])))
+    RR = []
+    XR = None
+    if compare or ranking:               # as the driver: one model per release day of any plan, shared by all
+        lags = set(sites_plan(sites, pm)[2]) | set(contrast_plan(compare, sites, pm)[2] if compare else ())
+        for ranked in (ranking_plan(ranking, sites, pm)['plans'] if ranking else ()):
+            lags |= set(ranked[2])
+        union = lagged_models(pm, sorted(lags))
         RS = ReleaseSites(pm, sites['sites'], sites['days'], union)
-        RB = ReleaseSites(pm, compare['sites'], sites['days'], union)
+        if compare:
+            RB = ReleaseSites(pm, compare['sites'], sites['days'], union)
+        if ranking:
+            from parasitoids_amd.predictive import PlanRanking
+            RR = [ReleaseSites(pm, p['sites'], sites['days'], union) for p in ranking['plans']]
+            XR = PlanRanking([RS] + RR, thr, ranking.get('names'))
+            XR.profile(True)
     else:
         RS = ReleaseSites.with_lagged_models(pm, sites['sites'], sites['days']) if sites else None
     if compare:                          # and the plan's own summary to set the contrast's add against
@@ -570,7 +609,7 @@ def main():
             for first, length in rl[:8]:
                 try:
                     pm.evaluate(*mcmc.model_args(rows[first, cols]), want_stats=False)
-                    if union:
+                    if compare or ranking:
                         for lag, m in sorted(union.items()):       # each once per member, not once per plan
                             m.evaluate(*mcmc.model_args(rows[first, cols]), ndays=sites['days'][-1] - lag + 1,
                                        want_stats=False)
@@ -627,6 +666,10 @@ def main():
                     RB.apply()
                     SC.add(length)
                     XC.add(length)
+                if XR is not None:
+                    for R in RR:
+                        R.apply()
+                    XR.add(length)
                 n += 1
         ms, launches = S.profile()
     if H is not None:
@@ -720,8 +763,15 @@ def main():
         c_ms, c_launches = XC.profile()
         cs_ms, cs_launches = SC.profile()
         c_bytes = XC.nbytes
-        for h in (XC, SC, RB) + tuple(union.values()):
+        for h in (XC, SC, RB):
             h.close()
+    if XR is not None:
+        r_ms, r_launches = XR.profile()
+        r_bytes = XR.nbytes
+        for h in [XR] + RR:
+            h.close()
+    for h in union.values():
+        h.close()
     if RS is not None:
         RS.close()
     npz, js = res.save(args.out, {'chains': chains, 'burn': args.burn, 'thin': args.thin, 'rad_res': args.rad_res,
@@ -910,6 +960,15 @@ def main():
             if c_ms > 0 else None
         out['contrast_bytes'] = c_bytes
         out['outputs'] += ['%s_contrast.npz' % args.out]
+    if ranking:
+        out['ranking_add_ms_per_member'] = round(r_ms / max(r_launches, 1), 4)
+        out['ranking_launches_timed'] = r_launches
+        out['ranking_plans'] = 1 + len(ranking['plans'])
+        # what every add must move: every plan's fields, 8 B per plan, cell and output
+        out['ranking_read_GBps'] = round(8 * (1 + len(ranking['plans'])) * ncell * len(sites['days'])
+                                         / (r_ms / max(r_launches, 1) * 1e-3) / 1e9, 1) if r_ms > 0 else None
+        out['ranking_bytes'] = r_bytes
+        out['outputs'] += ['%s_ranking.npz' % args.out]
     print(json.dumps(out))
     res.summary.close()
     if res.histogram is not None:
@@ -922,7 +981,7 @@ def main():
         res.dependence.close()
     if res.mc_error is not None:
         res.mc_error.close()
-    for pr in (res.representative, res.emergence, res.exposure, res.sites, res.contrast, res.peak, res.excursion, res.catch, res.information,
+    for pr in (res.representative, res.emergence, res.exposure, res.sites, res.contrast, res.ranking, res.peak, res.excursion, res.catch, res.information,
                res.core_range, res.patches, res.pathways, res.neighbourhood, res.modes, res.proximity, res.origin):
         if pr is not None:
             pr.close()
