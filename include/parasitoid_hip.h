@@ -348,6 +348,15 @@ int ps_model_mvn_cdf_values(ps_model* m, double cell, double mu_x, double mu_y, 
 /* hand the kernels of the last batch straight to a solver on the same device
  * (no host round trip): equivalent to ps_chain_set_kernels with days [first, first+count). */
 int ps_chain_set_kernels_from_model(ps_solver* s, ps_model* m, int first, int count);
+/* The same with kernels idx[0..count) of the last batch, in that order, repeats allowed: equivalent to
+ * ps_chain_set_kernels with those kernels, so that many sequences of days run over one batch (weather
+ * ensembles).  One launch (k_gather_kernels: one block row per kernel, grid-stride over its entries) copies the
+ * chosen segments of the model's COO pool into a staging block the model owns, on the model's stream; the
+ * solver's stream waits for it by event and copies the block, and the next gather waits for that copy: no host
+ * synchronisation of its own.  PS_ERR_BAD_ARG: a null handle, count < 0, a null idx with count > 0, more than
+ * 65535 kernels, solver and model on different devices; PS_ERR_STATE: an index outside the last batch; a failed
+ * day's own status. */
+int ps_chain_set_kernels_from_model_indexed(ps_solver* s, ps_model* m, const int32_t* idx, int count);
 int ps_solver_set_state_from_model(ps_solver* s, ps_model* m, int i);
 
 /* ---- device-resident exchange between ranks (Run.py:412-425 maps prob_mass over a process pool; here
@@ -893,6 +902,60 @@ int ps_mcerr_reset(ps_mcerr* h);
 int ps_mcerr_prof(ps_mcerr* h, int enable, double* add_ms, int64_t* add_launches, double* close_ms,
                   int64_t* close_launches);
 void ps_mcerr_destroy(ps_mcerr* h);
+
+/* ---- weather and parameter variance of the posterior maps: members in groups ----
+ * (no reference counterpart.)  A weather ensemble evaluates every parameter vector under several wind
+ * sequences; the members of one vector are a group.  Per slot and cell, fp64 planes of [slot][pitch], pitch =
+ * N*N rounded up to 64 cells: imean, iM2 -- the open group, its draws with weight 1 each; omean, oM2 -- Welford
+ * over the closed groups' means with weights w_g; wS = sum w_g s2_g; and the three planes finalize leaves: 8
+ * planes x 8 B per cell and slot (739 MB at R = 400, 18 days; PS_ERR_OOM from a size check before anything is
+ * allocated).  Host side: the open group's draws k, the closed groups G, their weight W, sum w_g / k_g and the
+ * members (draws added).  Every operation is rounded on its own (no contraction), so the statements below,
+ * executed one operation at a time in IEEE double, give every plane bit for bit:
+ *   add (k' = k + 1):  d = v - imean;  if d != 0:  imean' = imean + d / k';  iM2 = iM2 + d * (v - imean')
+ *   close(w), k >= 2:  s2 = iM2 / (k - 1);  wS = wS + w * s2;  Wn = W + w;  d = imean - omean
+ *                      if d != 0:  omean' = omean + (d * w) / Wn;  oM2 = oM2 + (w * d) * (imean - omean')
+ *                      imean = iM2 = +0.0
+ *   merge (no open group on either side): d = omean_b - omean_a;  omean_a += d * (Wb / W);
+ *                      oM2_a = (oM2_a + oM2_b) + (d * d) * ((Wa * Wb) / W);  wS_a += wS_b, W = Wa + Wb (the
+ *                      expressions of ps_depend_merge); into a destination without groups a device copy
+ *   finalize (G >= 2, no open group), kinv = (sum w_g / k_g) / W from the host:
+ *                      vw = wS / W;  vm = oM2 / W;  vp = vm - vw * kinv;  if not (vp > 0): vp = +0.0
+ *                      tot = vp + vw;  share = tot > 0 ? vw / tot : +0.0
+ * vw is the variance over the wind at fixed parameters; vp the variance of the parameters' effect, the one-way
+ * random-effects estimate (the between-group variance less the share of the within-group variance that the
+ * group means of k_g draws carry) with the package's / W convention, clipped at 0.  One thread owns a pair of
+ * cells (16-byte accesses; the tail cell of the odd N*N has its own thread), one launch covers all pairs: no
+ * atomics, no LDS, and a pair where nothing changes is not stored. */
+typedef struct ps_nested ps_nested;
+int ps_nested_create(int device, int N, int nslot, ps_nested** out);
+/* One draw of the open group, value and arguments as ps_summary_add (same value bit for bit), weight 1.
+ * Enqueued on the solver's stream; no host synchronisation. */
+int ps_nested_add(ps_nested* h, ps_solver* s, int nslot, const int32_t* kind, const int32_t* idx,
+                  const double* stat_scale, const double* post_scale, const int32_t* use_delta, double negval);
+/* One draw whose values are the current outputs of a projection / a release plan (slot e takes Y_e), on the
+ * handle's stream behind the source's last operation.  PS_ERR_BAD_ARG: outputs, device or domain not the
+ * handle's; PS_ERR_STATE: a source without finished fields. */
+int ps_nested_add_project(ps_nested* h, ps_project* p);
+int ps_nested_add_sites(ps_nested* h, ps_sites* p);
+/* The open group becomes a closed group of weight >= 1.  PS_ERR_STATE: fewer than 2 draws in it. */
+int ps_nested_close(ps_nested* h, uint32_t weight);
+/* dst += src.  PS_ERR_BAD_ARG: null, the same handle, or handles that differ in device, domain or slots;
+ * PS_ERR_STATE: an open group on either side. */
+int ps_nested_merge(ps_nested* dst, ps_nested* src);
+/* vw, vp and share of the present groups.  PS_ERR_STATE: an open group, or fewer than 2 closed groups. */
+int ps_nested_finalize(ps_nested* h);
+/* total_weight: W; members: draws added; groups: G; open_draws: k; weight_per_draws: sum w_g / k_g */
+int ps_nested_info(ps_nested* h, double* total_weight, int64_t* members, int64_t* groups, int64_t* open_draws,
+                   double* weight_per_draws);
+/* One plane of one slot (synchronises): 0 imean, 1 iM2, 2 omean, 3 oM2, 4 wS at any time; 5 vw, 6 vp, 7 share
+ * after ps_nested_finalize -- PS_ERR_STATE once an add, close or merge has followed it. */
+int ps_nested_fetch(ps_nested* h, int slot, int what, double* out /* N*N */);
+int ps_nested_reset(ps_nested* h);
+/* measurement: HIP-event timing of the add launches and of the close launches */
+int ps_nested_prof(ps_nested* h, int enable, double* add_ms, int64_t* add_launches, double* close_ms,
+                   int64_t* close_launches);
+void ps_nested_destroy(ps_nested* h);
 
 /* ---- posterior peak maps: how high each cell gets, on which day, and for how many days it stays above ----
  * (no reference counterpart).  Per member reductions along time: max_s v_s is not linear, so neither E[max] nor

@@ -122,6 +122,7 @@ SIGNATURES = {
     'ps_model_mvn_cdf_values': (C.c_int, [_VP, C.c_double, C.c_double, C.c_double, C.c_double,
                                           C.c_double, C.c_double, _I32P, _F64P, C.c_int64]),
     'ps_chain_set_kernels_from_model': (C.c_int, [_VP, _VP, C.c_int, C.c_int]),
+    'ps_chain_set_kernels_from_model_indexed': (C.c_int, [_VP, _VP, _I32P, C.c_int]),
     'ps_solver_set_state_from_model': (C.c_int, [_VP, _VP, C.c_int]),
     'ps_model_export_device': (C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP, _VP, C.c_int64]),
     'ps_chain_set_kernels_device': (C.c_int, [_VP, C.c_int, _I64P, _I32P, _VP, _VP, _VP]),
@@ -247,6 +248,18 @@ SIGNATURES = {
     'ps_mcerr_reset': (C.c_int, [_VP]),
     'ps_mcerr_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P, _F64P, _I64P]),
     'ps_mcerr_destroy': (None, [_VP]),
+    'ps_nested_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(_VP)]),
+    'ps_nested_add': (C.c_int, [_VP, _VP, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P, C.c_double]),
+    'ps_nested_add_project': (C.c_int, [_VP, _VP]),
+    'ps_nested_add_sites': (C.c_int, [_VP, _VP]),
+    'ps_nested_close': (C.c_int, [_VP, C.c_uint32]),
+    'ps_nested_merge': (C.c_int, [_VP, _VP]),
+    'ps_nested_finalize': (C.c_int, [_VP]),
+    'ps_nested_info': (C.c_int, [_VP, _F64P, _I64P, _I64P, _I64P, _F64P]),
+    'ps_nested_fetch': (C.c_int, [_VP, C.c_int, C.c_int, _F64P]),
+    'ps_nested_reset': (C.c_int, [_VP]),
+    'ps_nested_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P, _F64P, _I64P]),
+    'ps_nested_destroy': (None, [_VP]),
     'ps_peak_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _F64P, C.POINTER(_VP)]),
     'ps_peak_add': (C.c_int, [_VP, _VP, C.c_int, _I32P, _I32P, _F64P, _F64P, _I32P, C.c_double, C.c_uint32]),
     'ps_peak_add_project': (C.c_int, [_VP, _VP, C.c_uint32]),

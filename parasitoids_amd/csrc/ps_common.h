@@ -220,6 +220,7 @@ int ps_solver_set_state_device_coo(ps_solver* s, const int* row, const int* col,
                                    int64_t nnz, int off);
 int ps_solver_dom_len_internal(ps_solver* s);
 int ps_solver_device_internal(ps_solver* s);
+hipStream_t ps_solver_stream_internal(ps_solver* s);   // the stream the chain and its kernel copies run on
 
 // the view of one solver record that ps_summary.hip accumulates (ps_solver_record_internal)
 struct PsRecordView {

@@ -43,7 +43,26 @@ struct ps_model {
   // scratch for mvn_cdf_values
   DevBuf<double> stamp;
   DevBuf<int> stampH;
+  // staging block of ps_chain_set_kernels_from_model_indexed: the chosen kernels of the pool, concatenated
+  DevBuf<int> grow, gcol;
+  DevBuf<double> gval;
+  DevBuf<long long> gdesc;           // per chosen kernel: first entry in the pool, first entry in the block, entries
+  PsLastOp staged;                   // the last operation on the staging block: a gather here, or a solver's copy out of it
 };
+
+// One block row per chosen kernel (blockIdx.y), grid-stride over its entries: the kernel's segment of the batch's
+// COO pool copied to its place in the staging block.
+__global__ void __launch_bounds__(256)
+    k_gather_kernels(const long long* __restrict__ desc, const int* __restrict__ srow, const int* __restrict__ scol,
+                     const double* __restrict__ sval, int* __restrict__ drow, int* __restrict__ dcol,
+                     double* __restrict__ dval) {
+  const long long src = desc[3 * blockIdx.y], dst = desc[3 * blockIdx.y + 1], n = desc[3 * blockIdx.y + 2];
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    drow[dst + i] = srow[src + i];
+    dcol[dst + i] = scol[src + i];
+    dval[dst + i] = sval[src + i];
+  }
+}
 
 // Gauss-Legendre half rules of Genz's BVU (published with MVNDST/TVPACK)
 static const double kW1[3] = {0.1713244923791705, 0.3607615730481384, 0.4679139345726904};
@@ -104,6 +123,12 @@ extern "C" int ps_model_create(ps_model** out, int device) {
     delete m;
     return ps_fail(PS_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e));
   }
+  e = m->staged.create();
+  if (e != hipSuccess) {
+    (void)hipStreamDestroy(m->stream);
+    delete m;
+    return ps_fail(PS_ERR_HIP, "hipEventCreate: %s", hipGetErrorString(e));
+  }
   *out = m;
   return PS_OK;
 }
@@ -117,11 +142,14 @@ extern "C" int ps_model_set_option(ps_model* m, const char* key, double value) {
 extern "C" int ps_model_destroy(ps_model* m) {
   if (!m) return PS_OK;
   (void)hipSetDevice(m->device);
+  m->staged.sync();   // a solver may still be copying out of the staging block
   if (m->stream) {
     (void)hipStreamSynchronize(m->stream);
     (void)hipStreamDestroy(m->stream);
   }
   ps_dev_quiesce();
+  m->staged.destroy();
+  m->grow.release(); m->gcol.release(); m->gval.release(); m->gdesc.release();
   m->wind.release(); m->day_keys.release(); m->day_idx.release(); m->start_time.release();
   m->hprob.release(); m->scratch.release(); m->pmf.release(); m->psum.release(); m->pmin.release();
   m->rowsum.release(); m->rowcnt.release(); m->rowoff.release(); m->doff.release(); m->rowrad.release();
@@ -480,6 +508,55 @@ extern "C" int ps_chain_set_kernels_from_model(ps_solver* s, ps_model* m, int fi
   for (int d = 0; d <= count; ++d) off[d] = m->off[first + d] - m->off[first];
   return ps_chain_adopt_device_kernels(s, count, off.data(), m->kshape.data() + first, m->orow.p + m->off[first],
                                        m->ocol.p + m->off[first], m->oval.p + m->off[first]);
+}
+
+// ps_chain_set_kernels with kernels idx[0..count) of the last batch, in that order, repeats allowed: many
+// sequences of days run over one batch of kernels.  One launch gathers the chosen segments of the COO pool into
+// the model's staging block on the model's stream; the solver's stream waits for it by event, copies the block
+// (ps_chain_adopt_device_kernels), and the next gather waits for that copy the same way: no host synchronisation
+// of its own.
+extern "C" int ps_chain_set_kernels_from_model_indexed(ps_solver* s, ps_model* m, const int32_t* idx, int count) {
+  if (!s || !m || count < 0 || (count > 0 && !idx)) return ps_fail(PS_ERR_BAD_ARG, "set_kernels_indexed: bad arguments");
+  if (count > 65535) return ps_fail(PS_ERR_BAD_ARG, "set_kernels_indexed: %d kernels, at most 65535", count);
+  for (int i = 0; i < count; ++i)
+    if (idx[i] < 0 || idx[i] >= m->nd) return ps_fail(PS_ERR_STATE, "day %d not in the last batch of %d", idx[i], m->nd);
+  if (ps_solver_device_internal(s) != m->device) return ps_fail(PS_ERR_BAD_ARG, "solver and model live on different devices");
+  for (int i = 0; i < count; ++i)
+    if (m->hinfo[idx[i]].status != 0) return ps_fail(m->hinfo[idx[i]].status, "day %d of the batch failed its checks", idx[i]);
+  std::vector<int64_t> off((size_t)count + 1, 0);
+  std::vector<int32_t> kshape((size_t)std::max(count, 1), 0);
+  std::vector<long long> desc((size_t)std::max(count, 1) * 3, 0);
+  int64_t longest = 0;
+  for (int i = 0; i < count; ++i) {
+    const int64_t n = m->off[idx[i] + 1] - m->off[idx[i]];
+    off[i + 1] = off[i] + n;
+    kshape[i] = m->kshape[idx[i]];
+    desc[3 * (size_t)i] = m->off[idx[i]];
+    desc[3 * (size_t)i + 1] = off[i];
+    desc[3 * (size_t)i + 2] = n;
+    longest = std::max(longest, n);
+  }
+  const int64_t tot = off[count];
+  PS_HIP(hipSetDevice(m->device));
+  PS_TRY(m->grow.ensure(std::max<int64_t>(tot, 1)));
+  PS_TRY(m->gcol.ensure(std::max<int64_t>(tot, 1)));
+  PS_TRY(m->gval.ensure(std::max<int64_t>(tot, 1)));
+  PS_TRY(m->gdesc.ensure(desc.size()));
+  hipStream_t ss = ps_solver_stream_internal(s);
+  if (tot > 0) {
+    PS_TRY(m->staged.wait(m->stream));   // the previous adoption's copy out of the block
+    // (no synchronisation: copies from pageable host memory are staged before hipMemcpyAsync returns)
+    PS_HIP(hipMemcpyAsync(m->gdesc.p, desc.data(), desc.size() * sizeof(long long), hipMemcpyHostToDevice, m->stream));
+    const unsigned bx = (unsigned)std::min<int64_t>((longest + 255) / 256, 64);
+    hipLaunchKernelGGL(k_gather_kernels, dim3(bx, count), dim3(256), 0, m->stream, m->gdesc.p, m->orow.p, m->ocol.p,
+                       m->oval.p, m->grow.p, m->gcol.p, m->gval.p);
+    PS_HIP(hipGetLastError());
+    PS_TRY(m->staged.mark(m->stream));
+    PS_TRY(m->staged.wait(ss));
+  }
+  PS_TRY(ps_chain_adopt_device_kernels(s, count, off.data(), kshape.data(), m->grow.p, m->gcol.p, m->gval.p));
+  if (tot > 0) PS_TRY(m->staged.mark(ss));
+  return PS_OK;
 }
 
 // ---- device-resident exchange of day kernels between ranks (days sharded over the GPUs, the

@@ -3253,6 +3253,7 @@ extern "C" int ps_solver_owner_fft(ps_solver* s, int owner) {
 
 int ps_solver_dom_len_internal(ps_solver* s) { return s->N; }
 int ps_solver_device_internal(ps_solver* s) { return s->device; }
+hipStream_t ps_solver_stream_internal(ps_solver* s) { return s->stream; }
 
 // ps_summary.hip: one record of s with the device statistics of its day.  The chain leaves the
 // statistics to ps_chain_stats (finalize_days); with want_stats the day's are finalised here, on the

@@ -191,6 +191,13 @@ class HipSolve():
         L.check(self._lib.ps_chain_set_kernels_from_model(self._h, model._h, int(first), int(count)))
         self._nk = int(count)
 
+    def set_kernels_from_model_indexed(self, model, idx):
+        '''Adopt kernels idx[0], idx[1], ... of the model's last batch, in that order and with repeats, as
+        the chain's day kernels, device to device: what set_kernels does with those kernels.'''
+        idx = L.i32(idx)
+        L.check(self._lib.ps_chain_set_kernels_from_model_indexed(self._h, model._h, L.p_i32(idx), len(idx)))
+        self._nk = len(idx)
+
     def set_state(self, A):
         '''Replace the Fourier-space solution by fft2(A) (what the constructor does,
         cuda_lib.py:34-54), keeping plans, buffers and uploaded kernels.'''

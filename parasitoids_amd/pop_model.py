@@ -43,8 +43,9 @@ class PopModel():
         self._solvers = {}
         self.model.close()
 
-    def _solver_for(self, max_shape):
-        """A solver whose torus holds kernels up to `max_shape`.  In exact mode the torus is the
+    def _solver_for(self, max_shape, first=0):
+        """A solver whose torus holds kernels up to `max_shape`, its state entry `first` of the model's last
+        batch.  In exact mode the torus is the
         reference's N + max_shape//2, so solvers are keyed by max_shape.  In fast mode any
         torus >= that works: the solver is created for the largest max_shape that still maps
         to the same FFT size, so one solver (plans + ~GBs of buffers) serves every evaluation
@@ -76,10 +77,10 @@ class PopModel():
         if s is None:
             if len(self._solvers) >= self._max_solvers:
                 self._solvers.pop(next(iter(self._solvers))).close()
-            s = self._hip.HipSolve.from_model(self.model, 0, [key, key], mode=self.mode,
+            s = self._hip.HipSolve.from_model(self.model, first, [key, key], mode=self.mode,
                                               device=self.device, chain_only=True)
         else:
-            s.set_state_from_model(self.model, 0)
+            s.set_state_from_model(self.model, first)
         self._solvers[key] = s          # most recently used last
         return s
 
@@ -103,6 +104,66 @@ class PopModel():
         self._stats = None
         if nd > 1:
             solver.set_kernels_from_model(self.model, 1, nd - 1)
+            solver.run_chain(0, nd - 1, negval=1e-8, scale=scale, renorm=self.prob_model)
+        if not want_stats:
+            return None
+        st0 = solver.record_stats(L.REC_STATE, 0, 1e-8, 1.0, False)
+        return [(st0.nnz, st0.sum * scale)] + [(s.nnz, s.sum) for s in self.stats]
+
+    def build_pool(self, hparams, Dparams, Dlparams, mu_r, n_periods, pool_days, first_days):
+        '''One device batch of day kernels for many sequences of days under the same parameters (weather
+        ensembles, predictive.wind_sequences): entries 0..D-1 are `pool_days` without a start time; where
+        `r_start` is not None one entry per distinct day of `first_days` follows, built with it -- a
+        sequence's release day.  `run_sequence` then runs any sequence over these days without building a
+        kernel again.  A day that fails its checks fails only the sequences that use it.'''
+        pool_days = list(pool_days)
+        firsts = []
+        if self.r_start is not None:
+            for d in first_days:
+                if d not in firsts:
+                    firsts.append(d)
+        starts = [None] * len(pool_days) + [self.r_start] * len(firsts)
+        kshape, _nnz, _warned, _status = self.model.build(
+            pool_days + firsts, hparams, Dparams, Dlparams, mu_r, n_periods, self.rad_dist, self.rad_res, starts)
+        index = {d: i for i, d in enumerate(pool_days)}
+        first = {d: len(pool_days) + j for j, d in enumerate(firsts)} if firsts else index
+        missing = [d for d in first_days if d not in first]
+        if missing:
+            raise ValueError('first day %r is not among the pool days %r' % (missing[0], pool_days))
+        self._pool = dict(batch=self.model.last, index=index, first=first, kshape=kshape, checked=False)
+
+    def check_pool(self):
+        '''Raise / warn like the reference for every entry of the last build_pool, once: a caller that must know
+        whether any sequence can fail before it runs the first.'''
+        for i in range(len(self._pool['kshape'])):
+            self.model.check(i)
+        self._pool['checked'] = True
+
+    def run_sequence(self, seq, want_stats=False):
+        '''One model evaluation over the days `seq` of the last `build_pool`: the state from the entry of
+        seq[0] as a release day, the other days' kernels adopted from the pool by index, the chain run as
+        `evaluate` runs it.  The solver is chosen by the largest kernel of this sequence, as an evaluation of
+        PopModel(days=seq) chooses it, so the reference torus of the exact and auto modes is the run's own.
+        Returns as `evaluate` does.'''
+        pool = getattr(self, '_pool', None)
+        if pool is None or pool['batch'] is not self.model.last:
+            raise ValueError('run_sequence needs the batch of the last build_pool; the model has built another since')
+        seq = list(seq)
+        try:
+            entries = [pool['first'][seq[0]]] + [pool['index'][d] for d in seq[1:]]
+        except (KeyError, IndexError):
+            raise ValueError('sequence %r leaves the days of the last build_pool' % (seq,))
+        if not pool['checked']:
+            for i in sorted(set(entries)):
+                self.model.check(i)
+        nd = len(entries)
+        solver = self._solver_for(int(pool['kshape'][entries].max()), entries[0])
+        self.solver = solver
+        scale = float(self.r_number)          # dist(1) = 1 for a one-day release
+        self._nd = nd
+        self._stats = None
+        if nd > 1:
+            solver.set_kernels_from_model_indexed(self.model, entries[1:])
             solver.run_chain(0, nd - 1, negval=1e-8, scale=scale, renorm=self.prob_model)
         if not want_stats:
             return None

@@ -77,6 +77,11 @@ numbers and release days; the posterior of the origin with the parameter uncerta
 members' own evidence as row log-weights for `reweight=`.  Inference about the past: it recommends nothing.  With
 `known=` the releases that are facts lie in the background of every finding, and `second_source()` says whether the
 findings need a second source or the known releases explain them.
+`wind_sequences` resamples the days of the wind record by a circular moving-block bootstrap and `posterior_predictive(
+wind=...)` evaluates every run under each sequence, over one batch of day kernels per run (`PopModel.build_pool`,
+`run_sequence`); `WeatherShare` keeps, on the device, the members in groups -- one parameter vector under several
+sequences -- and splits every cell's variance into the part over the wind and the parameters' own (ps_nested_*,
+csrc/ps_nested.hip): the one axis of uncertainty that no other map shows.
 """
 import ctypes as C
 import json
@@ -2499,11 +2504,12 @@ def exposure_plan(exposure, ndays=None):
 # 'apply' is the source's own.  The three orders differ for no better reason than the history of the maps.
 FEED_ORDER = {
     'days': ('summary', 'origin', 'core_range', 'reweight', 'reweight_histogram', 'reweight_arrival', 'catch', 'neighbourhood', 'proximity', 'information', 'excursion', 'mc_error',
-             'sensitivity', 'dependence', 'histogram', 'arrival', 'peak', 'patches', 'pathways', 'modes'),
-    'projection': ('apply', 'summary', 'reweight', 'reweight_histogram', 'mc_error', 'sensitivity', 'dependence', 'histogram', 'catch'),
+             'sensitivity', 'dependence', 'histogram', 'arrival', 'peak', 'patches', 'pathways', 'weather', 'modes'),
+    'projection': ('apply', 'summary', 'reweight', 'reweight_histogram', 'mc_error', 'sensitivity', 'dependence', 'histogram', 'catch',
+                   'weather'),
     'sites': ('apply', 'summary', 'reweight', 'reweight_histogram', 'reweight_arrival', 'mc_error', 'sensitivity',
               'dependence', 'histogram', 'arrival', 'peak', 'excursion', 'core_range', 'catch', 'neighbourhood', 'proximity', 'information', 'patches', 'pathways',
-              'modes'),
+              'weather', 'modes'),
     'compare': ('apply', 'contrast'),
     'ranking': ('apply', 'ranking'),
 }
@@ -2558,6 +2564,7 @@ FEED = {
     'pathways': _add_length,
     'modes': _add_length,
     'origin': _add_length,
+    'weather': lambda acc, fs, m: acc.add(),       # one draw of the run's group; the driver closes it with the length
 }
 ACCUMULATORS = tuple(name for name in FEED if name != 'apply')
 
@@ -2689,6 +2696,13 @@ def _build_origin(fs, q):
         return OriginMaps(fs._source, q.origin, fs._late)
 
 
+def _build_weather(fs, q):
+    '''the WeatherShare of a weather ensemble (wind= with share); None, and nothing built, without'''
+    plan = getattr(q, 'wind_plan', None)
+    if plan is not None and plan['share']:
+        return fs._over(WeatherShare, (fs._days,), ())
+
+
 def _reserve_modes(mp, nruns):
     '''room for a chain's runs before its first evaluation; where the device has not that much free, a ValueError
     that names the figure'''
@@ -2730,6 +2744,7 @@ BUILD = {
                                                    (q.pw_thr, q.pw_conn)),
     'modes': _build_modes,
     'origin': _build_origin,
+    'weather': _build_weather,
 }
 
 
@@ -4454,6 +4469,196 @@ def pool_mc_error(pairs):
         s.close()
     first.rhat = rhat
     return first
+
+
+# ------------------------------------------------------------------ weather ensembles
+WIND_KEYS = ('draws', 'block', 'seed', 'pool', 'sequences', 'share', 'pool_kernels')
+WEATHER_PLANES = {'imean': 0, 'iM2': 1, 'omean': 2, 'oM2': 3, 'wS': 4, 'vw': 5, 'vp': 6, 'share': 7}
+WEATHER_PARTS = {'weather': 5, 'parameter': 6}
+
+
+def _whole(value, name, least):
+    '''an integer >= least that is no bool -> int'''
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or value < least:
+        raise ValueError('wind: %s must be an integer >= %d, got %r' % (name, least, value))
+    return int(value)
+
+
+def wind_sequences(pool, ndays, draws, block=3, seed=0):
+    '''[draws, ndays] int: day keys resampled from `pool` -- the sorted distinct day keys of a wind record, at
+    least 2 -- by the circular moving-block bootstrap (Politis & Romano 1992).  A draw is made of blocks of `block`
+    consecutive pool entries, the successor of the last pool day being the first; the block starts come from
+    numpy.random.Generator(PCG64(seed)).integers(0, len(pool)); the last block is cut to length.  block=1 gives
+    independent days.  The days keep the order and the repeats of one recorded season: no weather is generated.'''
+    keys = [int(d) for d in pool]
+    if len(keys) < 2 or any(b <= a for a, b in zip(keys, keys[1:])):
+        raise ValueError('wind: the pool must be at least 2 sorted distinct day keys, got %r' % (list(pool),))
+    ndays, draws, block = _whole(ndays, 'ndays', 1), _whole(draws, 'draws', 1), _whole(block, 'block', 1)
+    rng = np.random.Generator(np.random.PCG64(_whole(seed, 'seed', 0)))
+    nblock = -(-ndays // block)
+    starts = rng.integers(0, len(keys), size=(draws, nblock))
+    pos = (starts[:, :, None] + np.arange(block)[None, None, :]) % len(keys)
+    return np.asarray(keys, dtype=np.int64)[pos.reshape(draws, nblock * block)[:, :ndays]]
+
+
+def check_wind(arg, pop_model):
+    '''wind=dict(draws=8, block=3, seed=0, pool=None, sequences=None, share=True, pool_kernels=True) of
+    posterior_predictive against the model -> the plan: the same keys, `pool` the sorted distinct day keys drawn
+    from (default every day of the model's wind record), `sequences` [K, len(pop_model.days)] the day keys as
+    evaluated -- the user's rows where given, which replace the draws, else wind_sequences -- and `used`, the sorted
+    distinct days among them.  ValueError on a bad key, length, count or type, and on fewer than 2 sequences
+    while `share` is true (a variance within a group needs two draws).'''
+    if not isinstance(arg, dict) or set(arg) - set(WIND_KEYS):
+        raise ValueError('wind must be dict(%s), got %r' % (', '.join(WIND_KEYS), arg))
+    record = sorted(int(d) for d in pop_model.wind_data.keys())
+    ndays = len(pop_model.days)
+    plan = dict(draws=_whole(arg.get('draws', 8), 'draws', 1), block=_whole(arg.get('block', 3), 'block', 1),
+                seed=_whole(arg.get('seed', 0), 'seed', 0))
+    for flag in ('share', 'pool_kernels'):
+        if not isinstance(arg.get(flag, True), (bool, np.bool_)):
+            raise ValueError('wind: %s must be True or False, got %r' % (flag, arg[flag]))
+        plan[flag] = bool(arg.get(flag, True))
+
+    def keys_of(values, what):
+        try:
+            keys = [_whole(d, 'a day key of ' + what, min(record)) for d in values]
+        except TypeError:
+            raise ValueError('wind: %s must be a list of day keys, got %r' % (what, values))
+        off = [d for d in keys if d not in record]
+        if off:
+            raise ValueError('wind: day %r of %s is not in the wind record %r' % (off[0], what, record))
+        return keys
+    pool = record if arg.get('pool') is None else sorted(set(keys_of(arg['pool'], 'the pool')))
+    if len(pool) < 2:
+        raise ValueError('wind: the pool needs at least 2 distinct days, got %r' % (pool,))
+    plan['pool'] = pool
+    if arg.get('sequences') is None:
+        seqs = wind_sequences(pool, ndays, plan['draws'], plan['block'], plan['seed'])
+    else:
+        try:
+            rows = [list(r) for r in arg['sequences']]
+        except TypeError:
+            raise ValueError('wind: sequences must be rows of day keys, got %r' % (arg['sequences'],))
+        if not rows:
+            raise ValueError('wind: sequences is empty')
+        for r in rows:
+            if len(r) != ndays:
+                raise ValueError('wind: a sequence has %d days, the model %d' % (len(r), ndays))
+        seqs = np.asarray([keys_of(r, 'a sequence') for r in rows], dtype=np.int64)
+        plan['draws'] = len(rows)
+    if plan['share'] and len(seqs) < 2:
+        raise ValueError('wind: the weather share needs at least 2 sequences per run, got %d (share=False runs one)'
+                         % len(seqs))
+    plan['sequences'] = seqs
+    plan['used'] = sorted(set(int(d) for d in seqs.ravel()))
+    return plan
+
+
+class WeatherShare(_Accumulator):
+    '''How much of a cell's posterior spread is weather and how much is parameters, on the device (ps_nested_*,
+    csrc/ps_nested.hip).  The members come in groups: `add()` takes the model's last evaluation (of a projection:
+    its last apply) as one more draw of the open group -- one parameter vector under one more wind sequence --
+    and `close_group(weight)` closes the group with the run's weight; at least 2 draws per group and 2 groups.
+    `variance(day, 'weather')` is the variance over the wind at fixed parameters, the weighted mean of the groups'
+    own sample variances; `variance(day, 'parameter')` the variance of the group means less what their k_g draws
+    of weather leave in them, the one-way random-effects estimate with the package's / W convention, clipped at 0;
+    `share(day)` the weather's part of their sum.  days as SpreadSummary; of `for_projection` the output index.'''
+    _prefix, _noun, _prof_pairs = 'ps_nested', 'weather share', 2
+    _info_types = (C.c_double, C.c_int64, C.c_int64, C.c_int64, C.c_double)   # W, members, groups, open draws, sum w/k
+
+    def __init__(self, pop_model, days=None):
+        self._setup(pop_model, _model_days(pop_model, days), None)
+
+    @classmethod
+    def for_projection(cls, projection):
+        '''The split of the outputs of `projection` (a Projection or a ReleaseSites), one slot per output that
+        carries weight: `add()` takes the outputs of its last `apply()`.'''
+        self = cls.__new__(cls)
+        self._setup(projection.pm, list(range(projection.nout)), projection)
+        return self
+
+    def _setup(self, pop_model, days, projection):
+        self._attach(pop_model)
+        self._set_source(projection, days, projection and projection.live)
+        self.nbytes = len(self._slot) * self.pitch * 64        # eight fp64 planes
+        self._final = False
+        self._create(len(self._slot))
+
+    def add(self):
+        '''one more draw of the open group, weight 1; no host synchronisation'''
+        self._read('add', self._proj)
+        self._final = False
+
+    def close_group(self, weight=1):
+        '''the open group (>= 2 draws) becomes a closed group of integer weight >= 1'''
+        self._call('close', self._weight(weight))
+        self._final = False
+
+    def merge(self, other):
+        '''self += other (same device, domain and days; no open group on either side)'''
+        if list(other.days) != self.days or other._slot != self._slot:
+            raise ValueError('weather shares over different days')
+        self._call('merge', other._h)
+        self._final = False
+
+    def reset(self):
+        self._call('reset')
+        self._final = False
+
+    @property
+    def groups(self):
+        return self._info()[2]
+
+    @property
+    def open_draws(self):
+        return self._info()[3]
+
+    def plane(self, day, what):
+        '''[N, N] float64: a raw plane by name (WEATHER_PLANES); 'vw', 'vp' and 'share' are finalized first'''
+        code = WEATHER_PLANES[what] if what in WEATHER_PLANES else self._index(what, 8, 'plane')
+        slot = self._slot_of(day)
+        if slot is None:
+            return np.zeros((self.N, self.N), dtype=np.float64)
+        if code >= 5 and not self._final:
+            self._call('finalize')
+            self._final = True
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        self._call('fetch', slot, code, L.p_f64(out))
+        return out
+
+    def mean(self, day):
+        '''the weighted mean of the groups' means'''
+        return self.plane(day, 'omean')
+
+    def variance(self, day, part='total'):
+        '''part: 'weather' | 'parameter' | 'total', the sum of the two'''
+        if part == 'total':
+            return self.plane(day, 'vp') + self.plane(day, 'vw')
+        if part not in WEATHER_PARTS:
+            raise ValueError("part must be 'weather', 'parameter' or 'total', got %r" % (part,))
+        return self.plane(day, WEATHER_PARTS[part])
+
+    def share(self, day):
+        '''weather / total; 0 where the total is 0'''
+        return self.plane(day, 'share')
+
+    def profile(self, enable=None):
+        '''HIP-event time of the add and of the close launches: (add ms, add launches, close ms, close launches)'''
+        return self._profile(enable)
+
+
+def weather_block(ws, keys, labels, prefix, mean_of, maps):
+    '''The json block of one WeatherShare -- groups, members, total weight and per day the mean-weighted share
+    sum(share mean) / sum(mean), mean_of(key) the summary's mean map -- its maps appended to `maps` as save_maps
+    takes them: per day `{prefix}{label}` with `_vw`, `_vp` and `_share`.'''
+    shares = {}
+    for key, label in zip(keys, labels):
+        share, mean = ws.share(key), mean_of(key)
+        maps.append(('%s%s' % (prefix, label), [('_vw', ws.variance(key, 'weather')),
+                                                ('_vp', ws.variance(key, 'parameter')), ('_share', share)]))
+        total = float(mean.sum())
+        shares[str(label)] = float((share * mean).sum() / total) if total > 0 else 0.0
+    return {'groups': ws.groups, 'members': ws.members, 'total_weight': ws.total_weight, 'weather_share': shares}
 
 
 # ------------------------------------------------------------------ reweighting for new observations
@@ -7533,7 +7738,9 @@ class PredictiveResult():
     compare= and `compare_plan` that plan (ReleaseSites.describe()), both None where not asked for; `ranking`: the
     PlanRanking of the release plan and the further plans of ranking=, `ranking_plans` all of them, plan A's first
     (ReleaseSites.describe()), and `ranking_levels` the levels of its saved area quantiles, all None where not
-    asked for; `mc_error`:
+    asked for; `weather`: the WeatherShare over the summary's days of a weather ensemble (wind= with share; the
+    projections and the plan carry one of their own) and `wind` its plan as evaluated (pool, block, seed, the
+    sequences, host seconds of the kernel batches and the draws), both None without wind=; `mc_error`:
     the MonteCarloError over the summary's days, all chains' half sequences pooled in chain order, its `rhat`
     their split R-hat maps, and `mc_plan` = dict(batches, batch_weight, sequences), both None where not asked for
     (the projections and the plan then carry an `mc_error` of their own); `peak`: the PeakPosterior over the
@@ -7575,7 +7782,9 @@ class PredictiveResult():
                  representative=None, representative_days=None, representative_chains=None, neighbourhood=None,
                  modes=None, dependence=None, pathways=None, pathway_levels=None, proximity=None, origin=None,
                  reweight_histogram=None, reweight_arrival=None, ranking=None, ranking_plans=None,
-                 ranking_levels=None):
+                 ranking_levels=None, weather=None, wind=None):
+        self.weather = weather
+        self.wind = wind
         self.ranking = ranking
         self.ranking_plans = ranking_plans
         self.ranking_levels = ranking_levels
@@ -7701,6 +7910,11 @@ class PredictiveResult():
         outfile_sites_repr.npz), their block under `predictive.representative` (`predictive.sites.representative`).
         Ensemble modes go into outfile_modes.npz (save_modes; those of a release plan into outfile_sites_modes.npz),
         their block under `predictive.modes` (`predictive.sites.modes`).
+        A weather ensemble's split goes into outfile_weather.npz: per day `{label}_vw_*`, `{label}_vp_*` and
+        `{label}_share_*` (the variance over the wind, the parameters' and the weather's share), those of a
+        projection or a plan under the labels `NAME_{label}`; under `predictive.wind` of the json the pool, block,
+        seed and sequences as evaluated, the groups, the members and per day the mean-weighted share
+        sum(share mean) / sum(mean) (`predictive.wind.NAME` for a projection or a plan).
         -> (npz path, json path)'''
         s = self.summary
         if s is None:
@@ -7966,12 +8180,78 @@ class PredictiveResult():
                                                  ['x%d' % e for e in range(len(px.windows))], name + '_', mmaps)
             save_maps('%s_mcerr' % outfile, mmaps)
             meta['predictive']['mc_error'] = block
+        if self.wind is not None:
+            w = self.wind
+            block = {'pool': list(w['pool']), 'block': w['block'], 'seed': w['seed'], 'share': w['share'],
+                     'pool_kernels': w['pool_kernels'], 'sequences': np.asarray(w['sequences']).tolist()}
+            if self.weather is not None:
+                wmaps = []
+                labels = [s.pm.days[d] if d < len(s.pm.days) else d for d in s.days]
+                block.update(weather_block(self.weather, s.days, labels, '', s.mean, wmaps))
+                for name, pr in (('emergence', self.emergence), ('exposure', self.exposure), ('sites', self.sites)):
+                    if pr is not None and pr.weather is not None:
+                        block[name] = weather_block(pr.weather, list(range(len(pr.labels))), pr.labels, name + '_',
+                                                    pr.summary.mean, wmaps)
+                save_maps('%s_weather' % outfile, wmaps)
+            meta['predictive']['wind'] = block
         with open(str(outfile) + '.json', 'w') as fobj:
             json.dump(meta, fobj, default=str)
         return str(outfile) + '.npz', str(outfile) + '.json'
 
 
-def _evaluate_runs(pm, rows, run_list, model_cols, evaluate, want_obs, locinfo, sets=()):
+def _evaluate_wind_run(pm, theta, first, length, wind, sets):
+    '''One run of a chain under every wind sequence of the checked wind= plan: one batch of day kernels for the
+    days the sequences use (PopModel.build_pool), every entry checked before the first sequence runs -- a run with
+    a failing day is a failed member and is added nowhere -- then per sequence the chain (run_sequence; with
+    pool_kernels=False an evaluation of the model over days=sequence, the A/B leg) and every set's feed with the
+    run's length, and after the last the close of the run's group in every WeatherShare.  -> False for a failed
+    member.  wind['build_s'] / wind['draw_s'] collect the host time of the builds (which end in a synchronise) and
+    of the enqueueing of the draws.'''
+    args = mcmc.model_args(theta)
+    seqs = wind['sequences']
+    recorded = pm.days
+
+    def parameter_failure(e):
+        return isinstance(e, (AssertionError, ValueError)) or (isinstance(e, L.HipError)
+                                                               and e.code in mcmc._PARAMETER_ERRORS)
+    t0 = time.perf_counter()
+    try:
+        pm.build_pool(*args, wind['used'], [int(s[0]) for s in seqs])
+        pm.check_pool()
+    except (AssertionError, ValueError, L.HipError) as e:
+        if not parameter_failure(e):
+            raise
+        return False
+    t1 = time.perf_counter()
+    wind['build_s'].append(t1 - t0)
+    for j, seq in enumerate(seqs):
+        try:
+            if wind['pool_kernels']:
+                pm.run_sequence([int(d) for d in seq])
+            else:
+                pm.days = [int(d) for d in seq]
+                try:
+                    pm.evaluate(*args, want_stats=False)
+                finally:
+                    pm.days = recorded
+        except (AssertionError, ValueError, L.HipError) as e:
+            if not parameter_failure(e):
+                raise
+            if j == 0:
+                return False
+            raise RuntimeError('wind: draw %d of the run at row %d failed after %d draws of it were added (%s)'
+                               % (j, first, j, e))
+        member = types.SimpleNamespace(theta=theta, first=first, length=length, lam=None)
+        for fs in sets:
+            fs.feed(member)
+    for fs in sets:
+        if getattr(fs, 'weather', None) is not None:
+            fs.weather.close_group(length)
+    wind['draw_s'].append(time.perf_counter() - t1)
+    return True
+
+
+def _evaluate_runs(pm, rows, run_list, model_cols, evaluate, want_obs, locinfo, sets=(), wind=None):
     '''one chain: evaluate every run and feed it to the chain's sets (_FieldSet) in the order given, each in the
     FEED_ORDER of its kind.  With a 'sites' set the models of the plan's later release days are evaluated with the
     base model -- with a 'compare' or 'ranking' set those of all plans' (its `lagged`), each once -- and a member for which any
@@ -7979,7 +8259,8 @@ def _evaluate_runs(pm, rows, run_list, model_cols, evaluate, want_obs, locinfo, 
     hypotheses' later release days are evaluated too; a model the plan shares is evaluated once, over the days its
     longest reader needs.  The solver's FFT size follows the days evaluated, so where the findings reach further than
     the plan's output days the plan's maps can differ in their last bits from a run without origin= (never where
-    the plan needs at least as many days).  -> (expected per run or None, failed)'''
+    the plan needs at least as many days).  wind: the checked plan of wind=; every run is then evaluated under each of
+    its sequences (_evaluate_wind_run) and a member is (run, draw).  -> (expected per run or None, failed)'''
     expected = []
     failed = 0
     kinds = {fs._kind: fs for fs in sets}
@@ -7989,6 +8270,11 @@ def _evaluate_runs(pm, rows, run_list, model_cols, evaluate, want_obs, locinfo, 
     origin = getattr(kinds.get('days'), 'origin', None)
     for first, length in run_list:
         theta = rows[first, model_cols]
+        if wind is not None:
+            ok = _evaluate_wind_run(pm, theta, first, length, wind, sets)
+            failed += not ok
+            expected.append(True if ok else None)
+            continue
         if evaluate is not None:
             exp = evaluate(theta)
             if exp is None:
@@ -8152,6 +8438,25 @@ def _check_request(q):
         check_contrast_thresholds(thresholds)
         if pm0 is None:
             q.rk_plan = None
+    q.wind_plan = None
+    if getattr(q, 'wind', None) is not None:          # a weather ensemble: what it cannot go with, then its own plan
+        season = 'its observations belong to the recorded season'
+        single = 'its member counts and chain rows assume one member per run'
+        for name, why in (('evaluate', 'it needs the device'), ('locinfo', season), ('reweight', season),
+                          ('origin', season), ('mc_error', single), ('representative', single),
+                          ('sensitivity', single), ('dependence', single)):
+            arg = getattr(q, name, None)
+            if arg is not None and arg is not False:
+                raise ValueError('wind= does not go with %s=: %s' % (name, why))
+        if pm0 is None:
+            raise ValueError('wind= needs a PopModel')
+        q.wind_plan = check_wind(q.wind, pm0)
+        late = [('sites', q.site_plan[2] if q.site_plan else ()), ('compare', q.cmp_plan[2] if q.cmp_plan else ())]
+        late += [('ranking', ranked[2]) for ranked in (q.rk_plan['plans'] if q.rk_plan else ())]
+        for name, lags in late:
+            if any(int(lag) > 0 for lag in lags):
+                raise ValueError('wind= does not go with a plan of %s= that releases after day 0: the models of '
+                                 'the later release days carry their own wind' % name)
     chains = q.chains
     if isinstance(chains, (str, os.PathLike)) or (isinstance(chains, tuple) and len(chains) == 2
                                                    and not isinstance(chains[0], (str, os.PathLike, tuple))):
@@ -8266,7 +8571,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                          sensitivity=None, compare=None, mc_error=None, peak=None, excursion=None, reweight=None,
                          catch=None, information=None, core_range=None, patches=None, representative=None,
                          neighbourhood=None, modes=None, dependence=None, pathways=None, proximity=None,
-                         origin=None, ranking=None):
+                         origin=None, ranking=None, wind=None):
     '''Posterior predictive spread of one or more chains (`Sampler.save` files or (trace, names) pairs). Burn and
     thin apply per chain; consecutive rows with identical model parameters are one evaluation weighted by the
     run's length.
@@ -8515,7 +8820,27 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         Carlo error of these maps and a search for where to put a trap are not computed.  With sites= a lagged
         model that the plan shares is evaluated once over the days its longest reader needs; where the findings
         reach further than the plan, the plan's maps can differ in their last bits from a run without origin=.
-        Without origin= nothing is built and `origin` is None.'''
+        Without origin= nothing is built and `origin` is None.
+
+    wind: dict(draws=8, block=3, seed=0, pool=None, sequences=None, share=True, pool_kernels=True) (check_wind; bad
+        arguments fail before any evaluation), a weather ensemble: every map above answers "what if we release like
+        this?" under the one recorded order of the wind, and this evaluates every run under `draws` orders of it --
+        circular moving-block bootstrap draws of the pool's days (wind_sequences), or the `sequences` given, rows of
+        day keys of the model's length ("last year's order", a second season added to wind_data).  Per run one
+        batch of day kernels is built for the days the sequences use (PopModel.build_pool) and every sequence runs
+        its chain over it (run_sequence; pool_kernels=False evaluates the model over days=sequence instead, the A/B
+        leg); every set is fed every draw with the run's length, so a member is (run, draw) and the summary's maps
+        are those of the joint ensemble.  With share each set also fills a WeatherShare -- one draw per sequence,
+        the group closed with the run's length -- merged in chain order into `weather` (and `sites.weather`, ...):
+        the variance over the wind at fixed parameters, the parameters' own and the weather's share of their sum.
+        A run with a failing day under any sequence is a failed member and is added nowhere.  Not with evaluate=,
+        locinfo=, reweight= or origin= (their observations belong to the recorded season), mc_error=,
+        representative=, sensitivity= or dependence= (they assume one member per run), nor with a plan that
+        releases after day 0 (the models of the later release days carry their own wind).  Resampling 18 or 30
+        recorded days says what a reordering and repetition of that season's weather would do; it is no
+        climatology and nothing is generated -- a longer wind_data is the remedy.  A day's kernel keeps the record's
+        own next day for its last periods, whatever follows it in a sequence.  `wind`: the plan as evaluated.
+        Without wind= no call is added, `weather` is None and every saved file is what it was.'''
     q = types.SimpleNamespace(**locals())
     t0 = time.perf_counter()
     _check_request(q)                 # bad arguments fail before any evaluation
@@ -8525,6 +8850,9 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     late = {}                                  # per model the models of the plans' later release days
     results = [None] * nch
     errs = []
+    wind_plan = q.wind_plan
+    if wind_plan is not None:                  # the host time of the runs' kernel batches and of their draws
+        wind_plan = dict(wind_plan, build_s=[], draw_s=[])
 
     def work(p):
         try:
@@ -8539,8 +8867,10 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                             lags |= set(ranked[2])
                         lags |= set(q.or_plan['model_lags'] if q.or_plan else ())   # the known lags among them
                         late[p] = lagged_models(pm, sorted(lags))
-                    _build_sets(chain_sets[ci], q, pm, ci, len(rl), late.get(p))
-                results[ci] = _evaluate_runs(pm, rows, rl, mcols, evaluate, q.want_obs, locinfo, chain_sets[ci])
+                    draws = len(wind_plan['sequences']) if wind_plan else 1     # a member is (run, draw)
+                    _build_sets(chain_sets[ci], q, pm, ci, len(rl) * draws, late.get(p))
+                results[ci] = _evaluate_runs(pm, rows, rl, mcols, evaluate, q.want_obs, locinfo, chain_sets[ci],
+                                             wind_plan)
         except BaseException as e:       # re-raised in the caller's thread
             errs.append((p, e))
 
@@ -8580,7 +8910,8 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
             raise
     if q.md_plan is not None:         # the members are those of run_rec below
         md_runs = [(ci, first, length) for ci, p in enumerate(prepared)
-                   for (first, length), e in zip(p[1], results[ci][0]) if e is not None]
+                   for (first, length), e in zip(p[1], results[ci][0]) if e is not None
+                   for _draw in range(len(wind_plan['sequences']) if wind_plan else 1)]
         for fs in (day, merged.get('sites')):
             if fs is not None and fs.modes is not None:
                 fs.modes.runs, fs.modes.chains = md_runs, [p[0][:, p[2]] for p in prepared]
@@ -8644,7 +8975,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         pathway_levels=q.pw_levels if q.pw_thr else None, proximity=day.proximity, origin=day.origin,
         reweight_histogram=day.reweight_histogram, reweight_arrival=day.reweight_arrival,
         ranking=ranked.ranking, ranking_plans=ranked.plan,
-        ranking_levels=q.rk_plan['levels'] if q.rk_plan else None)
+        ranking_levels=q.rk_plan['levels'] if q.rk_plan else None, weather=day.weather, wind=wind_plan)
     if day.information is not None:   # the stated convention: past cap / 2 the ensemble bounds the map
         warn_information(day.information)
         if 'sites' in merged:

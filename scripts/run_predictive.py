@@ -85,6 +85,14 @@ Without --chain a short chain is sampled first (--samples) and saved next to --o
         [--modes [K]] [--modes-days d1,d2|all] [--modes-transform sqrt|raw]
         [--origin 'EAST,NORTH,DAY,KIND,RATE[,N];...'] [--origin-amounts 0.1,1,10] [--origin-lags 0,2]
         [--origin-levels 0.5,0.95] [--origin-prior file.npy] [--origin-known 'EAST,NORTH,AMOUNT[,LAG];...' | sites]
+        [--wind-draws K] [--wind-block 3] [--wind-seed 0] [--wind-pool d1,d2,...] [--wind-plain]
+
+With --wind-draws K a weather ensemble: every run is evaluated under K orders of the wind record, drawn by a circular
+moving-block bootstrap (--wind-block days per block, --wind-seed, --wind-pool the days drawn from), over one batch of
+day kernels per run (--wind-plain: every sequence as a model of its own, the A/B leg); the maps are those of the joint
+ensemble, PREFIX_weather.npz holds per day the variance over the wind, the parameters' own and the weather's share,
+and the line gains wind_build_ms_per_run, wind_ms_per_member and weather_ms_per_member.  The observation-level
+predictive is left out: the observations belong to the recorded order.
 
 With --origin the origin maps: for findings 'EAST,NORTH,DAY,KIND,RATE[,N]' (metres from the domain centre, model day,
 count | none | found, the rate and for a count the number found) the posterior of where, when (--origin-lags) and in
@@ -154,6 +162,13 @@ def main():
     ap.add_argument('--thresholds', default='1,10')
     ap.add_argument('--out', default='predictive_out/pp')
     ap.add_argument('--synthetic', action='store_true')
+    ap.add_argument('--wind-draws', type=int, default=0,
+                    help='weather ensemble: every run under K resampled orders of the wind record (default: off)')
+    ap.add_argument('--wind-block', type=int, default=3, help='days per block of the moving-block bootstrap')
+    ap.add_argument('--wind-seed', type=int, default=0)
+    ap.add_argument('--wind-pool', default='', help='day keys d1,d2,... drawn from (default: the whole record)')
+    ap.add_argument('--wind-plain', action='store_true',
+                    help='evaluate every sequence as a model of its own instead of over one batch of kernels (A/B)')
     ap.add_argument('--chains-parallel', action='store_true',
                     help='one PopModel and host thread per chain (mcmc.run_parallel style)')
     ap.add_argument('--samples', type=int, default=60, help='without --chain: length of the chain sampled first')
@@ -468,9 +483,15 @@ def main():
         if rw_maps:
             reweight['options'] = dict(maps=tuple(rw_maps))
         rw_plan = check_reweight(reweight, pm.rad_dist, pm.rad_res, len(days))
+    wind = None
+    if args.wind_draws:                  # a bad pool or count fails before any evaluation (check_wind)
+        wind = dict(draws=args.wind_draws, block=args.wind_block, seed=args.wind_seed,
+                    pool=[int(d) for d in args.wind_pool.split(',') if d.strip()] or None,
+                    pool_kernels=not args.wind_plain)
     t0 = time.perf_counter()
     res = posterior_predictive(pms if len(pms) > 1 else pm, chains, burn=args.burn, thin=args.thin,
-                               thresholds=thr, locinfo=li, cell_area=cell_area, seed=args.seed,
+                               thresholds=thr, locinfo=None if wind else li, cell_area=cell_area, seed=args.seed,
+                               **({'wind': wind} if wind else {}),
                                quantiles=levels or None, bins=bins, arrival=arrival or None, arrival_levels=a_levels,
                                emergence=emergence, exposure=exposure, sites=sites, sensitivity=sens,
                                compare=compare, mc_error=mc_error, peak=peak, excursion=excursion,
@@ -577,6 +598,11 @@ def main():
         IC = CatchFields(pm, [(t[0], t[1], 1 + k % 16) for e, t in enumerate(IF.traps) for k in range(t[2] + 3)][:32])
         IF.profile(True)
         IC.profile(True)
+    WS = None
+    if wind:                             # the draw and the close of the variance split, beside the summary's add
+        from parasitoids_amd.predictive import WeatherShare
+        WS = WeatherShare(pm)
+        WS.profile(True)
     with SpreadSummary(pm, None, thr) as S:
         S.profile(True)
         if H is not None:
@@ -618,6 +644,10 @@ def main():
                 except Exception:
                     continue
                 S.add(length)
+                if WS is not None:       # groups of two draws: the timing does not depend on what the draws are
+                    WS.add()
+                    if WS.open_draws == 2:
+                        WS.close_group(length)
                 if RG is not None:
                     RG.add(length)
                 if CF is not None:
@@ -672,6 +702,10 @@ def main():
                     XR.add(length)
                 n += 1
         ms, launches = S.profile()
+    if WS is not None:
+        ws_ms, ws_adds, ws_close_ms, ws_closes = WS.profile()
+        ws_bytes = WS.nbytes
+        WS.close()
     if H is not None:
         h_ms, h_launches = H.profile()[:2]
         H.close()
@@ -788,6 +822,20 @@ def main():
            'days': nday, 'thresholds': thr, 'chains': len(chains), 'chains_parallel': len(pms) > 1,
            'bayes_evaluations_per_hour': None if bayes_rate is None else round(bayes_rate, 1),
            'outputs': [npz, js]}
+    if wind:                             # a member is (run, draw); the builds' host time ends in a synchronise
+        w = res.wind
+        members = (res.evaluations - res.failed) * len(w['sequences'])
+        out['wind_draws'] = len(w['sequences'])
+        out['wind_pool_kernels'] = w['pool_kernels']
+        out['wind_members'] = members
+        out['runs_per_hour'] = out['value']
+        out['value'] = out['wind_members_per_hour'] = round(3600.0 * members / dt, 1)
+        out['wind_ms_per_member'] = round(1e3 * dt / max(members, 1), 4)
+        out['wind_build_ms_per_run'] = round(1e3 * sum(w['build_s']) / max(len(w['build_s']), 1), 4)
+        out['weather_ms_per_member'] = round(ws_ms / max(ws_adds, 1), 4)
+        out['weather_close_ms_per_run'] = round(ws_close_ms / max(ws_closes, 1), 4)
+        out['weather_bytes'] = ws_bytes
+        out['outputs'] += ['%s_weather.npz' % args.out]
     if catch:
         out['catch_ms_per_member'] = round(cf_ms / max(cf_launches, 1), 4)
         out['catch_launches_timed'] = cf_launches
