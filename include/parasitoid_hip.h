@@ -1634,6 +1634,54 @@ int ps_overlap_prof(ps_overlap* h, int enable, double* pairs_ms, int64_t* pairs_
                     int64_t* subset_n);
 void ps_overlap_destroy(ps_overlap* h);
 
+/* ---- reweighted excursion regions: the excursion functions under one real weight per member ----
+ * (no reference counterpart.)  The excursion functions of a ps_excur rest on the members' integer weights.  New
+ * findings give every member a real weight (importance reweighting), and everything the functions need is a function
+ * of the kept masks and those weights: no member is evaluated again, and the weights may be chosen after the run.
+ * Setting: one plane (threshold k, slot) of a ps_excur, members m = 0..M-1 in add order, w_m >= 0 finite, not all 0.
+ * Every line is a statement of its own; there is no multiply, so nothing contracts:
+ *   W = w_0 + w_1 + ... in add order, from 0.0
+ *   C(c) = 0.0, then for m = 0, 1, ...: C += w_m where bit_m(c) is set; one writer per cell
+ *   hi_m = max{C(c) : bit_m(c) = 0, c a real cell}, 0.0 if there is none
+ *   lo_m = min{C(c) : bit_m(c) = 1}, +inf if the mask is empty
+ *   u(c) = min(C, W - C)
+ *   above   A+(c) = sum_m w_m [hi_m < C],                  0 where C == 0
+ *   below   A-(c) = sum_m w_m [lo_m > C]
+ *   contour Ac(c) = sum_m w_m [hi_m < W - u and lo_m > u], 0 where u + u >= W
+ *   each sum over the members in add order from 0.0; every map is A / W, one division; prob is C / W
+ * A member of weight 0 keeps its mask and its bounds and adds 0.  Non-negative doubles order like their bit
+ * patterns: the bounds are integer maxima and minima of 64-bit words, so no order of waves changes a bit.  With
+ * w_m the integer weights of the members, C, hi, lo (its "none" as +inf) and the three maps are those of the
+ * ps_excur, bit for bit.
+ * State: the handle borrows the ps_excur -- the caller keeps it alive -- and owns a stream, two fp64 planes of the
+ * pitch (C and the map scratch) and 3 x members x 8 B (hi, lo, w; grown on demand, the free memory checked first).
+ * It keeps one current plane: the maps and fetches answer for it, and are refused (PS_ERR_STATE) once the ps_excur
+ * holds other members than when the plane was formed. */
+#define PS_WEXCUR_ABOVE 0
+#define PS_WEXCUR_BELOW 1
+#define PS_WEXCUR_CONTOUR 2
+#define PS_WEXCUR_PROB 3
+typedef struct ps_wexcur ps_wexcur;
+/* PS_ERR_BAD_ARG unless e is on `device` with domain N */
+int ps_wexcur_create(int device, int N, ps_excur* e, ps_wexcur** out);
+/* forms C and the bounds of plane (k, slot) under w[members] and keeps them as the current plane (synchronises).
+ * Refused, enqueuing nothing and keeping the current plane: PS_ERR_BAD_ARG for a plane out of range, members != e's
+ * members, a weight that is negative or not finite, or weights that are all 0; PS_ERR_STATE while e holds no member */
+int ps_wexcur_plane(ps_wexcur* h, int k, int slot, int64_t members, const double* w);
+int ps_wexcur_fetch_counts(ps_wexcur* h, double* out /* N*N */);
+/* either pointer may be NULL */
+int ps_wexcur_fetch_bounds(ps_wexcur* h, double* hi /* members */, double* lo /* members */);
+/* what = PS_WEXCUR_ABOVE / _BELOW / _CONTOUR / _PROB of the current plane (synchronises) */
+int ps_wexcur_map(ps_wexcur* h, int what, double* out /* N*N */);
+/* any pointer may be NULL; members and total_weight (W): of the current plane, 0 without one; bytes: the device
+ * memory held now */
+int ps_wexcur_info(ps_wexcur* h, int64_t* members, int64_t* bytes, double* total_weight);
+/* the integer weights the members of e were added with, in add order; PS_ERR_BAD_ARG for members != e's members */
+int ps_wexcur_member_weights(ps_wexcur* h, int64_t members, uint32_t* out /* members */);
+/* measurement: HIP-event timing of the count launches [0], the bounds [1] and the maps [2], as ps_excur_prof */
+int ps_wexcur_prof(ps_wexcur* h, int enable, double* ms /* 3 */, int64_t* launches /* 3 */);
+void ps_wexcur_destroy(ps_wexcur* h);
+
 /* ---- neighbourhood fields: the largest value of one member's field within r of each cell ----
  * (no reference counterpart; the neighbourhood maximum of Schwartz & Sobash 2017, whose ensemble statistics the
  * accumulators below then take.)  A handle lives on one device and holds nout outputs (1..32) over nin inputs

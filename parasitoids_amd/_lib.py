@@ -451,6 +451,15 @@ SIGNATURES = {
     'ps_overlap_info': (C.c_int, [_VP, _I64P, _I64P, _I32P]),
     'ps_overlap_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P, _F64P, _I64P]),
     'ps_overlap_destroy': (None, [_VP]),
+    'ps_wexcur_create': (C.c_int, [C.c_int, C.c_int, _VP, C.POINTER(_VP)]),
+    'ps_wexcur_plane': (C.c_int, [_VP, C.c_int, C.c_int, C.c_int64, _F64P]),
+    'ps_wexcur_fetch_counts': (C.c_int, [_VP, _F64P]),
+    'ps_wexcur_fetch_bounds': (C.c_int, [_VP, _F64P, _F64P]),
+    'ps_wexcur_map': (C.c_int, [_VP, C.c_int, _F64P]),
+    'ps_wexcur_info': (C.c_int, [_VP, _I64P, _I64P, _F64P]),
+    'ps_wexcur_member_weights': (C.c_int, [_VP, C.c_int64, C.POINTER(C.c_uint32)]),
+    'ps_wexcur_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P]),
+    'ps_wexcur_destroy': (None, [_VP]),
     'ps_modes_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_VP)]),
     'ps_modes_reserve': (C.c_int, [_VP, C.c_int64]),
     'ps_modes_set_window': (C.c_int, [_VP, C.c_int]),

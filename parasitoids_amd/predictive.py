@@ -64,6 +64,8 @@ of a detached focus, or by the growth of such a focus, and per member and day th
 of an `ExcursionMaps`, and the count plane of any selection of members (ps_overlap_*, csrc/ps_overlap.hip);
 `RepresentativeMembers` reads from it, in integers on the host, the inclusion depth of every member, the deepest
 member, the central band and k-medoids scenarios -- which single outcome is typical, which no summary map can say.
+`ReweightedExcursion` (`ExcursionMaps.reweighted`) gives, from the same masks and one log-weight per member, the
+excursion functions under new findings (ps_wexcur_*, csrc/ps_wexcur.hip), for a scenario chosen after the run.
 `NeighbourhoodFields` turns, on the device, one member's field into its largest value within a disc of each cell
 (ps_nbhd_*, csrc/ps_nbhd.hip); the existing accumulators take it per member (`NeighbourhoodPosterior`): the
 probability of at least t wasps somewhere within r metres, which no per-cell map gives.
@@ -820,6 +822,155 @@ class ExcursionMaps(_Accumulator):
     def profile(self, enable=None):
         '''HIP-event time of the add, finalize and map launches: (add ms, adds, finalize ms, finalizes, map ms,
         map launches); enable switches it'''
+        ms = np.zeros(3, dtype=np.float64)
+        n = np.zeros(3, dtype=np.int64)
+        self._call('prof', -1 if enable is None else int(bool(enable)), L.p_f64(ms), L.p_i64(n))
+        return float(ms[0]), int(n[0]), float(ms[1]), int(n[1]), float(ms[2]), int(n[2])
+
+    def reweighted(self, log_weights):
+        '''The ReweightedExcursion of these maps under one log-weight per member in add order (-inf: the member
+        drops out; ValueError for NaN, +inf, a wrong length or all -inf) -- OriginMaps.log_weights() per run, a
+        trap's log-likelihood per member, or any scenario chosen after the chains have run.  No member is evaluated
+        again.  It is closed with these maps, or by its own close().'''
+        rw = ReweightedExcursion(self, log_weights)
+        self._reweighted = [r for r in getattr(self, '_reweighted', []) if r._h] + [rw]
+        return rw
+
+    def close(self):
+        for rw in getattr(self, '_reweighted', []):       # they read these masks: first
+            rw.close()
+        self._reweighted = []
+        super().close()
+
+
+def excursion_member_weights(log_weights, run_lengths):
+    '''float64 [members]: w_m = n_m exp(l_m - max l), 0.0 at l_m = -inf -- the definition of
+    ReweightedArrival.member_weights; n_m the integer weight a member was added with.  ValueError for NaN, +inf, a
+    wrong length or where every log-weight is -inf.'''
+    import math
+    try:
+        lw = [float(v) for v in np.asarray(log_weights, dtype=np.float64).ravel()]
+    except (TypeError, ValueError):
+        raise ValueError('log_weights must be one number per member, got %r' % (log_weights,))
+    n = [int(v) for v in run_lengths]
+    if len(lw) != len(n):
+        raise ValueError('%d log-weights given, the excursion maps hold %d members' % (len(lw), len(n)))
+    if any(math.isnan(v) or v == math.inf for v in lw):
+        raise ValueError('the log-weights hold NaN or +inf')
+    ref = max(lw) if lw else -math.inf
+    if ref == -math.inf:
+        raise ValueError('every log-weight is -inf: no member is left with weight')
+    return np.array([0.0 if l == -math.inf else k * math.exp(l - ref) for l, k in zip(lw, n)], dtype=np.float64)
+
+
+class ReweightedExcursion(_Handle):
+    '''The excursion functions of an ExcursionMaps under one real weight per member, on the device (ps_wexcur_*,
+    csrc/ps_wexcur.hip): from the members' kept masks and w_m = n_m exp(l_m - max l) (excursion_member_weights) the
+    weighted count C_w, the members' bounds on it and `above`, `below`, `contour` with the meaning of ExcursionMaps',
+    every map a sum over the members in add order divided once by W = sum w_m.  With equal log-weights every map
+    holds the bits of the parent's; with members at -inf those of maps fed the other members only.  `weights`
+    [members] float64, `total` W (summed in add order) and `ess`, Kish's (sum w)^2 / sum w^2.  The object keeps the
+    plane (k, day) it formed last, so the maps of one plane cost one plane build.  It borrows the parent: after a
+    further add, merge or reset on the parent every call fails with a ValueError that says so -- the weights no
+    longer match the members; take a new `reweighted()`.'''
+    _prefix, _noun = 'ps_wexcur', 'reweighted excursion maps'
+    _info_types = (C.c_int64, C.c_int64, C.c_double)       # members of the current plane, bytes, its W
+
+    ABOVE, BELOW, CONTOUR, PROB = 0, 1, 2, 3
+
+    def __init__(self, excursion, log_weights):
+        if not isinstance(excursion, ExcursionMaps):
+            raise ValueError('excursion maps are reweighted over an ExcursionMaps, got %r' % (type(excursion).__name__,))
+        self.excursion = excursion
+        self._maps()
+        M = excursion.members
+        lw = np.asarray(log_weights, dtype=np.float64)
+        if lw.ndim != 1 or lw.shape[0] != M:
+            raise ValueError('%s log-weights given, the excursion maps hold %d members' % (lw.shape, M))
+        self._attach(excursion.pm)
+        self.thresholds, self.days = excursion.thresholds, excursion.days
+        self._create(excursion._h)
+        n = np.empty(M, dtype=np.uint32)
+        self._call('member_weights', M, n.ctypes.data_as(C.POINTER(C.c_uint32)))
+        self.run_lengths = n
+        self.log_weights = lw.copy()
+        try:
+            self.weights = excursion_member_weights(lw, n)
+        except ValueError:
+            self.close()
+            raise
+        total = 0.0
+        for w in self.weights:
+            total = total + float(w)
+        self.total = total
+        self.ess = float(self.weights.sum()) ** 2 / float((self.weights * self.weights).sum())
+        self._plane = None
+
+    def _maps(self):
+        if not self.excursion._h:
+            raise ValueError('the ExcursionMaps of these reweighted excursion maps are closed')
+        return self.excursion
+
+    @property
+    def nbytes(self):
+        '''the device memory the handle holds now'''
+        return self._info()[1]
+
+    def _form(self, k, day):
+        '''plane (k, day) as the handle's current plane'''
+        E = self._maps()
+        if E.members != self.weights.size:
+            raise ValueError('the excursion maps hold %d members, these weights are for %d: members were added, merged '
+                             'or reset since; take a new reweighted()' % (E.members, self.weights.size))
+        key = (E._k(k), E._slot_of(day))
+        if self._plane != key:
+            self._plane = None
+            self._call('plane', key[0], key[1], self.weights.size, L.p_f64(self.weights))
+            self._plane = key
+
+    def counts(self, k, day):
+        '''[N, N] float64 C_w: the weight of the members at or above t_k on `day`'''
+        self._form(k, day)
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        self._call('fetch_counts', L.p_f64(out))
+        return out
+
+    def bounds(self, k, day):
+        '''(hi, lo), each [members] float64 in add order: hi the largest C_w outside the member's mask (0: none), lo
+        the smallest inside it (+inf: the mask is empty)'''
+        self._form(k, day)
+        hi, lo = np.empty(self.weights.size), np.empty(self.weights.size)
+        self._call('fetch_bounds', L.p_f64(hi), L.p_f64(lo))
+        return hi, lo
+
+    def _map(self, k, day, what):
+        self._form(k, day)
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        self._call('map', what, L.p_f64(out))
+        return out
+
+    def prob(self, k, day):
+        '''[N, N] float64: C_w / W, the reweighted probability of >= t_k at the cell'''
+        return self._map(k, day, self.PROB)
+
+    def above(self, k, day):
+        '''[N, N] float64 F+ under the weights, as ExcursionMaps.above'''
+        return self._map(k, day, self.ABOVE)
+
+    def below(self, k, day):
+        '''[N, N] float64 F- under the weights, as ExcursionMaps.below'''
+        return self._map(k, day, self.BELOW)
+
+    def contour(self, k, day):
+        '''[N, N] float64 Fc under the weights, as ExcursionMaps.contour'''
+        return self._map(k, day, self.CONTOUR)
+
+    region = ExcursionMaps.region
+    areas = ExcursionMaps.areas
+
+    def profile(self, enable=None):
+        '''HIP-event time of the count, bounds and map launches: (count ms, launches, bounds ms, launches, map ms,
+        launches); enable switches it'''
         ms = np.zeros(3, dtype=np.float64)
         n = np.zeros(3, dtype=np.int64)
         self._call('prof', -1 if enable is None else int(bool(enable)), L.p_f64(ms), L.p_i64(n))
@@ -2760,6 +2911,8 @@ class _FieldSet():
             setattr(self, name, accumulators.get(name))
         self.plan = None
         self.representative = None     # the RepresentativeMembers over `excursion`, built once the chains are merged
+        self.reweight_excursion = None # {scenario: ReweightedExcursion} over `excursion`, likewise
+        self._rw_lam = None            # per member of `excursion` the run's log-weights, where those are built
         self._kind = self._name = self._source = self._against = self._days = self._half = self._rw_feed = None
         self._chain = self._late = None
         self._owns = False
@@ -2801,6 +2954,8 @@ class _FieldSet():
                 acc.reserve(nruns)
             if name == 'modes' and acc is not None:
                 _reserve_modes(acc, nruns)
+        if 'excursion' in _reweight_maps(q) and self.excursion is not None:
+            self._rw_lam = []
         return self
 
     def feed(self, m):
@@ -2808,6 +2963,8 @@ class _FieldSet():
             acc = getattr(self, name, None)
             if acc is not None or name == 'apply':
                 FEED[name](acc, self, m)
+        if self._rw_lam is not None:     # the excursion maps have taken the member: its log-weights, in add order
+            self._rw_lam.append([float(v) for v in m.lam])
 
     def merge(self, other):
         for name in ACCUMULATORS:
@@ -2815,6 +2972,8 @@ class _FieldSet():
             # the Monte Carlo error sequences are pooled (_merge_chains), as are a catch's own, not merged
             if name != 'mc_error' and mine is not None and theirs is not None:
                 mine.merge(theirs)
+        if self._rw_lam is not None and other._rw_lam is not None:      # as the excursion maps' members
+            self._rw_lam.extend(other._rw_lam)
 
     def close(self):
         if self.representative is not None:    # it reads the excursion maps: first
@@ -4666,7 +4825,7 @@ MAX_REWEIGHT_SCENARIOS = 4
 MAX_REWEIGHT_SLOTS = 32    # ps_wsum: the slots of one launch's descriptors
 PROBE_KINDS = ('count', 'none', 'found')
 DEFAULT_MIN_ESS = 50.0
-REWEIGHT_MAPS = ('quantiles', 'arrival')      # the 'maps' option of reweight=: what else is reweighted
+REWEIGHT_MAPS = ('quantiles', 'arrival', 'excursion')      # the 'maps' option of reweight=: what else is reweighted
 
 
 def check_scenarios(scenarios):
@@ -4805,7 +4964,7 @@ def reweight_diagnostics(row_log_weights):
 
 
 def check_reweight_maps(maps):
-    '''the 'maps' option of reweight=: a subset of REWEIGHT_MAPS ('quantiles', 'arrival') as a tuple in that order,
+    '''the 'maps' option of reweight=: a subset of REWEIGHT_MAPS ('quantiles', 'arrival', 'excursion') as a tuple in that order,
     () for None; ValueError otherwise'''
     if maps is None:
         return ()
@@ -7660,6 +7819,54 @@ def save_excursion(outfile, exc, levels=(0.9, 0.95)):
             'total_weight': exc.total_weight, 'cell_area': exc.cell_area, 'areas': areas}
 
 
+def save_reweight_excursion(outfile, rx, levels=(0.9, 0.95)):
+    '''outfile.npz of the ReweightedExcursion of every scenario ({name: ReweightedExcursion} over one ExcursionMaps)
+    through save_maps: per scenario index j and day of the maps, under the label `{day}_s{j}`, the CSR triplets
+    `{day}_s{j}_above{k}_*`, `{day}_s{j}_below{k}_*` and `{day}_s{j}_contour{k}_*`; dense int8
+    `{day}_s{j}_region{k}_{tag}` per level, as save_excursion's; `wexcur_counts` [scenarios, thresholds, days, N, N],
+    `wexcur_hi` / `wexcur_lo` [scenarios, thresholds, days, members] and `wexcur_weights` [scenarios, members], all
+    float64; `wexcur_scenarios` the names, `wexcur_thresholds`, `wexcur_days` and `days` -> its block for the json:
+    scenarios, thresholds, days, levels, cell area and per scenario members, total weight, ess and per threshold and
+    day the areas of ReweightedExcursion.areas'''
+    levels = check_excursion_levels(levels)
+    names = list(rx)
+    first = rx[names[0]]
+    nk = len(first.thresholds)
+    maps, extra, block = [], {}, {}
+    for j, name in enumerate(names):
+        R = rx[name]
+        areas = [[] for _ in range(nk)]
+        cnt, hi, lo = [], [], []
+        for k in range(nk):       # plane by plane: one plane build serves its maps, counts and bounds
+            cnt.append([]), hi.append([]), lo.append([])
+            for d in R.days:
+                Fp, Fm, Fc = R.above(k, d), R.below(k, d), R.contour(k, d)
+                maps.append(('%s_s%d' % (d, j), [('_above%d' % k, Fp), ('_below%d' % k, Fm), ('_contour%d' % k, Fc)]))
+                for p in levels:
+                    extra['%s_s%d_region%d_%s' % (d, j, k, level_tag(p))] = \
+                        (Fp >= p).astype(np.int8) - (Fm >= p).astype(np.int8)
+                areas[k].append({'day': d, 'levels': [
+                    {'level': p, 'above': float(int((Fp >= p).sum())) * R.cell_area,
+                     'below': float(int((Fm >= p).sum())) * R.cell_area,
+                     'band': float(int((Fc < p).sum())) * R.cell_area} for p in levels]})
+                cnt[k].append(R.counts(k, d))
+                b = R.bounds(k, d)
+                hi[k].append(b[0]), lo[k].append(b[1])
+        extra.setdefault('wexcur_counts', []).append(cnt)
+        extra.setdefault('wexcur_hi', []).append(hi)
+        extra.setdefault('wexcur_lo', []).append(lo)
+        extra.setdefault('wexcur_weights', []).append(R.weights)
+        block[name] = {'members': int(R.weights.size), 'total_weight': R.total, 'ess': R.ess, 'areas': areas}
+    for key in ('wexcur_counts', 'wexcur_hi', 'wexcur_lo', 'wexcur_weights'):
+        extra[key] = np.array(extra[key], dtype=np.float64)
+    extra['wexcur_scenarios'] = np.array(names)
+    extra['wexcur_thresholds'] = np.asarray(first.thresholds, dtype=np.float64)
+    extra['wexcur_days'] = extra['days'] = np.asarray(first.days)
+    save_maps(outfile, maps, extra)
+    return {'scenarios': names, 'thresholds': list(first.thresholds), 'days': list(first.days), 'levels': levels,
+            'cell_area': first.cell_area, 'scenario': block}
+
+
 def save_range(outfile, rng, levels=(0.5, 0.9)):
     '''outfile.npz of one RangeMaps through save_maps: per day of the maps, under the label `{day}`, the CSR
     triplets `{day}_prange{j}_*` of the probability that the cell lies in the member's p_j region; the count planes
@@ -7753,6 +7960,8 @@ class PredictiveResult():
     their own); `reweight_histogram` / `reweight_arrival`: the ReweightedHistogram and the ReweightedArrival over
     the summary's days, on the edges of quantiles= and the thresholds of arrival=, None unless reweight's
     options['maps'] names 'quantiles' / 'arrival' (the projections then carry a `reweight_histogram`, the plan both);
+    `reweight_excursion`: {scenario: ReweightedExcursion} over `excursion`, None unless the maps name 'excursion' (the
+    plan then carries one over its own excursion maps);
     `catch`: the CatchPosterior of the traps over the model's day fields, None where not asked for
     (the emergence projection and the plan then carry a `catch` of their own where asked for); `information`: the
     InformationPosterior of the described traps over the model's day fields, None where not asked for (the plan then
@@ -7782,7 +7991,8 @@ class PredictiveResult():
                  representative=None, representative_days=None, representative_chains=None, neighbourhood=None,
                  modes=None, dependence=None, pathways=None, pathway_levels=None, proximity=None, origin=None,
                  reweight_histogram=None, reweight_arrival=None, ranking=None, ranking_plans=None,
-                 ranking_levels=None, weather=None, wind=None):
+                 ranking_levels=None, weather=None, wind=None, reweight_excursion=None):
+        self.reweight_excursion = reweight_excursion
         self.weather = weather
         self.wind = wind
         self.ranking = ranking
@@ -7888,7 +8098,9 @@ class PredictiveResult():
         Reweighted quantile and arrival maps (reweight's maps option) go into outfile_reweight_quantiles.npz
         (save_reweight_quantiles: `s{j}_{label}_q{tag}_*`) and outfile_reweight_arrival.npz (save_reweight_arrival:
         `s{j}_{label}_parr{k}_*`, dense `s{j}_arrival{k}_q{tag}`), those of a projection or a plan into
-        outfile_NAME_reweight_quantiles.npz / outfile_NAME_reweight_arrival.npz; `predictive.reweight` of the json
+        outfile_NAME_reweight_quantiles.npz / outfile_NAME_reweight_arrival.npz; reweighted excursion regions into
+        outfile_reweight_excur.npz and outfile_sites_reweight_excur.npz (save_reweight_excursion), their block under
+        `predictive.reweight.excursion` (`predictive.sites.reweight.excursion`); `predictive.reweight` of the json
         then carries `maps` and, with arrival maps, per scenario the reached-area curve `reached_area`
         (`predictive.sites.reweight.reached_area` for a plan).
         Excursion maps go into outfile_excur.npz (save_excursion; those of a release plan into
@@ -8113,6 +8325,14 @@ class PredictiveResult():
                         meta['predictive'][name[:-1]].setdefault('reweight', {})
                     block['reached_area'] = {n: [ra.reached_area(n, k, fs.arrival, ra_levels)
                                                  for k in range(len(ra.thresholds))] for n in ra.scenarios}
+            # maps=('excursion',): outfile_reweight_excur.npz, the plan's outfile_sites_reweight_excur.npz
+            for name, fs in (('', self), ('sites_', self.sites)):
+                rx = getattr(fs, 'reweight_excursion', None)
+                if rx:
+                    block = save_reweight_excursion('%s_%sreweight_excur' % (outfile, name), rx,
+                                                    self.excursion_levels)
+                    (meta['predictive']['reweight'] if not name else
+                     meta['predictive'][name[:-1]].setdefault('reweight', {}))['excursion'] = block
         area = getattr(self, 'cell_area', None)
         for name, cp in [('', self.catch)] + [(n + '_', pr.catch) for n, pr in (
                 ('emergence', self.emergence), ('sites', self.sites)) if pr is not None]:
@@ -8409,7 +8629,7 @@ def _check_request(q):
         q.a_levels = check_levels(q.arrival_levels)
         if days is not None:
             check_arrival_days(days)
-    for what, have in (('quantiles', q.levels), ('arrival', q.a_thr)):
+    for what, have in (('quantiles', q.levels), ('arrival', q.a_thr), ('excursion', q.ex_thr)):
         if what in _reweight_maps(q) and not have:
             raise ValueError("reweight: maps=%r reweights the maps of %s=, and there is none" % (what, what))
     wanted = [(name, arg, plan) for name, arg, plan in (('emergence', q.emergence, emergence_plan),
@@ -8671,8 +8891,12 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         also reweights the quantile and the arrival maps: each chain then fills a ReweightedHistogram on the edges of
         quantiles= and a ReweightedArrival on the thresholds of arrival=, fed the same log-weights right after the
         ReweightedSummary, merged in chain order into `reweight_histogram` / `reweight_arrival`; the projections get
-        a ReweightedHistogram.for_projection, the plan both. Without `maps` nothing of this is built or called.
-        Peak, excursion, contrast, range, patch, pathway and Monte Carlo error maps and the histograms inside the
+        a ReweightedHistogram.for_projection, the plan both. 'excursion' among the maps (needs excursion=) keeps
+        per member of the excursion maps the run's log-weights and, once the chains are merged, builds
+        `reweight_excursion` = {name: ReweightedExcursion} over `excursion` -- and over the plan's, as
+        `sites.reweight_excursion` -- from the kept masks, the members in the merged add order; nothing is added to
+        the evaluation of a member. Without `maps` nothing of this is built or called.
+        Peak, contrast, range, patch, pathway and Monte Carlo error maps and the histograms inside the
         neighbourhood and proximity posteriors get none. `reweight_info` carries per scenario the diagnostics of the row
         weights (reweight_diagnostics); a UserWarning where ess < min_ess (reweight['options'] = dict(min_ess=50))
         -- importance reweighting degrades as the new data disagree with the posterior -- and a ValueError naming
@@ -8940,6 +9164,16 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
                 warnings.warn('reweight: scenario %r has an effective sample size of %.3g rows (min_ess %g): the '
                               'new data disagree with the posterior, the reweighted maps rest on few members'
                               % (n, diag[n]['ess'], rw_plan['min_ess']), UserWarning)
+        try:                          # over the merged excursion maps, the members in the merged add order
+            for fs in (day, merged.get('sites')):
+                if fs is not None and fs._rw_lam is not None:
+                    fs.reweight_excursion = {}
+                    for j, n in enumerate(rw_plan['names']):
+                        fs.reweight_excursion[n] = fs.excursion.reweighted([lam[j] for lam in fs._rw_lam])
+        except BaseException:
+            for fs in merged.values():
+                fs.close()
+            raise
     run_rec = [(ci, first, length) for ci, p in enumerate(prepared)
                for (first, length), e in zip(p[1], results[ci][0]) if e is not None]
     observations = None
@@ -8974,7 +9208,7 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         neighbourhood=day.neighbourhood, modes=day.modes, dependence=day.dependence, pathways=day.pathways,
         pathway_levels=q.pw_levels if q.pw_thr else None, proximity=day.proximity, origin=day.origin,
         reweight_histogram=day.reweight_histogram, reweight_arrival=day.reweight_arrival,
-        ranking=ranked.ranking, ranking_plans=ranked.plan,
+        reweight_excursion=day.reweight_excursion, ranking=ranked.ranking, ranking_plans=ranked.plan,
         ranking_levels=q.rk_plan['levels'] if q.rk_plan else None, weather=day.weather, wind=wind_plan)
     if day.information is not None:   # the stated convention: past cap / 2 the ensemble bounds the map
         warn_information(day.information)

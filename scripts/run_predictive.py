@@ -47,7 +47,8 @@ chain row after burn and thin (several chains: concatenated in chain order), by 
 members, with the effective sample size of every scenario in the json -- saved as PREFIX_reweight.npz (and
 PREFIX_NAME_reweight.npz for every projection and plan asked for), and with --reweight-maps quantiles,arrival the
 reweighted quantile maps of --quantiles and arrival maps of --arrival as PREFIX_reweight_quantiles.npz and
-PREFIX_reweight_arrival.npz; with --catch also the catch-probability maps --
+PREFIX_reweight_arrival.npz, and with excursion among them the excursion regions of --excursion under every
+scenario, from the members' kept masks, as PREFIX_reweight_excur.npz; with --catch also the catch-probability maps --
 per trap 'DAY,RATE[,N]' and cell the posterior mean, sd and the probability (--catch-levels) that a trap of effort
 RATE on model day DAY catches at least N wasps; --catch-emergence: traps over the emergence days of --emergence --
 saved as PREFIX_catch.npz (and PREFIX_emergence_catch.npz, PREFIX_sites_catch.npz); with --neighbourhood also the
@@ -78,7 +79,7 @@ Without --chain a short chain is sampled first (--samples) and saved next to --o
         [--pathways 1,10] [--pathway-connectivity 8] [--pathway-levels 0.05,0.5,0.95]
         [--representative [K]] [--representative-epsilon 0.02] [--representative-central 0.5]
         [--reweight 'NAME:east,north,day,kind,rate[,n];...'] [--reweight-file NAME=weights.npy]
-        [--reweight-maps quantiles,arrival]
+        [--reweight-maps quantiles,arrival,excursion]
         [--catch 'DAY,RATE[,N];...'] [--catch-levels 0.5,0.95] [--catch-emergence 'OBSDAY,RATE[,N];...']
         [--information 'DAY,RATE[,YMAX];...'] [--neighbourhood 'DAY,RADIUS_M;...']
         [--proximity 'DAY,T[,in];...'] [--proximity-radii 100,400,1600] [--proximity-levels 0.05,0.5,0.95]
@@ -278,17 +279,18 @@ def main():
     ap.add_argument('--reweight-file', action='append', default=None, metavar='NAME=NPY',
                     help='a reweighting scenario from a .npy of one log-weight per chain row after burn and thin '
                          '(repeatable)')
-    ap.add_argument('--reweight-maps', default='', metavar='quantiles,arrival',
-                    help='with --reweight / --reweight-file: also reweight the quantile maps (needs --quantiles) and '
-                         'the arrival maps (needs --arrival), saved as PREFIX_reweight_quantiles.npz / '
-                         'PREFIX_reweight_arrival.npz (default: off)')
+    ap.add_argument('--reweight-maps', default='', metavar='quantiles,arrival,excursion',
+                    help='with --reweight / --reweight-file: also reweight the quantile maps (needs --quantiles), '
+                         'the arrival maps (needs --arrival) and the excursion regions (needs --excursion), saved as '
+                         'PREFIX_reweight_quantiles.npz / PREFIX_reweight_arrival.npz / PREFIX_reweight_excur.npz '
+                         '(default: off)')
     args = ap.parse_args()
     rw_specs, rw_files = parse_reweight(ap, args.reweight, args.reweight_file)
     rw_maps = [m.strip() for m in args.reweight_maps.split(',') if m.strip()]
     if rw_maps and not (rw_specs or rw_files):
         ap.error('--reweight-maps reweights more maps of a scenario: give --reweight or --reweight-file too')
-    if [m for m in rw_maps if m not in ('quantiles', 'arrival')] or len(set(rw_maps)) != len(rw_maps):
-        ap.error("--reweight-maps takes a subset of 'quantiles,arrival', got %r" % args.reweight_maps)
+    if [m for m in rw_maps if m not in ('quantiles', 'arrival', 'excursion')] or len(set(rw_maps)) != len(rw_maps):
+        ap.error("--reweight-maps takes a subset of 'quantiles,arrival,excursion', got %r" % args.reweight_maps)
     for m in rw_maps:
         if not getattr(args, m).strip():
             ap.error('--reweight-maps %s reweights the maps of --%s: give --%s too' % (m, m, m))
@@ -886,7 +888,7 @@ def main():
             out['reweight_maps'] = rw_maps
             out['reweight_maps_ms_per_member'] = round(rwm_ms / max(rwm_members, 1), 4)
             out['reweight_maps_detail'] = rwm_detail
-            out['outputs'] += ['%s_reweight_%s.npz' % (args.out, m) for m in rw_maps]
+            out['outputs'] += ['%s_reweight_%s.npz' % (args.out, 'excur' if m == 'excursion' else m) for m in rw_maps]
         out['reweight_diagnostics'] = res.reweight_info['diagnostics']
         out['outputs'] += ['%s_reweight.npz' % args.out] + ['%s_%s_reweight.npz' % (args.out, n) for n, on in
                                                             (('emergence', emergence), ('exposure', exposure),
