@@ -251,9 +251,16 @@ def bump(N):
 
 def fma(a, b, c):
     """a * b + c with one rounding: the exact value as a ratio of integers (every denominator is a power of two), and
-    Python's integer true division, which rounds correctly"""
+    Python's integer true division, which rounds correctly.  An infinite argument gives what IEEE arithmetic gives
+    (no rounding is left to do), and a result beyond the largest double is the infinity of its sign"""
+    if not (math.isfinite(a) and math.isfinite(b) and math.isfinite(c)):
+        return a * b + c
     (na, da), (nb, db), (nc, dc) = a.as_integer_ratio(), b.as_integer_ratio(), c.as_integer_ratio()
-    return (na * nb * dc + nc * da * db) / (da * db * dc)
+    num = na * nb * dc + nc * da * db
+    try:
+        return num / (da * db * dc)
+    except OverflowError:
+        return math.inf if num > 0 else -math.inf
 
 
 def welford(values, weights, fused):
@@ -310,7 +317,7 @@ def exact_moments(values, weights):
         S2 = sum(int(w) * x * x for w, x in zip(weights, n))
         out[0][i] = Fraction(S, W * D)
         out[1][i] = Fraction(W * S2 - S * S, W * D * D)
-        out[2][i] = Fraction(max(n), D * 2 ** 53)
+        out[2][i] = Fraction(max(abs(x) for x in n), D * 2 ** 53)
         out[3][i] = Fraction(S2, D * D * 2 ** 53)
     return tuple(out)
 
