@@ -2000,6 +2000,62 @@ int ps_origin_fetch_background(ps_origin* p, double* bg /* nfind */, double* l0)
  * null rows; reset, reserve and the growth of the rows carry them along; info's bytes include them. */
 int ps_origin_null_rows(ps_origin* p, int64_t members_expected, double* rows /* members */);
 
+/* ---- reweighted paired contrast: is plan A still better than plan B under new observations? ----
+ * (no reference counterpart.)  ps_contrast's maps of d = a - b with the real weights of ps_wsum: J scenarios
+ * (1..4), nslot slots (1..32) of N x N cells and K thresholds (0..4, each finite and > 0, strictly increasing).
+ * a and b are the fields two ps_sites or two ps_project hold for the same member, so the pairing, which the
+ * reweighted maps of either plan alone have lost, is kept.  Per scenario j on the device, all fp64 (pitch as
+ * ps_summary; P = 2 + 2 K):
+ *   mean[j][slot][pitch], m2[j][slot][pitch], S[j][slot][P][pitch]
+ * with the planes of S in the order pos (d > 0), neg (d < 0), gain_0 (a >= t_0 > b), loss_0 (b >= t_0 > a),
+ * gain_1, ..., and on the host W_j (a double, 0 while empty), members_j and skipped_j.  The whole block,
+ * J * (4 + 2 K) * 8 B * nslot * pitch, is checked against the free device memory first: PS_ERR_OOM before
+ * anything is allocated.  At R = 400 (N = 801, pitch 641 664), 18 output days and K = 2 one scenario takes
+ * 641 664 x 18 x 64 B = 739 MB.  The per-member coverage rows are not kept here: they are those of the
+ * ps_contrast fed alongside.  One thread owns a pair of cells: no atomics, the same calls in the same order
+ * give the same bits.  Every operation runs on the handle's stream behind its last one. */
+typedef struct ps_wcontrast ps_wcontrast;
+/* PS_ERR_BAD_ARG (and *out = NULL) for nscen outside 1..4, nslot outside 1..32, nthr outside 0..4 or thresholds
+ * that are not finite, > 0 and strictly increasing */
+int ps_wcontrast_create(int device, int N, int nscen, int nslot, int nthr, const double* thr, ps_wcontrast** out);
+/* One member from the last apply of a and b, as ps_contrast_add_sites / _add_project take them: slot e takes
+ * a = Y_e of a and b = Y_e of b.  rescale[nscen] (r, in [0, 1]) and omega[nscen] (>= 0, finite) as ps_wsum_add;
+ * omega_j == 0: the member leaves scenario j untouched and skipped_j grows by one.  For a scenario with
+ * omega > 0, every step a statement of its own (one rounding each, but for the two statements of
+ * ps_summary_add, which contract as they do there):
+ *   host:      W = W * r;  W = W + omega;
+ *   per cell:  d = a - b (once, for every scenario);  q = q * r;  S_p = S_p * r (every plane);  e = d - m;
+ *              e != 0:  m += e omega / W,  q += omega e (d - m)        (the statements of ps_summary_add)
+ *              d > 0: S_pos = S_pos + omega;   d < 0: S_neg = S_neg + omega;
+ *              a >= t_k and b < t_k: S_gain_k = S_gain_k + omega;   b >= t_k and a < t_k: S_loss_k = S_loss_k + omega
+ * so with r = 1 and integer omega the handle holds the mean and M2 of a ps_contrast fed alongside bit for bit,
+ * and its sums are that handle's counts.  A value is stored only where its bits changed, and with r == 1 a pair
+ * of cells with d == 0 against a mean of 0 reads its means alone.  An add moves, per slot and cell, 16 B of a
+ * and b and per scenario that takes the member 8 B of mean; where something can change, 16 + 16 P B more, read
+ * and written.  One launch per member on the handle's stream behind both sources' last operation, no host
+ * synchronisation; their next apply waits for the read.  PS_ERR_BAD_ARG (everything is checked before anything
+ * is enqueued; a refused add changes nothing): a == b, a source with other outputs than the handle's slots or of
+ * another device or domain, a wrong nscen, r outside [0, 1], omega NaN, negative or infinite. */
+int ps_wcontrast_add_sites(ps_wcontrast* h, ps_sites* a, ps_sites* b, int nscen, const double* rescale,
+                           const double* omega);
+int ps_wcontrast_add_project(ps_wcontrast* h, ps_project* a, ps_project* b, int nscen, const double* rescale,
+                             const double* omega);
+/* dst += src per scenario, same device, N, scenarios, slots and thresholds; src stays as it is.  The rule and
+ * the expressions of ps_wsum_merge: Wa' = Wa ra, Wb' = Wb rb, W = Wa' + Wb',
+ *   e = mean_b - mean_a;  mean = mean_a + e (Wb' / W);  m2 = m2a ra + m2b rb + e^2 (Wa' Wb' / W);  S = Sa ra + Sb rb.
+ * A scenario empty in src adds its skipped count alone; into a scenario empty in dst it is a device copy, bit
+ * for bit, W included (ra, rb unused). */
+int ps_wcontrast_merge(ps_wcontrast* dst, ps_wcontrast* src, const double* ra, const double* rb);
+/* per scenario (any pointer may be NULL): W, members (adds with omega > 0) and skipped (adds with omega == 0) */
+int ps_wcontrast_info(ps_wcontrast* h, double* total_weight /* nscen */, int64_t* members, int64_t* skipped);
+/* one slot of one scenario to the host (synchronises): what 0 mean, 1 variance m2 / W, 2 P(d > 0), 3 P(d < 0),
+ * 4 + 2k gain_k, 5 + 2k loss_k, each probability min(S / W, 1.0).  PS_ERR_STATE while the scenario has W = 0. */
+int ps_wcontrast_fetch(ps_wcontrast* h, int scen, int slot, int what, double* out /* N*N */);
+int ps_wcontrast_reset(ps_wcontrast* h);
+/* measurement: HIP-event timing of the add launches, as ps_summary_prof */
+int ps_wcontrast_prof(ps_wcontrast* h, int enable, double* total_ms, int64_t* launches);
+void ps_wcontrast_destroy(ps_wcontrast* h);
+
 #ifdef __cplusplus
 }
 #endif

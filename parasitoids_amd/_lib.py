@@ -460,6 +460,15 @@ SIGNATURES = {
     'ps_wexcur_member_weights': (C.c_int, [_VP, C.c_int64, C.POINTER(C.c_uint32)]),
     'ps_wexcur_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P]),
     'ps_wexcur_destroy': (None, [_VP]),
+    'ps_wcontrast_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F64P, C.POINTER(_VP)]),
+    'ps_wcontrast_add_sites': (C.c_int, [_VP, _VP, _VP, C.c_int, _F64P, _F64P]),
+    'ps_wcontrast_add_project': (C.c_int, [_VP, _VP, _VP, C.c_int, _F64P, _F64P]),
+    'ps_wcontrast_merge': (C.c_int, [_VP, _VP, _F64P, _F64P]),
+    'ps_wcontrast_info': (C.c_int, [_VP, _F64P, _I64P, _I64P]),
+    'ps_wcontrast_fetch': (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, _F64P]),
+    'ps_wcontrast_reset': (C.c_int, [_VP]),
+    'ps_wcontrast_prof': (C.c_int, [_VP, C.c_int, _F64P, _I64P]),
+    'ps_wcontrast_destroy': (None, [_VP]),
     'ps_modes_create': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_VP)]),
     'ps_modes_reserve': (C.c_int, [_VP, C.c_int64]),
     'ps_modes_set_window': (C.c_int, [_VP, C.c_int]),

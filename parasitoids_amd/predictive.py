@@ -2661,7 +2661,7 @@ FEED_ORDER = {
     'sites': ('apply', 'summary', 'reweight', 'reweight_histogram', 'reweight_arrival', 'mc_error', 'sensitivity',
               'dependence', 'histogram', 'arrival', 'peak', 'excursion', 'core_range', 'catch', 'neighbourhood', 'proximity', 'information', 'patches', 'pathways',
               'weather', 'modes'),
-    'compare': ('apply', 'contrast'),
+    'compare': ('apply', 'contrast', 'reweight_contrast'),
     'ranking': ('apply', 'ranking'),
 }
 
@@ -2710,6 +2710,7 @@ FEED = {
     'information': lambda acc, fs, m: acc.add(m.length, m.lam),
     'mc_error': _add_halves,
     'contrast': _add_length,
+    'reweight_contrast': lambda acc, fs, m: acc.add(m.lam, m.length),      # m.lam: set by the day set's 'reweight'
     'ranking': _add_length,
     'patches': _add_length,
     'pathways': _add_length,
@@ -2766,6 +2767,13 @@ def _build_reweight_arrival(fs, q):
     if 'arrival' in _reweight_maps(q):
         names = q.rw_plan['names']
         return fs._over(ReweightedArrival, (names, q.a_thr, fs._days), (names, q.a_thr))
+
+
+def _build_reweight_contrast(fs, q):
+    '''the ReweightedContrast of plan A against this set's plan B on the request's thresholds; None, and nothing
+    built, without maps=(..., 'contrast')'''
+    if 'contrast' in _reweight_maps(q):
+        return ReweightedContrast(fs._against, fs._source, q.rw_plan['names'], q.thresholds)
 
 
 def _build_catch(fs, q):
@@ -2889,6 +2897,7 @@ BUILD = {
     'information': _build_information,
     'mc_error': _build_mc_error,
     'contrast': lambda fs, q: PlanContrast(fs._against, fs._source, q.thresholds),
+    'reweight_contrast': _build_reweight_contrast,
     'ranking': lambda fs, q: PlanRanking([fs._against] + fs._source.plans, q.thresholds, q.rk_plan['names']),
     'patches': lambda fs, q: q.pt_thr and fs._over(PatchMaps, (q.pt_thr, fs._days, q.pt_conn), (q.pt_thr, q.pt_conn)),
     'pathways': lambda fs, q: q.pw_thr and fs._over(PathwayMaps, (q.pw_thr, q.pw_days or fs._days, q.pw_conn),
@@ -2912,7 +2921,7 @@ class _FieldSet():
         self.plan = None
         self.representative = None     # the RepresentativeMembers over `excursion`, built once the chains are merged
         self.reweight_excursion = None # {scenario: ReweightedExcursion} over `excursion`, likewise
-        self._rw_lam = None            # per member of `excursion` the run's log-weights, where those are built
+        self._rw_lam = None            # per member of `excursion` (of `contrast`) the run's log-weights, where those are built
         self._kind = self._name = self._source = self._against = self._days = self._half = self._rw_feed = None
         self._chain = self._late = None
         self._owns = False
@@ -2954,7 +2963,7 @@ class _FieldSet():
                 acc.reserve(nruns)
             if name == 'modes' and acc is not None:
                 _reserve_modes(acc, nruns)
-        if 'excursion' in _reweight_maps(q) and self.excursion is not None:
+        if ('excursion' in _reweight_maps(q) and self.excursion is not None) or self.reweight_contrast is not None:
             self._rw_lam = []
         return self
 
@@ -2963,7 +2972,7 @@ class _FieldSet():
             acc = getattr(self, name, None)
             if acc is not None or name == 'apply':
                 FEED[name](acc, self, m)
-        if self._rw_lam is not None:     # the excursion maps have taken the member: its log-weights, in add order
+        if self._rw_lam is not None:     # the excursion maps (the contrast) have taken the member: its log-weights, in add order
             self._rw_lam.append([float(v) for v in m.lam])
 
     def merge(self, other):
@@ -3387,6 +3396,21 @@ def contrast_plan(arg, sites_arg, pop_model=None):
     return sites_plan(dict(sites=arg['sites'], days=a_days), pop_model)
 
 
+def _check_paired(a, b):
+    '''what a paired accumulator asks of its two sources: two ReleaseSites or two Projection, not the same one, on
+    the same device and domain with the same outputs (of two ReleaseSites also the same output days)'''
+    if a is b:
+        raise ValueError('a plan is compared with another one, not with itself')
+    if type(a) is not type(b) or not isinstance(a, (ReleaseSites, Projection)):
+        raise ValueError('two ReleaseSites or two Projection expected, got %s and %s'
+                         % (type(a).__name__, type(b).__name__))
+    if a.pm.device != b.pm.device:
+        raise ValueError('the plans\' models are on devices %r and %r' % (a.pm.device, b.pm.device))
+    for name in ('device', 'N', 'nout', 'live') + (('days',) if isinstance(a, ReleaseSites) else ()):
+        if getattr(a, name) != getattr(b, name):
+            raise ValueError('the plans differ in %s: %r and %r' % (name, getattr(a, name), getattr(b, name)))
+
+
 class PlanContrast(_Accumulator):
     '''The posterior of the difference of two plans, member by member, on the device: `a` and `b` are two
     ReleaseSites or two Projection on the same device and domain with the same outputs (nout, live; of two
@@ -3402,16 +3426,7 @@ class PlanContrast(_Accumulator):
     _prefix = 'ps_contrast'
 
     def __init__(self, a, b, thresholds=()):
-        if a is b:
-            raise ValueError('a plan is compared with another one, not with itself')
-        if type(a) is not type(b) or not isinstance(a, (ReleaseSites, Projection)):
-            raise ValueError('two ReleaseSites or two Projection expected, got %s and %s'
-                             % (type(a).__name__, type(b).__name__))
-        if a.pm.device != b.pm.device:
-            raise ValueError('the plans\' models are on devices %r and %r' % (a.pm.device, b.pm.device))
-        for name in ('device', 'N', 'nout', 'live') + (('days',) if isinstance(a, ReleaseSites) else ()):
-            if getattr(a, name) != getattr(b, name):
-                raise ValueError('the plans differ in %s: %r and %r' % (name, getattr(a, name), getattr(b, name)))
+        _check_paired(a, b)
         self.thresholds = check_contrast_thresholds(thresholds)
         self.a, self.b = a, b
         self._attach(a.pm)
@@ -4825,7 +4840,7 @@ MAX_REWEIGHT_SCENARIOS = 4
 MAX_REWEIGHT_SLOTS = 32    # ps_wsum: the slots of one launch's descriptors
 PROBE_KINDS = ('count', 'none', 'found')
 DEFAULT_MIN_ESS = 50.0
-REWEIGHT_MAPS = ('quantiles', 'arrival', 'excursion')      # the 'maps' option of reweight=: what else is reweighted
+REWEIGHT_MAPS = ('quantiles', 'arrival', 'contrast', 'excursion')      # the 'maps' option of reweight=: what else is reweighted
 
 
 def check_scenarios(scenarios):
@@ -4964,7 +4979,7 @@ def reweight_diagnostics(row_log_weights):
 
 
 def check_reweight_maps(maps):
-    '''the 'maps' option of reweight=: a subset of REWEIGHT_MAPS ('quantiles', 'arrival', 'excursion') as a tuple in that order,
+    '''the 'maps' option of reweight=: a subset of REWEIGHT_MAPS ('quantiles', 'arrival', 'contrast', 'excursion') as a tuple in that order,
     () for None; ValueError otherwise'''
     if maps is None:
         return ()
@@ -5513,6 +5528,189 @@ class ReweightedArrival(_ReweightedCounts):
                         'radius_quantiles': [float(np.sqrt(a / np.pi)) for a in q]})
         return out
 
+
+def reweighted_coverage_difference(cells_a, cells_b, weights, log_weights, cell_area, levels=(0.05, 0.5, 0.95)):
+    '''coverage_difference for members of real weight omega_m = w_m exp(lambda_m - max lambda), the maximum over the
+    members with w > 0 and a finite lambda: per output {'mean', 'quantiles', 'p_a_larger', 'p_b_larger'} of the
+    signed area A - B in m^2 from the paired per-member cell counts cells_a, cells_b [members, nout], the members'
+    integer weights and their log-weights (finite or -inf).  The mean is sum omega d / sum omega, both sums by
+    math.fsum; a lower quantile is the smallest distinct d whose cumulative omega (over the sorted distinct d, each
+    prefix by math.fsum) is >= p sum omega; p_a_larger (p_b_larger) is the share of sum omega with d > 0 (d < 0).
+    With every lambda = 0 these are coverage_difference's numbers exactly.  ValueError when every member is at
+    -inf or without weight.'''
+    import math
+    levels = check_levels(levels)
+    a = np.asarray(cells_a, dtype=np.int64)
+    b = np.asarray(cells_b, dtype=np.int64)
+    w = np.asarray(weights, dtype=np.int64).ravel()
+    lam = np.asarray(log_weights, dtype=np.float64).ravel()
+    if a.ndim != 2 or a.shape != b.shape or a.shape[0] != w.size or lam.size != w.size:
+        raise ValueError('cell counts %r and %r with %d weights and %d log-weights' % (a.shape, b.shape, w.size, lam.size))
+    if w.size and w.min() < 0:
+        raise ValueError('weights must be >= 0')
+    if np.isnan(lam).any() or (lam == np.inf).any():
+        raise ValueError('log-weights hold NaN or +inf')
+    alive = (w > 0) & np.isfinite(lam)
+    if not alive.any():
+        raise ValueError('nothing accumulated: every member is at -inf or without weight')
+    top = float(lam[alive].max())
+    om = [float(wm) * math.exp(float(lm) - top) if ok else 0.0 for wm, lm, ok in zip(w, lam, alive)]
+    W = math.fsum(om)
+    out = []
+    for s in range(a.shape[1]):
+        d = a[:, s] - b[:, s]
+        by_d = {}
+        for dm, o in zip(d.tolist(), om):
+            by_d.setdefault(dm, []).append(o)
+        distinct = sorted(by_d)
+        seen, cum = [], []
+        for v in distinct:
+            seen.extend(by_d[v])
+            cum.append(math.fsum(seen))
+        q = []
+        for p in levels:
+            at = next((i for i, c in enumerate(cum) if c >= float(p) * W), len(distinct) - 1)
+            q.append(float(distinct[at]) * float(cell_area))
+        out.append({'mean': math.fsum(o * float(dm) for dm, o in zip(d.tolist(), om)) / W * float(cell_area),
+                    'quantiles': q,
+                    'p_a_larger': math.fsum(o for dm, o in zip(d.tolist(), om) if dm > 0) / W,
+                    'p_b_larger': math.fsum(o for dm, o in zip(d.tolist(), om) if dm < 0) / W})
+    return out
+
+
+class ReweightedContrast(_Handle):
+    '''The maps of a PlanContrast under up to 4 reweighting scenarios at once, on the device (ps_wcontrast_*,
+    csrc/ps_wcontrast.hip): is plan A still better than plan B, now that the traps found this?  `a` and `b` as
+    PlanContrast takes them (two ReleaseSites or two Projection, same device, domain and outputs), scenarios and
+    the log scale as ReweightedSummary (per scenario `ref`, the largest log-weight so far), thresholds as
+    PlanContrast (0..4, finite, > 0, strictly increasing).  After both plans were applied to one member,
+    `add(log_weights, weight)` accumulates per output and cell d = a - b with the real weight
+    weight exp(log_weights[j]) in scenario j: its weighted mean and M2, the weight of the members with d > 0 and
+    with d < 0 and per threshold of those with a >= t_k > b (gain) and b >= t_k > a (loss).  The accessors take the
+    scenario's name and the output index; outputs kept off the device read as zeros.  A scenario whose log-weights
+    are all 0 holds the bits of a PlanContrast fed alongside.  The per-member coverage rows are that
+    PlanContrast's: reweighted_coverage_difference takes them with the members' log-weights.  The ranking of
+    several plans, Pareto smoothing, the Monte Carlo error or sensitivity of these maps and any search for a plan
+    are not computed.'''
+
+    _prefix, _noun = 'ps_wcontrast', 'reweighted contrast'
+
+    def __init__(self, a, b, scenarios, thresholds=()):
+        import math
+        _check_paired(a, b)
+        self.scenarios = check_scenarios(scenarios)
+        self.thresholds = check_contrast_thresholds(thresholds)
+        self.a, self.b = a, b
+        self._attach(a.pm)
+        self.device, self.nout, self.live = a.device, a.nout, list(a.live)
+        self.labels = list(getattr(a, 'days', range(a.nout)))
+        self._slot = {e: i for i, e in enumerate(self.live)}
+        n = len(self.live)
+        if not 1 <= n <= MAX_REWEIGHT_SLOTS:
+            raise ValueError('%d slots; 1..%d fit one handle' % (n, MAX_REWEIGHT_SLOTS))
+        self.ref = [-math.inf] * len(self.scenarios)
+        self.nbytes = len(self.scenarios) * (4 + 2 * len(self.thresholds)) * 8 * n * self.pitch
+        thr = L.f64(self.thresholds if self.thresholds else [0.0])
+        self._create(len(self.scenarios), n, len(self.thresholds), L.p_f64(thr))
+
+    def _j(self, name):
+        if name not in self.scenarios:
+            raise ValueError('scenario %r is not one of %r' % (name, self.scenarios))
+        return self.scenarios.index(name)
+
+    def scale(self, log_weights, weight=1):
+        '''(r, omega, ref) per scenario that add() would pass for these log-weights, without adding (reweight_scale)'''
+        return reweight_scale(self.scenarios, self.ref, log_weights, weight)
+
+    def add(self, log_weights, weight=1):
+        '''Accumulate the last apply of both plans with weight `weight` (the run length) times exp(log_weights[j])
+        in scenario j (on the handle's stream behind both; no host synchronisation).  A refused add changes
+        nothing.'''
+        r, om, ref = self.scale(log_weights, weight)
+        self._from_fields('add', self.a, self.b._h, len(self.scenarios), L.p_f64(L.f64(r)), L.p_f64(L.f64(om)))
+        # a member whose weight underflowed is skipped and moves no reference
+        self.ref = [b if o > 0.0 else a for a, b, o in zip(self.ref, ref, om)]
+
+    def merge(self, other):
+        '''self += other (same device, domain, scenarios, outputs and thresholds), both brought to the larger of the
+        two references per scenario (reweight_merge_scale); other is unchanged'''
+        if other.live != self.live or other.nout != self.nout or list(other.labels) != self.labels \
+                or other.scenarios != self.scenarios:
+            raise ValueError('reweighted contrasts over different outputs or scenarios')
+        ra, rb, ref = reweight_merge_scale(self.ref, other.ref)
+        self._call('merge', other._h, L.p_f64(L.f64(ra)), L.p_f64(L.f64(rb)))
+        self.ref = ref
+
+    def reset(self):
+        import math
+        self._call('reset')
+        self.ref = [-math.inf] * len(self.scenarios)
+
+    def _info(self):
+        n = len(self.scenarios)
+        w, m, s = np.zeros(n), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+        self._call('info', L.p_f64(w), L.p_i64(m), L.p_i64(s))
+        return w, m, s
+
+    def total_weight(self, name):
+        '''W of the scenario on its own scale exp(ref)'''
+        return float(self._info()[0][self._j(name)])
+
+    def log_total_weight(self, name):
+        '''ref + log W: the log of the scenario's total weight (-inf while it is empty)'''
+        import math
+        j = self._j(name)
+        W = float(self._info()[0][j])
+        return -math.inf if W == 0.0 else self.ref[j] + math.log(W)
+
+    def members(self, name):
+        return int(self._info()[1][self._j(name)])
+
+    def skipped(self, name):
+        return int(self._info()[2][self._j(name)])
+
+    def fetch_slot(self, scen, slot, what):
+        '''raw access by scenario and slot index (0 mean, 1 variance, 2 P(d > 0), 3 P(d < 0), 4 + 2k gain, 5 + 2k loss)'''
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        self._call('fetch', int(scen), int(slot), int(what), L.p_f64(out))
+        return out
+
+    def _fetch(self, name, e, what):
+        j = self._j(name)
+        e = self._e(e)
+        if e not in self._slot:                                   # an output without weight
+            return np.zeros((self.N, self.N), dtype=np.float64)
+        return self.fetch_slot(j, self._slot[e], what)
+
+    def mean(self, name, e):
+        '''[N, N] float64: the mean of A - B on output e under the scenario'''
+        return self._fetch(name, e, 0)
+
+    def variance(self, name, e):
+        return self._fetch(name, e, 1)
+
+    def sd(self, name, e):
+        return np.sqrt(self.variance(name, e))
+
+    def prob_positive(self, name, e):
+        '''P(A > B) per cell under the scenario'''
+        return self._fetch(name, e, 2)
+
+    def prob_negative(self, name, e):
+        '''P(A < B) per cell under the scenario'''
+        return self._fetch(name, e, 3)
+
+    def gain(self, name, e, k):
+        '''P(A >= thresholds[k] > B) per cell under the scenario'''
+        return self._fetch(name, e, 4 + 2 * self._k(k))
+
+    def loss(self, name, e, k):
+        '''P(B >= thresholds[k] > A) per cell under the scenario'''
+        return self._fetch(name, e, 5 + 2 * self._k(k))
+
+    def profile(self, enable=None):
+        '''HIP-event time of the add launches: (total ms, launches); enable switches it'''
+        return self._profile(enable)
 
 
 class _ReweightFeed():
@@ -7819,6 +8017,42 @@ def save_excursion(outfile, exc, levels=(0.9, 0.95)):
             'total_weight': exc.total_weight, 'cell_area': exc.cell_area, 'areas': areas}
 
 
+def save_reweight_contrast(outfile, rc, contrast=None, levels=(0.05, 0.5, 0.95)):
+    '''outfile.npz of one ReweightedContrast through save_maps(signed=True): per scenario index j and output label
+    the signed CSR triplets `s{j}_{label}_*` of the reweighted mean of A - B, `s{j}_{label}_sd_*`,
+    `s{j}_{label}_ppos_*` / `_pneg_*` and per threshold `s{j}_{label}_pgain{k}_*` / `_ploss{k}_*`, as the contrast's
+    own file; `scenarios` the names, `labels` the labels.  -> the json block: per scenario the thresholds, the total
+    log-weight, members and skipped and, with the PlanContrast fed alongside and the members' log-weights
+    (rc.member_log_weights, [members][scenarios] in its add order), per threshold the
+    reweighted_coverage_difference of its paired rows'''
+    nk = len(rc.thresholds)
+    maps = []
+    for j, name in enumerate(rc.scenarios):
+        for e, label in enumerate(rc.labels):
+            out_maps = [('', rc.mean(name, e)), ('_sd', rc.sd(name, e)), ('_ppos', rc.prob_positive(name, e)),
+                        ('_pneg', rc.prob_negative(name, e))]
+            for k in range(nk):
+                out_maps += [('_pgain%d' % k, rc.gain(name, e, k)), ('_ploss%d' % k, rc.loss(name, e, k))]
+            maps.append(('s%d_%s' % (j, label), out_maps))
+    save_maps(outfile, maps, {'scenarios': np.array(rc.scenarios), 'labels': np.array(rc.labels)}, signed=True)
+    block = {}
+    lam = getattr(rc, 'member_log_weights', None)
+    for j, name in enumerate(rc.scenarios):
+        rec = {'thresholds': list(rc.thresholds), 'log_total_weight': rc.log_total_weight(name),
+               'members': rc.members(name), 'skipped': rc.skipped(name)}
+        if contrast is not None and lam is not None:
+            rec['levels'] = list(levels)
+            rec['coverage_difference'] = []
+            for k in range(nk):
+                ca, cb, w = contrast.coverage(k)
+                rows = reweighted_coverage_difference(ca, cb, w, [m[j] for m in lam], contrast.cell_area, levels)
+                for label, row in zip(contrast.labels, rows):
+                    row['label'] = label
+                rec['coverage_difference'].append(rows)
+        block[name] = rec
+    return block
+
+
 def save_reweight_excursion(outfile, rx, levels=(0.9, 0.95)):
     '''outfile.npz of the ReweightedExcursion of every scenario ({name: ReweightedExcursion} over one ExcursionMaps)
     through save_maps: per scenario index j and day of the maps, under the label `{day}_s{j}`, the CSR triplets
@@ -7961,7 +8195,8 @@ class PredictiveResult():
     the summary's days, on the edges of quantiles= and the thresholds of arrival=, None unless reweight's
     options['maps'] names 'quantiles' / 'arrival' (the projections then carry a `reweight_histogram`, the plan both);
     `reweight_excursion`: {scenario: ReweightedExcursion} over `excursion`, None unless the maps name 'excursion' (the
-    plan then carries one over its own excursion maps);
+    plan then carries one over its own excursion maps); `reweight_contrast`: the ReweightedContrast of the release
+    plan against the plan of compare=, None unless the maps name 'contrast';
     `catch`: the CatchPosterior of the traps over the model's day fields, None where not asked for
     (the emergence projection and the plan then carry a `catch` of their own where asked for); `information`: the
     InformationPosterior of the described traps over the model's day fields, None where not asked for (the plan then
@@ -7991,7 +8226,8 @@ class PredictiveResult():
                  representative=None, representative_days=None, representative_chains=None, neighbourhood=None,
                  modes=None, dependence=None, pathways=None, pathway_levels=None, proximity=None, origin=None,
                  reweight_histogram=None, reweight_arrival=None, ranking=None, ranking_plans=None,
-                 ranking_levels=None, weather=None, wind=None, reweight_excursion=None):
+                 ranking_levels=None, weather=None, wind=None, reweight_excursion=None, reweight_contrast=None):
+        self.reweight_contrast = reweight_contrast
         self.reweight_excursion = reweight_excursion
         self.weather = weather
         self.wind = wind
@@ -8100,7 +8336,10 @@ class PredictiveResult():
         `s{j}_{label}_parr{k}_*`, dense `s{j}_arrival{k}_q{tag}`), those of a projection or a plan into
         outfile_NAME_reweight_quantiles.npz / outfile_NAME_reweight_arrival.npz; reweighted excursion regions into
         outfile_reweight_excur.npz and outfile_sites_reweight_excur.npz (save_reweight_excursion), their block under
-        `predictive.reweight.excursion` (`predictive.sites.reweight.excursion`); `predictive.reweight` of the json
+        `predictive.reweight.excursion` (`predictive.sites.reweight.excursion`); a reweighted contrast into
+        outfile_reweight_contrast.npz (save_reweight_contrast: `s{j}_{label}_*` as the contrast's own file), its
+        block -- per scenario the thresholds, the total log-weight and per threshold the reweighted coverage
+        difference -- under `predictive.reweight.contrast`; `predictive.reweight` of the json
         then carries `maps` and, with arrival maps, per scenario the reached-area curve `reached_area`
         (`predictive.sites.reweight.reached_area` for a plan).
         Excursion maps go into outfile_excur.npz (save_excursion; those of a release plan into
@@ -8333,6 +8572,11 @@ class PredictiveResult():
                                                     self.excursion_levels)
                     (meta['predictive']['reweight'] if not name else
                      meta['predictive'][name[:-1]].setdefault('reweight', {}))['excursion'] = block
+            # maps=('contrast',): outfile_reweight_contrast.npz, per scenario the coverage difference into the json
+            if self.reweight_contrast is not None:
+                meta['predictive']['reweight']['contrast'] = save_reweight_contrast(
+                    '%s_reweight_contrast' % outfile, self.reweight_contrast, self.contrast,
+                    list(self.arrival_levels or (0.05, 0.5, 0.95)))
         area = getattr(self, 'cell_area', None)
         for name, cp in [('', self.catch)] + [(n + '_', pr.catch) for n, pr in (
                 ('emergence', self.emergence), ('sites', self.sites)) if pr is not None]:
@@ -8629,9 +8873,11 @@ def _check_request(q):
         q.a_levels = check_levels(q.arrival_levels)
         if days is not None:
             check_arrival_days(days)
-    for what, have in (('quantiles', q.levels), ('arrival', q.a_thr), ('excursion', q.ex_thr)):
+    for what, of, have in (('quantiles', 'quantiles', q.levels), ('arrival', 'arrival', q.a_thr),
+                           ('excursion', 'excursion', q.ex_thr),
+                           ('contrast', 'compare', getattr(q, 'compare', None) is not None)):
         if what in _reweight_maps(q) and not have:
-            raise ValueError("reweight: maps=%r reweights the maps of %s=, and there is none" % (what, what))
+            raise ValueError("reweight: maps=%r reweights the maps of %s=, and there is none" % (what, of))
     wanted = [(name, arg, plan) for name, arg, plan in (('emergence', q.emergence, emergence_plan),
                                                         ('exposure', q.exposure, exposure_plan)) if arg is not None]
     q.plans = [(name,) + plan(arg) for name, arg, plan in wanted]      # bad projection arguments
@@ -8895,8 +9141,13 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         per member of the excursion maps the run's log-weights and, once the chains are merged, builds
         `reweight_excursion` = {name: ReweightedExcursion} over `excursion` -- and over the plan's, as
         `sites.reweight_excursion` -- from the kept masks, the members in the merged add order; nothing is added to
-        the evaluation of a member. Without `maps` nothing of this is built or called.
-        Peak, contrast, range, patch, pathway and Monte Carlo error maps and the histograms inside the
+        the evaluation of a member. 'contrast' among the maps (needs compare=) reweights the paired contrast:
+        each chain fills a ReweightedContrast of plan A against plan B on the run's thresholds, fed the run's
+        log-weights and length right after the PlanContrast, merged in chain order into `reweight_contrast`; the
+        per-member coverage rows stay the PlanContrast's, and save() weights them by the members' log-weights
+        (reweighted_coverage_difference). The ranking of ranking= is not reweighted. Without `maps` nothing of
+        this is built or called.
+        Peak, range, patch, pathway and Monte Carlo error maps and the histograms inside the
         neighbourhood and proximity posteriors get none. `reweight_info` carries per scenario the diagnostics of the row
         weights (reweight_diagnostics); a UserWarning where ess < min_ess (reweight['options'] = dict(min_ess=50))
         -- importance reweighting degrades as the new data disagree with the posterior -- and a ValueError naming
@@ -9190,6 +9441,8 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
     prov = [{'source': p[4], 'rows': int(len(p[0])), 'runs': len(p[1]), 'burn': int(burn), 'thin': int(thin)}
             for p in prepared]
     plan_b = merged.get('compare', _FieldSet())
+    if plan_b.reweight_contrast is not None:      # per member of `contrast`, in the merged add order
+        plan_b.reweight_contrast.member_log_weights = plan_b._rw_lam
     ranked = merged.get('ranking', _FieldSet())
     res = PredictiveResult(
         summary=day.summary, rows=int(sum(len(p[0]) for p in prepared)), evaluations=sum(len(p[1]) for p in prepared),
@@ -9209,7 +9462,8 @@ def posterior_predictive(pop_model, chains, burn=0, thin=1, days=None, threshold
         pathway_levels=q.pw_levels if q.pw_thr else None, proximity=day.proximity, origin=day.origin,
         reweight_histogram=day.reweight_histogram, reweight_arrival=day.reweight_arrival,
         reweight_excursion=day.reweight_excursion, ranking=ranked.ranking, ranking_plans=ranked.plan,
-        ranking_levels=q.rk_plan['levels'] if q.rk_plan else None, weather=day.weather, wind=wind_plan)
+        ranking_levels=q.rk_plan['levels'] if q.rk_plan else None, weather=day.weather, wind=wind_plan,
+        reweight_contrast=plan_b.reweight_contrast)
     if day.information is not None:   # the stated convention: past cap / 2 the ensemble bounds the map
         warn_information(day.information)
         if 'sites' in merged:

@@ -48,7 +48,8 @@ members, with the effective sample size of every scenario in the json -- saved a
 PREFIX_NAME_reweight.npz for every projection and plan asked for), and with --reweight-maps quantiles,arrival the
 reweighted quantile maps of --quantiles and arrival maps of --arrival as PREFIX_reweight_quantiles.npz and
 PREFIX_reweight_arrival.npz, and with excursion among them the excursion regions of --excursion under every
-scenario, from the members' kept masks, as PREFIX_reweight_excur.npz; with --catch also the catch-probability maps --
+scenario, from the members' kept masks, as PREFIX_reweight_excur.npz, and with contrast among them the paired
+contrast of --compare-sites under every scenario as PREFIX_reweight_contrast.npz; with --catch also the catch-probability maps --
 per trap 'DAY,RATE[,N]' and cell the posterior mean, sd and the probability (--catch-levels) that a trap of effort
 RATE on model day DAY catches at least N wasps; --catch-emergence: traps over the emergence days of --emergence --
 saved as PREFIX_catch.npz (and PREFIX_emergence_catch.npz, PREFIX_sites_catch.npz); with --neighbourhood also the
@@ -79,7 +80,7 @@ Without --chain a short chain is sampled first (--samples) and saved next to --o
         [--pathways 1,10] [--pathway-connectivity 8] [--pathway-levels 0.05,0.5,0.95]
         [--representative [K]] [--representative-epsilon 0.02] [--representative-central 0.5]
         [--reweight 'NAME:east,north,day,kind,rate[,n];...'] [--reweight-file NAME=weights.npy]
-        [--reweight-maps quantiles,arrival,excursion]
+        [--reweight-maps quantiles,arrival,contrast,excursion]
         [--catch 'DAY,RATE[,N];...'] [--catch-levels 0.5,0.95] [--catch-emergence 'OBSDAY,RATE[,N];...']
         [--information 'DAY,RATE[,YMAX];...'] [--neighbourhood 'DAY,RADIUS_M;...']
         [--proximity 'DAY,T[,in];...'] [--proximity-radii 100,400,1600] [--proximity-levels 0.05,0.5,0.95]
@@ -279,21 +280,25 @@ def main():
     ap.add_argument('--reweight-file', action='append', default=None, metavar='NAME=NPY',
                     help='a reweighting scenario from a .npy of one log-weight per chain row after burn and thin '
                          '(repeatable)')
-    ap.add_argument('--reweight-maps', default='', metavar='quantiles,arrival,excursion',
+    ap.add_argument('--reweight-maps', default='', metavar='quantiles,arrival,contrast,excursion',
                     help='with --reweight / --reweight-file: also reweight the quantile maps (needs --quantiles), '
-                         'the arrival maps (needs --arrival) and the excursion regions (needs --excursion), saved as '
-                         'PREFIX_reweight_quantiles.npz / PREFIX_reweight_arrival.npz / PREFIX_reweight_excur.npz '
+                         'the arrival maps (needs --arrival), the excursion regions (needs --excursion) and the paired '
+                         'contrast of two plans (needs --compare-sites), saved as PREFIX_reweight_quantiles.npz / '
+                         'PREFIX_reweight_arrival.npz / PREFIX_reweight_excur.npz / PREFIX_reweight_contrast.npz '
                          '(default: off)')
     args = ap.parse_args()
     rw_specs, rw_files = parse_reweight(ap, args.reweight, args.reweight_file)
     rw_maps = [m.strip() for m in args.reweight_maps.split(',') if m.strip()]
     if rw_maps and not (rw_specs or rw_files):
         ap.error('--reweight-maps reweights more maps of a scenario: give --reweight or --reweight-file too')
-    if [m for m in rw_maps if m not in ('quantiles', 'arrival', 'excursion')] or len(set(rw_maps)) != len(rw_maps):
-        ap.error("--reweight-maps takes a subset of 'quantiles,arrival,excursion', got %r" % args.reweight_maps)
+    if [m for m in rw_maps if m not in ('quantiles', 'arrival', 'contrast', 'excursion')] \
+            or len(set(rw_maps)) != len(rw_maps):
+        ap.error("--reweight-maps takes a subset of 'quantiles,arrival,contrast,excursion', got %r" % args.reweight_maps)
     for m in rw_maps:
-        if not getattr(args, m).strip():
-            ap.error('--reweight-maps %s reweights the maps of --%s: give --%s too' % (m, m, m))
+        of = 'compare_sites' if m == 'contrast' else m
+        if not (getattr(args, of) or '').strip():
+            ap.error('--reweight-maps %s reweights the maps of --%s: give --%s too'
+                     % (m, of.replace('_', '-'), of.replace('_', '-')))
     if args.compare_sites and not args.sites:
         ap.error('--compare-sites names plan B and needs plan A: give --sites too')
     if args.rank_sites and not args.sites:
@@ -545,6 +550,14 @@ def main():
         SC = SpreadSummary.for_projection(RS, thr)
         XC.profile(True)
         SC.profile(True)
+    XW = []                              # the reweighted contrast: the request's scenarios, then four (the first's log-weights)
+    if compare and reweight and 'contrast' in rw_maps:
+        from parasitoids_amd.predictive import ReweightedContrast
+        XW = [ReweightedContrast(RS, RB, rw_plan['names'], thr)]
+        if len(rw_plan['names']) != 4:
+            XW.append(ReweightedContrast(RS, RB, ['s0', 's1', 's2', 's3'], thr))
+        for h in XW:
+            h.profile(True)
     projections = [Projection(pm, W, in_days) for W, in_days, _labels in plans]
     H = SpreadHistogram(pm, None, bins) if levels else None
     A = ArrivalMaps(pm, arrival) if arrival else None
@@ -698,6 +711,8 @@ def main():
                     RB.apply()
                     SC.add(length)
                     XC.add(length)
+                    for h in XW:
+                        h.add([lam[j % len(lam)] for j in range(len(h.scenarios))], length)
                 if XR is not None:
                     for R in RR:
                         R.apply()
@@ -799,7 +814,9 @@ def main():
         c_ms, c_launches = XC.profile()
         cs_ms, cs_launches = SC.profile()
         c_bytes = XC.nbytes
-        for h in (XC, SC, RB):
+        xw_report = [{'scenarios': len(h.scenarios), 'add_ms_per_member': round(h.profile()[0] / max(h.profile()[1], 1), 4),
+                      'launches_timed': h.profile()[1], 'bytes': h.nbytes} for h in XW]
+        for h in XW + [XC, SC, RB]:
             h.close()
     if XR is not None:
         r_ms, r_launches = XR.profile()
@@ -888,7 +905,8 @@ def main():
             out['reweight_maps'] = rw_maps
             out['reweight_maps_ms_per_member'] = round(rwm_ms / max(rwm_members, 1), 4)
             out['reweight_maps_detail'] = rwm_detail
-            out['outputs'] += ['%s_reweight_%s.npz' % (args.out, 'excur' if m == 'excursion' else m) for m in rw_maps]
+            out['outputs'] += ['%s_reweight_%s.npz' % (args.out, 'excur' if m == 'excursion' else m) for m in rw_maps
+                               if m != 'contrast']
         out['reweight_diagnostics'] = res.reweight_info['diagnostics']
         out['outputs'] += ['%s_reweight.npz' % args.out] + ['%s_%s_reweight.npz' % (args.out, n) for n, on in
                                                             (('emergence', emergence), ('exposure', exposure),
@@ -1009,6 +1027,15 @@ def main():
         out['contrast_read_GBps'] = round(16 * ncell * len(sites['days']) / (c_ms / max(c_launches, 1) * 1e-3) / 1e9, 1) \
             if c_ms > 0 else None
         out['contrast_bytes'] = c_bytes
+        if xw_report:
+            # what every add must move: both plans' fields and one mean per scenario, 16 + 8 J B per cell and output
+            out['reweight_contrast_add_ms_per_member'] = xw_report[0]['add_ms_per_member']
+            for rec in xw_report:
+                ms_add = rec['add_ms_per_member']
+                rec['read_GBps'] = round((16 + rec['scenarios'] * 8) * ncell * len(sites['days'])
+                                         / (ms_add * 1e-3) / 1e9, 1) if ms_add > 0 else None
+            out['reweight_contrast_detail'] = xw_report
+            out['outputs'] += ['%s_reweight_contrast.npz' % args.out]
         out['outputs'] += ['%s_contrast.npz' % args.out]
     if ranking:
         out['ranking_add_ms_per_member'] = round(r_ms / max(r_launches, 1), 4)
