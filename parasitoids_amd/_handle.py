@@ -3,14 +3,18 @@
 calls behind it, the counters of ps_<x>_info, profiling, the index checks -- and the two ways an add or an
 apply reads its fields: the day records of the model's last evaluation, or the outputs of a fields source.  A class
 states its `_prefix`, `_info_types`, `_prof_pairs` and `_noun`, calls `_attach` and `_create`, and keeps only what is
-its own; `_Accumulator` adds reset, total_weight and members for those that sum weighted members.  HipSolve and
-WindModel are not of this kind: their handles are retargeted and cached.
+its own; `_Accumulator` adds reset, total_weight and members for those that sum weighted members, `_FieldSource`
+what the sources of fields share.  HipSolve and WindModel are not of this kind: their handles are retargeted and
+cached.
 """
 import ctypes as C
+
+import numpy as np
 
 from . import _lib as L
 
 NEGVAL = 1e-8          # r_small_vals threshold of the daily solutions (CalcSol.py:126-132)
+MAX_PROJECT_IN = 32    # ps_project: the input records of one launch's descriptors
 
 
 def _day_slots(days):
@@ -31,6 +35,16 @@ def _check_evaluated(pm, days, what):
     nd = getattr(pm, '_nd', 0)
     if pm.solver is None or max(days) >= nd:
         raise ValueError('the last evaluation has %d days; the %s needs day %d' % (nd, what, max(days)))
+
+
+def check_in_days(in_days):
+    '''a projection's input days as a list of ints: 1..32 model days >= 0, strictly increasing'''
+    d = [int(x) for x in in_days]
+    if not 1 <= len(d) <= MAX_PROJECT_IN:
+        raise ValueError('%d projection input days; 1..%d fit one launch' % (len(d), MAX_PROJECT_IN))
+    if d[0] < 0 or any(b <= a for a, b in zip(d, d[1:])):
+        raise ValueError('projection input days must be model days >= 0, strictly increasing: %r' % (d,))
+    return d
 
 
 class _Handle():
@@ -168,3 +182,93 @@ class _Accumulator(_Handle):
         '''the add that takes the weight and nothing else'''
         w = self._weight(weight)
         self._read('add', self._proj, w)
+
+
+class _FieldSource(_Handle):
+    '''a handle whose apply leaves `nout` fields on the device, those of `live` carrying weight, which the accumulators
+    read through their for_projection: a projection, a release plan, or fields computed per item (a trap, a window)
+    from one input each -- a model day, or an output of a projection or a plan.  A class of the last kind states the
+    attribute its items live under (`_items`: 'traps'), the word its messages use (`_item`: 'trap'), its item check
+    (`_check`), its input limit (`_max_in`) and `_setup(pop_model, inputs, nin)`, and gives `_from_days` and `_over`
+    its own constructor and for_projection to keep their argument names.'''
+    _items = _item = _check = _max_in = None
+    _info_n = 4            # the out-parameters of ps_<x>_info; the applies are the last
+    _source = None         # the projection or plan whose outputs an apply reads; None: the model's day records
+
+    def _from_days(self, pop_model, items, days):
+        '''the constructor: an item's first entry is a model day; days: the model days the handle reads, default the
+        items' own'''
+        items = self._check(items)
+        setattr(self, self._items, items)
+        used = sorted({t[0] for t in items})
+        self.in_days = used if days is None else check_in_days(days)
+        if len(self.in_days) > self._max_in:
+            raise ValueError('%d input days; at most %d fit one handle' % (len(self.in_days), self._max_in))
+        missing = [d for d in used if d not in self.in_days]
+        if missing:
+            raise ValueError('%s days %r are not among the days %r' % (self._item, missing, self.in_days))
+        self._source = None
+        self._setup(pop_model, [self.in_days.index(t[0]) for t in items], len(self.in_days))
+        self._set_days(self.in_days)
+
+    @classmethod
+    def _over(cls, source, items, labels):
+        '''for_projection: an item's first entry is the output label of `source` (labels: one per output, default a
+        ReleaseSites' output days, else the output indices); an output without weight is refused'''
+        self = cls.__new__(cls)
+        items = cls._check(items, 'output')
+        setattr(self, cls._items, items)
+        if labels is None:
+            labels = getattr(source, 'days', None) if source.fields_kind == 'sites' else None
+        labels = list(range(source.nout)) if labels is None else [int(x) for x in labels]
+        if len(labels) != source.nout:
+            raise ValueError('%d labels for %d outputs' % (len(labels), source.nout))
+        slot = {e: i for i, e in enumerate(source.live)}        # the source's device slot of every output
+        inputs = []
+        for t in items:
+            if t[0] not in labels or labels.index(t[0]) not in slot:
+                raise ValueError('%s %r: %d is not an output that carries weight (%r)' % (cls._item, t, t[0], labels))
+            inputs.append(slot[labels.index(t[0])])
+        self.in_days = None
+        self._source = source
+        self._setup(source.pm, inputs, len(source.live))
+        return self
+
+    def apply(self):
+        '''The fields of the last evaluation of the model (enqueued on the solver's stream), or of the source's last
+        apply (on the handle's stream); no host synchronisation; the outputs of the previous apply are
+        overwritten.'''
+        self._read('apply', self._source)
+
+    @property
+    def applies(self):
+        '''the applies so far; of a release plan the complete passes over its groups'''
+        n = C.c_int64()
+        self._call('info', *[None] * (self._info_n - 1), C.byref(n))
+        return n.value
+
+    def field(self, e):
+        '''[N, N] float64: output e of the last apply; zeros for an output without weight, which is kept off the
+        device'''
+        e = self._e(e)
+        if e not in self.live:
+            return np.zeros((self.N, self.N), dtype=np.float64)
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        self._call('fetch', self.live.index(e), L.p_f64(out))
+        return out
+
+    def gather(self, rows, cols):
+        '''[nout, n] float64: every output of the last apply at the cells (rows[k], cols[k])'''
+        rows, cols = L.i32(np.asarray(rows).ravel()), L.i32(np.asarray(cols).ravel())
+        if rows.size != cols.size:
+            raise ValueError('%d rows and %d columns' % (rows.size, cols.size))
+        out = np.zeros((self.nout, rows.size), dtype=np.float64)
+        got = out if len(self.live) == self.nout else np.zeros((len(self.live), rows.size), dtype=np.float64)
+        self._call('gather', rows.size, L.p_i32(rows), L.p_i32(cols), L.p_f64(got))
+        if got is not out:
+            out[self.live] = got
+        return out
+
+    def profile(self, enable=None):
+        '''HIP-event time of the apply launches: (total ms, launches) per timed pass; enable switches it'''
+        return self._profile(enable)

@@ -23,13 +23,8 @@
 
 namespace {
 
-struct ArrSlot {
-  const double* rec;
-  const ps_day_stats* stats;   // nullptr: no delta
-  double stat_scale, post_scale;
-};
 struct ArrSlots {
-  ArrSlot s[PS_ARR_MAX_SLOT];
+  PsSrc s[PS_ARR_MAX_SLOT];
 };
 struct ArrThr {
   double t[PS_ARR_MAX_THR];
@@ -70,7 +65,7 @@ __global__ void __launch_bounds__(PS_ARR_THREADS) k_arrival_add(ArrSlots desc, A
     double2 rn = make_double2(0.0, 0.0);
     if (live && s + 1 < nslot) arr_load(desc.s[s + 1].rec, pair, i, rn);
     if (live) {
-      const ArrSlot& sd = desc.s[s];
+      const PsSrc& sd = desc.s[s];
       const double delta = sdelta[s];
       const double v0 = ps_record_value(r.x, sd.stat_scale, sd.post_scale, delta, negval);
       const double v1 = pair ? ps_record_value(r.y, sd.stat_scale, sd.post_scale, delta, negval) : 0.0;
@@ -337,16 +332,9 @@ extern "C" int ps_arrival_add(ps_arrival* a, ps_solver* s, int nslot, const int3
   // every descriptor first: an add with a bad slot enqueues nothing
   ArrSlots desc;
   hipStream_t stream = nullptr;
-  for (int i = 0; i < nslot; ++i) {
-    PsRecordView v;
-    PS_TRY(ps_solver_record_internal(s, kind[i], idx[i], use_delta[i] != 0, &v));
-    if (v.device != a->device)
-      return ps_fail(PS_ERR_BAD_ARG, "arrival_add: solver on device %d, handle on device %d", v.device, a->device);
-    if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "arrival_add: solver domain %d, handle domain %d", v.N, a->N);
-    desc.s[i] = ArrSlot{v.rec, v.stats, stat_scale[i], post_scale[i]};
-    stream = v.stream;
-  }
-  for (int i = nslot; i < PS_ARR_MAX_SLOT; ++i) desc.s[i] = ArrSlot{nullptr, nullptr, 0.0, 0.0};
+  PS_TRY(ps_read_records("arrival_add", "handle", a->device, a->N, s, nslot, kind, idx, stat_scale, post_scale,
+                         use_delta, false, desc.s, &stream));
+  for (int i = nslot; i < PS_ARR_MAX_SLOT; ++i) desc.s[i] = PsSrc{nullptr, nullptr, 0.0, 0.0};
   return arr_launch(a, desc, stream, negval, weight);
 }
 
@@ -358,18 +346,11 @@ static int arr_add_fields(ps_arrival* a, void* h, const PsFieldsOps& src, const 
   if (a->W + weight > 0xffffffffull)
     return ps_fail(PS_ERR_BAD_ARG, "%s: total weight %llu would overflow the uint32 counts", who,
                    (unsigned long long)(a->W + weight));
-  PsProjectView v;
-  PS_TRY(src.view(h, &v));
-  if (v.nout != a->nslot)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: the %s has %d outputs, the handle %d slots", who, src.what, v.nout, a->nslot);
-  if (v.device != a->device)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: %s on device %d, handle on device %d", who, src.what, v.device, a->device);
-  if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "%s: %s domain %d, handle domain %d", who, src.what, v.N, a->N);
-  PS_HIP(hipSetDevice(a->device));
   // slot e takes Y_e: no statistics, both scales 1 and negval 0, so the value rule returns Y itself
   ArrSlots desc;
-  for (int e = 0; e < PS_ARR_MAX_SLOT; ++e)
-    desc.s[e] = e < a->nslot ? ArrSlot{v.Y + (int64_t)e * v.pitch, nullptr, 1.0, 1.0} : ArrSlot{nullptr, nullptr, 0.0, 0.0};
+  PS_TRY(ps_read_fields(who, "handle", "slots", a->device, a->N, a->nslot, h, src, desc.s));
+  for (int e = a->nslot; e < PS_ARR_MAX_SLOT; ++e) desc.s[e] = PsSrc{nullptr, nullptr, 0.0, 0.0};
+  PS_HIP(hipSetDevice(a->device));
   PS_TRY(src.wait(h, a->stream));
   PS_TRY(arr_launch(a, desc, a->stream, 0.0, weight));
   return src.mark(h, a->stream);   // the next apply overwrites Y only after this read

@@ -231,6 +231,48 @@ struct PsRecordView {
 };
 int ps_solver_record_internal(ps_solver* s, int kind, int idx, int want_stats, PsRecordView* out);
 
+// Where one slot of an add, or one input of an apply, reads its field: a solver record with the scales of the
+// value rule (ps_record_value), or an output of a fields source (no statistics, both scales 1).  The kernels take
+// blocks of these by value, some inside a struct of their own that adds the slot.
+struct PsSrc {
+  const double* rec;           // nullptr: PS_REC_NONE
+  const ps_day_stats* stats;   // nullptr: no delta
+  double stat_scale, post_scale;
+};
+// the same inside a kernel's own descriptor {rec, stats, stat_scale, post_scale, slot}, where the kernel reads the slot
+template <typename Slot>
+static inline Slot ps_slotted(const PsSrc& r, int slot) {
+  return Slot{r.rec, r.stats, r.stat_scale, r.post_scale, slot};
+}
+
+// out[0..n): the records (kind[i], idx[i]) of the solver's last evaluation, for a handle (noun: what the messages
+// call it, who: the entry point) on `device` with domain N; a solver on another device or of another domain is
+// refused.  *stream becomes the stream the records are written on.  none_ok: a PS_REC_NONE slot gives the all-null
+// descriptor and names no stream; *any (may be nullptr) says whether any slot named one.  Nothing is enqueued and
+// no handle is touched, so a caller that resolves first enqueues nothing for a bad slot.  This is the one caller
+// of ps_solver_record_internal; static, as ps_read_fields, so that the library exports no symbol for either.
+static inline int ps_read_records(const char* who, const char* noun, int device, int N, ps_solver* s, int n,
+                                  const int32_t* kind, const int32_t* idx, const double* stat_scale,
+                                  const double* post_scale, const int32_t* use_delta, bool none_ok, PsSrc* out,
+                                  hipStream_t* stream, bool* any = nullptr) {
+  if (any) *any = false;
+  for (int i = 0; i < n; ++i) {
+    if (none_ok && kind[i] == PS_REC_NONE) {
+      out[i] = PsSrc{nullptr, nullptr, 0.0, 0.0};
+      continue;
+    }
+    PsRecordView v;
+    PS_TRY(ps_solver_record_internal(s, kind[i], idx[i], use_delta[i] != 0, &v));
+    if (v.device != device)
+      return ps_fail(PS_ERR_BAD_ARG, "%s: solver on device %d, %s on device %d", who, v.device, noun, device);
+    if (v.N != N) return ps_fail(PS_ERR_BAD_ARG, "%s: solver domain %d, %s domain %d", who, v.N, noun, N);
+    out[i] = PsSrc{v.rec, v.stats, stat_scale[i], post_scale[i]};
+    *stream = v.stream;
+    if (any) *any = true;
+  }
+  return PS_OK;
+}
+
 // the output fields of a projection that ps_summary.hip and ps_hist.hip accumulate (ps_project.hip);
 // PS_ERR_STATE before the first apply.  A reader orders its stream behind the projection's last operation
 // (wait), and the projection's next apply behind the read (mark).
@@ -242,12 +284,30 @@ struct PsProjectView {
 // The same triple for every handle that owns such fields, so that an accumulator has one code path for all
 // of them: the projections (ps_project.hip) and the release plans (ps_sites.hip, PS_ERR_STATE also while a
 // pass over the plan's groups is under way).  what: the handle's name in the accumulators' messages.
+// A reader resolves the fields with ps_read_fields, then wait, its launches on its own stream, mark.
 struct PsFieldsOps {
   const char* what;
   int (*view)(void* handle, PsProjectView* out);
   int (*wait)(void* handle, hipStream_t stream);
   int (*mark)(void* handle, hipStream_t stream);
 };
+
+// out[0..n): output e of the fields source h as slot (units "slots") or input (units "inputs") e of a handle
+// (noun, who: as ps_read_records) on `device` with domain N that has n of them -- Y_e itself under the value
+// rule: no statistics, both scales 1.  Refused in this order: a source that is not ready (view), another number
+// of outputs, another device, another domain.  wait, the launch and mark stay with the caller.
+static inline int ps_read_fields(const char* who, const char* noun, const char* units, int device, int N, int n,
+                                 void* h, const PsFieldsOps& src, PsSrc* out) {
+  PsProjectView v;
+  PS_TRY(src.view(h, &v));
+  if (v.nout != n)
+    return ps_fail(PS_ERR_BAD_ARG, "%s: the %s has %d outputs, the %s %d %s", who, src.what, v.nout, noun, n, units);
+  if (v.device != device)
+    return ps_fail(PS_ERR_BAD_ARG, "%s: %s on device %d, %s on device %d", who, src.what, v.device, noun, device);
+  if (v.N != N) return ps_fail(PS_ERR_BAD_ARG, "%s: %s domain %d, %s domain %d", who, src.what, v.N, noun, N);
+  for (int e = 0; e < n; ++e) out[e] = PsSrc{v.Y + (int64_t)e * v.pitch, nullptr, 1.0, 1.0};
+  return PS_OK;
+}
 PsFieldsOps ps_project_fields();
 PsFieldsOps ps_sites_fields();
 PsFieldsOps ps_peak_fields();    // the last member's peak field of a ps_peak (ps_peak.hip): nout = 1

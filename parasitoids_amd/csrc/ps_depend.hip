@@ -334,7 +334,7 @@ static int dep_check_add(ps_depend* a, const char* who, int nparam, const int32_
 }
 
 // one member from the slot descriptors d (one per slot of the handle), enqueued on `stream`
-static int dep_launch(ps_depend* a, const std::vector<DepSlot>& d, hipStream_t stream, double negval,
+static int dep_launch(ps_depend* a, const std::vector<PsSrc>& d, hipStream_t stream, double negval,
                       const int32_t* bin, uint32_t weight) {
   const int nslot = a->nslot;
   PS_TRY(a->last.wait(stream));
@@ -349,7 +349,7 @@ static int dep_launch(ps_depend* a, const std::vector<DepSlot>& d, hipStream_t s
   for (int c0 = 0; c0 < nslot; c0 += PS_DEP_CHUNK) {
     const int n = std::min(PS_DEP_CHUNK, nslot - c0);
     DepSlots desc;
-    for (int i = 0; i < n; ++i) desc.s[i] = d[(size_t)(c0 + i)];
+    for (int i = 0; i < n; ++i) desc.s[i] = ps_slotted<DepSlot>(d[(size_t)(c0 + i)], c0 + i);
     hipLaunchKernelGGL(dep_add_kernels[a->nparam - 1], dim3(bx, n), dim3(threads), 0, stream, desc, a->mean, a->m2,
                        a->S, a->ncell, a->pitch, dep_total(a), pl, negval, (double)weight, Wn);
     PS_HIP(hipGetLastError());
@@ -372,17 +372,10 @@ extern "C" int ps_depend_add(ps_depend* a, ps_solver* s, int nslot, const int32_
     return ps_fail(PS_ERR_BAD_ARG, "depend_add: %d slots given, the handle has %d", nslot, a->nslot);
   PS_HIP(hipSetDevice(a->device));
   // every descriptor first: an add with a bad slot enqueues nothing
-  std::vector<DepSlot> d((size_t)nslot);
+  std::vector<PsSrc> d((size_t)nslot);
   hipStream_t stream = nullptr;
-  for (int i = 0; i < nslot; ++i) {
-    PsRecordView v;
-    PS_TRY(ps_solver_record_internal(s, kind[i], idx[i], use_delta[i] != 0, &v));
-    if (v.device != a->device)
-      return ps_fail(PS_ERR_BAD_ARG, "depend_add: solver on device %d, handle on device %d", v.device, a->device);
-    if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "depend_add: solver domain %d, handle domain %d", v.N, a->N);
-    d[i] = DepSlot{v.rec, v.stats, stat_scale[i], post_scale[i], i};
-    stream = v.stream;
-  }
+  PS_TRY(ps_read_records("depend_add", "handle", a->device, a->N, s, nslot, kind, idx, stat_scale, post_scale,
+                         use_delta, false, d.data(), &stream));
   return dep_launch(a, d, stream, negval, bin, weight);
 }
 
@@ -391,17 +384,10 @@ static int dep_add_fields(ps_depend* a, void* h, const PsFieldsOps& src, const c
                           const int32_t* bin, uint32_t weight) {
   if (!h) return ps_fail(PS_ERR_BAD_ARG, "%s: bad arguments", who);
   PS_TRY(dep_check_add(a, who, nparam, bin, weight));
-  PsProjectView v;
-  PS_TRY(src.view(h, &v));
-  if (v.nout != a->nslot)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: the %s has %d outputs, the handle %d slots", who, src.what, v.nout, a->nslot);
-  if (v.device != a->device)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: %s on device %d, handle on device %d", who, src.what, v.device, a->device);
-  if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "%s: %s domain %d, handle domain %d", who, src.what, v.N, a->N);
-  PS_HIP(hipSetDevice(a->device));
   // slot k takes Y_k: no statistics, both scales 1 and negval 0, so the value rule returns Y itself
-  std::vector<DepSlot> d((size_t)a->nslot);
-  for (int k = 0; k < a->nslot; ++k) d[(size_t)k] = DepSlot{v.Y + (int64_t)k * v.pitch, nullptr, 1.0, 1.0, k};
+  std::vector<PsSrc> d((size_t)a->nslot);
+  PS_TRY(ps_read_fields(who, "handle", "slots", a->device, a->N, a->nslot, h, src, d.data()));
+  PS_HIP(hipSetDevice(a->device));
   PS_TRY(src.wait(h, a->stream));
   PS_TRY(dep_launch(a, d, a->stream, 0.0, bin, weight));
   return src.mark(h, a->stream);   // the next apply overwrites Y only after this read

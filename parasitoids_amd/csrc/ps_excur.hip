@@ -28,13 +28,8 @@
 
 namespace {
 
-struct ExcSlot {
-  const double* rec;
-  const ps_day_stats* stats;   // nullptr: no delta
-  double stat_scale, post_scale;
-};
 struct ExcSlots {
-  ExcSlot s[PS_EXC_MAX_SLOT];
+  PsSrc s[PS_EXC_MAX_SLOT];
 };
 struct ExcThr {
   double t[PS_EXC_MAX_THR];
@@ -59,7 +54,7 @@ __global__ void __launch_bounds__(PS_EXC_THREADS) k_excur_add(ExcSlots desc, Exc
   for (int s = 0; s < nslot; ++s) {
     double rn = 0.0;
     if (real && s + 1 < nslot) rn = desc.s[s + 1].rec[i];
-    const ExcSlot& sd = desc.s[s];
+    const PsSrc& sd = desc.s[s];
     const double v = real ? ps_record_value(r, sd.stat_scale, sd.post_scale, sdelta[s], negval) : 0.0;
 #pragma unroll
     for (int k = 0; k < PS_EXC_MAX_THR; ++k) {
@@ -363,16 +358,9 @@ extern "C" int ps_excur_add(ps_excur* a, ps_solver* s, int nslot, const int32_t*
   // every descriptor first: an add with a bad slot enqueues nothing
   ExcSlots desc;
   hipStream_t stream = nullptr;
-  for (int i = 0; i < nslot; ++i) {
-    PsRecordView v;
-    PS_TRY(ps_solver_record_internal(s, kind[i], idx[i], use_delta[i] != 0, &v));
-    if (v.device != a->device)
-      return ps_fail(PS_ERR_BAD_ARG, "excur_add: solver on device %d, handle on device %d", v.device, a->device);
-    if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "excur_add: solver domain %d, handle domain %d", v.N, a->N);
-    desc.s[i] = ExcSlot{v.rec, v.stats, stat_scale[i], post_scale[i]};
-    stream = v.stream;
-  }
-  for (int i = nslot; i < PS_EXC_MAX_SLOT; ++i) desc.s[i] = ExcSlot{nullptr, nullptr, 0.0, 0.0};
+  PS_TRY(ps_read_records("excur_add", "handle", a->device, a->N, s, nslot, kind, idx, stat_scale, post_scale, use_delta,
+                         false, desc.s, &stream));
+  for (int i = nslot; i < PS_EXC_MAX_SLOT; ++i) desc.s[i] = PsSrc{nullptr, nullptr, 0.0, 0.0};
   return exc_launch(a, desc, stream, negval, weight, "excur_add");
 }
 
@@ -381,18 +369,11 @@ extern "C" int ps_excur_add(ps_excur* a, ps_solver* s, int nslot, const int32_t*
 static int exc_add_fields(ps_excur* a, void* h, const PsFieldsOps& src, const char* who, uint32_t weight) {
   if (!a || !h) return ps_fail(PS_ERR_BAD_ARG, "%s: bad arguments", who);
   PS_TRY(exc_check_weight(a, who, weight));
-  PsProjectView v;
-  PS_TRY(src.view(h, &v));
-  if (v.nout != a->nslot)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: the %s has %d outputs, the handle %d slots", who, src.what, v.nout, a->nslot);
-  if (v.device != a->device)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: %s on device %d, handle on device %d", who, src.what, v.device, a->device);
-  if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "%s: %s domain %d, handle domain %d", who, src.what, v.N, a->N);
-  PS_HIP(hipSetDevice(a->device));
   // slot e takes Y_e: no statistics, both scales 1 and negval 0, so the value rule returns Y itself
   ExcSlots desc;
-  for (int e = 0; e < PS_EXC_MAX_SLOT; ++e)
-    desc.s[e] = e < a->nslot ? ExcSlot{v.Y + (int64_t)e * v.pitch, nullptr, 1.0, 1.0} : ExcSlot{nullptr, nullptr, 0.0, 0.0};
+  PS_TRY(ps_read_fields(who, "handle", "slots", a->device, a->N, a->nslot, h, src, desc.s));
+  for (int e = a->nslot; e < PS_EXC_MAX_SLOT; ++e) desc.s[e] = PsSrc{nullptr, nullptr, 0.0, 0.0};
+  PS_HIP(hipSetDevice(a->device));
   PS_TRY(src.wait(h, a->stream));
   PS_TRY(exc_launch(a, desc, a->stream, 0.0, weight, who));
   return src.mark(h, a->stream);   // the next apply overwrites the source's fields only after this read

@@ -29,13 +29,8 @@
 
 namespace {
 
-struct GainSlot {
-  const double* rec;
-  const ps_day_stats* stats;   // nullptr: no delta
-  double stat_scale, post_scale;
-};
 struct GainSlots {
-  GainSlot s[PS_GAIN_MAX_IN];
+  PsSrc s[PS_GAIN_MAX_IN];
 };
 // the traps in group order: group g reads input gin[g] and owns the entries gstart[g] .. gstart[g + 1] - 1
 struct GainTab {
@@ -351,16 +346,9 @@ extern "C" int ps_gain_apply(ps_gain* c, ps_solver* s, int nin, const int32_t* k
   // every descriptor first: an apply with a bad record enqueues nothing
   GainSlots desc;
   hipStream_t stream = nullptr;
-  for (int i = 0; i < nin; ++i) {
-    PsRecordView v;
-    PS_TRY(ps_solver_record_internal(s, kind[i], idx[i], use_delta[i] != 0, &v));
-    if (v.device != c->device)
-      return ps_fail(PS_ERR_BAD_ARG, "gain_apply: solver on device %d, handle on device %d", v.device, c->device);
-    if (v.N != c->N) return ps_fail(PS_ERR_BAD_ARG, "gain_apply: solver domain %d, handle domain %d", v.N, c->N);
-    desc.s[i] = GainSlot{v.rec, v.stats, stat_scale[i], post_scale[i]};
-    stream = v.stream;
-  }
-  for (int i = nin; i < PS_GAIN_MAX_IN; ++i) desc.s[i] = GainSlot{nullptr, nullptr, 0.0, 0.0};
+  PS_TRY(ps_read_records("gain_apply", "handle", c->device, c->N, s, nin, kind, idx, stat_scale, post_scale, use_delta,
+                         false, desc.s, &stream));
+  for (int i = nin; i < PS_GAIN_MAX_IN; ++i) desc.s[i] = PsSrc{nullptr, nullptr, 0.0, 0.0};
   return gain_launch(c, desc, stream, negval);
 }
 
@@ -368,18 +356,11 @@ extern "C" int ps_gain_apply(ps_gain* c, ps_solver* s, int nin, const int32_t* k
 // source's output i, on the handle's stream behind the source's last operation
 static int gain_apply_fields(ps_gain* c, void* h, const PsFieldsOps& src, const char* who) {
   if (!c || !h) return ps_fail(PS_ERR_BAD_ARG, "%s: bad arguments", who);
-  PsProjectView v;
-  PS_TRY(src.view(h, &v));
-  if (v.nout != c->nin)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: the %s has %d outputs, the handle %d inputs", who, src.what, v.nout, c->nin);
-  if (v.device != c->device)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: %s on device %d, handle on device %d", who, src.what, v.device, c->device);
-  if (v.N != c->N) return ps_fail(PS_ERR_BAD_ARG, "%s: %s domain %d, handle domain %d", who, src.what, v.N, c->N);
-  PS_HIP(hipSetDevice(c->device));
   // input i takes Y_i: no statistics, both scales 1 and negval 0, so the value rule returns Y itself
   GainSlots desc;
-  for (int i = 0; i < PS_GAIN_MAX_IN; ++i)
-    desc.s[i] = i < c->nin ? GainSlot{v.Y + (int64_t)i * v.pitch, nullptr, 1.0, 1.0} : GainSlot{nullptr, nullptr, 0.0, 0.0};
+  PS_TRY(ps_read_fields(who, "handle", "inputs", c->device, c->N, c->nin, h, src, desc.s));
+  for (int i = c->nin; i < PS_GAIN_MAX_IN; ++i) desc.s[i] = PsSrc{nullptr, nullptr, 0.0, 0.0};
+  PS_HIP(hipSetDevice(c->device));
   PS_TRY(src.wait(h, c->stream));
   PS_TRY(gain_launch(c, desc, c->stream, 0.0));
   return src.mark(h, c->stream);   // the source's next apply overwrites its fields only after this read

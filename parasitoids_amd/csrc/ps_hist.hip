@@ -243,7 +243,7 @@ extern "C" int ps_hist_create(int device, int N, int nslot, int nedge, const dou
 }
 
 // one member from the slot descriptors d (one per slot of the histogram), enqueued on `stream`
-static int hist_launch(ps_hist* a, const std::vector<HistSlot>& d, hipStream_t stream, double negval,
+static int hist_launch(ps_hist* a, const std::vector<PsSrc>& d, hipStream_t stream, double negval,
                        uint32_t weight) {
   const int nslot = a->nslot;
   PS_TRY(a->last.wait(stream));
@@ -255,7 +255,7 @@ static int hist_launch(ps_hist* a, const std::vector<HistSlot>& d, hipStream_t s
   for (int c0 = 0; c0 < nslot; c0 += PS_HIST_CHUNK) {
     const int n = std::min(PS_HIST_CHUNK, nslot - c0);
     HistSlots desc;
-    for (int i = 0; i < n; ++i) desc.s[i] = d[(size_t)(c0 + i)];
+    for (int i = 0; i < n; ++i) desc.s[i] = ps_slotted<HistSlot>(d[(size_t)(c0 + i)], c0 + i);
     hipLaunchKernelGGL(k_hist_add, dim3(bx, n), dim3(threads), 0, stream, desc, a->d_edges, a->nedge, a->cnt, a->rng,
                        a->ncell, a->pitch, negval, weight);
     PS_HIP(hipGetLastError());
@@ -279,17 +279,10 @@ extern "C" int ps_hist_add(ps_hist* a, ps_solver* s, int nslot, const int32_t* k
                    (unsigned long long)(a->W + weight));
   PS_HIP(hipSetDevice(a->device));
   // every descriptor first: an add with a bad slot enqueues nothing
-  std::vector<HistSlot> d((size_t)nslot);
+  std::vector<PsSrc> d((size_t)nslot);
   hipStream_t stream = nullptr;
-  for (int i = 0; i < nslot; ++i) {
-    PsRecordView v;
-    PS_TRY(ps_solver_record_internal(s, kind[i], idx[i], use_delta[i] != 0, &v));
-    if (v.device != a->device)
-      return ps_fail(PS_ERR_BAD_ARG, "hist_add: solver on device %d, histogram on device %d", v.device, a->device);
-    if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "hist_add: solver domain %d, histogram domain %d", v.N, a->N);
-    d[i] = HistSlot{v.rec, v.stats, stat_scale[i], post_scale[i], i};
-    stream = v.stream;
-  }
+  PS_TRY(ps_read_records("hist_add", "histogram", a->device, a->N, s, nslot, kind, idx, stat_scale, post_scale,
+                         use_delta, false, d.data(), &stream));
   return hist_launch(a, d, stream, negval, weight);
 }
 
@@ -300,17 +293,10 @@ static int hist_add_fields(ps_hist* a, void* h, const PsFieldsOps& src, const ch
   if (a->W + weight > 0xffffffffull)
     return ps_fail(PS_ERR_BAD_ARG, "%s: total weight %llu would overflow the uint32 counts", who,
                    (unsigned long long)(a->W + weight));
-  PsProjectView v;
-  PS_TRY(src.view(h, &v));
-  if (v.nout != a->nslot)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: the %s has %d outputs, the histogram %d slots", who, src.what, v.nout, a->nslot);
-  if (v.device != a->device)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: %s on device %d, histogram on device %d", who, src.what, v.device, a->device);
-  if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "%s: %s domain %d, histogram domain %d", who, src.what, v.N, a->N);
-  PS_HIP(hipSetDevice(a->device));
   // slot e takes Y_e: no statistics, both scales 1 and negval 0, so the value rule returns Y itself
-  std::vector<HistSlot> d((size_t)a->nslot);
-  for (int e = 0; e < a->nslot; ++e) d[(size_t)e] = HistSlot{v.Y + (int64_t)e * v.pitch, nullptr, 1.0, 1.0, e};
+  std::vector<PsSrc> d((size_t)a->nslot);
+  PS_TRY(ps_read_fields(who, "histogram", "slots", a->device, a->N, a->nslot, h, src, d.data()));
+  PS_HIP(hipSetDevice(a->device));
   PS_TRY(src.wait(h, a->stream));
   PS_TRY(hist_launch(a, d, a->stream, 0.0, weight));
   return src.mark(h, a->stream);   // the next apply overwrites Y only after this read

@@ -219,17 +219,10 @@ static int lin_record_pass(ps_linspread* a, ps_solver* s, int nslot, const int32
   if (nslot != a->nslot) return ps_fail(PS_ERR_BAD_ARG, "%s: %d slots given, the handle has %d", who, nslot, a->nslot);
   PS_HIP(hipSetDevice(a->device));
   // every descriptor first: a call with a bad slot enqueues nothing
-  std::vector<LinSlot> d((size_t)nslot);
+  std::vector<PsSrc> d((size_t)nslot);
   hipStream_t stream = nullptr;
-  for (int i = 0; i < nslot; ++i) {
-    PsRecordView v;
-    PS_TRY(ps_solver_record_internal(s, kind[i], idx[i], use_delta[i] != 0, &v));
-    if (v.device != a->device)
-      return ps_fail(PS_ERR_BAD_ARG, "%s: solver on device %d, handle on device %d", who, v.device, a->device);
-    if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "%s: solver domain %d, handle domain %d", who, v.N, a->N);
-    d[i] = LinSlot{v.rec, v.stats, stat_scale[i], post_scale[i], i};
-    stream = v.stream;
-  }
+  PS_TRY(ps_read_records(who, "handle", a->device, a->N, s, nslot, kind, idx, stat_scale, post_scale, use_delta, false,
+                         d.data(), &stream));
   PS_TRY(a->last.wait(stream));
   hipEvent_t e1 = nullptr;
   if (!set) PS_TRY(a->prof.begin(0, stream, &e1));
@@ -239,7 +232,7 @@ static int lin_record_pass(ps_linspread* a, ps_solver* s, int nslot, const int32
   for (int c0 = 0; c0 < nslot; c0 += PS_LIN_CHUNK) {
     const int n = std::min(PS_LIN_CHUNK, nslot - c0);
     LinSlots desc;
-    for (int i = 0; i < n; ++i) desc.s[i] = d[(size_t)(c0 + i)];
+    for (int i = 0; i < n; ++i) desc.s[i] = ps_slotted<LinSlot>(d[(size_t)(c0 + i)], c0 + i);
     hipLaunchKernelGGL(k_linspread_add, dim3(bx, n), dim3(threads), 0, stream, desc, dst, a->ncell, a->pitch, negval,
                        coef, set);
     PS_HIP(hipGetLastError());

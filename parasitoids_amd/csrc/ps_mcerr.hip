@@ -311,7 +311,7 @@ static int mce_timed(ps_mcerr* h, int channel, hipStream_t stream, F body) {
 // One member from the slot descriptors d (one per slot), enqueued on `stream`: the weight is split at the batch
 // boundaries -- the open batch is filled and closed, then whole batches of b, then the rest -- and every piece is
 // one launch of the add kernel on the same source.
-static int mce_launch(ps_mcerr* h, const std::vector<MceSlot>& d, hipStream_t stream, double negval, uint32_t weight) {
+static int mce_launch(ps_mcerr* h, const std::vector<PsSrc>& d, hipStream_t stream, double negval, uint32_t weight) {
   PS_TRY(h->last.wait(stream));
   MceThr thr;
   for (int k = 0; k < PS_MCE_MAX_THR; ++k) thr.t[k] = k < h->nthr ? h->thr[(size_t)k] : 0.0;
@@ -330,7 +330,7 @@ static int mce_launch(ps_mcerr* h, const std::vector<MceSlot>& d, hipStream_t st
         const int n = std::min(PS_MCE_CHUNK, h->nslot - c0);
         MceSlots desc;
         for (int i = 0; i < PS_MCE_CHUNK; ++i)
-          desc.s[i] = i < n ? d[(size_t)(c0 + i)] : MceSlot{nullptr, nullptr, 0.0, 0.0, 0};
+          desc.s[i] = i < n ? ps_slotted<MceSlot>(d[(size_t)(c0 + i)], c0 + i) : MceSlot{nullptr, nullptr, 0.0, 0.0, 0};
         hipLaunchKernelGGL(k_mcerr_add, dim3(bx, n), dim3(PS_MCE_THREADS), 0, stream, desc, mce_val(h, MCE_BMEAN),
                            mce_val(h, MCE_BM2), h->bcnt, h->ncell, h->pitch, h->nthr, thr, negval, (double)piece, Wn,
                            piece);
@@ -377,17 +377,10 @@ extern "C" int ps_mcerr_add(ps_mcerr* h, ps_solver* s, int nslot, const int32_t*
   PS_TRY(mce_check_weight(h, "mcerr_add", weight));
   PS_HIP(hipSetDevice(h->device));
   // every descriptor first: an add with a bad slot enqueues nothing
-  std::vector<MceSlot> d((size_t)nslot);
+  std::vector<PsSrc> d((size_t)nslot);
   hipStream_t stream = nullptr;
-  for (int i = 0; i < nslot; ++i) {
-    PsRecordView v;
-    PS_TRY(ps_solver_record_internal(s, kind[i], idx[i], use_delta[i] != 0, &v));
-    if (v.device != h->device)
-      return ps_fail(PS_ERR_BAD_ARG, "mcerr_add: solver on device %d, handle on device %d", v.device, h->device);
-    if (v.N != h->N) return ps_fail(PS_ERR_BAD_ARG, "mcerr_add: solver domain %d, handle domain %d", v.N, h->N);
-    d[(size_t)i] = MceSlot{v.rec, v.stats, stat_scale[i], post_scale[i], i};
-    stream = v.stream;
-  }
+  PS_TRY(ps_read_records("mcerr_add", "handle", h->device, h->N, s, nslot, kind, idx, stat_scale, post_scale, use_delta,
+                         false, d.data(), &stream));
   return mce_launch(h, d, stream, negval, weight);
 }
 
@@ -395,17 +388,10 @@ extern "C" int ps_mcerr_add(ps_mcerr* h, ps_solver* s, int nslot, const int32_t*
 static int mce_add_fields(ps_mcerr* h, void* p, const PsFieldsOps& src, const char* who, uint32_t weight) {
   if (!h || !p) return ps_fail(PS_ERR_BAD_ARG, "%s: bad arguments", who);
   PS_TRY(mce_check_weight(h, who, weight));
-  PsProjectView v;
-  PS_TRY(src.view(p, &v));
-  if (v.nout != h->nslot)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: the %s has %d outputs, the handle %d slots", who, src.what, v.nout, h->nslot);
-  if (v.device != h->device)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: %s on device %d, handle on device %d", who, src.what, v.device, h->device);
-  if (v.N != h->N) return ps_fail(PS_ERR_BAD_ARG, "%s: %s domain %d, handle domain %d", who, src.what, v.N, h->N);
-  PS_HIP(hipSetDevice(h->device));
   // slot e takes Y_e: no statistics, both scales 1 and negval 0, so the value rule returns Y itself
-  std::vector<MceSlot> d((size_t)h->nslot);
-  for (int e = 0; e < h->nslot; ++e) d[(size_t)e] = MceSlot{v.Y + (int64_t)e * v.pitch, nullptr, 1.0, 1.0, e};
+  std::vector<PsSrc> d((size_t)h->nslot);
+  PS_TRY(ps_read_fields(who, "handle", "slots", h->device, h->N, h->nslot, p, src, d.data()));
+  PS_HIP(hipSetDevice(h->device));
   PS_TRY(src.wait(p, h->stream));
   PS_TRY(mce_launch(h, d, h->stream, 0.0, weight));
   return src.mark(p, h->stream);   // the next apply overwrites Y only after this read

@@ -33,13 +33,8 @@ namespace {
 
 typedef double modes_d4 __attribute__((ext_vector_type(4)));
 
-struct ModSlot {
-  const double* rec;
-  const ps_day_stats* stats;   // nullptr: no delta
-  double stat_scale, post_scale;
-};
 struct ModSlots {
-  ModSlot s[PS_MOD_MAX_SLOT];
+  PsSrc s[PS_MOD_MAX_SLOT];
 };
 
 // thread i owns cell i of every slot; the grid covers the pitch, so the pad cells get their zeros
@@ -52,7 +47,7 @@ __global__ void __launch_bounds__(PS_MOD_THREADS) k_modes_add(ModSlots desc, int
   if (i >= pitch) return;
   const bool real = i < ncell;
   for (int s = 0; s < nslot; ++s) {
-    const ModSlot& sd = desc.s[s];
+    const PsSrc& sd = desc.s[s];
     double v = 0.0;
     if (real) v = ps_record_value(sd.rec[i], sd.stat_scale, sd.post_scale, sdelta[s], negval);
     X[(int64_t)s * pitch + i] = root ? __dsqrt_rn(v) : v;
@@ -418,16 +413,9 @@ extern "C" int ps_modes_add(ps_modes* a, ps_solver* s, int nslot, const int32_t*
   // every descriptor first: an add with a bad slot enqueues nothing
   ModSlots desc;
   hipStream_t stream = nullptr;
-  for (int i = 0; i < nslot; ++i) {
-    PsRecordView v;
-    PS_TRY(ps_solver_record_internal(s, kind[i], idx[i], use_delta[i] != 0, &v));
-    if (v.device != a->device)
-      return ps_fail(PS_ERR_BAD_ARG, "modes_add: solver on device %d, handle on device %d", v.device, a->device);
-    if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "modes_add: solver domain %d, handle domain %d", v.N, a->N);
-    desc.s[i] = ModSlot{v.rec, v.stats, stat_scale[i], post_scale[i]};
-    stream = v.stream;
-  }
-  for (int i = nslot; i < PS_MOD_MAX_SLOT; ++i) desc.s[i] = ModSlot{nullptr, nullptr, 0.0, 0.0};
+  PS_TRY(ps_read_records("modes_add", "handle", a->device, a->N, s, nslot, kind, idx, stat_scale, post_scale, use_delta,
+                         false, desc.s, &stream));
+  for (int i = nslot; i < PS_MOD_MAX_SLOT; ++i) desc.s[i] = PsSrc{nullptr, nullptr, 0.0, 0.0};
   return mod_launch(a, desc, stream, negval, weight, "modes_add");
 }
 
@@ -435,18 +423,11 @@ extern "C" int ps_modes_add(ps_modes* a, ps_solver* s, int nslot, const int32_t*
 static int mod_add_fields(ps_modes* a, void* h, const PsFieldsOps& src, const char* who, uint32_t weight) {
   if (!a || !h) return ps_fail(PS_ERR_BAD_ARG, "%s: bad arguments", who);
   PS_TRY(mod_check_weight(a, who, weight));
-  PsProjectView v;
-  PS_TRY(src.view(h, &v));
-  if (v.nout != a->nslot)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: the %s has %d outputs, the handle %d slots", who, src.what, v.nout, a->nslot);
-  if (v.device != a->device)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: %s on device %d, handle on device %d", who, src.what, v.device, a->device);
-  if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "%s: %s domain %d, handle domain %d", who, src.what, v.N, a->N);
-  PS_HIP(hipSetDevice(a->device));
   // slot e takes Y_e: no statistics, both scales 1 and negval 0, so the value rule returns Y itself
   ModSlots desc;
-  for (int e = 0; e < PS_MOD_MAX_SLOT; ++e)
-    desc.s[e] = e < a->nslot ? ModSlot{v.Y + (int64_t)e * v.pitch, nullptr, 1.0, 1.0} : ModSlot{nullptr, nullptr, 0.0, 0.0};
+  PS_TRY(ps_read_fields(who, "handle", "slots", a->device, a->N, a->nslot, h, src, desc.s));
+  for (int e = a->nslot; e < PS_MOD_MAX_SLOT; ++e) desc.s[e] = PsSrc{nullptr, nullptr, 0.0, 0.0};
+  PS_HIP(hipSetDevice(a->device));
   PS_TRY(src.wait(h, a->stream));
   PS_TRY(mod_launch(a, desc, a->stream, 0.0, weight, who));
   return src.mark(h, a->stream);   // the next apply overwrites the source's fields only after this read

@@ -43,13 +43,8 @@ static_assert(NB_TX == 64 && NB_TY % NB_WAVES == 0, "one wave per tile row");
 
 namespace {
 
-struct NbhdSlot {
-  const double* rec;
-  const ps_day_stats* stats;   // nullptr: no delta
-  double stat_scale, post_scale;
-};
 struct NbhdSlots {
-  NbhdSlot s[PS_NBHD_MAX_IN];
+  PsSrc s[PS_NBHD_MAX_IN];
 };
 // the outputs in group order (ascending input, the outputs of one input in ascending e, as CatchTab); pass p reads
 // input pin[p] and owns the entries pstart[p] .. pstart[p + 1] - 1, at most NB_CHUNK of them
@@ -404,16 +399,9 @@ extern "C" int ps_nbhd_apply(ps_nbhd* c, ps_solver* s, int nin, const int32_t* k
   // every descriptor first: an apply with a bad record enqueues nothing
   NbhdSlots desc;
   hipStream_t stream = nullptr;
-  for (int i = 0; i < nin; ++i) {
-    PsRecordView v;
-    PS_TRY(ps_solver_record_internal(s, kind[i], idx[i], use_delta[i] != 0, &v));
-    if (v.device != c->device)
-      return ps_fail(PS_ERR_BAD_ARG, "nbhd_apply: solver on device %d, handle on device %d", v.device, c->device);
-    if (v.N != c->N) return ps_fail(PS_ERR_BAD_ARG, "nbhd_apply: solver domain %d, handle domain %d", v.N, c->N);
-    desc.s[i] = NbhdSlot{v.rec, v.stats, stat_scale[i], post_scale[i]};
-    stream = v.stream;
-  }
-  for (int i = nin; i < PS_NBHD_MAX_IN; ++i) desc.s[i] = NbhdSlot{nullptr, nullptr, 0.0, 0.0};
+  PS_TRY(ps_read_records("nbhd_apply", "handle", c->device, c->N, s, nin, kind, idx, stat_scale, post_scale, use_delta,
+                         false, desc.s, &stream));
+  for (int i = nin; i < PS_NBHD_MAX_IN; ++i) desc.s[i] = PsSrc{nullptr, nullptr, 0.0, 0.0};
   return nbhd_launch(c, desc, stream, negval);
 }
 
@@ -421,18 +409,11 @@ extern "C" int ps_nbhd_apply(ps_nbhd* c, ps_solver* s, int nin, const int32_t* k
 // source's output i, on the handle's stream behind the source's last operation
 static int nbhd_apply_fields(ps_nbhd* c, void* h, const PsFieldsOps& src, const char* who) {
   if (!c || !h) return ps_fail(PS_ERR_BAD_ARG, "%s: bad arguments", who);
-  PsProjectView v;
-  PS_TRY(src.view(h, &v));
-  if (v.nout != c->nin)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: the %s has %d outputs, the handle %d inputs", who, src.what, v.nout, c->nin);
-  if (v.device != c->device)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: %s on device %d, handle on device %d", who, src.what, v.device, c->device);
-  if (v.N != c->N) return ps_fail(PS_ERR_BAD_ARG, "%s: %s domain %d, handle domain %d", who, src.what, v.N, c->N);
-  PS_HIP(hipSetDevice(c->device));
   // input i takes Y_i: no statistics, both scales 1 and negval 0, so the value rule returns Y itself
   NbhdSlots desc;
-  for (int i = 0; i < PS_NBHD_MAX_IN; ++i)
-    desc.s[i] = i < c->nin ? NbhdSlot{v.Y + (int64_t)i * v.pitch, nullptr, 1.0, 1.0} : NbhdSlot{nullptr, nullptr, 0.0, 0.0};
+  PS_TRY(ps_read_fields(who, "handle", "inputs", c->device, c->N, c->nin, h, src, desc.s));
+  for (int i = c->nin; i < PS_NBHD_MAX_IN; ++i) desc.s[i] = PsSrc{nullptr, nullptr, 0.0, 0.0};
+  PS_HIP(hipSetDevice(c->device));
   PS_TRY(src.wait(h, c->stream));
   PS_TRY(nbhd_launch(c, desc, c->stream, 0.0));
   return src.mark(h, c->stream);   // the source's next apply overwrites its fields only after this read

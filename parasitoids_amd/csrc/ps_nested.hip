@@ -251,7 +251,7 @@ static int nst_timed(ps_nested* h, int channel, hipStream_t stream, F body) {
 }
 
 // one draw of the open group from the slot descriptors d (one per slot), enqueued on `stream`
-static int nst_launch(ps_nested* h, const std::vector<NstSlot>& d, hipStream_t stream, double negval) {
+static int nst_launch(ps_nested* h, const std::vector<PsSrc>& d, hipStream_t stream, double negval) {
   PS_TRY(h->last.wait(stream));
   const double kn = (double)(h->k + 1);
   const unsigned bx = nst_blocks(h->ncell / 2 + 1);
@@ -260,7 +260,7 @@ static int nst_launch(ps_nested* h, const std::vector<NstSlot>& d, hipStream_t s
       const int n = std::min(PS_NST_CHUNK, h->nslot - c0);
       NstSlots desc;
       for (int i = 0; i < PS_NST_CHUNK; ++i)
-        desc.s[i] = i < n ? d[(size_t)(c0 + i)] : NstSlot{nullptr, nullptr, 0.0, 0.0, 0};
+        desc.s[i] = i < n ? ps_slotted<NstSlot>(d[(size_t)(c0 + i)], c0 + i) : NstSlot{nullptr, nullptr, 0.0, 0.0, 0};
       hipLaunchKernelGGL(k_nested_add, dim3(bx, n), dim3(PS_NST_THREADS), 0, stream, desc, nst_val(h, NST_IMEAN),
                          nst_val(h, NST_IM2), h->ncell, h->pitch, negval, kn);
       PS_HIP(hipGetLastError());
@@ -283,34 +283,20 @@ extern "C" int ps_nested_add(ps_nested* h, ps_solver* s, int nslot, const int32_
   if (nslot != h->nslot) return ps_fail(PS_ERR_BAD_ARG, "nested_add: %d slots given, the handle has %d", nslot, h->nslot);
   PS_HIP(hipSetDevice(h->device));
   // every descriptor first: an add with a bad slot enqueues nothing
-  std::vector<NstSlot> d((size_t)nslot);
+  std::vector<PsSrc> d((size_t)nslot);
   hipStream_t stream = nullptr;
-  for (int i = 0; i < nslot; ++i) {
-    PsRecordView v;
-    PS_TRY(ps_solver_record_internal(s, kind[i], idx[i], use_delta[i] != 0, &v));
-    if (v.device != h->device)
-      return ps_fail(PS_ERR_BAD_ARG, "nested_add: solver on device %d, handle on device %d", v.device, h->device);
-    if (v.N != h->N) return ps_fail(PS_ERR_BAD_ARG, "nested_add: solver domain %d, handle domain %d", v.N, h->N);
-    d[(size_t)i] = NstSlot{v.rec, v.stats, stat_scale[i], post_scale[i], i};
-    stream = v.stream;
-  }
+  PS_TRY(ps_read_records("nested_add", "handle", h->device, h->N, s, nslot, kind, idx, stat_scale, post_scale,
+                         use_delta, false, d.data(), &stream));
   return nst_launch(h, d, stream, negval);
 }
 
 // one draw whose values are the current fields of a projection or a release plan (who: the entry point)
 static int nst_add_fields(ps_nested* h, void* p, const PsFieldsOps& src, const char* who) {
   if (!h || !p) return ps_fail(PS_ERR_BAD_ARG, "%s: bad arguments", who);
-  PsProjectView v;
-  PS_TRY(src.view(p, &v));
-  if (v.nout != h->nslot)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: the %s has %d outputs, the handle %d slots", who, src.what, v.nout, h->nslot);
-  if (v.device != h->device)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: %s on device %d, handle on device %d", who, src.what, v.device, h->device);
-  if (v.N != h->N) return ps_fail(PS_ERR_BAD_ARG, "%s: %s domain %d, handle domain %d", who, src.what, v.N, h->N);
-  PS_HIP(hipSetDevice(h->device));
   // slot e takes Y_e: no statistics, both scales 1 and negval 0, so the value rule returns Y itself
-  std::vector<NstSlot> d((size_t)h->nslot);
-  for (int e = 0; e < h->nslot; ++e) d[(size_t)e] = NstSlot{v.Y + (int64_t)e * v.pitch, nullptr, 1.0, 1.0, e};
+  std::vector<PsSrc> d((size_t)h->nslot);
+  PS_TRY(ps_read_fields(who, "handle", "slots", h->device, h->N, h->nslot, p, src, d.data()));
+  PS_HIP(hipSetDevice(h->device));
   PS_TRY(src.wait(p, h->stream));
   PS_TRY(nst_launch(h, d, h->stream, 0.0));
   return src.mark(p, h->stream);   // the next apply overwrites Y only after this read

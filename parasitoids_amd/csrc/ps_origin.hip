@@ -37,13 +37,8 @@
 
 namespace {
 
-struct OrgSlot {
-  const double* rec;           // nullptr: PS_REC_NONE, the group is not released yet on this day
-  const ps_day_stats* stats;   // nullptr: no delta
-  double stat_scale, post_scale;
-};
-struct OrgSlots {
-  OrgSlot s[PS_ORIGIN_MAX_SLOT];
+struct OrgSlots {   // rec nullptr (PS_REC_NONE): the group is not released yet on this day
+  PsSrc s[PS_ORIGIN_MAX_SLOT];
 };
 struct OrgGroup {
   int nh, pad_;
@@ -77,7 +72,7 @@ __global__ void __launch_bounds__(PS_ORIGIN_LANES)
   const int q = threadIdx.x;
   if (q < nfind) {
     const OriginFinding f = find[q];
-    const OrgSlot sd = desc.s[f.slot];
+    const PsSrc sd = desc.s[f.slot];
     const double delta = sd.rec && sd.stats ? sd.stats->delta : 0.0;
     for (int j = 0; j < kn.n; ++j) {
       double v = 0.0;
@@ -127,7 +122,7 @@ __global__ void __launch_bounds__(PS_ORIGIN_THREADS)
   for (int q = 0; q < nfind; ++q) {
     if (!alive) break;
     const OriginFinding f = find[q];
-    const OrgSlot sd = desc.s[f.slot];
+    const PsSrc sd = desc.s[f.slot];
     double v = 0.0;
     int64_t src;
     if (sd.rec && origin_source(N, f.rowR, f.colR, r, c, &src)) {
@@ -516,21 +511,9 @@ extern "C" int ps_origin_add(ps_origin* p, ps_solver* s, int group, int nslot, c
   OrgSlots desc;
   hipStream_t stream = nullptr;
   bool any = false;
-  for (int e = 0; e < nslot; ++e) {
-    if (kind[e] == PS_REC_NONE) {
-      desc.s[e] = OrgSlot{nullptr, nullptr, 0.0, 0.0};
-      continue;
-    }
-    PsRecordView v;
-    PS_TRY(ps_solver_record_internal(s, kind[e], idx[e], use_delta[e] != 0, &v));
-    if (v.device != p->device)
-      return ps_fail(PS_ERR_BAD_ARG, "origin_add: solver on device %d, handle on device %d", v.device, p->device);
-    if (v.N != p->N) return ps_fail(PS_ERR_BAD_ARG, "origin_add: solver domain %d, handle domain %d", v.N, p->N);
-    desc.s[e] = OrgSlot{v.rec, v.stats, stat_scale[e], post_scale[e]};
-    stream = v.stream;
-    any = true;
-  }
-  for (int e = nslot; e < PS_ORIGIN_MAX_SLOT; ++e) desc.s[e] = OrgSlot{nullptr, nullptr, 0.0, 0.0};
+  PS_TRY(ps_read_records("origin_add", "handle", p->device, p->N, s, nslot, kind, idx, stat_scale, post_scale,
+                         use_delta, true, desc.s, &stream, &any));
+  for (int e = nslot; e < PS_ORIGIN_MAX_SLOT; ++e) desc.s[e] = PsSrc{nullptr, nullptr, 0.0, 0.0};
   if (!any)   // such a lag explains no finding, and no record names the stream to run on
     return ps_fail(PS_ERR_BAD_ARG, "origin_add: group %d is released on no day of a finding (every slot is PS_REC_NONE)",
                    group);
@@ -659,20 +642,9 @@ extern "C" int ps_origin_background(ps_origin* p, ps_solver* s, int kgroup, int 
   // every descriptor first: a call with a bad record enqueues nothing
   OrgSlots desc;
   hipStream_t stream = p->stream;   // a known group released after every finding reads no record: the handle's stream
-  for (int e = 0; e < nslot; ++e) {
-    if (kind[e] == PS_REC_NONE) {
-      desc.s[e] = OrgSlot{nullptr, nullptr, 0.0, 0.0};
-      continue;
-    }
-    PsRecordView v;
-    PS_TRY(ps_solver_record_internal(s, kind[e], idx[e], use_delta[e] != 0, &v));
-    if (v.device != p->device)
-      return ps_fail(PS_ERR_BAD_ARG, "origin_background: solver on device %d, handle on device %d", v.device, p->device);
-    if (v.N != p->N) return ps_fail(PS_ERR_BAD_ARG, "origin_background: solver domain %d, handle domain %d", v.N, p->N);
-    desc.s[e] = OrgSlot{v.rec, v.stats, stat_scale[e], post_scale[e]};
-    stream = v.stream;
-  }
-  for (int e = nslot; e < PS_ORIGIN_MAX_SLOT; ++e) desc.s[e] = OrgSlot{nullptr, nullptr, 0.0, 0.0};
+  PS_TRY(ps_read_records("origin_background", "handle", p->device, p->N, s, nslot, kind, idx, stat_scale, post_scale,
+                         use_delta, true, desc.s, &stream));
+  for (int e = nslot; e < PS_ORIGIN_MAX_SLOT; ++e) desc.s[e] = PsSrc{nullptr, nullptr, 0.0, 0.0};
   if (kgroup == 0) PS_TRY(org_reserve_rows(p, p->members + 1));
   PS_TRY(p->last.wait(stream));
   hipLaunchKernelGGL(k_origin_background, dim3(1), dim3(PS_ORIGIN_LANES), 0, stream, desc, p->kgroups[kgroup], p->find,

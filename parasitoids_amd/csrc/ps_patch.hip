@@ -34,13 +34,8 @@
 
 namespace {
 
-struct PatSlot {
-  const double* rec;
-  const ps_day_stats* stats;   // nullptr: no delta
-  double stat_scale, post_scale;
-};
 struct PatSlots {
-  PatSlot s[PS_PAT_MAX_SLOT];
+  PsSrc s[PS_PAT_MAX_SLOT];
 };
 struct PatThr {
   double t[PS_PAT_MAX_THR];
@@ -73,7 +68,7 @@ __global__ void __launch_bounds__(PS_PAT_THREADS) k_patch_init(PatSlots desc, Pa
   const uint32_t c = blockIdx.x * (uint32_t)PS_PAT_THREADS + threadIdx.x;
   if (c >= ncell) return;
   const int p = blockIdx.y, k = p / nslot, s = p - k * nslot;
-  const PatSlot& sd = desc.s[s];
+  const PsSrc& sd = desc.s[s];
   const double delta = sd.stats ? sd.stats->delta : 0.0;
   const double v = ps_record_value(sd.rec[c], sd.stat_scale, sd.post_scale, delta, negval);
   parent[p * pitch + c] = v >= thr.t[k] ? c : PATCH_NONE;
@@ -384,16 +379,9 @@ extern "C" int ps_patch_add(ps_patch* a, ps_solver* s, int nslot, const int32_t*
   // every descriptor first: an add with a bad slot enqueues nothing
   PatSlots desc;
   hipStream_t stream = nullptr;
-  for (int i = 0; i < nslot; ++i) {
-    PsRecordView v;
-    PS_TRY(ps_solver_record_internal(s, kind[i], idx[i], use_delta[i] != 0, &v));
-    if (v.device != a->device)
-      return ps_fail(PS_ERR_BAD_ARG, "patch_add: solver on device %d, handle on device %d", v.device, a->device);
-    if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "patch_add: solver domain %d, handle domain %d", v.N, a->N);
-    desc.s[i] = PatSlot{v.rec, v.stats, stat_scale[i], post_scale[i]};
-    stream = v.stream;
-  }
-  for (int i = nslot; i < PS_PAT_MAX_SLOT; ++i) desc.s[i] = PatSlot{nullptr, nullptr, 0.0, 0.0};
+  PS_TRY(ps_read_records("patch_add", "handle", a->device, a->N, s, nslot, kind, idx, stat_scale, post_scale, use_delta,
+                         false, desc.s, &stream));
+  for (int i = nslot; i < PS_PAT_MAX_SLOT; ++i) desc.s[i] = PsSrc{nullptr, nullptr, 0.0, 0.0};
   return pat_launch(a, desc, stream, negval, weight);
 }
 
@@ -405,18 +393,11 @@ static int pat_add_fields(ps_patch* a, void* h, const PsFieldsOps& src, const ch
   if (a->W + weight > 0xffffffffull)
     return ps_fail(PS_ERR_BAD_ARG, "%s: total weight %llu would overflow the uint32 counts", who,
                    (unsigned long long)(a->W + weight));
-  PsProjectView v;
-  PS_TRY(src.view(h, &v));
-  if (v.nout != a->nslot)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: the %s has %d outputs, the handle %d slots", who, src.what, v.nout, a->nslot);
-  if (v.device != a->device)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: %s on device %d, handle on device %d", who, src.what, v.device, a->device);
-  if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "%s: %s domain %d, handle domain %d", who, src.what, v.N, a->N);
-  PS_HIP(hipSetDevice(a->device));
   // slot e takes Y_e: no statistics, both scales 1 and negval 0, so the value rule returns Y itself
   PatSlots desc;
-  for (int e = 0; e < PS_PAT_MAX_SLOT; ++e)
-    desc.s[e] = e < a->nslot ? PatSlot{v.Y + (int64_t)e * v.pitch, nullptr, 1.0, 1.0} : PatSlot{nullptr, nullptr, 0.0, 0.0};
+  PS_TRY(ps_read_fields(who, "handle", "slots", a->device, a->N, a->nslot, h, src, desc.s));
+  for (int e = a->nslot; e < PS_PAT_MAX_SLOT; ++e) desc.s[e] = PsSrc{nullptr, nullptr, 0.0, 0.0};
+  PS_HIP(hipSetDevice(a->device));
   PS_TRY(src.wait(h, a->stream));
   PS_TRY(pat_launch(a, desc, a->stream, 0.0, weight));
   return src.mark(h, a->stream);   // the next apply overwrites Y only after this read

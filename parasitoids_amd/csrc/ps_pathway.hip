@@ -41,13 +41,8 @@
 
 namespace {
 
-struct PwSlot {
-  const double* rec;
-  const ps_day_stats* stats;   // nullptr: no delta
-  double stat_scale, post_scale;
-};
 struct PwSlots {
-  PwSlot s[PS_PW_MAX_SLOT];
+  PsSrc s[PS_PW_MAX_SLOT];
 };
 struct PwThr {
   double t[PS_PW_MAX_THR];
@@ -84,7 +79,7 @@ __global__ void __launch_bounds__(PS_PW_THREADS) k_pathway_init(PwSlots desc, Pw
   const uint32_t c = blockIdx.x * (uint32_t)PS_PW_THREADS + threadIdx.x;
   if (c >= ncell) return;
   const int p = blockIdx.y, k = p / nslot, s = p - k * nslot;
-  const PwSlot& sd = desc.s[s];
+  const PsSrc& sd = desc.s[s];
   const double delta = sd.stats ? sd.stats->delta : 0.0;
   const double v = ps_record_value(sd.rec[c], sd.stat_scale, sd.post_scale, delta, negval);
   parent[p * pitch + c] = v >= thr.t[k] ? c : PATCH_NONE;
@@ -400,16 +395,9 @@ extern "C" int ps_pathway_add(ps_pathway* a, ps_solver* s, int nslot, const int3
   // every descriptor first: an add with a bad slot enqueues nothing
   PwSlots desc;
   hipStream_t stream = nullptr;
-  for (int i = 0; i < nslot; ++i) {
-    PsRecordView v;
-    PS_TRY(ps_solver_record_internal(s, kind[i], idx[i], use_delta[i] != 0, &v));
-    if (v.device != a->device)
-      return ps_fail(PS_ERR_BAD_ARG, "pathway_add: solver on device %d, handle on device %d", v.device, a->device);
-    if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "pathway_add: solver domain %d, handle domain %d", v.N, a->N);
-    desc.s[i] = PwSlot{v.rec, v.stats, stat_scale[i], post_scale[i]};
-    stream = v.stream;
-  }
-  for (int i = nslot; i < PS_PW_MAX_SLOT; ++i) desc.s[i] = PwSlot{nullptr, nullptr, 0.0, 0.0};
+  PS_TRY(ps_read_records("pathway_add", "handle", a->device, a->N, s, nslot, kind, idx, stat_scale, post_scale,
+                         use_delta, false, desc.s, &stream));
+  for (int i = nslot; i < PS_PW_MAX_SLOT; ++i) desc.s[i] = PsSrc{nullptr, nullptr, 0.0, 0.0};
   return pw_launch(a, desc, stream, negval, weight);
 }
 
@@ -422,18 +410,11 @@ extern "C" int ps_pathway_add_sites(ps_pathway* a, ps_sites* h, uint32_t weight)
     return ps_fail(PS_ERR_BAD_ARG, "%s: total weight %llu would overflow the uint32 counts", who,
                    (unsigned long long)(a->W + weight));
   const PsFieldsOps src = ps_sites_fields();
-  PsProjectView v;
-  PS_TRY(src.view(h, &v));
-  if (v.nout != a->nslot)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: the %s has %d outputs, the handle %d slots", who, src.what, v.nout, a->nslot);
-  if (v.device != a->device)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: %s on device %d, handle on device %d", who, src.what, v.device, a->device);
-  if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "%s: %s domain %d, handle domain %d", who, src.what, v.N, a->N);
-  PS_HIP(hipSetDevice(a->device));
   // slot e takes Y_e: no statistics, both scales 1 and negval 0, so the value rule returns Y itself
   PwSlots desc;
-  for (int e = 0; e < PS_PW_MAX_SLOT; ++e)
-    desc.s[e] = e < a->nslot ? PwSlot{v.Y + (int64_t)e * v.pitch, nullptr, 1.0, 1.0} : PwSlot{nullptr, nullptr, 0.0, 0.0};
+  PS_TRY(ps_read_fields(who, "handle", "slots", a->device, a->N, a->nslot, h, src, desc.s));
+  for (int e = a->nslot; e < PS_PW_MAX_SLOT; ++e) desc.s[e] = PsSrc{nullptr, nullptr, 0.0, 0.0};
+  PS_HIP(hipSetDevice(a->device));
   PS_TRY(src.wait(h, a->stream));
   PS_TRY(pw_launch(a, desc, a->stream, 0.0, weight));
   return src.mark(h, a->stream);   // the next apply overwrites Y only after this read

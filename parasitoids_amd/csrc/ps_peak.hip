@@ -22,13 +22,8 @@
 
 namespace {
 
-struct PeakSlot {
-  const double* rec;
-  const ps_day_stats* stats;   // nullptr: no delta
-  double stat_scale, post_scale;
-};
 struct PeakSlots {
-  PeakSlot s[PS_PEAK_MAX_SLOT];
+  PsSrc s[PS_PEAK_MAX_SLOT];
 };
 struct PeakThr {
   double t[PS_PEAK_MAX_THR];
@@ -82,7 +77,7 @@ __global__ void __launch_bounds__(PS_PEAK_THREADS) k_peak_add(PeakSlots desc, Pe
   for (int s = 0; s < nslot; ++s) {
     double2 rn = make_double2(0.0, 0.0);
     if (s + 1 < nslot) peak_load(desc.s[s + 1].rec, pair, i, rn);
-    const PeakSlot& sd = desc.s[s];
+    const PsSrc& sd = desc.s[s];
     const double delta = sdelta[s];
     const double v0 = ps_record_value(r.x, sd.stat_scale, sd.post_scale, delta, negval);
     const double v1 = pair ? ps_record_value(r.y, sd.stat_scale, sd.post_scale, delta, negval) : 0.0;
@@ -302,16 +297,9 @@ extern "C" int ps_peak_add(ps_peak* a, ps_solver* s, int nslot, const int32_t* k
   // every descriptor first: an add with a bad slot enqueues nothing
   PeakSlots desc;
   hipStream_t stream = nullptr;
-  for (int i = 0; i < nslot; ++i) {
-    PsRecordView v;
-    PS_TRY(ps_solver_record_internal(s, kind[i], idx[i], use_delta[i] != 0, &v));
-    if (v.device != a->device)
-      return ps_fail(PS_ERR_BAD_ARG, "peak_add: solver on device %d, handle on device %d", v.device, a->device);
-    if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "peak_add: solver domain %d, handle domain %d", v.N, a->N);
-    desc.s[i] = PeakSlot{v.rec, v.stats, stat_scale[i], post_scale[i]};
-    stream = v.stream;
-  }
-  for (int i = nslot; i < PS_PEAK_MAX_SLOT; ++i) desc.s[i] = PeakSlot{nullptr, nullptr, 0.0, 0.0};
+  PS_TRY(ps_read_records("peak_add", "handle", a->device, a->N, s, nslot, kind, idx, stat_scale, post_scale, use_delta,
+                         false, desc.s, &stream));
+  for (int i = nslot; i < PS_PEAK_MAX_SLOT; ++i) desc.s[i] = PsSrc{nullptr, nullptr, 0.0, 0.0};
   return peak_launch(a, desc, stream, negval, weight);
 }
 
@@ -320,18 +308,11 @@ extern "C" int ps_peak_add(ps_peak* a, ps_solver* s, int nslot, const int32_t* k
 static int peak_add_fields(ps_peak* a, void* h, const PsFieldsOps& src, const char* who, uint32_t weight) {
   if (!a || !h) return ps_fail(PS_ERR_BAD_ARG, "%s: bad arguments", who);
   PS_TRY(peak_check_weight(a, who, weight));
-  PsProjectView v;
-  PS_TRY(src.view(h, &v));
-  if (v.nout != a->nslot)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: the %s has %d outputs, the handle %d slots", who, src.what, v.nout, a->nslot);
-  if (v.device != a->device)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: %s on device %d, handle on device %d", who, src.what, v.device, a->device);
-  if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "%s: %s domain %d, handle domain %d", who, src.what, v.N, a->N);
-  PS_HIP(hipSetDevice(a->device));
   // slot e takes Y_e: no statistics, both scales 1 and negval 0, so the value rule returns Y itself
   PeakSlots desc;
-  for (int e = 0; e < PS_PEAK_MAX_SLOT; ++e)
-    desc.s[e] = e < a->nslot ? PeakSlot{v.Y + (int64_t)e * v.pitch, nullptr, 1.0, 1.0} : PeakSlot{nullptr, nullptr, 0.0, 0.0};
+  PS_TRY(ps_read_fields(who, "handle", "slots", a->device, a->N, a->nslot, h, src, desc.s));
+  for (int e = a->nslot; e < PS_PEAK_MAX_SLOT; ++e) desc.s[e] = PsSrc{nullptr, nullptr, 0.0, 0.0};
+  PS_HIP(hipSetDevice(a->device));
   PS_TRY(src.wait(h, a->stream));
   PS_TRY(peak_launch(a, desc, a->stream, 0.0, weight));
   return src.mark(h, a->stream);   // the next apply overwrites the source's fields only after this read

@@ -25,13 +25,8 @@
 
 namespace {
 
-struct ProjSlot {
-  const double* rec;
-  const ps_day_stats* stats;   // nullptr: no delta
-  double stat_scale, post_scale;
-};
 struct ProjSlots {
-  ProjSlot s[PS_PROJ_MAX_IN];
+  PsSrc s[PS_PROJ_MAX_IN];
 };
 struct ProjTile {
   double w[PS_PROJ_MAX_IN][PS_PROJ_TILE];   // [entry][output of the tile]; 0 past nout
@@ -227,16 +222,9 @@ extern "C" int ps_project_apply(ps_project* p, ps_solver* s, int nin, const int3
   // every descriptor first: an apply with a bad record enqueues nothing
   ProjSlots desc;
   hipStream_t stream = nullptr;
-  for (int i = 0; i < nin; ++i) {
-    PsRecordView v;
-    PS_TRY(ps_solver_record_internal(s, kind[i], idx[i], use_delta[i] != 0, &v));
-    if (v.device != p->device)
-      return ps_fail(PS_ERR_BAD_ARG, "project_apply: solver on device %d, handle on device %d", v.device, p->device);
-    if (v.N != p->N) return ps_fail(PS_ERR_BAD_ARG, "project_apply: solver domain %d, handle domain %d", v.N, p->N);
-    desc.s[i] = ProjSlot{v.rec, v.stats, stat_scale[i], post_scale[i]};
-    stream = v.stream;
-  }
-  for (int i = nin; i < PS_PROJ_MAX_IN; ++i) desc.s[i] = ProjSlot{nullptr, nullptr, 0.0, 0.0};
+  PS_TRY(ps_read_records("project_apply", "handle", p->device, p->N, s, nin, kind, idx, stat_scale, post_scale,
+                         use_delta, false, desc.s, &stream));
+  for (int i = nin; i < PS_PROJ_MAX_IN; ++i) desc.s[i] = PsSrc{nullptr, nullptr, 0.0, 0.0};
   PS_TRY(p->last.wait(stream));
   hipEvent_t e1 = nullptr;
   PS_TRY(p->prof.begin(0, stream, &e1));

@@ -32,13 +32,8 @@
 
 namespace {
 
-struct ProxSlot {
-  const double* rec;
-  const ps_day_stats* stats;   // nullptr: no delta
-  double stat_scale, post_scale;
-};
 struct ProxSlots {
-  ProxSlot s[PS_PROX_MAX_IN];
+  PsSrc s[PS_PROX_MAX_IN];
 };
 struct ProxTab {
   int input[PS_PROX_MAX_OUT];
@@ -52,7 +47,7 @@ __global__ void __launch_bounds__(256) k_prox_mask(ProxSlots desc, ProxTab tab, 
   const int e = blockIdx.y;
   const int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (c >= pitch) return;   // pitch is a multiple of 64: whole waves leave
-  const ProxSlot sd = desc.s[tab.input[e]];
+  const PsSrc sd = desc.s[tab.input[e]];
   bool in = false;
   if (c < ncell) {
     const double delta = sd.stats ? sd.stats->delta : 0.0;
@@ -267,16 +262,9 @@ extern "C" int ps_prox_apply(ps_prox* c, ps_solver* s, int nin, const int32_t* k
   // every descriptor first: an apply with a bad record enqueues nothing
   ProxSlots desc;
   hipStream_t stream = nullptr;
-  for (int i = 0; i < nin; ++i) {
-    PsRecordView v;
-    PS_TRY(ps_solver_record_internal(s, kind[i], idx[i], use_delta[i] != 0, &v));
-    if (v.device != c->device)
-      return ps_fail(PS_ERR_BAD_ARG, "prox_apply: solver on device %d, handle on device %d", v.device, c->device);
-    if (v.N != c->N) return ps_fail(PS_ERR_BAD_ARG, "prox_apply: solver domain %d, handle domain %d", v.N, c->N);
-    desc.s[i] = ProxSlot{v.rec, v.stats, stat_scale[i], post_scale[i]};
-    stream = v.stream;
-  }
-  for (int i = nin; i < PS_PROX_MAX_IN; ++i) desc.s[i] = ProxSlot{nullptr, nullptr, 0.0, 0.0};
+  PS_TRY(ps_read_records("prox_apply", "handle", c->device, c->N, s, nin, kind, idx, stat_scale, post_scale, use_delta,
+                         false, desc.s, &stream));
+  for (int i = nin; i < PS_PROX_MAX_IN; ++i) desc.s[i] = PsSrc{nullptr, nullptr, 0.0, 0.0};
   return prox_launch(c, desc, stream, negval);
 }
 
@@ -284,18 +272,11 @@ extern "C" int ps_prox_apply(ps_prox* c, ps_solver* s, int nin, const int32_t* k
 // source's output i, on the handle's stream behind the source's last operation
 static int prox_apply_fields(ps_prox* c, void* h, const PsFieldsOps& src, const char* who) {
   if (!c || !h) return ps_fail(PS_ERR_BAD_ARG, "%s: bad arguments", who);
-  PsProjectView v;
-  PS_TRY(src.view(h, &v));
-  if (v.nout != c->nin)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: the %s has %d outputs, the handle %d inputs", who, src.what, v.nout, c->nin);
-  if (v.device != c->device)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: %s on device %d, handle on device %d", who, src.what, v.device, c->device);
-  if (v.N != c->N) return ps_fail(PS_ERR_BAD_ARG, "%s: %s domain %d, handle domain %d", who, src.what, v.N, c->N);
-  PS_HIP(hipSetDevice(c->device));
   // input i takes Y_i: no statistics, both scales 1 and negval 0, so the value rule returns Y itself
   ProxSlots desc;
-  for (int i = 0; i < PS_PROX_MAX_IN; ++i)
-    desc.s[i] = i < c->nin ? ProxSlot{v.Y + (int64_t)i * v.pitch, nullptr, 1.0, 1.0} : ProxSlot{nullptr, nullptr, 0.0, 0.0};
+  PS_TRY(ps_read_fields(who, "handle", "inputs", c->device, c->N, c->nin, h, src, desc.s));
+  for (int i = c->nin; i < PS_PROX_MAX_IN; ++i) desc.s[i] = PsSrc{nullptr, nullptr, 0.0, 0.0};
+  PS_HIP(hipSetDevice(c->device));
   PS_TRY(src.wait(h, c->stream));
   PS_TRY(prox_launch(c, desc, c->stream, 0.0));
   return src.mark(h, c->stream);   // the source's next apply overwrites its fields only after this read

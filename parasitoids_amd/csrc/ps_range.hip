@@ -35,13 +35,8 @@
 
 namespace {
 
-struct RngSlot {
-  const double* rec;
-  const ps_day_stats* stats;   // nullptr: no delta
-  double stat_scale, post_scale;
-};
 struct RngSlots {
-  RngSlot s[PS_RNG_MAX_SLOT];
+  PsSrc s[PS_RNG_MAX_SLOT];
 };
 // p_j = m * 2^-k exactly, m the 53-bit significand
 struct RngFrac {
@@ -59,7 +54,7 @@ struct RangeState {
   uint64_t hist[PS_RNG_MAX_SLOT][PS_RNG_MAX_FRAC][RNG_BINS];
 };
 
-__device__ inline double rng_value(const RngSlot& sd, int64_t i, double negval) {
+__device__ inline double rng_value(const PsSrc& sd, int64_t i, double negval) {
   const double delta = sd.stats ? sd.stats->delta : 0.0;
   return ps_record_value(sd.rec[i], sd.stat_scale, sd.post_scale, delta, negval);
 }
@@ -480,16 +475,9 @@ extern "C" int ps_range_add(ps_range* a, ps_solver* s, int nslot, const int32_t*
   // every descriptor first: an add with a bad slot enqueues nothing
   RngSlots desc;
   hipStream_t stream = nullptr;
-  for (int i = 0; i < nslot; ++i) {
-    PsRecordView v;
-    PS_TRY(ps_solver_record_internal(s, kind[i], idx[i], use_delta[i] != 0, &v));
-    if (v.device != a->device)
-      return ps_fail(PS_ERR_BAD_ARG, "range_add: solver on device %d, handle on device %d", v.device, a->device);
-    if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "range_add: solver domain %d, handle domain %d", v.N, a->N);
-    desc.s[i] = RngSlot{v.rec, v.stats, stat_scale[i], post_scale[i]};
-    stream = v.stream;
-  }
-  for (int i = nslot; i < PS_RNG_MAX_SLOT; ++i) desc.s[i] = RngSlot{nullptr, nullptr, 0.0, 0.0};
+  PS_TRY(ps_read_records("range_add", "handle", a->device, a->N, s, nslot, kind, idx, stat_scale, post_scale, use_delta,
+                         false, desc.s, &stream));
+  for (int i = nslot; i < PS_RNG_MAX_SLOT; ++i) desc.s[i] = PsSrc{nullptr, nullptr, 0.0, 0.0};
   return rng_launch(a, desc, stream, negval, weight);
 }
 
@@ -501,18 +489,11 @@ static int rng_add_fields(ps_range* a, void* h, const PsFieldsOps& src, const ch
   if (a->W + weight > 0xffffffffull)
     return ps_fail(PS_ERR_BAD_ARG, "%s: total weight %llu would overflow the uint32 counts", who,
                    (unsigned long long)(a->W + weight));
-  PsProjectView v;
-  PS_TRY(src.view(h, &v));
-  if (v.nout != a->nslot)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: the %s has %d outputs, the handle %d slots", who, src.what, v.nout, a->nslot);
-  if (v.device != a->device)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: %s on device %d, handle on device %d", who, src.what, v.device, a->device);
-  if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "%s: %s domain %d, handle domain %d", who, src.what, v.N, a->N);
-  PS_HIP(hipSetDevice(a->device));
   // slot e takes Y_e: no statistics, both scales 1 and negval 0, so the value rule returns Y itself
   RngSlots desc;
-  for (int e = 0; e < PS_RNG_MAX_SLOT; ++e)
-    desc.s[e] = e < a->nslot ? RngSlot{v.Y + (int64_t)e * v.pitch, nullptr, 1.0, 1.0} : RngSlot{nullptr, nullptr, 0.0, 0.0};
+  PS_TRY(ps_read_fields(who, "handle", "slots", a->device, a->N, a->nslot, h, src, desc.s));
+  for (int e = a->nslot; e < PS_RNG_MAX_SLOT; ++e) desc.s[e] = PsSrc{nullptr, nullptr, 0.0, 0.0};
+  PS_HIP(hipSetDevice(a->device));
   PS_TRY(src.wait(h, a->stream));
   PS_TRY(rng_launch(a, desc, a->stream, 0.0, weight));
   return src.mark(h, a->stream);   // the next apply overwrites Y only after this read

@@ -310,7 +310,7 @@ static int sens_check_add(ps_sens* a, const char* who, int nparam, const double*
 }
 
 // one member from the slot descriptors d (one per slot of the handle), enqueued on `stream`
-static int sens_launch(ps_sens* a, const std::vector<SensSlot>& d, hipStream_t stream, double negval, const double* e,
+static int sens_launch(ps_sens* a, const std::vector<PsSrc>& d, hipStream_t stream, double negval, const double* e,
                        uint32_t weight) {
   const int nslot = a->nslot;
   PS_TRY(a->last.wait(stream));
@@ -325,7 +325,7 @@ static int sens_launch(ps_sens* a, const std::vector<SensSlot>& d, hipStream_t s
   for (int c0 = 0; c0 < nslot; c0 += PS_SENS_CHUNK) {
     const int n = std::min(PS_SENS_CHUNK, nslot - c0);
     SensSlots desc;
-    for (int i = 0; i < n; ++i) desc.s[i] = d[(size_t)(c0 + i)];
+    for (int i = 0; i < n; ++i) desc.s[i] = ps_slotted<SensSlot>(d[(size_t)(c0 + i)], c0 + i);
     hipLaunchKernelGGL(sens_add_kernels[a->nparam - 1], dim3(bx, n), dim3(threads), 0, stream, desc, a->mean, a->m2,
                        a->C, a->ncell, a->pitch, sens_total(a), dev, negval, (double)weight, Wn);
     PS_HIP(hipGetLastError());
@@ -347,17 +347,10 @@ extern "C" int ps_sens_add(ps_sens* a, ps_solver* s, int nslot, const int32_t* k
   if (nslot != a->nslot) return ps_fail(PS_ERR_BAD_ARG, "sens_add: %d slots given, the handle has %d", nslot, a->nslot);
   PS_HIP(hipSetDevice(a->device));
   // every descriptor first: an add with a bad slot enqueues nothing
-  std::vector<SensSlot> d((size_t)nslot);
+  std::vector<PsSrc> d((size_t)nslot);
   hipStream_t stream = nullptr;
-  for (int i = 0; i < nslot; ++i) {
-    PsRecordView v;
-    PS_TRY(ps_solver_record_internal(s, kind[i], idx[i], use_delta[i] != 0, &v));
-    if (v.device != a->device)
-      return ps_fail(PS_ERR_BAD_ARG, "sens_add: solver on device %d, handle on device %d", v.device, a->device);
-    if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "sens_add: solver domain %d, handle domain %d", v.N, a->N);
-    d[i] = SensSlot{v.rec, v.stats, stat_scale[i], post_scale[i], i};
-    stream = v.stream;
-  }
+  PS_TRY(ps_read_records("sens_add", "handle", a->device, a->N, s, nslot, kind, idx, stat_scale, post_scale, use_delta,
+                         false, d.data(), &stream));
   return sens_launch(a, d, stream, negval, e, weight);
 }
 
@@ -366,17 +359,10 @@ static int sens_add_fields(ps_sens* a, void* h, const PsFieldsOps& src, const ch
                            uint32_t weight) {
   if (!h) return ps_fail(PS_ERR_BAD_ARG, "%s: bad arguments", who);
   PS_TRY(sens_check_add(a, who, nparam, e, weight));
-  PsProjectView v;
-  PS_TRY(src.view(h, &v));
-  if (v.nout != a->nslot)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: the %s has %d outputs, the handle %d slots", who, src.what, v.nout, a->nslot);
-  if (v.device != a->device)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: %s on device %d, handle on device %d", who, src.what, v.device, a->device);
-  if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "%s: %s domain %d, handle domain %d", who, src.what, v.N, a->N);
-  PS_HIP(hipSetDevice(a->device));
   // slot k takes Y_k: no statistics, both scales 1 and negval 0, so the value rule returns Y itself
-  std::vector<SensSlot> d((size_t)a->nslot);
-  for (int k = 0; k < a->nslot; ++k) d[(size_t)k] = SensSlot{v.Y + (int64_t)k * v.pitch, nullptr, 1.0, 1.0, k};
+  std::vector<PsSrc> d((size_t)a->nslot);
+  PS_TRY(ps_read_fields(who, "handle", "slots", a->device, a->N, a->nslot, h, src, d.data()));
+  PS_HIP(hipSetDevice(a->device));
   PS_TRY(src.wait(h, a->stream));
   PS_TRY(sens_launch(a, d, a->stream, 0.0, e, weight));
   return src.mark(h, a->stream);   // the next apply overwrites Y only after this read

@@ -32,13 +32,8 @@
 
 namespace {
 
-struct SiteSlot {
-  const double* rec;           // nullptr: PS_REC_NONE, the group is not released yet on this output day
-  const ps_day_stats* stats;   // nullptr: no delta
-  double stat_scale, post_scale;
-};
-struct SiteSlots {
-  SiteSlot s[PS_SITES_MAX_OUT];
+struct SiteSlots {   // rec nullptr (PS_REC_NONE): the group is not released yet on this output day
+  PsSrc s[PS_SITES_MAX_OUT];
 };
 struct SiteTab {
   double amount[PS_SITES_MAX_SITE];
@@ -51,7 +46,7 @@ struct SiteTab {
 __global__ void __launch_bounds__(PS_SITES_THREADS) k_sites_apply(SiteSlots desc, SiteTab tab, int nsite, int first,
                                                                   double* __restrict__ Y, int N, int64_t ncell,
                                                                   int64_t pitch, double negval) {
-  const SiteSlot sd = desc.s[blockIdx.y];
+  const PsSrc sd = desc.s[blockIdx.y];
   if (!sd.rec && !first) return;   // nothing to add: Y stays as it is
   const int64_t npair = ncell >> 1;
   const int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -230,21 +225,9 @@ extern "C" int ps_sites_apply(ps_sites* p, ps_solver* s, int group, int nout, co
   SiteSlots desc;
   hipStream_t stream = nullptr;
   bool any = false;
-  for (int e = 0; e < nout; ++e) {
-    if (kind[e] == PS_REC_NONE) {
-      desc.s[e] = SiteSlot{nullptr, nullptr, 0.0, 0.0};
-      continue;
-    }
-    PsRecordView v;
-    PS_TRY(ps_solver_record_internal(s, kind[e], idx[e], use_delta[e] != 0, &v));
-    if (v.device != p->device)
-      return ps_fail(PS_ERR_BAD_ARG, "sites_apply: solver on device %d, handle on device %d", v.device, p->device);
-    if (v.N != p->N) return ps_fail(PS_ERR_BAD_ARG, "sites_apply: solver domain %d, handle domain %d", v.N, p->N);
-    desc.s[e] = SiteSlot{v.rec, v.stats, stat_scale[e], post_scale[e]};
-    stream = v.stream;
-    any = true;
-  }
-  for (int e = nout; e < PS_SITES_MAX_OUT; ++e) desc.s[e] = SiteSlot{nullptr, nullptr, 0.0, 0.0};
+  PS_TRY(ps_read_records("sites_apply", "handle", p->device, p->N, s, nout, kind, idx, stat_scale, post_scale,
+                         use_delta, true, desc.s, &stream, &any));
+  for (int e = nout; e < PS_SITES_MAX_OUT; ++e) desc.s[e] = PsSrc{nullptr, nullptr, 0.0, 0.0};
   if (!any)   // such a group belongs in no plan, and no record names the stream to run on
     return ps_fail(PS_ERR_BAD_ARG, "sites_apply: group %d is released on no output day (every slot is PS_REC_NONE)",
                    group);

@@ -167,7 +167,7 @@ extern "C" int ps_summary_create(int device, int N, int nslot, int nthr, const d
 }
 
 // one member from the slot descriptors d (one per slot of the summary), enqueued on `stream`
-static int sum_launch(ps_summary* a, const std::vector<SumSlot>& d, hipStream_t stream, double negval,
+static int sum_launch(ps_summary* a, const std::vector<PsSrc>& d, hipStream_t stream, double negval,
                       uint32_t weight) {
   const int nslot = a->nslot;
   PS_TRY(a->last.wait(stream));
@@ -182,7 +182,7 @@ static int sum_launch(ps_summary* a, const std::vector<SumSlot>& d, hipStream_t 
   for (int c0 = 0; c0 < nslot; c0 += PS_SUM_CHUNK) {
     const int n = std::min(PS_SUM_CHUNK, nslot - c0);
     SumSlots desc;
-    for (int i = 0; i < n; ++i) desc.s[i] = d[(size_t)(c0 + i)];
+    for (int i = 0; i < n; ++i) desc.s[i] = ps_slotted<SumSlot>(d[(size_t)(c0 + i)], c0 + i);
     hipLaunchKernelGGL(k_summary_add, dim3(bx, n), dim3(threads), 0, stream, desc, a->mean, a->m2, a->cnt, a->ncell,
                        a->pitch, a->nthr, thr, negval, (double)weight, Wn, weight);
     PS_HIP(hipGetLastError());
@@ -206,17 +206,10 @@ extern "C" int ps_summary_add(ps_summary* a, ps_solver* s, int nslot, const int3
                    (unsigned long long)(a->W + weight));
   PS_HIP(hipSetDevice(a->device));
   // every descriptor first: an add with a bad slot enqueues nothing
-  std::vector<SumSlot> d((size_t)nslot);
+  std::vector<PsSrc> d((size_t)nslot);
   hipStream_t stream = nullptr;
-  for (int i = 0; i < nslot; ++i) {
-    PsRecordView v;
-    PS_TRY(ps_solver_record_internal(s, kind[i], idx[i], use_delta[i] != 0, &v));
-    if (v.device != a->device)
-      return ps_fail(PS_ERR_BAD_ARG, "summary_add: solver on device %d, summary on device %d", v.device, a->device);
-    if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "summary_add: solver domain %d, summary domain %d", v.N, a->N);
-    d[i] = SumSlot{v.rec, v.stats, stat_scale[i], post_scale[i], i};
-    stream = v.stream;
-  }
+  PS_TRY(ps_read_records("summary_add", "summary", a->device, a->N, s, nslot, kind, idx, stat_scale, post_scale,
+                          use_delta, false, d.data(), &stream));
   return sum_launch(a, d, stream, negval, weight);
 }
 
@@ -227,17 +220,10 @@ static int sum_add_fields(ps_summary* a, void* h, const PsFieldsOps& src, const 
   if (a->W + weight > 0xffffffffull)
     return ps_fail(PS_ERR_BAD_ARG, "%s: total weight %llu would overflow the uint32 counts", who,
                    (unsigned long long)(a->W + weight));
-  PsProjectView v;
-  PS_TRY(src.view(h, &v));
-  if (v.nout != a->nslot)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: the %s has %d outputs, the summary %d slots", who, src.what, v.nout, a->nslot);
-  if (v.device != a->device)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: %s on device %d, summary on device %d", who, src.what, v.device, a->device);
-  if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "%s: %s domain %d, summary domain %d", who, src.what, v.N, a->N);
-  PS_HIP(hipSetDevice(a->device));
   // slot e takes Y_e: no statistics, both scales 1 and negval 0, so the value rule returns Y itself
-  std::vector<SumSlot> d((size_t)a->nslot);
-  for (int e = 0; e < a->nslot; ++e) d[(size_t)e] = SumSlot{v.Y + (int64_t)e * v.pitch, nullptr, 1.0, 1.0, e};
+  std::vector<PsSrc> d((size_t)a->nslot);
+  PS_TRY(ps_read_fields(who, "summary", "slots", a->device, a->N, a->nslot, h, src, d.data()));
+  PS_HIP(hipSetDevice(a->device));
   PS_TRY(src.wait(h, a->stream));
   PS_TRY(sum_launch(a, d, a->stream, 0.0, weight));
   return src.mark(h, a->stream);   // the next apply overwrites Y only after this read

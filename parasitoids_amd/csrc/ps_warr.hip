@@ -22,13 +22,8 @@
 
 namespace {
 
-struct WaSlot {
-  const double* rec;
-  const ps_day_stats* stats;   // nullptr: no delta
-  double stat_scale, post_scale;
-};
 struct WaSlots {
-  WaSlot s[PS_WARR_MAX_SLOT];
+  PsSrc s[PS_WARR_MAX_SLOT];
 };
 struct WaThr {
   double t[PS_WARR_MAX_THR];
@@ -72,7 +67,7 @@ __global__ void __launch_bounds__(PS_WARR_THREADS) k_warr_add(WaSlots desc, WaTh
     double2 rn = make_double2(0.0, 0.0);
     if (live && s + 1 < nslot) wa_load(desc.s[s + 1].rec, pair, i, rn);
     if (live) {
-      const WaSlot& sd = desc.s[s];
+      const PsSrc& sd = desc.s[s];
       const double delta = sdelta[s];
       const double v0 = ps_record_value(r.x, sd.stat_scale, sd.post_scale, delta, negval);
       const double v1 = pair ? ps_record_value(r.y, sd.stat_scale, sd.post_scale, delta, negval) : 0.0;
@@ -340,16 +335,9 @@ extern "C" int ps_warr_add(ps_warr* a, ps_solver* s, int nslot, const int32_t* k
   // every descriptor first: an add with a bad slot enqueues nothing
   WaSlots desc;
   hipStream_t stream = nullptr;
-  for (int i = 0; i < nslot; ++i) {
-    PsRecordView v;
-    PS_TRY(ps_solver_record_internal(s, kind[i], idx[i], use_delta[i] != 0, &v));
-    if (v.device != a->device)
-      return ps_fail(PS_ERR_BAD_ARG, "warr_add: solver on device %d, handle on device %d", v.device, a->device);
-    if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "warr_add: solver domain %d, handle domain %d", v.N, a->N);
-    desc.s[i] = WaSlot{v.rec, v.stats, stat_scale[i], post_scale[i]};
-    stream = v.stream;
-  }
-  for (int i = nslot; i < PS_WARR_MAX_SLOT; ++i) desc.s[i] = WaSlot{nullptr, nullptr, 0.0, 0.0};
+  PS_TRY(ps_read_records("warr_add", "handle", a->device, a->N, s, nslot, kind, idx, stat_scale, post_scale, use_delta,
+                         false, desc.s, &stream));
+  for (int i = nslot; i < PS_WARR_MAX_SLOT; ++i) desc.s[i] = PsSrc{nullptr, nullptr, 0.0, 0.0};
   return wa_launch(a, desc, stream, negval, rescale, omega);
 }
 
@@ -359,18 +347,11 @@ static int wa_add_fields(ps_warr* a, void* h, const PsFieldsOps& src, const char
                          const double* omega) {
   if (!h) return ps_fail(PS_ERR_BAD_ARG, "%s: bad arguments", who);
   PS_TRY(wa_check_add(a, who, nscen, rescale, omega));
-  PsProjectView v;
-  PS_TRY(src.view(h, &v));
-  if (v.nout != a->nslot)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: the %s has %d outputs, the handle %d slots", who, src.what, v.nout, a->nslot);
-  if (v.device != a->device)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: %s on device %d, handle on device %d", who, src.what, v.device, a->device);
-  if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "%s: %s domain %d, handle domain %d", who, src.what, v.N, a->N);
-  PS_HIP(hipSetDevice(a->device));
   // slot e takes Y_e: no statistics, both scales 1 and negval 0, so the value rule returns Y itself
   WaSlots desc;
-  for (int e = 0; e < PS_WARR_MAX_SLOT; ++e)
-    desc.s[e] = e < a->nslot ? WaSlot{v.Y + (int64_t)e * v.pitch, nullptr, 1.0, 1.0} : WaSlot{nullptr, nullptr, 0.0, 0.0};
+  PS_TRY(ps_read_fields(who, "handle", "slots", a->device, a->N, a->nslot, h, src, desc.s));
+  for (int e = a->nslot; e < PS_WARR_MAX_SLOT; ++e) desc.s[e] = PsSrc{nullptr, nullptr, 0.0, 0.0};
+  PS_HIP(hipSetDevice(a->device));
   PS_TRY(src.wait(h, a->stream));
   PS_TRY(wa_launch(a, desc, a->stream, 0.0, rescale, omega));
   return src.mark(h, a->stream);   // the next apply overwrites Y only after this read

@@ -331,7 +331,7 @@ static int wh_check_add(ps_whist* a, const char* who, int nscen, const double* r
 
 // one member from the slot descriptors d (one per slot of the handle), enqueued on `stream`: the rescale of the
 // scenarios with r != 1 first, where there is one, then the add
-static int wh_launch(ps_whist* a, const std::vector<WhSlot>& d, hipStream_t stream, double negval, const double* rescale,
+static int wh_launch(ps_whist* a, const std::vector<PsSrc>& d, hipStream_t stream, double negval, const double* rescale,
                      const double* omega) {
   WhScen sc;
   double Wn[PS_WHIST_MAX_SCEN] = {0, 0, 0, 0};
@@ -364,7 +364,10 @@ static int wh_launch(ps_whist* a, const std::vector<WhSlot>& d, hipStream_t stre
     hipEvent_t e1 = nullptr;
     PS_TRY(a->prof.begin(0, stream, &e1));
     WhSlots desc;
-    for (int i = 0; i < PS_WHIST_MAX_SLOT; ++i) desc.s[i] = d[(size_t)std::min(i, a->nslot - 1)];
+    for (int i = 0; i < PS_WHIST_MAX_SLOT; ++i) {   // the unused tail repeats the last slot
+      const int q = std::min(i, a->nslot - 1);
+      desc.s[i] = ps_slotted<WhSlot>(d[(size_t)q], q);
+    }
     const int64_t npair = a->ncell / 2 + 1;   // the pairs and the tail cell's thread
     const int bx = (int)((npair + threads - 1) / threads);
     hipLaunchKernelGGL(wh_add_kernels[a->nscen - 1], dim3(bx, a->nslot), dim3(threads), 0, stream, desc, a->d_edges,
@@ -393,17 +396,10 @@ extern "C" int ps_whist_add(ps_whist* a, ps_solver* s, int nslot, const int32_t*
   if (nslot != a->nslot) return ps_fail(PS_ERR_BAD_ARG, "whist_add: %d slots given, the handle has %d", nslot, a->nslot);
   PS_HIP(hipSetDevice(a->device));
   // every descriptor first: an add with a bad slot enqueues nothing
-  std::vector<WhSlot> d((size_t)nslot);
+  std::vector<PsSrc> d((size_t)nslot);
   hipStream_t stream = nullptr;
-  for (int i = 0; i < nslot; ++i) {
-    PsRecordView v;
-    PS_TRY(ps_solver_record_internal(s, kind[i], idx[i], use_delta[i] != 0, &v));
-    if (v.device != a->device)
-      return ps_fail(PS_ERR_BAD_ARG, "whist_add: solver on device %d, handle on device %d", v.device, a->device);
-    if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "whist_add: solver domain %d, handle domain %d", v.N, a->N);
-    d[i] = WhSlot{v.rec, v.stats, stat_scale[i], post_scale[i], i};
-    stream = v.stream;
-  }
+  PS_TRY(ps_read_records("whist_add", "handle", a->device, a->N, s, nslot, kind, idx, stat_scale, post_scale, use_delta,
+                         false, d.data(), &stream));
   return wh_launch(a, d, stream, negval, rescale, omega);
 }
 
@@ -412,17 +408,10 @@ static int wh_add_fields(ps_whist* a, void* h, const PsFieldsOps& src, const cha
                          const double* omega) {
   if (!h) return ps_fail(PS_ERR_BAD_ARG, "%s: bad arguments", who);
   PS_TRY(wh_check_add(a, who, nscen, rescale, omega));
-  PsProjectView v;
-  PS_TRY(src.view(h, &v));
-  if (v.nout != a->nslot)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: the %s has %d outputs, the handle %d slots", who, src.what, v.nout, a->nslot);
-  if (v.device != a->device)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: %s on device %d, handle on device %d", who, src.what, v.device, a->device);
-  if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "%s: %s domain %d, handle domain %d", who, src.what, v.N, a->N);
-  PS_HIP(hipSetDevice(a->device));
   // slot e takes Y_e: no statistics, both scales 1 and negval 0, so the value rule returns Y itself
-  std::vector<WhSlot> d((size_t)a->nslot);
-  for (int e = 0; e < a->nslot; ++e) d[(size_t)e] = WhSlot{v.Y + (int64_t)e * v.pitch, nullptr, 1.0, 1.0, e};
+  std::vector<PsSrc> d((size_t)a->nslot);
+  PS_TRY(ps_read_fields(who, "handle", "slots", a->device, a->N, a->nslot, h, src, d.data()));
+  PS_HIP(hipSetDevice(a->device));
   PS_TRY(src.wait(h, a->stream));
   PS_TRY(wh_launch(a, d, a->stream, 0.0, rescale, omega));
   return src.mark(h, a->stream);   // the next apply overwrites Y only after this read

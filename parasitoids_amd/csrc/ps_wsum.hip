@@ -265,7 +265,7 @@ static int ws_check_add(ps_wsum* a, const char* who, int nscen, const double* re
 }
 
 // one member from the slot descriptors d (one per slot of the handle), enqueued on `stream`
-static int ws_launch(ps_wsum* a, const std::vector<WsSlot>& d, hipStream_t stream, double negval, const double* rescale,
+static int ws_launch(ps_wsum* a, const std::vector<PsSrc>& d, hipStream_t stream, double negval, const double* rescale,
                      const double* omega) {
   WsScen sc;
   bool any = false;
@@ -290,7 +290,10 @@ static int ws_launch(ps_wsum* a, const std::vector<WsSlot>& d, hipStream_t strea
     WsThr thr;
     for (int k = 0; k < PS_WSUM_MAX_THR; ++k) thr.t[k] = a->thr[k];
     WsSlots desc;
-    for (int i = 0; i < PS_WSUM_MAX_SLOT; ++i) desc.s[i] = d[(size_t)std::min(i, a->nslot - 1)];
+    for (int i = 0; i < PS_WSUM_MAX_SLOT; ++i) {   // the unused tail repeats the last slot
+      const int q = std::min(i, a->nslot - 1);
+      desc.s[i] = ps_slotted<WsSlot>(d[(size_t)q], q);
+    }
     const int64_t npair = a->ncell / 2 + 1;
     const int threads = 256;
     const int bx = (int)std::min<int64_t>((npair + threads - 1) / threads, 4096);
@@ -320,17 +323,10 @@ extern "C" int ps_wsum_add(ps_wsum* a, ps_solver* s, int nslot, const int32_t* k
   if (nslot != a->nslot) return ps_fail(PS_ERR_BAD_ARG, "wsum_add: %d slots given, the handle has %d", nslot, a->nslot);
   PS_HIP(hipSetDevice(a->device));
   // every descriptor first: an add with a bad slot enqueues nothing
-  std::vector<WsSlot> d((size_t)nslot);
+  std::vector<PsSrc> d((size_t)nslot);
   hipStream_t stream = nullptr;
-  for (int i = 0; i < nslot; ++i) {
-    PsRecordView v;
-    PS_TRY(ps_solver_record_internal(s, kind[i], idx[i], use_delta[i] != 0, &v));
-    if (v.device != a->device)
-      return ps_fail(PS_ERR_BAD_ARG, "wsum_add: solver on device %d, handle on device %d", v.device, a->device);
-    if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "wsum_add: solver domain %d, handle domain %d", v.N, a->N);
-    d[i] = WsSlot{v.rec, v.stats, stat_scale[i], post_scale[i], i};
-    stream = v.stream;
-  }
+  PS_TRY(ps_read_records("wsum_add", "handle", a->device, a->N, s, nslot, kind, idx, stat_scale, post_scale, use_delta,
+                         false, d.data(), &stream));
   return ws_launch(a, d, stream, negval, rescale, omega);
 }
 
@@ -339,17 +335,10 @@ static int ws_add_fields(ps_wsum* a, void* h, const PsFieldsOps& src, const char
                          const double* omega) {
   if (!h) return ps_fail(PS_ERR_BAD_ARG, "%s: bad arguments", who);
   PS_TRY(ws_check_add(a, who, nscen, rescale, omega));
-  PsProjectView v;
-  PS_TRY(src.view(h, &v));
-  if (v.nout != a->nslot)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: the %s has %d outputs, the handle %d slots", who, src.what, v.nout, a->nslot);
-  if (v.device != a->device)
-    return ps_fail(PS_ERR_BAD_ARG, "%s: %s on device %d, handle on device %d", who, src.what, v.device, a->device);
-  if (v.N != a->N) return ps_fail(PS_ERR_BAD_ARG, "%s: %s domain %d, handle domain %d", who, src.what, v.N, a->N);
-  PS_HIP(hipSetDevice(a->device));
   // slot e takes Y_e: no statistics, both scales 1 and negval 0, so the value rule returns Y itself
-  std::vector<WsSlot> d((size_t)a->nslot);
-  for (int e = 0; e < a->nslot; ++e) d[(size_t)e] = WsSlot{v.Y + (int64_t)e * v.pitch, nullptr, 1.0, 1.0, e};
+  std::vector<PsSrc> d((size_t)a->nslot);
+  PS_TRY(ps_read_fields(who, "handle", "slots", a->device, a->N, a->nslot, h, src, d.data()));
+  PS_HIP(hipSetDevice(a->device));
   PS_TRY(src.wait(h, a->stream));
   PS_TRY(ws_launch(a, d, a->stream, 0.0, rescale, omega));
   return src.mark(h, a->stream);   // the next apply overwrites Y only after this read

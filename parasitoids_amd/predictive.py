@@ -97,13 +97,13 @@ import numpy as np
 from . import Bayes_funcs as BF
 from . import _lib as L
 from . import mcmc
-from ._handle import NEGVAL, _Accumulator, _Handle, _check_evaluated, _day_scales, _day_slots
+from ._handle import (MAX_PROJECT_IN, NEGVAL, _Accumulator, _FieldSource, _Handle, _check_evaluated, _day_scales,
+                      _day_slots, check_in_days)
 
 DEFAULT_BINS = (1e-8, 1e6, 16)   # NEGVAL .. above any r_number, 16 bins per decade: 225 edges
 MAX_EDGES = 1024
 MAX_ARRIVAL_SLOTS = 32     # ps_arrival: the day slots of one launch's descriptors
 MAX_ARRIVAL_THRESHOLDS = 4
-MAX_PROJECT_IN = 32        # ps_project: the input records of one launch's descriptors
 MAX_PROJECT_OUT = 32
 MAX_SITES = 32             # ps_sites: the sites of one plan, its release days (groups) and its outputs
 MAX_SITE_GROUPS = 8
@@ -2500,16 +2500,6 @@ def check_weights(weights, nin=None, zero_rows=False):
     return np.ascontiguousarray(W)
 
 
-def check_in_days(in_days):
-    '''a projection's input days as a list of ints: 1..32 model days >= 0, strictly increasing'''
-    d = [int(x) for x in in_days]
-    if not 1 <= len(d) <= MAX_PROJECT_IN:
-        raise ValueError('%d projection input days; 1..%d fit one launch' % (len(d), MAX_PROJECT_IN))
-    if d[0] < 0 or any(b <= a for a, b in zip(d, d[1:])):
-        raise ValueError('projection input days must be model days >= 0, strictly increasing: %r' % (d,))
-    return d
-
-
 def emergence_weights(collection_day, in_days, obs_days=None):
     '''[nout, len(in_days)] weights of the emergence projection of Bayes_funcs.popdensity_to_emergence, built
     from Bayes_funcs._projection_matrix: leaves collected on `collection_day` (days post release) carry the
@@ -2552,7 +2542,7 @@ def exposure_weights(in_days, upto):
     return (d[None, :] <= u[:, None]).astype(np.float64)
 
 
-class Projection(_Handle):
+class Projection(_FieldSource):
     '''Y_e(c) = sum_d weights[e][d] v_d(c) of `pop_model`'s last evaluation, on the device: v_d the value
     SpreadSummary adds for model day in_days[d] (strictly increasing, at most 32), weights [nout, nin] finite
     and >= 0 (check_weights), at most 32 outputs.  The sum runs in ascending d from +0.0 with the product and
@@ -2574,41 +2564,6 @@ class Projection(_Handle):
         W = np.ascontiguousarray(self.weights[self.live])
         self._create(len(self.in_days), len(self.live), L.p_f64(W))
         self._set_days(self.in_days)
-
-    def apply(self):
-        '''Project the last evaluation of the model (enqueued on the solver's stream; no host
-        synchronisation); the outputs of the previous apply are overwritten.'''
-        self._from_model('apply')
-
-    @property
-    def applies(self):
-        n = C.c_int64()
-        self._call('info', None, None, None, C.byref(n))
-        return n.value
-
-    def field(self, e):
-        '''[N, N] float64: output e of the last apply'''
-        e = self._e(e)
-        if e not in self._slot:
-            return np.zeros((self.N, self.N), dtype=np.float64)
-        out = np.empty((self.N, self.N), dtype=np.float64)
-        self._call('fetch', self._slot[e], L.p_f64(out))
-        return out
-
-    def gather(self, rows, cols):
-        '''[nout, n] float64: every output of the last apply at the cells (rows[k], cols[k])'''
-        rows, cols = L.i32(np.asarray(rows).ravel()), L.i32(np.asarray(cols).ravel())
-        if rows.size != cols.size:
-            raise ValueError('%d rows and %d columns' % (rows.size, cols.size))
-        got = np.zeros((len(self.live), rows.size), dtype=np.float64)
-        self._call('gather', rows.size, L.p_i32(rows), L.p_i32(cols), L.p_f64(got))
-        out = np.zeros((self.nout, rows.size), dtype=np.float64)
-        out[self.live] = got
-        return out
-
-    def profile(self, enable=None):
-        '''HIP-event time of the apply launches: (total ms, launches); enable switches it'''
-        return self._profile(enable)
 
 
 
@@ -3213,7 +3168,7 @@ def sites_plan(arg, pop_model=None):
     return sites, days, lags
 
 
-class ReleaseSites(_Handle):
+class ReleaseSites(_FieldSource):
     '''The field of a whole release plan, member by member, on the device: Y_e = sum over the sites of
     amount * (the field of that site's release on output day days[e], translated to the site).  sites:
     [(east_m, north_m, amount[, lag_days=0]), ...] (check_sites); days: output model days counted from the first
@@ -3225,7 +3180,7 @@ class ReleaseSites(_Handle):
     every bit.  Every output carries weight (`live`), so SpreadSummary.for_projection,
     SpreadHistogram.for_projection and ArrivalMaps.for_projection accept a plan.'''
     fields_kind = 'sites'        # the accumulators' entry points for these fields: ps_*_add_sites
-    _prefix = 'ps_sites'
+    _prefix, _info_n = 'ps_sites', 5
     _owned = ()                  # the lagged models with_lagged_models built: closed with the plan
 
     def __init__(self, pop_model, sites, days=None, lagged=None):
@@ -3299,32 +3254,6 @@ class ReleaseSites(_Handle):
             calls.append((m.solver._h, g, self.nout, L.p_i32(kind), L.p_i32(idx), L.p_f64(stat), L.p_f64(post),
                           L.p_i32(delta), NEGVAL))                 # the pointers keep their arrays alive
         return calls
-
-    @property
-    def applies(self):
-        '''complete passes over the plan's groups'''
-        n = C.c_int64()
-        self._call('info', None, None, None, None, C.byref(n))
-        return n.value
-
-    def field(self, e):
-        '''[N, N] float64: output e (model day days[e]) of the last apply'''
-        out = np.empty((self.N, self.N), dtype=np.float64)
-        self._call('fetch', self._e(e), L.p_f64(out))
-        return out
-
-    def gather(self, rows, cols):
-        '''[nout, n] float64: every output of the last apply at the cells (rows[k], cols[k])'''
-        rows, cols = L.i32(np.asarray(rows).ravel()), L.i32(np.asarray(cols).ravel())
-        if rows.size != cols.size:
-            raise ValueError('%d rows and %d columns' % (rows.size, cols.size))
-        out = np.zeros((self.nout, rows.size), dtype=np.float64)
-        self._call('gather', rows.size, L.p_i32(rows), L.p_i32(cols), L.p_f64(out))
-        return out
-
-    def profile(self, enable=None):
-        '''HIP-event time of the apply launches, one per group: (total ms, launches); enable switches it'''
-        return self._profile(enable)
 
     def describe(self):
         '''the plan for a result file: sites in metres and cells, release days, output days'''
@@ -5864,7 +5793,7 @@ def required_rate(traps, means, day, n, level):
     return out
 
 
-class CatchFields(_Handle):
+class CatchFields(_FieldSource):
     '''Y_e(c) = P(Poisson(rate_e v(c)) >= n_e) of `pop_model`'s last evaluation, on the device (ps_catch_*,
     csrc/ps_catch.hip): what a trap of effort rate_e on model day day_e would find at every cell, under the
     package's own observation model (mcmc.loglik_parts).  traps: [(day, rate[, n=1]), ...] (check_traps), v the
@@ -5876,19 +5805,10 @@ class CatchFields(_Handle):
     ReweightedSummary.for_projection accept it.'''
     fields_kind = 'catch'        # the accumulators' entry points for these fields: ps_*_add_catch
     _prefix, _noun = 'ps_catch', 'catch fields'
+    _items, _item, _check, _max_in = 'traps', 'trap', staticmethod(check_traps), MAX_CATCH_IN
 
     def __init__(self, pop_model, traps, days=None):
-        self.traps = check_traps(traps)
-        used = sorted({t[0] for t in self.traps})
-        self.in_days = used if days is None else check_in_days(days)
-        if len(self.in_days) > MAX_CATCH_IN:
-            raise ValueError('%d input days; at most %d fit one handle' % (len(self.in_days), MAX_CATCH_IN))
-        missing = [d for d in used if d not in self.in_days]
-        if missing:
-            raise ValueError('trap days %r are not among the days %r' % (missing, self.in_days))
-        self._source = None
-        self._setup(pop_model, [self.in_days.index(t[0]) for t in self.traps], len(self.in_days))
-        self._set_days(self.in_days)
+        self._from_days(pop_model, traps, days)
 
     @classmethod
     def for_projection(cls, source, traps, labels=None):
@@ -5896,23 +5816,7 @@ class CatchFields(_Handle):
         the source's output label (labels: one per output, default a ReleaseSites' output days, else the output
         indices); `apply()` reads the outputs of the source's last apply.  An output without weight is
         refused.'''
-        self = cls.__new__(cls)
-        self.traps = check_traps(traps, 'output')
-        if labels is None:
-            labels = getattr(source, 'days', None) if source.fields_kind == 'sites' else None
-        labels = list(range(source.nout)) if labels is None else [int(x) for x in labels]
-        if len(labels) != source.nout:
-            raise ValueError('%d labels for %d outputs' % (len(labels), source.nout))
-        slot = {e: i for i, e in enumerate(source.live)}        # the source's device slot of every output
-        inputs = []
-        for t in self.traps:
-            if t[0] not in labels or labels.index(t[0]) not in slot:
-                raise ValueError('trap %r: %d is not an output that carries weight (%r)' % (t, t[0], labels))
-            inputs.append(slot[labels.index(t[0])])
-        self.in_days = None
-        self._source = source
-        self._setup(source.pm, inputs, len(source.live))
-        return self
+        return cls._over(source, traps, labels)
 
     def _setup(self, pop_model, inputs, nin):
         self._attach(pop_model)
@@ -5923,37 +5827,6 @@ class CatchFields(_Handle):
         self.nbytes = self.nout * self.pitch * 8                 # the output fields
         self._create(int(nin), self.nout, L.p_i32(L.i32(inputs)), L.p_f64(L.f64(self.rates)),
                      L.p_i32(L.i32(self.counts)))
-
-    def apply(self):
-        '''The catch fields of the last evaluation of the model (enqueued on the solver's stream), or of the
-        source's last apply (on the handle's stream); no host synchronisation; the outputs of the previous apply
-        are overwritten.'''
-        self._read('apply', self._source)
-
-    @property
-    def applies(self):
-        n = C.c_int64()
-        self._call('info', None, None, None, C.byref(n))
-        return n.value
-
-    def field(self, e):
-        '''[N, N] float64: output e of the last apply'''
-        out = np.empty((self.N, self.N), dtype=np.float64)
-        self._call('fetch', self._e(e), L.p_f64(out))
-        return out
-
-    def gather(self, rows, cols):
-        '''[nout, n] float64: every output of the last apply at the cells (rows[k], cols[k])'''
-        rows, cols = L.i32(np.asarray(rows).ravel()), L.i32(np.asarray(cols).ravel())
-        if rows.size != cols.size:
-            raise ValueError('%d rows and %d columns' % (rows.size, cols.size))
-        out = np.zeros((self.nout, rows.size), dtype=np.float64)
-        self._call('gather', rows.size, L.p_i32(rows), L.p_i32(cols), L.p_f64(out))
-        return out
-
-    def profile(self, enable=None):
-        '''HIP-event time of the apply launches: (total ms, launches); enable switches it'''
-        return self._profile(enable)
 
 
 
@@ -6145,7 +6018,7 @@ def check_neighbourhood(neighbourhood, ndays=None, cell_m=None, evaluate=None):
     return {'windows': windows, 'given': [list(t) for t in windows]}
 
 
-class NeighbourhoodFields(_Handle):
+class NeighbourhoodFields(_FieldSource):
     '''Z_e(y, x) = max of v over the cells of the domain within radius_e of (y, x), of `pop_model`'s last
     evaluation, on the device (ps_nbhd_*, csrc/ps_nbhd.hip): per member the largest density a search within
     radius_e metres of the cell would meet on model day day_e.  windows: [(day, radius_m), ...] (check_windows),
@@ -6159,19 +6032,10 @@ class NeighbourhoodFields(_Handle):
     MonteCarloError.for_projection and ReweightedSummary.for_projection accept it.'''
     fields_kind = 'nbhd'         # the accumulators' entry points for these fields: ps_*_add_nbhd
     _prefix, _noun = 'ps_nbhd', 'neighbourhood fields'
+    _items, _item, _check, _max_in = 'windows', 'window', staticmethod(check_windows), MAX_NBHD_IN
 
     def __init__(self, pop_model, windows, days=None):
-        self.windows = check_windows(windows)
-        used = sorted({t[0] for t in self.windows})
-        self.in_days = used if days is None else check_in_days(days)
-        if len(self.in_days) > MAX_NBHD_IN:
-            raise ValueError('%d input days; at most %d fit one handle' % (len(self.in_days), MAX_NBHD_IN))
-        missing = [d for d in used if d not in self.in_days]
-        if missing:
-            raise ValueError('window days %r are not among the days %r' % (missing, self.in_days))
-        self._source = None
-        self._setup(pop_model, [self.in_days.index(t[0]) for t in self.windows], len(self.in_days))
-        self._set_days(self.in_days)
+        self._from_days(pop_model, windows, days)
 
     @classmethod
     def for_projection(cls, source, windows, labels=None):
@@ -6179,23 +6043,7 @@ class NeighbourhoodFields(_Handle):
         entry is the source's output label (labels: one per output, default a ReleaseSites' output days, else the
         output indices); `apply()` reads the outputs of the source's last apply.  An output without weight is
         refused.'''
-        self = cls.__new__(cls)
-        self.windows = check_windows(windows, 'output')
-        if labels is None:
-            labels = getattr(source, 'days', None) if source.fields_kind == 'sites' else None
-        labels = list(range(source.nout)) if labels is None else [int(x) for x in labels]
-        if len(labels) != source.nout:
-            raise ValueError('%d labels for %d outputs' % (len(labels), source.nout))
-        slot = {e: i for i, e in enumerate(source.live)}        # the source's device slot of every output
-        inputs = []
-        for t in self.windows:
-            if t[0] not in labels or labels.index(t[0]) not in slot:
-                raise ValueError('window %r: %d is not an output that carries weight (%r)' % (t, t[0], labels))
-            inputs.append(slot[labels.index(t[0])])
-        self.in_days = None
-        self._source = source
-        self._setup(source.pm, inputs, len(source.live))
-        return self
+        return cls._over(source, windows, labels)
 
     def _setup(self, pop_model, inputs, nin):
         self._attach(pop_model)
@@ -6214,33 +6062,6 @@ class NeighbourhoodFields(_Handle):
     def set_skip(self, on=True):
         '''the empty-tile pre-pass of the next applies: on (the default) or off; the outputs are the same'''
         self._call('set_skip', int(bool(on)))
-
-    def apply(self):
-        '''The neighbourhood fields of the last evaluation of the model (enqueued on the solver's stream), or of
-        the source's last apply (on the handle's stream); no host synchronisation; the outputs of the previous
-        apply are overwritten.'''
-        self._read('apply', self._source)
-
-    @property
-    def applies(self):
-        n = C.c_int64()
-        self._call('info', None, None, None, C.byref(n))
-        return n.value
-
-    def field(self, e):
-        '''[N, N] float64: output e of the last apply'''
-        out = np.empty((self.N, self.N), dtype=np.float64)
-        self._call('fetch', self._e(e), L.p_f64(out))
-        return out
-
-    def gather(self, rows, cols):
-        '''[nout, n] float64: every output of the last apply at the cells (rows[k], cols[k])'''
-        rows, cols = L.i32(np.asarray(rows).ravel()), L.i32(np.asarray(cols).ravel())
-        if rows.size != cols.size:
-            raise ValueError('%d rows and %d columns' % (rows.size, cols.size))
-        out = np.zeros((self.nout, rows.size), dtype=np.float64)
-        self._call('gather', rows.size, L.p_i32(rows), L.p_i32(cols), L.p_f64(out))
-        return out
 
     def profile(self, enable=None):
         '''HIP-event time of the applies, pre-pass included: (total ms, applies); enable switches it'''
@@ -6476,7 +6297,7 @@ def check_proximity(proximity, ndays=None, cell_m=None, evaluate=None):
             'given': {'windows': [list(t) for t in windows], 'radii_m': radii, 'levels': levels, 'ladder': ladder}}
 
 
-class ProximityFields(_Handle):
+class ProximityFields(_FieldSource):
     '''Z_e(y, x) = the distance in metres from (y, x) to the nearest cell of the set S_e = {v >= t_e} of
     `pop_model`'s last evaluation, on the device (ps_prox_*, csrc/ps_prox.hip): per member how far from each cell
     the nearest ground lies that holds at least t_e on model day day_e.  windows: [(day, t[, 'to' | 'in']), ...]
@@ -6492,42 +6313,17 @@ class ProximityFields(_Handle):
     ReweightedSummary.for_projection accept it.'''
     fields_kind = 'prox'         # the accumulators' entry points for these fields: ps_*_add_prox
     _prefix, _noun, _prof_pairs = 'ps_prox', 'proximity fields', 2
+    _items, _item, _check, _max_in = 'windows', 'window', staticmethod(check_prox_windows), MAX_PROX_IN
 
     def __init__(self, pop_model, windows, days=None):
-        self.windows = check_prox_windows(windows)
-        used = sorted({t[0] for t in self.windows})
-        self.in_days = used if days is None else check_in_days(days)
-        if len(self.in_days) > MAX_PROX_IN:
-            raise ValueError('%d input days; at most %d fit one handle' % (len(self.in_days), MAX_PROX_IN))
-        missing = [d for d in used if d not in self.in_days]
-        if missing:
-            raise ValueError('window days %r are not among the days %r' % (missing, self.in_days))
-        self._source = None
-        self._setup(pop_model, [self.in_days.index(t[0]) for t in self.windows], len(self.in_days))
-        self._set_days(self.in_days)
+        self._from_days(pop_model, windows, days)
 
     @classmethod
     def for_projection(cls, source, windows, labels=None):
         '''The proximity fields of the outputs of `source` (a Projection or a ReleaseSites): a window's first entry
         is the source's output label (labels: one per output, default a ReleaseSites' output days, else the output
         indices); `apply()` reads the outputs of the source's last apply.  An output without weight is refused.'''
-        self = cls.__new__(cls)
-        self.windows = check_prox_windows(windows, 'output')
-        if labels is None:
-            labels = getattr(source, 'days', None) if source.fields_kind == 'sites' else None
-        labels = list(range(source.nout)) if labels is None else [int(x) for x in labels]
-        if len(labels) != source.nout:
-            raise ValueError('%d labels for %d outputs' % (len(labels), source.nout))
-        slot = {e: i for i, e in enumerate(source.live)}        # the source's device slot of every output
-        inputs = []
-        for t in self.windows:
-            if t[0] not in labels or labels.index(t[0]) not in slot:
-                raise ValueError('window %r: %d is not an output that carries weight (%r)' % (t, t[0], labels))
-            inputs.append(slot[labels.index(t[0])])
-        self.in_days = None
-        self._source = source
-        self._setup(source.pm, inputs, len(source.live))
-        return self
+        return cls._over(source, windows, labels)
 
     def _setup(self, pop_model, inputs, nin):
         self._attach(pop_model)
@@ -6546,12 +6342,6 @@ class ProximityFields(_Handle):
         the default; the outputs are the same'''
         self._call('set_strip', int(width))
 
-    def apply(self):
-        '''The proximity fields of the last evaluation of the model (enqueued on the solver's stream), or of the
-        source's last apply (on the handle's stream); no host synchronisation; the outputs of the previous apply
-        are overwritten.'''
-        self._read('apply', self._source)
-
     def _counter(self, k):
         out = [C.c_int(), C.c_int(), C.c_int(), C.c_int64(), C.c_int()]
         self._call('info', *[C.byref(v) for v in out])
@@ -6566,25 +6356,10 @@ class ProximityFields(_Handle):
         '''the columns of one workgroup's strip in the column pass'''
         return self._counter(4)
 
-    def field(self, e):
-        '''[N, N] float64: output e of the last apply, in metres'''
-        out = np.empty((self.N, self.N), dtype=np.float64)
-        self._call('fetch', self._e(e), L.p_f64(out))
-        return out
-
     def d2(self, e):
         '''[N, N] uint32: the squared distance of output e in cells, far2 where the set searched for is empty'''
         out = np.empty((self.N, self.N), dtype=np.uint32)
         self._call('fetch_d2', self._e(e), out.ctypes.data_as(C.POINTER(C.c_uint32)))
-        return out
-
-    def gather(self, rows, cols):
-        '''[nout, n] float64: every output of the last apply at the cells (rows[k], cols[k]), in metres'''
-        rows, cols = L.i32(np.asarray(rows).ravel()), L.i32(np.asarray(cols).ravel())
-        if rows.size != cols.size:
-            raise ValueError('%d rows and %d columns' % (rows.size, cols.size))
-        out = np.zeros((self.nout, rows.size), dtype=np.float64)
-        self._call('gather', rows.size, L.p_i32(rows), L.p_i32(cols), L.p_f64(out))
         return out
 
     def profile(self, enable=None):
@@ -6813,7 +6588,7 @@ def weight_entropy(weights):
     return float(-(q * np.log(q)).sum())
 
 
-class InformationFields(_Handle):
+class InformationFields(_FieldSource):
     '''One member's whole count distribution at every cell for traps the user describes, on the device
     (ps_gain_*, csrc/ps_gain.hip): trap e = (day, rate[, ymax=0]) observes Poisson(rate v) as the classes 0, 1,
     .., ymax and ">= ymax + 1" (ymax = 0: found / none), v the value SpreadSummary adds for that day, under the
@@ -6825,20 +6600,11 @@ class InformationFields(_Handle):
     ReweightedSummary.for_projection accept it, one slot per plane; InformationPosterior turns their means into
     the information maps.'''
     fields_kind = 'gain'         # the accumulators' entry points for these fields: ps_*_add_gain
-    _prefix, _noun = 'ps_gain', 'information fields'
+    _prefix, _noun, _info_n = 'ps_gain', 'information fields', 5
+    _items, _item, _check, _max_in = 'traps', 'trap', staticmethod(check_info_traps), MAX_GAIN_IN
 
     def __init__(self, pop_model, traps, days=None):
-        self.traps = check_info_traps(traps)
-        used = sorted({t[0] for t in self.traps})
-        self.in_days = used if days is None else check_in_days(days)
-        if len(self.in_days) > MAX_GAIN_IN:
-            raise ValueError('%d input days; at most %d fit one handle' % (len(self.in_days), MAX_GAIN_IN))
-        missing = [d for d in used if d not in self.in_days]
-        if missing:
-            raise ValueError('trap days %r are not among the days %r' % (missing, self.in_days))
-        self._source = None
-        self._setup(pop_model, [self.in_days.index(t[0]) for t in self.traps], len(self.in_days))
-        self._set_days(self.in_days)
+        self._from_days(pop_model, traps, days)
 
     @classmethod
     def for_projection(cls, source, traps, labels=None):
@@ -6846,23 +6612,7 @@ class InformationFields(_Handle):
         entry is the source's output label (labels: one per output, default a ReleaseSites' output days, else the
         output indices); `apply()` reads the outputs of the source's last apply.  An output without weight is
         refused.'''
-        self = cls.__new__(cls)
-        self.traps = check_info_traps(traps, 'output')
-        if labels is None:
-            labels = getattr(source, 'days', None) if source.fields_kind == 'sites' else None
-        labels = list(range(source.nout)) if labels is None else [int(x) for x in labels]
-        if len(labels) != source.nout:
-            raise ValueError('%d labels for %d outputs' % (len(labels), source.nout))
-        slot = {e: i for i, e in enumerate(source.live)}        # the source's device slot of every output
-        inputs = []
-        for t in self.traps:
-            if t[0] not in labels or labels.index(t[0]) not in slot:
-                raise ValueError('trap %r: %d is not an output that carries weight (%r)' % (t, t[0], labels))
-            inputs.append(slot[labels.index(t[0])])
-        self.in_days = None
-        self._source = source
-        self._setup(source.pm, inputs, len(source.live))
-        return self
+        return cls._over(source, traps, labels)
 
     def _setup(self, pop_model, inputs, nin):
         self._attach(pop_model)
@@ -6876,17 +6626,7 @@ class InformationFields(_Handle):
         self._create(int(nin), self.ntrap, L.p_i32(L.i32(inputs)), L.p_f64(L.f64(self.rates)),
                      L.p_i32(L.i32(self.ymax)))
 
-    def apply(self):
-        '''The planes of the last evaluation of the model (enqueued on the solver's stream), or of the source's
-        last apply (on the handle's stream); no host synchronisation; the planes of the previous apply are
-        overwritten.'''
-        self._read('apply', self._source)
-
-    @property
-    def applies(self):
-        n = C.c_int64()
-        self._call('info', None, None, None, None, C.byref(n))
-        return n.value
+    field = property()     # none: a trap's planes go by name (`plane`), and `_e` is a trap's index
 
     def _e(self, e):
         return self._index(e, self.ntrap, 'trap')
@@ -6908,15 +6648,6 @@ class InformationFields(_Handle):
         self._call('fetch', self.plane_index(e, name), L.p_f64(out))
         return out
 
-    def gather(self, rows, cols):
-        '''[planes, n] float64: every plane of the last apply at the cells (rows[k], cols[k])'''
-        rows, cols = L.i32(np.asarray(rows).ravel()), L.i32(np.asarray(cols).ravel())
-        if rows.size != cols.size:
-            raise ValueError('%d rows and %d columns' % (rows.size, cols.size))
-        out = np.zeros((self.nout, rows.size), dtype=np.float64)
-        self._call('gather', rows.size, L.p_i32(rows), L.p_i32(cols), L.p_f64(out))
-        return out
-
     def finish(self, accumulator, scenario=None):
         '''the information maps of every trap from the mean planes of `accumulator`, a
         SpreadSummary.for_projection(self) or, with the scenario's name, a ReweightedSummary.for_projection(self);
@@ -6935,10 +6666,6 @@ class InformationFields(_Handle):
         out = np.empty((self.N, self.N), dtype=np.float64)
         self._call('fetch_result', self._e(e), names.index(what), L.p_f64(out))
         return out
-
-    def profile(self, enable=None):
-        '''HIP-event time of the apply launches: (total ms, launches); enable switches it'''
-        return self._profile(enable)
 
 
 

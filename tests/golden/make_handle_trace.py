@@ -1,5 +1,5 @@
-"""Records tests/golden/handle_calls_trace.json: what the fifteen classes that own one handle of the C library
-(fourteen in parasitoids_amd.predictive, laplace.LinearisedSpread) send to the library, what they return and what
+"""Records tests/golden/handle_calls_trace.json: what the seventeen classes that own one handle of the C library
+(sixteen in parasitoids_amd.predictive, laplace.LinearisedSpread) send to the library, what they return and what
 they refuse, with no device and no library.  `_lib._lib` holds a recording stand-in while `record()` runs: every
 ps_* symbol of `_lib.SIGNATURES` returns 0 and appends (symbol, arguments), the arguments decoded with the
 signature -- scalars by value, handles as small integers, pointers as 'null' or 'set', numpy arrays handed to a
@@ -8,8 +8,8 @@ its out-pointer, an info or prof writes fixed numbers, every other output array 
 
     python tests/golden/make_handle_trace.py        # rewrites the fixture
 
-The fixture was recorded at the commit before the classes got their shared base; tests/test_handles_cpu.py
-re-records and compares.  The module only uses names that exist at both commits.  Where an add is given both a
+The fixture was recorded at the commit before the classes got their shared base, NeighbourhoodFields and
+ProximityFields at the commit before the field sources got theirs; tests/test_handles_cpu.py re-records and compares.  The module only uses names that exist at both commits.  Where an add is given both a
 weight below 1 and a model that is not evaluated far enough, the classes used to differ in which ValueError
 came; no case here does both."""
 import contextlib
@@ -317,6 +317,25 @@ def specs():
                 ('result', lambda o: o.result(0, 'entropy')), ('shape', lambda o: [o.ntrap, o.ymax, o.base])],
         refuse=[('trap', lambda o: o.result(2, 'gain')), ('plane', lambda o: o.plane(0, 'p9')),
                 ('what', lambda o: o.result(0, 'loss'))], merges=False, resets=False, weighs=False)
+    S['NeighbourhoodFields'] = dict(
+        make=lambda pm, src: PP.NeighbourhoodFields(pm, [(1, 4.0), (4, 0.0)]) if src is None else
+        PP.NeighbourhoodFields.for_projection(src, [(0, 4.0), (2, 9.0)]),
+        over=(None, 'project', 'sites'), use=lambda o: o.apply(), zero=None,
+        access=[('applies', lambda o: o.applies), ('field', lambda o: o.field(1)),
+                ('gather', lambda o: o.gather([0, 1], [2, 3])), ('set_skip', lambda o: o.set_skip(False)),
+                ('discs', lambda o: [o.radii_m, o.r2, o.half, o.cells])],
+        refuse=[('output', lambda o: o.field(2)), ('gather', lambda o: o.gather([0, 1], [2]))],
+        merges=False, resets=False, weighs=False)
+    S['ProximityFields'] = dict(
+        make=lambda pm, src: PP.ProximityFields(pm, [(1, 0.5), (4, 0.25, 'in')]) if src is None else
+        PP.ProximityFields.for_projection(src, [(0, 0.5, 'in'), (2, 1.0)]),
+        over=(None, 'project', 'sites'), use=lambda o: o.apply(), zero=None,
+        access=[('applies', lambda o: o.applies), ('strip', lambda o: o.strip), ('field', lambda o: o.field(1)),
+                ('d2', lambda o: o.d2(0)), ('gather', lambda o: o.gather([0, 1], [2, 3])),
+                ('set_strip', lambda o: o.set_strip(8)),
+                ('sets', lambda o: [o.thresholds, o.sides, o.cell_m, o.far2, o.far_m])],
+        refuse=[('output', lambda o: o.d2(2)), ('gather', lambda o: o.gather([0, 1], [2]))],
+        merges=False, resets=False, weighs=False)
     S['LinearisedSpread'] = dict(
         make=lambda pm, src: LA.LinearisedSpread(pm, [0, 2, 5], 2, [0.5], ['sig_x', 'lam']), over=(None,),
         use=lambda o: (o.set_center(), o.add(1, 0.25)), zero=None,

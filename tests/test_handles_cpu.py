@@ -1,11 +1,11 @@
-"""CPU tests of the fifteen classes that own one handle of the C library (fourteen in parasitoids_amd.predictive and
+"""CPU tests of the seventeen classes that own one handle of the C library (sixteen in parasitoids_amd.predictive and
 laplace.LinearisedSpread): what each sends to the library, what it returns and what it refuses on the host.  No
 device and no library: tests/golden/make_handle_trace.py puts a recording stand-in in `_lib._lib` and walks every
 class through its life -- construction from the model and through every for_projection it has, one add or apply on
 each path, merge, reset, the counters, profile, one accessor per fetch symbol, close twice, the `with` form, a create
 the library refuses, and the refusals that never reach the library.  The expected trace
-(tests/golden/handle_calls_trace.json) was recorded before the classes got their shared base (_handle._Handle), so
-every symbol, argument, returned value, exception type and text here is the one the copied classes gave."""
+(tests/golden/handle_calls_trace.json) was recorded before the classes got their shared base (_handle._Handle), and
+NeighbourhoodFields and ProximityFields before the field sources got theirs (_handle._FieldSource), so every symbol, argument, returned value, exception type and text here is the one the copied classes gave."""
 import importlib.util
 import json
 import os
@@ -43,8 +43,10 @@ def _scenarios():
 def test_fixture_covers_every_class_and_source(traces):
     got, want = traces
     assert list(got) == list(want) == _scenarios()
-    assert len(REC.specs()) == 15
-    assert os.path.getsize(REC.FIXTURE) < os.path.getsize(os.path.join(GOLDEN, 'predictive_driver_trace.json'))
+    assert len(REC.specs()) == 17
+    # per class no larger than the driver's trace allowed the first fifteen
+    driver = os.path.getsize(os.path.join(GOLDEN, 'predictive_driver_trace.json'))
+    assert os.path.getsize(REC.FIXTURE) * 15 < driver * len(REC.specs())
 
 
 @pytest.mark.parametrize('scenario', _scenarios())

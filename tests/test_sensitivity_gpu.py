@@ -569,11 +569,15 @@ def test_c_abi_refusals():
             refused(lib.ps_sens_add_project(H._h, P3._h, 3, L.p_f64(e), 1), L.PS_ERR_STATE)
             P2.apply()
             P3.apply()
-            refused(lib.ps_sens_add_project(H._h, P2._h, 3, L.p_f64(e), 1), L.PS_ERR_BAD_ARG, b'2 outputs', b'3 slots')
+            refused(lib.ps_sens_add_project(H._h, P2._h, 3, L.p_f64(e), 1), L.PS_ERR_BAD_ARG,
+                    b'sens_add_project: the projection has 2 outputs, the handle 3 slots')
+            assert lib.ps_last_error() == b'sens_add_project: the projection has 2 outputs, the handle 3 slots'
             refused(lib.ps_sens_add_project(H._h, P3._h, 2, L.p_f64(e), 1), L.PS_ERR_BAD_ARG, b'sens_add_project',
                     b'2 parameters given')
             refused(lib.ps_sens_add_project(H._h, P3._h, 3, L.p_f64(e), 0), L.PS_ERR_BAD_ARG, b'weight must be >= 1')
-            refused(lib.ps_sens_add_project(Ho._h, P3._h, 3, L.p_f64(e), 1), L.PS_ERR_BAD_ARG, b'domain 257', b'domain 129')
+            refused(lib.ps_sens_add_project(Ho._h, P3._h, 3, L.p_f64(e), 1), L.PS_ERR_BAD_ARG,
+                    b'sens_add_project: projection domain 257, handle domain 129')
+            assert lib.ps_last_error() == b'sens_add_project: projection domain 257, handle domain 129'
             assert lib.ps_sens_add_project(H._h, P3._h, 3, L.p_f64(e), 1) == L.PS_OK and H.members == 2
         # the wrapper: a theta of the wrong length, a model that has not run far enough, names
         with pytest.raises(ValueError, match='theta has 3 entries'):

@@ -506,7 +506,8 @@ def test_posterior_predictive_with_a_release_plan(tmp_path, monkeypatch):
 
 def test_refusals_at_the_c_abi_and_the_handles_stay_usable():
     from parasitoids_amd import _lib as L
-    from parasitoids_amd.predictive import NEGVAL, ArrivalMaps, ReleaseSites, SpreadHistogram, SpreadSummary
+    from parasitoids_amd.predictive import (NEGVAL, ArrivalMaps, CatchFields, ReleaseSites, SpreadHistogram,
+                                            SpreadSummary, _day_scales)
     lib = L.load()
     dev = L.default_device()
     h = L._VP()
@@ -539,7 +540,8 @@ def test_refusals_at_the_c_abi_and_the_handles_stay_usable():
     with ReleaseSites(pm, _metres(cells, 64), [0, 2, 5]) as P, ReleaseSites(big, _metres(cells, 128), [0, 2, 5]) as P128, \
             SpreadSummary.for_projection(P, THR) as S, SpreadHistogram.for_projection(P) as H, \
             ArrivalMaps.for_projection(P, THR) as A, SpreadSummary(pm, [0, 1]) as S2, \
-            SpreadHistogram(pm, [0, 1]) as H2, ArrivalMaps(pm, THR, [0, 1]) as A2:
+            SpreadHistogram(pm, [0, 1]) as H2, ArrivalMaps(pm, THR, [0, 1]) as A2, \
+            CatchFields(pm, [(0, 1.0), (1, 1.0)]) as CF:
         _evaluate(pm, MEMBERS[0])
         _evaluate(big, MEMBERS[0])
         P.profile(True)
@@ -547,7 +549,18 @@ def test_refusals_at_the_c_abi_and_the_handles_stay_usable():
         wrong = list(call)
         wrong[0] = big.solver._h
         assert lib.ps_sites_apply(P._h, *wrong) == L.PS_ERR_BAD_ARG               # a solver of another domain
-        assert b'solver domain 257, handle domain 129' in lib.ps_last_error()
+        assert lib.ps_last_error() == b'sites_apply: solver domain 257, handle domain 129'
+        # the same refusal, word for word, of an add and of an apply over the day records of that solver
+        stat, post = _day_scales(big, [0, 1])
+
+        def records(h):
+            return (h._h, big.solver._h, 2, L.p_i32(h._kind), L.p_i32(h._idx), L.p_f64(stat), L.p_f64(post),
+                    L.p_i32(h._delta), NEGVAL)
+        assert lib.ps_summary_add(*records(S2), 1) == L.PS_ERR_BAD_ARG
+        assert lib.ps_last_error() == b'summary_add: solver domain 257, summary domain 129'
+        assert lib.ps_catch_apply(*records(CF)) == L.PS_ERR_BAD_ARG
+        assert lib.ps_last_error() == b'catch_apply: solver domain 257, handle domain 129'
+        assert CF.applies == 0
         wrong = list(call)
         wrong[2] = 2
         assert lib.ps_sites_apply(P._h, *wrong) == L.PS_ERR_BAD_ARG               # two slots for three outputs
